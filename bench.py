@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: autoregressive audio samples/sec on BASELINE config 2.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,6 +16,15 @@ Multi-GPU = independent clips per rank (weak scaling), no data-path collective.
 
 `python bench.py --gpus N` with N > 1 and no torchrun environment starts the N ranks itself
 (one child process per device, spawned BEFORE anything touches the GPU) and relays rank 0's line.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs of
+the last step when --dump-outputs is given, the line.  --full adds the secondary figures after the
+timed steps: the train legs, Trainer.fit, the extras (temperature 1.0, end-to-end generate, batch
+sweep, configs 3 and 5) and the CPU baselines (each still switched off by its --no-* option).
+
+--dump-outputs DIR writes what the timed path returned in its last step -- the (batch, new samples)
+greedy class indices of rank 0 -- as DIR/samples_last_step.npy in float32; the inputs are seeded,
+so two builds given the same arguments can be compared output for output.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
 """
@@ -649,6 +658,22 @@ def extra_lines(dev, sd, rf, n_new, rank):
     return out
 
 
+DUMP_MAX_FLOATS = 16 << 20  # 64 MB of float32
+
+
+def dump_outputs(path: str, gen, n_new: int) -> None:
+    """The samples the last timed ``advance(n_new)`` generated, (batch, n_new) class indices as float32 (exact below
+    2**24).  Beyond 64 MB a fixed, seeded choice of time positions is kept, in time order."""
+    import numpy as np
+    last = gen.samples[:, gen.t - n_new + 1:gen.t + 1].cpu().numpy().astype(np.float32)
+    if last.size > DUMP_MAX_FLOATS:
+        keep = np.sort(np.random.default_rng(0).choice(n_new, DUMP_MAX_FLOATS // last.shape[0], replace=False))
+        last = np.ascontiguousarray(last[:, keep])
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "samples_last_step.npy"), last)
+    log(f"wrote {os.path.join(path, 'samples_last_step.npy')} {last.shape}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -656,10 +681,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--new-samples", type=int, default=16000, help="samples per sequence per step")
     ap.add_argument("--variant", type=int, default=0, help="0 auto, 1 generic, 2 stream, 3 pipe, 5 fold")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train-leg", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the T=1.0 and end-to-end lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's samples to DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the train legs, Trainer.fit, the extras and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-train-leg", action="store_true", help="with --full: skip the train legs and Trainer.fit")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extras")
     args = ap.parse_args()
+    run_train = args.full and not args.no_train_leg
+    run_extras = args.full and not args.no_extras
+    run_cpu = args.full and not args.no_cpu_baseline
 
     if os.environ.get("MOVENET_BENCH_DUMP_MAPS") == "1":
         # diagnostics: the executable mappings of the process, to resolve a native stack trace
@@ -749,6 +780,8 @@ def main():
 
     assert gen.t == rf - 1 + (K + W) * n_new
     gen.check_errors()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gen, n_new)
     variant_used = gen.variant
     total_samples = world * BATCH * n_new * K
     value = total_samples / elapsed
@@ -761,7 +794,7 @@ def main():
     # every HBM-bound kernel slower, the slab reduces 3x -- with or without empty_cache(); device
     # memory handed back fragmented is our reading, not verified)
     train, train3, fit = None, None, None
-    if not args.no_train_leg:
+    if run_train:
         del gen
         torch.cuda.empty_cache()
         # both M2 workloads at every N: config 2 (audio only, BASELINE configs[1]) and config 3
@@ -791,7 +824,7 @@ def main():
             torch.cuda.empty_cache()
 
     extras = None
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and run_extras:
         try:
             extras = extra_lines(dev, sd, rf, n_new, rank)
             log(f"rank 0: extras {extras}")
@@ -862,7 +895,7 @@ def main():
         out["train_step_config3"] = train3
         out["trainer_fit"] = fit
         out["extras"] = extras
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and run_cpu:
             cb = cpu_baseline(sd_cpu)
             out["cpu_baseline"] = cb
             cached = cpu_cached_line(sd_cpu)

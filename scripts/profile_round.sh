@@ -27,7 +27,7 @@ pass() {  # pass <name> <stdout file> <command ...>
   fi
 }
 
-BENCH="python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline"
+BENCH="python3 $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline"
 # 1. the bench command itself, plain and under the kernel trace
 pass bench $OUT/bench.json $BENCH
 pass bench_under_rocprof $OUT/bench_under_rocprof.json \

@@ -21,7 +21,7 @@ def test_bench_two_ranks_one_device():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-           "--new-samples", "128", "--variant", "2", "--no-cpu-baseline", "--no-extras"]
+           "--new-samples", "128", "--variant", "2", "--full", "--no-cpu-baseline", "--no-extras"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
