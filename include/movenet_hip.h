@@ -74,8 +74,8 @@ typedef struct mvn_params {
 } mvn_params;
 
 int mvn_abi_version(void);
-/* The library's A/B switches (MOVENET_HIP_* environment variables selecting kernel forms: cross-checks in the
- * tests, same-box comparisons) are parsed once per process at first use; this parses them again. */
+/* The library's kernel-form switches (MOVENET_HIP_* environment variables; the tests cross-check kernel forms
+ * with them) are parsed once per process at first use; this parses them again. */
 int mvn_reload_switches(void);
 const char *mvn_last_error(void);
 
@@ -217,7 +217,7 @@ typedef struct mvn_fwd_buffers {
   float *sg;    /* save: L x (B, C, Tp) sigmoid(g);   else NULL                 */
   float *z;     /* (B, C, Tp) scratch: the gated activation of the unfused layer
                    kernels; the fused paths keep z on chip and write the layers'
-                   packed weight images here (fused_layer.h, fused_fwd_bf3.h)        */
+                   packed weight images here (fused_fwd_bf3.h)                 */
   float *skip;  /* (B, K, Sp) sum of skips                                      */
   float *a1;    /* (B, Q, Sp) head hidden activation lrelu(conv1(lrelu(skip)))  */
   const float *ctx; /* optional local conditioning (B, C, ctx_ld), column t = time t

@@ -25,17 +25,11 @@ void parse_switches() {
   };
   Switches w;
   const char *t = getenv("MOVENET_HIP_FORWARD_TILE");
-  w.forward_tile = (t && t[0] == '6') ? 64 : (t && t[0] == '3') ? 32 : (t && t[0]) ? 32 : 0;
-  w.head_f32 = is("MOVENET_HIP_HEAD_MFMA", 'f');
+  w.forward_tile = t && t[0];
   w.forward_f32 = is("MOVENET_HIP_FORWARD_MFMA", 'f');
-  w.wgrad_f32 = is("MOVENET_HIP_WGRAD_MFMA", 'f');
   w.no_fused_forward = is("MOVENET_HIP_NO_FUSED_FORWARD", '1');
-  w.no_persistent_forward = is("MOVENET_HIP_NO_PERSISTENT_FORWARD", '1');
-  w.no_dense_strip = is("MOVENET_HIP_NO_DENSE_STRIP", '1');
-  w.no_side_stream = is("MOVENET_HIP_NO_SIDE_STREAM", '1');
   w.no_fused_backward = is("MOVENET_HIP_NO_FUSED_BACKWARD", '1');
   w.bwd_split = is("MOVENET_HIP_BWD_FORM", 's');
-  w.embed_scalar = is("MOVENET_HIP_EMBED_GRAD", 's');
   g_switches = w;
 }
 const Switches &switches() {

@@ -1,13 +1,11 @@
-// One gated residual layer of the full-sequence forward, PERSISTENT form (C = K = 64, audio only, fp32):
-// reference arithmetic movenet/modules.py:67-93, as fused_layer.h -- f,g = dilated k=2 convs;
+// One gated residual layer of the full-sequence forward, PERSISTENT form (C = K = 64, fp32):
+// reference arithmetic movenet/modules.py:67-93 -- f,g = dilated k=2 convs;
 // z = tanh(f) sigmoid(g); x' = x + Wr z + br; skip (+)= Ws z + bs for t >= RF - 1.
 //
-// fused_layer64_kernel (fused_layer.h) streams its 48 KB of weights from L2 through LDS for
-// every 128-column tile and passes 21 barriers per tile: 43 % matrix-core utilisation, 174 us per
-// layer at config 2.  This kernel is built like the backward halves (fused_bwd.h): a 512-thread
-// workgroup per CU walks 64-column tiles of a 512-step chunk, and BOTH products run in the
+// The tile kernel (fused_layer64p_kernel) is built like the backward halves (fused_bwd.h): a
+// 256-thread workgroup, two per CU, walks 32-column tiles of its chunk, and BOTH products run in the
 // transposed form with their weights in REGISTERS for the whole launch:
-//   F'[t][m] = sum_k X[k][t] W[k][m]   X = [x(t-d); x(t)] staged once per tile (128 x 64, pitch 68)
+//   F'[t][m] = sum_k X[k][t] W[k][m]   X = [x(t-d); x(t)] staged once per tile (128 x 32, pitch 36)
 //     wave -> (32 t x 32 channels, tap): filter AND gate block of its channels over the 64 rows
 //     of its tap (2 x 32 weights per lane); the two taps' partial sums meet through LDS, each
 //     wave finishing half of the block: gate in registers, z / tanh / sigmoid to LDS tiles
@@ -15,8 +13,10 @@
 //   epilogue through the staging tiles as whole-row float4 accesses: tanh, sigmoid, x' = (y + br) + x
 //   (x from the staged tile), skip (+)= y + bs.
 // The next tile's X waits in registers, then in the second X buffer; five barriers per tile.
-// Summation order differs from fused_layer64_kernel (two 64-deep partial sums instead of one
-// 128-deep chain): same values to fp32 rounding, not the same bits.
+// It replaced a per-tile kernel that streamed its 48 KB of weights from L2 through LDS for every
+// 128-column tile (21 barriers per tile, 43 % matrix-core utilisation, 174 us per layer at config 2).
+// Summation order differs from the two-kernel form (gemm_wx_staged_kernel<FgOpT> then <RsOp>: one
+// 128-deep chain) -- two 64-deep partial sums: same values to fp32 rounding, not the same bits.
 #pragma once
 #include <cstdlib>
 #include <type_traits>
@@ -25,6 +25,8 @@
 #include "fused_bwd.h"
 
 namespace mvn {
+
+constexpr int FP_C = 64;  // channels (C = K) of every persistent forward layer kernel
 
 struct FusedFwdPArgs {
   int t_begin, t_end, d, t_skip0, t_base, first_layer;
@@ -38,13 +40,10 @@ struct FusedFwdPArgs {
   const float *wpack = nullptr;  // fused_fwd_bf3.h: the layer's LDS image, written once per forward call (or NULL)
 };
 
-// NTB = 32-step blocks per tile: 2 -> 64-column tiles, 512 threads, one workgroup per CU (122 KB of
-// LDS); 1 -> 32-column tiles, 256 threads, TWO workgroups per CU (65 KB each) whose phases run
-// under each other's MFMAs -- the same registers per wave either way (a wave's blocks are 32 wide).
-template <int NTB>
-__global__ __launch_bounds__(256 * NTB, NTB == 1 ? 2 : 1) void fused_layer64p_kernel(FusedFwdPArgs a, int chunks_per_b,
-                                                                               int chunk_t) {
-  constexpr int C = 64, TT = 32 * NTB, LD = TT + 4, NTH = 256 * NTB;
+// 32-column tiles, 256 threads, TWO workgroups per CU (65 KB of LDS each) whose phases run under each
+// other's MFMAs.  (A 64-column form -- 512 threads, one workgroup per CU -- was measured and removed.)
+__global__ __launch_bounds__(256, 2) void fused_layer64p_kernel(FusedFwdPArgs a, int chunks_per_b, int chunk_t) {
+  constexpr int C = 64, TT = 32, LD = TT + 4, NTH = 256;
   extern __shared__ __attribute__((aligned(16))) float fp_lds[];
   float (*X)[128][LD] = (float (*)[128][LD])fp_lds;              // [2]: x(t - d) rows | x(t) rows
   float (*Z)[LD] = (float (*)[LD])(fp_lds + 2 * 128 * LD);       // gated activation
@@ -61,8 +60,8 @@ __global__ __launch_bounds__(256 * NTB, NTB == 1 ? 2 : 1) void fused_layer64p_ke
   // in the (out, in, tap) / (out, in) tensors -- fetched straight from global memory every wave
   // instruction touched 64 cache lines, 49 000 line requests per workgroup: longer than its tiles
   // (three passes of 32 KB through the tile buffers: filter, gate, residual | skip)
-  const int tt = (wave >> 1) % NTB, cc = wave & 1, kh = wave / (2 * NTB);   // first product: block (tt, cc), tap kh
-  const int t2 = wave >> 2, mt = wave & 3;                                  // second product: block (t2, mt)
+  const int cc = wave & 1, kh = wave / 2;     // first product: block cc, tap kh
+  const int t2 = wave >> 2, mt = wave & 3;    // second product: block (t2, mt)
   float wfr[32], wgr[32], wrs[32];
 #pragma unroll
   for (int pass = 0; pass < 3; ++pass) {
@@ -160,7 +159,7 @@ __global__ __launch_bounds__(256 * NTB, NTB == 1 ? 2 : 1) void fused_layer64p_ke
       float av[2][8];
       auto fetch = [&](int g, int S) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) av[S][i] = X[cur][64 * kh + 2 * (8 * g + i) + lh][32 * tt + li];
+        for (int i = 0; i < 8; ++i) av[S][i] = X[cur][64 * kh + 2 * (8 * g + i) + lh][li];
       };
       fetch(0, 0);
 #pragma unroll
@@ -184,7 +183,7 @@ __global__ __launch_bounds__(256 * NTB, NTB == 1 ? 2 : 1) void fused_layer64p_ke
       constexpr int q0 = decltype(QB)::value;
 #pragma unroll
       for (int qq = 0; qq < 2; ++qq) {
-        const int q = q0 + qq, tc = 32 * tt + 8 * q + h4;
+        const int q = q0 + qq, tc = 8 * q + h4;
         *(f4 *)&S1[32 * cc + li][tc] = f4{accf[4 * q], accf[4 * q + 1], accf[4 * q + 2], accf[4 * q + 3]};
         *(f4 *)&S2[32 * cc + li][tc] = f4{accg[4 * q], accg[4 * q + 1], accg[4 * q + 2], accg[4 * q + 3]};
       }
@@ -196,7 +195,7 @@ __global__ __launch_bounds__(256 * NTB, NTB == 1 ? 2 : 1) void fused_layer64p_ke
       constexpr int q0 = decltype(QB)::value;
 #pragma unroll
       for (int qq = 0; qq < 2; ++qq) {
-        const int q = q0 + qq, tc = 32 * tt + 8 * q + h4;
+        const int q = q0 + qq, tc = 8 * q + h4;
         const f4 pf = *(const f4 *)&S1[32 * cc + li][tc], pg = *(const f4 *)&S2[32 * cc + li][tc];
         f4 tv, sv;
         tv.x = tanh_fast(accf[4 * q] + pf.x);     sv.x = sigmoid_fast(accg[4 * q] + pg.x);
@@ -285,7 +284,7 @@ __global__ __launch_bounds__(256 * NTB, NTB == 1 ? 2 : 1) void fused_layer64p_ke
 
 // ----------------------------------------------------------------------------------------
 // STRIP form: one WAVE owns a strip of 32 time columns and runs the whole layer on it without a
-// single barrier (r2b timing builds: the tile kernels above spend 45 % of their time with waves
+// single barrier (r2b timing builds: the tile kernel above, 32 and 64 columns, spent 45 % of its time with waves
 // waiting at barriers for a sibling whose SIMD is held by another wave's MFMA burst).
 //   * both weight matrices sit in LDS for the whole launch (96 KB, read-only), laid out per MFMA
 //     block and lane so that one ds_read_b128 feeds four MFMAs (A operand: lane -> output row);
@@ -693,28 +692,23 @@ static int launch_dense_strip(const DenseStripArgs &a, int m_total, int batch, h
   return MVN_OK;
 }
 
-template <int NTB>
 static int launch_fused_layer64p_t(const FusedFwdPArgs &a, int batch, hipStream_t s) {
-  constexpr int TT = 32 * NTB, LDS_BYTES = (2 * 128 + 3 * 64) * (TT + 4) * (int)sizeof(float);
+  constexpr int TT = 32, LDS_BYTES = (2 * 128 + 3 * 64) * (TT + 4) * (int)sizeof(float);
   const int nt = a.t_end - (a.t_begin & ~TILE_ALIGN);
   if (a.t_end <= a.t_begin || batch <= 0) return MVN_OK;
   int chunks, chunk_t;
-  fb_chunks(nt, batch, NTB == 1 ? 2 : 1, &chunks, &chunk_t, TT);  // one round of workgroups (fused_bwd.h)
-  const void *fn = (const void *)fused_layer64p_kernel<NTB>;
-  const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(fused_layer64p)");
+  fb_chunks(nt, batch, 2, &chunks, &chunk_t, TT);  // one round of workgroups (fused_bwd.h)
+  const int rc = ensure_max_dynamic_lds((const void *)fused_layer64p_kernel, "hipFuncSetAttribute(fused_layer64p)");
   if (rc) return rc;
-  hipLaunchKernelGGL(fused_layer64p_kernel<NTB>, dim3(chunks * batch), dim3(256 * NTB), LDS_BYTES, s, a, chunks, chunk_t);
+  hipLaunchKernelGGL(fused_layer64p_kernel, dim3(chunks * batch), dim3(256), LDS_BYTES, s, a, chunks, chunk_t);
   return MVN_OK;
 }
-// The strip kernel is the default; MOVENET_HIP_FORWARD_TILE=32 / 64 select the tile kernels (A/B, tests)
+// The strip kernel is the default; MOVENET_HIP_FORWARD_TILE (any value) selects the tile kernel (tests)
 static int launch_fused_layer64p(const FusedFwdPArgs &a, int batch, hipStream_t s) {
   if (a.ctx.p) return launch_fused_layer64s(a, batch, s);  // conditioned: the strip kernel only (the caller checks the row length)
-  const int tile = switches().forward_tile;
-  if (tile == 64) return launch_fused_layer64p_t<2>(a, batch, s);
-  if (tile == 32) return launch_fused_layer64p_t<1>(a, batch, s);
   // (the strip kernel's buffer resources span 2 GB from a sequence's base: rows of more than 4 M
   // columns -- 25 x the reference's MAX_AUDIO_FRAMES -- go to the tile kernel)
-  if (a.xin.ld > (1 << 22) || a.skip.ld > (1 << 22)) return launch_fused_layer64p_t<1>(a, batch, s);
+  if (switches().forward_tile || a.xin.ld > (1 << 22) || a.skip.ld > (1 << 22)) return launch_fused_layer64p_t(a, batch, s);
   return launch_fused_layer64s(a, batch, s);
 }
 

@@ -838,10 +838,7 @@ constexpr size_t DS3_IMG1_F = (64 * 256 * 6 + 256 * 4) / 4, DS3_IMG2_F = (256 * 
 constexpr size_t DS3_IMG_F = DS3_IMG1_F + 4 * DS3_IMG2_F;      // forward: conv1 + conv2's four blocks
 constexpr size_t DS3_BWD_IMG_F = 4 * DS3_IMG2_F + DS3_IMG2_F;  // backward: conv2^T's four blocks + conv1^T
 
-// MOVENET_HIP_FORWARD_MFMA=f32 keeps the fp32-MFMA strip kernel (A/B, tests); read per call
-// MOVENET_HIP_HEAD_MFMA=f32 keeps the head's fp32 kernels (strips for the convolutions, the staged kernel for their
-// data gradients); common.h: Switches
-static bool head_bf3_enabled() { return !switches().head_f32; }
+// MOVENET_HIP_FORWARD_MFMA=f32 keeps the fp32-MFMA strip kernel and the head's fp32 kernels (tests); common.h: Switches
 static bool forward_bf3_enabled() { return !switches().forward_f32; }
 
 // the LDS images of layers 0 .. L-1 into `dst` (L x FS3_PACK_F floats), one launch per 32 layers

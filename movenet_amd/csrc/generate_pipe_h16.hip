@@ -14,9 +14,8 @@
 //   * the vector operand of every product (residual stream, popped queue entry, context
 //     column, gated activation, head activations) is rounded to fp16 when it is written to
 //     LDS, and a lane reads its 64 inputs with 8 ds_read_b128 instead of 16;
-//   * products and sums run in fp16 x fp16 -> fp32: v_mfma_f32_16x16x32_f16 in the layer stages (r3,
-//     the default: "fp16 MFMA 1x1 convs" as BASELINE configs[4] is written), v_dot2c_f32_f16 in the
-//     head and in the layer stages' dot-product form (MOVENET_H16_FORM=dot2).
+//   * products and sums run in fp16 x fp16 -> fp32: v_mfma_f32_16x16x32_f16 in the layer stages (r3:
+//     "fp16 MFMA 1x1 convs" as BASELINE configs[4] is written), v_dot2c_f32_f16 in the head.
 // Everything else stays fp32: the residual stream itself, the skip sum, the past-tap
 // partial sums, biases, gating, the embedding rows (a gather, no product), the dilation
 // queues in HBM/L2, logits and the double softmax.
@@ -35,8 +34,7 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));  // 16 bytes
 
 namespace h16 {
 constexpr int C = 128, Q = 256, NT = 512;
-constexpr int LPS = 2;              // layers per stage, dot-product form
-// layers per stage, matrix-core form: THREE when a pipeline serves one sequence (21 stages instead of
+// layers per stage: THREE when a pipeline serves one sequence (21 stages instead of
 // 31: ten hops less on the chain; the third layer's past taps and the skip tiles stream from L2
 // behind the hand-on), two when it serves several in turn (there the stages' service time per turn
 // is what bounds the step, and L2 streaming per turn costs more than ten hops save)
@@ -44,9 +42,6 @@ template <bool MULTI>
 struct LpsM {
   static constexpr int value = MULTI ? 2 : 3;
 };
-constexpr int KQ = 2;               // lanes sharing one channel's two rows
-constexpr int KPER = C / KQ;        // 64 inputs per lane
-constexpr int NV = KPER / 8;        // 8 h8 vectors per row per lane
 constexpr int MAT_H = 2 * C * C;    // halves per 2C x C matrix
 constexpr int MAT_F = MAT_H / 2;    // ... in float units of the packed blob
 constexpr int LAYER_F = 3 * MAT_F + 2 * C;  // WC | WP | WR (halves) | residual, skip biases (fp32)
@@ -57,19 +52,15 @@ constexpr int HEAD_F = W1_F + Q + W2_F + Q;
 constexpr int GRAN = 2 * C;         // granules per inbox: C residual stream | C running skip sum
 constexpr int GL = C / 64;          // the chain polls the residual granules only: one 16-byte load per lane
 constexpr int W1NV = (C / 2) / 8;   // conv1: 2 threads per row, 64 inputs each = 8 vectors
-// LDS bytes: layer stage LPS * 64 KB of past-tap weights + vectors; head stage 64 KB of conv1
-constexpr int LDS_BYTES = LPS * MAT_H * 2 + 8192;
 // r3, several sequences per pipeline (as gen_fold_kernel<true>): a pipeline serves up to GMAX
 // sequences in turn; what survives from a sequence's turn to its next is the past-tap part of its
-// f/g sums (pf, pg of the LPS layers: four floats per channel), kept in LDS behind the vectors
+// f/g sums (pf, pg of the stage's two layers: four floats per channel), kept in LDS behind the vectors
 constexpr int GMAX = 8;
-constexpr int PFS_F = 2 * LPS;      // floats per channel and sequence
-constexpr int PFS_FM = PFS_F;       // ... matrix-core form (two layers per stage when MULTI)
-constexpr int LDS_BYTES_MULTI = LDS_BYTES + GMAX * C * PFS_F * 4;
-// matrix-core form: two layers' past taps in LDS (a third streams from L2) + 4 KB of vectors
+constexpr int PFS_FM = 4;           // floats per channel and sequence
+// LDS bytes: two layers' past taps (a third streams from L2) + 4 KB of vectors; head stage 64 KB of conv1
 constexpr int LDS_BYTES_M = 2 * MAT_H * 2 + 4096;
 constexpr int LDS_BYTES_M_MULTI = LDS_BYTES_M + GMAX * C * PFS_FM * 4;
-static_assert(LDS_BYTES_M_MULTI <= 160 * 1024 && LDS_BYTES_MULTI <= 160 * 1024, "one CU's LDS");
+static_assert(LDS_BYTES_M_MULTI <= 160 * 1024, "one CU's LDS");
 }  // namespace h16
 
 __device__ __forceinline__ float dot8(const h8 w, const h8 x, float acc) {
@@ -77,36 +68,6 @@ __device__ __forceinline__ float dot8(const h8 w, const h8 x, float acc) {
   acc = __builtin_amdgcn_fdot2(h2{w[2], w[3]}, h2{x[2], x[3]}, acc, false);
   acc = __builtin_amdgcn_fdot2(h2{w[4], w[5]}, h2{x[4], x[5]}, acc, false);
   return __builtin_amdgcn_fdot2(h2{w[6], w[7]}, h2{x[6], x[7]}, acc, false);
-}
-// two rows (registers) against the same LDS vector of 8*N halves: four independent chains
-// per row, combined in a fixed order
-template <int N>
-__device__ __forceinline__ void dot2_rows(const h8 (&wa)[N], const h8 (&wb)[N], const _Float16 *xp, float &ra,
-                                          float &rb) {
-  // the vector is fetched four h8 at a time (16 registers live, not 32: next to 128 weight
-  // registers the whole vector spills), the second half requested before the first is used
-  constexpr int CH = 4;
-  static_assert(N % CH == 0, "whole chunks");
-  float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
-  h8 x[2][CH];
-#pragma unroll
-  for (int i = 0; i < CH; ++i) x[0][i] = ((const h8 *)xp)[i];
-#pragma unroll
-  for (int ch = 0; ch < N / CH; ++ch) {
-    if (ch + 1 < N / CH) {
-#pragma unroll
-      for (int i = 0; i < CH; ++i) x[(ch + 1) & 1][i] = ((const h8 *)xp)[CH * (ch + 1) + i];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      a[i & 3] = dot8(wa[CH * ch + i], x[ch & 1][i], a[i & 3]);
-      b[i & 3] = dot8(wb[CH * ch + i], x[ch & 1][i], b[i & 3]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  ra = (a[0] + a[2]) + (a[1] + a[3]);
-  rb = (b[0] + b[2]) + (b[1] + b[3]);
 }
 // one row whose weights are fetched on the fly (LDS or L2): [N][stride] h8 at column idx.
 // Four vectors at a time behind scheduling fences: hoisted together, the 2 x N vectors of a
@@ -132,8 +93,8 @@ __device__ __forceinline__ float pair_sum(float v) { return v + dpp_mov<DPP_XOR1
 
 // MULTI = false: one sequence per pipeline (nseq == nb).  MULTI = true: pipeline b serves sequences
 // b, b + nb, b + 2 nb, ... < nseq in turn.
-// MFMA = true (r3): every product of a layer stage on the matrix cores (see the layer stage below).
-template <bool MULTI, bool MFMA>
+// Every product of a layer stage runs on the matrix cores (r3, see the layer stage below).
+template <bool MULTI>
 __global__ __launch_bounds__(512, 2) void gen_pipe_h16_kernel(GenArgs a, u64 *hand, unsigned *err, int NS,
                                                              int nb, int nseq) {
   using namespace h16;
@@ -160,9 +121,8 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_h16_kernel(GenArgs a, u64 *ha
   int bq = b;                                           // the sequence whose turn it is
   u64 *inbox = hand + ((size_t)b * NS + s) * GRAN;
   u64 *outbox = hand + ((size_t)b * NS + s_next) * GRAN;
-  constexpr int LDSB = MFMA ? LDS_BYTES_M : LDS_BYTES;
-  int *iflag = (int *)(smem_b + LDSB - 64);  // [0] ok flag, [3] fast-edge flag
-  float *pfs = (float *)(smem_b + LDSB);     // MULTI: [GMAX][C][PFS_F(M)] (layer stages), head: indices
+  int *iflag = (int *)(smem_b + LDS_BYTES_M - 64);  // [0] ok flag, [3] fast-edge flag
+  float *pfs = (float *)(smem_b + LDS_BYTES_M);     // MULTI: [GMAX][C][PFS_FM] (layer stages), head: indices
   bool fast_edge = false;
   {
     unsigned *xcc = err + 16;
@@ -181,16 +141,16 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_h16_kernel(GenArgs a, u64 *ha
     __syncthreads();
   }
 
-  if (MFMA && s < NS - 1) {
-    // ================= layer stage, MATRIX-CORE form: layers l0 .. l0+nl-1 =================
+  if (s < NS - 1) {
+    // ================= layer stage: layers l0 .. l0+nl-1 =================
     // A mat-vec wastes 15 of an MFMA's 16 columns, and still: scripts/probes/h16_phase.hip times one
     // 256 x 128 phase (vector reads, products, barrier) at 412 cycles with eight
-    // v_mfma_f32_16x16x32_f16 per wave against 464 (all waves) / 520 (one wave per SIMD, the form
-    // below) with v_dot2c -- and the matrix cores return every row's COMPLETE sum to a lane, so the
-    // DPP lane sums go as well.  (Half of the rows each way is slower than either: 545.)
+    // v_mfma_f32_16x16x32_f16 per wave against 464 (all waves) / 520 (one wave per SIMD, the r2
+    // dot-product form, since removed) with v_dot2c -- and the matrix cores return every row's
+    // COMPLETE sum to a lane, so the DPP lane sums go as well.  (Half of the rows each way is slower than either: 545.)
     // Wave w owns channels [16 w, 16 w + 16): four 16-row tiles per layer -- filter, gate, residual,
     // skip -- x four k-steps of 32 inputs, the A operands in registers (lane l: row l % 16, inputs
-    // 32 kk + 8 (l / 16) .. + 8: 64 registers per layer, as many as the dot-product form); the B
+    // 32 kk + 8 (l / 16) .. + 8: 64 registers per layer, as many as the r2 form); the B
     // operand is the stage's vector in every column (lane l reads inputs 32 kk + 8 (l / 16) .. + 8:
     // four ds_read_b128, the same for the 16 lanes of a row group); the accumulator of lane l holds
     // rows 4 (l / 16) + r, r < 4, in every column: lane 16 q + r (r < 4) post-processes channel
@@ -439,205 +399,6 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_h16_kernel(GenArgs a, u64 *ha
     return;
   }
 
-  if (!MFMA && s < NS - 1) {
-    // ================= layer stage, dot-product form (r2 + the r3 skip lane): layers l0 .. l0+nl-1 =================
-    const int l0 = s * LPS, nl = min(LPS, L - l0);
-    const bool fg_group = tid < 256;
-    const int t = tid & 255, c = t / KQ, kq = t % KQ;
-    const bool lead = kq == 0;
-    h8 *wp = (h8 *)smem_b;                                   // [LPS][2*NV][256] h8: past-tap f|g weights
-    float *cur = (float *)(smem_b + LPS * MAT_H * 2);        // [C] residual stream (fp32)
-    _Float16 *curh = (_Float16 *)(cur + 2 * C);              // [C] the stream as the products' operand
-    // r3: the running skip sum travels on a lane of its own (as in gen_fold_kernel): the chain waits
-    // for the C residual granules only -- ONE 16-byte poll per lane through poll16 -- and the lane
-    // that owns a channel fetches its skip granule off the chain and adds it when the stage hands on
-    const u64 *skbox = inbox + C + c;  // (rebound per turn when MULTI)
-    _Float16 *zbh = curh + C;                                // [C] gated activation
-    _Float16 *pasth = zbh + C;                               // [LPS][C] popped queue entries
-    _Float16 *ctxh = pasth + LPS * C;                        // [C] context column
-    float *ring = a.state + (size_t)b * a.state_per_seq;
-    auto bind = [&](int g) {  // MULTI: the pointers of sequence b + g nb
-      bq = b + g * nb;
-      inbox = hand + ((size_t)bq * NS + s) * GRAN;
-      outbox = hand + ((size_t)bq * NS + s_next) * GRAN;
-      skbox = inbox + C + c;
-      ring = a.state + (size_t)bq * a.state_per_seq;
-    };
-
-    h8 wa[LPS][NV], wb[LPS][NV];  // FG: f_c | g_c current-tap rows; RS: res_c | skip_c
-    float bias_r[LPS], bias_s[LPS], pf[LPS], pg[LPS], xs[LPS];
-    int doff[LPS], dmask[LPS];
-#pragma unroll
-    for (int j = 0; j < LPS; ++j) {
-      bias_r[j] = 0.f; bias_s[j] = 0.f; pf[j] = 0.f; pg[j] = 0.f; xs[j] = 0.f;
-      doff[j] = 0; dmask[j] = 0;
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        wa[j][i] = h8{0, 0, 0, 0, 0, 0, 0, 0};
-        wb[j][i] = h8{0, 0, 0, 0, 0, 0, 0, 0};
-      }
-      if (j < nl) {
-        const float *lw = a.w + EMB_F + (size_t)(l0 + j) * LAYER_F;
-        const h8 *wc8 = (const h8 *)lw, *wp8 = (const h8 *)(lw + MAT_F), *wr8 = (const h8 *)(lw + 2 * MAT_F);
-        if (fg_group) {
-#pragma unroll
-          for (int i = 0; i < NV; ++i) {
-            wa[j][i] = wc8[i * 256 + t];
-            wb[j][i] = wc8[(NV + i) * 256 + t];
-          }
-#pragma unroll
-          for (int i = 0; i < 2 * NV; ++i) wp[(j * 2 * NV + i) * 256 + t] = wp8[i * 256 + t];
-        } else {
-#pragma unroll
-          for (int i = 0; i < NV; ++i) {
-            wa[j][i] = wr8[i * 256 + t];
-            wb[j][i] = wr8[(NV + i) * 256 + t];
-          }
-          bias_r[j] = lw[3 * MAT_F + c];
-          bias_s[j] = lw[3 * MAT_F + C + c];
-        }
-        const int l = l0 + j;
-        dmask[j] = (1 << (l % a.layer_size)) - 1;
-        doff[j] = ring_offset(l, a.layer_size, C);
-      }
-    }
-
-    // Off the critical path: push this step's layer inputs into the dilation queues, pop the
-    // entries step tn needs (RS lead lanes), then the past-tap half of step tn's f/g sums
-    auto precompute = [&](int tn, bool push) {
-      int tq = t;
-      asm volatile("" : "+v"(tq));  // addresses rebuilt per step: the chain needs the registers
-      const int cq = tq / KQ, kk = tq % KQ;
-      if (!fg_group && lead) {
-#pragma unroll
-        for (int j = 0; j < LPS; ++j)
-          if (j < nl) {
-            float *base = ring + doff[j] + cq;
-            if (push) base[((tn - 1) & dmask[j]) * C] = xs[j];
-            const float pv = (push && dmask[j] == 0) ? xs[j] : ring_load(base + (tn & dmask[j]) * C);
-            pasth[j * C + cq] = (_Float16)pv;
-          }
-      }
-      if (a.ctx_tm && fg_group && tq < C)
-        ctxh[tq] = (_Float16)a.ctx_tm[(size_t)bq * a.ctx_stride_b + (size_t)tn * C + tq];
-      __syncthreads();
-      if (fg_group) {
-#pragma unroll
-        for (int j = 0; j < LPS; ++j)
-          if (j < nl) {
-            const h8 *wpj = wp + j * 2 * NV * 256;
-            pf[j] = pair_sum(dot_stream_h<NV>(wpj, 256, tq, pasth + j * C + KPER * kk));
-            pg[j] = pair_sum(dot_stream_h<NV>(wpj + NV * 256, 256, tq, pasth + j * C + KPER * kk));
-            if (a.ctx_tm) {
-              // 1x1 context convs (modules.py:58-63, :75-77), weights streamed from L2
-              const float *wc = a.wctx + (size_t)(l0 + j) * CTX_LAYER_F;
-              pf[j] += pair_sum(dot_stream_h<NV>((const h8 *)wc, 256, tq, ctxh + KPER * kk)) + wc[MAT_F + cq];
-              pg[j] += pair_sum(dot_stream_h<NV>((const h8 *)wc + NV * 256, 256, tq, ctxh + KPER * kk)) +
-                       wc[MAT_F + C + cq];
-            }
-          }
-      }
-    };
-    // MULTI: a sequence's pf / pg between its turns (FG lead lanes write, both lanes of a channel read)
-    auto save_pf = [&](int g) {
-      if (MULTI && fg_group && lead) *(f4 *)(pfs + ((size_t)g * C + c) * PFS_F) = f4{pf[0], pg[0], pf[1], pg[1]};
-    };
-    auto load_pf = [&](int g) {
-      if (MULTI && fg_group) {
-        const f4 v = *(const f4 *)(pfs + ((size_t)g * C + c) * PFS_F);
-        pf[0] = v.x; pg[0] = v.y; pf[1] = v.z; pg[1] = v.w;
-      }
-    };
-    static_assert(LPS == 2, "save_pf / load_pf move two layers' sums as one float4");
-    __syncthreads();
-    if (MULTI) {
-      for (int g = 0; g < G; ++g) {
-        bind(g);
-        precompute(a.t_begin, false);
-        save_pf(g);
-        __syncthreads();  // the FG waves have read this sequence's popped entries: the next one's may land
-      }
-    } else {
-      precompute(a.t_begin, false);
-    }
-
-    bool alive = true;
-    for (int ts = a.t_begin; ts < a.t_end && alive; ++ts)
-    for (int g = 0; g < G; ++g) {
-      if (MULTI) bind(g);
-      const unsigned epoch = (unsigned)(ts - a.t_begin + 1);
-      if (wave == 0) {
-        float v[GL];
-        const bool ok = wait_inbox<GL>(inbox, epoch, err, v);  // the C residual granules
-        if (ok) {
-          cur[2 * lane] = v[0];
-          cur[2 * lane + 1] = v[1];
-          *(h2 *)(curh + 2 * lane) = h2{(_Float16)v[0], (_Float16)v[1]};
-        }
-        if (lane == 0) iflag[0] = ok ? 1 : 0;
-      }
-      lds_barrier();
-      MVN_STAMP(b, s, ts - a.t_begin, 0);
-      load_pf(g);
-      // skip lane: the granule was sent with the residual ones; its load is issued here and used
-      // when the stage hands on (the spin loop is only the fallback)
-      const u64 sk_peek = (!fg_group && lead) ? peek_granule(skbox) : 0;
-      float skipacc = 0.f;
-#pragma unroll
-      for (int j = 0; j < LPS; ++j)
-        if (j < nl) {
-          float old = 0.f;
-          if (fg_group) {
-            float f, g;
-            dot2_rows<NV>(wa[j], wb[j], curh + KPER * kq, f, g);
-            f = pair_sum(f) + pf[j];
-            g = pair_sum(g) + pg[j];
-            const float z = gate_fast(f, g);
-            if (lead) zbh[c] = (_Float16)z;
-          } else if (lead) {
-            old = cur[c];  // this layer's input: residual add below, queue push later
-          }
-          lds_barrier();
-          if (!fg_group) {
-            float r, k;
-            dot2_rows<NV>(wa[j], wb[j], zbh + KPER * kq, r, k);
-            r = pair_sum(r);
-            k = pair_sum(k);
-            if (lead) {
-              xs[j] = old;
-              const float outv = (r + bias_r[j]) + old;
-              cur[c] = outv;
-              curh[c] = (_Float16)outv;
-              skipacc += k + bias_s[j];
-              if (j == nl - 1) {
-                // the stage's last layer: hand the activation on before anything else
-                put_granule(outbox + c, epoch, outv, fast_edge);
-                const float skin = (unsigned)(sk_peek >> 32) == epoch ? __uint_as_float((unsigned)sk_peek)
-                                                                      : wait_granule(skbox, epoch, err);
-                put_granule(outbox + C + c, epoch, skin + skipacc, fast_edge);
-              }
-            }
-          }
-          lds_barrier();
-        }
-      MVN_STAMP(b, s, ts - a.t_begin, 1);
-      if (iflag[0] == 0) {  // hand-off timed out (checked after the step: off the chain)
-        alive = false;
-        break;
-      }
-      if (ts + 1 < a.t_end) {
-        precompute(ts + 1, true);
-        save_pf(g);
-      } else if (!fg_group && lead) {
-        // last step of the launch: push only (the next launch pops in its prologue)
-#pragma unroll
-        for (int j = 0; j < LPS; ++j)
-          if (j < nl) ring[doff[j] + c + (ts & dmask[j]) * C] = xs[j];
-      }
-    }
-    return;
-  }
-
   // ============================ head stage ============================
   {
     h8 *big = (h8 *)smem_b;                                   // conv1 weights [W1NV][512] h8 (64 KB)
@@ -789,32 +550,25 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_h16_kernel(GenArgs a, u64 *ha
 }
 
 // ---- packing: state_dict layouts (fp32) -> per-thread register order, halves ------------
-// each 2C x C matrix: [2*NV][t (256)] vectors of 8 halves; thread t = KQ*c + kq owns rows
-// (c, C+c) x inputs k = KPER*kq + 8*(iv % NV) + e: vectors 0..NV-1 row c, NV..2NV-1 row C+c
-__device__ __forceinline__ void h16_matrix_index(int h, int &row, int &k, bool mfma) {
+// each 2C x C matrix in MFMA A-operand order: [tile 2][kk 4][wave 8][lane 64] vectors of 8 halves; lane l
+// of wave w holds row 16 w + l % 16 of the tile's half (filter | gate, residual | skip), inputs
+// 32 kk + 8 (l / 16) + e
+__device__ __forceinline__ void h16_matrix_index(int h, int &row, int &k) {
   using namespace h16;
   const int e = h & 7, v = h >> 3;
-  if (mfma) {
-    // MFMA A-operand order: [tile 2][kk 4][wave 8][lane 64] vectors; lane l of wave w holds row
-    // 16 w + l % 16 of the tile's half (filter | gate, residual | skip), inputs 32 kk + 8 (l / 16) + e
-    const int l = v & 63, w = (v >> 6) & 7, kk = (v >> 9) & 3, t = v >> 11;
-    row = t * C + 16 * w + (l & 15);
-    k = 32 * kk + 8 * (l >> 4) + e;
-    return;
-  }
-  const int t = v & 255, iv = v >> 8;
-  row = (iv / NV) * C + t / KQ;
-  k = KPER * (t % KQ) + 8 * (iv % NV) + e;
+  const int l = v & 63, w = (v >> 6) & 7, kk = (v >> 9) & 3, t = v >> 11;
+  row = t * C + 16 * w + (l & 15);
+  k = 32 * kk + 8 * (l >> 4) + e;
 }
 __global__ void pack_layer_h16_kernel(const float *fw, const float *gw, const float *rw, const float *rb,
-                                      const float *sw, const float *sb, float *__restrict__ dst, bool mfma) {
+                                      const float *sw, const float *sb, float *__restrict__ dst) {
   using namespace h16;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;  // half index for the matrices
   _Float16 *dh = (_Float16 *)dst;
   if (i < 3 * MAT_H) {
     const int region = i / MAT_H;
     int row, k;
-    h16_matrix_index(i - region * MAT_H, row, k, mfma);
+    h16_matrix_index(i - region * MAT_H, row, k);
     const float v = region < 2 ? fg_elem(fw, gw, C, row, region == 0 ? C + k : k)  // WC current, WP past tap
                                : rs_elem(rw, sw, C, row, k);
     dh[i] = (_Float16)v;
@@ -824,13 +578,13 @@ __global__ void pack_layer_h16_kernel(const float *fw, const float *gw, const fl
   }
 }
 __global__ void pack_ctx_h16_kernel(const float *wcf, const float *bcf, const float *wcg, const float *bcg,
-                                    float *__restrict__ dst, bool mfma) {
+                                    float *__restrict__ dst) {
   using namespace h16;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   _Float16 *dh = (_Float16 *)dst;
   if (i < MAT_H) {
     int row, k;
-    h16_matrix_index(i, row, k, mfma);
+    h16_matrix_index(i, row, k);
     dh[i] = (_Float16)(row < C ? wcf[(size_t)row * C + k] : wcg[(size_t)(row - C) * C + k]);
   } else if (i < MAT_H + 2 * C) {
     const int o = i - MAT_H;
@@ -866,22 +620,15 @@ __global__ void pack_embed_h16_kernel(const float *__restrict__ causal_w, float 
   dst[i] = causal_w[((size_t)c * Q + qq) * 2 + tap];
 }
 
-// Which layer-stage form packs and runs: the matrix-core form unless MOVENET_H16_FORM=dot2 (the
-// packed weight order differs, so pack and launch read the same switch; read once per process).
-static bool h16_mfma_form() {
-  static const bool on = [] {
-    const char *e = getenv("MOVENET_H16_FORM");
-    return !(e && e[0] == 'd');
-  }();
-  return on;
-}
-
 bool pipe_h16_ok(const mvn_dims *d) {
   return d->residual_channels == 128 && d->skip_channels == 128 && d->input_channels == 256 &&
          n_layers(d) >= 1;
 }
-// stages per pipeline for SIZING (hand-off area, co-residency): the two-layer forms' count, the larger one
-int pipe_h16_stages(const mvn_dims *d) { return (n_layers(d) + h16::LPS - 1) / h16::LPS + 1; }
+// stages per pipeline for SIZING (hand-off area, co-residency): the two-layer count (MULTI), the larger one
+int pipe_h16_stages(const mvn_dims *d) {
+  constexpr int lps = h16::LpsM<true>::value;
+  return (n_layers(d) + lps - 1) / lps + 1;
+}
 int pipe_h16_pipelines(const mvn_dims *d) {  // co-resident pipelines
   const int NS = pipe_h16_stages(d);
   return NS <= PIPE_XCD_CUS ? 8 * (PIPE_XCD_CUS / NS) : 8 / ((NS + PIPE_XCD_CUS - 1) / PIPE_XCD_CUS);
@@ -899,7 +646,7 @@ int pipe_h16_pack(const mvn_dims *d, const mvn_params *p, float *packed, bool ha
   for (int l = 0; l < L; ++l)
     hipLaunchKernelGGL(pack_layer_h16_kernel, dim3((3 * MAT_H + 2 * C + 255) / 256), dim3(256), 0, s,
                        p->filter_w[l], p->gate_w[l], p->residual_w[l], p->residual_b[l], p->skip_w[l],
-                       p->skip_b[l], packed + EMB_F + (size_t)l * LAYER_F, h16_mfma_form());
+                       p->skip_b[l], packed + EMB_F + (size_t)l * LAYER_F);
   float *head = packed + EMB_F + (size_t)L * LAYER_F;
   hipLaunchKernelGGL(pack_head_h16_kernel, dim3((Q * C + Q * Q + Q + 255) / 256), dim3(256), 0, s, p->head1_w,
                      p->head1_b, p->head2_w, p->head2_b, head);
@@ -908,7 +655,7 @@ int pipe_h16_pack(const mvn_dims *d, const mvn_params *p, float *packed, bool ha
     for (int l = 0; l < L; ++l)
       hipLaunchKernelGGL(pack_ctx_h16_kernel, dim3((MAT_H + 2 * C + 255) / 256), dim3(256), 0, s,
                          p->ctx_filter_w[l], p->ctx_filter_b[l], p->ctx_gate_w[l], p->ctx_gate_b[l],
-                         ctx + (size_t)l * CTX_LAYER_F, h16_mfma_form());
+                         ctx + (size_t)l * CTX_LAYER_F);
   }
   return check_hip(hipGetLastError(), "pipe_h16_pack");
 }
@@ -921,13 +668,11 @@ int pipe_h16_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand,
   const int pipes = std::min(batch, pipe_h16_pipelines(d));
   const bool multi = batch > pipes;
   int dev = 0, cus = 0, per_cu = 0, coop = 0;
-  const bool mm = h16_mfma_form();
-  // (a pipeline that serves one sequence runs three layers per stage in the matrix-core form)
-  const int lps = mm ? (multi ? LpsM<true>::value : LpsM<false>::value) : LPS;
+  // (a pipeline that serves one sequence runs three layers per stage)
+  const int lps = multi ? LpsM<true>::value : LpsM<false>::value;
   int NS = (n_layers(d) + lps - 1) / lps + 1;
-  const void *fn = multi ? (mm ? (const void *)gen_pipe_h16_kernel<true, true> : (const void *)gen_pipe_h16_kernel<true, false>)
-                         : (mm ? (const void *)gen_pipe_h16_kernel<false, true> : (const void *)gen_pipe_h16_kernel<false, false>);
-  const int lds_bytes = mm ? (multi ? LDS_BYTES_M_MULTI : LDS_BYTES_M) : (multi ? LDS_BYTES_MULTI : LDS_BYTES);
+  const void *fn = multi ? (const void *)gen_pipe_h16_kernel<true> : (const void *)gen_pipe_h16_kernel<false>;
+  const int lds_bytes = multi ? LDS_BYTES_M_MULTI : LDS_BYTES_M;
   int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(gen_pipe_h16)");
   if (rc) return rc;
   if (check_hip(hipGetDevice(&dev), "hipGetDevice") ||

@@ -26,7 +26,6 @@
 
 #include "common.h"
 #include "gemm_family.h"
-#include "fused_layer.h"
 #include "fused_bwd.h"
 #include "fused_fwd.h"
 #include "fused_fwd_bf3.h"
@@ -1125,15 +1124,9 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
       f.sg = act_view(save ? buf->sg + (size_t)l * g.act : nullptr, batch, C, g.Tp);
       launch_gemm_staged(f, 2 * ((C + 31) / 32 * 32), batch, s, f16);
     };
-    // C = K = 64, audio only, fp32: the layer as ONE kernel (fused_layer.h); same bits as the
-    // two-kernel form below (MOVENET_HIP_NO_FUSED_FORWARD=1 keeps the latter: A/B and tests)
-    const bool no_fused = switches().no_fused_forward;
-    // (the layer's weights are re-packed k-major into the z scratch, which this path never
-    // touches otherwise: z stays in LDS)
-    // ... and its persistent successor (fused_fwd.h: weights in registers, 64-column tiles);
-    // MOVENET_HIP_NO_PERSISTENT_FORWARD=1 keeps the per-tile kernel (common.h: Switches)
-    const bool no_persistent = switches().no_persistent_forward;
-    if (C == FL_C && Kc == FL_C && !f16 && !no_fused && !no_persistent &&
+    // C = K = 64, fp32: the layer as ONE kernel (a strip kernel of fused_fwd_bf3.h / fused_fwd.h, or the tile
+    // kernel of fused_fwd.h); MOVENET_HIP_NO_FUSED_FORWARD=1 keeps the two-kernel form below (tests)
+    if (C == FP_C && Kc == FP_C && !f16 && !switches().no_fused_forward &&
         (!has_ctx || (g.Tp <= (1 << 22) && buf->ctx_ld <= (1 << 22)))) {
       FusedFwdPArgs fp;
       if (has_ctx) {  // conditioned layer: the strip kernel with the context as a third K block
@@ -1181,24 +1174,6 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
       A += d;
       continue;
     }
-    if (C == FL_C && Kc == FL_C && !has_ctx && !f16 && !no_fused && (size_t)g.act >= (size_t)g.L * FL_PACK_F) {
-      if (l == 0)
-        for (int ll = 0; ll < g.L; ++ll)
-          hipLaunchKernelGGL(fused_pack_kernel, dim3((FL_PACK_F + 255) / 256), dim3(256), 0, s, p->filter_w[ll],
-                             p->gate_w[ll], p->residual_w[ll], p->skip_w[ll], buf->z + (size_t)ll * FL_PACK_F);
-      FusedLayerArgs fa;
-      fa.t_begin = A + d; fa.t_end = T; fa.d = d; fa.t_skip0 = t_skip0; fa.t_base = g.t_base;
-      fa.first_layer = (l == 0);
-      fa.wpack = buf->z + (size_t)l * FL_PACK_F;
-      fa.br = p->residual_b[l]; fa.bs = p->skip_b[l];
-      fa.xin = xin; fa.xout = xout; fa.skip = skipv;
-      if (l == g.L - 1) fa.xout.p = nullptr;  // the last residual output is never used
-      fa.th = act_view(save ? buf->th + (size_t)l * g.act : nullptr, batch, C, g.Tp);
-      fa.sg = act_view(save ? buf->sg + (size_t)l * g.act : nullptr, batch, C, g.Tp);
-      launch_fused_layer64(fa, batch, s);
-      A += d;
-      continue;
-    }
     if (has_ctx) run_fg(FgOpT<true>()); else run_fg(FgOpT<false>());
     RsOp r;
     r.K = C; r.t_begin = A + d; r.t_end = T; r.C = C; r.Kc = Kc; r.t_skip0 = t_skip0;
@@ -1217,13 +1192,13 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
     h1.K = Kc; h1.t_begin = g.pad; h1.t_end = g.pad + g.S; h1.M = Q; h1.wmat = p->head1_w;
     h1.ldw = Kc; h1.bias = p->head1_b; h1.xin = skipv; h1.yout = a1v; h1.ref = a1v;
     h1.t_out_end = g.pad + g.S; h1.aligned_out = 1;
-    // Q = 256, K = 64: the strip form reads the skip sum once (fused_fwd.h); MOVENET_HIP_NO_DENSE_STRIP=1: A/B
-    const bool strip_ok = Kc == 64 && !f16 && !switches().no_dense_strip;
+    // Q = 256, K = 64: the strip form reads the skip sum once (fused_fwd.h)
+    const bool strip_ok = Kc == 64 && !f16;
     const bool strip = strip_ok && Q == 256;  // (the fp32 strips: Q = 256 only)
     // r3: both head convolutions as strip kernels on the bf16 matrix cores (fused_fwd_bf3.h), their LDS images
     // packed once per call behind the layers' in the z scratch
     const size_t img_off = (size_t)g.L * std::max(FS3_PACK_F, FSC_PACK_F);
-    if (strip_ok && head_q_strip(Q) && forward_bf3_enabled() && head_bf3_enabled() && (size_t)g.act >= img_off + DS3_IMG_F)
+    if (strip_ok && head_q_strip(Q) && forward_bf3_enabled() && (size_t)g.act >= img_off + DS3_IMG_F)
       head_img = buf->z + img_off;
     if (head_img) {
       DenseStripArgs da;
@@ -1248,7 +1223,7 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
     // `out` is the caller's contiguous (B, Q, S_out): column s of the head = out column s - pad
     h2.yout = act_view(out - g.pad, batch, Q, S_out);
     h2.t_out_end = g.pad + S_out; h2.aligned_out = 0;
-    const bool strip2 = Q == 256 && !f16 && !switches().no_dense_strip;
+    const bool strip2 = Q == 256 && !f16;
     if (head_img && S_out > 0) {
       // four row blocks of 64 on the bf16 matrix cores (fused_fwd_bf3.h)
       DenseStripArgs da;
@@ -1369,7 +1344,7 @@ int mvn_backward(const mvn_dims *dims, const mvn_params *p, const mvn_param_grad
   float *bwd_head_img = nullptr;
   {
     const size_t off = (size_t)g.L * std::max(FS3_PACK_F, FSC_PACK_F) + DS3_IMG_F;
-    if (head_q_strip(Q) && Kc == 64 && fwd->z && forward_bf3_enabled() && head_bf3_enabled() && (size_t)g.act >= off + DS3_BWD_IMG_F)
+    if (head_q_strip(Q) && Kc == 64 && fwd->z && forward_bf3_enabled() && (size_t)g.act >= off + DS3_BWD_IMG_F)
       bwd_head_img = fwd->z + off;
   }
   if (!dout) {
@@ -1467,15 +1442,12 @@ int mvn_backward(const mvn_dims *dims, const mvn_params *p, const mvn_param_grad
   //   ev[1]: dfg of this layer ready (s -> s2)
   //   ev[2], ev[3]: WgRs / WgFg done (s2 -> s: the buffers they read may be overwritten)
   SideStream *side = nullptr;
-  // MOVENET_HIP_NO_SIDE_STREAM=1 keeps everything on the caller's stream (profiling: kernel
-  // durations are only comparable when the kernels do not share the machine)
-  const bool no_side = switches().no_side_stream;
   // MOVENET_HIP_NO_FUSED_BACKWARD=1: the two-kernel forms (cross-checks, profiling)
     const bool fused_bwd = !switches().no_fused_backward;
   // (with both fused halves every kernel of the layer loop runs on the caller's stream: no fork,
   // and none of the two event records + waits per layer that go with it -- ~60 gaps of ~8 us per step)
   const bool all_fused = fused_bwd && C == 64 && Kc == 64;  // (conditioned layers too: bwd_dctx_wgctx64_kernel)
-  const bool fork = bias_scratch2 && !no_side && !all_fused;
+  const bool fork = bias_scratch2 && !all_fused;
   hipStream_t s2 = s;
   if (fork) {
     rc = side_stream(&side);
@@ -1708,9 +1680,8 @@ int mvn_backward(const mvn_dims *dims, const mvn_params *p, const mvn_param_grad
     const int chunks64 = (T + EG64_CHUNK - 1) / EG64_CHUNK;
     if (C == 64 && Q % EG64_PARTS == 0 && (size_t)Q / EG64_PARTS * 64 * sizeof(float) <= 64 * 1024 && slab &&
         (size_t)chunks64 * batch * 2 * Q * 64 <= slab_floats) {
-      // MOVENET_HIP_EMBED_GRAD=scalar keeps the LDS read-modify-write kernel (A/B, tests); Q = 256: the product form
-      const bool mfma_form = Q == 256 && !switches().embed_scalar;
-      if (mfma_form) {
+      // Q = 256: the product form; any other Q: the LDS read-modify-write kernel
+      if (Q == 256) {
         hipLaunchKernelGGL(embed_grad64_mfma_kernel, dim3(chunks64, batch), dim3(256), 0, s, index, index_stride,
                            act_view(dxo_p, batch, C, g.Tp), T, slab);
       } else {

@@ -226,7 +226,12 @@ def test_cross_entropy_on_probs_matches_torch_autograd():
     assert not acc.requires_grad
 
 
-@pytest.mark.parametrize("layers,t_len,batch", [((3, 2), 100, 3), ((10, 1), 1024 + 700 + 37, 2), ((6, 2), 64 * 9 + 1, 1)])
+# large enough for the split halves' per-chunk slabs and bias partials (the smaller shapes are not)
+HALVES_SHAPE = ((3, 2), 6000, 8)
+
+
+@pytest.mark.parametrize("layers,t_len,batch", [((3, 2), 100, 3), ((10, 1), 1024 + 700 + 37, 2), ((6, 2), 64 * 9 + 1, 1),
+                                                HALVES_SHAPE])
 def test_fused_backward_kernels_match_two_kernel_forms_and_oracle(monkeypatch, layers, t_len, batch):
     """C = K = 64 takes the fused backward (r4: csrc/fused_bwd_l.h, ONE kernel per layer with the input
     gradient in scatter form; before: csrc/fused_bwd.h, dz + residual/skip weight gradients, then dx +
@@ -261,8 +266,10 @@ def test_fused_backward_kernels_match_two_kernel_forms_and_oracle(monkeypatch, l
         monkeypatch.delenv("MOVENET_HIP_BWD_FORM", raising=False)
         from movenet_amd import _native as N
         # (a silent fall-back to a slower form must not pass for the form under test)
-        # ("split" falls to the generic kernels where its per-chunk slabs do not fit these small tensors' scratch)
-        assert N.lib().mvn_last_backward_form() in {"one": (N.BWD_FORM_ONE,), "split": (N.BWD_FORM_HALVES, N.BWD_FORM_GENERIC),
+        # ("split" falls to the generic kernels where its per-chunk slabs do not fit the small tensors' scratch;
+        # HALVES_SHAPE must take the halves, or the split switch would cross-check nothing)
+        split = (N.BWD_FORM_HALVES,) if (layers, t_len, batch) == HALVES_SHAPE else (N.BWD_FORM_HALVES, N.BWD_FORM_GENERIC)
+        assert N.lib().mvn_last_backward_form() in {"one": (N.BWD_FORM_ONE,), "split": split,
                                                     "plain": (N.BWD_FORM_GENERIC,)}[form]
         return {k: (None if p.grad is None else p.grad.cpu()) for k, p in m.named_parameters()}
 
@@ -322,9 +329,9 @@ def test_embedding_gradient_with_repeated_classes(pattern):
 
 
 @pytest.mark.parametrize("layers,t_len,batch", [((3, 2), 100, 3), ((10, 1), 1024 + 700 + 37, 2), ((6, 2), 64 * 9 + 1, 17)])
-def test_persistent_forward_kernel_matches_per_tile_kernel_and_oracle(monkeypatch, layers, t_len, batch):
-    """C = K = 64 takes the persistent forward layer kernel (csrc/fused_fwd.h); the per-tile
-    kernel (MOVENET_HIP_NO_PERSISTENT_FORWARD=1) sums each f/g value in one 128-deep chain where
+def test_persistent_forward_kernel_matches_two_kernel_form_and_oracle(monkeypatch, layers, t_len, batch):
+    """C = K = 64 takes the persistent forward layer kernel (csrc/fused_fwd.h); the two-kernel
+    form (MOVENET_HIP_NO_FUSED_FORWARD=1) sums each f/g value in one 128-deep chain where
     this one adds two 64-deep halves: equal to fp32 rounding.  Ragged lengths put t_begin, RF - 1
     and T inside tiles; batch 17 makes the one-round chunking uneven.  Inference (no tanh/sigmoid
     saved) and training mode, logits and probabilities."""
@@ -336,11 +343,11 @@ def test_persistent_forward_kernel_matches_per_tile_kernel_and_oracle(monkeypatc
     dims = O.Dims(**cfg)
     x = one_hot(synthetic_indices(batch, t_len, 256, 78), 256)
 
-    def outputs(per_tile, train):
-        if per_tile:
-            monkeypatch.setenv("MOVENET_HIP_NO_PERSISTENT_FORWARD", "1")
+    def outputs(two_kernel, train):
+        if two_kernel:
+            monkeypatch.setenv("MOVENET_HIP_NO_FUSED_FORWARD", "1")
         else:
-            monkeypatch.delenv("MOVENET_HIP_NO_PERSISTENT_FORWARD", raising=False)
+            monkeypatch.delenv("MOVENET_HIP_NO_FUSED_FORWARD", raising=False)
         m = _model(cfg, sd)
         m.train(train)
         with torch.set_grad_enabled(train):
@@ -349,10 +356,9 @@ def test_persistent_forward_kernel_matches_per_tile_kernel_and_oracle(monkeypatc
     for train in (False, True):
         a, b_ = outputs(False, train), outputs(True, train)
         assert rel_err(a, b_) < 2e-6, train
-        # the strip kernel is the default; its tile-kernel siblings (32 / 64 columns) must agree too
-        for tile in ("32", "64"):
-            monkeypatch.setenv("MOVENET_HIP_FORWARD_TILE", tile)
-            assert rel_err(outputs(False, train), b_) < 2e-6, (train, tile)
+        # the strip kernel is the default; its tile-kernel sibling (32 columns) must agree too
+        monkeypatch.setenv("MOVENET_HIP_FORWARD_TILE", "1")
+        assert rel_err(outputs(False, train), b_) < 2e-6, (train, "tile")
         monkeypatch.delenv("MOVENET_HIP_FORWARD_TILE")
         # ... and so must the strip kernel on fp32 MFMAs (the default forms each fp32 product from six bf16 MFMAs)
         monkeypatch.setenv("MOVENET_HIP_FORWARD_MFMA", "f32")
@@ -368,7 +374,7 @@ def test_bf16x3_forward_is_fp32_class(monkeypatch, gain):
     """csrc/fused_fwd_bf3.h: the audio-only forward layer forms every fp32 product on the bf16 matrix cores --
     operands split EXACTLY into three bf16 planes, six MFMAs per block, fp32 accumulation.  Measured against the
     same layer on fp32 MFMAs in TWO summation orders (the strip kernel, MOVENET_HIP_FORWARD_MFMA=f32, and the
-    per-tile kernel, MOVENET_HIP_NO_PERSISTENT_FORWARD=1), at a size that takes the packed weight images of the layers
+    two-kernel form, MOVENET_HIP_NO_FUSED_FORWARD=1), at a size that takes the packed weight images of the layers
     AND of the head's bf16 x 3 strip kernels (30 layers, 5 x 5000 samples, 1929 ragged output columns): logits, loss and every parameter gradient (the backward pass reads the tanh / sigmoid saved by
     the forward under test) differ from the fp32 strip by no more than the two fp32 forms differ from each other
     (x 3; floor: 2e-6 of range for logits, 1e-5 for gradients).  Gain 4 makes the 30-layer stack amplify last-bit
@@ -381,11 +387,11 @@ def test_bf16x3_forward_is_fp32_class(monkeypatch, gain):
 
     def run(form):
         monkeypatch.delenv("MOVENET_HIP_FORWARD_MFMA", raising=False)
-        monkeypatch.delenv("MOVENET_HIP_NO_PERSISTENT_FORWARD", raising=False)
+        monkeypatch.delenv("MOVENET_HIP_NO_FUSED_FORWARD", raising=False)
         if form == "f32 strip":
             monkeypatch.setenv("MOVENET_HIP_FORWARD_MFMA", "f32")
-        elif form == "f32 tile":
-            monkeypatch.setenv("MOVENET_HIP_NO_PERSISTENT_FORWARD", "1")
+        elif form == "f32 two-kernel":
+            monkeypatch.setenv("MOVENET_HIP_NO_FUSED_FORWARD", "1")
         m = _model(cfg, sd)
         m.train(True)
         logits = m(x, output_unnormalized=False)  # raw logits (Q1: the reference's flag is inverted)
@@ -397,8 +403,8 @@ def test_bf16x3_forward_is_fp32_class(monkeypatch, gain):
 
     la, loss_a, ga = run("bf16x3")
     lb, loss_b, gb = run("f32 strip")
-    lc, loss_c, gc = run("f32 tile")
-    monkeypatch.delenv("MOVENET_HIP_NO_PERSISTENT_FORWARD", raising=False)
+    lc, loss_c, gc = run("f32 two-kernel")
+    monkeypatch.delenv("MOVENET_HIP_NO_FUSED_FORWARD", raising=False)
     assert torch.isfinite(la).all() and la.abs().max() > 1.0
     assert rel_err(la, lb) < max(2e-6, 3 * rel_err(lc, lb)), (rel_err(la, lb), rel_err(lc, lb))
     rms = lambda u, v: float((u.double() - v.double()).pow(2).mean().sqrt())  # noqa: E731
