@@ -250,6 +250,18 @@ int mvn_forward_f16(const mvn_dims *dims, const mvn_params *params, const int32_
                     int index_stride, int batch, int t_len, const mvn_fwd_buffers *buf, float *out,
                     int normalize, int remove_last, int save, void *stream);
 
+/* mvn_forward with BF16 OPERANDS and FP32 ACCUMULATION in the products of the gated layers (opt-in
+ * mixed-precision training; the reference trains under torch.autocast, movenet/trainer.py:124):
+ * x(t), x(t - d), z = tanh sigmoid and the four weight tensors of each layer are rounded to bf16
+ * (round to nearest even) as they are staged and multiplied by ONE v_mfma_f32_32x32x16_bf16 per
+ * block; the embedding / causal conv, biases, gating, residual adds, the skip sum, the head, the
+ * softmax and every tensor in HBM stay fp32.  Same arguments and buffers as mvn_forward; `save`
+ * keeps what mvn_backward_bf16 differentiates.  Audio-only, residual_channels = skip_channels = 64,
+ * any input_channels; anything else (or a context) returns MVN_ERR_UNSUPPORTED and launches nothing. */
+int mvn_forward_bf16(const mvn_dims *dims, const mvn_params *params, const int32_t *index,
+                     int index_stride, int batch, int t_len, const mvn_fwd_buffers *buf, float *out,
+                     int normalize, int remove_last, int save, void *stream);
+
 /* Gradients, same layouts as mvn_params (members may not be NULL except ctx_*);
  * mvn_backward ACCUMULATES into them (zero them first for a fresh gradient). */
 typedef struct mvn_param_grads {
@@ -294,14 +306,26 @@ int mvn_backward(const mvn_dims *dims, const mvn_params *params, const mvn_param
                  const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
                  const float *dout, int normalize, int remove_last, void *stream);
 
+/* The backward of mvn_forward_bf16: mvn_backward's arguments and buffers, with the layers' products on
+ * bf16 operands (dxo, dskip and the weights in the dz / input-gradient products; df | dg, x and z in
+ * the weight-gradient products) and fp32 accumulation; the head, the embedding gradient and every
+ * buffer stay fp32.  Same dims as mvn_forward_bf16; a batch / length whose scratch the bf16 layer
+ * kernel cannot place returns MVN_ERR_UNSUPPORTED before anything is launched. */
+int mvn_backward_bf16(const mvn_dims *dims, const mvn_params *params, const mvn_param_grads *grads,
+                      const int32_t *index, int index_stride, int batch, int t_len,
+                      const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
+                      const float *dout, int normalize, int remove_last, void *stream);
+
 /* Diagnostic: which form the layer loop of the process's last mvn_backward took -- 0 none yet,
  * 1 the generic two-kernel forms (any dims), 2 the two fused halves per layer (C = K = 64,
  * csrc/fused_bwd.h), 3 ONE kernel per layer with the input gradient in scatter form
- * (csrc/fused_bwd_l.h, the default at C = K = 64).  Tests assert on it so that a silent
+ * (csrc/fused_bwd_l.h, the default at C = K = 64), 4 the bf16 layer kernel of mvn_backward_bf16
+ * (csrc/fused_bf16.h).  Tests assert on it so that a silent
  * fall-back to a slower form cannot pass for the fast one. */
 #define MVN_BWD_FORM_GENERIC 1
 #define MVN_BWD_FORM_HALVES 2
 #define MVN_BWD_FORM_ONE 3
+#define MVN_BWD_FORM_BF16 4
 int mvn_last_backward_form(void);
 
 /* ------------------------------------------------------------------------

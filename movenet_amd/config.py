@@ -155,7 +155,14 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--log_video", type=_flag, default=False)
     a("--wandb_api_key", type=str, default="")
     a("--wandb_project", type=str, default="dance2music-pl-testing")
+    # Lightning's Trainer(precision=...): 32 (exact fp32, the default) or bf16 (mixed precision,
+    # Trainer's docstring); passed to train_model, not part of TrainingConfig
+    a("--precision", type=_precision, default=32, choices=[32, "bf16"])
     return p
+
+
+def _precision(x):
+    return 32 if x == "32" else x
 
 
 def config_from_args(args) -> TrainingConfig:

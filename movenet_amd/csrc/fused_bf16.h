@@ -1,0 +1,663 @@
+// bf16 mixed precision for the audio-only C = K = 64 layer stack (mvn_forward_bf16 / mvn_backward_bf16): every product
+// of a gated layer takes its operands rounded ONCE to bf16 (round to nearest even: v_cvt_pk_bf16_f32, which keeps a NaN
+// a NaN) and runs as ONE v_mfma_f32_32x32x16_bf16 per 32 x 32 x 16 block with fp32 accumulation, where the exact
+// kernels (fused_fwd_bf3.h, fused_bwd_l.h) split each fp32 operand into three bf16 planes and issue six.  Rounded:
+//   forward   x(t), x(t - d) and z = tanh sigmoid as products' inputs, the four weight tensors;
+//   backward  dxo, dskip and the four weight tensors (dz and input-gradient products), df | dg, x and z (weight
+//             gradients).
+// Everything else stays fp32: biases, the gate arithmetic and its derivative, the residual add, the skip sum, the bias
+// gradients, every tensor in HBM (saved activations, A' / P0, the weight-gradient slabs) and the reductions.  The two
+// kernels below keep the dataflow, the buffers and the launch geometry of their exact twins; what they drop is the split
+// (44 vector instructions per eight values there, four v_cvt_pk_bf16_f32 here) and two thirds of the weight images.
+#pragma once
+#include "fused_bwd_l.h"
+
+namespace mvn {
+
+typedef float f32x2_b16 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2_b16 __attribute__((ext_vector_type(2)));
+
+// {bf16(a), bf16(b)} in one register, a in the low half (round to nearest even)
+__device__ __forceinline__ unsigned b16_pack2(float a, float b) {
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_b16{a, b}, bf16x2_b16));
+}
+__device__ __forceinline__ u32x4 b16_pack8(const float *x) {
+  return u32x4{b16_pack2(x[0], x[1]), b16_pack2(x[2], x[3]), b16_pack2(x[4], x[5]), b16_pack2(x[6], x[7])};
+}
+__device__ __forceinline__ unsigned short b16_one(float w) { return __builtin_bit_cast(unsigned short, (__bf16)w); }
+#define B16_MFMA(acc_, a_, b_) \
+  acc_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a_), __builtin_bit_cast(bf16x8, b_), acc_, 0, 0, 0)
+
+// ----------------------------------------------------------------------------------------
+// Forward: fused_layer64s_bf3_kernel with one plane.  LDS image [block][k-step][lane][8 bf16] (1 KB per block and
+// k-step): W1 4 x 8 KB, W2 4 x 4 KB, then br | bs as floats -- 48.5 KB against 144.5.
+// ----------------------------------------------------------------------------------------
+constexpr int FB16_W1_BYTES = 4 * 8 * 1024, FB16_W2_BYTES = 4 * 4 * 1024;
+constexpr int FB16_LDS_BYTES = FB16_W1_BYTES + FB16_W2_BYTES + 128 * 4;
+constexpr int FB16_PACK_F = FB16_LDS_BYTES / 4;
+
+// fs3_stage_weights' element order, one bf16 per weight
+__device__ __forceinline__ void fb16_stage_weights(unsigned char *img, const float *wf, const float *wg, const float *wr,
+                                                   const float *ws, const float *br, const float *bs, int tid, int nthreads) {
+  unsigned short *W1 = (unsigned short *)img;
+  unsigned short *W2 = (unsigned short *)(img + FB16_W1_BYTES);
+  float *BI = (float *)(img + FB16_W1_BYTES + FB16_W2_BYTES);
+  for (int sI = tid; sI < 2 * 8192; sI += nthreads) {
+    const int g = sI >> 13, r = sI & 8191;  // g: 0 filter, 1 gate; source (out, in, tap)
+    const int tap = r & 1, kc = (r >> 1) & 63, cm = r >> 7;
+    const int lhs = (kc >> 2) & 1, j = (kc & 3) + 4 * (kc >> 3);
+    const int blk = 2 * g + (cm >> 5), ln = (cm & 31) + 32 * lhs, ks = (tap ? 0 : 4) + (j >> 3);
+    W1[((blk * 8 + ks) * 64 + ln) * 8 + (j & 7)] = b16_one((g ? wg : wf)[r]);
+  }
+  for (int sI = tid; sI < 2 * 4096; sI += nthreads) {
+    const int g = sI >> 12, r = sI & 4095;  // g: 0 residual, 1 skip; source (out, in)
+    const int kc = r & 63, m2 = r >> 6;
+    const int lhs = (kc >> 2) & 1, j = (kc & 3) + 4 * (kc >> 3);
+    const int blk = 2 * g + (m2 >> 5), ln = (m2 & 31) + 32 * lhs, ks = j >> 3;
+    W2[((blk * 4 + ks) * 64 + ln) * 8 + (j & 7)] = b16_one((g ? ws : wr)[r]);
+  }
+  for (int i = tid; i < 128; i += nthreads) BI[i] = i < 64 ? br[i] : bs[i - 64];
+}
+
+__global__ __launch_bounds__(256) void fb16_pack_kernel(Fs3PackArgs p, float *dst) {
+  const int l = blockIdx.y;
+  fb16_stage_weights((unsigned char *)(dst + (size_t)l * FB16_PACK_F), p.wf[l], p.wg[l], p.wr[l], p.ws[l], p.br[l], p.bs[l],
+                     blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
+}
+
+// acc[blk] += W[blk] (NKS k-steps of the image at LDS byte address wa) x B, B value e of k-step ks = bval(ks, e)
+template <int NKS, class BV>
+__device__ __forceinline__ void fb16_product(f32x16 (&acc)[4], unsigned wa, BV bval) {
+  typedef __attribute__((address_space(3))) u32x4 lds_u4;
+#pragma unroll
+  for (int ks = 0; ks < NKS; ++ks) {
+    u32x4 bq;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bq[i] = b16_pack2(bval(ks, 2 * i), bval(ks, 2 * i + 1));
+#pragma unroll
+    for (int blk = 0; blk < 4; ++blk) {
+      const u32x4 aq = *(const lds_u4 *)(uintptr_t)(wa + 1024u * (unsigned)(blk * NKS + ks));
+      B16_MFMA(acc[blk], aq, bq);
+    }
+  }
+}
+
+__global__ __launch_bounds__(512, 1) void fused_layer64s_bf16_kernel(FusedFwdPArgs a, int chunks_per_b, int chunk_t) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char fb16_lds[];
+  const float *BI = (const float *)(fb16_lds + FB16_W1_BYTES + FB16_W2_BYTES);  // br | bs
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.x / chunks_per_b, ch = blockIdx.x - b * chunks_per_b;
+  const int li = lane & 31, lh = lane >> 5;
+  const int tb = (a.t_begin & ~TILE_ALIGN) + ch * chunk_t, te = min(a.t_end, tb + chunk_t);
+  const int skip_lo = max(a.t_begin, a.t_skip0);
+  // ---- weights into LDS: the image fb16_pack_kernel wrote once per forward call (a linear copy), or converted here
+  if (a.wpack) {
+    typedef float f4_ __attribute__((ext_vector_type(4)));
+    constexpr int N16 = FB16_LDS_BYTES / 16, PER = (N16 + 511) / 512;
+    const f4_ *src = (const f4_ *)a.wpack;
+    f4_ v[PER];
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int at = tid + 512 * i;
+      if (at < N16) v[i] = src[at];
+    }
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int at = tid + 512 * i;
+      if (at < N16) ((f4_ *)fb16_lds)[at] = v[i];
+    }
+  } else {
+    fb16_stage_weights(fb16_lds, a.wf, a.wg, a.wr, a.ws, a.br, a.bs, tid, 512);
+  }
+  __syncthreads();
+  const unsigned w1a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)fb16_lds + 16u * lane;
+  const unsigned w2a = w1a + (unsigned)FB16_W1_BYTES;
+  const int cbase = 4 * lh;
+
+  constexpr int RSRC = 0x00020000;  // raw buffer, 32-bit data format (gfx9)
+  const __amdgpu_buffer_rsrc_t xb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.xin.p + (size_t)b * a.xin.sb), 0, 0x7FFFFFFF, RSRC);
+  const __amdgpu_buffer_rsrc_t thb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.th.p + (size_t)b * a.th.sb), 0, 0x7FFFFFFF, RSRC);
+  const __amdgpu_buffer_rsrc_t sgb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.sg.p + (size_t)b * a.sg.sb), 0, 0x7FFFFFFF, RSRC);
+  const __amdgpu_buffer_rsrc_t xob = __builtin_amdgcn_make_buffer_rsrc((void *)(a.xout.p + (size_t)b * a.xout.sb), 0, 0x7FFFFFFF, RSRC);
+  const __amdgpu_buffer_rsrc_t skb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.skip.p + (size_t)b * a.skip.sb - a.t_base), 0, 0x7FFFFFFF, RSRC);
+  const bool save = a.th.p != nullptr, has_out = a.xout.p != nullptr;
+  int xld4 = 4 * a.xin.ld, thld4 = 4 * a.th.ld, xold4 = 4 * a.xout.ld, skld4 = 4 * a.skip.ld;
+
+  // (the strip schedule of fused_layer64s_bf3_kernel: x(t) one strip ahead, x(t - d) at the top of the strip, the skip
+  // accumulator's old values under the second product; lanes that must not store carry an offset past the resource)
+  auto column = [&](int t0_, bool &live_, int &tc_) {
+    const int t_ = t0_ + li;
+    live_ = t_ >= a.t_begin && t_ < te;
+    tc_ = live_ ? t_ : a.t_begin;  // (clamped: dead lanes read a valid column, zeroed afterwards)
+  };
+  float xb1[32];  // x(t) of the current strip: B operand of k-steps 0..3, residual input
+  {
+    bool lv;
+    int tcc;
+    column(tb + 32 * wave, lv, tcc);
+    const int o1 = 4 * (cbase * a.xin.ld + tcc);
+    FS_FENCE(xld4);
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+      const float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, o1, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
+      xb1[j] = lv ? v : 0.f;
+    }
+  }
+
+  constexpr int FS_OOB = (int)0x80000000;
+  for (int t0 = tb + 32 * wave; t0 < te; t0 += 32 * 8) {
+    const int t = t0 + li;
+    bool live;
+    int tc;
+    column(t0, live, tc);
+    const bool skip_live = t >= skip_lo && t < te;
+    const int ox0 = 4 * (cbase * a.xin.ld + tc - a.d);
+    const int oth = (save && live) ? 4 * (cbase * a.th.ld + tc) : FS_OOB, oxo = 4 * (cbase * a.xout.ld + tc);
+    const int osk = 4 * (cbase * a.skip.ld + (skip_live ? t : skip_lo));
+    float xn1[32];  // x(t) of the NEXT strip
+    float xa0[32];  // x(t - d): B operand of k-steps 4..7; later the skip accumulator's old values
+    FS_FENCE(xld4);
+#pragma unroll
+    for (int j = 0; j < 32; ++j)
+      xa0[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, ox0, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
+    if (!(t0 >= a.t_begin && t0 + 32 <= te)) {
+#pragma unroll
+      for (int j = 0; j < 32; ++j) xa0[j] = live ? xa0[j] : 0.f;
+    }
+    // ---- f | g: four 32 x 32 blocks (f c<32, f c>=32, g c<32, g c>=32), K = 128 = 8 k-steps, the x(t) half first
+    f32x16 acc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    fb16_product<8>(acc, w1a, [&](int ks, int e) { return ks < 4 ? xb1[8 * ks + e] : xa0[8 * (ks - 4) + e]; });
+    // ---- gate in registers (fp32); tanh / sigmoid leave; z in accumulator order = the next B operand
+    float z[32];
+    FS_FENCE(thld4);
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float tv = tanh_fast(acc[h][r]);
+        const float sv = sigmoid_fast(acc[2 + h][r]);
+        z[16 * h + r] = tv * sv;
+        const int c0 = 32 * h + (r & 3) + 8 * (r >> 2);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(tv), thb, oth, c0 * thld4, FS_AUX_SAVE);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sv), sgb, oth, c0 * thld4, FS_AUX_SAVE);
+      }
+    FS_FENCE(skld4);
+    if (!a.first_layer) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          xa0[16 * h + r] = __uint_as_float(
+              __builtin_amdgcn_raw_buffer_load_b32(skb, osk, (32 * h + (r & 3) + 8 * (r >> 2)) * skld4, 0));
+    }
+    if (t0 + 32 * 8 < te) {
+      bool lv;
+      int tcc;
+      column(t0 + 32 * 8, lv, tcc);
+      const int o1 = 4 * (cbase * a.xin.ld + tcc);
+      FS_FENCE(xld4);
+#pragma unroll
+      for (int j = 0; j < 32; ++j)
+        xn1[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, o1, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
+      if (!(t0 + 32 * 8 >= a.t_begin && t0 + 32 * 8 + 32 <= te)) {
+#pragma unroll
+        for (int j = 0; j < 32; ++j) xn1[j] = lv ? xn1[j] : 0.f;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 32; ++j) xn1[j] = 0.f;
+    }
+    // ---- residual | skip: four blocks (res c<32, res c>=32, skip k<32, skip k>=32), K = 64 = 4 k-steps
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    fb16_product<4>(acc, w2a, [&](int ks, int e) { return z[8 * ks + e]; });
+    // ---- x' = (y + br) + x(t); skip (+)= y + bs, columns t - t_base, live from skip_lo
+    FS_FENCE(xold4);
+    FS_FENCE(skld4);
+    {
+      const int oxo_m = (has_out && live) ? oxo : FS_OOB, osk_m = skip_live ? osk : FS_OOB;
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int c0 = 32 * h + (r & 3) + 8 * (r >> 2);
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((acc[h][r] + BI[c0 + cbase]) + xb1[16 * h + r]), xob, oxo_m,
+                                                c0 * xold4, 0);
+        }
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int k0 = 32 * h + (r & 3) + 8 * (r >> 2);
+          const float v = acc[2 + h][r] + BI[64 + k0 + cbase];
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a.first_layer ? v : xa0[16 * h + r] + v), skb, osk_m, k0 * skld4, 0);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 32; ++j) xb1[j] = xn1[j];
+  }
+}
+
+// the LDS images of layers 0 .. L-1 into `dst` (L x FB16_PACK_F floats), one launch per 32 layers
+static int launch_fb16_pack(const mvn_params *p, int L, float *dst, hipStream_t s) {
+  for (int l0 = 0; l0 < L; l0 += FS3_PACK_LAYERS) {
+    const int n = std::min(FS3_PACK_LAYERS, L - l0);
+    Fs3PackArgs pa;
+    for (int i = 0; i < FS3_PACK_LAYERS; ++i) {
+      const int l = l0 + std::min(i, n - 1);
+      pa.wf[i] = p->filter_w[l]; pa.wg[i] = p->gate_w[l]; pa.wr[i] = p->residual_w[l]; pa.ws[i] = p->skip_w[l];
+      pa.br[i] = p->residual_b[l]; pa.bs[i] = p->skip_b[l];
+    }
+    hipLaunchKernelGGL(fb16_pack_kernel, dim3(8, n), dim3(256), 0, s, pa, dst + (size_t)l0 * FB16_PACK_F);
+  }
+  return check_hip(hipGetLastError(), "fb16_pack");
+}
+static int launch_fused_layer64s_bf16(const FusedFwdPArgs &a, int batch, hipStream_t s) {
+  const int nt = a.t_end - (a.t_begin & ~TILE_ALIGN);
+  if (a.t_end <= a.t_begin || batch <= 0) return MVN_OK;
+  int chunks, chunk_t;
+  fb_chunks(nt, batch, 1, &chunks, &chunk_t, 256);  // a chunk: whole rounds of the 8 waves' strips
+  const void *fn = (const void *)fused_layer64s_bf16_kernel;
+  const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(fused_layer64s_bf16)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(fused_layer64s_bf16_kernel, dim3(chunks * batch), dim3(512), FB16_LDS_BYTES, s, a, chunks, chunk_t);
+  return MVN_OK;
+}
+
+// ----------------------------------------------------------------------------------------
+// Backward: bwd_layer64_kernel<false> with one plane -- same roles, tiles, barriers, scatter outputs (A', P0) and slab /
+// bias-partial formats (reduce_layer64_kernel and bwd_scatter_combine_kernel are shared).  Per slot: the LDS reads of the
+// next operand, four conversions, ONE MFMA.  [Wr | Ws]^T is a 16 KB image (48 KB as planes), the tap weights of a wave
+// 16 registers (48): 118 KB of LDS in all.
+// ----------------------------------------------------------------------------------------
+constexpr int FBL16_WIMG_BYTES = 2 * 8 * 1024;  // [c block][k-step][lane][8 bf16]
+constexpr int FBL16_LDS_BYTES = 3 * FBL_TILE_F * 4 + FBL16_WIMG_BYTES;
+
+__global__ __launch_bounds__(512, 1) void bwd_layer64_bf16_kernel(FusedBwdLArgs a, int chunks_per_b, int chunk_t,
+                                                                 float *__restrict__ rs_bias_part, float *__restrict__ rs_part,
+                                                                 float *__restrict__ fg_part) {
+  constexpr int C = FB_C, LD = W2_LD, TT = W2_T;
+  extern __shared__ __attribute__((aligned(16))) float fbl16_lds[];
+  float (*U)[LD] = (float (*)[LD])fbl16_lds;                      // [dxo; dskip], then [x(t - d); x(t)]
+  float (*Gt)[LD] = (float (*)[LD])(fbl16_lds + FBL_TILE_F);      // tanh | sigmoid, then df | dg
+  float (*O)[LD] = (float (*)[LD])(fbl16_lds + 2 * FBL_TILE_F);   // dxo -> A' | P0
+  unsigned short *wimg = (unsigned short *)(fbl16_lds + 3 * FBL_TILE_F);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.x / chunks_per_b, ch = blockIdx.x - b * chunks_per_b;
+  const int li = lane & 31, lh = lane >> 5, h4 = 4 * lh;
+  const int tb = (a.t_lo & ~TILE_ALIGN) + ch * chunk_t, te = min(a.t_end, tb + chunk_t);
+  const int skip_lo = max(a.t_lo, a.t_skip0);
+  const bool has_dxo = a.ga.p != nullptr;
+
+  // ---- [Wr | Ws]^T as the dz product's A operand: lane -> row c = 32 cb + (lane & 31), element j of k-step ks ->
+  // o = 16 ks + 8 (lane >> 5) + j (o < 64: residual rows, else skip rows)
+  for (int i = tid; i < 2 * C * C; i += 512) {
+    const int o = i >> 6, c = i & 63;
+    const float w = o < C ? a.wr[(size_t)o * C + c] : a.ws[(size_t)(o - C) * C + c];
+    wimg[((((c >> 5) * 8 + (o >> 4)) * 64 + (c & 31) + 32 * ((o >> 3) & 1)) * 8) + (o & 7)] = b16_one(w);
+  }
+  const unsigned wa0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned short *)wimg + 16u * lane;
+
+  // ---- phase-2 roles: tap half, K half, channel block; B operand W_tap[o][32 wc + li] for o = 64 kh + 16 j + 8 lh + e
+  const int half = wave >> 2, kh = (wave >> 1) & 1, wc = wave & 1;
+  u32x4 wp[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float wv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int o = 64 * kh + 16 * j + 8 * lh + e;
+      const float *src = o < C ? a.wf : a.wg;
+      wv[e] = src[((size_t)(o & (C - 1)) * C + 32 * wc + li) * 2 + (half ? 0 : 1)];
+    }
+    wp[j] = b16_pack8(wv);
+  }
+  const int wm = wave >> 1, wn = wave & 1;  // filter / gate weight gradient: rows [32 wm, +32), columns [64 wn, +64)
+  f32x16 accw[2], accr;                     // accr: residual / skip weight gradient, block (rows [32 wm, +32), channels [32 wn, +32))
+#pragma unroll
+  for (int r = 0; r < 16; ++r) accw[0][r] = accw[1][r] = accr[r] = 0.f;
+  // phase-1 roles: dz block (channels [32 cb1, +32), steps [32 tq1, +32)) over the K half kh1 of the tile's 128 rows
+  const int kh1 = wave >> 2, tq1 = (wave >> 1) & 1, cb1 = wave & 1;
+  float *Zx = &O[C][0];  // the first K halves' partial dz in the P0 staging rows, idle in phase 1
+
+  // ---- staging (bwd_layer64_kernel's): thread -> rows (tid >> 4) + 32 p, columns 4 (tid & 15) .. +3
+  const int srow = tid >> 4, st = 4 * (tid & 15);
+  f4 r_ga[2], r_gp[2], r_ds[2], r_th[2], r_sg[2], r_x[4];
+  float bsum[4] = {0.f, 0.f, 0.f, 0.f};
+  bool z_ga = false, z_ds = false;
+  const __amdgpu_buffer_rsrc_t gab = fb_rsrc(a.ga.p + (size_t)b * a.ga.sb);
+  const __amdgpu_buffer_rsrc_t gpb = fb_rsrc(a.gp.p + (size_t)b * a.gp.sb);
+  const __amdgpu_buffer_rsrc_t dskb = fb_rsrc(a.dskip.p + (size_t)b * a.dskip.sb);
+  const __amdgpu_buffer_rsrc_t thb = fb_rsrc(a.th.p + (size_t)b * a.th.sb);
+  const __amdgpu_buffer_rsrc_t sgb = fb_rsrc(a.sg.p + (size_t)b * a.sg.sb);
+  const __amdgpu_buffer_rsrc_t xinb = fb_rsrc(a.xin.p + (size_t)b * a.xin.sb);
+  const __amdgpu_buffer_rsrc_t oab = fb_rsrc(a.oa.p + (size_t)b * a.oa.sb);
+  const __amdgpu_buffer_rsrc_t opb = fb_rsrc(a.op.p + (size_t)b * a.op.sb);
+  const int vo_t = 4 * (srow * a.th.ld + st), vo_ds = 4 * (srow * a.dskip.ld + st);
+  auto interior = [&](int t0) {
+    const bool x_full = t0 >= a.t_lo && t0 + TT <= te;
+    const bool ga_ok = !has_dxo || t0 >= a.up_lo || t0 + TT <= a.up_lo;
+    const bool gp_ok = !has_dxo || t0 + TT + a.up_d <= a.t_end || t0 + a.up_d >= a.t_end;
+    const bool s_ok = t0 >= skip_lo || t0 + TT <= skip_lo;
+    return x_full && ga_ok && gp_ok && s_ok;
+  };
+  auto gload_r_part = [&](int t0, int part) {  // part 0..4: A', P0 (shifted), dskip, tanh, sigmoid of tile t0
+    int ld_t = 4 * a.th.ld, ld_ds = 4 * a.dskip.ld;
+    asm volatile("" : "+s"(ld_t), "+s"(ld_ds));
+    const int c4 = 4 * t0;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      if (part == 0) {
+        r_ga[p] = (has_dxo && t0 >= a.up_lo) ? fb_load16(gab, vo_t, 32 * p * ld_t + c4) : fb_load16(thb, vo_t, c4);
+      } else if (part == 1) {
+        r_gp[p] = (has_dxo && t0 + a.up_d < a.t_end) ? fb_load16(gpb, vo_t, 32 * p * ld_t + c4 + 4 * a.up_d) : kZero4;
+      } else if (part == 2) {
+        r_ds[p] = t0 >= skip_lo ? fb_load16(dskb, vo_ds, 32 * p * ld_ds + c4 - 4 * a.t_base) : fb_load16(sgb, vo_t, c4);
+      } else if (part == 3) {
+        r_th[p] = fb_load16(thb, vo_t, 32 * p * ld_t + c4);
+      } else {
+        r_sg[p] = fb_load16(sgb, vo_t, 32 * p * ld_t + c4);
+      }
+    }
+  };
+  auto gload_r_edge = [&](int t0) {
+    int srow_q = srow;
+    asm volatile("" : "+v"(srow_q));
+    const int t = t0 + st;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int row = 32 * p + srow_q;
+      r_ga[p] = has_dxo ? ld4_edge(a.ga.at(b, row, 0), t, a.up_lo, te) : kZero4;
+      r_gp[p] = has_dxo ? ld4_edge(a.gp.at(b, row, 0) + a.up_d, t, a.t_lo, min(a.t_end - a.up_d, te)) : kZero4;
+    }
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int row = 32 * p + srow_q;
+      r_ds[p] = ld4_edge(a.dskip.at(b, row, 0) - a.t_base, t, skip_lo, te);
+      r_th[p] = ld4_edge(a.th.at(b, row, 0), t, a.t_lo, te);
+      r_sg[p] = ld4_edge(a.sg.at(b, row, 0), t, a.t_lo, te);
+    }
+  };
+  auto set_zero_flags = [&](int t0, bool inter) {
+    z_ga = inter && (!has_dxo || t0 < a.up_lo);
+    z_ds = inter && t0 < skip_lo;
+  };
+  auto gload_x = [&](int t0) {  // rows [0, 64): x(t - d); [64, 128): x(t)
+    if (t0 >= a.t_lo && t0 + TT <= te) {
+      int ld_x = 4 * a.th.ld;
+      asm volatile("" : "+s"(ld_x));
+#pragma unroll
+      for (int p = 0; p < 4; ++p) r_x[p] = fb_load16(xinb, vo_t, 32 * (p & 1) * ld_x + 4 * t0 - (p < 2 ? 4 * a.d : 0));
+    } else {
+      int srow_q = srow;
+      asm volatile("" : "+v"(srow_q));
+      const int t = t0 + st;
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+        r_x[p] = ld4_edge(a.xin.at(b, 32 * (p & 1) + srow_q, 0) - (p < 2 ? a.d : 0), t, a.t_lo, te);
+    }
+  };
+  auto lstore_r = [&]() {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const f4 dxo = z_ga ? r_gp[p] : f4_add(r_ga[p], r_gp[p]);
+      const f4 dsk = z_ds ? kZero4 : r_ds[p];
+      *(f4 *)&U[32 * p + srow][st] = dxo;
+      *(f4 *)&O[32 * p + srow][st] = dxo;
+      *(f4 *)&U[C + 32 * p + srow][st] = dsk;
+      bsum[p] += (dxo.x + dxo.y) + (dxo.z + dxo.w);  // bias gradients = row sums (fp32)
+      bsum[2 + p] += (dsk.x + dsk.y) + (dsk.z + dsk.w);
+      *(f4 *)&Gt[32 * p + srow][st] = r_th[p];
+      *(f4 *)&Gt[C + 32 * p + srow][st] = r_sg[p];
+    }
+  };
+  auto row8 = [&](const float *row, float (&o)[8]) {  // 8 consecutive values of a row
+    const f4 a0 = *(const f4 *)row, a1 = *(const f4 *)(row + 4);
+    o[0] = a0.x; o[1] = a0.y; o[2] = a0.z; o[3] = a0.w; o[4] = a1.x; o[5] = a1.y; o[6] = a1.z; o[7] = a1.w;
+  };
+
+  {
+    const bool inter = interior(tb);
+    if (inter) {
+#pragma unroll
+      for (int part = 0; part < 5; ++part) gload_r_part(tb, part);
+    } else {
+      gload_r_edge(tb);
+    }
+    set_zero_flags(tb, inter);
+  }
+  lstore_r();
+  __syncthreads();  // (covers the weight image too)
+  typedef __attribute__((address_space(3))) u32x4 lds_u4;
+  for (int t0 = tb; t0 < te; t0 += TT) {
+    const bool more = t0 + TT < te;
+    gload_x(t0);  // this tile's x rows fly under phase 1
+    f32x16 accd;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) accd[r] = 0.f;
+    {
+      // ---- phase 1: 12 slots
+      //   slots 0-3:  dz (32 c x 32 t), this wave's K half = [Wr | Ws]^T (A: image in LDS) x [dxo; dskip] (B: read across
+      //               the tile's rows), one k-step each;
+      //   slots 4-11: residual / skip weight gradient, rows [32 wm, +32) of [dxo; dskip] x z^T (channels [32 wn, +32)),
+      //               K = time: per 16 steps the row operand (even slot), then z = tanh x sigmoid and the product
+      float ob[2][8], sgv[2][8];
+      auto fetch1 = [&](int sI, float (&o)[8], float (&s)[8]) {
+        if (sI < 4) {
+          const int ks = 4 * kh1 + sI;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] = U[16 * ks + 8 * lh + e][32 * tq1 + li];
+        } else {
+          const int G = (sI - 4) >> 1;
+          if (((sI - 4) & 1) == 0) {
+            row8(&U[32 * wm + li][16 * G + 2 * h4], o);
+          } else {
+            row8(&Gt[32 * wn + li][16 * G + 2 * h4], o);
+            row8(&Gt[C + 32 * wn + li][16 * G + 2 * h4], s);
+          }
+        }
+      };
+      u32x4 wA[2], aq;
+      auto fetchA = [&](int sI, u32x4 &w) { w = *(const lds_u4 *)(uintptr_t)(wa0 + 1024u * (unsigned)(cb1 * 8 + 4 * kh1 + sI)); };
+      fetch1(0, ob[0], sgv[0]);
+      fetchA(0, wA[0]);
+#pragma clang loop unroll(full)
+      for (int sI = 0; sI < 12; ++sI) {
+        if (sI + 1 < 12) fetch1(sI + 1, ob[(sI + 1) & 1], sgv[(sI + 1) & 1]);
+        if (sI + 1 < 4) fetchA(sI + 1, wA[(sI + 1) & 1]);
+        float (&xc)[8] = ob[sI & 1];
+        if (sI < 4) {
+          B16_MFMA(accd, wA[sI & 1], b16_pack8(xc));
+        } else if (((sI - 4) & 1) == 0) {
+          aq = b16_pack8(xc);
+        } else {
+          float zv[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) zv[e] = xc[e] * sgv[sI & 1][e];
+          B16_MFMA(accr, aq, b16_pack8(zv));
+        }
+      }
+      // the two K halves of a block meet through the P0 staging rows, each wave handing over the HALF of its partial
+      // sums the other one finishes (registers 8 (1 - kh1) .. +8)
+#pragma unroll
+      for (int r = 0; r < 8; ++r) Zx[(((2 * tq1 + cb1) * 2 + kh1) * 8 + r) * 64 + lane] = kh1 ? accd[r] : accd[8 + r];
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the x rows (and the previous tile's stores)
+    __syncthreads();  // B1: U and tanh | sigmoid have been read; the partial sums of dz are staged
+    {
+      // ---- gate derivative in place (fp32): this lane holds dz of channels 32 cb1 + acc_row(r) at t = 32 tq1 + li
+      float tv[8], sv[8], dzv[8];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const int rr = 8 * kh1 + r, c = 32 * cb1 + (rr & 3) + 8 * (rr >> 2) + h4, tc = 32 * tq1 + li;
+        tv[r] = Gt[c][tc];
+        sv[r] = Gt[C + c][tc];
+        dzv[r] = Zx[(((2 * tq1 + cb1) * 2 + (1 - kh1)) * 8 + r) * 64 + lane];
+      }
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const int rr = 8 * kh1 + r, c = 32 * cb1 + (rr & 3) + 8 * (rr >> 2) + h4, tc = 32 * tq1 + li;
+        const float dz = dzv[r] + (kh1 ? accd[8 + r] : accd[r]);
+        Gt[c][tc] = dz * sv[r] * (1.0f - tv[r] * tv[r]);
+        Gt[C + c][tc] = dz * tv[r] * sv[r] * (1.0f - sv[r]);
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) *(f4 *)&U[32 * p + srow][st] = r_x[p];
+    __syncthreads();  // B2: df | dg and the x rows are staged
+    const bool spread = more && interior(t0 + TT);
+    if (more && !spread) gload_r_edge(t0 + TT);
+    // ---- phase 2: this wave's K half of its tap's product for both 32-step blocks, and its two blocks of the
+    // filter / gate weight gradient; the next tile's loads in parts between the steps
+    f32x16 accd2[2];
+#pragma unroll
+    for (int ub = 0; ub < 2; ++ub)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) accd2[ub][r] = 0.f;
+    {
+      // 20 slots, five per 16 time steps: the weight gradient's row operand of dfg, its two x operands, then this wave's
+      // k-step of the tap product for both 32-step blocks (operand read ACROSS the tile's rows)
+      float xb[2][8];
+      auto fetch2 = [&](int sI, float (&o)[8]) {
+        const int G = sI / 5, k = sI - 5 * G;
+        if (k < 3) {
+          const float *row = k == 0 ? &Gt[32 * wm + li][0] : &U[64 * wn + 32 * (k - 1) + li][0];
+          row8(row + 16 * G + 2 * h4, o);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] = Gt[64 * kh + 16 * G + 8 * lh + e][32 * (k - 3) + li];
+        }
+      };
+      u32x4 aq;
+      fetch2(0, xb[0]);
+#pragma clang loop unroll(full)
+      for (int sI = 0; sI < 20; ++sI) {
+        const int G = sI / 5, k = sI - 5 * G;
+        if (sI + 1 < 20) fetch2(sI + 1, xb[(sI + 1) & 1]);
+        if (spread && k == 0) {
+          gload_r_part(t0 + TT, G);
+          if (G == 3) gload_r_part(t0 + TT, 4);
+        }
+        const u32x4 xq = b16_pack8(xb[sI & 1]);
+        if (k == 0) {
+          aq = xq;
+        } else if (k < 3) {
+          B16_MFMA(accw[k - 1], aq, xq);
+        } else {
+          B16_MFMA(accd2[k - 3], xq, wp[G]);
+        }
+      }
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the next tile's loads, ahead of this tile's stores
+    // ---- the K halves meet in O: rows [0, 64) hold dxo (tap 1: A' = dxo + W1^T dfg), rows [64, 128) take P0
+    if (kh == 0) {
+#pragma unroll
+      for (int ub = 0; ub < 2; ++ub)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          f4 *p4 = (f4 *)&O[64 * half + 32 * wc + li][32 * ub + 8 * q + h4];
+          const f4 v = f4{accd2[ub][4 * q], accd2[ub][4 * q + 1], accd2[ub][4 * q + 2], accd2[ub][4 * q + 3]};
+          *p4 = half ? v : f4_add(*p4, v);
+        }
+    }
+    __syncthreads();  // B3: U and G have been read; the first K halves are in O
+    if (kh == 1) {
+#pragma unroll
+      for (int ub = 0; ub < 2; ++ub)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          f4 *p4 = (f4 *)&O[64 * half + 32 * wc + li][32 * ub + 8 * q + h4];
+          *p4 = f4_add(*p4, f4{accd2[ub][4 * q], accd2[ub][4 * q + 1], accd2[ub][4 * q + 2], accd2[ub][4 * q + 3]});
+        }
+    }
+    __syncthreads();  // B4
+    {
+      // whole-row float4 stores: rows srow + 32 p (A' rows, then P0 rows), columns t0 + st .. +3 inside [t_lo, te)
+      const int t = t0 + st;
+      if (t >= a.t_lo && t + 3 < te) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          fb_store16(*(const f4 *)&O[32 * p + srow][st], oab, vo_t, 4 * (32 * p * a.th.ld + t0));
+          fb_store16(*(const f4 *)&O[C + 32 * p + srow][st], opb, vo_t, 4 * (32 * p * a.th.ld + t0));
+        }
+      } else {
+        float *ba = a.oa.p + (size_t)b * a.oa.sb + t, *bp = a.op.p + (size_t)b * a.op.sb + t;
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (t + e >= a.t_lo && t + e < te) {
+              ba[(size_t)(32 * p + srow) * a.oa.ld + e] = O[32 * p + srow][st + e];
+              bp[(size_t)(32 * p + srow) * a.op.ld + e] = O[C + 32 * p + srow][st + e];
+            }
+      }
+    }
+    // (a thread's lstore_r() overwrites exactly the O elements the same thread has just read; U and G were
+    // last read before B3)
+    if (more) {
+      set_zero_flags(t0 + TT, spread);
+      lstore_r();
+    }
+    __syncthreads();  // B5
+  }
+  // ---- this workgroup's slabs and bias partial sums (wgrad2_kernel's formats: 128 x 128, 128 x 64, 128)
+  {
+    int tid_e = threadIdx.x;
+    asm volatile("" : "+v"(tid_e));
+    const int lane_e = tid_e & 63, wave_e = tid_e >> 6, wm_e = wave_e >> 1, wn_e = wave_e & 1;
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = 32 * wm_e + acc_row(r, lane_e), n = 64 * wn_e + 32 * ni + (lane_e & 31);
+        fg_part[((size_t)blockIdx.x * 128 + m) * 128 + n] = accw[ni][r];
+      }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int m = 32 * wm_e + acc_row(r, lane_e), n = 32 * wn_e + (lane_e & 31);
+      rs_part[((size_t)blockIdx.x * 128 + m) * 64 + n] = accr[r];
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    float v = bsum[p];  // 16 lanes share a row
+    v += __shfl_xor(v, 1, 64);
+    v += __shfl_xor(v, 2, 64);
+    v += __shfl_xor(v, 4, 64);
+    v += __shfl_xor(v, 8, 64);
+    if ((tid & 15) == 0) rs_bias_part[(size_t)blockIdx.x * 128 + (p < 2 ? 32 * p : C + 32 * (p - 2)) + srow] = v;
+  }
+}
+
+// launch_bwd_layer64 for the bf16 kernel (audio-only layers: no df | dg output); same plan, same reduce
+template <class RsOp, class FgOp>
+static int launch_bwd_layer64_bf16(const FusedBwdLArgs &a, const RsOp &rs, const FgOp &fg, int batch, const FusedBwdLPlan &pl,
+                                   hipStream_t s) {
+  if (pl.chunks <= 0) return MVN_OK;
+  const int ldt = a.th.ld;
+  if (a.dfg.p || a.sg.ld != ldt || a.xin.ld != ldt || a.oa.ld != ldt || a.op.ld != ldt || a.gp.ld != ldt ||
+      (a.ga.p && a.ga.ld != ldt)) {
+    set_error("bwd_layer64_bf16: audio-only layers, and the (B, ch, Tp) views must share one row pitch");
+    return MVN_ERR_BAD_ARG;
+  }
+  const int n = pl.chunks * batch;
+  const void *fn = (const void *)bwd_layer64_bf16_kernel;
+  const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(bwd_layer64_bf16)");
+  if (rc) return rc;
+  void *args[] = {(void *)&a, (void *)&pl.chunks, (void *)&pl.chunk_t, (void *)&pl.bias, (void *)&pl.rs, (void *)&pl.fg};
+  if (check_hip(hipLaunchKernel(fn, dim3(n), dim3(512), args, (size_t)FBL16_LDS_BYTES, s), "bwd_layer64_bf16"))
+    return MVN_ERR_LAUNCH;
+  hipLaunchKernelGGL((reduce_layer64_kernel<RsOp, FgOp>), dim3(260 + 128 * 128 / 32), dim3(32 * RED_SEG), 0, s, rs, pl.rs,
+                     pl.bias, n, fg, pl.fg, n);
+  return MVN_OK;
+}
+
+}  // namespace mvn

@@ -30,6 +30,7 @@
 #include "fused_fwd.h"
 #include "fused_fwd_bf3.h"
 #include "fused_bwd_l.h"
+#include "fused_bf16.h"
 
 namespace mvn {
 
@@ -1003,6 +1004,24 @@ struct SideStream {
   hipStream_t s = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
+// The dims the bf16 entry points run (fused_bf16.h): audio-only C = K = 64 layers, rows within the layer kernels'
+// buffer resources.  Anything else is refused -- never computed in fp32 instead.
+static int bf16_supported(const char *what, const Geometry &g, bool has_ctx) {
+  if (g.C != 64 || g.Kc != 64) {
+    set_error("%s: bf16 needs residual_channels = skip_channels = 64 (got %d, %d)", what, g.C, g.Kc);
+    return MVN_ERR_UNSUPPORTED;
+  }
+  if (has_ctx) {
+    set_error("%s: bf16 runs audio-only layers (no context)", what);
+    return MVN_ERR_UNSUPPORTED;
+  }
+  if (g.Tp > (1 << 21) || g.Sp > (1 << 21)) {
+    set_error("%s: bf16 needs t_len <= %d", what, 1 << 21);
+    return MVN_ERR_UNSUPPORTED;
+  }
+  return MVN_OK;
+}
+
 static int side_stream(SideStream **out) {
   static SideStream table[64];
   static std::mutex mu;
@@ -1063,10 +1082,14 @@ int mvn_padded_len(int n) { return n <= 0 ? 0 : (n + 63) / 64 * 64; }
 
 static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t *index, int index_stride,
                         int batch, int t_len, const mvn_fwd_buffers *buf, float *out, int normalize,
-                        int remove_last, int save, void *stream_, bool f16) {
+                        int remove_last, int save, void *stream_, bool f16, bool bf16 = false) {
   Geometry g;
   int rc = make_geometry(dims, batch, t_len, g);
   if (rc) return rc;
+  if (bf16) {  // (decided before any launch: there is no fp32 fall-back)
+    rc = bf16_supported("mvn_forward_bf16", g, buf && buf->ctx != nullptr);
+    if (rc) return rc;
+  }
   if (!p || !buf || !buf->acts || !buf->z || !buf->skip || !buf->a1 ||
       (save && (!buf->th || !buf->sg)) ||
       (buf->dense_audio ? buf->dense_ld < t_len : (!index || index_stride < t_len))) {
@@ -1124,6 +1147,30 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
       f.sg = act_view(save ? buf->sg + (size_t)l * g.act : nullptr, batch, C, g.Tp);
       launch_gemm_staged(f, 2 * ((C + 31) / 32 * 32), batch, s, f16);
     };
+    // bf16 operands (fused_bf16.h): the strip kernel with one-plane weight images, packed once per call into the z
+    // scratch when it holds them (bf16_supported has checked the dims and the row lengths)
+    if (bf16) {
+      FusedFwdPArgs fp;
+      fp.t_begin = A + d; fp.t_end = T; fp.d = d; fp.t_skip0 = t_skip0; fp.t_base = g.t_base;
+      fp.first_layer = (l == 0);
+      fp.wf = p->filter_w[l]; fp.wg = p->gate_w[l]; fp.wr = p->residual_w[l]; fp.ws = p->skip_w[l];
+      fp.br = p->residual_b[l]; fp.bs = p->skip_b[l];
+      fp.xin = xin; fp.xout = xout; fp.skip = skipv;
+      if (l == g.L - 1) fp.xout.p = nullptr;  // the last residual output is never used
+      fp.th = act_view(save ? buf->th + (size_t)l * g.act : nullptr, batch, C, g.Tp);
+      fp.sg = act_view(save ? buf->sg + (size_t)l * g.act : nullptr, batch, C, g.Tp);
+      if ((size_t)g.act >= (size_t)g.L * FB16_PACK_F) {
+        if (l == 0) {
+          const int rc3 = launch_fb16_pack(p, g.L, buf->z, s);
+          if (rc3) return rc3;
+        }
+        fp.wpack = buf->z + (size_t)l * FB16_PACK_F;
+      }
+      const int rc2 = launch_fused_layer64s_bf16(fp, batch, s);
+      if (rc2) return rc2;
+      A += d;
+      continue;
+    }
     // C = K = 64, fp32: the layer as ONE kernel (a strip kernel of fused_fwd_bf3.h / fused_fwd.h, or the tile
     // kernel of fused_fwd.h); MOVENET_HIP_NO_FUSED_FORWARD=1 keeps the two-kernel form below (tests)
     if (C == FP_C && Kc == FP_C && !f16 && !switches().no_fused_forward &&
@@ -1260,6 +1307,13 @@ int mvn_forward(const mvn_dims *dims, const mvn_params *p, const int32_t *index,
                       false);
 }
 
+int mvn_forward_bf16(const mvn_dims *dims, const mvn_params *p, const int32_t *index, int index_stride,
+                     int batch, int t_len, const mvn_fwd_buffers *buf, float *out, int normalize,
+                     int remove_last, int save, void *stream_) {
+  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_,
+                      false, true);
+}
+
 int mvn_forward_f16(const mvn_dims *dims, const mvn_params *p, const int32_t *index, int index_stride,
                     int batch, int t_len, const mvn_fwd_buffers *buf, float *out, int normalize,
                     int remove_last, int save, void *stream_) {
@@ -1270,10 +1324,10 @@ int mvn_forward_f16(const mvn_dims *dims, const mvn_params *p, const int32_t *in
 static int g_last_bwd_form = 0;  // (process-wide: autograd runs the backward on a thread of its own)
 int mvn_last_backward_form(void) { return g_last_bwd_form; }
 
-int mvn_backward(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
-                 const int32_t *index, int index_stride, int batch, int t_len,
-                 const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
-                 const float *dout, int normalize, int remove_last, void *stream_) {
+static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
+                         const int32_t *index, int index_stride, int batch, int t_len,
+                         const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
+                         const float *dout, int normalize, int remove_last, void *stream_, bool bf16) {
   Geometry g;
   int rc = make_geometry(dims, batch, t_len, g);
   if (rc) return rc;
@@ -1347,6 +1401,56 @@ int mvn_backward(const mvn_dims *dims, const mvn_params *p, const mvn_param_grad
     if (head_q_strip(Q) && Kc == 64 && fwd->z && forward_bf3_enabled() && (size_t)g.act >= off + DS3_BWD_IMG_F)
       bwd_head_img = fwd->z + off;
   }
+  // layers, last to first
+  int A_lo[4096];
+  {
+    int A = 0;
+    for (int l = 0; l <= g.L && l < 4096; ++l) {
+      A_lo[l] = A;
+      if (l < g.L) A += dilation_of(dims, l);
+    }
+  }
+  const bool has_ctx = fwd->ctx != nullptr;
+  if (has_ctx && (!bwd->dctx || !gr->ctx_filter_w || !gr->ctx_filter_b || !gr->ctx_gate_w ||
+                  !gr->ctx_gate_b || !p->ctx_filter_w || !p->ctx_gate_w)) {
+    set_error("mvn_backward: context given without dctx buffer / context-conv gradients");
+    return MVN_ERR_BAD_ARG;
+  }
+  // (tensors too small for the reservation above -- the parity tests' smallest -- get a bias region sized for
+  // the workgroups that fit: the plan takes fewer, longer chunks then)
+  float *sc_bias = bias_scratch2, *sc_slab = slab;
+  size_t sc_bias_floats = bias2_floats, sc_slab_floats = slab_floats;
+  if (!sc_bias && !has_ctx && slab) {
+    const size_t total = (size_t)batch * Q * g.Sp, n_fit = total / (128 * 64 + 128 * 128 + 128);
+    if (n_fit >= (size_t)batch) {
+      sc_bias_floats = n_fit * 128;
+      sc_slab_floats = total - sc_bias_floats;
+      sc_bias = bwd->da1 + sc_slab_floats;
+    }
+  }
+  if (bf16) {  // (decided before any launch: there is no fp32 fall-back)
+    rc = bf16_supported("mvn_backward_bf16", g, has_ctx);
+    if (rc) return rc;
+    FusedBwdLPlan pl0;
+    auto fits = [&]() {
+      return sc_bias && g.L < 4095 && bwd_layer64_plan(A_lo[1], T, batch, sc_bias, sc_bias_floats, sc_slab, sc_slab_floats, &pl0);
+    };
+    if (!fits() && fwd->z) {
+      // short outputs (da1 is (B, Q, Sp)): the slabs go to the forward's z scratch instead, which holds nothing the layer
+      // loop reads -- the bf16 forward keeps z in registers and its weight images there, and the head's backward, which
+      // may stage its own images in it, runs before the loop on the same stream
+      const size_t total = (size_t)g.act, n_fit = total / (128 * 64 + 128 * 128 + 128);
+      sc_bias_floats = n_fit * 128;
+      sc_slab = fwd->z;
+      sc_slab_floats = total - sc_bias_floats;
+      sc_bias = fwd->z + sc_slab_floats;
+    }
+    if (!fits()) {
+      set_error("mvn_backward_bf16: the layer kernel's weight-gradient slabs do not fit the scratch at batch %d, t_len %d",
+                batch, t_len);
+      return MVN_ERR_UNSUPPORTED;
+    }
+  }
   if (!dout) {
     // the caller has filled bwd->dlogit itself (mvn_softmax_ce_backward: the trainer's loss and
     // the model's softmax differentiated in one pass)
@@ -1407,21 +1511,6 @@ int mvn_backward(const mvn_dims *dims, const mvn_params *p, const mvn_param_grad
       launch_gemm_staged(d1, Kc, batch, s);
     }
   }
-  // layers, last to first
-  int A_lo[4096];
-  {
-    int A = 0;
-    for (int l = 0; l <= g.L && l < 4096; ++l) {
-      A_lo[l] = A;
-      if (l < g.L) A += dilation_of(dims, l);
-    }
-  }
-  const bool has_ctx = fwd->ctx != nullptr;
-  if (has_ctx && (!bwd->dctx || !gr->ctx_filter_w || !gr->ctx_filter_b || !gr->ctx_gate_w ||
-                  !gr->ctx_gate_b || !p->ctx_filter_w || !p->ctx_gate_w)) {
-    set_error("mvn_backward: context given without dctx buffer / context-conv gradients");
-    return MVN_ERR_BAD_ARG;
-  }
   Act ctxv = act_view(const_cast<float *>(fwd->ctx), batch, C, has_ctx ? fwd->ctx_ld : 0);
   Act dctxv = act_view(bwd->dctx, batch, C, g.Tp);
   if (has_ctx) {
@@ -1446,7 +1535,7 @@ int mvn_backward(const mvn_dims *dims, const mvn_params *p, const mvn_param_grad
     const bool fused_bwd = !switches().no_fused_backward;
   // (with both fused halves every kernel of the layer loop runs on the caller's stream: no fork,
   // and none of the two event records + waits per layer that go with it -- ~60 gaps of ~8 us per step)
-  const bool all_fused = fused_bwd && C == 64 && Kc == 64;  // (conditioned layers too: bwd_dctx_wgctx64_kernel)
+  const bool all_fused = bf16 || (fused_bwd && C == 64 && Kc == 64);  // (conditioned layers too: bwd_dctx_wgctx64_kernel)
   const bool fork = bias_scratch2 && !all_fused;
   hipStream_t s2 = s;
   if (fork) {
@@ -1468,19 +1557,7 @@ int mvn_backward(const mvn_dims *dims, const mvn_params *p, const mvn_param_grad
   // MOVENET_HIP_BWD_FORM=split keeps the two-half form of r2 / r3 (cross-checks, A/B; common.h: Switches).
   Act spair[2][2];
   bool scatter = false;
-  // (tensors too small for the reservation above -- the parity tests' smallest -- get a bias region sized for
-  // the workgroups that fit: the plan takes fewer, longer chunks then)
-  float *sc_bias = bias_scratch2, *sc_slab = slab;
-  size_t sc_bias_floats = bias2_floats, sc_slab_floats = slab_floats;
-  if (!sc_bias && !has_ctx && slab) {
-    const size_t total = (size_t)batch * Q * g.Sp, n_fit = total / (128 * 64 + 128 * 128 + 128);
-    if (n_fit >= (size_t)batch) {
-      sc_bias_floats = n_fit * 128;
-      sc_slab_floats = total - sc_bias_floats;
-      sc_bias = bwd->da1 + sc_slab_floats;
-    }
-  }
-  if (all_fused && sc_bias && g.L < 4095 && g.Tp <= (1 << 21) && !switches().bwd_split) {
+  if (all_fused && sc_bias && g.L < 4095 && g.Tp <= (1 << 21) && (bf16 || !switches().bwd_split)) {
     spair[0][0] = act_view(bwd->dx_a, batch, C, g.Tp);
     spair[0][1] = act_view(bwd->dx_b, batch, C, g.Tp);
     bool have = true;
@@ -1498,7 +1575,11 @@ int mvn_backward(const mvn_dims *dims, const mvn_params *p, const mvn_param_grad
     scatter = have && bwd_layer64_plan(A_lo[1], T, batch, sc_bias, sc_bias_floats, sc_slab, sc_slab_floats, &pl0) &&
               (!has_ctx || bwd_dctx_wgctx64_fits(A_lo[1], T, batch, bias_scratch2, bias2_floats, slab, slab_floats, &cc, &cct));
   }
-  g_last_bwd_form = scatter ? MVN_BWD_FORM_ONE : MVN_BWD_FORM_GENERIC;
+  if (bf16 && !scatter) {
+    set_error("mvn_backward_bf16: the bf16 layer kernels cannot run these buffers");
+    return MVN_ERR_UNSUPPORTED;
+  }
+  g_last_bwd_form = bf16 ? MVN_BWD_FORM_BF16 : scatter ? MVN_BWD_FORM_ONE : MVN_BWD_FORM_GENERIC;
   if (scatter) {
     int po = 1 ^ ((g.L - 1) & 1);  // (so that layer 0 writes pair 1 and the dense dx0 can go to dx_a)
     for (int l = g.L - 1; l >= 0; --l) {
@@ -1529,7 +1610,7 @@ int mvn_backward(const mvn_dims *dims, const mvn_params *p, const mvn_param_grad
         set_error("mvn_backward: the fused layer backward lost its scratch at layer %d", l);
         return MVN_ERR_BAD_ARG;
       }
-      rc = launch_bwd_layer64(fa, wr, wf, batch, pl, s);
+      rc = bf16 ? launch_bwd_layer64_bf16(fa, wr, wf, batch, pl, s) : launch_bwd_layer64(fa, wr, wf, batch, pl, s);
       if (rc) return rc;
       if (has_ctx) {  // (behind the layer's reduce: the slab scratch is free again)
         int c_chunks = 0, c_chunk_t = 0;
@@ -1714,6 +1795,22 @@ int mvn_backward(const mvn_dims *dims, const mvn_params *p, const mvn_param_grad
     }
   }
   return check_hip(hipGetLastError(), "mvn_backward");
+}
+
+int mvn_backward(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
+                 const int32_t *index, int index_stride, int batch, int t_len,
+                 const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
+                 const float *dout, int normalize, int remove_last, void *stream_) {
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_,
+                       false);
+}
+
+int mvn_backward_bf16(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
+                      const int32_t *index, int index_stride, int batch, int t_len,
+                      const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
+                      const float *dout, int normalize, int remove_last, void *stream_) {
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_,
+                       true);
 }
 
 int mvn_gen_prime_from_forward(const mvn_dims *dims, const mvn_fwd_buffers *fwd, int batch,

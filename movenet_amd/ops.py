@@ -100,10 +100,12 @@ class ForwardBuffers:
 
 
 def run_forward(dims: N.Dims, sd: Dict[str, torch.Tensor], idx: torch.Tensor, normalize: bool,
-                remove_last: bool, save: bool, ctx=None, f16: bool = False) -> Tuple[torch.Tensor, ForwardBuffers]:
+                remove_last: bool, save: bool, ctx=None, f16: bool = False,
+                bf16: bool = False) -> Tuple[torch.Tensor, ForwardBuffers]:
     """idx: (B,T) int32 class indices, or a (B,Q,T) fp32 tensor for inputs that are
     not one-hot (dense causal conv).  ``f16``: fp16 operands / fp32 accumulation in every
-    product (mvn_forward_f16; inference and generator priming)."""
+    product (mvn_forward_f16; inference and generator priming).  ``bf16``: bf16 operands /
+    fp32 accumulation in the layers' products (mvn_forward_bf16; trains with mvn_backward_bf16)."""
     lib = N.lib()
     _require_gpu(idx, "audio")
     dense = None
@@ -126,11 +128,11 @@ def run_forward(dims: N.Dims, sd: Dict[str, torch.Tensor], idx: torch.Tensor, no
         out = (torch.empty if buf.guard is None else buf.guard.empty)(
             (B, dims.input_channels, max(s_out, 0)), dtype=torch.float32, device=dev)
         params, keep = pack_params(dims, sd, L)
-        fwd = lib.mvn_forward_f16 if f16 else lib.mvn_forward
-        N.check(fwd(dims, params, None if dense is not None else idx.data_ptr(),
-                    0 if dense is not None else idx.stride(0), B, T, buf.struct,
-                    out.data_ptr(), int(normalize), int(remove_last), int(save),
-                    _stream_ptr(dev)), "mvn_forward_f16" if f16 else "mvn_forward")
+        name = "mvn_forward_f16" if f16 else "mvn_forward_bf16" if bf16 else "mvn_forward"
+        N.check(getattr(lib, name)(dims, params, None if dense is not None else idx.data_ptr(),
+                                   0 if dense is not None else idx.stride(0), B, T, buf.struct,
+                                   out.data_ptr(), int(normalize), int(remove_last), int(save),
+                                   _stream_ptr(dev)), name)
         if buf.guard is not None:
             buf.guard.check("mvn_forward")
     buf._keep = keep  # parameter tensors stay alive until the kernels have run
@@ -150,7 +152,8 @@ class _WaveNetFunction(torch.autograd.Function):
         if f16 and save:
             raise RuntimeError("movenet_amd: forward_precision 'fp16' is inference-only "
                                "(mvn_backward differentiates the fp32 forward); use torch.no_grad()")
-        out, buf = run_forward(dims, sd, idx, normalize, remove_last, save, context, f16=f16)
+        out, buf = run_forward(dims, sd, idx, normalize, remove_last, save, context, f16=f16,
+                               bf16=bool(getattr(dims, "_bf16", False)))
         ctx_.dims, ctx_.names, ctx_.idx, ctx_.buf = dims, names, idx, buf
         ctx_.normalize, ctx_.remove_last, ctx_.saved_fwd = normalize, remove_last, save
         ctx_.has_context = context is not None
@@ -244,12 +247,14 @@ def _run_backward(ctx_, params, out, dout, fill_dlogit):
             rf = N.check(lib.mvn_receptive_fields(dims), "mvn_receptive_fields")
             fill_dlogit(dlogit, buf.Sp, (rf - 1) & 31)
         params_c, pkeep = pack_params(dims, sd, L)
-        N.check(lib.mvn_backward(dims, params_c, g, None if dense_in else idx.data_ptr(),
-                                 0 if dense_in else idx.stride(0), B, T,
-                                 buf.struct, bw, None if out is None else out.data_ptr(),
-                                 None if dout is None else dout.data_ptr(),
-                                 int(ctx_.normalize), int(ctx_.remove_last), _stream_ptr(dev)),
-                "mvn_backward")
+        # (a bf16 forward is differentiated by the bf16 backward: same operand rounding both ways)
+        name = "mvn_backward_bf16" if getattr(dims, "_bf16", False) else "mvn_backward"
+        N.check(getattr(lib, name)(dims, params_c, g, None if dense_in else idx.data_ptr(),
+                                   0 if dense_in else idx.stride(0), B, T,
+                                   buf.struct, bw, None if out is None else out.data_ptr(),
+                                   None if dout is None else dout.data_ptr(),
+                                   int(ctx_.normalize), int(ctx_.remove_last), _stream_ptr(dev)),
+                name)
         if guard is not None:
             guard.check("mvn_backward")
     # (buffers are released with the autograd node; a retained graph may run backward again)
@@ -282,7 +287,8 @@ class _WaveNetLossFunction(torch.autograd.Function):
         lib = N.lib()
         sd = dict(zip(names, params))
         save = any(ctx_.needs_input_grad[4:]) and bool(getattr(dims, "_grad_mode", True))
-        out, buf = run_forward(dims, sd, idx, False, True, save, context)  # logits, last column dropped
+        # logits, last column dropped
+        out, buf = run_forward(dims, sd, idx, False, True, save, context, bf16=bool(getattr(dims, "_bf16", False)))
         B, Q, S = out.shape
         if target.shape != (B, S):
             raise ValueError(f"target must be (batch, {S}), got {tuple(target.shape)}")
@@ -396,15 +402,30 @@ def upsample_video(model, video: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def _tagged_dims(dims, f16: bool = False, context=None):
+def _tagged_dims(dims, f16: bool = False, context=None, bf16: bool = False):
     """A copy of the dims struct carrying what the autograd Functions cannot see from inside
     ``forward``: whether grad mode was on at the call, and the operand precision."""
     d = N.make_dims(dims.layer_size, dims.stack_size, dims.input_channels, dims.residual_channels,
                     dims.skip_channels)
     d._grad_mode = torch.is_grad_enabled()
     d._f16 = f16
+    d._bf16 = bf16
     d._video_slot = getattr(context, "_mvn_video_slot", None) if context is not None else None
     return d
+
+
+def bf16_mode(model, conditioned: bool) -> bool:
+    """Whether ``model.forward_precision`` asks for the bf16 layer kernels; raises ValueError, before
+    anything is launched, for what they do not run (mvn_forward_bf16 / mvn_backward_bf16 refuse the same)."""
+    if getattr(model, "forward_precision", "fp32") != "bf16":
+        return False
+    C, K = model._dims.residual_channels, model._dims.skip_channels
+    if C != 64 or K != 64:
+        raise ValueError("forward_precision 'bf16' needs residual_channels = skip_channels = 64, "
+                         f"got {C} and {K}")
+    if conditioned:
+        raise ValueError("forward_precision 'bf16' runs audio-only models: no video context")
+    return True
 
 
 def _decoder_params(model, with_context: bool):
@@ -421,10 +442,11 @@ def wavenet_forward(model, audio: torch.Tensor, context=None, output_unnormalize
     (B, C, T) or None.  One-hot input runs the causal conv as a gather; the check that the
     input IS one-hot is read after the kernels have been enqueued (no host wait on an idle
     GPU) and anything else is rerun through the dense causal conv."""
+    bf16 = bf16_mode(model, context is not None)
     model.compute_output_size(audio)  # ValueError when T < RF, like the reference
     idx, check = model._indices_async(audio)
     names, params = _decoder_params(model, context is not None)
-    dims = _tagged_dims(model._dims, f16=model.forward_precision == "fp16", context=context)
+    dims = _tagged_dims(model._dims, f16=model.forward_precision == "fp16", context=context, bf16=bf16)
     out = _WaveNetFunction.apply(dims, names, idx, bool(output_unnormalized),
                                  bool(remove_last), context, *params)
     if not model._all_one_hot(check):  # dense causal conv on the tensor itself
@@ -444,12 +466,13 @@ def wavenet_forward_loss(model, audio: torch.Tensor, context=None, target=None):
     the accuracy -- movenet/pytorch_lightning_trainer.py:62-66 -- with the softmax, the loss and
     the accuracy fused into one pass over the head's logits and their gradients into one pass
     back.  Same values as ``cross_entropy_on_probs(wavenet_forward(...), target)``."""
+    bf16 = bf16_mode(model, context is not None)
     model.compute_output_size(audio)
     rf = model.receptive_fields
     idx, check = model._indices_async(audio)
     names, params = _decoder_params(model, context is not None)
     tg = idx[:, rf:].to(torch.int64) if target is None else target
-    dims = _tagged_dims(model._dims, context=context)
+    dims = _tagged_dims(model._dims, context=context, bf16=bf16)
     res = _WaveNetLossFunction.apply(dims, names, idx, tg, context, *params)
     if not model._all_one_hot(check):  # (read after the enqueue: no idle GPU) dense causal conv
         del res  # release the discarded pass (saved activations) before the rerun allocates

@@ -72,7 +72,8 @@ class Dance2Music(nn.Module):
 
     def _shared_step(self, batch, prefix: str):
         audio, video, contexts, fps, info = batch
-        dtype = getattr(torch, f"float{self.precision}")
+        # ("bf16": the one-hot batch is exact in bfloat16; the model takes the class indices from it)
+        dtype = torch.bfloat16 if self.precision == "bf16" else getattr(torch, f"float{self.precision}")
         audio = audio.type(dtype).to(self.device)
         if self.config.use_video:
             video = video.type(dtype).to(self.device)
@@ -192,7 +193,17 @@ class Trainer:
                  accumulate_grad_batches: int = 1, logger=None, log_every_n_steps: int = 1,
                  num_sanity_val_steps: int = 0, callbacks=None, track_grad_norm: int = 2,
                  limit_train_batches: Optional[int] = None, device: Optional[str] = None,
-                 enable_checkpointing: bool = True, limit_val_batches: Optional[int] = None):
+                 enable_checkpointing: bool = True, limit_val_batches: Optional[int] = None,
+                 precision=32):
+        # Lightning's precision switch: 32 (default) trains in exact fp32; "bf16" runs the layer stack's
+        # products on bf16 operands with fp32 accumulation (WaveNet.forward_precision = "bf16"), fp32
+        # everywhere else -- master weights, optimizer, head and loss included
+        if precision in (16, "16", "16-mixed"):
+            raise NotImplementedError("precision=16 (fp16 training) needs loss scaling, which movenet_amd "
+                                      "does not implement; use precision='bf16' or 32")
+        if precision not in (32, "32", "bf16"):
+            raise ValueError(f"precision must be 32 or 'bf16', got {precision!r}")
+        self.precision = 32 if precision in (32, "32") else "bf16"
         self.max_epochs = max_epochs
         self.root = Path(default_root_dir) if default_root_dir is not None else None
         self.clip = gradient_clip_val or 0.0
@@ -212,6 +223,13 @@ class Trainer:
         self.global_step = 0
 
     def fit(self, model: Dance2Music) -> None:
+        if self.precision == "bf16":
+            if model.config.use_video:
+                raise ValueError("Trainer(precision='bf16') trains audio-only models: set use_video to False")
+            model.model.forward_precision = "bf16"
+            model.precision = "bf16"
+            from .ops import bf16_mode
+            bf16_mode(model.model, False)  # (the channel constraint, before anything runs)
         rank, world, local_rank = init_distributed(model.config.dist_backend
                                                    if torch.cuda.is_available() else "gloo",
                                                    model.config.dist_port)
@@ -343,7 +361,7 @@ class Trainer:
 
 def train_model(dataset: str, config: TrainingConfig, logger_name: Optional[str] = None,
                 log_video: bool = False, wandb_project: Optional[str] = None,
-                limit_train_batches: Optional[int] = None) -> Trainer:
+                limit_train_batches: Optional[int] = None, precision=32) -> Trainer:
     model = Dance2Music(dataset, config)
     if logger_name == "wandb":
         raise NotImplementedError("wandb logging is a SaaS integration and out of scope "
@@ -361,7 +379,8 @@ def train_model(dataset: str, config: TrainingConfig, logger_name: Optional[str]
         accumulate_grad_batches=config.accumulation_steps, logger=None, log_every_n_steps=1,
         num_sanity_val_steps=0, callbacks=callbacks, track_grad_norm=2,
         limit_train_batches=(limit_train_batches if limit_train_batches is not None
-                             else config.n_steps_per_epoch))
+                             else config.n_steps_per_epoch),
+        precision=precision)
     trainer.fit(model=model)
     return trainer
 
@@ -373,4 +392,4 @@ if __name__ == "__main__":
                         format="%(asctime)s: %(levelname)s: %(name)s: %(message)s")
     args = arg_parser().parse_args()
     train_model(args.dataset, config_from_args(args), logger_name=args.logger,
-                log_video=args.log_video, wandb_project=args.wandb_project)
+                log_video=args.log_video, wandb_project=args.wandb_project, precision=args.precision)

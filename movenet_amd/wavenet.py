@@ -73,7 +73,9 @@ class WaveNet(nn.Module):
         self._gen_variant = N.GEN_AUTO
         self.last_generate_fallback = None  # variant a timed-out PIPE call was rerun on
         # "fp32" (default) or "fp16": fp16 operands / fp32 accumulation in every product of
-        # forward() (mvn_forward_f16, any dims; inference only -- training stays fp32)
+        # forward() (mvn_forward_f16, any dims; inference only -- training stays fp32), or "bf16":
+        # bf16 operands / fp32 accumulation in the layers' products, forward AND backward
+        # (mvn_forward_bf16 / mvn_backward_bf16: audio-only, residual = skip channels = 64)
         self.forward_precision = "fp32"
 
     # ---- precision of generate() ----------------------------------------
@@ -185,7 +187,8 @@ class WaveNet(nn.Module):
         ``F.cross_entropy(output, target)`` and accuracy (pytorch_lightning_trainer.py:62-66)
         -- as ONE autograd node (ops.wavenet_forward_loss); going through ``forward`` keeps
         module hooks firing on the fused path."""
-        from .ops import wavenet_forward, wavenet_forward_loss  # HIP full-sequence kernels
+        from .ops import bf16_mode, wavenet_forward, wavenet_forward_loss  # HIP full-sequence kernels
+        bf16_mode(self, video is not None)  # (refused before the video encoder runs)
         context = None if video is None else self.upsample_video(video)
         if return_loss:
             return wavenet_forward_loss(self, audio, context, target)
