@@ -29,6 +29,11 @@ inline long long dilation_sum(const mvn_dims *d) {
   return (long long)d->stack_size * ((1LL << d->layer_size) - 1);
 }
 int validate_dims(const mvn_dims *d);
+// Whether a (rows, ld) fp32 tensor addressed from ONE base through a raw buffer resource (col_rsrc below, the head's
+// strip kernels) has every element within the resource's 0x7FFFFFFF bytes: 32-bit offsets 4 (row ld + column).  Past
+// that a load returns 0 and a store is dropped -- no fault, no error -- so the callers take a form with 64-bit
+// addresses instead.
+inline bool rows_fit_rsrc(long long rows, long long ld) { return 4 * rows * ld <= 0x7FFFFFFFLL; }
 // Raise a kernel's dynamic-LDS limit to the CU's 160 KiB on the CURRENT device, once per
 // (kernel, device): hipFuncSetAttribute applies to the current device's copy of the code
 // object, so a per-process flag would leave a second device at the 64 KiB default.

@@ -1240,7 +1240,8 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
     h1.ldw = Kc; h1.bias = p->head1_b; h1.xin = skipv; h1.yout = a1v; h1.ref = a1v;
     h1.t_out_end = g.pad + g.S; h1.aligned_out = 1;
     // Q = 256, K = 64: the strip form reads the skip sum once (fused_fwd.h)
-    const bool strip_ok = Kc == 64 && !f16;
+    // (the strip kernels address a sequence's (Q, Sp) / (Kc, Sp) rows with 32-bit offsets: common.h rows_fit_rsrc)
+    const bool strip_ok = Kc == 64 && !f16 && rows_fit_rsrc(Q, g.Sp);
     const bool strip = strip_ok && Q == 256;  // (the fp32 strips: Q = 256 only)
     // r3: both head convolutions as strip kernels on the bf16 matrix cores (fused_fwd_bf3.h), their LDS images
     // packed once per call behind the layers' in the z scratch
@@ -1270,7 +1271,7 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
     // `out` is the caller's contiguous (B, Q, S_out): column s of the head = out column s - pad
     h2.yout = act_view(out - g.pad, batch, Q, S_out);
     h2.t_out_end = g.pad + S_out; h2.aligned_out = 0;
-    const bool strip2 = Q == 256 && !f16;
+    const bool strip2 = Q == 256 && !f16 && rows_fit_rsrc(Q, g.Sp);
     if (head_img && S_out > 0) {
       // four row blocks of 64 on the bf16 matrix cores (fused_fwd_bf3.h)
       DenseStripArgs da;
@@ -1289,7 +1290,7 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
       launch_gemm_staged(h2, Q, batch, s, f16);
     }
     if (normalize) {
-      if (Q <= 4 * CQ)
+      if (Q <= 4 * CQ && rows_fit_rsrc(Q, S_out))  // (32-bit offsets into the sequence's (Q, S_out) tensor)
         hipLaunchKernelGGL(softmax_cols_kernel, dim3((S_out + 63) / 64, batch), dim3(256), 0, s, out, Q,
                            S_out);
       else
@@ -1398,7 +1399,8 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
   float *bwd_head_img = nullptr;
   {
     const size_t off = (size_t)g.L * std::max(FS3_PACK_F, FSC_PACK_F) + DS3_IMG_F;
-    if (head_q_strip(Q) && Kc == 64 && fwd->z && forward_bf3_enabled() && (size_t)g.act >= off + DS3_BWD_IMG_F)
+    if (head_q_strip(Q) && Kc == 64 && fwd->z && forward_bf3_enabled() && (size_t)g.act >= off + DS3_BWD_IMG_F &&
+        rows_fit_rsrc(Q, g.Sp))
       bwd_head_img = fwd->z + off;
   }
   // layers, last to first
@@ -1531,8 +1533,9 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
   //   ev[1]: dfg of this layer ready (s -> s2)
   //   ev[2], ev[3]: WgRs / WgFg done (s2 -> s: the buffers they read may be overwritten)
   SideStream *side = nullptr;
-  // MOVENET_HIP_NO_FUSED_BACKWARD=1: the two-kernel forms (cross-checks, profiling)
-    const bool fused_bwd = !switches().no_fused_backward;
+  // MOVENET_HIP_NO_FUSED_BACKWARD=1: the two-kernel forms (cross-checks, profiling); so do rows longer than the fused
+  // kernels' buffer resources span in the (2C, Tp) dfg tensor (common.h rows_fit_rsrc: Tp > ~4.2 M at C = 64)
+  const bool fused_bwd = !switches().no_fused_backward && rows_fit_rsrc(2 * C, g.Tp);
   // (with both fused halves every kernel of the layer loop runs on the caller's stream: no fork,
   // and none of the two event records + waits per layer that go with it -- ~60 gaps of ~8 us per step)
   const bool all_fused = bf16 || (fused_bwd && C == 64 && Kc == 64);  // (conditioned layers too: bwd_dctx_wgctx64_kernel)

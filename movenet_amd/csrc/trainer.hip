@@ -308,7 +308,8 @@ int mvn_softmax_ce_forward(float *logits_probs, const long long *target, int bat
     return MVN_ERR_BAD_ARG;
   }
   if (batch == 0 || s_len == 0) return MVN_OK;
-  if (classes <= 4 * mvn::TQ)
+  // (the column form addresses a sequence's (Q, S) tensor with 32-bit offsets: common.h rows_fit_rsrc)
+  if (classes <= 4 * mvn::TQ && mvn::rows_fit_rsrc(classes, s_len))
     hipLaunchKernelGGL(mvn::softmax_ce_fwd_cols_kernel, dim3((s_len + 63) / 64, batch), dim3(256), 0,
                        (hipStream_t)stream, logits_probs, target, classes, s_len, loss_part, correct_part);
   else
@@ -326,7 +327,7 @@ int mvn_softmax_ce_backward(const float *probs, const long long *target, int bat
     return MVN_ERR_BAD_ARG;
   }
   if (batch == 0 || dlogit_cols == 0) return MVN_OK;
-  if (classes <= 4 * mvn::TQ)
+  if (classes <= 4 * mvn::TQ && mvn::rows_fit_rsrc(classes, s_len) && mvn::rows_fit_rsrc(classes, dlogit_ld))
     hipLaunchKernelGGL(mvn::softmax_ce_bwd_cols_kernel, dim3((dlogit_cols + 63) / 64, batch), dim3(256), 0,
                        (hipStream_t)stream, probs, target, classes, s_len, scale, upstream, dlogit,
                        dlogit_batch_stride, dlogit_ld, dlogit_col0, dlogit_cols);

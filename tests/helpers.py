@@ -31,3 +31,25 @@ def rel_err(a, b) -> float:
     a = torch.as_tensor(np.asarray(a)).double()
     b = torch.as_tensor(np.asarray(b)).double()
     return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
+
+
+# ---- rows past a 32-bit buffer offset (the column loss / softmax kernels, the head strips) ----
+# Row q, column t of one (Q, ld) tensor sits at byte offset 4 (q ld + t) from the sequence's base.
+OFFSET_LIMIT = 1 << 31
+
+
+def long_row_lengths(Q: int) -> dict:
+    """Row strides at the edge of the 32-bit offset limit of a (Q, ld) fp32 tensor, multiples of 64:
+    ``below`` -- every offset fits; ``tail`` -- only the tail columns of the LAST row cross;
+    ``past`` -- the rows from about 85 % of Q on start beyond the limit."""
+    fit = OFFSET_LIMIT // (4 * Q)                    # first column past the limit in row Q - 1 ... (for ld = fit)
+    below = fit // 64 * 64 - 128
+    tail = fit // 64 * 64 + 2048
+    assert 4 * (Q - 1) * tail < OFFSET_LIMIT < 4 * Q * tail
+    past = -(-OFFSET_LIMIT // (4 * Q * 85 // 100)) // 64 * 64 + 64
+    return dict(below=below, tail=tail, past=past)
+
+
+def first_bad_row(Q: int, ld: int) -> int:
+    """The first row that starts at or past the limit (Q when none does)."""
+    return min(Q, -(-OFFSET_LIMIT // (4 * ld)))
