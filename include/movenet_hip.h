@@ -355,8 +355,11 @@ int mvn_upsample_video(const mvn_dims *dims, const mvn_video_params *vp, const f
 
 /* d_u2, d_u1, d_enc: scratch of the same shapes as u2, u1, enc.  `scratch` (r4): room for the per-workgroup
  * weight-gradient slabs of the up-sampler's backward kernel (C = 64), mvn_upsample_video_scratch_floats(dims, batch,
- * frames) floats; NULL or too small: the gradients are added with atomics instead (correct, ~5x slower, and the
- * summation order then varies from run to run). */
+ * frames) floats; NULL or smaller than that: the scratch is not touched and the gradients of all three layers are
+ * added with atomics instead (correct, ~5x slower, and the summation order then varies from run to run).  Every pointer is checked before the first launch (a refused call
+ * has written nothing).  With C = 64 the kernel reads the rows of dctx, d_u2 and d_u1 sixteen bytes at a time: dctx_ld
+ * must be a multiple of 4 and the three pointers 16-byte aligned, otherwise the call is refused with MVN_ERR_BAD_ARG
+ * (mvn_padded_len rows of an allocator's buffer always are). */
 size_t mvn_upsample_video_scratch_floats(const mvn_dims *dims, int batch, int frames);
 int mvn_upsample_video_backward(const mvn_dims *dims, const mvn_video_params *vp,
                                 const mvn_video_grads *vg, const float *video, int batch, int frames,

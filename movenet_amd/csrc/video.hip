@@ -428,7 +428,20 @@ int mvn_upsample_video_backward(const mvn_dims *dims, const mvn_video_params *vp
   if (rc) return rc;
   if (!vp || !vg || !vg->conv_w || !vg->conv_b || !video || !enc || !u1 || !u2 || !dctx || !d_u2 ||
       !d_u1 || !d_enc || dctx_ld < 1000 * frames) {
-    set_error("mvn_upsample_video_backward: NULL buffer");
+    set_error("mvn_upsample_video_backward: NULL buffer or dctx_ld < 1000*frames");
+    return MVN_ERR_BAD_ARG;
+  }
+  // (every pointer is checked before the first launch: a refused call has written nothing)
+  for (int i = 0; i < 3; ++i)
+    if (!vp->up_w[i] || !vg->up_w[i] || !vg->up_b[i]) {
+      set_error("mvn_upsample_video_backward: NULL upsampler parameter or gradient pointer");
+      return MVN_ERR_BAD_ARG;
+    }
+  // up_bwd64_kernel stages the rows of dout (dctx, then d_u2 and d_u1) with 16-byte loads
+  if (dims->residual_channels == 64 &&
+      (dctx_ld % 4 != 0 || ((uintptr_t)dctx | (uintptr_t)d_u2 | (uintptr_t)d_u1) % 16 != 0)) {
+    set_error("mvn_upsample_video_backward: C = 64 needs dctx_ld a multiple of 4 (got %d) and dctx, d_u2, d_u1 "
+              "16-byte aligned", dctx_ld);
     return MVN_ERR_BAD_ARG;
   }
   if (batch == 0) return MVN_OK;
@@ -437,15 +450,15 @@ int mvn_upsample_video_backward(const mvn_dims *dims, const mvn_video_params *vp
   const float *acts[3] = {enc, u1, u2};
   float *dacts[3] = {d_enc, d_u1, d_u2};
   int lens[4] = {F, F * kUp, F * kUp * kUp, F * kUp * kUp * kUp};
+  // one decision per call: a scratch below the sizing function's answer is not used at all (the two short layers
+  // would fit their slabs into it and only the last one take the atomics: neither form, and a caller's too-small
+  // buffer written to)
+  if (C == 64 && scratch_floats < up_bwd64_scratch_floats(lens[2], batch)) scratch = nullptr;
   for (int i = 2; i >= 0; --i) {
     // layer i maps acts[i] (length lens[i]) to its output (length lens[i+1])
     Act dout = act_view(const_cast<float *>(i == 2 ? dctx : dacts[i + 1]), batch, C,
                         i == 2 ? dctx_ld : mvn_padded_len(lens[i + 1]));
     Act xin = act_view(const_cast<float *>(acts[i]), batch, C, mvn_padded_len(lens[i]));
-    if (!vg->up_w[i] || !vg->up_b[i]) {
-      set_error("mvn_upsample_video_backward: NULL gradient pointer");
-      return MVN_ERR_BAD_ARG;
-    }
     if (C == 64) {  // (r4: one kernel per layer, dout staged as it lies in memory)
       UpBwdArgs ua;
       ua.n = lens[i]; ua.wt = vp->up_w[i]; ua.dout = dout; ua.xin = xin;

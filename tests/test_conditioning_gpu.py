@@ -10,7 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import one_hot, rel_err, synthetic_indices, weights_of
+from helpers import grad_bound, one_hot, rel_err, synthetic_indices, weights_of
 from movenet_amd.utils.weights import make_state_dict
 from oracle import wavenet_oracle as O
 
@@ -211,3 +211,83 @@ def test_conditioned_rounds_match_generic_kernel(channels, which, B):
     plain.prime(pidx)
     plain.advance(n_new)
     assert not torch.equal(plain.samples, runs[pipelined])  # the context matters
+
+
+def test_three_channel_video_forward_backward_vs_oracle(monkeypatch):
+    """``WaveNet(context_in_channels=3)``: the video encoder's form for cin > 1 (one frame per workgroup,
+    channel-interleaved pixel reads) and its weight gradient under a C = K = 64 decoder, 2 frames.  Logits and every
+    gradient against the oracle, under the weighted sum of squared LOGITS of
+    test_conditioned_fused_backward_matches_generic_kernels_and_oracle and with its bounds."""
+    import movenet_amd.wavenet as W
+    frames, B, cin = 2, 2, 3
+    T = 1000 * frames
+    monkeypatch.setattr(W, "MAX_AUDIO_FRAMES", T)
+    monkeypatch.setattr(W, "MAX_VIDEO_FRAMES", frames)
+    cfg = dict(layer_size=3, stack_size=2, input_channels=256, residual_channels=64, skip_channels=64)
+    sd = make_state_dict(**cfg, context_in_channels=cin, seed=29, gain=1.5)
+    assert sd["video_conv.weight"].shape == (64, cin, 1, 64, 64)
+    dims = O.Dims(**cfg)
+    x = one_hot(synthetic_indices(B, T, 256, 1234), 256)
+    video = torch.from_numpy(np.random.default_rng(4321).random((B, frames, 64, 64, cin), dtype=np.float32))
+    w = torch.linspace(0.5, 1.5, 256).view(1, 256, 1)
+
+    m = _model(dict(cfg, context_in_channels=cin), sd).train()
+    out = m(x.to(DEV), video.to(DEV), output_unnormalized=False)
+    loss = (out * w.to(DEV)).square().mean()
+    loss.backward()
+    got = {k: (None if p.grad is None else p.grad.cpu()) for k, p in m.named_parameters()}
+
+    params = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    ctx = O.upsample_video(params, video, expect_frames=T)
+    out_o = O.forward(params, dims, x, context=ctx, output_unnormalized=False)
+    loss_o = (out_o * w).square().mean()
+    loss_o.backward()
+    assert out.shape == out_o.shape
+    assert rel_err(out.detach().cpu(), out_o.detach()) < 2e-5
+    assert abs(loss.item() - loss_o.item()) < 2e-5 * abs(loss_o.item())
+    assert got["video_conv.weight"] is not None
+    for k, g in got.items():
+        if params[k].grad is None:
+            assert g is None, k
+        else:
+            assert rel_err(g, params[k].grad) < 3e-4, k
+
+
+# (frame counts for which the constructor's geomspace ladder of lengths is exact: 7 is, 3 and 5 are not)
+@pytest.mark.parametrize("C,frames,B,cin", [(64, 7, 3, 3), (16, 2, 2, 1)])
+def test_upsample_video_differentiated_on_its_own(monkeypatch, C, frames, B, cin):
+    """``model.upsample_video(video)`` with no decoder behind it: ``ctx.backward(dctx)`` takes the branch of
+    _UpsampleVideoFunction.backward that allocates its own eight gradient buffers.  Against the oracle in float64,
+    upstream gradient standard-normal noise; bounds: 1e-5 on the context (fixture G7's), helpers.grad_bound on the
+    gradients (2e-5 unless the oracle in fp32 is itself further than 5e-6 from float64)."""
+    import movenet_amd.wavenet as W
+    monkeypatch.setattr(W, "MAX_AUDIO_FRAMES", 1000 * frames)
+    monkeypatch.setattr(W, "MAX_VIDEO_FRAMES", frames)
+    cfg = dict(layer_size=2, stack_size=2, input_channels=64, residual_channels=C, skip_channels=C)
+    sd = make_state_dict(**cfg, context_in_channels=cin, seed=31, gain=3.0)
+    g = torch.Generator().manual_seed(7)
+    video = torch.randn(B, frames, 64, 64, cin, generator=g)
+    dctx = torch.randn(B, C, 1000 * frames, generator=g)
+
+    def oracle(dtype):
+        params = {k: v.to(dtype).clone().requires_grad_(True) for k, v in sd.items() if k.startswith("video_")}
+        ctx = O.upsample_video(params, video.to(dtype), expect_frames=1000 * frames)
+        ctx.backward(dctx.to(dtype))
+        return ctx.detach(), {k: p.grad for k, p in params.items()}
+
+    (ctx64, g64), (_, g32) = oracle(torch.float64), oracle(torch.float32)
+    m = _model(dict(cfg, context_in_channels=cin), sd).train()
+    ctx = m.upsample_video(video.to(DEV))
+    assert ctx.shape == ctx64.shape and rel_err(ctx.detach().cpu(), ctx64) < 1e-5
+    ctx.backward(dctx.to(DEV))
+    got = {k: p.grad for k, p in m.named_parameters() if p.grad is not None}
+    assert sorted(got) == sorted(g64)   # the eight video parameters and nothing else
+    for k in g64:
+        bound = grad_bound(rel_err(g32[k], g64[k]))
+        e = rel_err(got[k].cpu(), g64[k])
+        print(f"{k}: {e:.2e} (bound {bound:.1e})")
+        assert e < bound, (k, e, bound)
+    # a second pass accumulates into .grad through autograd: twice the gradient
+    m.upsample_video(video.to(DEV)).backward(dctx.to(DEV))
+    for k in g64:
+        assert rel_err(dict(m.named_parameters())[k].grad.cpu(), 2 * g64[k]) < grad_bound(rel_err(g32[k], g64[k])), k
