@@ -440,6 +440,29 @@ int mvn_adamw_step(float *param, const float *grad, float *exp_avg, float *exp_a
 int mvn_mu_law_encode(const float *x, int32_t *index, size_t n, int classes, void *stream);
 int mvn_mu_law_decode(const int32_t *index, float *x, size_t n, int classes, void *stream);
 
+/* The loader's waveform front end (movenet/dataset.py:253-289 behind the decoder): a batch of clips of different
+ * lengths, as interleaved int16 PCM in one upload, -> (batch, n_out) int32 class indices.  Per clip: channel mean of
+ * pcm / 32768; resample of the whole clip to n_out frames by torchaudio's sinc_interp_hann rule (lowpass_filter_width
+ * 6, roll-off 0.99), the taps evaluated in place; when `normalize`, y <- 2 (y - min)/(max - min) - 1
+ * unless max == min; mu-law of mvn_mu_law_encode, clamped to 0 .. classes-1.
+ *   pcm      DEVICE, pcm_len int16 elements
+ *   clips    DEVICE, one descriptor per clip: element offset of its first sample, frames, channels
+ *   y        DEVICE (batch, n_out) fp32: the resampled waveform before normalisation (written in full)
+ *   scratch  DEVICE mvn_audio_frontend_scratch_floats(batch, n_out) floats, 8-byte aligned: (min, max) per tile
+ *   index    DEVICE (batch, n_out) int32
+ * The descriptors are read on the device, so they are checked there: a clip whose span does not lie inside
+ * [0, pcm_len), or with frames > 100 n_out-ish (the window of one output tile no longer fits the LDS; frames <=
+ * 100 n_out always fits), is not read at all and its row of `index` is filled with -1.  8-bit PCM is shipped as
+ * (v - 128) << 8, 24- and 32-bit PCM rounded to 16 bits, by the host.  Two launches, no atomics: bit-reproducible. */
+typedef struct {
+  int64_t offset;
+  int32_t frames;
+  int32_t channels;
+} mvn_audio_clip;
+size_t mvn_audio_frontend_scratch_floats(int batch, int n_out);
+int mvn_audio_frontend(const int16_t *pcm, long long pcm_len, const mvn_audio_clip *clips, int batch, int classes,
+                       int n_out, int normalize, float *y, float *scratch, int32_t *index, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,9 @@ SIGNATURES = {
                                       C.c_void_p]),
     "mvn_index_to_onehot": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p]),
+    "mvn_audio_frontend_scratch_floats": (C.c_size_t, [C.c_int, C.c_int]),
+    "mvn_audio_frontend": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mvn_publish_words": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 

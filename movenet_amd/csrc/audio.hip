@@ -1,0 +1,227 @@
+// The loader's waveform front end (movenet/dataset.py:253-289 without the decoder): interleaved int16 PCM of a batch of
+// clips of different lengths -> (B, N) class indices, in two kernels.
+//
+//   af_resample_kernel   channel mean + sinc_interp_hann resample of the WHOLE clip to N frames (lowpass_filter_width 6,
+//                        roll-off 0.99), fp32 y, and the (min, max) of every tile of outputs
+//   af_quantise_kernel   the clip's (min, max) from the tile partials, min-max normalise, mu-law, clamp -> int32 index
+//
+// Per output sample k of a clip of n frames (g = gcd(n, N), orig = n/g, new = N/g, s = 0.99 min(orig, new)/orig):
+//   c = k orig/new,  y[k] = sum_i m[i] h(i - c),  u = (i - c) s,  h = s sinc(pi u) cos^2(pi u/12) for |u| < 6, else 0
+// k orig is a 64-bit integer product; i0 = floor(c) and the phase (k orig) mod new are taken from it exactly, so the
+// float part of a tap's argument is (i - i0) - phase/new: a small integer minus a fraction, whatever the clip's length.
+//
+// Clips come through a DEVICE descriptor array (one launch per batch, not per clip).  Every read of the upload is
+// bounded by the descriptor's own span [offset, offset + frames channels), and a descriptor whose span does not lie
+// inside [0, pcm_len) -- or whose ratio n/N needs a longer window than the LDS tile holds (n <= 100 N always fits) --
+// is never read through: its row of indices is filled with -1.
+#include "common.h"
+
+#include <cmath>
+
+namespace mvn {
+
+constexpr int kAfTile = 1024;   // output samples per workgroup
+constexpr int kAfWin = 8192;    // fp32 input window in LDS (32 KiB)
+constexpr int kAfMinSub = 64;   // a workgroup walks its tile in sub-tiles of at least this many outputs
+constexpr int kAfThreads = 256;
+
+struct AfGeom {
+  long long orig, neu;
+  float s;   // base / orig: the tap argument's scale and the filter's gain
+  int W;     // taps reach i0 - W .. i0 + W + 1
+  int sub;   // outputs per staged window
+  bool ok;
+};
+
+__device__ __forceinline__ AfGeom af_geom(const mvn_audio_clip &c, long long pcm_len, int N) {
+  AfGeom g;
+  g.ok = c.frames >= 1 && c.channels >= 1 && c.offset >= 0 &&
+         c.offset + (long long)c.frames * c.channels <= pcm_len;
+  g.orig = g.neu = 1;
+  g.s = 0.f;
+  g.W = g.sub = 0;
+  if (!g.ok) return g;
+  long long a = c.frames, b = N;
+  while (b) {
+    const long long t = a % b;
+    a = b;
+    b = t;
+  }
+  g.orig = c.frames / a;
+  g.neu = N / a;
+  const double sd = 0.99 * (double)(g.orig < g.neu ? g.orig : g.neu) / (double)g.orig;
+  g.s = (float)sd;
+  g.W = (int)(6.0 / sd) + 1;
+  const long long room = (long long)kAfWin - 2LL * g.W - 4;
+  if (room < 0) {
+    g.ok = false;
+    return g;
+  }
+  const long long sub = 1 + room * g.neu / g.orig;
+  g.sub = (int)(sub < kAfTile ? sub : kAfTile);
+  if (g.sub < kAfMinSub) g.ok = false;
+  return g;
+}
+
+__device__ __forceinline__ float wave_min(float v) { return -wave_max(-v); }
+
+__global__ __launch_bounds__(kAfThreads) void af_resample_kernel(const int16_t *__restrict__ pcm, long long pcm_len,
+                                                                 const mvn_audio_clip *__restrict__ clips, int N,
+                                                                 float *__restrict__ y, float2 *__restrict__ part) {
+  __shared__ float win[kAfWin];
+  __shared__ float red[2 * (kAfThreads / kWave)];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const mvn_audio_clip c = clips[b];
+  const AfGeom g = af_geom(c, pcm_len, N);
+  const int t0 = blockIdx.x * kAfTile, t1 = min(N, t0 + kAfTile);
+  float *yb = y + (size_t)b * N;
+  if (!g.ok) {  // (workgroup-uniform) nothing of the upload is read
+    for (int k = t0 + tid; k < t1; k += kAfThreads) yb[k] = 0.f;
+    if (tid == 0) part[(size_t)b * gridDim.x + blockIdx.x] = make_float2(0.f, 0.f);
+    return;
+  }
+  const int16_t *src = pcm + c.offset;
+  const int ch = c.channels, W = g.W;
+  const float den = 32768.0f * (float)ch, s = g.s, fneu = (float)g.neu;
+  const float kPi = 3.14159265358979323846f;
+  float mn = INFINITY, mx = -INFINITY;
+  for (int k0 = t0; k0 < t1; k0 += g.sub) {
+    const int k1 = min(t1, k0 + g.sub);
+    const long long lo = ((long long)k0 * g.orig) / g.neu - W;
+    const long long hi = ((long long)(k1 - 1) * g.orig) / g.neu + W + 1;
+    const int len = (int)min(hi - lo + 1, (long long)kAfWin);  // (af_geom sized sub so that the window fits)
+    __syncthreads();  // the previous window has been consumed
+    for (int j = tid; j < len; j += kAfThreads) {
+      const long long i = lo + j;
+      float v = 0.f;  // m[i] = 0 outside the clip
+      if (i >= 0 && i < c.frames) {
+        int sum = 0;
+        for (int q = 0; q < ch; ++q) sum += src[i * ch + q];
+        v = (float)sum / den;
+      }
+      win[j] = v;
+    }
+    __syncthreads();
+    for (int k = k0 + tid; k < k1; k += kAfThreads) {
+      const long long p = (long long)k * g.orig;
+      const long long i0 = p / g.neu;
+      const float frac = (float)(p - i0 * g.neu) / fneu;
+      const float *w = win + (int)(i0 - lo);
+      float acc = 0.f;
+      for (int d = -W; d <= W + 1; ++d) {
+        const float u = ((float)d - frac) * s;
+        float h = 0.f;
+        if (fabsf(u) < 6.0f) {
+          const float sinc = u == 0.f ? 1.0f : sinpif(u) / (kPi * u);
+          const float cw = cospif(u / 12.0f);
+          h = s * sinc * (cw * cw);
+        }
+        acc = fmaf(w[d], h, acc);
+      }
+      yb[k] = acc;
+      mn = fminf(mn, acc);
+      mx = fmaxf(mx, acc);
+    }
+  }
+  mn = wave_min(mn);
+  mx = wave_max(mx);
+  const int wave = tid / kWave;
+  if ((tid & (kWave - 1)) == 0) {
+    red[2 * wave] = mn;
+    red[2 * wave + 1] = mx;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int v = 1; v < kAfThreads / kWave; ++v) {
+      mn = fminf(mn, red[2 * v]);
+      mx = fmaxf(mx, red[2 * v + 1]);
+    }
+    part[(size_t)b * gridDim.x + blockIdx.x] = make_float2(mn, mx);
+  }
+}
+
+// audio <- (audio - min) / (max - min); audio * 2 - 1 (dataset.py:271-275), a clip with max == min left as it is (the
+// silent clip of the reference's `sum() == 0` test); then the mu-law of mu_law_encode_kernel, clamped to 0 .. Q-1
+// (an un-normalised resample may overshoot [-1, 1]).
+__global__ __launch_bounds__(kAfThreads) void af_quantise_kernel(const mvn_audio_clip *__restrict__ clips,
+                                                                 long long pcm_len, int N, int Q, int normalize,
+                                                                 int tiles, const float *__restrict__ y,
+                                                                 const float2 *__restrict__ part,
+                                                                 int32_t *__restrict__ idx) {
+  __shared__ float red[2 * (kAfThreads / kWave)];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int t0 = blockIdx.x * kAfTile, t1 = min(N, t0 + kAfTile);
+  int32_t *ib = idx + (size_t)b * N;
+  const AfGeom g = af_geom(clips[b], pcm_len, N);
+  if (!g.ok) {
+    for (int k = t0 + tid; k < t1; k += kAfThreads) ib[k] = -1;
+    return;
+  }
+  float mn = INFINITY, mx = -INFINITY;
+  if (normalize) {  // every workgroup folds the clip's partials in the same order: one (min, max) per clip, reproducibly
+    for (int t = tid; t < tiles; t += kAfThreads) {
+      const float2 p = part[(size_t)b * tiles + t];
+      mn = fminf(mn, p.x);
+      mx = fmaxf(mx, p.y);
+    }
+    mn = wave_min(mn);
+    mx = wave_max(mx);
+    if ((tid & (kWave - 1)) == 0) {
+      red[2 * (tid / kWave)] = mn;
+      red[2 * (tid / kWave) + 1] = mx;
+    }
+    __syncthreads();
+    mn = red[0];
+    mx = red[1];
+    for (int v = 1; v < kAfThreads / kWave; ++v) {
+      mn = fminf(mn, red[2 * v]);
+      mx = fmaxf(mx, red[2 * v + 1]);
+    }
+  }
+  const bool scale = normalize && mx != mn;
+  const float mu = (float)(Q - 1), range = mx - mn, lmu = log1pf(mu);
+  const float *yb = y + (size_t)b * N;
+  for (int k = t0 + tid; k < t1; k += kAfThreads) {
+    float v = yb[k];
+    if (scale) {
+      v = (v - mn) / range;
+      v = v * 2.0f - 1.0f;
+    }
+    const float z = copysignf(log1pf(mu * fabsf(v)) / lmu, v);
+    const int q = (int)((z + 1.0f) / 2.0f * mu + 0.5f);
+    ib[k] = min(max(q, 0), Q - 1);
+  }
+}
+
+}  // namespace mvn
+
+extern "C" {
+
+size_t mvn_audio_frontend_scratch_floats(int batch, int n_out) {
+  if (batch < 1 || n_out < 1) return 0;
+  return 2 * (size_t)batch * (size_t)((n_out + mvn::kAfTile - 1) / mvn::kAfTile);
+}
+
+int mvn_audio_frontend(const int16_t *pcm, long long pcm_len, const mvn_audio_clip *clips, int batch, int classes,
+                       int n_out, int normalize, float *y, float *scratch, int32_t *index, void *stream) {
+  if (!pcm || !clips || !y || !scratch || !index || pcm_len < 1 || batch < 1 || batch > 65535 || n_out < 1 ||
+      classes < 2 || classes > 65536) {
+    mvn::set_error("mvn_audio_frontend: bad argument");
+    return MVN_ERR_BAD_ARG;
+  }
+  if (((uintptr_t)scratch & 7u) != 0) {
+    mvn::set_error("mvn_audio_frontend: scratch must be 8-byte aligned");
+    return MVN_ERR_BAD_ARG;
+  }
+  const int tiles = (n_out + mvn::kAfTile - 1) / mvn::kAfTile;
+  const dim3 grid(tiles, batch);
+  hipLaunchKernelGGL(mvn::af_resample_kernel, grid, dim3(mvn::kAfThreads), 0, (hipStream_t)stream, pcm, pcm_len,
+                     clips, n_out, y, (float2 *)scratch);
+  int rc = mvn::check_hip(hipGetLastError(), "audio_frontend (resample)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(mvn::af_quantise_kernel, grid, dim3(mvn::kAfThreads), 0, (hipStream_t)stream, clips, pcm_len,
+                     n_out, classes, normalize, tiles, (const float *)y, (const float2 *)scratch, index);
+  return mvn::check_hip(hipGetLastError(), "audio_frontend (quantise)");
+}
+
+}  // extern "C"

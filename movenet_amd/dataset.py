@@ -12,6 +12,14 @@ a synthetic source:
 Class indices are U{0..Q-1} (SURVEY.md section 8d "Synthetic inputs"); the
 optional random contiguous crop ``batch_subsample_frac`` follows
 dataset.py:232-242.
+
+Beside it, a folder of integer-PCM WAV files in the reference's layout (``WavFolderLoader``):
+
+    --dataset /data/my_wavs          # <dir>/train/<context>/*.wav, <dir>/valid/<context>/*.wav
+
+What the reference does to a decoded waveform (channel mean, resample to MAX_AUDIO_FRAMES, min-max normalisation,
+mu-law, one-hot: dataset.py:253-289) runs on the GPU behind the upload (ops.audio_frontend); the decoder itself
+stays out of scope.
 """
 from __future__ import annotations
 
@@ -194,11 +202,235 @@ def _to_device_async(x: np.ndarray, device: torch.device) -> torch.Tensor:
         return _PinnedRing.to_device(_ring("video", device).stage(np.ascontiguousarray(x)), device)
 
 
+def read_wav_header(path: str) -> dict:
+    """rate / frames / channels / sample width of an integer-PCM WAV (standard library ``wave``); ValueError naming
+    the file for anything else (float WAVs, compressed formats, broken headers)."""
+    import wave
+    try:
+        with wave.open(str(path), "rb") as w:
+            info = dict(rate=w.getframerate(), frames=w.getnframes(), channels=w.getnchannels(),
+                        width=w.getsampwidth(), comptype=w.getcomptype())
+    except (wave.Error, EOFError) as e:
+        raise ValueError(f"{path}: not an integer-PCM WAV ({e})") from e
+    if info["comptype"] != "NONE" or info["width"] not in (1, 2, 3, 4) or info["channels"] < 1:
+        raise ValueError(f"{path}: only 8/16/24/32-bit integer PCM is read "
+                         f"(sample width {info['width']}, compression {info['comptype']})")
+    return info
+
+
+def read_wav_pcm16(path: str) -> tuple:
+    """(interleaved int16 samples, frames, channels, rate) of an integer-PCM WAV, in the form the GPU front end
+    takes: 16-bit as stored; 8-bit (unsigned) as ``(v - 128) << 8``, which is the same waveform exactly; 24- and
+    32-bit rounded to the nearest 16-bit value (saturating) -- the model quantises to at most 256 classes."""
+    import wave
+    h = read_wav_header(path)
+    with wave.open(str(path), "rb") as w:
+        raw = w.readframes(h["frames"])
+    width, ch = h["width"], h["channels"]
+    n = len(raw) // (width * ch)
+    raw = raw[: n * width * ch]
+    if width == 2:
+        pcm = np.frombuffer(raw, dtype="<i2")
+    elif width == 1:
+        pcm = (np.frombuffer(raw, dtype=np.uint8).astype(np.int16) - 128) << 8
+    else:
+        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, width).astype(np.int64)
+        v = sum(b[:, k] << (8 * k) for k in range(width))
+        v = np.where(v >= 1 << (8 * width - 1), v - (1 << (8 * width)), v)  # two's complement
+        shift = 8 * width - 16
+        pcm = np.clip((v + (1 << (shift - 1))) >> shift, -32768, 32767)
+    return np.ascontiguousarray(pcm, dtype=np.int16), n, ch, h["rate"]
+
+
+class _IndexCache:
+    """(N,) int16 class indices of the clips seen so far, on the device.  They do not depend on the epoch (the crop
+    does).  Past ``max_bytes`` nothing is evicted: new clips are simply not kept."""
+
+    def __init__(self, max_bytes: int):
+        self.max_bytes, self.bytes = int(max_bytes), 0
+        self.rows: dict = {}
+        self.hits = self.misses = 0
+
+    def put(self, key, row: torch.Tensor) -> None:
+        size = row.numel() * 2
+        if key not in self.rows and self.bytes + size <= self.max_bytes:
+            self.rows[key] = row.to(torch.int16)
+            self.bytes += size
+
+
+_INDEX_CACHES: dict = {}
+
+
+class WavFolderLoader:
+    """Clips from a folder of WAV files, in the reference's KineticsDataset layout with ``.wav`` for ``.mp4``
+    (movenet/dataset.py:101-140):
+
+        <dir>/train/<context>/*.wav      <dir>/valid/<context>/*.wav
+
+    Stems containing ``_raw`` or starting with ``.`` are skipped (:126).  Same interface and sharding rules as
+    SyntheticLoader.  The files are read with the standard library's ``wave`` (integer PCM only); the interleaved
+    int16 samples of a batch cross PCIe from the pinned staging ring as one asynchronous copy on the training stream,
+    and everything the reference does to a decoded waveform -- channel mean, resample of the whole clip to
+    MAX_AUDIO_FRAMES, min-max normalisation, mu-law (dataset.py:253-289) -- runs behind it on the GPU
+    (ops.audio_frontend), then the one-hot expansion of the Batch contract (mvn_index_to_onehot).  ``__iter__`` never
+    waits for the GPU.  There is no CPU path: iterating needs ``device=`` to be an MI355X.
+
+    Build definitions (torchaudio is absent, so these are stated, not pinned): the resample is
+    ``sinc_interp_hann`` with ``lowpass_filter_width = 6``, ``rolloff = 0.99``; of the reference's ``sum() == 0``
+    test before normalising, only the silent-clip case is reproduced -- a clip with ``max == min`` is left as it is.
+
+    Index cache: the (N,) indices of every clip seen stay on the device as int16, up to ``cache_bytes``; from the
+    second epoch on a cached clip costs no file read, no upload and no front-end launch.  Loaders of the same split,
+    class count, normalisation and device share one cache (the trainer builds a loader per epoch).
+
+    Video (``use_video=True``): ``<stem>.npy`` beside ``<stem>.wav`` holding (F, 64, 64) or (F, 64, 64, 1) values in
+    [0, 1], ALREADY gray and ALREADY 64 x 64 -- RGB -> gray and the spatial resize belong to the decoder side and are
+    out of scope.  It is reduced to ``frames // 1000`` frames by pytorchvideo's uniform_temporal_subsample rule."""
+
+    def __init__(self, root, input_channels: int, batch_size: int, train: bool = True,
+                 rank: int = 0, world_size: int = 1, shuffle: bool = False,
+                 batch_subsample_frac: Optional[float] = None, use_video: bool = False,
+                 normalize_audio: bool = True, device=None, cache_bytes: int = 4 << 30, **_ignored):
+        import os
+        from pathlib import Path
+        from . import wavenet as W
+        self.root_path = Path(root) / ("train" if train else "valid")
+        self.frames = int(W.MAX_AUDIO_FRAMES)
+        self.seed = 1234 + (0 if train else 10007)
+        self.Q, self.batch_size = input_channels, batch_size
+        self.rank, self.world = rank, max(world_size, 1)
+        self.shuffle, self.frac = shuffle, batch_subsample_frac
+        self.use_video, self.normalize = use_video, bool(normalize_audio)
+        self.device = torch.device(device) if device is not None else None
+        if use_video and (self.frames % 1000 or batch_subsample_frac is not None):
+            raise ValueError("video batches need frames % 1000 == 0 and no batch_subsample_frac "
+                             "(the reference crops audio and video independently, dataset.py:232-242, "
+                             "which its own size assert then rejects)")
+        if input_channels > 32768:
+            raise ValueError("input_channels above 32768 do not fit the int16 index cache")
+        self.contexts = sorted(p.name for p in self.root_path.glob("*") if p.is_dir()) \
+            if self.root_path.is_dir() else []
+        self.index = []  # (context, path, header)
+        for context in self.contexts:
+            for fp in sorted((self.root_path / context).glob("*.wav")):
+                if "_raw" in fp.stem or fp.stem.startswith("."):
+                    continue
+                h = read_wav_header(str(fp))
+                if h["frames"] < 1:
+                    raise ValueError(f"{fp}: no audio frames")
+                if h["frames"] > 100 * self.frames:
+                    raise ValueError(f"{fp}: {h['frames']} frames is more than 100 x the {self.frames} frames "
+                                     "the front end resamples to")
+                if use_video and not fp.with_suffix(".npy").is_file():
+                    raise ValueError(f"{fp}: use_video needs the clip's frames in {fp.with_suffix('.npy').name}")
+                self.index.append((context, str(fp), h))
+        if not self.index:
+            raise ValueError(f"{self.root_path}: no .wav clips (expected <context>/*.wav below it)")
+        self.filepaths = [fp for _, fp, _ in self.index]
+        self.info = [dict(video_fps=0.0, audio_fps=float(h["rate"]), video_orig_dim=0,
+                          audio_orig_dim=int(h["frames"])) for _, _, h in self.index]
+        self.n_clips = len(self.index)
+        key = (os.path.abspath(str(self.root_path)), self.Q, self.frames, self.normalize, str(self.device))
+        cache = _INDEX_CACHES.get(key)
+        if cache is None or cache.max_bytes != int(cache_bytes):
+            cache = _INDEX_CACHES[key] = _IndexCache(cache_bytes)
+        self.cache = cache
+        self.epoch = 0
+
+    set_epoch = SyntheticLoader.set_epoch
+    _order = SyntheticLoader._order
+    __len__ = SyntheticLoader.__len__
+
+    def cache_stats(self) -> dict:
+        c = self.cache
+        return dict(hits=c.hits, misses=c.misses, clips=len(c.rows), bytes=c.bytes)
+
+    def _video(self, i: int) -> np.ndarray:
+        fp = self.index[i][1][:-len(".wav")] + ".npy"
+        v = np.load(fp, allow_pickle=False)
+        if v.ndim == 4 and v.shape[-1] == 1:
+            v = v[..., 0]
+        if v.ndim != 3 or v.shape[1:] != (64, 64) or v.shape[0] < 1:
+            raise ValueError(f"{fp}: expected (F, 64, 64) or (F, 64, 64, 1) gray frames, got {v.shape}")
+        n = self.frames // 1000
+        # pytorchvideo.transforms.functional.uniform_temporal_subsample: linspace, clamp, truncate
+        at = np.clip(np.linspace(0, v.shape[0] - 1, n), 0, v.shape[0] - 1).astype(np.int64)
+        return np.ascontiguousarray(v[at], dtype=np.float32)[..., None]
+
+    def _indices(self, ids: List[int]) -> torch.Tensor:
+        """(B, N) int32 class indices of the clips on the device: cached rows as they are, the others read,
+        uploaded and sent through the front end in ONE launch pair."""
+        from .ops import audio_clip_descriptors, audio_frontend
+        cache, dev = self.cache, self.device
+        todo = [i for i in dict.fromkeys(ids) if i not in cache.rows]
+        cache.hits += sum(i in cache.rows for i in ids)
+        cache.misses += len(ids) - sum(i in cache.rows for i in ids)
+        fresh = {}
+        if todo:
+            clips = [read_wav_pcm16(self.index[i][1]) for i in todo]
+            total = sum(c[0].size for c in clips)
+            # (padded to a 256 Ki-sample step: batches of like-sized clips reuse the ring's pinned buffers)
+            pcm = np.zeros(-(-total // (1 << 18)) * (1 << 18), dtype=np.int16)
+            np.concatenate([c[0] for c in clips], out=pcm[:total])
+            frames, channels = [c[1] for c in clips], [c[2] for c in clips]
+            d_pcm = _PinnedRing.to_device(_ring("pcm", dev).stage(pcm), dev)
+            d_desc = _PinnedRing.to_device(
+                _ring("clips", dev).stage(audio_clip_descriptors(frames, channels)), dev)
+            idx = audio_frontend(d_pcm, frames, channels, self.Q, n_out=self.frames, normalize=self.normalize,
+                                 descriptors=d_desc)
+            for row, i in enumerate(todo):
+                fresh[i] = idx[row]
+                cache.put(i, idx[row])
+        if len(todo) == len(ids) and todo == list(ids):
+            return idx
+        return torch.stack([fresh[i] if i in fresh else cache.rows[i].to(torch.int32) for i in ids])
+
+    def __iter__(self) -> Iterator[Batch]:
+        if self.device is None or self.device.type != "cuda":
+            raise RuntimeError("WavFolderLoader: the waveform front end is a HIP kernel; pass device= an MI355X "
+                               "(there is no CPU path)")
+        from . import _native as N
+        order = self._order()
+        crop_rng = random.Random(self.seed * 31 + self.epoch * 7 + self.rank)
+        dev = self.device
+        for s in range(0, len(order), self.batch_size):
+            ids = order[s:s + self.batch_size]
+            with torch.cuda.device(dev):
+                idx = self._indices(ids)
+                B, T = idx.shape
+                if self.frac is not None:  # dataset.py:232-237, on the indices: only the crop is expanded
+                    n = math.ceil(T * self.frac)
+                    start = crop_rng.randint(0, T - n)
+                    idx, T = idx[:, start:start + n], n
+                audio = torch.empty(B, self.Q, T, dtype=torch.float32, device=dev)
+                N.check(N.lib().mvn_index_to_onehot(idx.data_ptr(), idx.stride(0), audio.data_ptr(), B, self.Q, T,
+                                                    torch.cuda.current_stream(dev).cuda_stream),
+                        "mvn_index_to_onehot")
+            video = None
+            if self.use_video:
+                video = _to_device_async(np.stack([self._video(i) for i in ids]), dev)
+            yield Batch(audio, video, [self.index[i][0] for i in ids], [self.filepaths[i] for i in ids],
+                        [self.info[i] for i in ids])
+
+
+def _is_wav_folder(filepath) -> bool:
+    import os
+    p = str(filepath)
+    return os.path.isdir(p) and (os.path.isdir(os.path.join(p, "train")) or os.path.isdir(os.path.join(p, "valid")))
+
+
 def get_dataloader(filepath, input_channels: int, batch_size: int = 64, train: bool = True,
                    rank: int = 0, world_size: int = 0, use_video: bool = True,
                    normalize_audio: bool = True, batch_subsample_frac: Optional[float] = None,
-                   **kwargs) -> SyntheticLoader:
-    """Signature of movenet/dataset.py:59-98."""
+                   **kwargs):
+    """Signature of movenet/dataset.py:59-98.  ``synthetic://...`` gives a SyntheticLoader; an existing directory
+    with a ``train`` or ``valid`` sub-folder gives a WavFolderLoader; anything else raises ValueError."""
+    if not str(filepath).startswith("synthetic://") and _is_wav_folder(filepath):
+        extra = {"cache_bytes": kwargs["cache_bytes"]} if "cache_bytes" in kwargs else {}
+        return WavFolderLoader(filepath, input_channels, batch_size, train=train, rank=rank,
+                               world_size=world_size, shuffle=kwargs.get("shuffle", False),
+                               batch_subsample_frac=batch_subsample_frac, use_video=use_video,
+                               normalize_audio=normalize_audio, device=kwargs.get("device"), **extra)
     return SyntheticLoader(str(filepath), input_channels, batch_size, train=train, rank=rank,
                            world_size=world_size, shuffle=kwargs.get("shuffle", False),
                            batch_subsample_frac=batch_subsample_frac, use_video=use_video,

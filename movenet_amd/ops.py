@@ -505,6 +505,74 @@ def mu_law_decode(index: torch.Tensor, quantization_channels: int) -> torch.Tens
     return out
 
 
+AUDIO_FRONTEND_MAX_RATIO = 100  # frames <= 100 n_out: the longest clip whose output tile's window fits the LDS
+
+
+def audio_clip_descriptors(frames, channels, offsets=None):
+    """Host array of mvn_audio_clip records (int64 offset, int32 frames, int32 channels) as (B, 4) int32;
+    ``offsets`` default to the clips lying back to back in the upload."""
+    import numpy as np
+    rec = np.zeros(len(frames), dtype=[("offset", "<i8"), ("frames", "<i4"), ("channels", "<i4")])
+    rec["frames"], rec["channels"] = frames, channels
+    if offsets is None:
+        spans = rec["frames"].astype(np.int64) * rec["channels"]
+        offsets = np.concatenate([[0], np.cumsum(spans)[:-1]]) if len(spans) else []
+    rec["offset"] = offsets
+    return rec.view(np.int32).reshape(len(frames), 4)
+
+
+def audio_frontend(pcm: torch.Tensor, frames, channels, quantization_channels: int, n_out: int = None,
+                   normalize: bool = True, offsets=None, descriptors: torch.Tensor = None,
+                   return_waveform: bool = False, out: torch.Tensor = None, waveform_out: torch.Tensor = None):
+    """Waveforms -> class indices on the GPU (mvn_audio_frontend): channel mean, resample of each whole clip to
+    ``n_out`` frames (default MAX_AUDIO_FRAMES; sinc_interp_hann, width 6, roll-off 0.99), min-max normalisation,
+    mu-law.
+
+    ``pcm``: 1-D int16 tensor on the GPU, the clips' interleaved samples (8-bit files as ``(v - 128) << 8``, 24- and
+    32-bit files rounded to 16 bits: dataset.read_wav_pcm16).  ``frames`` / ``channels`` / ``offsets``: per clip, host
+    sequences (offsets default to back-to-back), checked here against the upload; ``descriptors`` is the same
+    already on the device ((B, 4) int32 of audio_clip_descriptors -- the loader ships it through its pinned ring).
+    Returns (B, n_out) int32 indices, with ``return_waveform`` also the (B, n_out) fp32 waveform before
+    normalisation.  Nothing here waits for the GPU."""
+    _require_gpu(pcm, "pcm")
+    if pcm.dtype != torch.int16 or pcm.dim() != 1 or not pcm.is_contiguous():
+        raise ValueError("pcm must be a contiguous 1-D int16 tensor")
+    if n_out is None:
+        from . import wavenet as W
+        n_out = W.MAX_AUDIO_FRAMES
+    B = len(frames)
+    if B < 1 or len(channels) != B:
+        raise ValueError("frames and channels must name the same, non-zero number of clips")
+    desc = audio_clip_descriptors(frames, channels, offsets)
+    rec = desc.view([("offset", "<i8"), ("frames", "<i4"), ("channels", "<i4")]).reshape(B)
+    for b in range(B):
+        o, n, c = int(rec["offset"][b]), int(rec["frames"][b]), int(rec["channels"][b])
+        if n < 1 or c < 1 or o < 0 or o + n * c > pcm.numel():
+            raise ValueError(f"clip {b}: {n} frames x {c} channels at offset {o} do not lie inside the "
+                             f"upload of {pcm.numel()} samples")
+        if n > AUDIO_FRONTEND_MAX_RATIO * n_out:
+            raise ValueError(f"clip {b}: {n} frames is more than {AUDIO_FRONTEND_MAX_RATIO} x the {n_out} "
+                             "output frames the front end resamples to")
+    dev = pcm.device
+    lib = N.lib()
+    with torch.cuda.device(dev):
+        if descriptors is None:
+            descriptors = torch.from_numpy(desc).to(dev)
+        if tuple(descriptors.shape) != (B, 4) or descriptors.dtype != torch.int32 or not descriptors.is_contiguous():
+            raise ValueError("descriptors must be a contiguous (B, 4) int32 tensor")
+        y = waveform_out if waveform_out is not None else torch.empty(B, n_out, dtype=torch.float32, device=dev)
+        idx = out if out is not None else torch.empty(B, n_out, dtype=torch.int32, device=dev)
+        for t, dt, what in ((y, torch.float32, "waveform_out"), (idx, torch.int32, "out")):
+            if tuple(t.shape) != (B, n_out) or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{what} must be a contiguous ({B}, {n_out}) {dt} tensor on {dev}")
+        scratch = torch.empty(max(int(lib.mvn_audio_frontend_scratch_floats(B, n_out)), 2), dtype=torch.float32,
+                              device=dev)
+        N.check(lib.mvn_audio_frontend(pcm.data_ptr(), pcm.numel(), descriptors.data_ptr(), B,
+                                       int(quantization_channels), int(n_out), int(bool(normalize)), y.data_ptr(),
+                                       scratch.data_ptr(), idx.data_ptr(), _stream_ptr(dev)), "mvn_audio_frontend")
+    return (idx, y) if return_waveform else idx
+
+
 class _CrossEntropyOnProbs(torch.autograd.Function):
     """loss, accuracy of the trainer (row F3): mvn_ce_on_probs_forward / _backward."""
 
