@@ -1,4 +1,4 @@
-// Shared by the generator kernels (generate.hip, generate_pipe.hip).
+// Shared by the generator kernels (generate.hip, generate_pipe.hip, generate_fold.hip, generate_pipe_h16.hip).
 #pragma once
 #include "common.h"
 
@@ -91,6 +91,25 @@ size_t fold_hand_floats(const mvn_dims *d, int batch);
 int fold_pack(const mvn_dims *d, const mvn_params *p, float *packed, hipStream_t s);
 int fold_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_floats_total,
                 size_t status_offset_floats, hipStream_t s);
+
+// ---- shared by the three pipelined variants (defined in generate_pipe.hip) ---------------
+// One launch of a pipelined generator kernel (GenArgs, u64 *hand, unsigned *err, int NS, int nb, int nseq):
+// co-residency and capacity check (MVN_ERR_UNSUPPORTED), hand-off area bounds (MVN_ERR_BAD_ARG), the memsets of
+// every polled word, then a cooperative launch where available and allowed (pipe_common.h), else an ordinary one.
+struct PipeLaunch {
+  const void *fn;       // the kernel
+  const char *name;     // the variant, for messages
+  int NT;               // threads per workgroup
+  size_t lds_bytes;     // dynamic LDS
+  int NS, GRAN;         // stages per pipeline, granules per inbox
+  int slots;            // grid = 8 workgroups (one per XCD) per slot
+  int pipes, batch;     // pipelines launched, sequences they serve
+  int max_batch, per_pipe;  // the variant's limits: sequences per launch, per pipeline
+};
+int pipe_launch_common(const PipeLaunch &p, const GenArgs &a, float *hand, size_t hand_floats_total,
+                       size_t status_offset_floats, hipStream_t s);
+// embedding tables [tap 2][256][C] of a packed blob, C = 64 or 128; classes >= qm (the model's count) are zero
+void pack_embed(int C, const float *causal_w, float *dst, int qm, hipStream_t s);
 
 // Hand-off area of the generator state, shared by the pipelined variants: [granules: the
 // largest variant's count][16 flag words, the sticky status word first][placement words]

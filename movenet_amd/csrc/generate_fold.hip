@@ -223,23 +223,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
   u64 *outbox = hand + ((size_t)b * NS + s_next) * GRAN;
   int *iflag = (int *)(smem + LDS_FLOATS - 16);  // [0] ok flag, [3] fast-edge flag
   float *pfs = smem + LDS_FLOATS;                // MULTI: [GMAX][C][PFS_F] (layer stages), head: indices
-  bool fast_edge = false;
-  {
-    unsigned *xcc = err + 16;  // [nb * NS] words, zeroed by the launch's memset
-    const unsigned mine = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xF) + 1;  // HW_REG_XCC_ID[3:0]
-    if (tid == 0) {
-      __hip_atomic_store(xcc + b * NS + s, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      unsigned other = 0;
-      for (unsigned spins = 0; spins < (1u << 20) && other == 0; ++spins) {
-        other = __hip_atomic_load(xcc + b * NS + s_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (other == 0) __builtin_amdgcn_s_sleep(8);
-      }
-      iflag[3] = (other == mine) ? 1 : 0;  // unknown (time-out) => the safe form
-    }
-    __syncthreads();
-    fast_edge = iflag[3] != 0;
-    __syncthreads();
-  }
+  const bool fast_edge = pipe_edge_is_fast(err + 16, b, s, s_next, NS, iflag);
 
   if (s < NS - 1) {
     // ================= layer stage: layers l0 .. l0 + nl - 1 =================
@@ -568,14 +552,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
     const float *b1 = hw + W1_F, *b2 = hw + W1_F + Q + W2_F;
     const f4 *WSp = (const f4 *)(hw + W1_F + Q + W2_F + Q);
     const float *bsl = hw + W1_F + Q + W2_F + Q + WSL_F;
-    int32_t *samples = a.samples + (size_t)b * a.stride;
     int *hidx = (int *)pfs;  // MULTI: [GMAX][2] = {idx_cur, idx_prev} of each sequence between its turns
-    auto bind = [&](int g) {
-      bq = b + g * nb;
-      inbox = hand + ((size_t)bq * NS + s) * GRAN;
-      outbox = hand + ((size_t)bq * NS + s_next) * GRAN;
-      samples = a.samples + (size_t)bq * a.stride;
-    };
 
     // last layer's skip 1x1: thread (cs = tid >> 3, q8 = tid & 7), 8 inputs;
     // conv1: thread (o1 = tid >> 1, q1 = tid & 1), 32 inputs; conv2: thread (og = tid >> 3,
@@ -596,64 +573,17 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
     const float bslr = bsl[og];
     __syncthreads();
 
-    int idx_cur = 0, idx_prev = -1;
-    auto send_h0 = [&](unsigned ep) {  // wave 0: xp = the causal conv's two embedding rows, zl = sk = 0
-      const int ic = min(max(idx_cur, 0), a.Q - 1), ip = min(idx_prev, a.Q - 1);
-      float v = E1[ic * C + lane];
-      if (ip >= 0) v += E0[ip * C + lane];
-      put_granule(outbox + lane, ep, v, fast_edge);
-      put_granule(outbox + C + lane, ep, 0.f, fast_edge);
-      put_granule(outbox + 2 * C + lane, ep, 0.f, fast_edge);
+    // (head_loop starts a step with xp = the causal conv's two embedding rows, zl = sk = 0)
+    auto await = [&](const u64 *inbox, unsigned epoch) {  // wave 0
+      float v[2];
+      const bool ok = wait_inbox64(inbox + C, epoch, err, v);  // zl (the last stage's xp' is not used)
+      if (ok && lane < 32) {
+        zlb[2 * lane] = v[0];
+        zlb[2 * lane + 1] = v[1];
+      }
+      return ok;
     };
-    for (int g = 0; g < G; ++g) {
-      if (MULTI) bind(g);
-      if (wave == 0) {
-        idx_cur = samples[a.t_begin];
-        idx_prev = a.t_begin > 0 ? samples[a.t_begin - 1] : -1;
-        if (a.t_begin < a.t_end) send_h0(1u);
-        MVN_STAMP(b, s, 0, 1);
-        if (MULTI && lane == 0) {
-          hidx[2 * g] = idx_cur;
-          hidx[2 * g + 1] = idx_prev;
-        }
-      }
-    }
-    if (MULTI) __syncthreads();
-
-    bool alive = true;
-    for (int ts = a.t_begin; ts < a.t_end && alive; ++ts)
-    for (int g = 0; g < G; ++g) {
-      if (MULTI) {
-        bind(g);
-        if (wave == 0) {  // (written by this wave's lane 0 a whole round ago)
-          idx_cur = hidx[2 * g];
-          idx_prev = hidx[2 * g + 1];
-        }
-      }
-      const unsigned epoch = (unsigned)(ts - a.t_begin + 1);
-      const int u = ts + 1;
-      const bool want_out = (a.logits_out || a.choices_out) && u >= a.logits_t0;
-      const bool do_head = u < a.n_total && (u >= a.n_given || want_out);  // block-uniform
-      int next_idx = 0;
-      // this step's Philox uniform, formed while the step's input is still on its way (the fence
-      // keeps it from being sunk to its use behind the head's barriers)
-      float uni = 0.f;
-      if (wave == 0 && a.temperature > 0.f) {
-        uni = philox_uniform(a.seed, (uint32_t)u, (uint32_t)bq);
-        asm volatile("" : "+v"(uni));
-      }
-      if (wave == 0) {
-        if (u < a.n_given) next_idx = samples[u];  // prompt / teacher forcing
-        float v[2];
-        const bool ok = wait_inbox64(inbox + C, epoch, err, v);  // zl (the last stage's xp' is not used)
-        if (ok && lane < 32) {
-          zlb[2 * lane] = v[0];
-          zlb[2 * lane + 1] = v[1];
-        }
-        if (lane == 0) iflag[0] = ok ? 1 : 0;
-      }
-      lds_barrier();
-      MVN_STAMP(b, s, ts - a.t_begin, 0);
+    auto logits = [&](const u64 *inbox, unsigned epoch, bool do_head) {
       const u64 sk_peek = peek_granule(inbox + 2 * C + og);
       float sv = 0.f;
       if (do_head) {
@@ -670,64 +600,22 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
       if (q2 == 0)
         skin = (unsigned)(sk_peek >> 32) == epoch ? __uint_as_float((unsigned)sk_peek)
                                                   : wait_granule(inbox + 2 * C + og, epoch, err);
-      if (do_head) {
-        // skip sum, then the head's first leaky-ReLU (modules.py:140)
-        if (q2 == 0) a0[og] = leaky(skin + (sv + bslr));
-        lds_barrier();
-        {
-          f4 x[8];
-          ldsn<8>(x, a0 + 32 * q1);
-          float hsum = dotn<8>(w1, x);
-          hsum += dpp_mov<DPP_XOR1>(hsum);
-          if (q1 == 0) a1[o1] = leaky(hsum + b1r);
-        }
-        lds_barrier();
-        {
-          f4 x[8];
-          ldsn<8>(x, a1 + 32 * q2);
-          float s0 = dotn<8>(w2[0], x), s1 = dotn<8>(w2[1], x);
-          float s2 = dotn<8>(w2[2], x), s3 = dotn<8>(w2[3], x);
-          s0 = quad_sum(s0); s0 += other_quad(s0);
-          s1 = quad_sum(s1); s1 += other_quad(s1);
-          s2 = quad_sum(s2); s2 += other_quad(s2);
-          s3 = quad_sum(s3); s3 += other_quad(s3);
-          const int sel = q2 & 3;
-          if (q2 < 4) lgb[4 * og + sel] = (sel == 0 ? s0 : sel == 1 ? s1 : sel == 2 ? s2 : s3) + b2r;
-        }
-        lds_barrier();
+      if (!do_head) return;
+      // skip sum, then the head's first leaky-ReLU (modules.py:140)
+      if (q2 == 0) a0[og] = leaky(skin + (sv + bslr));
+      lds_barrier();
+      {
+        f4 x[8];
+        ldsn<8>(x, a0 + 32 * q1);
+        float hsum = dotn<8>(w1, x);
+        hsum += dpp_mov<DPP_XOR1>(hsum);
+        if (q1 == 0) a1[o1] = leaky(hsum + b1r);
       }
-      if (wave == 0) {
-        if (do_head) {
-          const f4 lv = ((const f4 *)lgb)[lane];
-          const float lg[4] = {lv.x, lv.y, lv.z, lv.w};
-          if (a.logits_out && u >= a.logits_t0 && 4 * lane < a.Q)  // (rows of a.Q logits: the padding is not written)
-            ((f4 *)(a.logits_out + ((size_t)bq * (a.n_total - a.logits_t0) + (u - a.logits_t0)) * a.Q))[lane] = lv;
-          const int pick = choose_class(lg, a.temperature, uni, lane, a.Q);
-          if (u >= a.n_given) next_idx = pick;
-          idx_prev = idx_cur;
-          idx_cur = next_idx;
-          if (ts + 1 < a.t_end) send_h0(epoch + 1);
-          MVN_STAMP(b, s, ts + 1 - a.t_begin, 1);
-          if (lane == 0) {
-            if (a.choices_out && u >= a.logits_t0) a.choices_out[(size_t)bq * a.n_total + u] = pick;
-            if (u >= a.n_given) samples[u] = pick;
-          }
-        } else {
-          idx_prev = idx_cur;
-          idx_cur = next_idx;
-          if (ts + 1 < a.t_end) send_h0(epoch + 1);
-          MVN_STAMP(b, s, ts + 1 - a.t_begin, 1);
-        }
-        if (MULTI && lane == 0) {
-          hidx[2 * g] = idx_cur;
-          hidx[2 * g + 1] = idx_prev;
-        }
-      }
-      if (iflag[0] == 0) {  // hand-off timed out
-        alive = false;
-        break;
-      }
-    }
+      lds_barrier();
+      head_conv2_f32(w2, a1, lgb, og, q2, b2r);
+      lds_barrier();
+    };
+    head_loop<C, GRAN, MULTI, 2>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
   }
 }
 
@@ -803,29 +691,13 @@ __global__ void pack_fold_stage_kernel(FoldLayers p, float *__restrict__ dst) {
   dst[i] = (float)v;
 }
 
-// `qm`: the MODEL's class count (64, 128 or 256).  The head always runs 256 classes wide: classes >= qm are padding --
-// zero rows and columns, conv2 bias -inf, so that their logits are -inf (probability 0 in the first softmax;
-// choose_class masks them in the second) and they are never picked.
+// the fp32 head's sections (pipe_common.h: pack_head_f32), then the last layer's skip 1x1 and its bias
 __global__ void pack_fold_head_kernel(const float *w1, const float *b1, const float *w2, const float *b2,
                                       const float *sw_last, const float *sb_last, float *__restrict__ dst, int qm) {
   using namespace fold;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < W1_F) {
-    // conv1: [8][tid (512)] float4, thread (o1 = tid >> 1, q1 = tid & 1) owns 32 inputs
-    const int e = i & 3, v = i >> 2, tid = v & (NT - 1), i4 = v >> 9;
-    const int o = tid >> 1;
-    dst[i] = o < qm ? w1[(size_t)o * C + 32 * (tid & 1) + 4 * i4 + e] : 0.f;
-  } else if (i < W1_F + Q) {
-    dst[i] = i - W1_F < qm ? b1[i - W1_F] : 0.f;
-  } else if (i < W1_F + Q + W2_F) {
-    const int ii = i - W1_F - Q;
-    const int e = ii & 3, v = ii >> 2, tid = v & (NT - 1), rest = v >> 9, r = rest >> 3, i8 = rest & 7;
-    const int o = 4 * (tid >> 3) + r, k = 32 * (tid & 7) + 4 * i8 + e;
-    dst[i] = (o < qm && k < qm) ? w2[(size_t)o * qm + k] : 0.f;
-  } else if (i < W1_F + Q + W2_F + Q) {
-    const int o = i - W1_F - Q - W2_F;
-    dst[i] = o < qm ? b2[o] : -INFINITY;
-  } else if (i < W1_F + Q + W2_F + Q + WSL_F) {
+  if (pack_head_f32(i, C, C / 2, qm, w1, b1, w2, b2, dst)) return;
+  if (i < W1_F + Q + W2_F + Q + WSL_F) {
     // last layer's skip 1x1: [2][tid (512)] float4, thread (cs = tid >> 3, q8 = tid & 7) owns 8 inputs
     const int ii = i - (W1_F + Q + W2_F + Q);
     const int e = ii & 3, v = ii >> 2, tid = v & (NT - 1), i2 = v >> 9;
@@ -833,14 +705,6 @@ __global__ void pack_fold_head_kernel(const float *w1, const float *b1, const fl
   } else if (i < HEAD_F) {
     dst[i] = sb_last ? sb_last[i - (W1_F + Q + W2_F + Q + WSL_F)] : 0.f;
   }
-}
-
-__global__ void pack_fold_embed_kernel(const float *__restrict__ causal_w, float *__restrict__ dst, int qm) {
-  using namespace fold;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= EMB_F) return;
-  const int tap = i / (Q * C), r = i - tap * Q * C, qq = r / C, c = r - qq * C;
-  dst[i] = qq < qm ? causal_w[((size_t)c * qm + qq) * 2 + tap] : 0.f;
 }
 
 bool fold_ok(const mvn_dims *d) {
@@ -875,7 +739,7 @@ size_t fold_hand_floats(const mvn_dims *d, int batch) {
 int fold_pack(const mvn_dims *d, const mvn_params *p, float *packed, hipStream_t s) {
   using namespace fold;
   const int L = n_layers(d), NSL = fold_stages(d) - 1;
-  hipLaunchKernelGGL(pack_fold_embed_kernel, dim3((EMB_F + 255) / 256), dim3(256), 0, s, p->causal_w, packed, d->input_channels);
+  pack_embed(C, p->causal_w, packed, d->input_channels, s);
   for (int st = 0; st < NSL; ++st) {
     FoldLayers fl;
     for (int j = 0; j < 4; ++j) {
@@ -909,65 +773,26 @@ int fold_pack(const mvn_dims *d, const mvn_params *p, float *packed, hipStream_t
 int fold_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_floats_total,
                 size_t status_offset_floats, hipStream_t s) {
   using namespace fold;
-  int NS = fold_stages(d);
-  const int pipes = fold_launch_pipelines(d, batch);
-  const bool multi = batch > pipes;
-  const void *fn = multi ? (const void *)gen_fold_kernel<true> : (const void *)gen_fold_kernel<false>;
-  int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(gen_fold)");
-  if (rc) return rc;
-  const size_t lds_bytes = (multi ? LDS_FLOATS_MULTI : LDS_FLOATS) * sizeof(float);
-  int dev = 0, cus = 0, per_cu = 0, coop = 0;
-  if (check_hip(hipGetDevice(&dev), "hipGetDevice") ||
-      check_hip(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "hipDeviceGetAttribute(CUs)") ||
-      check_hip(hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev),
-                "hipDeviceGetAttribute(cooperative)") ||
-      check_hip(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, NT, lds_bytes),
-                "hipOccupancyMaxActiveBlocksPerMultiprocessor(gen_fold)"))
-    return MVN_ERR_LAUNCH;
-  const int slots = pipes <= fold_pipelines(d) ? (pipes + 7) / 8 * NS : PIPE_XCD_CUS;
-  if (cus < 8 * PIPE_XCD_CUS || batch > fold_max_batch(d) || per_cu < 1 || slots * 8 > per_cu * cus) {
-    set_error("FOLD variant: %d stages per pipeline, %d pipelines of at most %d sequences each on %d CUs (batch %d "
-              "asked for)", NS, cus < 8 * PIPE_XCD_CUS ? 0 : fold_pipelines_max(d), GMAX, cus, batch);
-    return MVN_ERR_UNSUPPORTED;
-  }
-  // hand-off area layout of the generator state: [granules ...][16 flag words at
-  // status_offset][placement words]; this variant's granules and placement words must fit
-  const size_t gran_floats = (size_t)batch * NS * GRAN * 2;
-  if (gran_floats > status_offset_floats || status_offset_floats + 16 + (size_t)batch * NS > hand_floats_total) {
-    set_error("FOLD variant: hand-off area too small (%zu granule floats, status word at %zu of %zu)",
-              gran_floats, status_offset_floats, hand_floats_total);
-    return MVN_ERR_BAD_ARG;
-  }
-  unsigned *err = (unsigned *)(hand + status_offset_floats);
-  rc = check_hip(hipMemsetAsync(hand, 0, gran_floats * sizeof(float), s), "hipMemsetAsync(granules)");
-  if (rc) return rc;
-  rc = check_hip(hipMemsetAsync(err + 16, 0, (hand_floats_total - status_offset_floats - 16) * sizeof(float), s),
-                 "hipMemsetAsync(placement words)");
-  if (rc) return rc;
-  u64 *gran = (u64 *)hand;
-  GenArgs args = a;
-  int nb = pipes, nseq = batch;
-  if (coop && pipe_cooperative_launch()) {
-    void *kargs[] = {(void *)&args, (void *)&gran, (void *)&err, (void *)&NS, (void *)&nb, (void *)&nseq};
-    return check_hip(hipLaunchCooperativeKernel(fn, dim3(slots * 8), dim3(NT), kargs, (unsigned)lds_bytes, s),
-                     "mvn_generate(fold, cooperative launch)");
-  }
-  if (multi)
-    hipLaunchKernelGGL(gen_fold_kernel<true>, dim3(slots * 8), dim3(NT), lds_bytes, s, args, gran, err, NS, nb, nseq);
-  else
-    hipLaunchKernelGGL(gen_fold_kernel<false>, dim3(slots * 8), dim3(NT), lds_bytes, s, args, gran, err, NS, nb, nseq);
-  return check_hip(hipGetLastError(), "mvn_generate(fold)");
+  PipeLaunch p;
+  p.name = "FOLD";
+  p.NT = NT;
+  p.NS = fold_stages(d);
+  p.GRAN = GRAN;
+  p.pipes = fold_launch_pipelines(d, batch);
+  const bool multi = batch > p.pipes;
+  p.fn = multi ? (const void *)gen_fold_kernel<true> : (const void *)gen_fold_kernel<false>;
+  p.lds_bytes = (multi ? LDS_FLOATS_MULTI : LDS_FLOATS) * sizeof(float);
+  // the kernel's own map: whole pipelines inside the XCDs, or every CU (the left-over ones form pipelines across XCDs)
+  p.slots = p.pipes <= fold_pipelines(d) ? (p.pipes + 7) / 8 * p.NS : PIPE_XCD_CUS;
+  p.batch = batch;
+  p.max_batch = fold_max_batch(d);
+  p.per_pipe = GMAX;
+  return pipe_launch_common(p, a, hand, hand_floats_total, status_offset_floats, s);
 }
 
 }  // namespace mvn
 
 #ifdef MVN_PIPE_STAMPS
-extern "C" int mvn_debug_read_stamps_fold(unsigned long long *out, size_t n) {
-  if (n > sizeof(mvn::g_stamps) / 8) n = sizeof(mvn::g_stamps) / 8;
-  return mvn::check_hip(hipMemcpyFromSymbol(out, HIP_SYMBOL(mvn::g_stamps), n * 8), "read stamps");
-}
-extern "C" int mvn_debug_read_fine_fold(unsigned long long *out, size_t n) {
-  if (n > sizeof(mvn::g_fine) / 8) n = sizeof(mvn::g_fine) / 8;
-  return mvn::check_hip(hipMemcpyFromSymbol(out, HIP_SYMBOL(mvn::g_fine), n * 8), "read fine");
-}
+extern "C" int mvn_debug_read_stamps_fold(unsigned long long *out, size_t n) { return mvn::debug_read(mvn::g_stamps, out, n, "read stamps"); }
+extern "C" int mvn_debug_read_fine_fold(unsigned long long *out, size_t n) { return mvn::debug_read(mvn::g_fine, out, n, "read fine"); }
 #endif

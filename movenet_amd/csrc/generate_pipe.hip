@@ -74,22 +74,8 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_kernel(GenArgs a, u64 *hand, 
   constexpr int NF4 = P::NF4, MAT_F = P::MAT_F, GRAN = P::GRAN, GL = P::GL, PFS_F = P::PFS_F;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // Workgroup i is dispatched to XCD i % 8 (observed; every edge verifies its placement
-  // below, so this is speed only -- but co-residency needs <= 32 workgroups per XCD, which
-  // the host checks with the same arithmetic).  A pipeline of NS <= 32 stages sits in
-  // one XCD so that its hops stay inside one L2; a longer one spans XS adjacent XCDs.
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
   int b, s;
-  if (NS <= PIPE_XCD_CUS) {
-    b = xcd + 8 * (slot / NS);
-    s = slot % NS;
-  } else {
-    const int XS = (NS + PIPE_XCD_CUS - 1) / PIPE_XCD_CUS, SPX = (NS + XS - 1) / XS;
-    b = xcd / XS;
-    s = (xcd % XS) * SPX + slot;
-    if (slot >= SPX || s >= NS) return;
-  }
-  if (b >= nb) return;
+  if (!pipe_place(blockIdx.x, NS, b, s) || b >= nb) return;
   // The status word is STICKY: raised by a timed-out hand-off, cleared only when the host
   // zeroes the generator state (RingGenerator.reset).  A launch that finds it raised does
   // nothing, so a failure in one advance() chunk cannot be papered over by the next one.
@@ -102,24 +88,7 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_kernel(GenArgs a, u64 *hand, 
   u64 *outbox = hand + ((size_t)b * NS + s_next) * GRAN;
   int *iflag = (int *)(smem + P::LDS_FLOATS - 16);  // [0] ok flag, [3] fast-edge flag
   float *pfs = smem + P::LDS_FLOATS;                // MULTI: [GMAX][C][PFS_F] (layer stages), head: indices
-  // placement handshake: publish my XCC id (+1), read my consumer's
-  bool fast_edge = false;
-  {
-    unsigned *xcc = err + 16;  // [nb * NS] words, zeroed by the launch's memset
-    const unsigned mine = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xF) + 1;  // HW_REG_XCC_ID[3:0]
-    if (tid == 0) {
-      __hip_atomic_store(xcc + b * NS + s, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      unsigned other = 0;
-      for (unsigned spins = 0; spins < (1u << 20) && other == 0; ++spins) {
-        other = __hip_atomic_load(xcc + b * NS + s_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (other == 0) __builtin_amdgcn_s_sleep(8);
-      }
-      iflag[3] = (other == mine) ? 1 : 0;  // unknown (time-out) => the safe form
-    }
-    __syncthreads();
-    fast_edge = iflag[3] != 0;
-    __syncthreads();
-  }
+  const bool fast_edge = pipe_edge_is_fast(err + 16, b, s, s_next, NS, iflag);
 
   if (s < NS - 1) {
     // ================= layer stage: layers l0 .. l0+nl-1 =================
@@ -252,37 +221,23 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_kernel(GenArgs a, u64 *hand, 
     for (int g = 0; g < G; ++g) {
       if (MULTI) bind(g);
       const unsigned epoch = (unsigned)(ts - a.t_begin + 1);
-      // The step starts as soon as the C residual-stream granules are in; the running skip sum
-      // (sent a little later by the producer, see below) is awaited by wave 4 while the filter/gate
-      // waves already work on the first layer.  (r3: C = 128 too -- one 16-byte poll per lane through
-      // poll16 instead of the two-load spin loop over 2C granules, and only the residual row of the
-      // residual|skip product on the chain.)
-      constexpr bool SPLIT = true;
+      // The step starts as soon as the C residual-stream granules (0..C-1) are in; the running skip sum
+      // (granules C..2C-1, sent a little later by the producer, see below) is awaited by wave 4 while the
+      // filter/gate waves already work on the first layer.  One 16-byte poll per lane through poll16 either way.
       if (wave == 0) {
+        float v[2];
         bool ok;
-        if constexpr (SPLIT && CC == 128) {
-          float v[2];
+        if constexpr (CC == 128) {
           ok = wait_inbox<2>(inbox, epoch, err, v);
           if (ok) {
             cur[2 * lane] = v[0];
             cur[2 * lane + 1] = v[1];
           }
-        } else if constexpr (SPLIT) {
-          float v[2];
+        } else {
           ok = wait_inbox64(inbox, epoch, err, v);
           if (ok && lane < 32) {
             cur[2 * lane] = v[0];
             cur[2 * lane + 1] = v[1];
-          }
-        } else {
-          float v[GL];
-          ok = wait_inbox<GL>(inbox, epoch, err, v);
-          if (ok) {
-            // granules 0..C-1 residual stream, C..2C-1 running skip sum
-            cur[2 * lane] = v[0];
-            cur[2 * lane + 1] = v[1];
-            skin[2 * lane] = v[GL - 2];
-            skin[2 * lane + 1] = v[GL - 1];
           }
         }
         if (lane == 0) iflag[0] = ok ? 1 : 0;
@@ -290,28 +245,25 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_kernel(GenArgs a, u64 *hand, 
       lds_barrier();
       MVN_STAMP(b, s, ts - a.t_begin, 0);
       load_pf(g);
-      if constexpr (SPLIT) {
-        if (wave == 4) {  // off the chain: the residual/skip waves idle during the first f/g phase
-          float v[2];
-          bool ok;
-          if constexpr (CC == 128) {
-            ok = wait_inbox<2>(inbox + C, epoch, err, v);
-            if (ok) {
-              skin[2 * lane] = v[0];
-              skin[2 * lane + 1] = v[1];
-            }
-          } else {
-            ok = wait_inbox64(inbox + C, epoch, err, v);
-            if (ok && lane < 32) {
-              skin[2 * lane] = v[0];
-              skin[2 * lane + 1] = v[1];
-            }
+      if (wave == 4) {  // off the chain: the residual/skip waves idle during the first f/g phase
+        float v[2];
+        bool ok;
+        if constexpr (CC == 128) {
+          ok = wait_inbox<2>(inbox + C, epoch, err, v);
+          if (ok) {
+            skin[2 * lane] = v[0];
+            skin[2 * lane + 1] = v[1];
           }
-          if (lane == 0) iflag[1] = ok ? 1 : 0;
+        } else {
+          ok = wait_inbox64(inbox + C, epoch, err, v);
+          if (ok && lane < 32) {
+            skin[2 * lane] = v[0];
+            skin[2 * lane + 1] = v[1];
+          }
         }
+        if (lane == 0) iflag[1] = ok ? 1 : 0;
       }
       float skipacc = 0.f;
-      if constexpr (!SPLIT) skipacc = (!fg_group && lead) ? skin[c] : 0.f;
 #pragma unroll
       for (int j = 0; j < LPS; ++j)
         if (j < nl) {
@@ -329,67 +281,46 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_kernel(GenArgs a, u64 *hand, 
             old = cur[c];  // this layer's input: residual add below, queue push later
           }
           lds_barrier();
-          if constexpr (SPLIT) {
-            // Only the residual row is on the chain: it is finished and published first; the
-            // skip row (same z, kept in registers) follows behind the barrier, while the
-            // filter/gate waves are already on the next layer.
-            f4 xz[CC == 64 ? NF4 : 1];  // C = 64: z stays in registers for the skip row; C = 128: re-read
-            if (!fg_group) {
-              if (j == 0) MVN_FINE(b, s, ts - a.t_begin, 2, 256);
-              if (j == 0 && lead) skipacc = skin[c];  // wave 4 stored it before this barrier
-              float r;
-              if constexpr (CC == 64) {
-                ldsn<NF4>(xz, zb + KPER * kq);
-                r = chan_sum<KQ>(dotn<NF4>(wa[j], xz));
-              } else {
-                r = chan_sum<KQ>(dot1_lds<NF4>(wa[j], zb + KPER * kq));
-              }
-              if (j == 0) MVN_FINE(b, s, ts - a.t_begin, 3, 256);
-              if (lead) {
-                xs[j] = old;
-                const float outv = (r + bias_r[j]) + old;
-                cur[c] = outv;
-                if (j == nl - 1) put_granule(outbox + c, epoch, outv, fast_edge);  // hand on at once
-              }
-              if (j == 0) MVN_FINE(b, s, ts - a.t_begin, 4, 256);
+          // Only the residual row is on the chain: it is finished and published first; the
+          // skip row (same z, kept in registers) follows behind the barrier, while the
+          // filter/gate waves are already on the next layer.
+          f4 xz[CC == 64 ? NF4 : 1];  // C = 64: z stays in registers for the skip row; C = 128: re-read
+          if (!fg_group) {
+            if (j == 0) MVN_FINE(b, s, ts - a.t_begin, 2, 256);
+            if (j == 0 && lead) skipacc = skin[c];  // wave 4 stored it before this barrier
+            float r;
+            if constexpr (CC == 64) {
+              ldsn<NF4>(xz, zb + KPER * kq);
+              r = chan_sum<KQ>(dotn<NF4>(wa[j], xz));
+            } else {
+              r = chan_sum<KQ>(dot1_lds<NF4>(wa[j], zb + KPER * kq));
             }
-            lds_barrier();
-            if (!fg_group) {
-              // (C = 128: one layer per stage, so zb is untouched until the next step's first phase)
-              float k;
-              if constexpr (CC == 64) k = chan_sum<KQ>(dotn<NF4>(wb[j], xz));
-              else k = chan_sum<KQ>(dot1_lds<NF4>(wb[j], zb + KPER * kq));
-              if (lead) {
-                skipacc += k + bias_s[j];
-                if (j == nl - 1) put_granule(outbox + C + c, epoch, skipacc, fast_edge);
-              }
+            if (j == 0) MVN_FINE(b, s, ts - a.t_begin, 3, 256);
+            if (lead) {
+              xs[j] = old;
+              const float outv = (r + bias_r[j]) + old;
+              cur[c] = outv;
+              if (j == nl - 1) put_granule(outbox + c, epoch, outv, fast_edge);  // hand on at once
             }
-          } else {
-            if (!fg_group) {
-              float r, k;
-              dot2_lds<NF4>(wa[j], wb[j], zb + KPER * kq, r, k);
-              r = chan_sum<KQ>(r);
-              k = chan_sum<KQ>(k);
-              if (lead) {
-                xs[j] = old;
-                const float outv = (r + bias_r[j]) + old;
-                cur[c] = outv;
-                skipacc += k + bias_s[j];
-                if (j == nl - 1) {
-                  // the stage's last layer: hand the activation on before anything else
-                  put_granule(outbox + c, epoch, outv, fast_edge);
-                  put_granule(outbox + C + c, epoch, skipacc, fast_edge);
-                }
-              }
+            if (j == 0) MVN_FINE(b, s, ts - a.t_begin, 4, 256);
+          }
+          lds_barrier();
+          if (!fg_group) {
+            // (C = 128: one layer per stage, so zb is untouched until the next step's first phase)
+            float k;
+            if constexpr (CC == 64) k = chan_sum<KQ>(dotn<NF4>(wb[j], xz));
+            else k = chan_sum<KQ>(dot1_lds<NF4>(wb[j], zb + KPER * kq));
+            if (lead) {
+              skipacc += k + bias_s[j];
+              if (j == nl - 1) put_granule(outbox + C + c, epoch, skipacc, fast_edge);
             }
-            lds_barrier();
           }
           if (j == 0) MVN_FINE(b, s, ts - a.t_begin, 5, 0);
         }
       MVN_STAMP(b, s, ts - a.t_begin, 1);
       // hand-off timed out (checked after the step: off the chain; iflag[1] was written by wave 4
       // before the first f/g -> r/s barrier of this step)
-      if (iflag[0] == 0 || (SPLIT && iflag[1] == 0)) {
+      if (iflag[0] == 0 || iflag[1] == 0) {
         alive = false;
         break;
       }
@@ -422,14 +353,7 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_kernel(GenArgs a, u64 *hand, 
     const float *hw = a.w + P::EMB_F + (size_t)L * P::LAYER_F;
     const f4 *W1p = (const f4 *)hw, *W2p = (const f4 *)(hw + P::W1_F + Q);
     const float *b1 = hw + P::W1_F, *b2 = hw + P::W1_F + Q + P::W2_F;
-    int32_t *samples = a.samples + (size_t)b * a.stride;
     int *hidx = (int *)pfs;  // MULTI: [GMAX][2] = {idx_cur, idx_prev} of each sequence between its turns
-    auto bind = [&](int g) {
-      bq = b + g * nb;
-      inbox = hand + ((size_t)bq * NS + s) * GRAN;
-      outbox = hand + ((size_t)bq * NS + s_next) * GRAN;
-      samples = a.samples + (size_t)bq * a.stride;
-    };
 
     // conv1: thread (o1 = tid>>1, q1 = tid&1), C/2 inputs; conv2: thread (og = tid>>3,
     // q2 = tid&7), 4 outputs x 32 inputs
@@ -449,141 +373,40 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_kernel(GenArgs a, u64 *hand, 
     const float b2r = b2[4 * og + (q2 & 3)];
     __syncthreads();
 
-    // Wave 0 closes every step alone (softmax, choice) and immediately opens the next
-    // one: it gathers the two embedding rows of the causal conv (modules.py:28-30 on a
-    // one-hot input) and hands them to stage 0, so no barrier sits between the choice
-    // and the next step's first hop.
-    int idx_cur = 0, idx_prev = -1;
-    auto send_h0 = [&](unsigned ep) {  // wave 0: granules c = residual, C + c = skip sum 0
-      const int ic = min(max(idx_cur, 0), a.Q - 1), ip = min(idx_prev, a.Q - 1);
-#pragma unroll
-      for (int j = 0; j < C / 64; ++j) {
-        const int ch = lane + 64 * j;
-        float v = E1[ic * C + ch];
-        if (ip >= 0) v += E0[ip * C + ch];
-        put_granule(outbox + ch, ep, v, fast_edge);
-        put_granule(outbox + C + ch, ep, 0.f, fast_edge);
-      }
-    };
-    for (int g = 0; g < G; ++g) {
-      if (MULTI) bind(g);
-      if (wave == 0) {
-        idx_cur = samples[a.t_begin];
-        idx_prev = a.t_begin > 0 ? samples[a.t_begin - 1] : -1;
-        if (a.t_begin < a.t_end) send_h0(1u);
-        MVN_STAMP(b, s, 0, 1);
-        if (MULTI && lane == 0) {
-          hidx[2 * g] = idx_cur;
-          hidx[2 * g + 1] = idx_prev;
-        }
-      }
-    }
-    if (MULTI) __syncthreads();
-
-    bool alive = true;
-    for (int ts = a.t_begin; ts < a.t_end && alive; ++ts)
-    for (int g = 0; g < G; ++g) {
-      if (MULTI) {
-        bind(g);
-        if (wave == 0) {  // (written by this wave's lane 0 a whole round ago)
-          idx_cur = hidx[2 * g];
-          idx_prev = hidx[2 * g + 1];
-        }
-      }
-      const unsigned epoch = (unsigned)(ts - a.t_begin + 1);
-      const int u = ts + 1;
-      const bool want_out = (a.logits_out || a.choices_out) && u >= a.logits_t0;
-      const bool do_head = u < a.n_total && (u >= a.n_given || want_out);  // block-uniform
-      int next_idx = 0;
-      // this step's Philox uniform, formed while the step's input is still on its way (the fence
-      // keeps it from being sunk to its use behind the head's barriers)
-      float uni = 0.f;
-      if (wave == 0 && a.temperature > 0.f) {
-        uni = philox_uniform(a.seed, (uint32_t)u, (uint32_t)bq);
-        asm volatile("" : "+v"(uni));
-      }
-      if (wave == 0) {
-        if (u < a.n_given) next_idx = samples[u];  // prompt / teacher forcing
-        float v[GL];
-        const bool ok = wait_inbox<GL>(inbox, epoch, err, v);
-        if (ok) {
-          // only the skip sum (granules C..2C-1) feeds the head
-          if (GL == 2) {
-            if (lane >= 32) {
-              a0[2 * (lane - 32)] = leaky(v[0]);
-              a0[2 * (lane - 32) + 1] = leaky(v[1]);
-            }
-          } else {
-            a0[2 * lane] = leaky(v[GL - 2]);
-            a0[2 * lane + 1] = leaky(v[GL - 1]);
-          }
-        }
-        if (lane == 0) iflag[0] = ok ? 1 : 0;
-      }
-      lds_barrier();
-      MVN_STAMP(b, s, ts - a.t_begin, 0);
-      if (do_head) {
-        {
-          float hsum;
-          if constexpr (TABLES_IN_LDS) {
-            f4 x[W1N4];
-            ldsn<W1N4>(x, a0 + P::W1N * q1);
-            hsum = dotn<W1N4>(w1, x);
-          } else {
-            hsum = dot_stream<W1N4>((const f4 *)big, NT, tid, a0 + P::W1N * q1);
-          }
-          hsum += dpp_mov<DPP_XOR1>(hsum);
-          if (q1 == 0) a1[o1] = leaky(hsum + b1r);
-        }
-        lds_barrier();
-        {
-          f4 x[8];
-          ldsn<8>(x, a1 + 32 * q2);
-          float s0 = dotn<8>(w2[0], x), s1 = dotn<8>(w2[1], x);
-          float s2 = dotn<8>(w2[2], x), s3 = dotn<8>(w2[3], x);
-          s0 = quad_sum(s0); s0 += other_quad(s0);
-          s1 = quad_sum(s1); s1 += other_quad(s1);
-          s2 = quad_sum(s2); s2 += other_quad(s2);
-          s3 = quad_sum(s3); s3 += other_quad(s3);
-          const int sel = q2 & 3;
-          if (q2 < 4) lgb[4 * og + sel] = (sel == 0 ? s0 : sel == 1 ? s1 : sel == 2 ? s2 : s3) + b2r;
-        }
-        lds_barrier();
-      }
-      if (wave == 0) {
-        if (do_head) {
-          // lane i owns classes 4i..4i+3; every reduction is intra-wave (DPP + readlane)
-          const f4 lv = ((const f4 *)lgb)[lane];
-          float lg[4] = {lv.x, lv.y, lv.z, lv.w};
-          if (a.logits_out && u >= a.logits_t0 && 4 * lane < a.Q)  // (rows of a.Q logits: the padding is not written)
-            ((f4 *)(a.logits_out +
-                    ((size_t)bq * (a.n_total - a.logits_t0) + (u - a.logits_t0)) * a.Q))[lane] = lv;
-          const int pick = choose_class(lg, a.temperature, uni, lane, a.Q);
-          if (u >= a.n_given) next_idx = pick;
-          idx_prev = idx_cur;
-          idx_cur = next_idx;
-          if (ts + 1 < a.t_end) send_h0(epoch + 1);
-          MVN_STAMP(b, s, ts + 1 - a.t_begin, 1);
-          if (lane == 0) {
-            if (a.choices_out && u >= a.logits_t0) a.choices_out[(size_t)bq * a.n_total + u] = pick;
-            if (u >= a.n_given) samples[u] = pick;
+    auto await = [&](const u64 *inbox, unsigned epoch) {  // wave 0
+      float v[GL];
+      const bool ok = wait_inbox<GL>(inbox, epoch, err, v);
+      if (ok) {
+        // only the skip sum (granules C..2C-1) feeds the head
+        if (GL == 2) {
+          if (lane >= 32) {
+            a0[2 * (lane - 32)] = leaky(v[0]);
+            a0[2 * (lane - 32) + 1] = leaky(v[1]);
           }
         } else {
-          idx_prev = idx_cur;
-          idx_cur = next_idx;
-          if (ts + 1 < a.t_end) send_h0(epoch + 1);
-          MVN_STAMP(b, s, ts + 1 - a.t_begin, 1);
-        }
-        if (MULTI && lane == 0) {
-          hidx[2 * g] = idx_cur;
-          hidx[2 * g + 1] = idx_prev;
+          a0[2 * lane] = leaky(v[GL - 2]);
+          a0[2 * lane + 1] = leaky(v[GL - 1]);
         }
       }
-      if (iflag[0] == 0) {  // hand-off timed out
-        alive = false;
-        break;
+      return ok;
+    };
+    auto logits = [&](const u64 *, unsigned, bool do_head) {
+      if (!do_head) return;
+      float hsum;
+      if constexpr (TABLES_IN_LDS) {
+        f4 x[W1N4];
+        ldsn<W1N4>(x, a0 + P::W1N * q1);
+        hsum = dotn<W1N4>(w1, x);
+      } else {
+        hsum = dot_stream<W1N4>((const f4 *)big, NT, tid, a0 + P::W1N * q1);
       }
-    }
+      hsum += dpp_mov<DPP_XOR1>(hsum);
+      if (q1 == 0) a1[o1] = leaky(hsum + b1r);
+      lds_barrier();
+      head_conv2_f32(w2, a1, lgb, og, q2, b2r);
+      lds_barrier();
+    };
+    head_loop<C, GRAN, MULTI, 1>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
   }
 }
 
@@ -612,40 +435,25 @@ __global__ void pack_layer_pipe_kernel(const float *fw, const float *gw, const f
     dst[i] = rs_elem(rw, sw, C, row, k);
 }
 
-// `qm`: the model's class count (64, 128 or 256); the head runs 256 wide, classes >= qm are padding (zero rows and
-// columns, conv2 bias -inf: see pack_fold_head_kernel)
 template <int CC>
 __global__ void pack_head_pipe_kernel(const float *w1, const float *b1, const float *w2,
                                       const float *b2, float *__restrict__ dst, int qm) {
-  using P = PipeCfg<CC>;
-  constexpr int C = P::C, Q = P::Q, NT = P::NT, W1N = P::W1N;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < P::W1_F) {
-    // conv1: [W1N/4][tid (512)] float4, thread (o1 = tid>>1, q1 = tid&1) owns W1N inputs
-    const int e = i & 3, v = i >> 2, tid = v & (NT - 1), i4 = v >> 9;
-    const int o = tid >> 1;
-    dst[i] = o < qm ? w1[(size_t)o * C + W1N * (tid & 1) + 4 * i4 + e] : 0.f;
-  } else if (i < P::W1_F + Q) {
-    dst[i] = i - P::W1_F < qm ? b1[i - P::W1_F] : 0.f;
-  } else if (i < P::W1_F + Q + P::W2_F) {
-    const int ii = i - P::W1_F - Q;
-    const int e = ii & 3, v = ii >> 2, tid = v & (NT - 1), rest = v >> 9, r = rest >> 3, i8 = rest & 7;
-    const int o = 4 * (tid >> 3) + r, k = 32 * (tid & 7) + 4 * i8 + e;
-    dst[i] = (o < qm && k < qm) ? w2[(size_t)o * qm + k] : 0.f;
-  } else if (i < P::HEAD_F) {
-    const int o = i - P::W1_F - Q - P::W2_F;
-    dst[i] = o < qm ? b2[o] : -INFINITY;
-  }
+  pack_head_f32(blockIdx.x * blockDim.x + threadIdx.x, CC, PipeCfg<CC>::W1N, qm, w1, b1, w2, b2, dst);
 }
 
-template <int CC>
-__global__ void pack_embed_pipe_kernel(const float *__restrict__ causal_w, float *__restrict__ dst, int qm) {
-  using P = PipeCfg<CC>;
-  constexpr int C = P::C, Q = P::Q;
+// the embedding tables of every pipelined variant: [tap 2][Q = 256][C] fp32, classes >= qm zero
+template <int C>
+__global__ void pack_embed_kernel(const float *__restrict__ causal_w, float *__restrict__ dst, int qm) {
+  constexpr int Q = HEAD_Q;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P::EMB_F) return;
+  if (i >= 2 * Q * C) return;
   const int tap = i / (Q * C), r = i - tap * Q * C, qq = r / C, c = r - qq * C;
   dst[i] = qq < qm ? causal_w[((size_t)c * qm + qq) * 2 + tap] : 0.f;
+}
+void pack_embed(int C, const float *causal_w, float *dst, int qm, hipStream_t s) {
+  const dim3 grid((2 * HEAD_Q * C + 255) / 256);
+  if (C == 64) hipLaunchKernelGGL(pack_embed_kernel<64>, grid, dim3(256), 0, s, causal_w, dst, qm);
+  else hipLaunchKernelGGL(pack_embed_kernel<128>, grid, dim3(256), 0, s, causal_w, dst, qm);
 }
 
 template <int CC>
@@ -673,12 +481,7 @@ bool pipe_ok(const mvn_dims *d) {
 }
 static int pipe_lps(const mvn_dims *d) { return d->residual_channels == 64 ? 4 : 1; }
 int pipe_stages(const mvn_dims *d) { return (n_layers(d) + pipe_lps(d) - 1) / pipe_lps(d) + 1; }
-int pipe_pipelines(const mvn_dims *d) {
-  // the kernel's placement: NS <= 32 -> floor(32/NS) pipelines in each of the 8 XCDs,
-  // otherwise one pipeline per group of ceil(NS/32) XCDs
-  const int NS = pipe_stages(d);
-  return NS <= PIPE_XCD_CUS ? 8 * (PIPE_XCD_CUS / NS) : 8 / ((NS + PIPE_XCD_CUS - 1) / PIPE_XCD_CUS);
-}
+int pipe_pipelines(const mvn_dims *d) { return pipe_pipelines_of(pipe_stages(d)); }
 int pipe_max_batch(const mvn_dims *d) {  // each pipeline serves up to GMAX sequences in turn
   return (d->residual_channels == 64 ? PipeCfg<64>::GMAX : PipeCfg<128>::GMAX) * pipe_pipelines(d);
 }
@@ -698,8 +501,7 @@ template <int CC>
 static int pipe_pack_t(const mvn_dims *d, const mvn_params *p, float *packed, hipStream_t s) {
   using P = PipeCfg<CC>;
   const int L = n_layers(d);
-  hipLaunchKernelGGL(pack_embed_pipe_kernel<CC>, dim3((P::EMB_F + 255) / 256), dim3(256), 0, s,
-                     p->causal_w, packed, d->input_channels);
+  pack_embed(CC, p->causal_w, packed, d->input_channels, s);
   for (int l = 0; l < L; ++l)
     hipLaunchKernelGGL(pack_layer_pipe_kernel<CC>, dim3((P::LAYER_F + 255) / 256), dim3(256), 0, s,
                        p->filter_w[l], p->gate_w[l], p->residual_w[l], p->residual_b[l], p->skip_w[l],
@@ -734,76 +536,73 @@ int pipe_pack_ctx(const mvn_dims *d, const mvn_params *p, float *ctx_section, hi
 // repeats the same check with the occupancy query.  Another PROCESS holding CUs can still
 // starve a stage: then the bounded spins raise the sticky status word and the caller
 // (WaveNet.generate) reruns the call on a kernel without hand-offs.
-template <int CC>
-static int pipe_launch_t(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_total,
-                         size_t status_off, hipStream_t s) {
-  using P = PipeCfg<CC>;
-  int NS = pipe_stages(d);
-  // up to pipe_pipelines(d) sequences: one per pipeline; more: ceil(batch / pipelines) each, in turn
-  const int pipes = std::min(batch, pipe_pipelines(d));
-  const bool multi = batch > pipes;
-  const void *fn = multi ? (const void *)gen_pipe_kernel<CC, true> : (const void *)gen_pipe_kernel<CC, false>;
-  int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(gen_pipe)");
+int pipe_launch_common(const PipeLaunch &p, const GenArgs &a, float *hand, size_t hand_total, size_t status_off,
+                       hipStream_t s) {
+  int rc = ensure_max_dynamic_lds(p.fn, "hipFuncSetAttribute(pipelined generator)");
   if (rc) return rc;
-  const size_t lds_bytes = (multi ? P::LDS_FLOATS_MULTI : P::LDS_FLOATS) * sizeof(float);
-  // grid: 8 workgroups (one per XCD) per slot; see the kernel's (xcd, slot) -> (b, s) map
-  const int XS = (NS + PIPE_XCD_CUS - 1) / PIPE_XCD_CUS;
-  const int slots = NS <= PIPE_XCD_CUS ? (pipes + 7) / 8 * NS : (NS + XS - 1) / XS;
   int dev = 0, cus = 0, per_cu = 0, coop = 0;
   if (check_hip(hipGetDevice(&dev), "hipGetDevice") ||
       check_hip(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev),
                 "hipDeviceGetAttribute(CUs)") ||
       check_hip(hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev),
                 "hipDeviceGetAttribute(cooperative)") ||
-      check_hip(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, P::NT, lds_bytes),
-                "hipOccupancyMaxActiveBlocksPerMultiprocessor(gen_pipe)"))
+      check_hip(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, p.fn, p.NT, p.lds_bytes),
+                "hipOccupancyMaxActiveBlocksPerMultiprocessor(pipelined generator)"))
     return MVN_ERR_LAUNCH;
-  if (per_cu < 1 || slots * 8 > per_cu * cus) {
-    set_error("PIPE variant: grid of %d workgroups is not co-resident (%d per CU x %d CUs)",
-              slots * 8, per_cu, cus);
+  if (cus < 8 * PIPE_XCD_CUS || p.batch > p.max_batch || per_cu < 1 || p.slots * 8 > per_cu * cus) {
+    set_error("%s variant: %d stages per pipeline, %d pipelines of at most %d sequences each on %d CUs "
+              "(batch %d asked for; grid of %d workgroups, %d per CU)", p.name, p.NS,
+              cus < 8 * PIPE_XCD_CUS ? 0 : p.max_batch / p.per_pipe, p.per_pipe, cus, p.batch, p.slots * 8, per_cu);
     return MVN_ERR_UNSUPPORTED;
   }
-  // Every polled word is re-initialised by memset nodes ahead of each launch: the granules
-  // and the placement words -- NOT the 16 flag words between them (the sticky status word).
-  const size_t gran_floats = (size_t)batch * NS * P::GRAN * 2;
-  if (gran_floats > status_off || status_off + 16 + (size_t)batch * NS > hand_total) {
-    set_error("PIPE variant: hand-off area too small");
+  // Hand-off area of the generator state: [granules ...][16 flag words at status_off][placement words]; this
+  // variant's granules and placement words must fit.  Every polled word is re-initialised by memset nodes ahead of
+  // each launch: the granules and the placement words -- NOT the 16 flag words between them (the sticky status word).
+  const size_t gran_floats = (size_t)p.batch * p.NS * p.GRAN * 2;
+  if (gran_floats > status_off || status_off + 16 + (size_t)p.batch * p.NS > hand_total) {
+    set_error("%s variant: hand-off area too small (%zu granule floats, status word at %zu of %zu)", p.name,
+              gran_floats, status_off, hand_total);
     return MVN_ERR_BAD_ARG;
   }
   unsigned *err = (unsigned *)(hand + status_off);
-  const size_t tail_floats = hand_total - status_off - 16;
   rc = check_hip(hipMemsetAsync(hand, 0, gran_floats * sizeof(float), s), "hipMemsetAsync(granules)");
   if (rc) return rc;
-  rc = check_hip(hipMemsetAsync(err + 16, 0, tail_floats * sizeof(float), s),
+  rc = check_hip(hipMemsetAsync(err + 16, 0, (hand_total - status_off - 16) * sizeof(float), s),
                  "hipMemsetAsync(placement words)");
   if (rc) return rc;
   u64 *gran = (u64 *)hand;
   GenArgs args = a;
-  int nb = pipes, nseq = batch;
+  int NS = p.NS, nb = p.pipes, nseq = p.batch;
   void *kargs[] = {(void *)&args, (void *)&gran, (void *)&err, (void *)&NS, (void *)&nb, (void *)&nseq};
+  const dim3 grid(p.slots * 8), block(p.NT);
   if (coop && pipe_cooperative_launch())
-    return check_hip(hipLaunchCooperativeKernel(fn, dim3(slots * 8), dim3(P::NT), kargs,
-                                                (unsigned)lds_bytes, s),
-                     "mvn_generate(pipe, cooperative launch)");
-  return check_hip(hipLaunchKernel(fn, dim3(slots * 8), dim3(P::NT), kargs, lds_bytes, s), "mvn_generate(pipe)");
+    return check_hip(hipLaunchCooperativeKernel(p.fn, grid, block, kargs, (unsigned)p.lds_bytes, s),
+                     "mvn_generate(pipelined, cooperative launch)");
+  return check_hip(hipLaunchKernel(p.fn, grid, block, kargs, p.lds_bytes, s), "mvn_generate(pipelined)");
 }
 
+template <int CC>
+static void pipe_launch_fill(PipeLaunch &p, bool multi) {
+  using P = PipeCfg<CC>;
+  p.fn = multi ? (const void *)gen_pipe_kernel<CC, true> : (const void *)gen_pipe_kernel<CC, false>;
+  p.lds_bytes = (multi ? P::LDS_FLOATS_MULTI : P::LDS_FLOATS) * sizeof(float);
+  p.GRAN = P::GRAN;
+  p.per_pipe = P::GMAX;
+}
 int pipe_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_total, size_t status_off,
                 hipStream_t s) {
-  const int NS = pipe_stages(d);
-  int dev = 0, cus = 0;
-  if (check_hip(hipGetDevice(&dev), "hipGetDevice")) return MVN_ERR_LAUNCH;
-  if (check_hip(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev),
-                "hipDeviceGetAttribute"))
-    return MVN_ERR_LAUNCH;
-  if (cus < 8 * PIPE_XCD_CUS || batch > pipe_max_batch(d)) {
-    set_error("PIPE variant: %d stages per pipeline, %d pipelines of at most %d sequences each on %d CUs "
-              "(batch %d asked for)", NS, cus < 8 * PIPE_XCD_CUS ? 0 : pipe_pipelines(d),
-              pipe_max_batch(d) / std::max(1, pipe_pipelines(d)), cus, batch);
-    return MVN_ERR_UNSUPPORTED;
-  }
-  return d->residual_channels == 64 ? pipe_launch_t<64>(a, d, batch, hand, hand_total, status_off, s)
-                                    : pipe_launch_t<128>(a, d, batch, hand, hand_total, status_off, s);
+  PipeLaunch p;
+  p.name = "PIPE";
+  p.NT = 512;
+  p.NS = pipe_stages(d);
+  // up to pipe_pipelines(d) sequences: one per pipeline; more: ceil(batch / pipelines) each, in turn
+  p.pipes = std::min(batch, pipe_pipelines(d));
+  p.slots = pipe_grid_slots(p.NS, p.pipes);
+  p.batch = batch;
+  p.max_batch = pipe_max_batch(d);
+  if (d->residual_channels == 64) pipe_launch_fill<64>(p, batch > p.pipes);
+  else pipe_launch_fill<128>(p, batch > p.pipes);
+  return pipe_launch_common(p, a, hand, hand_total, status_off, s);
 }
 
 }  // namespace mvn
@@ -812,12 +611,6 @@ extern "C" int mvn_gen_launch_is_cooperative(void) { return mvn::pipe_cooperativ
 
 
 #ifdef MVN_PIPE_STAMPS
-extern "C" int mvn_debug_read_stamps(unsigned long long *out, size_t n) {
-  if (n > sizeof(mvn::g_stamps) / 8) n = sizeof(mvn::g_stamps) / 8;
-  return mvn::check_hip(hipMemcpyFromSymbol(out, HIP_SYMBOL(mvn::g_stamps), n * 8), "read stamps");
-}
-extern "C" int mvn_debug_read_fine(unsigned long long *out, size_t n) {
-  if (n > sizeof(mvn::g_fine) / 8) n = sizeof(mvn::g_fine) / 8;
-  return mvn::check_hip(hipMemcpyFromSymbol(out, HIP_SYMBOL(mvn::g_fine), n * 8), "read fine");
-}
+extern "C" int mvn_debug_read_stamps(unsigned long long *out, size_t n) { return mvn::debug_read(mvn::g_stamps, out, n, "read stamps"); }
+extern "C" int mvn_debug_read_fine(unsigned long long *out, size_t n) { return mvn::debug_read(mvn::g_fine, out, n, "read fine"); }
 #endif

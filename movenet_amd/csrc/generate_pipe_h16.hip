@@ -100,20 +100,8 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_h16_kernel(GenArgs a, u64 *ha
   using namespace h16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // (xcd, slot) -> (sequence, stage): same placement as gen_pipe_kernel (speed only; every edge
-  // verifies its own placement below)
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  int b, s;
-  if (NS <= PIPE_XCD_CUS) {
-    b = xcd + 8 * (slot / NS);
-    s = slot % NS;
-  } else {
-    const int XS = (NS + PIPE_XCD_CUS - 1) / PIPE_XCD_CUS, SPX = (NS + XS - 1) / XS;
-    b = xcd / XS;
-    s = (xcd % XS) * SPX + slot;
-    if (slot >= SPX || s >= NS) return;
-  }
-  if (b >= nb) return;
+  int b, s;  // (sequence, stage): the placement of gen_pipe_kernel
+  if (!pipe_place(blockIdx.x, NS, b, s) || b >= nb) return;
   if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;  // sticky status
   const int L = a.L;
   const int s_next = s + 1 == NS ? 0 : s + 1;
@@ -123,23 +111,7 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_h16_kernel(GenArgs a, u64 *ha
   u64 *outbox = hand + ((size_t)b * NS + s_next) * GRAN;
   int *iflag = (int *)(smem_b + LDS_BYTES_M - 64);  // [0] ok flag, [3] fast-edge flag
   float *pfs = (float *)(smem_b + LDS_BYTES_M);     // MULTI: [GMAX][C][PFS_FM] (layer stages), head: indices
-  bool fast_edge = false;
-  {
-    unsigned *xcc = err + 16;
-    const unsigned mine = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xF) + 1;  // HW_REG_XCC_ID[3:0]
-    if (tid == 0) {
-      __hip_atomic_store(xcc + b * NS + s, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      unsigned other = 0;
-      for (unsigned spins = 0; spins < (1u << 20) && other == 0; ++spins) {
-        other = __hip_atomic_load(xcc + b * NS + s_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (other == 0) __builtin_amdgcn_s_sleep(8);
-      }
-      iflag[3] = (other == mine) ? 1 : 0;
-    }
-    __syncthreads();
-    fast_edge = iflag[3] != 0;
-    __syncthreads();
-  }
+  const bool fast_edge = pipe_edge_is_fast(err + 16, b, s, s_next, NS, iflag);
 
   if (s < NS - 1) {
     // ================= layer stage: layers l0 .. l0+nl-1 =================
@@ -409,14 +381,7 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_h16_kernel(GenArgs a, u64 *ha
     const float *hw = a.w + EMB_F + (size_t)L * LAYER_F;
     const h8 *W1p = (const h8 *)hw, *W2p = (const h8 *)(hw + W1_F + Q);
     const float *b1 = hw + W1_F, *b2 = hw + W1_F + Q + W2_F;
-    int32_t *samples = a.samples + (size_t)b * a.stride;
     int *hidx = (int *)pfs;  // MULTI: [GMAX][2] = {idx_cur, idx_prev} of each sequence between its turns
-    auto bind = [&](int g) {
-      bq = b + g * nb;
-      inbox = hand + ((size_t)bq * NS + s) * GRAN;
-      outbox = hand + ((size_t)bq * NS + s_next) * GRAN;
-      samples = a.samples + (size_t)bq * a.stride;
-    };
 
     // conv1: thread (o1 = tid>>1, q1 = tid&1), 64 inputs; conv2: thread (og = tid>>3, q2 = tid&7),
     // 4 outputs x 32 inputs
@@ -431,121 +396,39 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_h16_kernel(GenArgs a, u64 *ha
     const float b2r = b2[4 * og + (q2 & 3)];
     __syncthreads();
 
-    int idx_cur = 0, idx_prev = -1;
-    auto send_h0 = [&](unsigned ep) {  // wave 0: granules c = residual, C + c = skip sum 0
-      const int ic = min(max(idx_cur, 0), Q - 1), ip = min(idx_prev, Q - 1);
-#pragma unroll
-      for (int j = 0; j < C / 64; ++j) {
-        const int ch = lane + 64 * j;
-        float v = E1[ic * C + ch];
-        if (ip >= 0) v += E0[ip * C + ch];
-        put_granule(outbox + ch, ep, v, fast_edge);
-        put_granule(outbox + C + ch, ep, 0.f, fast_edge);
-      }
+    auto await = [&](const u64 *inbox, unsigned epoch) {  // wave 0
+      float v[GL];
+      const bool ok = wait_inbox<GL>(inbox + C, epoch, err, v);  // only the skip sum feeds the head
+      if (ok) *(h2 *)(a0h + 2 * lane) = h2{(_Float16)leaky(v[0]), (_Float16)leaky(v[1])};
+      return ok;
     };
-    for (int g = 0; g < G; ++g) {
-      if (MULTI) bind(g);
-      if (wave == 0) {
-        idx_cur = samples[a.t_begin];
-        idx_prev = a.t_begin > 0 ? samples[a.t_begin - 1] : -1;
-        if (a.t_begin < a.t_end) send_h0(1u);
-        MVN_STAMP(b, s, 0, 1);
-        if (MULTI && lane == 0) {
-          hidx[2 * g] = idx_cur;
-          hidx[2 * g + 1] = idx_prev;
-        }
-      }
-    }
-    if (MULTI) __syncthreads();
-
-    bool alive = true;
-    for (int ts = a.t_begin; ts < a.t_end && alive; ++ts)
-    for (int g = 0; g < G; ++g) {
-      if (MULTI) {
-        bind(g);
-        if (wave == 0) {  // (written by this wave's lane 0 a whole round ago)
-          idx_cur = hidx[2 * g];
-          idx_prev = hidx[2 * g + 1];
-        }
-      }
-      const unsigned epoch = (unsigned)(ts - a.t_begin + 1);
-      const int u = ts + 1;
-      const bool want_out = (a.logits_out || a.choices_out) && u >= a.logits_t0;
-      const bool do_head = u < a.n_total && (u >= a.n_given || want_out);  // block-uniform
-      int next_idx = 0;
-      // this step's Philox uniform, formed while the step's input is still on its way (the fence
-      // keeps it from being sunk to its use behind the head's barriers)
-      float uni = 0.f;
-      if (wave == 0 && a.temperature > 0.f) {
-        uni = philox_uniform(a.seed, (uint32_t)u, (uint32_t)bq);
-        asm volatile("" : "+v"(uni));
-      }
-      if (wave == 0) {
-        if (u < a.n_given) next_idx = samples[u];  // prompt / teacher forcing
-        float v[GL];
-        const bool ok = wait_inbox<GL>(inbox + C, epoch, err, v);  // only the skip sum feeds the head
-        if (ok) *(h2 *)(a0h + 2 * lane) = h2{(_Float16)leaky(v[0]), (_Float16)leaky(v[1])};
-        if (lane == 0) iflag[0] = ok ? 1 : 0;
+    auto logits = [&](const u64 *, unsigned, bool do_head) {
+      if (!do_head) return;
+      {
+        float hsum = dot_stream_h<W1NV>(big, NT, tid, a0h + (C / 2) * q1);
+        hsum = pair_sum(hsum);
+        if (q1 == 0) a1h[o1] = (_Float16)leaky(hsum + b1r);
       }
       lds_barrier();
-      MVN_STAMP(b, s, ts - a.t_begin, 0);
-      if (do_head) {
-        {
-          float hsum = dot_stream_h<W1NV>(big, NT, tid, a0h + (C / 2) * q1);
-          hsum = pair_sum(hsum);
-          if (q1 == 0) a1h[o1] = (_Float16)leaky(hsum + b1r);
-        }
-        lds_barrier();
-        {
-          h8 x[4];
+      {
+        h8 x[4];
 #pragma unroll
-          for (int i = 0; i < 4; ++i) x[i] = ((const h8 *)(a1h + 32 * q2))[i];
-          float sv[4];
+        for (int i = 0; i < 4; ++i) x[i] = ((const h8 *)(a1h + 32 * q2))[i];
+        float sv[4];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float e0 = dot8(w2[r][0], x[0], 0.f), e1 = dot8(w2[r][1], x[1], 0.f);
-            const float e2 = dot8(w2[r][2], x[2], 0.f), e3 = dot8(w2[r][3], x[3], 0.f);
-            float t4 = (e0 + e2) + (e1 + e3);
-            t4 = quad_sum(t4);
-            sv[r] = t4 + other_quad(t4);
-          }
-          const int sel = q2 & 3;
-          if (q2 < 4) lgb[4 * og + sel] = (sel == 0 ? sv[0] : sel == 1 ? sv[1] : sel == 2 ? sv[2] : sv[3]) + b2r;
+        for (int r = 0; r < 4; ++r) {
+          const float e0 = dot8(w2[r][0], x[0], 0.f), e1 = dot8(w2[r][1], x[1], 0.f);
+          const float e2 = dot8(w2[r][2], x[2], 0.f), e3 = dot8(w2[r][3], x[3], 0.f);
+          float t4 = (e0 + e2) + (e1 + e3);
+          t4 = quad_sum(t4);
+          sv[r] = t4 + other_quad(t4);
         }
-        lds_barrier();
+        const int sel = q2 & 3;
+        if (q2 < 4) lgb[4 * og + sel] = (sel == 0 ? sv[0] : sel == 1 ? sv[1] : sel == 2 ? sv[2] : sv[3]) + b2r;
       }
-      if (wave == 0) {
-        if (do_head) {
-          const f4 lv = ((const f4 *)lgb)[lane];
-          const float lg[4] = {lv.x, lv.y, lv.z, lv.w};
-          if (a.logits_out && u >= a.logits_t0)
-            ((f4 *)(a.logits_out + ((size_t)bq * (a.n_total - a.logits_t0) + (u - a.logits_t0)) * Q))[lane] = lv;
-          const int pick = choose_class(lg, a.temperature, uni, lane, Q);
-          if (u >= a.n_given) next_idx = pick;
-          idx_prev = idx_cur;
-          idx_cur = next_idx;
-          if (ts + 1 < a.t_end) send_h0(epoch + 1);
-          MVN_STAMP(b, s, ts + 1 - a.t_begin, 1);
-          if (lane == 0) {
-            if (a.choices_out && u >= a.logits_t0) a.choices_out[(size_t)bq * a.n_total + u] = pick;
-            if (u >= a.n_given) samples[u] = pick;
-          }
-        } else {
-          idx_prev = idx_cur;
-          idx_cur = next_idx;
-          if (ts + 1 < a.t_end) send_h0(epoch + 1);
-          MVN_STAMP(b, s, ts + 1 - a.t_begin, 1);
-        }
-        if (MULTI && lane == 0) {
-          hidx[2 * g] = idx_cur;
-          hidx[2 * g + 1] = idx_prev;
-        }
-      }
-      if (iflag[0] == 0) {  // hand-off timed out
-        alive = false;
-        break;
-      }
-    }
+      lds_barrier();
+    };
+    head_loop<C, GRAN, MULTI, 1>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
   }
 }
 
@@ -612,13 +495,6 @@ __global__ void pack_head_h16_kernel(const float *w1, const float *b1, const flo
     dst[W1_F + Q + W2_F + o] = b2[o];
   }
 }
-__global__ void pack_embed_h16_kernel(const float *__restrict__ causal_w, float *__restrict__ dst) {
-  using namespace h16;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= EMB_F) return;
-  const int tap = i / (Q * C), r = i - tap * Q * C, qq = r / C, c = r - qq * C;
-  dst[i] = causal_w[((size_t)c * Q + qq) * 2 + tap];
-}
 
 bool pipe_h16_ok(const mvn_dims *d) {
   return d->residual_channels == 128 && d->skip_channels == 128 && d->input_channels == 256 &&
@@ -629,10 +505,7 @@ int pipe_h16_stages(const mvn_dims *d) {
   constexpr int lps = h16::LpsM<true>::value;
   return (n_layers(d) + lps - 1) / lps + 1;
 }
-int pipe_h16_pipelines(const mvn_dims *d) {  // co-resident pipelines
-  const int NS = pipe_h16_stages(d);
-  return NS <= PIPE_XCD_CUS ? 8 * (PIPE_XCD_CUS / NS) : 8 / ((NS + PIPE_XCD_CUS - 1) / PIPE_XCD_CUS);
-}
+int pipe_h16_pipelines(const mvn_dims *d) { return pipe_pipelines_of(pipe_h16_stages(d)); }  // co-resident pipelines
 int pipe_h16_max_batch(const mvn_dims *d) { return h16::GMAX * pipe_h16_pipelines(d); }  // GMAX sequences each
 size_t pipe_h16_weights_floats(const mvn_dims *d) {
   return (size_t)h16::EMB_F + (size_t)n_layers(d) * h16::LAYER_F + h16::HEAD_F;
@@ -642,7 +515,7 @@ size_t pipe_h16_ctx_layer_floats() { return h16::CTX_LAYER_F; }
 int pipe_h16_pack(const mvn_dims *d, const mvn_params *p, float *packed, bool has_ctx, hipStream_t s) {
   using namespace h16;
   const int L = n_layers(d);
-  hipLaunchKernelGGL(pack_embed_h16_kernel, dim3((EMB_F + 255) / 256), dim3(256), 0, s, p->causal_w, packed);
+  pack_embed(C, p->causal_w, packed, Q, s);
   for (int l = 0; l < L; ++l)
     hipLaunchKernelGGL(pack_layer_h16_kernel, dim3((3 * MAT_H + 2 * C + 255) / 256), dim3(256), 0, s,
                        p->filter_w[l], p->gate_w[l], p->residual_w[l], p->residual_b[l], p->skip_w[l],
@@ -665,63 +538,27 @@ int pipe_h16_pack(const mvn_dims *d, const mvn_params *p, float *packed, bool ha
 int pipe_h16_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_total,
                     size_t status_off, hipStream_t s) {
   using namespace h16;
-  const int pipes = std::min(batch, pipe_h16_pipelines(d));
-  const bool multi = batch > pipes;
-  int dev = 0, cus = 0, per_cu = 0, coop = 0;
+  PipeLaunch p;
+  p.name = "PIPE_F16";
+  p.NT = NT;
+  p.GRAN = GRAN;
+  p.pipes = std::min(batch, pipe_h16_pipelines(d));
+  const bool multi = batch > p.pipes;
   // (a pipeline that serves one sequence runs three layers per stage)
   const int lps = multi ? LpsM<true>::value : LpsM<false>::value;
-  int NS = (n_layers(d) + lps - 1) / lps + 1;
-  const void *fn = multi ? (const void *)gen_pipe_h16_kernel<true> : (const void *)gen_pipe_h16_kernel<false>;
-  const int lds_bytes = multi ? LDS_BYTES_M_MULTI : LDS_BYTES_M;
-  int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(gen_pipe_h16)");
-  if (rc) return rc;
-  if (check_hip(hipGetDevice(&dev), "hipGetDevice") ||
-      check_hip(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev),
-                "hipDeviceGetAttribute(CUs)") ||
-      check_hip(hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev),
-                "hipDeviceGetAttribute(cooperative)") ||
-      check_hip(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, NT, lds_bytes),
-                "hipOccupancyMaxActiveBlocksPerMultiprocessor(gen_pipe_h16)"))
-    return MVN_ERR_LAUNCH;
-  const int XS = (NS + PIPE_XCD_CUS - 1) / PIPE_XCD_CUS;
-  const int slots = NS <= PIPE_XCD_CUS ? (pipes + 7) / 8 * NS : (NS + XS - 1) / XS;
-  if (cus < 8 * PIPE_XCD_CUS || batch > pipe_h16_max_batch(d) || per_cu < 1 || slots * 8 > per_cu * cus) {
-    set_error("PIPE_F16 variant: %d stages per pipeline, %d pipelines of at most %d sequences each on %d CUs "
-              "(batch %d asked for)", NS, cus < 8 * PIPE_XCD_CUS ? 0 : pipe_h16_pipelines(d), GMAX, cus, batch);
-    return MVN_ERR_UNSUPPORTED;
-  }
-  if ((size_t)batch * NS * GRAN * 2 > status_off || status_off + 16 + (size_t)batch * NS > hand_total) {
-    set_error("PIPE_F16 variant: hand-off area too small");
-    return MVN_ERR_BAD_ARG;
-  }
-  unsigned *err = (unsigned *)(hand + status_off);
-  const size_t tail_floats = hand_total - status_off - 16;
-  rc = check_hip(hipMemsetAsync(hand, 0, (size_t)batch * NS * GRAN * 2 * sizeof(float), s),
-                 "hipMemsetAsync(granules)");
-  if (rc) return rc;
-  rc = check_hip(hipMemsetAsync(err + 16, 0, tail_floats * sizeof(float), s), "hipMemsetAsync(placement words)");
-  if (rc) return rc;
-  u64 *gran = (u64 *)hand;
-  GenArgs args = a;
-  int nb = pipes, nseq = batch;
-  if (coop && pipe_cooperative_launch()) {
-    void *kargs[] = {(void *)&args, (void *)&gran, (void *)&err, (void *)&NS, (void *)&nb, (void *)&nseq};
-    return check_hip(hipLaunchCooperativeKernel(fn, dim3(slots * 8), dim3(NT), kargs, (unsigned)lds_bytes, s),
-                     "mvn_generate(pipe_f16, cooperative launch)");
-  }
-  void *kargs[] = {(void *)&args, (void *)&gran, (void *)&err, (void *)&NS, (void *)&nb, (void *)&nseq};
-  return check_hip(hipLaunchKernel(fn, dim3(slots * 8), dim3(NT), kargs, (size_t)lds_bytes, s), "mvn_generate(pipe_f16)");
+  p.NS = (n_layers(d) + lps - 1) / lps + 1;
+  p.fn = multi ? (const void *)gen_pipe_h16_kernel<true> : (const void *)gen_pipe_h16_kernel<false>;
+  p.lds_bytes = multi ? LDS_BYTES_M_MULTI : LDS_BYTES_M;
+  p.slots = pipe_grid_slots(p.NS, p.pipes);
+  p.batch = batch;
+  p.max_batch = pipe_h16_max_batch(d);
+  p.per_pipe = GMAX;
+  return pipe_launch_common(p, a, hand, hand_total, status_off, s);
 }
 
 }  // namespace mvn
 
 #ifdef MVN_PIPE_STAMPS
-extern "C" int mvn_debug_read_stamps_h16(unsigned long long *out, size_t n) {
-  if (n > sizeof(mvn::g_stamps) / 8) n = sizeof(mvn::g_stamps) / 8;
-  return mvn::check_hip(hipMemcpyFromSymbol(out, HIP_SYMBOL(mvn::g_stamps), n * 8), "read stamps");
-}
-extern "C" int mvn_debug_read_fine_h16(unsigned long long *out, size_t n) {
-  if (n > sizeof(mvn::g_fine) / 8) n = sizeof(mvn::g_fine) / 8;
-  return mvn::check_hip(hipMemcpyFromSymbol(out, HIP_SYMBOL(mvn::g_fine), n * 8), "read fine");
-}
+extern "C" int mvn_debug_read_stamps_h16(unsigned long long *out, size_t n) { return mvn::debug_read(mvn::g_stamps, out, n, "read stamps"); }
+extern "C" int mvn_debug_read_fine_h16(unsigned long long *out, size_t n) { return mvn::debug_read(mvn::g_fine, out, n, "read fine"); }
 #endif

@@ -1,6 +1,7 @@
-// Device helpers shared by the PIPE generator kernels (generate_pipe.hip: fp32, C = 64 / 128;
-// generate_pipe_h16.hip: fp16 operands, C = 128): the granule hand-off, cross-lane moves as
-// DPP, the gate, and the step-closing choice (double softmax, arg-max / inverse-CDF sample).
+// Shared by the pipelined generator kernels (generate_pipe.hip: fp32, C = 64 / 128; generate_fold.hip: fp32,
+// C = 64, folded layers; generate_pipe_h16.hip: fp16 operands, C = 128): placement and its handshake, the granule
+// hand-off, cross-lane moves as DPP, the gate, the step-closing choice (double softmax, arg-max / inverse-CDF
+// sample), the head stage's step loop and the fp32 head's packing.
 #pragma once
 #include <cstdio>
 #include <cstdlib>
@@ -16,7 +17,7 @@ typedef float4 f4;
 
 constexpr int PIPE_XCD_CUS = 32;  // CUs per XCD: one workgroup (133 KB of LDS) per CU
 constexpr unsigned PIPE_SPIN_LIMIT = 1u << 23;
-constexpr int PIPE_MAX_GRAN = 256;
+constexpr int HEAD_Q = 256, HEAD_NT = 512;  // every pipelined head: 256 classes wide, 512 threads
 
 // How the pipelined generators are launched.  Default: hipLaunchCooperativeKernel -- the runtime then guarantees
 // what the hand-offs need, every stage of every pipeline co-resident (it refuses the launch otherwise, and does not
@@ -55,6 +56,52 @@ inline bool pipe_cooperative_launch() {
   return on;
 }
 
+// Placement of gen_pipe_kernel and gen_pipe_h16_kernel (gen_fold_kernel has a map of its own).  Workgroup i is
+// dispatched to XCD i % 8 (observed; every edge verifies its placement in pipe_edge_is_fast, so this is speed
+// only -- but co-residency needs <= 32 workgroups per XCD, which the host checks with the arithmetic below).  A
+// pipeline of NS <= 32 stages sits in one XCD so that its hops stay inside one L2: floor(32 / NS) pipelines in each
+// of the 8 XCDs; a longer one spans pipe_span(NS) adjacent XCDs.
+__host__ __device__ inline int pipe_span(int NS) { return (NS + PIPE_XCD_CUS - 1) / PIPE_XCD_CUS; }
+inline int pipe_pipelines_of(int NS) {  // co-resident pipelines of NS stages
+  return NS <= PIPE_XCD_CUS ? 8 * (PIPE_XCD_CUS / NS) : 8 / pipe_span(NS);
+}
+inline int pipe_grid_slots(int NS, int pipes) {  // the grid is 8 workgroups (one per XCD) per slot
+  return NS <= PIPE_XCD_CUS ? (pipes + 7) / 8 * NS : (NS + pipe_span(NS) - 1) / pipe_span(NS);
+}
+// workgroup `block` -> pipeline b, stage s; false: a workgroup with nothing to do
+__device__ __forceinline__ bool pipe_place(unsigned block, int NS, int &b, int &s) {
+  const int xcd = block & 7, slot = block >> 3;
+  if (NS <= PIPE_XCD_CUS) {
+    b = xcd + 8 * (slot / NS);
+    s = slot % NS;
+    return true;
+  }
+  const int XS = pipe_span(NS), SPX = (NS + XS - 1) / XS;
+  b = xcd / XS;
+  s = (xcd % XS) * SPX + slot;
+  return slot < SPX && s < NS;
+}
+
+// Placement handshake of edge (b, s) -> (b, s_next): publish my XCC id (+1), read my consumer's.  `xcc`: the
+// [nb * NS] placement words, zeroed by the launch's memset; `iflag`: the stage's LDS flag words ([3] is used here).
+// True when both ends were found on one XCD; unknown (time-out) => false, the safe form.
+__device__ __forceinline__ bool pipe_edge_is_fast(unsigned *xcc, int b, int s, int s_next, int NS, int *iflag) {
+  const unsigned mine = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xF) + 1;  // HW_REG_XCC_ID[3:0]
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(xcc + b * NS + s, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned other = 0;
+    for (unsigned spins = 0; spins < (1u << 20) && other == 0; ++spins) {
+      other = __hip_atomic_load(xcc + b * NS + s_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (other == 0) __builtin_amdgcn_s_sleep(8);
+    }
+    iflag[3] = (other == mine) ? 1 : 0;
+  }
+  __syncthreads();
+  const bool fast = iflag[3] != 0;
+  __syncthreads();
+  return fast;
+}
+
 #ifdef MVN_PIPE_STAMPS
 // Diagnostic build only (python -m movenet_amd.csrc.build --stamps): wall-clock
 // (s_memrealtime, 100 MHz) stamps of "inbox complete" and "outbox sent" per stage
@@ -74,6 +121,12 @@ static __device__ unsigned long long g_fine[16][16][64][8];
     if ((bb) < 16 && (ss) < 16 && (step) < 64 && threadIdx.x == (who))              \
       g_fine[bb][ss][step][slot] = __builtin_amdgcn_s_memtime();                    \
   } while (0)
+// body of the mvn_debug_read_* exports (a set per translation unit: g_stamps / g_fine are static)
+template <class T>
+inline int debug_read(const T &sym, unsigned long long *out, size_t n, const char *what) {
+  if (n > sizeof(T) / 8) n = sizeof(T) / 8;
+  return check_hip(hipMemcpyFromSymbol(out, HIP_SYMBOL(sym), n * 8), what);
+}
 #else
 #define MVN_STAMP(bb, ss, step, which) do {} while (0)
 #define MVN_FINE(bb, ss, step, slot, who) do {} while (0)
@@ -563,6 +616,167 @@ __device__ __forceinline__ int choose_class(const float (&lg)[4], float temperat
       argmax_take(rv, pick, lane_value(bv, row), __builtin_amdgcn_readlane(bi, row));
   }
   return pick;
+}
+
+// fp32 conv2 of the head: thread (og = tid >> 3, q2 = tid & 7) holds 4 output rows x 32 inputs in w2; the eight
+// threads of a row group meet by DPP, and threads q2 < 4 store logits 4 og + q2
+__device__ __forceinline__ void head_conv2_f32(const v2f (&w2)[4][16], const float *a1, float *lgb, int og, int q2,
+                                               float b2r) {
+  f4 x[8];
+  ldsn<8>(x, a1 + 32 * q2);
+  float s0 = dotn<8>(w2[0], x), s1 = dotn<8>(w2[1], x);
+  float s2 = dotn<8>(w2[2], x), s3 = dotn<8>(w2[3], x);
+  s0 = quad_sum(s0); s0 += other_quad(s0);
+  s1 = quad_sum(s1); s1 += other_quad(s1);
+  s2 = quad_sum(s2); s2 += other_quad(s2);
+  s3 = quad_sum(s3); s3 += other_quad(s3);
+  const int sel = q2 & 3;
+  if (q2 < 4) lgb[4 * og + sel] = (sel == 0 ? s0 : sel == 1 ? s1 : sel == 2 ? s2 : s3) + b2r;
+}
+
+// The step loop of the head stage (the last stage of pipeline b; its consumer is stage 0), for every pipelined
+// kernel.  Wave 0 closes every step alone (softmax, choice) and immediately opens the next one: it gathers the two
+// embedding rows of the causal conv (modules.py:28-30 on a one-hot input; E0 / E1: the [Q][C] tables of the two
+// taps) and hands them to stage 0, so no barrier sits between the choice and the next step's first hop.
+// A granule row is GRAN = (1 + NZ) C wide: the residual stream, then NZ lanes that start a step as zeros (PIPE: the
+// skip sum; FOLD: zl and the skip sum).  What differs between the kernels is passed in:
+//   await(inbox, epoch)            wave 0: wait for the head's input of this step, store it to LDS; false on time-out
+//   logits(inbox, epoch, do_head)  all waves, behind a barrier: the dense head into lgb[256], closed by a barrier
+//                                  (do_head is block-uniform; false: no logits are needed for this step)
+// iflag / hidx: LDS words ([0]: the hand-off's ok flag; MULTI: [GMAX][2] = {idx_cur, idx_prev} of each sequence
+// between its turns).
+template <int C, int GRAN, bool MULTI, int NZ, class Await, class Logits>
+__device__ __forceinline__ void head_loop(const GenArgs &a, u64 *hand, int NS, int nb, int b, int G, bool fast_edge,
+                                          const float *E0, const float *E1, int *iflag, int *hidx, const float *lgb,
+                                          Await await, Logits logits) {
+  static_assert(GRAN == (1 + NZ) * C, "residual stream + NZ zero lanes");
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, s = NS - 1;
+  int bq;  // the sequence whose turn it is: b + g nb
+  const u64 *inbox;
+  u64 *outbox;
+  int32_t *samples;
+  auto bind = [&](int g) {
+    bq = b + g * nb;
+    inbox = hand + ((size_t)bq * NS + s) * GRAN;
+    outbox = hand + (size_t)bq * NS * GRAN;
+    samples = a.samples + (size_t)bq * a.stride;
+  };
+  int idx_cur = 0, idx_prev = -1;
+  auto send_h0 = [&](unsigned ep) {  // wave 0
+    const int ic = min(max(idx_cur, 0), a.Q - 1), ip = min(idx_prev, a.Q - 1);
+#pragma unroll
+    for (int j = 0; j < C / 64; ++j) {
+      const int ch = lane + 64 * j;
+      float v = E1[ic * C + ch];
+      if (ip >= 0) v += E0[ip * C + ch];
+      put_granule(outbox + ch, ep, v, fast_edge);
+#pragma unroll
+      for (int z = 1; z <= NZ; ++z) put_granule(outbox + z * C + ch, ep, 0.f, fast_edge);
+    }
+  };
+  for (int g = 0; g < G; ++g) {
+    bind(g);
+    if (wave == 0) {
+      idx_cur = samples[a.t_begin];
+      idx_prev = a.t_begin > 0 ? samples[a.t_begin - 1] : -1;
+      if (a.t_begin < a.t_end) send_h0(1u);
+      MVN_STAMP(b, s, 0, 1);
+      if (MULTI && lane == 0) {
+        hidx[2 * g] = idx_cur;
+        hidx[2 * g + 1] = idx_prev;
+      }
+    }
+  }
+  if (MULTI) __syncthreads();
+
+  for (int ts = a.t_begin; ts < a.t_end; ++ts)
+  for (int g = 0; g < G; ++g) {
+    if (MULTI) {
+      bind(g);
+      if (wave == 0) {  // (written by this wave's lane 0 a whole round ago)
+        idx_cur = hidx[2 * g];
+        idx_prev = hidx[2 * g + 1];
+      }
+    }
+    const unsigned epoch = (unsigned)(ts - a.t_begin + 1);
+    const int u = ts + 1;
+    const bool want_out = (a.logits_out || a.choices_out) && u >= a.logits_t0;
+    const bool do_head = u < a.n_total && (u >= a.n_given || want_out);  // block-uniform
+    int next_idx = 0;
+    // this step's Philox uniform, formed while the step's input is still on its way (the fence
+    // keeps it from being sunk to its use behind the head's barriers)
+    float uni = 0.f;
+    if (wave == 0 && a.temperature > 0.f) {
+      uni = philox_uniform(a.seed, (uint32_t)u, (uint32_t)bq);
+      asm volatile("" : "+v"(uni));
+    }
+    if (wave == 0) {
+      if (u < a.n_given) next_idx = samples[u];  // prompt / teacher forcing
+      const bool ok = await(inbox, epoch);
+      if (lane == 0) iflag[0] = ok ? 1 : 0;
+    }
+    lds_barrier();
+    MVN_STAMP(b, s, ts - a.t_begin, 0);
+    logits(inbox, epoch, do_head);
+    if (wave == 0) {
+      int pick = 0;
+      if (do_head) {
+        // lane i owns classes 4i..4i+3; every reduction is intra-wave (DPP + readlane)
+        const f4 lv = ((const f4 *)lgb)[lane];
+        const float lg[4] = {lv.x, lv.y, lv.z, lv.w};
+        // (rows of a.Q logits: the padding of a smaller model is not written; fp16 PIPE takes Q = 256 only)
+        if (a.logits_out && u >= a.logits_t0 && 4 * lane < a.Q)
+          ((f4 *)(a.logits_out + ((size_t)bq * (a.n_total - a.logits_t0) + (u - a.logits_t0)) * a.Q))[lane] = lv;
+        pick = choose_class(lg, a.temperature, uni, lane, a.Q);
+        if (u >= a.n_given) next_idx = pick;
+      }
+      idx_prev = idx_cur;
+      idx_cur = next_idx;
+      if (ts + 1 < a.t_end) send_h0(epoch + 1);
+      MVN_STAMP(b, s, ts + 1 - a.t_begin, 1);
+      if (do_head && lane == 0) {
+        if (a.choices_out && u >= a.logits_t0) a.choices_out[(size_t)bq * a.n_total + u] = pick;
+        if (u >= a.n_given) samples[u] = pick;
+      }
+      if (MULTI && lane == 0) {
+        hidx[2 * g] = idx_cur;
+        hidx[2 * g + 1] = idx_prev;
+      }
+    }
+    if (iflag[0] == 0) return;  // hand-off timed out
+  }
+}
+
+// ---- packing of the fp32 head (PIPE and FOLD) -----------------------------------------------------------------
+// Element i of the sections conv1 | b1 | conv2 | b2 (W1_F + Q + W2_F + Q floats) in the per-thread register order;
+// false when i lies behind them.  C: conv1's inputs, W1N = C / 2 of them per thread.  `qm`: the MODEL's class count
+// (64, 128 or 256).  The head always runs 256 classes wide: classes >= qm are padding -- zero rows and columns,
+// conv2 bias -inf, so that their logits are -inf (probability 0 in the first softmax; choose_class masks them in
+// the second) and they are never picked.
+__device__ __forceinline__ bool pack_head_f32(int i, int C, int W1N, int qm, const float *w1, const float *b1,
+                                              const float *w2, const float *b2, float *__restrict__ dst) {
+  constexpr int Q = HEAD_Q, NT = HEAD_NT;
+  const int W1_F = Q * C, W2_F = Q * Q;
+  if (i < W1_F) {
+    // conv1: [W1N/4][tid (512)] float4, thread (o1 = tid>>1, q1 = tid&1) owns W1N inputs
+    const int e = i & 3, v = i >> 2, tid = v & (NT - 1), i4 = v >> 9;
+    const int o = tid >> 1;
+    dst[i] = o < qm ? w1[(size_t)o * C + W1N * (tid & 1) + 4 * i4 + e] : 0.f;
+  } else if (i < W1_F + Q) {
+    dst[i] = i - W1_F < qm ? b1[i - W1_F] : 0.f;
+  } else if (i < W1_F + Q + W2_F) {
+    // conv2: [4 r][8][tid (512)] float4, thread (og = tid>>3, q2 = tid&7): output 4 og + r, inputs 32 q2 ..
+    const int ii = i - W1_F - Q;
+    const int e = ii & 3, v = ii >> 2, tid = v & (NT - 1), rest = v >> 9, r = rest >> 3, i8 = rest & 7;
+    const int o = 4 * (tid >> 3) + r, k = 32 * (tid & 7) + 4 * i8 + e;
+    dst[i] = (o < qm && k < qm) ? w2[(size_t)o * qm + k] : 0.f;
+  } else if (i < W1_F + Q + W2_F + Q) {
+    const int o = i - W1_F - Q - W2_F;
+    dst[i] = o < qm ? b2[o] : -INFINITY;
+  } else {
+    return false;
+  }
+  return true;
 }
 
 }  // namespace mvn
