@@ -15,13 +15,17 @@
 // inbox carries 3C granules {xp, zl, sk}: xp = the stream WITHOUT the previous stage's last
 // residual term, zl = that stage's last gated activation -- the two the chain waits for -- and
 // sk = the running skip sum, which travels on a lane of its own (sent and awaited off the chain,
-// after the stage's third phase).  Waves 0-3 (the chain) compute
+// after the stage's third phase).  The two ends differ: stage 0 has no previous layer, so the head
+// sends it xp alone and its zl / sk terms are not formed; the last layer stage feeds the head, which
+// reads zl and sk but no xp', so its helpers send sk' first and no xp'.
+// Waves 0-3 (the chain) compute
 //     z_0 = gate(Wc_0 xp + (Wc_0 Wr_prev) zl + pf_0)
 //     z_1 = gate((Wc_1 Wr_0) z_0 + base_1 + pf_1)          and (Wc_2 Wr_0) z_0 for the helpers' base_2
 //     z_2 = gate((Wc_2 Wr_1) z_1 + base_2 + pf_2)          -> sent on as the next stage's zl
 // with their five matrices in registers; waves 4-7 (the helpers) compute one phase ahead
 //     base_1 = Wc_1 xp + (Wc_1 Wr_prev) zl,    x_0 = xp + Wr_prev zl
-//     base_2 = Wc_2 x_0  [+ the chain's term],  x_1 = x_0 + Wr_0 z_0 + br_0
+//     base_2 = Wc_2 x_0  [+ the chain's term]
+//     (third phase)                             x_1 = x_0 + Wr_0 z_0 + br_0
 //                                               x_2 = x_1 + Wr_1 z_1 + br_1   -> xp' = x_2 + br_2 sent early
 // and, after the third phase, sk' = sk + Ws_prev zl + Ws_0 z_0 + Ws_1 z_1 + biases (the skip 1x1
 // of a stage's LAST layer is added by the next stage, the head for the last one).  The constant
@@ -33,6 +37,7 @@
 // the layer-by-layer order at the 1e-7 level (logits within 2e-5 of the range, greedy
 // fixtures bit-exact: tests/test_generate_gpu.py).
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "gen_common.h"
@@ -225,8 +230,14 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
   float *pfs = smem + LDS_FLOATS;                // MULTI: [GMAX][C][PFS_F] (layer stages), head: indices
   const bool fast_edge = pipe_edge_is_fast(err + 16, b, s, s_next, NS, iflag);
 
-  if (s < NS - 1) {
-    // ================= layer stage: layers l0 .. l0 + nl - 1 =================
+  // ================= layer stage: layers l0 .. l0 + nl - 1 =================
+  // Two forms, chosen per workgroup (s is block-uniform).  FIRST: stage 0 has no previous layer -- its inbox carries xp
+  // alone (the head sends no zl and no skip sum), x_0 = xp, its skip sum starts at 0, and the products against
+  // A0', B1', Wr_prev and Ws_prev (packed as zeros for it) are not formed.  Each of them added w * 0 to a finite
+  // sum, which is exact; the one assumption is that the weights are finite (0 * inf would have been a NaN).
+  auto layer_stage = [&](auto first_stage) {
+    constexpr bool FIRST = decltype(first_stage)::value;
+    const bool last = s == NS - 2;  // feeds the head, which reads zl' and sk' only
     const int l0 = s * LPS, nl = min(LPS, L - l0);
     const bool chain = tid < 256;
     const int t = tid & 255, c = t >> 2, kq = t & 3;
@@ -261,11 +272,11 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
     const float *vecs = sec + N_MAT * MAT_F;
 
     // chain waves: A0, A0', A1, A2, B2'; helper waves: B1, B1', B2, RR, RS
-    FoldMat m0, m1, m2, m3, m4;
+    FoldMat m0, m1 = {}, m2, m3, m4;
     {
       const int first = chain ? M_A0 : M_B1;
       fold_load(m0, sec + (size_t)(first + 0) * MAT_F, t);
-      fold_load(m1, sec + (size_t)(first + 1) * MAT_F, t);
+      if (!FIRST) fold_load(m1, sec + (size_t)(first + 1) * MAT_F, t);  // A0' / B1'
       fold_load(m2, sec + (size_t)(first + 2) * MAT_F, t);
       fold_load(m3, sec + (size_t)(first + 3) * MAT_F, t);
       fold_load(m4, sec + (size_t)(first + 4) * MAT_F, t);
@@ -387,10 +398,10 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
       }
       const unsigned epoch = (unsigned)(ts - a.t_begin + 1);
       if (wave == 0) {
-        // 2C granules: lane i takes 2i, 2i + 1 (xp for i < 32, zl above) with one 16-byte load
+        // 2C granules: lane i takes 2i, 2i + 1 (xp for i < 32, zl above) with one 16-byte load; FIRST: xp alone
         float v[2];
-        const bool ok = wait_inbox<2>(inbox, epoch, err, v);
-        if (ok) {
+        const bool ok = FIRST ? wait_inbox64(inbox, epoch, err, v) : wait_inbox<2>(inbox, epoch, err, v);
+        if (ok && (!FIRST || lane < 32)) {
           float *dst = vec + 2 * lane;  // O_XP and O_ZL are adjacent
           dst[0] = v[0];
           dst[1] = v[1];
@@ -406,10 +417,10 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
       if (chain) {
         f4 xa[NF4], xb[NF4];
         ldsv<NF4>(xa, vq, O_XP);
-        ldsv<NF4>(xb, vq, O_ZL);
+        if (!FIRST) ldsv<NF4>(xb, vq, O_ZL);
         v2f acc[4];
         pair_acc<true>(acc, m0.w, xa);
-        pair_acc<false>(acc, m1.w, xb);
+        if (!FIRST) pair_acc<false>(acc, m1.w, xb);
         const v2f fg = pair_sum(acc);
         const float f = chan_sum<KQ>(fg.x) + pf[0];
         const float g = chan_sum<KQ>(fg.y) + pg[0];
@@ -419,15 +430,16 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
       } else {
         f4 xa[NF4], xb[NF4];
         ldsv<NF4>(xa, vq, O_XP);
-        ldsv<NF4>(xb, vq, O_ZL);
+        if (!FIRST) ldsv<NF4>(xb, vq, O_ZL);
         v2f acc[4];
         pair_acc<true>(acc, m0.w, xa);
-        pair_acc<false>(acc, m1.w, xb);
+        if (!FIRST) pair_acc<false>(acc, m1.w, xb);
         const v2f fg = pair_sum(acc);
-        float r = split_dot<0>(m3.w, xb);                          // Wr_prev zl
+        float r = 0.f;                                             // (FIRST: the + 0 keeps a -0 of xp what it was, +0)
+        if (!FIRST) r = split_dot<0>(m3.w, xb);                    // Wr_prev zl
         const float f = chan_sum<KQ>(fg.x);
         const float g = chan_sum<KQ>(fg.y);
-        r = chan_sum<KQ>(r);
+        if (!FIRST) r = chan_sum<KQ>(r);
         if (lead) {
           xv = LDSF(vc, O_XP) + r;               // x_0 (br_prev already inside xp)
           LDSF(vc, O_X0) = xv;
@@ -456,22 +468,18 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
         if (lead) LDSF(vc, O_Z1) = z;
         MVN_FINE(b, s, ts - a.t_begin, 3, 0);
       } else {
-        f4 xa[NF4], xz[NF4];
+        // (x_1 = x_0 + Wr_0 z_0 + br_0 is first needed for x_2: formed in phase 2, where the SIMDs have issue slots
+        // to spare -- this phase closes on the helpers)
+        f4 xa[NF4];
         ldsv<NF4>(xa, vq, O_X0);
-        ldsv<NF4>(xz, vq, O_Z0);
-        const float br0 = LDSF(vc, O_VEC + V_BR0);
         v2f acc[4];
         pair_acc<true>(acc, m2.w, xa);                             // Wc_2 x_0
         const v2f fg = pair_sum(acc);
-        float r = split_dot<1>(m3.w, xz);                          // Wr_0 z_0
         const float f = chan_sum<KQ>(fg.x);
         const float g = chan_sum<KQ>(fg.y);
-        r = chan_sum<KQ>(r);
         if (lead) {
           LDSF(vc, O_B2) = f;
           LDSF(vc, O_B2 + C) = g;
-          xv = (xv + br0) + r;           // x_1
-          xs[1] = xv;
         }
         MVN_FINE(b, s, ts - a.t_begin, 7, 256);
       }
@@ -490,31 +498,60 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
         if (lead) put_granule(ob + C, epoch, z, fast_edge);
         MVN_FINE(b, s, ts - a.t_begin, 5, 0);
       } else {
-        const u64 sk_peek = peek_granule(ibs);
+        u64 sk_peek = 0;
+        if (!FIRST) sk_peek = peek_granule(ibs);
         f4 xz[NF4];
         ldsv<NF4>(xz, vq, O_Z1);
-        const float br1 = LDSF(vc, O_VEC + V_BR1), br2 = LDSF(vc, O_VEC + V_BR2);
-        float r = split_dot<0>(m4.w, xz);                          // Wr_1 z_1
-        r = chan_sum<KQ>(r);
-        if (lead) {
-          xv = (xv + br1) + r;          // x_2
-          xs[2] = xv;
-          put_granule(ob, epoch, xv + br2, fast_edge);
-        }
+        // the stream: x_1, x_2 for the queue pushes, and xp' = x_2 + br_2 for the next stage (the head does not read it)
+        auto stream = [&](bool send) {
+          f4 xz0[NF4];
+          ldsv<NF4>(xz0, vq, O_Z0);
+          const float br0 = LDSF(vc, O_VEC + V_BR0), br1 = LDSF(vc, O_VEC + V_BR1), br2 = LDSF(vc, O_VEC + V_BR2);
+          float r0 = split_dot<1>(m3.w, xz0);                      // Wr_0 z_0
+          float r = split_dot<0>(m4.w, xz);                        // Wr_1 z_1
+          r0 = chan_sum<KQ>(r0);
+          r = chan_sum<KQ>(r);
+          if (lead) {
+            xv = (xv + br0) + r0;       // x_1
+            xs[1] = xv;
+            xv = (xv + br1) + r;        // x_2
+            xs[2] = xv;
+            if (send) put_granule(ob, epoch, xv + br2, fast_edge);
+          }
+          MVN_FINE(b, s, ts - a.t_begin, 8, 256);
+        };
         // skip lane: sk' = sk + (Ws_prev zl + bs_prev) + (Ws_0 z_0 + bs_0) + (Ws_1 z_1 + bs_1)
-        float k1 = split_dot<1>(m4.w, xz);
-        unsigned wss = lds_addr(lmat + 3 * MAT_F) + 16u * t;  // SS = {Ws_prev; Ws_0}
-        asm volatile("" : "+v"(wss));
-        float kp = split_dot_lds<0>(wss, vq + 4u * O_ZL);
-        float k0 = split_dot_lds<1>(wss, vq + 4u * O_Z0);
-        kp = chan_sum<KQ>(kp);
-        k0 = chan_sum<KQ>(k0);
-        k1 = chan_sum<KQ>(k1);
-        if (lead) {
-          const float bsp = LDSF(vc, O_VEC + V_BSP), bs0 = LDSF(vc, O_VEC + V_BS0), bs1 = LDSF(vc, O_VEC + V_BS1);
-          const float skin = (unsigned)(sk_peek >> 32) == epoch ? __uint_as_float((unsigned)sk_peek)
-                                                                : wait_granule(ibs, epoch, err);
-          put_granule(ob + 2 * C, epoch, ((skin + (kp + bsp)) + (k0 + bs0)) + (k1 + bs1), fast_edge);
+        auto skip = [&] {
+          float k1 = split_dot<1>(m4.w, xz);
+          unsigned wss = lds_addr(lmat + 3 * MAT_F) + 16u * t;  // SS = {Ws_prev; Ws_0}
+          asm volatile("" : "+v"(wss));
+          float kp = 0.f;
+          if (!FIRST) kp = split_dot_lds<0>(wss, vq + 4u * O_ZL);
+          float k0 = split_dot_lds<1>(wss, vq + 4u * O_Z0);
+          if (!FIRST) kp = chan_sum<KQ>(kp);
+          k0 = chan_sum<KQ>(k0);
+          k1 = chan_sum<KQ>(k1);
+          if (lead) {
+            const float bs0 = LDSF(vc, O_VEC + V_BS0), bs1 = LDSF(vc, O_VEC + V_BS1);
+            float sk0 = 0.f;  // FIRST: the skip sum starts here
+            if (!FIRST) {
+              const float bsp = LDSF(vc, O_VEC + V_BSP);
+              const float skin = (unsigned)(sk_peek >> 32) == epoch ? __uint_as_float((unsigned)sk_peek)
+                                                                    : wait_granule(ibs, epoch, err);
+              sk0 = skin + (kp + bsp);
+            }
+            put_granule(ob + 2 * C, epoch, (sk0 + (k0 + bs0)) + (k1 + bs1), fast_edge);
+          }
+          MVN_FINE(b, s, ts - a.t_begin, 9, 256);
+        };
+        if (last) {
+          // the head cannot form its first activation without sk': here the skip lane is ON the step's critical path,
+          // so it goes first, and the stream (needed after the closing barrier only) is not sent at all
+          skip();
+          stream(false);
+        } else {
+          stream(true);
+          skip();
         }
       }
       MVN_STAMP(b, s, ts - a.t_begin, 1);
@@ -535,6 +572,12 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
           if (j < nl) ring[doff[j] + cq + (ts & dmask[j]) * C] = xs[j];
       }
     }
+  };
+  if (s < NS - 1) {
+    if (s == 0)
+      layer_stage(std::true_type{});
+    else
+      layer_stage(std::false_type{});
     return;
   }
 
@@ -573,10 +616,10 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
     const float bslr = bsl[og];
     __syncthreads();
 
-    // (head_loop starts a step with xp = the causal conv's two embedding rows, zl = sk = 0)
+    // (head_loop starts a step with xp = the causal conv's two embedding rows alone: stage 0 reads no zl and no sk)
     auto await = [&](const u64 *inbox, unsigned epoch) {  // wave 0
       float v[2];
-      const bool ok = wait_inbox64(inbox + C, epoch, err, v);  // zl (the last stage's xp' is not used)
+      const bool ok = wait_inbox64(inbox + C, epoch, err, v);  // zl (the last stage sends no xp')
       if (ok && lane < 32) {
         zlb[2 * lane] = v[0];
         zlb[2 * lane + 1] = v[1];
@@ -584,6 +627,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
       return ok;
     };
     auto logits = [&](const u64 *inbox, unsigned epoch, bool do_head) {
+      MVN_FINE(b, NS - 1, epoch - 1, 0, 0);
       const u64 sk_peek = peek_granule(inbox + 2 * C + og);
       float sv = 0.f;
       if (do_head) {
@@ -600,6 +644,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
       if (q2 == 0)
         skin = (unsigned)(sk_peek >> 32) == epoch ? __uint_as_float((unsigned)sk_peek)
                                                   : wait_granule(inbox + 2 * C + og, epoch, err);
+      MVN_FINE(b, NS - 1, epoch - 1, 1, 0);
       if (!do_head) return;
       // skip sum, then the head's first leaky-ReLU (modules.py:140)
       if (q2 == 0) a0[og] = leaky(skin + (sv + bslr));
@@ -612,10 +657,12 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
         if (q1 == 0) a1[o1] = leaky(hsum + b1r);
       }
       lds_barrier();
+      MVN_FINE(b, NS - 1, epoch - 1, 3, 0);
       head_conv2_f32(w2, a1, lgb, og, q2, b2r);
       lds_barrier();
+      MVN_FINE(b, NS - 1, epoch - 1, 4, 0);
     };
-    head_loop<C, GRAN, MULTI, 2>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
+    head_loop<C, GRAN, MULTI, 2, 0>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
   }
 }
 

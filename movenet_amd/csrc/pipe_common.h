@@ -114,8 +114,8 @@ static __device__ unsigned long long g_stamps[16][16][64][4];
       g_stamps[bb][ss][step][2 + (which)] = __builtin_amdgcn_s_memtime();           \
     }                                                                               \
   } while (0)
-// finer shader-clock stamps inside the first layer of a stage (thread `who`)
-static __device__ unsigned long long g_fine[16][16][64][8];
+// finer shader-clock stamps inside a stage (thread `who`)
+static __device__ unsigned long long g_fine[16][16][64][12];
 #define MVN_FINE(bb, ss, step, slot, who)                                           \
   do {                                                                              \
     if ((bb) < 16 && (ss) < 16 && (step) < 64 && threadIdx.x == (who))              \
@@ -639,17 +639,18 @@ __device__ __forceinline__ void head_conv2_f32(const v2f (&w2)[4][16], const flo
 // embedding rows of the causal conv (modules.py:28-30 on a one-hot input; E0 / E1: the [Q][C] tables of the two
 // taps) and hands them to stage 0, so no barrier sits between the choice and the next step's first hop.
 // A granule row is GRAN = (1 + NZ) C wide: the residual stream, then NZ lanes that start a step as zeros (PIPE: the
-// skip sum; FOLD: zl and the skip sum).  What differs between the kernels is passed in:
+// skip sum; FOLD: zl and the skip sum).  NZ_SENT of them are written as zeros for stage 0 (all, unless stage 0
+// knows them to be zero and does not read them: FOLD).  What differs between the kernels is passed in:
 //   await(inbox, epoch)            wave 0: wait for the head's input of this step, store it to LDS; false on time-out
 //   logits(inbox, epoch, do_head)  all waves, behind a barrier: the dense head into lgb[256], closed by a barrier
 //                                  (do_head is block-uniform; false: no logits are needed for this step)
 // iflag / hidx: LDS words ([0]: the hand-off's ok flag; MULTI: [GMAX][2] = {idx_cur, idx_prev} of each sequence
 // between its turns).
-template <int C, int GRAN, bool MULTI, int NZ, class Await, class Logits>
+template <int C, int GRAN, bool MULTI, int NZ, int NZ_SENT = NZ, class Await, class Logits>
 __device__ __forceinline__ void head_loop(const GenArgs &a, u64 *hand, int NS, int nb, int b, int G, bool fast_edge,
                                           const float *E0, const float *E1, int *iflag, int *hidx, const float *lgb,
                                           Await await, Logits logits) {
-  static_assert(GRAN == (1 + NZ) * C, "residual stream + NZ zero lanes");
+  static_assert(GRAN == (1 + NZ) * C && NZ_SENT <= NZ, "residual stream + NZ zero lanes");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, s = NS - 1;
   int bq;  // the sequence whose turn it is: b + g nb
   const u64 *inbox;
@@ -671,7 +672,7 @@ __device__ __forceinline__ void head_loop(const GenArgs &a, u64 *hand, int NS, i
       if (ip >= 0) v += E0[ip * C + ch];
       put_granule(outbox + ch, ep, v, fast_edge);
 #pragma unroll
-      for (int z = 1; z <= NZ; ++z) put_granule(outbox + z * C + ch, ep, 0.f, fast_edge);
+      for (int z = 1; z <= NZ_SENT; ++z) put_granule(outbox + z * C + ch, ep, 0.f, fast_edge);
     }
   };
   for (int g = 0; g < G; ++g) {
@@ -734,6 +735,7 @@ __device__ __forceinline__ void head_loop(const GenArgs &a, u64 *hand, int NS, i
       idx_cur = next_idx;
       if (ts + 1 < a.t_end) send_h0(epoch + 1);
       MVN_STAMP(b, s, ts + 1 - a.t_begin, 1);
+      MVN_FINE(b, s, ts - a.t_begin, 5, 0);
       if (do_head && lane == 0) {
         if (a.choices_out && u >= a.logits_t0) a.choices_out[(size_t)bq * a.n_total + u] = pick;
         if (u >= a.n_given) samples[u] = pick;

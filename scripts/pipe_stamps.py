@@ -72,18 +72,8 @@ if not WIDE:
       f" (min {hops[NS-1].min():.2f}, max {hops[NS-1].max():.2f})")
 print("sum compute %.2f us, sum hops %.2f us" % (compute.mean(0).mean(1).sum() + head.mean(),
                                                sum(h.mean() for h in hops)))
-if "--json" in sys.argv and not WIDE:
-    import json
-    path = sys.argv[sys.argv.index("--json") + 1]
-    json.dump({"variant": "fold" if FOLD else "pipe", "batch": B, "stages": NS - 1,
-               "note": "in-kernel s_memrealtime stamps of the diagnostic build (libmovenet_hip_stamps.so), averaged over steps 8..63 "
-                       "of one launch and the sequences: stage chain = inbox complete -> outbox sent, hop = outbox sent -> the next "
-                       "stage's inbox complete (the last hop: head -> stage 0), head = its inbox complete -> its send",
-               "step_us": float(step.mean()), "stage_chain_us": [float(compute[:, s].mean()) for s in range(NS - 1)],
-               "hop_us": [float(h.mean()) for h in hops], "head_us": float(head.mean()),
-               "shader_clock_MHz_median": float(np.median(mhz))}, open(path, "w"), indent=1)
-
-fine = np.zeros((16, 16, 64, 8), dtype=np.uint64)
+fine = np.zeros((16, 16, 64, 12), dtype=np.uint64)
+extra = {}
 read_fine.argtypes = [C.c_void_p, C.c_size_t]
 if H16 and read_fine(fine.ctypes.data, fine.size) == 0:
     f = fine[:B, :NS - 1, 8:, :6].astype(np.int64)
@@ -93,13 +83,33 @@ if H16 and read_fine(fine.ctypes.data, fine.size) == 0:
                        ("layer 1: both phases and their barrier, up to the hand-on", 4, 5), ("stage: first phase start -> hand-on", 0, 5)):
         print(f"  {nm:52s} {np.median(f[..., i1] - f[..., i0]):7.0f}")
 elif FOLD and read_fine(fine.ctypes.data, fine.size) == 0:
-    f = fine[:B, :NS - 1, 8:, :].astype(np.int64)
+    f = fine[:B, :NS - 1, 8:, :8].astype(np.int64)
     seg = [("phase 0 chain work (xp, zl dots, gate, z0 write)", 0, 1), ("phase 0 helper work (thread 256)", 0, 6),
            ("phase 0 incl. barrier", 0, 2), ("phase 1 chain work", 2, 3), ("phase 1 helper work", 2, 7),
            ("phase 1 incl. barrier", 2, 4), ("phase 2 chain work incl. send", 4, 5), ("whole stage", 0, 5)]
     print("a FOLD stage, shader cycles (median over stages, steps, sequences):")
     for nm, i0, i1 in seg:
         print(f"  {nm:52s} {np.median(f[..., i1] - f[..., i0]):7.0f}")
+    # the two ends of the pipeline against a middle stage, the sends of phase 2 (thread 256 = the helpers' first
+    # lane: slot 8 after the xp' store, 9 after the sk' store) and the head (stage NS - 1: slot 0 inbox complete,
+    # 1 skip term formed, 3 conv1 done, 4 conv2 done, 5 sample sent)
+    f = fine[:B, :NS - 1, 8:, :].astype(np.int64)
+    seg2 = [("phase0_chain", 0, 1), ("phase0_helpers", 0, 6), ("phase0_with_barrier", 0, 2), ("phase1_chain", 2, 3),
+            ("phase1_helpers", 2, 7), ("phase1_with_barrier", 2, 4), ("phase2_zl_sent", 4, 5), ("phase2_xp_sent", 4, 8),
+            ("phase2_sk_sent", 4, 9), ("stage_to_zl_sent", 0, 5)]
+    print("per class of stage, shader cycles (median):   stage 0 | stages 1..%d | stage %d" % (NS - 3, NS - 2))
+    for nm, i0, i1 in seg2:
+        row = [float(np.median(f[:, sl, :, i1] - f[:, sl, :, i0])) for sl in (slice(0, 1), slice(1, NS - 2), slice(NS - 2, NS - 1))]
+        extra.setdefault("stage_cycles", {})[nm] = dict(zip(("first", "middle", "last"), row))
+        print(f"  {nm:22s} {row[0]:7.0f} {row[1]:7.0f} {row[2]:7.0f}")
+    h = fine[:B, NS - 1, 8:, :].astype(np.int64)
+    hseg = [("inbox_complete_to_skip_term", 0, 1), ("skip_term_to_conv1_done", 1, 3), ("conv2", 3, 4),
+            ("choice_and_send", 4, 5), ("inbox_complete_to_sent", 0, 5)]
+    print("head, shader cycles (median; p90):")
+    for nm, i0, i1 in hseg:
+        d = h[..., i1] - h[..., i0]
+        extra.setdefault("head_cycles", {})[nm] = {"median": float(np.median(d)), "p90": float(np.percentile(d, 90))}
+        print(f"  {nm:32s} {np.median(d):7.0f} {np.percentile(d, 90):7.0f}")
 elif read_fine(fine.ctypes.data, fine.size) == 0:
     f = fine[:B, :NS - 1, 8:, :6].astype(np.int64)
     names = ["FG: x loads, dots, lane sums, gate, z write", "barrier FG->RS (two threads' clocks)",
@@ -110,3 +120,14 @@ elif read_fine(fine.ctypes.data, fine.size) == 0:
         d = f[..., k + 1] - f[..., k]
         print(f"  {nm:46s} {np.median(d):7.0f}")
     print(f"  {'whole layer':46s} {np.median(f[..., 5] - f[..., 0]):7.0f}")
+
+if "--json" in sys.argv and not WIDE:
+    import json
+    path = sys.argv[sys.argv.index("--json") + 1]
+    json.dump({"variant": "fold" if FOLD else "pipe", "batch": B, "stages": NS - 1,
+               "note": "in-kernel s_memrealtime stamps of the diagnostic build (libmovenet_hip_stamps.so), averaged over steps 8..63 "
+                       "of one launch and the sequences: stage chain = inbox complete -> outbox sent, hop = outbox sent -> the next "
+                       "stage's inbox complete (the last hop: head -> stage 0), head = its inbox complete -> its send",
+               "step_us": float(step.mean()), "stage_chain_us": [float(compute[:, s].mean()) for s in range(NS - 1)],
+               "hop_us": [float(h.mean()) for h in hops], "head_us": float(head.mean()),
+               "shader_clock_MHz_median": float(np.median(mhz)), **extra}, open(path, "w"), indent=1)
