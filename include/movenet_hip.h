@@ -212,12 +212,18 @@ int mvn_padded_len(int n); /* n rounded up to a multiple of 64 */
 
 /* Caller-provided device buffers (floats).  n_act = save ? L+1 : 2. */
 typedef struct mvn_fwd_buffers {
-  float *acts;  /* n_act x (B, C, Tp): layer inputs; acts[0] = causal conv out  */
+  float *acts;  /* n_act x (B, C, Tp): layer inputs; acts[0] = causal conv out;
+                   save: plane L (the last layer's residual output, which nothing
+                   uses) is never written                                       */
   float *th;    /* save: L x (B, C, Tp) tanh(f);      else NULL                 */
   float *sg;    /* save: L x (B, C, Tp) sigmoid(g);   else NULL                 */
   float *z;     /* (B, C, Tp) scratch: the gated activation of the unfused layer
                    kernels; the fused paths keep z on chip and write the layers'
-                   packed weight images here (fused_fwd_bf3.h)                 */
+                   packed weight images here (fused_fwd_bf3.h).  SHARED by the two
+                   passes: mvn_backward stages images (and, in bf16, slabs) of its
+                   own in it, so its contents are undefined after either call; every
+                   other saved tensor is left bit-identical by mvn_backward, which
+                   may therefore run again over the same saved forward           */
   float *skip;  /* (B, K, Sp) sum of skips                                      */
   float *a1;    /* (B, Q, Sp) head hidden activation lrelu(conv1(lrelu(skip)))  */
   const float *ctx; /* optional local conditioning (B, C, ctx_ld), column t = time t
@@ -233,7 +239,12 @@ typedef struct mvn_fwd_buffers {
 
 /* out: (B, Q, S_out) contiguous, S_out = S - (remove_last ? 1 : 0); softmax over
  * Q when `normalize` (the reference's inverted flag output_unnormalized=True,
- * wavenet.py:189-191).  save != 0 keeps what mvn_backward needs in `buf`. */
+ * wavenet.py:189-191); written in full, its rows need no alignment (any S_out); may be
+ * NULL when S_out == 0.  save != 0 keeps what mvn_backward needs in `buf`.
+ * No buffer has to be initialised: the library reads only what it (or the caller, for the
+ * inputs' columns < t_len) has written.  Every argument is checked before the first launch:
+ * a call that returns MVN_ERR_BAD_ARG / _BAD_DIMS / _TOO_SHORT / _UNSUPPORTED has written
+ * nothing. */
 int mvn_forward(const mvn_dims *dims, const mvn_params *params, const int32_t *index,
                 int index_stride, int batch, int t_len, const mvn_fwd_buffers *buf, float *out,
                 int normalize, int remove_last, int save, void *stream);
@@ -290,7 +301,8 @@ typedef struct mvn_bwd_buffers {
   float *dskip;  /* (B, K, Sp) */
   float *da1;    /* (B, Q, Sp) */
   float *dlogit; /* (B, Q, Sp) */
-  float *dctx;   /* (B, C, Tp) gradient w.r.t. fwd->ctx (written); NULL when audio only */
+  float *dctx;   /* (B, C, Tp) gradient w.r.t. fwd->ctx, written in full (not accumulated):
+                    columns >= t_len are zero; NULL when audio only */
 } mvn_bwd_buffers;
 
 /* dout: gradient w.r.t. mvn_forward's `out` (same shape); `out` itself is needed
@@ -300,7 +312,9 @@ typedef struct mvn_bwd_buffers {
  * mvn_softmax_ce_backward does.  Requires the forward ran with save.
  * Part of the work is enqueued on a stream the library owns (one per device) and joined
  * back into `stream` with events before the call returns: to the caller it is ordinary
- * stream-ordered work.  da1 / dlogit / dfg double as scratch of the weight gradients. */
+ * stream-ordered work.  da1 / dlogit / dfg double as scratch of the weight gradients, and so
+ * does fwd->z.  index_stride / dense_ld / ctx_ld are checked as in mvn_forward.  S_out == 0
+ * (t_len == RF with remove_last): MVN_OK, nothing is launched, `out` / `dout` may be NULL. */
 int mvn_backward(const mvn_dims *dims, const mvn_params *params, const mvn_param_grads *grads,
                  const int32_t *index, int index_stride, int batch, int t_len,
                  const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,

@@ -1101,6 +1101,11 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
     set_error("mvn_forward: out is NULL");
     return MVN_ERR_BAD_ARG;
   }
+  // (every refusal is decided here, in front of the first launch: a refused call has written nothing)
+  if (buf->ctx && (!p->ctx_filter_w || !p->ctx_filter_b || !p->ctx_gate_w || !p->ctx_gate_b || buf->ctx_ld < t_len)) {
+    set_error("mvn_forward: context given without context-conv parameters / ctx_ld < t_len");
+    return MVN_ERR_BAD_ARG;
+  }
   if (batch == 0) return MVN_OK;
   hipStream_t s = (hipStream_t)stream_;
   const int C = g.C, Kc = g.Kc, Q = g.Q, T = g.T;
@@ -1124,11 +1129,6 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
   Act zv = act_view(buf->z, batch, C, g.Tp);
   Act skipv = act_view(buf->skip, batch, Kc, g.Sp);
   const bool has_ctx = buf->ctx != nullptr;
-  if (has_ctx && (!p->ctx_filter_w || !p->ctx_filter_b || !p->ctx_gate_w || !p->ctx_gate_b ||
-                  buf->ctx_ld < T)) {
-    set_error("mvn_forward: context given without context-conv parameters / ctx_ld < t_len");
-    return MVN_ERR_BAD_ARG;
-  }
   Act ctxv = act_view(const_cast<float *>(buf->ctx), batch, C, has_ctx ? buf->ctx_ld : 0);
   int A = 0;  // first valid time of the current layer's input
   for (int l = 0; l < g.L; ++l) {
@@ -1332,17 +1332,21 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
   Geometry g;
   int rc = make_geometry(dims, batch, t_len, g);
   if (rc) return rc;
+  const int S_out = g.S - (remove_last ? 1 : 0);
   if (fwd && !fwd->dense_audio && !index) {
     set_error("mvn_backward: index is NULL");
     return MVN_ERR_BAD_ARG;
   }
+  if (fwd && ((fwd->dense_audio ? fwd->dense_ld : index_stride) < t_len || (fwd->ctx && fwd->ctx_ld < t_len))) {
+    set_error("mvn_backward: index / dense-audio stride or ctx_ld < t_len");
+    return MVN_ERR_BAD_ARG;
+  }
   if (!p || !gr || !fwd || !bwd || !fwd->acts || !fwd->th || !fwd->sg || !fwd->skip ||
       !fwd->a1 || !bwd->dx_a || !bwd->dx_b || !bwd->dfg || !bwd->dskip || !bwd->da1 ||
-      !bwd->dlogit || (dout && normalize && !out)) {
+      !bwd->dlogit || (dout && normalize && !out && S_out > 0)) {  // (an empty output has no `out` to read)
     set_error("mvn_backward: NULL buffer");
     return MVN_ERR_BAD_ARG;
   }
-  const int S_out = g.S - (remove_last ? 1 : 0);
   if (batch == 0 || S_out <= 0) return MVN_OK;
   hipStream_t s = (hipStream_t)stream_;
   const int C = g.C, Kc = g.Kc, Q = g.Q, T = g.T;

@@ -1,6 +1,8 @@
 """Shared helpers for the parity tests (CPU and GPU)."""
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
 
@@ -67,3 +69,41 @@ def grad_bound(fp32_deviation: float) -> float:
     if fp32_deviation <= 5e-6:
         return GRAD_TOL
     return min(4.0 * fp32_deviation, GRAD_TOL_MAX)
+
+
+# ---- sentinel bands around the buffers handed to the C ABI (GPU tests) ----
+DEV = "cuda:0"
+SENTINEL = -1234.5
+BAND = 1 << 14                     # elements of sentinel behind (and, with front=True, in front of) every buffer
+
+
+class _Guard:
+    """Buffers carved out of larger allocations, a band of sentinel values behind each and -- ``front=True`` -- in
+    front of each (64 KB: the buffer keeps the allocator's alignment)"""
+
+    def __init__(self, front=False):
+        self.bands, self.front = [], front
+
+    def new(self, shape, fill=None, name="buffer", dtype=torch.float32):
+        n = math.prod(shape)
+        lo = BAND if self.front else 0
+        raw = torch.empty(lo + n + BAND, dtype=dtype, device=DEV)
+        sentinel = SENTINEL if dtype.is_floating_point else int(SENTINEL)
+        for band, where in ((raw[:lo], "in front of"), (raw[lo + n:], "past the end of")):
+            band.fill_(sentinel)
+            self.bands.append((name, tuple(shape), band, sentinel, where))
+        out = raw[lo:lo + n].view(shape)
+        if fill is not None:
+            out.fill_(fill)
+        return out
+
+    def put(self, t, name="buffer"):
+        out = self.new(tuple(t.shape), name=name, dtype=t.dtype)
+        out.copy_(t)
+        return out
+
+    def check(self, what):
+        torch.cuda.synchronize()
+        for name, shape, band, sentinel, where in self.bands:
+            bad = int((band != sentinel).sum())
+            assert bad == 0, f"{what} wrote {bad} elements {where} {name} {shape}"

@@ -42,14 +42,11 @@ import pytest
 import torch
 import torch.nn.functional as Fn
 
-from helpers import grad_bound
+from helpers import BAND, DEV, SENTINEL, _Guard, grad_bound
 from movenet_amd import _native as N
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-SENTINEL = -1234.5
 NAN = float("nan")
-BAND = 1 << 14                     # floats of sentinel behind every buffer
 TOL_FWD = 1e-5
 PNAMES = ("conv_w", "conv_b", "up_w0", "up_b0", "up_w1", "up_b1", "up_w2", "up_b2")
 SLAB_FLOATS = 640 * 64 + 64        # one workgroup's weight-gradient slab and its 64 bias sums (C = 64)
@@ -62,34 +59,6 @@ def _stream():
 
 def _err(got, want):
     return ((got.double().cpu() - want).abs().max() / want.abs().max().clamp_min(1e-30)).item()
-
-
-class _Guard:
-    """Buffers carved from the front of larger allocations, a band of sentinel values behind each"""
-
-    def __init__(self):
-        self.bands = []
-
-    def new(self, shape, fill=None, name="buffer"):
-        n = math.prod(shape)
-        raw = torch.empty(n + BAND, dtype=torch.float32, device=DEV)
-        raw[n:].fill_(SENTINEL)
-        self.bands.append((name, tuple(shape), raw[n:]))
-        out = raw[:n].view(shape)
-        if fill is not None:
-            out.fill_(fill)
-        return out
-
-    def put(self, t, name="buffer"):
-        out = self.new(tuple(t.shape), name=name)
-        out.copy_(t)
-        return out
-
-    def check(self, what):
-        torch.cuda.synchronize()
-        for name, shape, band in self.bands:
-            bad = int((band != SENTINEL).sum())
-            assert bad == 0, f"{what} wrote {bad} floats past the end of {name} {shape}"
 
 
 def _dims(C):
