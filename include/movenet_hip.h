@@ -185,6 +185,26 @@ int mvn_generate(const mvn_dims *dims, int variant, const float *packed, float *
                  float *logits_out, int32_t *choices_out, int logits_t0,
                  const float *context_tm, void *stream);
 
+/* The rule a sampled step (temperature > 0) draws by.  REFERENCE: softmax(softmax(logits)/T), as
+ * above -- its second softmax sees inputs in [0, 1], so the draw is close to uniform whatever the
+ * logits say.  MODEL: the distribution the network was trained to predict,
+ *     p_q = exp((l_q - max l) / T) / sum_j exp((l_j - max l) / T)
+ * over the step's raw fp32 head logits l.  Both draw by the same inverse CDF on the same Philox
+ * uniform of (seed, time, sequence): the smallest class q with sum_{j<=q} p_j > uniform * total,
+ * Q - 1 if none qualifies.  Padding classes of a 256-wide head (logit -inf) get probability 0. */
+#define MVN_SAMPLE_REFERENCE 0
+#define MVN_SAMPLE_MODEL 1
+
+/* mvn_generate with the sampling rule chosen: `sampling` is MVN_SAMPLE_REFERENCE (what mvn_generate
+ * passes) or MVN_SAMPLE_MODEL; any other value is MVN_ERR_BAD_ARG, before any launch.  The rule
+ * changes only the choice of a sampled step: temperature <= 0 is the same greedy arg-max under
+ * both, and logits_out, the state and the network arithmetic do not depend on it. */
+int mvn_generate_ex(const mvn_dims *dims, int variant, const float *packed, float *state,
+                    int32_t *samples, int batch, int sample_stride, int n_total, int n_given,
+                    int t_begin, int t_end, float temperature, uint64_t seed,
+                    float *logits_out, int32_t *choices_out, int logits_t0,
+                    const float *context_tm, int sampling, void *stream);
+
 /* Local conditioning in generation (BUILD DEFINITION, the reference raises: SURVEY.md
  * Q7): step t adds the context column of time t to every layer's filter/gate sums.
  * context_tm is (batch, n_total, C) TIME-major (one coalesced 4C-byte read per step);

@@ -25,6 +25,8 @@ MVN_ERR_UNSUPPORTED = -5
 GEN_AUTO, GEN_GENERIC, GEN_STREAM, GEN_PIPE, GEN_PIPE_F16, GEN_FOLD = 0, 1, 2, 3, 4, 5
 BWD_FORM_GENERIC, BWD_FORM_HALVES, BWD_FORM_ONE = 1, 2, 3  # mvn_last_backward_form (include/movenet_hip.h)
 BWD_FORM_BF16 = 4  # mvn_backward_bf16's layer kernel
+SAMPLE_REFERENCE, SAMPLE_MODEL = 0, 1  # mvn_generate_ex's rule of a sampled step (include/movenet_hip.h)
+SAMPLING_RULES = {"reference": SAMPLE_REFERENCE, "model": SAMPLE_MODEL}
 PIPE_VARIANTS = (GEN_PIPE, GEN_PIPE_F16, GEN_FOLD)  # variants with a hand-off status word
 
 
@@ -109,6 +111,9 @@ SIGNATURES = {
     "mvn_generate": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "mvn_generate_ex": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                  C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "mvn_transpose_context": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                         C.c_void_p]),
     "mvn_padded_len": (C.c_int, [C.c_int]),
@@ -210,6 +215,13 @@ def check(rc: int, what: str) -> int:
     if rc in (MVN_ERR_BAD_DIMS, MVN_ERR_BAD_ARG, MVN_ERR_UNSUPPORTED):
         raise ValueError(msg)
     raise RuntimeError(msg)
+
+
+def sampling_rule(value) -> int:
+    """"reference" / "model" -> MVN_SAMPLE_*; ValueError for anything else."""
+    if not isinstance(value, str) or value not in SAMPLING_RULES:
+        raise ValueError(f"sampling must be 'reference' or 'model', got {value!r}")
+    return SAMPLING_RULES[value]
 
 
 def make_dims(layer_size: int, stack_size: int, input_channels: int, residual_channels: int,

@@ -16,6 +16,7 @@ struct GenArgs {
   float *logits_out;
   int32_t *choices_out;
   int logits_t0;
+  int sampling;  // MVN_SAMPLE_*: the rule of a sampled step (temperature > 0); greedy steps do not consult it
   // local conditioning (NULL = audio only): context (B, n_total, C) time-major and the
   // packed context-conv section of the weight blob
   const float *ctx_tm;

@@ -15,6 +15,7 @@
 //   logits = W2.lrelu(W1.lrelu(skip) + b1) + b2             (modules.py:139-142)
 //   x_{t+1} = argmax / multinomial of softmax(softmax(logits)[/T])
 //                                                    (wavenet.py:189-191, :227-233)
+//             or, MVN_SAMPLE_MODEL: multinomial of softmax(logits / T)
 //
 // Two variants:
 //   GENERIC  any dims; weights stored transposed ([in][out]) so a thread per
@@ -198,33 +199,38 @@ __global__ __launch_bounds__(1024) void gen_generic_kernel(GenArgs a) {
           a.logits_out[((size_t)b * (a.n_total - a.logits_t0) + (u - a.logits_t0)) * Q + q] = v;
       }
       __syncthreads();
-      // softmax(softmax(x)[/T])  (wavenet.py:189-191 then :227-233)
+      // softmax(softmax(x)[/T])  (wavenet.py:189-191 then :227-233), or on a sampled step under
+      // MVN_SAMPLE_MODEL the weights exp((x - max) / T) of softmax(x / T): thread 0 draws against their total
       float m = -INFINITY;
       for (int q = tid; q < Q; q += NT) m = fmaxf(m, logits[q]);
       m = block_max_g(m, red);
-      float s = 0.f;
-      for (int q = tid; q < Q; q += NT) {
-        const float e = expf(logits[q] - m);
-        a1[q] = e;
-        s += e;
+      if (a.temperature > 0.f && a.sampling == MVN_SAMPLE_MODEL) {  // block-uniform
+        for (int q = tid; q < Q; q += NT) a1[q] = expf((logits[q] - m) / a.temperature);
+      } else {
+        float s = 0.f;
+        for (int q = tid; q < Q; q += NT) {
+          const float e = expf(logits[q] - m);
+          a1[q] = e;
+          s += e;
+        }
+        s = block_sum_g(s, red);
+        float m2 = -INFINITY;
+        for (int q = tid; q < Q; q += NT) {
+          float p = a1[q] / s;
+          if (a.temperature > 0.f) p = p / a.temperature;
+          a1[q] = p;
+          m2 = fmaxf(m2, p);
+        }
+        m2 = block_max_g(m2, red);
+        float s2 = 0.f;
+        for (int q = tid; q < Q; q += NT) {
+          const float e = expf(a1[q] - m2);
+          a1[q] = e;
+          s2 += e;
+        }
+        s2 = block_sum_g(s2, red);
+        for (int q = tid; q < Q; q += NT) a1[q] = a1[q] / s2;
       }
-      s = block_sum_g(s, red);
-      float m2 = -INFINITY;
-      for (int q = tid; q < Q; q += NT) {
-        float p = a1[q] / s;
-        if (a.temperature > 0.f) p = p / a.temperature;
-        a1[q] = p;
-        m2 = fmaxf(m2, p);
-      }
-      m2 = block_max_g(m2, red);
-      float s2 = 0.f;
-      for (int q = tid; q < Q; q += NT) {
-        const float e = expf(a1[q] - m2);
-        a1[q] = e;
-        s2 += e;
-      }
-      s2 = block_sum_g(s2, red);
-      for (int q = tid; q < Q; q += NT) a1[q] = a1[q] / s2;
       __syncthreads();
       if (tid == 0) {
         int choice = 0;
@@ -483,28 +489,35 @@ __global__ __launch_bounds__(256, 1) void gen_stream64_kernel(GenArgs a) {
       // bias, no probability in either softmax, never written out)
       if (a.logits_out && u >= a.logits_t0 && tid < a.Q)
         a.logits_out[((size_t)b * (a.n_total - a.logits_t0) + (u - a.logits_t0)) * a.Q + tid] = lg;
-      // softmax -> [/T] -> softmax, one class per thread
+      // softmax -> [/T] -> softmax (or, MVN_SAMPLE_MODEL: softmax(logits / T)), one class per thread
       float m = wave_max(lg);
       if (lane == 0) red[0 + wave] = m;
       lds_barrier();
       m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-      const float e = expf(lg - m);
-      float s = wave_sum(e);
-      if (lane == 0) red[4 + wave] = s;
-      lds_barrier();
-      s = (red[4] + red[5]) + (red[6] + red[7]);
-      float p = e / s;
-      if (a.temperature > 0.f) p = p / a.temperature;
-      float m2 = wave_max(p);
-      if (lane == 0) red[8 + wave] = m2;
-      lds_barrier();
-      m2 = fmaxf(fmaxf(red[8], red[9]), fmaxf(red[10], red[11]));
-      const float e2 = tid < a.Q ? expf(p - m2) : 0.f;
-      float s2 = wave_sum(e2);
-      if (lane == 0) red[12 + wave] = s2;
-      lds_barrier();
-      s2 = (red[12] + red[13]) + (red[14] + red[15]);
-      const float p2 = e2 / s2;
+      float p2;
+      if (a.temperature > 0.f && a.sampling == MVN_SAMPLE_MODEL) {  // block-uniform
+        // the weight exp((l - max) / T) of softmax(logits / T): the scan below draws against the total (a padding
+        // class, logit -inf, weighs exactly 0)
+        p2 = expf((lg - m) / a.temperature);
+      } else {
+        const float e = expf(lg - m);
+        float s = wave_sum(e);
+        if (lane == 0) red[4 + wave] = s;
+        lds_barrier();
+        s = (red[4] + red[5]) + (red[6] + red[7]);
+        float p = e / s;
+        if (a.temperature > 0.f) p = p / a.temperature;
+        float m2 = wave_max(p);
+        if (lane == 0) red[8 + wave] = m2;
+        lds_barrier();
+        m2 = fmaxf(fmaxf(red[8], red[9]), fmaxf(red[10], red[11]));
+        const float e2 = tid < a.Q ? expf(p - m2) : 0.f;
+        float s2 = wave_sum(e2);
+        if (lane == 0) red[12 + wave] = s2;
+        lds_barrier();
+        s2 = (red[12] + red[13]) + (red[14] + red[15]);
+        p2 = e2 / s2;
+      }
 
       int cand;
       if (a.temperature > 0.f) {
@@ -941,9 +954,24 @@ int mvn_generate(const mvn_dims *dims, int variant, const float *packed, float *
                  int32_t *samples, int batch, int sample_stride, int n_total, int n_given,
                  int t_begin, int t_end, float temperature, uint64_t seed, float *logits_out,
                  int32_t *choices_out, int logits_t0, const float *context_tm, void *stream) {
+  return mvn_generate_ex(dims, variant, packed, state, samples, batch, sample_stride, n_total, n_given, t_begin,
+                         t_end, temperature, seed, logits_out, choices_out, logits_t0, context_tm,
+                         MVN_SAMPLE_REFERENCE, stream);
+}
+
+int mvn_generate_ex(const mvn_dims *dims, int variant, const float *packed, float *state,
+                    int32_t *samples, int batch, int sample_stride, int n_total, int n_given,
+                    int t_begin, int t_end, float temperature, uint64_t seed, float *logits_out,
+                    int32_t *choices_out, int logits_t0, const float *context_tm, int sampling,
+                    void *stream) {
   if (variant == MVN_GEN_AUTO) {
     mvn::set_error("mvn_generate: resolve the variant with mvn_gen_variant first (the packed "
                    "weight layout depends on it)");
+    return MVN_ERR_BAD_ARG;
+  }
+  if (sampling != MVN_SAMPLE_REFERENCE && sampling != MVN_SAMPLE_MODEL) {
+    mvn::set_error("mvn_generate_ex: bad argument (sampling %d is neither MVN_SAMPLE_REFERENCE nor "
+                   "MVN_SAMPLE_MODEL)", sampling);
     return MVN_ERR_BAD_ARG;
   }
   variant = mvn_gen_variant(dims, variant, batch > 0 ? batch : 1);
@@ -977,6 +1005,7 @@ int mvn_generate(const mvn_dims *dims, int variant, const float *packed, float *
   a.logits_out = logits_out;
   a.choices_out = choices_out;
   a.logits_t0 = logits_t0;
+  a.sampling = sampling;
   a.ctx_tm = context_tm;
   a.ctx_stride_b = (long long)n_total * dims->residual_channels;
   a.wctx = packed + mvn::gen_base_floats(dims, variant);

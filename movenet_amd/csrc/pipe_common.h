@@ -1,7 +1,7 @@
 // Shared by the pipelined generator kernels (generate_pipe.hip: fp32, C = 64 / 128; generate_fold.hip: fp32,
 // C = 64, folded layers; generate_pipe_h16.hip: fp16 operands, C = 128): placement and its handshake, the granule
-// hand-off, cross-lane moves as DPP, the gate, the step-closing choice (double softmax, arg-max / inverse-CDF
-// sample), the head stage's step loop and the fp32 head's packing.
+// hand-off, cross-lane moves as DPP, the gate, the step-closing choice (double softmax or, MVN_SAMPLE_MODEL, the
+// model's own softmax; arg-max / inverse-CDF sample), the head stage's step loop and the fp32 head's packing.
 #pragma once
 #include <cstdio>
 #include <cstdlib>
@@ -485,7 +485,8 @@ __device__ __forceinline__ float chan_sum(float v) {
 // Wave 0 closes a step alone: lane i owns the logits of classes 4i .. 4i+3 (Q = 256); every
 // reduction is intra-wave (DPP + readlane), no barrier.  Returns the class WaveNet.generate
 // picks for time u: softmax (wavenet.py:189-191), [/ T], softmax again, then multinomial by
-// inverse CDF on the Philox uniform of (seed, u, b) or the first arg-max (:227-233).
+// inverse CDF on the Philox uniform of (seed, u, b) or the first arg-max (:227-233); under
+// MVN_SAMPLE_MODEL a sampled step draws from softmax(logits / T) instead (choose_class).
 // v_exp_f32 / v_rcp_f32 forms (1-2 ulp): the choice depends on the ORDER of the
 // probabilities, which these monotone maps preserve.
 // Greedy decoding, the common case: when the largest logit leads the runner-up by a clear margin,
@@ -532,19 +533,14 @@ __device__ __forceinline__ bool greedy_pick_clear(const float (&lg)[4], int lane
   return rv - rs >= 1e-3f;
 }
 
-// `uniform`: philox_uniform(seed, u, b), formed by the caller BEFORE it waits for the step's input (ten
-// Philox rounds of integer multiplies: ~0.15 us that do not depend on the logits).
-__device__ __forceinline__ int choose_class(const float (&lg)[4], float temperature, float uniform, int lane, int Q) {
-  if (!(temperature > 0.f)) {
-    int fast;
-    if (greedy_pick_clear(lg, lane, fast)) return fast;
-  }
-  const float m = wave_max_dpp(fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3])));
-  float e[4];
+// The reference's double softmax of a step, unnormalised: e[k] = exp(p_k - max p) with p = softmax(lg) * inv_t
+// (inv_t: 1 / T of a sampled step, 1 for a greedy one); returns the sum of e over the wave.
+__device__ __forceinline__ float double_softmax(const float (&lg)[4], float m, float inv_t, int lane, int Q,
+                                                float (&e)[4]) {
 #pragma unroll
   for (int k = 0; k < 4; ++k) e[k] = __expf(lg[k] - m);
   const float sm = wave_sum_dpp((e[0] + e[1]) + (e[2] + e[3]));
-  const float rs = __builtin_amdgcn_rcpf(sm) * (temperature > 0.f ? __builtin_amdgcn_rcpf(temperature) : 1.0f);
+  const float rs = __builtin_amdgcn_rcpf(sm) * inv_t;
   float p[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) p[k] = e[k] * rs;
@@ -555,48 +551,62 @@ __device__ __forceinline__ int choose_class(const float (&lg)[4], float temperat
   // in this second softmax either, where exp(0 - m2) would give each of them some)
 #pragma unroll
   for (int k = 0; k < 4; ++k) e[k] = 4 * lane + k < Q ? __expf(p[k] - m2) : 0.f;
-  const float s2sum = wave_sum_dpp((e[0] + e[1]) + (e[2] + e[3]));
-  const float rs2 = __builtin_amdgcn_rcpf(s2sum);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) p[k] = e[k] * rs2;  // the distribution generate() uses
+  return wave_sum_dpp((e[0] + e[1]) + (e[2] + e[3]));
+}
 
-  int pick;
-  if (temperature > 0.f) {
-    const float lsum = (p[0] + p[1]) + (p[2] + p[3]);
-    // inclusive scan of the lane totals in class order: four DPP row shifts inside each row of 16
-    // lanes (zeros shifted in), then the totals of the rows below as scalars (six __shfl_up steps
-    // = six LDS-crossbar round trips before: ~0.25 us of every sampled step)
-    float incl = lsum;
-    incl += dpp_mov<0x111>(incl);  // row_shr:1
-    incl += dpp_mov<0x112>(incl);  // row_shr:2
-    incl += dpp_mov<0x114>(incl);  // row_shr:4
-    incl += dpp_mov<0x118>(incl);  // row_shr:8
-    {
-      const float r0 = lane_value(incl, 15), r1 = lane_value(incl, 31), r2 = lane_value(incl, 47);
-      const int row = lane >> 4;
-      incl += row == 0 ? 0.f : row == 1 ? r0 : row == 2 ? r0 + r1 : (r0 + r1) + r2;
-    }
-    const float total = lane_value(incl, 63);
-    const float target = uniform * total;
-    const float cdf = incl - lsum;
-    int cand = Q - 1;
-    bool hit = false;
+// Inverse CDF over the wave's 256 weights p (lane i: classes 4i .. 4i+3, need not sum to one): the smallest class
+// whose running sum exceeds uniform * total, Q - 1 if none does.
+__device__ __forceinline__ int sample_cdf(const float (&p)[4], float uniform, int lane, int Q) {
+  const float lsum = (p[0] + p[1]) + (p[2] + p[3]);
+  // inclusive scan of the lane totals in class order: four DPP row shifts inside each row of 16
+  // lanes (zeros shifted in), then the totals of the rows below as scalars (six __shfl_up steps
+  // = six LDS-crossbar round trips before: ~0.25 us of every sampled step)
+  float incl = lsum;
+  incl += dpp_mov<0x111>(incl);  // row_shr:1
+  incl += dpp_mov<0x112>(incl);  // row_shr:2
+  incl += dpp_mov<0x114>(incl);  // row_shr:4
+  incl += dpp_mov<0x118>(incl);  // row_shr:8
+  {
+    const float r0 = lane_value(incl, 15), r1 = lane_value(incl, 31), r2 = lane_value(incl, 47);
+    const int row = lane >> 4;
+    incl += row == 0 ? 0.f : row == 1 ? r0 : row == 2 ? r0 + r1 : (r0 + r1) + r2;
+  }
+  const float total = lane_value(incl, 63);
+  const float target = uniform * total;
+  const float cdf = incl - lsum;
+  int cand = Q - 1;
+  bool hit = false;
 #pragma unroll
-    for (int k = 3; k >= 0; --k) {
-      // walk down so that the smallest qualifying class wins
-      const float c_k = cdf + (k == 0 ? p[0] : k == 1 ? p[0] + p[1]
-                                              : k == 2 ? (p[0] + p[1]) + p[2]
-                                                       : ((p[0] + p[1]) + p[2]) + p[3]);
-      if (c_k > target) {
-        cand = 4 * lane + k;
-        hit = true;
-      }
+  for (int k = 3; k >= 0; --k) {
+    // walk down so that the smallest qualifying class wins
+    const float c_k = cdf + (k == 0 ? p[0] : k == 1 ? p[0] + p[1]
+                                            : k == 2 ? (p[0] + p[1]) + p[2]
+                                                     : ((p[0] + p[1]) + p[2]) + p[3]);
+    if (c_k > target) {
+      cand = 4 * lane + k;
+      hit = true;
     }
-    // the smallest qualifying class over the wave = the candidate of the FIRST lane that has one
-    // (classes ascend with the lane): one ballot and one readlane instead of a min-reduction
-    const unsigned long long lanes = __builtin_amdgcn_ballot_w64(hit);
-    pick = lanes ? __builtin_amdgcn_readlane(cand, __builtin_ctzll(lanes)) : Q - 1;
-  } else {
+  }
+  // the smallest qualifying class over the wave = the candidate of the FIRST lane that has one
+  // (classes ascend with the lane): one ballot and one readlane instead of a min-reduction
+  const unsigned long long lanes = __builtin_amdgcn_ballot_w64(hit);
+  return lanes ? __builtin_amdgcn_readlane(cand, __builtin_ctzll(lanes)) : Q - 1;
+}
+
+// `uniform`: philox_uniform(seed, u, b), formed by the caller BEFORE it waits for the step's input (ten
+// Philox rounds of integer multiplies: ~0.15 us that do not depend on the logits).
+// `sampling` (MVN_SAMPLE_*, wave-uniform) is read on sampled steps only: a greedy step leaves through its own
+// branch first, the same code under both rules.
+__device__ __forceinline__ int choose_class(const float (&lg)[4], float temperature, int sampling, float uniform,
+                                            int lane, int Q) {
+  if (!(temperature > 0.f)) {
+    int pick;
+    if (greedy_pick_clear(lg, lane, pick)) return pick;
+    const float m = wave_max_dpp(fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3])));
+    float e[4], p[4];
+    const float rs2 = __builtin_amdgcn_rcpf(double_softmax(lg, m, 1.0f, lane, Q, e));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p[k] = e[k] * rs2;  // the distribution generate() uses
     float bv = p[0];
     int bi = 4 * lane;
 #pragma unroll
@@ -614,8 +624,24 @@ __device__ __forceinline__ int choose_class(const float (&lg)[4], float temperat
 #pragma unroll
     for (int row = 16; row < 64; row += 16)
       argmax_take(rv, pick, lane_value(bv, row), __builtin_amdgcn_readlane(bi, row));
+    return pick;
   }
-  return pick;
+  const float m = wave_max_dpp(fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3])));
+  const float inv_t = __builtin_amdgcn_rcpf(temperature);
+  float p[4];
+  if (sampling == MVN_SAMPLE_MODEL) {
+    // softmax(logits / T), unnormalised: 1 / T folded into the exponent, no second softmax, and no division by
+    // the sum either -- the inverse CDF scales its uniform by the total.  The largest weight is exp(0) = 1, so the
+    // total lies in [1, 256]; a padding class (logit -inf) has exp(-inf) = 0 exactly.
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p[k] = __expf((lg[k] - m) * inv_t);
+  } else {
+    float e[4];
+    const float rs2 = __builtin_amdgcn_rcpf(double_softmax(lg, m, inv_t, lane, Q, e));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p[k] = e[k] * rs2;  // the distribution generate() uses
+  }
+  return sample_cdf(p, uniform, lane, Q);
 }
 
 // fp32 conv2 of the head: thread (og = tid >> 3, q2 = tid & 7) holds 4 output rows x 32 inputs in w2; the eight
@@ -728,7 +754,7 @@ __device__ __forceinline__ void head_loop(const GenArgs &a, u64 *hand, int NS, i
         // (rows of a.Q logits: the padding of a smaller model is not written; fp16 PIPE takes Q = 256 only)
         if (a.logits_out && u >= a.logits_t0 && 4 * lane < a.Q)
           ((f4 *)(a.logits_out + ((size_t)bq * (a.n_total - a.logits_t0) + (u - a.logits_t0)) * a.Q))[lane] = lv;
-        pick = choose_class(lg, a.temperature, uni, lane, a.Q);
+        pick = choose_class(lg, a.temperature, a.sampling, uni, lane, a.Q);
         if (u >= a.n_given) next_idx = pick;
       }
       idx_prev = idx_cur;

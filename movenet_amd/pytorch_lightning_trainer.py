@@ -42,6 +42,7 @@ class Dance2Music(nn.Module):
         self.dataset_fp = dataset_fp
         self.config = config
         self.model = WaveNet(**asdict(config.model_config))
+        self.model.generate_sampling = config.generate_sampling  # (ValueError for an unknown rule)
         self.current_epoch = 0
         self.precision = 32
         self.rank, self.world_size = 0, 1

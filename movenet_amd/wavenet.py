@@ -77,6 +77,7 @@ class WaveNet(nn.Module):
         # bf16 operands / fp32 accumulation in the layers' products, forward AND backward
         # (mvn_forward_bf16 / mvn_backward_bf16: audio-only, residual = skip channels = 64)
         self.forward_precision = "fp32"
+        self._gen_sampling = "reference"
 
     # ---- precision of generate() ----------------------------------------
     @property
@@ -96,6 +97,20 @@ class WaveNet(nn.Module):
             self._gen_variant = N.GEN_PIPE_F16
         else:
             raise ValueError(f"generate_precision must be 'fp32' or 'fp16', got {value!r}")
+
+    # ---- what a sampled generate() step draws from -----------------------
+    @property
+    def generate_sampling(self) -> str:
+        """"reference" (default: the reference's rule, softmax(softmax(logits) / T) -- its second softmax
+        sees inputs in [0, 1], so the draw is close to uniform whatever the model has learned) or "model":
+        the distribution the network was trained to predict, softmax(logits / T).  Only steps with
+        temperature > 0 consult it; greedy decoding is the same under both."""
+        return getattr(self, "_gen_sampling", "reference")  # (a module pickled before the attribute existed)
+
+    @generate_sampling.setter
+    def generate_sampling(self, value: str) -> None:
+        N.sampling_rule(value)  # ValueError for anything else
+        self._gen_sampling = value
 
     # ---- shape arithmetic (host only) ---------------------------------
     @property
@@ -222,7 +237,8 @@ class WaveNet(nn.Module):
             raise ValueError(f"the upsampled video covers {context.shape[2]} samples, "
                              f"n_samples={n_total} asked for")
         kw = dict(batch=idx.shape[0], n_total=n_total, device=audio.device,
-                  temperature=float(temperature), seed=seed, context=context)
+                  temperature=float(temperature), seed=seed, context=context,
+                  sampling=self.generate_sampling)
         def run(variant, group):
             if group:
                 gen = GroupedGenerator(self.layer_size, self.stack_size, self.input_channels,
