@@ -205,6 +205,35 @@ int mvn_generate_ex(const mvn_dims *dims, int variant, const float *packed, floa
                     float *logits_out, int32_t *choices_out, int logits_t0,
                     const float *context_tm, int sampling, void *stream);
 
+/* mvn_generate_ex with top-k and top-p (nucleus) truncation of a sampled step; mvn_generate_ex passes
+ * (0, 1.0f): both off.  A sampled step (temperature > 0) forms fp32 weights w_q >= 0 over the Q classes,
+ * not necessarily normalised -- MODEL: exp((l_q - max l) / T); REFERENCE: the double softmax.
+ * Truncation sets some of them to zero before the unchanged inverse-CDF draw on the unchanged Philox
+ * uniform of (seed, time, sequence):
+ *  1. top_k = k >= 0.  0: off; k >= Q: the same as off.  theta_k is the k-th largest value of w,
+ *     counted with multiplicity over the Q real classes; class q is kept iff w_q >= theta_k.  Exact
+ *     ties at the threshold are all kept.
+ *  2. top_p = p in (0, 1].  1.0: off.  Applied after top-k: with S the sum of the weights top-k kept,
+ *     theta_p is the largest weight value v for which the sum of the kept weights >= v reaches p * S;
+ *     class q is kept iff w_q >= max(theta_k, theta_p).  The largest weight always survives, so the
+ *     kept set is never empty.
+ *  3. The draw: the smallest class q whose running sum over the truncated weights exceeds
+ *     uniform * total_kept.  If rounding lets no class qualify, the highest-indexed kept class --
+ *     never a dropped one.
+ *  4. With both off, mvn_generate_ex's behaviour to the bit (the Q - 1 fallback included).  Greedy
+ *     steps (temperature <= 0) ignore both knobs.  Truncation applies under either rule: it acts on
+ *     whatever weights the step draws from.  logits_out, the state and the network arithmetic never
+ *     depend on the knobs.
+ * The thresholds are exact for the fp32 weights (a radix select on their bit patterns: no sort, no
+ * tolerance); the sums of 2. are fp32 sums.
+ * top_k < 0, or top_p outside (0, 1] (NaN included): MVN_ERR_BAD_ARG with a mvn_last_error() text,
+ * before any launch and before any buffer is touched. */
+int mvn_generate_trunc(const mvn_dims *dims, int variant, const float *packed, float *state,
+                       int32_t *samples, int batch, int sample_stride, int n_total, int n_given,
+                       int t_begin, int t_end, float temperature, uint64_t seed,
+                       float *logits_out, int32_t *choices_out, int logits_t0,
+                       const float *context_tm, int sampling, int top_k, float top_p, void *stream);
+
 /* Local conditioning in generation (BUILD DEFINITION, the reference raises: SURVEY.md
  * Q7): step t adds the context column of time t to every layer's filter/gate sums.
  * context_tm is (batch, n_total, C) TIME-major (one coalesced 4C-byte read per step);

@@ -114,6 +114,10 @@ SIGNATURES = {
     "mvn_generate_ex": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                   C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "mvn_generate_trunc": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                     C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                     C.c_float, C.c_void_p]),
     "mvn_transpose_context": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                         C.c_void_p]),
     "mvn_padded_len": (C.c_int, [C.c_int]),
@@ -222,6 +226,16 @@ def sampling_rule(value) -> int:
     if not isinstance(value, str) or value not in SAMPLING_RULES:
         raise ValueError(f"sampling must be 'reference' or 'model', got {value!r}")
     return SAMPLING_RULES[value]
+
+
+def truncation(top_k, top_p):
+    """(top_k, top_p) of mvn_generate_trunc as (int, float); ValueError unless top_k is an integer >= 0 (0: off) and
+    top_p a number in (0, 1] (1: off; NaN refused)."""
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0:
+        raise ValueError(f"top_k must be an integer >= 0 (0: off), got {top_k!r}")
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must lie in (0, 1] (1: off), got {top_p!r}")
+    return int(top_k), float(top_p)
 
 
 def make_dims(layer_size: int, stack_size: int, input_channels: int, residual_channels: int,

@@ -54,6 +54,10 @@ class TrainingConfig:
     # softmax(softmax(logits) / T), or "model", the model's own softmax(logits / T).  Not a field of the
     # reference's config: a JSON written without it loads with the default.
     generate_sampling: str = "reference"
+    # truncation of a sampled step before the draw (WaveNet.generate_top_k / generate_top_p): the k likeliest classes
+    # (0: off), then the smallest head of them that holds p of their mass (1.0: off).  Not reference fields either.
+    generate_top_k: int = 0
+    generate_top_p: float = 1.0
 
     scheduler: Optional[str] = "OneCycleLR"
     lr_pct_start: float = 0.45
@@ -134,6 +138,8 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--generate_n_samples", type=lambda x: x if x is None else int(x), default=None)
     a("--generate_temperature", type=float, default=1.0)
     a("--generate_sampling", type=str, default="reference", choices=["reference", "model"])
+    a("--generate_top_k", type=int, default=0)
+    a("--generate_top_p", type=float, default=1.0)
     a("--n_epochs", type=int, default=10)
     a("--n_steps_per_epoch", type=int, default=None)
     a("--use_video", type=_flag, default=True)
@@ -176,7 +182,7 @@ def config_from_args(args) -> TrainingConfig:
         "lr_pct_start base_learning_rate scheduler_step_size_up scheduler_step_size_down "
         "scheduler_cyclic_mode scheduler_cyclic_gamma scheduler_cycle_momentum max_learning_rate "
         "scheduler_step_size scheduler_step_gamma scheduler_milestones weight_decay "
-        "generate_n_samples generate_temperature generate_sampling accumulation_steps num_workers val_num_workers "
+        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p accumulation_steps num_workers val_num_workers "
         "pin_memory n_epochs n_steps_per_epoch use_video batch_subsample_frac "
         "val_batch_subsample_frac dist_backend dist_port model_output_path log_samples_every"
     ).split()

@@ -17,6 +17,10 @@ struct GenArgs {
   int32_t *choices_out;
   int logits_t0;
   int sampling;  // MVN_SAMPLE_*: the rule of a sampled step (temperature > 0); greedy steps do not consult it
+  // truncation of a sampled step's weights before the draw (mvn_generate_trunc): keep the top_k largest (0: off;
+  // the host passes 0 for top_k >= Q), then the smallest head of them that holds top_p of their mass (1: off)
+  int top_k;
+  float top_p;
   // local conditioning (NULL = audio only): context (B, n_total, C) time-major and the
   // packed context-conv section of the weight blob
   const float *ctx_tm;

@@ -16,6 +16,7 @@
 //   x_{t+1} = argmax / multinomial of softmax(softmax(logits)[/T])
 //                                                    (wavenet.py:189-191, :227-233)
 //             or, MVN_SAMPLE_MODEL: multinomial of softmax(logits / T)
+//             either after top-k / top-p truncation of the step's weights (mvn_generate_trunc)
 //
 // Two variants:
 //   GENERIC  any dims; weights stored transposed ([in][out]) so a thread per
@@ -86,6 +87,56 @@ __device__ float block_sum_g(float v, float *red) {
   for (int w = 1; w < nw; ++w) r += red[w];
   __syncthreads();
   return r;
+}
+
+// Top-k / top-p truncation of a sampled step (include/movenet_hip.h, mvn_generate_trunc) for the two kernels of this
+// file, called by the 64 threads of WAVE 0 with the step's weights w[0 .. Q) >= 0 in LDS (written behind a barrier;
+// the caller puts another one behind the call).  The same exact selection as pipe_common.h's truncate_weights:
+// non-negative floats order like their bit patterns, and a radix select on the pattern, most significant bit first,
+// finds the top_k-th largest weight (the classes at or above a candidate are counted) and the largest weight value
+// whose head of the distribution holds top_p of what top-k kept (they are summed; the fp32 sum of non-negative terms
+// is monotone in each, so the bit walk is exact for it).  One wave and no barrier in the 62 rounds: lane i takes
+// classes i, i + 64, ...  Dropped classes are zeroed in w; returns the highest-indexed kept class.
+__device__ int truncate_weights_lds(float *w, int Q, int top_k, float top_p) {
+  const int lane = threadIdx.x;  // < 64
+  const int qend = (Q + 63) & ~63;  // wave-uniform trip count
+  auto count_from = [&](unsigned lo) {
+    int n = 0;
+    for (int q = lane; q < qend; q += 64)
+      n += __builtin_popcountll(__builtin_amdgcn_ballot_w64(q < Q && __float_as_uint(w[q]) >= lo));
+    return n;
+  };
+  auto mass_from = [&](unsigned lo) {
+    float s = 0.f;
+    for (int q = lane; q < Q; q += 64) s += __float_as_uint(w[q]) >= lo ? w[q] : 0.f;
+    return wave_sum(s);  // (xor butterfly: the same value in every lane)
+  };
+  unsigned theta = 0;  // wave-uniform throughout
+  if (top_k > 0) {
+    for (int bit = 30; bit >= 0; --bit) {
+      const unsigned cand = theta | (1u << bit);
+      if (count_from(cand) >= top_k) theta = cand;
+    }
+  }
+  if (top_p < 1.f) {
+    const float need = top_p * mass_from(theta);
+    unsigned tp = 0;
+    for (int bit = 30; bit >= 0; --bit) {
+      const unsigned cand = tp | (1u << bit);
+      if (mass_from(cand > theta ? cand : theta) >= need) tp = cand;
+    }
+    theta = tp > theta ? tp : theta;
+  }
+  int top = -1;
+  for (int q = lane; q < Q; q += 64) {
+    if (__float_as_uint(w[q]) >= theta)
+      top = q;
+    else
+      w[q] = 0.f;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) top = max(top, __shfl_xor(top, o, 64));
+  return top >= 0 ? top : Q - 1;
 }
 
 __global__ __launch_bounds__(1024) void gen_generic_kernel(GenArgs a) {
@@ -232,6 +283,12 @@ __global__ __launch_bounds__(1024) void gen_generic_kernel(GenArgs a) {
         for (int q = tid; q < Q; q += NT) a1[q] = a1[q] / s2;
       }
       __syncthreads();
+      int fallback = Q - 1;  // of a draw that no class's running sum exceeds
+      if (a.temperature > 0.f && (a.top_k > 0 || a.top_p < 1.f)) {  // block-uniform
+        // (a zeroed class leaves thread 0's running sum as it was: it never qualifies before the class in front)
+        if (tid < 64) fallback = truncate_weights_lds(a1, Q, a.top_k, a.top_p);
+        __syncthreads();
+      }
       if (tid == 0) {
         int choice = 0;
         if (a.temperature > 0.f) {
@@ -239,7 +296,7 @@ __global__ __launch_bounds__(1024) void gen_generic_kernel(GenArgs a) {
           for (int q = 0; q < Q; ++q) total += a1[q];
           const float target = philox_uniform(a.seed, (uint32_t)u, (uint32_t)b) * total;
           float cdf = 0.f;
-          choice = Q - 1;
+          choice = fallback;
           for (int q = 0; q < Q; ++q) {
             cdf += a1[q];
             if (cdf > target) {
@@ -302,7 +359,7 @@ __global__ __launch_bounds__(256, 1) void gen_stream64_kernel(GenArgs a) {
   float *sk = prs + 256;            // [64]
   float *a1 = sk + 64;              // [256]
   float *red = a1 + 256;            // [8][4]
-  int *ired = (int *)(red + 32);    // [8]: [0..3] per-wave candidate, [4] prev idx, [5] cur idx
+  int *ired = (int *)(red + 32);    // [8]: [0..3] per-wave candidate, [4] prev idx, [5] cur idx, [6] truncation's top class
   float *pastAll = red + 32 + 8;    // [L][64]
   float *pctx = pastAll + (size_t)L * 64;  // [L][128] context-conv terms of the step (conditioned runs only)
   float *cvec = pctx + (a.ctx_tm ? (size_t)L * 128 : 0);  // [64] the step's context column
@@ -521,6 +578,20 @@ __global__ __launch_bounds__(256, 1) void gen_stream64_kernel(GenArgs a) {
 
       int cand;
       if (a.temperature > 0.f) {
+        int fallback = a.Q - 1;
+        const bool trunc = a.top_k > 0 || a.top_p < 1.f;  // block-uniform
+        if (trunc) {
+          // a1 is free (conv2 has read it, barriers ago): the weights go through it, wave 0 zeroes the dropped ones
+          a1[tid] = p2;
+          lds_barrier();
+          if (tid < 64) {
+            const int top = truncate_weights_lds(a1, a.Q, a.top_k, a.top_p);
+            if (tid == 0) ired[6] = top;
+          }
+          lds_barrier();
+          p2 = a1[tid];
+          fallback = ired[6];
+        }
         // inclusive scan of p2 over the 256 classes
         float c = p2;
 #pragma unroll
@@ -536,7 +607,9 @@ __global__ __launch_bounds__(256, 1) void gen_stream64_kernel(GenArgs a) {
         if (wave > 2) base += red[18];
         const float total = ((red[16] + red[17]) + red[18]) + red[19];
         const float target = philox_uniform(a.seed, (uint32_t)u, (uint32_t)b) * total;
-        cand = (base + c > target) ? tid : a.Q - 1;
+        // (truncated: only a class of positive weight may qualify -- the scan associates the sums of neighbouring
+        // classes differently, and a zeroed class could otherwise cross the target a rounding before the kept one)
+        cand = (base + c > target && (!trunc || p2 > 0.f)) ? tid : fallback;
         // first class whose cdf exceeds the target
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) cand = min(cand, __shfl_xor(cand, off, 64));
@@ -964,6 +1037,16 @@ int mvn_generate_ex(const mvn_dims *dims, int variant, const float *packed, floa
                     int t_begin, int t_end, float temperature, uint64_t seed, float *logits_out,
                     int32_t *choices_out, int logits_t0, const float *context_tm, int sampling,
                     void *stream) {
+  return mvn_generate_trunc(dims, variant, packed, state, samples, batch, sample_stride, n_total, n_given, t_begin,
+                            t_end, temperature, seed, logits_out, choices_out, logits_t0, context_tm, sampling, 0,
+                            1.0f, stream);
+}
+
+int mvn_generate_trunc(const mvn_dims *dims, int variant, const float *packed, float *state,
+                       int32_t *samples, int batch, int sample_stride, int n_total, int n_given,
+                       int t_begin, int t_end, float temperature, uint64_t seed, float *logits_out,
+                       int32_t *choices_out, int logits_t0, const float *context_tm, int sampling,
+                       int top_k, float top_p, void *stream) {
   if (variant == MVN_GEN_AUTO) {
     mvn::set_error("mvn_generate: resolve the variant with mvn_gen_variant first (the packed "
                    "weight layout depends on it)");
@@ -972,6 +1055,11 @@ int mvn_generate_ex(const mvn_dims *dims, int variant, const float *packed, floa
   if (sampling != MVN_SAMPLE_REFERENCE && sampling != MVN_SAMPLE_MODEL) {
     mvn::set_error("mvn_generate_ex: bad argument (sampling %d is neither MVN_SAMPLE_REFERENCE nor "
                    "MVN_SAMPLE_MODEL)", sampling);
+    return MVN_ERR_BAD_ARG;
+  }
+  if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) {  // (a NaN top_p fails the comparison)
+    mvn::set_error("mvn_generate_trunc: bad argument (top_k %d must be >= 0, top_p %g must lie in (0, 1])", top_k,
+                   (double)top_p);
     return MVN_ERR_BAD_ARG;
   }
   variant = mvn_gen_variant(dims, variant, batch > 0 ? batch : 1);
@@ -1006,6 +1094,8 @@ int mvn_generate_ex(const mvn_dims *dims, int variant, const float *packed, floa
   a.choices_out = choices_out;
   a.logits_t0 = logits_t0;
   a.sampling = sampling;
+  a.top_k = top_k >= a.Q ? 0 : top_k;  // every class kept: off, to the bit
+  a.top_p = top_p;
   a.ctx_tm = context_tm;
   a.ctx_stride_b = (long long)n_total * dims->residual_channels;
   a.wctx = packed + mvn::gen_base_floats(dims, variant);

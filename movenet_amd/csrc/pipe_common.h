@@ -1,7 +1,8 @@
 // Shared by the pipelined generator kernels (generate_pipe.hip: fp32, C = 64 / 128; generate_fold.hip: fp32,
 // C = 64, folded layers; generate_pipe_h16.hip: fp16 operands, C = 128): placement and its handshake, the granule
 // hand-off, cross-lane moves as DPP, the gate, the step-closing choice (double softmax or, MVN_SAMPLE_MODEL, the
-// model's own softmax; arg-max / inverse-CDF sample), the head stage's step loop and the fp32 head's packing.
+// model's own softmax; top-k / top-p truncation; arg-max / inverse-CDF sample), the head stage's step loop and the
+// fp32 head's packing.
 #pragma once
 #include <cstdio>
 #include <cstdlib>
@@ -555,8 +556,12 @@ __device__ __forceinline__ float double_softmax(const float (&lg)[4], float m, f
 }
 
 // Inverse CDF over the wave's 256 weights p (lane i: classes 4i .. 4i+3, need not sum to one): the smallest class
-// whose running sum exceeds uniform * total, Q - 1 if none does.
-__device__ __forceinline__ int sample_cdf(const float (&p)[4], float uniform, int lane, int Q) {
+// whose running sum exceeds uniform * total, `fallback` if none does (Q - 1 without truncation).
+// POSITIVE (truncated steps): only a class of positive weight may be picked.  In exact arithmetic the smallest
+// qualifying class always has one; in fp32 the running sums of neighbouring classes are associated differently, and
+// a class truncation has zeroed could otherwise qualify by a rounding before the kept class in front of it does.
+template <bool POSITIVE>
+__device__ __forceinline__ int sample_cdf(const float (&p)[4], float uniform, int lane, int fallback) {
   const float lsum = (p[0] + p[1]) + (p[2] + p[3]);
   // inclusive scan of the lane totals in class order: four DPP row shifts inside each row of 16
   // lanes (zeros shifted in), then the totals of the rows below as scalars (six __shfl_up steps
@@ -574,7 +579,7 @@ __device__ __forceinline__ int sample_cdf(const float (&p)[4], float uniform, in
   const float total = lane_value(incl, 63);
   const float target = uniform * total;
   const float cdf = incl - lsum;
-  int cand = Q - 1;
+  int cand = fallback;
   bool hit = false;
 #pragma unroll
   for (int k = 3; k >= 0; --k) {
@@ -582,7 +587,7 @@ __device__ __forceinline__ int sample_cdf(const float (&p)[4], float uniform, in
     const float c_k = cdf + (k == 0 ? p[0] : k == 1 ? p[0] + p[1]
                                             : k == 2 ? (p[0] + p[1]) + p[2]
                                                      : ((p[0] + p[1]) + p[2]) + p[3]);
-    if (c_k > target) {
+    if (c_k > target && (!POSITIVE || p[k] > 0.f)) {
       cand = 4 * lane + k;
       hit = true;
     }
@@ -590,15 +595,67 @@ __device__ __forceinline__ int sample_cdf(const float (&p)[4], float uniform, in
   // the smallest qualifying class over the wave = the candidate of the FIRST lane that has one
   // (classes ascend with the lane): one ballot and one readlane instead of a min-reduction
   const unsigned long long lanes = __builtin_amdgcn_ballot_w64(hit);
-  return lanes ? __builtin_amdgcn_readlane(cand, __builtin_ctzll(lanes)) : Q - 1;
+  return lanes ? __builtin_amdgcn_readlane(cand, __builtin_ctzll(lanes)) : fallback;
+}
+
+// Top-k / top-p truncation of a sampled step (include/movenet_hip.h, mvn_generate_trunc), wave 0: lane i holds the
+// weights p >= 0 of classes 4i .. 4i+3.  Non-negative floats order like their bit patterns, so both thresholds are
+// found EXACTLY, without a sort, by a radix select on the pattern, most significant bit first (31 rounds each; the
+// sign bit is clear): a candidate bit stays set when the classes at or above the candidate still
+//   top-k:  number >= top_k          (one ballot + popcount per register: scalar, no cross-lane move)
+//   top-p:  hold >= top_p * S        (one wave_sum_dpp; S = what top-k kept, summed the same way)
+// Both predicates only shrink as the candidate grows -- the fp32 sum too: every addition of non-negative terms is
+// monotone in each of them -- so the greedy bit walk ends on the largest threshold that satisfies them: the top_k-th
+// largest weight, and the largest weight value whose head of the distribution reaches top_p * S.  Classes below
+// max(theta_k, theta_p), and the padding of a smaller model (>= Q), are zeroed in p.  Returns the highest-indexed
+// kept class, the draw's fallback.  The largest weight is never dropped: no candidate above it is ever accepted.
+__device__ __forceinline__ int truncate_weights(float (&p)[4], int top_k, float top_p, int lane, int Q) {
+  unsigned u[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) u[k] = __float_as_uint(p[k]);
+  unsigned theta = 0;  // wave-uniform throughout
+  if (top_k > 0) {
+#pragma unroll 1
+    for (int bit = 30; bit >= 0; --bit) {
+      const unsigned cand = theta | (1u << bit);  // (> 0: a padding class, weight +0, never counts)
+      int n = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) n += __builtin_popcountll(__builtin_amdgcn_ballot_w64(u[k] >= cand));
+      if (n >= top_k) theta = cand;
+    }
+  }
+  if (top_p < 1.f) {
+    auto mass_from = [&](unsigned lo) {
+      return wave_sum_dpp(((u[0] >= lo ? p[0] : 0.f) + (u[1] >= lo ? p[1] : 0.f)) +
+                          ((u[2] >= lo ? p[2] : 0.f) + (u[3] >= lo ? p[3] : 0.f)));
+    };
+    const float need = top_p * mass_from(theta);
+    unsigned tp = 0;
+#pragma unroll 1
+    for (int bit = 30; bit >= 0; --bit) {
+      const unsigned cand = tp | (1u << bit);
+      if (mass_from(cand > theta ? cand : theta) >= need) tp = cand;
+    }
+    theta = tp > theta ? tp : theta;
+  }
+  int top = -1;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const bool keep = u[k] >= theta && 4 * lane + k < Q;
+    p[k] = keep ? p[k] : 0.f;
+    top = keep ? 4 * lane + k : top;
+  }
+  const unsigned long long lanes = __builtin_amdgcn_ballot_w64(top >= 0);
+  return lanes ? __builtin_amdgcn_readlane(top, 63 - __builtin_clzll(lanes)) : Q - 1;
 }
 
 // `uniform`: philox_uniform(seed, u, b), formed by the caller BEFORE it waits for the step's input (ten
 // Philox rounds of integer multiplies: ~0.15 us that do not depend on the logits).
 // `sampling` (MVN_SAMPLE_*, wave-uniform) is read on sampled steps only: a greedy step leaves through its own
-// branch first, the same code under both rules.
-__device__ __forceinline__ int choose_class(const float (&lg)[4], float temperature, int sampling, float uniform,
-                                            int lane, int Q) {
+// branch first, the same code under both rules.  `top_k` / `top_p` (wave-uniform; 0 / 1: off) likewise: a sampled
+// step with either set truncates its weights, whichever rule formed them, before the same inverse CDF.
+__device__ __forceinline__ int choose_class(const float (&lg)[4], float temperature, int sampling, int top_k,
+                                            float top_p, float uniform, int lane, int Q) {
   if (!(temperature > 0.f)) {
     int pick;
     if (greedy_pick_clear(lg, lane, pick)) return pick;
@@ -641,7 +698,11 @@ __device__ __forceinline__ int choose_class(const float (&lg)[4], float temperat
 #pragma unroll
     for (int k = 0; k < 4; ++k) p[k] = e[k] * rs2;  // the distribution generate() uses
   }
-  return sample_cdf(p, uniform, lane, Q);
+  if (top_k > 0 || top_p < 1.f) {
+    const int top = truncate_weights(p, top_k, top_p, lane, Q);
+    return sample_cdf<true>(p, uniform, lane, top);
+  }
+  return sample_cdf<false>(p, uniform, lane, Q - 1);
 }
 
 // fp32 conv2 of the head: thread (og = tid >> 3, q2 = tid & 7) holds 4 output rows x 32 inputs in w2; the eight
@@ -754,7 +815,7 @@ __device__ __forceinline__ void head_loop(const GenArgs &a, u64 *hand, int NS, i
         // (rows of a.Q logits: the padding of a smaller model is not written; fp16 PIPE takes Q = 256 only)
         if (a.logits_out && u >= a.logits_t0 && 4 * lane < a.Q)
           ((f4 *)(a.logits_out + ((size_t)bq * (a.n_total - a.logits_t0) + (u - a.logits_t0)) * a.Q))[lane] = lv;
-        pick = choose_class(lg, a.temperature, a.sampling, uni, lane, a.Q);
+        pick = choose_class(lg, a.temperature, a.sampling, a.top_k, a.top_p, uni, lane, a.Q);
         if (u >= a.n_given) next_idx = pick;
       }
       idx_prev = idx_cur;

@@ -1,6 +1,6 @@
 """Host side of the ring-buffer generator: owns the packed weights, the
 dilation-queue state and the sample buffer as torch tensors (device memory and
-stream plumbing only) and drives ``mvn_generate_ex`` through the C ABI.
+stream plumbing only) and drives ``mvn_generate_trunc`` through the C ABI.
 
 Replaces the per-sample window loop of /root/reference/movenet/wavenet.py:217-237.
 """
@@ -177,12 +177,17 @@ class RingGenerator:
                  residual_channels: int, skip_channels: int, state_dict: Dict[str, torch.Tensor],
                  batch: int, n_total: int, device, variant: int = N.GEN_AUTO,
                  temperature: float = 0.0, seed: int = 0,
-                 context: Optional[torch.Tensor] = None, sampling: str = "reference"):
+                 context: Optional[torch.Tensor] = None, sampling: str = "reference", top_k: int = 0,
+                 top_p: float = 1.0):
         """``sampling``: what a sampled step (temperature > 0) draws from -- "reference": the reference's
         softmax(softmax(logits) / T), close to uniform whatever the model predicts; "model": the model's own
-        softmax(logits / T).  Greedy decoding (temperature <= 0) is the same under both."""
+        softmax(logits / T).  Greedy decoding (temperature <= 0) is the same under both.
+        ``top_k`` / ``top_p``: truncation of a sampled step before the draw (include/movenet_hip.h,
+        mvn_generate_trunc) -- keep the ``top_k`` likeliest classes (0: off), then the smallest head of them that holds
+        ``top_p`` of their mass (1.0: off); greedy decoding ignores both."""
         self._sampling = N.sampling_rule(sampling)
         self.sampling = sampling
+        self.top_k, self.top_p = N.truncation(top_k, top_p)  # ValueError before anything is allocated
         self.lib = N.lib()
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -283,14 +288,14 @@ class RingGenerator:
     def _run(self, t_begin: int, t_end: int, n_given: int, logits_out=None, choices_out=None,
              logits_t0: int = 0) -> None:
         with torch.cuda.device(self.device):
-            N.check(self.lib.mvn_generate_ex(
+            N.check(self.lib.mvn_generate_trunc(
                 self.dims, self.variant, self.packed.data_ptr(), self.state.data_ptr(),
                 self.samples.data_ptr(), self.batch, self.samples.stride(0), self.n_total, n_given,
                 t_begin, t_end, self.temperature, self.seed,
                 None if logits_out is None else logits_out.data_ptr(),
                 None if choices_out is None else choices_out.data_ptr(),
                 logits_t0, None if self.context_tm is None else self.context_tm.data_ptr(),
-                self._sampling, _stream_ptr(self.device)), "mvn_generate_ex")
+                self._sampling, self.top_k, self.top_p, _stream_ptr(self.device)), "mvn_generate_trunc")
 
     def prime(self, prompt_idx: torch.Tensor) -> None:
         """Load a (B, P) prompt (P >= 1 class indices per sequence) and run the
@@ -496,9 +501,10 @@ class GroupedGenerator:
     def __init__(self, layer_size, stack_size, input_channels, residual_channels, skip_channels,
                  state_dict, batch: int, n_total: int, device, group: int, temperature: float = 0.0,
                  seed: int = 0, context: Optional[torch.Tensor] = None, variant: int = N.GEN_PIPE,
-                 sampling: str = "reference"):
+                 sampling: str = "reference", top_k: int = 0, top_p: float = 1.0):
         N.sampling_rule(sampling)  # ValueError before anything is allocated
         self.sampling = sampling
+        self.top_k, self.top_p = N.truncation(top_k, top_p)  # (the same values for every group)
         self.batch, self.n_total, self.device = int(batch), int(n_total), torch.device(device)
         self.variant = variant
         self.samples = torch.zeros(self.batch, self.n_total, dtype=torch.int32, device=self.device)
@@ -509,7 +515,8 @@ class GroupedGenerator:
                               state_dict, batch=b1 - b0, n_total=n_total, device=device,
                               variant=variant, temperature=temperature,
                               seed=(int(seed) + 0x9E3779B97F4A7C15 * gi) & (2 ** 64 - 1),
-                              context=None if context is None else context[b0:b1], sampling=sampling)
+                              context=None if context is None else context[b0:b1], sampling=sampling,
+                              top_k=self.top_k, top_p=self.top_p)
             g.samples = self.samples[b0:b1]  # a contiguous row block of the shared tensor
             self.groups.append(g)
             self.bounds.append((b0, b1))

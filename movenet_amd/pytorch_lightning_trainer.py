@@ -43,6 +43,8 @@ class Dance2Music(nn.Module):
         self.config = config
         self.model = WaveNet(**asdict(config.model_config))
         self.model.generate_sampling = config.generate_sampling  # (ValueError for an unknown rule)
+        self.model.generate_top_k = config.generate_top_k        # (... a negative k, a p outside (0, 1])
+        self.model.generate_top_p = config.generate_top_p
         self.current_epoch = 0
         self.precision = 32
         self.rank, self.world_size = 0, 1

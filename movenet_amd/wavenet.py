@@ -78,6 +78,7 @@ class WaveNet(nn.Module):
         # (mvn_forward_bf16 / mvn_backward_bf16: audio-only, residual = skip channels = 64)
         self.forward_precision = "fp32"
         self._gen_sampling = "reference"
+        self._gen_top_k, self._gen_top_p = 0, 1.0
 
     # ---- precision of generate() ----------------------------------------
     @property
@@ -111,6 +112,27 @@ class WaveNet(nn.Module):
     def generate_sampling(self, value: str) -> None:
         N.sampling_rule(value)  # ValueError for anything else
         self._gen_sampling = value
+
+    # ---- truncation of a sampled generate() step --------------------------
+    @property
+    def generate_top_k(self) -> int:
+        """0 (default: off) or k: a sampled step draws among the k likeliest classes only (ties at the k-th weight
+        all kept; k >= input_channels is the same as off).  Greedy decoding ignores it."""
+        return getattr(self, "_gen_top_k", 0)  # (a module pickled before the attribute existed)
+
+    @generate_top_k.setter
+    def generate_top_k(self, value: int) -> None:
+        self._gen_top_k = N.truncation(value, 1.0)[0]  # ValueError for anything else
+
+    @property
+    def generate_top_p(self) -> float:
+        """1.0 (default: off) or p in (0, 1): a sampled step draws from the smallest head of the distribution that
+        holds p of its mass (nucleus sampling), applied after ``generate_top_k``.  Greedy decoding ignores it."""
+        return getattr(self, "_gen_top_p", 1.0)
+
+    @generate_top_p.setter
+    def generate_top_p(self, value: float) -> None:
+        self._gen_top_p = N.truncation(0, value)[1]
 
     # ---- shape arithmetic (host only) ---------------------------------
     @property
@@ -238,7 +260,7 @@ class WaveNet(nn.Module):
                              f"n_samples={n_total} asked for")
         kw = dict(batch=idx.shape[0], n_total=n_total, device=audio.device,
                   temperature=float(temperature), seed=seed, context=context,
-                  sampling=self.generate_sampling)
+                  sampling=self.generate_sampling, top_k=self.generate_top_k, top_p=self.generate_top_p)
         def run(variant, group):
             if group:
                 gen = GroupedGenerator(self.layer_size, self.stack_size, self.input_channels,
