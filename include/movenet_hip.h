@@ -486,6 +486,32 @@ int mvn_softmax_ce_backward(const float *probs, const long long *target, int bat
                             long long dlogit_batch_stride, int dlogit_ld, int dlogit_col0,
                             int dlogit_cols, void *stream);
 
+/* The loss the fused pair differentiates.  REFERENCE: the two calls above -- cross_entropy applied to
+ * the model's PROBABILITIES, a second softmax over values in [0, 1], so the loss of a column lies in
+ * [ln(e + Q - 1) - 1, ln Q].  MODEL: the negative log-likelihood of the model's own softmax(logits),
+ *     loss = mean over (b,s) of  logsumexp_q(logits[b,:,s]) - logits[b,target,s]   (nats),
+ *     dlogit_q = scale * upstream * (p_q - [q == target]),
+ * formed from the max and the exp-sum the softmax takes anyway: one exponential pass forward, none
+ * backward. */
+#define MVN_LOSS_REFERENCE 0
+#define MVN_LOSS_MODEL 1
+
+/* mvn_softmax_ce_forward / _backward with the loss rule chosen: `loss_rule` is MVN_LOSS_REFERENCE (what
+ * the two calls above pass) or MVN_LOSS_MODEL; any other value is MVN_ERR_BAD_ARG, before any launch and
+ * before any buffer is touched.  The rule changes the loss and its gradient only: the probabilities
+ * written in place are the same bits under both, and so are the accuracy counts (first maximum of the
+ * probabilities, target clamped to [0, Q-1]); slots, their zero-initialisation contract and the dlogit
+ * window (columns [col0, col0 + s_len) written, [col0 + s_len, col0 + cols) zeroed, nothing outside) are
+ * those of the calls above.  Under MODEL the target's logit is read before the column is overwritten,
+ * and the backward reads no logits: only the probabilities and the target. */
+int mvn_softmax_ce_forward_ex(float *logits_probs, const long long *target, int batch, int classes,
+                              int s_len, float *loss_part, int32_t *correct_part, int loss_rule,
+                              void *stream);
+int mvn_softmax_ce_backward_ex(const float *probs, const long long *target, int batch, int classes,
+                               int s_len, float scale, const float *upstream, float *dlogit,
+                               long long dlogit_batch_stride, int dlogit_ld, int dlogit_col0,
+                               int dlogit_cols, int loss_rule, void *stream);
+
 /* One optimizer step of torch.optim.AdamW (decoupled != 0) or torch.optim.Adam (decoupled == 0,
  * weight decay added to the gradient) over flat fp32 buffers of n elements
  * (movenet/pytorch_lightning_trainer.py:186-189; arithmetic of torch's _single_tensor_adam,

@@ -27,6 +27,8 @@ BWD_FORM_GENERIC, BWD_FORM_HALVES, BWD_FORM_ONE = 1, 2, 3  # mvn_last_backward_f
 BWD_FORM_BF16 = 4  # mvn_backward_bf16's layer kernel
 SAMPLE_REFERENCE, SAMPLE_MODEL = 0, 1  # mvn_generate_ex's rule of a sampled step (include/movenet_hip.h)
 SAMPLING_RULES = {"reference": SAMPLE_REFERENCE, "model": SAMPLE_MODEL}
+LOSS_REFERENCE, LOSS_MODEL = 0, 1  # mvn_softmax_ce_*_ex's loss rule (include/movenet_hip.h)
+LOSS_RULES = {"reference": LOSS_REFERENCE, "model": LOSS_MODEL}
 PIPE_VARIANTS = (GEN_PIPE, GEN_PIPE_F16, GEN_FOLD)  # variants with a hand-off status word
 
 
@@ -160,6 +162,11 @@ SIGNATURES = {
     "mvn_softmax_ce_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
                                           C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p]),
+    "mvn_softmax_ce_forward_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.c_void_p]),
+    "mvn_softmax_ce_backward_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                             C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_void_p]),
     "mvn_adamw_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float,
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
                                  C.POINTER(C.c_size_t), C.c_int, C.c_void_p]),
@@ -226,6 +233,13 @@ def sampling_rule(value) -> int:
     if not isinstance(value, str) or value not in SAMPLING_RULES:
         raise ValueError(f"sampling must be 'reference' or 'model', got {value!r}")
     return SAMPLING_RULES[value]
+
+
+def loss_rule(value) -> int:
+    """"reference" / "model" -> MVN_LOSS_*; ValueError for anything else."""
+    if not isinstance(value, str) or value not in LOSS_RULES:
+        raise ValueError(f"loss_rule must be 'reference' or 'model', got {value!r}")
+    return LOSS_RULES[value]
 
 
 def truncation(top_k, top_p):

@@ -59,6 +59,11 @@ class TrainingConfig:
     generate_top_k: int = 0
     generate_top_p: float = 1.0
 
+    # what the train step minimises (WaveNet.loss_rule): "reference", the reference's cross_entropy applied to the
+    # model's probabilities, or "model", cross_entropy of the logits (the negative log-likelihood of the distribution
+    # --generate_sampling model draws from).  Not a reference field: a JSON written without it loads with the default.
+    loss_rule: str = "reference"
+
     scheduler: Optional[str] = "OneCycleLR"
     lr_pct_start: float = 0.45
     base_learning_rate: float = 0.0003
@@ -140,6 +145,7 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--generate_sampling", type=str, default="reference", choices=["reference", "model"])
     a("--generate_top_k", type=int, default=0)
     a("--generate_top_p", type=float, default=1.0)
+    a("--loss_rule", type=str, default="reference", choices=["reference", "model"])
     a("--n_epochs", type=int, default=10)
     a("--n_steps_per_epoch", type=int, default=None)
     a("--use_video", type=_flag, default=True)
@@ -182,7 +188,7 @@ def config_from_args(args) -> TrainingConfig:
         "lr_pct_start base_learning_rate scheduler_step_size_up scheduler_step_size_down "
         "scheduler_cyclic_mode scheduler_cyclic_gamma scheduler_cycle_momentum max_learning_rate "
         "scheduler_step_size scheduler_step_gamma scheduler_milestones weight_decay "
-        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p accumulation_steps num_workers val_num_workers "
+        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p loss_rule accumulation_steps num_workers val_num_workers "
         "pin_memory n_epochs n_steps_per_epoch use_video batch_subsample_frac "
         "val_batch_subsample_frac dist_backend dist_port model_output_path log_samples_every"
     ).split()

@@ -8,6 +8,9 @@
 //                            straight into mvn_backward's padded dlogit tensor: the gradient
 //                            of the loss through cross_entropy's own log-softmax and through
 //                            the model's softmax in one read and one write
+//   mvn_softmax_ce_*_ex      the same pair with the loss rule chosen: MVN_LOSS_MODEL is the negative log-likelihood
+//                            of softmax(logits) itself -- same probabilities, one exponential pass forward, a
+//                            streaming p - onehot backward (ce_model_bwd_kernel)
 //   mvn_adamw_step           torch.optim.AdamW / Adam over ONE flat parameter / gradient /
 //                            moment buffer (pytorch_lightning_trainer.py:186-189)
 //
@@ -31,10 +34,13 @@ __device__ __forceinline__ float t_col_reduce(float v, float (*part)[64], int wa
 // 64 columns per workgroup, wave w holds class rows [64w, 64w+64) of them, lane = column (r4c: raw-buffer column accesses and
 // ONE division per column -- common.h col_ld / sm_exp -- 4100 -> ~1900 vector instructions per wave, four waves per SIMD
 // instead of two)
-__global__ __launch_bounds__(256) void softmax_ce_fwd_cols_kernel(float *__restrict__ y,
-                                                                  const long long *__restrict__ target,
-                                                                  int Q, int S, float *__restrict__ loss_part,
-                                                                  int32_t *__restrict__ correct_part) {
+// MODEL (MVN_LOSS_MODEL): the loss is the column's own -log p_target = (m + log sum) - l_target, from the max and the
+// exp-sum above: the target's logit is picked up as the column is loaded, and the second log-softmax (64 exponentials
+// and two reductions per thread) is not formed.  Probabilities and accuracy: the same instructions under both rules.
+template <bool MODEL>
+__device__ __forceinline__ void softmax_ce_fwd_cols(float *__restrict__ y, const long long *__restrict__ target, int Q,
+                                                    int S, float *__restrict__ loss_part,
+                                                    int32_t *__restrict__ correct_part) {
   __shared__ float part[4][64];
   __shared__ int argp[4][64];
   const int lane = threadIdx.x & 63, b = blockIdx.y;
@@ -43,13 +49,16 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_cols_kernel(float *__restr
   const bool live = s < S;
   const __amdgpu_buffer_rsrc_t yb = col_rsrc(y + (size_t)b * Q * S);
   const int voff = 4 * (live ? s : 0), row = 4 * S;
+  const long long tg = live ? target[(size_t)b * S + s] : 0;
+  const int tq = (int)min(max(tg, 0LL), (long long)(Q - 1));
   float v[TQ];
-  float m = -INFINITY;
+  float m = -INFINITY, pt = 0.f;  // pt: the target's probability (REFERENCE) or its raw logit (MODEL)
 #pragma unroll
   for (int i = 0; i < TQ; ++i) {
     const int q = TQ * wave + i;
     v[i] = q < Q ? col_ld(yb, voff, q * row) : -INFINITY;
     v[i] = live ? v[i] : -INFINITY;
+    if (MODEL && q == tq) pt = v[i];
     m = fmaxf(m, v[i]);
   }
   m = t_col_reduce(m, part, wave, lane, true);
@@ -61,10 +70,8 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_cols_kernel(float *__restr
   }
   sum = t_col_reduce(sum, part, wave, lane, false);
   const float inv = 1.0f / sum;
-  // probabilities (wavenet.py:189-191), then cross_entropy ON them: a second log-softmax
-  const long long tg = live ? target[(size_t)b * S + s] : 0;
-  const int tq = (int)min(max(tg, 0LL), (long long)(Q - 1));
-  float m2 = -INFINITY, pt = 0.f;
+  // probabilities (wavenet.py:189-191), then (REFERENCE) cross_entropy ON them: a second log-softmax
+  float m2 = -INFINITY;
   int arg = 0;
 #pragma unroll
   for (int i = 0; i < TQ; ++i) {
@@ -76,7 +83,7 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_cols_kernel(float *__restr
         m2 = v[i];
         arg = q;
       }
-      if (q == tq) pt = v[i];
+      if (!MODEL && q == tq) pt = v[i];
     } else {
       v[i] = -INFINITY;
     }
@@ -84,16 +91,18 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_cols_kernel(float *__restr
   const float wave_m2 = m2;
   m2 = t_col_reduce(m2, part, wave, lane, true);
   float sum2 = 0.f;
+  if (!MODEL) {
 #pragma unroll
-  for (int i = 0; i < TQ; ++i) sum2 += sm_exp(v[i] - m2);
-  sum2 = t_col_reduce(sum2, part, wave, lane, false);
+    for (int i = 0; i < TQ; ++i) sum2 += sm_exp(v[i] - m2);
+    sum2 = t_col_reduce(sum2, part, wave, lane, false);
+  }
   argp[wave][lane] = wave_m2 == m2 ? arg : 0x7fffffff;
   const float pt_all = t_col_reduce(pt, part, wave, lane, false);  // one wave holds it, the others 0
   float loss = 0.f;
   int ok = 0;
   if (wave == 0 && live) {
     const int a0 = min(min(argp[0][lane], argp[1][lane]), min(argp[2][lane], argp[3][lane]));
-    loss = (m2 + logf(sum2)) - pt_all;
+    loss = MODEL ? (m + logf(sum)) - pt_all : (m2 + logf(sum2)) - pt_all;
     ok = a0 == tq;
   }
   if (wave == 0) {
@@ -105,6 +114,21 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_cols_kernel(float *__restr
       correct_part[wg] = (int)okf;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void softmax_ce_fwd_cols_kernel(float *__restrict__ y,
+                                                                  const long long *__restrict__ target,
+                                                                  int Q, int S, float *__restrict__ loss_part,
+                                                                  int32_t *__restrict__ correct_part) {
+  softmax_ce_fwd_cols<false>(y, target, Q, S, loss_part, correct_part);
+}
+
+// (with fewer uses of the column to order its work by, the compiler kept loads and exponentials of the whole column
+// live at once: 183 registers, two waves per SIMD; held to the four of the reference form)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void softmax_ce_model_fwd_cols_kernel(
+    float *__restrict__ y, const long long *__restrict__ target, int Q, int S, float *__restrict__ loss_part,
+    int32_t *__restrict__ correct_part) {
+  softmax_ce_fwd_cols<true>(y, target, Q, S, loss_part, correct_part);
 }
 
 // (r4c: the column's probabilities are the only array a thread keeps -- the exponentials are formed twice, the second time
@@ -174,6 +198,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 }
 
 // any Q: one thread per column, the column walked several times (slow path)
+template <bool MODEL>
 __global__ __launch_bounds__(256) void softmax_ce_fwd_kernel(float *__restrict__ y,
                                                              const long long *__restrict__ target, int Q, int S,
                                                              float *__restrict__ loss_part,
@@ -183,6 +208,9 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_kernel(float *__restrict__
   int ok = 0;
   if (s < S) {
     float *col = y + (size_t)b * Q * S + s;
+    const long long tg = target[(size_t)b * S + s];
+    const int tq = (int)min(max(tg, 0LL), (long long)(Q - 1));
+    const float lt = MODEL ? col[(size_t)tq * S] : 0.f;  // the target's logit, before the column is overwritten
     float m = -INFINITY;
     for (int q = 0; q < Q; ++q) m = fmaxf(m, col[(size_t)q * S]);
     float sum = 0.f;
@@ -202,11 +230,13 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_kernel(float *__restrict__
         arg = q;
       }
     }
-    float sum2 = 0.f;
-    for (int q = 0; q < Q; ++q) sum2 += sm_exp(col[(size_t)q * S] - m2);
-    const long long tg = target[(size_t)b * S + s];
-    const int tq = (int)min(max(tg, 0LL), (long long)(Q - 1));
-    loss = (m2 + logf(sum2)) - col[(size_t)tq * S];
+    if (MODEL) {
+      loss = (m + logf(sum)) - lt;
+    } else {
+      float sum2 = 0.f;
+      for (int q = 0; q < Q; ++q) sum2 += sm_exp(col[(size_t)q * S] - m2);
+      loss = (m2 + logf(sum2)) - col[(size_t)tq * S];
+    }
     ok = arg == tq;
   }
   __shared__ float ls[4];
@@ -257,6 +287,62 @@ __global__ __launch_bounds__(256) void softmax_ce_bwd_kernel(const float *__rest
   }
 }
 
+// MODEL rule (MVN_LOSS_MODEL): dlogit = scale upstream (p - onehot(target)) -- no exponential, no sum over the column, so
+// nothing of the column forms above is kept (no 64-register column, no LDS): a streaming kernel, one read of the
+// probabilities and one write of the window.  A thread owns FOUR consecutive columns of the dlogit tensor, counted
+// from the ROW's start (so that its 16-byte store is aligned whenever the rows are: mvn_backward's (B, Q, Sp) tensor,
+// whatever dlogit_col0), and walks MB_ROWS class rows with them: the four targets are read once per thread, each row
+// is one 16-byte load and one 16-byte store.  The probabilities' four columns sit dlogit_col0 elements off that grid:
+// their type carries the 4-byte alignment they have, and so does the store's (gfx950 serves either with one
+// instruction).  64-bit addresses throughout: any Q, any row length -- the one kernel serves the shapes of both
+// column forms.  Groups that straddle an edge of the window take the element-wise tail below.
+typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
+constexpr int MB_ROWS = 16;
+
+__global__ __launch_bounds__(256) void ce_model_bwd_kernel(const float *__restrict__ p,
+                                                           const long long *__restrict__ target, int Q, int S,
+                                                           float scale, const float *__restrict__ upstream,
+                                                           float *__restrict__ dlogit, long long d_sb, int d_ld,
+                                                           int col0, int s_cols) {
+  const int b = blockIdx.z, q0 = blockIdx.y * MB_ROWS;
+  // first column of the thread's group in the dlogit row, and the window position it maps to (may be negative)
+  const long long a0 = 4LL * ((long long)(col0 >> 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x);
+  const long long s0 = a0 - col0;
+  if (s0 >= s_cols || s0 + 3 < 0) return;
+  if (upstream) scale *= *upstream;
+  const bool whole = s0 >= 0 && s0 + 3 < S;  // the whole group inside [0, S)
+  const long long *trow = target + ((long long)b * S + s0);
+  int tq[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const long long tg = (whole || (s0 + e >= 0 && s0 + e < S)) ? trow[e] : 0;
+    tq[e] = (int)min(max(tg, 0LL), (long long)(Q - 1));
+  }
+  const float *prow = p + ((long long)b * Q * S + s0);  // (dereferenced only where 0 <= s < S)
+  float *drow = dlogit + ((long long)b * d_sb + a0);
+  const int q1 = min(Q, q0 + MB_ROWS);
+  if (whole) {  // one load, one store per row
+#pragma unroll 4
+    for (int q = q0; q < q1; ++q) {
+      const f4u pv = *(const f4u *)(prow + (size_t)q * S);
+      f4u g;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) g[e] = scale * (pv[e] - (q == tq[e] ? 1.0f : 0.0f));
+      *(f4u *)(drow + (size_t)q * d_ld) = g;
+    }
+    return;
+  }
+  for (int q = q0; q < q1; ++q) {  // an edge of the window: element by element; [S, s_cols) is zeroed
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const long long s = s0 + e;
+      if (s < 0 || s >= s_cols) continue;
+      const float g = s < S ? scale * (prow[(size_t)q * S + e] - (q == tq[e] ? 1.0f : 0.0f)) : 0.f;
+      drow[(size_t)q * d_ld + e] = g;
+    }
+  }
+}
+
 // ---- AdamW / Adam over a flat buffer ------------------------------------------------------
 // torch.optim.AdamW's arithmetic (its _single_tensor_adam, no amsgrad, no maximize):
 //   p *= 1 - lr wd  (decoupled)  |  g += wd p  (Adam's L2 form)
@@ -301,33 +387,59 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float *__restrict__ p, 
 
 extern "C" {
 
-int mvn_softmax_ce_forward(float *logits_probs, const long long *target, int batch, int classes, int s_len,
-                           float *loss_part, int32_t *correct_part, void *stream) {
+// (the plain entry points and their _ex forms share these: `what` is the name the caller's error text carries)
+static int softmax_ce_forward_impl(const char *what, float *logits_probs, const long long *target, int batch,
+                                   int classes, int s_len, float *loss_part, int32_t *correct_part, int loss_rule,
+                                   void *stream) {
   if (!logits_probs || !target || !loss_part || !correct_part || batch < 0 || classes < 2 || s_len < 0) {
-    mvn::set_error("mvn_softmax_ce_forward: bad argument");
+    mvn::set_error("%s: bad argument", what);
+    return MVN_ERR_BAD_ARG;
+  }
+  if (loss_rule != MVN_LOSS_REFERENCE && loss_rule != MVN_LOSS_MODEL) {
+    mvn::set_error("%s: bad argument (loss_rule %d is neither MVN_LOSS_REFERENCE nor MVN_LOSS_MODEL)", what, loss_rule);
     return MVN_ERR_BAD_ARG;
   }
   if (batch == 0 || s_len == 0) return MVN_OK;
+  const bool model = loss_rule == MVN_LOSS_MODEL;
   // (the column form addresses a sequence's (Q, S) tensor with 32-bit offsets: common.h rows_fit_rsrc)
-  if (classes <= 4 * mvn::TQ && mvn::rows_fit_rsrc(classes, s_len))
-    hipLaunchKernelGGL(mvn::softmax_ce_fwd_cols_kernel, dim3((s_len + 63) / 64, batch), dim3(256), 0,
-                       (hipStream_t)stream, logits_probs, target, classes, s_len, loss_part, correct_part);
-  else
-    hipLaunchKernelGGL(mvn::softmax_ce_fwd_kernel, dim3((s_len + 255) / 256, batch), dim3(256), 0,
-                       (hipStream_t)stream, logits_probs, target, classes, s_len, loss_part, correct_part);
-  return mvn::check_hip(hipGetLastError(), "mvn_softmax_ce_forward");
+  if (classes <= 4 * mvn::TQ && mvn::rows_fit_rsrc(classes, s_len)) {
+    const auto kernel = model ? mvn::softmax_ce_model_fwd_cols_kernel : mvn::softmax_ce_fwd_cols_kernel;
+    hipLaunchKernelGGL(kernel, dim3((s_len + 63) / 64, batch), dim3(256), 0, (hipStream_t)stream, logits_probs,
+                       target, classes, s_len, loss_part, correct_part);
+  } else {
+    const auto kernel = model ? mvn::softmax_ce_fwd_kernel<true> : mvn::softmax_ce_fwd_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((s_len + 255) / 256, batch), dim3(256), 0, (hipStream_t)stream, logits_probs,
+                       target, classes, s_len, loss_part, correct_part);
+  }
+  return mvn::check_hip(hipGetLastError(), what);
 }
 
-int mvn_softmax_ce_backward(const float *probs, const long long *target, int batch, int classes, int s_len,
-                            float scale, const float *upstream, float *dlogit, long long dlogit_batch_stride,
-                            int dlogit_ld, int dlogit_col0, int dlogit_cols, void *stream) {
+static int softmax_ce_backward_impl(const char *what, const float *probs, const long long *target, int batch,
+                                    int classes, int s_len, float scale, const float *upstream, float *dlogit,
+                                    long long dlogit_batch_stride, int dlogit_ld, int dlogit_col0, int dlogit_cols,
+                                    int loss_rule, void *stream) {
   if (!probs || !target || !dlogit || batch < 0 || classes < 2 || s_len < 0 || dlogit_cols < s_len ||
       dlogit_col0 < 0 || dlogit_ld < dlogit_col0 + dlogit_cols) {
-    mvn::set_error("mvn_softmax_ce_backward: bad argument");
+    mvn::set_error("%s: bad argument", what);
+    return MVN_ERR_BAD_ARG;
+  }
+  if (loss_rule != MVN_LOSS_REFERENCE && loss_rule != MVN_LOSS_MODEL) {
+    mvn::set_error("%s: bad argument (loss_rule %d is neither MVN_LOSS_REFERENCE nor MVN_LOSS_MODEL)", what, loss_rule);
     return MVN_ERR_BAD_ARG;
   }
   if (batch == 0 || dlogit_cols == 0) return MVN_OK;
-  if (classes <= 4 * mvn::TQ && mvn::rows_fit_rsrc(classes, s_len) && mvn::rows_fit_rsrc(classes, dlogit_ld))
+  if (loss_rule == MVN_LOSS_MODEL) {
+    // groups of four dlogit columns from the row's start: those that overlap the window [col0, col0 + cols)
+    const long long groups = ((long long)dlogit_col0 + dlogit_cols + 3) / 4 - dlogit_col0 / 4;
+    const long long rows = (classes + mvn::MB_ROWS - 1) / mvn::MB_ROWS;
+    if (rows > 65535 || batch > 65535) {
+      mvn::set_error("%s: more than 65535 x %d classes or 65535 sequences", what, mvn::MB_ROWS);
+      return MVN_ERR_BAD_ARG;
+    }
+    hipLaunchKernelGGL(mvn::ce_model_bwd_kernel, dim3((unsigned)((groups + 255) / 256), (unsigned)rows, batch),
+                       dim3(256), 0, (hipStream_t)stream, probs, target, classes, s_len, scale, upstream, dlogit,
+                       dlogit_batch_stride, dlogit_ld, dlogit_col0, dlogit_cols);
+  } else if (classes <= 4 * mvn::TQ && mvn::rows_fit_rsrc(classes, s_len) && mvn::rows_fit_rsrc(classes, dlogit_ld))
     hipLaunchKernelGGL(mvn::softmax_ce_bwd_cols_kernel, dim3((dlogit_cols + 63) / 64, batch), dim3(256), 0,
                        (hipStream_t)stream, probs, target, classes, s_len, scale, upstream, dlogit,
                        dlogit_batch_stride, dlogit_ld, dlogit_col0, dlogit_cols);
@@ -335,7 +447,35 @@ int mvn_softmax_ce_backward(const float *probs, const long long *target, int bat
     hipLaunchKernelGGL(mvn::softmax_ce_bwd_kernel, dim3((dlogit_cols + 255) / 256, batch), dim3(256), 0,
                        (hipStream_t)stream, probs, target, classes, s_len, scale, upstream, dlogit,
                        dlogit_batch_stride, dlogit_ld, dlogit_col0, dlogit_cols);
-  return mvn::check_hip(hipGetLastError(), "mvn_softmax_ce_backward");
+  return mvn::check_hip(hipGetLastError(), what);
+}
+
+int mvn_softmax_ce_forward(float *logits_probs, const long long *target, int batch, int classes, int s_len,
+                           float *loss_part, int32_t *correct_part, void *stream) {
+  return softmax_ce_forward_impl("mvn_softmax_ce_forward", logits_probs, target, batch, classes, s_len, loss_part,
+                                 correct_part, MVN_LOSS_REFERENCE, stream);
+}
+
+int mvn_softmax_ce_forward_ex(float *logits_probs, const long long *target, int batch, int classes, int s_len,
+                              float *loss_part, int32_t *correct_part, int loss_rule, void *stream) {
+  return softmax_ce_forward_impl("mvn_softmax_ce_forward_ex", logits_probs, target, batch, classes, s_len,
+                                 loss_part, correct_part, loss_rule, stream);
+}
+
+int mvn_softmax_ce_backward(const float *probs, const long long *target, int batch, int classes, int s_len,
+                            float scale, const float *upstream, float *dlogit, long long dlogit_batch_stride,
+                            int dlogit_ld, int dlogit_col0, int dlogit_cols, void *stream) {
+  return softmax_ce_backward_impl("mvn_softmax_ce_backward", probs, target, batch, classes, s_len, scale, upstream,
+                                  dlogit, dlogit_batch_stride, dlogit_ld, dlogit_col0, dlogit_cols,
+                                  MVN_LOSS_REFERENCE, stream);
+}
+
+int mvn_softmax_ce_backward_ex(const float *probs, const long long *target, int batch, int classes, int s_len,
+                               float scale, const float *upstream, float *dlogit, long long dlogit_batch_stride,
+                               int dlogit_ld, int dlogit_col0, int dlogit_cols, int loss_rule, void *stream) {
+  return softmax_ce_backward_impl("mvn_softmax_ce_backward_ex", probs, target, batch, classes, s_len, scale,
+                                  upstream, dlogit, dlogit_batch_stride, dlogit_ld, dlogit_col0, dlogit_cols,
+                                  loss_rule, stream);
 }
 
 int mvn_adamw_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n, float lr,

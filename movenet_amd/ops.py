@@ -276,16 +276,18 @@ def _grads_for_autograd(ctx_, grads, dctx, n_fixed, need):
 
 class _WaveNetLossFunction(torch.autograd.Function):
     """Forward + the trainer's loss in one autograd node (row F3): the head's logits become
-    probabilities and the loss / accuracy partial sums in ONE pass (mvn_softmax_ce_forward);
-    backward differentiates loss -> logits in ONE pass (mvn_softmax_ce_backward) straight into
+    probabilities and the loss / accuracy partial sums in ONE pass (mvn_softmax_ce_forward_ex);
+    backward differentiates loss -> logits in ONE pass (mvn_softmax_ce_backward_ex) straight into
     mvn_backward's dlogit buffer.  args: dims, names, idx, target (B,S) int64, ctx, *params;
-    returns (loss, accuracy, probs)."""
+    returns (loss, accuracy, probs).  ``dims._loss_rule`` (N.LOSS_REFERENCE when absent) picks the
+    loss: cross_entropy on the probabilities, or the negative log-likelihood of softmax(logits)."""
     N_FIXED = 5
 
     @staticmethod
     def forward(ctx_, dims, names, idx, target, context, *params):
         lib = N.lib()
         sd = dict(zip(names, params))
+        rule = int(getattr(dims, "_loss_rule", N.LOSS_REFERENCE))
         save = any(ctx_.needs_input_grad[4:]) and bool(getattr(dims, "_grad_mode", True))
         # logits, last column dropped
         out, buf = run_forward(dims, sd, idx, False, True, save, context, bf16=bool(getattr(dims, "_bf16", False)))
@@ -297,15 +299,16 @@ class _WaveNetLossFunction(torch.autograd.Function):
             parts = max(lib.mvn_ce_parts(B, S), 1)
             loss_part = torch.zeros(parts, dtype=torch.float32, device=out.device)
             ok_part = torch.zeros(parts, dtype=torch.int32, device=out.device)
-            N.check(lib.mvn_softmax_ce_forward(out.data_ptr(), tg.data_ptr(), B, Q, S, loss_part.data_ptr(),
-                                               ok_part.data_ptr(), _stream_ptr(out.device)),
-                    "mvn_softmax_ce_forward")
+            N.check(lib.mvn_softmax_ce_forward_ex(out.data_ptr(), tg.data_ptr(), B, Q, S, loss_part.data_ptr(),
+                                                  ok_part.data_ptr(), rule, _stream_ptr(out.device)),
+                    "mvn_softmax_ce_forward_ex")
         n = max(B * S, 1)
         loss = loss_part.sum() / n
         acc = ok_part.sum().to(torch.float32) / n
         ctx_.dims, ctx_.names, ctx_.idx, ctx_.buf = dims, names, idx, buf
         ctx_.normalize, ctx_.remove_last, ctx_.saved_fwd = True, True, save
         ctx_.has_context = context is not None
+        ctx_.loss_rule = rule
         ctx_.video_slot = getattr(dims, "_video_slot", None) if context is not None else None
         ctx_.save_for_backward(out, tg, *params)
         ctx_.mark_non_differentiable(acc, out)
@@ -321,10 +324,10 @@ class _WaveNetLossFunction(torch.autograd.Function):
         up = dloss.detach().to(device=probs.device, dtype=torch.float32).reshape(1).contiguous()
 
         def fill(dlogit, Sp, pad):
-            N.check(lib.mvn_softmax_ce_backward(
+            N.check(lib.mvn_softmax_ce_backward_ex(
                 probs.data_ptr(), tg.data_ptr(), B, Q, S, 1.0 / max(B * S, 1), up.data_ptr(),
-                dlogit.data_ptr(), Q * Sp, Sp, pad, S + 1, _stream_ptr(probs.device)),
-                "mvn_softmax_ce_backward")
+                dlogit.data_ptr(), Q * Sp, Sp, pad, S + 1, ctx_.loss_rule, _stream_ptr(probs.device)),
+                "mvn_softmax_ce_backward_ex")
 
         grads, dctx = _run_backward(ctx_, params, None, None, fill)
         return _grads_for_autograd(ctx_, grads, dctx, _WaveNetLossFunction.N_FIXED, ctx_.needs_input_grad)
@@ -402,14 +405,15 @@ def upsample_video(model, video: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def _tagged_dims(dims, f16: bool = False, context=None, bf16: bool = False):
+def _tagged_dims(dims, f16: bool = False, context=None, bf16: bool = False, loss_rule: int = N.LOSS_REFERENCE):
     """A copy of the dims struct carrying what the autograd Functions cannot see from inside
-    ``forward``: whether grad mode was on at the call, and the operand precision."""
+    ``forward``: whether grad mode was on at the call, the operand precision and the loss rule."""
     d = N.make_dims(dims.layer_size, dims.stack_size, dims.input_channels, dims.residual_channels,
                     dims.skip_channels)
     d._grad_mode = torch.is_grad_enabled()
     d._f16 = f16
     d._bf16 = bf16
+    d._loss_rule = loss_rule
     d._video_slot = getattr(context, "_mvn_video_slot", None) if context is not None else None
     return d
 
@@ -459,20 +463,25 @@ def wavenet_forward(model, audio: torch.Tensor, context=None, output_unnormalize
     return out if audio.dtype == torch.float32 else out.to(audio.dtype)
 
 
-def wavenet_forward_loss(model, audio: torch.Tensor, context=None, target=None):
+def wavenet_forward_loss(model, audio: torch.Tensor, context=None, target=None, loss_rule=None):
     """(loss, accuracy, probabilities) of one trainer step in one autograd node:
     ``output = model(audio, video)`` (probabilities, Q1), ``target =
     audio[:, :, RF:].argmax(1)``, ``F.cross_entropy(output, target)`` (on probabilities, Q2) and
     the accuracy -- movenet/pytorch_lightning_trainer.py:62-66 -- with the softmax, the loss and
     the accuracy fused into one pass over the head's logits and their gradients into one pass
-    back.  Same values as ``cross_entropy_on_probs(wavenet_forward(...), target)``."""
+    back.  Same values as ``cross_entropy_on_probs(wavenet_forward(...), target)``.
+
+    ``loss_rule`` ("reference" / "model"; default: ``model.loss_rule``): under "model" the loss is
+    ``F.cross_entropy(logits, target)`` instead -- the mean negative log-likelihood, in nats, of the
+    distribution ``generate_sampling = "model"`` draws from; accuracy and probabilities are the same."""
+    rule = N.loss_rule(getattr(model, "loss_rule", "reference") if loss_rule is None else loss_rule)
     bf16 = bf16_mode(model, context is not None)
     model.compute_output_size(audio)
     rf = model.receptive_fields
     idx, check = model._indices_async(audio)
     names, params = _decoder_params(model, context is not None)
     tg = idx[:, rf:].to(torch.int64) if target is None else target
-    dims = _tagged_dims(model._dims, context=context, bf16=bf16)
+    dims = _tagged_dims(model._dims, context=context, bf16=bf16, loss_rule=rule)
     res = _WaveNetLossFunction.apply(dims, names, idx, tg, context, *params)
     if not model._all_one_hot(check):  # (read after the enqueue: no idle GPU) dense causal conv
         del res  # release the discarded pass (saved activations) before the rerun allocates

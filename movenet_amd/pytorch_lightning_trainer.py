@@ -6,7 +6,8 @@
         --layer_size 2 --stack_size 2 --batch_size 2 --n_epochs 1
 
 Same ``Dance2Music`` / ``train_model`` / CLI surface (:24-267 there): same loss
-(``cross_entropy`` applied to the model's PROBABILITIES), same
+(``cross_entropy`` applied to the model's PROBABILITIES; ``--loss_rule model``
+trains on ``cross_entropy`` of the logits instead), same
 accuracy, same optimizer and scheduler factories and kwargs, schedulers stepped
 per optimizer step.  pytorch_lightning is not available offline, so the loop
 that ``Trainer.fit`` would run is written out in ``Trainer`` below with the
@@ -45,6 +46,7 @@ class Dance2Music(nn.Module):
         self.model.generate_sampling = config.generate_sampling  # (ValueError for an unknown rule)
         self.model.generate_top_k = config.generate_top_k        # (... a negative k, a p outside (0, 1])
         self.model.generate_top_p = config.generate_top_p
+        self.model.loss_rule = getattr(config, "loss_rule", "reference")  # (a config pickled before the field existed)
         self.current_epoch = 0
         self.precision = 32
         self.rank, self.world_size = 0, 1
@@ -89,6 +91,8 @@ class Dance2Music(nn.Module):
         loss, acc, output = self(audio, video if self.config.use_video else None, return_loss=True)
         self.log(f"{prefix}_loss", loss, batch_size=self.config.batch_size)
         self.log(f"{prefix}_acc", acc, batch_size=self.config.batch_size)
+        if self.model.loss_rule == "model":  # the loss is a likelihood in nats: also in bits (a device scalar, no sync)
+            self.log(f"{prefix}_bits_per_sample", loss.detach() / math.log(2.0), batch_size=self.config.batch_size)
         return loss, output, audio, video
 
     def training_step(self, batch, batch_idx):
@@ -345,6 +349,8 @@ class Trainer:
             if val_sum[2] > 0:
                 model.logged_raw["val_loss"] = float(val_sum[0] / val_sum[2])
                 model.logged_raw["val_acc"] = float(val_sum[1] / val_sum[2])
+                if "val_bits_per_sample" in model.logged_raw:
+                    model.logged_raw["val_bits_per_sample"] = model.logged_raw["val_loss"] / math.log(2.0)
             self.val_epoch_means = {k: v for k, v in model.logged.items() if k.startswith("val")}
             if rank == 0:
                 print(json.dumps({"epoch": epoch, "epoch_seconds": epoch_s,

@@ -79,6 +79,7 @@ class WaveNet(nn.Module):
         self.forward_precision = "fp32"
         self._gen_sampling = "reference"
         self._gen_top_k, self._gen_top_p = 0, 1.0
+        self._loss_rule = "reference"
 
     # ---- precision of generate() ----------------------------------------
     @property
@@ -133,6 +134,21 @@ class WaveNet(nn.Module):
     @generate_top_p.setter
     def generate_top_p(self, value: float) -> None:
         self._gen_top_p = N.truncation(0, value)[1]
+
+    # ---- what forward(..., return_loss=True) minimises --------------------
+    @property
+    def loss_rule(self) -> str:
+        """"reference" (default: the reference's loss, cross_entropy applied to the model's PROBABILITIES -- a
+        second softmax over values in [0, 1], confined to [ln Q - 1, ln Q] whatever the model predicts) or "model":
+        cross_entropy of the head's logits, the mean negative log-likelihood (nats) of softmax(logits) -- the
+        distribution ``generate_sampling = "model"`` draws from.  Only ``forward(..., return_loss=True)`` consults
+        it; the probabilities and the accuracy it returns are the same under both."""
+        return getattr(self, "_loss_rule", "reference")  # (a module pickled before the attribute existed)
+
+    @loss_rule.setter
+    def loss_rule(self, value: str) -> None:
+        N.loss_rule(value)  # ValueError for anything else
+        self._loss_rule = value
 
     # ---- shape arithmetic (host only) ---------------------------------
     @property
@@ -223,7 +239,8 @@ class WaveNet(nn.Module):
         reference's ``output = self(audio, video)``, ``target = audio[:, :, RF:].argmax(1)``,
         ``F.cross_entropy(output, target)`` and accuracy (pytorch_lightning_trainer.py:62-66)
         -- as ONE autograd node (ops.wavenet_forward_loss); going through ``forward`` keeps
-        module hooks firing on the fused path."""
+        module hooks firing on the fused path.  ``loss_rule = "model"`` makes that loss
+        ``F.cross_entropy`` of the logits instead (the property's docstring)."""
         from .ops import bf16_mode, wavenet_forward, wavenet_forward_loss  # HIP full-sequence kernels
         bf16_mode(self, video is not None)  # (refused before the video encoder runs)
         context = None if video is None else self.upsample_video(video)
