@@ -212,14 +212,18 @@ int mvn_generate_ex(const mvn_dims *dims, int variant, const float *packed, floa
  * uniform of (seed, time, sequence):
  *  1. top_k = k >= 0.  0: off; k >= Q: the same as off.  theta_k is the k-th largest value of w,
  *     counted with multiplicity over the Q real classes; class q is kept iff w_q >= theta_k.  Exact
- *     ties at the threshold are all kept.
+ *     ties at the threshold are all kept.  "Kept" is a statement about the fp32 weights: where fewer
+ *     than k of them are positive (small T: the others underflowed to +0), theta_k is +0 and every
+ *     class is kept -- those of weight zero without effect, since a class of weight zero is never
+ *     drawn, kept or not (3.).
  *  2. top_p = p in (0, 1].  1.0: off.  Applied after top-k: with S the sum of the weights top-k kept,
  *     theta_p is the largest weight value v for which the sum of the kept weights >= v reaches p * S;
  *     class q is kept iff w_q >= max(theta_k, theta_p).  The largest weight always survives, so the
  *     kept set is never empty.
  *  3. The draw: the smallest class q whose running sum over the truncated weights exceeds
  *     uniform * total_kept.  If rounding lets no class qualify, the highest-indexed kept class --
- *     never a dropped one.
+ *     never a dropped one.  A truncated draw never returns a class whose fp32 weight is zero unless
+ *     it is that fallback.
  *  4. With both off, mvn_generate_ex's behaviour to the bit (the Q - 1 fallback included).  Greedy
  *     steps (temperature <= 0) ignore both knobs.  Truncation applies under either rule: it acts on
  *     whatever weights the step draws from.  logits_out, the state and the network arithmetic never

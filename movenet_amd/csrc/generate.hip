@@ -292,13 +292,16 @@ __global__ __launch_bounds__(1024) void gen_generic_kernel(GenArgs a) {
       if (tid == 0) {
         int choice = 0;
         if (a.temperature > 0.f) {
-          float total = 0.f;
-          for (int q = 0; q < Q; ++q) total += a1[q];
-          const float target = philox_uniform(a.seed, (uint32_t)u, (uint32_t)b) * total;
-          float cdf = 0.f;
+          // in double: an fp32 sum of ~1000 terms rounds the same way term after term (a floor weight of 1e-4
+          // beside a sum of 5 loses 0.2 % of itself each time), and with 1000 band edges inside that drift fewer
+          // than 99.9 % of the draws equalled float64's at Q >= 1000
+          double total = 0.0;
+          for (int q = 0; q < Q; ++q) total += (double)a1[q];
+          const double target = (double)philox_uniform(a.seed, (uint32_t)u, (uint32_t)b) * total;
+          double cdf = 0.0;
           choice = fallback;
           for (int q = 0; q < Q; ++q) {
-            cdf += a1[q];
+            cdf += (double)a1[q];
             if (cdf > target) {
               choice = q;
               break;
