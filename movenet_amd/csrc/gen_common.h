@@ -61,41 +61,28 @@ __device__ __forceinline__ float rs_elem(const float *rw, const float *sw, int C
 // class counts the 256-wide heads of the tuned generators take (padded at pack time: generate_fold.hip)
 inline bool head_q_ok(int q) { return q == 64 || q == 128 || q == 256; }
 
-// ---- PIPE variant (generate_pipe.hip) ------------------------------------
-bool pipe_ok(const mvn_dims *d);
-int pipe_stages(const mvn_dims *d);
-size_t pipe_hand_floats(const mvn_dims *d, int batch);  // hand-off area appended to the state
-int pipe_pipelines(const mvn_dims *d);                   // pipelines that fit co-resident (256 CUs)
-int pipe_max_batch(const mvn_dims *d);                   // ... each serving up to PipeCfg::GMAX sequences in turn
-size_t pipe_weights_floats(const mvn_dims *d);          // packed blob without the context section
-int pipe_pack(const mvn_dims *d, const mvn_params *p, float *packed, hipStream_t s);
-int pipe_pack_ctx(const mvn_dims *d, const mvn_params *p, float *ctx_section, hipStream_t s);
-int pipe_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_floats_total,
-                size_t status_offset_floats, hipStream_t s);
-
-
-// ---- PIPE variant with fp16 operands (generate_pipe_h16.hip), C = K = 128 ----------------
-bool pipe_h16_ok(const mvn_dims *d);
-int pipe_h16_stages(const mvn_dims *d);
-int pipe_h16_pipelines(const mvn_dims *d);  // pipelines co-resident on the chip
-int pipe_h16_max_batch(const mvn_dims *d);  // ... each serving up to h16::GMAX sequences in turn
-size_t pipe_h16_weights_floats(const mvn_dims *d);  // packed blob without the context section
-int pipe_h16_pack(const mvn_dims *d, const mvn_params *p, float *packed, bool has_ctx, hipStream_t s);
-int pipe_h16_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_floats_total,
-                    size_t status_offset_floats, hipStream_t s);
-
-// ---- FOLD variant (generate_fold.hip), C = K = 64: residual 1x1 folded into the next layer
-bool fold_ok(const mvn_dims *d);
-int fold_stages(const mvn_dims *d);
-int fold_pipelines(const mvn_dims *d);  // pipelines co-resident on the chip (one sequence each: the fastest step)
-int fold_pipelines_max(const mvn_dims *d);  // ... plus those the XCDs' left-over CUs form across XCDs (slower hops)
-int fold_max_batch(const mvn_dims *d);  // fold_pipelines_max, each serving up to fold::GMAX sequences in turn
-int fold_launch_pipelines(const mvn_dims *d, int batch);  // pipelines a launch of `batch` sequences runs on
-size_t fold_weights_floats(const mvn_dims *d);  // packed blob without the context section
-size_t fold_hand_floats(const mvn_dims *d, int batch);
-int fold_pack(const mvn_dims *d, const mvn_params *p, float *packed, hipStream_t s);
-int fold_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_floats_total,
-                size_t status_offset_floats, hipStream_t s);
+// ---- one generator kernel as the host sees it ------------------------------------------------
+// Everything generate.hip asks about a variant: it walks one table of these (GENERIC and STREAM defined there, the
+// pipelined three one each in their own file) and knows no variant by name.  A pipelined variant hands activations
+// from stage to stage through one inbox per (sequence, stage) in the state's hand-off area; a one-launch kernel has
+// no stages (`stages` and the three members behind it are NULL) and takes any batch.
+struct GenVariant {
+  int id;            // MVN_GEN_*
+  const char *name;  // in messages
+  bool (*ok)(const mvn_dims *);                            // the dims it takes
+  int (*stages)(const mvn_dims *);                         // per pipeline, as the hand-off area is sized
+  size_t (*inbox_floats)(const mvn_dims *);                // per (sequence, stage): the file's GRAN eight-byte granules
+  int (*max_batch)(const mvn_dims *);                      // sequences one launch holds on 256 CUs
+  int (*launch_pipelines)(const mvn_dims *, int batch);    // pipelines a launch of `batch` sequences runs on
+  size_t (*weights_floats)(const mvn_dims *);              // packed blob without the context section
+  // `ctx_section`: where the context convs' section goes, NULL for a model without them
+  int (*pack)(const mvn_dims *, const mvn_params *, float *packed, float *ctx_section, hipStream_t);
+  // `hand`: the hand-off area, `hand_total` floats long, its status word `status_off` floats in (pipelined only)
+  int (*launch)(const GenArgs &, const mvn_dims *, int batch, float *hand, size_t hand_total, size_t status_off,
+                hipStream_t);
+  const char *needs;  // the "does not fit" message: a format with at most one %d, the batch limit for the dims
+};
+extern const GenVariant PIPE_VARIANT, PIPE_F16_VARIANT, FOLD_VARIANT;
 
 // ---- shared by the three pipelined variants (defined in generate_pipe.hip) ---------------
 // One launch of a pipelined generator kernel (GenArgs, u64 *hand, unsigned *err, int NS, int nb, int nseq):
@@ -115,10 +102,7 @@ int pipe_launch_common(const PipeLaunch &p, const GenArgs &a, float *hand, size_
                        size_t status_offset_floats, hipStream_t s);
 // embedding tables [tap 2][256][C] of a packed blob, C = 64 or 128; classes >= qm (the model's count) are zero
 void pack_embed(int C, const float *causal_w, float *dst, int qm, hipStream_t s);
-
-// Hand-off area of the generator state, shared by the pipelined variants: [granules: the
-// largest variant's count][16 flag words, the sticky status word first][placement words]
-size_t hand_status_offset(const mvn_dims *d, int batch);  // floats from the area's start
-size_t hand_total_floats(const mvn_dims *d, int batch);
+// context section of PIPE and FOLD (one per-layer layout, C = 64 or 128)
+int pipe_pack_ctx(const mvn_dims *d, const mvn_params *p, float *ctx_section, hipStream_t s);
 
 }  // namespace mvn

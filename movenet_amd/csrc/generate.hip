@@ -775,31 +775,12 @@ static size_t generic_lds_bytes(const mvn_dims *d) {
   return sizeof(float) * ((size_t)2 * C + (size_t)L * C + partsz + C + 2 * K + 2 * Q + 16 + 4 + C);
 }
 
-size_t hand_status_offset(const mvn_dims *d, int batch) {
-  size_t g = 0;
-  if (pipe_ok(d)) g = std::max(g, (size_t)batch * pipe_stages(d) * 4 * d->residual_channels);
-  if (pipe_h16_ok(d)) g = std::max(g, (size_t)batch * pipe_h16_stages(d) * 4 * d->residual_channels);
-  if (fold_ok(d)) g = std::max(g, (size_t)batch * fold_stages(d) * 6 * d->residual_channels);
-  return g;
-}
-size_t hand_total_floats(const mvn_dims *d, int batch) {
-  size_t ns = 0;
-  if (pipe_ok(d)) ns = std::max(ns, (size_t)pipe_stages(d));
-  if (pipe_h16_ok(d)) ns = std::max(ns, (size_t)pipe_h16_stages(d));
-  if (fold_ok(d)) ns = std::max(ns, (size_t)fold_stages(d));
-  if (ns == 0) return 0;
-  return hand_status_offset(d, batch) + (16 + (size_t)batch * ns + 63) / 64 * 64;
-}
-
-// packed blob without the trailing context-conv section
-static size_t gen_base_floats(const mvn_dims *dims, int variant) {
-  const size_t C = dims->residual_channels, K = dims->skip_channels, Q = dims->input_channels;
-  const size_t L = n_layers(dims);
-  if (variant == MVN_GEN_PIPE) return pipe_weights_floats(dims);
-  if (variant == MVN_GEN_PIPE_F16) return pipe_h16_weights_floats(dims);
-  if (variant == MVN_GEN_FOLD) return fold_weights_floats(dims);
-  if (variant == MVN_GEN_STREAM) return s64::EMB_FLOATS + 4 * (L * s64::LAYER_F4 + s64::HEAD_F4);
-  return 2 * Q * C + L * (4 * C * C + C * (C + K) + (C + K)) + K * Q + Q + Q * Q + Q;
+// gen_stream64_kernel's carve-up, term by term (pctx and cvec: conditioned runs only)
+static size_t stream_lds_bytes(int L, bool conditioned) {
+  const size_t E0 = s64::Q * s64::C, E1 = E0, xcat = 128, pfg = 256, zbuf = 64, prs = 256, sk = 64, a1 = 256;
+  const size_t red = 32, ired = 8, pastAll = (size_t)L * 64;
+  const size_t pctx = conditioned ? (size_t)L * 128 : 0, cvec = conditioned ? 64 : 0;
+  return sizeof(float) * (E0 + E1 + xcat + pfg + zbuf + prs + sk + a1 + red + ired + pastAll + pctx + cvec);
 }
 
 // generic context section: per layer Wt[k (C)][o (2C): f | g] then bias[2C]
@@ -816,9 +797,134 @@ __global__ void pack_ctx_generic_kernel(const float *wcf, const float *bcf, cons
   }
 }
 
+// ======================================================================
+// the variants as the host sees them (gen_common.h: GenVariant)
+// ======================================================================
+static bool generic_ok(const mvn_dims *d) {
+  return d->residual_channels <= 256 && d->skip_channels <= 256 && d->input_channels <= 1024 &&
+         generic_lds_bytes(d) <= 160 * 1024;
+}
 static bool stream_ok(const mvn_dims *d) {
   return d->residual_channels == 64 && d->skip_channels == 64 && head_q_ok(d->input_channels) &&
          n_layers(d) <= 80;
+}
+static size_t generic_weights_floats(const mvn_dims *d) {
+  const size_t C = d->residual_channels, K = d->skip_channels, Q = d->input_channels, L = n_layers(d);
+  return 2 * Q * C + L * (4 * C * C + C * (C + K) + (C + K)) + K * Q + Q + Q * Q + Q;
+}
+static size_t stream_weights_floats(const mvn_dims *d) {
+  return s64::EMB_FLOATS + 4 * ((size_t)n_layers(d) * s64::LAYER_F4 + s64::HEAD_F4);
+}
+
+// the generic context section (STREAM reads it too)
+static void pack_ctx_generic(const mvn_dims *d, const mvn_params *p, float *ctx_section, hipStream_t stream) {
+  const int C = d->residual_channels, n = 2 * C * C + 2 * C;
+  for (int l = 0; l < n_layers(d); ++l)
+    hipLaunchKernelGGL(pack_ctx_generic_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, p->ctx_filter_w[l],
+                       p->ctx_filter_b[l], p->ctx_gate_w[l], p->ctx_gate_b[l], ctx_section + (size_t)l * n, C);
+}
+static int generic_pack(const mvn_dims *d, const mvn_params *p, float *packed, float *ctx_section,
+                        hipStream_t stream) {
+  if (ctx_section) pack_ctx_generic(d, p, ctx_section, stream);
+  const int C = d->residual_channels, K = d->skip_channels, Q = d->input_channels, L = n_layers(d);
+  const int ne = 2 * Q * C;
+  hipLaunchKernelGGL(pack_embed_kernel, dim3((ne + 255) / 256), dim3(256), 0, stream, p->causal_w, packed, Q, C);
+  float *lw = packed + 2 * (size_t)Q * C;
+  const size_t n = 4 * (size_t)C * C + (size_t)C * (C + K) + (C + K);
+  for (int l = 0; l < L; ++l)
+    hipLaunchKernelGGL(pack_layer_generic_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                       p->filter_w[l], p->gate_w[l], p->residual_w[l], p->residual_b[l], p->skip_w[l], p->skip_b[l],
+                       lw + l * n, C, K);
+  const size_t nh = (size_t)K * Q + Q + (size_t)Q * Q + Q;
+  hipLaunchKernelGGL(pack_head_generic_kernel, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, stream,
+                     p->head1_w, p->head1_b, p->head2_w, p->head2_b, lw + L * n, Q, K);
+  return check_hip(hipGetLastError(), "mvn_gen_pack_weights");
+}
+// (the STREAM layout is 256 classes wide whatever the model's Q: padded)
+static int stream_pack(const mvn_dims *d, const mvn_params *p, float *packed, float *ctx_section,
+                       hipStream_t stream) {
+  if (ctx_section) pack_ctx_generic(d, p, ctx_section, stream);
+  const int Q = d->input_channels, L = n_layers(d);
+  hipLaunchKernelGGL(pack_embed_s64_kernel, dim3((s64::EMB_FLOATS + 255) / 256), dim3(256), 0, stream,
+                     p->causal_w, packed, Q);
+  float *lw = packed + (size_t)s64::EMB_FLOATS;
+  const int n = s64::LAYER_F4 * 4;
+  for (int l = 0; l < L; ++l)
+    hipLaunchKernelGGL(pack_layer_s64_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, p->filter_w[l],
+                       p->gate_w[l], p->residual_w[l], p->residual_b[l], p->skip_w[l], p->skip_b[l],
+                       lw + (size_t)l * n);
+  const int nh = s64::HEAD_F4 * 4;
+  hipLaunchKernelGGL(pack_head_s64_kernel, dim3((nh + 255) / 256), dim3(256), 0, stream, p->head1_w, p->head1_b,
+                     p->head2_w, p->head2_b, lw + (size_t)L * n, Q);
+  return check_hip(hipGetLastError(), "mvn_gen_pack_weights");
+}
+
+static int generic_launch(const GenArgs &a, const mvn_dims *d, int batch, float *, size_t, size_t,
+                          hipStream_t stream) {
+  int rc = ensure_max_dynamic_lds((const void *)gen_generic_kernel, "hipFuncSetAttribute(gen_generic)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(gen_generic_kernel, dim3(batch), dim3(generic_threads(d)), generic_lds_bytes(d), stream, a);
+  return check_hip(hipGetLastError(), "mvn_generate");
+}
+static int stream_launch(const GenArgs &a, const mvn_dims *, int batch, float *, size_t, size_t,
+                         hipStream_t stream) {
+  const size_t lds = stream_lds_bytes(a.L, a.ctx_tm != nullptr);
+  if (lds > 160 * 1024) {
+    set_error("STREAM variant: %d conditioned layers do not fit a CU's LDS", a.L);
+    return MVN_ERR_UNSUPPORTED;
+  }
+  int rc = ensure_max_dynamic_lds((const void *)gen_stream64_kernel, "hipFuncSetAttribute(gen_stream64)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(gen_stream64_kernel, dim3(batch), dim3(256), lds, stream, a);
+  return check_hip(hipGetLastError(), "mvn_generate");
+}
+
+static const GenVariant GENERIC_VARIANT = {
+    MVN_GEN_GENERIC, "GENERIC", generic_ok, nullptr, nullptr, nullptr, nullptr, generic_weights_floats,
+    generic_pack, generic_launch, "GENERIC variant needs C,K<=256, Q<=1024 and <=160 KiB of LDS"};
+static const GenVariant STREAM_VARIANT = {
+    MVN_GEN_STREAM, "STREAM", stream_ok, nullptr, nullptr, nullptr, nullptr, stream_weights_floats,
+    stream_pack, stream_launch, "STREAM variant needs C=K=64, Q in {64,128,256}, <=80 layers"};
+
+static const GenVariant *const VARIANTS[] = {&GENERIC_VARIANT, &STREAM_VARIANT, &PIPE_VARIANT, &PIPE_F16_VARIANT,
+                                             &FOLD_VARIANT};
+// What MVN_GEN_AUTO takes, best first: FOLD where it holds the batch (config 2: 14.6 us per step against PIPE's
+// 16.8; 16 pipelines of up to 8 sequences), PIPE above that (24 pipelines of up to 8; config 5: 4 of up to 16),
+// then the one-launch kernels; PIPE_F16 only on request (fp32 is the default).  DESIGN.md section 4.1
+static const GenVariant *const AUTO_ORDER[] = {&FOLD_VARIANT, &PIPE_VARIANT, &STREAM_VARIANT, &GENERIC_VARIANT};
+
+static const GenVariant *find_variant(int id) {
+  for (const GenVariant *v : VARIANTS)
+    if (v->id == id) return v;
+  return nullptr;
+}
+
+static int device_cus() {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+    return 256;  // no device visible (build box): the MI355X figure
+  return cus;
+}
+// the dims, and for a pipelined variant a batch its co-resident pipelines hold on a whole MI355X
+static bool variant_fits(const GenVariant &v, const mvn_dims *d, int batch) {
+  return v.ok(d) && (!v.stages || (batch >= 1 && device_cus() >= 256 && batch <= v.max_batch(d)));
+}
+
+// Hand-off area of the generator state, shared by the pipelined variants: [granules: the
+// largest variant's count][16 flag words, the sticky status word first][placement words]
+static size_t hand_status_offset(const mvn_dims *d, int batch) {  // floats from the area's start
+  size_t g = 0;
+  for (const GenVariant *v : VARIANTS)
+    if (v->stages && v->ok(d)) g = std::max(g, (size_t)batch * v->stages(d) * v->inbox_floats(d));
+  return g;
+}
+static size_t hand_total_floats(const mvn_dims *d, int batch) {
+  size_t ns = 0;
+  for (const GenVariant *v : VARIANTS)
+    if (v->stages && v->ok(d)) ns = std::max(ns, (size_t)v->stages(d));
+  if (ns == 0) return 0;
+  return hand_status_offset(d, batch) + (16 + (size_t)batch * ns + 63) / 64 * 64;
 }
 
 }  // namespace mvn
@@ -857,91 +963,41 @@ int mvn_transpose_context(const float *ctx, int ctx_ld, int batch, int channels,
   return mvn::check_hip(hipGetLastError(), "mvn_transpose_context");
 }
 
-static int device_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    return 256;  // no device visible (build box): the MI355X figure
-  return cus;
-}
-
 int mvn_gen_launch_pipelines(const mvn_dims *dims, int variant, int batch) {
   int rc = mvn::validate_dims(dims);
   if (rc) return rc;
   if (batch < 1) return 0;
-  if (variant == MVN_GEN_FOLD && mvn::fold_ok(dims)) return mvn::fold_launch_pipelines(dims, batch);
-  if (variant == MVN_GEN_PIPE && mvn::pipe_ok(dims)) return std::min(batch, mvn::pipe_pipelines(dims));
-  if (variant == MVN_GEN_PIPE_F16 && mvn::pipe_h16_ok(dims)) return std::min(batch, mvn::pipe_h16_pipelines(dims));
-  return 0;
+  const mvn::GenVariant *v = mvn::find_variant(variant);
+  return v && v->stages && v->ok(dims) ? v->launch_pipelines(dims, batch) : 0;
 }
 
 int mvn_gen_variant(const mvn_dims *dims, int requested, int batch) {
   int rc = mvn::validate_dims(dims);
   if (rc) return rc;
-  const bool pipe_fits =
-      mvn::pipe_ok(dims) && batch >= 1 && device_cus() >= 256 && batch <= mvn::pipe_max_batch(dims);
-  const bool fold_fits =
-      mvn::fold_ok(dims) && batch >= 1 && device_cus() >= 256 && batch <= mvn::fold_max_batch(dims);
   if (requested == MVN_GEN_AUTO) {
-    // FOLD where it holds the batch (config 2: 14.6 us per step against PIPE's 16.8; 16 pipelines
-    // of up to 8 sequences), PIPE above that (24 pipelines of up to 8; config 5: 4 of up to 16);
-    // DESIGN.md section 4.1
-    if (fold_fits) return MVN_GEN_FOLD;
-    if (pipe_fits) return MVN_GEN_PIPE;
-    return mvn::stream_ok(dims) ? MVN_GEN_STREAM : MVN_GEN_GENERIC;
+    for (const mvn::GenVariant *v : mvn::AUTO_ORDER)
+      if (mvn::variant_fits(*v, dims, batch)) return v->id;
+    return MVN_GEN_GENERIC;  // the fallback even for dims it refuses: the refusal comes when it is asked for by id
   }
-  if (requested == MVN_GEN_PIPE) {
-    if (!pipe_fits) {
-      mvn::set_error("PIPE variant needs C=K in {64,128}, Q in {64,128,256}, 256 CUs and batch <= %d for these "
-                     "dims (stages per sequence: ceil(L/4)+1 at C=64, L+1 at C=128; 32 per XCD)",
-                     mvn::pipe_ok(dims) ? mvn::pipe_max_batch(dims) : 0);
-      return MVN_ERR_UNSUPPORTED;
-    }
-    return MVN_GEN_PIPE;
+  const mvn::GenVariant *v = mvn::find_variant(requested);
+  if (!v) {
+    mvn::set_error("unknown generate variant %d", requested);
+    return MVN_ERR_BAD_ARG;
   }
-  if (requested == MVN_GEN_FOLD) {
-    if (!fold_fits) {
-      mvn::set_error("FOLD variant needs C=K=64, Q in {64,128,256}, 256 CUs and batch <= %d for these dims "
-                     "(ceil(L/3)+1 stages per sequence, 32 per XCD)",
-                     mvn::fold_ok(dims) ? mvn::fold_max_batch(dims) : 0);
-      return MVN_ERR_UNSUPPORTED;
-    }
-    return MVN_GEN_FOLD;
+  if (!mvn::variant_fits(*v, dims, batch)) {
+    // (a format from the table, so the compiler does not check it: `needs` holds at most one %d -- the batch limit;
+    // GENERIC's and STREAM's hold none and ignore the argument.  tests/test_gen_variant_table_host.py pins every text)
+    mvn::set_error(v->needs, v->stages && v->ok(dims) ? v->max_batch(dims) : 0);
+    return MVN_ERR_UNSUPPORTED;
   }
-  if (requested == MVN_GEN_PIPE_F16) {
-    if (!mvn::pipe_h16_ok(dims) || batch < 1 || device_cus() < 256 || batch > mvn::pipe_h16_max_batch(dims)) {
-      mvn::set_error("PIPE_F16 variant needs C=K=128, Q=256, 256 CUs and batch <= %d for these dims "
-                     "(ceil(L/2)+1 stages per sequence, 32 per XCD)",
-                     mvn::pipe_h16_ok(dims) ? mvn::pipe_h16_max_batch(dims) : 0);
-      return MVN_ERR_UNSUPPORTED;
-    }
-    return MVN_GEN_PIPE_F16;
-  }
-  if (requested == MVN_GEN_STREAM) {
-    if (!mvn::stream_ok(dims)) {
-      mvn::set_error("STREAM variant needs C=K=64, Q in {64,128,256}, <=80 layers");
-      return MVN_ERR_UNSUPPORTED;
-    }
-    return MVN_GEN_STREAM;
-  }
-  if (requested == MVN_GEN_GENERIC) {
-    if (dims->residual_channels > 256 || dims->skip_channels > 256 || dims->input_channels > 1024 ||
-        mvn::generic_lds_bytes(dims) > 160 * 1024) {
-      mvn::set_error("GENERIC variant needs C,K<=256, Q<=1024 and <=160 KiB of LDS");
-      return MVN_ERR_UNSUPPORTED;
-    }
-    return MVN_GEN_GENERIC;
-  }
-  mvn::set_error("unknown generate variant %d", requested);
-  return MVN_ERR_BAD_ARG;
+  return v->id;
 }
 
 size_t mvn_gen_weights_floats(const mvn_dims *dims, int variant) {
   variant = mvn_gen_variant(dims, variant, 1);
   if (variant < 0) return 0;
-  const size_t C = dims->residual_channels, K = dims->skip_channels, Q = dims->input_channels;
-  const size_t L = mvn::n_layers(dims);
-  return mvn::gen_base_floats(dims, variant) + L * (2 * C * C + 2 * C);  // + context-conv section
+  const size_t C = dims->residual_channels, L = mvn::n_layers(dims);
+  return mvn::find_variant(variant)->weights_floats(dims) + L * (2 * C * C + 2 * C);  // + context-conv section
 }
 
 size_t mvn_gen_state_floats(const mvn_dims *dims, int batch) {
@@ -972,58 +1028,9 @@ int mvn_gen_pack_weights(const mvn_dims *dims, int variant, const mvn_params *p,
     mvn::set_error("mvn_gen_pack_weights: NULL parameter pointer");
     return MVN_ERR_BAD_ARG;
   }
-  hipStream_t stream = (hipStream_t)stream_;
+  const mvn::GenVariant &v = *mvn::find_variant(variant);
   const bool has_ctx = p->ctx_filter_w && p->ctx_filter_b && p->ctx_gate_w && p->ctx_gate_b;
-  float *ctx_section = packed + mvn::gen_base_floats(dims, variant);
-  if (variant == MVN_GEN_PIPE) {
-    int rc = mvn::pipe_pack(dims, p, packed, stream);
-    if (rc || !has_ctx) return rc;
-    return mvn::pipe_pack_ctx(dims, p, ctx_section, stream);
-  }
-  if (variant == MVN_GEN_PIPE_F16) return mvn::pipe_h16_pack(dims, p, packed, has_ctx, stream);
-  if (variant == MVN_GEN_FOLD) {
-    int rc = mvn::fold_pack(dims, p, packed, stream);
-    if (rc || !has_ctx) return rc;
-    return mvn::pipe_pack_ctx(dims, p, ctx_section, stream);  // same per-layer layout as PIPE
-  }
-  if (has_ctx && (variant == MVN_GEN_GENERIC || variant == MVN_GEN_STREAM)) {  // (STREAM reads the generic section)
-    const int Cc = dims->residual_channels, n = 2 * Cc * Cc + 2 * Cc;
-    for (int l = 0; l < mvn::n_layers(dims); ++l)
-      hipLaunchKernelGGL(mvn::pack_ctx_generic_kernel, dim3((n + 255) / 256), dim3(256), 0, stream,
-                         p->ctx_filter_w[l], p->ctx_filter_b[l], p->ctx_gate_w[l], p->ctx_gate_b[l],
-                         ctx_section + (size_t)l * n, Cc);
-  }
-  const int C = dims->residual_channels, K = dims->skip_channels, Q = dims->input_channels;
-  const int L = mvn::n_layers(dims);
-  if (variant == MVN_GEN_STREAM) {  // (its layout is 256 classes wide whatever the model's Q: padded)
-    hipLaunchKernelGGL(mvn::pack_embed_s64_kernel, dim3((mvn::s64::EMB_FLOATS + 255) / 256), dim3(256), 0, stream,
-                       p->causal_w, packed, Q);
-  } else {
-    const int n = 2 * Q * C;
-    hipLaunchKernelGGL(mvn::pack_embed_kernel, dim3((n + 255) / 256), dim3(256), 0, stream,
-                       p->causal_w, packed, Q, C);
-  }
-  float *lw = packed + (variant == MVN_GEN_STREAM ? (size_t)mvn::s64::EMB_FLOATS : 2 * (size_t)Q * C);
-  if (variant == MVN_GEN_STREAM) {
-    const int n = mvn::s64::LAYER_F4 * 4;
-    for (int l = 0; l < L; ++l)
-      hipLaunchKernelGGL(mvn::pack_layer_s64_kernel, dim3((n + 255) / 256), dim3(256), 0, stream,
-                         p->filter_w[l], p->gate_w[l], p->residual_w[l], p->residual_b[l],
-                         p->skip_w[l], p->skip_b[l], lw + (size_t)l * n);
-    const int nh = mvn::s64::HEAD_F4 * 4;
-    hipLaunchKernelGGL(mvn::pack_head_s64_kernel, dim3((nh + 255) / 256), dim3(256), 0, stream,
-                       p->head1_w, p->head1_b, p->head2_w, p->head2_b, lw + (size_t)L * n, Q);
-  } else {
-    const size_t n = 4 * (size_t)C * C + (size_t)C * (C + K) + (C + K);
-    for (int l = 0; l < L; ++l)
-      hipLaunchKernelGGL(mvn::pack_layer_generic_kernel, dim3((unsigned)((n + 255) / 256)),
-                         dim3(256), 0, stream, p->filter_w[l], p->gate_w[l], p->residual_w[l],
-                         p->residual_b[l], p->skip_w[l], p->skip_b[l], lw + l * n, C, K);
-    const size_t nh = (size_t)K * Q + Q + (size_t)Q * Q + Q;
-    hipLaunchKernelGGL(mvn::pack_head_generic_kernel, dim3((unsigned)((nh + 255) / 256)), dim3(256),
-                       0, stream, p->head1_w, p->head1_b, p->head2_w, p->head2_b, lw + L * n, Q, K);
-  }
-  return mvn::check_hip(hipGetLastError(), "mvn_gen_pack_weights");
+  return v.pack(dims, p, packed, has_ctx ? packed + v.weights_floats(dims) : nullptr, (hipStream_t)stream_);
 }
 
 int mvn_generate(const mvn_dims *dims, int variant, const float *packed, float *state,
@@ -1101,35 +1108,12 @@ int mvn_generate_trunc(const mvn_dims *dims, int variant, const float *packed, f
   a.top_p = top_p;
   a.ctx_tm = context_tm;
   a.ctx_stride_b = (long long)n_total * dims->residual_channels;
-  a.wctx = packed + mvn::gen_base_floats(dims, variant);
-  if (variant == MVN_GEN_PIPE || variant == MVN_GEN_PIPE_F16 || variant == MVN_GEN_FOLD) {
-    float *hand = state + (size_t)batch * a.state_per_seq;
-    const size_t total = mvn::hand_total_floats(dims, batch), soff = mvn::hand_status_offset(dims, batch);
-    if (variant == MVN_GEN_PIPE) return mvn::pipe_launch(a, dims, batch, hand, total, soff, (hipStream_t)stream);
-    if (variant == MVN_GEN_FOLD) return mvn::fold_launch(a, dims, batch, hand, total, soff, (hipStream_t)stream);
-    return mvn::pipe_h16_launch(a, dims, batch, hand, total, soff, (hipStream_t)stream);
-  }
-  if (variant == MVN_GEN_STREAM) {
-    const size_t lds =
-        sizeof(float) * ((size_t)mvn::s64::EMB_FLOATS + 128 + 256 + 64 + 256 + 64 + 256 + 32 + 8 +
-                         (size_t)a.L * 64 + (context_tm ? (size_t)a.L * 128 + 64 : 0));
-    if (lds > 160 * 1024) {
-      mvn::set_error("STREAM variant: %d conditioned layers do not fit a CU's LDS", a.L);
-      return MVN_ERR_UNSUPPORTED;
-    }
-    int rc = mvn::ensure_max_dynamic_lds((const void *)mvn::gen_stream64_kernel,
-                                         "hipFuncSetAttribute(gen_stream64)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(mvn::gen_stream64_kernel, dim3(batch), dim3(256), lds, (hipStream_t)stream, a);
-  } else {
-    const size_t lds = mvn::generic_lds_bytes(dims);
-    int rc = mvn::ensure_max_dynamic_lds((const void *)mvn::gen_generic_kernel,
-                                         "hipFuncSetAttribute(gen_generic)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(mvn::gen_generic_kernel, dim3(batch), dim3(mvn::generic_threads(dims)), lds,
-                       (hipStream_t)stream, a);
-  }
-  return mvn::check_hip(hipGetLastError(), "mvn_generate");
+  const mvn::GenVariant &v = *mvn::find_variant(variant);
+  a.wctx = packed + v.weights_floats(dims);
+  float *hand = state + (size_t)batch * a.state_per_seq;  // (behind the queues; the pipelined variants' only)
+  const size_t total = v.stages ? mvn::hand_total_floats(dims, batch) : 0;
+  const size_t soff = v.stages ? mvn::hand_status_offset(dims, batch) : 0;
+  return v.launch(a, dims, batch, hand, total, soff, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -754,36 +754,34 @@ __global__ void pack_fold_head_kernel(const float *w1, const float *b1, const fl
   }
 }
 
-bool fold_ok(const mvn_dims *d) {
+static int fold_stages(const mvn_dims *d) { return (n_layers(d) + fold::LPS - 1) / fold::LPS + 1; }
+static bool fold_ok(const mvn_dims *d) {
   // (r4: Q in {64, 128, 256} -- the head runs 256 classes wide, a smaller model's are padded at pack time)
   return d->residual_channels == 64 && d->skip_channels == 64 && head_q_ok(d->input_channels) &&
-         n_layers(d) >= 1 && (n_layers(d) + fold::LPS - 1) / fold::LPS + 1 <= PIPE_XCD_CUS;
+         n_layers(d) >= 1 && fold_stages(d) <= PIPE_XCD_CUS;
 }
-int fold_stages(const mvn_dims *d) { return (n_layers(d) + fold::LPS - 1) / fold::LPS + 1; }
-int fold_pipelines(const mvn_dims *d) { return 8 * (PIPE_XCD_CUS / fold_stages(d)); }  // co-resident pipelines
-int fold_pipelines_max(const mvn_dims *d) {  // ... plus the pipelines the XCDs' left-over CUs form across XCDs
+static size_t fold_inbox_floats(const mvn_dims *) { return 2 * fold::GRAN; }
+static int fold_pipelines(const mvn_dims *d) { return 8 * (PIPE_XCD_CUS / fold_stages(d)); }  // co-resident pipelines
+static int fold_pipelines_max(const mvn_dims *d) {  // ... plus the pipelines the XCDs' left-over CUs form across XCDs
   const int NS = fold_stages(d);
   return fold_pipelines(d) + 8 * (PIPE_XCD_CUS - (PIPE_XCD_CUS / NS) * NS) / NS;
 }
-int fold_max_batch(const mvn_dims *d) { return fold::GMAX * fold_pipelines_max(d); }     // GMAX sequences each
+static int fold_max_batch(const mvn_dims *d) { return fold::GMAX * fold_pipelines_max(d); }     // GMAX sequences each
 // Pipelines a launch of `batch` sequences runs on: one sequence each up to fold_pipelines(d) (the fastest step);
 // rounds on those while the pipeline's latency bounds the step (up to FOLD_LATENCY_ROUNDS each); every pipeline
 // the chip holds beyond that, where the step is rounds x the stages' service time per turn
 constexpr int FOLD_LATENCY_ROUNDS = 5;
-int fold_launch_pipelines(const mvn_dims *d, int batch) {
+static int fold_launch_pipelines(const mvn_dims *d, int batch) {
   const int p = fold_pipelines(d);
   if (batch <= p) return batch;
   return batch <= FOLD_LATENCY_ROUNDS * p ? p : fold_pipelines_max(d);
 }
-size_t fold_weights_floats(const mvn_dims *d) {
+static size_t fold_weights_floats(const mvn_dims *d) {
   return (size_t)fold::EMB_F + (size_t)(fold_stages(d) - 1) * fold::STAGE_F + fold::HEAD_F;
 }
-size_t fold_hand_floats(const mvn_dims *d, int batch) {
-  const size_t n = (size_t)batch * fold_stages(d);
-  return n * fold::GRAN * 2 + (16 + n + 63) / 64 * 64;
-}
 
-int fold_pack(const mvn_dims *d, const mvn_params *p, float *packed, hipStream_t s) {
+// (context section: the PIPE variant's per-layer layout -- same thread mapping --, packed by it)
+static int fold_pack(const mvn_dims *d, const mvn_params *p, float *packed, float *ctx_section, hipStream_t s) {
   using namespace fold;
   const int L = n_layers(d), NSL = fold_stages(d) - 1;
   pack_embed(C, p->causal_w, packed, d->input_channels, s);
@@ -810,18 +808,17 @@ int fold_pack(const mvn_dims *d, const mvn_params *p, float *packed, hipStream_t
   hipLaunchKernelGGL(pack_fold_head_kernel, dim3((HEAD_F + 255) / 256), dim3(256), 0, s, p->head1_w, p->head1_b,
                      p->head2_w, p->head2_b, tail_real ? p->skip_w[l_tail] : nullptr,
                      tail_real ? p->skip_b[l_tail] : nullptr, packed + EMB_F + (size_t)NSL * STAGE_F, d->input_channels);
-  return check_hip(hipGetLastError(), "fold_pack");
+  const int rc = check_hip(hipGetLastError(), "fold_pack");
+  return rc || !ctx_section ? rc : pipe_pack_ctx(d, p, ctx_section, s);
 }
 
-// context section: the PIPE variant's per-layer layout (same thread mapping), packed by it
-//
 // Up to fold_pipelines(d) sequences: one sequence per pipeline (gen_fold_kernel<false>).  More:
 // the pipelines serve ceil(batch / pipelines) sequences each in turn (gen_fold_kernel<true>).
-int fold_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_floats_total,
-                size_t status_offset_floats, hipStream_t s) {
+static int fold_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_floats_total,
+                       size_t status_offset_floats, hipStream_t s) {
   using namespace fold;
   PipeLaunch p;
-  p.name = "FOLD";
+  p.name = FOLD_VARIANT.name;
   p.NT = NT;
   p.NS = fold_stages(d);
   p.GRAN = GRAN;
@@ -836,6 +833,14 @@ int fold_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, siz
   p.per_pipe = GMAX;
   return pipe_launch_common(p, a, hand, hand_floats_total, status_offset_floats, s);
 }
+
+#ifndef __HIP_DEVICE_COMPILE__  // (the device pass would emit the constant, host function pointers and all)
+const GenVariant FOLD_VARIANT = {
+    MVN_GEN_FOLD, "FOLD", fold_ok, fold_stages, fold_inbox_floats, fold_max_batch, fold_launch_pipelines,
+    fold_weights_floats, fold_pack, fold_launch,
+    "FOLD variant needs C=K=64, Q in {64,128,256}, 256 CUs and batch <= %d for these dims "
+    "(ceil(L/3)+1 stages per sequence, 32 per XCD)"};
+#endif
 
 }  // namespace mvn
 

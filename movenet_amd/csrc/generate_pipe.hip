@@ -474,24 +474,23 @@ __global__ void pack_ctx_pipe_kernel(const float *wcf, const float *bcf, const f
   dst[i] = (i4 / NF4) ? wcg[(size_t)c * C + k] : wcf[(size_t)c * C + k];
 }
 
-bool pipe_ok(const mvn_dims *d) {
+static bool pipe_ok(const mvn_dims *d) {
   const int c = d->residual_channels;
   return (c == 64 || c == 128) && d->skip_channels == c && head_q_ok(d->input_channels) &&
          n_layers(d) >= 1;
 }
 static int pipe_lps(const mvn_dims *d) { return d->residual_channels == 64 ? 4 : 1; }
-int pipe_stages(const mvn_dims *d) { return (n_layers(d) + pipe_lps(d) - 1) / pipe_lps(d) + 1; }
-int pipe_pipelines(const mvn_dims *d) { return pipe_pipelines_of(pipe_stages(d)); }
-int pipe_max_batch(const mvn_dims *d) {  // each pipeline serves up to GMAX sequences in turn
+static int pipe_stages(const mvn_dims *d) { return (n_layers(d) + pipe_lps(d) - 1) / pipe_lps(d) + 1; }
+static int pipe_pipelines(const mvn_dims *d) { return pipe_pipelines_of(pipe_stages(d)); }  // co-resident (256 CUs)
+static int pipe_max_batch(const mvn_dims *d) {  // each pipeline serves up to GMAX sequences in turn
   return (d->residual_channels == 64 ? PipeCfg<64>::GMAX : PipeCfg<128>::GMAX) * pipe_pipelines(d);
 }
-size_t pipe_hand_floats(const mvn_dims *d, int batch) {
-  // batch * NS inboxes of 2C granules (2 floats each), then 16 flag words (error word
-  // first) and batch * NS placement words, padded to 64 floats
-  const size_t n = (size_t)batch * pipe_stages(d);
-  return n * 2 * d->residual_channels * 2 + (16 + n + 63) / 64 * 64;
+static size_t pipe_inbox_floats(const mvn_dims *d) {
+  return 2 * (d->residual_channels == 64 ? PipeCfg<64>::GRAN : PipeCfg<128>::GRAN);
 }
-size_t pipe_weights_floats(const mvn_dims *d) {
+// up to pipe_pipelines(d) sequences: one per pipeline; more: ceil(batch / pipelines) each, in turn
+static int pipe_launch_pipelines(const mvn_dims *d, int batch) { return std::min(batch, pipe_pipelines(d)); }
+static size_t pipe_weights_floats(const mvn_dims *d) {
   const size_t L = n_layers(d);
   return d->residual_channels == 64 ? PipeCfg<64>::EMB_F + L * PipeCfg<64>::LAYER_F + PipeCfg<64>::HEAD_F
                                     : PipeCfg<128>::EMB_F + L * PipeCfg<128>::LAYER_F + PipeCfg<128>::HEAD_F;
@@ -511,8 +510,9 @@ static int pipe_pack_t(const mvn_dims *d, const mvn_params *p, float *packed, hi
                      packed + P::EMB_F + (size_t)L * P::LAYER_F, d->input_channels);
   return check_hip(hipGetLastError(), "pipe_pack");
 }
-int pipe_pack(const mvn_dims *d, const mvn_params *p, float *packed, hipStream_t s) {
-  return d->residual_channels == 64 ? pipe_pack_t<64>(d, p, packed, s) : pipe_pack_t<128>(d, p, packed, s);
+static int pipe_pack(const mvn_dims *d, const mvn_params *p, float *packed, float *ctx_section, hipStream_t s) {
+  const int rc = d->residual_channels == 64 ? pipe_pack_t<64>(d, p, packed, s) : pipe_pack_t<128>(d, p, packed, s);
+  return rc || !ctx_section ? rc : pipe_pack_ctx(d, p, ctx_section, s);
 }
 
 template <int CC>
@@ -589,14 +589,13 @@ static void pipe_launch_fill(PipeLaunch &p, bool multi) {
   p.GRAN = P::GRAN;
   p.per_pipe = P::GMAX;
 }
-int pipe_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_total, size_t status_off,
-                hipStream_t s) {
+static int pipe_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_total,
+                       size_t status_off, hipStream_t s) {
   PipeLaunch p;
-  p.name = "PIPE";
+  p.name = PIPE_VARIANT.name;
   p.NT = 512;
   p.NS = pipe_stages(d);
-  // up to pipe_pipelines(d) sequences: one per pipeline; more: ceil(batch / pipelines) each, in turn
-  p.pipes = std::min(batch, pipe_pipelines(d));
+  p.pipes = pipe_launch_pipelines(d, batch);
   p.slots = pipe_grid_slots(p.NS, p.pipes);
   p.batch = batch;
   p.max_batch = pipe_max_batch(d);
@@ -604,6 +603,14 @@ int pipe_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, siz
   else pipe_launch_fill<128>(p, batch > p.pipes);
   return pipe_launch_common(p, a, hand, hand_total, status_off, s);
 }
+
+#ifndef __HIP_DEVICE_COMPILE__  // (the device pass would emit the constant, host function pointers and all)
+const GenVariant PIPE_VARIANT = {
+    MVN_GEN_PIPE, "PIPE", pipe_ok, pipe_stages, pipe_inbox_floats, pipe_max_batch, pipe_launch_pipelines,
+    pipe_weights_floats, pipe_pack, pipe_launch,
+    "PIPE variant needs C=K in {64,128}, Q in {64,128,256}, 256 CUs and batch <= %d for these "
+    "dims (stages per sequence: ceil(L/4)+1 at C=64, L+1 at C=128; 32 per XCD)"};
+#endif
 
 }  // namespace mvn
 

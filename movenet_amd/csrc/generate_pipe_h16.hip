@@ -496,23 +496,24 @@ __global__ void pack_head_h16_kernel(const float *w1, const float *b1, const flo
   }
 }
 
-bool pipe_h16_ok(const mvn_dims *d) {
+static bool pipe_h16_ok(const mvn_dims *d) {
   return d->residual_channels == 128 && d->skip_channels == 128 && d->input_channels == 256 &&
          n_layers(d) >= 1;
 }
 // stages per pipeline for SIZING (hand-off area, co-residency): the two-layer count (MULTI), the larger one
-int pipe_h16_stages(const mvn_dims *d) {
+static int pipe_h16_stages(const mvn_dims *d) {
   constexpr int lps = h16::LpsM<true>::value;
   return (n_layers(d) + lps - 1) / lps + 1;
 }
-int pipe_h16_pipelines(const mvn_dims *d) { return pipe_pipelines_of(pipe_h16_stages(d)); }  // co-resident pipelines
-int pipe_h16_max_batch(const mvn_dims *d) { return h16::GMAX * pipe_h16_pipelines(d); }  // GMAX sequences each
-size_t pipe_h16_weights_floats(const mvn_dims *d) {
+static size_t pipe_h16_inbox_floats(const mvn_dims *) { return 2 * h16::GRAN; }
+static int pipe_h16_pipelines(const mvn_dims *d) { return pipe_pipelines_of(pipe_h16_stages(d)); }  // co-resident pipelines
+static int pipe_h16_max_batch(const mvn_dims *d) { return h16::GMAX * pipe_h16_pipelines(d); }  // GMAX sequences each
+static int pipe_h16_launch_pipelines(const mvn_dims *d, int batch) { return std::min(batch, pipe_h16_pipelines(d)); }
+static size_t pipe_h16_weights_floats(const mvn_dims *d) {
   return (size_t)h16::EMB_F + (size_t)n_layers(d) * h16::LAYER_F + h16::HEAD_F;
 }
-size_t pipe_h16_ctx_layer_floats() { return h16::CTX_LAYER_F; }
 
-int pipe_h16_pack(const mvn_dims *d, const mvn_params *p, float *packed, bool has_ctx, hipStream_t s) {
+static int pipe_h16_pack(const mvn_dims *d, const mvn_params *p, float *packed, float *ctx, hipStream_t s) {
   using namespace h16;
   const int L = n_layers(d);
   pack_embed(C, p->causal_w, packed, Q, s);
@@ -523,8 +524,7 @@ int pipe_h16_pack(const mvn_dims *d, const mvn_params *p, float *packed, bool ha
   float *head = packed + EMB_F + (size_t)L * LAYER_F;
   hipLaunchKernelGGL(pack_head_h16_kernel, dim3((Q * C + Q * Q + Q + 255) / 256), dim3(256), 0, s, p->head1_w,
                      p->head1_b, p->head2_w, p->head2_b, head);
-  if (has_ctx) {
-    float *ctx = packed + pipe_h16_weights_floats(d);
+  if (ctx) {
     for (int l = 0; l < L; ++l)
       hipLaunchKernelGGL(pack_ctx_h16_kernel, dim3((MAT_H + 2 * C + 255) / 256), dim3(256), 0, s,
                          p->ctx_filter_w[l], p->ctx_filter_b[l], p->ctx_gate_w[l], p->ctx_gate_b[l],
@@ -533,16 +533,16 @@ int pipe_h16_pack(const mvn_dims *d, const mvn_params *p, float *packed, bool ha
   return check_hip(hipGetLastError(), "pipe_h16_pack");
 }
 
-// `hand`: the hand-off area of the generator state (gen_common.h: hand_status_offset): this
+// `hand`: the hand-off area of the generator state (generate.hip: hand_status_offset): this
 // variant uses the first batch * NS inboxes and placement words of it.
-int pipe_h16_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_total,
-                    size_t status_off, hipStream_t s) {
+static int pipe_h16_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_total,
+                           size_t status_off, hipStream_t s) {
   using namespace h16;
   PipeLaunch p;
-  p.name = "PIPE_F16";
+  p.name = PIPE_F16_VARIANT.name;
   p.NT = NT;
   p.GRAN = GRAN;
-  p.pipes = std::min(batch, pipe_h16_pipelines(d));
+  p.pipes = pipe_h16_launch_pipelines(d, batch);
   const bool multi = batch > p.pipes;
   // (a pipeline that serves one sequence runs three layers per stage)
   const int lps = multi ? LpsM<true>::value : LpsM<false>::value;
@@ -555,6 +555,14 @@ int pipe_h16_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand,
   p.per_pipe = GMAX;
   return pipe_launch_common(p, a, hand, hand_total, status_off, s);
 }
+
+#ifndef __HIP_DEVICE_COMPILE__  // (the device pass would emit the constant, host function pointers and all)
+const GenVariant PIPE_F16_VARIANT = {
+    MVN_GEN_PIPE_F16, "PIPE_F16", pipe_h16_ok, pipe_h16_stages, pipe_h16_inbox_floats, pipe_h16_max_batch,
+    pipe_h16_launch_pipelines, pipe_h16_weights_floats, pipe_h16_pack, pipe_h16_launch,
+    "PIPE_F16 variant needs C=K=128, Q=256, 256 CUs and batch <= %d for these dims "
+    "(ceil(L/2)+1 stages per sequence, 32 per XCD)"};
+#endif
 
 }  // namespace mvn
 
