@@ -238,6 +238,40 @@ int mvn_generate_trunc(const mvn_dims *dims, int variant, const float *packed, f
                        float *logits_out, int32_t *choices_out, int logits_t0,
                        const float *context_tm, int sampling, int top_k, float top_p, void *stream);
 
+/* Per-sequence sampling settings: what mvn_generate_trunc takes once per launch (temperature, seed,
+ * top_k, top_p), once per SEQUENCE of the launch -- a sweep over settings on one prompt is one launch
+ * instead of one per setting, and a sequence's draws depend on its own (seed, row) alone: not on its
+ * position in the batch, nor on how a caller splits a batch into launches. */
+typedef struct mvn_seq_sampling { /* 24 bytes, one per sequence of the launch */
+  float temperature;              /* <= 0 (or NaN): this sequence decodes greedily */
+  int32_t top_k;                  /* 0: off */
+  float top_p;                    /* 1.0: off */
+  uint32_t row;                   /* second Philox counter word of this sequence (what `b` is on the scalar path) */
+  uint64_t seed;                  /* Philox key of this sequence */
+} mvn_seq_sampling;
+
+/* Host-only validator and normaliser of `batch` entries in HOST memory for a model of `classes` classes;
+ * touches no GPU.  The rules of mvn_generate_trunc's scalars, row by row: top_k < 0, or top_p outside
+ * (0, 1] (NaN included), is MVN_ERR_BAD_ARG with a mvn_last_error() text that names the first offending
+ * row, and nothing is modified; otherwise every top_k >= classes becomes 0 in place, so that "off" is off
+ * to the bit.  temperature, row and seed take any value. */
+int mvn_seq_sampling_check(mvn_seq_sampling *host, int batch, int classes);
+
+/* mvn_generate_trunc with the four settings per sequence: `per_seq` is a DEVICE array of `batch` entries
+ * that has passed mvn_seq_sampling_check (NULL: MVN_ERR_BAD_ARG); it is read by the kernel, so it must stay
+ * unchanged until the launch has run.  `sampling` (the rule) stays one value per call.
+ * The step of sequence b that predicts time u does exactly what mvn_generate_trunc does with per_seq[b]'s
+ * temperature, top_k and top_p, on the uniform philox_uniform(per_seq[b].seed, u, per_seq[b].row): with
+ * every entry (T, k, p, seed, row = b) the call is mvn_generate_trunc(T, seed, k, p) to the bit -- samples,
+ * logits_out and choices_out.  Greedy and sampled sequences may share a launch.  In the pipelined variants
+ * a pipeline serves several sequences in turn: the settings follow the sequence.
+ * Entries that never passed the check cause no out-of-range access; which class they draw is unspecified. */
+int mvn_generate_seq(const mvn_dims *dims, int variant, const float *packed, float *state,
+                     int32_t *samples, int batch, int sample_stride, int n_total, int n_given,
+                     int t_begin, int t_end, const mvn_seq_sampling *per_seq,
+                     float *logits_out, int32_t *choices_out, int logits_t0,
+                     const float *context_tm, int sampling, void *stream);
+
 /* Local conditioning in generation (BUILD DEFINITION, the reference raises: SURVEY.md
  * Q7): step t adds the context column of time t to every layer's filter/gate sums.
  * context_tm is (batch, n_total, C) TIME-major (one coalesced 4C-byte read per step);

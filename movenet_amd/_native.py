@@ -90,6 +90,12 @@ class BwdBuffers(C.Structure):
                 ("dctx", C.c_void_p)]
 
 
+class SeqSampling(C.Structure):
+    """mvn_seq_sampling: the sampling settings of one sequence of a mvn_generate_seq launch (24 bytes)."""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("row", C.c_uint32),
+                ("seed", C.c_uint64)]
+
+
 class VideoParams(C.Structure):  # also used for mvn_video_grads (same layout)
     _fields_ = [("conv_w", C.c_void_p), ("conv_b", C.c_void_p),
                 ("up_w", C.c_void_p * 3), ("up_b", C.c_void_p * 3)]
@@ -120,6 +126,10 @@ SIGNATURES = {
                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                      C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                      C.c_float, C.c_void_p]),
+    "mvn_seq_sampling_check": (C.c_int, [C.POINTER(SeqSampling), C.c_int, C.c_int]),
+    "mvn_generate_seq": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "mvn_transpose_context": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                         C.c_void_p]),
     "mvn_padded_len": (C.c_int, [C.c_int]),
@@ -250,6 +260,66 @@ def truncation(top_k, top_p):
     if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0.0 < top_p <= 1.0:
         raise ValueError(f"top_p must lie in (0, 1] (1: off), got {top_p!r}")
     return int(top_k), float(top_p)
+
+
+def _per_sequence(value) -> bool:
+    """True for what the generators take as one value per sequence: a list, tuple, numpy array or tensor that is
+    not 0-dimensional."""
+    if isinstance(value, (list, tuple)):
+        return True
+    return hasattr(value, "__len__") and hasattr(value, "tolist") and getattr(value, "ndim", 1) != 0
+
+
+def any_per_sequence(*values) -> bool:
+    return any(_per_sequence(v) for v in values)
+
+
+def seq_sampling_array(batch: int, classes: int, temperature, top_k, top_p, seed, rows=None):
+    """The checked HOST array of mvn_generate_seq, (SeqSampling * batch): ``temperature``, ``top_k``, ``top_p`` and
+    ``seed`` each a scalar (the same for every sequence) or a 1-D sequence / tensor of length ``batch``; ``rows``
+    (default: 0 .. batch - 1) the sequences' second Philox counter words.  ValueError for a wrong length or a value
+    mvn_seq_sampling_check refuses (top_k < 0, top_p outside (0, 1]; the message names the row); every top_k >=
+    ``classes`` comes back as 0.  Allocates nothing on a device."""
+    batch = int(batch)
+
+    def column(value, name, conv):
+        if _per_sequence(value):
+            value = value.tolist() if hasattr(value, "tolist") else list(value)
+            if not isinstance(value, list) or any(isinstance(v, (list, tuple)) for v in value):
+                raise ValueError(f"{name} must be a scalar or a 1-D sequence of length {batch}")
+            if len(value) != batch:
+                raise ValueError(f"{name} has {len(value)} entries for a batch of {batch}")
+        else:
+            value = [value] * batch
+        out = []
+        for b, v in enumerate(value):
+            try:
+                if isinstance(v, bool):
+                    raise TypeError
+                out.append(conv(v))
+            except (TypeError, ValueError):
+                raise ValueError(f"{name} of row {b} is {v!r}") from None
+        return out
+
+    def whole(v):
+        if isinstance(v, float) and not v.is_integer():
+            raise ValueError
+        return int(v)
+
+    cols = (column(temperature, "temperature", float), column(top_k, "top_k", whole), column(top_p, "top_p", float),
+            column(seed, "seed", whole), column(list(range(batch)) if rows is None else rows, "rows", whole))
+    for b, (k, r) in enumerate(zip(cols[1], cols[4])):
+        if not -2 ** 31 <= k < 2 ** 31:
+            raise ValueError(f"top_k of row {b} is {k!r}")
+        if not 0 <= r < 2 ** 32:
+            raise ValueError(f"rows: row {b} is {r!r}, not a 32-bit counter word")
+    arr = (SeqSampling * max(batch, 1))()
+    for b, (t, k, p, s, r) in enumerate(zip(*cols)):
+        arr[b] = SeqSampling(t, k, p, r, s & (2 ** 64 - 1))
+    rc = lib().mvn_seq_sampling_check(arr, batch, int(classes))
+    if rc != MVN_OK:
+        raise ValueError(last_error())
+    return arr
 
 
 def make_dims(layer_size: int, stack_size: int, input_channels: int, residual_channels: int,

@@ -10,6 +10,11 @@ offline); here the decoded waveforms are written as 16-bit PCM ``.wav`` files at
 rate (MAX_AUDIO_FRAMES / 10 = 16 kHz) under ``<default_root_dir>/samples/<split>/`` with
 one JSON line per clip in ``samples/index.jsonl`` (the table's columns).  The decoding runs
 on the GPU (``mvn_mu_law_decode``: formula of RESEARCH.md:156-163, parity unpinned).
+
+``temperature_sweep`` (default empty: off, the files and rows above unchanged): every logged clip is generated once
+per temperature of the sweep -- by the module, in ONE ``generate()`` call that carries each clip len(sweep) times with
+a temperature per sequence -- so ``outputs["generated_output"]`` holds len(sweep) rows per clip, clip-major.  They are
+written as ``...-gen-T<value>.wav``, one index row per (clip, temperature) with a ``temperature`` field.
 """
 from __future__ import annotations
 
@@ -41,11 +46,12 @@ def write_wav(path: Path, waveform: np.ndarray, sample_rate: int = SAMPLE_RATE) 
 
 class LogSamplesCallback:
     def __init__(self, log_every_n_epochs: int = 10, log_video: bool = True, temperature: float = 1.0,
-                 out_dir: Optional[str] = None):
+                 out_dir: Optional[str] = None, temperature_sweep=()):
         self.log_every_n_epochs = log_every_n_epochs
         self.log_video = log_video  # kept for signature parity: there is no video to re-attach
         self.temperature = temperature
         self.out_dir = Path(out_dir) if out_dir is not None else None
+        self.temperature_sweep = [float(t) for t in (temperature_sweep or ())]
         self.columns = list(COLUMNS)
 
     def on_train_batch_end(self, trainer, pl_module, outputs, batch, batch_idx):
@@ -76,6 +82,9 @@ class LogSamplesCallback:
         gen = None
         if outputs.get("generated_output", None) is not None:
             gen = self._decode(outputs["generated_output"], Q)
+        sweep = self.temperature_sweep if gen is not None else []
+        if sweep and len(gen) != len(fps) * len(sweep):
+            raise ValueError(f"generated_output holds {len(gen)} clips for {len(fps)} clips x {len(sweep)} temperatures")
         rows = []
         for i, fp in enumerate(fps):
             stem = f"epoch={trainer.current_epoch}-batch={batch_idx}-clip={i}"
@@ -83,6 +92,13 @@ class LogSamplesCallback:
                      "pred_audio": root / split / f"{stem}-pred.wav"}
             write_wav(files["origin_audio"], origin[i])
             write_wav(files["pred_audio"], pred[i])
+            for j, t in enumerate(sweep):
+                swept = dict(files, gen_audio=root / split / f"{stem}-gen-T{t:g}.wav")
+                write_wav(swept["gen_audio"], gen[i * len(sweep) + j])
+                rows.append({"split": split, "epoch": trainer.current_epoch, "batch_idx": batch_idx, "fp": fp,
+                             **{k: str(v.relative_to(root)) for k, v in swept.items()}, "temperature": t})
+            if sweep:
+                continue
             if gen is not None:
                 files["gen_audio"] = root / split / f"{stem}-gen.wav"
                 write_wav(files["gen_audio"], gen[i])

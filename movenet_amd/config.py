@@ -58,6 +58,9 @@ class TrainingConfig:
     # (0: off), then the smallest head of them that holds p of their mass (1.0: off).  Not reference fields either.
     generate_top_k: int = 0
     generate_top_p: float = 1.0
+    # temperatures each logged clip is generated at, all in ONE generate() call (empty: off -- generate_temperature
+    # alone, as before); the sample logger then writes one file per clip and temperature.  Not a reference field.
+    generate_temperature_sweep: List[float] = field(default_factory=list)
 
     # what the train step minimises (WaveNet.loss_rule): "reference", the reference's cross_entropy applied to the
     # model's probabilities, or "model", cross_entropy of the logits (the negative log-likelihood of the distribution
@@ -145,6 +148,7 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--generate_sampling", type=str, default="reference", choices=["reference", "model"])
     a("--generate_top_k", type=int, default=0)
     a("--generate_top_p", type=float, default=1.0)
+    a("--generate_temperature_sweep", type=lambda x: [float(t) for t in x.split(",") if t.strip()], default=[])
     a("--loss_rule", type=str, default="reference", choices=["reference", "model"])
     a("--n_epochs", type=int, default=10)
     a("--n_steps_per_epoch", type=int, default=None)
@@ -188,7 +192,7 @@ def config_from_args(args) -> TrainingConfig:
         "lr_pct_start base_learning_rate scheduler_step_size_up scheduler_step_size_down "
         "scheduler_cyclic_mode scheduler_cyclic_gamma scheduler_cycle_momentum max_learning_rate "
         "scheduler_step_size scheduler_step_gamma scheduler_milestones weight_decay "
-        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p loss_rule accumulation_steps num_workers val_num_workers "
+        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule accumulation_steps num_workers val_num_workers "
         "pin_memory n_epochs n_steps_per_epoch use_video batch_subsample_frac "
         "val_batch_subsample_frac dist_backend dist_port model_output_path log_samples_every"
     ).split()

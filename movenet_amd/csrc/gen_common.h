@@ -4,7 +4,11 @@
 
 namespace mvn {
 
-struct GenArgs {
+// GenScalarArgs: what a kernel takes where one temperature, seed, top_k and top_p hold for the whole launch -- the
+// kernel argument of every instantiation that existed before mvn_generate_seq, layout unchanged (their code is the
+// same to the instruction).  GenArgs (below) adds the per-sequence array: what the host drivers pass around, and the
+// kernel argument of the SEQ instantiations.
+struct GenScalarArgs {
   int L, layer_size, Q, C, K;
   const float *w;
   float *state;
@@ -27,6 +31,38 @@ struct GenArgs {
   long long ctx_stride_b;
   const float *wctx;
 };
+struct GenArgs : GenScalarArgs {
+  // mvn_generate_seq: DEVICE array of one entry per sequence of the launch (NULL on every other entry point); the
+  // kernels' SEQ instantiations read temperature, top_k, top_p, seed and row from it instead of the scalars above
+  const mvn_seq_sampling *per_seq;
+};
+// The kernel argument of an instantiation.  A launch hands every kernel a GenArgs; a scalar instantiation's
+// parameter is its leading GenScalarArgs (the base sits at offset 0).
+template <bool SEQ>
+struct KArgsOf { typedef GenScalarArgs type; };
+template <>
+struct KArgsOf<true> { typedef GenArgs type; };
+template <bool SEQ>
+using KArgs = typename KArgsOf<SEQ>::type;
+
+// What a step of sequence b samples by: the launch's scalars with row = b (what every kernel did before
+// mvn_generate_seq), or, by the kernel argument's type, entry b of a.per_seq.  b is uniform over the wave or
+// block that makes the choice, so the loads are uniform; an entry that never passed mvn_seq_sampling_check only
+// changes which class is drawn (every consumer keeps its index in [0, Q) whatever the values).
+struct SeqSampling {
+  float temperature;
+  int top_k;
+  float top_p;
+  uint64_t seed;
+  uint32_t row;  // second Philox counter word
+};
+__device__ __forceinline__ SeqSampling seq_sampling(const GenScalarArgs &a, int b) {
+  return {a.temperature, a.top_k, a.top_p, a.seed, (uint32_t)b};
+}
+__device__ __forceinline__ SeqSampling seq_sampling(const GenArgs &a, int b) {
+  const mvn_seq_sampling *s = a.per_seq + b;
+  return {s->temperature, s->top_k, s->top_p, s->seed, s->row};
+}
 
 __device__ __forceinline__ int ring_offset(int l, int layer_size, int C) {
   const int stack = l / layer_size, pos = l - stack * layer_size;
@@ -85,7 +121,7 @@ struct GenVariant {
 extern const GenVariant PIPE_VARIANT, PIPE_F16_VARIANT, FOLD_VARIANT;
 
 // ---- shared by the three pipelined variants (defined in generate_pipe.hip) ---------------
-// One launch of a pipelined generator kernel (GenArgs, u64 *hand, unsigned *err, int NS, int nb, int nseq):
+// One launch of a pipelined generator kernel (KArgs<SEQ>, u64 *hand, unsigned *err, int NS, int nb, int nseq):
 // co-residency and capacity check (MVN_ERR_UNSUPPORTED), hand-off area bounds (MVN_ERR_BAD_ARG), the memsets of
 // every polled word, then a cooperative launch where available and allowed (pipe_common.h), else an ordinary one.
 struct PipeLaunch {

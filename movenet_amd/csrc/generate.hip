@@ -32,6 +32,11 @@
 
 namespace mvn {
 
+// A sampling setting of the sequence a GENERIC or STREAM workgroup serves: the launch's scalar, read from the kernel
+// argument in place as before mvn_generate_seq (going through a copy or a reference reorders the argument loads of the
+// scalar instantiations, and with them their registers), or the field of `ps`, the block's entry of a.per_seq.
+#define BLOCK_SETTING(field) (SEQ ? ps.field : a.field)
+
 // ======================================================================
 // GENERIC variant
 // ======================================================================
@@ -139,7 +144,9 @@ __device__ int truncate_weights_lds(float *w, int Q, int top_k, float top_p) {
   return top >= 0 ? top : Q - 1;
 }
 
-__global__ __launch_bounds__(1024) void gen_generic_kernel(GenArgs a) {
+// SEQ: the block reads its sequence's sampling settings from a.per_seq (mvn_generate_seq), once, ahead of the step loop
+template <bool SEQ>
+__global__ __launch_bounds__(1024) void gen_generic_kernel(KArgs<SEQ> a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, NT = blockDim.x, b = blockIdx.x;
   const int C = a.C, K = a.K, Q = a.Q, L = a.L;
@@ -167,6 +174,8 @@ __global__ __launch_bounds__(1024) void gen_generic_kernel(GenArgs a) {
   const float *W2t = b1 + Q, *b2 = W2t + (size_t)Q * Q;
   float *ring = a.state + (size_t)b * a.state_per_seq;
   int32_t *samples = a.samples + (size_t)b * a.stride;
+  SeqSampling ps = {};  // SEQ: the block's entry of a.per_seq, loaded once ahead of the step loop (block-uniform)
+  if constexpr (SEQ) ps = seq_sampling(a, b);
 
   int Pfg, cfg, Prs, crs, P1, c1, P2, c2;
   split_parts(2 * C, 2 * C, NT, Pfg, cfg);
@@ -255,8 +264,8 @@ __global__ __launch_bounds__(1024) void gen_generic_kernel(GenArgs a) {
       float m = -INFINITY;
       for (int q = tid; q < Q; q += NT) m = fmaxf(m, logits[q]);
       m = block_max_g(m, red);
-      if (a.temperature > 0.f && a.sampling == MVN_SAMPLE_MODEL) {  // block-uniform
-        for (int q = tid; q < Q; q += NT) a1[q] = expf((logits[q] - m) / a.temperature);
+      if (BLOCK_SETTING(temperature) > 0.f && a.sampling == MVN_SAMPLE_MODEL) {  // block-uniform
+        for (int q = tid; q < Q; q += NT) a1[q] = expf((logits[q] - m) / BLOCK_SETTING(temperature));
       } else {
         float s = 0.f;
         for (int q = tid; q < Q; q += NT) {
@@ -268,7 +277,7 @@ __global__ __launch_bounds__(1024) void gen_generic_kernel(GenArgs a) {
         float m2 = -INFINITY;
         for (int q = tid; q < Q; q += NT) {
           float p = a1[q] / s;
-          if (a.temperature > 0.f) p = p / a.temperature;
+          if (BLOCK_SETTING(temperature) > 0.f) p = p / BLOCK_SETTING(temperature);
           a1[q] = p;
           m2 = fmaxf(m2, p);
         }
@@ -284,20 +293,20 @@ __global__ __launch_bounds__(1024) void gen_generic_kernel(GenArgs a) {
       }
       __syncthreads();
       int fallback = Q - 1;  // of a draw that no class's running sum exceeds
-      if (a.temperature > 0.f && (a.top_k > 0 || a.top_p < 1.f)) {  // block-uniform
+      if (BLOCK_SETTING(temperature) > 0.f && (BLOCK_SETTING(top_k) > 0 || BLOCK_SETTING(top_p) < 1.f)) {  // block-uniform
         // (a zeroed class leaves thread 0's running sum as it was: it never qualifies before the class in front)
-        if (tid < 64) fallback = truncate_weights_lds(a1, Q, a.top_k, a.top_p);
+        if (tid < 64) fallback = truncate_weights_lds(a1, Q, BLOCK_SETTING(top_k), BLOCK_SETTING(top_p));
         __syncthreads();
       }
       if (tid == 0) {
         int choice = 0;
-        if (a.temperature > 0.f) {
+        if (BLOCK_SETTING(temperature) > 0.f) {
           // in double: an fp32 sum of ~1000 terms rounds the same way term after term (a floor weight of 1e-4
           // beside a sum of 5 loses 0.2 % of itself each time), and with 1000 band edges inside that drift fewer
           // than 99.9 % of the draws equalled float64's at Q >= 1000
           double total = 0.0;
           for (int q = 0; q < Q; ++q) total += (double)a1[q];
-          const double target = (double)philox_uniform(a.seed, (uint32_t)u, (uint32_t)b) * total;
+          const double target = (double)philox_uniform(BLOCK_SETTING(seed), (uint32_t)u, (SEQ ? ps.row : (uint32_t)b)) * total;
           double cdf = 0.0;
           choice = fallback;
           for (int q = 0; q < Q; ++q) {
@@ -346,7 +355,9 @@ __device__ __forceinline__ float dot4(const f4 w, const f4 x, float acc) {
   return fmaf(w.w, x.w, acc);
 }
 
-__global__ __launch_bounds__(256, 1) void gen_stream64_kernel(GenArgs a) {
+// SEQ: as gen_generic_kernel's
+template <bool SEQ>
+__global__ __launch_bounds__(256, 1) void gen_stream64_kernel(KArgs<SEQ> a) {
   using namespace s64;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, b = blockIdx.x;
@@ -373,6 +384,8 @@ __global__ __launch_bounds__(256, 1) void gen_stream64_kernel(GenArgs a) {
   const float *b1 = (const float *)(head + W1_F4), *b2 = (const float *)(W2p + W2_F4);
   float *ring = a.state + (size_t)b * a.state_per_seq;
   int32_t *samples = a.samples + (size_t)b * a.stride;
+  SeqSampling ps = {};  // SEQ: the block's entry of a.per_seq, loaded once ahead of the step loop (block-uniform)
+  if constexpr (SEQ) ps = seq_sampling(a, b);
 
   // embedding tables -> LDS (once per launch)
   {
@@ -555,10 +568,10 @@ __global__ __launch_bounds__(256, 1) void gen_stream64_kernel(GenArgs a) {
       lds_barrier();
       m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
       float p2;
-      if (a.temperature > 0.f && a.sampling == MVN_SAMPLE_MODEL) {  // block-uniform
+      if (BLOCK_SETTING(temperature) > 0.f && a.sampling == MVN_SAMPLE_MODEL) {  // block-uniform
         // the weight exp((l - max) / T) of softmax(logits / T): the scan below draws against the total (a padding
         // class, logit -inf, weighs exactly 0)
-        p2 = expf((lg - m) / a.temperature);
+        p2 = expf((lg - m) / BLOCK_SETTING(temperature));
       } else {
         const float e = expf(lg - m);
         float s = wave_sum(e);
@@ -566,7 +579,7 @@ __global__ __launch_bounds__(256, 1) void gen_stream64_kernel(GenArgs a) {
         lds_barrier();
         s = (red[4] + red[5]) + (red[6] + red[7]);
         float p = e / s;
-        if (a.temperature > 0.f) p = p / a.temperature;
+        if (BLOCK_SETTING(temperature) > 0.f) p = p / BLOCK_SETTING(temperature);
         float m2 = wave_max(p);
         if (lane == 0) red[8 + wave] = m2;
         lds_barrier();
@@ -580,15 +593,15 @@ __global__ __launch_bounds__(256, 1) void gen_stream64_kernel(GenArgs a) {
       }
 
       int cand;
-      if (a.temperature > 0.f) {
+      if (BLOCK_SETTING(temperature) > 0.f) {
         int fallback = a.Q - 1;
-        const bool trunc = a.top_k > 0 || a.top_p < 1.f;  // block-uniform
+        const bool trunc = BLOCK_SETTING(top_k) > 0 || BLOCK_SETTING(top_p) < 1.f;  // block-uniform
         if (trunc) {
           // a1 is free (conv2 has read it, barriers ago): the weights go through it, wave 0 zeroes the dropped ones
           a1[tid] = p2;
           lds_barrier();
           if (tid < 64) {
-            const int top = truncate_weights_lds(a1, a.Q, a.top_k, a.top_p);
+            const int top = truncate_weights_lds(a1, a.Q, BLOCK_SETTING(top_k), BLOCK_SETTING(top_p));
             if (tid == 0) ired[6] = top;
           }
           lds_barrier();
@@ -609,7 +622,7 @@ __global__ __launch_bounds__(256, 1) void gen_stream64_kernel(GenArgs a) {
         if (wave > 1) base += red[17];
         if (wave > 2) base += red[18];
         const float total = ((red[16] + red[17]) + red[18]) + red[19];
-        const float target = philox_uniform(a.seed, (uint32_t)u, (uint32_t)b) * total;
+        const float target = philox_uniform(BLOCK_SETTING(seed), (uint32_t)u, (SEQ ? ps.row : (uint32_t)b)) * total;
         // (truncated: only a class of positive weight may qualify -- the scan associates the sums of neighbouring
         // classes differently, and a zeroed class could otherwise cross the target a rounding before the kept one)
         cand = (base + c > target && (!trunc || p2 > 0.f)) ? tid : fallback;
@@ -634,7 +647,7 @@ __global__ __launch_bounds__(256, 1) void gen_stream64_kernel(GenArgs a) {
       if (lane == 0) ired[wave] = cand;
       lds_barrier();
       int pick;
-      if (a.temperature > 0.f) {
+      if (BLOCK_SETTING(temperature) > 0.f) {
         pick = min(min(ired[0], ired[1]), min(ired[2], ired[3]));
       } else {
         pick = ired[0];
@@ -861,9 +874,14 @@ static int stream_pack(const mvn_dims *d, const mvn_params *p, float *packed, fl
 
 static int generic_launch(const GenArgs &a, const mvn_dims *d, int batch, float *, size_t, size_t,
                           hipStream_t stream) {
-  int rc = ensure_max_dynamic_lds((const void *)gen_generic_kernel, "hipFuncSetAttribute(gen_generic)");
+  const void *fn = a.per_seq ? (const void *)gen_generic_kernel<true> : (const void *)gen_generic_kernel<false>;
+  int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(gen_generic)");
   if (rc) return rc;
-  hipLaunchKernelGGL(gen_generic_kernel, dim3(batch), dim3(generic_threads(d)), generic_lds_bytes(d), stream, a);
+  const dim3 grid(batch), block(generic_threads(d));
+  if (a.per_seq)
+    hipLaunchKernelGGL(gen_generic_kernel<true>, grid, block, generic_lds_bytes(d), stream, a);
+  else
+    hipLaunchKernelGGL(gen_generic_kernel<false>, grid, block, generic_lds_bytes(d), stream, a);
   return check_hip(hipGetLastError(), "mvn_generate");
 }
 static int stream_launch(const GenArgs &a, const mvn_dims *, int batch, float *, size_t, size_t,
@@ -873,9 +891,13 @@ static int stream_launch(const GenArgs &a, const mvn_dims *, int batch, float *,
     set_error("STREAM variant: %d conditioned layers do not fit a CU's LDS", a.L);
     return MVN_ERR_UNSUPPORTED;
   }
-  int rc = ensure_max_dynamic_lds((const void *)gen_stream64_kernel, "hipFuncSetAttribute(gen_stream64)");
+  const void *fn = a.per_seq ? (const void *)gen_stream64_kernel<true> : (const void *)gen_stream64_kernel<false>;
+  int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(gen_stream64)");
   if (rc) return rc;
-  hipLaunchKernelGGL(gen_stream64_kernel, dim3(batch), dim3(256), lds, stream, a);
+  if (a.per_seq)
+    hipLaunchKernelGGL(gen_stream64_kernel<true>, dim3(batch), dim3(256), lds, stream, a);
+  else
+    hipLaunchKernelGGL(gen_stream64_kernel<false>, dim3(batch), dim3(256), lds, stream, a);
   return check_hip(hipGetLastError(), "mvn_generate");
 }
 
@@ -1052,11 +1074,61 @@ int mvn_generate_ex(const mvn_dims *dims, int variant, const float *packed, floa
                             1.0f, stream);
 }
 
+// top_k < 0, or top_p outside (0, 1] (a NaN fails the comparison)
+static bool bad_truncation(int top_k, float top_p) { return top_k < 0 || !(top_p > 0.f && top_p <= 1.f); }
+
+int mvn_seq_sampling_check(mvn_seq_sampling *host, int batch, int classes) {
+  if (!host || batch < 0 || classes < 1) {
+    mvn::set_error("mvn_seq_sampling_check: bad argument (batch %d classes %d)", batch, classes);
+    return MVN_ERR_BAD_ARG;
+  }
+  for (int b = 0; b < batch; ++b)
+    if (bad_truncation(host[b].top_k, host[b].top_p)) {
+      mvn::set_error("mvn_seq_sampling_check: bad argument in row %d (top_k %d must be >= 0, top_p %g must lie in "
+                     "(0, 1])", b, host[b].top_k, (double)host[b].top_p);
+      return MVN_ERR_BAD_ARG;
+    }
+  for (int b = 0; b < batch; ++b)
+    if (host[b].top_k >= classes) host[b].top_k = 0;  // every class kept: off, to the bit
+  return MVN_OK;
+}
+
+// The one host driver of every mvn_generate* entry point: `per_seq` NULL (the four scalars hold for every sequence,
+// row = its index) or the checked device array of mvn_generate_seq (the scalars are then not read).
+static int generate_driver(const mvn_dims *dims, int variant, const float *packed, float *state,
+                           int32_t *samples, int batch, int sample_stride, int n_total, int n_given,
+                           int t_begin, int t_end, float temperature, uint64_t seed, float *logits_out,
+                           int32_t *choices_out, int logits_t0, const float *context_tm, int sampling,
+                           int top_k, float top_p, const mvn_seq_sampling *per_seq, void *stream);
+
 int mvn_generate_trunc(const mvn_dims *dims, int variant, const float *packed, float *state,
                        int32_t *samples, int batch, int sample_stride, int n_total, int n_given,
                        int t_begin, int t_end, float temperature, uint64_t seed, float *logits_out,
                        int32_t *choices_out, int logits_t0, const float *context_tm, int sampling,
                        int top_k, float top_p, void *stream) {
+  return generate_driver(dims, variant, packed, state, samples, batch, sample_stride, n_total, n_given, t_begin,
+                         t_end, temperature, seed, logits_out, choices_out, logits_t0, context_tm, sampling, top_k,
+                         top_p, nullptr, stream);
+}
+
+int mvn_generate_seq(const mvn_dims *dims, int variant, const float *packed, float *state,
+                     int32_t *samples, int batch, int sample_stride, int n_total, int n_given,
+                     int t_begin, int t_end, const mvn_seq_sampling *per_seq, float *logits_out,
+                     int32_t *choices_out, int logits_t0, const float *context_tm, int sampling, void *stream) {
+  if (!per_seq) {
+    mvn::set_error("mvn_generate_seq: bad argument (per_seq is NULL)");
+    return MVN_ERR_BAD_ARG;
+  }
+  return generate_driver(dims, variant, packed, state, samples, batch, sample_stride, n_total, n_given, t_begin,
+                         t_end, 0.f, 0, logits_out, choices_out, logits_t0, context_tm, sampling, 0, 1.0f, per_seq,
+                         stream);
+}
+
+static int generate_driver(const mvn_dims *dims, int variant, const float *packed, float *state,
+                           int32_t *samples, int batch, int sample_stride, int n_total, int n_given,
+                           int t_begin, int t_end, float temperature, uint64_t seed, float *logits_out,
+                           int32_t *choices_out, int logits_t0, const float *context_tm, int sampling,
+                           int top_k, float top_p, const mvn_seq_sampling *per_seq, void *stream) {
   if (variant == MVN_GEN_AUTO) {
     mvn::set_error("mvn_generate: resolve the variant with mvn_gen_variant first (the packed "
                    "weight layout depends on it)");
@@ -1067,7 +1139,7 @@ int mvn_generate_trunc(const mvn_dims *dims, int variant, const float *packed, f
                    "MVN_SAMPLE_MODEL)", sampling);
     return MVN_ERR_BAD_ARG;
   }
-  if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) {  // (a NaN top_p fails the comparison)
+  if (bad_truncation(top_k, top_p)) {
     mvn::set_error("mvn_generate_trunc: bad argument (top_k %d must be >= 0, top_p %g must lie in (0, 1])", top_k,
                    (double)top_p);
     return MVN_ERR_BAD_ARG;
@@ -1106,6 +1178,7 @@ int mvn_generate_trunc(const mvn_dims *dims, int variant, const float *packed, f
   a.sampling = sampling;
   a.top_k = top_k >= a.Q ? 0 : top_k;  // every class kept: off, to the bit
   a.top_p = top_p;
+  a.per_seq = per_seq;
   a.ctx_tm = context_tm;
   a.ctx_stride_b = (long long)n_total * dims->residual_channels;
   const mvn::GenVariant &v = *mvn::find_variant(variant);

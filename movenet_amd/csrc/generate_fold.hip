@@ -198,8 +198,9 @@ __device__ __forceinline__ float split_dot_lds(unsigned waddr, unsigned xaddr) {
 
 // MULTI = false: one sequence per pipeline (nseq == nb), the form every config-2 figure up to
 // batch 16 is measured on.  MULTI = true: pipeline b serves sequences b, b + nb, b + 2 nb, ... < nseq.
-template <bool MULTI>
-__global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, unsigned *err, int NS, int nb, int nseq) {
+// SEQ: the head reads each sequence's sampling settings from a.per_seq (mvn_generate_seq); the layer stages do not differ.
+template <bool MULTI, bool SEQ>
+__global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ> a, u64 *hand, unsigned *err, int NS, int nb, int nseq) {
   using namespace fold;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -662,7 +663,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(GenArgs a, u64 *hand, 
       lds_barrier();
       MVN_FINE(b, NS - 1, epoch - 1, 4, 0);
     };
-    head_loop<C, GRAN, MULTI, 2, 0>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
+    head_loop<C, GRAN, MULTI, SEQ, 2, 0>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
   }
 }
 
@@ -824,7 +825,8 @@ static int fold_launch(const GenArgs &a, const mvn_dims *d, int batch, float *ha
   p.GRAN = GRAN;
   p.pipes = fold_launch_pipelines(d, batch);
   const bool multi = batch > p.pipes;
-  p.fn = multi ? (const void *)gen_fold_kernel<true> : (const void *)gen_fold_kernel<false>;
+  p.fn = a.per_seq ? (multi ? (const void *)gen_fold_kernel<true, true> : (const void *)gen_fold_kernel<false, true>)
+                   : (multi ? (const void *)gen_fold_kernel<true, false> : (const void *)gen_fold_kernel<false, false>);
   p.lds_bytes = (multi ? LDS_FLOATS_MULTI : LDS_FLOATS) * sizeof(float);
   // the kernel's own map: whole pipelines inside the XCDs, or every CU (the left-over ones form pipelines across XCDs)
   p.slots = p.pipes <= fold_pipelines(d) ? (p.pipes + 7) / 8 * p.NS : PIPE_XCD_CUS;

@@ -66,8 +66,9 @@ struct PipeCfg {
 //
 // MULTI = false: one sequence per pipeline (nseq == nb).  MULTI = true: pipeline b serves sequences
 // b, b + nb, b + 2 nb, ... < nseq in turn, one step of each per round.
-template <int CC, bool MULTI>
-__global__ __launch_bounds__(512, 2) void gen_pipe_kernel(GenArgs a, u64 *hand, unsigned *err, int NS,
+// SEQ: the head reads each sequence's sampling settings from a.per_seq (mvn_generate_seq); the layer stages do not differ.
+template <int CC, bool MULTI, bool SEQ>
+__global__ __launch_bounds__(512, 2) void gen_pipe_kernel(KArgs<SEQ> a, u64 *hand, unsigned *err, int NS,
                                                          int nb, int nseq) {
   using P = PipeCfg<CC>;
   constexpr int C = P::C, Q = P::Q, NT = P::NT, LPS = P::LPS, KQ = P::KQ, KPER = P::KPER;
@@ -406,7 +407,7 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_kernel(GenArgs a, u64 *hand, 
       head_conv2_f32(w2, a1, lgb, og, q2, b2r);
       lds_barrier();
     };
-    head_loop<C, GRAN, MULTI, 1>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
+    head_loop<C, GRAN, MULTI, SEQ, 1>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
   }
 }
 
@@ -582,9 +583,10 @@ int pipe_launch_common(const PipeLaunch &p, const GenArgs &a, float *hand, size_
 }
 
 template <int CC>
-static void pipe_launch_fill(PipeLaunch &p, bool multi) {
+static void pipe_launch_fill(PipeLaunch &p, bool multi, bool seq) {
   using P = PipeCfg<CC>;
-  p.fn = multi ? (const void *)gen_pipe_kernel<CC, true> : (const void *)gen_pipe_kernel<CC, false>;
+  p.fn = seq ? (multi ? (const void *)gen_pipe_kernel<CC, true, true> : (const void *)gen_pipe_kernel<CC, false, true>)
+             : (multi ? (const void *)gen_pipe_kernel<CC, true, false> : (const void *)gen_pipe_kernel<CC, false, false>);
   p.lds_bytes = (multi ? P::LDS_FLOATS_MULTI : P::LDS_FLOATS) * sizeof(float);
   p.GRAN = P::GRAN;
   p.per_pipe = P::GMAX;
@@ -599,8 +601,8 @@ static int pipe_launch(const GenArgs &a, const mvn_dims *d, int batch, float *ha
   p.slots = pipe_grid_slots(p.NS, p.pipes);
   p.batch = batch;
   p.max_batch = pipe_max_batch(d);
-  if (d->residual_channels == 64) pipe_launch_fill<64>(p, batch > p.pipes);
-  else pipe_launch_fill<128>(p, batch > p.pipes);
+  if (d->residual_channels == 64) pipe_launch_fill<64>(p, batch > p.pipes, a.per_seq != nullptr);
+  else pipe_launch_fill<128>(p, batch > p.pipes, a.per_seq != nullptr);
   return pipe_launch_common(p, a, hand, hand_total, status_off, s);
 }
 

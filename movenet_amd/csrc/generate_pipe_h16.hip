@@ -94,8 +94,9 @@ __device__ __forceinline__ float pair_sum(float v) { return v + dpp_mov<DPP_XOR1
 // MULTI = false: one sequence per pipeline (nseq == nb).  MULTI = true: pipeline b serves sequences
 // b, b + nb, b + 2 nb, ... < nseq in turn.
 // Every product of a layer stage runs on the matrix cores (r3, see the layer stage below).
-template <bool MULTI>
-__global__ __launch_bounds__(512, 2) void gen_pipe_h16_kernel(GenArgs a, u64 *hand, unsigned *err, int NS,
+// SEQ: the head reads each sequence's sampling settings from a.per_seq (mvn_generate_seq); the layer stages do not differ.
+template <bool MULTI, bool SEQ>
+__global__ __launch_bounds__(512, 2) void gen_pipe_h16_kernel(KArgs<SEQ> a, u64 *hand, unsigned *err, int NS,
                                                              int nb, int nseq) {
   using namespace h16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];
@@ -428,7 +429,7 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_h16_kernel(GenArgs a, u64 *ha
       }
       lds_barrier();
     };
-    head_loop<C, GRAN, MULTI, 1>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
+    head_loop<C, GRAN, MULTI, SEQ, 1>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
   }
 }
 
@@ -547,7 +548,9 @@ static int pipe_h16_launch(const GenArgs &a, const mvn_dims *d, int batch, float
   // (a pipeline that serves one sequence runs three layers per stage)
   const int lps = multi ? LpsM<true>::value : LpsM<false>::value;
   p.NS = (n_layers(d) + lps - 1) / lps + 1;
-  p.fn = multi ? (const void *)gen_pipe_h16_kernel<true> : (const void *)gen_pipe_h16_kernel<false>;
+  p.fn = a.per_seq
+             ? (multi ? (const void *)gen_pipe_h16_kernel<true, true> : (const void *)gen_pipe_h16_kernel<false, true>)
+             : (multi ? (const void *)gen_pipe_h16_kernel<true, false> : (const void *)gen_pipe_h16_kernel<false, false>);
   p.lds_bytes = multi ? LDS_BYTES_M_MULTI : LDS_BYTES_M;
   p.slots = pipe_grid_slots(p.NS, p.pipes);
   p.batch = batch;

@@ -733,8 +733,10 @@ __device__ __forceinline__ void head_conv2_f32(const v2f (&w2)[4][16], const flo
 //                                  (do_head is block-uniform; false: no logits are needed for this step)
 // iflag / hidx: LDS words ([0]: the hand-off's ok flag; MULTI: [GMAX][2] = {idx_cur, idx_prev} of each sequence
 // between its turns).
-template <int C, int GRAN, bool MULTI, int NZ, int NZ_SENT = NZ, class Await, class Logits>
-__device__ __forceinline__ void head_loop(const GenArgs &a, u64 *hand, int NS, int nb, int b, int G, bool fast_edge,
+// SEQ (mvn_generate_seq): the settings of a step are those of the sequence whose turn it is, a.per_seq[bq], loaded
+// where the uniform is formed -- before the wait for the step's input, off the dependent chain.
+template <int C, int GRAN, bool MULTI, bool SEQ, int NZ, int NZ_SENT = NZ, class Await, class Logits>
+__device__ __forceinline__ void head_loop(const KArgs<SEQ> &a, u64 *hand, int NS, int nb, int b, int G, bool fast_edge,
                                           const float *E0, const float *E1, int *iflag, int *hidx, const float *lgb,
                                           Await await, Logits logits) {
   static_assert(GRAN == (1 + NZ) * C && NZ_SENT <= NZ, "residual stream + NZ zero lanes");
@@ -794,8 +796,10 @@ __device__ __forceinline__ void head_loop(const GenArgs &a, u64 *hand, int NS, i
     // this step's Philox uniform, formed while the step's input is still on its way (the fence
     // keeps it from being sunk to its use behind the head's barriers)
     float uni = 0.f;
-    if (wave == 0 && a.temperature > 0.f) {
-      uni = philox_uniform(a.seed, (uint32_t)u, (uint32_t)bq);
+    SeqSampling ss = seq_sampling((const GenScalarArgs &)a, bq);
+    if (SEQ && wave == 0) ss = seq_sampling(a, bq);
+    if (wave == 0 && ss.temperature > 0.f) {
+      uni = philox_uniform(ss.seed, (uint32_t)u, ss.row);
       asm volatile("" : "+v"(uni));
     }
     if (wave == 0) {
@@ -815,7 +819,7 @@ __device__ __forceinline__ void head_loop(const GenArgs &a, u64 *hand, int NS, i
         // (rows of a.Q logits: the padding of a smaller model is not written; fp16 PIPE takes Q = 256 only)
         if (a.logits_out && u >= a.logits_t0 && 4 * lane < a.Q)
           ((f4 *)(a.logits_out + ((size_t)bq * (a.n_total - a.logits_t0) + (u - a.logits_t0)) * a.Q))[lane] = lv;
-        pick = choose_class(lg, a.temperature, a.sampling, a.top_k, a.top_p, uni, lane, a.Q);
+        pick = choose_class(lg, ss.temperature, a.sampling, ss.top_k, ss.top_p, uni, lane, a.Q);
         if (u >= a.n_given) next_idx = pick;
       }
       idx_prev = idx_cur;

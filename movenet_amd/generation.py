@@ -1,6 +1,7 @@
 """Host side of the ring-buffer generator: owns the packed weights, the
 dilation-queue state and the sample buffer as torch tensors (device memory and
-stream plumbing only) and drives ``mvn_generate_trunc`` through the C ABI.
+stream plumbing only) and drives ``mvn_generate_trunc`` -- or, with settings per sequence,
+``mvn_generate_seq`` -- through the C ABI.
 
 Replaces the per-sample window loop of /root/reference/movenet/wavenet.py:217-237.
 """
@@ -178,16 +179,30 @@ class RingGenerator:
                  batch: int, n_total: int, device, variant: int = N.GEN_AUTO,
                  temperature: float = 0.0, seed: int = 0,
                  context: Optional[torch.Tensor] = None, sampling: str = "reference", top_k: int = 0,
-                 top_p: float = 1.0):
+                 top_p: float = 1.0, rows=None):
         """``sampling``: what a sampled step (temperature > 0) draws from -- "reference": the reference's
         softmax(softmax(logits) / T), close to uniform whatever the model predicts; "model": the model's own
         softmax(logits / T).  Greedy decoding (temperature <= 0) is the same under both.
         ``top_k`` / ``top_p``: truncation of a sampled step before the draw (include/movenet_hip.h,
         mvn_generate_trunc) -- keep the ``top_k`` likeliest classes (0: off), then the smallest head of them that holds
-        ``top_p`` of their mass (1.0: off); greedy decoding ignores both."""
+        ``top_p`` of their mass (1.0: off); greedy decoding ignores both.
+        ``temperature``, ``seed``, ``top_k`` and ``top_p`` each take one value or a sequence / 1-D tensor of ``batch``
+        values.  All four single: one ``mvn_generate_trunc`` launch with them, sequence b drawing on Philox row b.  Any
+        of them a sequence (or ``rows`` given): the settings go to the device once and the launches are
+        ``mvn_generate_seq``'s -- sequence b samples by its own entry, on its own seed and on row ``rows[b]``
+        (default b), so its draws do not depend on where in which batch it sits.  The attributes are then lists."""
         self._sampling = N.sampling_rule(sampling)
         self.sampling = sampling
-        self.top_k, self.top_p = N.truncation(top_k, top_p)  # ValueError before anything is allocated
+        seq_host = None
+        if rows is not None or N.any_per_sequence(temperature, seed, top_k, top_p):  # ValueError before anything is allocated
+            seq_host = N.seq_sampling_array(batch, input_channels, temperature, top_k, top_p, seed, rows)
+            entries = [seq_host[b] for b in range(int(batch))]
+            temperature, seed = [e.temperature for e in entries], [e.seed for e in entries]
+            self.top_k, self.top_p = [e.top_k for e in entries], [e.top_p for e in entries]
+            self.rows = [e.row for e in entries]
+        else:
+            self.top_k, self.top_p = N.truncation(top_k, top_p)
+            temperature, seed = float(temperature), int(seed) & (2 ** 64 - 1)
         self.lib = N.lib()
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -218,8 +233,11 @@ class RingGenerator:
                     self.context.data_ptr(), self.context.stride(1), self.batch, residual_channels,
                     self.n_total, self.context_tm.data_ptr(), _stream_ptr(self.device)),
                     "mvn_transpose_context")
-        self.temperature, self.seed = float(temperature), int(seed) & (2 ** 64 - 1)
+        self.temperature, self.seed = temperature, seed
+        self._per_seq = None  # device copy of the mvn_seq_sampling array (per-sequence settings only)
         with torch.cuda.device(self.device):
+            if seq_host is not None:
+                self._per_seq = torch.frombuffer(seq_host, dtype=torch.uint8).to(self.device)
             nw = self.lib.mvn_gen_weights_floats(self.dims, self.variant)
             ns = self.lib.mvn_gen_state_floats(self.dims, self.batch)
             self._queue_floats = self.batch * (self.rf - stack_size) * residual_channels
@@ -287,6 +305,17 @@ class RingGenerator:
 
     def _run(self, t_begin: int, t_end: int, n_given: int, logits_out=None, choices_out=None,
              logits_t0: int = 0) -> None:
+        if self._per_seq is not None:
+            with torch.cuda.device(self.device):
+                N.check(self.lib.mvn_generate_seq(
+                    self.dims, self.variant, self.packed.data_ptr(), self.state.data_ptr(),
+                    self.samples.data_ptr(), self.batch, self.samples.stride(0), self.n_total, n_given,
+                    t_begin, t_end, self._per_seq.data_ptr(),
+                    None if logits_out is None else logits_out.data_ptr(),
+                    None if choices_out is None else choices_out.data_ptr(),
+                    logits_t0, None if self.context_tm is None else self.context_tm.data_ptr(),
+                    self._sampling, _stream_ptr(self.device)), "mvn_generate_seq")
+            return
         with torch.cuda.device(self.device):
             N.check(self.lib.mvn_generate_trunc(
                 self.dims, self.variant, self.packed.data_ptr(), self.state.data_ptr(),
@@ -496,27 +525,42 @@ class GroupedGenerator:
     ``advance``; ``auto_plan`` picks this as long as the groups' step times add up to less than
     one launch of a kernel that holds every sequence (STREAM: 78 us).
     Same interface as ``RingGenerator``; ``samples`` is one (B, n_total) tensor the groups
-    write their row blocks of.  Each group draws from its own Philox key (seed + group)."""
+    write their row blocks of.  Each group draws from its own Philox key (seed + group) -- unless any of
+    ``temperature``, ``seed``, ``top_k``, ``top_p`` is a sequence of ``batch`` values (or ``rows`` is given): each group
+    then receives its slice of the settings with the sequences' own seeds and their GLOBAL rows, and the samples are
+    those of a single launch to the bit."""
 
     def __init__(self, layer_size, stack_size, input_channels, residual_channels, skip_channels,
                  state_dict, batch: int, n_total: int, device, group: int, temperature: float = 0.0,
                  seed: int = 0, context: Optional[torch.Tensor] = None, variant: int = N.GEN_PIPE,
-                 sampling: str = "reference", top_k: int = 0, top_p: float = 1.0):
+                 sampling: str = "reference", top_k: int = 0, top_p: float = 1.0, rows=None):
         N.sampling_rule(sampling)  # ValueError before anything is allocated
         self.sampling = sampling
-        self.top_k, self.top_p = N.truncation(top_k, top_p)  # (the same values for every group)
+        per_seq = None
+        if rows is not None or N.any_per_sequence(temperature, seed, top_k, top_p):
+            host = N.seq_sampling_array(batch, input_channels, temperature, top_k, top_p, seed, rows)
+            per_seq = [host[b] for b in range(int(batch))]
+            self.top_k, self.top_p = [e.top_k for e in per_seq], [e.top_p for e in per_seq]
+        else:
+            self.top_k, self.top_p = N.truncation(top_k, top_p)  # (the same values for every group)
         self.batch, self.n_total, self.device = int(batch), int(n_total), torch.device(device)
         self.variant = variant
         self.samples = torch.zeros(self.batch, self.n_total, dtype=torch.int32, device=self.device)
         self.groups, self.bounds = [], []
         for gi, b0 in enumerate(range(0, self.batch, group)):
             b1 = min(self.batch, b0 + group)
+            if per_seq is not None:
+                mine = per_seq[b0:b1]
+                settings = dict(temperature=[e.temperature for e in mine], seed=[e.seed for e in mine],
+                                top_k=[e.top_k for e in mine], top_p=[e.top_p for e in mine],
+                                rows=[e.row for e in mine])
+            else:
+                settings = dict(temperature=temperature, seed=(int(seed) + 0x9E3779B97F4A7C15 * gi) & (2 ** 64 - 1),
+                                top_k=self.top_k, top_p=self.top_p)
             g = RingGenerator(layer_size, stack_size, input_channels, residual_channels, skip_channels,
                               state_dict, batch=b1 - b0, n_total=n_total, device=device,
-                              variant=variant, temperature=temperature,
-                              seed=(int(seed) + 0x9E3779B97F4A7C15 * gi) & (2 ** 64 - 1),
-                              context=None if context is None else context[b0:b1], sampling=sampling,
-                              top_k=self.top_k, top_p=self.top_p)
+                              variant=variant, context=None if context is None else context[b0:b1],
+                              sampling=sampling, **settings)
             g.samples = self.samples[b0:b1]  # a contiguous row block of the shared tensor
             self.groups.append(g)
             self.bounds.append((b0, b1))

@@ -70,6 +70,13 @@ class Dance2Music(nn.Module):
     def generate(self, audio, video):
         if (self.config.log_samples_every is not None
                 and (self.current_epoch + 1) % self.config.log_samples_every == 0):
+            sweep = list(getattr(self.config, "generate_temperature_sweep", None) or ())
+            if sweep:
+                # every clip once per temperature, clip-major, in ONE generate() call (LogSamplesCallback's layout)
+                n = len(sweep)
+                return self.model.generate(
+                    audio.repeat_interleave(n, dim=0), None if video is None else video.repeat_interleave(n, dim=0),
+                    n_samples=self.config.generate_n_samples, temperature=sweep * audio.shape[0]).detach()
             return self.model.generate(
                 audio, video, n_samples=self.config.generate_n_samples,
                 temperature=self.config.generate_temperature).detach()
@@ -381,7 +388,8 @@ def train_model(dataset: str, config: TrainingConfig, logger_name: Optional[str]
         # the reference attaches this callback only under wandb (:223-229); without wandb the
         # decoded samples go to <model_output_path>/samples/ as .wav files
         from .callbacks import LogSamplesCallback
-        callbacks.append(LogSamplesCallback(log_every_n_epochs=config.log_samples_every, log_video=log_video))
+        callbacks.append(LogSamplesCallback(log_every_n_epochs=config.log_samples_every, log_video=log_video,
+                                            temperature_sweep=getattr(config, "generate_temperature_sweep", None) or ()))
     trainer = Trainer(
         max_epochs=config.n_epochs, default_root_dir=config.model_output_path,
         gradient_clip_val=config.gradient_clipping,

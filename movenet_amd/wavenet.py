@@ -135,6 +135,19 @@ class WaveNet(nn.Module):
     def generate_top_p(self, value: float) -> None:
         self._gen_top_p = N.truncation(0, value)[1]
 
+    # ---- the Philox key(s) of generate() -----------------------------------
+    @property
+    def generate_seed(self):
+        """None (default: every ``generate()`` call draws a key from torch's generator), an int, or a sequence of B
+        ints, one key per sequence of the batch (``generate()`` refuses another length)."""
+        return getattr(self, "_gen_seed", None)  # (a module pickled before the attribute existed)
+
+    @generate_seed.setter
+    def generate_seed(self, value) -> None:
+        if value is not None:
+            N.seq_sampling_array(len(value) if N.any_per_sequence(value) else 1, self.input_channels, 1.0, 0, 1.0, value)
+        self._gen_seed = value
+
     # ---- what forward(..., return_loss=True) minimises --------------------
     @property
     def loss_rule(self) -> str:
@@ -251,9 +264,21 @@ class WaveNet(nn.Module):
 
     @torch.no_grad()
     def generate(self, audio, video=None, global_features=None, n_samples: Optional[int] = None,
-                 temperature: float = 1.0):
+                 temperature=1.0):
         """wavenet.py:193-239: copy the first RF prompt samples, then generate
-        autoregressively up to n_samples (default: the prompt's own length)."""
+        autoregressively up to n_samples (default: the prompt's own length).
+
+        ``temperature`` takes one value or a sequence of B values, one per sequence of the batch (a temperature sweep
+        on one prompt is ONE launch: repeat the prompt), and ``generate_seed`` likewise; with either a sequence,
+        sequence b draws on its own seed and row b whatever the launch plan.  A wrong length or a bad value is a
+        ValueError before anything runs."""
+        top_k, top_p, seed = self.generate_top_k, self.generate_top_p, self.generate_seed
+        per_seq = N.any_per_sequence(temperature, seed)
+        if per_seq:  # (validates lengths and values; the seed drawn below replaces the placeholder)
+            N.seq_sampling_array(int(audio.shape[0]), self.input_channels, temperature, top_k, top_p,
+                                 0 if seed is None else seed)
+        else:
+            temperature = float(temperature)
         self.eval()  # the reference leaves the module in eval mode (SURVEY Q10)
         # BUILD DEFINITION for video != None (the reference fails its size assert there,
         # SURVEY.md Q7): the context column of time t conditions the step that consumes x_t
@@ -268,7 +293,8 @@ class WaveNet(nn.Module):
             n = min(rf, n_total, audio.shape[2])
             out[:, :, :n] = audio[:, :, :n]
             return out
-        seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        if seed is None:
+            seed = int(torch.empty((), dtype=torch.int64).random_().item())
         state = self._decoder_state()
         if context is None:
             state = {k: v for k, v in state.items() if ".context_conv_" not in k}
@@ -276,8 +302,8 @@ class WaveNet(nn.Module):
             raise ValueError(f"the upsampled video covers {context.shape[2]} samples, "
                              f"n_samples={n_total} asked for")
         kw = dict(batch=idx.shape[0], n_total=n_total, device=audio.device,
-                  temperature=float(temperature), seed=seed, context=context,
-                  sampling=self.generate_sampling, top_k=self.generate_top_k, top_p=self.generate_top_p)
+                  temperature=temperature, seed=seed, context=context,
+                  sampling=self.generate_sampling, top_k=top_k, top_p=top_p)
         def run(variant, group):
             if group:
                 gen = GroupedGenerator(self.layer_size, self.stack_size, self.input_channels,
