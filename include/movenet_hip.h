@@ -427,7 +427,63 @@ int mvn_backward_bf16(const mvn_dims *dims, const mvn_params *params, const mvn_
 #define MVN_BWD_FORM_HALVES 2
 #define MVN_BWD_FORM_ONE 3
 #define MVN_BWD_FORM_BF16 4
+#define MVN_BWD_FORM_ONE_GLOBAL 5 /* form 3 with the label's row sums: mvn_backward_global */
 int mvn_last_backward_form(void);
+
+/* ------------------------------------------------------------------------
+ * Global conditioning on a class label (BUILD DEFINITION): sequence b carries a
+ * C-vector e_b that enters every gated layer where local context does, as a column constant in time:
+ *     f_l(b, :, t) += Wcf_l (ctx(b, :, t) + e_b) + bcf_l      (the same for g_l with Wcg_l, bcg_l)
+ * General path (any dims, with or without video): add e_b to the context and run the conditioned
+ * entry points.  For the generators mvn_context_add_global adds global (batch, channels) to every
+ * time row of the (batch, t_len, channels) time-major context_tm; fill != 0 writes the rows
+ * instead (no video: the buffer need not be initialised).
+ * ------------------------------------------------------------------------ */
+int mvn_context_add_global(float *context_tm, const float *global, int batch, int channels, int t_len,
+                           int fill, void *stream);
+
+/* Fast path: residual_channels = skip_channels = 64, fp32, no video.  The label's term of a layer
+ * is ONE 2C-vector per sequence, so no layer runs a context product:
+ *   mvn_global_bias           gbias (L, batch, 128) = [Wcf_l e_b + bcf_l | Wcg_l e_b + bcg_l], e (batch, 64)
+ *   mvn_forward_global        mvn_forward with buf->ctx == NULL; the layers add gbias[l][b] to their
+ *                             filter / gate pre-activations in front of tanh / sigmoid
+ *   mvn_backward_global       mvn_backward for such a forward.  scratch: mvn_global_scratch_floats() floats
+ *                             (the layer kernel's second pair of gradient tensors, its weight-gradient
+ *                             slabs and bias partials; scratch_floats says how many there are);
+ *                             rowsum (L, batch, 128) receives sum_t (df | dg)(b, :, t) of every layer
+ *                             (zero it first: a call without output columns launches nothing)
+ *   mvn_global_bias_backward  grads->ctx_filter_w / _b / ctx_gate_w / _b of every layer are WRITTEN with
+ *                             sum_b rowsum (x) e_b and sum_b rowsum; de (batch, 64) = sum_l Wcf_l^T r_f +
+ *                             Wcg_l^T r_g
+ * General path: mvn_backward_scratch is mvn_backward (same arguments, same results, fwd->ctx the context
+ * the label has joined) with the conditioned layers' one-kernel form taking its second pair of gradient
+ * tensors, slabs and bias partials from `scratch` (mvn_global_scratch_floats() floats) instead of dlogit /
+ * da1, which are too small for them at short outputs and small Q: MVN_BWD_FORM_ONE wherever the switches
+ * allow it.  Without a context, or with a scratch too small, it is mvn_backward.
+ * mvn_global_fast_path: 1 when mvn_forward_global and mvn_backward_global run this batch / length
+ * under the process's MOVENET_HIP_* switches, else 0 (take the general path); the two refuse with
+ * MVN_ERR_UNSUPPORTED, before anything is launched, exactly where it returns 0.
+ * mvn_last_backward_form() reports MVN_BWD_FORM_ONE_GLOBAL after mvn_backward_global. */
+int mvn_global_fast_path(const mvn_dims *dims, int batch, int t_len);
+int mvn_global_bias(const mvn_dims *dims, const mvn_params *params, const float *e, int batch,
+                    float *gbias, void *stream);
+int mvn_forward_global(const mvn_dims *dims, const mvn_params *params, const int32_t *index,
+                       int index_stride, int batch, int t_len, const mvn_fwd_buffers *buf, float *out,
+                       int normalize, int remove_last, int save, const float *gbias, void *stream);
+int mvn_backward_global(const mvn_dims *dims, const mvn_params *params, const mvn_param_grads *grads,
+                        const int32_t *index, int index_stride, int batch, int t_len,
+                        const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
+                        const float *dout, int normalize, int remove_last, float *scratch,
+                        size_t scratch_floats, float *rowsum, void *stream);
+int mvn_backward_scratch(const mvn_dims *dims, const mvn_params *params, const mvn_param_grads *grads,
+                         const int32_t *index, int index_stride, int batch, int t_len,
+                         const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
+                         const float *dout, int normalize, int remove_last, float *scratch,
+                         size_t scratch_floats, void *stream);
+size_t mvn_global_scratch_floats(const mvn_dims *dims, int batch, int t_len);
+int mvn_global_bias_backward(const mvn_dims *dims, const mvn_params *params,
+                             const mvn_param_grads *grads, const float *rowsum, const float *e,
+                             int batch, float *de, void *stream);
 
 /* ------------------------------------------------------------------------
  * Local conditioning: video encoder + learned upsampler (movenet/wavenet.py:94-118,

@@ -75,7 +75,9 @@ class LogSamplesCallback:
         root = self.out_dir or (Path(trainer.root) / "samples" if trainer.root is not None else None)
         if root is None:
             return
-        audio, _, _, fps, _infos = batch
+        audio, _, contexts, fps, _infos = batch
+        # (a model with global classes was given each clip's own label; the row says which)
+        labelled = bool(getattr(pl_module, "global_classes", None))
         Q = pl_module.config.model_config.input_channels
         origin = self._decode(audio.to(outputs["output"].device), Q)
         pred = self._decode(outputs["output"], Q)
@@ -104,6 +106,10 @@ class LogSamplesCallback:
                 write_wav(files["gen_audio"], gen[i])
             rows.append({"split": split, "epoch": trainer.current_epoch, "batch_idx": batch_idx, "fp": fp,
                          **{k: str(v.relative_to(root)) for k, v in files.items()}})
+        if labelled:
+            where = {str(fp): str(c) for fp, c in zip(fps, contexts)}
+            for r in rows:
+                r["context"] = where[str(r["fp"])]
         with open(root / "index.jsonl", "a") as f:
             for r in rows:
                 f.write(json.dumps(r) + "\n")

@@ -67,6 +67,11 @@ class TrainingConfig:
     # --generate_sampling model draws from).  Not a reference field: a JSON written without it loads with the default.
     loss_rule: str = "reference"
 
+    # global conditioning on the clip's class label (WaveNet(global_classes=...)): the sorted context folders
+    # of the training set are the classes and every batch's context names go to forward() as global_features.  Not a
+    # reference field: a JSON written without it loads with the default (off).
+    use_global: bool = False
+
     scheduler: Optional[str] = "OneCycleLR"
     lr_pct_start: float = 0.45
     base_learning_rate: float = 0.0003
@@ -153,6 +158,7 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--n_epochs", type=int, default=10)
     a("--n_steps_per_epoch", type=int, default=None)
     a("--use_video", type=_flag, default=True)
+    a("--use_global", type=_flag, default=False)
     a("--batch_subsample_frac", type=float, default=None)
     a("--val_batch_subsample_frac", type=float, default=None)
     a("--gradient_clipping", type=float, default=0.0)
@@ -193,7 +199,7 @@ def config_from_args(args) -> TrainingConfig:
         "scheduler_cyclic_mode scheduler_cyclic_gamma scheduler_cycle_momentum max_learning_rate "
         "scheduler_step_size scheduler_step_gamma scheduler_milestones weight_decay "
         "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule accumulation_steps num_workers val_num_workers "
-        "pin_memory n_epochs n_steps_per_epoch use_video batch_subsample_frac "
+        "pin_memory n_epochs n_steps_per_epoch use_video use_global batch_subsample_frac "
         "val_batch_subsample_frac dist_backend dist_port model_output_path log_samples_every"
     ).split()
     kw = {k: getattr(args, k) for k in copied}  # NB: gradient_clipping is not among them (Q11)

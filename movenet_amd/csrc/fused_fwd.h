@@ -38,6 +38,7 @@ struct FusedFwdPArgs {
   const float *wcf = nullptr, *wcg = nullptr, *bcf = nullptr, *bcg = nullptr;  // (64, 64), (64)
   Act ctx = Act{nullptr, 0, 0};
   const float *wpack = nullptr;  // fused_fwd_bf3.h: the layer's LDS image, written once per forward call (or NULL)
+  const float *gbias = nullptr;  // global conditioning (fused_layer64s_bf3_kernel<true>): (batch, 128) f | g bias of this layer
 };
 
 // 32-column tiles, 256 threads, TWO workgroups per CU (65 KB of LDS each) whose phases run under each

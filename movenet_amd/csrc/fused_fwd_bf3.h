@@ -155,6 +155,11 @@ __global__ __launch_bounds__(256) void fs3_pack_kernel(Fs3PackArgs p, float *dst
                     blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
 }
 
+// GLOBAL (global conditioning): a label is constant in time, so its context term is ONE 2C-vector per
+// (layer, sequence), gbias = [Wcf e_b + bcf | Wcg e_b + bcg] (global_cond.h: global_bias_kernel); the instantiation
+// keeps it in 128 floats of LDS behind br | bs and adds it to the f | g pre-activations in front of tanh / sigmoid.
+// GLOBAL = false is the audio-only kernel as it was: every added line sits under `if constexpr (GLOBAL)`.
+template <bool GLOBAL>
 __global__ __launch_bounds__(512, 1) void fused_layer64s_bf3_kernel(FusedFwdPArgs a, int chunks_per_b, int chunk_t) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fs3_lds[];
   unsigned short *W1 = (unsigned short *)fs3_lds;                     // [4 blocks][8 k-steps][3 planes][64 lanes][8]
@@ -186,6 +191,9 @@ __global__ __launch_bounds__(512, 1) void fused_layer64s_bf3_kernel(FusedFwdPArg
     }
   } else {
     fs3_stage_weights(fs3_lds, a.wf, a.wg, a.wr, a.ws, a.br, a.bs, tid, 512);
+  }
+  if constexpr (GLOBAL) {
+    if (tid < 128) BI[128 + tid] = a.gbias[(size_t)b * 128 + tid];  // (f rows | g rows of this sequence)
   }
   __syncthreads();
   const unsigned w1a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)fs3_lds + 16u * lane;
@@ -278,10 +286,15 @@ __global__ __launch_bounds__(512, 1) void fused_layer64s_bf3_kernel(FusedFwdPArg
     for (int h = 0; h < 2; ++h)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float tv = tanh_fast(acc[h][r]);
-        const float sv = sigmoid_fast(acc[2 + h][r]);
-        z[16 * h + r] = tv * sv;
         const int c0 = 32 * h + (r & 3) + 8 * (r >> 2);
+        float fv = acc[h][r], gv = acc[2 + h][r];
+        if constexpr (GLOBAL) {
+          fv += BI[128 + c0 + cbase];
+          gv += BI[192 + c0 + cbase];
+        }
+        const float tv = tanh_fast(fv);
+        const float sv = sigmoid_fast(gv);
+        z[16 * h + r] = tv * sv;
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(tv), thb, oth, c0 * thld4, FS_AUX_SAVE);
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sv), sgb, oth, c0 * thld4, FS_AUX_SAVE);
       }
@@ -861,10 +874,18 @@ static int launch_fused_layer64s_bf3(const FusedFwdPArgs &a, int batch, hipStrea
   if (a.t_end <= a.t_begin || batch <= 0) return MVN_OK;
   int chunks, chunk_t;
   fb_chunks(nt, batch, 1, &chunks, &chunk_t, 256);  // a chunk: whole rounds of the 8 waves' strips
-  const void *fn = (const void *)fused_layer64s_bf3_kernel;
+  if (a.gbias) {  // global conditioning: 128 more floats of LDS hold the sequence's bias vector
+    const void *fn = (const void *)fused_layer64s_bf3_kernel<true>;
+    const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(fused_layer64s_bf3<global>)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(fused_layer64s_bf3_kernel<true>, dim3(chunks * batch), dim3(512), FS3_LDS_BYTES + 128 * 4, s, a, chunks,
+                       chunk_t);
+    return MVN_OK;
+  }
+  const void *fn = (const void *)fused_layer64s_bf3_kernel<false>;
   const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(fused_layer64s_bf3)");
   if (rc) return rc;
-  hipLaunchKernelGGL(fused_layer64s_bf3_kernel, dim3(chunks * batch), dim3(512), FS3_LDS_BYTES, s, a, chunks, chunk_t);
+  hipLaunchKernelGGL(fused_layer64s_bf3_kernel<false>, dim3(chunks * batch), dim3(512), FS3_LDS_BYTES, s, a, chunks, chunk_t);
   return MVN_OK;
 }
 

@@ -31,6 +31,7 @@
 #include "fused_fwd_bf3.h"
 #include "fused_bwd_l.h"
 #include "fused_bf16.h"
+#include "global_cond.h"
 
 namespace mvn {
 
@@ -1076,13 +1077,46 @@ static int head_bwd1_bf3(const DenseStripArgs &da, const mvn_params *p, int Kc, 
   (Q == 256 ? call_<256> : Q == 128 ? call_<128> : call_<64>)
 static bool head_q_strip(int Q) { return Q == 256 || Q == 128 || Q == 64; }
 
+// Global conditioning, fast path (global_cond.h): what the forward's strip kernel and the backward's scatter form need.
+// Decided from the dims, the switches and the sizes of the caller's buffers alone, so that mvn_global_fast_path can
+// answer before anything is allocated; anything else takes the general path (the label as a constant context).
+static bool global_forward_fast(const Geometry &g) {
+  return g.C == FP_C && g.Kc == FP_C && !switches().no_fused_forward && forward_bf3_enabled() && !switches().forward_tile &&
+         g.Tp <= (1 << 22) && g.Sp <= (1 << 22);
+}
+static bool global_backward_fast(const mvn_dims *dims, const Geometry &g, int batch) {
+  if (g.C != 64 || g.Kc != 64 || switches().no_fused_backward || switches().bwd_split || !rows_fit_rsrc(2 * g.C, g.Tp) ||
+      g.L >= 4095 || g.Tp > (1 << 21))
+    return false;
+  // (the layer kernel's slabs and bias partials live in the caller's scratch, mvn_global_scratch_floats: the path does
+  // not depend on what the (B, Q, Sp) da1 tensor happens to hold -- short outputs and small Q take it too)
+  return batch >= 1;
+}
+constexpr size_t GC_PER_WG = 128 * 64 + 128 * 128 + 128;  // a workgroup's two slabs and its bias partials
+static size_t global_scratch_floats(const mvn_dims *dims, const Geometry &g, int batch) {
+  // workgroups per sequence of the layer kernel (one per CU) and of the conditioned layers' context pass (two per CU):
+  // never more than the tiles of the longest layer, nor than the kernels' chunk counts at any layer (fb_chunks)
+  const int t_lo = dilation_of(dims, 0), nt = std::max(1, g.T - (t_lo & ~TILE_ALIGN));
+  const int tiles = (nt + W2_T - 1) / W2_T;
+  const int want = std::max(1, 2 * fb_device_cus() / std::max(batch, 1));
+  return 2 * (size_t)g.act + (size_t)std::max(1, std::min(tiles, want)) * batch * GC_PER_WG;
+}
+static void global_cond_tables(const mvn_params *p, int l0, int n, GlobalCondArgs *ga) {
+  for (int i = 0; i < GC_LAYERS; ++i) {
+    const int l = l0 + std::min(i, n - 1);
+    ga->wcf[i] = p->ctx_filter_w[l]; ga->wcg[i] = p->ctx_gate_w[l];
+    ga->bcf[i] = p->ctx_filter_b[l]; ga->bcg[i] = p->ctx_gate_b[l];
+  }
+}
+
 extern "C" {
 
 int mvn_padded_len(int n) { return n <= 0 ? 0 : (n + 63) / 64 * 64; }
 
 static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t *index, int index_stride,
                         int batch, int t_len, const mvn_fwd_buffers *buf, float *out, int normalize,
-                        int remove_last, int save, void *stream_, bool f16, bool bf16 = false) {
+                        int remove_last, int save, void *stream_, bool f16, bool bf16 = false,
+                        const float *gbias = nullptr) {
   Geometry g;
   int rc = make_geometry(dims, batch, t_len, g);
   if (rc) return rc;
@@ -1105,6 +1139,11 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
   if (buf->ctx && (!p->ctx_filter_w || !p->ctx_filter_b || !p->ctx_gate_w || !p->ctx_gate_b || buf->ctx_ld < t_len)) {
     set_error("mvn_forward: context given without context-conv parameters / ctx_ld < t_len");
     return MVN_ERR_BAD_ARG;
+  }
+  if (gbias && (buf->ctx || !global_forward_fast(g))) {
+    set_error("mvn_forward_global: needs residual = skip channels = 64, no context and the bf16 x 3 strip kernel "
+              "(mvn_global_fast_path)");
+    return MVN_ERR_UNSUPPORTED;
   }
   if (batch == 0) return MVN_OK;
   hipStream_t s = (hipStream_t)stream_;
@@ -1188,6 +1227,7 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
       if (l == g.L - 1) fp.xout.p = nullptr;  // the last residual output is never used
       fp.th = act_view(save ? buf->th + (size_t)l * g.act : nullptr, batch, C, g.Tp);
       fp.sg = act_view(save ? buf->sg + (size_t)l * g.act : nullptr, batch, C, g.Tp);
+      if (gbias) fp.gbias = gbias + (size_t)l * batch * 128;  // (global conditioning: the instantiation with the bias add)
       // audio-only layers: the strip kernel on the bf16 matrix cores (fp32 = 3 bf16 planes, fused_fwd_bf3.h)
       // unless a tile form / the fp32-MFMA strip was asked for, or the rows are longer than a buffer resource spans
       const bool bf3 = !fp.ctx.p && forward_bf3_enabled() && !switches().forward_tile &&
@@ -1328,7 +1368,14 @@ int mvn_last_backward_form(void) { return g_last_bwd_form; }
 static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
                          const int32_t *index, int index_stride, int batch, int t_len,
                          const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
-                         const float *dout, int normalize, int remove_last, void *stream_, bool bf16) {
+                         const float *dout, int normalize, int remove_last, void *stream_, bool bf16,
+                         float *gpair = nullptr, size_t gpair_floats = 0, float *grow = nullptr) {
+  // gpair (mvn_backward_global, mvn_backward_scratch): the caller's scratch for the one-kernel layer backward -- fast path (grow given) and
+  // conditioned layers (fwd->ctx: the label has joined the context) alike; without it the conditioned layers look for
+  // that room in dlogit / da1 and take another form where those are too small (short outputs, small Q).
+  // gpair / grow: the second pair of (B, C, Tp) scatter tensors -- the layer kernel writes
+  // df | dg into the dfg tensor here -- and the (L, B, 2C) row sums of df | dg
+  const bool glob = grow != nullptr;
   Geometry g;
   int rc = make_geometry(dims, batch, t_len, g);
   if (rc) return rc;
@@ -1417,6 +1464,12 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
     }
   }
   const bool has_ctx = fwd->ctx != nullptr;
+  if (glob && (!gpair || has_ctx || bf16 || !global_backward_fast(dims, g, batch) ||
+               gpair_floats < 2 * (size_t)g.act + (size_t)batch * GC_PER_WG)) {
+    set_error("mvn_backward_global: needs the one-kernel layer backward at residual = skip channels = 64 without context "
+              "(mvn_global_fast_path)");
+    return MVN_ERR_UNSUPPORTED;
+  }
   if (has_ctx && (!bwd->dctx || !gr->ctx_filter_w || !gr->ctx_filter_b || !gr->ctx_gate_w ||
                   !gr->ctx_gate_b || !p->ctx_filter_w || !p->ctx_gate_w)) {
     set_error("mvn_backward: context given without dctx buffer / context-conv gradients");
@@ -1426,7 +1479,14 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
   // the workgroups that fit: the plan takes fewer, longer chunks then)
   float *sc_bias = bias_scratch2, *sc_slab = slab;
   size_t sc_bias_floats = bias2_floats, sc_slab_floats = slab_floats;
-  if (!sc_bias && !has_ctx && slab) {
+  const bool ext = gpair && (glob || has_ctx) && !bf16 && gpair_floats >= 2 * (size_t)g.act + (size_t)batch * GC_PER_WG;
+  if (ext) {  // the caller's scratch: the second scatter pair, then the slabs, then the bias partials
+    const size_t n_fit = (gpair_floats - 2 * (size_t)g.act) / GC_PER_WG;
+    sc_slab = gpair + 2 * (size_t)g.act;
+    sc_slab_floats = n_fit * (GC_PER_WG - 128);
+    sc_bias = sc_slab + sc_slab_floats;
+    sc_bias_floats = n_fit * 128;
+  } else if (!sc_bias && !has_ctx && slab) {
     const size_t total = (size_t)batch * Q * g.Sp, n_fit = total / (128 * 64 + 128 * 128 + 128);
     if (n_fit >= (size_t)batch) {
       sc_bias_floats = n_fit * 128;
@@ -1568,7 +1628,10 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
     spair[0][0] = act_view(bwd->dx_a, batch, C, g.Tp);
     spair[0][1] = act_view(bwd->dx_b, batch, C, g.Tp);
     bool have = true;
-    if (!has_ctx) {
+    if (ext) {
+      spair[1][0] = act_view(gpair, batch, C, g.Tp);
+      spair[1][1] = act_view(gpair + (size_t)g.act, batch, C, g.Tp);
+    } else if (!has_ctx) {
       spair[1][0] = Act{bwd->dfg, (long long)2 * C * g.Tp, g.Tp};
       spair[1][1] = Act{bwd->dfg + (size_t)C * g.Tp, (long long)2 * C * g.Tp, g.Tp};
     } else if (2 * g.act <= g.hid) {
@@ -1580,13 +1643,17 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
     FusedBwdLPlan pl0;
     int cc = 0, cct = 0;
     scatter = have && bwd_layer64_plan(A_lo[1], T, batch, sc_bias, sc_bias_floats, sc_slab, sc_slab_floats, &pl0) &&
-              (!has_ctx || bwd_dctx_wgctx64_fits(A_lo[1], T, batch, bias_scratch2, bias2_floats, slab, slab_floats, &cc, &cct));
+              (!has_ctx || bwd_dctx_wgctx64_fits(A_lo[1], T, batch, sc_bias, sc_bias_floats, sc_slab, sc_slab_floats, &cc, &cct));
   }
   if (bf16 && !scatter) {
     set_error("mvn_backward_bf16: the bf16 layer kernels cannot run these buffers");
     return MVN_ERR_UNSUPPORTED;
   }
-  g_last_bwd_form = bf16 ? MVN_BWD_FORM_BF16 : scatter ? MVN_BWD_FORM_ONE : MVN_BWD_FORM_GENERIC;
+  if (glob && !scatter) {
+    set_error("mvn_backward_global: the one-kernel layer backward cannot run these buffers");
+    return MVN_ERR_UNSUPPORTED;
+  }
+  g_last_bwd_form = bf16 ? MVN_BWD_FORM_BF16 : glob ? MVN_BWD_FORM_ONE_GLOBAL : scatter ? MVN_BWD_FORM_ONE : MVN_BWD_FORM_GENERIC;
   if (scatter) {
     int po = 1 ^ ((g.L - 1) & 1);  // (so that layer 0 writes pair 1 and the dense dx0 can go to dx_a)
     for (int l = g.L - 1; l >= 0; --l) {
@@ -1603,7 +1670,7 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
       fa.sg = act_view(fwd->sg + (size_t)l * g.act, batch, C, g.Tp);
       fa.xin = act_view(fwd->acts + (size_t)l * g.act, batch, C, g.Tp);
       fa.oa = spair[po][0]; fa.op = spair[po][1];
-      fa.dfg = has_ctx ? dfg : Act{nullptr, 0, 0};
+      fa.dfg = (has_ctx || glob) ? dfg : Act{nullptr, 0, 0};
       WgRsOp wr;
       wr.t_begin = t_lo; wr.t_end = T; wr.C = C; wr.Kc = Kc; wr.t_skip0 = t_skip0; wr.t_base = g.t_base;
       wr.dxo = fa.ga; wr.dskip = dskip; wr.th = fa.th; wr.sg = fa.sg;
@@ -1619,9 +1686,12 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
       }
       rc = bf16 ? launch_bwd_layer64_bf16(fa, wr, wf, batch, pl, s) : launch_bwd_layer64(fa, wr, wf, batch, pl, s);
       if (rc) return rc;
+      if (glob)  // the label's term: row sums of df | dg over the layer's valid columns (global_cond.h)
+        hipLaunchKernelGGL(global_rowsum_kernel, dim3(32, batch), dim3(256), 0, s, bwd->dfg, (long long)2 * C * g.Tp, g.Tp,
+                           t_lo, T, grow + (size_t)l * batch * 128);
       if (has_ctx) {  // (behind the layer's reduce: the slab scratch is free again)
         int c_chunks = 0, c_chunk_t = 0;
-        if (!bwd_dctx_wgctx64_fits(t_lo, T, batch, bias_scratch2, bias2_floats, slab, slab_floats, &c_chunks, &c_chunk_t)) {
+        if (!bwd_dctx_wgctx64_fits(t_lo, T, batch, sc_bias, sc_bias_floats, sc_slab, sc_slab_floats, &c_chunks, &c_chunk_t)) {
           set_error("mvn_backward: the context pass lost its scratch at layer %d", l);
           return MVN_ERR_BAD_ARG;
         }
@@ -1630,7 +1700,7 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
         fc.dfg = dfg; fc.ctx = ctxv; fc.dctx = dctxv;
         WgCtxOp co;
         co.dwcf = gr->ctx_filter_w[l]; co.dwcg = gr->ctx_gate_w[l]; co.dbcf = gr->ctx_filter_b[l]; co.dbcg = gr->ctx_gate_b[l];
-        launch_bwd_dctx_wgctx64(fc, co, batch, bias_scratch2, slab, c_chunks, c_chunk_t, s);
+        launch_bwd_dctx_wgctx64(fc, co, batch, sc_bias, sc_slab, c_chunks, c_chunk_t, s);
       }
       po ^= 1;
     }
@@ -1818,6 +1888,124 @@ int mvn_backward_bf16(const mvn_dims *dims, const mvn_params *p, const mvn_param
                       const float *dout, int normalize, int remove_last, void *stream_) {
   return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_,
                        true);
+}
+
+int mvn_global_fast_path(const mvn_dims *dims, int batch, int t_len) {
+  Geometry g;
+  if (make_geometry(dims, batch, t_len, g) || batch < 1) return 0;
+  return global_forward_fast(g) && global_backward_fast(dims, g, batch) ? 1 : 0;
+}
+
+int mvn_global_bias(const mvn_dims *dims, const mvn_params *p, const float *e, int batch, float *gbias, void *stream_) {
+  int rc = validate_dims(dims);
+  if (rc) return rc;
+  if (dims->residual_channels != 64) {
+    set_error("mvn_global_bias: residual_channels = 64 only (got %d)", dims->residual_channels);
+    return MVN_ERR_UNSUPPORTED;
+  }
+  if (!p || !p->ctx_filter_w || !p->ctx_filter_b || !p->ctx_gate_w || !p->ctx_gate_b || !e || !gbias || batch < 0 ||
+      batch > 65535) {
+    set_error("mvn_global_bias: bad argument");
+    return MVN_ERR_BAD_ARG;
+  }
+  if (batch == 0) return MVN_OK;
+  const int L = n_layers(dims);
+  for (int l0 = 0; l0 < L; l0 += GC_LAYERS) {
+    const int n = std::min(GC_LAYERS, L - l0);
+    GlobalCondArgs ga;
+    global_cond_tables(p, l0, n, &ga);
+    hipLaunchKernelGGL(global_bias_kernel, dim3(batch, n), dim3(128), 0, (hipStream_t)stream_, ga, e,
+                       gbias + (size_t)l0 * batch * 128, batch);
+  }
+  return check_hip(hipGetLastError(), "mvn_global_bias");
+}
+
+int mvn_global_bias_backward(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr, const float *rowsum,
+                             const float *e, int batch, float *de, void *stream_) {
+  int rc = validate_dims(dims);
+  if (rc) return rc;
+  if (dims->residual_channels != 64) {
+    set_error("mvn_global_bias_backward: residual_channels = 64 only (got %d)", dims->residual_channels);
+    return MVN_ERR_UNSUPPORTED;
+  }
+  if (!p || !p->ctx_filter_w || !p->ctx_gate_w || !p->ctx_filter_b || !p->ctx_gate_b || !gr || !gr->ctx_filter_w || !gr->ctx_filter_b || !gr->ctx_gate_w ||
+      !gr->ctx_gate_b || !rowsum || !e || !de || batch < 0 || batch > 65535) {
+    set_error("mvn_global_bias_backward: bad argument");
+    return MVN_ERR_BAD_ARG;
+  }
+  if (batch == 0) return MVN_OK;
+  const int L = n_layers(dims);
+  for (int l0 = 0; l0 < L; l0 += GC_LAYERS) {
+    const int n = std::min(GC_LAYERS, L - l0);
+    GlobalCondArgs ga;
+    GlobalCondGrads gg;
+    global_cond_tables(p, l0, n, &ga);  // (the kernel reads the weights only)
+    for (int i = 0; i < GC_LAYERS; ++i) {
+      const int l = l0 + std::min(i, n - 1);
+      gg.dwcf[i] = gr->ctx_filter_w[l]; gg.dwcg[i] = gr->ctx_gate_w[l];
+      gg.dbcf[i] = gr->ctx_filter_b[l]; gg.dbcg[i] = gr->ctx_gate_b[l];
+    }
+    hipLaunchKernelGGL(global_bias_backward_kernel, dim3(n + batch), dim3(256), 0, (hipStream_t)stream_, ga, gg,
+                       rowsum + (size_t)l0 * batch * 128, e, de, n, batch, l0 > 0 ? 1 : 0);
+  }
+  return check_hip(hipGetLastError(), "mvn_global_bias_backward");
+}
+
+int mvn_forward_global(const mvn_dims *dims, const mvn_params *p, const int32_t *index, int index_stride,
+                       int batch, int t_len, const mvn_fwd_buffers *buf, float *out, int normalize,
+                       int remove_last, int save, const float *gbias, void *stream_) {
+  if (!gbias) {
+    set_error("mvn_forward_global: gbias is NULL");
+    return MVN_ERR_BAD_ARG;
+  }
+  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_,
+                      false, false, gbias);
+}
+
+int mvn_backward_global(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
+                        const int32_t *index, int index_stride, int batch, int t_len,
+                        const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
+                        const float *dout, int normalize, int remove_last, float *scratch, size_t scratch_floats,
+                        float *rowsum, void *stream_) {
+  if (!scratch || !rowsum) {
+    set_error("mvn_backward_global: scratch / rowsum is NULL");
+    return MVN_ERR_BAD_ARG;
+  }
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_,
+                       false, scratch, scratch_floats, rowsum);
+}
+
+int mvn_backward_scratch(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
+                         const int32_t *index, int index_stride, int batch, int t_len,
+                         const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
+                         const float *dout, int normalize, int remove_last, float *scratch, size_t scratch_floats,
+                         void *stream_) {
+  if (!scratch) {
+    set_error("mvn_backward_scratch: scratch is NULL");
+    return MVN_ERR_BAD_ARG;
+  }
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_,
+                       false, scratch, scratch_floats, nullptr);
+}
+
+size_t mvn_global_scratch_floats(const mvn_dims *dims, int batch, int t_len) {
+  Geometry g;
+  if (make_geometry(dims, batch, t_len, g) || batch < 1) return 0;
+  return global_scratch_floats(dims, g, batch);
+}
+
+int mvn_context_add_global(float *context_tm, const float *global, int batch, int channels, int t_len, int fill,
+                           void *stream_) {
+  if (!context_tm || !global || batch < 0 || batch > 65535 || channels < 1 || t_len < 1) {
+    set_error("mvn_context_add_global: bad argument");
+    return MVN_ERR_BAD_ARG;
+  }
+  if (batch == 0) return MVN_OK;
+  const long long per_seq = (long long)t_len * channels;
+  const unsigned blocks = (unsigned)std::min<long long>((per_seq + 255) / 256, 2048);
+  hipLaunchKernelGGL(context_add_global_kernel, dim3(blocks, batch), dim3(256), 0, (hipStream_t)stream_, context_tm, global,
+                     channels, per_seq, fill ? 1 : 0);
+  return check_hip(hipGetLastError(), "mvn_context_add_global");
 }
 
 int mvn_gen_prime_from_forward(const mvn_dims *dims, const mvn_fwd_buffers *fwd, int batch,

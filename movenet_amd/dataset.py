@@ -84,6 +84,7 @@ class SyntheticLoader:
                              "(the reference crops audio and video independently, dataset.py:232-242, "
                              "which its own size assert then rejects)")
         self.epoch = 0
+        self.contexts = ["synthetic"]  # (the one context name every synthetic clip reports)
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = epoch
@@ -308,8 +309,7 @@ class WavFolderLoader:
                              "which its own size assert then rejects)")
         if input_channels > 32768:
             raise ValueError("input_channels above 32768 do not fit the int16 index cache")
-        self.contexts = sorted(p.name for p in self.root_path.glob("*") if p.is_dir()) \
-            if self.root_path.is_dir() else []
+        self.contexts = _context_folders(self.root_path)
         self.index = []  # (context, path, header)
         for context in self.contexts:
             for fp in sorted((self.root_path / context).glob("*.wav")):
@@ -417,6 +417,23 @@ def _is_wav_folder(filepath) -> bool:
     import os
     p = str(filepath)
     return os.path.isdir(p) and (os.path.isdir(os.path.join(p, "train")) or os.path.isdir(os.path.join(p, "valid")))
+
+
+def _context_folders(split_path) -> List[str]:
+    """Sorted names of the <context> folders below one split of a WAV tree (no file is opened)."""
+    from pathlib import Path
+    split_path = Path(split_path)
+    return sorted(p.name for p in split_path.glob("*") if p.is_dir()) if split_path.is_dir() else []
+
+
+def training_contexts(filepath) -> List[str]:
+    """The context names of a source's TRAINING split, sorted -- the class map of ``--use_global`` -- without building
+    a loader: the <context> folders of ``<dir>/train``, or the one name every synthetic clip reports."""
+    import os
+    if not str(filepath).startswith("synthetic://") and _is_wav_folder(filepath):
+        return _context_folders(os.path.join(str(filepath), "train"))
+    parse_synthetic(str(filepath))  # (ValueError for a source that is neither)
+    return ["synthetic"]
 
 
 def get_dataloader(filepath, input_channels: int, batch_size: int = 64, train: bool = True,

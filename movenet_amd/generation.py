@@ -179,8 +179,12 @@ class RingGenerator:
                  batch: int, n_total: int, device, variant: int = N.GEN_AUTO,
                  temperature: float = 0.0, seed: int = 0,
                  context: Optional[torch.Tensor] = None, sampling: str = "reference", top_k: int = 0,
-                 top_p: float = 1.0, rows=None):
-        """``sampling``: what a sampled step (temperature > 0) draws from -- "reference": the reference's
+                 top_p: float = 1.0, rows=None, global_context: Optional[torch.Tensor] = None):
+        """``global_context``: (batch, C) fp32 on the device, one vector per sequence that conditions every step (global
+        conditioning): added to every time row of the time-major context copy the kernels read
+        (mvn_context_add_global); without ``context`` the copy is filled with it.  ``state_dict`` must then hold the
+        layers' context convs.
+        ``sampling``: what a sampled step (temperature > 0) draws from -- "reference": the reference's
         softmax(softmax(logits) / T), close to uniform whatever the model predicts; "model": the model's own
         softmax(logits / T).  Greedy decoding (temperature <= 0) is the same under both.
         ``top_k`` / ``top_p``: truncation of a sampled step before the draw (include/movenet_hip.h,
@@ -233,6 +237,20 @@ class RingGenerator:
                     self.context.data_ptr(), self.context.stride(1), self.batch, residual_channels,
                     self.n_total, self.context_tm.data_ptr(), _stream_ptr(self.device)),
                     "mvn_transpose_context")
+        self.global_context = None
+        if global_context is not None:
+            _require_gpu(global_context, "global_context")
+            if tuple(global_context.shape) != (batch, residual_channels):
+                raise ValueError(f"global_context must be (batch, {residual_channels}), got {tuple(global_context.shape)}")
+            self.global_context = global_context.detach().to(torch.float32).contiguous()
+            with torch.cuda.device(self.device):
+                fill = self.context_tm is None
+                if fill:
+                    self.context_tm = torch.empty(self.batch, self.n_total, residual_channels,
+                                                  dtype=torch.float32, device=self.device)
+                N.check(self.lib.mvn_context_add_global(
+                    self.context_tm.data_ptr(), self.global_context.data_ptr(), self.batch, residual_channels,
+                    self.n_total, int(fill), _stream_ptr(self.device)), "mvn_context_add_global")
         self.temperature, self.seed = temperature, seed
         self._per_seq = None  # device copy of the mvn_seq_sampling array (per-sequence settings only)
         with torch.cuda.device(self.device):
@@ -344,6 +362,9 @@ class RingGenerator:
             from .ops import run_forward
             idx = self.samples[:, :P].contiguous()
             ctx = None if self.context is None else self.context[:, :, :P]
+            if self.global_context is not None:  # (the prompt's columns only: the steps read the time-major copy)
+                g = self.global_context[:, :, None]
+                ctx = g.expand(-1, -1, P) if ctx is None else ctx + g
             _, buf = run_forward(self.dims, self._sd, idx, False, False, save=True, ctx=ctx,
                                  f16=self.variant == N.GEN_PIPE_F16)
             with torch.cuda.device(self.device):
@@ -533,7 +554,8 @@ class GroupedGenerator:
     def __init__(self, layer_size, stack_size, input_channels, residual_channels, skip_channels,
                  state_dict, batch: int, n_total: int, device, group: int, temperature: float = 0.0,
                  seed: int = 0, context: Optional[torch.Tensor] = None, variant: int = N.GEN_PIPE,
-                 sampling: str = "reference", top_k: int = 0, top_p: float = 1.0, rows=None):
+                 sampling: str = "reference", top_k: int = 0, top_p: float = 1.0, rows=None,
+                 global_context: Optional[torch.Tensor] = None):
         N.sampling_rule(sampling)  # ValueError before anything is allocated
         self.sampling = sampling
         per_seq = None
@@ -560,6 +582,7 @@ class GroupedGenerator:
             g = RingGenerator(layer_size, stack_size, input_channels, residual_channels, skip_channels,
                               state_dict, batch=b1 - b0, n_total=n_total, device=device,
                               variant=variant, context=None if context is None else context[b0:b1],
+                              global_context=None if global_context is None else global_context[b0:b1],
                               sampling=sampling, **settings)
             g.samples = self.samples[b0:b1]  # a contiguous row block of the shared tensor
             self.groups.append(g)

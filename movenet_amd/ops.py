@@ -101,11 +101,13 @@ class ForwardBuffers:
 
 def run_forward(dims: N.Dims, sd: Dict[str, torch.Tensor], idx: torch.Tensor, normalize: bool,
                 remove_last: bool, save: bool, ctx=None, f16: bool = False,
-                bf16: bool = False) -> Tuple[torch.Tensor, ForwardBuffers]:
+                bf16: bool = False, gvec=None) -> Tuple[torch.Tensor, ForwardBuffers]:
     """idx: (B,T) int32 class indices, or a (B,Q,T) fp32 tensor for inputs that are
     not one-hot (dense causal conv).  ``f16``: fp16 operands / fp32 accumulation in every
     product (mvn_forward_f16; inference and generator priming).  ``bf16``: bf16 operands /
-    fp32 accumulation in the layers' products (mvn_forward_bf16; trains with mvn_backward_bf16)."""
+    fp32 accumulation in the layers' products (mvn_forward_bf16; trains with mvn_backward_bf16).
+    ``gvec``: (B, C) fp32 global vectors on the fast path of global conditioning (mvn_global_bias +
+    mvn_forward_global: C = K = 64, no ``ctx``; the caller has asked mvn_global_fast_path)."""
     lib = N.lib()
     _require_gpu(idx, "audio")
     dense = None
@@ -129,9 +131,17 @@ def run_forward(dims: N.Dims, sd: Dict[str, torch.Tensor], idx: torch.Tensor, no
             (B, dims.input_channels, max(s_out, 0)), dtype=torch.float32, device=dev)
         params, keep = pack_params(dims, sd, L)
         name = "mvn_forward_f16" if f16 else "mvn_forward_bf16" if bf16 else "mvn_forward"
+        tail = ()
+        if gvec is not None:  # one 2C-vector per (layer, sequence) instead of a context product per column
+            name = "mvn_forward_global"
+            gbias = (torch.empty if buf.guard is None else buf.guard.empty)((L, B, 128), dtype=torch.float32, device=dev)
+            N.check(lib.mvn_global_bias(dims, params, gvec.data_ptr(), B, gbias.data_ptr(), _stream_ptr(dev)),
+                    "mvn_global_bias")
+            tail = (gbias.data_ptr(),)
+            buf.gbias = gbias
         N.check(getattr(lib, name)(dims, params, None if dense is not None else idx.data_ptr(),
                                    0 if dense is not None else idx.stride(0), B, T, buf.struct,
-                                   out.data_ptr(), int(normalize), int(remove_last), int(save),
+                                   out.data_ptr(), int(normalize), int(remove_last), int(save), *tail,
                                    _stream_ptr(dev)), name)
         if buf.guard is not None:
             buf.guard.check("mvn_forward")
@@ -140,11 +150,12 @@ def run_forward(dims: N.Dims, sd: Dict[str, torch.Tensor], idx: torch.Tensor, no
 
 
 class _WaveNetFunction(torch.autograd.Function):
-    """args: dims, names, idx, normalize, remove_last, ctx (Tensor or None), *params"""
-    N_FIXED = 6
+    """args: dims, names, idx, normalize, remove_last, ctx (Tensor or None), gvec (Tensor or None), *params.
+    ``gvec``: the (B, C) global vectors of the fast path of global conditioning (``context`` is None then)."""
+    N_FIXED = 7
 
     @staticmethod
-    def forward(ctx_, dims, names, idx, normalize, remove_last, context, *params):
+    def forward(ctx_, dims, names, idx, normalize, remove_last, context, gvec, *params):
         sd = dict(zip(names, params))
         # (grad mode itself is off inside forward(): the caller records whether it was on)
         save = any(ctx_.needs_input_grad[5:]) and bool(getattr(dims, "_grad_mode", True))
@@ -152,9 +163,10 @@ class _WaveNetFunction(torch.autograd.Function):
         if f16 and save:
             raise RuntimeError("movenet_amd: forward_precision 'fp16' is inference-only "
                                "(mvn_backward differentiates the fp32 forward); use torch.no_grad()")
+        gvec = None if gvec is None else gvec.detach().to(torch.float32).contiguous()
         out, buf = run_forward(dims, sd, idx, normalize, remove_last, save, context, f16=f16,
-                               bf16=bool(getattr(dims, "_bf16", False)))
-        ctx_.dims, ctx_.names, ctx_.idx, ctx_.buf = dims, names, idx, buf
+                               bf16=bool(getattr(dims, "_bf16", False)), gvec=gvec)
+        ctx_.dims, ctx_.names, ctx_.idx, ctx_.buf, ctx_.gvec = dims, names, idx, buf, gvec
         ctx_.normalize, ctx_.remove_last, ctx_.saved_fwd = normalize, remove_last, save
         ctx_.has_context = context is not None
         ctx_.video_slot = getattr(dims, "_video_slot", None) if context is not None else None
@@ -167,8 +179,8 @@ class _WaveNetFunction(torch.autograd.Function):
             raise RuntimeError("movenet_amd: forward ran without saved activations")
         out, *params = ctx_.saved_tensors
         dout = dout.to(torch.float32).contiguous()
-        grads, dctx = _run_backward(ctx_, params, out, dout, None)
-        return _grads_for_autograd(ctx_, grads, dctx, _WaveNetFunction.N_FIXED, ctx_.needs_input_grad)
+        grads, dctx, dgvec = _run_backward(ctx_, params, out, dout, None)
+        return _grads_for_autograd(ctx_, grads, dctx, dgvec, _WaveNetFunction.N_FIXED, ctx_.needs_input_grad)
 
 
 class _GuardBands:
@@ -199,7 +211,7 @@ class _GuardBands:
 def _run_backward(ctx_, params, out, dout, fill_dlogit):
     """mvn_backward for a saved forward.  ``dout``: gradient w.r.t. the model output, or None
     when ``fill_dlogit(dlogit, Sp, pad)`` writes the gradient w.r.t. the logits itself (the
-    fused loss).  Returns ({name: grad view into ONE flat buffer}, dctx or None)."""
+    fused loss).  Returns ({name: grad view into ONE flat buffer}, dctx or None, dgvec or None)."""
     lib = N.lib()
     dims, names, idx, buf = ctx_.dims, ctx_.names, ctx_.idx, ctx_.buf
     L = dims.layer_size * dims.stack_size
@@ -249,19 +261,42 @@ def _run_backward(ctx_, params, out, dout, fill_dlogit):
         params_c, pkeep = pack_params(dims, sd, L)
         # (a bf16 forward is differentiated by the bf16 backward: same operand rounding both ways)
         name = "mvn_backward_bf16" if getattr(dims, "_bf16", False) else "mvn_backward"
+        gvec, tail, dgvec = getattr(ctx_, "gvec", None), (), None
+        if gvec is not None:
+            # global conditioning, fast path: the layer kernel leaves df | dg in the dfg tensor (its scatter pairs move
+            # to a scratch of their own), their row sums land in `rowsum` and one kernel turns those into the
+            # context-conv gradients and the gradient of the global vectors
+            name = "mvn_backward_global"
+            n_scratch = int(lib.mvn_global_scratch_floats(dims, B, T))
+            scratch = alloc((n_scratch,), **f32)
+            rowsum = alloc((L, B, 128), **f32)
+            rowsum.zero_()
+            tail = (scratch.data_ptr(), n_scratch, rowsum.data_ptr())
+        elif (getattr(dims, "_label_in_context", False) and ctx_.has_context and C == 64 and K == 64
+              and name == "mvn_backward"):
+            # global conditioning, general path: the conditioned layers' one-kernel backward with a scratch of its own
+            # (dlogit / da1, where it looks otherwise, do not hold it at short outputs or small Q)
+            name = "mvn_backward_scratch"
+            n_scratch = int(lib.mvn_global_scratch_floats(dims, B, T))
+            scratch = alloc((n_scratch,), **f32)
+            tail = (scratch.data_ptr(), n_scratch)
         N.check(getattr(lib, name)(dims, params_c, g, None if dense_in else idx.data_ptr(),
                                    0 if dense_in else idx.stride(0), B, T,
                                    buf.struct, bw, None if out is None else out.data_ptr(),
                                    None if dout is None else dout.data_ptr(),
-                                   int(ctx_.normalize), int(ctx_.remove_last), _stream_ptr(dev)),
+                                   int(ctx_.normalize), int(ctx_.remove_last), *tail, _stream_ptr(dev)),
                 name)
+        if gvec is not None:
+            dgvec = alloc((B, C), **f32)
+            N.check(lib.mvn_global_bias_backward(dims, params_c, g, rowsum.data_ptr(), gvec.data_ptr(), B,
+                                                 dgvec.data_ptr(), _stream_ptr(dev)), "mvn_global_bias_backward")
         if guard is not None:
-            guard.check("mvn_backward")
+            guard.check(name)
     # (buffers are released with the autograd node; a retained graph may run backward again)
-    return grads, (dctx[:, :, :T] if dctx is not None else None)
+    return grads, (dctx[:, :, :T] if dctx is not None else None), dgvec
 
 
-def _grads_for_autograd(ctx_, grads, dctx, n_fixed, need):
+def _grads_for_autograd(ctx_, grads, dctx, dgvec, n_fixed, need):
     dims, names = ctx_.dims, ctx_.names
     L = dims.layer_size * dims.stack_size
     last = f"residual_conv_stack.conv_layers.{L - 1}.conv_residual."
@@ -270,27 +305,29 @@ def _grads_for_autograd(ctx_, grads, dctx, n_fixed, need):
         # the last layer's residual conv never reaches the output: the
         # reference leaves its .grad None, so do we
         result.append(None if (n.startswith(last) or not want) else grads[n])
-    dcontext = dctx if (ctx_.has_context and need[n_fixed - 1]) else None
-    return (*([None] * (n_fixed - 1)), dcontext, *result)
+    dcontext = dctx if (ctx_.has_context and need[n_fixed - 2]) else None
+    return (*([None] * (n_fixed - 2)), dcontext, dgvec if need[n_fixed - 1] else None, *result)
 
 
 class _WaveNetLossFunction(torch.autograd.Function):
     """Forward + the trainer's loss in one autograd node (row F3): the head's logits become
     probabilities and the loss / accuracy partial sums in ONE pass (mvn_softmax_ce_forward_ex);
     backward differentiates loss -> logits in ONE pass (mvn_softmax_ce_backward_ex) straight into
-    mvn_backward's dlogit buffer.  args: dims, names, idx, target (B,S) int64, ctx, *params;
+    mvn_backward's dlogit buffer.  args: dims, names, idx, target (B,S) int64, ctx, gvec, *params;
     returns (loss, accuracy, probs).  ``dims._loss_rule`` (N.LOSS_REFERENCE when absent) picks the
     loss: cross_entropy on the probabilities, or the negative log-likelihood of softmax(logits)."""
-    N_FIXED = 5
+    N_FIXED = 6
 
     @staticmethod
-    def forward(ctx_, dims, names, idx, target, context, *params):
+    def forward(ctx_, dims, names, idx, target, context, gvec, *params):
         lib = N.lib()
         sd = dict(zip(names, params))
         rule = int(getattr(dims, "_loss_rule", N.LOSS_REFERENCE))
         save = any(ctx_.needs_input_grad[4:]) and bool(getattr(dims, "_grad_mode", True))
         # logits, last column dropped
-        out, buf = run_forward(dims, sd, idx, False, True, save, context, bf16=bool(getattr(dims, "_bf16", False)))
+        gvec = None if gvec is None else gvec.detach().to(torch.float32).contiguous()
+        out, buf = run_forward(dims, sd, idx, False, True, save, context, bf16=bool(getattr(dims, "_bf16", False)),
+                               gvec=gvec)
         B, Q, S = out.shape
         if target.shape != (B, S):
             raise ValueError(f"target must be (batch, {S}), got {tuple(target.shape)}")
@@ -305,7 +342,7 @@ class _WaveNetLossFunction(torch.autograd.Function):
         n = max(B * S, 1)
         loss = loss_part.sum() / n
         acc = ok_part.sum().to(torch.float32) / n
-        ctx_.dims, ctx_.names, ctx_.idx, ctx_.buf = dims, names, idx, buf
+        ctx_.dims, ctx_.names, ctx_.idx, ctx_.buf, ctx_.gvec = dims, names, idx, buf, gvec
         ctx_.normalize, ctx_.remove_last, ctx_.saved_fwd = True, True, save
         ctx_.has_context = context is not None
         ctx_.loss_rule = rule
@@ -329,8 +366,8 @@ class _WaveNetLossFunction(torch.autograd.Function):
                 dlogit.data_ptr(), Q * Sp, Sp, pad, S + 1, ctx_.loss_rule, _stream_ptr(probs.device)),
                 "mvn_softmax_ce_backward_ex")
 
-        grads, dctx = _run_backward(ctx_, params, None, None, fill)
-        return _grads_for_autograd(ctx_, grads, dctx, _WaveNetLossFunction.N_FIXED, ctx_.needs_input_grad)
+        grads, dctx, dgvec = _run_backward(ctx_, params, None, None, fill)
+        return _grads_for_autograd(ctx_, grads, dctx, dgvec, _WaveNetLossFunction.N_FIXED, ctx_.needs_input_grad)
 
 
 class _UpsampleVideoFunction(torch.autograd.Function):
@@ -405,20 +442,23 @@ def upsample_video(model, video: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def _tagged_dims(dims, f16: bool = False, context=None, bf16: bool = False, loss_rule: int = N.LOSS_REFERENCE):
+def _tagged_dims(dims, f16: bool = False, context=None, bf16: bool = False, loss_rule: int = N.LOSS_REFERENCE,
+                 label_in_context: bool = False):
     """A copy of the dims struct carrying what the autograd Functions cannot see from inside
-    ``forward``: whether grad mode was on at the call, the operand precision and the loss rule."""
+    ``forward``: whether grad mode was on at the call, the operand precision, the loss rule and whether a label's
+    vector has joined the context (general path of global conditioning: the backward then brings a scratch)."""
     d = N.make_dims(dims.layer_size, dims.stack_size, dims.input_channels, dims.residual_channels,
                     dims.skip_channels)
     d._grad_mode = torch.is_grad_enabled()
     d._f16 = f16
     d._bf16 = bf16
     d._loss_rule = loss_rule
+    d._label_in_context = bool(label_in_context)
     d._video_slot = getattr(context, "_mvn_video_slot", None) if context is not None else None
     return d
 
 
-def bf16_mode(model, conditioned: bool) -> bool:
+def bf16_mode(model, conditioned: bool, labelled: bool = False) -> bool:
     """Whether ``model.forward_precision`` asks for the bf16 layer kernels; raises ValueError, before
     anything is launched, for what they do not run (mvn_forward_bf16 / mvn_backward_bf16 refuse the same)."""
     if getattr(model, "forward_precision", "fp32") != "bf16":
@@ -429,7 +469,58 @@ def bf16_mode(model, conditioned: bool) -> bool:
                          f"got {C} and {K}")
     if conditioned:
         raise ValueError("forward_precision 'bf16' runs audio-only models: no video context")
+    if labelled:
+        raise ValueError("forward_precision 'bf16' runs audio-only models: no global conditioning (global_features)")
     return True
+
+
+def global_vector(model, global_features, batch: int):
+    """The (B, C) global vectors e_b of ``global_features``, or None for a model built without
+    ``global_classes`` (the argument is then ignored, as the reference ignores it).  (B,) integers index the rows of
+    ``global_embedding.weight``; a (B, G) float tensor mixes them (one-hot, or a blend of styles).  ValueError, before
+    anything is launched, for a missing argument, a wrong length / width or an index outside [0, G)."""
+    G = int(getattr(model, "global_classes", 0))
+    if G <= 0:
+        return None
+    if global_features is None:
+        raise ValueError(f"this model was built with global_classes={G}: global_features is required")
+    E = model.global_embedding.weight
+    gf = global_features if torch.is_tensor(global_features) else torch.as_tensor(global_features)
+    if gf.dim() == 1 and not gf.is_floating_point() and gf.dtype != torch.bool:
+        if gf.shape[0] != batch:
+            raise ValueError(f"global_features has {gf.shape[0]} entries for a batch of {batch}")
+        host = gf.detach().cpu()
+        if batch and (int(host.min()) < 0 or int(host.max()) >= G):
+            raise ValueError(f"global_features holds a class outside [0, {G}): {host.tolist()}")
+        return E[gf.to(device=E.device, dtype=torch.int64)]
+    if gf.dim() == 2 and gf.is_floating_point():
+        if gf.shape[0] != batch or gf.shape[1] != G:
+            raise ValueError(f"global_features must be ({batch},) class indices or ({batch}, {G}) rows, "
+                             f"got {tuple(gf.shape)}")
+        return gf.to(device=E.device, dtype=E.dtype) @ E
+    raise ValueError(f"global_features must be ({batch},) integer class indices or ({batch}, {G}) float rows, "
+                     f"got {tuple(gf.shape)} {gf.dtype}")
+
+
+def _global_plan(model, context, gvec, batch: int, t_len: int):
+    """(context, gvec) as the autograd nodes take them.  Fast path (C = K = 64, fp32, no video, ``model.global_path ==
+    "auto"`` and mvn_global_fast_path grants the shape under the process's kernel switches): the vectors go in as they
+    are.  General path: they join the context as a column constant in time and the conditioned kernels run."""
+    if gvec is None:
+        return context, None
+    dims = model._dims
+    if (context is None and getattr(model, "global_path", "auto") == "auto" and model.forward_precision == "fp32"
+            and dims.residual_channels == 64 and dims.skip_channels == 64):
+        with torch.cuda.device(gvec.device):
+            if N.lib().mvn_global_fast_path(dims, batch, t_len) == 1:
+                return None, gvec
+    if context is None:
+        return gvec[:, :, None].expand(-1, -1, t_len), None
+    both = context + gvec[:, :, None]
+    slot = getattr(context, "_mvn_video_slot", None)
+    if slot is not None:
+        both._mvn_video_slot = slot
+    return both, None
 
 
 def _decoder_params(model, with_context: bool):
@@ -440,30 +531,33 @@ def _decoder_params(model, with_context: bool):
 
 
 def wavenet_forward(model, audio: torch.Tensor, context=None, output_unnormalized: bool = True,
-                    remove_last: bool = True) -> torch.Tensor:
+                    remove_last: bool = True, gvec=None) -> torch.Tensor:
     """WaveNet.forward.  NOTE the reference's inverted flag (wavenet.py:189-191):
     output_unnormalized=True returns PROBABILITIES.  ``context``: upsampled video
     (B, C, T) or None.  One-hot input runs the causal conv as a gather; the check that the
     input IS one-hot is read after the kernels have been enqueued (no host wait on an idle
     GPU) and anything else is rerun through the dense causal conv."""
-    bf16 = bf16_mode(model, context is not None)
+    bf16 = bf16_mode(model, context is not None, gvec is not None)
     model.compute_output_size(audio)  # ValueError when T < RF, like the reference
+    labelled = gvec is not None
+    context, gvec = _global_plan(model, context, gvec, int(audio.shape[0]), int(audio.shape[2]))
     idx, check = model._indices_async(audio)
-    names, params = _decoder_params(model, context is not None)
-    dims = _tagged_dims(model._dims, f16=model.forward_precision == "fp16", context=context, bf16=bf16)
+    names, params = _decoder_params(model, context is not None or gvec is not None)
+    dims = _tagged_dims(model._dims, f16=model.forward_precision == "fp16", context=context, bf16=bf16,
+                        label_in_context=labelled and gvec is None)
     out = _WaveNetFunction.apply(dims, names, idx, bool(output_unnormalized),
-                                 bool(remove_last), context, *params)
+                                 bool(remove_last), context, gvec, *params)
     if not model._all_one_hot(check):  # dense causal conv on the tensor itself
         # (a dense input pays the discarded index pass: one extra forward; its buffers --
         # saved activations included -- are released BEFORE the rerun allocates its own)
         del out
         dense = audio.detach().to(torch.float32).contiguous()
         out = _WaveNetFunction.apply(dims, names, dense, bool(output_unnormalized),
-                                     bool(remove_last), context, *params)
+                                     bool(remove_last), context, gvec, *params)
     return out if audio.dtype == torch.float32 else out.to(audio.dtype)
 
 
-def wavenet_forward_loss(model, audio: torch.Tensor, context=None, target=None, loss_rule=None):
+def wavenet_forward_loss(model, audio: torch.Tensor, context=None, target=None, loss_rule=None, gvec=None):
     """(loss, accuracy, probabilities) of one trainer step in one autograd node:
     ``output = model(audio, video)`` (probabilities, Q1), ``target =
     audio[:, :, RF:].argmax(1)``, ``F.cross_entropy(output, target)`` (on probabilities, Q2) and
@@ -475,19 +569,22 @@ def wavenet_forward_loss(model, audio: torch.Tensor, context=None, target=None, 
     ``F.cross_entropy(logits, target)`` instead -- the mean negative log-likelihood, in nats, of the
     distribution ``generate_sampling = "model"`` draws from; accuracy and probabilities are the same."""
     rule = N.loss_rule(getattr(model, "loss_rule", "reference") if loss_rule is None else loss_rule)
-    bf16 = bf16_mode(model, context is not None)
+    bf16 = bf16_mode(model, context is not None, gvec is not None)
     model.compute_output_size(audio)
+    labelled = gvec is not None
+    context, gvec = _global_plan(model, context, gvec, int(audio.shape[0]), int(audio.shape[2]))
     rf = model.receptive_fields
     idx, check = model._indices_async(audio)
-    names, params = _decoder_params(model, context is not None)
+    names, params = _decoder_params(model, context is not None or gvec is not None)
     tg = idx[:, rf:].to(torch.int64) if target is None else target
-    dims = _tagged_dims(model._dims, context=context, bf16=bf16, loss_rule=rule)
-    res = _WaveNetLossFunction.apply(dims, names, idx, tg, context, *params)
+    dims = _tagged_dims(model._dims, context=context, bf16=bf16, loss_rule=rule,
+                        label_in_context=labelled and gvec is None)
+    res = _WaveNetLossFunction.apply(dims, names, idx, tg, context, gvec, *params)
     if not model._all_one_hot(check):  # (read after the enqueue: no idle GPU) dense causal conv
         del res  # release the discarded pass (saved activations) before the rerun allocates
         dense = audio.detach().to(torch.float32).contiguous()
         tg = audio[:, :, rf:].argmax(1) if target is None else target
-        res = _WaveNetLossFunction.apply(dims, names, dense, tg, context, *params)
+        res = _WaveNetLossFunction.apply(dims, names, dense, tg, context, gvec, *params)
     return res
 
 

@@ -28,7 +28,7 @@ import torch
 import torch.nn as nn
 
 from .config import TrainingConfig, arg_parser, config_from_args
-from .dataset import get_dataloader
+from .dataset import get_dataloader, training_contexts
 from .optim import FlatAdamW, order_like_backward
 from .generation import HostWords
 from .utils.host import cap_torch_threads
@@ -42,7 +42,9 @@ class Dance2Music(nn.Module):
         self.learning_rate = config.learning_rate
         self.dataset_fp = dataset_fp
         self.config = config
-        self.model = WaveNet(**asdict(config.model_config))
+        # --use_global 1: the sorted context folders of the TRAINING set are the classes of the model's global embedding
+        self.global_classes = self._class_map() if getattr(config, "use_global", False) else []
+        self.model = WaveNet(**asdict(config.model_config), global_classes=len(self.global_classes))
         self.model.generate_sampling = config.generate_sampling  # (ValueError for an unknown rule)
         self.model.generate_top_k = config.generate_top_k        # (... a negative k, a p outside (0, 1])
         self.model.generate_top_p = config.generate_top_p
@@ -67,7 +69,24 @@ class Dance2Music(nn.Module):
     def forward(self, audio, video, **kwargs):
         return self.model(audio, video, **kwargs)
 
-    def generate(self, audio, video):
+    def _class_map(self):
+        names = training_contexts(self.dataset_fp)
+        if not names:
+            raise ValueError(f"use_global: {self.dataset_fp} has no training contexts")
+        return names
+
+    def class_indices(self, contexts):
+        """``Batch.contexts`` names -> the (B,) class tensor ``forward`` takes as ``global_features`` (None when the
+        model has no global classes); a name the training set lacks is a ValueError that names it."""
+        if not self.global_classes:
+            return None
+        where = {name: i for i, name in enumerate(self.global_classes)}
+        unknown = sorted({str(n) for n in contexts if n not in where})
+        if unknown:
+            raise ValueError(f"context {unknown[0]!r} is not among the training set's classes {self.global_classes}")
+        return torch.tensor([where[n] for n in contexts], dtype=torch.int64)
+
+    def generate(self, audio, video, labels=None):
         if (self.config.log_samples_every is not None
                 and (self.current_epoch + 1) % self.config.log_samples_every == 0):
             sweep = list(getattr(self.config, "generate_temperature_sweep", None) or ())
@@ -76,9 +95,10 @@ class Dance2Music(nn.Module):
                 n = len(sweep)
                 return self.model.generate(
                     audio.repeat_interleave(n, dim=0), None if video is None else video.repeat_interleave(n, dim=0),
+                    None if labels is None else labels.repeat_interleave(n, dim=0),
                     n_samples=self.config.generate_n_samples, temperature=sweep * audio.shape[0]).detach()
             return self.model.generate(
-                audio, video, n_samples=self.config.generate_n_samples,
+                audio, video, labels, n_samples=self.config.generate_n_samples,
                 temperature=self.config.generate_temperature).detach()
         return None
 
@@ -95,21 +115,23 @@ class Dance2Music(nn.Module):
         # over the head's logits, their gradient in one pass back (ops.wavenet_forward_loss)
         # (through both modules' __call__, like the reference's self(audio, video): forward
         # hooks and overrides keep firing)
-        loss, acc, output = self(audio, video if self.config.use_video else None, return_loss=True)
+        labels = self.class_indices(contexts)  # (None without --use_global)
+        extra = {} if labels is None else {"global_features": labels}
+        loss, acc, output = self(audio, video if self.config.use_video else None, return_loss=True, **extra)
         self.log(f"{prefix}_loss", loss, batch_size=self.config.batch_size)
         self.log(f"{prefix}_acc", acc, batch_size=self.config.batch_size)
         if self.model.loss_rule == "model":  # the loss is a likelihood in nats: also in bits (a device scalar, no sync)
             self.log(f"{prefix}_bits_per_sample", loss.detach() / math.log(2.0), batch_size=self.config.batch_size)
-        return loss, output, audio, video
+        return loss, output, audio, video, labels
 
     def training_step(self, batch, batch_idx):
-        loss, output, audio, video = self._shared_step(batch, "train")
+        loss, output, audio, video, labels = self._shared_step(batch, "train")
         return {"loss": loss, "output": output.detach(),
-                "generated_output": self.generate(audio, video)}
+                "generated_output": self.generate(audio, video, labels)}
 
     def validation_step(self, batch, batch_idx):
-        _, output, audio, video = self._shared_step(batch, "val")
-        return {"output": output.detach(), "generated_output": self.generate(audio, video)}
+        _, output, audio, video, labels = self._shared_step(batch, "val")
+        return {"output": output.detach(), "generated_output": self.generate(audio, video, labels)}
 
     def _loader(self, train: bool):
         c = self.config
@@ -141,7 +163,8 @@ class Dance2Music(nn.Module):
                              f"Must be one of {opt_kw.keys()}")
         if c.optimizer in ("Adam", "AdamW") and self.device.type == "cuda":
             # same update rule as torch.optim.Adam / AdamW, one HIP kernel over one flat buffer
-            optimizer = FlatAdamW(order_like_backward(self.model, bool(c.use_video)), decoupled=c.optimizer == "AdamW",
+            # (labels train the layers' context convs too: their gradients sit where a video-conditioned run's do)
+            optimizer = FlatAdamW(order_like_backward(self.model, bool(c.use_video) or bool(self.global_classes)), decoupled=c.optimizer == "AdamW",
                                   **opt_kw[c.optimizer])
         else:
             optimizer = getattr(torch.optim, c.optimizer)(self.model.parameters(), **opt_kw[c.optimizer])
@@ -367,7 +390,9 @@ class Trainer:
                     ck = self.root / "checkpoints"
                     ck.mkdir(parents=True, exist_ok=True)
                     # Lightning's layout: "state_dict" with the LightningModule's "model." prefix
+                    names = list(getattr(model, "global_classes", []) or [])  # class i of global_embedding <-> names[i]
                     torch.save({"epoch": epoch, "global_step": self.global_step,
+                                **({"global_classes": names} if names else {}),
                                 "state_dict": {f"model.{k}": v.detach().cpu()
                                                for k, v in model.model.state_dict().items()}},
                                ck / f"epoch={epoch}-step={self.global_step}.ckpt")

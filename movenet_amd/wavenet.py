@@ -47,8 +47,14 @@ def upsample_kernel_size_solver(in_size, out_size, stride=1, padding=0, output_p
 class WaveNet(nn.Module):
     def __init__(self, layer_size: int, stack_size: int, input_channels: int,
                  residual_channels: int = 16, skip_channels: int = 16,
-                 context_in_channels: int = 1):
+                 context_in_channels: int = 1, global_classes: int = 0):
+        """``global_classes`` (an extension behind the reference's arguments; 0, the default, is the reference's
+        module to the bit): G > 0 registers ``global_embedding.weight`` (G, residual_channels) behind every other
+        parameter and makes ``global_features`` a required input of ``forward`` / ``generate``."""
         super().__init__()
+        if isinstance(global_classes, bool) or not isinstance(global_classes, int) or global_classes < 0:
+            raise ValueError(f"global_classes must be an integer >= 0, got {global_classes!r}")
+        self.global_classes = global_classes
         self.layer_size = layer_size
         self.stack_size = stack_size
         self.input_channels = input_channels
@@ -68,6 +74,11 @@ class WaveNet(nn.Module):
         self.causal_conv = CausalConv1d(Q, C)
         self.residual_conv_stack = ResidualConvStack(layer_size, stack_size, C, K)
         self.dense_conv = DenseConv(K, Q)
+        if global_classes > 0:  # (registered last: the draws of every other parameter under a seed do not move)
+            self.global_embedding = nn.Embedding(global_classes, C)
+        # "auto" (default): global conditioning takes the fast path where it exists (C = K = 64, fp32, no video: one
+        # bias vector per layer and sequence); "context": always the general path, the label as a constant context
+        self._global_path = "auto"
 
         self._dims = N.make_dims(layer_size, stack_size, Q, C, K)
         self._gen_variant = N.GEN_AUTO
@@ -147,6 +158,19 @@ class WaveNet(nn.Module):
         if value is not None:
             N.seq_sampling_array(len(value) if N.any_per_sequence(value) else 1, self.input_channels, 1.0, 0, 1.0, value)
         self._gen_seed = value
+
+    # ---- which kernels global conditioning runs ----------------------------
+    @property
+    def global_path(self) -> str:
+        """"auto" (default) or "context": force the general path of global conditioning -- the global vector added to
+        the context, the conditioned kernels as they are (tests, A/B measurements)."""
+        return getattr(self, "_global_path", "auto")
+
+    @global_path.setter
+    def global_path(self, value: str) -> None:
+        if value not in ("auto", "context"):
+            raise ValueError(f"global_path must be 'auto' or 'context', got {value!r}")
+        self._global_path = value
 
     # ---- what forward(..., return_loss=True) minimises --------------------
     @property
@@ -230,7 +254,8 @@ class WaveNet(nn.Module):
         return out if dtype == torch.float32 else out.to(dtype)
 
     def _decoder_state(self):
-        return {k: v for k, v in self.state_dict().items() if not k.startswith("video_")}
+        return {k: v for k, v in self.state_dict().items()
+                if not k.startswith("video_") and not k.startswith("global_embedding.")}
 
     # ---- model API ------------------------------------------------------
     def upsample_video(self, video):
@@ -247,6 +272,13 @@ class WaveNet(nn.Module):
         and gate pre-activations at the same absolute time (right-aligned, like the
         residual input at modules.py:84).
 
+        BUILD DEFINITION for ``global_features`` (the reference declares the argument and never uses it):
+        a model built with ``global_classes = G > 0`` owns ``global_embedding.weight`` E of shape (G, C), and sequence
+        b carries the vector e_b = E[class_b] for a (B,) integer tensor of classes in [0, G), or row_b @ E for a
+        (B, G) float tensor (one-hot, or a mixture).  It enters every gated layer exactly where the context does, as a
+        column constant in time: f_l += Wcf_l (ctx + e_b) + bcf_l, g_l += Wcg_l (ctx + e_b) + bcg_l, with ctx the
+        up-sampled video or zero.  With G > 0 the argument is required (ValueError); with G = 0 it is ignored.
+
         ``return_loss=True`` (an extension; the default is the reference's signature and
         result): returns ``(loss, accuracy, probabilities)`` of the trainer's step -- the
         reference's ``output = self(audio, video)``, ``target = audio[:, :, RF:].argmax(1)``,
@@ -254,13 +286,14 @@ class WaveNet(nn.Module):
         -- as ONE autograd node (ops.wavenet_forward_loss); going through ``forward`` keeps
         module hooks firing on the fused path.  ``loss_rule = "model"`` makes that loss
         ``F.cross_entropy`` of the logits instead (the property's docstring)."""
-        from .ops import bf16_mode, wavenet_forward, wavenet_forward_loss  # HIP full-sequence kernels
-        bf16_mode(self, video is not None)  # (refused before the video encoder runs)
+        from .ops import bf16_mode, global_vector, wavenet_forward, wavenet_forward_loss  # HIP full-sequence kernels
+        gvec = global_vector(self, global_features, int(audio.shape[0]))  # (ValueError before anything is launched)
+        bf16_mode(self, video is not None, gvec is not None)  # (refused before the video encoder runs)
         context = None if video is None else self.upsample_video(video)
         if return_loss:
-            return wavenet_forward_loss(self, audio, context, target)
+            return wavenet_forward_loss(self, audio, context, target, gvec=gvec)
         return wavenet_forward(self, audio, context, output_unnormalized=output_unnormalized,
-                               remove_last=remove_last)
+                               remove_last=remove_last, gvec=gvec)
 
     @torch.no_grad()
     def generate(self, audio, video=None, global_features=None, n_samples: Optional[int] = None,
@@ -271,7 +304,10 @@ class WaveNet(nn.Module):
         ``temperature`` takes one value or a sequence of B values, one per sequence of the batch (a temperature sweep
         on one prompt is ONE launch: repeat the prompt), and ``generate_seed`` likewise; with either a sequence,
         sequence b draws on its own seed and row b whatever the launch plan.  A wrong length or a bad value is a
-        ValueError before anything runs."""
+        ValueError before anything runs.  ``global_features``: as in ``forward`` -- the label's vector conditions
+        every step (required for a model built with ``global_classes``)."""
+        from .ops import global_vector
+        gvec = global_vector(self, global_features, int(audio.shape[0]))
         top_k, top_p, seed = self.generate_top_k, self.generate_top_p, self.generate_seed
         per_seq = N.any_per_sequence(temperature, seed)
         if per_seq:  # (validates lengths and values; the seed drawn below replaces the placeholder)
@@ -296,13 +332,14 @@ class WaveNet(nn.Module):
         if seed is None:
             seed = int(torch.empty((), dtype=torch.int64).random_().item())
         state = self._decoder_state()
-        if context is None:
+        if context is None and gvec is None:
             state = {k: v for k, v in state.items() if ".context_conv_" not in k}
-        elif context.shape[2] < n_total:
+        elif context is not None and context.shape[2] < n_total:
             raise ValueError(f"the upsampled video covers {context.shape[2]} samples, "
                              f"n_samples={n_total} asked for")
         kw = dict(batch=idx.shape[0], n_total=n_total, device=audio.device,
                   temperature=temperature, seed=seed, context=context,
+                  global_context=None if gvec is None else gvec.detach().to(torch.float32).contiguous(),
                   sampling=self.generate_sampling, top_k=top_k, top_p=top_p)
         def run(variant, group):
             if group:
@@ -320,7 +357,7 @@ class WaveNet(nn.Module):
 
         with torch.cuda.device(audio.device):
             if self._gen_variant == N.GEN_AUTO:
-                kind, group, variant = auto_plan(self._dims, idx.shape[0], context is not None)
+                kind, group, variant = auto_plan(self._dims, idx.shape[0], context is not None or gvec is not None)
             else:
                 kind, group, variant = "single", 0, self._gen_variant
                 if variant == N.GEN_PIPE_F16 and idx.shape[0] > max_pipe_batch(self._dims, variant):
