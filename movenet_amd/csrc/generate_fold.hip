@@ -310,7 +310,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ> a, u64 *han
     // not L2).  The entries step tn needs were pushed at least two steps ago (dilation 1 takes
     // this step's value instead), so they are requested at the TOP of the turn and arrive under
     // the wait for the inbox and the chain.
-    float popv[LPS] = {0.f, 0.f, 0.f};
+    float (&popv)[LPS] = pg;  // (helper lanes only, which never touch pg: three registers the MULTI forms do not have to spare)
     auto prefetch_pops = [&](int tn) {
       if (MULTI && !chain && lead) {
         int cq = c;
@@ -453,7 +453,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ> a, u64 *han
       lds_barrier();
       MVN_FINE(b, s, ts - a.t_begin, 2, 0);
       // ---- phase 1
-      v2f b2 = {0.f, 0.f};  // chain: (Wc_2 Wr_0) z_0, this thread's 16 inputs
+      v2f b2 = {0.f, 0.f};  // chain: (Wc_2 Wr_0) z_0, this thread's 16 inputs; helpers: .x = their 16 terms of Wr_0 z_0
       if (chain) {
         f4 xz[NF4];
         ldsv<NF4>(xz, vq, O_Z0);
@@ -469,12 +469,18 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ> a, u64 *han
         if (lead) LDSF(vc, O_Z1) = z;
         MVN_FINE(b, s, ts - a.t_begin, 3, 0);
       } else {
-        // (x_1 = x_0 + Wr_0 z_0 + br_0 is first needed for x_2: formed in phase 2, where the SIMDs have issue slots
-        // to spare -- this phase closes on the helpers)
-        f4 xa[NF4];
+        // x_1 = x_0 + Wr_0 z_0 + br_0 is first needed for x_2, in phase 2, but xp' must not leave the stage after zl':
+        // the next stage waits for both in ONE inbox wait, and xp' is off the critical chain.  So the product is
+        // split over the two phases: this thread's 16 terms of Wr_0 z_0 are summed here and held in b2.x (the
+        // register pair the chain keeps its own b2 in); the cross-lane adds and the stream update wait for phase 2.
+        // (Measured, DESIGN 4.1c: this phase closes on the helpers again, ~100 cycles later; the hop gives back more.)
+        f4 xa[NF4], xz0[NF4];
         ldsv<NF4>(xa, vq, O_X0);
+        ldsv<NF4>(xz0, vq, O_Z0);
         v2f acc[4];
         pair_acc<true>(acc, m2.w, xa);                             // Wc_2 x_0
+        b2.x = split_dot<1>(m3.w, xz0);                            // Wr_0 z_0, before the sum over the channel's lanes
+        asm volatile("" : "+v"(b2));                               // formed here, not sunk behind the barrier
         const v2f fg = pair_sum(acc);
         const float f = chan_sum<KQ>(fg.x);
         const float g = chan_sum<KQ>(fg.y);
@@ -501,15 +507,20 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ> a, u64 *han
       } else {
         u64 sk_peek = 0;
         if (!FIRST) sk_peek = peek_granule(ibs);
+        // the residual biases, read by every lane in front of z_1 (volatile: not to be sunk into the lead lanes' block
+        // behind the cross-lane adds, where the LDS round trip stood in front of the xp' put)
+        const float br0v = *(volatile lds_f *)(uintptr_t)(vc + 4u * (O_VEC + V_BR0));
+        const float br1v = *(volatile lds_f *)(uintptr_t)(vc + 4u * (O_VEC + V_BR1));
+        const float br2v = *(volatile lds_f *)(uintptr_t)(vc + 4u * (O_VEC + V_BR2));
         f4 xz[NF4];
         ldsv<NF4>(xz, vq, O_Z1);
         // the stream: x_1, x_2 for the queue pushes, and xp' = x_2 + br_2 for the next stage (the head does not read it)
         auto stream = [&](bool send) {
-          f4 xz0[NF4];
-          ldsv<NF4>(xz0, vq, O_Z0);
-          const float br0 = LDSF(vc, O_VEC + V_BR0), br1 = LDSF(vc, O_VEC + V_BR1), br2 = LDSF(vc, O_VEC + V_BR2);
-          float r0 = split_dot<1>(m3.w, xz0);                      // Wr_0 z_0
+          float br0 = send ? br0v : LDSF(vc, O_VEC + V_BR0), br1 = send ? br1v : LDSF(vc, O_VEC + V_BR1),
+                br2 = send ? br2v : LDSF(vc, O_VEC + V_BR2);
+          float r0 = b2.x;                                         // Wr_0 z_0: the 16 terms summed in phase 1
           float r = split_dot<0>(m4.w, xz);                        // Wr_1 z_1
+          asm volatile("" : "+v"(br0), "+v"(br1), "+v"(br2));      // (in registers before the cross-lane adds)
           r0 = chan_sum<KQ>(r0);
           r = chan_sum<KQ>(r);
           if (lead) {
