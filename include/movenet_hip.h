@@ -615,6 +615,22 @@ int mvn_adamw_step(float *param, const float *grad, float *exp_avg, float *exp_a
                    float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                    int decoupled, const size_t *skip_ranges, int n_skip, void *stream);
 
+/* mvn_adamw_step with an exponential moving average (EMA) of the parameters kept in the same launch.
+ * param, exp_avg and exp_avg_sq come out as mvn_adamw_step leaves them, bit for bit; behind that, for
+ * every element that is stepped,
+ *     ema[i] = ema[i] + (param_new[i] - ema[i]) * ema_weight,
+ * ema_weight = 1 - decay of this update, formed by the caller (in double, then rounded to float).
+ *   ema         DEVICE, n floats, distinct from the other four buffers; the caller initialises it
+ *               (to the parameters)
+ *   ema_weight  in (0, 1]; 1 makes ema a copy of the stepped elements
+ * Elements inside a skip range are left untouched in ema as in the other buffers.  A null ema or an
+ * ema_weight outside (0, 1] (NaN included) is MVN_ERR_BAD_ARG, like mvn_adamw_step's own refusals before
+ * any launch; n == 0 is MVN_OK. */
+int mvn_adamw_ema_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *ema,
+                       size_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       int step, int decoupled, float ema_weight, const size_t *skip_ranges, int n_skip,
+                       void *stream);
+
 /* mu-law companding either side of the model (movenet/dataset.py:278-289 encode ->
  * one-hot; movenet/callbacks.py:66-76 argmax -> decode).  The reference calls torchaudio,
  * which is absent offline and pinned by no fixture: formula of RESEARCH.md:156-163,

@@ -15,6 +15,11 @@ on the GPU (``mvn_mu_law_decode``: formula of RESEARCH.md:156-163, parity unpinn
 per temperature of the sweep -- by the module, in ONE ``generate()`` call that carries each clip len(sweep) times with
 a temperature per sequence -- so ``outputs["generated_output"]`` holds len(sweep) rows per clip, clip-major.  They are
 written as ``...-gen-T<value>.wav``, one index row per (clip, temperature) with a ``temperature`` field.
+
+With ``--ema_decay`` the module generates ``outputs["generated_output"]`` on the averaged weights
+(``Dance2Music.averaged_weights``), on the train hook and on the validation hook, and the validation hook's
+``outputs["output"]`` comes from them too (the whole validation loop runs on them); the train hook's
+``outputs["output"]`` is the raw iterate's, like the train metrics.
 """
 from __future__ import annotations
 

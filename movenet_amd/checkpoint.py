@@ -32,15 +32,21 @@ def strip_prefixes(sd: Dict[str, torch.Tensor]) -> "OrderedDict[str, torch.Tenso
     return out
 
 
-def load_state_dict_file(path) -> "OrderedDict[str, torch.Tensor]":
+def load_state_dict_file(path, ema: bool = False) -> "OrderedDict[str, torch.Tensor]":
+    """The weights in ``path``; with ``ema`` the averaged weights a run with ``--ema_decay`` saves beside them
+    (``"ema_state_dict"``, same prefixes) -- ValueError for a file that holds none."""
     obj = torch.load(path, map_location="cpu", weights_only=True)
-    if isinstance(obj, dict) and "state_dict" in obj and isinstance(obj["state_dict"], dict):
+    if ema:
+        if not (isinstance(obj, dict) and isinstance(obj.get("ema_state_dict"), dict)):
+            raise ValueError(f"{path}: no 'ema_state_dict' (not a checkpoint of a run with --ema_decay > 0)")
+        obj = obj["ema_state_dict"]
+    elif isinstance(obj, dict) and "state_dict" in obj and isinstance(obj["state_dict"], dict):
         obj = obj["state_dict"]
     if not isinstance(obj, dict) or not all(torch.is_tensor(v) for v in obj.values()):
         raise ValueError(f"{path}: neither a state_dict nor a Lightning checkpoint")
     return strip_prefixes(obj)
 
 
-def load_into(model: torch.nn.Module, path, strict: bool = True):
-    """model.load_state_dict from any of the reference's checkpoint flavours."""
-    return model.load_state_dict(load_state_dict_file(path), strict=strict)
+def load_into(model: torch.nn.Module, path, strict: bool = True, ema: bool = False):
+    """model.load_state_dict from any of the reference's checkpoint flavours (``ema``: the averaged weights)."""
+    return model.load_state_dict(load_state_dict_file(path, ema=ema), strict=strict)

@@ -72,6 +72,13 @@ class TrainingConfig:
     # reference field: a JSON written without it loads with the default (off).
     use_global: bool = False
 
+    # exponential moving average of the weights, kept by the fused optimizer step (FlatAdamW(ema_decay=...), DESIGN
+    # 4.6): 0 is off; above 0, validation, the logged samples and the checkpoint's "ema_state_dict" come from the
+    # averaged weights.  ema_warmup ramps the decay as min(ema_decay, (1 + t) / (10 + t)).  Not reference fields: a JSON
+    # written without them loads with the defaults (off).
+    ema_decay: float = 0.0
+    ema_warmup: bool = True
+
     scheduler: Optional[str] = "OneCycleLR"
     lr_pct_start: float = 0.45
     base_learning_rate: float = 0.0003
@@ -155,6 +162,8 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--generate_top_p", type=float, default=1.0)
     a("--generate_temperature_sweep", type=lambda x: [float(t) for t in x.split(",") if t.strip()], default=[])
     a("--loss_rule", type=str, default="reference", choices=["reference", "model"])
+    a("--ema_decay", type=float, default=0.0)
+    a("--ema_warmup", type=_flag, default=True)
     a("--n_epochs", type=int, default=10)
     a("--n_steps_per_epoch", type=int, default=None)
     a("--use_video", type=_flag, default=True)
@@ -198,7 +207,7 @@ def config_from_args(args) -> TrainingConfig:
         "lr_pct_start base_learning_rate scheduler_step_size_up scheduler_step_size_down "
         "scheduler_cyclic_mode scheduler_cyclic_gamma scheduler_cycle_momentum max_learning_rate "
         "scheduler_step_size scheduler_step_gamma scheduler_milestones weight_decay "
-        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule accumulation_steps num_workers val_num_workers "
+        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule ema_decay ema_warmup accumulation_steps num_workers val_num_workers "
         "pin_memory n_epochs n_steps_per_epoch use_video use_global batch_subsample_frac "
         "val_batch_subsample_frac dist_backend dist_port model_output_path log_samples_every"
     ).split()

@@ -13,6 +13,8 @@
 //                            streaming p - onehot backward (ce_model_bwd_kernel)
 //   mvn_adamw_step           torch.optim.AdamW / Adam over ONE flat parameter / gradient /
 //                            moment buffer (pytorch_lightning_trainer.py:186-189)
+//   mvn_adamw_ema_step       the same step, with an exponential moving average of the parameters
+//                            updated in the same launch
 //
 // The arithmetic of the first two is that of softmax_cols_kernel (sequence.hip) followed by
 // ce_probs_cols_kernel (common.hip), operation for operation: the fused forms return the same
@@ -383,6 +385,44 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float *__restrict__ p, 
   }
 }
 
+// The same step with an exponential moving average of the parameters kept behind it (mvn_adamw_ema_step): p, m and v
+// by adamw_flat_kernel's expressions, one for one (same inputs, same bits), then
+//   ema = ema + (p_new - ema) w        w = 1 - decay_t, from the host
+// on the value p was just given, while it is still in a register: one more read and write per element, no second pass.
+// A skipped element's average is left alone with its parameter.
+__global__ __launch_bounds__(256) void adamw_ema_flat_kernel(float *__restrict__ p, const float *__restrict__ g,
+                                                             float *__restrict__ m, float *__restrict__ v,
+                                                             float *__restrict__ ema, unsigned long long n, float lr,
+                                                             float beta1, float beta2, float eps, float wd, float bc1,
+                                                             float bc2_sqrt, int decoupled, float ema_w,
+                                                             AdamSkip skip) {
+  const unsigned long long i0 = ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i0 >= n) return;
+  const float step_size = lr / bc1;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const unsigned long long i = i0 + e;
+    if (i >= n) return;
+    bool skipped = false;
+    for (int k = 0; k < skip.n; ++k) skipped = skipped || (i >= skip.lo[k] && i < skip.hi[k]);
+    if (skipped) continue;
+    float pv = p[i], gv = g[i];
+    if (decoupled)
+      pv = pv * (1.0f - lr * wd);
+    else
+      gv = gv + wd * pv;
+    const float mv = m[i] + (gv - m[i]) * (1.0f - beta1);
+    const float vv = beta2 * v[i] + (1.0f - beta2) * gv * gv;
+    m[i] = mv;
+    v[i] = vv;
+    const float denom = sqrtf(vv) / bc2_sqrt + eps;
+    const float pn = pv - step_size * (mv / denom);
+    p[i] = pn;
+    const float ev = ema[i];
+    ema[i] = ev + (pn - ev) * ema_w;
+  }
+}
+
 }  // namespace mvn
 
 extern "C" {
@@ -501,6 +541,35 @@ int mvn_adamw_step(float *param, const float *grad, float *exp_avg, float *exp_a
                      (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, (unsigned long long)n, lr, beta1,
                      beta2, eps, weight_decay, bc1, bc2_sqrt, decoupled, sk);
   return mvn::check_hip(hipGetLastError(), "mvn_adamw_step");
+}
+
+int mvn_adamw_ema_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *ema, size_t n,
+                       float lr, float beta1, float beta2, float eps, float weight_decay, int step, int decoupled,
+                       float ema_weight, const size_t *skip_ranges, int n_skip, void *stream) {
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !ema || step < 1 || n_skip < 0 || n_skip > 4 ||
+      (n_skip > 0 && !skip_ranges)) {
+    mvn::set_error("mvn_adamw_ema_step: bad argument (ema set, step >= 1, at most 4 skip ranges)");
+    return MVN_ERR_BAD_ARG;
+  }
+  if (!(ema_weight > 0.f && ema_weight <= 1.f)) {  // (NaN fails both comparisons)
+    mvn::set_error("mvn_adamw_ema_step: bad argument (ema_weight %g lies outside (0, 1])", (double)ema_weight);
+    return MVN_ERR_BAD_ARG;
+  }
+  if (n == 0) return MVN_OK;
+  mvn::AdamSkip sk;
+  sk.n = n_skip;
+  for (int k = 0; k < 4; ++k) {
+    sk.lo[k] = k < n_skip ? skip_ranges[2 * k] : 0;
+    sk.hi[k] = k < n_skip ? skip_ranges[2 * k + 1] : 0;
+  }
+  // bias corrections as mvn_adamw_step forms them
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+  const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+  const size_t threads = (n + 3) / 4;
+  hipLaunchKernelGGL(mvn::adamw_ema_flat_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, ema, (unsigned long long)n, lr, beta1,
+                     beta2, eps, weight_decay, bc1, bc2_sqrt, decoupled, ema_weight, sk);
+  return mvn::check_hip(hipGetLastError(), "mvn_adamw_ema_step");
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@ parallel over clips (movenet_amd/parallel.py) when launched with torchrun.
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import math
 import os
@@ -53,6 +54,7 @@ class Dance2Music(nn.Module):
         self.precision = 32
         self.rank, self.world_size = 0, 1
         self.logged_raw = {}  # name -> 0-dim device tensor or float, as logged (no host sync)
+        self.ema_optimizer = None  # the FlatAdamW that keeps the weights' average (--ema_decay > 0), else None
 
     @property
     def device(self) -> torch.device:
@@ -86,9 +88,27 @@ class Dance2Music(nn.Module):
             raise ValueError(f"context {unknown[0]!r} is not among the training set's classes {self.global_classes}")
         return torch.tensor([where[n] for n in contexts], dtype=torch.int64)
 
+    def averaged_weights(self):
+        """Context: the model runs on the averaged weights (``FlatAdamW.averaged_parameters``) -- a no-op without
+        ``--ema_decay``, and inside a caller's own ``averaged_parameters()`` (the validation loop)."""
+        opt = self.ema_optimizer
+        if opt is None or opt.inside_average:
+            return contextlib.nullcontext()
+        return opt.averaged_parameters()
+
+    def _generates_now(self) -> bool:
+        return (self.config.log_samples_every is not None
+                and (self.current_epoch + 1) % self.config.log_samples_every == 0)
+
+    def _generate_averaged(self, audio, video, labels):
+        """``generate`` for the sample logger: on the averaged weights when there are any.  (The views are swapped
+        only on a step that generates; the step's autograd graph holds the parameters themselves, which point into
+        the raw buffer again before ``backward`` runs.)"""
+        with (self.averaged_weights() if self._generates_now() else contextlib.nullcontext()):
+            return self.generate(audio, video, labels)  # (which keeps the epoch gate: None on the other epochs)
+
     def generate(self, audio, video, labels=None):
-        if (self.config.log_samples_every is not None
-                and (self.current_epoch + 1) % self.config.log_samples_every == 0):
+        if self._generates_now():
             sweep = list(getattr(self.config, "generate_temperature_sweep", None) or ())
             if sweep:
                 # every clip once per temperature, clip-major, in ONE generate() call (LogSamplesCallback's layout)
@@ -127,11 +147,11 @@ class Dance2Music(nn.Module):
     def training_step(self, batch, batch_idx):
         loss, output, audio, video, labels = self._shared_step(batch, "train")
         return {"loss": loss, "output": output.detach(),
-                "generated_output": self.generate(audio, video, labels)}
+                "generated_output": self._generate_averaged(audio, video, labels)}
 
     def validation_step(self, batch, batch_idx):
         _, output, audio, video, labels = self._shared_step(batch, "val")
-        return {"output": output.detach(), "generated_output": self.generate(audio, video, labels)}
+        return {"output": output.detach(), "generated_output": self._generate_averaged(audio, video, labels)}
 
     def _loader(self, train: bool):
         c = self.config
@@ -161,11 +181,19 @@ class Dance2Music(nn.Module):
         if c.optimizer not in opt_kw:
             raise ValueError(f"optimizer {c.optimizer} not recognized. "
                              f"Must be one of {opt_kw.keys()}")
-        if c.optimizer in ("Adam", "AdamW") and self.device.type == "cuda":
+        ema_decay = float(getattr(c, "ema_decay", 0.0))  # (a config pickled before the fields existed)
+        flat = c.optimizer in ("Adam", "AdamW") and self.device.type == "cuda"
+        if ema_decay > 0 and not flat:
+            raise ValueError(f"--ema_decay {ema_decay:g} needs the fused Adam / AdamW step on a GPU (the average is "
+                             f"kept by its kernel); optimizer {c.optimizer} on {self.device.type} has none")
+        self.ema_optimizer = None
+        if flat:
             # same update rule as torch.optim.Adam / AdamW, one HIP kernel over one flat buffer
             # (labels train the layers' context convs too: their gradients sit where a video-conditioned run's do)
             optimizer = FlatAdamW(order_like_backward(self.model, bool(c.use_video) or bool(self.global_classes)), decoupled=c.optimizer == "AdamW",
+                                  ema_decay=ema_decay, ema_warmup=bool(getattr(c, "ema_warmup", True)),
                                   **opt_kw[c.optimizer])
+            self.ema_optimizer = optimizer if ema_decay > 0 else None
         else:
             optimizer = getattr(torch.optim, c.optimizer)(self.model.parameters(), **opt_kw[c.optimizer])
         print(f"using optimizer: {optimizer}")
@@ -258,6 +286,7 @@ class Trainer:
         self.rank = 0
         self.history = []      # one dict per optimizer step
         self.global_step = 0
+        self.optimizer = None  # what fit() steps (its averaged_parameters() / ema_state_dict() when --ema_decay is on)
 
     def fit(self, model: Dance2Music) -> None:
         if self.precision == "bf16":
@@ -278,10 +307,16 @@ class Trainer:
             raise RuntimeError("movenet_amd trains on MI355X devices only (no CPU path)")
         model.to(dev)
         opt_cfg = model.configure_optimizers()
-        optimizer = opt_cfg["optimizer"]
+        optimizer = self.optimizer = opt_cfg["optimizer"]
+        averaging = model.ema_optimizer is not None
         scheduler = opt_cfg.get("lr_scheduler", {}).get("scheduler")
         sync = FlatGradSync(model.model.parameters(), world)
         sync.broadcast_parameters(0)
+        if averaging and world > 1:
+            # the average starts at the parameters every rank now holds; from here each rank forms the same average from
+            # the same reduced gradients, and nothing of it is ever exchanged
+            with torch.no_grad():
+                optimizer.ema.copy_(optimizer.flat)
         log_f = None
         if self.root is not None and rank == 0:
             self.root.mkdir(parents=True, exist_ok=True)
@@ -359,7 +394,8 @@ class Trainer:
             # ranks' shards: what Lightning's self.log(..., on_epoch=True) reports for
             # validation_step (pytorch_lightning_trainer.py:91-92), not the last batch's values
             val_dev = torch.zeros(3, dtype=torch.float64, device=dev)  # loss * n, acc * n, n
-            with torch.no_grad():
+            # (--ema_decay: val_loss / val_acc / val_bits_per_sample and the validation samples are the averaged weights')
+            with torch.no_grad(), (optimizer.averaged_parameters() if averaging else contextlib.nullcontext()):
                 for batch_idx, batch in enumerate(model.val_dataloader()):
                     if self.limit_val is not None and batch_idx >= self.limit_val:
                         break
@@ -391,8 +427,12 @@ class Trainer:
                     ck.mkdir(parents=True, exist_ok=True)
                     # Lightning's layout: "state_dict" with the LightningModule's "model." prefix
                     names = list(getattr(model, "global_classes", []) or [])  # class i of global_embedding <-> names[i]
+                    ema = ({"ema_state_dict": {f"model.{k}": v.detach().cpu()
+                                               for k, v in optimizer.ema_state_dict(model.model).items()},
+                            "ema_decay": optimizer.ema_decay, "ema_updates": optimizer.ema_updates}
+                           if averaging else {})  # (absent without --ema_decay)
                     torch.save({"epoch": epoch, "global_step": self.global_step,
-                                **({"global_classes": names} if names else {}),
+                                **({"global_classes": names} if names else {}), **ema,
                                 "state_dict": {f"model.{k}": v.detach().cpu()
                                                for k, v in model.model.state_dict().items()}},
                                ck / f"epoch={epoch}-step={self.global_step}.ckpt")
