@@ -272,6 +272,43 @@ int mvn_generate_seq(const mvn_dims *dims, int variant, const float *packed, flo
                      float *logits_out, int32_t *choices_out, int logits_t0,
                      const float *context_tm, int sampling, void *stream);
 
+/* Classifier-free guidance.  A guided launch holds `pairs` pairs = 2 * pairs rows of
+ * samples, state (that of batch = 2 * pairs: mvn_gen_state_floats), per_seq, logits_out, choices_out and
+ * context_tm: rows [0, pairs) are the UNCONDITIONAL rows, rows [pairs, 2 * pairs) the CONDITIONAL ones, and pair p
+ * is rows p and p + pairs.  The caller gives both rows of a pair the same prompt; they differ only in their
+ * context_tm rows (video, or zeros, against the same plus the label's vector).
+ * The step of pair p that predicts time u forms, over the raw fp32 head logits l_u, l_c of its two rows,
+ *     l[q] = l_c[q] + (guidance[p] - 1) * (l_c[q] - l_u[q])        for q < Q
+ * in fp32 in exactly this order -- subtract, multiply, add, nothing fused -- so a scale of 1 gives l_c to the
+ * bit.  Padding classes q >= Q of a 256-wide head keep their -inf (the formula is not applied to them).  The
+ * guided logits then go through the unchanged choice of mvn_generate_seq with the settings of the CONDITIONAL
+ * row's entry, per_seq[p + pairs] (temperature, top_k, top_p, seed, row), under `sampling`; a greedy step takes
+ * the arg-max of the guided logits by the same greedy rule.  The pick is written to samples[u] (u >= n_given)
+ * and to choices_out of BOTH rows, and both rows consume it at the next step.  Columns u < n_given (prompt /
+ * teacher forcing) must hold the same in both rows of a pair.  Where a caller breaks that contract the result is
+ * defined per variant: MVN_GEN_GENERIC consumes each row's own column, the pipelined variants (PIPE, PIPE_F16,
+ * FOLD) keep one pair of indices per pair and feed both rows the conditional row's column.  logits_out rows stay each row's own raw logits; the state and the network arithmetic never depend on
+ * the scales.  Chunked launches (t_begin / t_end) carry state as those of mvn_generate do.
+ *
+ * mvn_gen_guided_max_pairs: host-only arithmetic -- the pairs one guided launch of `variant` takes for `dims`;
+ * 0: the variant has no guided form (MVN_GEN_STREAM) or does not take the dims; negative on bad dims.  A
+ * pipelined variant serves pair p on pipeline p in two consecutive turns (unconditional row first), so its limit
+ * is its pipeline count for the dims (FOLD at config 2: 23); MVN_GEN_GENERIC runs one workgroup per pair and
+ * returns 0x3FFFFFFF.
+ *
+ * Refused before any launch and before any buffer is touched: per_seq or guidance NULL, or pairs < 1:
+ * MVN_ERR_BAD_ARG; pairs above the limit, or a variant without a guided form: MVN_ERR_UNSUPPORTED with a
+ * mvn_last_error() text that names the limit.  `per_seq` (2 * pairs entries that have passed
+ * mvn_seq_sampling_check) and `guidance` (pairs floats) are DEVICE arrays the host cannot validate: a
+ * non-finite scale only changes which class is drawn and never causes an out-of-range access (every consumer
+ * of a pick clamps it to [0, Q)). */
+int mvn_gen_guided_max_pairs(const mvn_dims *dims, int variant);
+int mvn_generate_guided(const mvn_dims *dims, int variant, const float *packed, float *state,
+                        int32_t *samples, int pairs, int sample_stride, int n_total, int n_given,
+                        int t_begin, int t_end, const mvn_seq_sampling *per_seq, const float *guidance,
+                        float *logits_out, int32_t *choices_out, int logits_t0,
+                        const float *context_tm, int sampling, void *stream);
+
 /* Local conditioning in generation (BUILD DEFINITION, the reference raises: SURVEY.md
  * Q7): step t adds the context column of time t to every layer's filter/gate sums.
  * context_tm is (batch, n_total, C) TIME-major (one coalesced 4C-byte read per step);

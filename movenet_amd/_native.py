@@ -131,6 +131,10 @@ SIGNATURES = {
     "mvn_generate_seq": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "mvn_gen_guided_max_pairs": (C.c_int, [C.POINTER(Dims), C.c_int]),
+    "mvn_generate_guided": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "mvn_transpose_context": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                         C.c_void_p]),
     "mvn_padded_len": (C.c_int, [C.c_int]),
@@ -341,6 +345,32 @@ def seq_sampling_array(batch: int, classes: int, temperature, top_k, top_p, seed
     if rc != MVN_OK:
         raise ValueError(last_error())
     return arr
+
+
+def guidance_scales(batch: int, guidance):
+    """The classifier-free guidance scales of ``batch`` sequences as a list of floats: ``guidance`` a number (the same
+    for every sequence) or a 1-D sequence / tensor of ``batch`` numbers.  ValueError for a wrong length or a value that
+    is not a finite number.  Allocates nothing on a device."""
+    batch = int(batch)
+    if _per_sequence(guidance):
+        values = guidance.tolist() if hasattr(guidance, "tolist") else list(guidance)
+        if not isinstance(values, list) or any(isinstance(v, (list, tuple)) for v in values):
+            raise ValueError(f"guidance must be a number or a 1-D sequence of length {batch}")
+        if len(values) != batch:
+            raise ValueError(f"guidance has {len(values)} entries for a batch of {batch}")
+    else:
+        values = [guidance] * batch
+    out = []
+    for b, v in enumerate(values):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), float("-inf")):
+            raise ValueError(f"guidance of row {b} is {v!r}, not a finite number")
+        out.append(float(v))
+    return out
+
+
+def guided_max_pairs(dims, variant: int) -> int:
+    """mvn_gen_guided_max_pairs: the pairs one guided launch of ``variant`` takes for ``dims`` (0: no guided form)."""
+    return check(lib().mvn_gen_guided_max_pairs(dims, int(variant)), "mvn_gen_guided_max_pairs")
 
 
 def make_dims(layer_size: int, stack_size: int, input_channels: int, residual_channels: int,

@@ -51,12 +51,13 @@ def write_wav(path: Path, waveform: np.ndarray, sample_rate: int = SAMPLE_RATE) 
 
 class LogSamplesCallback:
     def __init__(self, log_every_n_epochs: int = 10, log_video: bool = True, temperature: float = 1.0,
-                 out_dir: Optional[str] = None, temperature_sweep=()):
+                 out_dir: Optional[str] = None, temperature_sweep=(), guidance: float = 1.0):
         self.log_every_n_epochs = log_every_n_epochs
         self.log_video = log_video  # kept for signature parity: there is no video to re-attach
         self.temperature = temperature
         self.out_dir = Path(out_dir) if out_dir is not None else None
         self.temperature_sweep = [float(t) for t in (temperature_sweep or ())]
+        self.guidance = float(guidance)  # the module's classifier-free guidance scale (1.0: off, no field in the rows)
         self.columns = list(COLUMNS)
 
     def on_train_batch_end(self, trainer, pl_module, outputs, batch, batch_idx):
@@ -111,6 +112,9 @@ class LogSamplesCallback:
                 write_wav(files["gen_audio"], gen[i])
             rows.append({"split": split, "epoch": trainer.current_epoch, "batch_idx": batch_idx, "fp": fp,
                          **{k: str(v.relative_to(root)) for k, v in files.items()}})
+        if gen is not None and self.guidance != 1.0:  # (as a sweep's rows carry their temperature)
+            for r in rows:
+                r["guidance"] = self.guidance
         if labelled:
             where = {str(fp): str(c) for fp, c in zip(fps, contexts)}
             for r in rows:

@@ -6,8 +6,9 @@ namespace mvn {
 
 // GenScalarArgs: what a kernel takes where one temperature, seed, top_k and top_p hold for the whole launch -- the
 // kernel argument of every instantiation that existed before mvn_generate_seq, layout unchanged (their code is the
-// same to the instruction).  GenArgs (below) adds the per-sequence array: what the host drivers pass around, and the
-// kernel argument of the SEQ instantiations.
+// same to the instruction).  GenSeqArgs (below) adds the per-sequence array: the kernel argument of the SEQ
+// instantiations, layout unchanged too.  GenArgs adds the guidance scales: what the host drivers pass around, and the
+// kernel argument of the GUIDED instantiations.
 struct GenScalarArgs {
   int L, layer_size, Q, C, K;
   const float *w;
@@ -31,19 +32,34 @@ struct GenScalarArgs {
   long long ctx_stride_b;
   const float *wctx;
 };
-struct GenArgs : GenScalarArgs {
+struct GenSeqArgs : GenScalarArgs {
   // mvn_generate_seq: DEVICE array of one entry per sequence of the launch (NULL on every other entry point); the
   // kernels' SEQ instantiations read temperature, top_k, top_p, seed and row from it instead of the scalars above
   const mvn_seq_sampling *per_seq;
 };
+struct GenArgs : GenSeqArgs {
+  // mvn_generate_guided: DEVICE array of one classifier-free guidance scale per pair of the launch (NULL on every other
+  // entry point; read by the GUIDED instantiations alone).  Rows [0, pairs) are then the unconditional rows, rows
+  // [pairs, 2 pairs) the conditional ones
+  const float *guidance;
+};
+// The guided logits of a step (include/movenet_hip.h, mvn_generate_guided): sub, mul, add in fp32, `sm1` = s - 1.  The
+// library is built with -ffp-contract=off, so nothing is fused: s = 1 returns lc.
+__device__ __forceinline__ float guided_logit(float lc, float lu, float sm1) {
+  const float d = lc - lu;
+  const float m = sm1 * d;
+  return lc + m;
+}
 // The kernel argument of an instantiation.  A launch hands every kernel a GenArgs; a scalar instantiation's
-// parameter is its leading GenScalarArgs (the base sits at offset 0).
-template <bool SEQ>
+// parameter is its leading GenScalarArgs, a SEQ one's its leading GenSeqArgs (the bases sit at offset 0).
+template <bool SEQ, bool GUIDED = false>
 struct KArgsOf { typedef GenScalarArgs type; };
 template <>
-struct KArgsOf<true> { typedef GenArgs type; };
-template <bool SEQ>
-using KArgs = typename KArgsOf<SEQ>::type;
+struct KArgsOf<true, false> { typedef GenSeqArgs type; };
+template <>
+struct KArgsOf<true, true> { typedef GenArgs type; };
+template <bool SEQ, bool GUIDED = false>
+using KArgs = typename KArgsOf<SEQ, GUIDED>::type;
 
 // What a step of sequence b samples by: the launch's scalars with row = b (what every kernel did before
 // mvn_generate_seq), or, by the kernel argument's type, entry b of a.per_seq.  b is uniform over the wave or
@@ -59,7 +75,7 @@ struct SeqSampling {
 __device__ __forceinline__ SeqSampling seq_sampling(const GenScalarArgs &a, int b) {
   return {a.temperature, a.top_k, a.top_p, a.seed, (uint32_t)b};
 }
-__device__ __forceinline__ SeqSampling seq_sampling(const GenArgs &a, int b) {
+__device__ __forceinline__ SeqSampling seq_sampling(const GenSeqArgs &a, int b) {
   const mvn_seq_sampling *s = a.per_seq + b;
   return {s->temperature, s->top_k, s->top_p, s->seed, s->row};
 }
@@ -116,6 +132,10 @@ struct GenVariant {
   // `hand`: the hand-off area, `hand_total` floats long, its status word `status_off` floats in (pipelined only)
   int (*launch)(const GenArgs &, const mvn_dims *, int batch, float *hand, size_t hand_total, size_t status_off,
                 hipStream_t);
+  // mvn_generate_guided: `pairs` pairs, 2 pairs rows (a.per_seq and a.guidance set); NULL: the variant has no guided form.
+  // A pipelined variant runs it on `pairs` pipelines of exactly two turns each: at most launch_pipelines(d, any) pairs
+  int (*launch_guided)(const GenArgs &, const mvn_dims *, int pairs, float *hand, size_t hand_total,
+                       size_t status_off, hipStream_t);
   const char *needs;  // the "does not fit" message: a format with at most one %d, the batch limit for the dims
 };
 extern const GenVariant PIPE_VARIANT, PIPE_F16_VARIANT, FOLD_VARIANT;

@@ -145,10 +145,14 @@ __device__ int truncate_weights_lds(float *w, int Q, int top_k, float top_p) {
 }
 
 // SEQ: the block reads its sequence's sampling settings from a.per_seq (mvn_generate_seq), once, ahead of the step loop
-template <bool SEQ>
-__global__ __launch_bounds__(1024) void gen_generic_kernel(KArgs<SEQ> a) {
+// GUIDED (mvn_generate_guided; SEQ): one workgroup per PAIR.  Each step runs the pair's unconditional row
+// (b = pair) and then its conditional row (b = pair + pairs) through the same step body, keeps the first one's
+// logits in Q more floats of LDS, and makes the one choice on the guided logits; thread 0 writes it to both rows.
+template <bool SEQ, bool GUIDED = false>
+__global__ __launch_bounds__(1024) void gen_generic_kernel(KArgs<SEQ, GUIDED> a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int tid = threadIdx.x, NT = blockDim.x, b = blockIdx.x;
+  const int tid = threadIdx.x, NT = blockDim.x;
+  int b = blockIdx.x;  // (GUIDED: the row whose half of the step it is)
   const int C = a.C, K = a.K, Q = a.Q, L = a.L;
   int partsz = NT;
   if (2 * C > partsz) partsz = 2 * C;
@@ -165,6 +169,7 @@ __global__ __launch_bounds__(1024) void gen_generic_kernel(KArgs<SEQ> a) {
   float *red = logits + Q;           // [16]
   int *ichoice = (int *)(red + 16);  // [4]
   float *ctxv = red + 16 + 4;        // [C] context vector of this step
+  [[maybe_unused]] float *lgu = ctxv + C;  // GUIDED: [Q] the unconditional row's logits of this step
 
   const float *E0t = a.w, *E1t = a.w + (size_t)Q * C;
   const float *lw = a.w + 2 * (size_t)Q * C;
@@ -176,6 +181,13 @@ __global__ __launch_bounds__(1024) void gen_generic_kernel(KArgs<SEQ> a) {
   int32_t *samples = a.samples + (size_t)b * a.stride;
   SeqSampling ps = {};  // SEQ: the block's entry of a.per_seq, loaded once ahead of the step loop (block-uniform)
   if constexpr (SEQ) ps = seq_sampling(a, b);
+  [[maybe_unused]] const int pair = blockIdx.x, pairs = gridDim.x;
+  [[maybe_unused]] float sm1 = 0.f;  // GUIDED: the pair's scale - 1
+  if constexpr (GUIDED) {
+    static_assert(SEQ, "a guided launch reads its settings per sequence");
+    ps = seq_sampling(a, pair + pairs);  // the conditional row's
+    sm1 = a.guidance[pair] - 1.0f;
+  }
 
   int Pfg, cfg, Prs, crs, P1, c1, P2, c2;
   split_parts(2 * C, 2 * C, NT, Pfg, cfg);
@@ -183,7 +195,13 @@ __global__ __launch_bounds__(1024) void gen_generic_kernel(KArgs<SEQ> a) {
   split_parts(K, Q, NT, P1, c1);
   split_parts(Q, Q, NT, P2, c2);
 
-  for (int t = a.t_begin; t < a.t_end; ++t) {
+  for (int t = a.t_begin; t < a.t_end; ++t)
+  for (int half = 0; half < (GUIDED ? 2 : 1); ++half) {
+    if constexpr (GUIDED) {
+      b = pair + half * pairs;
+      ring = a.state + (size_t)b * a.state_per_seq;
+      samples = a.samples + (size_t)b * a.stride;
+    }
     int idx_t = samples[t];
     int idx_p = t > 0 ? samples[t - 1] : -1;
     idx_t = min(max(idx_t, 0), Q - 1);
@@ -257,8 +275,15 @@ __global__ __launch_bounds__(1024) void gen_generic_kernel(KArgs<SEQ> a) {
         logits[q] = v;
         if (a.logits_out && u >= a.logits_t0)
           a.logits_out[((size_t)b * (a.n_total - a.logits_t0) + (u - a.logits_t0)) * Q + q] = v;
+        if constexpr (GUIDED) {  // (logits_out: each row's own raw logits, above)
+          if (half == 0) lgu[q] = v;
+          else logits[q] = guided_logit(v, lgu[q], sm1);
+        }
       }
       __syncthreads();
+      if constexpr (GUIDED) {
+        if (half == 0) continue;  // block-uniform; the conditional half closes the step (the barrier above orders the halves)
+      }
       // softmax(softmax(x)[/T])  (wavenet.py:189-191 then :227-233), or on a sampled step under
       // MVN_SAMPLE_MODEL the weights exp((x - max) / T) of softmax(x / T): thread 0 draws against their total
       float m = -INFINITY;
@@ -326,6 +351,10 @@ __global__ __launch_bounds__(1024) void gen_generic_kernel(KArgs<SEQ> a) {
         }
         if (a.choices_out && u >= a.logits_t0) a.choices_out[(size_t)b * a.n_total + u] = choice;
         if (u >= a.n_given) samples[u] = choice;
+        if constexpr (GUIDED) {  // ... and to the unconditional row
+          if (a.choices_out && u >= a.logits_t0) a.choices_out[(size_t)pair * a.n_total + u] = choice;
+          if (u >= a.n_given) a.samples[(size_t)pair * a.stride + u] = choice;
+        }
         ichoice[0] = choice;
       }
     }
@@ -884,6 +913,19 @@ static int generic_launch(const GenArgs &a, const mvn_dims *d, int batch, float 
     hipLaunchKernelGGL(gen_generic_kernel<false>, grid, block, generic_lds_bytes(d), stream, a);
   return check_hip(hipGetLastError(), "mvn_generate");
 }
+// one workgroup per pair; Q more floats of LDS than generic_launch (the unconditional row's logits)
+static int generic_launch_guided(const GenArgs &a, const mvn_dims *d, int pairs, float *, size_t, size_t,
+                                 hipStream_t stream) {
+  const size_t lds = generic_lds_bytes(d) + sizeof(float) * (size_t)d->input_channels;
+  if (lds > 160 * 1024) {
+    set_error("GENERIC variant: a guided launch of these dims needs %zu bytes of LDS (at most 160 KiB)", lds);
+    return MVN_ERR_UNSUPPORTED;
+  }
+  int rc = ensure_max_dynamic_lds((const void *)gen_generic_kernel<true, true>, "hipFuncSetAttribute(gen_generic, guided)");
+  if (rc) return rc;
+  hipLaunchKernelGGL((gen_generic_kernel<true, true>), dim3(pairs), dim3(generic_threads(d)), lds, stream, a);
+  return check_hip(hipGetLastError(), "mvn_generate_guided");
+}
 static int stream_launch(const GenArgs &a, const mvn_dims *, int batch, float *, size_t, size_t,
                          hipStream_t stream) {
   const size_t lds = stream_lds_bytes(a.L, a.ctx_tm != nullptr);
@@ -903,10 +945,10 @@ static int stream_launch(const GenArgs &a, const mvn_dims *, int batch, float *,
 
 static const GenVariant GENERIC_VARIANT = {
     MVN_GEN_GENERIC, "GENERIC", generic_ok, nullptr, nullptr, nullptr, nullptr, generic_weights_floats,
-    generic_pack, generic_launch, "GENERIC variant needs C,K<=256, Q<=1024 and <=160 KiB of LDS"};
+    generic_pack, generic_launch, generic_launch_guided, "GENERIC variant needs C,K<=256, Q<=1024 and <=160 KiB of LDS"};
 static const GenVariant STREAM_VARIANT = {
     MVN_GEN_STREAM, "STREAM", stream_ok, nullptr, nullptr, nullptr, nullptr, stream_weights_floats,
-    stream_pack, stream_launch, "STREAM variant needs C=K=64, Q in {64,128,256}, <=80 layers"};
+    stream_pack, stream_launch, nullptr, "STREAM variant needs C=K=64, Q in {64,128,256}, <=80 layers"};
 
 static const GenVariant *const VARIANTS[] = {&GENERIC_VARIANT, &STREAM_VARIANT, &PIPE_VARIANT, &PIPE_F16_VARIANT,
                                              &FOLD_VARIANT};
@@ -1099,7 +1141,8 @@ static int generate_driver(const mvn_dims *dims, int variant, const float *packe
                            int32_t *samples, int batch, int sample_stride, int n_total, int n_given,
                            int t_begin, int t_end, float temperature, uint64_t seed, float *logits_out,
                            int32_t *choices_out, int logits_t0, const float *context_tm, int sampling,
-                           int top_k, float top_p, const mvn_seq_sampling *per_seq, void *stream);
+                           int top_k, float top_p, const mvn_seq_sampling *per_seq, const float *guidance,
+                           void *stream);
 
 int mvn_generate_trunc(const mvn_dims *dims, int variant, const float *packed, float *state,
                        int32_t *samples, int batch, int sample_stride, int n_total, int n_given,
@@ -1108,7 +1151,7 @@ int mvn_generate_trunc(const mvn_dims *dims, int variant, const float *packed, f
                        int top_k, float top_p, void *stream) {
   return generate_driver(dims, variant, packed, state, samples, batch, sample_stride, n_total, n_given, t_begin,
                          t_end, temperature, seed, logits_out, choices_out, logits_t0, context_tm, sampling, top_k,
-                         top_p, nullptr, stream);
+                         top_p, nullptr, nullptr, stream);
 }
 
 int mvn_generate_seq(const mvn_dims *dims, int variant, const float *packed, float *state,
@@ -1121,14 +1164,53 @@ int mvn_generate_seq(const mvn_dims *dims, int variant, const float *packed, flo
   }
   return generate_driver(dims, variant, packed, state, samples, batch, sample_stride, n_total, n_given, t_begin,
                          t_end, 0.f, 0, logits_out, choices_out, logits_t0, context_tm, sampling, 0, 1.0f, per_seq,
-                         stream);
+                         nullptr, stream);
+}
+
+int mvn_gen_guided_max_pairs(const mvn_dims *dims, int variant) {
+  int rc = mvn::validate_dims(dims);
+  if (rc) return rc;
+  const mvn::GenVariant *v = mvn::find_variant(variant);
+  if (!v || !v->launch_guided || !v->ok(dims)) return 0;
+  // a pipelined variant: a pipeline per pair, so every pipeline the chip holds for the dims; a one-launch kernel
+  // takes a workgroup per pair: any count whose 2 pairs rows an int holds
+  return v->stages ? v->launch_pipelines(dims, 1 << 20) : 0x3FFFFFFF;
+}
+
+int mvn_generate_guided(const mvn_dims *dims, int variant, const float *packed, float *state,
+                        int32_t *samples, int pairs, int sample_stride, int n_total, int n_given,
+                        int t_begin, int t_end, const mvn_seq_sampling *per_seq, const float *guidance,
+                        float *logits_out, int32_t *choices_out, int logits_t0, const float *context_tm,
+                        int sampling, void *stream) {
+  if (!per_seq || !guidance || pairs < 1) {
+    mvn::set_error("mvn_generate_guided: bad argument (per_seq %s, guidance %s, pairs %d)", per_seq ? "given" : "is NULL",
+                   guidance ? "given" : "is NULL", pairs);
+    return MVN_ERR_BAD_ARG;
+  }
+  if (variant == MVN_GEN_AUTO) {
+    mvn::set_error("mvn_generate: resolve the variant with mvn_gen_variant first (the packed "
+                   "weight layout depends on it)");
+    return MVN_ERR_BAD_ARG;
+  }
+  const int limit = mvn_gen_guided_max_pairs(dims, variant);
+  if (limit < 0) return limit;
+  if (pairs > limit) {
+    const mvn::GenVariant *v = mvn::find_variant(variant);
+    mvn::set_error("mvn_generate_guided: the %s variant takes at most %d pairs per guided launch for these dims "
+                   "(%d asked for)", v ? v->name : "unknown", limit, pairs);
+    return MVN_ERR_UNSUPPORTED;
+  }
+  return generate_driver(dims, variant, packed, state, samples, 2 * pairs, sample_stride, n_total, n_given, t_begin,
+                         t_end, 0.f, 0, logits_out, choices_out, logits_t0, context_tm, sampling, 0, 1.0f, per_seq,
+                         guidance, stream);
 }
 
 static int generate_driver(const mvn_dims *dims, int variant, const float *packed, float *state,
                            int32_t *samples, int batch, int sample_stride, int n_total, int n_given,
                            int t_begin, int t_end, float temperature, uint64_t seed, float *logits_out,
                            int32_t *choices_out, int logits_t0, const float *context_tm, int sampling,
-                           int top_k, float top_p, const mvn_seq_sampling *per_seq, void *stream) {
+                           int top_k, float top_p, const mvn_seq_sampling *per_seq, const float *guidance,
+                           void *stream) {
   if (variant == MVN_GEN_AUTO) {
     mvn::set_error("mvn_generate: resolve the variant with mvn_gen_variant first (the packed "
                    "weight layout depends on it)");
@@ -1179,6 +1261,7 @@ static int generate_driver(const mvn_dims *dims, int variant, const float *packe
   a.top_k = top_k >= a.Q ? 0 : top_k;  // every class kept: off, to the bit
   a.top_p = top_p;
   a.per_seq = per_seq;
+  a.guidance = guidance;
   a.ctx_tm = context_tm;
   a.ctx_stride_b = (long long)n_total * dims->residual_channels;
   const mvn::GenVariant &v = *mvn::find_variant(variant);
@@ -1186,6 +1269,7 @@ static int generate_driver(const mvn_dims *dims, int variant, const float *packe
   float *hand = state + (size_t)batch * a.state_per_seq;  // (behind the queues; the pipelined variants' only)
   const size_t total = v.stages ? mvn::hand_total_floats(dims, batch) : 0;
   const size_t soff = v.stages ? mvn::hand_status_offset(dims, batch) : 0;
+  if (guidance) return v.launch_guided(a, dims, batch / 2, hand, total, soff, (hipStream_t)stream);
   return v.launch(a, dims, batch, hand, total, soff, (hipStream_t)stream);
 }
 

@@ -199,8 +199,10 @@ __device__ __forceinline__ float split_dot_lds(unsigned waddr, unsigned xaddr) {
 // MULTI = false: one sequence per pipeline (nseq == nb), the form every config-2 figure up to
 // batch 16 is measured on.  MULTI = true: pipeline b serves sequences b, b + nb, b + 2 nb, ... < nseq.
 // SEQ: the head reads each sequence's sampling settings from a.per_seq (mvn_generate_seq); the layer stages do not differ.
-template <bool MULTI, bool SEQ>
-__global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ> a, u64 *hand, unsigned *err, int NS, int nb, int nseq) {
+// GUIDED (mvn_generate_guided): MULTI and SEQ with nseq = 2 nb -- pipeline b serves the unconditional row b and the
+// conditional row b + nb of pair b in its two turns; only the head stage differs (pipe_common.h: head_loop).
+template <bool MULTI, bool SEQ, bool GUIDED = false>
+__global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, u64 *hand, unsigned *err, int NS, int nb, int nseq) {
   using namespace fold;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -674,7 +676,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ> a, u64 *han
       lds_barrier();
       MVN_FINE(b, NS - 1, epoch - 1, 4, 0);
     };
-    head_loop<C, GRAN, MULTI, SEQ, 2, 0>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
+    head_loop<C, GRAN, MULTI, SEQ, 2, 0, GUIDED>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
   }
 }
 
@@ -826,17 +828,18 @@ static int fold_pack(const mvn_dims *d, const mvn_params *p, float *packed, floa
 
 // Up to fold_pipelines(d) sequences: one sequence per pipeline (gen_fold_kernel<false>).  More:
 // the pipelines serve ceil(batch / pipelines) sequences each in turn (gen_fold_kernel<true>).
-static int fold_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_floats_total,
-                       size_t status_offset_floats, hipStream_t s) {
+// `guided`: batch = 2 pairs rows on exactly `pairs` pipelines, two turns each (gen_fold_kernel<true, true, true>).
+static int fold_launch_any(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_floats_total,
+                           size_t status_offset_floats, hipStream_t s, bool guided) {
   using namespace fold;
   PipeLaunch p;
   p.name = FOLD_VARIANT.name;
   p.NT = NT;
   p.NS = fold_stages(d);
   p.GRAN = GRAN;
-  p.pipes = fold_launch_pipelines(d, batch);
-  const bool multi = batch > p.pipes;
-  p.fn = a.per_seq ? (multi ? (const void *)gen_fold_kernel<true, true> : (const void *)gen_fold_kernel<false, true>)
+  p.pipes = guided ? batch / 2 : fold_launch_pipelines(d, batch);
+  const bool multi = guided || batch > p.pipes;
+  p.fn = guided ? (const void *)gen_fold_kernel<true, true, true> : a.per_seq ? (multi ? (const void *)gen_fold_kernel<true, true> : (const void *)gen_fold_kernel<false, true>)
                    : (multi ? (const void *)gen_fold_kernel<true, false> : (const void *)gen_fold_kernel<false, false>);
   p.lds_bytes = (multi ? LDS_FLOATS_MULTI : LDS_FLOATS) * sizeof(float);
   // the kernel's own map: whole pipelines inside the XCDs, or every CU (the left-over ones form pipelines across XCDs)
@@ -846,11 +849,19 @@ static int fold_launch(const GenArgs &a, const mvn_dims *d, int batch, float *ha
   p.per_pipe = GMAX;
   return pipe_launch_common(p, a, hand, hand_floats_total, status_offset_floats, s);
 }
+static int fold_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_floats_total,
+                       size_t status_offset_floats, hipStream_t s) {
+  return fold_launch_any(a, d, batch, hand, hand_floats_total, status_offset_floats, s, false);
+}
+static int fold_launch_guided(const GenArgs &a, const mvn_dims *d, int pairs, float *hand, size_t hand_floats_total,
+                              size_t status_offset_floats, hipStream_t s) {
+  return fold_launch_any(a, d, 2 * pairs, hand, hand_floats_total, status_offset_floats, s, true);
+}
 
 #ifndef __HIP_DEVICE_COMPILE__  // (the device pass would emit the constant, host function pointers and all)
 const GenVariant FOLD_VARIANT = {
     MVN_GEN_FOLD, "FOLD", fold_ok, fold_stages, fold_inbox_floats, fold_max_batch, fold_launch_pipelines,
-    fold_weights_floats, fold_pack, fold_launch,
+    fold_weights_floats, fold_pack, fold_launch, fold_launch_guided,
     "FOLD variant needs C=K=64, Q in {64,128,256}, 256 CUs and batch <= %d for these dims "
     "(ceil(L/3)+1 stages per sequence, 32 per XCD)"};
 #endif

@@ -67,8 +67,10 @@ struct PipeCfg {
 // MULTI = false: one sequence per pipeline (nseq == nb).  MULTI = true: pipeline b serves sequences
 // b, b + nb, b + 2 nb, ... < nseq in turn, one step of each per round.
 // SEQ: the head reads each sequence's sampling settings from a.per_seq (mvn_generate_seq); the layer stages do not differ.
-template <int CC, bool MULTI, bool SEQ>
-__global__ __launch_bounds__(512, 2) void gen_pipe_kernel(KArgs<SEQ> a, u64 *hand, unsigned *err, int NS,
+// GUIDED (mvn_generate_guided): MULTI and SEQ with nseq = 2 nb -- pipeline b serves the unconditional row b and the
+// conditional row b + nb of pair b in its two turns; only the head stage differs (pipe_common.h: head_loop).
+template <int CC, bool MULTI, bool SEQ, bool GUIDED = false>
+__global__ __launch_bounds__(512, 2) void gen_pipe_kernel(KArgs<SEQ, GUIDED> a, u64 *hand, unsigned *err, int NS,
                                                          int nb, int nseq) {
   using P = PipeCfg<CC>;
   constexpr int C = P::C, Q = P::Q, NT = P::NT, LPS = P::LPS, KQ = P::KQ, KPER = P::KPER;
@@ -407,7 +409,7 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_kernel(KArgs<SEQ> a, u64 *han
       head_conv2_f32(w2, a1, lgb, og, q2, b2r);
       lds_barrier();
     };
-    head_loop<C, GRAN, MULTI, SEQ, 1>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
+    head_loop<C, GRAN, MULTI, SEQ, 1, 1, GUIDED>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
   }
 }
 
@@ -583,33 +585,42 @@ int pipe_launch_common(const PipeLaunch &p, const GenArgs &a, float *hand, size_
 }
 
 template <int CC>
-static void pipe_launch_fill(PipeLaunch &p, bool multi, bool seq) {
+static void pipe_launch_fill(PipeLaunch &p, bool multi, bool seq, bool guided) {
   using P = PipeCfg<CC>;
-  p.fn = seq ? (multi ? (const void *)gen_pipe_kernel<CC, true, true> : (const void *)gen_pipe_kernel<CC, false, true>)
+  p.fn = guided ? (const void *)gen_pipe_kernel<CC, true, true, true> : seq ? (multi ? (const void *)gen_pipe_kernel<CC, true, true> : (const void *)gen_pipe_kernel<CC, false, true>)
              : (multi ? (const void *)gen_pipe_kernel<CC, true, false> : (const void *)gen_pipe_kernel<CC, false, false>);
   p.lds_bytes = (multi ? P::LDS_FLOATS_MULTI : P::LDS_FLOATS) * sizeof(float);
   p.GRAN = P::GRAN;
   p.per_pipe = P::GMAX;
 }
-static int pipe_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_total,
-                       size_t status_off, hipStream_t s) {
+// `guided`: batch = 2 pairs rows on exactly `pairs` pipelines, two turns each (the GUIDED instantiation).
+static int pipe_launch_any(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_total,
+                           size_t status_off, hipStream_t s, bool guided) {
   PipeLaunch p;
   p.name = PIPE_VARIANT.name;
   p.NT = 512;
   p.NS = pipe_stages(d);
-  p.pipes = pipe_launch_pipelines(d, batch);
+  p.pipes = guided ? batch / 2 : pipe_launch_pipelines(d, batch);
   p.slots = pipe_grid_slots(p.NS, p.pipes);
   p.batch = batch;
   p.max_batch = pipe_max_batch(d);
-  if (d->residual_channels == 64) pipe_launch_fill<64>(p, batch > p.pipes, a.per_seq != nullptr);
-  else pipe_launch_fill<128>(p, batch > p.pipes, a.per_seq != nullptr);
+  if (d->residual_channels == 64) pipe_launch_fill<64>(p, guided || batch > p.pipes, a.per_seq != nullptr, guided);
+  else pipe_launch_fill<128>(p, guided || batch > p.pipes, a.per_seq != nullptr, guided);
   return pipe_launch_common(p, a, hand, hand_total, status_off, s);
+}
+static int pipe_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_total,
+                       size_t status_off, hipStream_t s) {
+  return pipe_launch_any(a, d, batch, hand, hand_total, status_off, s, false);
+}
+static int pipe_launch_guided(const GenArgs &a, const mvn_dims *d, int pairs, float *hand, size_t hand_total,
+                              size_t status_off, hipStream_t s) {
+  return pipe_launch_any(a, d, 2 * pairs, hand, hand_total, status_off, s, true);
 }
 
 #ifndef __HIP_DEVICE_COMPILE__  // (the device pass would emit the constant, host function pointers and all)
 const GenVariant PIPE_VARIANT = {
     MVN_GEN_PIPE, "PIPE", pipe_ok, pipe_stages, pipe_inbox_floats, pipe_max_batch, pipe_launch_pipelines,
-    pipe_weights_floats, pipe_pack, pipe_launch,
+    pipe_weights_floats, pipe_pack, pipe_launch, pipe_launch_guided,
     "PIPE variant needs C=K in {64,128}, Q in {64,128,256}, 256 CUs and batch <= %d for these "
     "dims (stages per sequence: ceil(L/4)+1 at C=64, L+1 at C=128; 32 per XCD)"};
 #endif

@@ -95,8 +95,10 @@ __device__ __forceinline__ float pair_sum(float v) { return v + dpp_mov<DPP_XOR1
 // b, b + nb, b + 2 nb, ... < nseq in turn.
 // Every product of a layer stage runs on the matrix cores (r3, see the layer stage below).
 // SEQ: the head reads each sequence's sampling settings from a.per_seq (mvn_generate_seq); the layer stages do not differ.
-template <bool MULTI, bool SEQ>
-__global__ __launch_bounds__(512, 2) void gen_pipe_h16_kernel(KArgs<SEQ> a, u64 *hand, unsigned *err, int NS,
+// GUIDED (mvn_generate_guided): MULTI and SEQ with nseq = 2 nb -- pipeline b serves the unconditional row b and the
+// conditional row b + nb of pair b in its two turns; only the head stage differs (pipe_common.h: head_loop).
+template <bool MULTI, bool SEQ, bool GUIDED = false>
+__global__ __launch_bounds__(512, 2) void gen_pipe_h16_kernel(KArgs<SEQ, GUIDED> a, u64 *hand, unsigned *err, int NS,
                                                              int nb, int nseq) {
   using namespace h16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];
@@ -429,7 +431,7 @@ __global__ __launch_bounds__(512, 2) void gen_pipe_h16_kernel(KArgs<SEQ> a, u64 
       }
       lds_barrier();
     };
-    head_loop<C, GRAN, MULTI, SEQ, 1>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
+    head_loop<C, GRAN, MULTI, SEQ, 1, 1, GUIDED>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
   }
 }
 
@@ -536,19 +538,20 @@ static int pipe_h16_pack(const mvn_dims *d, const mvn_params *p, float *packed, 
 
 // `hand`: the hand-off area of the generator state (generate.hip: hand_status_offset): this
 // variant uses the first batch * NS inboxes and placement words of it.
-static int pipe_h16_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_total,
-                           size_t status_off, hipStream_t s) {
+// `guided`: batch = 2 pairs rows on exactly `pairs` pipelines, two turns each (gen_pipe_h16_kernel<true, true, true>).
+static int pipe_h16_launch_any(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_total,
+                               size_t status_off, hipStream_t s, bool guided) {
   using namespace h16;
   PipeLaunch p;
   p.name = PIPE_F16_VARIANT.name;
   p.NT = NT;
   p.GRAN = GRAN;
-  p.pipes = pipe_h16_launch_pipelines(d, batch);
-  const bool multi = batch > p.pipes;
+  p.pipes = guided ? batch / 2 : pipe_h16_launch_pipelines(d, batch);
+  const bool multi = guided || batch > p.pipes;
   // (a pipeline that serves one sequence runs three layers per stage)
   const int lps = multi ? LpsM<true>::value : LpsM<false>::value;
   p.NS = (n_layers(d) + lps - 1) / lps + 1;
-  p.fn = a.per_seq
+  p.fn = guided ? (const void *)gen_pipe_h16_kernel<true, true, true> : a.per_seq
              ? (multi ? (const void *)gen_pipe_h16_kernel<true, true> : (const void *)gen_pipe_h16_kernel<false, true>)
              : (multi ? (const void *)gen_pipe_h16_kernel<true, false> : (const void *)gen_pipe_h16_kernel<false, false>);
   p.lds_bytes = multi ? LDS_BYTES_M_MULTI : LDS_BYTES_M;
@@ -558,11 +561,20 @@ static int pipe_h16_launch(const GenArgs &a, const mvn_dims *d, int batch, float
   p.per_pipe = GMAX;
   return pipe_launch_common(p, a, hand, hand_total, status_off, s);
 }
+static int pipe_h16_launch(const GenArgs &a, const mvn_dims *d, int batch, float *hand, size_t hand_total,
+                           size_t status_off, hipStream_t s) {
+  return pipe_h16_launch_any(a, d, batch, hand, hand_total, status_off, s, false);
+}
+static int pipe_h16_launch_guided(const GenArgs &a, const mvn_dims *d, int pairs, float *hand, size_t hand_total,
+                                  size_t status_off, hipStream_t s) {
+  return pipe_h16_launch_any(a, d, 2 * pairs, hand, hand_total, status_off, s, true);
+}
 
 #ifndef __HIP_DEVICE_COMPILE__  // (the device pass would emit the constant, host function pointers and all)
 const GenVariant PIPE_F16_VARIANT = {
     MVN_GEN_PIPE_F16, "PIPE_F16", pipe_h16_ok, pipe_h16_stages, pipe_h16_inbox_floats, pipe_h16_max_batch,
     pipe_h16_launch_pipelines, pipe_h16_weights_floats, pipe_h16_pack, pipe_h16_launch,
+    pipe_h16_launch_guided,
     "PIPE_F16 variant needs C=K=128, Q=256, 256 CUs and batch <= %d for these dims "
     "(ceil(L/2)+1 stages per sequence, 32 per XCD)"};
 #endif

@@ -735,8 +735,13 @@ __device__ __forceinline__ void head_conv2_f32(const v2f (&w2)[4][16], const flo
 // between its turns).
 // SEQ (mvn_generate_seq): the settings of a step are those of the sequence whose turn it is, a.per_seq[bq], loaded
 // where the uniform is formed -- before the wait for the step's input, off the dependent chain.
-template <int C, int GRAN, bool MULTI, bool SEQ, int NZ, int NZ_SENT = NZ, class Await, class Logits>
-__device__ __forceinline__ void head_loop(const KArgs<SEQ> &a, u64 *hand, int NS, int nb, int b, int G, bool fast_edge,
+// GUIDED (mvn_generate_guided; MULTI and SEQ, G = 2, nb = pairs): pipeline b serves pair b -- turn 0 its unconditional
+// row b, turn 1 its conditional row b + nb.  Turn 0 keeps the row's logits in wave 0's registers and closes nothing;
+// turn 1 forms the guided logits from the two rows', makes the one choice by the conditional row's settings and opens
+// the next step of BOTH rows (unconditional first: stage 0 serves it first).  No hand-off is added: stage 0 waits for
+// its row's next input one turn longer, through the same bounded waits.
+template <int C, int GRAN, bool MULTI, bool SEQ, int NZ, int NZ_SENT = NZ, bool GUIDED = false, class Await, class Logits>
+__device__ __forceinline__ void head_loop(const KArgs<SEQ, GUIDED> &a, u64 *hand, int NS, int nb, int b, int G, bool fast_edge,
                                           const float *E0, const float *E1, int *iflag, int *hidx, const float *lgb,
                                           Await await, Logits logits) {
   static_assert(GRAN == (1 + NZ) * C && NZ_SENT <= NZ, "residual stream + NZ zero lanes");
@@ -779,6 +784,12 @@ __device__ __forceinline__ void head_loop(const KArgs<SEQ> &a, u64 *hand, int NS
   }
   if (MULTI) __syncthreads();
 
+  [[maybe_unused]] float lgu[4] = {0.f, 0.f, 0.f, 0.f};  // GUIDED, wave 0: the unconditional row's logits of this step
+  [[maybe_unused]] float sm1 = 0.f;                       // GUIDED: the pair's scale - 1 (wave-uniform)
+  if constexpr (GUIDED) {
+    static_assert(MULTI && SEQ, "a guided launch is a MULTI, SEQ launch of two turns per pipeline");
+    sm1 = a.guidance[b] - 1.0f;
+  }
   for (int ts = a.t_begin; ts < a.t_end; ++ts)
   for (int g = 0; g < G; ++g) {
     if (MULTI) {
@@ -797,7 +808,9 @@ __device__ __forceinline__ void head_loop(const KArgs<SEQ> &a, u64 *hand, int NS
     // keeps it from being sunk to its use behind the head's barriers)
     float uni = 0.f;
     SeqSampling ss = seq_sampling((const GenScalarArgs &)a, bq);
-    if (SEQ && wave == 0) ss = seq_sampling(a, bq);
+    bool settings_turn = true;  // GUIDED: the settings, and the uniform, are the conditional row's -- turn 1 only
+    if constexpr (GUIDED) settings_turn = g == 1;
+    if (SEQ && wave == 0 && settings_turn) ss = seq_sampling(a, bq);
     if (wave == 0 && ss.temperature > 0.f) {
       uni = philox_uniform(ss.seed, (uint32_t)u, ss.row);
       asm volatile("" : "+v"(uni));
@@ -810,6 +823,47 @@ __device__ __forceinline__ void head_loop(const KArgs<SEQ> &a, u64 *hand, int NS
     lds_barrier();
     MVN_STAMP(b, s, ts - a.t_begin, 0);
     logits(inbox, epoch, do_head);
+    if constexpr (GUIDED) {
+      if (wave == 0) {
+        const f4 lv = do_head ? ((const f4 *)lgb)[lane] : f4{0.f, 0.f, 0.f, 0.f};
+        if (do_head && a.logits_out && u >= a.logits_t0 && 4 * lane < a.Q)  // each row's own raw logits
+          ((f4 *)(a.logits_out + ((size_t)bq * (a.n_total - a.logits_t0) + (u - a.logits_t0)) * a.Q))[lane] = lv;
+        if (g == 0) {
+          lgu[0] = lv.x; lgu[1] = lv.y; lgu[2] = lv.z; lgu[3] = lv.w;
+        } else {
+          int pick = 0;
+          if (do_head) {
+            // (classes >= Q, the padding of a 256-wide head, keep their -inf: -inf - -inf would be a NaN)
+            const float lc[4] = {lv.x, lv.y, lv.z, lv.w};
+            float lg[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) lg[k] = 4 * lane + k < a.Q ? guided_logit(lc[k], lgu[k], sm1) : lc[k];
+            pick = choose_class(lg, ss.temperature, a.sampling, ss.top_k, ss.top_p, uni, lane, a.Q);
+            if (u >= a.n_given) next_idx = pick;
+          }
+          idx_prev = idx_cur;  // (one pair of indices: both rows consume the same samples)
+          idx_cur = next_idx;
+          if (ts + 1 < a.t_end) {
+            bind(0);
+            send_h0(epoch + 1);
+            bind(1);
+            send_h0(epoch + 1);
+          }
+          if (lane == 0) {
+            if (do_head) {
+#pragma unroll
+              for (int r = 0; r < 2; ++r) {
+                const size_t row = (size_t)(b + r * nb);
+                if (a.choices_out && u >= a.logits_t0) a.choices_out[row * a.n_total + u] = pick;
+                if (u >= a.n_given) a.samples[row * a.stride + u] = pick;
+              }
+            }
+            hidx[0] = hidx[2] = idx_cur;
+            hidx[1] = hidx[3] = idx_prev;
+          }
+        }
+      }
+    } else
     if (wave == 0) {
       int pick = 0;
       if (do_head) {

@@ -179,8 +179,13 @@ class RingGenerator:
                  batch: int, n_total: int, device, variant: int = N.GEN_AUTO,
                  temperature: float = 0.0, seed: int = 0,
                  context: Optional[torch.Tensor] = None, sampling: str = "reference", top_k: int = 0,
-                 top_p: float = 1.0, rows=None, global_context: Optional[torch.Tensor] = None):
-        """``global_context``: (batch, C) fp32 on the device, one vector per sequence that conditions every step (global
+                 top_p: float = 1.0, rows=None, global_context: Optional[torch.Tensor] = None, guidance=None):
+        """``guidance`` (classifier-free guidance): None (off), one scale or a sequence of ``batch``
+        scales.  The generator then owns 2 * batch rows -- ``samples_all``: rows [0, batch) the unconditional ones,
+        WITHOUT ``global_context`` (the zero vector in its place), rows [batch, 2 batch) the conditional ones with it;
+        both with the same prompt, the same ``context`` and the caller's per-sequence settings (``rows`` included) --
+        and launches ``mvn_generate_guided``; ``samples`` and ``teacher_forced`` expose the ``batch`` conditional rows.
+        ``global_context``: (batch, C) fp32 on the device, one vector per sequence that conditions every step (global
         conditioning): added to every time row of the time-major context copy the kernels read
         (mvn_context_add_global); without ``context`` the copy is filled with it.  ``state_dict`` must then hold the
         layers' context convs.
@@ -197,13 +202,20 @@ class RingGenerator:
         (default b), so its draws do not depend on where in which batch it sits.  The attributes are then lists."""
         self._sampling = N.sampling_rule(sampling)
         self.sampling = sampling
+        self.guidance = None if guidance is None else N.guidance_scales(batch, guidance)  # ValueError before anything is allocated
+        guided = self.guidance is not None
         seq_host = None
-        if rows is not None or N.any_per_sequence(temperature, seed, top_k, top_p):  # ValueError before anything is allocated
+        if guided or rows is not None or N.any_per_sequence(temperature, seed, top_k, top_p):  # ValueError before anything is allocated
             seq_host = N.seq_sampling_array(batch, input_channels, temperature, top_k, top_p, seed, rows)
             entries = [seq_host[b] for b in range(int(batch))]
             temperature, seed = [e.temperature for e in entries], [e.seed for e in entries]
             self.top_k, self.top_p = [e.top_k for e in entries], [e.top_p for e in entries]
             self.rows = [e.row for e in entries]
+            if guided:  # the pair's two rows sample by the same entry (the kernel reads the conditional row's)
+                both = (N.SeqSampling * (2 * int(batch)))()
+                for b, e in enumerate(entries):
+                    both[b] = both[b + int(batch)] = e
+                seq_host = both
         else:
             self.top_k, self.top_p = N.truncation(top_k, top_p)
             temperature, seed = float(temperature), int(seed) & (2 ** 64 - 1)
@@ -217,10 +229,27 @@ class RingGenerator:
         self.Q = input_channels
         self.rf = N.check(self.lib.mvn_receptive_fields(self.dims), "mvn_receptive_fields")
         self.batch, self.n_total = int(batch), int(n_total)
+        self.nrows = 2 * self.batch if guided else self.batch  # rows of state, samples and context the launches see
         with torch.cuda.device(self.device):
-            self.variant = N.check(self.lib.mvn_gen_variant(self.dims, variant, self.batch),
+            if guided and variant == N.GEN_AUTO:  # the best kernel with a guided form that holds the pairs
+                variant = next((v for v in (N.GEN_FOLD, N.GEN_PIPE, N.GEN_GENERIC)
+                                if self.lib.mvn_gen_guided_max_pairs(self.dims, v) >= self.batch
+                                and self.lib.mvn_gen_variant(self.dims, v, self.nrows) == v), N.GEN_GENERIC)
+            self.variant = N.check(self.lib.mvn_gen_variant(self.dims, variant, self.nrows),
                                    "mvn_gen_variant")
-            # (r4: STREAM takes local conditioning too -- the context terms of all layers are formed at the top of a step)
+            if guided:
+                limit = N.guided_max_pairs(self.dims, self.variant)
+                if self.batch > limit:
+                    raise RuntimeError(f"movenet_amd: a guided launch of variant {self.variant} takes at most {limit} "
+                                       f"pairs for these dims ({self.batch} asked for)")
+        if guided:  # the same video for both rows of a pair; the label's vector for the conditional rows only
+            if context is not None:
+                context = torch.cat([context, context], 0)
+            if global_context is not None:
+                if tuple(global_context.shape) != (batch, residual_channels):
+                    raise ValueError(f"global_context must be (batch, {residual_channels}), got {tuple(global_context.shape)}")
+                global_context = torch.cat([torch.zeros_like(global_context), global_context], 0)
+        batch = self.nrows  # (r4: STREAM takes local conditioning too -- the context terms of all layers are formed at the top of a step)
         self.context = None      # (B, C, >= n_total) upsampled video as given
         self.context_tm = None   # (B, n_total, C) time-major copy the kernels read
         if context is not None:
@@ -231,10 +260,10 @@ class RingGenerator:
                                  f"got {tuple(context.shape)}")
             self.context = context.detach().to(torch.float32).contiguous()
             with torch.cuda.device(self.device):
-                self.context_tm = torch.empty(self.batch, self.n_total, residual_channels,
+                self.context_tm = torch.empty(self.nrows, self.n_total, residual_channels,
                                               dtype=torch.float32, device=self.device)
                 N.check(self.lib.mvn_transpose_context(
-                    self.context.data_ptr(), self.context.stride(1), self.batch, residual_channels,
+                    self.context.data_ptr(), self.context.stride(1), self.nrows, residual_channels,
                     self.n_total, self.context_tm.data_ptr(), _stream_ptr(self.device)),
                     "mvn_transpose_context")
         self.global_context = None
@@ -246,19 +275,22 @@ class RingGenerator:
             with torch.cuda.device(self.device):
                 fill = self.context_tm is None
                 if fill:
-                    self.context_tm = torch.empty(self.batch, self.n_total, residual_channels,
+                    self.context_tm = torch.empty(self.nrows, self.n_total, residual_channels,
                                                   dtype=torch.float32, device=self.device)
                 N.check(self.lib.mvn_context_add_global(
-                    self.context_tm.data_ptr(), self.global_context.data_ptr(), self.batch, residual_channels,
+                    self.context_tm.data_ptr(), self.global_context.data_ptr(), self.nrows, residual_channels,
                     self.n_total, int(fill), _stream_ptr(self.device)), "mvn_context_add_global")
         self.temperature, self.seed = temperature, seed
         self._per_seq = None  # device copy of the mvn_seq_sampling array (per-sequence settings only)
+        self._guidance = None  # device copy of the scales, one per pair (guided only)
         with torch.cuda.device(self.device):
             if seq_host is not None:
                 self._per_seq = torch.frombuffer(seq_host, dtype=torch.uint8).to(self.device)
+            if guided:
+                self._guidance = torch.tensor(self.guidance, dtype=torch.float32).to(self.device)
             nw = self.lib.mvn_gen_weights_floats(self.dims, self.variant)
-            ns = self.lib.mvn_gen_state_floats(self.dims, self.batch)
-            self._queue_floats = self.batch * (self.rf - stack_size) * residual_channels
+            ns = self.lib.mvn_gen_state_floats(self.dims, self.nrows)
+            self._queue_floats = self.nrows * (self.rf - stack_size) * residual_channels
             # (MOVENET_DEBUG_GUARD=1, tests: a band of sentinels behind the packed weights and the state -- queues,
             # hand-off granules, placement words -- checked in check_errors())
             self._guard = None
@@ -273,13 +305,24 @@ class RingGenerator:
             else:
                 self.packed = torch.empty(nw, dtype=torch.float32, device=self.device)
                 self.state = torch.zeros(max(ns, 1), dtype=torch.float32, device=self.device)
-            self.samples = torch.zeros(self.batch, self.n_total, dtype=torch.int32, device=self.device)
+            self.samples_all = torch.zeros(self.nrows, self.n_total, dtype=torch.int32, device=self.device)
         self.t = 0          # number of time steps consumed so far
         self.n_given = 1
         # queues primed by one full-sequence forward (MFMA kernels) instead of stepping; the
         # fp16-operand variant primes with the fp16-operand forward: ONE arithmetic throughout
         self.prime_with_forward = True
         self.repack(state_dict)
+
+    @property
+    def samples(self) -> torch.Tensor:
+        """(batch, n_total) int32: every row the launches see -- guided: the conditional rows of ``samples_all``."""
+        return self.samples_all[self.nrows - self.batch:]
+
+    @samples.setter
+    def samples(self, value: torch.Tensor) -> None:  # (GroupedGenerator: a row block of its shared tensor)
+        if self._guidance is not None:
+            raise RuntimeError("movenet_amd: the samples of a guided generator are a view of samples_all")
+        self.samples_all = value
 
     def repack(self, state_dict: Dict[str, torch.Tensor]) -> None:
         self._sd = state_dict
@@ -302,7 +345,7 @@ class RingGenerator:
         is then a no-op until the state is zeroed again."""
         if self.variant not in N.PIPE_VARIANTS:
             return None
-        word = self.lib.mvn_gen_status_offset(self.dims, self.batch)
+        word = self.lib.mvn_gen_status_offset(self.dims, self.nrows)
         return self.state[word:word + 1].view(torch.int32)
 
     def check_errors(self) -> None:
@@ -323,6 +366,17 @@ class RingGenerator:
 
     def _run(self, t_begin: int, t_end: int, n_given: int, logits_out=None, choices_out=None,
              logits_t0: int = 0) -> None:
+        if self._guidance is not None:
+            with torch.cuda.device(self.device):
+                N.check(self.lib.mvn_generate_guided(
+                    self.dims, self.variant, self.packed.data_ptr(), self.state.data_ptr(),
+                    self.samples_all.data_ptr(), self.batch, self.samples_all.stride(0), self.n_total, n_given,
+                    t_begin, t_end, self._per_seq.data_ptr(), self._guidance.data_ptr(),
+                    None if logits_out is None else logits_out.data_ptr(),
+                    None if choices_out is None else choices_out.data_ptr(),
+                    logits_t0, None if self.context_tm is None else self.context_tm.data_ptr(),
+                    self._sampling, _stream_ptr(self.device)), "mvn_generate_guided")
+            return
         if self._per_seq is not None:
             with torch.cuda.device(self.device):
                 N.check(self.lib.mvn_generate_seq(
@@ -353,14 +407,16 @@ class RingGenerator:
             raise ValueError(f"prompt shape {tuple(prompt_idx.shape)} does not fit "
                              f"(batch {self.batch}, n_total {self.n_total})")
         self.reset()
-        self.samples.zero_()
+        self.samples_all.zero_()
         self.samples[:, :P] = prompt_idx.to(torch.int32)
+        if self._guidance is not None:  # the same prompt in both rows of a pair
+            self.samples_all[:self.batch, :P] = self.samples[:, :P]
         self.n_given = P
         if self.prime_with_forward and P >= self.rf:
             # one full-sequence forward over the prompt (MFMA kernels), then copy
             # each layer's most recent d_l inputs into its queue
             from .ops import run_forward
-            idx = self.samples[:, :P].contiguous()
+            idx = self.samples_all[:, :P].contiguous()
             ctx = None if self.context is None else self.context[:, :, :P]
             if self.global_context is not None:  # (the prompt's columns only: the steps read the time-major copy)
                 g = self.global_context[:, :, None]
@@ -369,7 +425,7 @@ class RingGenerator:
                                  f16=self.variant == N.GEN_PIPE_F16)
             with torch.cuda.device(self.device):
                 N.check(self.lib.mvn_gen_prime_from_forward(
-                    self.dims, buf.struct, self.batch, P, self.state.data_ptr(),
+                    self.dims, buf.struct, self.nrows, P, self.state.data_ptr(),
                     _stream_ptr(self.device)), "mvn_gen_prime_from_forward")
         else:
             self._run(0, P - 1, P)
@@ -383,17 +439,21 @@ class RingGenerator:
 
     def teacher_forced(self, indices: torch.Tensor, logits_t0: int):
         """Feed a fully given (B, n_total) history; return (choices, logits) for
-        times >= logits_t0 -- used by the parity tests."""
+        times >= logits_t0 -- used by the parity tests.  Guided: both rows of a pair are fed the history; the
+        conditional rows' (choices, logits) are returned and ``teacher_forced_all`` keeps those of all 2 * batch rows."""
         _require_gpu(indices, "indices")
         assert indices.shape == (self.batch, self.n_total)
         self.reset()
         self.samples.copy_(indices.to(torch.int32))
-        logits = torch.zeros(self.batch, self.n_total - logits_t0, self.Q, dtype=torch.float32,
+        if self._guidance is not None:
+            self.samples_all[:self.batch].copy_(self.samples)
+        logits = torch.zeros(self.nrows, self.n_total - logits_t0, self.Q, dtype=torch.float32,
                              device=self.device)
-        choices = torch.full((self.batch, self.n_total), -1, dtype=torch.int32, device=self.device)
+        choices = torch.full((self.nrows, self.n_total), -1, dtype=torch.int32, device=self.device)
         self._run(0, self.n_total - 1, self.n_total, logits, choices, logits_t0)
         self.t = self.n_total - 1
-        return choices, logits
+        self.teacher_forced_all = (choices, logits)
+        return choices[self.nrows - self.batch:], logits[self.nrows - self.batch:]
 
 
 # Measured cost model of a pipelined launch (DESIGN.md sections 4.1, 4.1c): its P pipelines serve
@@ -486,8 +546,12 @@ def _launch_step_us(dims, variant: int, n: int):
     return t_one if rounds <= 1 else max(t_multi, t_turn * rounds)
 
 
-def auto_plan(dims, batch: int, has_context: bool, calibration=None):
-    """``calibration``: ``{"pipelined": f, "single": f}`` scale factors of the two kernel families on the device at hand
+def auto_plan(dims, batch: int, has_context: bool, calibration=None, guided: bool = False):
+    """``guided`` (classifier-free guidance: ``batch`` pairs): one launch of the best pipelined kernel
+    whose pipelines hold the pairs (``mvn_gen_guided_max_pairs``; FOLD at config 2: 23), groups of at most that many
+    pairs beyond it while the groups' modelled steps -- a launch's latency plus one turn -- add up to less than
+    GENERIC's (the one-launch kernel with a guided form); not measured, the unguided tables stand in.
+    ``calibration``: ``{"pipelined": f, "single": f}`` scale factors of the two kernel families on the device at hand
     (default: ``calibrate(dims)``, measured once at first need -- only batches beyond ONE pipelined launch consult it;
     pass ``{"pipelined": 1.0, "single": 1.0}`` for the tables as measured on the reference box).
 
@@ -502,8 +566,24 @@ def auto_plan(dims, batch: int, has_context: bool, calibration=None):
     pipelines x 16 rounds, 73 us whatever the number), groups of up to 64 until GENERIC's 490 us is
     cheaper (beyond 384)."""
     lib = N.lib()
-    single = N.check(lib.mvn_gen_variant(dims, N.GEN_AUTO, batch), "mvn_gen_variant")
     C = dims.residual_channels
+    if guided:
+        for variant in (N.GEN_FOLD, N.GEN_PIPE):
+            cap = max_pipe_batch(dims, variant, guided=True)
+            model = _PIPELINED_US.get((C, variant))
+            if cap <= 0 or model is None:
+                continue
+            k = -(-batch // cap)
+            if k == 1:
+                return "single", 0, variant
+            # (placeholders, NOT measured: the unguided conditioned GENERIC step -- 290 us at C = 64 --, twice for the two
+            # rows a guided workgroup runs, against a pipelined launch's latency plus one turn per group)
+            generic_us = 290.0 if C == 64 else _T_SINGLE_US.get((C, True), 0.0)
+            if k * (model[1] + model[2]) < 2 * generic_us:
+                return "grouped", -(-batch // k), variant
+            break
+        return "single", 0, N.GEN_GENERIC
+    single = N.check(lib.mvn_gen_variant(dims, N.GEN_AUTO, batch), "mvn_gen_variant")
     best = None
     for variant in (N.GEN_FOLD, N.GEN_PIPE):
         cap = max_pipe_batch(dims, variant)
@@ -525,11 +605,14 @@ def auto_plan(dims, batch: int, has_context: bool, calibration=None):
     return "single", 0, single  # the kernel the C library's AUTO names: every sequence in one launch
 
 
-def max_pipe_batch(dims, variant: int = N.GEN_PIPE) -> int:
-    """Largest batch one PIPE launch holds co-resident for these dims (0: no PIPE kernel)."""
+def max_pipe_batch(dims, variant: int = N.GEN_PIPE, guided: bool = False) -> int:
+    """Largest batch one PIPE launch holds co-resident for these dims (0: no PIPE kernel); ``guided``: the most PAIRS
+    of a guided launch (``mvn_gen_guided_max_pairs``: a pipeline per pair)."""
     lib = N.lib()
     if lib.mvn_gen_variant(dims, variant, 1) < 0:
         return 0
+    if guided:
+        return max(0, int(lib.mvn_gen_guided_max_pairs(dims, variant)))
     lo, hi = 1, 512
     while lo < hi:  # mvn_gen_variant is monotone in the batch
         mid = (lo + hi + 1) // 2
@@ -555,11 +638,15 @@ class GroupedGenerator:
                  state_dict, batch: int, n_total: int, device, group: int, temperature: float = 0.0,
                  seed: int = 0, context: Optional[torch.Tensor] = None, variant: int = N.GEN_PIPE,
                  sampling: str = "reference", top_k: int = 0, top_p: float = 1.0, rows=None,
-                 global_context: Optional[torch.Tensor] = None):
+                 global_context: Optional[torch.Tensor] = None, guidance=None):
+        """``guidance``: as ``RingGenerator``'s; the groups are then groups of ``group`` PAIRS, each sequence keeps
+        its own settings and global row (as with per-sequence settings), and ``samples`` collects the groups'
+        conditional rows after every ``prime`` / ``advance``."""
         N.sampling_rule(sampling)  # ValueError before anything is allocated
         self.sampling = sampling
+        self.guidance = None if guidance is None else N.guidance_scales(batch, guidance)
         per_seq = None
-        if rows is not None or N.any_per_sequence(temperature, seed, top_k, top_p):
+        if self.guidance is not None or rows is not None or N.any_per_sequence(temperature, seed, top_k, top_p):
             host = N.seq_sampling_array(batch, input_channels, temperature, top_k, top_p, seed, rows)
             per_seq = [host[b] for b in range(int(batch))]
             self.top_k, self.top_p = [e.top_k for e in per_seq], [e.top_p for e in per_seq]
@@ -583,19 +670,28 @@ class GroupedGenerator:
                               state_dict, batch=b1 - b0, n_total=n_total, device=device,
                               variant=variant, context=None if context is None else context[b0:b1],
                               global_context=None if global_context is None else global_context[b0:b1],
-                              sampling=sampling, **settings)
-            g.samples = self.samples[b0:b1]  # a contiguous row block of the shared tensor
+                              sampling=sampling, guidance=None if self.guidance is None else self.guidance[b0:b1],
+                              **settings)
+            if self.guidance is None:
+                g.samples = self.samples[b0:b1]  # a contiguous row block of the shared tensor
             self.groups.append(g)
             self.bounds.append((b0, b1))
         self.rf, self.dims = self.groups[0].rf, self.groups[0].dims
 
+    def _collect(self) -> None:  # guided: a group's conditional rows are a view of ITS 2 x pairs rows
+        if self.guidance is not None:
+            for g, (b0, b1) in zip(self.groups, self.bounds):
+                self.samples[b0:b1].copy_(g.samples)
+
     def prime(self, prompt_idx: torch.Tensor) -> None:
         for g, (b0, b1) in zip(self.groups, self.bounds):
             g.prime(prompt_idx[b0:b1])
+        self._collect()
 
     def advance(self, n_new: int) -> None:
         for g in self.groups:
             g.advance(n_new)
+        self._collect()
 
     def check_errors(self) -> None:
         for g in self.groups:

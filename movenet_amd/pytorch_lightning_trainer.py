@@ -50,6 +50,12 @@ class Dance2Music(nn.Module):
         self.model.generate_top_k = config.generate_top_k        # (... a negative k, a p outside (0, 1])
         self.model.generate_top_p = config.generate_top_p
         self.model.loss_rule = getattr(config, "loss_rule", "reference")  # (a config pickled before the field existed)
+        # classifier-free guidance: the scale of the logged samples, and label dropout on train steps --
+        # its mask comes from a host generator of its own, seeded from the run's seed (no draw from torch's)
+        if float(getattr(config, "generate_guidance", 1.0)) != 1.0:
+            self.model.generate_guidance = float(config.generate_guidance)  # (ValueError without global classes)
+        self.model.global_dropout = float(getattr(config, "global_dropout", 0.0))
+        self.model.global_dropout_generator = torch.Generator().manual_seed(torch.initial_seed() & (2 ** 63 - 1))
         self.current_epoch = 0
         self.precision = 32
         self.rank, self.world_size = 0, 1
@@ -145,6 +151,10 @@ class Dance2Music(nn.Module):
         return loss, output, audio, video, labels
 
     def training_step(self, batch, batch_idx):
+        if self.model.global_dropout > 0:
+            # (generate() leaves the model in eval mode, as the reference's does: with samples logged on train steps the
+            # rest of the epoch would run without label dropout, which forward applies in train mode only)
+            self.model.train()
         loss, output, audio, video, labels = self._shared_step(batch, "train")
         return {"loss": loss, "output": output.detach(),
                 "generated_output": self._generate_averaged(audio, video, labels)}
@@ -454,7 +464,8 @@ def train_model(dataset: str, config: TrainingConfig, logger_name: Optional[str]
         # decoded samples go to <model_output_path>/samples/ as .wav files
         from .callbacks import LogSamplesCallback
         callbacks.append(LogSamplesCallback(log_every_n_epochs=config.log_samples_every, log_video=log_video,
-                                            temperature_sweep=getattr(config, "generate_temperature_sweep", None) or ()))
+                                            temperature_sweep=getattr(config, "generate_temperature_sweep", None) or (),
+                                            guidance=float(getattr(config, "generate_guidance", 1.0))))
     trainer = Trainer(
         max_epochs=config.n_epochs, default_root_dir=config.model_output_path,
         gradient_clip_val=config.gradient_clipping,

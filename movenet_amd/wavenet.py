@@ -159,6 +159,49 @@ class WaveNet(nn.Module):
             N.seq_sampling_array(len(value) if N.any_per_sequence(value) else 1, self.input_channels, 1.0, 0, 1.0, value)
         self._gen_seed = value
 
+    # ---- classifier-free guidance of generate() ----------------
+    @property
+    def generate_guidance(self):
+        """1.0 (default: off -- ``generate()`` takes the unguided path untouched), a float s, or a sequence of B floats,
+        one scale per sequence of the batch (``generate()`` refuses another length).  The network then runs twice per
+        step, with the label's vector and with the zero vector in its place (the "no label" condition label dropout
+        trains: ``global_dropout``), and the step draws from l_c + (s - 1) (l_c - l_u).  Needs a model built with
+        ``global_classes``; a value that is not finite is a ValueError."""
+        return getattr(self, "_gen_guidance", 1.0)
+
+    @generate_guidance.setter
+    def generate_guidance(self, value) -> None:
+        scales = N.guidance_scales(len(value) if N.any_per_sequence(value) else 1, value)  # ValueError for anything else
+        if int(getattr(self, "global_classes", 0)) <= 0 and any(s != 1.0 for s in scales):
+            raise ValueError("generate_guidance needs a model built with global_classes (there is no label to guide by)")
+        self._gen_guidance = list(scales) if N.any_per_sequence(value) else scales[0]
+
+    # ---- label dropout of train-mode forward() ---------------------------------
+    @property
+    def global_dropout(self) -> float:
+        """0.0 (default: off, nothing is drawn) or P in [0, 1]: in TRAIN mode ``forward`` replaces the label's vector
+        of each sequence by zeros with probability P -- the mask (``global_dropout_mask``) is drawn from
+        ``global_dropout_generator``, a host ``torch.Generator`` (default: one seeded with 0), never from torch's
+        global generator.  Eval mode and ``generate()`` never drop."""
+        return getattr(self, "_global_dropout", 0.0)
+
+    @global_dropout.setter
+    def global_dropout(self, value: float) -> None:
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.0 <= value <= 1.0:
+            raise ValueError(f"global_dropout must lie in [0, 1], got {value!r}")
+        self._global_dropout = float(value)
+
+    def global_dropout_mask(self, batch: int):
+        """The (batch,) float32 host mask of one train step -- 0 where the label is dropped, 1 elsewhere -- or None
+        when ``global_dropout`` is 0 (nothing is drawn then)."""
+        p = self.global_dropout
+        if p <= 0.0:
+            return None
+        gen = getattr(self, "global_dropout_generator", None)
+        if gen is None:
+            gen = self.global_dropout_generator = torch.Generator().manual_seed(0)
+        return (torch.rand(int(batch), generator=gen) >= p).to(torch.float32)
+
     # ---- which kernels global conditioning runs ----------------------------
     @property
     def global_path(self) -> str:
@@ -288,6 +331,10 @@ class WaveNet(nn.Module):
         ``F.cross_entropy`` of the logits instead (the property's docstring)."""
         from .ops import bf16_mode, global_vector, wavenet_forward, wavenet_forward_loss  # HIP full-sequence kernels
         gvec = global_vector(self, global_features, int(audio.shape[0]))  # (ValueError before anything is launched)
+        if gvec is not None and self.training:  # label dropout: both paths below see an ordinary e
+            keep = self.global_dropout_mask(int(audio.shape[0]))
+            if keep is not None:
+                gvec = gvec * keep.to(device=gvec.device, dtype=gvec.dtype)[:, None]
         bf16_mode(self, video is not None, gvec is not None)  # (refused before the video encoder runs)
         context = None if video is None else self.upsample_video(video)
         if return_loss:
@@ -309,6 +356,13 @@ class WaveNet(nn.Module):
         from .ops import global_vector
         gvec = global_vector(self, global_features, int(audio.shape[0]))
         top_k, top_p, seed = self.generate_top_k, self.generate_top_p, self.generate_seed
+        guidance = self.generate_guidance
+        if N.any_per_sequence(guidance) or guidance != 1.0:  # (1.0: today's path, untouched)
+            guidance = N.guidance_scales(int(audio.shape[0]), guidance)  # ValueError for a wrong length
+            if gvec is None:
+                raise ValueError("generate_guidance needs a model built with global_classes")
+        else:
+            guidance = None
         per_seq = N.any_per_sequence(temperature, seed)
         if per_seq:  # (validates lengths and values; the seed drawn below replaces the placeholder)
             N.seq_sampling_array(int(audio.shape[0]), self.input_channels, temperature, top_k, top_p,
@@ -341,6 +395,8 @@ class WaveNet(nn.Module):
                   temperature=temperature, seed=seed, context=context,
                   global_context=None if gvec is None else gvec.detach().to(torch.float32).contiguous(),
                   sampling=self.generate_sampling, top_k=top_k, top_p=top_p)
+        if guidance is not None:
+            kw["guidance"] = guidance
         def run(variant, group):
             if group:
                 gen = GroupedGenerator(self.layer_size, self.stack_size, self.input_channels,
@@ -357,11 +413,13 @@ class WaveNet(nn.Module):
 
         with torch.cuda.device(audio.device):
             if self._gen_variant == N.GEN_AUTO:
-                kind, group, variant = auto_plan(self._dims, idx.shape[0], context is not None or gvec is not None)
+                kind, group, variant = auto_plan(self._dims, idx.shape[0], context is not None or gvec is not None,
+                                                 guided=guidance is not None)
             else:
                 kind, group, variant = "single", 0, self._gen_variant
-                if variant == N.GEN_PIPE_F16 and idx.shape[0] > max_pipe_batch(self._dims, variant):
-                    kind, group = "grouped", max_pipe_batch(self._dims, variant)  # groups take turns
+                if variant == N.GEN_PIPE_F16 and idx.shape[0] > max_pipe_batch(self._dims, variant,
+                                                                               guided=guidance is not None):
+                    kind, group = "grouped", max_pipe_batch(self._dims, variant, guided=guidance is not None)  # groups take turns
         try:
             gen = run(variant, group if kind == "grouped" else 0)
         except PipeHandoffTimeout:
@@ -370,8 +428,8 @@ class WaveNet(nn.Module):
             with torch.cuda.device(audio.device):
                 lib = N.lib()
                 # (STREAM: C = K = 64, any batch in one launch, conditioned or not -- r4; GENERIC otherwise)
-                fallback = N.GEN_STREAM if lib.mvn_gen_variant(
-                    self._dims, N.GEN_STREAM, idx.shape[0]) == N.GEN_STREAM else N.GEN_GENERIC
+                fallback = N.GEN_STREAM if guidance is None and lib.mvn_gen_variant(
+                    self._dims, N.GEN_STREAM, idx.shape[0]) == N.GEN_STREAM else N.GEN_GENERIC  # (guided: GENERIC)
             self.last_generate_fallback = fallback
             name = {N.GEN_STREAM: "STREAM", N.GEN_GENERIC: "GENERIC"}[fallback]
             print(f"[movenet_amd] generate: pipelined kernel (variant {variant}) timed out waiting for a "
