@@ -74,6 +74,10 @@ constexpr int LDS_FLOATS = N_LDS_MAT * MAT_F + 1536 + 16;
 constexpr int GMAX = 8;
 constexpr int PFS_F = 8;                    // floats per channel and sequence: pf0 pg0 pf1 pg1 | pf2 pg2 - -
 constexpr int LDS_FLOATS_MULTI = LDS_FLOATS + GMAX * C * PFS_F;
+// the head stage keeps, behind its 16 index words there, conv2's partial sums by k-slice: [8 waves][Q]
+constexpr int HEAD_PART_OFF = 16, HEAD_PART_F = 8 * Q;
+constexpr int LDS_FLOATS_ONE = LDS_FLOATS + HEAD_PART_OFF + HEAD_PART_F;  // MULTI = false: the layer stages use LDS_FLOATS of it
+static_assert(LDS_FLOATS_MULTI >= LDS_FLOATS_ONE, "the head's partial sums fit behind the index words");
 }  // namespace fold
 
 // A thread's share of a matrix: 32 floats = 8 float4 of the packed order.  Two formats:
@@ -295,6 +299,9 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
     // the stage's bias vectors live in LDS behind the step vectors (read where needed: the six
     // per-lane copies cost the chain its registers)
     for (int i = tid; i < VEC_F; i += NT) vec[O_VEC + i] = vecs[i];
+    // the step vectors start as zeros: a stage with fewer than LPS real layers never writes the popped entries of the
+    // missing ones, and their (zero) past-tap matrices would multiply whatever the LDS held -- 0 * NaN is a NaN
+    for (int i = tid; i < O_VEC; i += NT) vec[i] = 0.f;
 #pragma unroll
     for (int j = 0; j < LPS; ++j) {
       pf[j] = 0.f; pg[j] = 0.f;
@@ -601,8 +608,9 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
     float *vec = smem + N_LDS_MAT * MAT_F;
     float *zlb = vec;                     // [C] last layer's gated activation
     float *a0 = zlb + C;                  // [C] lrelu(skip)
-    float *a1 = a0 + C;                   // [Q]
-    float *lgb = a1 + Q;                  // [Q] logits
+    float *a1 = a0 + C;                   // [Q] conv1's result: wave w writes, and alone reads, a1[32 w .. 32 w + 31]
+    float *b2l = a1 + Q;                  // [Q] conv2's bias (wave 0 reads it with the partial sums: four registers less)
+    float *part = pfs + HEAD_PART_OFF;    // [8][Q] conv2's partial sums: row w = wave w's k-slice, all outputs
     const float *E0 = tab, *E1 = tab + Q * C;
     const float *hw = a.w + EMB_F + (size_t)(NS - 1) * STAGE_F;
     const f4 *W1p = (const f4 *)hw, *W2p = (const f4 *)(hw + W1_F + Q);
@@ -612,8 +620,10 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
     int *hidx = (int *)pfs;  // MULTI: [GMAX][2] = {idx_cur, idx_prev} of each sequence between its turns
 
     // last layer's skip 1x1: thread (cs = tid >> 3, q8 = tid & 7), 8 inputs;
-    // conv1: thread (o1 = tid >> 1, q1 = tid & 1), 32 inputs; conv2: thread (og = tid >> 3,
-    // q2 = tid & 7), 4 outputs x 32 inputs
+    // conv1: thread (o1 = tid >> 1, q1 = tid & 1), 32 inputs; conv2 by k-slices: thread (wave, lane), outputs
+    // 4 lane .. 4 lane + 3 x inputs 32 wave .. 32 wave + 31 -- the 32 values conv1 has just left in this very wave.
+    // The packed section is pack_head_f32's [r][i8][tid] for thread (og = tid >> 3, q2 = tid & 7): this thread takes
+    // what tid = 8 lane + wave took there (uncoalesced, once per launch)
     const int o1 = tid >> 1, q1 = tid & 1, og = tid >> 3, q2 = tid & 7;
     v2f wsl[4], w1[16], w2[4][16];
     {
@@ -623,10 +633,10 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
       loadn<2>(wsl, WSp, NT, tid);
       loadn<8>(w1, W1p, NT, tid);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) loadn<8>(w2[r], W2p + r * 8 * NT, NT, tid);
+      for (int r = 0; r < 4; ++r) loadn<8>(w2[r], W2p + r * 8 * NT, NT, 8 * lane + wave);
     }
     const float b1r = b1[o1];
-    const float b2r = b2[4 * og + (q2 & 3)];
+    if (tid < Q) b2l[tid] = b2[tid];
     const float bslr = bsl[og];
     __syncthreads();
 
@@ -663,20 +673,39 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
       // skip sum, then the head's first leaky-ReLU (modules.py:140)
       if (q2 == 0) a0[og] = leaky(skin + (sv + bslr));
       lds_barrier();
+      // conv1, and conv2 over the wave's own k-slice: the wave that forms a1[32 w ..] is the one that reads it, so no
+      // barrier and no other wave's LDS traffic stands between the two (the LDS serves a wave's accesses in order)
+      f4 x[8];
       {
-        f4 x[8];
         ldsn<8>(x, a0 + 32 * q1);
         float hsum = dotn<8>(w1, x);
         hsum += dpp_mov<DPP_XOR1>(hsum);
-        if (q1 == 0) a1[o1] = leaky(hsum + b1r);
+        const float h = leaky(hsum + b1r);  // both lanes of a pair hold it
+        if (q1 == 0) a1[o1] = h;
+        asm volatile("" ::: "memory");
+        ldsn<8>(x, a1 + 32 * wave);  // one address per wave: a broadcast, no bank conflict
       }
-      lds_barrier();
       MVN_FINE(b, NS - 1, epoch - 1, 3, 0);
-      head_conv2_f32(w2, a1, lgb, og, q2, b2r);
+      ((f4 *)part)[64 * wave + lane] = f4{dotn<8>(w2[0], x), dotn<8>(w2[1], x), dotn<8>(w2[2], x), dotn<8>(w2[3], x)};
       lds_barrier();
       MVN_FINE(b, NS - 1, epoch - 1, 4, 0);
     };
-    head_loop<C, GRAN, MULTI, SEQ, 2, 0, GUIDED>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, lgb, await, logits);
+    // wave 0: the logits of classes 4 lane .. 4 lane + 3 = the eight slices' partial sums, added as the DPP tree of
+    // head_conv2_f32 adds them -- ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)), then the bias: the same bits
+    auto take = [&](const float *, int) {
+      f4 p[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) p[j] = ((const f4 *)part)[64 * j + lane];
+      const f4 b2v = ((const f4 *)b2l)[lane];
+      f4 r;
+      r.x = (((p[0].x + p[1].x) + (p[2].x + p[3].x)) + ((p[4].x + p[5].x) + (p[6].x + p[7].x))) + b2v.x;
+      r.y = (((p[0].y + p[1].y) + (p[2].y + p[3].y)) + ((p[4].y + p[5].y) + (p[6].y + p[7].y))) + b2v.y;
+      r.z = (((p[0].z + p[1].z) + (p[2].z + p[3].z)) + ((p[4].z + p[5].z) + (p[6].z + p[7].z))) + b2v.z;
+      r.w = (((p[0].w + p[1].w) + (p[2].w + p[3].w)) + ((p[4].w + p[5].w) + (p[6].w + p[7].w))) + b2v.w;
+      return r;
+    };
+    head_loop<C, GRAN, MULTI, SEQ, 2, 0, GUIDED>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, part, await, logits,
+                                                 take);
   }
 }
 
@@ -841,7 +870,7 @@ static int fold_launch_any(const GenArgs &a, const mvn_dims *d, int batch, float
   const bool multi = guided || batch > p.pipes;
   p.fn = guided ? (const void *)gen_fold_kernel<true, true, true> : a.per_seq ? (multi ? (const void *)gen_fold_kernel<true, true> : (const void *)gen_fold_kernel<false, true>)
                    : (multi ? (const void *)gen_fold_kernel<true, false> : (const void *)gen_fold_kernel<false, false>);
-  p.lds_bytes = (multi ? LDS_FLOATS_MULTI : LDS_FLOATS) * sizeof(float);
+  p.lds_bytes = (multi ? LDS_FLOATS_MULTI : LDS_FLOATS_ONE) * sizeof(float);
   // the kernel's own map: whole pipelines inside the XCDs, or every CU (the left-over ones form pipelines across XCDs)
   p.slots = p.pipes <= fold_pipelines(d) ? (p.pipes + 7) / 8 * p.NS : PIPE_XCD_CUS;
   p.batch = batch;

@@ -731,6 +731,8 @@ __device__ __forceinline__ void head_conv2_f32(const v2f (&w2)[4][16], const flo
 //   await(inbox, epoch)            wave 0: wait for the head's input of this step, store it to LDS; false on time-out
 //   logits(inbox, epoch, do_head)  all waves, behind a barrier: the dense head into lgb[256], closed by a barrier
 //                                  (do_head is block-uniform; false: no logits are needed for this step)
+//   take(lgb, lane)                wave 0, behind that barrier: the float4 of logits 4 lane .. 4 lane + 3.  Default: the
+//                                  read of lgb; FOLD sums its waves' partial sums here instead (generate_fold.hip)
 // iflag / hidx: LDS words ([0]: the hand-off's ok flag; MULTI: [GMAX][2] = {idx_cur, idx_prev} of each sequence
 // between its turns).
 // SEQ (mvn_generate_seq): the settings of a step are those of the sequence whose turn it is, a.per_seq[bq], loaded
@@ -740,10 +742,14 @@ __device__ __forceinline__ void head_conv2_f32(const v2f (&w2)[4][16], const flo
 // turn 1 forms the guided logits from the two rows', makes the one choice by the conditional row's settings and opens
 // the next step of BOTH rows (unconditional first: stage 0 serves it first).  No hand-off is added: stage 0 waits for
 // its row's next input one turn longer, through the same bounded waits.
-template <int C, int GRAN, bool MULTI, bool SEQ, int NZ, int NZ_SENT = NZ, bool GUIDED = false, class Await, class Logits>
+struct HeadLgbRead {
+  __device__ __forceinline__ f4 operator()(const float *lgb, int lane) const { return ((const f4 *)lgb)[lane]; }
+};
+template <int C, int GRAN, bool MULTI, bool SEQ, int NZ, int NZ_SENT = NZ, bool GUIDED = false, class Await, class Logits,
+          class Take = HeadLgbRead>
 __device__ __forceinline__ void head_loop(const KArgs<SEQ, GUIDED> &a, u64 *hand, int NS, int nb, int b, int G, bool fast_edge,
                                           const float *E0, const float *E1, int *iflag, int *hidx, const float *lgb,
-                                          Await await, Logits logits) {
+                                          Await await, Logits logits, Take take = Take()) {
   static_assert(GRAN == (1 + NZ) * C && NZ_SENT <= NZ, "residual stream + NZ zero lanes");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, s = NS - 1;
   int bq;  // the sequence whose turn it is: b + g nb
@@ -825,7 +831,7 @@ __device__ __forceinline__ void head_loop(const KArgs<SEQ, GUIDED> &a, u64 *hand
     logits(inbox, epoch, do_head);
     if constexpr (GUIDED) {
       if (wave == 0) {
-        const f4 lv = do_head ? ((const f4 *)lgb)[lane] : f4{0.f, 0.f, 0.f, 0.f};
+        const f4 lv = do_head ? take(lgb, lane) : f4{0.f, 0.f, 0.f, 0.f};
         if (do_head && a.logits_out && u >= a.logits_t0 && 4 * lane < a.Q)  // each row's own raw logits
           ((f4 *)(a.logits_out + ((size_t)bq * (a.n_total - a.logits_t0) + (u - a.logits_t0)) * a.Q))[lane] = lv;
         if (g == 0) {
@@ -868,7 +874,7 @@ __device__ __forceinline__ void head_loop(const KArgs<SEQ, GUIDED> &a, u64 *hand
       int pick = 0;
       if (do_head) {
         // lane i owns classes 4i..4i+3; every reduction is intra-wave (DPP + readlane)
-        const f4 lv = ((const f4 *)lgb)[lane];
+        const f4 lv = take(lgb, lane);
         const float lg[4] = {lv.x, lv.y, lv.z, lv.w};
         // (rows of a.Q logits: the padding of a smaller model is not written; fp16 PIPE takes Q = 256 only)
         if (a.logits_out && u >= a.logits_t0 && 4 * lane < a.Q)
@@ -913,6 +919,7 @@ __device__ __forceinline__ bool pack_head_f32(int i, int C, int W1N, int qm, con
     dst[i] = i - W1_F < qm ? b1[i - W1_F] : 0.f;
   } else if (i < W1_F + Q + W2_F) {
     // conv2: [4 r][8][tid (512)] float4, thread (og = tid>>3, q2 = tid&7): output 4 og + r, inputs 32 q2 ..
+    // (FOLD reads this section through the permutation tid = 8 lane + wave: its wave w owns inputs 32 w .., all outputs)
     const int ii = i - W1_F - Q;
     const int e = ii & 3, v = ii >> 2, tid = v & (NT - 1), rest = v >> 9, r = rest >> 3, i8 = rest & 7;
     const int o = 4 * (tid >> 3) + r, k = 32 * (tid & 7) + 4 * i8 + e;

@@ -92,7 +92,8 @@ elif FOLD and read_fine(fine.ctypes.data, fine.size) == 0:
         print(f"  {nm:52s} {np.median(f[..., i1] - f[..., i0]):7.0f}")
     # the two ends of the pipeline against a middle stage, the sends of phase 2 (thread 256 = the helpers' first
     # lane: slot 8 after the xp' store, 9 after the sk' store) and the head (stage NS - 1: slot 0 inbox complete,
-    # 1 skip term formed, 3 conv1 done, 4 conv2 done, 5 sample sent)
+    # 1 skip term formed, 3 conv1 done in wave 0 (each wave goes on to conv2 over its own k-slice when ITS conv1 is done),
+    # 4 the barrier behind conv2's partial sums, in front of wave 0's slice sum, 5 sample sent)
     f = fine[:B, :NS - 1, 8:, :].astype(np.int64)
     seg2 = [("phase0_chain", 0, 1), ("phase0_helpers", 0, 6), ("phase0_with_barrier", 0, 2), ("phase1_chain", 2, 3),
             ("phase1_helpers", 2, 7), ("phase1_with_barrier", 2, 4), ("phase2_zl_sent", 4, 5), ("phase2_xp_sent", 4, 8),
