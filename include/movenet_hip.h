@@ -458,13 +458,14 @@ int mvn_backward_bf16(const mvn_dims *dims, const mvn_params *params, const mvn_
  * 1 the generic two-kernel forms (any dims), 2 the two fused halves per layer (C = K = 64,
  * csrc/fused_bwd.h), 3 ONE kernel per layer with the input gradient in scatter form
  * (csrc/fused_bwd_l.h, the default at C = K = 64), 4 the bf16 layer kernel of mvn_backward_bf16
- * (csrc/fused_bf16.h).  Tests assert on it so that a silent
+ * (csrc/fused_bf16.h), 5 and 6 forms 3 and 4 with the label's row sums.  Tests assert on it so that a silent
  * fall-back to a slower form cannot pass for the fast one. */
 #define MVN_BWD_FORM_GENERIC 1
 #define MVN_BWD_FORM_HALVES 2
 #define MVN_BWD_FORM_ONE 3
 #define MVN_BWD_FORM_BF16 4
 #define MVN_BWD_FORM_ONE_GLOBAL 5 /* form 3 with the label's row sums: mvn_backward_global */
+#define MVN_BWD_FORM_BF16_GLOBAL 6 /* form 4 with the label's row sums: mvn_backward_bf16_global */
 int mvn_last_backward_form(void);
 
 /* ------------------------------------------------------------------------
@@ -521,6 +522,32 @@ size_t mvn_global_scratch_floats(const mvn_dims *dims, int batch, int t_len);
 int mvn_global_bias_backward(const mvn_dims *dims, const mvn_params *params,
                              const mvn_param_grads *grads, const float *rowsum, const float *e,
                              int batch, float *de, void *stream);
+
+/* The fast path on bf16 operands (csrc/fused_bf16.h): mvn_forward_bf16 / mvn_backward_bf16 with the
+ * label's term.  gbias is mvn_global_bias's, fp32 and never rounded: the layers' filter / gate
+ * accumulators start from gbias[l][b] instead of zero.  The backward's layer kernel sums the rows of
+ * its fp32 df | dg itself (no dfg tensor is written): rowsum (L, batch, 128) receives
+ * sum_t (df | dg)(b, :, t) of every layer, for mvn_global_bias_backward (zero it first: a call without
+ * output columns launches nothing).  scratch: mvn_global_bf16_scratch_floats() floats -- the layer
+ * kernel's weight-gradient slabs, bias partials and row-sum partials, so that short outputs and small
+ * Q run too.  Every sum runs in a fixed order: two calls give the same bits.
+ * Refused before anything is launched or written: MVN_ERR_UNSUPPORTED for residual_channels or
+ * skip_channels != 64, for buf->ctx / fwd->ctx != NULL and for a batch / length the bf16 layer kernels
+ * cannot place (mvn_global_bf16_path returns 0 exactly there, 1 elsewhere; it consults no switch);
+ * MVN_ERR_BAD_ARG for a NULL gbias / scratch / rowsum or scratch_floats below
+ * mvn_global_bf16_scratch_floats().  mvn_last_backward_form() reports MVN_BWD_FORM_BF16_GLOBAL. */
+int mvn_global_bf16_path(const mvn_dims *dims, int batch, int t_len);
+size_t mvn_global_bf16_scratch_floats(const mvn_dims *dims, int batch, int t_len);
+int mvn_forward_bf16_global(const mvn_dims *dims, const mvn_params *params, const int32_t *index,
+                            int index_stride, int batch, int t_len, const mvn_fwd_buffers *buf,
+                            float *out, int normalize, int remove_last, int save, const float *gbias,
+                            void *stream);
+int mvn_backward_bf16_global(const mvn_dims *dims, const mvn_params *params,
+                             const mvn_param_grads *grads, const int32_t *index, int index_stride,
+                             int batch, int t_len, const mvn_fwd_buffers *fwd,
+                             const mvn_bwd_buffers *bwd, const float *out, const float *dout,
+                             int normalize, int remove_last, float *scratch, size_t scratch_floats,
+                             float *rowsum, void *stream);
 
 /* ------------------------------------------------------------------------
  * Local conditioning: video encoder + learned upsampler (movenet/wavenet.py:94-118,

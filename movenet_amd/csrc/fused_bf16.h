@@ -9,8 +9,22 @@
 // gradients, every tensor in HBM (saved activations, A' / P0, the weight-gradient slabs) and the reductions.  The two
 // kernels below keep the dataflow, the buffers and the launch geometry of their exact twins; what they drop is the split
 // (44 vector instructions per eight values there, four v_cvt_pk_bf16_f32 here) and two thirds of the weight images.
+//
+// GLOBAL (mvn_forward_bf16_global / mvn_backward_bf16_global; DESIGN 7.3, choice (a)): the class label's term, ONE fp32
+// 2C-vector gb[l][b] per (layer, sequence) from global_bias_kernel, nothing in it rounded to bf16.
+//   forward   the f | g accumulators START from gb (128 floats of LDS behind br | bs) instead of from zero: one LDS read
+//             per accumulator register and no add in front of tanh / sigmoid (the accumulator-start form: 85.0 us per
+//             layer launch at config 2 against 68.0 for <false>; the add-after-the-product form of
+//             fused_layer64s_bf3_kernel<true> was not built here, so the two forms have NOT been measured against each
+//             other);
+//   backward  r[l][b] = sum_t (df | dg)(b, :, t) from the fp32 tile in LDS behind barrier B2, four registers per thread
+//             as the bias gradients' bsum[], one 128-float partial per workgroup, summed in double and in chunk order by
+//             global_rowsum_reduce_kernel (global_cond.h).  No dfg tensor is written or read.  120.2 us per layer
+//             launch against 119.1 for <false>, plus 6.2 us for the reduce launch.
+// GLOBAL = false is each kernel as it was: every added line sits under `if constexpr (GLOBAL)`.
 #pragma once
 #include "fused_bwd_l.h"
+#include "global_cond.h"
 
 namespace mvn {
 
@@ -82,9 +96,10 @@ __device__ __forceinline__ void fb16_product(f32x16 (&acc)[4], unsigned wa, BV b
   }
 }
 
+template <bool GLOBAL>
 __global__ __launch_bounds__(512, 1) void fused_layer64s_bf16_kernel(FusedFwdPArgs a, int chunks_per_b, int chunk_t) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fb16_lds[];
-  const float *BI = (const float *)(fb16_lds + FB16_W1_BYTES + FB16_W2_BYTES);  // br | bs
+  const float *BI = (const float *)(fb16_lds + FB16_W1_BYTES + FB16_W2_BYTES);  // br | bs (GLOBAL: | gb f rows | gb g rows)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.x / chunks_per_b, ch = blockIdx.x - b * chunks_per_b;
@@ -109,6 +124,9 @@ __global__ __launch_bounds__(512, 1) void fused_layer64s_bf16_kernel(FusedFwdPAr
     }
   } else {
     fb16_stage_weights(fb16_lds, a.wf, a.wg, a.wr, a.ws, a.br, a.bs, tid, 512);
+  }
+  if constexpr (GLOBAL) {
+    if (tid < 128) ((float *)fb16_lds)[FB16_PACK_F + tid] = a.gbias[(size_t)b * 128 + tid];  // (this sequence's f | g rows)
   }
   __syncthreads();
   const unsigned w1a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)fb16_lds + 16u * lane;
@@ -170,7 +188,12 @@ __global__ __launch_bounds__(512, 1) void fused_layer64s_bf16_kernel(FusedFwdPAr
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+      for (int r = 0; r < 16; ++r) {
+        if constexpr (GLOBAL)  // accumulator row = channel (r & 3) + 8 (r >> 2) + 4 lh of block i, the same in every lane
+          acc[i][r] = BI[128 + 32 * i + (r & 3) + 8 * (r >> 2) + cbase];
+        else
+          acc[i][r] = 0.f;
+      }
     fb16_product<8>(acc, w1a, [&](int ks, int e) { return ks < 4 ? xb1[8 * ks + e] : xa0[8 * (ks - 4) + e]; });
     // ---- gate in registers (fp32); tanh / sigmoid leave; z in accumulator order = the next B operand
     float z[32];
@@ -264,10 +287,18 @@ static int launch_fused_layer64s_bf16(const FusedFwdPArgs &a, int batch, hipStre
   if (a.t_end <= a.t_begin || batch <= 0) return MVN_OK;
   int chunks, chunk_t;
   fb_chunks(nt, batch, 1, &chunks, &chunk_t, 256);  // a chunk: whole rounds of the 8 waves' strips
-  const void *fn = (const void *)fused_layer64s_bf16_kernel;
+  if (a.gbias) {  // global conditioning: 128 more floats of LDS hold the sequence's bias vector
+    const void *fn = (const void *)fused_layer64s_bf16_kernel<true>;
+    const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(fused_layer64s_bf16<global>)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(fused_layer64s_bf16_kernel<true>, dim3(chunks * batch), dim3(512), FB16_LDS_BYTES + 128 * 4, s, a, chunks,
+                       chunk_t);
+    return MVN_OK;
+  }
+  const void *fn = (const void *)fused_layer64s_bf16_kernel<false>;
   const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(fused_layer64s_bf16)");
   if (rc) return rc;
-  hipLaunchKernelGGL(fused_layer64s_bf16_kernel, dim3(chunks * batch), dim3(512), FB16_LDS_BYTES, s, a, chunks, chunk_t);
+  hipLaunchKernelGGL(fused_layer64s_bf16_kernel<false>, dim3(chunks * batch), dim3(512), FB16_LDS_BYTES, s, a, chunks, chunk_t);
   return MVN_OK;
 }
 
@@ -280,9 +311,10 @@ static int launch_fused_layer64s_bf16(const FusedFwdPArgs &a, int batch, hipStre
 constexpr int FBL16_WIMG_BYTES = 2 * 8 * 1024;  // [c block][k-step][lane][8 bf16]
 constexpr int FBL16_LDS_BYTES = 3 * FBL_TILE_F * 4 + FBL16_WIMG_BYTES;
 
+template <bool GLOBAL>
 __global__ __launch_bounds__(512, 1) void bwd_layer64_bf16_kernel(FusedBwdLArgs a, int chunks_per_b, int chunk_t,
                                                                  float *__restrict__ rs_bias_part, float *__restrict__ rs_part,
-                                                                 float *__restrict__ fg_part) {
+                                                                 float *__restrict__ fg_part, float *__restrict__ g_part) {
   constexpr int C = FB_C, LD = W2_LD, TT = W2_T;
   extern __shared__ __attribute__((aligned(16))) float fbl16_lds[];
   float (*U)[LD] = (float (*)[LD])fbl16_lds;                      // [dxo; dskip], then [x(t - d); x(t)]
@@ -332,6 +364,8 @@ __global__ __launch_bounds__(512, 1) void bwd_layer64_bf16_kernel(FusedBwdLArgs 
   const int srow = tid >> 4, st = 4 * (tid & 15);
   f4 r_ga[2], r_gp[2], r_ds[2], r_th[2], r_sg[2], r_x[4];
   float bsum[4] = {0.f, 0.f, 0.f, 0.f};
+  // (GLOBAL only: row sums of df | dg, rows 32 p + srow; <false> never touches it and the compiler drops it)
+  [[maybe_unused]] float gsum[GLOBAL ? 4 : 1] = {};
   bool z_ga = false, z_ds = false;
   const __amdgpu_buffer_rsrc_t gab = fb_rsrc(a.ga.p + (size_t)b * a.ga.sb);
   const __amdgpu_buffer_rsrc_t gpb = fb_rsrc(a.gp.p + (size_t)b * a.gp.sb);
@@ -513,6 +547,24 @@ __global__ __launch_bounds__(512, 1) void bwd_layer64_bf16_kernel(FusedBwdLArgs 
 #pragma unroll
     for (int p = 0; p < 4; ++p) *(f4 *)&U[32 * p + srow][st] = r_x[p];
     __syncthreads();  // B2: df | dg and the x rows are staged
+    if constexpr (GLOBAL) {
+      // the label's term: this thread's share of the rows of df | dg (fp32, unrounded), columns [t_lo, te) only.  A
+      // column outside is zero already -- its tanh, sigmoid, dxo and dskip were staged as zeros (ld4_edge), so
+      // dz = 0 and df = dg = 0 x 0 -- but the mask costs an edge tile four compares and leaves nothing to a stale value.
+      const int tg = t0 + st;
+      const bool full = t0 >= a.t_lo && t0 + TT <= te;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        f4 v = *(const f4 *)&Gt[32 * p + srow][st];
+        if (!full) {
+          v.x = (tg >= a.t_lo && tg < te) ? v.x : 0.f;
+          v.y = (tg + 1 >= a.t_lo && tg + 1 < te) ? v.y : 0.f;
+          v.z = (tg + 2 >= a.t_lo && tg + 2 < te) ? v.z : 0.f;
+          v.w = (tg + 3 >= a.t_lo && tg + 3 < te) ? v.w : 0.f;
+        }
+        gsum[p] += (v.x + v.y) + (v.z + v.w);
+      }
+    }
     const bool spread = more && interior(t0 + TT);
     if (more && !spread) gload_r_edge(t0 + TT);
     // ---- phase 2: this wave's K half of its tap's product for both 32-step blocks, and its two blocks of the
@@ -635,12 +687,25 @@ __global__ __launch_bounds__(512, 1) void bwd_layer64_bf16_kernel(FusedBwdLArgs 
     v += __shfl_xor(v, 8, 64);
     if ((tid & 15) == 0) rs_bias_part[(size_t)blockIdx.x * 128 + (p < 2 ? 32 * p : C + 32 * (p - 2)) + srow] = v;
   }
+  if constexpr (GLOBAL) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      float v = gsum[p];  // 16 lanes share a row
+      v += __shfl_xor(v, 1, 64);
+      v += __shfl_xor(v, 2, 64);
+      v += __shfl_xor(v, 4, 64);
+      v += __shfl_xor(v, 8, 64);
+      if ((tid & 15) == 0) g_part[(size_t)blockIdx.x * 128 + 32 * p + srow] = v;  // rows [0, 64): df, [64, 128): dg
+    }
+  }
 }
 
-// launch_bwd_layer64 for the bf16 kernel (audio-only layers: no df | dg output); same plan, same reduce
+// launch_bwd_layer64 for the bf16 kernel (no df | dg output); same plan, same reduce.  g_part / rowsum (both or neither):
+// the GLOBAL instantiation leaves a 128-float partial of the df | dg row sums per workgroup in g_part (as many as the
+// plan's bias partials), and rowsum (batch, 128) of this layer receives their sums.
 template <class RsOp, class FgOp>
 static int launch_bwd_layer64_bf16(const FusedBwdLArgs &a, const RsOp &rs, const FgOp &fg, int batch, const FusedBwdLPlan &pl,
-                                   hipStream_t s) {
+                                   hipStream_t s, float *g_part = nullptr, float *rowsum = nullptr) {
   if (pl.chunks <= 0) return MVN_OK;
   const int ldt = a.th.ld;
   if (a.dfg.p || a.sg.ld != ldt || a.xin.ld != ldt || a.oa.ld != ldt || a.op.ld != ldt || a.gp.ld != ldt ||
@@ -649,14 +714,24 @@ static int launch_bwd_layer64_bf16(const FusedBwdLArgs &a, const RsOp &rs, const
     return MVN_ERR_BAD_ARG;
   }
   const int n = pl.chunks * batch;
-  const void *fn = (const void *)bwd_layer64_bf16_kernel;
+  const bool glob = g_part != nullptr;
+  if (glob != (rowsum != nullptr)) {
+    set_error("bwd_layer64_bf16: g_part and rowsum go together");
+    return MVN_ERR_BAD_ARG;
+  }
+  const void *fn = glob ? (const void *)bwd_layer64_bf16_kernel<true> : (const void *)bwd_layer64_bf16_kernel<false>;
   const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(bwd_layer64_bf16)");
   if (rc) return rc;
-  void *args[] = {(void *)&a, (void *)&pl.chunks, (void *)&pl.chunk_t, (void *)&pl.bias, (void *)&pl.rs, (void *)&pl.fg};
+  void *args[] = {(void *)&a, (void *)&pl.chunks, (void *)&pl.chunk_t, (void *)&pl.bias, (void *)&pl.rs, (void *)&pl.fg,
+                  (void *)&g_part};
   if (check_hip(hipLaunchKernel(fn, dim3(n), dim3(512), args, (size_t)FBL16_LDS_BYTES, s), "bwd_layer64_bf16"))
     return MVN_ERR_LAUNCH;
   hipLaunchKernelGGL((reduce_layer64_kernel<RsOp, FgOp>), dim3(260 + 128 * 128 / 32), dim3(32 * RED_SEG), 0, s, rs, pl.rs,
                      pl.bias, n, fg, pl.fg, n);
+  if (glob) {  // (a failed launch would leave the caller's zero-filled rowsum: silently zero context gradients)
+    hipLaunchKernelGGL(global_rowsum_reduce_kernel, dim3(batch), dim3(128), 0, s, g_part, pl.chunks, rowsum);
+    return check_hip(hipGetLastError(), "bwd_layer64_bf16<global>: reduce launches");
+  }
   return MVN_OK;
 }
 

@@ -4,7 +4,7 @@
 // constant in time:  f_l += Wcf_l e_b + bcf_l,  g_l += Wcg_l e_b + bcg_l.
 //   general path: context_add_global_kernel adds e_b to (or fills with it) every time row of the generators' time-major
 //                 context copy; the conditioned kernels then run as they are.
-//   fast path (C = K = 64, no video, fp32): the term is ONE 2C-vector per (layer, sequence).
+//   fast path (C = K = 64, no video): the term is ONE 2C-vector per (layer, sequence).  fp32:
 //     forward   global_bias_kernel            gb[l][b] = [Wcf_l e_b + bcf_l | Wcg_l e_b + bcg_l], all layers in one launch;
 //                                             fused_layer64s_bf3_kernel<true> adds it in front of tanh / sigmoid
 //     backward  global_rowsum_kernel          r[l][b] = sum over the layer's valid columns of (df | dg)(b, :, t), read from
@@ -13,6 +13,9 @@
 //                                             price of one write and one read of (B, 2C, T) floats per layer)
 //               global_bias_backward_kernel   dWcf_l = sum_b r_f (x) e_b, dbcf_l = sum_b r_f (same for the gate),
 //                                             de_b = sum_l Wcf_l^T r_f + Wcg_l^T r_g
+//   bf16 (fused_bf16.h, the GLOBAL instantiations; choice (a)): the same global_bias_kernel and
+//   global_bias_backward_kernel around layer kernels that start f | g from gb and sum the rows of df | dg themselves;
+//               global_rowsum_reduce_kernel   r[l][b] = sum over the layer kernel's workgroups of their partial row sums
 // Every sum runs in a fixed order (the backward's in double): no atomics, the same bits run to run.
 #pragma once
 
@@ -76,6 +79,17 @@ __global__ __launch_bounds__(256) void global_rowsum_kernel(const float *__restr
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   if (lane == 0) r[(size_t)b * 128 + row] = (float)v;
+}
+
+// The bf16 layer backward's row sums (fused_bf16.h: bwd_layer64_bf16_kernel<true> sums df | dg inside the kernel, one
+// 128-float partial per workgroup, workgroup = sequence b x chunk ch): r[b][row] = sum_ch g_part[b chunks + ch][row], in
+// double and in chunk order.  grid (batch), 128 threads.
+__global__ __launch_bounds__(128) void global_rowsum_reduce_kernel(const float *__restrict__ g_part, int chunks,
+                                                                   float *__restrict__ r) {
+  const int b = blockIdx.x, row = threadIdx.x;
+  double acc = 0.0;
+  for (int ch = 0; ch < chunks; ++ch) acc += (double)g_part[((size_t)b * chunks + ch) * 128 + row];
+  r[(size_t)b * 128 + row] = (float)acc;
 }
 
 // grid (layers of this launch + batch), 256 threads.  r: (layers, batch, 128) from this launch's first layer on.

@@ -1101,6 +1101,25 @@ static size_t global_scratch_floats(const mvn_dims *dims, const Geometry &g, int
   const int want = std::max(1, 2 * fb_device_cus() / std::max(batch, 1));
   return 2 * (size_t)g.act + (size_t)std::max(1, std::min(tiles, want)) * batch * GC_PER_WG;
 }
+// Global conditioning in bf16 (fused_bf16.h, the GLOBAL instantiations): what the bf16 layer kernels place, whatever
+// the switches say (the bf16 entry points consult none).  The backward's scratch holds, per workgroup of the layer
+// kernel, its two slabs, its bias partials and its partial row sums of df | dg; the scatter pairs stay where the
+// audio-only bf16 backward keeps them (no dfg tensor is written, so its halves are free).
+static bool global_bf16_path(const Geometry &g, int batch) {
+  return g.C == 64 && g.Kc == 64 && batch >= 1 && g.L < 4095 && g.Tp <= (1 << 21) && g.Sp <= (1 << 21) &&
+         rows_fit_rsrc(2 * g.C, g.Tp);
+}
+constexpr size_t GC16_PER_WG = GC_PER_WG + 128;
+static size_t global_bf16_wgs(const mvn_dims *dims, const Geometry &g, int batch) {
+  // workgroups of the layer kernel at its longest layer (one per CU, never more than its tiles: fb_chunks)
+  const int t_lo = dilation_of(dims, 0), nt = std::max(1, g.T - (t_lo & ~TILE_ALIGN));
+  const int tiles = (nt + W2_T - 1) / W2_T;
+  const int want = std::max(1, fb_device_cus() / std::max(batch, 1));
+  return (size_t)std::max(1, std::min(tiles, want)) * batch;
+}
+static size_t global_bf16_scratch_floats(const mvn_dims *dims, const Geometry &g, int batch) {
+  return global_bf16_wgs(dims, g, batch) * GC16_PER_WG;
+}
 static void global_cond_tables(const mvn_params *p, int l0, int n, GlobalCondArgs *ga) {
   for (int i = 0; i < GC_LAYERS; ++i) {
     const int l = l0 + std::min(i, n - 1);
@@ -1121,7 +1140,7 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
   int rc = make_geometry(dims, batch, t_len, g);
   if (rc) return rc;
   if (bf16) {  // (decided before any launch: there is no fp32 fall-back)
-    rc = bf16_supported("mvn_forward_bf16", g, buf && buf->ctx != nullptr);
+    rc = bf16_supported(gbias ? "mvn_forward_bf16_global" : "mvn_forward_bf16", g, buf && buf->ctx != nullptr);
     if (rc) return rc;
   }
   if (!p || !buf || !buf->acts || !buf->z || !buf->skip || !buf->a1 ||
@@ -1140,7 +1159,7 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
     set_error("mvn_forward: context given without context-conv parameters / ctx_ld < t_len");
     return MVN_ERR_BAD_ARG;
   }
-  if (gbias && (buf->ctx || !global_forward_fast(g))) {
+  if (gbias && !bf16 && (buf->ctx || !global_forward_fast(g))) {
     set_error("mvn_forward_global: needs residual = skip channels = 64, no context and the bf16 x 3 strip kernel "
               "(mvn_global_fast_path)");
     return MVN_ERR_UNSUPPORTED;
@@ -1205,6 +1224,7 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
         }
         fp.wpack = buf->z + (size_t)l * FB16_PACK_F;
       }
+      if (gbias) fp.gbias = gbias + (size_t)l * batch * 128;  // (global conditioning: f | g start from the label's term)
       const int rc2 = launch_fused_layer64s_bf16(fp, batch, s);
       if (rc2) return rc2;
       A += d;
@@ -1464,7 +1484,7 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
     }
   }
   const bool has_ctx = fwd->ctx != nullptr;
-  if (glob && (!gpair || has_ctx || bf16 || !global_backward_fast(dims, g, batch) ||
+  if (glob && !bf16 && (!gpair || has_ctx || !global_backward_fast(dims, g, batch) ||
                gpair_floats < 2 * (size_t)g.act + (size_t)batch * GC_PER_WG)) {
     set_error("mvn_backward_global: needs the one-kernel layer backward at residual = skip channels = 64 without context "
               "(mvn_global_fast_path)");
@@ -1494,14 +1514,38 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
       sc_bias = bwd->da1 + sc_slab_floats;
     }
   }
+  float *g_part = nullptr;  // bf16 + labels: the layer kernel's partial row sums of df | dg, one 128-vector per workgroup
   if (bf16) {  // (decided before any launch: there is no fp32 fall-back)
-    rc = bf16_supported("mvn_backward_bf16", g, has_ctx);
+    rc = bf16_supported(glob ? "mvn_backward_bf16_global" : "mvn_backward_bf16", g, has_ctx);
     if (rc) return rc;
+    if (glob) {
+      // the caller's scratch (mvn_global_bf16_scratch_floats): slabs, bias partials, row-sum partials of n_fit
+      // workgroups -- independent of what da1 or the forward's z scratch hold (short outputs, small Q)
+      if (!gpair || !global_bf16_path(g, batch) || gpair_floats < global_bf16_scratch_floats(dims, g, batch)) {
+        set_error("mvn_backward_bf16_global: scratch missing or smaller than mvn_global_bf16_scratch_floats()");
+        return MVN_ERR_BAD_ARG;
+      }
+      const size_t n_fit = gpair_floats / GC16_PER_WG, per_wg = GC_PER_WG - 128;
+      // never more workgroups than mvn_backward_bf16 would place at this shape (its slabs live in da1, else in the
+      // forward's z scratch -- below): both passes then cut a sequence into the same chunks, and a zero label term gives
+      // the audio-only pass's gradients to the bit.  Where that pass places nothing, the scratch alone decides.
+      size_t n_audio = std::min(sc_slab ? sc_slab_floats / per_wg : 0, sc_bias ? sc_bias_floats / 128 : 0);
+      if (n_audio < (size_t)batch && fwd->z) {
+        const size_t total = (size_t)g.act, nz = total / GC_PER_WG;
+        n_audio = std::min((total - nz * 128) / per_wg, nz);
+      }
+      const size_t n_use = n_audio >= (size_t)batch ? std::min(n_fit, n_audio) : n_fit;
+      sc_slab = gpair;
+      sc_slab_floats = n_use * per_wg;
+      sc_bias = gpair + n_fit * per_wg;
+      sc_bias_floats = n_use * 128;
+      g_part = sc_bias + n_fit * 128;  // n_fit * 128 floats: the plan never places more workgroups than n_use <= n_fit
+    }
     FusedBwdLPlan pl0;
     auto fits = [&]() {
       return sc_bias && g.L < 4095 && bwd_layer64_plan(A_lo[1], T, batch, sc_bias, sc_bias_floats, sc_slab, sc_slab_floats, &pl0);
     };
-    if (!fits() && fwd->z) {
+    if (!fits() && fwd->z && !glob) {
       // short outputs (da1 is (B, Q, Sp)): the slabs go to the forward's z scratch instead, which holds nothing the layer
       // loop reads -- the bf16 forward keeps z in registers and its weight images there, and the head's backward, which
       // may stage its own images in it, runs before the loop on the same stream
@@ -1653,7 +1697,7 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
     set_error("mvn_backward_global: the one-kernel layer backward cannot run these buffers");
     return MVN_ERR_UNSUPPORTED;
   }
-  g_last_bwd_form = bf16 ? MVN_BWD_FORM_BF16 : glob ? MVN_BWD_FORM_ONE_GLOBAL : scatter ? MVN_BWD_FORM_ONE : MVN_BWD_FORM_GENERIC;
+  g_last_bwd_form = bf16 ? (glob ? MVN_BWD_FORM_BF16_GLOBAL : MVN_BWD_FORM_BF16) : glob ? MVN_BWD_FORM_ONE_GLOBAL : scatter ? MVN_BWD_FORM_ONE : MVN_BWD_FORM_GENERIC;
   if (scatter) {
     int po = 1 ^ ((g.L - 1) & 1);  // (so that layer 0 writes pair 1 and the dense dx0 can go to dx_a)
     for (int l = g.L - 1; l >= 0; --l) {
@@ -1670,7 +1714,7 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
       fa.sg = act_view(fwd->sg + (size_t)l * g.act, batch, C, g.Tp);
       fa.xin = act_view(fwd->acts + (size_t)l * g.act, batch, C, g.Tp);
       fa.oa = spair[po][0]; fa.op = spair[po][1];
-      fa.dfg = (has_ctx || glob) ? dfg : Act{nullptr, 0, 0};
+      fa.dfg = (has_ctx || (glob && !bf16)) ? dfg : Act{nullptr, 0, 0};
       WgRsOp wr;
       wr.t_begin = t_lo; wr.t_end = T; wr.C = C; wr.Kc = Kc; wr.t_skip0 = t_skip0; wr.t_base = g.t_base;
       wr.dxo = fa.ga; wr.dskip = dskip; wr.th = fa.th; wr.sg = fa.sg;
@@ -1684,9 +1728,11 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
         set_error("mvn_backward: the fused layer backward lost its scratch at layer %d", l);
         return MVN_ERR_BAD_ARG;
       }
-      rc = bf16 ? launch_bwd_layer64_bf16(fa, wr, wf, batch, pl, s) : launch_bwd_layer64(fa, wr, wf, batch, pl, s);
+      // (bf16 + labels: the row sums come out of the layer kernel itself, no dfg tensor -- fused_bf16.h)
+      rc = bf16 ? launch_bwd_layer64_bf16(fa, wr, wf, batch, pl, s, g_part, g_part ? grow + (size_t)l * batch * 128 : nullptr)
+                : launch_bwd_layer64(fa, wr, wf, batch, pl, s);
       if (rc) return rc;
-      if (glob)  // the label's term: row sums of df | dg over the layer's valid columns (global_cond.h)
+      if (glob && !bf16)  // the label's term: row sums of df | dg over the layer's valid columns (global_cond.h)
         hipLaunchKernelGGL(global_rowsum_kernel, dim3(32, batch), dim3(256), 0, s, bwd->dfg, (long long)2 * C * g.Tp, g.Tp,
                            t_lo, T, grow + (size_t)l * batch * 128);
       if (has_ctx) {  // (behind the layer's reduce: the slab scratch is free again)
@@ -1973,6 +2019,67 @@ int mvn_backward_global(const mvn_dims *dims, const mvn_params *p, const mvn_par
   }
   return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_,
                        false, scratch, scratch_floats, rowsum);
+}
+
+int mvn_global_bf16_path(const mvn_dims *dims, int batch, int t_len) {
+  Geometry g;
+  if (make_geometry(dims, batch, t_len, g) || batch < 1) return 0;
+  return global_bf16_path(g, batch) ? 1 : 0;
+}
+
+size_t mvn_global_bf16_scratch_floats(const mvn_dims *dims, int batch, int t_len) {
+  Geometry g;
+  if (make_geometry(dims, batch, t_len, g) || batch < 1) return 0;
+  return global_bf16_scratch_floats(dims, g, batch);
+}
+
+// The refusals of the two labelled bf16 entry points, in the order the header documents them, all in front of the
+// first launch: the dims, a context, a batch / length the bf16 layer kernels cannot place (MVN_ERR_UNSUPPORTED).
+static int bf16_global_supported(const char *what, const mvn_dims *dims, int batch, int t_len, bool has_ctx, Geometry &g) {
+  int rc = make_geometry(dims, batch, t_len, g);
+  if (rc) return rc;
+  rc = bf16_supported(what, g, has_ctx);
+  if (rc) return rc;
+  if (batch >= 1 && !global_bf16_path(g, batch)) {
+    set_error("%s: the bf16 layer kernels cannot place batch %d, t_len %d (mvn_global_bf16_path)", what, batch, t_len);
+    return MVN_ERR_UNSUPPORTED;
+  }
+  return MVN_OK;
+}
+
+int mvn_forward_bf16_global(const mvn_dims *dims, const mvn_params *p, const int32_t *index, int index_stride,
+                            int batch, int t_len, const mvn_fwd_buffers *buf, float *out, int normalize,
+                            int remove_last, int save, const float *gbias, void *stream_) {
+  Geometry g;
+  const int rc = bf16_global_supported("mvn_forward_bf16_global", dims, batch, t_len, buf && buf->ctx != nullptr, g);
+  if (rc) return rc;
+  if (!gbias) {
+    set_error("mvn_forward_bf16_global: gbias is NULL");
+    return MVN_ERR_BAD_ARG;
+  }
+  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_,
+                      false, true, gbias);
+}
+
+int mvn_backward_bf16_global(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
+                             const int32_t *index, int index_stride, int batch, int t_len,
+                             const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
+                             const float *dout, int normalize, int remove_last, float *scratch, size_t scratch_floats,
+                             float *rowsum, void *stream_) {
+  Geometry g;
+  const int rc = bf16_global_supported("mvn_backward_bf16_global", dims, batch, t_len, fwd && fwd->ctx != nullptr, g);
+  if (rc) return rc;
+  if (!scratch || !rowsum) {
+    set_error("mvn_backward_bf16_global: scratch / rowsum is NULL");
+    return MVN_ERR_BAD_ARG;
+  }
+  if (batch >= 1 && scratch_floats < global_bf16_scratch_floats(dims, g, batch)) {
+    set_error("mvn_backward_bf16_global: scratch holds %zu floats, mvn_global_bf16_scratch_floats() asks for %zu", scratch_floats,
+              global_bf16_scratch_floats(dims, g, batch));
+    return MVN_ERR_BAD_ARG;
+  }
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_,
+                       true, scratch, scratch_floats, rowsum);
 }
 
 int mvn_backward_scratch(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,

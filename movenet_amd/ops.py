@@ -107,7 +107,8 @@ def run_forward(dims: N.Dims, sd: Dict[str, torch.Tensor], idx: torch.Tensor, no
     product (mvn_forward_f16; inference and generator priming).  ``bf16``: bf16 operands /
     fp32 accumulation in the layers' products (mvn_forward_bf16; trains with mvn_backward_bf16).
     ``gvec``: (B, C) fp32 global vectors on the fast path of global conditioning (mvn_global_bias +
-    mvn_forward_global: C = K = 64, no ``ctx``; the caller has asked mvn_global_fast_path)."""
+    mvn_forward_global, with ``bf16`` mvn_forward_bf16_global: C = K = 64, no ``ctx``; the caller has asked
+    mvn_global_fast_path / mvn_global_bf16_path)."""
     lib = N.lib()
     _require_gpu(idx, "audio")
     dense = None
@@ -133,7 +134,7 @@ def run_forward(dims: N.Dims, sd: Dict[str, torch.Tensor], idx: torch.Tensor, no
         name = "mvn_forward_f16" if f16 else "mvn_forward_bf16" if bf16 else "mvn_forward"
         tail = ()
         if gvec is not None:  # one 2C-vector per (layer, sequence) instead of a context product per column
-            name = "mvn_forward_global"
+            name = "mvn_forward_bf16_global" if bf16 else "mvn_forward_global"
             gbias = (torch.empty if buf.guard is None else buf.guard.empty)((L, B, 128), dtype=torch.float32, device=dev)
             N.check(lib.mvn_global_bias(dims, params, gvec.data_ptr(), B, gbias.data_ptr(), _stream_ptr(dev)),
                     "mvn_global_bias")
@@ -265,9 +266,14 @@ def _run_backward(ctx_, params, out, dout, fill_dlogit):
         if gvec is not None:
             # global conditioning, fast path: the layer kernel leaves df | dg in the dfg tensor (its scatter pairs move
             # to a scratch of their own), their row sums land in `rowsum` and one kernel turns those into the
-            # context-conv gradients and the gradient of the global vectors
-            name = "mvn_backward_global"
-            n_scratch = int(lib.mvn_global_scratch_floats(dims, B, T))
+            # context-conv gradients and the gradient of the global vectors.  bf16: the layer kernel sums the rows
+            # itself; the scratch holds its slabs and partial sums
+            if name == "mvn_backward_bf16":
+                name = "mvn_backward_bf16_global"
+                n_scratch = int(lib.mvn_global_bf16_scratch_floats(dims, B, T))
+            else:
+                name = "mvn_backward_global"
+                n_scratch = int(lib.mvn_global_scratch_floats(dims, B, T))
             scratch = alloc((n_scratch,), **f32)
             rowsum = alloc((L, B, 128), **f32)
             rowsum.zero_()
@@ -460,7 +466,9 @@ def _tagged_dims(dims, f16: bool = False, context=None, bf16: bool = False, loss
 
 def bf16_mode(model, conditioned: bool, labelled: bool = False) -> bool:
     """Whether ``model.forward_precision`` asks for the bf16 layer kernels; raises ValueError, before
-    anything is launched, for what they do not run (mvn_forward_bf16 / mvn_backward_bf16 refuse the same)."""
+    anything is launched, for what they do not run (mvn_forward_bf16 / mvn_backward_bf16 refuse the same).  Labels run
+    in bf16 only where the model asks for the one-vector-per-layer path by name (``global_path = "bias"``:
+    mvn_forward_bf16_global / mvn_backward_bf16_global); "auto" and "context" refuse them as before."""
     if getattr(model, "forward_precision", "fp32") != "bf16":
         return False
     C, K = model._dims.residual_channels, model._dims.skip_channels
@@ -469,8 +477,9 @@ def bf16_mode(model, conditioned: bool, labelled: bool = False) -> bool:
                          f"got {C} and {K}")
     if conditioned:
         raise ValueError("forward_precision 'bf16' runs audio-only models: no video context")
-    if labelled:
-        raise ValueError("forward_precision 'bf16' runs audio-only models: no global conditioning (global_features)")
+    if labelled and getattr(model, "global_path", "auto") != "bias":
+        raise ValueError("forward_precision 'bf16' runs audio-only models: no global conditioning (global_features) "
+                         "unless global_path is 'bias'")
     return True
 
 
@@ -505,10 +514,27 @@ def global_vector(model, global_features, batch: int):
 def _global_plan(model, context, gvec, batch: int, t_len: int):
     """(context, gvec) as the autograd nodes take them.  Fast path (C = K = 64, fp32, no video, ``model.global_path ==
     "auto"`` and mvn_global_fast_path grants the shape under the process's kernel switches): the vectors go in as they
-    are.  General path: they join the context as a column constant in time and the conditioned kernels run."""
+    are.  General path: they join the context as a column constant in time and the conditioned kernels run.
+    ``global_path == "bias"`` requires the one-vector-per-layer path -- fp32: that fast path; bf16: the labelled bf16
+    layer kernels, where mvn_global_bf16_path grants the shape -- and raises ValueError where it does not exist."""
     if gvec is None:
         return context, None
     dims = model._dims
+    if getattr(model, "global_path", "auto") == "bias":
+        precision = model.forward_precision
+        if context is not None:
+            raise ValueError("global_path 'bias' runs models without a video context")
+        if dims.residual_channels != 64 or dims.skip_channels != 64:
+            raise ValueError("global_path 'bias' needs residual_channels = skip_channels = 64, "
+                             f"got {dims.residual_channels} and {dims.skip_channels}")
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f"global_path 'bias' runs forward_precision 'fp32' or 'bf16', not {precision!r}")
+        with torch.cuda.device(gvec.device):
+            ask = "mvn_global_bf16_path" if precision == "bf16" else "mvn_global_fast_path"
+            if getattr(N.lib(), ask)(dims, batch, t_len) != 1:
+                raise ValueError(f"global_path 'bias': the {precision} layer kernels do not run batch {batch}, length "
+                                 f"{t_len} under the process's kernel switches ({ask} returned 0)")
+        return None, gvec
     if (context is None and getattr(model, "global_path", "auto") == "auto" and model.forward_precision == "fp32"
             and dims.residual_channels == 64 and dims.skip_channels == 64):
         with torch.cuda.device(gvec.device):

@@ -272,7 +272,9 @@ class Trainer:
                  precision=32):
         # Lightning's precision switch: 32 (default) trains in exact fp32; "bf16" runs the layer stack's
         # products on bf16 operands with fp32 accumulation (WaveNet.forward_precision = "bf16"), fp32
-        # everywhere else -- master weights, optimizer, head and loss included
+        # everywhere else -- master weights, optimizer, head and loss included.  fit() then SETS, and leaves set,
+        # model.model.forward_precision = "bf16" and, on a model with class labels (--use_global), model.model.global_path
+        # = "bias": the model keeps both after training (reset them for an fp32 use with video, which "bias" refuses)
         if precision in (16, "16", "16-mixed"):
             raise NotImplementedError("precision=16 (fp16 training) needs loss scaling, which movenet_amd "
                                       "does not implement; use precision='bf16' or 32")
@@ -306,6 +308,9 @@ class Trainer:
             model.precision = "bf16"
             from .ops import bf16_mode
             bf16_mode(model.model, False)  # (the channel constraint, before anything runs)
+            if int(getattr(model.model, "global_classes", 0)) > 0:
+                # labels (--use_global): the one-vector-per-layer path of the bf16 layer kernels, by name
+                model.model.global_path = "bias"
         rank, world, local_rank = init_distributed(model.config.dist_backend
                                                    if torch.cuda.is_available() else "gloo",
                                                    model.config.dist_port)

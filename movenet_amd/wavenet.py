@@ -205,14 +205,19 @@ class WaveNet(nn.Module):
     # ---- which kernels global conditioning runs ----------------------------
     @property
     def global_path(self) -> str:
-        """"auto" (default) or "context": force the general path of global conditioning -- the global vector added to
-        the context, the conditioned kernels as they are (tests, A/B measurements)."""
+        """"auto" (default): the one-vector-per-layer fast path where fp32 runs it, else the general path.  "context":
+        force the general path of global conditioning -- the global vector added to the context, the conditioned
+        kernels as they are (tests, A/B measurements).  "bias": REQUIRE the one-vector-per-layer path, in whichever
+        precision the model runs -- under ``forward_precision = "bf16"`` the labelled bf16 layer kernels
+        (mvn_forward_bf16_global / mvn_backward_bf16_global), under fp32 the fast path "auto" prefers; ValueError, before
+        anything is launched, where that path does not exist (a video context, residual or skip channels other than
+        64, fp16, kernel switches or a shape that mvn_global_fast_path / mvn_global_bf16_path refuses)."""
         return getattr(self, "_global_path", "auto")
 
     @global_path.setter
     def global_path(self, value: str) -> None:
-        if value not in ("auto", "context"):
-            raise ValueError(f"global_path must be 'auto' or 'context', got {value!r}")
+        if value not in ("auto", "context", "bias"):
+            raise ValueError(f"global_path must be 'auto', 'context' or 'bias', got {value!r}")
         self._global_path = value
 
     # ---- what forward(..., return_loss=True) minimises --------------------
@@ -336,6 +341,8 @@ class WaveNet(nn.Module):
             if keep is not None:
                 gvec = gvec * keep.to(device=gvec.device, dtype=gvec.dtype)[:, None]
         bf16_mode(self, video is not None, gvec is not None)  # (refused before the video encoder runs)
+        if gvec is not None and video is not None and self.global_path == "bias":
+            raise ValueError("global_path 'bias' runs models without a video context")
         context = None if video is None else self.upsample_video(video)
         if return_loss:
             return wavenet_forward_loss(self, audio, context, target, gvec=gvec)
