@@ -549,6 +549,34 @@ int mvn_backward_bf16_global(const mvn_dims *dims, const mvn_params *params,
                              int normalize, int remove_last, float *scratch, size_t scratch_floats,
                              float *rowsum, void *stream);
 
+/* Video context on bf16 operands (csrc/fused_bf16.h): mvn_forward_bf16 / mvn_backward_bf16 for conditioned layers,
+ * buf->ctx / fwd->ctx the (B, 64, ctx_ld) context as in mvn_forward.  Forward: f | g is ONE contraction over K = 192,
+ * bf(W_fg) bf([x(t - d); x(t)]) + bf([Wcf; Wcg]) bf(ctx(t)), in fp32 accumulators that start from bcf | bcg (fp32, never
+ * rounded); ctx and the context weights are rounded once as they are staged.  Backward: the layer kernel's arithmetic is
+ * mvn_backward_bf16's (the context term does not enter dx); its fp32 df | dg tile also goes to bwd->dfg, from which the
+ * context pass of mvn_backward forms dctx, the context-conv weight and bias gradients in fp32 from the unrounded dfg,
+ * ctx and weights.  Where mvn_backward_bf16 runs a shape, the layer pass cuts each sequence into the same chunks: zero
+ * context weights and biases give its logits and gradients to the bit.
+ * scratch: mvn_bf16_ctx_scratch_floats() floats (the layer kernel's second pair of gradient tensors, the two passes'
+ * slabs and bias partials: dlogit / da1 / fwd->z are too small for them at short outputs and small Q).
+ * Refused before anything is launched or written: MVN_ERR_UNSUPPORTED for residual_channels or skip_channels != 64,
+ * rows (t_len, ctx_ld) beyond 2^21 and a batch / length the kernels cannot place (mvn_bf16_ctx_path returns 0 exactly
+ * there, for any ctx_ld <= 2^21; it consults no switch); MVN_ERR_BAD_ARG for no ctx, no dctx, no dfg, no context-conv
+ * parameters or gradients, ctx_ld < t_len, no scratch or one below mvn_bf16_ctx_scratch_floats().
+ * mvn_last_backward_form() reports MVN_BWD_FORM_BF16_CTX.  mvn_forward_bf16, mvn_backward_bf16 and the _global pair keep
+ * refusing a context. */
+#define MVN_BWD_FORM_BF16_CTX 7 /* form 4 for conditioned layers: mvn_backward_bf16_ctx */
+int mvn_bf16_ctx_path(const mvn_dims *dims, int batch, int t_len);
+size_t mvn_bf16_ctx_scratch_floats(const mvn_dims *dims, int batch, int t_len);
+int mvn_forward_bf16_ctx(const mvn_dims *dims, const mvn_params *params, const int32_t *index,
+                         int index_stride, int batch, int t_len, const mvn_fwd_buffers *buf, float *out,
+                         int normalize, int remove_last, int save, void *stream);
+int mvn_backward_bf16_ctx(const mvn_dims *dims, const mvn_params *params, const mvn_param_grads *grads,
+                          const int32_t *index, int index_stride, int batch, int t_len,
+                          const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
+                          const float *dout, int normalize, int remove_last, float *scratch,
+                          size_t scratch_floats, void *stream);
+
 /* ------------------------------------------------------------------------
  * Local conditioning: video encoder + learned upsampler (movenet/wavenet.py:94-118,
  * :149-156).  video (B, F, 64, 64, Cin) fp32 -> Conv3d(k=(1,64,64)) -> (B, C, F)

@@ -27,6 +27,7 @@ BWD_FORM_GENERIC, BWD_FORM_HALVES, BWD_FORM_ONE = 1, 2, 3  # mvn_last_backward_f
 BWD_FORM_BF16 = 4  # mvn_backward_bf16's layer kernel
 BWD_FORM_ONE_GLOBAL = 5  # mvn_backward_global: BWD_FORM_ONE with the label's row sums of df | dg
 BWD_FORM_BF16_GLOBAL = 6  # mvn_backward_bf16_global: BWD_FORM_BF16 with the row sums formed inside the layer kernel
+BWD_FORM_BF16_CTX = 7  # mvn_backward_bf16_ctx: BWD_FORM_BF16 writing df | dg for the fp32 context pass
 SAMPLE_REFERENCE, SAMPLE_MODEL = 0, 1  # mvn_generate_ex's rule of a sampled step (include/movenet_hip.h)
 SAMPLING_RULES = {"reference": SAMPLE_REFERENCE, "model": SAMPLE_MODEL}
 LOSS_REFERENCE, LOSS_MODEL = 0, 1  # mvn_softmax_ce_*_ex's loss rule (include/movenet_hip.h)
@@ -183,6 +184,15 @@ SIGNATURES = {
                                            C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FwdBuffers),
                                            C.POINTER(BwdBuffers), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mvn_bf16_ctx_path": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_int]),
+    "mvn_bf16_ctx_scratch_floats": (C.c_size_t, [C.POINTER(Dims), C.c_int, C.c_int]),
+    "mvn_forward_bf16_ctx": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.c_void_p, C.c_int, C.c_int,
+                                       C.c_int, C.POINTER(FwdBuffers), C.c_void_p, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p]),
+    "mvn_backward_bf16_ctx": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(ParamGrads),
+                                        C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FwdBuffers),
+                                        C.POINTER(BwdBuffers), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
     "mvn_upsample_video": (C.c_int, [C.POINTER(Dims), C.POINTER(VideoParams), C.c_void_p, C.c_int,
                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int, C.c_void_p]),

@@ -71,6 +71,9 @@ class TrainingConfig:
     # of the training set are the classes and every batch's context names go to forward() as global_features.  Not a
     # reference field: a JSON written without it loads with the default (off).
     use_global: bool = False
+    # Trainer(precision="bf16") with use_video: opt in to the video context on bf16 operands (WaveNet.bf16_context; not a
+    # reference field)
+    bf16_video: bool = False
     # classifier-free guidance of a labelled model.  generate_guidance: the scale the sample logger
     # generates with (WaveNet.generate_guidance; 1.0: off, plain conditional generation).  global_dropout: with this
     # probability per sequence and TRAIN step the label's vector is replaced by zeros, so that the model also learns
@@ -175,6 +178,7 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--n_steps_per_epoch", type=int, default=None)
     a("--use_video", type=_flag, default=True)
     a("--use_global", type=_flag, default=False)
+    a("--bf16_video", type=_flag, default=False)
     a("--generate_guidance", type=float, default=1.0)
     a("--global_dropout", type=float, default=0.0)
     a("--batch_subsample_frac", type=float, default=None)
@@ -217,7 +221,7 @@ def config_from_args(args) -> TrainingConfig:
         "scheduler_cyclic_mode scheduler_cyclic_gamma scheduler_cycle_momentum max_learning_rate "
         "scheduler_step_size scheduler_step_gamma scheduler_milestones weight_decay "
         "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule ema_decay ema_warmup accumulation_steps num_workers val_num_workers "
-        "pin_memory n_epochs n_steps_per_epoch use_video use_global generate_guidance global_dropout batch_subsample_frac "
+        "pin_memory n_epochs n_steps_per_epoch use_video use_global bf16_video generate_guidance global_dropout batch_subsample_frac "
         "val_batch_subsample_frac dist_backend dist_port model_output_path log_samples_every"
     ).split()
     kw = {k: getattr(args, k) for k in copied}  # NB: gradient_clipping is not among them (Q11)

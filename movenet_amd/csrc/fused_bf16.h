@@ -49,19 +49,25 @@ __device__ __forceinline__ unsigned short b16_one(float w) { return __builtin_bi
 constexpr int FB16_W1_BYTES = 4 * 8 * 1024, FB16_W2_BYTES = 4 * 4 * 1024;
 constexpr int FB16_LDS_BYTES = FB16_W1_BYTES + FB16_W2_BYTES + 128 * 4;
 constexpr int FB16_PACK_F = FB16_LDS_BYTES / 4;
+// CTX (conditioned layers): the f | g image holds 12 k-steps per block -- [Wcf; Wcg] behind the two taps -- and bcf | bcg
+// follow br | bs as floats: 48 + 16 KB of weights, 65 KB in all.
+constexpr int FB16C_W1_BYTES = 4 * 12 * 1024;
+constexpr int FB16C_LDS_BYTES = FB16C_W1_BYTES + FB16_W2_BYTES + 256 * 4;
+constexpr int FB16C_PACK_F = FB16C_LDS_BYTES / 4;
 
 // fs3_stage_weights' element order, one bf16 per weight
+template <int NKS1 = 8>
 __device__ __forceinline__ void fb16_stage_weights(unsigned char *img, const float *wf, const float *wg, const float *wr,
                                                    const float *ws, const float *br, const float *bs, int tid, int nthreads) {
   unsigned short *W1 = (unsigned short *)img;
-  unsigned short *W2 = (unsigned short *)(img + FB16_W1_BYTES);
-  float *BI = (float *)(img + FB16_W1_BYTES + FB16_W2_BYTES);
+  unsigned short *W2 = (unsigned short *)(img + 4 * NKS1 * 1024);
+  float *BI = (float *)(img + 4 * NKS1 * 1024 + FB16_W2_BYTES);
   for (int sI = tid; sI < 2 * 8192; sI += nthreads) {
     const int g = sI >> 13, r = sI & 8191;  // g: 0 filter, 1 gate; source (out, in, tap)
     const int tap = r & 1, kc = (r >> 1) & 63, cm = r >> 7;
     const int lhs = (kc >> 2) & 1, j = (kc & 3) + 4 * (kc >> 3);
     const int blk = 2 * g + (cm >> 5), ln = (cm & 31) + 32 * lhs, ks = (tap ? 0 : 4) + (j >> 3);
-    W1[((blk * 8 + ks) * 64 + ln) * 8 + (j & 7)] = b16_one((g ? wg : wf)[r]);
+    W1[((blk * NKS1 + ks) * 64 + ln) * 8 + (j & 7)] = b16_one((g ? wg : wf)[r]);
   }
   for (int sI = tid; sI < 2 * 4096; sI += nthreads) {
     const int g = sI >> 12, r = sI & 4095;  // g: 0 residual, 1 skip; source (out, in)
@@ -72,15 +78,41 @@ __device__ __forceinline__ void fb16_stage_weights(unsigned char *img, const flo
   }
   for (int i = tid; i < 128; i += nthreads) BI[i] = i < 64 ? br[i] : bs[i - 64];
 }
+// the conditioned layer's image: the audio-only element order at 12 k-steps per block, [Wcf; Wcg] (out, in) as k-steps
+// 8..11 in the residual | skip image's order, bcf | bcg behind br | bs
+__device__ __forceinline__ void fb16c_stage_weights(unsigned char *img, const float *wf, const float *wg, const float *wr,
+                                                    const float *ws, const float *br, const float *bs, const float *wcf,
+                                                    const float *wcg, const float *bcf, const float *bcg, int tid, int nthreads) {
+  fb16_stage_weights<12>(img, wf, wg, wr, ws, br, bs, tid, nthreads);
+  unsigned short *W1 = (unsigned short *)img;
+  float *BC = (float *)(img + FB16C_W1_BYTES + FB16_W2_BYTES) + 128;
+  for (int sI = tid; sI < 2 * 4096; sI += nthreads) {
+    const int g = sI >> 12, r = sI & 4095;  // g: 0 filter, 1 gate; source (out, in)
+    const int kc = r & 63, m2 = r >> 6;
+    const int lhs = (kc >> 2) & 1, j = (kc & 3) + 4 * (kc >> 3);
+    const int blk = 2 * g + (m2 >> 5), ln = (m2 & 31) + 32 * lhs, ks = 8 + (j >> 3);
+    W1[((blk * 12 + ks) * 64 + ln) * 8 + (j & 7)] = b16_one((g ? wcg : wcf)[r]);
+  }
+  for (int i = tid; i < 128; i += nthreads) BC[i] = i < 64 ? bcf[i] : bcg[i - 64];
+}
 
 __global__ __launch_bounds__(256) void fb16_pack_kernel(Fs3PackArgs p, float *dst) {
   const int l = blockIdx.y;
   fb16_stage_weights((unsigned char *)(dst + (size_t)l * FB16_PACK_F), p.wf[l], p.wg[l], p.wr[l], p.ws[l], p.br[l], p.bs[l],
                      blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
 }
+struct Fb16cPackArgs {
+  const float *wcf[FS3_PACK_LAYERS], *wcg[FS3_PACK_LAYERS], *bcf[FS3_PACK_LAYERS], *bcg[FS3_PACK_LAYERS];
+};
+__global__ __launch_bounds__(256) void fb16c_pack_kernel(Fs3PackArgs p, Fb16cPackArgs c, float *dst) {
+  const int l = blockIdx.y;
+  fb16c_stage_weights((unsigned char *)(dst + (size_t)l * FB16C_PACK_F), p.wf[l], p.wg[l], p.wr[l], p.ws[l], p.br[l], p.bs[l],
+                      c.wcf[l], c.wcg[l], c.bcf[l], c.bcg[l], blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
+}
 
-// acc[blk] += W[blk] (NKS k-steps of the image at LDS byte address wa) x B, B value e of k-step ks = bval(ks, e)
-template <int NKS, class BV>
+// acc[blk] += W[blk] (NKS k-steps of the image at LDS byte address wa, from k-step KS0 of the block's STRIDE) x B, B value
+// e of k-step ks = bval(ks, e)
+template <int NKS, int STRIDE = NKS, int KS0 = 0, class BV>
 __device__ __forceinline__ void fb16_product(f32x16 (&acc)[4], unsigned wa, BV bval) {
   typedef __attribute__((address_space(3))) u32x4 lds_u4;
 #pragma unroll
@@ -90,16 +122,22 @@ __device__ __forceinline__ void fb16_product(f32x16 (&acc)[4], unsigned wa, BV b
     for (int i = 0; i < 4; ++i) bq[i] = b16_pack2(bval(ks, 2 * i), bval(ks, 2 * i + 1));
 #pragma unroll
     for (int blk = 0; blk < 4; ++blk) {
-      const u32x4 aq = *(const lds_u4 *)(uintptr_t)(wa + 1024u * (unsigned)(blk * NKS + ks));
+      const u32x4 aq = *(const lds_u4 *)(uintptr_t)(wa + 1024u * (unsigned)(blk * STRIDE + KS0 + ks));
       B16_MFMA(acc[blk], aq, bq);
     }
   }
 }
 
-template <bool GLOBAL>
+// CTX (mvn_forward_bf16_ctx; never together with GLOBAL): the conditioned layer -- K = 192, the context as k-steps 8..11 of
+// a 12-k-step image, the accumulators started from bcf | bcg (one vector for all sequences).
+template <bool GLOBAL, bool CTX = false>
 __global__ __launch_bounds__(512, 1) void fused_layer64s_bf16_kernel(FusedFwdPArgs a, int chunks_per_b, int chunk_t) {
+  static_assert(!(GLOBAL && CTX), "the label's bias form and the context form are separate kernels");
   extern __shared__ __attribute__((aligned(16))) unsigned char fb16_lds[];
-  const float *BI = (const float *)(fb16_lds + FB16_W1_BYTES + FB16_W2_BYTES);  // br | bs (GLOBAL: | gb f rows | gb g rows)
+  constexpr int W1_BYTES = CTX ? FB16C_W1_BYTES : FB16_W1_BYTES, LDS_BYTES = CTX ? FB16C_LDS_BYTES : FB16_LDS_BYTES;
+  constexpr int NKS1 = CTX ? 12 : 8;
+  // br | bs (GLOBAL: | gb f rows | gb g rows; CTX: | bcf | bcg)
+  const float *BI = (const float *)(fb16_lds + W1_BYTES + FB16_W2_BYTES);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.x / chunks_per_b, ch = blockIdx.x - b * chunks_per_b;
@@ -109,7 +147,7 @@ __global__ __launch_bounds__(512, 1) void fused_layer64s_bf16_kernel(FusedFwdPAr
   // ---- weights into LDS: the image fb16_pack_kernel wrote once per forward call (a linear copy), or converted here
   if (a.wpack) {
     typedef float f4_ __attribute__((ext_vector_type(4)));
-    constexpr int N16 = FB16_LDS_BYTES / 16, PER = (N16 + 511) / 512;
+    constexpr int N16 = LDS_BYTES / 16, PER = (N16 + 511) / 512;
     const f4_ *src = (const f4_ *)a.wpack;
     f4_ v[PER];
 #pragma unroll
@@ -122,6 +160,8 @@ __global__ __launch_bounds__(512, 1) void fused_layer64s_bf16_kernel(FusedFwdPAr
       const int at = tid + 512 * i;
       if (at < N16) ((f4_ *)fb16_lds)[at] = v[i];
     }
+  } else if constexpr (CTX) {
+    fb16c_stage_weights(fb16_lds, a.wf, a.wg, a.wr, a.ws, a.br, a.bs, a.wcf, a.wcg, a.bcf, a.bcg, tid, 512);
   } else {
     fb16_stage_weights(fb16_lds, a.wf, a.wg, a.wr, a.ws, a.br, a.bs, tid, 512);
   }
@@ -130,7 +170,7 @@ __global__ __launch_bounds__(512, 1) void fused_layer64s_bf16_kernel(FusedFwdPAr
   }
   __syncthreads();
   const unsigned w1a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)fb16_lds + 16u * lane;
-  const unsigned w2a = w1a + (unsigned)FB16_W1_BYTES;
+  const unsigned w2a = w1a + (unsigned)W1_BYTES;
   const int cbase = 4 * lh;
 
   constexpr int RSRC = 0x00020000;  // raw buffer, 32-bit data format (gfx9)
@@ -141,6 +181,13 @@ __global__ __launch_bounds__(512, 1) void fused_layer64s_bf16_kernel(FusedFwdPAr
   const __amdgpu_buffer_rsrc_t skb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.skip.p + (size_t)b * a.skip.sb - a.t_base), 0, 0x7FFFFFFF, RSRC);
   const bool save = a.th.p != nullptr, has_out = a.xout.p != nullptr;
   int xld4 = 4 * a.xin.ld, thld4 = 4 * a.th.ld, xold4 = 4 * a.xout.ld, skld4 = 4 * a.skip.ld;
+  // CTX: the context (B, C, ctx_ld), column t = time t, read like the x(t) block (its own row pitch)
+  [[maybe_unused]] __amdgpu_buffer_rsrc_t cxb;
+  [[maybe_unused]] int cxld4 = 0;
+  if constexpr (CTX) {
+    cxb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.ctx.p + (size_t)b * a.ctx.sb), 0, 0x7FFFFFFF, RSRC);
+    cxld4 = 4 * a.ctx.ld;
+  }
 
   // (the strip schedule of fused_layer64s_bf3_kernel: x(t) one strip ahead, x(t - d) at the top of the strip, the skip
   // accumulator's old values under the second product; lanes that must not store carry an offset past the resource)
@@ -183,18 +230,33 @@ __global__ __launch_bounds__(512, 1) void fused_layer64s_bf16_kernel(FusedFwdPAr
 #pragma unroll
       for (int j = 0; j < 32; ++j) xa0[j] = live ? xa0[j] : 0.f;
     }
+    // CTX: ctx(t) of this strip, B operand of k-steps 8..11 (requested with x(t - d), consumed in a phase of its own
+    // behind the audio product: the three operand blocks are never all live in bf16 form at once)
+    [[maybe_unused]] float xc[CTX ? 32 : 1];
+    if constexpr (CTX) {
+      const int oc = 4 * (cbase * a.ctx.ld + tc);
+      FS_FENCE(cxld4);
+#pragma unroll
+      for (int j = 0; j < 32; ++j)
+        xc[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(cxb, oc, ((j & 3) + 8 * (j >> 2)) * cxld4, 0));
+      if (!(t0 >= a.t_begin && t0 + 32 <= te)) {
+#pragma unroll
+        for (int j = 0; j < 32; ++j) xc[j] = live ? xc[j] : 0.f;
+      }
+    }
     // ---- f | g: four 32 x 32 blocks (f c<32, f c>=32, g c<32, g c>=32), K = 128 = 8 k-steps, the x(t) half first
     f32x16 acc[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        if constexpr (GLOBAL)  // accumulator row = channel (r & 3) + 8 (r >> 2) + 4 lh of block i, the same in every lane
+        if constexpr (GLOBAL || CTX)  // accumulator row = channel (r & 3) + 8 (r >> 2) + 4 lh of block i, the same in every lane
           acc[i][r] = BI[128 + 32 * i + (r & 3) + 8 * (r >> 2) + cbase];
         else
           acc[i][r] = 0.f;
       }
-    fb16_product<8>(acc, w1a, [&](int ks, int e) { return ks < 4 ? xb1[8 * ks + e] : xa0[8 * (ks - 4) + e]; });
+    fb16_product<8, NKS1>(acc, w1a, [&](int ks, int e) { return ks < 4 ? xb1[8 * ks + e] : xa0[8 * (ks - 4) + e]; });
+    if constexpr (CTX) fb16_product<4, NKS1, 8>(acc, w1a, [&](int ks, int e) { return xc[8 * ks + e]; });
     // ---- gate in registers (fp32); tanh / sigmoid leave; z in accumulator order = the next B operand
     float z[32];
     FS_FENCE(thld4);
@@ -282,11 +344,37 @@ static int launch_fb16_pack(const mvn_params *p, int L, float *dst, hipStream_t 
   }
   return check_hip(hipGetLastError(), "fb16_pack");
 }
+static int launch_fb16c_pack(const mvn_params *p, int L, float *dst, hipStream_t s) {
+  for (int l0 = 0; l0 < L; l0 += FS3_PACK_LAYERS) {
+    const int n = std::min(FS3_PACK_LAYERS, L - l0);
+    Fs3PackArgs pa;
+    Fb16cPackArgs pc;
+    for (int i = 0; i < FS3_PACK_LAYERS; ++i) {
+      const int l = l0 + std::min(i, n - 1);
+      pa.wf[i] = p->filter_w[l]; pa.wg[i] = p->gate_w[l]; pa.wr[i] = p->residual_w[l]; pa.ws[i] = p->skip_w[l];
+      pa.br[i] = p->residual_b[l]; pa.bs[i] = p->skip_b[l];
+      pc.wcf[i] = p->ctx_filter_w[l]; pc.wcg[i] = p->ctx_gate_w[l]; pc.bcf[i] = p->ctx_filter_b[l]; pc.bcg[i] = p->ctx_gate_b[l];
+    }
+    hipLaunchKernelGGL(fb16c_pack_kernel, dim3(8, n), dim3(256), 0, s, pa, pc, dst + (size_t)l0 * FB16C_PACK_F);
+  }
+  return check_hip(hipGetLastError(), "fb16c_pack");
+}
 static int launch_fused_layer64s_bf16(const FusedFwdPArgs &a, int batch, hipStream_t s) {
   const int nt = a.t_end - (a.t_begin & ~TILE_ALIGN);
   if (a.t_end <= a.t_begin || batch <= 0) return MVN_OK;
   int chunks, chunk_t;
   fb_chunks(nt, batch, 1, &chunks, &chunk_t, 256);  // a chunk: whole rounds of the 8 waves' strips
+  if (a.ctx.p) {  // conditioned layer: the 12-k-step image
+    if (a.gbias) {
+      set_error("fused_layer64s_bf16: a context and a label bias do not go together");
+      return MVN_ERR_BAD_ARG;
+    }
+    const void *fn = (const void *)fused_layer64s_bf16_kernel<false, true>;
+    const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(fused_layer64s_bf16_ctx)");
+    if (rc) return rc;
+    hipLaunchKernelGGL((fused_layer64s_bf16_kernel<false, true>), dim3(chunks * batch), dim3(512), FB16C_LDS_BYTES, s, a, chunks, chunk_t);
+    return MVN_OK;
+  }
   if (a.gbias) {  // global conditioning: 128 more floats of LDS hold the sequence's bias vector
     const void *fn = (const void *)fused_layer64s_bf16_kernel<true>;
     const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(fused_layer64s_bf16<global>)");
@@ -311,10 +399,13 @@ static int launch_fused_layer64s_bf16(const FusedFwdPArgs &a, int batch, hipStre
 constexpr int FBL16_WIMG_BYTES = 2 * 8 * 1024;  // [c block][k-step][lane][8 bf16]
 constexpr int FBL16_LDS_BYTES = 3 * FBL_TILE_F * 4 + FBL16_WIMG_BYTES;
 
-template <bool GLOBAL>
+// WRITE_DFG (mvn_backward_bf16_ctx; never together with GLOBAL): the same arithmetic, the fp32 df | dg tile also written
+// to a.dfg for the context pass, as bwd_layer64_kernel<true> does.
+template <bool GLOBAL, bool WRITE_DFG = false>
 __global__ __launch_bounds__(512, 1) void bwd_layer64_bf16_kernel(FusedBwdLArgs a, int chunks_per_b, int chunk_t,
                                                                  float *__restrict__ rs_bias_part, float *__restrict__ rs_part,
                                                                  float *__restrict__ fg_part, float *__restrict__ g_part) {
+  static_assert(!(GLOBAL && WRITE_DFG), "the label's row sums and the dfg output are separate kernels");
   constexpr int C = FB_C, LD = W2_LD, TT = W2_T;
   extern __shared__ __attribute__((aligned(16))) float fbl16_lds[];
   float (*U)[LD] = (float (*)[LD])fbl16_lds;                      // [dxo; dskip], then [x(t - d); x(t)]
@@ -375,6 +466,8 @@ __global__ __launch_bounds__(512, 1) void bwd_layer64_bf16_kernel(FusedBwdLArgs 
   const __amdgpu_buffer_rsrc_t xinb = fb_rsrc(a.xin.p + (size_t)b * a.xin.sb);
   const __amdgpu_buffer_rsrc_t oab = fb_rsrc(a.oa.p + (size_t)b * a.oa.sb);
   const __amdgpu_buffer_rsrc_t opb = fb_rsrc(a.op.p + (size_t)b * a.op.sb);
+  [[maybe_unused]] __amdgpu_buffer_rsrc_t dfgb;  // WRITE_DFG: df | dg (B, 2C, Tp) for the context pass
+  if constexpr (WRITE_DFG) dfgb = fb_rsrc(a.dfg.p + (size_t)b * a.dfg.sb);
   const int vo_t = 4 * (srow * a.th.ld + st), vo_ds = 4 * (srow * a.dskip.ld + st);
   auto interior = [&](int t0) {
     const bool x_full = t0 >= a.t_lo && t0 + TT <= te;
@@ -547,6 +640,22 @@ __global__ __launch_bounds__(512, 1) void bwd_layer64_bf16_kernel(FusedBwdLArgs 
 #pragma unroll
     for (int p = 0; p < 4; ++p) *(f4 *)&U[32 * p + srow][st] = r_x[p];
     __syncthreads();  // B2: df | dg and the x rows are staged
+    if constexpr (WRITE_DFG) {
+      // the fp32, unrounded df | dg tile for the context pass (bwd_dctx_wgctx64_kernel), columns [t_lo, te) only: the
+      // store of bwd_layer64_kernel<true>
+      const int t = t0 + st;
+      if (t >= a.t_lo && t + 3 < te) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) fb_store16(*(const f4 *)&Gt[32 * p + srow][st], dfgb, vo_t, 4 * (32 * p * a.th.ld + t0));
+      } else {
+        float *base = a.dfg.p + (size_t)b * a.dfg.sb + t;
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (t + e >= a.t_lo && t + e < te) base[(size_t)(32 * p + srow) * a.dfg.ld + e] = Gt[32 * p + srow][st + e];
+      }
+    }
     if constexpr (GLOBAL) {
       // the label's term: this thread's share of the rows of df | dg (fp32, unrounded), columns [t_lo, te) only.  A
       // column outside is zero already -- its tanh, sigmoid, dxo and dskip were staged as zeros (ld4_edge), so
@@ -700,7 +809,7 @@ __global__ __launch_bounds__(512, 1) void bwd_layer64_bf16_kernel(FusedBwdLArgs 
   }
 }
 
-// launch_bwd_layer64 for the bf16 kernel (no df | dg output); same plan, same reduce.  g_part / rowsum (both or neither):
+// launch_bwd_layer64 for the bf16 kernel (a.dfg given: the conditioned form, which writes df | dg); same plan, same reduce.  g_part / rowsum (both or neither):
 // the GLOBAL instantiation leaves a 128-float partial of the df | dg row sums per workgroup in g_part (as many as the
 // plan's bias partials), and rowsum (batch, 128) of this layer receives their sums.
 template <class RsOp, class FgOp>
@@ -708,18 +817,25 @@ static int launch_bwd_layer64_bf16(const FusedBwdLArgs &a, const RsOp &rs, const
                                    hipStream_t s, float *g_part = nullptr, float *rowsum = nullptr) {
   if (pl.chunks <= 0) return MVN_OK;
   const int ldt = a.th.ld;
-  if (a.dfg.p || a.sg.ld != ldt || a.xin.ld != ldt || a.oa.ld != ldt || a.op.ld != ldt || a.gp.ld != ldt ||
+  const bool wd = a.dfg.p != nullptr;
+  if ((wd && a.dfg.ld != ldt) || a.sg.ld != ldt || a.xin.ld != ldt || a.oa.ld != ldt || a.op.ld != ldt || a.gp.ld != ldt ||
       (a.ga.p && a.ga.ld != ldt)) {
-    set_error("bwd_layer64_bf16: audio-only layers, and the (B, ch, Tp) views must share one row pitch");
+    set_error("bwd_layer64_bf16: the (B, ch, Tp) views must share one row pitch");
     return MVN_ERR_BAD_ARG;
   }
   const int n = pl.chunks * batch;
   const bool glob = g_part != nullptr;
+  if (glob && wd) {
+    set_error("bwd_layer64_bf16: the label's row sums and a dfg output do not go together");
+    return MVN_ERR_BAD_ARG;
+  }
   if (glob != (rowsum != nullptr)) {
     set_error("bwd_layer64_bf16: g_part and rowsum go together");
     return MVN_ERR_BAD_ARG;
   }
-  const void *fn = glob ? (const void *)bwd_layer64_bf16_kernel<true> : (const void *)bwd_layer64_bf16_kernel<false>;
+  const void *fn = wd     ? (const void *)bwd_layer64_bf16_kernel<false, true>
+                   : glob ? (const void *)bwd_layer64_bf16_kernel<true>
+                          : (const void *)bwd_layer64_bf16_kernel<false>;
   const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(bwd_layer64_bf16)");
   if (rc) return rc;
   void *args[] = {(void *)&a, (void *)&pl.chunks, (void *)&pl.chunk_t, (void *)&pl.bias, (void *)&pl.rs, (void *)&pl.fg,

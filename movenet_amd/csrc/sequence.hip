@@ -1135,12 +1135,15 @@ int mvn_padded_len(int n) { return n <= 0 ? 0 : (n + 63) / 64 * 64; }
 static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t *index, int index_stride,
                         int batch, int t_len, const mvn_fwd_buffers *buf, float *out, int normalize,
                         int remove_last, int save, void *stream_, bool f16, bool bf16 = false,
-                        const float *gbias = nullptr) {
+                        const float *gbias = nullptr, bool ctx16 = false) {
+  // ctx16 (mvn_forward_bf16_ctx): bf16 with the context as a third K block of the layer kernel; the caller has checked
+  // that there is one
   Geometry g;
   int rc = make_geometry(dims, batch, t_len, g);
   if (rc) return rc;
   if (bf16) {  // (decided before any launch: there is no fp32 fall-back)
-    rc = bf16_supported(gbias ? "mvn_forward_bf16_global" : "mvn_forward_bf16", g, buf && buf->ctx != nullptr);
+    rc = bf16_supported(gbias ? "mvn_forward_bf16_global" : ctx16 ? "mvn_forward_bf16_ctx" : "mvn_forward_bf16", g,
+                        !ctx16 && buf && buf->ctx != nullptr);
     if (rc) return rc;
   }
   if (!p || !buf || !buf->acts || !buf->z || !buf->skip || !buf->a1 ||
@@ -1217,7 +1220,17 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
       if (l == g.L - 1) fp.xout.p = nullptr;  // the last residual output is never used
       fp.th = act_view(save ? buf->th + (size_t)l * g.act : nullptr, batch, C, g.Tp);
       fp.sg = act_view(save ? buf->sg + (size_t)l * g.act : nullptr, batch, C, g.Tp);
-      if ((size_t)g.act >= (size_t)g.L * FB16_PACK_F) {
+      if (has_ctx) {  // (ctx16: the conditioned form, its image 12 k-steps per f | g block)
+        fp.wcf = p->ctx_filter_w[l]; fp.wcg = p->ctx_gate_w[l]; fp.bcf = p->ctx_filter_b[l]; fp.bcg = p->ctx_gate_b[l];
+        fp.ctx = ctxv;
+        if ((size_t)g.act >= (size_t)g.L * FB16C_PACK_F) {
+          if (l == 0) {
+            const int rc3 = launch_fb16c_pack(p, g.L, buf->z, s);
+            if (rc3) return rc3;
+          }
+          fp.wpack = buf->z + (size_t)l * FB16C_PACK_F;
+        }
+      } else if ((size_t)g.act >= (size_t)g.L * FB16_PACK_F) {
         if (l == 0) {
           const int rc3 = launch_fb16_pack(p, g.L, buf->z, s);
           if (rc3) return rc3;
@@ -1389,7 +1402,9 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
                          const int32_t *index, int index_stride, int batch, int t_len,
                          const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
                          const float *dout, int normalize, int remove_last, void *stream_, bool bf16,
-                         float *gpair = nullptr, size_t gpair_floats = 0, float *grow = nullptr) {
+                         float *gpair = nullptr, size_t gpair_floats = 0, float *grow = nullptr, bool ctx16 = false) {
+  // ctx16 (mvn_backward_bf16_ctx): the bf16 layer kernel's dfg-writing form with the fp32 context pass behind it; gpair
+  // holds the second scatter pair, the slabs and the bias partials, as for the fp32 conditioned layers
   // gpair (mvn_backward_global, mvn_backward_scratch): the caller's scratch for the one-kernel layer backward -- fast path (grow given) and
   // conditioned layers (fwd->ctx: the label has joined the context) alike; without it the conditioned layers look for
   // that room in dlogit / da1 and take another form where those are too small (short outputs, small Q).
@@ -1499,13 +1514,36 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
   // the workgroups that fit: the plan takes fewer, longer chunks then)
   float *sc_bias = bias_scratch2, *sc_slab = slab;
   size_t sc_bias_floats = bias2_floats, sc_slab_floats = slab_floats;
-  const bool ext = gpair && (glob || has_ctx) && !bf16 && gpair_floats >= 2 * (size_t)g.act + (size_t)batch * GC_PER_WG;
+  const bool ext = gpair && (glob || has_ctx) && (!bf16 || ctx16) && gpair_floats >= 2 * (size_t)g.act + (size_t)batch * GC_PER_WG;
+  // (the context pass's share of the caller's scratch: all of it, whatever the layer pass is held to below)
+  float *cx_bias = nullptr, *cx_slab = nullptr;
+  size_t cx_bias_floats = 0, cx_slab_floats = 0;
   if (ext) {  // the caller's scratch: the second scatter pair, then the slabs, then the bias partials
     const size_t n_fit = (gpair_floats - 2 * (size_t)g.act) / GC_PER_WG;
     sc_slab = gpair + 2 * (size_t)g.act;
     sc_slab_floats = n_fit * (GC_PER_WG - 128);
     sc_bias = sc_slab + sc_slab_floats;
     sc_bias_floats = n_fit * 128;
+    if (ctx16) {
+      cx_bias = sc_bias; cx_slab = sc_slab; cx_bias_floats = sc_bias_floats; cx_slab_floats = sc_slab_floats;
+      // never more workgroups in the layer pass than mvn_backward_bf16 would place at this shape (its slabs live in da1,
+      // else in the forward's z scratch): both passes then cut a sequence into the same chunks, and zero context weights
+      // give the audio-only pass's gradients to the bit.  Where that pass places nothing, the scratch alone decides.
+      const size_t per_wg = GC_PER_WG - 128;
+      size_t n_audio = std::min(slab ? slab_floats / per_wg : 0, bias_scratch2 ? bias2_floats / 128 : 0);
+      if (n_audio < (size_t)batch && slab) {  // (its second try in da1: one region cut into slabs and partials)
+        const size_t total = (size_t)batch * Q * g.Sp, nd = total / GC_PER_WG;
+        if (nd >= (size_t)batch && !bias_scratch2) n_audio = std::min((total - nd * 128) / per_wg, nd);
+      }
+      if (n_audio < (size_t)batch && fwd->z) {
+        const size_t total = (size_t)g.act, nz = total / GC_PER_WG;
+        n_audio = std::min((total - nz * 128) / per_wg, nz);
+      }
+      if (n_audio >= (size_t)batch && n_audio < n_fit) {
+        sc_slab_floats = n_audio * per_wg;
+        sc_bias_floats = n_audio * 128;
+      }
+    }
   } else if (!sc_bias && !has_ctx && slab) {
     const size_t total = (size_t)batch * Q * g.Sp, n_fit = total / (128 * 64 + 128 * 128 + 128);
     if (n_fit >= (size_t)batch) {
@@ -1516,8 +1554,13 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
   }
   float *g_part = nullptr;  // bf16 + labels: the layer kernel's partial row sums of df | dg, one 128-vector per workgroup
   if (bf16) {  // (decided before any launch: there is no fp32 fall-back)
-    rc = bf16_supported(glob ? "mvn_backward_bf16_global" : "mvn_backward_bf16", g, has_ctx);
+    rc = bf16_supported(glob ? "mvn_backward_bf16_global" : ctx16 ? "mvn_backward_bf16_ctx" : "mvn_backward_bf16", g,
+                        has_ctx && !ctx16);
     if (rc) return rc;
+    if (ctx16 && !ext) {
+      set_error("mvn_backward_bf16_ctx: scratch missing or smaller than mvn_bf16_ctx_scratch_floats()");
+      return MVN_ERR_BAD_ARG;
+    }
     if (glob) {
       // the caller's scratch (mvn_global_bf16_scratch_floats): slabs, bias partials, row-sum partials of n_fit
       // workgroups -- independent of what da1 or the forward's z scratch hold (short outputs, small Q)
@@ -1545,7 +1588,7 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
     auto fits = [&]() {
       return sc_bias && g.L < 4095 && bwd_layer64_plan(A_lo[1], T, batch, sc_bias, sc_bias_floats, sc_slab, sc_slab_floats, &pl0);
     };
-    if (!fits() && fwd->z && !glob) {
+    if (!fits() && fwd->z && !glob && !ctx16) {
       // short outputs (da1 is (B, Q, Sp)): the slabs go to the forward's z scratch instead, which holds nothing the layer
       // loop reads -- the bf16 forward keeps z in registers and its weight images there, and the head's backward, which
       // may stage its own images in it, runs before the loop on the same stream
@@ -1560,6 +1603,14 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
                 batch, t_len);
       return MVN_ERR_UNSUPPORTED;
     }
+    int cc0 = 0, cct0 = 0;
+    if (ctx16 && !bwd_dctx_wgctx64_fits(A_lo[1], T, batch, cx_bias, cx_bias_floats, cx_slab, cx_slab_floats, &cc0, &cct0)) {
+      set_error("mvn_backward_bf16_ctx: the context pass's slabs do not fit the scratch at batch %d, t_len %d", batch, t_len);
+      return MVN_ERR_UNSUPPORTED;
+    }
+  }
+  if (!ctx16) {  // (every other form gives the context pass the layer pass's scratch)
+    cx_bias = sc_bias; cx_slab = sc_slab; cx_bias_floats = sc_bias_floats; cx_slab_floats = sc_slab_floats;
   }
   if (!dout) {
     // the caller has filled bwd->dlogit itself (mvn_softmax_ce_backward: the trainer's loss and
@@ -1687,7 +1738,7 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
     FusedBwdLPlan pl0;
     int cc = 0, cct = 0;
     scatter = have && bwd_layer64_plan(A_lo[1], T, batch, sc_bias, sc_bias_floats, sc_slab, sc_slab_floats, &pl0) &&
-              (!has_ctx || bwd_dctx_wgctx64_fits(A_lo[1], T, batch, sc_bias, sc_bias_floats, sc_slab, sc_slab_floats, &cc, &cct));
+              (!has_ctx || bwd_dctx_wgctx64_fits(A_lo[1], T, batch, cx_bias, cx_bias_floats, cx_slab, cx_slab_floats, &cc, &cct));
   }
   if (bf16 && !scatter) {
     set_error("mvn_backward_bf16: the bf16 layer kernels cannot run these buffers");
@@ -1697,7 +1748,7 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
     set_error("mvn_backward_global: the one-kernel layer backward cannot run these buffers");
     return MVN_ERR_UNSUPPORTED;
   }
-  g_last_bwd_form = bf16 ? (glob ? MVN_BWD_FORM_BF16_GLOBAL : MVN_BWD_FORM_BF16) : glob ? MVN_BWD_FORM_ONE_GLOBAL : scatter ? MVN_BWD_FORM_ONE : MVN_BWD_FORM_GENERIC;
+  g_last_bwd_form = bf16 ? (glob ? MVN_BWD_FORM_BF16_GLOBAL : ctx16 ? MVN_BWD_FORM_BF16_CTX : MVN_BWD_FORM_BF16) : glob ? MVN_BWD_FORM_ONE_GLOBAL : scatter ? MVN_BWD_FORM_ONE : MVN_BWD_FORM_GENERIC;
   if (scatter) {
     int po = 1 ^ ((g.L - 1) & 1);  // (so that layer 0 writes pair 1 and the dense dx0 can go to dx_a)
     for (int l = g.L - 1; l >= 0; --l) {
@@ -1737,7 +1788,7 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
                            t_lo, T, grow + (size_t)l * batch * 128);
       if (has_ctx) {  // (behind the layer's reduce: the slab scratch is free again)
         int c_chunks = 0, c_chunk_t = 0;
-        if (!bwd_dctx_wgctx64_fits(t_lo, T, batch, sc_bias, sc_bias_floats, sc_slab, sc_slab_floats, &c_chunks, &c_chunk_t)) {
+        if (!bwd_dctx_wgctx64_fits(t_lo, T, batch, cx_bias, cx_bias_floats, cx_slab, cx_slab_floats, &c_chunks, &c_chunk_t)) {
           set_error("mvn_backward: the context pass lost its scratch at layer %d", l);
           return MVN_ERR_BAD_ARG;
         }
@@ -1746,7 +1797,7 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
         fc.dfg = dfg; fc.ctx = ctxv; fc.dctx = dctxv;
         WgCtxOp co;
         co.dwcf = gr->ctx_filter_w[l]; co.dwcg = gr->ctx_gate_w[l]; co.dbcf = gr->ctx_filter_b[l]; co.dbcg = gr->ctx_gate_b[l];
-        launch_bwd_dctx_wgctx64(fc, co, batch, sc_bias, sc_slab, c_chunks, c_chunk_t, s);
+        launch_bwd_dctx_wgctx64(fc, co, batch, cx_bias, cx_slab, c_chunks, c_chunk_t, s);
       }
       po ^= 1;
     }
@@ -1882,6 +1933,14 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
       return MVN_ERR_UNSUPPORTED;
     }
     const int chunks64 = (T + EG64_CHUNK - 1) / EG64_CHUNK;
+    // bf16 at short outputs (da1 too small for the per-chunk tables): the layer loop's slab scratch, idle by now, so
+    // that the table is summed in chunk order there too, not with atomics -- the audio-only and the conditioned pass
+    // then agree to the bit (same partials, same order, whichever buffer holds them)
+    if (bf16 && !(slab && (size_t)chunks64 * batch * 2 * Q * 64 <= slab_floats) && cx_slab &&
+        (size_t)chunks64 * batch * 2 * Q * 64 <= cx_slab_floats) {
+      slab = cx_slab;
+      slab_floats = cx_slab_floats;
+    }
     if (C == 64 && Q % EG64_PARTS == 0 && (size_t)Q / EG64_PARTS * 64 * sizeof(float) <= 64 * 1024 && slab &&
         (size_t)chunks64 * batch * 2 * Q * 64 <= slab_floats) {
       // Q = 256: the product form; any other Q: the LDS read-modify-write kernel
@@ -2080,6 +2139,81 @@ int mvn_backward_bf16_global(const mvn_dims *dims, const mvn_params *p, const mv
   }
   return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_,
                        true, scratch, scratch_floats, rowsum);
+}
+
+// Video context on bf16 operands (fused_bf16.h: the CTX and WRITE_DFG instantiations, with the fp32
+// context pass behind it).  What the kernels place is what the labelled bf16 form places; the scratch is the fp32
+// conditioned layers' (second scatter pair, slabs of the layer pass and of the context pass, bias partials).
+int mvn_bf16_ctx_path(const mvn_dims *dims, int batch, int t_len) {
+  Geometry g;
+  if (make_geometry(dims, batch, t_len, g) || batch < 1) return 0;
+  return global_bf16_path(g, batch) ? 1 : 0;
+}
+
+size_t mvn_bf16_ctx_scratch_floats(const mvn_dims *dims, int batch, int t_len) {
+  Geometry g;
+  if (make_geometry(dims, batch, t_len, g) || batch < 1) return 0;
+  return global_scratch_floats(dims, g, batch);
+}
+
+// The refusals that need no buffer: the dims, the rows, a batch / length the kernels cannot place (MVN_ERR_UNSUPPORTED)
+static int bf16_ctx_supported(const char *what, const mvn_dims *dims, int batch, int t_len, int ctx_ld, Geometry &g) {
+  int rc = make_geometry(dims, batch, t_len, g);
+  if (rc) return rc;
+  rc = bf16_supported(what, g, false);
+  if (rc) return rc;
+  if (ctx_ld > (1 << 21)) {
+    set_error("%s: bf16 needs ctx_ld <= %d", what, 1 << 21);
+    return MVN_ERR_UNSUPPORTED;
+  }
+  if (batch >= 1 && !global_bf16_path(g, batch)) {
+    set_error("%s: the bf16 layer kernels cannot place batch %d, t_len %d (mvn_bf16_ctx_path)", what, batch, t_len);
+    return MVN_ERR_UNSUPPORTED;
+  }
+  return MVN_OK;
+}
+
+int mvn_forward_bf16_ctx(const mvn_dims *dims, const mvn_params *p, const int32_t *index, int index_stride,
+                         int batch, int t_len, const mvn_fwd_buffers *buf, float *out, int normalize,
+                         int remove_last, int save, void *stream_) {
+  Geometry g;
+  const int rc = bf16_ctx_supported("mvn_forward_bf16_ctx", dims, batch, t_len, buf ? buf->ctx_ld : 0, g);
+  if (rc) return rc;
+  if (!buf || !buf->ctx) {
+    set_error("mvn_forward_bf16_ctx: no context (buf->ctx is NULL)");
+    return MVN_ERR_BAD_ARG;
+  }
+  if (!p || !p->ctx_filter_w || !p->ctx_filter_b || !p->ctx_gate_w || !p->ctx_gate_b || buf->ctx_ld < t_len) {
+    set_error("mvn_forward_bf16_ctx: no context-conv parameters / ctx_ld < t_len");
+    return MVN_ERR_BAD_ARG;
+  }
+  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_,
+                      false, true, nullptr, true);
+}
+
+int mvn_backward_bf16_ctx(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
+                          const int32_t *index, int index_stride, int batch, int t_len,
+                          const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
+                          const float *dout, int normalize, int remove_last, float *scratch, size_t scratch_floats,
+                          void *stream_) {
+  Geometry g;
+  const int rc = bf16_ctx_supported("mvn_backward_bf16_ctx", dims, batch, t_len, fwd ? fwd->ctx_ld : 0, g);
+  if (rc) return rc;
+  if (!fwd || !fwd->ctx || !bwd || !bwd->dctx || !bwd->dfg) {
+    set_error("mvn_backward_bf16_ctx: no context / dctx / dfg buffer");
+    return MVN_ERR_BAD_ARG;
+  }
+  if (!p || !p->ctx_filter_w || !p->ctx_filter_b || !p->ctx_gate_w || !p->ctx_gate_b || !gr || !gr->ctx_filter_w ||
+      !gr->ctx_filter_b || !gr->ctx_gate_w || !gr->ctx_gate_b || fwd->ctx_ld < t_len) {
+    set_error("mvn_backward_bf16_ctx: no context-conv parameters or gradients / ctx_ld < t_len");
+    return MVN_ERR_BAD_ARG;
+  }
+  if (!scratch || (batch >= 1 && scratch_floats < global_scratch_floats(dims, g, batch))) {
+    set_error("mvn_backward_bf16_ctx: scratch is NULL or holds fewer floats than mvn_bf16_ctx_scratch_floats()");
+    return MVN_ERR_BAD_ARG;
+  }
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_,
+                       true, scratch, scratch_floats, nullptr, true);
 }
 
 int mvn_backward_scratch(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,

@@ -108,7 +108,7 @@ def run_forward(dims: N.Dims, sd: Dict[str, torch.Tensor], idx: torch.Tensor, no
     fp32 accumulation in the layers' products (mvn_forward_bf16; trains with mvn_backward_bf16).
     ``gvec``: (B, C) fp32 global vectors on the fast path of global conditioning (mvn_global_bias +
     mvn_forward_global, with ``bf16`` mvn_forward_bf16_global: C = K = 64, no ``ctx``; the caller has asked
-    mvn_global_fast_path / mvn_global_bf16_path)."""
+    mvn_global_fast_path / mvn_global_bf16_path).  ``bf16`` with ``ctx``: mvn_forward_bf16_ctx."""
     lib = N.lib()
     _require_gpu(idx, "audio")
     dense = None
@@ -132,6 +132,8 @@ def run_forward(dims: N.Dims, sd: Dict[str, torch.Tensor], idx: torch.Tensor, no
             (B, dims.input_channels, max(s_out, 0)), dtype=torch.float32, device=dev)
         params, keep = pack_params(dims, sd, L)
         name = "mvn_forward_f16" if f16 else "mvn_forward_bf16" if bf16 else "mvn_forward"
+        if bf16 and ctx is not None:  # (bf16_mode has asked for WaveNet.bf16_context)
+            name = "mvn_forward_bf16_ctx"
         tail = ()
         if gvec is not None:  # one 2C-vector per (layer, sequence) instead of a context product per column
             name = "mvn_forward_bf16_global" if bf16 else "mvn_forward_global"
@@ -278,6 +280,13 @@ def _run_backward(ctx_, params, out, dout, fill_dlogit):
             rowsum = alloc((L, B, 128), **f32)
             rowsum.zero_()
             tail = (scratch.data_ptr(), n_scratch, rowsum.data_ptr())
+        elif name == "mvn_backward_bf16" and ctx_.has_context:
+            # video context in bf16: the layer kernel's dfg-writing form, then the fp32 context pass; the scratch holds
+            # the second pair of gradient tensors, both passes' slabs and the bias partials
+            name = "mvn_backward_bf16_ctx"
+            n_scratch = int(lib.mvn_bf16_ctx_scratch_floats(dims, B, T))
+            scratch = alloc((n_scratch,), **f32)
+            tail = (scratch.data_ptr(), n_scratch)
         elif (getattr(dims, "_label_in_context", False) and ctx_.has_context and C == 64 and K == 64
               and name == "mvn_backward"):
             # global conditioning, general path: the conditioned layers' one-kernel backward with a scratch of its own
@@ -468,13 +477,19 @@ def bf16_mode(model, conditioned: bool, labelled: bool = False) -> bool:
     """Whether ``model.forward_precision`` asks for the bf16 layer kernels; raises ValueError, before
     anything is launched, for what they do not run (mvn_forward_bf16 / mvn_backward_bf16 refuse the same).  Labels run
     in bf16 only where the model asks for the one-vector-per-layer path by name (``global_path = "bias"``:
-    mvn_forward_bf16_global / mvn_backward_bf16_global); "auto" and "context" refuse them as before."""
+    mvn_forward_bf16_global / mvn_backward_bf16_global); "auto" and "context" refuse them as before.  A video context
+    runs only where the model opts in a second time (``bf16_context = True``: mvn_forward_bf16_ctx /
+    mvn_backward_bf16_ctx); labels then ride in the context ("auto" / "context"), and "bias" with video keeps raising."""
     if getattr(model, "forward_precision", "fp32") != "bf16":
         return False
     C, K = model._dims.residual_channels, model._dims.skip_channels
     if C != 64 or K != 64:
         raise ValueError("forward_precision 'bf16' needs residual_channels = skip_channels = 64, "
                          f"got {C} and {K}")
+    if conditioned and getattr(model, "bf16_context", False):
+        if labelled and getattr(model, "global_path", "auto") == "bias":
+            raise ValueError("global_path 'bias' runs models without a video context")
+        return True
     if conditioned:
         raise ValueError("forward_precision 'bf16' runs audio-only models: no video context")
     if labelled and getattr(model, "global_path", "auto") != "bias":

@@ -134,7 +134,8 @@ class Dance2Music(nn.Module):
         dtype = torch.bfloat16 if self.precision == "bf16" else getattr(torch, f"float{self.precision}")
         audio = audio.type(dtype).to(self.device)
         if self.config.use_video:
-            video = video.type(dtype).to(self.device)
+            # (bf16 with video, Trainer(bf16_video=True): the encoder and up-sampler stay fp32, and so does their input)
+            video = video.type(torch.float32 if self.precision == "bf16" else dtype).to(self.device)
         # output = self(audio, video) (probabilities, Q1); target = audio[:, :, RF:].argmax(1);
         # loss = cross_entropy(output, target) on those probabilities (Q2); accuracy -- the
         # reference's lines 62-66 as ONE autograd node: softmax + loss + accuracy in one pass
@@ -269,7 +270,9 @@ class Trainer:
                  num_sanity_val_steps: int = 0, callbacks=None, track_grad_norm: int = 2,
                  limit_train_batches: Optional[int] = None, device: Optional[str] = None,
                  enable_checkpointing: bool = True, limit_val_batches: Optional[int] = None,
-                 precision=32):
+                 precision=32, bf16_video: bool = False):
+        # bf16_video: with precision="bf16", train a use_video model too -- the conditioned layers on bf16 operands
+        # (WaveNet.bf16_context, which fit() sets and leaves set); ValueError with precision=32.
         # Lightning's precision switch: 32 (default) trains in exact fp32; "bf16" runs the layer stack's
         # products on bf16 operands with fp32 accumulation (WaveNet.forward_precision = "bf16"), fp32
         # everywhere else -- master weights, optimizer, head and loss included.  fit() then SETS, and leaves set,
@@ -281,6 +284,9 @@ class Trainer:
         if precision not in (32, "32", "bf16"):
             raise ValueError(f"precision must be 32 or 'bf16', got {precision!r}")
         self.precision = 32 if precision in (32, "32") else "bf16"
+        self.bf16_video = bool(bf16_video)
+        if self.bf16_video and self.precision != "bf16":
+            raise ValueError("Trainer(bf16_video=True) needs precision='bf16'")
         self.max_epochs = max_epochs
         self.root = Path(default_root_dir) if default_root_dir is not None else None
         self.clip = gradient_clip_val or 0.0
@@ -302,13 +308,15 @@ class Trainer:
 
     def fit(self, model: Dance2Music) -> None:
         if self.precision == "bf16":
-            if model.config.use_video:
+            if model.config.use_video and not self.bf16_video:
                 raise ValueError("Trainer(precision='bf16') trains audio-only models: set use_video to False")
             model.model.forward_precision = "bf16"
             model.precision = "bf16"
+            if self.bf16_video:
+                model.model.bf16_context = True
             from .ops import bf16_mode
             bf16_mode(model.model, False)  # (the channel constraint, before anything runs)
-            if int(getattr(model.model, "global_classes", 0)) > 0:
+            if int(getattr(model.model, "global_classes", 0)) > 0 and not model.config.use_video:
                 # labels (--use_global): the one-vector-per-layer path of the bf16 layer kernels, by name
                 model.model.global_path = "bias"
         rank, world, local_rank = init_distributed(model.config.dist_backend
@@ -458,6 +466,7 @@ class Trainer:
 def train_model(dataset: str, config: TrainingConfig, logger_name: Optional[str] = None,
                 log_video: bool = False, wandb_project: Optional[str] = None,
                 limit_train_batches: Optional[int] = None, precision=32) -> Trainer:
+    # (bf16_video travels in the config: --bf16_video 1)
     model = Dance2Music(dataset, config)
     if logger_name == "wandb":
         raise NotImplementedError("wandb logging is a SaaS integration and out of scope "
@@ -478,7 +487,7 @@ def train_model(dataset: str, config: TrainingConfig, logger_name: Optional[str]
         num_sanity_val_steps=0, callbacks=callbacks, track_grad_norm=2,
         limit_train_batches=(limit_train_batches if limit_train_batches is not None
                              else config.n_steps_per_epoch),
-        precision=precision)
+        precision=precision, bf16_video=bool(getattr(config, "bf16_video", False)))
     trainer.fit(model=model)
     return trainer
 

@@ -88,6 +88,9 @@ class WaveNet(nn.Module):
         # bf16 operands / fp32 accumulation in the layers' products, forward AND backward
         # (mvn_forward_bf16 / mvn_backward_bf16: audio-only, residual = skip channels = 64)
         self.forward_precision = "fp32"
+        # under forward_precision "bf16": also run a video context on bf16 operands (mvn_forward_bf16_ctx /
+        # mvn_backward_bf16_ctx); False (default): a context is refused, as before.  Labels with video ride in the context
+        self.bf16_context = False
         self._gen_sampling = "reference"
         self._gen_top_k, self._gen_top_p = 0, 1.0
         self._loss_rule = "reference"
