@@ -31,6 +31,10 @@
 // of a stage's LAST layer is added by the next stage, the head for the last one).  The constant
 // vectors Wc_1 br_0 and Wc_2 (br_0 + br_1) are packed once and ride in pf_1 / pf_2.  The
 // explicit x_0, x_1, x_2 feed the dilation queues off the critical path, exactly as in PIPE.
+// The hop: EVERY wave of a stage polls the stage's xp | zl granules itself (the head's waves: zl) and keeps them in a
+// strip of LDS of its own, which it reads back behind its own write -- the LDS serves a wave's accesses in order, so
+// between "granules visible" and a lane's first ds_read there is neither a wait for the write nor a barrier (one wave
+// polling for all needed both, eleven times per sample).  The waves meet at the phase-0 barrier (the head: conv1's).
 //
 // The products Wc Wr are formed once at pack time (fp64 sums, rounded to fp32).  The folded
 // form is the same real-number function as the reference's; its fp32 rounding differs from
@@ -73,11 +77,18 @@ constexpr int LDS_FLOATS = N_LDS_MAT * MAT_F + 1536 + 16;
 // channel), kept in LDS behind the vectors; the head keeps two class indices per sequence.
 constexpr int GMAX = 8;
 constexpr int PFS_F = 8;                    // floats per channel and sequence: pf0 pg0 pf1 pg1 | pf2 pg2 - -
-constexpr int LDS_FLOATS_MULTI = LDS_FLOATS + GMAX * C * PFS_F;
+constexpr int PFS_ALL_F = GMAX * C * PFS_F;
 // the head stage keeps, behind its 16 index words there, conv2's partial sums by k-slice: [8 waves][Q]
 constexpr int HEAD_PART_OFF = 16, HEAD_PART_F = 8 * Q;
-constexpr int LDS_FLOATS_ONE = LDS_FLOATS + HEAD_PART_OFF + HEAD_PART_F;  // MULTI = false: the layer stages use LDS_FLOATS of it
-static_assert(LDS_FLOATS_MULTI >= LDS_FLOATS_ONE, "the head's partial sums fit behind the index words");
+static_assert(PFS_ALL_F >= HEAD_PART_OFF + HEAD_PART_F, "MULTI: the head's partial sums fit behind the index words");
+// behind both: the waves' inbox strips, [8 waves][xp | zl] -- every wave of a stage polls the stage's granules itself and
+// reads its inputs back from its own strip (the LDS serves a wave's accesses in order: no wait, no barrier in between)
+constexpr int WIN_F = 2 * C, WIN_ALL_F = (NT / 64) * WIN_F;
+constexpr int WIN_OFF_ONE = LDS_FLOATS + HEAD_PART_OFF + HEAD_PART_F;  // MULTI = false (the layer stages use LDS_FLOATS and the strips)
+constexpr int WIN_OFF_MULTI = LDS_FLOATS + PFS_ALL_F;
+constexpr int LDS_FLOATS_ONE = WIN_OFF_ONE + WIN_ALL_F, LDS_FLOATS_MULTI = WIN_OFF_MULTI + WIN_ALL_F;
+static_assert(LDS_FLOATS_ONE * sizeof(float) <= 160 * 1024, "one sequence per pipeline: a CU's LDS");
+static_assert(LDS_FLOATS_MULTI * sizeof(float) <= 160 * 1024, "several sequences per pipeline: a CU's LDS");
 }  // namespace fold
 
 // A thread's share of a matrix: 32 floats = 8 float4 of the packed order.  Two formats:
@@ -235,6 +246,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
   u64 *outbox = hand + ((size_t)b * NS + s_next) * GRAN;
   int *iflag = (int *)(smem + LDS_FLOATS - 16);  // [0] ok flag, [3] fast-edge flag
   float *pfs = smem + LDS_FLOATS;                // MULTI: [GMAX][C][PFS_F] (layer stages), head: indices
+  float *win = smem + (MULTI ? WIN_OFF_MULTI : WIN_OFF_ONE) + WIN_F * __builtin_amdgcn_readfirstlane(wave);  // this wave's inbox strip
   const bool fast_edge = pipe_edge_is_fast(err + 16, b, s, s_next, NS, iflag);
 
   // ================= layer stage: layers l0 .. l0 + nl - 1 =================
@@ -264,6 +276,8 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
     unsigned vc = lds_addr(vec) + 4u * c;          // this lane's channel
     unsigned vq = lds_addr(vec) + 4u * KPER * kq;  // this lane's 16 inputs
     asm volatile("" : "+v"(vc), "+v"(vq));
+    // the wave's strip holds xp | zl as the vectors do (O_XP, O_ZL): byte offset from the vectors, wave-uniform
+    unsigned wo = lds_addr(win) - lds_addr(vec);
     u64 *ob = outbox + c;                // granules of this lane's channel: xp' | zl' (+ C) | sk' (+ 2C)
     const u64 *ibs = inbox + 2 * C + c;
     float *ring = a.state + (size_t)b * a.state_per_seq;
@@ -387,6 +401,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
         pf[0] = v.x; pg[0] = v.y; pf[1] = v.z; pg[1] = v.w; pf[2] = w.x; pg[2] = w.y;
       }
     };
+    if (tid == 0) iflag[0] = 1;  // cleared by a wave whose hand-off times out
     __syncthreads();
     if (MULTI) {
       for (int g = 0; g < G; ++g) {
@@ -407,18 +422,21 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
         if (ts + 1 < a.t_end) prefetch_pops(ts + 1);
       }
       const unsigned epoch = (unsigned)(ts - a.t_begin + 1);
-      if (wave == 0) {
-        // 2C granules: lane i takes 2i, 2i + 1 (xp for i < 32, zl above) with one 16-byte load; FIRST: xp alone
+      {
+        // EVERY wave takes the 2C granules itself: lane i takes 2i, 2i + 1 (xp for i < 32, zl above) with one 16-byte load
+        // (FIRST: xp alone) and leaves them in the wave's own strip, which the wave alone reads -- behind its own write,
+        // so neither a wait for the write nor a barrier stands between "granules visible" and the first ds_read
         float v[2];
         const bool ok = FIRST ? wait_inbox64(inbox, epoch, err, v) : wait_inbox<2>(inbox, epoch, err, v);
         if (ok && (!FIRST || lane < 32)) {
-          float *dst = vec + 2 * lane;  // O_XP and O_ZL are adjacent
+          float *dst = win + 2 * lane;  // O_XP and O_ZL are adjacent
           dst[0] = v[0];
           dst[1] = v[1];
         }
-        if (lane == 0) iflag[0] = ok ? 1 : 0;
+        if (!ok && lane == 0) iflag[0] = 0;  // (the wave runs the step on stale values and leaves with the others below)
+        asm volatile("" ::: "memory");
       }
-      lds_barrier();
+      asm volatile("" : "+s"(wo));  // (added to the bases where used: not one more address register across the step)
       MVN_STAMP(b, s, ts - a.t_begin, 0);
       load_pf(g);
       float xv = 0.f;  // helper lead lanes: the explicit stream
@@ -426,8 +444,8 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
       // ---- phase 0
       if (chain) {
         f4 xa[NF4], xb[NF4];
-        ldsv<NF4>(xa, vq, O_XP);
-        if (!FIRST) ldsv<NF4>(xb, vq, O_ZL);
+        ldsv<NF4>(xa, vq + wo, O_XP);
+        if (!FIRST) ldsv<NF4>(xb, vq + wo, O_ZL);
         v2f acc[4];
         pair_acc<true>(acc, m0.w, xa);
         if (!FIRST) pair_acc<false>(acc, m1.w, xb);
@@ -439,8 +457,8 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
         MVN_FINE(b, s, ts - a.t_begin, 1, 0);
       } else {
         f4 xa[NF4], xb[NF4];
-        ldsv<NF4>(xa, vq, O_XP);
-        if (!FIRST) ldsv<NF4>(xb, vq, O_ZL);
+        ldsv<NF4>(xa, vq + wo, O_XP);
+        if (!FIRST) ldsv<NF4>(xb, vq + wo, O_ZL);
         v2f acc[4];
         pair_acc<true>(acc, m0.w, xa);
         if (!FIRST) pair_acc<false>(acc, m1.w, xb);
@@ -451,7 +469,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
         const float g = chan_sum<KQ>(fg.y);
         if (!FIRST) r = chan_sum<KQ>(r);
         if (lead) {
-          xv = LDSF(vc, O_XP) + r;               // x_0 (br_prev already inside xp)
+          xv = LDSF(vc + wo, O_XP) + r;               // x_0 (br_prev already inside xp)
           LDSF(vc, O_X0) = xv;
           xs[0] = xv;
           LDSF(vc, O_B1) = f;
@@ -547,7 +565,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
           unsigned wss = lds_addr(lmat + 3 * MAT_F) + 16u * t;  // SS = {Ws_prev; Ws_0}
           asm volatile("" : "+v"(wss));
           float kp = 0.f;
-          if (!FIRST) kp = split_dot_lds<0>(wss, vq + 4u * O_ZL);
+          if (!FIRST) kp = split_dot_lds<0>(wss, vq + wo + 4u * O_ZL);
           float k0 = split_dot_lds<1>(wss, vq + 4u * O_Z0);
           if (!FIRST) kp = chan_sum<KQ>(kp);
           k0 = chan_sum<KQ>(k0);
@@ -577,7 +595,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
       }
       MVN_STAMP(b, s, ts - a.t_begin, 1);
       lds_barrier();  // iflag and the step's LDS vectors are settled for everyone
-      if (iflag[0] == 0) {  // hand-off timed out (checked after the step: off the chain)
+      if (iflag[0] == 0) {  // some wave's hand-off timed out (checked after the step: off the chain)
         alive = false;
         break;
       }
@@ -606,8 +624,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
   {
     float *tab = smem;                    // embedding tables [2][Q][C] (128 KB)
     float *vec = smem + N_LDS_MAT * MAT_F;
-    float *zlb = vec;                     // [C] last layer's gated activation
-    float *a0 = zlb + C;                  // [C] lrelu(skip)
+    float *a0 = vec + C;                  // [C] lrelu(skip)  (the last layer's gated activation: in every wave's strip)
     float *a1 = a0 + C;                   // [Q] conv1's result: wave w writes, and alone reads, a1[32 w .. 32 w + 31]
     float *b2l = a1 + Q;                  // [Q] conv2's bias (wave 0 reads it with the partial sums: four registers less)
     float *part = pfs + HEAD_PART_OFF;    // [8][Q] conv2's partial sums: row w = wave w's k-slice, all outputs
@@ -638,16 +655,26 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
     const float b1r = b1[o1];
     if (tid < Q) b2l[tid] = b2[tid];
     const float bslr = bsl[og];
+    if (tid == 0) iflag[0] = 1;  // cleared by a wave whose hand-off times out
     __syncthreads();
 
     // (head_loop starts a step with xp = the causal conv's two embedding rows alone: stage 0 reads no zl and no sk)
-    auto await = [&](const u64 *inbox, unsigned epoch) {  // wave 0
+    // the strip's two addresses (lanes' writes, the skip 1x1's reads) are formed in the step, in front of the wait,
+    // from the thread index: held across the step they cost the per-sequence form two spilled registers
+    const unsigned zs = lds_addr(win);  // this wave's strip: zl alone is used
+    unsigned zrd = 0;
+    auto await = [&](const u64 *inbox, unsigned epoch) {  // every wave, into its own strip (head_loop: WAVE_INBOX)
+      unsigned zq = __builtin_amdgcn_readfirstlane(zs), tq = tid;
+      asm volatile("" : "+s"(zq), "+v"(tq));
+      const unsigned wa = zq + 8u * (tq & 63u);
+      zrd = zq + 32u * (tq & 7u);
       float v[2];
       const bool ok = wait_inbox64(inbox + C, epoch, err, v);  // zl (the last stage sends no xp')
       if (ok && lane < 32) {
-        zlb[2 * lane] = v[0];
-        zlb[2 * lane + 1] = v[1];
+        LDSF(wa, 0) = v[0];
+        LDSF(wa, 1) = v[1];
       }
+      asm volatile("" ::: "memory");
       return ok;
     };
     auto logits = [&](const u64 *inbox, unsigned epoch, bool do_head) {
@@ -657,7 +684,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
       if (do_head) {
         // the last layer's skip 1x1 (modules.py:90-91)
         f4 x[2];
-        ldsn<2>(x, zlb + 8 * q2);
+        ldsv<2>(x, zrd, 0);  // behind this wave's own write
         sv = dotn<2>(wsl, x);
         sv = quad_sum(sv);
         sv += other_quad(sv);
@@ -669,7 +696,10 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
         skin = (unsigned)(sk_peek >> 32) == epoch ? __uint_as_float((unsigned)sk_peek)
                                                   : wait_granule(inbox + 2 * C + og, epoch, err);
       MVN_FINE(b, NS - 1, epoch - 1, 1, 0);
-      if (!do_head) return;
+      if (!do_head) {
+        lds_barrier();  // (the one meeting of such a step: no wave is ever more than a step behind wave 0's send)
+        return;
+      }
       // skip sum, then the head's first leaky-ReLU (modules.py:140)
       if (q2 == 0) a0[og] = leaky(skin + (sv + bslr));
       lds_barrier();
@@ -704,7 +734,7 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
       r.w = (((p[0].w + p[1].w) + (p[2].w + p[3].w)) + ((p[4].w + p[5].w) + (p[6].w + p[7].w))) + b2v.w;
       return r;
     };
-    head_loop<C, GRAN, MULTI, SEQ, 2, 0, GUIDED>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, part, await, logits,
+    head_loop<C, GRAN, MULTI, SEQ, 2, 0, GUIDED, true>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, part, await, logits,
                                                  take);
   }
 }

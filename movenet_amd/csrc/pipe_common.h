@@ -733,6 +733,9 @@ __device__ __forceinline__ void head_conv2_f32(const v2f (&w2)[4][16], const flo
 //                                  (do_head is block-uniform; false: no logits are needed for this step)
 //   take(lgb, lane)                wave 0, behind that barrier: the float4 of logits 4 lane .. 4 lane + 3.  Default: the
 //                                  read of lgb; FOLD sums its waves' partial sums here instead (generate_fold.hip)
+// WAVE_INBOX (FOLD): await is called by EVERY wave and stores the input where that wave alone reads it; no barrier
+// follows it -- logits() meets at its own first barrier, also when do_head is false -- and iflag[0], set to 1 by the
+// caller in front of a barrier, is cleared by a wave whose wait times out.
 // iflag / hidx: LDS words ([0]: the hand-off's ok flag; MULTI: [GMAX][2] = {idx_cur, idx_prev} of each sequence
 // between its turns).
 // SEQ (mvn_generate_seq): the settings of a step are those of the sequence whose turn it is, a.per_seq[bq], loaded
@@ -745,8 +748,8 @@ __device__ __forceinline__ void head_conv2_f32(const v2f (&w2)[4][16], const flo
 struct HeadLgbRead {
   __device__ __forceinline__ f4 operator()(const float *lgb, int lane) const { return ((const f4 *)lgb)[lane]; }
 };
-template <int C, int GRAN, bool MULTI, bool SEQ, int NZ, int NZ_SENT = NZ, bool GUIDED = false, class Await, class Logits,
-          class Take = HeadLgbRead>
+template <int C, int GRAN, bool MULTI, bool SEQ, int NZ, int NZ_SENT = NZ, bool GUIDED = false, bool WAVE_INBOX = false,
+          class Await, class Logits, class Take = HeadLgbRead>
 __device__ __forceinline__ void head_loop(const KArgs<SEQ, GUIDED> &a, u64 *hand, int NS, int nb, int b, int G, bool fast_edge,
                                           const float *E0, const float *E1, int *iflag, int *hidx, const float *lgb,
                                           Await await, Logits logits, Take take = Take()) {
@@ -821,12 +824,17 @@ __device__ __forceinline__ void head_loop(const KArgs<SEQ, GUIDED> &a, u64 *hand
       uni = philox_uniform(ss.seed, (uint32_t)u, ss.row);
       asm volatile("" : "+v"(uni));
     }
-    if (wave == 0) {
-      if (u < a.n_given) next_idx = samples[u];  // prompt / teacher forcing
-      const bool ok = await(inbox, epoch);
-      if (lane == 0) iflag[0] = ok ? 1 : 0;
+    if constexpr (WAVE_INBOX) {
+      if (wave == 0 && u < a.n_given) next_idx = samples[u];  // prompt / teacher forcing
+      if (!await(inbox, epoch) && lane == 0) iflag[0] = 0;
+    } else {
+      if (wave == 0) {
+        if (u < a.n_given) next_idx = samples[u];  // prompt / teacher forcing
+        const bool ok = await(inbox, epoch);
+        if (lane == 0) iflag[0] = ok ? 1 : 0;
+      }
+      lds_barrier();
     }
-    lds_barrier();
     MVN_STAMP(b, s, ts - a.t_begin, 0);
     logits(inbox, epoch, do_head);
     if constexpr (GUIDED) {
