@@ -754,6 +754,28 @@ size_t mvn_audio_frontend_scratch_floats(int batch, int n_out);
 int mvn_audio_frontend(const int16_t *pcm, long long pcm_len, const mvn_audio_clip *clips, int batch, int classes,
                        int n_out, int normalize, float *y, float *scratch, int32_t *index, void *stream);
 
+/* The loader's video front end (movenet/dataset.py:292-310 behind the decoder): a batch of clips of different
+ * resolutions, as interleaved uint8 frames in one upload, -> (batch, n_frames, 64, 64) uint8 gray levels.  Per frame:
+ * L = uint8(0.2989 r + 0.587 g + 0.114 b), fp32 products and sums each rounded, the cast truncating (skipped for
+ * channels == 1); then torch's bilinear resize of L to 64 x 64 with align_corners=False and antialias as given,
+ * rounded half to even.  No division by 255: the levels are 0 .. 255.
+ *   pix      DEVICE, pix_len bytes: every clip's n_frames frames, each (n_frames, height, width, channels) uint8, rows
+ *            of width * channels bytes without padding; offsets and the pointer itself need no alignment
+ *   clips    DEVICE, one descriptor per clip: byte offset of its first frame, height, width, channels (3: RGB, 1: gray)
+ *   levels   DEVICE (batch, n_frames, 64, 64) uint8, written in full
+ *   status   DEVICE (batch,) int32: 0, or why the clip was not read
+ * The descriptors are read on the device, so they are checked there: a clip whose span does not lie inside
+ * [0, pix_len) (status 1), whose channels is not 1 or 3 (status 2), or whose height or width is outside [1, 4096]
+ * (status 3) is not read at all and its levels are zero.  On the host, a null pointer, pix_len < 0, batch < 0,
+ * n_frames < 1, antialias other than 0 or 1, or batch * n_frames * 16 workgroups beyond 2^31 - 1 is MVN_ERR_BAD_ARG
+ * before any launch; batch == 0 is MVN_OK and launches nothing.  One launch, no atomics: bit-reproducible. */
+typedef struct {
+  int64_t offset;
+  int32_t height, width, channels, reserved;
+} mvn_video_clip;
+int mvn_video_frontend(const uint8_t *pix, long long pix_len, const mvn_video_clip *clips, int batch, int n_frames,
+                       int antialias, uint8_t *levels, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

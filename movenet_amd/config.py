@@ -81,6 +81,10 @@ class TrainingConfig:
     # without them loads with the defaults (off).
     generate_guidance: float = 1.0
     global_dropout: float = 0.0
+    # raw uint8 frames in a WAV folder (WavFolderLoader): video_antialias is the resize rule of the GPU front
+    # end (False: torchvision 0.13 - 0.16's resize of a tensor; True: the default of 0.17 on).  Not a reference field:
+    # a JSON written without it loads with the default.
+    video_antialias: bool = False
 
     # exponential moving average of the weights, kept by the fused optimizer step (FlatAdamW(ema_decay=...), DESIGN
     # 4.6): 0 is off; above 0, validation, the logged samples and the checkpoint's "ema_state_dict" come from the
@@ -181,6 +185,7 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--bf16_video", type=_flag, default=False)
     a("--generate_guidance", type=float, default=1.0)
     a("--global_dropout", type=float, default=0.0)
+    a("--video_antialias", type=_flag, default=False)
     a("--batch_subsample_frac", type=float, default=None)
     a("--val_batch_subsample_frac", type=float, default=None)
     a("--gradient_clipping", type=float, default=0.0)
@@ -221,7 +226,7 @@ def config_from_args(args) -> TrainingConfig:
         "scheduler_cyclic_mode scheduler_cyclic_gamma scheduler_cycle_momentum max_learning_rate "
         "scheduler_step_size scheduler_step_gamma scheduler_milestones weight_decay "
         "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule ema_decay ema_warmup accumulation_steps num_workers val_num_workers "
-        "pin_memory n_epochs n_steps_per_epoch use_video use_global bf16_video generate_guidance global_dropout batch_subsample_frac "
+        "pin_memory n_epochs n_steps_per_epoch use_video use_global bf16_video generate_guidance global_dropout video_antialias batch_subsample_frac "
         "val_batch_subsample_frac dist_backend dist_port model_output_path log_samples_every"
     ).split()
     kw = {k: getattr(args, k) for k in copied}  # NB: gradient_clipping is not among them (Q11)

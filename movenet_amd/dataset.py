@@ -18,8 +18,9 @@ Beside it, a folder of integer-PCM WAV files in the reference's layout (``WavFol
     --dataset /data/my_wavs          # <dir>/train/<context>/*.wav, <dir>/valid/<context>/*.wav
 
 What the reference does to a decoded waveform (channel mean, resample to MAX_AUDIO_FRAMES, min-max normalisation,
-mu-law, one-hot: dataset.py:253-289) runs on the GPU behind the upload (ops.audio_frontend); the decoder itself
-stays out of scope.
+mu-law, one-hot: dataset.py:253-289) runs on the GPU behind the upload (ops.audio_frontend), and so does what it does to
+decoded frames (RGB -> gray, resize to 64 x 64: dataset.py:292-310; ops.video_frontend); the decoders themselves stay
+out of scope.
 """
 from __future__ import annotations
 
@@ -262,6 +263,49 @@ class _IndexCache:
 _INDEX_CACHES: dict = {}
 
 
+class _LevelCache:
+    """(n, 64, 64) uint8 gray levels of the raw-frame clips seen so far, on the device: one byte per pixel.  Past ``max_bytes`` nothing is evicted: new clips are simply not kept."""
+
+    def __init__(self, max_bytes: int):
+        self.max_bytes, self.bytes = int(max_bytes), 0
+        self.rows: dict = {}
+        self.hits = self.misses = 0
+
+    def put(self, key, levels: torch.Tensor) -> None:
+        size = levels.numel()
+        if key not in self.rows and self.bytes + size <= self.max_bytes:
+            self.rows[key] = levels.clone()  # (a view of the launch's output would keep the whole batch alive)
+            self.bytes += size
+
+
+_LEVEL_CACHES: dict = {}
+
+# Bound on the selected frames one front-end launch takes (and so on a pinned staging buffer of the ring): a batch whose
+# raw frames exceed it is split over several launches, clip by clip; a single clip beyond it goes up alone.
+VIDEO_STAGE_BYTES = 256 << 20
+VIDEO_UNIT_SCALE = float(np.float32(1.0 / 255.0))  # levels -> the [0, 1] of the pre-made form
+
+
+def inspect_video_file(fp: str):
+    """What ``<stem>.npy`` holds, from its header (the array is memory-mapped, nothing is read): ``None`` for the
+    pre-made form -- (F, 64, 64) or (F, 64, 64, 1), not uint8, taken as is -- or (F, H, W, channels) for raw uint8
+    frames, (F, H, W, 3) RGB or (F, H, W) gray.  ValueError naming the file for anything else."""
+    v = np.load(fp, mmap_mode="r", allow_pickle=False)
+    if v.dtype != np.uint8:
+        shape = v.shape[:-1] if v.ndim == 4 and v.shape[-1] == 1 else v.shape
+        if len(shape) != 3 or shape[1:] != (64, 64) or shape[0] < 1:
+            raise ValueError(f"{fp}: expected (F, 64, 64) or (F, 64, 64, 1) gray frames, got {v.shape}")
+        return None
+    if not (v.ndim == 3 or (v.ndim == 4 and v.shape[-1] == 3)):
+        raise ValueError(f"{fp}: raw uint8 frames are (F, H, W, 3) RGB or (F, H, W) gray, got {v.shape}")
+    F, H, W = (int(x) for x in v.shape[:3])
+    if F < 1:
+        raise ValueError(f"{fp}: no video frames in {v.shape}")
+    if not (1 <= H <= 4096 and 1 <= W <= 4096):
+        raise ValueError(f"{fp}: frames of {H} x {W} lie outside 1 .. 4096 per side")
+    return F, H, W, (3 if v.ndim == 4 else 1)
+
+
 class WavFolderLoader:
     """Clips from a folder of WAV files, in the reference's KineticsDataset layout with ``.wav`` for ``.mp4``
     (movenet/dataset.py:101-140):
@@ -284,14 +328,29 @@ class WavFolderLoader:
     second epoch on a cached clip costs no file read, no upload and no front-end launch.  Loaders of the same split,
     class count, normalisation and device share one cache (the trainer builds a loader per epoch).
 
-    Video (``use_video=True``): ``<stem>.npy`` beside ``<stem>.wav`` holding (F, 64, 64) or (F, 64, 64, 1) values in
-    [0, 1], ALREADY gray and ALREADY 64 x 64 -- RGB -> gray and the spatial resize belong to the decoder side and are
-    out of scope.  It is reduced to ``frames // 1000`` frames by pytorchvideo's uniform_temporal_subsample rule."""
+    Video (``use_video=True``): ``<stem>.npy`` beside ``<stem>.wav``, reduced to ``frames // 1000`` frames by
+    pytorchvideo's uniform_temporal_subsample rule.  Two forms, told apart by dtype, which may be mixed in a folder:
+
+    * pre-made: (F, 64, 64) or (F, 64, 64, 1), not uint8, values in [0, 1], ALREADY gray and ALREADY 64 x 64, taken as
+      they are;
+    * raw frames, as a decoder hands them over: uint8 (F, H, W, 3) RGB or (F, H, W) gray, H and W in [1, 4096].  The
+      file is memory-mapped and only the selected frames are copied out; the selected frames of a batch cross PCIe as
+      one asynchronous copy with their descriptors, and the reference's ``resize_video`` (torchvision
+      rgb_to_grayscale, then resize to 64 x 64: dataset.py:292-310) runs behind it on the GPU (ops.video_frontend;
+      ``video_antialias`` False is torchvision 0.13 - 0.16's resize of a tensor, True the default of 0.17 on).  A
+      batch whose selected frames exceed VIDEO_STAGE_BYTES is split over several launches.  The uint8 levels of every
+      raw clip seen stay on the device up to ``video_cache_bytes``, shared by loaders of the same split, antialias
+      setting and device; a cached clip costs no file read, no upload and no launch.  ``Batch.video`` is
+      ``levels.float() * fp32(1 / 255)``: the [0, 1] of the pre-made form.  (The reference's loader hands its model
+      0 .. 255; that range is not offered.)  The kernel's per-clip status of every launch is read once, when the
+      epoch's last batch has been handed out, and a refusal raises there: iterating itself never waits for the GPU."""
 
     def __init__(self, root, input_channels: int, batch_size: int, train: bool = True,
                  rank: int = 0, world_size: int = 1, shuffle: bool = False,
                  batch_subsample_frac: Optional[float] = None, use_video: bool = False,
-                 normalize_audio: bool = True, device=None, cache_bytes: int = 4 << 30, **_ignored):
+                 normalize_audio: bool = True, device=None, cache_bytes: int = 4 << 30,
+                 video_antialias: bool = False, video_cache_bytes: int = 4 << 30,
+                 **_ignored):
         import os
         from pathlib import Path
         from . import wavenet as W
@@ -309,6 +368,11 @@ class WavFolderLoader:
                              "which its own size assert then rejects)")
         if input_channels > 32768:
             raise ValueError("input_channels above 32768 do not fit the int16 index cache")
+        if video_antialias not in (False, True, 0, 1):
+            raise ValueError(f"video_antialias must be 0 or 1, got {video_antialias!r}")
+        self.video_antialias = bool(video_antialias)
+        self._video_status: list = []  # (clips, status tensor) of the front-end launches not yet looked at
+        self.raw_video: dict = {}  # clip -> (F, H, W, channels) of a raw-frame file (pre-made files are absent)
         self.contexts = _context_folders(self.root_path)
         self.index = []  # (context, path, header)
         for context in self.contexts:
@@ -323,18 +387,28 @@ class WavFolderLoader:
                                      "the front end resamples to")
                 if use_video and not fp.with_suffix(".npy").is_file():
                     raise ValueError(f"{fp}: use_video needs the clip's frames in {fp.with_suffix('.npy').name}")
+                if use_video:
+                    raw = inspect_video_file(str(fp.with_suffix(".npy")))
+                    if raw is not None:
+                        self.raw_video[len(self.index)] = raw
                 self.index.append((context, str(fp), h))
         if not self.index:
             raise ValueError(f"{self.root_path}: no .wav clips (expected <context>/*.wav below it)")
         self.filepaths = [fp for _, fp, _ in self.index]
-        self.info = [dict(video_fps=0.0, audio_fps=float(h["rate"]), video_orig_dim=0,
-                          audio_orig_dim=int(h["frames"])) for _, _, h in self.index]
+        self.info = [dict(video_fps=0.0, audio_fps=float(h["rate"]),
+                          video_orig_dim=self.raw_video[i][0] if i in self.raw_video else 0,
+                          audio_orig_dim=int(h["frames"])) for i, (_, _, h) in enumerate(self.index)]
         self.n_clips = len(self.index)
         key = (os.path.abspath(str(self.root_path)), self.Q, self.frames, self.normalize, str(self.device))
         cache = _INDEX_CACHES.get(key)
         if cache is None or cache.max_bytes != int(cache_bytes):
             cache = _INDEX_CACHES[key] = _IndexCache(cache_bytes)
         self.cache = cache
+        vkey = (os.path.abspath(str(self.root_path)), self.frames, self.video_antialias, str(self.device))
+        vcache = _LEVEL_CACHES.get(vkey)
+        if vcache is None or vcache.max_bytes != int(video_cache_bytes):
+            vcache = _LEVEL_CACHES[vkey] = _LevelCache(video_cache_bytes)
+        self.video_cache = vcache
         self.epoch = 0
 
     set_epoch = SyntheticLoader.set_epoch
@@ -343,19 +417,96 @@ class WavFolderLoader:
 
     def cache_stats(self) -> dict:
         c = self.cache
-        return dict(hits=c.hits, misses=c.misses, clips=len(c.rows), bytes=c.bytes)
+        stats = dict(hits=c.hits, misses=c.misses, clips=len(c.rows), bytes=c.bytes)
+        if self.use_video:  # the raw-frame clips' level cache (pre-made clips pass it by)
+            v = self.video_cache
+            stats.update(video_hits=v.hits, video_misses=v.misses, video_clips=len(v.rows), video_bytes=v.bytes)
+        return stats
+
+    def _frame_selection(self, F: int) -> np.ndarray:
+        """pytorchvideo.transforms.functional.uniform_temporal_subsample: linspace, clamp, truncate."""
+        return np.clip(np.linspace(0, F - 1, self.frames // 1000), 0, F - 1).astype(np.int64)
+
+    def _raw_frames(self, i: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """The selected frames of raw clip ``i`` as (n, H, W, channels) uint8, copied out of the memory-mapped file
+        (the frames that are not selected are never read)."""
+        F, H, W, ch = self.raw_video[i]
+        v = np.load(self.index[i][1][:-len(".wav")] + ".npy", mmap_mode="r", allow_pickle=False)
+        at = self._frame_selection(F)
+        if out is None:
+            out = np.empty((len(at), H, W, ch), dtype=np.uint8)
+        # (mode="clip": the default "raise" gathers into a temporary first; the indices are in range by construction)
+        np.take(v.reshape(F, H, W, ch), at, axis=0, out=out.reshape(len(at), H, W, ch), mode="clip")
+        return out
+
+    def _levels(self, ids: List[int]) -> dict:
+        """clip -> (n, 64, 64) uint8 levels on the device for the raw clips among ``ids``: cached ones as they are,
+        the others read, uploaded and sent through the front end, one launch per VIDEO_STAGE_BYTES of frames."""
+        from .ops import video_clip_descriptors, video_frontend
+        cache, dev, n = self.video_cache, self.device, self.frames // 1000
+        raw = [i for i in ids if i in self.raw_video]
+        todo = [i for i in dict.fromkeys(raw) if i not in cache.rows]
+        cache.hits += sum(i in cache.rows for i in raw)
+        cache.misses += len(raw) - sum(i in cache.rows for i in raw)
+        got = {i: cache.rows[i] for i in raw if i in cache.rows}
+        size = lambda i: n * self.raw_video[i][1] * self.raw_video[i][2] * self.raw_video[i][3]
+        while todo:
+            group = [todo.pop(0)]
+            total = size(group[0])
+            while todo and total + size(todo[0]) <= VIDEO_STAGE_BYTES:
+                total += size(todo[0])
+                group.append(todo.pop(0))
+            # (padded to a 1 MiB step: batches of like-sized clips reuse the ring's pinned buffers)
+            pix = np.empty(-(-total // (1 << 20)) * (1 << 20), dtype=np.uint8)
+            at = 0
+            for i in group:
+                self._raw_frames(i, out=pix[at:at + size(i)])
+                at += size(i)
+            shapes = [self.raw_video[i][1:] for i in group]
+            d_pix = _PinnedRing.to_device(_ring("pix", dev).stage(pix), dev)
+            d_desc = _PinnedRing.to_device(_ring("vclips", dev).stage(video_clip_descriptors(shapes, n)), dev)
+            levels, status = video_frontend(d_pix, shapes, n, antialias=self.video_antialias, descriptors=d_desc,
+                                            return_status=True)
+            self._video_status.append((list(group), status))
+            for row, i in enumerate(group):
+                got[i] = levels[row]
+                cache.put(i, levels[row])
+        return got
+
+    def check_video_status(self) -> None:
+        """Reads the per-clip status of the front-end launches made so far (this waits for them) and raises ValueError
+        naming the file of a clip the kernel refused.  ``__iter__`` calls it behind the epoch's last batch."""
+        pending, self._video_status = self._video_status, []
+        for group, status in pending:
+            for i, st in zip(group, status.cpu().tolist()):
+                if st:
+                    raise ValueError(f"{self.index[i][1][:-len('.wav')]}.npy: the video front end refused the clip "
+                                     f"on the device (status {st})")
+
+    def _video_batch(self, ids: List[int]) -> torch.Tensor:
+        """(B, n, 64, 64, 1) float32 on the device: raw clips through the front end, scaled into [0, 1];
+        pre-made clips as they are."""
+        dev = self.device
+        if not any(i in self.raw_video for i in ids):
+            return _to_device_async(np.stack([self._video(i) for i in ids]), dev)
+        with torch.cuda.device(dev):
+            levels = self._levels(ids)
+            rows = {i: levels[i].to(torch.float32) * VIDEO_UNIT_SCALE for i in dict.fromkeys(ids) if i in levels}
+            made = [i for i in dict.fromkeys(ids) if i not in levels]
+            if made:
+                up = _to_device_async(np.stack([self._video(i) for i in made]), dev)
+                rows.update({i: up[k, ..., 0] for k, i in enumerate(made)})
+            return torch.stack([rows[i] for i in ids])[..., None]
 
     def _video(self, i: int) -> np.ndarray:
+        """The selected frames of a pre-made clip, (n, 64, 64, 1) float32 as stored."""
         fp = self.index[i][1][:-len(".wav")] + ".npy"
         v = np.load(fp, allow_pickle=False)
         if v.ndim == 4 and v.shape[-1] == 1:
             v = v[..., 0]
         if v.ndim != 3 or v.shape[1:] != (64, 64) or v.shape[0] < 1:
             raise ValueError(f"{fp}: expected (F, 64, 64) or (F, 64, 64, 1) gray frames, got {v.shape}")
-        n = self.frames // 1000
-        # pytorchvideo.transforms.functional.uniform_temporal_subsample: linspace, clamp, truncate
-        at = np.clip(np.linspace(0, v.shape[0] - 1, n), 0, v.shape[0] - 1).astype(np.int64)
-        return np.ascontiguousarray(v[at], dtype=np.float32)[..., None]
+        return np.ascontiguousarray(v[self._frame_selection(v.shape[0])], dtype=np.float32)[..., None]
 
     def _indices(self, ids: List[int]) -> torch.Tensor:
         """(B, N) int32 class indices of the clips on the device: cached rows as they are, the others read,
@@ -408,9 +559,10 @@ class WavFolderLoader:
                         "mvn_index_to_onehot")
             video = None
             if self.use_video:
-                video = _to_device_async(np.stack([self._video(i) for i in ids]), dev)
+                video = self._video_batch(ids)
             yield Batch(audio, video, [self.index[i][0] for i in ids], [self.filepaths[i] for i in ids],
                         [self.info[i] for i in ids])
+        self.check_video_status()
 
 
 def _is_wav_folder(filepath) -> bool:
@@ -443,7 +595,8 @@ def get_dataloader(filepath, input_channels: int, batch_size: int = 64, train: b
     """Signature of movenet/dataset.py:59-98.  ``synthetic://...`` gives a SyntheticLoader; an existing directory
     with a ``train`` or ``valid`` sub-folder gives a WavFolderLoader; anything else raises ValueError."""
     if not str(filepath).startswith("synthetic://") and _is_wav_folder(filepath):
-        extra = {"cache_bytes": kwargs["cache_bytes"]} if "cache_bytes" in kwargs else {}
+        extra = {k: kwargs[k] for k in ("cache_bytes", "video_antialias", "video_cache_bytes")
+                 if k in kwargs}
         return WavFolderLoader(filepath, input_channels, batch_size, train=train, rank=rank,
                                world_size=world_size, shuffle=kwargs.get("shuffle", False),
                                batch_subsample_frac=batch_subsample_frac, use_video=use_video,

@@ -720,6 +720,97 @@ def audio_frontend(pcm: torch.Tensor, frames, channels, quantization_channels: i
     return (idx, y) if return_waveform else idx
 
 
+VIDEO_FRONTEND_SIZE = 64       # the front end's output is (64, 64) per frame (movenet/dataset.py:292-310)
+VIDEO_FRONTEND_MAX_DIM = 4096  # H, W <= 4096: a gray source row fits the kernel's LDS row
+
+_VIDEO_CLIP = [("offset", "<i8"), ("height", "<i4"), ("width", "<i4"), ("channels", "<i4"), ("reserved", "<i4")]
+
+
+def video_clip_descriptors(shapes, n_frames: int, offsets=None):
+    """Host array of mvn_video_clip records (int64 byte offset, int32 height, width, channels, reserved) as (B, 6)
+    int32; ``shapes`` is one (H, W, channels) per clip and ``offsets`` default to the clips' ``n_frames`` frames lying
+    back to back in the upload."""
+    import numpy as np
+    rec = np.zeros(len(shapes), dtype=_VIDEO_CLIP)
+    if len(shapes):
+        arr = np.asarray(shapes, dtype=np.int64).reshape(len(shapes), 3)
+        rec["height"], rec["width"], rec["channels"] = arr[:, 0], arr[:, 1], arr[:, 2]
+        if offsets is None:
+            spans = int(n_frames) * arr[:, 0] * arr[:, 1] * arr[:, 2]
+            offsets = np.concatenate([[0], np.cumsum(spans)[:-1]])
+        rec["offset"] = offsets
+    return rec.view(np.int32).reshape(len(shapes), 6)
+
+
+def video_frontend(pix: torch.Tensor, shapes, n_frames: int, antialias: bool = False,
+                   descriptors: torch.Tensor = None, *, offsets=None, out: torch.Tensor = None,
+                   return_status: bool = False, check: bool = True):
+    """Decoded frames -> 64 x 64 gray levels on the GPU (mvn_video_frontend): what the reference's loader does per
+    frame, torchvision's ``rgb_to_grayscale`` then ``resize`` to (64, 64) (bilinear, ``antialias`` as given; False is
+    what torchvision 0.13 - 0.16 do for tensors), rounded half to even.  No division by 255.
+
+    ``pix``: 1-D uint8 tensor on the GPU, every clip's ``n_frames`` frames as (n_frames, H, W, channels) bytes.
+    ``shapes``: per clip (H, W, channels), channels 3 (RGB) or 1 (already gray), H and W in [1, 4096]; ``offsets``:
+    per clip, byte offsets into ``pix`` (default back to back); both are checked here against the upload.
+    ``descriptors`` is the same already on the device ((B, 6) int32 of video_clip_descriptors -- the loader ships it
+    through its pinned ring).  Returns the (B, n_frames, 64, 64) uint8 levels.  The kernel checks the descriptors it
+    reads and reports per clip; a non-zero status raises ValueError (reading it waits for the launch), unless
+    ``return_status`` asks for (levels, status) instead (the loader, which reads the status at the end of the epoch)
+    or ``check=False`` skips the read.  The host checks see ``shapes`` and ``offsets`` only: a ``descriptors`` tensor
+    that says something else is judged by the kernel alone, which keeps it memory-safe but reports through ``status``
+    -- so with ``descriptors`` given, read the status."""
+    import numpy as np
+    _require_gpu(pix, "pix")
+    if pix.dtype != torch.uint8 or pix.dim() != 1 or not pix.is_contiguous():
+        raise ValueError("pix must be a contiguous 1-D uint8 tensor")
+    if isinstance(n_frames, bool) or not isinstance(n_frames, (int, np.integer)) or n_frames < 1:
+        raise ValueError(f"n_frames must be an integer >= 1, got {n_frames!r}")
+    if antialias not in (False, True, 0, 1):
+        raise ValueError(f"antialias must be False or True, got {antialias!r}")
+    B, n = len(shapes), int(n_frames)
+    if B < 1 or any(len(s) != 3 for s in shapes):
+        raise ValueError("shapes must name a non-zero number of clips, one (H, W, channels) each")
+    if offsets is not None and len(offsets) != B:
+        raise ValueError("offsets must name the same number of clips as shapes")
+    desc = video_clip_descriptors(shapes, n, offsets)
+    rec = desc.view(_VIDEO_CLIP).reshape(B)
+    for b in range(B):
+        o, h, w, c = (int(rec[k][b]) for k in ("offset", "height", "width", "channels"))
+        if c not in (1, 3):
+            raise ValueError(f"clip {b}: {c} channels; frames are RGB (3) or gray (1)")
+        if not (1 <= h <= VIDEO_FRONTEND_MAX_DIM and 1 <= w <= VIDEO_FRONTEND_MAX_DIM):
+            raise ValueError(f"clip {b}: frames of {h} x {w} lie outside 1 .. {VIDEO_FRONTEND_MAX_DIM} per side")
+        if o < 0 or o + n * h * w * c > pix.numel():
+            raise ValueError(f"clip {b}: {n} frames of {h} x {w} x {c} at offset {o} do not lie inside the "
+                             f"upload of {pix.numel()} bytes")
+    dev = pix.device
+    S = VIDEO_FRONTEND_SIZE
+    with torch.cuda.device(dev):
+        if descriptors is None:
+            descriptors = torch.from_numpy(desc).to(dev)
+        if (tuple(descriptors.shape) != (B, 6) or descriptors.dtype != torch.int32 or not descriptors.is_contiguous()
+                or descriptors.device != dev):
+            raise ValueError(f"descriptors must be a contiguous ({B}, 6) int32 tensor on {dev}")
+        levels = out if out is not None else torch.empty(B, n, S, S, dtype=torch.uint8, device=dev)
+        if (tuple(levels.shape) != (B, n, S, S) or levels.dtype != torch.uint8 or not levels.is_contiguous()
+                or levels.device != dev):
+            raise ValueError(f"out must be a contiguous ({B}, {n}, {S}, {S}) uint8 tensor on {dev}")
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        N.check(N.lib().mvn_video_frontend(pix.data_ptr(), pix.numel(), descriptors.data_ptr(), B, n,
+                                           int(bool(antialias)), levels.data_ptr(), status.data_ptr(),
+                                           _stream_ptr(dev)), "mvn_video_frontend")
+    if return_status:
+        return levels, status
+    if check:
+        st = status.cpu().tolist()
+        if any(st):
+            why = {1: "its span does not lie inside the upload", 2: "channels is not 1 or 3",
+                   3: "height or width outside 1 .. 4096"}
+            b = next(i for i, s in enumerate(st) if s)
+            raise ValueError(f"mvn_video_frontend refused clip {b} on the device: {why.get(st[b], st[b])}")
+    return levels
+
+
 class _CrossEntropyOnProbs(torch.autograd.Function):
     """loss, accuracy of the trainer (row F3): mvn_ce_on_probs_forward / _backward."""
 

@@ -172,6 +172,9 @@ class Dance2Music(nn.Module):
             rank=self.rank, world_size=self.world_size, shuffle=train, pin_memory=c.pin_memory,
             num_workers=c.num_workers if train else c.val_num_workers, use_video=c.use_video,
             batch_subsample_frac=c.batch_subsample_frac if train else c.val_batch_subsample_frac,
+            # raw uint8 frames of a WAV folder: the GPU front end's resize rule (getattr: a config pickled before the
+            # field existed)
+            video_antialias=bool(getattr(c, "video_antialias", False)),
             # row F2: class indices cross PCIe (4 bytes per sample), the (B,Q,T) one-hot the Batch
             # contract asks for is formed on the device
             device=self.device if self.device.type == "cuda" else None)
