@@ -776,6 +776,100 @@ typedef struct {
 int mvn_video_frontend(const uint8_t *pix, long long pix_len, const mvn_video_clip *clips, int batch, int n_frames,
                        int antialias, uint8_t *levels, int32_t *status, void *stream);
 
+/* ---- The five building blocks as calls of their own (csrc/blocks.hip; additive, ABI version unchanged) ----
+ * movenet/modules.py's CausalConv1d, DilatedCausalConv1d, GatedResidualConv1d and DenseConv, forward and backward, on
+ * tensors the caller lays out (ResidualConvStack is the gated layer, called once per layer).  All data is fp32 on the
+ * device.  A tensor is (batch, channels, len) behind `p` with row stride `ld` floats and batch stride channels * ld:
+ * any ld >= len and any 4-byte alignment works (a PyTorch-contiguous (B, C, T) with odd T goes in as it is), and columns
+ * at or beyond len are neither read nor written.  Weights have PyTorch's layouts: (out, in, 2) for the two-tap convs,
+ * (out, in) for the 1x1 convs.
+ *
+ * Semantics (n = T - d is the gated / dilated layer's output length):
+ *   causal   y[:, :, t] = W[:, :, 0] x[:, :, t - 1] + W[:, :, 1] x[:, :, t] (+ bias), x[-1] = 0;   y.len == x.len
+ *   dilated  y[:, :, j] = W[:, :, 0] x[:, :, j] + W[:, :, 1] x[:, :, j + d] (+ bias);              y.len == x.len - d
+ *   gated    f | g = dilated convs (+ the context's 1x1 convs and their biases on the LAST n columns of the context);
+ *            z = tanh(f) sigmoid(g); residual = Wr z + br + x[:, :, d:]; skip = (Ws z + bs)[:, :, n - skip.len:]
+ *            th / sg (both or neither): tanh(f) and sigmoid(g), (B, C, n) with one row stride -- what the backward reads
+ *   dense    y = W2 leaky_relu(W1 leaky_relu(x) + b1) + b2; hidden: the first conv's output (NULL: kept in scratch)
+ *
+ * Gradients: data gradients (dx, dcontext) are written in full -- dcontext over all of the context's columns, zero in
+ * front of the ones the layer used -- and a NULL tensor skips that product.  Parameter gradients ACCUMULATE (the rule
+ * of mvn_param_grads); a NULL pointer means "not wanted".  d_residual or d_skip (not both) may be NULL: that output
+ * received no gradient.  Summation runs in a fixed order (per-workgroup slabs added up by one thread per word, no float
+ * atomics): two calls on the same data give the same bits.
+ *
+ * Every argument is checked before the first launch and a refused call has written nothing: NULL pointers, ld < len,
+ * lengths that do not fit each other, T <= d, a context shorter than n and a scratch below the sizing function's answer
+ * are MVN_ERR_BAD_ARG; channel counts beyond 256 (residual, skip, the head's input) / 1024 (the head's output, the
+ * causal conv) are MVN_ERR_BAD_DIMS; rows of 2^31 bytes or more are MVN_ERR_UNSUPPORTED.  The sizing functions are
+ * host arithmetic (0 for shapes the calls refuse, never 0 otherwise).
+ *
+ * mvn_block_last_form(): the kernel form of the most recent block call of this process (0 before any) -- FUSED64 after a
+ * gated forward at C = K = 64 (one kernel per layer, z never written to memory), GENERIC after every other call,
+ * the backward passes at C = K = 64 included (they are composed from the generic kernel family). */
+typedef struct mvn_block_tensor {
+  float *p;
+  int32_t ld;  /* row stride, floats */
+  int32_t len; /* columns */
+} mvn_block_tensor;
+
+typedef struct mvn_block_gated_params {
+  const float *filter_w, *filter_b; /* (C, C, 2); bias (C) or NULL */
+  const float *gate_w, *gate_b;
+  const float *ctx_filter_w, *ctx_filter_b; /* (C, C), (C): read only when a context is given */
+  const float *ctx_gate_w, *ctx_gate_b;
+  const float *residual_w, *residual_b; /* (C, C), (C) */
+  const float *skip_w, *skip_b;         /* (K, C), (K) */
+} mvn_block_gated_params;
+
+typedef struct mvn_block_gated_grads { /* accumulated into; NULL: not wanted */
+  float *filter_w, *filter_b;
+  float *gate_w, *gate_b;
+  float *ctx_filter_w, *ctx_filter_b;
+  float *ctx_gate_w, *ctx_gate_b;
+  float *residual_w, *residual_b;
+  float *skip_w, *skip_b;
+} mvn_block_gated_grads;
+
+#define MVN_BLOCK_FORM_GENERIC 1
+#define MVN_BLOCK_FORM_FUSED64 2
+int mvn_block_last_form(void);
+
+/* scratch of the causal / dilated backward (channels in, channels out, the OUTPUT length) */
+size_t mvn_block_conv_scratch_floats(int cin, int cout, int batch, int t_len);
+int mvn_block_causal_forward(const float *w, const float *bias, int cin, int cout, const mvn_block_tensor *x,
+                             const mvn_block_tensor *y, int batch, void *stream);
+int mvn_block_causal_backward(const float *w, int cin, int cout, const mvn_block_tensor *x, const mvn_block_tensor *dy,
+                              const mvn_block_tensor *dx, float *dw, float *dbias, int batch, float *scratch,
+                              size_t scratch_floats, void *stream);
+int mvn_block_dilated_forward(const float *w, const float *bias, int channels, int dilation, const mvn_block_tensor *x,
+                              const mvn_block_tensor *y, int batch, void *stream);
+int mvn_block_dilated_backward(const float *w, int channels, int dilation, const mvn_block_tensor *x,
+                               const mvn_block_tensor *dy, const mvn_block_tensor *dx, float *dw, float *dbias, int batch,
+                               float *scratch, size_t scratch_floats, void *stream);
+
+/* t_len: the layer's INPUT length T.  backward == 0: what the forward needs when th / sg are not given */
+size_t mvn_block_gated_scratch_floats(int residual_channels, int skip_channels, int batch, int t_len, int dilation,
+                                      int has_context, int backward);
+int mvn_block_gated_forward(const mvn_block_gated_params *p, int residual_channels, int skip_channels, int dilation,
+                            const mvn_block_tensor *x, const mvn_block_tensor *context, const mvn_block_tensor *residual,
+                            const mvn_block_tensor *skip, const mvn_block_tensor *th, const mvn_block_tensor *sg,
+                            int batch, float *scratch, size_t scratch_floats, void *stream);
+int mvn_block_gated_backward(const mvn_block_gated_params *p, const mvn_block_gated_grads *grads, int residual_channels,
+                             int skip_channels, int dilation, const mvn_block_tensor *x, const mvn_block_tensor *context,
+                             const mvn_block_tensor *th, const mvn_block_tensor *sg, const mvn_block_tensor *d_residual,
+                             const mvn_block_tensor *d_skip, const mvn_block_tensor *dx, const mvn_block_tensor *dcontext,
+                             int batch, float *scratch, size_t scratch_floats, void *stream);
+
+size_t mvn_block_dense_scratch_floats(int in_channels, int out_channels, int batch, int s_len, int backward);
+int mvn_block_dense_forward(const float *w1, const float *b1, const float *w2, const float *b2, int in_channels,
+                            int out_channels, const mvn_block_tensor *x, const mvn_block_tensor *hidden,
+                            const mvn_block_tensor *y, int batch, float *scratch, size_t scratch_floats, void *stream);
+int mvn_block_dense_backward(const float *w1, const float *w2, int in_channels, int out_channels,
+                             const mvn_block_tensor *x, const mvn_block_tensor *hidden, const mvn_block_tensor *dy,
+                             const mvn_block_tensor *dx, float *dw1, float *db1, float *dw2, float *db2, int batch,
+                             float *scratch, size_t scratch_floats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ MVN_ERR_UNSUPPORTED = -5
 GEN_AUTO, GEN_GENERIC, GEN_STREAM, GEN_PIPE, GEN_PIPE_F16, GEN_FOLD = 0, 1, 2, 3, 4, 5
 BWD_FORM_GENERIC, BWD_FORM_HALVES, BWD_FORM_ONE = 1, 2, 3  # mvn_last_backward_form (include/movenet_hip.h)
 BWD_FORM_BF16 = 4  # mvn_backward_bf16's layer kernel
+BLOCK_FORM_GENERIC, BLOCK_FORM_FUSED64 = 1, 2  # mvn_block_last_form: the kernel form of the last block call
 BWD_FORM_ONE_GLOBAL = 5  # mvn_backward_global: BWD_FORM_ONE with the label's row sums of df | dg
 BWD_FORM_BF16_GLOBAL = 6  # mvn_backward_bf16_global: BWD_FORM_BF16 with the row sums formed inside the layer kernel
 BWD_FORM_BF16_CTX = 7  # mvn_backward_bf16_ctx: BWD_FORM_BF16 writing df | dg for the fp32 context pass
@@ -97,6 +98,21 @@ class SeqSampling(C.Structure):
     """mvn_seq_sampling: the sampling settings of one sequence of a mvn_generate_seq launch (24 bytes)."""
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("row", C.c_uint32),
                 ("seed", C.c_uint64)]
+
+
+class BlockTensor(C.Structure):
+    """mvn_block_tensor: (batch, channels, len) behind ``p``, row stride ``ld`` floats, batch stride channels * ld."""
+    _fields_ = [("p", C.c_void_p), ("ld", C.c_int32), ("len", C.c_int32)]
+
+
+class BlockGatedParams(C.Structure):  # also used for mvn_block_gated_grads (same layout)
+    _fields_ = [(n, C.c_void_p) for n in (
+        "filter_w", "filter_b", "gate_w", "gate_b", "ctx_filter_w", "ctx_filter_b", "ctx_gate_w", "ctx_gate_b",
+        "residual_w", "residual_b", "skip_w", "skip_b")]
+
+
+_BT = C.POINTER(BlockTensor)
+_BG = C.POINTER(BlockGatedParams)
 
 
 class VideoParams(C.Structure):  # also used for mvn_video_grads (same layout)
@@ -237,6 +253,26 @@ SIGNATURES = {
     "mvn_video_frontend": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "mvn_publish_words": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_void_p]),
+    # the five building blocks (csrc/blocks.hip)
+    "mvn_block_last_form": (C.c_int, []),
+    "mvn_block_conv_scratch_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mvn_block_causal_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _BT, _BT, C.c_int, C.c_void_p]),
+    "mvn_block_causal_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _BT, _BT, _BT, C.c_void_p, C.c_void_p,
+                                            C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mvn_block_dilated_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _BT, _BT, C.c_int, C.c_void_p]),
+    "mvn_block_dilated_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _BT, _BT, _BT, C.c_void_p, C.c_void_p,
+                                             C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mvn_block_gated_scratch_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mvn_block_gated_forward": (C.c_int, [_BG, C.c_int, C.c_int, C.c_int, _BT, _BT, _BT, _BT, _BT, _BT, C.c_int,
+                                          C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mvn_block_gated_backward": (C.c_int, [_BG, _BG, C.c_int, C.c_int, C.c_int, _BT, _BT, _BT, _BT, _BT, _BT, _BT, _BT,
+                                           C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mvn_block_dense_scratch_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mvn_block_dense_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _BT, _BT,
+                                          _BT, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mvn_block_dense_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _BT, _BT, _BT, _BT, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                           C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

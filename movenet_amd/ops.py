@@ -857,3 +857,342 @@ def cross_entropy_on_probs(probs: torch.Tensor, target: torch.Tensor):
     ``F.cross_entropy(probs, target)`` -- a log-softmax applied to what already are
     probabilities -- and ``(probs.argmax(1) == target).float().mean()``."""
     return _CrossEntropyOnProbs.apply(probs, target)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# The five building blocks as autograd nodes of their own (csrc/blocks.hip, mvn_block_*): what movenet_amd.modules'
+# forward methods call.  fp32, (batch, channels, frames), contiguous; activations are saved only when a gradient is
+# needed, and gradients come back as ordinary tensors (the flat buffers of _run_backward are the whole model's).
+# ----------------------------------------------------------------------------------------------------------------
+def _f32c(t):
+    return None if t is None else t.detach().to(torch.float32).contiguous()
+
+
+def _bt(t):
+    """mvn_block_tensor of a contiguous (B, ch, len) tensor (or None)."""
+    return None if t is None else N.BlockTensor(t.data_ptr(), t.stride(1), t.shape[2])
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _scratch(n: int, dev):
+    n = int(n)
+    return torch.empty(max(n, 1), dtype=torch.float32, device=dev), n
+
+
+def _block_input(x, what: str, channels: int):
+    if x.dim() != 3 or x.shape[1] != channels:
+        raise ValueError(f"{what} must be (batch, {channels}, frames), got {tuple(x.shape)}")
+    if x.shape[0] < 1 or x.shape[2] < 1:
+        raise ValueError(f"{what} must not be empty, got {tuple(x.shape)}")
+
+
+class _Conv2TapFunction(torch.autograd.Function):
+    """CausalConv1d (dilation 0: taps t - 1 and t, same length) and DilatedCausalConv1d (taps j and j + d)."""
+
+    @staticmethod
+    def forward(ctx_, dilation, x, w, bias):
+        lib = N.lib()
+        x, w, bias = _f32c(x), _f32c(w), _f32c(bias)
+        B, cin, T = x.shape
+        cout = w.shape[0]
+        n = T - dilation
+        dev = x.device
+        with torch.cuda.device(dev):
+            y = torch.empty((B, cout, n), dtype=torch.float32, device=dev)
+            if dilation == 0:
+                N.check(lib.mvn_block_causal_forward(w.data_ptr(), _ptr(bias), cin, cout, _bt(x), _bt(y), B,
+                                                     _stream_ptr(dev)), "mvn_block_causal_forward")
+            else:
+                N.check(lib.mvn_block_dilated_forward(w.data_ptr(), _ptr(bias), cin, dilation, _bt(x), _bt(y), B,
+                                                      _stream_ptr(dev)), "mvn_block_dilated_forward")
+        ctx_.dilation, ctx_.has_bias = dilation, bias is not None
+        if any(ctx_.needs_input_grad):
+            ctx_.save_for_backward(x, w)
+        return y
+
+    @staticmethod
+    def backward(ctx_, dy):
+        lib = N.lib()
+        x, w = ctx_.saved_tensors
+        B, cin, T = x.shape
+        cout, d = w.shape[0], ctx_.dilation
+        dev = x.device
+        dy = _f32c(dy)
+        need_x, need_w, need_b = ctx_.needs_input_grad[1], ctx_.needs_input_grad[2], ctx_.needs_input_grad[3] and ctx_.has_bias
+        with torch.cuda.device(dev):
+            dx = torch.empty_like(x) if need_x else None
+            dw = torch.zeros_like(w) if need_w else None
+            db = torch.zeros(cout, dtype=torch.float32, device=dev) if need_b else None
+            scratch, ns = _scratch(lib.mvn_block_conv_scratch_floats(cin, cout, B, T - d), dev)
+            if d == 0:
+                N.check(lib.mvn_block_causal_backward(w.data_ptr(), cin, cout, _bt(x), _bt(dy), _bt(dx), _ptr(dw), _ptr(db),
+                                                      B, scratch.data_ptr(), ns, _stream_ptr(dev)),
+                        "mvn_block_causal_backward")
+            else:
+                N.check(lib.mvn_block_dilated_backward(w.data_ptr(), cin, d, _bt(x), _bt(dy), _bt(dx), _ptr(dw), _ptr(db),
+                                                       B, scratch.data_ptr(), ns, _stream_ptr(dev)),
+                        "mvn_block_dilated_backward")
+        return None, dx, dw, db
+
+
+# per-layer parameter order of the gated layer's nodes (biases of the dilated convs are None in the reference's layer)
+GATED_PARAMS = ("filter_w", "filter_b", "gate_w", "gate_b", "ctx_filter_w", "ctx_filter_b", "ctx_gate_w", "ctx_gate_b",
+                "residual_w", "residual_b", "skip_w", "skip_b")
+
+
+def _gated_struct(tensors):
+    return N.BlockGatedParams(*[_ptr(t) for t in tensors])
+
+
+def _gated_forward_call(lib, ps, C, K, d, x, context, residual, skip, th, sg):
+    dev = x.device
+    B, T = x.shape[0], x.shape[2]
+    ns = 0 if th is not None else int(lib.mvn_block_gated_scratch_floats(C, K, B, T, d, int(context is not None), 0))
+    scratch, ns = _scratch(ns, dev)
+    N.check(lib.mvn_block_gated_forward(_gated_struct(ps), C, K, d, _bt(x), _bt(context), _bt(residual), _bt(skip),
+                                        _bt(th), _bt(sg), B, scratch.data_ptr(), ns, _stream_ptr(dev)),
+            "mvn_block_gated_forward")
+
+
+def _gated_backward_call(lib, ps, grads, C, K, d, x, context, th, sg, d_res, d_skip, dx, dctx):
+    dev = x.device
+    B, T = x.shape[0], x.shape[2]
+    scratch, ns = _scratch(lib.mvn_block_gated_scratch_floats(C, K, B, T, d, int(context is not None), 1), dev)
+    N.check(lib.mvn_block_gated_backward(_gated_struct(ps), _gated_struct(grads), C, K, d, _bt(x), _bt(context), _bt(th),
+                                         _bt(sg), _bt(d_res), _bt(d_skip), _bt(dx), _bt(dctx), B, scratch.data_ptr(), ns,
+                                         _stream_ptr(dev)), "mvn_block_gated_backward")
+
+
+def _check_gated_shapes(x, context, C, d):
+    _block_input(x, "input", C)
+    T = x.shape[2]
+    if T <= d:
+        raise RuntimeError(f"dilated causal convolution: input length T = {T} does not exceed the dilation d = {d}")
+    if context is not None:
+        _block_input(context, "context", C)
+        if context.shape[0] != x.shape[0]:
+            raise ValueError(f"context batch {context.shape[0]} != input batch {x.shape[0]}")
+
+
+class _GatedLayerFunction(torch.autograd.Function):
+    """GatedResidualConv1d: (input, context) -> (residual (B,C,T-d), skip (B,K,s)); s columns, already resolved."""
+    N_FIXED = 4
+
+    @staticmethod
+    def forward(ctx_, dilation, s, x, context, *params):
+        lib = N.lib()
+        x, context = _f32c(x), _f32c(context)
+        ps = [_f32c(p) for p in params]
+        C, K = ps[8].shape[0], ps[10].shape[0]
+        B, _, T = x.shape
+        n = T - dilation
+        dev = x.device
+        save = any(ctx_.needs_input_grad)
+        ctx_.set_materialize_grads(False)  # an output nobody used arrives as None, not as a tensor of zeros
+        with torch.cuda.device(dev):
+            f32 = dict(dtype=torch.float32, device=dev)
+            res, skip = torch.empty((B, C, n), **f32), torch.empty((B, K, s), **f32)
+            th = torch.empty((B, C, n), **f32) if save else None
+            sg = torch.empty((B, C, n), **f32) if save else None
+            _gated_forward_call(lib, ps, C, K, dilation, x, context, res, skip, th, sg)
+        ctx_.dilation, ctx_.has_context, ctx_.present = dilation, context is not None, [p is not None for p in ps]
+        if save:
+            ctx_.save_for_backward(x, th, sg, *([context] if context is not None else []), *[p for p in ps if p is not None])
+        return res, skip
+
+    @staticmethod
+    def backward(ctx_, d_res, d_skip):
+        if d_res is None and d_skip is None:
+            return (None,) * (_GatedLayerFunction.N_FIXED + len(ctx_.present))
+        lib = N.lib()
+        x, th, sg, *rest = ctx_.saved_tensors
+        context = rest.pop(0) if ctx_.has_context else None
+        it = iter(rest)
+        ps = [next(it) if here else None for here in ctx_.present]
+        C, K, d = ps[8].shape[0], ps[10].shape[0], ctx_.dilation
+        dev = x.device
+        need = ctx_.needs_input_grad
+        with torch.cuda.device(dev):
+            d_res, d_skip = _f32c(d_res), _f32c(d_skip)
+            dx = torch.empty_like(x) if need[2] else None
+            dctx = torch.empty_like(context) if (context is not None and need[3]) else None
+            grads = []
+            for i, p in enumerate(ps):
+                ctx_only = 4 <= i < 8
+                want = p is not None and need[_GatedLayerFunction.N_FIXED + i] and (context is not None or not ctx_only)
+                want = want and not (i in (8, 9) and d_res is None) and not (i in (10, 11) and d_skip is None)
+                grads.append(torch.zeros_like(p) if want else None)
+            _gated_backward_call(lib, ps, grads, C, K, d, x, context, th, sg, d_res, d_skip, dx, dctx)
+        return (None, None, dx, dctx, *grads)
+
+
+class _ResidualStackFunction(torch.autograd.Function):
+    """ResidualConvStack: the layers in turn; layer l writes its skip into plane l of the (L, B, K, s) result."""
+    N_FIXED = 4
+
+    @staticmethod
+    def forward(ctx_, dilations, s, x, context, *params):
+        lib = N.lib()
+        x, context = _f32c(x), _f32c(context)
+        ps = [_f32c(p) for p in params]
+        L, P = len(dilations), len(GATED_PARAMS)
+        C, K = ps[8].shape[0], ps[10].shape[0]
+        B = x.shape[0]
+        dev = x.device
+        save = any(ctx_.needs_input_grad)
+        saved = []
+        with torch.cuda.device(dev):
+            f32 = dict(dtype=torch.float32, device=dev)
+            skips = torch.empty((L, B, K, s), **f32)
+            cur = x
+            for l, d in enumerate(dilations):
+                n = cur.shape[2] - d
+                res = torch.empty((B, C, n), **f32)
+                th = torch.empty((B, C, n), **f32) if save else None
+                sg = torch.empty((B, C, n), **f32) if save else None
+                _gated_forward_call(lib, ps[l * P:(l + 1) * P], C, K, d, cur, context, res, skips[l], th, sg)
+                if save:
+                    saved += [cur, th, sg]
+                cur = res
+        ctx_.dilations, ctx_.has_context, ctx_.present = dilations, context is not None, [p is not None for p in ps]
+        if save:
+            ctx_.save_for_backward(*saved, *([context] if context is not None else []), *[p for p in ps if p is not None])
+        return skips
+
+    @staticmethod
+    def backward(ctx_, d_skips):
+        lib = N.lib()
+        dil = ctx_.dilations
+        L, P = len(dil), len(GATED_PARAMS)
+        tensors = list(ctx_.saved_tensors)
+        acts, rest = tensors[:3 * L], tensors[3 * L:]
+        context = rest.pop(0) if ctx_.has_context else None
+        it = iter(rest)
+        ps = [next(it) if here else None for here in ctx_.present]
+        C, K = ps[8].shape[0], ps[10].shape[0]
+        need = ctx_.needs_input_grad
+        dev = acts[0].device
+        grads = [None] * len(ps)
+        with torch.cuda.device(dev):
+            d_skips = _f32c(d_skips)
+            want_ctx = context is not None and need[3]
+            dctx = torch.zeros_like(context) if want_ctx else None
+            dctx_l = torch.empty_like(context) if want_ctx else None
+            d_res = None  # the last layer's residual leaves the stack unused (movenet/modules.py:119-130)
+            for l in reversed(range(L)):
+                x, th, sg = acts[3 * l:3 * l + 3]
+                lp = ps[l * P:(l + 1) * P]
+                lg = []
+                for i, p in enumerate(lp):
+                    want = p is not None and need[_ResidualStackFunction.N_FIXED + l * P + i]
+                    want = want and (context is not None or not 4 <= i < 8) and not (i in (8, 9) and d_res is None)
+                    lg.append(torch.zeros_like(p) if want else None)
+                dx = torch.empty_like(x) if (l > 0 or need[2]) else None
+                _gated_backward_call(lib, lp, lg, C, K, dil[l], x, context, th, sg, d_res, d_skips[l], dx, dctx_l)
+                if want_ctx:
+                    dctx += dctx_l
+                grads[l * P:(l + 1) * P] = lg
+                d_res = dx
+        return (None, None, d_res if need[2] else None, dctx, *grads)
+
+
+class _DenseConvFunction(torch.autograd.Function):
+    """DenseConv: conv2(leaky_relu(conv1(leaky_relu(x)))); the hidden layer is saved only when a gradient is needed."""
+
+    @staticmethod
+    def forward(ctx_, x, w1, b1, w2, b2):
+        lib = N.lib()
+        x, w1, b1, w2, b2 = (_f32c(t) for t in (x, w1, b1, w2, b2))
+        B, K, S = x.shape
+        Q = w1.shape[0]
+        dev = x.device
+        save = any(ctx_.needs_input_grad)
+        with torch.cuda.device(dev):
+            f32 = dict(dtype=torch.float32, device=dev)
+            y = torch.empty((B, Q, S), **f32)
+            h = torch.empty((B, Q, S), **f32) if save else None
+            scratch, ns = _scratch(0 if save else lib.mvn_block_dense_scratch_floats(K, Q, B, S, 0), dev)
+            N.check(lib.mvn_block_dense_forward(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), K, Q, _bt(x),
+                                                _bt(h), _bt(y), B, scratch.data_ptr(), ns, _stream_ptr(dev)),
+                    "mvn_block_dense_forward")
+        if save:
+            ctx_.save_for_backward(x, h, w1, w2)
+        return y
+
+    @staticmethod
+    def backward(ctx_, dy):
+        lib = N.lib()
+        x, h, w1, w2 = ctx_.saved_tensors
+        B, K, S = x.shape
+        Q = w1.shape[0]
+        dev = x.device
+        need = ctx_.needs_input_grad
+        with torch.cuda.device(dev):
+            dy = _f32c(dy)
+            dx = torch.empty_like(x) if need[0] else None
+            dw1 = torch.zeros_like(w1) if need[1] else None
+            db1 = torch.zeros(Q, dtype=torch.float32, device=dev) if need[2] else None
+            dw2 = torch.zeros_like(w2) if need[3] else None
+            db2 = torch.zeros(Q, dtype=torch.float32, device=dev) if need[4] else None
+            scratch, ns = _scratch(lib.mvn_block_dense_scratch_floats(K, Q, B, S, 1), dev)
+            N.check(lib.mvn_block_dense_backward(w1.data_ptr(), w2.data_ptr(), K, Q, _bt(x), _bt(h), _bt(dy), _bt(dx),
+                                                 _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), B, scratch.data_ptr(), ns,
+                                                 _stream_ptr(dev)), "mvn_block_dense_backward")
+        return dx, dw1, db1, dw2, db2
+
+
+def block_causal_conv(x, weight, bias=None):
+    _block_input(x, "input", weight.shape[1])
+    return _Conv2TapFunction.apply(0, x, weight, bias)
+
+
+def block_dilated_conv(x, weight, bias, dilation: int):
+    _block_input(x, "input", weight.shape[1])
+    if x.shape[2] <= dilation:
+        raise RuntimeError(f"dilated causal convolution: input length T = {x.shape[2]} does not exceed the dilation "
+                           f"d = {dilation}")
+    return _Conv2TapFunction.apply(int(dilation), x, weight, bias)
+
+
+def _resolved_context(context, n: int):
+    if context is not None and context.shape[2] < n:
+        raise ValueError(f"context has {context.shape[2]} columns, the layer's output has T - d = {n}")
+    return context
+
+
+def block_gated_layer(x, context, skip_size: int, dilation: int, params):
+    """``params``: the twelve tensors of GATED_PARAMS (None where the layer has no such bias)."""
+    C = params[8].shape[0]
+    _check_gated_shapes(x, context, C, dilation)
+    skip_size = int(skip_size)
+    if skip_size < 0:
+        raise ValueError(f"skip_size must not be negative, got {skip_size}")
+    n = x.shape[2] - dilation
+    _resolved_context(context, n)
+    s = n if (skip_size == 0 or skip_size > n) else skip_size  # skip[:, :, -skip_size:]
+    return _GatedLayerFunction.apply(int(dilation), s, x, context, *params)
+
+
+def block_residual_stack(x, context, skip_size: int, dilations, layer_params):
+    """``layer_params``: one GATED_PARAMS list per layer.  Returns the (L, B, K, skip_size) stack of skips."""
+    C = layer_params[0][8].shape[0]
+    _block_input(x, "input", C)
+    skip_size = int(skip_size)
+    out_len = x.shape[2] - sum(dilations)
+    if not 1 <= skip_size <= out_len:
+        raise ValueError(f"skip_size must lie in [1, T - sum(dilations)] = [1, {out_len}], got {skip_size}")
+    if context is not None:
+        _block_input(context, "context", C)
+        if context.shape[0] != x.shape[0] or context.shape[2] != x.shape[2]:
+            raise ValueError(f"context must be aligned with the input, (batch, {C}, {x.shape[2]}); got "
+                             f"{tuple(context.shape)}")
+    flat = [p for lp in layer_params for p in lp]
+    return _ResidualStackFunction.apply(tuple(int(d) for d in dilations), skip_size, x, context, *flat)
+
+
+def block_dense_conv(x, w1, b1, w2, b2):
+    _block_input(x, "input", w1.shape[1])
+    return _DenseConvFunction.apply(x, w1, b1, w2, b2)
