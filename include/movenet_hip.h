@@ -698,6 +698,30 @@ int mvn_softmax_ce_backward_ex(const float *probs, const long long *target, int 
                                long long dlogit_batch_stride, int dlogit_ld, int dlogit_col0,
                                int dlogit_cols, int loss_rule, void *stream);
 
+/* Scoring GIVEN audio under the model: per-position log-likelihood of the target from the head's logits, read
+ * only -- no probability tensor is formed and `logits` comes back bit for bit.  With y = logits / temperature:
+ *     logp[b,s]      = y_t - logsumexp_q(y[b,:,s])                       (nats)
+ *     entropy[b,s]   = -sum_q p_q log p_q of softmax(y); a class with p_q = 0 (a -inf logit included) adds exactly 0
+ *     rank[b,s]      = #{q : y_q > y_t} + #{q < t : y_q == y_t}, compared on the logits themselves (temperature > 0
+ *                      keeps their order): 0 exactly where the first-maximum accuracy rule of the loss calls above
+ *                      counts the column as correct
+ *     seq_nll[b]     = -sum_s logp[b,s]
+ *     seq_correct[b] = #{s : rank[b,s] == 0}
+ *   logits   (B, Q, S) fp32 as mvn_forward leaves them, rows at any 4-byte alignment
+ *   target   (B, S) int64, clamped to [0, Q-1] as the loss calls clamp it
+ *   logp, entropy, rank  (B, S) each; seq_nll, seq_correct  (B,) each; any of the five NULL: not formed, not written
+ *   scratch  mvn_score_scratch_floats(B, S) floats, NOT initialised by the caller: the first kernel writes every
+ *            per-workgroup partial sum the second one reads, and that one adds a sequence's partials in a fixed
+ *            order in double (no atomics: two calls on the same input return the same bits)
+ * temperature must be finite and above 0; that, or a scratch that is too small, is MVN_ERR_BAD_ARG before any
+ * launch and before any buffer is touched.  Q <= 256 with a sequence's (Q, S) tensor inside 2^31 bytes runs the
+ * column form of the loss calls (32-bit buffer offsets), anything else one thread per column with 64-bit
+ * addresses.  A column that is entirely -inf is undefined.  S == 0 stores zeros in seq_nll / seq_correct. */
+size_t mvn_score_scratch_floats(int batch, int s_len);
+int mvn_score_columns(const float *logits, const long long *target, int batch, int classes, int s_len,
+                      float temperature, float *logp, float *entropy, int32_t *rank, float *seq_nll,
+                      int32_t *seq_correct, float *scratch, size_t scratch_floats, void *stream);
+
 /* One optimizer step of torch.optim.AdamW (decoupled != 0) or torch.optim.Adam (decoupled == 0,
  * weight decay added to the gradient) over flat fp32 buffers of n elements
  * (movenet/pytorch_lightning_trainer.py:186-189; arithmetic of torch's _single_tensor_adam,

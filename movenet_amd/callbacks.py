@@ -16,6 +16,11 @@ per temperature of the sweep -- by the module, in ONE ``generate()`` call that c
 a temperature per sequence -- so ``outputs["generated_output"]`` holds len(sweep) rows per clip, clip-major.  They are
 written as ``...-gen-T<value>.wav``, one index row per (clip, temperature) with a ``temperature`` field.
 
+With ``--score_samples 1`` the module also scores each logged batch (``Dance2Music.score_samples``: one
+``WaveNet.score`` call) and every row of a clip carries ``bits_per_sample`` -- of the generated clip under the
+conditioning it was generated with -- and ``source_bits_per_sample`` -- of the clip it was prompted from.  Off (the
+default), no row carries either key.
+
 With ``--ema_decay`` the module generates ``outputs["generated_output"]`` on the averaged weights
 (``Dance2Music.averaged_weights``), on the train hook and on the validation hook, and the validation hook's
 ``outputs["output"]`` comes from them too (the whole validation loop runs on them); the train hook's
@@ -112,6 +117,14 @@ class LogSamplesCallback:
                 write_wav(files["gen_audio"], gen[i])
             rows.append({"split": split, "epoch": trainer.current_epoch, "batch_idx": batch_idx, "fp": fp,
                          **{k: str(v.relative_to(root)) for k, v in files.items()}})
+        scores = outputs.get("sample_scores", None) if gen is not None else None
+        if scores is not None:  # (--score_samples 1; rows are clip-major, len(sweep) or one per clip, as gen is)
+            bits = scores["bits_per_sample"].cpu().tolist()
+            source = scores["source_bits_per_sample"].cpu().tolist()
+            per_clip = max(len(sweep), 1)
+            for k, r in enumerate(rows):
+                r["bits_per_sample"] = bits[k]
+                r["source_bits_per_sample"] = source[k // per_clip]
         if gen is not None and self.guidance != 1.0:  # (as a sweep's rows carry their temperature)
             for r in rows:
                 r["guidance"] = self.guidance

@@ -93,6 +93,12 @@ class TrainingConfig:
     ema_decay: float = 0.0
     ema_warmup: bool = True
 
+    # sample logger: also score each logged batch (WaveNet.score, one call per batch) and write bits_per_sample -- of
+    # the generated clip under the conditioning it was generated with -- and source_bits_per_sample -- of the clip it
+    # was prompted from -- into the clip's index.jsonl rows.  Not a reference field: a JSON written without it loads
+    # with the default (off: no row changes).
+    score_samples: bool = False
+
     scheduler: Optional[str] = "OneCycleLR"
     lr_pct_start: float = 0.45
     base_learning_rate: float = 0.0003
@@ -178,6 +184,7 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--loss_rule", type=str, default="reference", choices=["reference", "model"])
     a("--ema_decay", type=float, default=0.0)
     a("--ema_warmup", type=_flag, default=True)
+    a("--score_samples", type=_flag, default=False)
     a("--n_epochs", type=int, default=10)
     a("--n_steps_per_epoch", type=int, default=None)
     a("--use_video", type=_flag, default=True)
@@ -225,7 +232,7 @@ def config_from_args(args) -> TrainingConfig:
         "lr_pct_start base_learning_rate scheduler_step_size_up scheduler_step_size_down "
         "scheduler_cyclic_mode scheduler_cyclic_gamma scheduler_cycle_momentum max_learning_rate "
         "scheduler_step_size scheduler_step_gamma scheduler_milestones weight_decay "
-        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule ema_decay ema_warmup accumulation_steps num_workers val_num_workers "
+        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule ema_decay ema_warmup score_samples accumulation_steps num_workers val_num_workers "
         "pin_memory n_epochs n_steps_per_epoch use_video use_global bf16_video generate_guidance global_dropout video_antialias batch_subsample_frac "
         "val_batch_subsample_frac dist_backend dist_port model_output_path log_samples_every"
     ).split()

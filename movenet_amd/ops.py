@@ -629,6 +629,86 @@ def wavenet_forward_loss(model, audio: torch.Tensor, context=None, target=None, 
     return res
 
 
+def score_temperature(temperature) -> float:
+    """``temperature`` of the scoring calls as a float; ValueError unless it is a finite number above 0."""
+    if (isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not temperature > 0
+            or temperature == float("inf")):
+        raise ValueError(f"temperature must be a finite number above 0, got {temperature!r}")
+    return float(temperature)
+
+
+def score_logits(logits: torch.Tensor, target: torch.Tensor, temperature: float = 1.0, entropy: bool = False,
+                 rank: bool = False) -> dict:
+    """Per-position log-likelihood of ``target`` under ``softmax(logits / temperature)`` in one read-only pass over
+    the logits (mvn_score_columns): no probability tensor, ``logits`` untouched.  ``logits`` (B, Q, S) float32 on the
+    GPU, ``target`` (B, S) integer classes (clamped to [0, Q-1]).  Returns a dict: ``logp`` (B, S) in nats,
+    ``seq_nll`` (B,) = -logp.sum(1), ``seq_correct`` (B,) int32 = the columns whose target is the first maximum, and
+    on request ``entropy`` (B, S) of the distribution and ``rank`` (B, S) int32 of the target in it (0: the first
+    maximum).  The sums are formed in a fixed order: the same bits on every call.  ValueError / RuntimeError before
+    any launch for a bad temperature, a shape mismatch or a CPU tensor."""
+    temperature = score_temperature(temperature)
+    _require_gpu(logits, "logits")
+    if logits.dim() != 3 or logits.dtype != torch.float32:
+        raise ValueError(f"logits must be a (batch, classes, positions) float32 tensor, got {tuple(logits.shape)} "
+                         f"{logits.dtype}")
+    B, Q, S = logits.shape
+    if tuple(target.shape) != (B, S) or target.is_floating_point() or target.dtype == torch.bool:
+        raise ValueError(f"target must be ({B}, {S}) integer classes, got {tuple(target.shape)} {target.dtype}")
+    _require_gpu(target, "target")
+    if Q < 1:
+        raise ValueError("logits hold no classes")
+    dev = logits.device
+    x = logits.detach().contiguous()
+    tg = target.detach().to(device=dev, dtype=torch.int64).contiguous()
+    lib = N.lib()
+    with torch.cuda.device(dev):
+        out = {"logp": torch.empty(B, S, dtype=torch.float32, device=dev),
+               "seq_nll": torch.empty(B, dtype=torch.float32, device=dev),
+               "seq_correct": torch.empty(B, dtype=torch.int32, device=dev)}
+        if entropy:
+            out["entropy"] = torch.empty(B, S, dtype=torch.float32, device=dev)
+        if rank:
+            out["rank"] = torch.empty(B, S, dtype=torch.int32, device=dev)
+        n = lib.mvn_score_scratch_floats(B, S)
+        scratch = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+        N.check(lib.mvn_score_columns(x.data_ptr(), tg.data_ptr(), B, Q, S, temperature, out["logp"].data_ptr(),
+                                      out["entropy"].data_ptr() if entropy else None,
+                                      out["rank"].data_ptr() if rank else None, out["seq_nll"].data_ptr(),
+                                      out["seq_correct"].data_ptr(), scratch.data_ptr(), n, _stream_ptr(dev)),
+                "mvn_score_columns")
+    return out
+
+
+def wavenet_score(model, audio: torch.Tensor, context=None, gvec=None, temperature: float = 1.0,
+                  entropy: bool = False, rank: bool = False) -> dict:
+    """``score_logits`` of the model's own logits for ``audio`` against ``audio[:, :, RF:]`` (WaveNet.score): the
+    forward's checks and kernels -- whatever ``forward_precision`` and ``global_path`` say -- with nothing saved and
+    nothing normalised, then mvn_score_columns on what the head wrote."""
+    temperature = score_temperature(temperature)
+    bf16 = bf16_mode(model, context is not None, gvec is not None)
+    model.compute_output_size(audio)  # ValueError when T < RF
+    idx, check = model._indices_async(audio)
+    out = score_indices(model, idx, context, gvec, temperature, entropy, rank, bf16=bf16)
+    if not model._all_one_hot(check):  # (read after the enqueue, as forward reads it)
+        raise ValueError("WaveNet.score expects one-hot audio (the target is its class index): a column of the input "
+                         "is not one-hot")
+    return out
+
+
+def score_indices(model, idx: torch.Tensor, context, gvec, temperature: float, entropy: bool, rank: bool,
+                  bf16: bool) -> dict:
+    """The scoring pass on class indices ``idx`` (B, T) int32 (what WaveNet.score and WaveNet.classify share)."""
+    B, T = idx.shape
+    context, gvec = _global_plan(model, context, gvec, B, T)
+    names, params = _decoder_params(model, context is not None or gvec is not None)
+    sd = {n: p.detach() for n, p in zip(names, params)}
+    if gvec is not None:
+        gvec = gvec.detach().to(torch.float32).contiguous()
+    logits, _ = run_forward(model._dims, sd, idx, False, True, False, context,
+                            f16=model.forward_precision == "fp16", bf16=bf16, gvec=gvec)
+    return score_logits(logits, idx[:, model.receptive_fields:], temperature, entropy=entropy, rank=rank)
+
+
 def mu_law_encode(x: torch.Tensor, quantization_channels: int) -> torch.Tensor:
     """float waveform in [-1, 1] (any shape, on the GPU) -> int32 class indices."""
     _require_gpu(x, "waveform")

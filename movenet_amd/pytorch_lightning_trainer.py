@@ -106,12 +106,34 @@ class Dance2Music(nn.Module):
         return (self.config.log_samples_every is not None
                 and (self.current_epoch + 1) % self.config.log_samples_every == 0)
 
-    def _generate_averaged(self, audio, video, labels):
-        """``generate`` for the sample logger: on the averaged weights when there are any.  (The views are swapped
-        only on a step that generates; the step's autograd graph holds the parameters themselves, which point into
-        the raw buffer again before ``backward`` runs.)"""
+    def _sample_outputs(self, audio, video, labels) -> dict:
+        """A step's ``generated_output`` for the sample logger -- ``generate`` on the averaged weights when there are
+        any -- and, with ``--score_samples 1`` on a step that generates, the clips' scores under ``"sample_scores"`` (a
+        key that is absent otherwise).  (The views are swapped only on a step that generates; the step's autograd graph
+        holds the parameters themselves, which point into the raw buffer again before ``backward`` runs.)"""
         with (self.averaged_weights() if self._generates_now() else contextlib.nullcontext()):
-            return self.generate(audio, video, labels)  # (which keeps the epoch gate: None on the other epochs)
+            gen = self.generate(audio, video, labels)  # (which keeps the epoch gate: None on the other epochs)
+            out = {"generated_output": gen}
+            if gen is not None and getattr(self.config, "score_samples", False):
+                out["sample_scores"] = self.score_samples(gen, audio, video, labels)
+        return out
+
+    def score_samples(self, generated, audio, video, labels=None) -> dict:
+        """bits per sample of the generated clips and of the clips they were prompted from, each under the clip's own
+        conditioning (video, label; temperature 1, no guidance: the model's own distribution), from ONE
+        ``WaveNet.score`` call: the generated rows (len(sweep) per clip, clip-major, under a temperature sweep), then
+        the sources.  A generated length other than the source's is scored over the common leading part."""
+        n = generated.shape[0] // audio.shape[0]
+        frames = min(int(generated.shape[2]), int(audio.shape[2]))
+        if video is not None and frames != int(audio.shape[2]):
+            raise ValueError("--score_samples with a video context needs generate_n_samples to be the clips' length")
+
+        def both(per_clip):
+            return None if per_clip is None else torch.cat([per_clip.repeat_interleave(n, dim=0), per_clip])
+        res = self.model.score(torch.cat([generated[:, :, :frames], audio[:, :, :frames].to(generated.dtype)]),
+                               both(video), both(labels))
+        bits = res.bits_per_sample.detach()
+        return {"bits_per_sample": bits[:generated.shape[0]], "source_bits_per_sample": bits[generated.shape[0]:]}
 
     def generate(self, audio, video, labels=None):
         if self._generates_now():
@@ -157,12 +179,11 @@ class Dance2Music(nn.Module):
             # rest of the epoch would run without label dropout, which forward applies in train mode only)
             self.model.train()
         loss, output, audio, video, labels = self._shared_step(batch, "train")
-        return {"loss": loss, "output": output.detach(),
-                "generated_output": self._generate_averaged(audio, video, labels)}
+        return {"loss": loss, "output": output.detach(), **self._sample_outputs(audio, video, labels)}
 
     def validation_step(self, batch, batch_idx):
         _, output, audio, video, labels = self._shared_step(batch, "val")
-        return {"output": output.detach(), "generated_output": self._generate_averaged(audio, video, labels)}
+        return {"output": output.detach(), **self._sample_outputs(audio, video, labels)}
 
     def _loader(self, train: bool):
         c = self.config

@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import math
 import sys
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -42,6 +42,16 @@ def upsample_kernel_size_solver(in_size, out_size, stride=1, padding=0, output_p
     (the ConvTranspose1d length formula); same contract as movenet/wavenet.py:34-47."""
     span = out_size - 1 - output_padding - (in_size - 1) * stride + 2 * padding
     return (int(span / dilation + 1),)
+
+
+class ScoreResult(NamedTuple):
+    """What ``WaveNet.score`` returns (S = T - RF scored positions per sequence)."""
+    logp: torch.Tensor             # (B, S) log p(x_t | x_<t, conditioning), nats
+    nll: torch.Tensor              # (B,)   -logp.sum(1)
+    bits_per_sample: torch.Tensor  # (B,)   nll / (S ln 2)
+    accuracy: torch.Tensor         # (B,)   share of positions whose sample is the first maximum
+    entropy: Optional[torch.Tensor] = None  # (B, S) entropy of each predictive distribution, nats (on request)
+    rank: Optional[torch.Tensor] = None     # (B, S) int32 rank of the sample in it, 0 = likeliest (on request)
 
 
 class WaveNet(nn.Module):
@@ -351,6 +361,84 @@ class WaveNet(nn.Module):
             return wavenet_forward_loss(self, audio, context, target, gvec=gvec)
         return wavenet_forward(self, audio, context, output_unnormalized=output_unnormalized,
                                remove_last=remove_last, gvec=gvec)
+
+    # ---- likelihood of GIVEN audio ---------------------------
+    def _score_checks(self, audio, video, global_features):
+        """The forward's own refusals, before anything is launched; returns (gvec, bf16)."""
+        from .ops import bf16_mode, global_vector
+        gvec = global_vector(self, global_features, int(audio.shape[0]))
+        bf16 = bf16_mode(self, video is not None, gvec is not None)
+        if gvec is not None and video is not None and self.global_path == "bias":
+            raise ValueError("global_path 'bias' runs models without a video context")
+        self.compute_output_size(audio)
+        return gvec, bf16
+
+    @staticmethod
+    def _score_result(raw: dict, positions: int) -> "ScoreResult":
+        nll = raw["seq_nll"]
+        return ScoreResult(logp=raw["logp"], nll=nll, bits_per_sample=nll / (max(positions, 1) * math.log(2.0)),
+                           accuracy=raw["seq_correct"].to(torch.float32) / max(positions, 1),
+                           entropy=raw.get("entropy"), rank=raw.get("rank"))
+
+    @torch.no_grad()
+    def score(self, audio, video=None, global_features=None, temperature: float = 1.0, entropy: bool = False,
+              rank: bool = False) -> "ScoreResult":
+        """How likely ``audio`` is under the model: log p(x_t | x_<t, conditioning) of every sample past the
+        receptive field, per position and per sequence, from the logits of one forward pass (same checks, same
+        kernels, ``forward_precision`` and ``global_path`` as ``forward``; nothing saved, no probability tensor).
+
+        Returns a ``ScoreResult``: ``logp`` (B, T - RF) in nats under softmax(logits / ``temperature``), ``nll`` (B,)
+        its negative sum, ``bits_per_sample`` (B,) = nll / ((T - RF) ln 2), ``accuracy`` (B,) the share of positions
+        whose sample is the first maximum, and on request ``entropy`` (B, T - RF) of each predictive distribution
+        and ``rank`` (B, T - RF) int32 of the sample in it (else None).  ``nll.mean() / (T - RF)`` is the loss
+        ``loss_rule = "model"`` reports for the same input.  Label dropout is never applied, the module's training
+        flag is left as it is, and ``audio`` must be one-hot (ValueError): its class indices are the targets."""
+        from .ops import score_temperature, wavenet_score
+        temperature = score_temperature(temperature)  # (ValueError before the video encoder runs)
+        gvec, _ = self._score_checks(audio, video, global_features)
+        context = None if video is None else self.upsample_video(video)
+        raw = wavenet_score(self, audio, context, gvec, temperature, entropy=entropy, rank=rank)
+        return self._score_result(raw, int(audio.shape[2]) - self.receptive_fields)
+
+    @torch.no_grad()
+    def classify(self, audio, video=None, log_prior=None, logits_budget_bytes: int = 1 << 30):
+        """Which class label explains ``audio`` best (a model built with ``global_classes = G > 0``; ValueError
+        otherwise): returns ``(loglik, posterior)``, both (B, G) -- ``loglik[b, c]`` = log p(x_b | class c), the
+        ``-nll`` of ``score`` with ``global_features = c``, and ``posterior`` = softmax(loglik + ``log_prior``)
+        over the classes (``log_prior``: (G,) or (B, G); default uniform).
+
+        The (class, sequence) pairs run through the scoring pass of ``score`` in chunks of as many pairs as keep a
+        chunk's logits within ``logits_budget_bytes`` (default 1 GiB; at least one pair), the audio's indices and
+        the up-sampled video formed once; each chunk takes the label path ``score`` would take for its batch."""
+        from .ops import score_indices
+        G = int(self.global_classes)
+        if G <= 0:
+            raise ValueError("classify needs a model built with global_classes (there are no labels to tell apart)")
+        if isinstance(logits_budget_bytes, bool) or not isinstance(logits_budget_bytes, int) or logits_budget_bytes < 1:
+            raise ValueError(f"logits_budget_bytes must be a positive integer, got {logits_budget_bytes!r}")
+        B = int(audio.shape[0])
+        if log_prior is not None:
+            log_prior = torch.as_tensor(log_prior)
+            if tuple(log_prior.shape) not in ((G,), (B, G)):
+                raise ValueError(f"log_prior must be ({G},) or ({B}, {G}), got {tuple(log_prior.shape)}")
+        _, bf16 = self._score_checks(audio, video, torch.zeros(B, dtype=torch.int64))
+        context = None if video is None else self.upsample_video(video)
+        idx = self._indices_of(audio)  # ValueError unless one-hot
+        positions = int(audio.shape[2]) - self.receptive_fields
+        per_pair = 4 * self.input_channels * max(positions, 1)
+        step = max(1, logits_budget_bytes // per_pair)
+        pairs = torch.arange(G * B, device=idx.device)  # class-major: pair = c B + b
+        E = self.global_embedding.weight.detach()
+        nll = []
+        for p0 in range(0, G * B, step):
+            rows = pairs[p0:p0 + step]
+            seq, cls = rows % B, rows // B
+            raw = score_indices(self, idx[seq], None if context is None else context[seq], E[cls], 1.0, False, False,
+                                bf16=bf16)
+            nll.append(raw["seq_nll"])
+        loglik = -torch.cat(nll).view(G, B).t().contiguous()
+        post = loglik.double() if log_prior is None else loglik.double() + log_prior.to(loglik.device).double()
+        return loglik, torch.softmax(post, dim=1).to(torch.float32)
 
     @torch.no_grad()
     def generate(self, audio, video=None, global_features=None, n_samples: Optional[int] = None,
