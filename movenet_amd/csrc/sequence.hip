@@ -1005,24 +1005,6 @@ struct SideStream {
   hipStream_t s = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
-// The dims the bf16 entry points run (fused_bf16.h): audio-only C = K = 64 layers, rows within the layer kernels'
-// buffer resources.  Anything else is refused -- never computed in fp32 instead.
-static int bf16_supported(const char *what, const Geometry &g, bool has_ctx) {
-  if (g.C != 64 || g.Kc != 64) {
-    set_error("%s: bf16 needs residual_channels = skip_channels = 64 (got %d, %d)", what, g.C, g.Kc);
-    return MVN_ERR_UNSUPPORTED;
-  }
-  if (has_ctx) {
-    set_error("%s: bf16 runs audio-only layers (no context)", what);
-    return MVN_ERR_UNSUPPORTED;
-  }
-  if (g.Tp > (1 << 21) || g.Sp > (1 << 21)) {
-    set_error("%s: bf16 needs t_len <= %d", what, 1 << 21);
-    return MVN_ERR_UNSUPPORTED;
-  }
-  return MVN_OK;
-}
-
 static int side_stream(SideStream **out) {
   static SideStream table[64];
   static std::mutex mu;
@@ -1128,24 +1110,75 @@ static void global_cond_tables(const mvn_params *p, int l0, int n, GlobalCondArg
   }
 }
 
+// What one full-sequence pass runs: every extern "C" entry point below fills one in and hands it to forward_impl /
+// backward_impl.  These are the legal combinations; nothing else is computed.
+//   F32  + PLAIN   mvn_forward, mvn_backward, mvn_backward_scratch (scratch given)
+//   F16  + PLAIN   mvn_forward_f16
+//   F32  + GLOBAL  mvn_forward_global (gbias), mvn_backward_global (scratch, rowsum)
+//   BF16 + PLAIN   mvn_forward_bf16, mvn_backward_bf16
+//   BF16 + GLOBAL  mvn_forward_bf16_global (gbias), mvn_backward_bf16_global (scratch, rowsum)
+//   BF16 + CTX16   mvn_forward_bf16_ctx, mvn_backward_bf16_ctx (scratch)
+struct SeqMode {
+  enum Precision { F32, F16, BF16 } precision;
+  // PLAIN: audio only, or the context the buffers carry through the fp32 conditioned layers; GLOBAL: one 2C-vector per
+  // (layer, sequence) in place of a context; CTX16: the buffers' context as a third K block of the bf16 layer kernel
+  enum Conditioning { PLAIN, GLOBAL, CTX16 } conditioning;
+  const char *who;             // the entry point's name, for its refusals
+  float *scratch; size_t scratch_floats;  // backward: the caller's scratch (mvn_*_scratch_floats), or nullptr
+  float *rowsum;               // backward, GLOBAL: the (L, B, 2C) row sums of df | dg
+  const float *gbias;          // forward, GLOBAL: the (L, B, 2C) vectors of mvn_global_bias
+};
+
+// Whether mode `m` runs geometry `g` -- the refusals that need no buffer, in the order include/movenet_hip.h documents:
+// the dims, a context the mode does not take, the row lengths, ctx_ld, a batch / length the bf16 layer kernels cannot
+// place (all MVN_ERR_UNSUPPORTED).  Only bf16 has any: anything it does not run is refused, never computed in fp32.
+static int mode_supported(const SeqMode &m, const Geometry &g, int batch, const mvn_fwd_buffers *buf) {
+  if (m.precision != SeqMode::BF16) return MVN_OK;
+  const bool ctx16 = m.conditioning == SeqMode::CTX16;
+  if (g.C != 64 || g.Kc != 64) {
+    set_error("%s: bf16 needs residual_channels = skip_channels = 64 (got %d, %d)", m.who, g.C, g.Kc);
+    return MVN_ERR_UNSUPPORTED;
+  }
+  if (!ctx16 && buf && buf->ctx) {
+    set_error("%s: bf16 runs audio-only layers (no context)", m.who);
+    return MVN_ERR_UNSUPPORTED;
+  }
+  if (g.Tp > (1 << 21) || g.Sp > (1 << 21)) {
+    set_error("%s: bf16 needs t_len <= %d", m.who, 1 << 21);
+    return MVN_ERR_UNSUPPORTED;
+  }
+  if (ctx16 && buf && buf->ctx_ld > (1 << 21)) {
+    set_error("%s: bf16 needs ctx_ld <= %d", m.who, 1 << 21);
+    return MVN_ERR_UNSUPPORTED;
+  }
+  if (m.conditioning != SeqMode::PLAIN && batch >= 1 && !global_bf16_path(g, batch)) {
+    set_error("%s: the bf16 layer kernels cannot place batch %d, t_len %d (%s)", m.who, batch, g.T,
+              ctx16 ? "mvn_bf16_ctx_path" : "mvn_global_bf16_path");
+    return MVN_ERR_UNSUPPORTED;
+  }
+  return MVN_OK;
+}
+static int mode_geometry(const SeqMode &m, const mvn_dims *dims, int batch, int t_len, const mvn_fwd_buffers *buf, Geometry &g) {
+  const int rc = make_geometry(dims, batch, t_len, g);
+  return rc ? rc : mode_supported(m, g, batch, buf);
+}
+// The four context-conv tensors of a parameter (or gradient) table, all present
+template <class P> static bool has_ctx_convs(const P *p) {
+  return p && p->ctx_filter_w && p->ctx_filter_b && p->ctx_gate_w && p->ctx_gate_b;
+}
+
 extern "C" {
 
 int mvn_padded_len(int n) { return n <= 0 ? 0 : (n + 63) / 64 * 64; }
 
 static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t *index, int index_stride,
                         int batch, int t_len, const mvn_fwd_buffers *buf, float *out, int normalize,
-                        int remove_last, int save, void *stream_, bool f16, bool bf16 = false,
-                        const float *gbias = nullptr, bool ctx16 = false) {
-  // ctx16 (mvn_forward_bf16_ctx): bf16 with the context as a third K block of the layer kernel; the caller has checked
-  // that there is one
+                        int remove_last, int save, void *stream_, const SeqMode &m) {
+  const bool f16 = m.precision == SeqMode::F16, bf16 = m.precision == SeqMode::BF16;
+  const float *const gbias = m.gbias;
   Geometry g;
-  int rc = make_geometry(dims, batch, t_len, g);
+  int rc = mode_geometry(m, dims, batch, t_len, buf, g);  // (decided before any launch: there is no fp32 fall-back)
   if (rc) return rc;
-  if (bf16) {  // (decided before any launch: there is no fp32 fall-back)
-    rc = bf16_supported(gbias ? "mvn_forward_bf16_global" : ctx16 ? "mvn_forward_bf16_ctx" : "mvn_forward_bf16", g,
-                        !ctx16 && buf && buf->ctx != nullptr);
-    if (rc) return rc;
-  }
   if (!p || !buf || !buf->acts || !buf->z || !buf->skip || !buf->a1 ||
       (save && (!buf->th || !buf->sg)) ||
       (buf->dense_audio ? buf->dense_ld < t_len : (!index || index_stride < t_len))) {
@@ -1158,7 +1191,7 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
     return MVN_ERR_BAD_ARG;
   }
   // (every refusal is decided here, in front of the first launch: a refused call has written nothing)
-  if (buf->ctx && (!p->ctx_filter_w || !p->ctx_filter_b || !p->ctx_gate_w || !p->ctx_gate_b || buf->ctx_ld < t_len)) {
+  if (buf->ctx && (!has_ctx_convs(p) || buf->ctx_ld < t_len)) {
     set_error("mvn_forward: context given without context-conv parameters / ctx_ld < t_len");
     return MVN_ERR_BAD_ARG;
   }
@@ -1209,7 +1242,7 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
       launch_gemm_staged(f, 2 * ((C + 31) / 32 * 32), batch, s, f16);
     };
     // bf16 operands (fused_bf16.h): the strip kernel with one-plane weight images, packed once per call into the z
-    // scratch when it holds them (bf16_supported has checked the dims and the row lengths)
+    // scratch when it holds them (mode_supported has checked the dims and the row lengths)
     if (bf16) {
       FusedFwdPArgs fp;
       fp.t_begin = A + d; fp.t_end = T; fp.d = d; fp.t_skip0 = t_skip0; fp.t_base = g.t_base;
@@ -1377,22 +1410,22 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
 int mvn_forward(const mvn_dims *dims, const mvn_params *p, const int32_t *index, int index_stride,
                 int batch, int t_len, const mvn_fwd_buffers *buf, float *out, int normalize,
                 int remove_last, int save, void *stream_) {
-  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_,
-                      false);
+  const SeqMode m = {SeqMode::F32, SeqMode::PLAIN, "mvn_forward"};
+  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_, m);
 }
 
 int mvn_forward_bf16(const mvn_dims *dims, const mvn_params *p, const int32_t *index, int index_stride,
                      int batch, int t_len, const mvn_fwd_buffers *buf, float *out, int normalize,
                      int remove_last, int save, void *stream_) {
-  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_,
-                      false, true);
+  const SeqMode m = {SeqMode::BF16, SeqMode::PLAIN, "mvn_forward_bf16"};
+  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_, m);
 }
 
 int mvn_forward_f16(const mvn_dims *dims, const mvn_params *p, const int32_t *index, int index_stride,
                     int batch, int t_len, const mvn_fwd_buffers *buf, float *out, int normalize,
                     int remove_last, int save, void *stream_) {
-  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_,
-                      true);
+  const SeqMode m = {SeqMode::F16, SeqMode::PLAIN, "mvn_forward_f16"};
+  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_, m);
 }
 
 static int g_last_bwd_form = 0;  // (process-wide: autograd runs the backward on a thread of its own)
@@ -1401,16 +1434,16 @@ int mvn_last_backward_form(void) { return g_last_bwd_form; }
 static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
                          const int32_t *index, int index_stride, int batch, int t_len,
                          const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
-                         const float *dout, int normalize, int remove_last, void *stream_, bool bf16,
-                         float *gpair = nullptr, size_t gpair_floats = 0, float *grow = nullptr, bool ctx16 = false) {
-  // ctx16 (mvn_backward_bf16_ctx): the bf16 layer kernel's dfg-writing form with the fp32 context pass behind it; gpair
-  // holds the second scatter pair, the slabs and the bias partials, as for the fp32 conditioned layers
-  // gpair (mvn_backward_global, mvn_backward_scratch): the caller's scratch for the one-kernel layer backward -- fast path (grow given) and
-  // conditioned layers (fwd->ctx: the label has joined the context) alike; without it the conditioned layers look for
-  // that room in dlogit / da1 and take another form where those are too small (short outputs, small Q).
-  // gpair / grow: the second pair of (B, C, Tp) scatter tensors -- the layer kernel writes
-  // df | dg into the dfg tensor here -- and the (L, B, 2C) row sums of df | dg
-  const bool glob = grow != nullptr;
+                         const float *dout, int normalize, int remove_last, void *stream_, const SeqMode &m) {
+  const bool bf16 = m.precision == SeqMode::BF16, glob = m.conditioning == SeqMode::GLOBAL,
+             ctx16 = m.conditioning == SeqMode::CTX16;
+  float *const gpair = m.scratch, *const grow = m.rowsum;
+  const size_t gpair_floats = m.scratch_floats;
+  // gpair: the caller's scratch for the one-kernel layer backward -- the second pair of (B, C, Tp) scatter tensors (the
+  // layer kernel writes df | dg into the dfg tensor here), the slabs and the bias partials: for glob, for ctx16 (the bf16
+  // layer kernel's dfg-writing form with the fp32 context pass behind it) and for conditioned fp32 layers (fwd->ctx: the
+  // label has joined the context), which without it look for that room in dlogit / da1 and take another form where
+  // those are too small (short outputs, small Q).  grow: the (L, B, 2C) row sums of df | dg
   Geometry g;
   int rc = make_geometry(dims, batch, t_len, g);
   if (rc) return rc;
@@ -1505,8 +1538,7 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
               "(mvn_global_fast_path)");
     return MVN_ERR_UNSUPPORTED;
   }
-  if (has_ctx && (!bwd->dctx || !gr->ctx_filter_w || !gr->ctx_filter_b || !gr->ctx_gate_w ||
-                  !gr->ctx_gate_b || !p->ctx_filter_w || !p->ctx_gate_w)) {
+  if (has_ctx && (!bwd->dctx || !has_ctx_convs(gr) || !p->ctx_filter_w || !p->ctx_gate_w)) {
     set_error("mvn_backward: context given without dctx buffer / context-conv gradients");
     return MVN_ERR_BAD_ARG;
   }
@@ -1554,8 +1586,7 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
   }
   float *g_part = nullptr;  // bf16 + labels: the layer kernel's partial row sums of df | dg, one 128-vector per workgroup
   if (bf16) {  // (decided before any launch: there is no fp32 fall-back)
-    rc = bf16_supported(glob ? "mvn_backward_bf16_global" : ctx16 ? "mvn_backward_bf16_ctx" : "mvn_backward_bf16", g,
-                        has_ctx && !ctx16);
+    rc = mode_supported(m, g, batch, fwd);
     if (rc) return rc;
     if (ctx16 && !ext) {
       set_error("mvn_backward_bf16_ctx: scratch missing or smaller than mvn_bf16_ctx_scratch_floats()");
@@ -1983,22 +2014,26 @@ int mvn_backward(const mvn_dims *dims, const mvn_params *p, const mvn_param_grad
                  const int32_t *index, int index_stride, int batch, int t_len,
                  const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
                  const float *dout, int normalize, int remove_last, void *stream_) {
-  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_,
-                       false);
+  const SeqMode m = {SeqMode::F32, SeqMode::PLAIN, "mvn_backward"};
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m);
 }
 
 int mvn_backward_bf16(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
                       const int32_t *index, int index_stride, int batch, int t_len,
                       const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
                       const float *dout, int normalize, int remove_last, void *stream_) {
-  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_,
-                       true);
+  const SeqMode m = {SeqMode::BF16, SeqMode::PLAIN, "mvn_backward_bf16"};
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m);
+}
+
+// The queries answer 0 for anything make_geometry refuses and for an empty batch
+static bool query_geometry(const mvn_dims *dims, int batch, int t_len, Geometry &g) {
+  return !make_geometry(dims, batch, t_len, g) && batch >= 1;
 }
 
 int mvn_global_fast_path(const mvn_dims *dims, int batch, int t_len) {
   Geometry g;
-  if (make_geometry(dims, batch, t_len, g) || batch < 1) return 0;
-  return global_forward_fast(g) && global_backward_fast(dims, g, batch) ? 1 : 0;
+  return query_geometry(dims, batch, t_len, g) && global_forward_fast(g) && global_backward_fast(dims, g, batch) ? 1 : 0;
 }
 
 int mvn_global_bias(const mvn_dims *dims, const mvn_params *p, const float *e, int batch, float *gbias, void *stream_) {
@@ -2008,8 +2043,7 @@ int mvn_global_bias(const mvn_dims *dims, const mvn_params *p, const float *e, i
     set_error("mvn_global_bias: residual_channels = 64 only (got %d)", dims->residual_channels);
     return MVN_ERR_UNSUPPORTED;
   }
-  if (!p || !p->ctx_filter_w || !p->ctx_filter_b || !p->ctx_gate_w || !p->ctx_gate_b || !e || !gbias || batch < 0 ||
-      batch > 65535) {
+  if (!has_ctx_convs(p) || !e || !gbias || batch < 0 || batch > 65535) {
     set_error("mvn_global_bias: bad argument");
     return MVN_ERR_BAD_ARG;
   }
@@ -2033,8 +2067,7 @@ int mvn_global_bias_backward(const mvn_dims *dims, const mvn_params *p, const mv
     set_error("mvn_global_bias_backward: residual_channels = 64 only (got %d)", dims->residual_channels);
     return MVN_ERR_UNSUPPORTED;
   }
-  if (!p || !p->ctx_filter_w || !p->ctx_gate_w || !p->ctx_filter_b || !p->ctx_gate_b || !gr || !gr->ctx_filter_w || !gr->ctx_filter_b || !gr->ctx_gate_w ||
-      !gr->ctx_gate_b || !rowsum || !e || !de || batch < 0 || batch > 65535) {
+  if (!has_ctx_convs(p) || !has_ctx_convs(gr) || !rowsum || !e || !de || batch < 0 || batch > 65535) {
     set_error("mvn_global_bias_backward: bad argument");
     return MVN_ERR_BAD_ARG;
   }
@@ -2063,8 +2096,9 @@ int mvn_forward_global(const mvn_dims *dims, const mvn_params *p, const int32_t 
     set_error("mvn_forward_global: gbias is NULL");
     return MVN_ERR_BAD_ARG;
   }
-  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_,
-                      false, false, gbias);
+  SeqMode m = {SeqMode::F32, SeqMode::GLOBAL, "mvn_forward_global"};
+  m.gbias = gbias;
+  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_, m);
 }
 
 int mvn_backward_global(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
@@ -2076,48 +2110,33 @@ int mvn_backward_global(const mvn_dims *dims, const mvn_params *p, const mvn_par
     set_error("mvn_backward_global: scratch / rowsum is NULL");
     return MVN_ERR_BAD_ARG;
   }
-  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_,
-                       false, scratch, scratch_floats, rowsum);
+  const SeqMode m = {SeqMode::F32, SeqMode::GLOBAL, "mvn_backward_global", scratch, scratch_floats, rowsum};
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m);
 }
 
 int mvn_global_bf16_path(const mvn_dims *dims, int batch, int t_len) {
   Geometry g;
-  if (make_geometry(dims, batch, t_len, g) || batch < 1) return 0;
-  return global_bf16_path(g, batch) ? 1 : 0;
+  return query_geometry(dims, batch, t_len, g) && global_bf16_path(g, batch) ? 1 : 0;
 }
 
 size_t mvn_global_bf16_scratch_floats(const mvn_dims *dims, int batch, int t_len) {
   Geometry g;
-  if (make_geometry(dims, batch, t_len, g) || batch < 1) return 0;
-  return global_bf16_scratch_floats(dims, g, batch);
-}
-
-// The refusals of the two labelled bf16 entry points, in the order the header documents them, all in front of the
-// first launch: the dims, a context, a batch / length the bf16 layer kernels cannot place (MVN_ERR_UNSUPPORTED).
-static int bf16_global_supported(const char *what, const mvn_dims *dims, int batch, int t_len, bool has_ctx, Geometry &g) {
-  int rc = make_geometry(dims, batch, t_len, g);
-  if (rc) return rc;
-  rc = bf16_supported(what, g, has_ctx);
-  if (rc) return rc;
-  if (batch >= 1 && !global_bf16_path(g, batch)) {
-    set_error("%s: the bf16 layer kernels cannot place batch %d, t_len %d (mvn_global_bf16_path)", what, batch, t_len);
-    return MVN_ERR_UNSUPPORTED;
-  }
-  return MVN_OK;
+  return query_geometry(dims, batch, t_len, g) ? global_bf16_scratch_floats(dims, g, batch) : 0;
 }
 
 int mvn_forward_bf16_global(const mvn_dims *dims, const mvn_params *p, const int32_t *index, int index_stride,
                             int batch, int t_len, const mvn_fwd_buffers *buf, float *out, int normalize,
                             int remove_last, int save, const float *gbias, void *stream_) {
+  SeqMode m = {SeqMode::BF16, SeqMode::GLOBAL, "mvn_forward_bf16_global"};
+  m.gbias = gbias;
   Geometry g;
-  const int rc = bf16_global_supported("mvn_forward_bf16_global", dims, batch, t_len, buf && buf->ctx != nullptr, g);
+  const int rc = mode_geometry(m, dims, batch, t_len, buf, g);  // (in front of the argument checks: the header's order)
   if (rc) return rc;
   if (!gbias) {
     set_error("mvn_forward_bf16_global: gbias is NULL");
     return MVN_ERR_BAD_ARG;
   }
-  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_,
-                      false, true, gbias);
+  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_, m);
 }
 
 int mvn_backward_bf16_global(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
@@ -2125,8 +2144,9 @@ int mvn_backward_bf16_global(const mvn_dims *dims, const mvn_params *p, const mv
                              const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
                              const float *dout, int normalize, int remove_last, float *scratch, size_t scratch_floats,
                              float *rowsum, void *stream_) {
+  const SeqMode m = {SeqMode::BF16, SeqMode::GLOBAL, "mvn_backward_bf16_global", scratch, scratch_floats, rowsum};
   Geometry g;
-  const int rc = bf16_global_supported("mvn_backward_bf16_global", dims, batch, t_len, fwd && fwd->ctx != nullptr, g);
+  const int rc = mode_geometry(m, dims, batch, t_len, fwd, g);
   if (rc) return rc;
   if (!scratch || !rowsum) {
     set_error("mvn_backward_bf16_global: scratch / rowsum is NULL");
@@ -2137,58 +2157,34 @@ int mvn_backward_bf16_global(const mvn_dims *dims, const mvn_params *p, const mv
               global_bf16_scratch_floats(dims, g, batch));
     return MVN_ERR_BAD_ARG;
   }
-  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_,
-                       true, scratch, scratch_floats, rowsum);
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m);
 }
 
 // Video context on bf16 operands (fused_bf16.h: the CTX and WRITE_DFG instantiations, with the fp32
 // context pass behind it).  What the kernels place is what the labelled bf16 form places; the scratch is the fp32
 // conditioned layers' (second scatter pair, slabs of the layer pass and of the context pass, bias partials).
-int mvn_bf16_ctx_path(const mvn_dims *dims, int batch, int t_len) {
-  Geometry g;
-  if (make_geometry(dims, batch, t_len, g) || batch < 1) return 0;
-  return global_bf16_path(g, batch) ? 1 : 0;
-}
+int mvn_bf16_ctx_path(const mvn_dims *dims, int batch, int t_len) { return mvn_global_bf16_path(dims, batch, t_len); }
 
 size_t mvn_bf16_ctx_scratch_floats(const mvn_dims *dims, int batch, int t_len) {
-  Geometry g;
-  if (make_geometry(dims, batch, t_len, g) || batch < 1) return 0;
-  return global_scratch_floats(dims, g, batch);
-}
-
-// The refusals that need no buffer: the dims, the rows, a batch / length the kernels cannot place (MVN_ERR_UNSUPPORTED)
-static int bf16_ctx_supported(const char *what, const mvn_dims *dims, int batch, int t_len, int ctx_ld, Geometry &g) {
-  int rc = make_geometry(dims, batch, t_len, g);
-  if (rc) return rc;
-  rc = bf16_supported(what, g, false);
-  if (rc) return rc;
-  if (ctx_ld > (1 << 21)) {
-    set_error("%s: bf16 needs ctx_ld <= %d", what, 1 << 21);
-    return MVN_ERR_UNSUPPORTED;
-  }
-  if (batch >= 1 && !global_bf16_path(g, batch)) {
-    set_error("%s: the bf16 layer kernels cannot place batch %d, t_len %d (mvn_bf16_ctx_path)", what, batch, t_len);
-    return MVN_ERR_UNSUPPORTED;
-  }
-  return MVN_OK;
+  return mvn_global_scratch_floats(dims, batch, t_len);
 }
 
 int mvn_forward_bf16_ctx(const mvn_dims *dims, const mvn_params *p, const int32_t *index, int index_stride,
                          int batch, int t_len, const mvn_fwd_buffers *buf, float *out, int normalize,
                          int remove_last, int save, void *stream_) {
+  const SeqMode m = {SeqMode::BF16, SeqMode::CTX16, "mvn_forward_bf16_ctx"};
   Geometry g;
-  const int rc = bf16_ctx_supported("mvn_forward_bf16_ctx", dims, batch, t_len, buf ? buf->ctx_ld : 0, g);
+  const int rc = mode_geometry(m, dims, batch, t_len, buf, g);
   if (rc) return rc;
   if (!buf || !buf->ctx) {
     set_error("mvn_forward_bf16_ctx: no context (buf->ctx is NULL)");
     return MVN_ERR_BAD_ARG;
   }
-  if (!p || !p->ctx_filter_w || !p->ctx_filter_b || !p->ctx_gate_w || !p->ctx_gate_b || buf->ctx_ld < t_len) {
+  if (!has_ctx_convs(p) || buf->ctx_ld < t_len) {
     set_error("mvn_forward_bf16_ctx: no context-conv parameters / ctx_ld < t_len");
     return MVN_ERR_BAD_ARG;
   }
-  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_,
-                      false, true, nullptr, true);
+  return forward_impl(dims, p, index, index_stride, batch, t_len, buf, out, normalize, remove_last, save, stream_, m);
 }
 
 int mvn_backward_bf16_ctx(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
@@ -2196,15 +2192,15 @@ int mvn_backward_bf16_ctx(const mvn_dims *dims, const mvn_params *p, const mvn_p
                           const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
                           const float *dout, int normalize, int remove_last, float *scratch, size_t scratch_floats,
                           void *stream_) {
+  const SeqMode m = {SeqMode::BF16, SeqMode::CTX16, "mvn_backward_bf16_ctx", scratch, scratch_floats};
   Geometry g;
-  const int rc = bf16_ctx_supported("mvn_backward_bf16_ctx", dims, batch, t_len, fwd ? fwd->ctx_ld : 0, g);
+  const int rc = mode_geometry(m, dims, batch, t_len, fwd, g);
   if (rc) return rc;
   if (!fwd || !fwd->ctx || !bwd || !bwd->dctx || !bwd->dfg) {
     set_error("mvn_backward_bf16_ctx: no context / dctx / dfg buffer");
     return MVN_ERR_BAD_ARG;
   }
-  if (!p || !p->ctx_filter_w || !p->ctx_filter_b || !p->ctx_gate_w || !p->ctx_gate_b || !gr || !gr->ctx_filter_w ||
-      !gr->ctx_filter_b || !gr->ctx_gate_w || !gr->ctx_gate_b || fwd->ctx_ld < t_len) {
+  if (!has_ctx_convs(p) || !has_ctx_convs(gr) || fwd->ctx_ld < t_len) {
     set_error("mvn_backward_bf16_ctx: no context-conv parameters or gradients / ctx_ld < t_len");
     return MVN_ERR_BAD_ARG;
   }
@@ -2212,8 +2208,7 @@ int mvn_backward_bf16_ctx(const mvn_dims *dims, const mvn_params *p, const mvn_p
     set_error("mvn_backward_bf16_ctx: scratch is NULL or holds fewer floats than mvn_bf16_ctx_scratch_floats()");
     return MVN_ERR_BAD_ARG;
   }
-  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_,
-                       true, scratch, scratch_floats, nullptr, true);
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m);
 }
 
 int mvn_backward_scratch(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
@@ -2225,14 +2220,13 @@ int mvn_backward_scratch(const mvn_dims *dims, const mvn_params *p, const mvn_pa
     set_error("mvn_backward_scratch: scratch is NULL");
     return MVN_ERR_BAD_ARG;
   }
-  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_,
-                       false, scratch, scratch_floats, nullptr);
+  const SeqMode m = {SeqMode::F32, SeqMode::PLAIN, "mvn_backward_scratch", scratch, scratch_floats};
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m);
 }
 
 size_t mvn_global_scratch_floats(const mvn_dims *dims, int batch, int t_len) {
   Geometry g;
-  if (make_geometry(dims, batch, t_len, g) || batch < 1) return 0;
-  return global_scratch_floats(dims, g, batch);
+  return query_geometry(dims, batch, t_len, g) ? global_scratch_floats(dims, g, batch) : 0;
 }
 
 int mvn_context_add_global(float *context_tm, const float *global, int batch, int channels, int t_len, int fill,

@@ -415,14 +415,15 @@ class RingGenerator:
         if self.prime_with_forward and P >= self.rf:
             # one full-sequence forward over the prompt (MFMA kernels), then copy
             # each layer's most recent d_l inputs into its queue
-            from .ops import run_forward
+            from .ops import SequenceMode, run_forward
             idx = self.samples_all[:, :P].contiguous()
             ctx = None if self.context is None else self.context[:, :, :P]
             if self.global_context is not None:  # (the prompt's columns only: the steps read the time-major copy)
                 g = self.global_context[:, :, None]
                 ctx = g.expand(-1, -1, P) if ctx is None else ctx + g
-            _, buf = run_forward(self.dims, self._sd, idx, False, False, save=True, ctx=ctx,
-                                 f16=self.variant == N.GEN_PIPE_F16)
+            mode = SequenceMode(precision="fp16" if self.variant == N.GEN_PIPE_F16 else "fp32",
+                                conditioning="none" if ctx is None else "context")
+            _, buf = run_forward(self.dims, self._sd, idx, False, False, save=True, mode=mode, cond=ctx)
             with torch.cuda.device(self.device):
                 N.check(self.lib.mvn_gen_prime_from_forward(
                     self.dims, buf.struct, self.nrows, P, self.state.data_ptr(),

@@ -8,7 +8,7 @@ allocator) and for the autograd hook; every arithmetic kernel is HIP.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import ctypes
 import os
@@ -99,17 +99,66 @@ class ForwardBuffers:
         self.dense = dense
 
 
+class SequenceMode(NamedTuple):
+    """What one full-sequence pass runs, decided once (plan_sequence, place_sequence); sequence_entry names its kernels."""
+    precision: str = "fp32"         # operands of the layers' products: "fp32" / "fp16" / "bf16"
+    conditioning: str = "none"      # what reaches the kernels: "none" / "context" (B, C, T) / "bias" (B, C) vectors
+    label_in_context: bool = False  # a label's vector has joined the context (general path of global conditioning)
+    loss_rule: int = N.LOSS_REFERENCE
+    grad_mode: bool = True          # grad mode at the call (it is off inside an autograd Function's forward)
+    video_slot: object = None       # VideoGradSlot of the context's up-sampler node, or None
+
+
+class SequenceEntry(NamedTuple):
+    forward: str
+    backward: Optional[str]              # None: inference only
+    path_query: Optional[str] = None     # asked before the pass is placed (place_sequence); None: any shape runs
+    scratch_query: Optional[str] = None  # floats of the backward's caller-owned scratch; None: it takes none
+    rowsum: bool = False                 # the backward fills (L, B, 128) row sums for mvn_global_bias_backward
+
+
+# Every legal (precision, conditioning) and the entry points that run it.  "bias" rows run mvn_global_bias in front of
+# the forward and mvn_global_bias_backward behind the backward.  "context+label": fp32, C = K = 64, a label in the
+# context -- the one-kernel layer backward with a scratch of its own (dlogit / da1, where it looks otherwise, do not
+# hold it at short outputs or small Q).  (mvn_bf16_ctx_path is not asked: the entry points refuse for themselves.)
+SEQUENCE_ENTRIES = {
+    ("fp32", "none"): SequenceEntry("mvn_forward", "mvn_backward"),
+    ("fp32", "context"): SequenceEntry("mvn_forward", "mvn_backward"),
+    ("fp32", "context+label"): SequenceEntry("mvn_forward", "mvn_backward_scratch", scratch_query="mvn_global_scratch_floats"),
+    ("fp32", "bias"): SequenceEntry("mvn_forward_global", "mvn_backward_global", "mvn_global_fast_path",
+                                    "mvn_global_scratch_floats", True),
+    ("fp16", "none"): SequenceEntry("mvn_forward_f16", None),
+    ("fp16", "context"): SequenceEntry("mvn_forward_f16", None),
+    ("bf16", "none"): SequenceEntry("mvn_forward_bf16", "mvn_backward_bf16"),
+    ("bf16", "bias"): SequenceEntry("mvn_forward_bf16_global", "mvn_backward_bf16_global", "mvn_global_bf16_path",
+                                    "mvn_global_bf16_scratch_floats", True),
+    ("bf16", "context"): SequenceEntry("mvn_forward_bf16_ctx", "mvn_backward_bf16_ctx", scratch_query="mvn_bf16_ctx_scratch_floats"),
+}
+
+
+def sequence_entry(mode: SequenceMode, dims) -> SequenceEntry:
+    """The row of SEQUENCE_ENTRIES that runs ``mode``; ValueError, by name, for a combination that has none."""
+    cond = mode.conditioning
+    if (mode.precision == "fp32" and cond == "context" and mode.label_in_context
+            and dims.residual_channels == 64 and dims.skip_channels == 64):
+        cond = "context+label"
+    entry = SEQUENCE_ENTRIES.get((mode.precision, cond))
+    if entry is None:
+        raise ValueError(f"movenet_amd: no sequence kernels run precision {mode.precision!r} with conditioning {cond!r}")
+    return entry
+
+
 def run_forward(dims: N.Dims, sd: Dict[str, torch.Tensor], idx: torch.Tensor, normalize: bool,
-                remove_last: bool, save: bool, ctx=None, f16: bool = False,
-                bf16: bool = False, gvec=None) -> Tuple[torch.Tensor, ForwardBuffers]:
+                remove_last: bool, save: bool, mode: SequenceMode = SequenceMode(),
+                cond=None) -> Tuple[torch.Tensor, ForwardBuffers]:
     """idx: (B,T) int32 class indices, or a (B,Q,T) fp32 tensor for inputs that are
-    not one-hot (dense causal conv).  ``f16``: fp16 operands / fp32 accumulation in every
-    product (mvn_forward_f16; inference and generator priming).  ``bf16``: bf16 operands /
-    fp32 accumulation in the layers' products (mvn_forward_bf16; trains with mvn_backward_bf16).
-    ``gvec``: (B, C) fp32 global vectors on the fast path of global conditioning (mvn_global_bias +
-    mvn_forward_global, with ``bf16`` mvn_forward_bf16_global: C = K = 64, no ``ctx``; the caller has asked
-    mvn_global_fast_path / mvn_global_bf16_path).  ``bf16`` with ``ctx``: mvn_forward_bf16_ctx."""
+    not one-hot (dense causal conv).  ``mode`` picks the entry point (SEQUENCE_ENTRIES); ``cond`` is what
+    ``mode.conditioning`` names: the (B, C, T) context, the (B, C) fp32 global vectors of the one-vector-per-layer path
+    (C = K = 64; the caller has asked the entry's path query), or None."""
     lib = N.lib()
+    entry = sequence_entry(mode, dims)
+    assert (cond is None) == (mode.conditioning == "none"), "mode.conditioning and the tensor given for it disagree"
+    ctx, gvec = (cond, None) if mode.conditioning == "context" else (None, cond)
     _require_gpu(idx, "audio")
     dense = None
     if idx.dim() == 3:
@@ -131,12 +180,8 @@ def run_forward(dims: N.Dims, sd: Dict[str, torch.Tensor], idx: torch.Tensor, no
         out = (torch.empty if buf.guard is None else buf.guard.empty)(
             (B, dims.input_channels, max(s_out, 0)), dtype=torch.float32, device=dev)
         params, keep = pack_params(dims, sd, L)
-        name = "mvn_forward_f16" if f16 else "mvn_forward_bf16" if bf16 else "mvn_forward"
-        if bf16 and ctx is not None:  # (bf16_mode has asked for WaveNet.bf16_context)
-            name = "mvn_forward_bf16_ctx"
-        tail = ()
+        name, tail = entry.forward, ()
         if gvec is not None:  # one 2C-vector per (layer, sequence) instead of a context product per column
-            name = "mvn_forward_bf16_global" if bf16 else "mvn_forward_global"
             gbias = (torch.empty if buf.guard is None else buf.guard.empty)((L, B, 128), dtype=torch.float32, device=dev)
             N.check(lib.mvn_global_bias(dims, params, gvec.data_ptr(), B, gbias.data_ptr(), _stream_ptr(dev)),
                     "mvn_global_bias")
@@ -153,33 +198,28 @@ def run_forward(dims: N.Dims, sd: Dict[str, torch.Tensor], idx: torch.Tensor, no
 
 
 class _WaveNetFunction(torch.autograd.Function):
-    """args: dims, names, idx, normalize, remove_last, ctx (Tensor or None), gvec (Tensor or None), *params.
-    ``gvec``: the (B, C) global vectors of the fast path of global conditioning (``context`` is None then)."""
-    N_FIXED = 7
+    """args: mode (SequenceMode), dims, names, idx, normalize, remove_last, ctx (Tensor or None), gvec (Tensor or
+    None), *params.  ``gvec``: the (B, C) global vectors of ``mode.conditioning == "bias"`` (``context`` is None then)."""
+    N_FIXED = 8
 
     @staticmethod
-    def forward(ctx_, dims, names, idx, normalize, remove_last, context, gvec, *params):
+    def forward(ctx_, mode, dims, names, idx, normalize, remove_last, context, gvec, *params):
         sd = dict(zip(names, params))
         # (grad mode itself is off inside forward(): the caller records whether it was on)
-        save = any(ctx_.needs_input_grad[5:]) and bool(getattr(dims, "_grad_mode", True))
-        f16 = bool(getattr(dims, "_f16", False))
-        if f16 and save:
+        save = any(ctx_.needs_input_grad[6:]) and mode.grad_mode
+        if save and sequence_entry(mode, dims).backward is None:
             raise RuntimeError("movenet_amd: forward_precision 'fp16' is inference-only "
                                "(mvn_backward differentiates the fp32 forward); use torch.no_grad()")
         gvec = None if gvec is None else gvec.detach().to(torch.float32).contiguous()
-        out, buf = run_forward(dims, sd, idx, normalize, remove_last, save, context, f16=f16,
-                               bf16=bool(getattr(dims, "_bf16", False)), gvec=gvec)
-        ctx_.dims, ctx_.names, ctx_.idx, ctx_.buf, ctx_.gvec = dims, names, idx, buf, gvec
+        out, buf = run_forward(dims, sd, idx, normalize, remove_last, save, mode, context if gvec is None else gvec)
+        ctx_.mode, ctx_.dims, ctx_.names, ctx_.idx, ctx_.buf, ctx_.gvec = mode, dims, names, idx, buf, gvec
         ctx_.normalize, ctx_.remove_last, ctx_.saved_fwd = normalize, remove_last, save
         ctx_.has_context = context is not None
-        ctx_.video_slot = getattr(dims, "_video_slot", None) if context is not None else None
         ctx_.save_for_backward(out, *params)
         return out
 
     @staticmethod
     def backward(ctx_, dout):
-        if not ctx_.saved_fwd:
-            raise RuntimeError("movenet_amd: forward ran without saved activations")
         out, *params = ctx_.saved_tensors
         dout = dout.to(torch.float32).contiguous()
         grads, dctx, dgvec = _run_backward(ctx_, params, out, dout, None)
@@ -215,6 +255,8 @@ def _run_backward(ctx_, params, out, dout, fill_dlogit):
     """mvn_backward for a saved forward.  ``dout``: gradient w.r.t. the model output, or None
     when ``fill_dlogit(dlogit, Sp, pad)`` writes the gradient w.r.t. the logits itself (the
     fused loss).  Returns ({name: grad view into ONE flat buffer}, dctx or None, dgvec or None)."""
+    if not ctx_.saved_fwd:
+        raise RuntimeError("movenet_amd: forward ran without saved activations")
     lib = N.lib()
     dims, names, idx, buf = ctx_.dims, ctx_.names, ctx_.idx, ctx_.buf
     L = dims.layer_size * dims.stack_size
@@ -228,7 +270,7 @@ def _run_backward(ctx_, params, out, dout, fill_dlogit):
         # fill kernel instead of ~190; FlatGradSync all-reduces the buffer in place and
         # FlatAdamW steps over it with one kernel)
         sizes = [p.numel() for p in params]
-        slot = getattr(ctx_, "video_slot", None)
+        slot = ctx_.mode.video_slot if ctx_.has_context else None
         flat = torch.zeros(sum(sizes) + (slot.total if slot is not None else 0), dtype=torch.float32,
                            device=dev)
         if slot is not None:  # the video encoder's gradients live behind the decoder's
@@ -263,45 +305,26 @@ def _run_backward(ctx_, params, out, dout, fill_dlogit):
             fill_dlogit(dlogit, buf.Sp, (rf - 1) & 31)
         params_c, pkeep = pack_params(dims, sd, L)
         # (a bf16 forward is differentiated by the bf16 backward: same operand rounding both ways)
-        name = "mvn_backward_bf16" if getattr(dims, "_bf16", False) else "mvn_backward"
-        gvec, tail, dgvec = getattr(ctx_, "gvec", None), (), None
-        if gvec is not None:
-            # global conditioning, fast path: the layer kernel leaves df | dg in the dfg tensor (its scatter pairs move
-            # to a scratch of their own), their row sums land in `rowsum` and one kernel turns those into the
-            # context-conv gradients and the gradient of the global vectors.  bf16: the layer kernel sums the rows
-            # itself; the scratch holds its slabs and partial sums
-            if name == "mvn_backward_bf16":
-                name = "mvn_backward_bf16_global"
-                n_scratch = int(lib.mvn_global_bf16_scratch_floats(dims, B, T))
-            else:
-                name = "mvn_backward_global"
-                n_scratch = int(lib.mvn_global_scratch_floats(dims, B, T))
+        entry = sequence_entry(ctx_.mode, dims)
+        name, gvec, tail, dgvec = entry.backward, ctx_.gvec, (), None
+        if entry.scratch_query is not None:
+            # the one-kernel layer backward's own scratch: slabs and partial sums, and (but bf16 + bias) the second pair
+            # of scatter tensors -- the layer kernel leaves df | dg in the dfg tensor
+            n_scratch = int(getattr(lib, entry.scratch_query)(dims, B, T))
             scratch = alloc((n_scratch,), **f32)
+            tail = (scratch.data_ptr(), n_scratch)
+        if entry.rowsum:
+            # (row sums of df | dg: mvn_global_bias_backward turns them into the context-conv and the vectors' gradients)
             rowsum = alloc((L, B, 128), **f32)
             rowsum.zero_()
-            tail = (scratch.data_ptr(), n_scratch, rowsum.data_ptr())
-        elif name == "mvn_backward_bf16" and ctx_.has_context:
-            # video context in bf16: the layer kernel's dfg-writing form, then the fp32 context pass; the scratch holds
-            # the second pair of gradient tensors, both passes' slabs and the bias partials
-            name = "mvn_backward_bf16_ctx"
-            n_scratch = int(lib.mvn_bf16_ctx_scratch_floats(dims, B, T))
-            scratch = alloc((n_scratch,), **f32)
-            tail = (scratch.data_ptr(), n_scratch)
-        elif (getattr(dims, "_label_in_context", False) and ctx_.has_context and C == 64 and K == 64
-              and name == "mvn_backward"):
-            # global conditioning, general path: the conditioned layers' one-kernel backward with a scratch of its own
-            # (dlogit / da1, where it looks otherwise, do not hold it at short outputs or small Q)
-            name = "mvn_backward_scratch"
-            n_scratch = int(lib.mvn_global_scratch_floats(dims, B, T))
-            scratch = alloc((n_scratch,), **f32)
-            tail = (scratch.data_ptr(), n_scratch)
+            tail += (rowsum.data_ptr(),)
         N.check(getattr(lib, name)(dims, params_c, g, None if dense_in else idx.data_ptr(),
                                    0 if dense_in else idx.stride(0), B, T,
                                    buf.struct, bw, None if out is None else out.data_ptr(),
                                    None if dout is None else dout.data_ptr(),
                                    int(ctx_.normalize), int(ctx_.remove_last), *tail, _stream_ptr(dev)),
                 name)
-        if gvec is not None:
+        if entry.rowsum:
             dgvec = alloc((B, C), **f32)
             N.check(lib.mvn_global_bias_backward(dims, params_c, g, rowsum.data_ptr(), gvec.data_ptr(), B,
                                                  dgvec.data_ptr(), _stream_ptr(dev)), "mvn_global_bias_backward")
@@ -328,21 +351,19 @@ class _WaveNetLossFunction(torch.autograd.Function):
     """Forward + the trainer's loss in one autograd node (row F3): the head's logits become
     probabilities and the loss / accuracy partial sums in ONE pass (mvn_softmax_ce_forward_ex);
     backward differentiates loss -> logits in ONE pass (mvn_softmax_ce_backward_ex) straight into
-    mvn_backward's dlogit buffer.  args: dims, names, idx, target (B,S) int64, ctx, gvec, *params;
-    returns (loss, accuracy, probs).  ``dims._loss_rule`` (N.LOSS_REFERENCE when absent) picks the
-    loss: cross_entropy on the probabilities, or the negative log-likelihood of softmax(logits)."""
-    N_FIXED = 6
+    mvn_backward's dlogit buffer.  args: mode (SequenceMode), dims, names, idx, target (B,S) int64, ctx, gvec,
+    *params; returns (loss, accuracy, probs).  ``mode.loss_rule`` picks the loss: cross_entropy on the
+    probabilities, or the negative log-likelihood of softmax(logits)."""
+    N_FIXED = 7
 
     @staticmethod
-    def forward(ctx_, dims, names, idx, target, context, gvec, *params):
+    def forward(ctx_, mode, dims, names, idx, target, context, gvec, *params):
         lib = N.lib()
         sd = dict(zip(names, params))
-        rule = int(getattr(dims, "_loss_rule", N.LOSS_REFERENCE))
-        save = any(ctx_.needs_input_grad[4:]) and bool(getattr(dims, "_grad_mode", True))
+        save = any(ctx_.needs_input_grad[5:]) and mode.grad_mode
         # logits, last column dropped
         gvec = None if gvec is None else gvec.detach().to(torch.float32).contiguous()
-        out, buf = run_forward(dims, sd, idx, False, True, save, context, bf16=bool(getattr(dims, "_bf16", False)),
-                               gvec=gvec)
+        out, buf = run_forward(dims, sd, idx, False, True, save, mode, context if gvec is None else gvec)
         B, Q, S = out.shape
         if target.shape != (B, S):
             raise ValueError(f"target must be (batch, {S}), got {tuple(target.shape)}")
@@ -352,24 +373,20 @@ class _WaveNetLossFunction(torch.autograd.Function):
             loss_part = torch.zeros(parts, dtype=torch.float32, device=out.device)
             ok_part = torch.zeros(parts, dtype=torch.int32, device=out.device)
             N.check(lib.mvn_softmax_ce_forward_ex(out.data_ptr(), tg.data_ptr(), B, Q, S, loss_part.data_ptr(),
-                                                  ok_part.data_ptr(), rule, _stream_ptr(out.device)),
+                                                  ok_part.data_ptr(), int(mode.loss_rule), _stream_ptr(out.device)),
                     "mvn_softmax_ce_forward_ex")
         n = max(B * S, 1)
         loss = loss_part.sum() / n
         acc = ok_part.sum().to(torch.float32) / n
-        ctx_.dims, ctx_.names, ctx_.idx, ctx_.buf, ctx_.gvec = dims, names, idx, buf, gvec
+        ctx_.mode, ctx_.dims, ctx_.names, ctx_.idx, ctx_.buf, ctx_.gvec = mode, dims, names, idx, buf, gvec
         ctx_.normalize, ctx_.remove_last, ctx_.saved_fwd = True, True, save
         ctx_.has_context = context is not None
-        ctx_.loss_rule = rule
-        ctx_.video_slot = getattr(dims, "_video_slot", None) if context is not None else None
         ctx_.save_for_backward(out, tg, *params)
         ctx_.mark_non_differentiable(acc, out)
         return loss, acc, out
 
     @staticmethod
     def backward(ctx_, dloss, _dacc, _dprobs):
-        if not ctx_.saved_fwd:
-            raise RuntimeError("movenet_amd: forward ran without saved activations")
         lib = N.lib()
         probs, tg, *params = ctx_.saved_tensors
         B, Q, S = probs.shape
@@ -378,7 +395,7 @@ class _WaveNetLossFunction(torch.autograd.Function):
         def fill(dlogit, Sp, pad):
             N.check(lib.mvn_softmax_ce_backward_ex(
                 probs.data_ptr(), tg.data_ptr(), B, Q, S, 1.0 / max(B * S, 1), up.data_ptr(),
-                dlogit.data_ptr(), Q * Sp, Sp, pad, S + 1, ctx_.loss_rule, _stream_ptr(probs.device)),
+                dlogit.data_ptr(), Q * Sp, Sp, pad, S + 1, int(ctx_.mode.loss_rule), _stream_ptr(probs.device)),
                 "mvn_softmax_ce_backward_ex")
 
         grads, dctx, dgvec = _run_backward(ctx_, params, None, None, fill)
@@ -457,45 +474,36 @@ def upsample_video(model, video: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def _tagged_dims(dims, f16: bool = False, context=None, bf16: bool = False, loss_rule: int = N.LOSS_REFERENCE,
-                 label_in_context: bool = False):
-    """A copy of the dims struct carrying what the autograd Functions cannot see from inside
-    ``forward``: whether grad mode was on at the call, the operand precision, the loss rule and whether a label's
-    vector has joined the context (general path of global conditioning: the backward then brings a scratch)."""
-    d = N.make_dims(dims.layer_size, dims.stack_size, dims.input_channels, dims.residual_channels,
-                    dims.skip_channels)
-    d._grad_mode = torch.is_grad_enabled()
-    d._f16 = f16
-    d._bf16 = bf16
-    d._loss_rule = loss_rule
-    d._label_in_context = bool(label_in_context)
-    d._video_slot = getattr(context, "_mvn_video_slot", None) if context is not None else None
-    return d
+_BIAS_WITH_VIDEO = "global_path 'bias' runs models without a video context"
+
+
+def plan_sequence(model, has_video: bool, has_label: bool) -> SequenceMode:
+    """Phase one of a pass's plan, shape-free: the precision ``model`` asks for and every ValueError that needs only
+    the model's attributes and whether a video / a label is given -- raised before the video encoder runs (the bf16
+    entry points refuse the same).  bf16 runs C = K = 64; a video context only where the model opts in a second time
+    (``bf16_context = True``; labels then ride in the context); labels without video only on the one-vector-per-layer
+    path, asked for by name (``global_path = "bias"``).  "bias" never runs with video."""
+    precision = getattr(model, "forward_precision", "fp32")
+    path = getattr(model, "global_path", "auto")
+    if precision == "bf16":
+        C, K = model._dims.residual_channels, model._dims.skip_channels
+        if C != 64 or K != 64:
+            raise ValueError("forward_precision 'bf16' needs residual_channels = skip_channels = 64, "
+                             f"got {C} and {K}")
+        if has_video and not getattr(model, "bf16_context", False):
+            raise ValueError("forward_precision 'bf16' runs audio-only models: no video context")
+        if has_label and not has_video and path != "bias":
+            raise ValueError("forward_precision 'bf16' runs audio-only models: no global conditioning (global_features) "
+                             "unless global_path is 'bias'")
+    if has_label and has_video and path == "bias":
+        raise ValueError(_BIAS_WITH_VIDEO)
+    return SequenceMode(precision=precision)
 
 
 def bf16_mode(model, conditioned: bool, labelled: bool = False) -> bool:
-    """Whether ``model.forward_precision`` asks for the bf16 layer kernels; raises ValueError, before
-    anything is launched, for what they do not run (mvn_forward_bf16 / mvn_backward_bf16 refuse the same).  Labels run
-    in bf16 only where the model asks for the one-vector-per-layer path by name (``global_path = "bias"``:
-    mvn_forward_bf16_global / mvn_backward_bf16_global); "auto" and "context" refuse them as before.  A video context
-    runs only where the model opts in a second time (``bf16_context = True``: mvn_forward_bf16_ctx /
-    mvn_backward_bf16_ctx); labels then ride in the context ("auto" / "context"), and "bias" with video keeps raising."""
-    if getattr(model, "forward_precision", "fp32") != "bf16":
-        return False
-    C, K = model._dims.residual_channels, model._dims.skip_channels
-    if C != 64 or K != 64:
-        raise ValueError("forward_precision 'bf16' needs residual_channels = skip_channels = 64, "
-                         f"got {C} and {K}")
-    if conditioned and getattr(model, "bf16_context", False):
-        if labelled and getattr(model, "global_path", "auto") == "bias":
-            raise ValueError("global_path 'bias' runs models without a video context")
-        return True
-    if conditioned:
-        raise ValueError("forward_precision 'bf16' runs audio-only models: no video context")
-    if labelled and getattr(model, "global_path", "auto") != "bias":
-        raise ValueError("forward_precision 'bf16' runs audio-only models: no global conditioning (global_features) "
-                         "unless global_path is 'bias'")
-    return True
+    """Whether ``model.forward_precision`` is 'bf16' -- then with plan_sequence's ValueErrors; else nothing is checked."""
+    return (getattr(model, "forward_precision", "fp32") == "bf16"
+            and plan_sequence(model, conditioned, labelled).precision == "bf16")
 
 
 def global_vector(model, global_features, batch: int):
@@ -526,42 +534,44 @@ def global_vector(model, global_features, batch: int):
                      f"got {tuple(gf.shape)} {gf.dtype}")
 
 
-def _global_plan(model, context, gvec, batch: int, t_len: int):
-    """(context, gvec) as the autograd nodes take them.  Fast path (C = K = 64, fp32, no video, ``model.global_path ==
-    "auto"`` and mvn_global_fast_path grants the shape under the process's kernel switches): the vectors go in as they
-    are.  General path: they join the context as a column constant in time and the conditioned kernels run.
-    ``global_path == "bias"`` requires the one-vector-per-layer path -- fp32: that fast path; bf16: the labelled bf16
-    layer kernels, where mvn_global_bf16_path grants the shape -- and raises ValueError where it does not exist."""
-    if gvec is None:
-        return context, None
-    dims = model._dims
-    if getattr(model, "global_path", "auto") == "bias":
-        precision = model.forward_precision
+def place_sequence(model, mode: SequenceMode, context, gvec, batch: int, t_len: int, loss_rule=None):
+    """Phase two, for a (batch, t_len): the finished mode and the (context, gvec) pair the autograd nodes take.
+    A label takes the one-vector-per-layer path ("bias": the vectors go in as they are) where ``model.global_path ==
+    "bias"`` requires it -- ValueError where it does not exist -- or where "auto" finds it: fp32, C = K = 64, no video,
+    and the row's path query grants the shape under the process's kernel switches.  Anywhere else it joins the context
+    as a column constant in time.  ``loss_rule``: the fused loss node's, which trains fp32 under precision 'fp16'."""
+    dims, path = model._dims, getattr(model, "global_path", "auto")
+    labelled, bias = gvec is not None, False
+    c64 = dims.residual_channels == 64 and dims.skip_channels == 64
+    if labelled and path == "bias":
         if context is not None:
-            raise ValueError("global_path 'bias' runs models without a video context")
-        if dims.residual_channels != 64 or dims.skip_channels != 64:
+            raise ValueError(_BIAS_WITH_VIDEO)
+        if not c64:
             raise ValueError("global_path 'bias' needs residual_channels = skip_channels = 64, "
                              f"got {dims.residual_channels} and {dims.skip_channels}")
-        if precision not in ("fp32", "bf16"):
-            raise ValueError(f"global_path 'bias' runs forward_precision 'fp32' or 'bf16', not {precision!r}")
+        if (mode.precision, "bias") not in SEQUENCE_ENTRIES:
+            raise ValueError(f"global_path 'bias' runs forward_precision 'fp32' or 'bf16', not {mode.precision!r}")
+    if labelled and (path == "bias" or (path == "auto" and context is None and mode.precision == "fp32" and c64)):
+        ask = SEQUENCE_ENTRIES[mode.precision, "bias"].path_query
         with torch.cuda.device(gvec.device):
-            ask = "mvn_global_bf16_path" if precision == "bf16" else "mvn_global_fast_path"
-            if getattr(N.lib(), ask)(dims, batch, t_len) != 1:
-                raise ValueError(f"global_path 'bias': the {precision} layer kernels do not run batch {batch}, length "
-                                 f"{t_len} under the process's kernel switches ({ask} returned 0)")
-        return None, gvec
-    if (context is None and getattr(model, "global_path", "auto") == "auto" and model.forward_precision == "fp32"
-            and dims.residual_channels == 64 and dims.skip_channels == 64):
-        with torch.cuda.device(gvec.device):
-            if N.lib().mvn_global_fast_path(dims, batch, t_len) == 1:
-                return None, gvec
-    if context is None:
-        return gvec[:, :, None].expand(-1, -1, t_len), None
-    both = context + gvec[:, :, None]
-    slot = getattr(context, "_mvn_video_slot", None)
-    if slot is not None:
-        both._mvn_video_slot = slot
-    return both, None
+            bias = getattr(N.lib(), ask)(dims, batch, t_len) == 1
+        if path == "bias" and not bias:
+            raise ValueError(f"global_path 'bias': the {mode.precision} layer kernels do not run batch {batch}, length "
+                             f"{t_len} under the process's kernel switches ({ask} returned 0)")
+    if labelled and not bias:
+        slot = getattr(context, "_mvn_video_slot", None)
+        context = gvec[:, :, None].expand(-1, -1, t_len) if context is None else context + gvec[:, :, None]
+        if slot is not None:
+            context._mvn_video_slot = slot
+        gvec = None
+    mode = mode._replace(
+        precision="fp32" if loss_rule is not None and mode.precision == "fp16" else mode.precision,
+        conditioning="bias" if bias else "none" if context is None else "context",
+        label_in_context=labelled and not bias,
+        loss_rule=N.LOSS_REFERENCE if loss_rule is None else loss_rule,
+        grad_mode=torch.is_grad_enabled(),
+        video_slot=None if context is None else getattr(context, "_mvn_video_slot", None))
+    return mode, context, gvec
 
 
 def _decoder_params(model, with_context: bool):
@@ -578,22 +588,19 @@ def wavenet_forward(model, audio: torch.Tensor, context=None, output_unnormalize
     (B, C, T) or None.  One-hot input runs the causal conv as a gather; the check that the
     input IS one-hot is read after the kernels have been enqueued (no host wait on an idle
     GPU) and anything else is rerun through the dense causal conv."""
-    bf16 = bf16_mode(model, context is not None, gvec is not None)
+    mode = plan_sequence(model, context is not None, gvec is not None)
     model.compute_output_size(audio)  # ValueError when T < RF, like the reference
-    labelled = gvec is not None
-    context, gvec = _global_plan(model, context, gvec, int(audio.shape[0]), int(audio.shape[2]))
+    mode, context, gvec = place_sequence(model, mode, context, gvec, int(audio.shape[0]), int(audio.shape[2]))
     idx, check = model._indices_async(audio)
-    names, params = _decoder_params(model, context is not None or gvec is not None)
-    dims = _tagged_dims(model._dims, f16=model.forward_precision == "fp16", context=context, bf16=bf16,
-                        label_in_context=labelled and gvec is None)
-    out = _WaveNetFunction.apply(dims, names, idx, bool(output_unnormalized),
+    names, params = _decoder_params(model, mode.conditioning != "none")
+    out = _WaveNetFunction.apply(mode, model._dims, names, idx, bool(output_unnormalized),
                                  bool(remove_last), context, gvec, *params)
     if not model._all_one_hot(check):  # dense causal conv on the tensor itself
         # (a dense input pays the discarded index pass: one extra forward; its buffers --
         # saved activations included -- are released BEFORE the rerun allocates its own)
         del out
         dense = audio.detach().to(torch.float32).contiguous()
-        out = _WaveNetFunction.apply(dims, names, dense, bool(output_unnormalized),
+        out = _WaveNetFunction.apply(mode, model._dims, names, dense, bool(output_unnormalized),
                                      bool(remove_last), context, gvec, *params)
     return out if audio.dtype == torch.float32 else out.to(audio.dtype)
 
@@ -610,22 +617,20 @@ def wavenet_forward_loss(model, audio: torch.Tensor, context=None, target=None, 
     ``F.cross_entropy(logits, target)`` instead -- the mean negative log-likelihood, in nats, of the
     distribution ``generate_sampling = "model"`` draws from; accuracy and probabilities are the same."""
     rule = N.loss_rule(getattr(model, "loss_rule", "reference") if loss_rule is None else loss_rule)
-    bf16 = bf16_mode(model, context is not None, gvec is not None)
+    mode = plan_sequence(model, context is not None, gvec is not None)
     model.compute_output_size(audio)
-    labelled = gvec is not None
-    context, gvec = _global_plan(model, context, gvec, int(audio.shape[0]), int(audio.shape[2]))
+    mode, context, gvec = place_sequence(model, mode, context, gvec, int(audio.shape[0]), int(audio.shape[2]),
+                                         loss_rule=rule)
     rf = model.receptive_fields
     idx, check = model._indices_async(audio)
-    names, params = _decoder_params(model, context is not None or gvec is not None)
+    names, params = _decoder_params(model, mode.conditioning != "none")
     tg = idx[:, rf:].to(torch.int64) if target is None else target
-    dims = _tagged_dims(model._dims, context=context, bf16=bf16, loss_rule=rule,
-                        label_in_context=labelled and gvec is None)
-    res = _WaveNetLossFunction.apply(dims, names, idx, tg, context, gvec, *params)
+    res = _WaveNetLossFunction.apply(mode, model._dims, names, idx, tg, context, gvec, *params)
     if not model._all_one_hot(check):  # (read after the enqueue: no idle GPU) dense causal conv
         del res  # release the discarded pass (saved activations) before the rerun allocates
         dense = audio.detach().to(torch.float32).contiguous()
         tg = audio[:, :, rf:].argmax(1) if target is None else target
-        res = _WaveNetLossFunction.apply(dims, names, dense, tg, context, gvec, *params)
+        res = _WaveNetLossFunction.apply(mode, model._dims, names, dense, tg, context, gvec, *params)
     return res
 
 
@@ -685,10 +690,10 @@ def wavenet_score(model, audio: torch.Tensor, context=None, gvec=None, temperatu
     forward's checks and kernels -- whatever ``forward_precision`` and ``global_path`` say -- with nothing saved and
     nothing normalised, then mvn_score_columns on what the head wrote."""
     temperature = score_temperature(temperature)
-    bf16 = bf16_mode(model, context is not None, gvec is not None)
+    mode = plan_sequence(model, context is not None, gvec is not None)
     model.compute_output_size(audio)  # ValueError when T < RF
     idx, check = model._indices_async(audio)
-    out = score_indices(model, idx, context, gvec, temperature, entropy, rank, bf16=bf16)
+    out = score_indices(model, idx, context, gvec, temperature, entropy, rank, mode)
     if not model._all_one_hot(check):  # (read after the enqueue, as forward reads it)
         raise ValueError("WaveNet.score expects one-hot audio (the target is its class index): a column of the input "
                          "is not one-hot")
@@ -696,16 +701,16 @@ def wavenet_score(model, audio: torch.Tensor, context=None, gvec=None, temperatu
 
 
 def score_indices(model, idx: torch.Tensor, context, gvec, temperature: float, entropy: bool, rank: bool,
-                  bf16: bool) -> dict:
-    """The scoring pass on class indices ``idx`` (B, T) int32 (what WaveNet.score and WaveNet.classify share)."""
+                  mode: SequenceMode) -> dict:
+    """The scoring pass on class indices ``idx`` (B, T) int32 (what WaveNet.score and WaveNet.classify share);
+    ``mode``: plan_sequence's, placed here for the chunk's batch."""
     B, T = idx.shape
-    context, gvec = _global_plan(model, context, gvec, B, T)
-    names, params = _decoder_params(model, context is not None or gvec is not None)
+    mode, context, gvec = place_sequence(model, mode, context, gvec, B, T)
+    names, params = _decoder_params(model, mode.conditioning != "none")
     sd = {n: p.detach() for n, p in zip(names, params)}
     if gvec is not None:
         gvec = gvec.detach().to(torch.float32).contiguous()
-    logits, _ = run_forward(model._dims, sd, idx, False, True, False, context,
-                            f16=model.forward_precision == "fp16", bf16=bf16, gvec=gvec)
+    logits, _ = run_forward(model._dims, sd, idx, False, True, False, mode, context if gvec is None else gvec)
     return score_logits(logits, idx[:, model.receptive_fields:], temperature, entropy=entropy, rank=rank)
 
 

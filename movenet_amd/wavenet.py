@@ -347,15 +347,13 @@ class WaveNet(nn.Module):
         -- as ONE autograd node (ops.wavenet_forward_loss); going through ``forward`` keeps
         module hooks firing on the fused path.  ``loss_rule = "model"`` makes that loss
         ``F.cross_entropy`` of the logits instead (the property's docstring)."""
-        from .ops import bf16_mode, global_vector, wavenet_forward, wavenet_forward_loss  # HIP full-sequence kernels
+        from .ops import global_vector, plan_sequence, wavenet_forward, wavenet_forward_loss  # HIP full-sequence kernels
         gvec = global_vector(self, global_features, int(audio.shape[0]))  # (ValueError before anything is launched)
         if gvec is not None and self.training:  # label dropout: both paths below see an ordinary e
             keep = self.global_dropout_mask(int(audio.shape[0]))
             if keep is not None:
                 gvec = gvec * keep.to(device=gvec.device, dtype=gvec.dtype)[:, None]
-        bf16_mode(self, video is not None, gvec is not None)  # (refused before the video encoder runs)
-        if gvec is not None and video is not None and self.global_path == "bias":
-            raise ValueError("global_path 'bias' runs models without a video context")
+        plan_sequence(self, video is not None, gvec is not None)  # (refused before the video encoder runs)
         context = None if video is None else self.upsample_video(video)
         if return_loss:
             return wavenet_forward_loss(self, audio, context, target, gvec=gvec)
@@ -364,14 +362,12 @@ class WaveNet(nn.Module):
 
     # ---- likelihood of GIVEN audio ---------------------------
     def _score_checks(self, audio, video, global_features):
-        """The forward's own refusals, before anything is launched; returns (gvec, bf16)."""
-        from .ops import bf16_mode, global_vector
+        """The forward's own refusals, before anything is launched; returns (gvec, the pass's planned mode)."""
+        from .ops import global_vector, plan_sequence
         gvec = global_vector(self, global_features, int(audio.shape[0]))
-        bf16 = bf16_mode(self, video is not None, gvec is not None)
-        if gvec is not None and video is not None and self.global_path == "bias":
-            raise ValueError("global_path 'bias' runs models without a video context")
+        mode = plan_sequence(self, video is not None, gvec is not None)
         self.compute_output_size(audio)
-        return gvec, bf16
+        return gvec, mode
 
     @staticmethod
     def _score_result(raw: dict, positions: int) -> "ScoreResult":
@@ -421,7 +417,7 @@ class WaveNet(nn.Module):
             log_prior = torch.as_tensor(log_prior)
             if tuple(log_prior.shape) not in ((G,), (B, G)):
                 raise ValueError(f"log_prior must be ({G},) or ({B}, {G}), got {tuple(log_prior.shape)}")
-        _, bf16 = self._score_checks(audio, video, torch.zeros(B, dtype=torch.int64))
+        _, mode = self._score_checks(audio, video, torch.zeros(B, dtype=torch.int64))
         context = None if video is None else self.upsample_video(video)
         idx = self._indices_of(audio)  # ValueError unless one-hot
         positions = int(audio.shape[2]) - self.receptive_fields
@@ -434,7 +430,7 @@ class WaveNet(nn.Module):
             rows = pairs[p0:p0 + step]
             seq, cls = rows % B, rows // B
             raw = score_indices(self, idx[seq], None if context is None else context[seq], E[cls], 1.0, False, False,
-                                bf16=bf16)
+                                mode)
             nll.append(raw["seq_nll"])
         loglik = -torch.cat(nll).view(G, B).t().contiguous()
         post = loglik.double() if log_prior is None else loglik.double() + log_prior.to(loglik.device).double()
