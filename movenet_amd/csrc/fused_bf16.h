@@ -101,9 +101,6 @@ __global__ __launch_bounds__(256) void fb16_pack_kernel(Fs3PackArgs p, float *ds
   fb16_stage_weights((unsigned char *)(dst + (size_t)l * FB16_PACK_F), p.wf[l], p.wg[l], p.wr[l], p.ws[l], p.br[l], p.bs[l],
                      blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
 }
-struct Fb16cPackArgs {
-  const float *wcf[FS3_PACK_LAYERS], *wcg[FS3_PACK_LAYERS], *bcf[FS3_PACK_LAYERS], *bcg[FS3_PACK_LAYERS];
-};
 __global__ __launch_bounds__(256) void fb16c_pack_kernel(Fs3PackArgs p, Fb16cPackArgs c, float *dst) {
   const int l = blockIdx.y;
   fb16c_stage_weights((unsigned char *)(dst + (size_t)l * FB16C_PACK_F), p.wf[l], p.wg[l], p.wr[l], p.ws[l], p.br[l], p.bs[l],
@@ -330,8 +327,65 @@ __global__ __launch_bounds__(512, 1) void fused_layer64s_bf16_kernel(FusedFwdPAr
   }
 }
 
-// the LDS images of layers 0 .. L-1 into `dst` (L x FB16_PACK_F floats), one launch per 32 layers
-static int launch_fb16_pack(const mvn_params *p, int L, float *dst, hipStream_t s) {
+// ----------------------------------------------------------------------------------------
+// The forward's layer forms, one row each: what a launch needs besides the layer's arguments.  (The table stands here
+// because this header sees every forward kernel: fused_fwd.h, fused_fwd_bf3.h and the ones above.)  sequence.hip picks
+// one row per call, in front of the first launch (plan_forward), and every layer of the call goes through
+// launch_layer_form with it; launch_layer_pack writes the row's L weight images where the z scratch holds them.
+// ----------------------------------------------------------------------------------------
+struct LayerForm {
+  const char *attr_what;                                  // error text of the kernel's dynamic-LDS attribute
+  void (*kernel)(FusedFwdPArgs, int, int);                // nullptr: the generic two-kernel form (sequence.hip: run_fg / RsOp)
+  int block, lds_bytes;                                   // threads per workgroup, dynamic LDS
+  int per_cu, granule;                                    // fb_chunks: workgroups per CU, columns a chunk is a multiple of
+  int pack_f;                                             // floats from one layer's LDS image to the next; 0: no image
+  const char *pack_what;                                  // error text of the pack launch
+  void (*pack)(Fs3PackArgs, float *);                     // the image's pack kernel: this one, or the one that
+  void (*pack_ctx)(Fs3PackArgs, Fb16cPackArgs, float *);  // takes the context convs as well
+};
+enum LayerFormId {
+  FORM_GENERIC, FORM_F32_TILE, FORM_F32_STRIP, FORM_F32_STRIP_CTX, FORM_BF3_STRIP, FORM_BF3_STRIP_BIAS, FORM_CTXW2_STRIP,
+  FORM_BF16_STRIP, FORM_BF16_STRIP_BIAS, FORM_BF16_STRIP_CTX, N_LAYER_FORMS
+};
+constexpr int F32_TILE_LDS_BYTES = (2 * 128 + 3 * 64) * (32 + 4) * (int)sizeof(float);
+constexpr int F32_STRIP_LDS_BYTES = (16384 + 8192 + 256) * (int)sizeof(float), F32_STRIP_CTX_LDS_BYTES = F32_STRIP_LDS_BYTES + 8192 * 4;
+constexpr int GBIAS_LDS_BYTES = 128 * 4;  // the bias forms: the sequence's f | g vector behind the image
+// strip kernels: 512 threads, one workgroup per CU, chunks of whole rounds of the 8 waves' 32-column strips; the tile
+// kernel: 256 threads, two workgroups per CU, 32-column tiles
+static const LayerForm LAYER_FORMS[N_LAYER_FORMS] = {
+    /* GENERIC            */ {nullptr, nullptr, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr},
+    /* F32_TILE           */ {"hipFuncSetAttribute(fused_layer64p)", fused_layer64p_kernel, 256, F32_TILE_LDS_BYTES, 2, 32, 0, nullptr, nullptr, nullptr},
+    /* F32_STRIP          */ {"hipFuncSetAttribute(fused_layer64s)", fused_layer64s_kernel<false>, 512, F32_STRIP_LDS_BYTES, 1, 256, 0, nullptr, nullptr, nullptr},
+    /* F32_STRIP_CTX      */ {"hipFuncSetAttribute(fused_layer64s)", fused_layer64s_kernel<true>, 512, F32_STRIP_CTX_LDS_BYTES, 1, 256, 0, nullptr, nullptr, nullptr},
+    /* BF3_STRIP          */ {"hipFuncSetAttribute(fused_layer64s_bf3)", fused_layer64s_bf3_kernel<false>, 512, FS3_LDS_BYTES, 1, 256, FS3_PACK_F, "fs3_pack", fs3_pack_kernel, nullptr},
+    /* BF3_STRIP_BIAS     */ {"hipFuncSetAttribute(fused_layer64s_bf3<global>)", fused_layer64s_bf3_kernel<true>, 512, FS3_LDS_BYTES + GBIAS_LDS_BYTES, 1, 256, FS3_PACK_F, "fs3_pack", fs3_pack_kernel, nullptr},
+    /* CTXW2_STRIP        */ {"hipFuncSetAttribute(fused_layer64s_ctxw2)", fused_layer64s_ctxw2_kernel, 512, FSC_LDS_BYTES, 1, 256, FSC_PACK_F, "fsc_pack", nullptr, fsc_pack_kernel},
+    /* BF16_STRIP         */ {"hipFuncSetAttribute(fused_layer64s_bf16)", fused_layer64s_bf16_kernel<false>, 512, FB16_LDS_BYTES, 1, 256, FB16_PACK_F, "fb16_pack", fb16_pack_kernel, nullptr},
+    /* BF16_STRIP_BIAS    */ {"hipFuncSetAttribute(fused_layer64s_bf16<global>)", fused_layer64s_bf16_kernel<true>, 512, FB16_LDS_BYTES + GBIAS_LDS_BYTES, 1, 256, FB16_PACK_F, "fb16_pack", fb16_pack_kernel, nullptr},
+    /* BF16_STRIP_CTX     */ {"hipFuncSetAttribute(fused_layer64s_bf16_ctx)", fused_layer64s_bf16_kernel<false, true>, 512, FB16C_LDS_BYTES, 1, 256, FB16C_PACK_F, "fb16c_pack", nullptr, fb16c_pack_kernel},
+};
+// The z scratch of a call: the chosen form's L images from its start, FWD_IMG_STRIDE_F floats reserved per layer whatever
+// the form, then the head's images (sequence.hip; the backward's head images follow those).  The head's offset is
+// computed from this one stride, not from the chosen row, so it is the same address in every mode: no form's image
+// may be larger.
+constexpr int FWD_IMG_STRIDE_F = FS3_PACK_F > FSC_PACK_F ? FS3_PACK_F : FSC_PACK_F;
+static_assert(FS3_PACK_F <= FWD_IMG_STRIDE_F && FSC_PACK_F <= FWD_IMG_STRIDE_F && FB16_PACK_F <= FWD_IMG_STRIDE_F &&
+                  FB16C_PACK_F <= FWD_IMG_STRIDE_F,
+              "a layer image larger than the stride the head's image offset is computed from would overlap the head's");
+static_assert(FS3_PACK_LAYERS == GC_LAYERS, "fill_ctx_tables fills the pack kernels' and global_cond.h's tables alike");
+
+// The context-conv pointer tables of layers l0 .. l0 + n - 1 (the unused tail repeats the last layer): A is Fb16cPackArgs
+// or GlobalCondArgs
+template <class A>
+static void fill_ctx_tables(const mvn_params *p, int l0, int n, A *a) {
+  for (int i = 0; i < FS3_PACK_LAYERS; ++i) {
+    const int l = l0 + std::min(i, n - 1);
+    a->wcf[i] = p->ctx_filter_w[l]; a->wcg[i] = p->ctx_gate_w[l];
+    a->bcf[i] = p->ctx_filter_b[l]; a->bcg[i] = p->ctx_gate_b[l];
+  }
+}
+// the LDS images of layers 0 .. L-1 into `dst` (L x f.pack_f floats), one launch per 32 layers
+static int launch_layer_pack(const LayerForm &f, const mvn_params *p, int L, float *dst, hipStream_t s) {
   for (int l0 = 0; l0 < L; l0 += FS3_PACK_LAYERS) {
     const int n = std::min(FS3_PACK_LAYERS, L - l0);
     Fs3PackArgs pa;
@@ -340,54 +394,24 @@ static int launch_fb16_pack(const mvn_params *p, int L, float *dst, hipStream_t 
       pa.wf[i] = p->filter_w[l]; pa.wg[i] = p->gate_w[l]; pa.wr[i] = p->residual_w[l]; pa.ws[i] = p->skip_w[l];
       pa.br[i] = p->residual_b[l]; pa.bs[i] = p->skip_b[l];
     }
-    hipLaunchKernelGGL(fb16_pack_kernel, dim3(8, n), dim3(256), 0, s, pa, dst + (size_t)l0 * FB16_PACK_F);
-  }
-  return check_hip(hipGetLastError(), "fb16_pack");
-}
-static int launch_fb16c_pack(const mvn_params *p, int L, float *dst, hipStream_t s) {
-  for (int l0 = 0; l0 < L; l0 += FS3_PACK_LAYERS) {
-    const int n = std::min(FS3_PACK_LAYERS, L - l0);
-    Fs3PackArgs pa;
-    Fb16cPackArgs pc;
-    for (int i = 0; i < FS3_PACK_LAYERS; ++i) {
-      const int l = l0 + std::min(i, n - 1);
-      pa.wf[i] = p->filter_w[l]; pa.wg[i] = p->gate_w[l]; pa.wr[i] = p->residual_w[l]; pa.ws[i] = p->skip_w[l];
-      pa.br[i] = p->residual_b[l]; pa.bs[i] = p->skip_b[l];
-      pc.wcf[i] = p->ctx_filter_w[l]; pc.wcg[i] = p->ctx_gate_w[l]; pc.bcf[i] = p->ctx_filter_b[l]; pc.bcg[i] = p->ctx_gate_b[l];
+    float *const img = dst + (size_t)l0 * f.pack_f;
+    if (f.pack_ctx) {
+      Fb16cPackArgs pc;
+      fill_ctx_tables(p, l0, n, &pc);
+      hipLaunchKernelGGL(f.pack_ctx, dim3(8, n), dim3(256), 0, s, pa, pc, img);
+    } else {
+      hipLaunchKernelGGL(f.pack, dim3(8, n), dim3(256), 0, s, pa, img);
     }
-    hipLaunchKernelGGL(fb16c_pack_kernel, dim3(8, n), dim3(256), 0, s, pa, pc, dst + (size_t)l0 * FB16C_PACK_F);
   }
-  return check_hip(hipGetLastError(), "fb16c_pack");
+  return check_hip(hipGetLastError(), f.pack_what);
 }
-static int launch_fused_layer64s_bf16(const FusedFwdPArgs &a, int batch, hipStream_t s) {
+// one layer in form `f` (not the generic one); the caller has raised the kernel's dynamic-LDS limit (f.attr_what)
+static void launch_layer_form(const LayerForm &f, const FusedFwdPArgs &a, int batch, hipStream_t s) {
   const int nt = a.t_end - (a.t_begin & ~TILE_ALIGN);
-  if (a.t_end <= a.t_begin || batch <= 0) return MVN_OK;
+  if (a.t_end <= a.t_begin || batch <= 0) return;
   int chunks, chunk_t;
-  fb_chunks(nt, batch, 1, &chunks, &chunk_t, 256);  // a chunk: whole rounds of the 8 waves' strips
-  if (a.ctx.p) {  // conditioned layer: the 12-k-step image
-    if (a.gbias) {
-      set_error("fused_layer64s_bf16: a context and a label bias do not go together");
-      return MVN_ERR_BAD_ARG;
-    }
-    const void *fn = (const void *)fused_layer64s_bf16_kernel<false, true>;
-    const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(fused_layer64s_bf16_ctx)");
-    if (rc) return rc;
-    hipLaunchKernelGGL((fused_layer64s_bf16_kernel<false, true>), dim3(chunks * batch), dim3(512), FB16C_LDS_BYTES, s, a, chunks, chunk_t);
-    return MVN_OK;
-  }
-  if (a.gbias) {  // global conditioning: 128 more floats of LDS hold the sequence's bias vector
-    const void *fn = (const void *)fused_layer64s_bf16_kernel<true>;
-    const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(fused_layer64s_bf16<global>)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(fused_layer64s_bf16_kernel<true>, dim3(chunks * batch), dim3(512), FB16_LDS_BYTES + 128 * 4, s, a, chunks,
-                       chunk_t);
-    return MVN_OK;
-  }
-  const void *fn = (const void *)fused_layer64s_bf16_kernel<false>;
-  const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(fused_layer64s_bf16)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(fused_layer64s_bf16_kernel<false>, dim3(chunks * batch), dim3(512), FB16_LDS_BYTES, s, a, chunks, chunk_t);
-  return MVN_OK;
+  fb_chunks(nt, batch, f.per_cu, &chunks, &chunk_t, f.granule);
+  hipLaunchKernelGGL(f.kernel, dim3(chunks * batch), dim3(f.block), f.lds_bytes, s, a, chunks, chunk_t);
 }
 
 // ----------------------------------------------------------------------------------------

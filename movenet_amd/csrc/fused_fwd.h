@@ -557,23 +557,6 @@ __global__ __launch_bounds__(512, 1) void fused_layer64s_kernel(FusedFwdPArgs a,
   }
 }
 
-static int launch_fused_layer64s(const FusedFwdPArgs &a, int batch, hipStream_t s) {
-  const int nt = a.t_end - (a.t_begin & ~TILE_ALIGN);
-  if (a.t_end <= a.t_begin || batch <= 0) return MVN_OK;
-  int chunks, chunk_t;
-  fb_chunks(nt, batch, 1, &chunks, &chunk_t, 256);  // a chunk: whole rounds of the 8 waves' strips
-  const bool has_ctx = a.ctx.p != nullptr;
-  const void *fn = has_ctx ? (const void *)fused_layer64s_kernel<true> : (const void *)fused_layer64s_kernel<false>;
-  const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(fused_layer64s)");
-  if (rc) return rc;
-  const size_t lds = ((has_ctx ? 24576 : 16384) + 8192 + 256) * sizeof(float);
-  if (has_ctx)
-    hipLaunchKernelGGL(fused_layer64s_kernel<true>, dim3(chunks * batch), dim3(512), lds, s, a, chunks, chunk_t);
-  else
-    hipLaunchKernelGGL(fused_layer64s_kernel<false>, dim3(chunks * batch), dim3(512), lds, s, a, chunks, chunk_t);
-  return MVN_OK;
-}
-
 // ----------------------------------------------------------------------------------------
 // The strip form for the head's 1x1 convs with 64 x 256 weights (conv1 forward: 64 -> 256 rows,
 // leaky-ReLU in and out; its data gradient: 256 -> 64 rows through W^T, times the leaky-ReLU
@@ -691,26 +674,6 @@ static int launch_dense_strip(const DenseStripArgs &a, int m_total, int batch, h
   hipLaunchKernelGGL((dense_strip_kernel<K, M, IN, OUT, TRANSPOSED>), dim3(chunks * batch, m_total / M), dim3(512),
                      (K * M + M) * sizeof(float), s, a, chunks, chunk_t);
   return MVN_OK;
-}
-
-static int launch_fused_layer64p_t(const FusedFwdPArgs &a, int batch, hipStream_t s) {
-  constexpr int TT = 32, LDS_BYTES = (2 * 128 + 3 * 64) * (TT + 4) * (int)sizeof(float);
-  const int nt = a.t_end - (a.t_begin & ~TILE_ALIGN);
-  if (a.t_end <= a.t_begin || batch <= 0) return MVN_OK;
-  int chunks, chunk_t;
-  fb_chunks(nt, batch, 2, &chunks, &chunk_t, TT);  // one round of workgroups (fused_bwd.h)
-  const int rc = ensure_max_dynamic_lds((const void *)fused_layer64p_kernel, "hipFuncSetAttribute(fused_layer64p)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(fused_layer64p_kernel, dim3(chunks * batch), dim3(256), LDS_BYTES, s, a, chunks, chunk_t);
-  return MVN_OK;
-}
-// The strip kernel is the default; MOVENET_HIP_FORWARD_TILE (any value) selects the tile kernel (tests)
-static int launch_fused_layer64p(const FusedFwdPArgs &a, int batch, hipStream_t s) {
-  if (a.ctx.p) return launch_fused_layer64s(a, batch, s);  // conditioned: the strip kernel only (the caller checks the row length)
-  // (the strip kernel's buffer resources span 2 GB from a sequence's base: rows of more than 4 M
-  // columns -- 25 x the reference's MAX_AUDIO_FRAMES -- go to the tile kernel)
-  if (switches().forward_tile || a.xin.ld > (1 << 22) || a.skip.ld > (1 << 22)) return launch_fused_layer64p_t(a, batch, s);
-  return launch_fused_layer64s(a, batch, s);
 }
 
 }  // namespace mvn

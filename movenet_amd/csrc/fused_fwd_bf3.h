@@ -149,6 +149,11 @@ struct Fs3PackArgs {
   const float *wf[FS3_PACK_LAYERS], *wg[FS3_PACK_LAYERS], *wr[FS3_PACK_LAYERS], *ws[FS3_PACK_LAYERS];
   const float *br[FS3_PACK_LAYERS], *bs[FS3_PACK_LAYERS];
 };
+// the context convs of the same layers, for the pack kernels of the conditioned forms (fsc_pack_kernel below,
+// fb16c_pack_kernel in fused_bf16.h)
+struct Fb16cPackArgs {
+  const float *wcf[FS3_PACK_LAYERS], *wcg[FS3_PACK_LAYERS], *bcf[FS3_PACK_LAYERS], *bcg[FS3_PACK_LAYERS];
+};
 __global__ __launch_bounds__(256) void fs3_pack_kernel(Fs3PackArgs p, float *dst) {
   const int l = blockIdx.y;
   fs3_stage_weights((unsigned char *)(dst + (size_t)l * FS3_PACK_F), p.wf[l], p.wg[l], p.wr[l], p.ws[l], p.br[l], p.bs[l],
@@ -376,12 +381,7 @@ constexpr int FSC_XD_BYTES = 4 * 4 * 3 * 1024;                               // 
 constexpr int FSC_W1_BYTES = 4 * 16 * 1024;                                  // [4 blocks][16 k-step groups][64 lanes][4] floats
 constexpr int FSC_LDS_BYTES = FSC_XD_BYTES + FSC_W1_BYTES + FS3_W2_BYTES, FSC_PACK_F = FSC_LDS_BYTES / 4;
 static_assert(FSC_LDS_BYTES == 160 * 1024, "the conditioned layer's image fills a CU's LDS");
-struct FscPackArgs {
-  const float *wf[FS3_PACK_LAYERS], *wg[FS3_PACK_LAYERS], *wr[FS3_PACK_LAYERS], *ws[FS3_PACK_LAYERS];
-  const float *br[FS3_PACK_LAYERS], *bs[FS3_PACK_LAYERS];
-  const float *wcf[FS3_PACK_LAYERS], *wcg[FS3_PACK_LAYERS], *bcf[FS3_PACK_LAYERS], *bcg[FS3_PACK_LAYERS];
-};
-__global__ __launch_bounds__(256) void fsc_pack_kernel(FscPackArgs p, float *dst) {
+__global__ __launch_bounds__(256) void fsc_pack_kernel(Fs3PackArgs p, Fb16cPackArgs c, float *dst) {
   const int l = blockIdx.y, tid = blockIdx.x * 256 + threadIdx.x, nthreads = gridDim.x * 256;
   unsigned char *img = (unsigned char *)(dst + (size_t)l * FSC_PACK_F);
   unsigned short *XD = (unsigned short *)img;
@@ -410,7 +410,7 @@ __global__ __launch_bounds__(256) void fsc_pack_kernel(FscPackArgs p, float *dst
     const int kc = r & 63, cm = r >> 6;
     const int lhs = (kc >> 2) & 1, kk = 32 + (kc & 3) + 4 * (kc >> 3);
     const int blk = 2 * g + (cm >> 5), ln = (cm & 31) + 32 * lhs;
-    W1[((blk * NK1 + (kk >> 2)) * 64 + ln) * 4 + (kk & 3)] = (g ? p.wcg[l] : p.wcf[l])[r];
+    W1[((blk * NK1 + (kk >> 2)) * 64 + ln) * 4 + (kk & 3)] = (g ? c.wcg[l] : c.wcf[l])[r];
   }
   for (int sI = tid; sI < 2 * 4096; sI += nthreads) {  // residual | skip as planes (fs3_stage_weights' layout)
     const int g = sI >> 12, r = sI & 4095;
@@ -668,33 +668,6 @@ __global__ __launch_bounds__(512, 1) void fused_layer64s_ctxw2_kernel(FusedFwdPA
   }
 }
 
-
-static int launch_fsc_pack(const mvn_params *p, int L, float *dst, hipStream_t s) {
-  for (int l0 = 0; l0 < L; l0 += FS3_PACK_LAYERS) {
-    const int n = std::min(FS3_PACK_LAYERS, L - l0);
-    FscPackArgs pa;
-    for (int i = 0; i < FS3_PACK_LAYERS; ++i) {
-      const int l = l0 + std::min(i, n - 1);
-      pa.wf[i] = p->filter_w[l]; pa.wg[i] = p->gate_w[l]; pa.wr[i] = p->residual_w[l]; pa.ws[i] = p->skip_w[l];
-      pa.br[i] = p->residual_b[l]; pa.bs[i] = p->skip_b[l];
-      pa.wcf[i] = p->ctx_filter_w[l]; pa.wcg[i] = p->ctx_gate_w[l]; pa.bcf[i] = p->ctx_filter_b[l]; pa.bcg[i] = p->ctx_gate_b[l];
-    }
-    hipLaunchKernelGGL(fsc_pack_kernel, dim3(8, n), dim3(256), 0, s, pa, dst + (size_t)l0 * FSC_PACK_F);
-  }
-  return check_hip(hipGetLastError(), "fsc_pack");
-}
-static int launch_fused_layer64s_ctxw2(const FusedFwdPArgs &a, int batch, hipStream_t s) {
-  const int nt = a.t_end - (a.t_begin & ~TILE_ALIGN);
-  if (a.t_end <= a.t_begin || batch <= 0) return MVN_OK;
-  int chunks, chunk_t;
-  fb_chunks(nt, batch, 1, &chunks, &chunk_t, 256);
-  const void *fn = (const void *)fused_layer64s_ctxw2_kernel;
-  const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(fused_layer64s_ctxw2)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(fused_layer64s_ctxw2_kernel, dim3(chunks * batch), dim3(512), FSC_LDS_BYTES, s, a, chunks, chunk_t);
-  return MVN_OK;
-}
-
 // ----------------------------------------------------------------------------------------
 // The head's two forward convolutions (dense_strip_kernel, fused_fwd.h) in the same form: weights as three bf16
 // planes in LDS -- K x M x 6 bytes, 96 KB for conv1 (64 -> 256 rows, all of them in one workgroup) and for conv2
@@ -853,40 +826,5 @@ constexpr size_t DS3_BWD_IMG_F = 4 * DS3_IMG2_F + DS3_IMG2_F;  // backward: conv
 
 // MOVENET_HIP_FORWARD_MFMA=f32 keeps the fp32-MFMA strip kernel and the head's fp32 kernels (tests); common.h: Switches
 static bool forward_bf3_enabled() { return !switches().forward_f32; }
-
-// the LDS images of layers 0 .. L-1 into `dst` (L x FS3_PACK_F floats), one launch per 32 layers
-static int launch_fs3_pack(const mvn_params *p, int L, float *dst, hipStream_t s) {
-  for (int l0 = 0; l0 < L; l0 += FS3_PACK_LAYERS) {
-    const int n = std::min(FS3_PACK_LAYERS, L - l0);
-    Fs3PackArgs pa;
-    for (int i = 0; i < FS3_PACK_LAYERS; ++i) {
-      const int l = l0 + std::min(i, n - 1);
-      pa.wf[i] = p->filter_w[l]; pa.wg[i] = p->gate_w[l]; pa.wr[i] = p->residual_w[l]; pa.ws[i] = p->skip_w[l];
-      pa.br[i] = p->residual_b[l]; pa.bs[i] = p->skip_b[l];
-    }
-    hipLaunchKernelGGL(fs3_pack_kernel, dim3(8, n), dim3(256), 0, s, pa, dst + (size_t)l0 * FS3_PACK_F);
-  }
-  return check_hip(hipGetLastError(), "fs3_pack");
-}
-
-static int launch_fused_layer64s_bf3(const FusedFwdPArgs &a, int batch, hipStream_t s) {
-  const int nt = a.t_end - (a.t_begin & ~TILE_ALIGN);
-  if (a.t_end <= a.t_begin || batch <= 0) return MVN_OK;
-  int chunks, chunk_t;
-  fb_chunks(nt, batch, 1, &chunks, &chunk_t, 256);  // a chunk: whole rounds of the 8 waves' strips
-  if (a.gbias) {  // global conditioning: 128 more floats of LDS hold the sequence's bias vector
-    const void *fn = (const void *)fused_layer64s_bf3_kernel<true>;
-    const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(fused_layer64s_bf3<global>)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(fused_layer64s_bf3_kernel<true>, dim3(chunks * batch), dim3(512), FS3_LDS_BYTES + 128 * 4, s, a, chunks,
-                       chunk_t);
-    return MVN_OK;
-  }
-  const void *fn = (const void *)fused_layer64s_bf3_kernel<false>;
-  const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(fused_layer64s_bf3)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(fused_layer64s_bf3_kernel<false>, dim3(chunks * batch), dim3(512), FS3_LDS_BYTES, s, a, chunks, chunk_t);
-  return MVN_OK;
-}
 
 }  // namespace mvn

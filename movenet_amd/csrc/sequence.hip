@@ -1059,13 +1059,10 @@ static int head_bwd1_bf3(const DenseStripArgs &da, const mvn_params *p, int Kc, 
   (Q == 256 ? call_<256> : Q == 128 ? call_<128> : call_<64>)
 static bool head_q_strip(int Q) { return Q == 256 || Q == 128 || Q == 64; }
 
-// Global conditioning, fast path (global_cond.h): what the forward's strip kernel and the backward's scatter form need.
-// Decided from the dims, the switches and the sizes of the caller's buffers alone, so that mvn_global_fast_path can
-// answer before anything is allocated; anything else takes the general path (the label as a constant context).
-static bool global_forward_fast(const Geometry &g) {
-  return g.C == FP_C && g.Kc == FP_C && !switches().no_fused_forward && forward_bf3_enabled() && !switches().forward_tile &&
-         g.Tp <= (1 << 22) && g.Sp <= (1 << 22);
-}
+// Global conditioning, fast path (global_cond.h): what the backward's scatter form needs (the forward's half is
+// global_forward_fast, behind plan_forward).  Decided from the dims, the switches and the sizes of the caller's buffers
+// alone, so that mvn_global_fast_path can answer before anything is allocated; anything else takes the general path
+// (the label as a constant context).
 static bool global_backward_fast(const mvn_dims *dims, const Geometry &g, int batch) {
   if (g.C != 64 || g.Kc != 64 || switches().no_fused_backward || switches().bwd_split || !rows_fit_rsrc(2 * g.C, g.Tp) ||
       g.L >= 4095 || g.Tp > (1 << 21))
@@ -1101,13 +1098,6 @@ static size_t global_bf16_wgs(const mvn_dims *dims, const Geometry &g, int batch
 }
 static size_t global_bf16_scratch_floats(const mvn_dims *dims, const Geometry &g, int batch) {
   return global_bf16_wgs(dims, g, batch) * GC16_PER_WG;
-}
-static void global_cond_tables(const mvn_params *p, int l0, int n, GlobalCondArgs *ga) {
-  for (int i = 0; i < GC_LAYERS; ++i) {
-    const int l = l0 + std::min(i, n - 1);
-    ga->wcf[i] = p->ctx_filter_w[l]; ga->wcg[i] = p->ctx_gate_w[l];
-    ga->bcf[i] = p->ctx_filter_b[l]; ga->bcg[i] = p->ctx_gate_b[l];
-  }
 }
 
 // What one full-sequence pass runs: every extern "C" entry point below fills one in and hands it to forward_impl /
@@ -1167,6 +1157,51 @@ template <class P> static bool has_ctx_convs(const P *p) {
   return p && p->ctx_filter_w && p->ctx_filter_b && p->ctx_gate_w && p->ctx_gate_b;
 }
 
+// The forward's kernel forms, decided once per call: the layers' row of LAYER_FORMS (fused_bf16.h), whether the z scratch
+// (`z_floats`) holds the row's L weight images (the kernels convert the weights themselves where it does not; the ctxw2
+// form has no such fall-back and is not chosen then), and the forms of the head's two convolutions.  forward_impl
+// launches what this says; the queries ask it as well.
+enum HeadForm { HEAD_GENERIC, HEAD_F32_STRIP, HEAD_BF3_STRIP };  // gemm_family.h; fused_fwd.h, Q = 256; fused_fwd_bf3.h
+struct FwdPlan {
+  const LayerForm *layer;
+  bool packed;
+  HeadForm head1, head2;  // (both or neither HEAD_BF3_STRIP)
+  size_t head_off;        // HEAD_BF3_STRIP: the head's images in the z scratch, behind the layers' (FWD_IMG_STRIDE_F)
+};
+static FwdPlan plan_forward(const SeqMode &m, const Geometry &g, bool has_ctx, int ctx_ld, const Switches &sw, size_t z_floats) {
+  const bool f16 = m.precision == SeqMode::F16, glob = m.conditioning == SeqMode::GLOBAL;
+  // the bf16 x 3 forms, unless a tile form / the fp32-MFMA strip was asked for; the strip kernels' buffer resources span
+  // 2 GB from a sequence's base: rows of more than 4 M columns -- 25 x the reference's MAX_AUDIO_FRAMES -- go to the tile kernel
+  const bool planes = !sw.forward_f32 && !sw.forward_tile, rows_fit = g.Tp <= (1 << 22) && g.Sp <= (1 << 22);
+  LayerFormId id = FORM_GENERIC;
+  if (m.precision == SeqMode::BF16) {  // (mode_supported has checked the dims and the row lengths; no switch is consulted)
+    id = has_ctx ? FORM_BF16_STRIP_CTX : glob ? FORM_BF16_STRIP_BIAS : FORM_BF16_STRIP;
+  } else if (g.C == FP_C && g.Kc == FP_C && !f16 && !sw.no_fused_forward) {  // fp32, C = K = 64: the layer as ONE kernel
+    if (!has_ctx)
+      id = planes && rows_fit ? (glob ? FORM_BF3_STRIP_BIAS : FORM_BF3_STRIP) : sw.forward_tile || !rows_fit ? FORM_F32_TILE : FORM_F32_STRIP;
+    else if (g.Tp <= (1 << 22) && ctx_ld <= (1 << 22))  // conditioned: the strip kernels only
+      id = planes && z_floats >= (size_t)g.L * FSC_PACK_F ? FORM_CTXW2_STRIP : FORM_F32_STRIP_CTX;
+  }
+  FwdPlan pl;
+  pl.layer = &LAYER_FORMS[id];
+  pl.packed = pl.layer->pack_f && z_floats >= (size_t)g.L * pl.layer->pack_f;
+  // the head's strips address a sequence's (Q, Sp) / (Kc, Sp) rows with 32-bit offsets (common.h rows_fit_rsrc)
+  const bool strip_ok = !f16 && rows_fit_rsrc(g.Q, g.Sp);
+  pl.head_off = (size_t)g.L * FWD_IMG_STRIDE_F;
+  if (strip_ok && g.Kc == 64 && head_q_strip(g.Q) && !sw.forward_f32 && z_floats >= pl.head_off + DS3_IMG_F) {
+    pl.head1 = pl.head2 = HEAD_BF3_STRIP;
+  } else {
+    pl.head1 = strip_ok && g.Kc == 64 && g.Q == 256 ? HEAD_F32_STRIP : HEAD_GENERIC;
+    pl.head2 = strip_ok && g.Q == 256 ? HEAD_F32_STRIP : HEAD_GENERIC;
+  }
+  return pl;
+}
+// Global conditioning, fast path: the fp32 forward adds the label's bias in one form only
+static bool global_forward_fast(const Geometry &g) {
+  const SeqMode m = {SeqMode::F32, SeqMode::GLOBAL, "mvn_forward_global"};
+  return plan_forward(m, g, false, 0, switches(), (size_t)g.act).layer == &LAYER_FORMS[FORM_BF3_STRIP_BIAS];
+}
+
 extern "C" {
 
 int mvn_padded_len(int n) { return n <= 0 ? 0 : (n + 63) / 64 * 64; }
@@ -1195,7 +1230,10 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
     set_error("mvn_forward: context given without context-conv parameters / ctx_ld < t_len");
     return MVN_ERR_BAD_ARG;
   }
-  if (gbias && !bf16 && (buf->ctx || !global_forward_fast(g))) {
+  const bool has_ctx = buf->ctx != nullptr;
+  const FwdPlan pl = plan_forward(m, g, has_ctx, buf->ctx_ld, switches(), (size_t)g.act);  // (z: one (B, C, Tp) tensor)
+  const LayerForm &form = *pl.layer;
+  if (gbias && !bf16 && &form != &LAYER_FORMS[FORM_BF3_STRIP_BIAS]) {  // (a context, or !global_forward_fast(g))
     set_error("mvn_forward_global: needs residual = skip channels = 64, no context and the bf16 x 3 strip kernel "
               "(mvn_global_fast_path)");
     return MVN_ERR_UNSUPPORTED;
@@ -1204,6 +1242,10 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
   hipStream_t s = (hipStream_t)stream_;
   const int C = g.C, Kc = g.Kc, Q = g.Q, T = g.T;
   const int t_skip0 = g.rf - 1;
+  if (form.kernel) {
+    rc = ensure_max_dynamic_lds((const void *)form.kernel, form.attr_what);
+    if (rc) return rc;
+  }
 
   Act x0 = act_view(buf->acts, batch, C, g.Tp);
   if (buf->dense_audio) {
@@ -1222,179 +1264,88 @@ static int forward_impl(const mvn_dims *dims, const mvn_params *p, const int32_t
   }
   Act zv = act_view(buf->z, batch, C, g.Tp);
   Act skipv = act_view(buf->skip, batch, Kc, g.Sp);
-  const bool has_ctx = buf->ctx != nullptr;
   Act ctxv = act_view(const_cast<float *>(buf->ctx), batch, C, has_ctx ? buf->ctx_ld : 0);
+  // the layers' weights as LDS images (the form's layout), written once per call into the z scratch, which the
+  // one-kernel forms never touch otherwise: z stays in registers
+  if (pl.packed) {
+    rc = launch_layer_pack(form, p, g.L, buf->z, s);
+    if (rc) return rc;
+  }
   int A = 0;  // first valid time of the current layer's input
   for (int l = 0; l < g.L; ++l) {
     const int d = dilation_of(dims, l);
     const int src = save ? l : (l & 1), dst = save ? l + 1 : ((l + 1) & 1);
     Act xin = act_view(buf->acts + (size_t)src * g.act, batch, C, g.Tp);
     Act xout = act_view(buf->acts + (size_t)dst * g.act, batch, C, g.Tp);
+    if (l == g.L - 1) xout.p = nullptr;  // the last residual output is never used
+    const Act th = act_view(save ? buf->th + (size_t)l * g.act : nullptr, batch, C, g.Tp);
+    const Act sg = act_view(save ? buf->sg + (size_t)l * g.act : nullptr, batch, C, g.Tp);
+    if (form.kernel) {  // the layer as ONE kernel (MOVENET_HIP_NO_FUSED_FORWARD=1 keeps the two-kernel form below: tests)
+      FusedFwdPArgs fp;
+      fp.t_begin = A + d; fp.t_end = T; fp.d = d; fp.t_skip0 = t_skip0; fp.t_base = g.t_base;
+      fp.first_layer = (l == 0);
+      fp.wf = p->filter_w[l]; fp.wg = p->gate_w[l]; fp.wr = p->residual_w[l]; fp.ws = p->skip_w[l];
+      fp.br = p->residual_b[l]; fp.bs = p->skip_b[l];
+      fp.xin = xin; fp.xout = xout; fp.skip = skipv; fp.th = th; fp.sg = sg;
+      if (has_ctx) {  // conditioned layer: the context as a third K block
+        fp.wcf = p->ctx_filter_w[l]; fp.wcg = p->ctx_gate_w[l]; fp.bcf = p->ctx_filter_b[l]; fp.bcg = p->ctx_gate_b[l];
+        fp.ctx = ctxv;
+      }
+      if (gbias) fp.gbias = gbias + (size_t)l * batch * 128;  // (global conditioning: f | g start from the label's term)
+      if (pl.packed) fp.wpack = buf->z + (size_t)l * form.pack_f;
+      launch_layer_form(form, fp, batch, s);
+      A += d;
+      continue;
+    }
     auto run_fg = [&](auto f) {
       f.K = has_ctx ? 3 * C : 2 * C; f.t_begin = A + d; f.t_end = T; f.C = C; f.d = d;
       f.wf = p->filter_w[l]; f.wg = p->gate_w[l];
       f.wcf = has_ctx ? p->ctx_filter_w[l] : nullptr; f.wcg = has_ctx ? p->ctx_gate_w[l] : nullptr;
       f.bcf = has_ctx ? p->ctx_filter_b[l] : nullptr; f.bcg = has_ctx ? p->ctx_gate_b[l] : nullptr;
       f.ctx = ctxv;
-      f.xin = xin; f.z = zv;
-      f.th = act_view(save ? buf->th + (size_t)l * g.act : nullptr, batch, C, g.Tp);
-      f.sg = act_view(save ? buf->sg + (size_t)l * g.act : nullptr, batch, C, g.Tp);
+      f.xin = xin; f.z = zv; f.th = th; f.sg = sg;
       launch_gemm_staged(f, 2 * ((C + 31) / 32 * 32), batch, s, f16);
     };
-    // bf16 operands (fused_bf16.h): the strip kernel with one-plane weight images, packed once per call into the z
-    // scratch when it holds them (mode_supported has checked the dims and the row lengths)
-    if (bf16) {
-      FusedFwdPArgs fp;
-      fp.t_begin = A + d; fp.t_end = T; fp.d = d; fp.t_skip0 = t_skip0; fp.t_base = g.t_base;
-      fp.first_layer = (l == 0);
-      fp.wf = p->filter_w[l]; fp.wg = p->gate_w[l]; fp.wr = p->residual_w[l]; fp.ws = p->skip_w[l];
-      fp.br = p->residual_b[l]; fp.bs = p->skip_b[l];
-      fp.xin = xin; fp.xout = xout; fp.skip = skipv;
-      if (l == g.L - 1) fp.xout.p = nullptr;  // the last residual output is never used
-      fp.th = act_view(save ? buf->th + (size_t)l * g.act : nullptr, batch, C, g.Tp);
-      fp.sg = act_view(save ? buf->sg + (size_t)l * g.act : nullptr, batch, C, g.Tp);
-      if (has_ctx) {  // (ctx16: the conditioned form, its image 12 k-steps per f | g block)
-        fp.wcf = p->ctx_filter_w[l]; fp.wcg = p->ctx_gate_w[l]; fp.bcf = p->ctx_filter_b[l]; fp.bcg = p->ctx_gate_b[l];
-        fp.ctx = ctxv;
-        if ((size_t)g.act >= (size_t)g.L * FB16C_PACK_F) {
-          if (l == 0) {
-            const int rc3 = launch_fb16c_pack(p, g.L, buf->z, s);
-            if (rc3) return rc3;
-          }
-          fp.wpack = buf->z + (size_t)l * FB16C_PACK_F;
-        }
-      } else if ((size_t)g.act >= (size_t)g.L * FB16_PACK_F) {
-        if (l == 0) {
-          const int rc3 = launch_fb16_pack(p, g.L, buf->z, s);
-          if (rc3) return rc3;
-        }
-        fp.wpack = buf->z + (size_t)l * FB16_PACK_F;
-      }
-      if (gbias) fp.gbias = gbias + (size_t)l * batch * 128;  // (global conditioning: f | g start from the label's term)
-      const int rc2 = launch_fused_layer64s_bf16(fp, batch, s);
-      if (rc2) return rc2;
-      A += d;
-      continue;
-    }
-    // C = K = 64, fp32: the layer as ONE kernel (a strip kernel of fused_fwd_bf3.h / fused_fwd.h, or the tile
-    // kernel of fused_fwd.h); MOVENET_HIP_NO_FUSED_FORWARD=1 keeps the two-kernel form below (tests)
-    if (C == FP_C && Kc == FP_C && !f16 && !switches().no_fused_forward &&
-        (!has_ctx || (g.Tp <= (1 << 22) && buf->ctx_ld <= (1 << 22)))) {
-      FusedFwdPArgs fp;
-      if (has_ctx) {  // conditioned layer: the strip kernel with the context as a third K block
-        fp.wcf = p->ctx_filter_w[l]; fp.wcg = p->ctx_gate_w[l]; fp.bcf = p->ctx_filter_b[l]; fp.bcg = p->ctx_gate_b[l];
-        fp.ctx = ctxv;
-      }
-      fp.t_begin = A + d; fp.t_end = T; fp.d = d; fp.t_skip0 = t_skip0; fp.t_base = g.t_base;
-      fp.first_layer = (l == 0);
-      fp.wf = p->filter_w[l]; fp.wg = p->gate_w[l]; fp.wr = p->residual_w[l]; fp.ws = p->skip_w[l];
-      fp.br = p->residual_b[l]; fp.bs = p->skip_b[l];
-      fp.xin = xin; fp.xout = xout; fp.skip = skipv;
-      if (l == g.L - 1) fp.xout.p = nullptr;  // the last residual output is never used
-      fp.th = act_view(save ? buf->th + (size_t)l * g.act : nullptr, batch, C, g.Tp);
-      fp.sg = act_view(save ? buf->sg + (size_t)l * g.act : nullptr, batch, C, g.Tp);
-      if (gbias) fp.gbias = gbias + (size_t)l * batch * 128;  // (global conditioning: the instantiation with the bias add)
-      // audio-only layers: the strip kernel on the bf16 matrix cores (fp32 = 3 bf16 planes, fused_fwd_bf3.h)
-      // unless a tile form / the fp32-MFMA strip was asked for, or the rows are longer than a buffer resource spans
-      const bool bf3 = !fp.ctx.p && forward_bf3_enabled() && !switches().forward_tile &&
-                       fp.xin.ld <= (1 << 22) && fp.skip.ld <= (1 << 22);
-      if (bf3 && (size_t)g.act >= (size_t)g.L * FS3_PACK_F) {
-        // the layers' weights as LDS images (three bf16 planes, the kernel's layout), written once per call into
-        // the z scratch, which this path never touches otherwise: z stays in registers
-        if (l == 0) {
-          const int rc3 = launch_fs3_pack(p, g.L, buf->z, s);
-          if (rc3) return rc3;
-        }
-        fp.wpack = buf->z + (size_t)l * FS3_PACK_F;
-      }
-      // conditioned layers: the strip kernel with its residual | skip product on the bf16 matrix cores and a packed
-      // weight image (same switches; the image needs the z scratch)
-      const bool ctxw2 = fp.ctx.p && forward_bf3_enabled() && !switches().forward_tile &&
-                         (size_t)g.act >= (size_t)g.L * FSC_PACK_F;
-      if (ctxw2) {
-        if (l == 0) {
-          const int rc3 = launch_fsc_pack(p, g.L, buf->z, s);
-          if (rc3) return rc3;
-        }
-        fp.wpack = buf->z + (size_t)l * FSC_PACK_F;
-        const int rc3 = launch_fused_layer64s_ctxw2(fp, batch, s);
-        if (rc3) return rc3;
-        A += d;
-        continue;
-      }
-      const int rc2 = bf3 ? launch_fused_layer64s_bf3(fp, batch, s) : launch_fused_layer64p(fp, batch, s);
-      if (rc2) return rc2;
-      A += d;
-      continue;
-    }
     if (has_ctx) run_fg(FgOpT<true>()); else run_fg(FgOpT<false>());
     RsOp r;
     r.K = C; r.t_begin = A + d; r.t_end = T; r.C = C; r.Kc = Kc; r.t_skip0 = t_skip0;
     r.t_base = g.t_base;
     r.wr = p->residual_w[l]; r.br = p->residual_b[l]; r.ws = p->skip_w[l]; r.bs = p->skip_b[l];
     r.z = zv; r.xin = xin; r.xout = xout; r.skip = skipv; r.first_layer = (l == 0);
-    if (l == g.L - 1) r.xout.p = nullptr;  // the last residual output is never used
     launch_gemm_staged(r, C + Kc, batch, s, f16);
     A += d;
   }
-  // head: a1 = lrelu(W1 lrelu(skip) + b1); logits = W2 a1 + b2   (columns s = 0..S-1)
+  // head: a1 = lrelu(W1 lrelu(skip) + b1); logits = W2 a1 + b2   (columns s = 0..S-1), each convolution in the plan's
+  // form: strips on the bf16 matrix cores, their LDS images packed once per call behind the layers' in the z scratch
+  // (fused_fwd_bf3.h); the fp32 strips at Q = 256, which read their input once / twice (fused_fwd.h); the generic kernel
   Act a1v = act_view(buf->a1, batch, Q, g.Sp);
-  float *head_img = nullptr;  // LDS images of the two head convolutions (bf16 planes), when the bf16 x 3 strips run
+  float *const head_img = pl.head1 == HEAD_BF3_STRIP ? buf->z + pl.head_off : nullptr;
+  auto run_dense = [&](auto h, const DenseStripArgs &da, int K, int aligned_out) {
+    h.K = K; h.M = Q; h.t_begin = da.t_begin; h.t_end = da.t_end; h.t_out_end = da.t_out_end; h.aligned_out = aligned_out;
+    h.wmat = da.wmat; h.ldw = da.ldw; h.bias = da.bias; h.xin = da.xin; h.yout = da.yout; h.ref = da.ref;
+    launch_gemm_staged(h, Q, batch, s, f16);
+    return MVN_OK;
+  };
   {
-    DenseOp<IN_LRELU, OUT_BIAS_LRELU, false> h1;
-    h1.K = Kc; h1.t_begin = g.pad; h1.t_end = g.pad + g.S; h1.M = Q; h1.wmat = p->head1_w;
-    h1.ldw = Kc; h1.bias = p->head1_b; h1.xin = skipv; h1.yout = a1v; h1.ref = a1v;
-    h1.t_out_end = g.pad + g.S; h1.aligned_out = 1;
-    // Q = 256, K = 64: the strip form reads the skip sum once (fused_fwd.h)
-    // (the strip kernels address a sequence's (Q, Sp) / (Kc, Sp) rows with 32-bit offsets: common.h rows_fit_rsrc)
-    const bool strip_ok = Kc == 64 && !f16 && rows_fit_rsrc(Q, g.Sp);
-    const bool strip = strip_ok && Q == 256;  // (the fp32 strips: Q = 256 only)
-    // r3: both head convolutions as strip kernels on the bf16 matrix cores (fused_fwd_bf3.h), their LDS images
-    // packed once per call behind the layers' in the z scratch
-    const size_t img_off = (size_t)g.L * std::max(FS3_PACK_F, FSC_PACK_F);
-    if (strip_ok && head_q_strip(Q) && forward_bf3_enabled() && (size_t)g.act >= img_off + DS3_IMG_F)
-      head_img = buf->z + img_off;
-    if (head_img) {
-      DenseStripArgs da;
-      da.t_begin = h1.t_begin; da.t_end = h1.t_end; da.t_out_end = h1.t_out_end;
-      da.wmat = p->head1_w; da.ldw = Kc; da.bias = p->head1_b; da.xin = skipv; da.yout = a1v; da.ref = a1v;
-      const int rc2 = MVN_HEAD_Q(head_fwd1_bf3)(da, p, Kc, head_img, batch, s);
-      if (rc2) return rc2;
-    } else if (strip) {
-      DenseStripArgs da;
-      da.t_begin = g.pad; da.t_end = g.pad + g.S; da.t_out_end = g.pad + g.S;
-      da.wmat = p->head1_w; da.ldw = Kc; da.bias = p->head1_b; da.xin = skipv; da.yout = a1v; da.ref = a1v;
-      const int rc2 = launch_dense_strip<64, 256, IN_LRELU, OUT_BIAS_LRELU, false>(da, Q, batch, s);
-      if (rc2) return rc2;
-    } else {
-      launch_gemm_staged(h1, Q, batch, s, f16);
-    }
+    DenseStripArgs da;
+    da.t_begin = g.pad; da.t_end = g.pad + g.S; da.t_out_end = g.pad + g.S;
+    da.wmat = p->head1_w; da.ldw = Kc; da.bias = p->head1_b; da.xin = skipv; da.yout = a1v; da.ref = a1v;
+    rc = pl.head1 == HEAD_BF3_STRIP   ? MVN_HEAD_Q(head_fwd1_bf3)(da, p, Kc, head_img, batch, s)
+         : pl.head1 == HEAD_F32_STRIP ? launch_dense_strip<64, 256, IN_LRELU, OUT_BIAS_LRELU, false>(da, Q, batch, s)
+                                      : run_dense(DenseOp<IN_LRELU, OUT_BIAS_LRELU, false>(), da, Kc, 1);
+    if (rc) return rc;
   }
   if (S_out > 0) {
-    DenseOp<IN_ID, OUT_BIAS, false> h2;
-    h2.K = Q; h2.t_begin = g.pad; h2.t_end = g.pad + g.S; h2.M = Q; h2.wmat = p->head2_w; h2.ldw = Q;
-    h2.bias = p->head2_b; h2.xin = a1v; h2.ref = a1v;
+    DenseStripArgs da;
+    da.t_begin = g.pad; da.t_end = g.pad + g.S; da.t_out_end = g.pad + S_out;
+    da.wmat = p->head2_w; da.ldw = Q; da.bias = p->head2_b; da.xin = a1v; da.ref = a1v;
     // `out` is the caller's contiguous (B, Q, S_out): column s of the head = out column s - pad
-    h2.yout = act_view(out - g.pad, batch, Q, S_out);
-    h2.t_out_end = g.pad + S_out; h2.aligned_out = 0;
-    const bool strip2 = Q == 256 && !f16 && rows_fit_rsrc(Q, g.Sp);
-    if (head_img && S_out > 0) {
-      // four row blocks of 64 on the bf16 matrix cores (fused_fwd_bf3.h)
-      DenseStripArgs da;
-      da.t_begin = h2.t_begin; da.t_end = h2.t_end; da.t_out_end = h2.t_out_end;
-      da.wmat = p->head2_w; da.ldw = Q; da.bias = p->head2_b; da.xin = a1v; da.yout = h2.yout; da.ref = a1v;
-      const int rc2 = MVN_HEAD_Q(head_fwd2_bf3)(da, head_img, batch, s);
-      if (rc2) return rc2;
-    } else if (strip2) {
-      // two row blocks of 128: a1 is read twice instead of once per 64-row block (four times)
-      DenseStripArgs da;
-      da.t_begin = h2.t_begin; da.t_end = h2.t_end; da.t_out_end = h2.t_out_end;
-      da.wmat = p->head2_w; da.ldw = Q; da.bias = p->head2_b; da.xin = a1v; da.yout = h2.yout; da.ref = a1v;
-      const int rc2 = launch_dense_strip<256, 128, IN_ID, OUT_BIAS, false>(da, Q, batch, s);
-      if (rc2) return rc2;
-    } else {
-      launch_gemm_staged(h2, Q, batch, s, f16);
-    }
+    da.yout = act_view(out - g.pad, batch, Q, S_out);
+    // bf16 x 3: four row blocks of 64; fp32 strips: two of 128 (a1 is read twice instead of once per 64-row block)
+    rc = pl.head2 == HEAD_BF3_STRIP   ? MVN_HEAD_Q(head_fwd2_bf3)(da, head_img, batch, s)
+         : pl.head2 == HEAD_F32_STRIP ? launch_dense_strip<256, 128, IN_ID, OUT_BIAS, false>(da, Q, batch, s)
+                                      : run_dense(DenseOp<IN_ID, OUT_BIAS, false>(), da, Q, 0);
+    if (rc) return rc;
     if (normalize) {
       if (Q <= 4 * CQ && rows_fit_rsrc(Q, S_out))  // (32-bit offsets into the sequence's (Q, S_out) tensor)
         hipLaunchKernelGGL(softmax_cols_kernel, dim3((S_out + 63) / 64, batch), dim3(256), 0, s, out, Q,
@@ -2052,7 +2003,7 @@ int mvn_global_bias(const mvn_dims *dims, const mvn_params *p, const float *e, i
   for (int l0 = 0; l0 < L; l0 += GC_LAYERS) {
     const int n = std::min(GC_LAYERS, L - l0);
     GlobalCondArgs ga;
-    global_cond_tables(p, l0, n, &ga);
+    fill_ctx_tables(p, l0, n, &ga);
     hipLaunchKernelGGL(global_bias_kernel, dim3(batch, n), dim3(128), 0, (hipStream_t)stream_, ga, e,
                        gbias + (size_t)l0 * batch * 128, batch);
   }
@@ -2077,7 +2028,7 @@ int mvn_global_bias_backward(const mvn_dims *dims, const mvn_params *p, const mv
     const int n = std::min(GC_LAYERS, L - l0);
     GlobalCondArgs ga;
     GlobalCondGrads gg;
-    global_cond_tables(p, l0, n, &ga);  // (the kernel reads the weights only)
+    fill_ctx_tables(p, l0, n, &ga);  // (the kernel reads the weights only)
     for (int i = 0; i < GC_LAYERS; ++i) {
       const int l = l0 + std::min(i, n - 1);
       gg.dwcf[i] = gr->ctx_filter_w[l]; gg.dwcg[i] = gr->ctx_gate_w[l];
