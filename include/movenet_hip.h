@@ -698,6 +698,25 @@ int mvn_softmax_ce_backward_ex(const float *probs, const long long *target, int 
                                long long dlogit_batch_stride, int dlogit_ld, int dlogit_col0,
                                int dlogit_cols, int loss_rule, void *stream);
 
+/* The _ex pair for sequences of their own length: `valid` is a DEVICE array of `batch` int32, read by the kernels
+ * and clamped there to [0, s_len]; sequence b counts its columns s < valid[b] only.
+ *   forward   the probabilities are written in place for EVERY column, the same bits as _ex; loss_part and
+ *             correct_part receive the counted columns only.  A column that is not counted is selected out, not
+ *             multiplied by 0: it adds exactly 0 even where its logits are NaN or infinite.  Slots, their
+ *             zero-initialisation contract and the fixed-order summation are those of _ex; the caller divides by
+ *             max(sum_b valid[b], 1) for the mean.
+ *   backward  columns [col0, col0 + valid[b]) of sequence b's window get the gradient with the caller's `scale`,
+ *             columns [col0 + valid[b], col0 + cols) get +0.0f whatever the probabilities there hold, nothing
+ *             outside the window is touched.  Workgroups that hold no counted column store zeros and read nothing.
+ * valid == NULL is the _ex call, kernel for kernel.  Refusals as _ex, before any launch. */
+int mvn_softmax_ce_forward_len(float *logits_probs, const long long *target, int batch, int classes,
+                               int s_len, float *loss_part, int32_t *correct_part, int loss_rule,
+                               const int32_t *valid, void *stream);
+int mvn_softmax_ce_backward_len(const float *probs, const long long *target, int batch, int classes,
+                                int s_len, float scale, const float *upstream, float *dlogit,
+                                long long dlogit_batch_stride, int dlogit_ld, int dlogit_col0,
+                                int dlogit_cols, int loss_rule, const int32_t *valid, void *stream);
+
 /* Scoring GIVEN audio under the model: per-position log-likelihood of the target from the head's logits, read
  * only -- no probability tensor is formed and `logits` comes back bit for bit.  With y = logits / temperature:
  *     logp[b,s]      = y_t - logsumexp_q(y[b,:,s])                       (nats)
@@ -721,6 +740,15 @@ size_t mvn_score_scratch_floats(int batch, int s_len);
 int mvn_score_columns(const float *logits, const long long *target, int batch, int classes, int s_len,
                       float temperature, float *logp, float *entropy, int32_t *rank, float *seq_nll,
                       int32_t *seq_correct, float *scratch, size_t scratch_floats, void *stream);
+
+/* mvn_score_columns for sequences of their own length: `valid` as in mvn_softmax_ce_forward_len (DEVICE, `batch`
+ * int32, clamped to [0, s_len] by the kernel; NULL: the call above).  A column s >= valid[b] gets logp = 0.0f,
+ * entropy = 0.0f and rank = -1, whatever its logits hold, and seq_nll / seq_correct run over the counted columns only
+ * -- same slots, same fixed order, in double, no atomics. */
+int mvn_score_columns_len(const float *logits, const long long *target, int batch, int classes, int s_len,
+                          float temperature, float *logp, float *entropy, int32_t *rank, float *seq_nll,
+                          int32_t *seq_correct, float *scratch, size_t scratch_floats, const int32_t *valid,
+                          void *stream);
 
 /* One optimizer step of torch.optim.AdamW (decoupled != 0) or torch.optim.Adam (decoupled == 0,
  * weight decay added to the gradient) over flat fp32 buffers of n elements
@@ -777,6 +805,25 @@ typedef struct {
 size_t mvn_audio_frontend_scratch_floats(int batch, int n_out);
 int mvn_audio_frontend(const int16_t *pcm, long long pcm_len, const mvn_audio_clip *clips, int batch, int classes,
                        int n_out, int normalize, float *y, float *scratch, int32_t *index, void *stream);
+
+/* The front end by RATE: clip b is resampled, as a whole, to its own n_out frames -- the arithmetic of the call above
+ * for that clip alone with that n_out, bit for bit, the min-max normalisation over those n_out values only -- into
+ * row b of (batch, width) outputs; columns [n_out, width) get y = 0 and the class mu-law gives 0.0,
+ * (int)((classes - 1) / 2.0f + 0.5f).  A descriptor with n_out outside [1, width], or one the call above would
+ * refuse, is not read through: its whole row of `index` is -1 (and of `y` 0).  `reserved` is ignored.
+ *   y, index  DEVICE (batch, width);  scratch  mvn_audio_frontend_var_scratch_floats(batch, width) floats, 8-byte
+ *   aligned.  Host refusals as above, with width in n_out's place. */
+typedef struct {
+  int64_t offset;
+  int32_t frames;
+  int32_t channels;
+  int32_t n_out;
+  int32_t reserved;
+} mvn_audio_clip_var;
+size_t mvn_audio_frontend_var_scratch_floats(int batch, int width);
+int mvn_audio_frontend_var(const int16_t *pcm, long long pcm_len, const mvn_audio_clip_var *clips, int batch,
+                           int classes, int width, int normalize, float *y, float *scratch, int32_t *index,
+                           void *stream);
 
 /* The loader's video front end (movenet/dataset.py:292-310 behind the decoder): a batch of clips of different
  * resolutions, as interleaved uint8 frames in one upload, -> (batch, n_frames, 64, 64) uint8 gray levels.  Per frame:

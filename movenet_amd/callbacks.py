@@ -98,8 +98,14 @@ class LogSamplesCallback:
         sweep = self.temperature_sweep if gen is not None else []
         if sweep and len(gen) != len(fps) * len(sweep):
             raise ValueError(f"generated_output holds {len(gen)} clips for {len(fps)} clips x {len(sweep)} temperatures")
+        # (clip_length="native": a clip shorter than the prompt, the first RF samples, has nothing to prompt from --
+        # it is left out and counted in the rows that are written)
+        prompt_ok = outputs.get("prompt_ok", None) if gen is not None else None
+        skipped_short = 0 if prompt_ok is None else sum(not ok for ok in prompt_ok)
         rows = []
         for i, fp in enumerate(fps):
+            if prompt_ok is not None and not prompt_ok[i]:
+                continue
             stem = f"epoch={trainer.current_epoch}-batch={batch_idx}-clip={i}"
             files = {"origin_audio": root / split / f"{stem}-origin.wav",
                      "pred_audio": root / split / f"{stem}-pred.wav"}
@@ -122,12 +128,17 @@ class LogSamplesCallback:
             bits = scores["bits_per_sample"].cpu().tolist()
             source = scores["source_bits_per_sample"].cpu().tolist()
             per_clip = max(len(sweep), 1)
-            for k, r in enumerate(rows):
-                r["bits_per_sample"] = bits[k]
-                r["source_bits_per_sample"] = source[k // per_clip]
+            kept = [i for i in range(len(fps)) if prompt_ok is None or prompt_ok[i]]
+            for k, r in enumerate(rows):  # (the scores cover every clip of the batch; the rows only the kept ones)
+                clip = kept[k // per_clip]
+                r["bits_per_sample"] = bits[clip * per_clip + k % per_clip]
+                r["source_bits_per_sample"] = source[clip]
         if gen is not None and self.guidance != 1.0:  # (as a sweep's rows carry their temperature)
             for r in rows:
                 r["guidance"] = self.guidance
+        if prompt_ok is not None:
+            for r in rows:
+                r["skipped_short"] = skipped_short
         if labelled:
             where = {str(fp): str(c) for fp, c in zip(fps, contexts)}
             for r in rows:

@@ -99,6 +99,12 @@ class TrainingConfig:
     # with the default (off: no row changes).
     score_samples: bool = False
 
+    # clips of a WAV folder at their own length (WavFolderLoader): "resample" stretches every clip onto
+    # the batch width (the reference's rule); "native" resamples every clip to audio_rate, pads the batch to that width
+    # and leaves the padding out of the loss.  Not reference fields: a JSON written without them loads with the defaults.
+    clip_length: str = "resample"
+    audio_rate: int = 16000
+
     scheduler: Optional[str] = "OneCycleLR"
     lr_pct_start: float = 0.45
     base_learning_rate: float = 0.0003
@@ -185,6 +191,8 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--ema_decay", type=float, default=0.0)
     a("--ema_warmup", type=_flag, default=True)
     a("--score_samples", type=_flag, default=False)
+    a("--clip_length", type=str, default="resample", choices=["resample", "native"])
+    a("--audio_rate", type=int, default=16000)
     a("--n_epochs", type=int, default=10)
     a("--n_steps_per_epoch", type=int, default=None)
     a("--use_video", type=_flag, default=True)
@@ -232,7 +240,7 @@ def config_from_args(args) -> TrainingConfig:
         "lr_pct_start base_learning_rate scheduler_step_size_up scheduler_step_size_down "
         "scheduler_cyclic_mode scheduler_cyclic_gamma scheduler_cycle_momentum max_learning_rate "
         "scheduler_step_size scheduler_step_gamma scheduler_milestones weight_decay "
-        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule ema_decay ema_warmup score_samples accumulation_steps num_workers val_num_workers "
+        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule ema_decay ema_warmup score_samples clip_length audio_rate accumulation_steps num_workers val_num_workers "
         "pin_memory n_epochs n_steps_per_epoch use_video use_global bf16_video generate_guidance global_dropout video_antialias batch_subsample_frac "
         "val_batch_subsample_frac dist_backend dist_port model_output_path log_samples_every"
     ).split()

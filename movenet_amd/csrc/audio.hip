@@ -65,20 +65,44 @@ __device__ __forceinline__ AfGeom af_geom(const mvn_audio_clip &c, long long pcm
 
 __device__ __forceinline__ float wave_min(float v) { return -wave_max(-v); }
 
-__global__ __launch_bounds__(kAfThreads) void af_resample_kernel(const int16_t *__restrict__ pcm, long long pcm_len,
-                                                                 const mvn_audio_clip *__restrict__ clips, int N,
-                                                                 float *__restrict__ y, float2 *__restrict__ part) {
+// The by-rate form (mvn_audio_frontend_var): clip b is resampled to ITS OWN n_out frames into a row of `width`; the rest
+// of the row is silence.  The descriptor, and what it makes of a row: N outputs to form (the whole width for a
+// descriptor that is refused, so that the whole row is marked), by the geometry of the plain form for N.
+struct AfRow {
+  mvn_audio_clip c;
+  AfGeom g;
+  int N;
+};
+__device__ __forceinline__ AfRow af_row_var(const mvn_audio_clip_var &v, long long pcm_len, int width) {
+  AfRow r;
+  r.c.offset = v.offset;
+  r.c.frames = v.frames;
+  r.c.channels = v.channels;
+  const bool fits = v.n_out >= 1 && v.n_out <= width;
+  r.N = fits ? v.n_out : width;
+  r.g = af_geom(r.c, pcm_len, r.N);
+  if (!fits) r.g.ok = false;
+  if (!r.g.ok) r.N = width;
+  return r;
+}
+
+// VAR = false: N outputs per row, rows N apart (the plain form, as it was).  VAR = true: N of `width` outputs.
+template <bool VAR>
+__device__ __forceinline__ void af_resample(const int16_t *__restrict__ pcm, const mvn_audio_clip &c, const AfGeom &g,
+                                            int N, int width, float *__restrict__ y, float2 *__restrict__ part) {
   __shared__ float win[kAfWin];
   __shared__ float red[2 * (kAfThreads / kWave)];
   const int b = blockIdx.y, tid = threadIdx.x;
-  const mvn_audio_clip c = clips[b];
-  const AfGeom g = af_geom(c, pcm_len, N);
   const int t0 = blockIdx.x * kAfTile, t1 = min(N, t0 + kAfTile);
-  float *yb = y + (size_t)b * N;
+  float *yb = y + (size_t)b * (VAR ? width : N);
   if (!g.ok) {  // (workgroup-uniform) nothing of the upload is read
     for (int k = t0 + tid; k < t1; k += kAfThreads) yb[k] = 0.f;
     if (tid == 0) part[(size_t)b * gridDim.x + blockIdx.x] = make_float2(0.f, 0.f);
     return;
+  }
+  if (VAR) {  // the silence behind the clip; a tile that holds nothing else ends here (workgroup-uniform)
+    for (int k = max(N, t0) + tid; k < min(width, t0 + kAfTile); k += kAfThreads) yb[k] = 0.f;
+    if (t0 >= N) return;
   }
   const int16_t *src = pcm + c.offset;
   const int ch = c.channels, W = g.W;
@@ -140,26 +164,49 @@ __global__ __launch_bounds__(kAfThreads) void af_resample_kernel(const int16_t *
   }
 }
 
+__global__ __launch_bounds__(kAfThreads) void af_resample_kernel(const int16_t *__restrict__ pcm, long long pcm_len,
+                                                                 const mvn_audio_clip *__restrict__ clips, int N,
+                                                                 float *__restrict__ y, float2 *__restrict__ part) {
+  const mvn_audio_clip c = clips[blockIdx.y];
+  const AfGeom g = af_geom(c, pcm_len, N);
+  af_resample<false>(pcm, c, g, N, N, y, part);
+}
+
+__global__ __launch_bounds__(kAfThreads) void af_resample_var_kernel(const int16_t *__restrict__ pcm,
+                                                                     long long pcm_len,
+                                                                     const mvn_audio_clip_var *__restrict__ clips,
+                                                                     int width, float *__restrict__ y,
+                                                                     float2 *__restrict__ part) {
+  const AfRow r = af_row_var(clips[blockIdx.y], pcm_len, width);
+  af_resample<true>(pcm, r.c, r.g, r.N, width, y, part);
+}
+
 // audio <- (audio - min) / (max - min); audio * 2 - 1 (dataset.py:271-275), a clip with max == min left as it is (the
 // silent clip of the reference's `sum() == 0` test); then the mu-law of mu_law_encode_kernel, clamped to 0 .. Q-1
 // (an un-normalised resample may overshoot [-1, 1]).
-__global__ __launch_bounds__(kAfThreads) void af_quantise_kernel(const mvn_audio_clip *__restrict__ clips,
-                                                                 long long pcm_len, int N, int Q, int normalize,
-                                                                 int tiles, const float *__restrict__ y,
-                                                                 const float2 *__restrict__ part,
-                                                                 int32_t *__restrict__ idx) {
+// VAR: the (min, max) runs over the tiles that hold the clip's N outputs, of the `tiles` slots a row has; the columns
+// behind them get the class mu-law gives 0.0.
+template <bool VAR>
+__device__ __forceinline__ void af_quantise(const AfGeom &g, int N, int width, int Q, int normalize, int tiles,
+                                            const float *__restrict__ y, const float2 *__restrict__ part,
+                                            int32_t *__restrict__ idx) {
   __shared__ float red[2 * (kAfThreads / kWave)];
   const int b = blockIdx.y, tid = threadIdx.x;
   const int t0 = blockIdx.x * kAfTile, t1 = min(N, t0 + kAfTile);
-  int32_t *ib = idx + (size_t)b * N;
-  const AfGeom g = af_geom(clips[b], pcm_len, N);
+  int32_t *ib = idx + (size_t)b * (VAR ? width : N);
   if (!g.ok) {
     for (int k = t0 + tid; k < t1; k += kAfThreads) ib[k] = -1;
     return;
   }
+  if (VAR) {  // (workgroup-uniform)
+    const int silence = (int)((float)(Q - 1) / 2.0f + 0.5f);
+    for (int k = max(N, t0) + tid; k < min(width, t0 + kAfTile); k += kAfThreads) ib[k] = silence;
+    if (t0 >= N) return;
+  }
+  const int own = VAR ? (N + kAfTile - 1) / kAfTile : tiles;
   float mn = INFINITY, mx = -INFINITY;
   if (normalize) {  // every workgroup folds the clip's partials in the same order: one (min, max) per clip, reproducibly
-    for (int t = tid; t < tiles; t += kAfThreads) {
+    for (int t = tid; t < own; t += kAfThreads) {
       const float2 p = part[(size_t)b * tiles + t];
       mn = fminf(mn, p.x);
       mx = fmaxf(mx, p.y);
@@ -180,7 +227,7 @@ __global__ __launch_bounds__(kAfThreads) void af_quantise_kernel(const mvn_audio
   }
   const bool scale = normalize && mx != mn;
   const float mu = (float)(Q - 1), range = mx - mn, lmu = log1pf(mu);
-  const float *yb = y + (size_t)b * N;
+  const float *yb = y + (size_t)b * (VAR ? width : N);
   for (int k = t0 + tid; k < t1; k += kAfThreads) {
     float v = yb[k];
     if (scale) {
@@ -191,6 +238,25 @@ __global__ __launch_bounds__(kAfThreads) void af_quantise_kernel(const mvn_audio
     const int q = (int)((z + 1.0f) / 2.0f * mu + 0.5f);
     ib[k] = min(max(q, 0), Q - 1);
   }
+}
+
+__global__ __launch_bounds__(kAfThreads) void af_quantise_kernel(const mvn_audio_clip *__restrict__ clips,
+                                                                 long long pcm_len, int N, int Q, int normalize,
+                                                                 int tiles, const float *__restrict__ y,
+                                                                 const float2 *__restrict__ part,
+                                                                 int32_t *__restrict__ idx) {
+  const AfGeom g = af_geom(clips[blockIdx.y], pcm_len, N);
+  af_quantise<false>(g, N, N, Q, normalize, tiles, y, part, idx);
+}
+
+__global__ __launch_bounds__(kAfThreads) void af_quantise_var_kernel(const mvn_audio_clip_var *__restrict__ clips,
+                                                                     long long pcm_len, int width, int Q,
+                                                                     int normalize, int tiles,
+                                                                     const float *__restrict__ y,
+                                                                     const float2 *__restrict__ part,
+                                                                     int32_t *__restrict__ idx) {
+  const AfRow r = af_row_var(clips[blockIdx.y], pcm_len, width);
+  af_quantise<true>(r.g, r.N, width, Q, normalize, tiles, y, part, idx);
 }
 
 }  // namespace mvn
@@ -222,6 +288,33 @@ int mvn_audio_frontend(const int16_t *pcm, long long pcm_len, const mvn_audio_cl
   hipLaunchKernelGGL(mvn::af_quantise_kernel, grid, dim3(mvn::kAfThreads), 0, (hipStream_t)stream, clips, pcm_len,
                      n_out, classes, normalize, tiles, (const float *)y, (const float2 *)scratch, index);
   return mvn::check_hip(hipGetLastError(), "audio_frontend (quantise)");
+}
+
+size_t mvn_audio_frontend_var_scratch_floats(int batch, int width) {
+  return mvn_audio_frontend_scratch_floats(batch, width);
+}
+
+int mvn_audio_frontend_var(const int16_t *pcm, long long pcm_len, const mvn_audio_clip_var *clips, int batch,
+                           int classes, int width, int normalize, float *y, float *scratch, int32_t *index,
+                           void *stream) {
+  if (!pcm || !clips || !y || !scratch || !index || pcm_len < 1 || batch < 1 || batch > 65535 || width < 1 ||
+      classes < 2 || classes > 65536) {
+    mvn::set_error("mvn_audio_frontend_var: bad argument");
+    return MVN_ERR_BAD_ARG;
+  }
+  if (((uintptr_t)scratch & 7u) != 0) {
+    mvn::set_error("mvn_audio_frontend_var: scratch must be 8-byte aligned");
+    return MVN_ERR_BAD_ARG;
+  }
+  const int tiles = (width + mvn::kAfTile - 1) / mvn::kAfTile;
+  const dim3 grid(tiles, batch);
+  hipLaunchKernelGGL(mvn::af_resample_var_kernel, grid, dim3(mvn::kAfThreads), 0, (hipStream_t)stream, pcm, pcm_len,
+                     clips, width, y, (float2 *)scratch);
+  int rc = mvn::check_hip(hipGetLastError(), "audio_frontend_var (resample)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(mvn::af_quantise_var_kernel, grid, dim3(mvn::kAfThreads), 0, (hipStream_t)stream, clips, pcm_len,
+                     width, classes, normalize, tiles, (const float *)y, (const float2 *)scratch, index);
+  return mvn::check_hip(hipGetLastError(), "audio_frontend_var (quantise)");
 }
 
 }  // extern "C"

@@ -54,13 +54,23 @@ __device__ __forceinline__ void score_store(const ScoreAcc &a, float m, float lt
   if (rank) rank[at] = a.above;
 }
 
+// MASK (mvn_score_columns_len): sequence b counts its columns s < valid[b] only (clamped to [0, S]); the others store
+// logp = entropy = 0 and rank = -1 and are SELECTED out of the two sums, whatever their logits hold.
+__device__ __forceinline__ void score_store_masked(size_t at, float *__restrict__ logp, float *__restrict__ entropy,
+                                                   int32_t *__restrict__ rank) {
+  if (logp) logp[at] = 0.f;
+  if (entropy) entropy[at] = 0.f;
+  if (rank) rank[at] = -1;
+}
+
 // 64 columns per workgroup, wave w holds class rows [64w, 64w + 64) of them, lane = column.  Lanes past the end of the
 // row work on column 0 (valid memory, nothing of it stored).  Two LDS exchanges: (max, target's logit), then the sums.
-template <bool ENTROPY>
+template <bool ENTROPY, bool MASK>
 __device__ __forceinline__ void score_cols(const float *__restrict__ y, const long long *__restrict__ target, int Q,
                                            int S, float inv_t, float *__restrict__ logp,
                                            float *__restrict__ entropy, int32_t *__restrict__ rank,
-                                           float *__restrict__ nll_part, int32_t *__restrict__ ok_part) {
+                                           float *__restrict__ nll_part, int32_t *__restrict__ ok_part,
+                                           const int32_t *__restrict__ valid) {
   __shared__ float part[4][4][64];
   const int lane = threadIdx.x & 63, b = blockIdx.y;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -100,10 +110,13 @@ __device__ __forceinline__ void score_cols(const float *__restrict__ y, const lo
   a.above = (__float_as_int(part[2][0][lane]) + __float_as_int(part[2][1][lane])) +
             (__float_as_int(part[2][2][lane]) + __float_as_int(part[2][3][lane]));
   float lp = 0.f;
-  if (live)
+  const bool counted = MASK ? s < min(max(valid[b], 0), S) : live;
+  if (counted)
     score_store(a, m, lt, inv_t, (size_t)b * S + s, logp, ENTROPY ? entropy : nullptr, rank, lp);
-  const float nll = wave_sum(live ? -lp : 0.f);
-  const float ok = wave_sum(live && a.above == 0 ? 1.f : 0.f);
+  else if (MASK && live)
+    score_store_masked((size_t)b * S + s, logp, ENTROPY ? entropy : nullptr, rank);
+  const float nll = wave_sum(counted ? -lp : 0.f);
+  const float ok = wave_sum(counted && a.above == 0 ? 1.f : 0.f);
   if (lane == 0) {
     const size_t wg = (size_t)b * gridDim.x + blockIdx.x;
     nll_part[wg] = nll;
@@ -117,20 +130,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     const float *__restrict__ y, const long long *__restrict__ target, int Q, int S, float inv_t,
     float *__restrict__ logp, float *__restrict__ entropy, int32_t *__restrict__ rank, float *__restrict__ nll_part,
     int32_t *__restrict__ ok_part) {
-  score_cols<ENTROPY>(y, target, Q, S, inv_t, logp, entropy, rank, nll_part, ok_part);
+  score_cols<ENTROPY, false>(y, target, Q, S, inv_t, logp, entropy, rank, nll_part, ok_part, nullptr);
+}
+
+template <bool ENTROPY>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void score_cols_len_kernel(
+    const float *__restrict__ y, const long long *__restrict__ target, int Q, int S, float inv_t,
+    float *__restrict__ logp, float *__restrict__ entropy, int32_t *__restrict__ rank, float *__restrict__ nll_part,
+    int32_t *__restrict__ ok_part, const int32_t *__restrict__ valid) {
+  score_cols<ENTROPY, true>(y, target, Q, S, inv_t, logp, entropy, rank, nll_part, ok_part, valid);
 }
 
 // any Q, any row length: one thread per column, 64-bit addresses, the column walked twice
-__global__ __launch_bounds__(256) void score_wide_kernel(const float *__restrict__ y,
-                                                         const long long *__restrict__ target, int Q, int S,
-                                                         float inv_t, float *__restrict__ logp,
-                                                         float *__restrict__ entropy, int32_t *__restrict__ rank,
-                                                         float *__restrict__ nll_part,
-                                                         int32_t *__restrict__ ok_part) {
+// (MASK: a column at or beyond valid[b] reads nothing)
+template <bool MASK>
+__device__ __forceinline__ void score_wide(const float *__restrict__ y, const long long *__restrict__ target, int Q,
+                                           int S, float inv_t, float *__restrict__ logp, float *__restrict__ entropy,
+                                           int32_t *__restrict__ rank, float *__restrict__ nll_part,
+                                           int32_t *__restrict__ ok_part, const int32_t *__restrict__ valid,
+                                           const long long s) {
   const int b = blockIdx.y;
-  const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   float nll = 0.f, ok = 0.f;
-  if (s < S) {
+  if (MASK && s < S && s >= min(max(valid[b], 0), S)) {
+    score_store_masked((size_t)b * S + s, logp, entropy, rank);
+  } else if (s < S) {
     const float *col = y + (size_t)b * Q * S + s;
     const long long tg = target[(size_t)b * S + s];
     const int tq = (int)min(max(tg, 0LL), (long long)(Q - 1));
@@ -157,6 +180,27 @@ __global__ __launch_bounds__(256) void score_wide_kernel(const float *__restrict
     nll_part[wg] = (ns[0] + ns[1]) + (ns[2] + ns[3]);
     ok_part[wg] = (int)((cs[0] + cs[1]) + (cs[2] + cs[3]));
   }
+}
+
+__global__ __launch_bounds__(256) void score_wide_kernel(const float *__restrict__ y,
+                                                         const long long *__restrict__ target, int Q, int S,
+                                                         float inv_t, float *__restrict__ logp,
+                                                         float *__restrict__ entropy, int32_t *__restrict__ rank,
+                                                         float *__restrict__ nll_part,
+                                                         int32_t *__restrict__ ok_part) {
+  score_wide<false>(y, target, Q, S, inv_t, logp, entropy, rank, nll_part, ok_part, nullptr,
+                    (long long)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void score_wide_len_kernel(const float *__restrict__ y,
+                                                             const long long *__restrict__ target, int Q, int S,
+                                                             float inv_t, float *__restrict__ logp,
+                                                             float *__restrict__ entropy, int32_t *__restrict__ rank,
+                                                             float *__restrict__ nll_part,
+                                                             int32_t *__restrict__ ok_part,
+                                                             const int32_t *__restrict__ valid) {
+  score_wide<true>(y, target, Q, S, inv_t, logp, entropy, rank, nll_part, ok_part, valid,
+                   (long long)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // One wave per sequence: lane i adds partials i, i + 64, ... in double, then a fixed butterfly -- the same order, hence
@@ -193,23 +237,25 @@ size_t mvn_score_scratch_floats(int batch, int s_len) {
   return 2 * (size_t)batch * (size_t)((s_len + 63) / 64);
 }
 
-int mvn_score_columns(const float *logits, const long long *target, int batch, int classes, int s_len,
-                      float temperature, float *logp, float *entropy, int32_t *rank, float *seq_nll,
-                      int32_t *seq_correct, float *scratch, size_t scratch_floats, void *stream) {
+// (mvn_score_columns and its _len form share this; `valid` == NULL launches the unmasked kernels)
+static int score_columns_impl(const char *what, const float *logits, const long long *target, int batch, int classes,
+                              int s_len, float temperature, float *logp, float *entropy, int32_t *rank,
+                              float *seq_nll, int32_t *seq_correct, float *scratch, size_t scratch_floats,
+                              const int32_t *valid, void *stream) {
   if (batch < 0 || classes < 1 || s_len < 0 || batch > 65535) {
-    mvn::set_error("mvn_score_columns: bad argument (batch in [0, 65535], classes >= 1, s_len >= 0)");
+    mvn::set_error("%s: bad argument (batch in [0, 65535], classes >= 1, s_len >= 0)", what);
     return MVN_ERR_BAD_ARG;
   }
   if (!(temperature > 0.f) || std::isinf(temperature)) {  // (NaN fails the comparison)
-    mvn::set_error("mvn_score_columns: bad argument (temperature %g is not a finite number above 0)",
+    mvn::set_error("%s: bad argument (temperature %g is not a finite number above 0)", what,
                    (double)temperature);
     return MVN_ERR_BAD_ARG;
   }
   if (batch == 0) return MVN_OK;
   const size_t need = mvn_score_scratch_floats(batch, s_len);
   if ((s_len > 0 && (!logits || !target)) || (need > 0 && !scratch) || scratch_floats < need) {
-    mvn::set_error("mvn_score_columns: bad argument (logits, target or scratch missing, or scratch of %zu floats "
-                   "where mvn_score_scratch_floats asks for %zu)", scratch_floats, need);
+    mvn::set_error("%s: bad argument (logits, target or scratch missing, or scratch of %zu floats "
+                   "where mvn_score_scratch_floats asks for %zu)", what, scratch_floats, need);
     return MVN_ERR_BAD_ARG;
   }
   const float inv_t = 1.0f / temperature;
@@ -219,23 +265,45 @@ int mvn_score_columns(const float *logits, const long long *target, int batch, i
   float *nll_part = scratch;
   int32_t *ok_part = (int32_t *)(scratch + (size_t)batch * parts);
   if (s_len > 0) {
-    if (cols) {
+    if (cols && valid) {
+      const auto kernel = entropy ? mvn::score_cols_len_kernel<true> : mvn::score_cols_len_kernel<false>;
+      hipLaunchKernelGGL(kernel, dim3(parts, batch), dim3(256), 0, (hipStream_t)stream, logits, target, classes,
+                         s_len, inv_t, logp, entropy, rank, nll_part, ok_part, valid);
+    } else if (cols) {
       const auto kernel = entropy ? mvn::score_cols_kernel<true> : mvn::score_cols_kernel<false>;
       hipLaunchKernelGGL(kernel, dim3(parts, batch), dim3(256), 0, (hipStream_t)stream, logits, target, classes,
                          s_len, inv_t, logp, entropy, rank, nll_part, ok_part);
+    } else if (valid) {
+      hipLaunchKernelGGL(mvn::score_wide_len_kernel, dim3(parts, batch), dim3(256), 0, (hipStream_t)stream, logits,
+                         target, classes, s_len, inv_t, logp, entropy, rank, nll_part, ok_part, valid);
     } else {
       hipLaunchKernelGGL(mvn::score_wide_kernel, dim3(parts, batch), dim3(256), 0, (hipStream_t)stream, logits,
                          target, classes, s_len, inv_t, logp, entropy, rank, nll_part, ok_part);
     }
-    const int rc = mvn::check_hip(hipGetLastError(), "mvn_score_columns");
+    const int rc = mvn::check_hip(hipGetLastError(), what);
     if (rc != MVN_OK) return rc;
   }
   if (seq_nll || seq_correct) {
     hipLaunchKernelGGL(mvn::score_reduce_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, nll_part, ok_part,
                        parts, seq_nll, seq_correct);
-    return mvn::check_hip(hipGetLastError(), "mvn_score_columns");
+    return mvn::check_hip(hipGetLastError(), what);
   }
   return MVN_OK;
+}
+
+int mvn_score_columns(const float *logits, const long long *target, int batch, int classes, int s_len,
+                      float temperature, float *logp, float *entropy, int32_t *rank, float *seq_nll,
+                      int32_t *seq_correct, float *scratch, size_t scratch_floats, void *stream) {
+  return score_columns_impl("mvn_score_columns", logits, target, batch, classes, s_len, temperature, logp, entropy,
+                            rank, seq_nll, seq_correct, scratch, scratch_floats, nullptr, stream);
+}
+
+int mvn_score_columns_len(const float *logits, const long long *target, int batch, int classes, int s_len,
+                          float temperature, float *logp, float *entropy, int32_t *rank, float *seq_nll,
+                          int32_t *seq_correct, float *scratch, size_t scratch_floats, const int32_t *valid,
+                          void *stream) {
+  return score_columns_impl("mvn_score_columns_len", logits, target, batch, classes, s_len, temperature, logp,
+                            entropy, rank, seq_nll, seq_correct, scratch, scratch_floats, valid, stream);
 }
 
 }  // extern "C"

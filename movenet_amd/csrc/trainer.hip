@@ -11,6 +11,8 @@
 //   mvn_softmax_ce_*_ex      the same pair with the loss rule chosen: MVN_LOSS_MODEL is the negative log-likelihood
 //                            of softmax(logits) itself -- same probabilities, one exponential pass forward, a
 //                            streaming p - onehot backward (ce_model_bwd_kernel)
+//   mvn_softmax_ce_*_len     the _ex pair over sequences of their own length: a device array of per-sequence column
+//                            counts, the columns beyond a sequence's count left out of the loss and zeroed in dlogit
 //   mvn_adamw_step           torch.optim.AdamW / Adam over ONE flat parameter / gradient /
 //                            moment buffer (pytorch_lightning_trainer.py:186-189)
 //   mvn_adamw_ema_step       the same step, with an exponential moving average of the parameters
@@ -39,10 +41,19 @@ __device__ __forceinline__ float t_col_reduce(float v, float (*part)[64], int wa
 // MODEL (MVN_LOSS_MODEL): the loss is the column's own -log p_target = (m + log sum) - l_target, from the max and the
 // exp-sum above: the target's logit is picked up as the column is loaded, and the second log-softmax (64 exponentials
 // and two reductions per thread) is not formed.  Probabilities and accuracy: the same instructions under both rules.
-template <bool MODEL>
+// MASK (the _len entry points): sequence b counts its columns s < valid[b] only, valid[b] clamped to [0, S].  The
+// forward forms and stores every column's probabilities as without it and SELECTS the other columns out of the two
+// sums, so that a NaN or an infinity in them adds exactly 0; the backward zeroes them as it zeroes [S, s_cols).
+// MASK = false never reads `valid`: those instantiations are the kernels they were.
+__device__ __forceinline__ int valid_cols(const int32_t *__restrict__ valid, int b, int S) {
+  return min(max(valid[b], 0), S);
+}
+
+template <bool MODEL, bool MASK>
 __device__ __forceinline__ void softmax_ce_fwd_cols(float *__restrict__ y, const long long *__restrict__ target, int Q,
                                                     int S, float *__restrict__ loss_part,
-                                                    int32_t *__restrict__ correct_part) {
+                                                    int32_t *__restrict__ correct_part,
+                                                    const int32_t *__restrict__ valid) {
   __shared__ float part[4][64];
   __shared__ int argp[4][64];
   const int lane = threadIdx.x & 63, b = blockIdx.y;
@@ -106,6 +117,11 @@ __device__ __forceinline__ void softmax_ce_fwd_cols(float *__restrict__ y, const
     const int a0 = min(min(argp[0][lane], argp[1][lane]), min(argp[2][lane], argp[3][lane]));
     loss = MODEL ? (m + logf(sum)) - pt_all : (m2 + logf(sum2)) - pt_all;
     ok = a0 == tq;
+    if (MASK) {
+      const bool counted = s < valid_cols(valid, b, S);
+      loss = counted ? loss : 0.f;
+      ok = counted ? ok : 0;
+    }
   }
   if (wave == 0) {
     loss = wave_sum(loss);
@@ -122,7 +138,7 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_cols_kernel(float *__restr
                                                                   const long long *__restrict__ target,
                                                                   int Q, int S, float *__restrict__ loss_part,
                                                                   int32_t *__restrict__ correct_part) {
-  softmax_ce_fwd_cols<false>(y, target, Q, S, loss_part, correct_part);
+  softmax_ce_fwd_cols<false, false>(y, target, Q, S, loss_part, correct_part, nullptr);
 }
 
 // (with fewer uses of the column to order its work by, the compiler kept loads and exponentials of the whole column
@@ -130,23 +146,51 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_cols_kernel(float *__restr
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void softmax_ce_model_fwd_cols_kernel(
     float *__restrict__ y, const long long *__restrict__ target, int Q, int S, float *__restrict__ loss_part,
     int32_t *__restrict__ correct_part) {
-  softmax_ce_fwd_cols<true>(y, target, Q, S, loss_part, correct_part);
+  softmax_ce_fwd_cols<true, false>(y, target, Q, S, loss_part, correct_part, nullptr);
+}
+
+// The masked twins, under the bounds of the kernels above, rule for rule (DESIGN.md 4.5 has what they compile to).
+__global__ __launch_bounds__(256) void softmax_ce_fwd_cols_len_kernel(float *__restrict__ y,
+                                                                      const long long *__restrict__ target, int Q,
+                                                                      int S, float *__restrict__ loss_part,
+                                                                      int32_t *__restrict__ correct_part,
+                                                                      const int32_t *__restrict__ valid) {
+  softmax_ce_fwd_cols<false, true>(y, target, Q, S, loss_part, correct_part, valid);
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void softmax_ce_model_fwd_cols_len_kernel(
+    float *__restrict__ y, const long long *__restrict__ target, int Q, int S, float *__restrict__ loss_part,
+    int32_t *__restrict__ correct_part, const int32_t *__restrict__ valid) {
+  softmax_ce_fwd_cols<true, true>(y, target, Q, S, loss_part, correct_part, valid);
 }
 
 // (r4c: the column's probabilities are the only array a thread keeps -- the exponentials are formed twice, the second time
 // where the gradient is written, and sum_q dprobs_q p_q comes from two sums of the first pass -- so that four waves fit a
 // SIMD: 248 -> ~110 registers)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void softmax_ce_bwd_cols_kernel(const float *__restrict__ p,
-                                                                  const long long *__restrict__ target,
-                                                                  int Q, int S, float scale,
-                                                                  const float *__restrict__ upstream,
-                                                                  float *__restrict__ dlogit, long long d_sb,
-                                                                  int d_ld, int col0, int s_cols) {
+// MASK: the columns that count end at valid[b] instead of S, and a workgroup that holds none of them stores its zeros
+// before it reads anything.
+template <bool MASK>
+__device__ __forceinline__ void softmax_ce_bwd_cols(const float *__restrict__ p, const long long *__restrict__ target,
+                                                    int Q, int S, float scale, const float *__restrict__ upstream,
+                                                    float *__restrict__ dlogit, long long d_sb, int d_ld, int col0,
+                                                    int s_cols, const int32_t *__restrict__ valid) {
   __shared__ float part[4][64], part2[4][64], part3[4][64];
   const int lane = threadIdx.x & 63, b = blockIdx.y;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int s = blockIdx.x * 64 + lane;
-  const bool live = s < S;
+  const int Sv = MASK ? valid_cols(valid, b, S) : S;
+  if (MASK && (int)blockIdx.x * 64 >= Sv) {  // (workgroup-uniform, ahead of every barrier)
+    if (s >= s_cols) return;
+    const __amdgpu_buffer_rsrc_t zb = col_rsrc(dlogit + (size_t)b * d_sb);
+    const int zvoff = 4 * (col0 + s), zrow = 4 * d_ld;
+#pragma unroll
+    for (int i = 0; i < TQ; ++i) {
+      const int q = TQ * wave + i;
+      if (q < Q) col_st(0.f, zb, zvoff, q * zrow);
+    }
+    return;
+  }
+  const bool live = s < Sv;
   const __amdgpu_buffer_rsrc_t pb = col_rsrc(p + (size_t)b * Q * S);
   const int voff = 4 * (live ? s : 0), row = 4 * S;
   float pv[TQ];
@@ -199,13 +243,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   }
 }
 
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void softmax_ce_bwd_cols_kernel(const float *__restrict__ p,
+                                                                  const long long *__restrict__ target,
+                                                                  int Q, int S, float scale,
+                                                                  const float *__restrict__ upstream,
+                                                                  float *__restrict__ dlogit, long long d_sb,
+                                                                  int d_ld, int col0, int s_cols) {
+  softmax_ce_bwd_cols<false>(p, target, Q, S, scale, upstream, dlogit, d_sb, d_ld, col0, s_cols, nullptr);
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void softmax_ce_bwd_cols_len_kernel(
+    const float *__restrict__ p, const long long *__restrict__ target, int Q, int S, float scale,
+    const float *__restrict__ upstream, float *__restrict__ dlogit, long long d_sb, int d_ld, int col0, int s_cols,
+    const int32_t *__restrict__ valid) {
+  softmax_ce_bwd_cols<true>(p, target, Q, S, scale, upstream, dlogit, d_sb, d_ld, col0, s_cols, valid);
+}
+
 // any Q: one thread per column, the column walked several times (slow path)
-template <bool MODEL>
-__global__ __launch_bounds__(256) void softmax_ce_fwd_kernel(float *__restrict__ y,
-                                                             const long long *__restrict__ target, int Q, int S,
-                                                             float *__restrict__ loss_part,
-                                                             int32_t *__restrict__ correct_part) {
-  const int b = blockIdx.y, s = blockIdx.x * blockDim.x + threadIdx.x;
+template <bool MODEL, bool MASK>
+__device__ __forceinline__ void softmax_ce_fwd_wide(float *__restrict__ y, const long long *__restrict__ target, int Q,
+                                                    int S, float *__restrict__ loss_part,
+                                                    int32_t *__restrict__ correct_part,
+                                                    const int32_t *__restrict__ valid, const int s) {
+  const int b = blockIdx.y;
   float loss = 0.f;
   int ok = 0;
   if (s < S) {
@@ -240,6 +300,11 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_kernel(float *__restrict__
       loss = (m2 + logf(sum2)) - col[(size_t)tq * S];
     }
     ok = arg == tq;
+    if (MASK) {
+      const bool counted = s < valid_cols(valid, b, S);
+      loss = counted ? loss : 0.f;
+      ok = counted ? ok : 0;
+    }
   }
   __shared__ float ls[4];
   __shared__ int cs[4];
@@ -257,15 +322,35 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_kernel(float *__restrict__
   }
 }
 
-__global__ __launch_bounds__(256) void softmax_ce_bwd_kernel(const float *__restrict__ p,
+template <bool MODEL>
+__global__ __launch_bounds__(256) void softmax_ce_fwd_kernel(float *__restrict__ y,
                                                              const long long *__restrict__ target, int Q, int S,
-                                                             float scale, const float *__restrict__ upstream,
-                                                             float *__restrict__ dlogit, long long d_sb, int d_ld,
-                                                             int col0, int s_cols) {
-  const int b = blockIdx.y, s = blockIdx.x * blockDim.x + threadIdx.x;
+                                                             float *__restrict__ loss_part,
+                                                             int32_t *__restrict__ correct_part) {
+  softmax_ce_fwd_wide<MODEL, false>(y, target, Q, S, loss_part, correct_part, nullptr,
+                                    blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+template <bool MODEL>
+__global__ __launch_bounds__(256) void softmax_ce_fwd_len_kernel(float *__restrict__ y,
+                                                                 const long long *__restrict__ target, int Q, int S,
+                                                                 float *__restrict__ loss_part,
+                                                                 int32_t *__restrict__ correct_part,
+                                                                 const int32_t *__restrict__ valid) {
+  softmax_ce_fwd_wide<MODEL, true>(y, target, Q, S, loss_part, correct_part, valid,
+                                   blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// (MASK: a thread at or beyond valid[b] takes the zeroing branch of the columns [S, s_cols) and reads no probability)
+template <bool MASK>
+__device__ __forceinline__ void softmax_ce_bwd_wide(const float *__restrict__ p, const long long *__restrict__ target,
+                                                    int Q, int S, float scale, const float *__restrict__ upstream,
+                                                    float *__restrict__ dlogit, long long d_sb, int d_ld, int col0,
+                                                    int s_cols, const int32_t *__restrict__ valid, const int s) {
+  const int b = blockIdx.y;
   if (s >= s_cols) return;
   float *dcol = dlogit + (size_t)b * d_sb + col0 + s;
-  if (s >= S) {
+  if (s >= (MASK ? valid_cols(valid, b, S) : S)) {
     for (int q = 0; q < Q; ++q) dcol[(size_t)q * d_ld] = 0.f;
     return;
   }
@@ -289,6 +374,25 @@ __global__ __launch_bounds__(256) void softmax_ce_bwd_kernel(const float *__rest
   }
 }
 
+__global__ __launch_bounds__(256) void softmax_ce_bwd_kernel(const float *__restrict__ p,
+                                                             const long long *__restrict__ target, int Q, int S,
+                                                             float scale, const float *__restrict__ upstream,
+                                                             float *__restrict__ dlogit, long long d_sb, int d_ld,
+                                                             int col0, int s_cols) {
+  softmax_ce_bwd_wide<false>(p, target, Q, S, scale, upstream, dlogit, d_sb, d_ld, col0, s_cols, nullptr,
+                             blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void softmax_ce_bwd_len_kernel(const float *__restrict__ p,
+                                                                 const long long *__restrict__ target, int Q, int S,
+                                                                 float scale, const float *__restrict__ upstream,
+                                                                 float *__restrict__ dlogit, long long d_sb, int d_ld,
+                                                                 int col0, int s_cols,
+                                                                 const int32_t *__restrict__ valid) {
+  softmax_ce_bwd_wide<true>(p, target, Q, S, scale, upstream, dlogit, d_sb, d_ld, col0, s_cols, valid,
+                            blockIdx.x * blockDim.x + threadIdx.x);
+}
+
 // MODEL rule (MVN_LOSS_MODEL): dlogit = scale upstream (p - onehot(target)) -- no exponential, no sum over the column, so
 // nothing of the column forms above is kept (no 64-register column, no LDS): a streaming kernel, one read of the
 // probabilities and one write of the window.  A thread owns FOUR consecutive columns of the dlogit tensor, counted
@@ -301,28 +405,37 @@ __global__ __launch_bounds__(256) void softmax_ce_bwd_kernel(const float *__rest
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 constexpr int MB_ROWS = 16;
 
-__global__ __launch_bounds__(256) void ce_model_bwd_kernel(const float *__restrict__ p,
-                                                           const long long *__restrict__ target, int Q, int S,
-                                                           float scale, const float *__restrict__ upstream,
-                                                           float *__restrict__ dlogit, long long d_sb, int d_ld,
-                                                           int col0, int s_cols) {
+// MASK: the columns that count end at Sv = valid[b] instead of S.  A group that lies whole inside [Sv, s_cols) stores
+// 16 bytes of zeros per row and reads nothing; one that straddles Sv takes the element-wise tail, like one at S.
+template <bool MASK>
+__device__ __forceinline__ void ce_model_bwd(const float *__restrict__ p, const long long *__restrict__ target, int Q,
+                                             int S, float scale, const float *__restrict__ upstream,
+                                             float *__restrict__ dlogit, long long d_sb, int d_ld, int col0,
+                                             int s_cols, const int32_t *__restrict__ valid) {
   const int b = blockIdx.z, q0 = blockIdx.y * MB_ROWS;
   // first column of the thread's group in the dlogit row, and the window position it maps to (may be negative)
   const long long a0 = 4LL * ((long long)(col0 >> 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x);
   const long long s0 = a0 - col0;
   if (s0 >= s_cols || s0 + 3 < 0) return;
+  const int Sv = MASK ? valid_cols(valid, b, S) : S;
   if (upstream) scale *= *upstream;
-  const bool whole = s0 >= 0 && s0 + 3 < S;  // the whole group inside [0, S)
+  const bool whole = s0 >= 0 && s0 + 3 < Sv;  // the whole group inside [0, Sv)
   const long long *trow = target + ((long long)b * S + s0);
   int tq[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    const long long tg = (whole || (s0 + e >= 0 && s0 + e < S)) ? trow[e] : 0;
+    const long long tg = (whole || (s0 + e >= 0 && s0 + e < Sv)) ? trow[e] : 0;
     tq[e] = (int)min(max(tg, 0LL), (long long)(Q - 1));
   }
   const float *prow = p + ((long long)b * Q * S + s0);  // (dereferenced only where 0 <= s < S)
   float *drow = dlogit + ((long long)b * d_sb + a0);
   const int q1 = min(Q, q0 + MB_ROWS);
+  if (MASK && s0 >= Sv && s0 + 3 < s_cols) {  // (s0 >= Sv >= 0) nothing here counts
+    const f4u zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int q = q0; q < q1; ++q) *(f4u *)(drow + (size_t)q * d_ld) = zero;
+    return;
+  }
   if (whole) {  // one load, one store per row
 #pragma unroll 4
     for (int q = q0; q < q1; ++q) {
@@ -334,15 +447,32 @@ __global__ __launch_bounds__(256) void ce_model_bwd_kernel(const float *__restri
     }
     return;
   }
-  for (int q = q0; q < q1; ++q) {  // an edge of the window: element by element; [S, s_cols) is zeroed
+  for (int q = q0; q < q1; ++q) {  // an edge of the window: element by element; [Sv, s_cols) is zeroed
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const long long s = s0 + e;
       if (s < 0 || s >= s_cols) continue;
-      const float g = s < S ? scale * (prow[(size_t)q * S + e] - (q == tq[e] ? 1.0f : 0.0f)) : 0.f;
+      const float g = s < Sv ? scale * (prow[(size_t)q * S + e] - (q == tq[e] ? 1.0f : 0.0f)) : 0.f;
       drow[(size_t)q * d_ld + e] = g;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void ce_model_bwd_kernel(const float *__restrict__ p,
+                                                           const long long *__restrict__ target, int Q, int S,
+                                                           float scale, const float *__restrict__ upstream,
+                                                           float *__restrict__ dlogit, long long d_sb, int d_ld,
+                                                           int col0, int s_cols) {
+  ce_model_bwd<false>(p, target, Q, S, scale, upstream, dlogit, d_sb, d_ld, col0, s_cols, nullptr);
+}
+
+__global__ __launch_bounds__(256) void ce_model_bwd_len_kernel(const float *__restrict__ p,
+                                                               const long long *__restrict__ target, int Q, int S,
+                                                               float scale, const float *__restrict__ upstream,
+                                                               float *__restrict__ dlogit, long long d_sb, int d_ld,
+                                                               int col0, int s_cols,
+                                                               const int32_t *__restrict__ valid) {
+  ce_model_bwd<true>(p, target, Q, S, scale, upstream, dlogit, d_sb, d_ld, col0, s_cols, valid);
 }
 
 // ---- AdamW / Adam over a flat buffer ------------------------------------------------------
@@ -427,10 +557,11 @@ __global__ __launch_bounds__(256) void adamw_ema_flat_kernel(float *__restrict__
 
 extern "C" {
 
-// (the plain entry points and their _ex forms share these: `what` is the name the caller's error text carries)
+// (the plain entry points, their _ex and their _len forms share these: `what` is the name the caller's error text
+// carries; `valid` == NULL launches the unmasked kernels)
 static int softmax_ce_forward_impl(const char *what, float *logits_probs, const long long *target, int batch,
                                    int classes, int s_len, float *loss_part, int32_t *correct_part, int loss_rule,
-                                   void *stream) {
+                                   const int32_t *valid, void *stream) {
   if (!logits_probs || !target || !loss_part || !correct_part || batch < 0 || classes < 2 || s_len < 0) {
     mvn::set_error("%s: bad argument", what);
     return MVN_ERR_BAD_ARG;
@@ -442,14 +573,18 @@ static int softmax_ce_forward_impl(const char *what, float *logits_probs, const 
   if (batch == 0 || s_len == 0) return MVN_OK;
   const bool model = loss_rule == MVN_LOSS_MODEL;
   // (the column form addresses a sequence's (Q, S) tensor with 32-bit offsets: common.h rows_fit_rsrc)
-  if (classes <= 4 * mvn::TQ && mvn::rows_fit_rsrc(classes, s_len)) {
-    const auto kernel = model ? mvn::softmax_ce_model_fwd_cols_kernel : mvn::softmax_ce_fwd_cols_kernel;
-    hipLaunchKernelGGL(kernel, dim3((s_len + 63) / 64, batch), dim3(256), 0, (hipStream_t)stream, logits_probs,
-                       target, classes, s_len, loss_part, correct_part);
+  const bool cols = classes <= 4 * mvn::TQ && mvn::rows_fit_rsrc(classes, s_len);
+  const dim3 grid(cols ? (s_len + 63) / 64 : (s_len + 255) / 256, batch);
+  if (valid) {
+    const auto kernel = cols ? (model ? mvn::softmax_ce_model_fwd_cols_len_kernel : mvn::softmax_ce_fwd_cols_len_kernel)
+                             : (model ? mvn::softmax_ce_fwd_len_kernel<true> : mvn::softmax_ce_fwd_len_kernel<false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, logits_probs, target, classes, s_len,
+                       loss_part, correct_part, valid);
   } else {
-    const auto kernel = model ? mvn::softmax_ce_fwd_kernel<true> : mvn::softmax_ce_fwd_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((s_len + 255) / 256, batch), dim3(256), 0, (hipStream_t)stream, logits_probs,
-                       target, classes, s_len, loss_part, correct_part);
+    const auto kernel = cols ? (model ? mvn::softmax_ce_model_fwd_cols_kernel : mvn::softmax_ce_fwd_cols_kernel)
+                             : (model ? mvn::softmax_ce_fwd_kernel<true> : mvn::softmax_ce_fwd_kernel<false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, logits_probs, target, classes, s_len,
+                       loss_part, correct_part);
   }
   return mvn::check_hip(hipGetLastError(), what);
 }
@@ -457,7 +592,7 @@ static int softmax_ce_forward_impl(const char *what, float *logits_probs, const 
 static int softmax_ce_backward_impl(const char *what, const float *probs, const long long *target, int batch,
                                     int classes, int s_len, float scale, const float *upstream, float *dlogit,
                                     long long dlogit_batch_stride, int dlogit_ld, int dlogit_col0, int dlogit_cols,
-                                    int loss_rule, void *stream) {
+                                    int loss_rule, const int32_t *valid, void *stream) {
   if (!probs || !target || !dlogit || batch < 0 || classes < 2 || s_len < 0 || dlogit_cols < s_len ||
       dlogit_col0 < 0 || dlogit_ld < dlogit_col0 + dlogit_cols) {
     mvn::set_error("%s: bad argument", what);
@@ -476,30 +611,54 @@ static int softmax_ce_backward_impl(const char *what, const float *probs, const 
       mvn::set_error("%s: more than 65535 x %d classes or 65535 sequences", what, mvn::MB_ROWS);
       return MVN_ERR_BAD_ARG;
     }
-    hipLaunchKernelGGL(mvn::ce_model_bwd_kernel, dim3((unsigned)((groups + 255) / 256), (unsigned)rows, batch),
-                       dim3(256), 0, (hipStream_t)stream, probs, target, classes, s_len, scale, upstream, dlogit,
-                       dlogit_batch_stride, dlogit_ld, dlogit_col0, dlogit_cols);
-  } else if (classes <= 4 * mvn::TQ && mvn::rows_fit_rsrc(classes, s_len) && mvn::rows_fit_rsrc(classes, dlogit_ld))
-    hipLaunchKernelGGL(mvn::softmax_ce_bwd_cols_kernel, dim3((dlogit_cols + 63) / 64, batch), dim3(256), 0,
-                       (hipStream_t)stream, probs, target, classes, s_len, scale, upstream, dlogit,
-                       dlogit_batch_stride, dlogit_ld, dlogit_col0, dlogit_cols);
-  else
-    hipLaunchKernelGGL(mvn::softmax_ce_bwd_kernel, dim3((dlogit_cols + 255) / 256, batch), dim3(256), 0,
-                       (hipStream_t)stream, probs, target, classes, s_len, scale, upstream, dlogit,
-                       dlogit_batch_stride, dlogit_ld, dlogit_col0, dlogit_cols);
+    const dim3 grid((unsigned)((groups + 255) / 256), (unsigned)rows, batch);
+    if (valid)
+      hipLaunchKernelGGL(mvn::ce_model_bwd_len_kernel, grid, dim3(256), 0, (hipStream_t)stream, probs, target,
+                         classes, s_len, scale, upstream, dlogit, dlogit_batch_stride, dlogit_ld, dlogit_col0,
+                         dlogit_cols, valid);
+    else
+      hipLaunchKernelGGL(mvn::ce_model_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, probs, target, classes,
+                         s_len, scale, upstream, dlogit, dlogit_batch_stride, dlogit_ld, dlogit_col0, dlogit_cols);
+  } else if (classes <= 4 * mvn::TQ && mvn::rows_fit_rsrc(classes, s_len) && mvn::rows_fit_rsrc(classes, dlogit_ld)) {
+    const dim3 grid((dlogit_cols + 63) / 64, batch);
+    if (valid)
+      hipLaunchKernelGGL(mvn::softmax_ce_bwd_cols_len_kernel, grid, dim3(256), 0, (hipStream_t)stream, probs, target,
+                         classes, s_len, scale, upstream, dlogit, dlogit_batch_stride, dlogit_ld, dlogit_col0,
+                         dlogit_cols, valid);
+    else
+      hipLaunchKernelGGL(mvn::softmax_ce_bwd_cols_kernel, grid, dim3(256), 0, (hipStream_t)stream, probs, target,
+                         classes, s_len, scale, upstream, dlogit, dlogit_batch_stride, dlogit_ld, dlogit_col0,
+                         dlogit_cols);
+  } else {
+    const dim3 grid((dlogit_cols + 255) / 256, batch);
+    if (valid)
+      hipLaunchKernelGGL(mvn::softmax_ce_bwd_len_kernel, grid, dim3(256), 0, (hipStream_t)stream, probs, target,
+                         classes, s_len, scale, upstream, dlogit, dlogit_batch_stride, dlogit_ld, dlogit_col0,
+                         dlogit_cols, valid);
+    else
+      hipLaunchKernelGGL(mvn::softmax_ce_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, probs, target, classes,
+                         s_len, scale, upstream, dlogit, dlogit_batch_stride, dlogit_ld, dlogit_col0, dlogit_cols);
+  }
   return mvn::check_hip(hipGetLastError(), what);
 }
 
 int mvn_softmax_ce_forward(float *logits_probs, const long long *target, int batch, int classes, int s_len,
                            float *loss_part, int32_t *correct_part, void *stream) {
   return softmax_ce_forward_impl("mvn_softmax_ce_forward", logits_probs, target, batch, classes, s_len, loss_part,
-                                 correct_part, MVN_LOSS_REFERENCE, stream);
+                                 correct_part, MVN_LOSS_REFERENCE, nullptr, stream);
 }
 
 int mvn_softmax_ce_forward_ex(float *logits_probs, const long long *target, int batch, int classes, int s_len,
                               float *loss_part, int32_t *correct_part, int loss_rule, void *stream) {
   return softmax_ce_forward_impl("mvn_softmax_ce_forward_ex", logits_probs, target, batch, classes, s_len,
-                                 loss_part, correct_part, loss_rule, stream);
+                                 loss_part, correct_part, loss_rule, nullptr, stream);
+}
+
+int mvn_softmax_ce_forward_len(float *logits_probs, const long long *target, int batch, int classes, int s_len,
+                               float *loss_part, int32_t *correct_part, int loss_rule, const int32_t *valid,
+                               void *stream) {
+  return softmax_ce_forward_impl("mvn_softmax_ce_forward_len", logits_probs, target, batch, classes, s_len,
+                                 loss_part, correct_part, loss_rule, valid, stream);
 }
 
 int mvn_softmax_ce_backward(const float *probs, const long long *target, int batch, int classes, int s_len,
@@ -507,7 +666,7 @@ int mvn_softmax_ce_backward(const float *probs, const long long *target, int bat
                             int dlogit_ld, int dlogit_col0, int dlogit_cols, void *stream) {
   return softmax_ce_backward_impl("mvn_softmax_ce_backward", probs, target, batch, classes, s_len, scale, upstream,
                                   dlogit, dlogit_batch_stride, dlogit_ld, dlogit_col0, dlogit_cols,
-                                  MVN_LOSS_REFERENCE, stream);
+                                  MVN_LOSS_REFERENCE, nullptr, stream);
 }
 
 int mvn_softmax_ce_backward_ex(const float *probs, const long long *target, int batch, int classes, int s_len,
@@ -515,7 +674,16 @@ int mvn_softmax_ce_backward_ex(const float *probs, const long long *target, int 
                                int dlogit_ld, int dlogit_col0, int dlogit_cols, int loss_rule, void *stream) {
   return softmax_ce_backward_impl("mvn_softmax_ce_backward_ex", probs, target, batch, classes, s_len, scale,
                                   upstream, dlogit, dlogit_batch_stride, dlogit_ld, dlogit_col0, dlogit_cols,
-                                  loss_rule, stream);
+                                  loss_rule, nullptr, stream);
+}
+
+int mvn_softmax_ce_backward_len(const float *probs, const long long *target, int batch, int classes, int s_len,
+                                float scale, const float *upstream, float *dlogit, long long dlogit_batch_stride,
+                                int dlogit_ld, int dlogit_col0, int dlogit_cols, int loss_rule, const int32_t *valid,
+                                void *stream) {
+  return softmax_ce_backward_impl("mvn_softmax_ce_backward_len", probs, target, batch, classes, s_len, scale,
+                                  upstream, dlogit, dlogit_batch_stride, dlogit_ld, dlogit_col0, dlogit_cols,
+                                  loss_rule, valid, stream);
 }
 
 int mvn_adamw_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n, float lr,

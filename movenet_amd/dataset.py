@@ -35,9 +35,12 @@ from .utils.weights import one_hot
 
 
 class Batch:
-    def __init__(self, audio, video, contexts, filepaths, info):
+    def __init__(self, audio, video, contexts, filepaths, info, lengths=None):
         self.audio, self.video = audio, video
         self.contexts, self.filepaths, self.info = contexts, filepaths, info
+        # real samples per clip where the rows end in padding (WavFolderLoader(clip_length="native")), else None;
+        # an attribute beside the five fields the batch unpacks into
+        self.lengths = lengths
 
     def pin_memory(self):
         self.audio = self.audio.pin_memory()
@@ -251,12 +254,14 @@ class _IndexCache:
     def __init__(self, max_bytes: int):
         self.max_bytes, self.bytes = int(max_bytes), 0
         self.rows: dict = {}
+        self.lengths: dict = {}  # clip -> real samples of its row (by-rate rows end in silence), beside the indices
         self.hits = self.misses = 0
 
-    def put(self, key, row: torch.Tensor) -> None:
+    def put(self, key, row: torch.Tensor, length: Optional[int] = None) -> None:
         size = row.numel() * 2
         if key not in self.rows and self.bytes + size <= self.max_bytes:
             self.rows[key] = row.to(torch.int16)
+            self.lengths[key] = row.numel() if length is None else int(length)
             self.bytes += size
 
 
@@ -343,14 +348,36 @@ class WavFolderLoader:
       setting and device; a cached clip costs no file read, no upload and no launch.  ``Batch.video`` is
       ``levels.float() * fp32(1 / 255)``: the [0, 1] of the pre-made form.  (The reference's loader hands its model
       0 .. 255; that range is not offered.)  The kernel's per-clip status of every launch is read once, when the
-      epoch's last batch has been handed out, and a refusal raises there: iterating itself never waits for the GPU."""
+      epoch's last batch has been handed out, and a refusal raises there: iterating itself never waits for the GPU.
+
+    Clips of their own length (``clip_length="native"``; the default ``"resample"`` is the rule above, to
+    the bit): every clip is resampled to ONE rate, ``audio_rate``, instead of onto one width -- clip b comes out
+    ``n_b = min(frames, round(frames_b * audio_rate / rate_b))`` samples long (``native_plan``), a clip that would come
+    out longer contributes its head, the first ``ceil(frames * rate_b / audio_rate)`` source frames resampled to
+    ``frames`` -- into rows of the unchanged width ``frames`` with silence behind it (ops.audio_frontend_var), and
+    ``Batch.lengths`` says how many samples of each row are real; the index cache keeps the lengths beside the
+    indices.  With ``batch_subsample_frac`` the window is drawn as above and a clip's length inside it is
+    ``clamp(len_b - start, 0, n)``.  Refused with ``use_video`` (video batches are fixed at ``frames``)."""
+
+    @staticmethod
+    def native_plan(clip_frames: int, clip_rate: int, frames: int, audio_rate: int):
+        """(source frames read, samples they are resampled to) of one clip under ``clip_length="native"``."""
+        n = int(round(clip_frames * audio_rate / clip_rate))
+        if n > frames:
+            return min(int(clip_frames), int(math.ceil(frames * clip_rate / audio_rate))), int(frames)
+        return int(clip_frames), max(n, 1)
+
+    @staticmethod
+    def cropped_lengths(lengths, start: int, n: int):
+        """Lengths of the clips inside the window [start, start + n) of their rows."""
+        return [min(max(int(v) - start, 0), n) for v in lengths]
 
     def __init__(self, root, input_channels: int, batch_size: int, train: bool = True,
                  rank: int = 0, world_size: int = 1, shuffle: bool = False,
                  batch_subsample_frac: Optional[float] = None, use_video: bool = False,
                  normalize_audio: bool = True, device=None, cache_bytes: int = 4 << 30,
                  video_antialias: bool = False, video_cache_bytes: int = 4 << 30,
-                 **_ignored):
+                 clip_length: str = "resample", audio_rate: int = 16000, **_ignored):
         import os
         from pathlib import Path
         from . import wavenet as W
@@ -366,6 +393,14 @@ class WavFolderLoader:
             raise ValueError("video batches need frames % 1000 == 0 and no batch_subsample_frac "
                              "(the reference crops audio and video independently, dataset.py:232-242, "
                              "which its own size assert then rejects)")
+        if clip_length not in ("resample", "native"):
+            raise ValueError(f"clip_length must be 'resample' or 'native', got {clip_length!r}")
+        if isinstance(audio_rate, bool) or not isinstance(audio_rate, int) or audio_rate < 1:
+            raise ValueError(f"audio_rate must be a positive integer, got {audio_rate!r}")
+        self.native, self.audio_rate = clip_length == "native", int(audio_rate)
+        if self.native and use_video:
+            raise ValueError(f"clip_length='native' cannot be combined with use_video: video batches are fixed at "
+                             f"{self.frames} frames")
         if input_channels > 32768:
             raise ValueError("input_channels above 32768 do not fit the int16 index cache")
         if video_antialias not in (False, True, 0, 1):
@@ -382,7 +417,9 @@ class WavFolderLoader:
                 h = read_wav_header(str(fp))
                 if h["frames"] < 1:
                     raise ValueError(f"{fp}: no audio frames")
-                if h["frames"] > 100 * self.frames:
+                if self.native and h["rate"] > 100 * self.audio_rate:
+                    raise ValueError(f"{fp}: a rate of {h['rate']} Hz is more than 100 x audio_rate {self.audio_rate}")
+                if not self.native and h["frames"] > 100 * self.frames:
                     raise ValueError(f"{fp}: {h['frames']} frames is more than 100 x the {self.frames} frames "
                                      "the front end resamples to")
                 if use_video and not fp.with_suffix(".npy").is_file():
@@ -400,6 +437,10 @@ class WavFolderLoader:
                           audio_orig_dim=int(h["frames"])) for i, (_, _, h) in enumerate(self.index)]
         self.n_clips = len(self.index)
         key = (os.path.abspath(str(self.root_path)), self.Q, self.frames, self.normalize, str(self.device))
+        if self.native:  # (by-rate rows are other rows: a cache of their own per rate)
+            key += ("native", self.audio_rate)
+        self.plans = [self.native_plan(h["frames"], h["rate"], self.frames, self.audio_rate) if self.native
+                      else (int(h["frames"]), self.frames) for _, _, h in self.index]
         cache = _INDEX_CACHES.get(key)
         if cache is None or cache.max_bytes != int(cache_bytes):
             cache = _INDEX_CACHES[key] = _IndexCache(cache_bytes)
@@ -511,7 +552,7 @@ class WavFolderLoader:
     def _indices(self, ids: List[int]) -> torch.Tensor:
         """(B, N) int32 class indices of the clips on the device: cached rows as they are, the others read,
         uploaded and sent through the front end in ONE launch pair."""
-        from .ops import audio_clip_descriptors, audio_frontend
+        from .ops import audio_clip_descriptors, audio_clip_var_descriptors, audio_frontend, audio_frontend_var
         cache, dev = self.cache, self.device
         todo = [i for i in dict.fromkeys(ids) if i not in cache.rows]
         cache.hits += sum(i in cache.rows for i in ids)
@@ -519,19 +560,27 @@ class WavFolderLoader:
         fresh = {}
         if todo:
             clips = [read_wav_pcm16(self.index[i][1]) for i in todo]
+            if self.native:  # a clip that would come out longer than the row contributes its head
+                clips = [(c[0].reshape(-1)[:self.plans[i][0] * c[2]], self.plans[i][0], c[2])
+                         for i, c in zip(todo, clips)]
             total = sum(c[0].size for c in clips)
             # (padded to a 256 Ki-sample step: batches of like-sized clips reuse the ring's pinned buffers)
             pcm = np.zeros(-(-total // (1 << 18)) * (1 << 18), dtype=np.int16)
             np.concatenate([c[0] for c in clips], out=pcm[:total])
             frames, channels = [c[1] for c in clips], [c[2] for c in clips]
             d_pcm = _PinnedRing.to_device(_ring("pcm", dev).stage(pcm), dev)
-            d_desc = _PinnedRing.to_device(
-                _ring("clips", dev).stage(audio_clip_descriptors(frames, channels)), dev)
-            idx = audio_frontend(d_pcm, frames, channels, self.Q, n_out=self.frames, normalize=self.normalize,
-                                 descriptors=d_desc)
+            if self.native:
+                d_desc = _PinnedRing.to_device(_ring("clips_var", dev).stage(
+                    audio_clip_var_descriptors(frames, channels, [self.plans[i][1] for i in todo])), dev)
+                idx = audio_frontend_var(d_pcm, d_desc, self.Q, self.frames, normalize=self.normalize)
+            else:
+                d_desc = _PinnedRing.to_device(
+                    _ring("clips", dev).stage(audio_clip_descriptors(frames, channels)), dev)
+                idx = audio_frontend(d_pcm, frames, channels, self.Q, n_out=self.frames, normalize=self.normalize,
+                                     descriptors=d_desc)
             for row, i in enumerate(todo):
                 fresh[i] = idx[row]
-                cache.put(i, idx[row])
+                cache.put(i, idx[row], self.plans[i][1])
         if len(todo) == len(ids) and todo == list(ids):
             return idx
         return torch.stack([fresh[i] if i in fresh else cache.rows[i].to(torch.int32) for i in ids])
@@ -549,10 +598,13 @@ class WavFolderLoader:
             with torch.cuda.device(dev):
                 idx = self._indices(ids)
                 B, T = idx.shape
+                lengths = [self.cache.lengths.get(i, self.plans[i][1]) for i in ids] if self.native else None
                 if self.frac is not None:  # dataset.py:232-237, on the indices: only the crop is expanded
                     n = math.ceil(T * self.frac)
                     start = crop_rng.randint(0, T - n)
                     idx, T = idx[:, start:start + n], n
+                    if lengths is not None:
+                        lengths = self.cropped_lengths(lengths, start, n)
                 audio = torch.empty(B, self.Q, T, dtype=torch.float32, device=dev)
                 N.check(N.lib().mvn_index_to_onehot(idx.data_ptr(), idx.stride(0), audio.data_ptr(), B, self.Q, T,
                                                     torch.cuda.current_stream(dev).cuda_stream),
@@ -561,7 +613,7 @@ class WavFolderLoader:
             if self.use_video:
                 video = self._video_batch(ids)
             yield Batch(audio, video, [self.index[i][0] for i in ids], [self.filepaths[i] for i in ids],
-                        [self.info[i] for i in ids])
+                        [self.info[i] for i in ids], lengths=lengths)
         self.check_video_status()
 
 
@@ -595,8 +647,8 @@ def get_dataloader(filepath, input_channels: int, batch_size: int = 64, train: b
     """Signature of movenet/dataset.py:59-98.  ``synthetic://...`` gives a SyntheticLoader; an existing directory
     with a ``train`` or ``valid`` sub-folder gives a WavFolderLoader; anything else raises ValueError."""
     if not str(filepath).startswith("synthetic://") and _is_wav_folder(filepath):
-        extra = {k: kwargs[k] for k in ("cache_bytes", "video_antialias", "video_cache_bytes")
-                 if k in kwargs}
+        extra = {k: kwargs[k] for k in ("cache_bytes", "video_antialias", "video_cache_bytes", "clip_length",
+                                        "audio_rate") if k in kwargs}
         return WavFolderLoader(filepath, input_channels, batch_size, train=train, rank=rank,
                                world_size=world_size, shuffle=kwargs.get("shuffle", False),
                                batch_subsample_frac=batch_subsample_frac, use_video=use_video,

@@ -347,20 +347,71 @@ def _grads_for_autograd(ctx_, grads, dctx, dgvec, n_fixed, need):
     return (*([None] * (n_fixed - 2)), dcontext, dgvec if need[n_fixed - 1] else None, *result)
 
 
+def valid_columns(lengths, T: int, RF: int):
+    """Per-sequence count of loss columns from per-sequence lengths: ``valid_b = clamp(len_b - RF, 0, S)`` with
+    ``S = T - RF`` (column s predicts sample RF + s, so it counts when that sample is real).  ``lengths``: (B,) host
+    sequence, numpy array or integer tensor of ``0 <= len_b <= T``.  Returns a list of ints; ValueError -- before
+    anything is launched -- for a wrong shape, a non-integer, a negative length or one above ``T``.  A tensor on the
+    GPU is read once through the pinned word channel of the one-hot check (generation.HostWords)."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.dim() != 1 or lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool:
+            raise ValueError(f"lengths must be a (batch,) integer tensor, got {tuple(lengths.shape)} {lengths.dtype}")
+        if lengths.is_cuda:
+            from .generation import HostWords
+            words = lengths.detach().clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()  # (a refused value stays one)
+            tokens = [HostWords.publish(words[i:i + HostWords.MAXW]) for i in range(0, words.numel(), HostWords.MAXW)]
+            values = [int(v) for t in tokens for v in HostWords.read(t)]
+        else:
+            values = lengths.tolist()
+    else:
+        if isinstance(lengths, (str, bytes)) or not hasattr(lengths, "__len__"):
+            raise ValueError(f"lengths must be a sequence of one integer per sequence, got {lengths!r}")
+        if getattr(lengths, "ndim", 1) != 1:
+            raise ValueError(f"lengths must be one-dimensional, got shape {getattr(lengths, 'shape', None)}")
+        values = lengths.tolist() if hasattr(lengths, "tolist") else list(lengths)
+    S = max(int(T) - int(RF), 0)
+    out = []
+    for b, v in enumerate(values):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"lengths[{b}] = {v!r} is not an integer")
+        if v < 0 or v > T:
+            raise ValueError(f"lengths[{b}] = {v} lies outside [0, {T}]")
+        out.append(min(max(v - int(RF), 0), S))
+    return out
+
+
+def _valid_for_batch(lengths, B: int, T: int, RF: int):
+    """``lengths`` of a (B, ., T) batch -> host list of valid column counts (None stays None)."""
+    if lengths is None:
+        return None
+    valid = valid_columns(lengths, T, RF)
+    if len(valid) != B:
+        raise ValueError(f"lengths names {len(valid)} sequences, the batch holds {B}")
+    return valid
+
+
+def counts_to_device(valid, device) -> torch.Tensor:
+    """Host list of column counts -> (B,) int32 on ``device`` through pinned memory: the copy is asynchronous for
+    the host (one from pageable memory is staged and may block it)."""
+    with torch.cuda.device(device):
+        return torch.tensor(valid, dtype=torch.int32).pin_memory().to(device, non_blocking=True)
+
+
 class _WaveNetLossFunction(torch.autograd.Function):
     """Forward + the trainer's loss in one autograd node (row F3): the head's logits become
     probabilities and the loss / accuracy partial sums in ONE pass (mvn_softmax_ce_forward_ex);
     backward differentiates loss -> logits in ONE pass (mvn_softmax_ce_backward_ex) straight into
-    mvn_backward's dlogit buffer.  args: mode (SequenceMode), dims, names, idx, target (B,S) int64, ctx, gvec,
-    *params; returns (loss, accuracy, probs).  ``mode.loss_rule`` picks the loss: cross_entropy on the
+    mvn_backward's dlogit buffer.  args: mode (SequenceMode), dims, names, idx, target (B,S) int64, valid, ctx,
+    gvec, *params; returns (loss, accuracy, probs).  ``valid``: None -- every column counts, the _ex calls -- or
+    ``(counts, scale)``: (B,) int32 on the device and the host's 1 / max(sum of counts, 1), for the _len calls.  ``mode.loss_rule`` picks the loss: cross_entropy on the
     probabilities, or the negative log-likelihood of softmax(logits)."""
-    N_FIXED = 7
+    N_FIXED = 8
 
     @staticmethod
-    def forward(ctx_, mode, dims, names, idx, target, context, gvec, *params):
+    def forward(ctx_, mode, dims, names, idx, target, valid, context, gvec, *params):
         lib = N.lib()
         sd = dict(zip(names, params))
-        save = any(ctx_.needs_input_grad[5:]) and mode.grad_mode
+        save = any(ctx_.needs_input_grad[6:]) and mode.grad_mode
         # logits, last column dropped
         gvec = None if gvec is None else gvec.detach().to(torch.float32).contiguous()
         out, buf = run_forward(dims, sd, idx, False, True, save, mode, context if gvec is None else gvec)
@@ -372,16 +423,28 @@ class _WaveNetLossFunction(torch.autograd.Function):
             parts = max(lib.mvn_ce_parts(B, S), 1)
             loss_part = torch.zeros(parts, dtype=torch.float32, device=out.device)
             ok_part = torch.zeros(parts, dtype=torch.int32, device=out.device)
-            N.check(lib.mvn_softmax_ce_forward_ex(out.data_ptr(), tg.data_ptr(), B, Q, S, loss_part.data_ptr(),
-                                                  ok_part.data_ptr(), int(mode.loss_rule), _stream_ptr(out.device)),
-                    "mvn_softmax_ce_forward_ex")
-        n = max(B * S, 1)
-        loss = loss_part.sum() / n
-        acc = ok_part.sum().to(torch.float32) / n
+            if valid is None:
+                N.check(lib.mvn_softmax_ce_forward_ex(out.data_ptr(), tg.data_ptr(), B, Q, S, loss_part.data_ptr(),
+                                                      ok_part.data_ptr(), int(mode.loss_rule),
+                                                      _stream_ptr(out.device)), "mvn_softmax_ce_forward_ex")
+            else:
+                if tuple(valid[0].shape) != (B,) or valid[0].dtype != torch.int32 or valid[0].device != out.device:
+                    raise ValueError(f"valid counts must be ({B},) int32 on {out.device}")
+                N.check(lib.mvn_softmax_ce_forward_len(out.data_ptr(), tg.data_ptr(), B, Q, S, loss_part.data_ptr(),
+                                                       ok_part.data_ptr(), int(mode.loss_rule), valid[0].data_ptr(),
+                                                       _stream_ptr(out.device)), "mvn_softmax_ce_forward_len")
+        if valid is None:
+            n = max(B * S, 1)
+            loss = loss_part.sum() / n
+            acc = ok_part.sum().to(torch.float32) / n
+        else:
+            loss = loss_part.sum() * valid[1]
+            acc = ok_part.sum().to(torch.float32) * valid[1]
+        ctx_.valid_scale = None if valid is None else valid[1]
         ctx_.mode, ctx_.dims, ctx_.names, ctx_.idx, ctx_.buf, ctx_.gvec = mode, dims, names, idx, buf, gvec
         ctx_.normalize, ctx_.remove_last, ctx_.saved_fwd = True, True, save
         ctx_.has_context = context is not None
-        ctx_.save_for_backward(out, tg, *params)
+        ctx_.save_for_backward(out, tg, *(() if valid is None else (valid[0],)), *params)
         ctx_.mark_non_differentiable(acc, out)
         return loss, acc, out
 
@@ -389,10 +452,17 @@ class _WaveNetLossFunction(torch.autograd.Function):
     def backward(ctx_, dloss, _dacc, _dprobs):
         lib = N.lib()
         probs, tg, *params = ctx_.saved_tensors
+        counts = params.pop(0) if ctx_.valid_scale is not None else None
         B, Q, S = probs.shape
         up = dloss.detach().to(device=probs.device, dtype=torch.float32).reshape(1).contiguous()
 
         def fill(dlogit, Sp, pad):
+            if counts is not None:
+                N.check(lib.mvn_softmax_ce_backward_len(
+                    probs.data_ptr(), tg.data_ptr(), B, Q, S, ctx_.valid_scale, up.data_ptr(), dlogit.data_ptr(), Q * Sp, Sp,
+                    pad, S + 1, int(ctx_.mode.loss_rule), counts.data_ptr(), _stream_ptr(probs.device)),
+                    "mvn_softmax_ce_backward_len")
+                return
             N.check(lib.mvn_softmax_ce_backward_ex(
                 probs.data_ptr(), tg.data_ptr(), B, Q, S, 1.0 / max(B * S, 1), up.data_ptr(),
                 dlogit.data_ptr(), Q * Sp, Sp, pad, S + 1, int(ctx_.mode.loss_rule), _stream_ptr(probs.device)),
@@ -605,7 +675,8 @@ def wavenet_forward(model, audio: torch.Tensor, context=None, output_unnormalize
     return out if audio.dtype == torch.float32 else out.to(audio.dtype)
 
 
-def wavenet_forward_loss(model, audio: torch.Tensor, context=None, target=None, loss_rule=None, gvec=None):
+def wavenet_forward_loss(model, audio: torch.Tensor, context=None, target=None, loss_rule=None, gvec=None,
+                         lengths=None):
     """(loss, accuracy, probabilities) of one trainer step in one autograd node:
     ``output = model(audio, video)`` (probabilities, Q1), ``target =
     audio[:, :, RF:].argmax(1)``, ``F.cross_entropy(output, target)`` (on probabilities, Q2) and
@@ -615,22 +686,31 @@ def wavenet_forward_loss(model, audio: torch.Tensor, context=None, target=None, 
 
     ``loss_rule`` ("reference" / "model"; default: ``model.loss_rule``): under "model" the loss is
     ``F.cross_entropy(logits, target)`` instead -- the mean negative log-likelihood, in nats, of the
-    distribution ``generate_sampling = "model"`` draws from; accuracy and probabilities are the same."""
+    distribution ``generate_sampling = "model"`` draws from; accuracy and probabilities are the same.
+
+    ``lengths`` ((B,) host sequence or integer tensor; default None: every column counts, today's calls): sequence b
+    holds ``lengths[b]`` real samples and padding behind them.  Loss and accuracy are then sums over the valid
+    columns (``valid_columns``) divided by ``max(N_valid, 1)``, and d loss / d logits is exactly 0 on every other
+    column (mvn_softmax_ce_*_len).  A host sequence adds no synchronisation: the divisor is formed on the host."""
     rule = N.loss_rule(getattr(model, "loss_rule", "reference") if loss_rule is None else loss_rule)
     mode = plan_sequence(model, context is not None, gvec is not None)
     model.compute_output_size(audio)
+    valid = _valid_for_batch(lengths, int(audio.shape[0]), int(audio.shape[2]), model.receptive_fields)
+    if valid is not None:
+        _require_gpu(audio, "audio")
+        valid = (counts_to_device(valid, audio.device), 1.0 / max(sum(valid), 1))
     mode, context, gvec = place_sequence(model, mode, context, gvec, int(audio.shape[0]), int(audio.shape[2]),
                                          loss_rule=rule)
     rf = model.receptive_fields
     idx, check = model._indices_async(audio)
     names, params = _decoder_params(model, mode.conditioning != "none")
     tg = idx[:, rf:].to(torch.int64) if target is None else target
-    res = _WaveNetLossFunction.apply(mode, model._dims, names, idx, tg, context, gvec, *params)
+    res = _WaveNetLossFunction.apply(mode, model._dims, names, idx, tg, valid, context, gvec, *params)
     if not model._all_one_hot(check):  # (read after the enqueue: no idle GPU) dense causal conv
         del res  # release the discarded pass (saved activations) before the rerun allocates
         dense = audio.detach().to(torch.float32).contiguous()
         tg = audio[:, :, rf:].argmax(1) if target is None else target
-        res = _WaveNetLossFunction.apply(mode, model._dims, names, dense, tg, context, gvec, *params)
+        res = _WaveNetLossFunction.apply(mode, model._dims, names, dense, tg, valid, context, gvec, *params)
     return res
 
 
@@ -643,14 +723,16 @@ def score_temperature(temperature) -> float:
 
 
 def score_logits(logits: torch.Tensor, target: torch.Tensor, temperature: float = 1.0, entropy: bool = False,
-                 rank: bool = False) -> dict:
+                 rank: bool = False, valid=None) -> dict:
     """Per-position log-likelihood of ``target`` under ``softmax(logits / temperature)`` in one read-only pass over
     the logits (mvn_score_columns): no probability tensor, ``logits`` untouched.  ``logits`` (B, Q, S) float32 on the
     GPU, ``target`` (B, S) integer classes (clamped to [0, Q-1]).  Returns a dict: ``logp`` (B, S) in nats,
     ``seq_nll`` (B,) = -logp.sum(1), ``seq_correct`` (B,) int32 = the columns whose target is the first maximum, and
     on request ``entropy`` (B, S) of the distribution and ``rank`` (B, S) int32 of the target in it (0: the first
-    maximum).  The sums are formed in a fixed order: the same bits on every call.  ValueError / RuntimeError before
-    any launch for a bad temperature, a shape mismatch or a CPU tensor."""
+    maximum).  The sums are formed in a fixed order: the same bits on every call.  ``valid`` ((B,) int32 on the
+    logits' device; default None: every column counts): sequence b counts its first ``valid[b]`` columns only -- the
+    others come back as logp = entropy = 0, rank = -1 and stay out of the sums (mvn_score_columns_len).  ValueError /
+    RuntimeError before any launch for a bad temperature, a shape mismatch or a CPU tensor."""
     temperature = score_temperature(temperature)
     _require_gpu(logits, "logits")
     if logits.dim() != 3 or logits.dtype != torch.float32:
@@ -663,6 +745,9 @@ def score_logits(logits: torch.Tensor, target: torch.Tensor, temperature: float 
     if Q < 1:
         raise ValueError("logits hold no classes")
     dev = logits.device
+    if valid is not None and (not isinstance(valid, torch.Tensor) or tuple(valid.shape) != (B,)
+                              or valid.dtype != torch.int32 or valid.device != dev):
+        raise ValueError(f"valid must be a ({B},) int32 tensor on {dev}")
     x = logits.detach().contiguous()
     tg = target.detach().to(device=dev, dtype=torch.int64).contiguous()
     lib = N.lib()
@@ -676,16 +761,19 @@ def score_logits(logits: torch.Tensor, target: torch.Tensor, temperature: float 
             out["rank"] = torch.empty(B, S, dtype=torch.int32, device=dev)
         n = lib.mvn_score_scratch_floats(B, S)
         scratch = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
-        N.check(lib.mvn_score_columns(x.data_ptr(), tg.data_ptr(), B, Q, S, temperature, out["logp"].data_ptr(),
-                                      out["entropy"].data_ptr() if entropy else None,
-                                      out["rank"].data_ptr() if rank else None, out["seq_nll"].data_ptr(),
-                                      out["seq_correct"].data_ptr(), scratch.data_ptr(), n, _stream_ptr(dev)),
-                "mvn_score_columns")
+        args = (x.data_ptr(), tg.data_ptr(), B, Q, S, temperature, out["logp"].data_ptr(),
+                out["entropy"].data_ptr() if entropy else None, out["rank"].data_ptr() if rank else None,
+                out["seq_nll"].data_ptr(), out["seq_correct"].data_ptr(), scratch.data_ptr(), n)
+        if valid is None:
+            N.check(lib.mvn_score_columns(*args, _stream_ptr(dev)), "mvn_score_columns")
+        else:
+            N.check(lib.mvn_score_columns_len(*args, valid.contiguous().data_ptr(), _stream_ptr(dev)),
+                    "mvn_score_columns_len")
     return out
 
 
 def wavenet_score(model, audio: torch.Tensor, context=None, gvec=None, temperature: float = 1.0,
-                  entropy: bool = False, rank: bool = False) -> dict:
+                  entropy: bool = False, rank: bool = False, valid=None) -> dict:
     """``score_logits`` of the model's own logits for ``audio`` against ``audio[:, :, RF:]`` (WaveNet.score): the
     forward's checks and kernels -- whatever ``forward_precision`` and ``global_path`` say -- with nothing saved and
     nothing normalised, then mvn_score_columns on what the head wrote."""
@@ -693,7 +781,7 @@ def wavenet_score(model, audio: torch.Tensor, context=None, gvec=None, temperatu
     mode = plan_sequence(model, context is not None, gvec is not None)
     model.compute_output_size(audio)  # ValueError when T < RF
     idx, check = model._indices_async(audio)
-    out = score_indices(model, idx, context, gvec, temperature, entropy, rank, mode)
+    out = score_indices(model, idx, context, gvec, temperature, entropy, rank, mode, valid=valid)
     if not model._all_one_hot(check):  # (read after the enqueue, as forward reads it)
         raise ValueError("WaveNet.score expects one-hot audio (the target is its class index): a column of the input "
                          "is not one-hot")
@@ -701,7 +789,7 @@ def wavenet_score(model, audio: torch.Tensor, context=None, gvec=None, temperatu
 
 
 def score_indices(model, idx: torch.Tensor, context, gvec, temperature: float, entropy: bool, rank: bool,
-                  mode: SequenceMode) -> dict:
+                  mode: SequenceMode, valid=None) -> dict:
     """The scoring pass on class indices ``idx`` (B, T) int32 (what WaveNet.score and WaveNet.classify share);
     ``mode``: plan_sequence's, placed here for the chunk's batch."""
     B, T = idx.shape
@@ -711,7 +799,8 @@ def score_indices(model, idx: torch.Tensor, context, gvec, temperature: float, e
     if gvec is not None:
         gvec = gvec.detach().to(torch.float32).contiguous()
     logits, _ = run_forward(model._dims, sd, idx, False, True, False, mode, context if gvec is None else gvec)
-    return score_logits(logits, idx[:, model.receptive_fields:], temperature, entropy=entropy, rank=rank)
+    return score_logits(logits, idx[:, model.receptive_fields:], temperature, entropy=entropy, rank=rank,
+                        valid=valid)
 
 
 def mu_law_encode(x: torch.Tensor, quantization_channels: int) -> torch.Tensor:
@@ -802,6 +891,49 @@ def audio_frontend(pcm: torch.Tensor, frames, channels, quantization_channels: i
         N.check(lib.mvn_audio_frontend(pcm.data_ptr(), pcm.numel(), descriptors.data_ptr(), B,
                                        int(quantization_channels), int(n_out), int(bool(normalize)), y.data_ptr(),
                                        scratch.data_ptr(), idx.data_ptr(), _stream_ptr(dev)), "mvn_audio_frontend")
+    return (idx, y) if return_waveform else idx
+
+
+_AUDIO_CLIP_VAR = [("offset", "<i8"), ("frames", "<i4"), ("channels", "<i4"), ("n_out", "<i4"), ("reserved", "<i4")]
+
+
+def audio_clip_var_descriptors(frames, channels, n_out, offsets=None):
+    """Host array of mvn_audio_clip_var records (int64 offset, int32 frames, channels, n_out, reserved) as (B, 6)
+    int32; ``offsets`` default to the clips lying back to back in the upload."""
+    import numpy as np
+    rec = np.zeros(len(frames), dtype=_AUDIO_CLIP_VAR)
+    rec["frames"], rec["channels"], rec["n_out"] = frames, channels, n_out
+    if offsets is None:
+        spans = rec["frames"].astype(np.int64) * rec["channels"]
+        offsets = np.concatenate([[0], np.cumsum(spans)[:-1]]) if len(spans) else []
+    rec["offset"] = offsets
+    return rec.view(np.int32).reshape(len(frames), 6)
+
+
+def audio_frontend_var(pcm: torch.Tensor, descriptors: torch.Tensor, quantization_channels: int, width: int,
+                       normalize: bool = True, return_waveform: bool = False):
+    """Waveforms -> class indices by RATE (mvn_audio_frontend_var): clip b resampled as a whole to its own ``n_out``
+    frames -- ``audio_frontend`` of that clip alone with that ``n_out``, bit for bit -- into row b of (B, ``width``)
+    indices, silence (the class of 0.0) behind it.  ``descriptors``: (B, 6) int32 on the GPU
+    (``audio_clip_var_descriptors``), checked on the device: a clip outside the upload or with ``n_out`` outside
+    [1, width] gives a row of -1.  Nothing here waits for the GPU."""
+    _require_gpu(pcm, "pcm")
+    if pcm.dtype != torch.int16 or pcm.dim() != 1 or not pcm.is_contiguous():
+        raise ValueError("pcm must be a contiguous 1-D int16 tensor")
+    _require_gpu(descriptors, "descriptors")
+    if descriptors.dim() != 2 or descriptors.shape[1] != 6 or descriptors.dtype != torch.int32 \
+            or not descriptors.is_contiguous() or descriptors.shape[0] < 1:
+        raise ValueError("descriptors must be a contiguous (B, 6) int32 tensor")
+    B, dev, lib = int(descriptors.shape[0]), pcm.device, N.lib()
+    with torch.cuda.device(dev):
+        y = torch.empty(B, width, dtype=torch.float32, device=dev)
+        idx = torch.empty(B, width, dtype=torch.int32, device=dev)
+        scratch = torch.empty(max(int(lib.mvn_audio_frontend_var_scratch_floats(B, width)), 2), dtype=torch.float32,
+                              device=dev)
+        N.check(lib.mvn_audio_frontend_var(pcm.data_ptr(), pcm.numel(), descriptors.data_ptr(), B,
+                                           int(quantization_channels), int(width), int(bool(normalize)),
+                                           y.data_ptr(), scratch.data_ptr(), idx.data_ptr(), _stream_ptr(dev)),
+                "mvn_audio_frontend_var")
     return (idx, y) if return_waveform else idx
 
 

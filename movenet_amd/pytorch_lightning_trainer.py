@@ -106,7 +106,7 @@ class Dance2Music(nn.Module):
         return (self.config.log_samples_every is not None
                 and (self.current_epoch + 1) % self.config.log_samples_every == 0)
 
-    def _sample_outputs(self, audio, video, labels) -> dict:
+    def _sample_outputs(self, audio, video, labels, lengths=None) -> dict:
         """A step's ``generated_output`` for the sample logger -- ``generate`` on the averaged weights when there are
         any -- and, with ``--score_samples 1`` on a step that generates, the clips' scores under ``"sample_scores"`` (a
         key that is absent otherwise).  (The views are swapped only on a step that generates; the step's autograd graph
@@ -115,14 +115,21 @@ class Dance2Music(nn.Module):
             gen = self.generate(audio, video, labels)  # (which keeps the epoch gate: None on the other epochs)
             out = {"generated_output": gen}
             if gen is not None and getattr(self.config, "score_samples", False):
-                out["sample_scores"] = self.score_samples(gen, audio, video, labels)
+                # (the call without lengths is the call it was: the argument goes only where the batch has lengths)
+                out["sample_scores"] = self.score_samples(gen, audio, video, labels,
+                                                          **({} if lengths is None else {"lengths": lengths}))
+            if gen is not None and lengths is not None:
+                # the logger prompts from a clip's first RF samples: clips shorter than that are left out of its rows
+                out["prompt_ok"] = [int(n) >= self.model.receptive_fields for n in lengths]
         return out
 
-    def score_samples(self, generated, audio, video, labels=None) -> dict:
+    def score_samples(self, generated, audio, video, labels=None, lengths=None) -> dict:
         """bits per sample of the generated clips and of the clips they were prompted from, each under the clip's own
         conditioning (video, label; temperature 1, no guidance: the model's own distribution), from ONE
         ``WaveNet.score`` call: the generated rows (len(sweep) per clip, clip-major, under a temperature sweep), then
-        the sources.  A generated length other than the source's is scored over the common leading part."""
+        the sources.  A generated length other than the source's is scored over the common leading part.  With
+        ``lengths`` (the batch's, clip_length="native") a source is scored over its own real samples only; the
+        generated rows are scored in full."""
         n = generated.shape[0] // audio.shape[0]
         frames = min(int(generated.shape[2]), int(audio.shape[2]))
         if video is not None and frames != int(audio.shape[2]):
@@ -131,7 +138,9 @@ class Dance2Music(nn.Module):
         def both(per_clip):
             return None if per_clip is None else torch.cat([per_clip.repeat_interleave(n, dim=0), per_clip])
         res = self.model.score(torch.cat([generated[:, :, :frames], audio[:, :, :frames].to(generated.dtype)]),
-                               both(video), both(labels))
+                               both(video), both(labels),
+                               lengths=None if lengths is None else
+                               [frames] * int(generated.shape[0]) + [min(int(v), frames) for v in lengths])
         bits = res.bits_per_sample.detach()
         return {"bits_per_sample": bits[:generated.shape[0]], "source_bits_per_sample": bits[generated.shape[0]:]}
 
@@ -166,24 +175,32 @@ class Dance2Music(nn.Module):
         # hooks and overrides keep firing)
         labels = self.class_indices(contexts)  # (None without --use_global)
         extra = {} if labels is None else {"global_features": labels}
+        lengths = getattr(batch, "lengths", None)  # (real samples per row: WavFolderLoader(clip_length="native"))
+        if lengths is not None:
+            from .ops import valid_columns
+            extra["lengths"] = lengths = [int(v) for v in lengths]
+            T, rf = int(audio.shape[2]), self.model.receptive_fields
+            # host arithmetic on the loader's host list: no synchronisation
+            self.log(f"{prefix}_valid_frac", sum(valid_columns(lengths, T, rf)) / max(len(lengths) * (T - rf), 1),
+                     batch_size=self.config.batch_size)
         loss, acc, output = self(audio, video if self.config.use_video else None, return_loss=True, **extra)
         self.log(f"{prefix}_loss", loss, batch_size=self.config.batch_size)
         self.log(f"{prefix}_acc", acc, batch_size=self.config.batch_size)
         if self.model.loss_rule == "model":  # the loss is a likelihood in nats: also in bits (a device scalar, no sync)
             self.log(f"{prefix}_bits_per_sample", loss.detach() / math.log(2.0), batch_size=self.config.batch_size)
-        return loss, output, audio, video, labels
+        return loss, output, audio, video, labels, lengths
 
     def training_step(self, batch, batch_idx):
         if self.model.global_dropout > 0:
             # (generate() leaves the model in eval mode, as the reference's does: with samples logged on train steps the
             # rest of the epoch would run without label dropout, which forward applies in train mode only)
             self.model.train()
-        loss, output, audio, video, labels = self._shared_step(batch, "train")
-        return {"loss": loss, "output": output.detach(), **self._sample_outputs(audio, video, labels)}
+        loss, output, audio, video, labels, lengths = self._shared_step(batch, "train")
+        return {"loss": loss, "output": output.detach(), **self._sample_outputs(audio, video, labels, lengths)}
 
     def validation_step(self, batch, batch_idx):
-        _, output, audio, video, labels = self._shared_step(batch, "val")
-        return {"output": output.detach(), **self._sample_outputs(audio, video, labels)}
+        _, output, audio, video, labels, lengths = self._shared_step(batch, "val")
+        return {"output": output.detach(), **self._sample_outputs(audio, video, labels, lengths)}
 
     def _loader(self, train: bool):
         c = self.config
@@ -196,6 +213,7 @@ class Dance2Music(nn.Module):
             # raw uint8 frames of a WAV folder: the GPU front end's resize rule (getattr: a config pickled before the
             # field existed)
             video_antialias=bool(getattr(c, "video_antialias", False)),
+            clip_length=getattr(c, "clip_length", "resample"), audio_rate=int(getattr(c, "audio_rate", 16000)),
             # row F2: class indices cross PCIe (4 bytes per sample), the (B,Q,T) one-hot the Batch
             # contract asks for is formed on the device
             device=self.device if self.device.type == "cuda" else None)

@@ -44,14 +44,25 @@ def upsample_kernel_size_solver(in_size, out_size, stride=1, padding=0, output_p
     return (int(span / dilation + 1),)
 
 
-class ScoreResult(NamedTuple):
-    """What ``WaveNet.score`` returns (S = T - RF scored positions per sequence)."""
+class _ScoreFields(NamedTuple):
     logp: torch.Tensor             # (B, S) log p(x_t | x_<t, conditioning), nats
     nll: torch.Tensor              # (B,)   -logp.sum(1)
-    bits_per_sample: torch.Tensor  # (B,)   nll / (S ln 2)
+    bits_per_sample: torch.Tensor  # (B,)   nll / (positions ln 2)
     accuracy: torch.Tensor         # (B,)   share of positions whose sample is the first maximum
     entropy: Optional[torch.Tensor] = None  # (B, S) entropy of each predictive distribution, nats (on request)
     rank: Optional[torch.Tensor] = None     # (B, S) int32 rank of the sample in it, 0 = likeliest (on request)
+
+
+class ScoreResult(_ScoreFields):
+    """What ``WaveNet.score`` returns (S = T - RF scored positions per sequence): the six fields above, as a tuple,
+    and ``positions``, (B,) int32 -- how many positions of each sequence were scored (S, or fewer with ``lengths``).
+    ``positions`` is an attribute beside the tuple: code that unpacks the six fields keeps working."""
+    positions: Optional[torch.Tensor] = None
+
+    def __new__(cls, *args, positions=None, **kwargs):
+        self = super().__new__(cls, *args, **kwargs)
+        self.positions = positions
+        return self
 
 
 class WaveNet(nn.Module):
@@ -327,7 +338,7 @@ class WaveNet(nn.Module):
         return out
 
     def forward(self, audio, video=None, global_features=None, output_unnormalized: bool = True,
-                remove_last: bool = True, return_loss: bool = False, target=None):
+                remove_last: bool = True, return_loss: bool = False, target=None, lengths=None):
         """BUILD DEFINITION for video != None: the reference raises a shape error at
         modules.py:75-77; here the upsampled video is added to the filter
         and gate pre-activations at the same absolute time (right-aligned, like the
@@ -346,8 +357,15 @@ class WaveNet(nn.Module):
         ``F.cross_entropy(output, target)`` and accuracy (pytorch_lightning_trainer.py:62-66)
         -- as ONE autograd node (ops.wavenet_forward_loss); going through ``forward`` keeps
         module hooks firing on the fused path.  ``loss_rule = "model"`` makes that loss
-        ``F.cross_entropy`` of the logits instead (the property's docstring)."""
+        ``F.cross_entropy`` of the logits instead (the property's docstring).
+
+        ``lengths`` (with ``return_loss=True`` only; (B,) host sequence or integer tensor, default None): sequence b
+        holds ``lengths[b]`` real samples and padding behind them; loss and accuracy then run over the columns that
+        predict a real sample (``ops.valid_columns``), divided by their number, and the padding's columns receive a
+        gradient of exactly 0.  Refused together with ``video``: video batches are fixed at
+        MAX_AUDIO_FRAMES frames."""
         from .ops import global_vector, plan_sequence, wavenet_forward, wavenet_forward_loss  # HIP full-sequence kernels
+        self._lengths_checks(lengths, video, return_loss)
         gvec = global_vector(self, global_features, int(audio.shape[0]))  # (ValueError before anything is launched)
         if gvec is not None and self.training:  # label dropout: both paths below see an ordinary e
             keep = self.global_dropout_mask(int(audio.shape[0]))
@@ -356,9 +374,19 @@ class WaveNet(nn.Module):
         plan_sequence(self, video is not None, gvec is not None)  # (refused before the video encoder runs)
         context = None if video is None else self.upsample_video(video)
         if return_loss:
-            return wavenet_forward_loss(self, audio, context, target, gvec=gvec)
+            return wavenet_forward_loss(self, audio, context, target, gvec=gvec, lengths=lengths)
         return wavenet_forward(self, audio, context, output_unnormalized=output_unnormalized,
                                remove_last=remove_last, gvec=gvec)
+
+    @staticmethod
+    def _lengths_checks(lengths, video, takes_lengths: bool = True):
+        if lengths is None:
+            return
+        if not takes_lengths:
+            raise ValueError("lengths goes with return_loss=True: without the loss there is nothing to leave out")
+        if video is not None:
+            raise ValueError(f"lengths cannot be combined with video: video batches are fixed at {MAX_AUDIO_FRAMES} "
+                             "frames")
 
     # ---- likelihood of GIVEN audio ---------------------------
     def _score_checks(self, audio, video, global_features):
@@ -370,15 +398,30 @@ class WaveNet(nn.Module):
         return gvec, mode
 
     @staticmethod
-    def _score_result(raw: dict, positions: int) -> "ScoreResult":
+    def _score_result(raw: dict, positions: int, valid=None) -> "ScoreResult":
         nll = raw["seq_nll"]
-        return ScoreResult(logp=raw["logp"], nll=nll, bits_per_sample=nll / (max(positions, 1) * math.log(2.0)),
-                           accuracy=raw["seq_correct"].to(torch.float32) / max(positions, 1),
-                           entropy=raw.get("entropy"), rank=raw.get("rank"))
+        if valid is None:
+            return ScoreResult(logp=raw["logp"], nll=nll, bits_per_sample=nll / (max(positions, 1) * math.log(2.0)),
+                               accuracy=raw["seq_correct"].to(torch.float32) / max(positions, 1),
+                               entropy=raw.get("entropy"), rank=raw.get("rank"),
+                               positions=torch.full_like(raw["seq_correct"], positions))
+        per = valid.clamp(min=1).to(torch.float32)
+        return ScoreResult(logp=raw["logp"], nll=nll, bits_per_sample=nll / (per * math.log(2.0)),
+                           accuracy=raw["seq_correct"].to(torch.float32) / per, entropy=raw.get("entropy"),
+                           rank=raw.get("rank"), positions=valid)
+
+    def _valid_on_device(self, lengths, audio):
+        """``lengths`` -> (B,) int32 valid column counts on the audio's device (None stays None)."""
+        from .ops import _valid_for_batch, counts_to_device
+        valid = _valid_for_batch(lengths, int(audio.shape[0]), int(audio.shape[2]), self.receptive_fields)
+        if valid is None:
+            return None
+        _require_gpu(audio, "audio")
+        return counts_to_device(valid, audio.device)
 
     @torch.no_grad()
     def score(self, audio, video=None, global_features=None, temperature: float = 1.0, entropy: bool = False,
-              rank: bool = False) -> "ScoreResult":
+              rank: bool = False, lengths=None) -> "ScoreResult":
         """How likely ``audio`` is under the model: log p(x_t | x_<t, conditioning) of every sample past the
         receptive field, per position and per sequence, from the logits of one forward pass (same checks, same
         kernels, ``forward_precision`` and ``global_path`` as ``forward``; nothing saved, no probability tensor).
@@ -388,16 +431,23 @@ class WaveNet(nn.Module):
         whose sample is the first maximum, and on request ``entropy`` (B, T - RF) of each predictive distribution
         and ``rank`` (B, T - RF) int32 of the sample in it (else None).  ``nll.mean() / (T - RF)`` is the loss
         ``loss_rule = "model"`` reports for the same input.  Label dropout is never applied, the module's training
-        flag is left as it is, and ``audio`` must be one-hot (ValueError): its class indices are the targets."""
+        flag is left as it is, and ``audio`` must be one-hot (ValueError): its class indices are the targets.
+
+        ``lengths`` (as in ``forward``; default None): sequence b is scored over the positions that predict one of
+        its ``lengths[b]`` real samples -- ``positions`` (B,) int32 holds their number, ``bits_per_sample`` and
+        ``accuracy`` divide by ``max(positions, 1)``, and the other positions come back as logp = entropy = 0 and
+        rank = -1.  Refused together with ``video``."""
         from .ops import score_temperature, wavenet_score
         temperature = score_temperature(temperature)  # (ValueError before the video encoder runs)
+        self._lengths_checks(lengths, video)
         gvec, _ = self._score_checks(audio, video, global_features)
+        valid = self._valid_on_device(lengths, audio)
         context = None if video is None else self.upsample_video(video)
-        raw = wavenet_score(self, audio, context, gvec, temperature, entropy=entropy, rank=rank)
-        return self._score_result(raw, int(audio.shape[2]) - self.receptive_fields)
+        raw = wavenet_score(self, audio, context, gvec, temperature, entropy=entropy, rank=rank, valid=valid)
+        return self._score_result(raw, int(audio.shape[2]) - self.receptive_fields, valid)
 
     @torch.no_grad()
-    def classify(self, audio, video=None, log_prior=None, logits_budget_bytes: int = 1 << 30):
+    def classify(self, audio, video=None, log_prior=None, logits_budget_bytes: int = 1 << 30, lengths=None):
         """Which class label explains ``audio`` best (a model built with ``global_classes = G > 0``; ValueError
         otherwise): returns ``(loglik, posterior)``, both (B, G) -- ``loglik[b, c]`` = log p(x_b | class c), the
         ``-nll`` of ``score`` with ``global_features = c``, and ``posterior`` = softmax(loglik + ``log_prior``)
@@ -405,7 +455,8 @@ class WaveNet(nn.Module):
 
         The (class, sequence) pairs run through the scoring pass of ``score`` in chunks of as many pairs as keep a
         chunk's logits within ``logits_budget_bytes`` (default 1 GiB; at least one pair), the audio's indices and
-        the up-sampled video formed once; each chunk takes the label path ``score`` would take for its batch."""
+        the up-sampled video formed once; each chunk takes the label path ``score`` would take for its batch.
+        ``lengths``: as in ``score`` -- each sequence's likelihood runs over its own real samples."""
         from .ops import score_indices
         G = int(self.global_classes)
         if G <= 0:
@@ -417,7 +468,9 @@ class WaveNet(nn.Module):
             log_prior = torch.as_tensor(log_prior)
             if tuple(log_prior.shape) not in ((G,), (B, G)):
                 raise ValueError(f"log_prior must be ({G},) or ({B}, {G}), got {tuple(log_prior.shape)}")
+        self._lengths_checks(lengths, video)
         _, mode = self._score_checks(audio, video, torch.zeros(B, dtype=torch.int64))
+        valid = self._valid_on_device(lengths, audio)
         context = None if video is None else self.upsample_video(video)
         idx = self._indices_of(audio)  # ValueError unless one-hot
         positions = int(audio.shape[2]) - self.receptive_fields
@@ -430,7 +483,7 @@ class WaveNet(nn.Module):
             rows = pairs[p0:p0 + step]
             seq, cls = rows % B, rows // B
             raw = score_indices(self, idx[seq], None if context is None else context[seq], E[cls], 1.0, False, False,
-                                mode)
+                                mode, valid=None if valid is None else valid[seq])
             nll.append(raw["seq_nll"])
         loglik = -torch.cat(nll).view(G, B).t().contiguous()
         post = loglik.double() if log_prior is None else loglik.double() + log_prior.to(loglik.device).double()
