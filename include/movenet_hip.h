@@ -438,7 +438,11 @@ typedef struct mvn_bwd_buffers {
  * back into `stream` with events before the call returns: to the caller it is ordinary
  * stream-ordered work.  da1 / dlogit / dfg double as scratch of the weight gradients, and so
  * does fwd->z.  index_stride / dense_ld / ctx_ld are checked as in mvn_forward.  S_out == 0
- * (t_len == RF with remove_last): MVN_OK, nothing is launched, `out` / `dout` may be NULL. */
+ * (t_len == RF with remove_last): MVN_OK, nothing is launched, `out` / `dout` may be NULL.
+ * Every refusal of mvn_backward and its siblings below is decided in front of the first launch -- also the
+ * ones that depend on the scratch sizes (buffers the bf16 / one-kernel layer backward cannot run, a context
+ * pass whose slabs do not fit at some layer, input_channels > 8192 without dense audio): a refused call has
+ * written nothing and leaves mvn_last_backward_form() as it was. */
 int mvn_backward(const mvn_dims *dims, const mvn_params *params, const mvn_param_grads *grads,
                  const int32_t *index, int index_stride, int batch, int t_len,
                  const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
@@ -448,7 +452,8 @@ int mvn_backward(const mvn_dims *dims, const mvn_params *params, const mvn_param
  * bf16 operands (dxo, dskip and the weights in the dz / input-gradient products; df | dg, x and z in
  * the weight-gradient products) and fp32 accumulation; the head, the embedding gradient and every
  * buffer stay fp32.  Same dims as mvn_forward_bf16; a batch / length whose scratch the bf16 layer
- * kernel cannot place returns MVN_ERR_UNSUPPORTED before anything is launched. */
+ * kernel cannot place returns MVN_ERR_UNSUPPORTED before anything is launched -- every refusal does (the note at
+ * mvn_backward): also "cannot run these buffers", which used to follow the head's backward. */
 int mvn_backward_bf16(const mvn_dims *dims, const mvn_params *params, const mvn_param_grads *grads,
                       const int32_t *index, int index_stride, int batch, int t_len,
                       const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
@@ -500,7 +505,9 @@ int mvn_context_add_global(float *context_tm, const float *global, int batch, in
  * allow it.  Without a context, or with a scratch too small, it is mvn_backward.
  * mvn_global_fast_path: 1 when mvn_forward_global and mvn_backward_global run this batch / length
  * under the process's MOVENET_HIP_* switches, else 0 (take the general path); the two refuse with
- * MVN_ERR_UNSUPPORTED, before anything is launched, exactly where it returns 0.
+ * MVN_ERR_UNSUPPORTED, before anything is launched, exactly where it returns 0.  So does every other refusal of
+ * mvn_backward_global and mvn_backward_scratch (the note at mvn_backward): buffers the one-kernel layer backward
+ * cannot run, or a context pass that finds no room at some layer, no longer come after the head's backward.
  * mvn_last_backward_form() reports MVN_BWD_FORM_ONE_GLOBAL after mvn_backward_global. */
 int mvn_global_fast_path(const mvn_dims *dims, int batch, int t_len);
 int mvn_global_bias(const mvn_dims *dims, const mvn_params *params, const float *e, int batch,
@@ -535,7 +542,8 @@ int mvn_global_bias_backward(const mvn_dims *dims, const mvn_params *params,
  * skip_channels != 64, for buf->ctx / fwd->ctx != NULL and for a batch / length the bf16 layer kernels
  * cannot place (mvn_global_bf16_path returns 0 exactly there, 1 elsewhere; it consults no switch);
  * MVN_ERR_BAD_ARG for a NULL gbias / scratch / rowsum or scratch_floats below
- * mvn_global_bf16_scratch_floats().  mvn_last_backward_form() reports MVN_BWD_FORM_BF16_GLOBAL. */
+ * mvn_global_bf16_scratch_floats().  "Before anything is launched" holds for every refusal of the backward (the
+ * note at mvn_backward).  mvn_last_backward_form() reports MVN_BWD_FORM_BF16_GLOBAL. */
 int mvn_global_bf16_path(const mvn_dims *dims, int batch, int t_len);
 size_t mvn_global_bf16_scratch_floats(const mvn_dims *dims, int batch, int t_len);
 int mvn_forward_bf16_global(const mvn_dims *dims, const mvn_params *params, const int32_t *index,
@@ -562,7 +570,8 @@ int mvn_backward_bf16_global(const mvn_dims *dims, const mvn_params *params,
  * Refused before anything is launched or written: MVN_ERR_UNSUPPORTED for residual_channels or skip_channels != 64,
  * rows (t_len, ctx_ld) beyond 2^21 and a batch / length the kernels cannot place (mvn_bf16_ctx_path returns 0 exactly
  * there, for any ctx_ld <= 2^21; it consults no switch); MVN_ERR_BAD_ARG for no ctx, no dctx, no dfg, no context-conv
- * parameters or gradients, ctx_ld < t_len, no scratch or one below mvn_bf16_ctx_scratch_floats().
+ * parameters or gradients, ctx_ld < t_len, no scratch or one below mvn_bf16_ctx_scratch_floats(); the same holds for
+ * slabs that do not fit the scratch in either pass (MVN_ERR_UNSUPPORTED; the note at mvn_backward).
  * mvn_last_backward_form() reports MVN_BWD_FORM_BF16_CTX.  mvn_forward_bf16, mvn_backward_bf16 and the _global pair keep
  * refusing a context. */
 #define MVN_BWD_FORM_BF16_CTX 7 /* form 4 for conditioned layers: mvn_backward_bf16_ctx */

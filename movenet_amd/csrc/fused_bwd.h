@@ -49,12 +49,16 @@ static int fb_device_cus() {
 // tile are two whole cache lines (first half 110 -> 103 us per layer, second 172.5 -> 169.8).
 // (Non-temporal loads of the saved activations changed nothing.)
 
-static void fb_chunks(int nt, int batch, int per_cu, int *chunks, int *chunk_t, int tile = W2_T) {
+// (fb_chunks_on: on a device of `cus` CUs -- pure, for the planning functions, which read the count once per call)
+static void fb_chunks_on(int cus, int nt, int batch, int per_cu, int *chunks, int *chunk_t, int tile = W2_T) {
   const int tiles = (nt + tile - 1) / tile;
-  const int want = std::max(1, per_cu * fb_device_cus() / std::max(batch, 1));
+  const int want = std::max(1, per_cu * cus / std::max(batch, 1));
   const int chunk_tiles = std::max(1, (tiles + want - 1) / want);
   *chunks = (tiles + chunk_tiles - 1) / chunk_tiles;
   *chunk_t = chunk_tiles * tile;
+}
+static void fb_chunks(int nt, int batch, int per_cu, int *chunks, int *chunk_t, int tile = W2_T) {
+  fb_chunks_on(fb_device_cus(), nt, batch, per_cu, chunks, chunk_t, tile);
 }
 
 // 16-byte raw buffer accesses: (resource of a tensor and sequence) + (per-lane byte offset, formed
@@ -307,45 +311,40 @@ __global__ __launch_bounds__(32 * RED_SEG) void reduce_rs64_kernel(Op op, const 
   }
 }
 
-// `op` describes where the gradients go (WgRsOp::dw / db); slab: chunks * batch * 128 * 64 floats,
-// bias_scratch: chunks * batch * 128 floats.  False when the scratch is too small (the caller
-// then runs the two-kernel form).
-// The first half's reduction, left for the second half's launch to run together with its own: one
-// reduce launch per layer instead of two (each costs ~5 us, most of it fixed).  `slab_used` floats
-// at the front of the slab scratch stay occupied until then.
+// Launch geometry of the first half on `cus` CUs (one round of two workgroups per CU): slab chunks * batch * 128 * 64
+// floats, bias_scratch chunks * batch * 128 floats (the bias partials are checked too: the scratch was sized for
+// wgrad2's 512-column chunks, and short sequences in small batches launch more workgroups than that has room for).
+// False when the scratch cannot hold it: the caller's plan then takes the two-kernel form.  chunks == 0: nothing to run.
+static bool bwd_dz_wgrs64_fits(int cus, int t_begin, int t_end, int batch, const float *bias_scratch, size_t bias_floats,
+                               const float *slab, size_t slab_floats, int *chunks, int *chunk_t) {
+  *chunks = 0;
+  *chunk_t = 0;
+  if (t_end <= t_begin || batch <= 0) return true;
+  fb_chunks_on(cus, t_end - (t_begin & ~TILE_ALIGN), batch, 2, chunks, chunk_t);
+  return bias_scratch && slab && (size_t)*chunks * batch * 128 * 64 <= slab_floats &&
+         (size_t)*chunks * batch * 128 <= bias_floats;
+}
+// `op` describes where the gradients go (WgRsOp::dw / db).  The first half's reduction is left for the second half's
+// launch to run together with its own: one reduce launch per layer instead of two (each costs ~5 us, most of it
+// fixed).  chunks * batch * 128 * 64 floats at the front of the slab scratch stay occupied until then.
 template <class WgOp>
 struct PendingRsReduce {
   bool on = false;
   WgOp op;
   const float *part = nullptr, *bias = nullptr;
   int nparts = 0;
-  size_t slab_used = 0;
 };
 
 template <class WgOp>
-static bool launch_bwd_dz_wgrs64(const FusedBwdAArgs &a, const WgOp &op, int batch, float *bias_scratch,
-                                 size_t bias_floats, float *slab, size_t slab_floats, hipStream_t s,
-                                 PendingRsReduce<WgOp> *defer = nullptr) {
-  const int nt = a.t_end - (a.t_begin & ~TILE_ALIGN);
-  if (a.t_end <= a.t_begin || batch <= 0) return true;
-  int chunks, chunk_t;
-  fb_chunks(nt, batch, 2, &chunks, &chunk_t);
-  const size_t need = (size_t)chunks * batch * 128 * 64;
-  // (r3: the bias partials -- 128 per workgroup -- are checked too: the scratch was sized for wgrad2's 512-column
-  // chunks, and short sequences in small batches launch more workgroups than that has room for)
-  if (!bias_scratch || !slab || need > slab_floats || (size_t)chunks * batch * 128 > bias_floats) return false;
+static void launch_bwd_dz_wgrs64(const FusedBwdAArgs &a, const WgOp &op, int batch, float *bias_scratch, float *slab,
+                                 int chunks, int chunk_t, hipStream_t s, PendingRsReduce<WgOp> *defer) {
+  if (chunks <= 0) return;
   hipLaunchKernelGGL(bwd_dz_wgrs64_kernel, dim3(chunks * batch), dim3(256), 0, s, a, chunks, chunk_t, bias_scratch, slab);
-  if (defer) {
-    defer->on = true;
-    defer->op = op;
-    defer->part = slab;
-    defer->bias = bias_scratch;
-    defer->nparts = chunks * batch;
-    defer->slab_used = need;
-  } else {
-    hipLaunchKernelGGL(reduce_rs64_kernel<WgOp>, dim3(256 + 4), dim3(32 * RED_SEG), 0, s, op, slab, bias_scratch, chunks * batch);
-  }
-  return true;
+  defer->on = true;
+  defer->op = op;
+  defer->part = slab;
+  defer->bias = bias_scratch;
+  defer->nparts = chunks * batch;
 }
 template <class WgOp>
 static void flush_pending_rs(PendingRsReduce<WgOp> &p, hipStream_t s) {
@@ -554,17 +553,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dctx_wgctx64_kernel(FusedBwdCArgs 
   }
 }
 
-// Launch geometry of the conditioned pass (the first half's): false when the scratch cannot hold it.
-static bool bwd_dctx_wgctx64_fits(int t_begin, int t_end, int batch, const float *bias_scratch, size_t bias_floats,
-                                  const float *slab, size_t slab_floats, int *chunks, int *chunk_t) {
-  const int nt = t_end - (t_begin & ~TILE_ALIGN);
-  *chunks = 0;
-  *chunk_t = 0;
-  if (t_end <= t_begin || batch <= 0) return true;
-  fb_chunks(nt, batch, 2, chunks, chunk_t);
-  return bias_scratch && slab && (size_t)*chunks * batch * 128 * 64 <= slab_floats &&
-         (size_t)*chunks * batch * 128 <= bias_floats;
-}
+// (launch geometry of the conditioned pass: the first half's, bwd_dz_wgrs64_fits, from the same scratch)
 static void launch_bwd_dctx_wgctx64(const FusedBwdCArgs &a, const WgCtxOp &op, int batch, float *bias_scratch,
                                     float *slab, int chunks, int chunk_t, hipStream_t s) {
   if (chunks <= 0) return;
@@ -862,37 +851,34 @@ __global__ __launch_bounds__(32 * RED_SEG) void reduce_layer64_kernel(RsOp rs, c
   }
 }
 
+// Launch geometry of the second half on `cus` CUs (one workgroup per CU): chunks * batch * 128 * 128 floats of `slab`
+// behind the `slab_used` floats a pending first half keeps at its front.  False when they do not fit.
+static bool bwd_dx_wgfg64_fits(int cus, int t_out0, int t_end, int batch, const float *slab, size_t slab_floats,
+                               size_t slab_used, int *chunks, int *chunk_t) {
+  *chunks = 0;
+  *chunk_t = 0;
+  if (slab_used > slab_floats) return false;
+  if (t_end <= t_out0 || batch <= 0) return true;
+  fb_chunks_on(cus, t_end - (t_out0 & ~TILE_ALIGN), batch, 1, chunks, chunk_t);
+  return slab && (size_t)*chunks * batch * 128 * 128 <= slab_floats - slab_used;
+}
+// `slab`: this half's own, behind a pending first half's
 template <class WgOp, class RsOp>
-static int launch_bwd_dx_wgfg64(const FusedBwdBArgs &a, const WgOp &op, int batch, float *slab,
-                                size_t slab_floats, hipStream_t s, bool *done, PendingRsReduce<RsOp> *pend) {
-  if (pend && pend->on) {  // the first half's slabs sit at the front of the scratch until they are reduced
-    if (pend->slab_used > slab_floats) return MVN_OK;
-    slab += pend->slab_used;
-    slab_floats -= pend->slab_used;
-  }
-  *done = false;
-  const int nt = a.t_end - (a.t_out0 & ~TILE_ALIGN);
-  if (a.t_end <= a.t_out0 || batch <= 0) {
-    *done = true;
-    return MVN_OK;
-  }
-  int chunks, chunk_t;
-  fb_chunks(nt, batch, 1, &chunks, &chunk_t);
-  const size_t need = (size_t)chunks * batch * 128 * 128;
-  if (!slab || need > slab_floats) return MVN_OK;
+static int launch_bwd_dx_wgfg64(const FusedBwdBArgs &a, const WgOp &op, int batch, float *slab, int chunks, int chunk_t,
+                                hipStream_t s, PendingRsReduce<RsOp> *pend) {
+  if (chunks <= 0) return MVN_OK;
   const void *fn = (const void *)bwd_dx_wgfg64_kernel;
   const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(bwd_dx_wgfg64)");
   if (rc) return rc;
   hipLaunchKernelGGL(bwd_dx_wgfg64_kernel, dim3(chunks * batch), dim3(512), FBB_LDS_FLOATS * sizeof(float), s, a,
                      chunks, chunk_t, slab);
-  if (pend && pend->on) {
+  if (pend->on) {
     hipLaunchKernelGGL((reduce_layer64_kernel<RsOp, WgOp>), dim3(260 + 128 * 128 / 32), dim3(32 * RED_SEG), 0, s, pend->op,
                        pend->part, pend->bias, pend->nparts, op, slab, chunks * batch);
     pend->on = false;
   } else {
     hipLaunchKernelGGL(slab_reduce_kernel<WgOp>, dim3(128 * 128 / 32), dim3(32 * RED_SEG), 0, s, op, slab, chunks * batch, 128, 128);
   }
-  *done = true;
   return MVN_OK;
 }
 

@@ -580,11 +580,14 @@ struct FusedBwdLPlan {
   float *bias = nullptr, *rs = nullptr, *fg = nullptr;
   size_t used = 0;  // floats of `slab` taken
 };
-static bool bwd_layer64_plan(int t_lo, int t_end, int batch, float *bias_scratch, size_t bias_floats, float *slab,
+// (With both pointers given and n_max >= 1 the answer is true whatever t_lo is: chunks is either <= n_max already or
+// recut to ceil(tiles / ceil(tiles / n_max)) <= n_max, so n * per_wg <= slab_floats and n * 128 <= bias_floats.  A
+// scratch that holds one layer therefore holds every layer.)
+static bool bwd_layer64_plan(int cus, int t_lo, int t_end, int batch, float *bias_scratch, size_t bias_floats, float *slab,
                              size_t slab_floats, FusedBwdLPlan *pl) {
   const int nt = t_end - (t_lo & ~TILE_ALIGN);
   if (t_end <= t_lo || batch <= 0) return true;
-  fb_chunks(nt, batch, 1, &pl->chunks, &pl->chunk_t);
+  fb_chunks_on(cus, nt, batch, 1, &pl->chunks, &pl->chunk_t);
   if (!bias_scratch || !slab) return false;
   // short sequences (the parity tests' sizes): fewer, longer chunks so that the slabs fit the scratch
   const size_t per_wg = 128 * 64 + 128 * 128;

@@ -1072,12 +1072,12 @@ static bool global_backward_fast(const mvn_dims *dims, const Geometry &g, int ba
   return batch >= 1;
 }
 constexpr size_t GC_PER_WG = 128 * 64 + 128 * 128 + 128;  // a workgroup's two slabs and its bias partials
-static size_t global_scratch_floats(const mvn_dims *dims, const Geometry &g, int batch) {
+static size_t global_scratch_floats(const mvn_dims *dims, const Geometry &g, int batch, int cus) {
   // workgroups per sequence of the layer kernel (one per CU) and of the conditioned layers' context pass (two per CU):
   // never more than the tiles of the longest layer, nor than the kernels' chunk counts at any layer (fb_chunks)
   const int t_lo = dilation_of(dims, 0), nt = std::max(1, g.T - (t_lo & ~TILE_ALIGN));
   const int tiles = (nt + W2_T - 1) / W2_T;
-  const int want = std::max(1, 2 * fb_device_cus() / std::max(batch, 1));
+  const int want = std::max(1, 2 * cus / std::max(batch, 1));
   return 2 * (size_t)g.act + (size_t)std::max(1, std::min(tiles, want)) * batch * GC_PER_WG;
 }
 // Global conditioning in bf16 (fused_bf16.h, the GLOBAL instantiations): what the bf16 layer kernels place, whatever
@@ -1089,15 +1089,15 @@ static bool global_bf16_path(const Geometry &g, int batch) {
          rows_fit_rsrc(2 * g.C, g.Tp);
 }
 constexpr size_t GC16_PER_WG = GC_PER_WG + 128;
-static size_t global_bf16_wgs(const mvn_dims *dims, const Geometry &g, int batch) {
+static size_t global_bf16_wgs(const mvn_dims *dims, const Geometry &g, int batch, int cus) {
   // workgroups of the layer kernel at its longest layer (one per CU, never more than its tiles: fb_chunks)
   const int t_lo = dilation_of(dims, 0), nt = std::max(1, g.T - (t_lo & ~TILE_ALIGN));
   const int tiles = (nt + W2_T - 1) / W2_T;
-  const int want = std::max(1, fb_device_cus() / std::max(batch, 1));
+  const int want = std::max(1, cus / std::max(batch, 1));
   return (size_t)std::max(1, std::min(tiles, want)) * batch;
 }
-static size_t global_bf16_scratch_floats(const mvn_dims *dims, const Geometry &g, int batch) {
-  return global_bf16_wgs(dims, g, batch) * GC16_PER_WG;
+static size_t global_bf16_scratch_floats(const mvn_dims *dims, const Geometry &g, int batch, int cus) {
+  return global_bf16_wgs(dims, g, batch, cus) * GC16_PER_WG;
 }
 
 // What one full-sequence pass runs: every extern "C" entry point below fills one in and hands it to forward_impl /
@@ -1200,6 +1200,252 @@ static FwdPlan plan_forward(const SeqMode &m, const Geometry &g, bool has_ctx, i
 static bool global_forward_fast(const Geometry &g) {
   const SeqMode m = {SeqMode::F32, SeqMode::GLOBAL, "mvn_forward_global"};
   return plan_forward(m, g, false, 0, switches(), (size_t)g.act).layer == &LAYER_FORMS[FORM_BF3_STRIP_BIAS];
+}
+
+// The backward's scratch regions and kernel forms, decided once per call: plan_backward is host arithmetic on the mode,
+// the geometry, the dilations, the switches, the CU count and which buffers there are -- no HIP call -- and every
+// refusal that depends on a size is issued there, in front of the first launch.  backward_impl launches what it says.
+// Every region is carved exactly once:
+//   tensor        regions, in the order of their use                                  free for them
+//   bwd->dfg      wg_bias (launch_wgrad's bias partials: the head's fall-back, the   until the layer loop writes df | dg;
+//                 generic loop) -- or head_slab | head_bias (the head's wgrad2);     the generic loop reduces each use
+//                 spair[1] = its two row halves (scatter form, audio only)           before it writes dfg
+//   fwd->z        head_img behind the forward's images; then sc_slab | sc_bias of    between the two passes; the head's
+//                 mvn_backward_bf16 at short outputs (cx_* the same)                  backward runs before the loop
+//   bwd->da1      slab | bias2 ("reserved": the halves, wgrad2, and sc_* / cx_* of   dead once the head's conv1 data
+//                 the scatter form) -- or, too small for that and without context,   gradient has run
+//                 sc_slab | sc_bias ("small"); embed_tab = slab                      (embed_tab: behind the loop)
+//   bwd->dlogit   ctx_wg_bias (generic loop, conditioned) -- or spair[1] (scatter    dead behind the head's backward
+//                 form, conditioned, no scratch from the caller)
+//   m.scratch     fp32 + label / context, bf16 + context: spair[1] | sc_slab | sc_bias, cx_* the same (bf16: the layer
+//                 pass held to audio_bf16_wgs of them);  bf16 + label: sc_slab | sc_bias | g_part (row-sum partials)
+// embed_tab is cx_slab instead where bf16 finds the per-chunk tables no room in da1.
+struct Region { float *p = nullptr; size_t floats = 0; };
+enum EmbedGradForm { EMBED_DENSE_AUDIO, EMBED_MFMA, EMBED_LDS, EMBED_TABLES, EMBED_ATOMICS };
+struct BwdPlan {
+  int cus;
+  int A_lo[4096];                // first valid time of layer l's input
+  Region wg_bias, head_slab, head_bias;  // head_bias.p == nullptr: launch_wgrad with wg_bias (which may be none: atomics)
+  float *head_img;               // the head's data gradients as bf16 x 3 strips (fused_fwd_bf3.h), else the generic kernel
+  Region slab, bias2;            // the layer loop's halves and wgrad2
+  Region sc_slab, sc_bias, cx_slab, cx_bias;  // scatter form: the layer kernel's and the context pass's
+  float *g_part;                 // bf16 + label: the layer kernel's partial row sums of df | dg, 128 per workgroup
+  float *ctx_wg_bias;            // generic loop: launch_wgrad's bias partials of the context convs (dfg is busy then)
+  Act spair[2][2];               // scatter form: the two pairs (A', P0) that alternate between the layers
+  // scatter: ONE kernel per layer (fused_bwd_l.h, fused_bf16.h); else the loop, each layer in halves_geometry's forms,
+  // forked onto the side stream unless every layer kernel is a fused one
+  bool scatter, fused_bwd, fork;
+  EmbedGradForm embed;
+  Region embed_tab;
+  int form;                      // what mvn_last_backward_form() reports after the call
+};
+// `total` floats at p as slabs | bias partials of as many workgroups of the layer kernel as fit
+static void cut_layer_wgs(float *p, size_t total, Region &slab, Region &bias) {
+  bias.floats = total / GC_PER_WG * 128;
+  slab = {p, total - bias.floats};
+  bias.p = p + slab.floats;
+}
+// Workgroups mvn_backward_bf16 would place at this shape: in its da1 regions, else in the forward's z scratch.  The
+// labelled and the conditioned bf16 backward never place more in their layer pass: both then cut a sequence into the
+// same chunks, and a zero label term / zero context weights give the audio-only pass's gradients to the bit.
+static size_t audio_bf16_wgs(const Region &slab, const Region &bias, const mvn_fwd_buffers *fwd, const Geometry &g, int batch) {
+  const size_t per_wg = GC_PER_WG - 128;
+  size_t n = bias.p ? std::min(slab.floats / per_wg, bias.floats / 128) : 0;
+  if (n < (size_t)batch && fwd->z) {
+    Region zs, zb;
+    cut_layer_wgs(fwd->z, (size_t)g.act, zs, zb);
+    n = std::min(zs.floats / per_wg, zb.floats / 128);
+  }
+  return n;
+}
+// One layer of the loop: a = the fused first half (and, conditioned, the fused context pass: it has the first half's
+// geometry in the same scratch), b = the fused second half behind a's slabs; neither: the two-kernel forms.
+struct HalvesGeom { bool a, b; int a_chunks, a_chunk_t, b_chunks, b_chunk_t; size_t a_used; };
+static HalvesGeom halves_geometry(const BwdPlan &pl, const Geometry &g, bool has_ctx, int batch, int l) {
+  HalvesGeom h = {};
+  const bool c64 = pl.fused_bwd && g.C == 64;
+  h.a = c64 && g.Kc == 64 && bwd_dz_wgrs64_fits(pl.cus, pl.A_lo[l + 1], g.T, batch, pl.bias2.p, pl.bias2.floats, pl.slab.p,
+                                                pl.slab.floats, &h.a_chunks, &h.a_chunk_t);
+  if (!h.a) h.a_chunks = 0;
+  h.a_used = (size_t)h.a_chunks * batch * 128 * 64;
+  h.b = c64 && (!has_ctx || h.a) &&
+        bwd_dx_wgfg64_fits(pl.cus, pl.A_lo[l], g.T, batch, pl.slab.p, pl.slab.floats, h.a_used, &h.b_chunks, &h.b_chunk_t);
+  if (!h.b) h.b_chunks = 0;
+  return h;
+}
+static int plan_backward(const SeqMode &m, const Geometry &g, const mvn_dims *dims, const Switches &sw, int cus, int batch,
+                         const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, BwdPlan &pl) {
+  const bool bf16 = m.precision == SeqMode::BF16, glob = m.conditioning == SeqMode::GLOBAL,
+             ctx16 = m.conditioning == SeqMode::CTX16, has_ctx = fwd->ctx != nullptr;
+  const int C = g.C, Kc = g.Kc, Q = g.Q, T = g.T;
+  const size_t act = (size_t)g.act, hid = (size_t)g.hid, per_wg = GC_PER_WG - 128;
+  pl.cus = cus;
+  for (int l = 0, A = 0; l <= g.L && l < 4096; ++l) {
+    pl.A_lo[l] = A;
+    if (l < g.L) A += dilation_of(dims, l);
+  }
+  const int t1 = pl.A_lo[1];  // the longest layer's outputs start here
+  // ---- dfg: per-workgroup bias partial sums of launch_wgrad, or the head's wgrad2 slabs + bias partials
+  pl.wg_bias = Region{bwd->dfg, 2 * act};
+  if ((size_t)((g.S + WG_CHUNK - 1) / WG_CHUNK) * batch * ((Q + 63) / 64 * 64) > 2 * act ||
+      (size_t)((T + WG_CHUNK - 1) / WG_CHUNK) * batch * ((C + Kc + 63) / 64 * 64) > 2 * act)
+    pl.wg_bias = Region{};
+  pl.head_slab = Region{bwd->dfg, 2 * act};
+  pl.head_bias = Region{};
+  {
+    const size_t n = (size_t)(g.S + TILE_ALIGN + W2_CHUNK - 1) / W2_CHUNK * batch, mpad = (size_t)(Q + 127) / 128 * 128;
+    if (n * mpad + n * mpad * mpad <= 2 * act) {
+      pl.head_slab.floats -= n * mpad;
+      pl.head_bias = Region{bwd->dfg + pl.head_slab.floats, n * mpad};
+    }
+  }
+  // ---- z: the head's LDS images behind the forward's, which nothing else touches between the two passes
+  const size_t img_off = (size_t)g.L * std::max(FS3_PACK_F, FSC_PACK_F) + DS3_IMG_F;
+  pl.head_img = head_q_strip(Q) && Kc == 64 && fwd->z && !sw.forward_f32 && act >= img_off + DS3_BWD_IMG_F &&
+                        rows_fit_rsrc(Q, g.Sp) ? fwd->z + img_off : nullptr;
+  // ---- da1: room for wgrad2's workgroups (512-column chunks) AND for the fused halves' (one round of two workgroups
+  // per CU whatever the length: up to 2 CUs + batch of them, 128 partial sums each) at its end -- "reserved"; else one
+  // cut for the layer kernel's workgroups that fit, which takes fewer, longer chunks then -- "small"
+  pl.slab = Region{bwd->da1, hid};
+  pl.bias2 = Region{};
+  {
+    const size_t wg2 = (size_t)((T + TILE_ALIGN + W2_CHUNK - 1) / W2_CHUNK) * batch, wgf = (size_t)2 * cus + batch;
+    const size_t need = std::max(wg2, wgf) * ((C + Kc + 127) / 128 * 128);
+    if (need <= hid / 2) {
+      pl.slab.floats -= need;
+      pl.bias2 = Region{bwd->da1 + pl.slab.floats, need};
+    }
+  }
+  Region au_slab = pl.slab, au_bias = pl.bias2;  // where the audio-only layer kernel finds its scratch in da1
+  if (!au_bias.p && hid / GC_PER_WG >= (size_t)batch) cut_layer_wgs(bwd->da1, hid, au_slab, au_bias);
+  // ---- the layer pass and the context pass of the scatter form
+  float *const gpair = m.scratch;
+  const bool ext = gpair && (glob || has_ctx) && (!bf16 || ctx16) && m.scratch_floats >= 2 * act + (size_t)batch * GC_PER_WG;
+  pl.sc_slab = pl.slab; pl.sc_bias = pl.bias2;
+  pl.cx_slab = pl.cx_bias = Region{};
+  pl.g_part = nullptr;
+  if (ctx16 && !ext) {
+    set_error("mvn_backward_bf16_ctx: scratch missing or smaller than mvn_bf16_ctx_scratch_floats()");
+    return MVN_ERR_BAD_ARG;
+  }
+  if (ext) {  // the caller's scratch: the second scatter pair, then the slabs, then the bias partials
+    const size_t n_fit = (m.scratch_floats - 2 * act) / GC_PER_WG;
+    pl.sc_slab = Region{gpair + 2 * act, n_fit * per_wg};
+    pl.sc_bias = Region{pl.sc_slab.p + pl.sc_slab.floats, n_fit * 128};
+    if (ctx16) {  // (the context pass's share: all of it, whatever the layer pass is held to)
+      pl.cx_slab = pl.sc_slab; pl.cx_bias = pl.sc_bias;
+      const size_t n_audio = audio_bf16_wgs(au_slab, au_bias, fwd, g, batch);
+      if (n_audio >= (size_t)batch && n_audio < n_fit) {
+        pl.sc_slab.floats = n_audio * per_wg;
+        pl.sc_bias.floats = n_audio * 128;
+      }
+    }
+  } else if (!has_ctx) {
+    pl.sc_slab = au_slab; pl.sc_bias = au_bias;
+  }
+  if (bf16 && glob) {
+    // slabs, bias partials, row-sum partials of n_fit workgroups -- independent of what da1 or z hold (short outputs, small Q)
+    if (!gpair || !global_bf16_path(g, batch) || m.scratch_floats < global_bf16_scratch_floats(dims, g, batch, cus)) {
+      set_error("mvn_backward_bf16_global: scratch missing or smaller than mvn_global_bf16_scratch_floats()");
+      return MVN_ERR_BAD_ARG;
+    }
+    const size_t n_fit = m.scratch_floats / GC16_PER_WG, n_audio = audio_bf16_wgs(au_slab, au_bias, fwd, g, batch);
+    const size_t n_use = n_audio >= (size_t)batch ? std::min(n_fit, n_audio) : n_fit;  // (none placed: the scratch decides)
+    pl.sc_slab = Region{gpair, n_use * per_wg};
+    pl.sc_bias = Region{gpair + n_fit * per_wg, n_use * 128};
+    pl.g_part = pl.sc_bias.p + n_fit * 128;  // n_fit * 128 floats: never more workgroups than n_use <= n_fit
+  }
+  auto layer_fits = [&]() {
+    FusedBwdLPlan lp;
+    return pl.sc_bias.p && g.L < 4095 &&
+           bwd_layer64_plan(cus, t1, T, batch, pl.sc_bias.p, pl.sc_bias.floats, pl.sc_slab.p, pl.sc_slab.floats, &lp);
+  };
+  int cc = 0, cct = 0;
+  auto ctx_fits = [&](int t_lo) {
+    return bwd_dz_wgrs64_fits(cus, t_lo, T, batch, pl.cx_bias.p, pl.cx_bias.floats, pl.cx_slab.p, pl.cx_slab.floats, &cc, &cct);
+  };
+  if (bf16) {
+    // short outputs (da1 is (B, Q, Sp)): the slabs go to the forward's z scratch instead, which holds nothing the layer
+    // loop reads -- the bf16 forward keeps z in registers and its weight images there, and the head's backward, which
+    // may stage its own images in it, runs before the loop on the same stream
+    if (!layer_fits() && fwd->z && !glob && !ctx16) cut_layer_wgs(fwd->z, act, pl.sc_slab, pl.sc_bias);
+    if (!layer_fits()) {
+      set_error("mvn_backward_bf16: the layer kernel's weight-gradient slabs do not fit the scratch at batch %d, t_len %d",
+                batch, T);
+      return MVN_ERR_UNSUPPORTED;
+    }
+    if (ctx16 && !ctx_fits(t1)) {
+      set_error("mvn_backward_bf16_ctx: the context pass's slabs do not fit the scratch at batch %d, t_len %d", batch, T);
+      return MVN_ERR_UNSUPPORTED;
+    }
+  }
+  if (!ctx16) {  // (every other form gives the context pass the layer pass's scratch)
+    pl.cx_slab = pl.sc_slab; pl.cx_bias = pl.sc_bias;
+  }
+  // ---- dlogit: bias partials of the context convs in the generic loop (dfg is busy while WgFgOp runs)
+  pl.ctx_wg_bias = (size_t)((T + WG_CHUNK - 1) / WG_CHUNK) * batch * ((2 * C + 63) / 64 * 64) > hid ? nullptr : bwd->dlogit;
+  // ---- the layers' form.  MOVENET_HIP_NO_FUSED_BACKWARD=1: the two-kernel forms (cross-checks, profiling); so do rows
+  // longer than the fused kernels' buffer resources span in the (2C, Tp) dfg tensor (rows_fit_rsrc: Tp > ~4.2 M at C = 64).
+  // With both fused halves every kernel of the loop runs on the caller's stream: no fork, and none of the two event
+  // records + waits per layer that go with it.  MOVENET_HIP_BWD_FORM=split keeps the two-half form of r2 / r3.
+  pl.fused_bwd = !sw.no_fused_backward && rows_fit_rsrc(2 * C, g.Tp);
+  const bool all_fused = bf16 || (pl.fused_bwd && C == 64 && Kc == 64);  // (conditioned layers too: bwd_dctx_wgctx64_kernel)
+  pl.fork = pl.bias2.p && !all_fused;
+  pl.scatter = false;
+  if (all_fused && pl.sc_bias.p && g.L < 4095 && g.Tp <= (1 << 21) && (bf16 || !sw.bwd_split)) {
+    // the second pair: the caller's scratch; audio only, the two row halves of the dfg tensor, which nothing else uses
+    // then; conditioned layers still write dfg for the context pass: dlogit when it is large enough
+    float *const second = ext ? gpair : !has_ctx ? bwd->dfg : 2 * act <= hid ? bwd->dlogit : nullptr;
+    const long long seq = ext || has_ctx ? (long long)C * g.Tp : (long long)2 * C * g.Tp;
+    const size_t half = ext || has_ctx ? act : (size_t)C * g.Tp;
+    pl.spair[0][0] = act_view(bwd->dx_a, batch, C, g.Tp);
+    pl.spair[0][1] = act_view(bwd->dx_b, batch, C, g.Tp);
+    pl.spair[1][0] = Act{second, seq, g.Tp};
+    pl.spair[1][1] = Act{second ? second + half : nullptr, seq, g.Tp};
+    pl.scatter = second && layer_fits() && (!has_ctx || ctx_fits(t1));
+  }
+  if (bf16 && !pl.scatter) {
+    set_error("mvn_backward_bf16: the bf16 layer kernels cannot run these buffers");
+    return MVN_ERR_UNSUPPORTED;
+  }
+  if (glob && !pl.scatter) {
+    set_error("mvn_backward_global: the one-kernel layer backward cannot run these buffers");
+    return MVN_ERR_UNSUPPORTED;
+  }
+  pl.form = bf16 ? (glob ? MVN_BWD_FORM_BF16_GLOBAL : ctx16 ? MVN_BWD_FORM_BF16_CTX : MVN_BWD_FORM_BF16)
+            : glob ? MVN_BWD_FORM_ONE_GLOBAL : pl.scatter ? MVN_BWD_FORM_ONE : MVN_BWD_FORM_GENERIC;
+  for (int l = g.L - 1; l >= 0; --l) {
+    // (scatter: the layer kernel fits every layer where it fits the first -- bwd_layer64_plan; the context pass's chunk
+    // count is not monotonic in the layer's length, fb_chunks, so every layer is asked)
+    if (pl.scatter && has_ctx && !ctx_fits(pl.A_lo[l + 1])) {
+      set_error("mvn_backward: the context pass lost its scratch at layer %d", l);
+      return MVN_ERR_BAD_ARG;
+    }
+    if (!pl.scatter) {
+      const HalvesGeom h = halves_geometry(pl, g, has_ctx, batch, l);
+      if (h.a && h.b) pl.form = MVN_BWD_FORM_HALVES;
+    }
+  }
+  // ---- the embedding gradient: per-chunk tables in the layer loop's slab scratch (idle by then), summed in chunk order
+  pl.embed = EMBED_DENSE_AUDIO;
+  pl.embed_tab = Region{};
+  if (!fwd->dense_audio) {
+    if (Q > 8192) {  // channels per workgroup: the table slice [cg][Q][2] fits 64 KB of LDS
+      set_error("mvn_backward: input_channels %d > 8192 not supported by the embedding gradient", Q);
+      return MVN_ERR_UNSUPPORTED;
+    }
+    const size_t need64 = (size_t)((T + EG64_CHUNK - 1) / EG64_CHUNK) * batch * 2 * Q * 64, table = (size_t)C * Q * 2;
+    pl.embed_tab = pl.slab;
+    // bf16 at short outputs (da1 too small for the tables): the layer pass's slabs, so that the table is summed in chunk
+    // order there too, not with atomics -- the audio-only and the conditioned pass then agree to the bit
+    if (bf16 && need64 > pl.slab.floats && pl.cx_slab.p && need64 <= pl.cx_slab.floats) pl.embed_tab = pl.cx_slab;
+    if (C == 64 && Q % EG64_PARTS == 0 && (size_t)Q / EG64_PARTS * 64 * sizeof(float) <= 64 * 1024 && need64 <= pl.embed_tab.floats)
+      pl.embed = Q == 256 ? EMBED_MFMA : EMBED_LDS;  // the product form; any other Q: the LDS read-modify-write kernel
+    else  // one table copy per (chunk, sequence); without room for them the workgroups add to the table with atomics
+      pl.embed = table % 64 == 0 && (size_t)((T + EG_CHUNK - 1) / EG_CHUNK) * batch * table <= pl.embed_tab.floats ? EMBED_TABLES
+                                                                                                                  : EMBED_ATOMICS;
+  }
+  return MVN_OK;
 }
 
 extern "C" {
@@ -1382,19 +1628,15 @@ int mvn_forward_f16(const mvn_dims *dims, const mvn_params *p, const int32_t *in
 static int g_last_bwd_form = 0;  // (process-wide: autograd runs the backward on a thread of its own)
 int mvn_last_backward_form(void) { return g_last_bwd_form; }
 
+// m.scratch: the caller's scratch for the one-kernel layer backward (GLOBAL, CTX16, and conditioned fp32 layers, which
+// without it look for that room in dlogit / da1 and take another form where those are too small: short outputs, small
+// Q).  m.rowsum: the (L, B, 2C) row sums of df | dg.  What lives where: BwdPlan.
 static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
                          const int32_t *index, int index_stride, int batch, int t_len,
                          const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
-                         const float *dout, int normalize, int remove_last, void *stream_, const SeqMode &m) {
-  const bool bf16 = m.precision == SeqMode::BF16, glob = m.conditioning == SeqMode::GLOBAL,
-             ctx16 = m.conditioning == SeqMode::CTX16;
-  float *const gpair = m.scratch, *const grow = m.rowsum;
-  const size_t gpair_floats = m.scratch_floats;
-  // gpair: the caller's scratch for the one-kernel layer backward -- the second pair of (B, C, Tp) scatter tensors (the
-  // layer kernel writes df | dg into the dfg tensor here), the slabs and the bias partials: for glob, for ctx16 (the bf16
-  // layer kernel's dfg-writing form with the fp32 context pass behind it) and for conditioned fp32 layers (fwd->ctx: the
-  // label has joined the context), which without it look for that room in dlogit / da1 and take another form where
-  // those are too small (short outputs, small Q).  grow: the (L, B, 2C) row sums of df | dg
+                         const float *dout, int normalize, int remove_last, void *stream_, const SeqMode &m, int cus) {
+  const bool bf16 = m.precision == SeqMode::BF16, glob = m.conditioning == SeqMode::GLOBAL;
+  float *const grow = m.rowsum;
   Geometry g;
   int rc = make_geometry(dims, batch, t_len, g);
   if (rc) return rc;
@@ -1414,77 +1656,9 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
     return MVN_ERR_BAD_ARG;
   }
   if (batch == 0 || S_out <= 0) return MVN_OK;
-  hipStream_t s = (hipStream_t)stream_;
-  const int C = g.C, Kc = g.Kc, Q = g.Q, T = g.T;
-  const int t_skip0 = g.rf - 1;
-
-  Act dlog = act_view(bwd->dlogit, batch, Q, g.Sp);
-  Act da1 = act_view(bwd->da1, batch, Q, g.Sp);
-  // per-workgroup bias partial sums live in the dfg scratch (free until the layer loop
-  // needs it: each use below is followed by its reduce before dfg is written)
-  float *bias_scratch = bwd->dfg;
-  {
-    const size_t need_head = (size_t)((g.S + WG_CHUNK - 1) / WG_CHUNK) * batch * ((Q + 63) / 64 * 64);
-    const size_t need_layer = (size_t)((T + WG_CHUNK - 1) / WG_CHUNK) * batch * ((C + Kc + 63) / 64 * 64);
-    const size_t have = (size_t)batch * 2 * C * g.Tp;
-    if (need_head > have || need_layer > have) bias_scratch = nullptr;
-  }
-  // scratch of the layer weight gradients (wgrad2): per-workgroup partial tiles and bias
-  // partial sums, both in da1, which is dead once the head's backward below has run
-  float *bias_scratch2 = nullptr, *slab = bwd->da1;
-  size_t slab_floats = (size_t)batch * Q * g.Sp, bias2_floats = 0;
-  {
-    // room for wgrad2's workgroups (512-column chunks) AND for the fused halves' (one round of two workgroups per
-    // CU whatever the length: up to 2 CUs + batch of them, 128 partial sums each).  r3: the second count was
-    // missing -- at T x batch < 2^18 (the parity tests' sizes, not the configs') the fused first half and the
-    // conditioned pass wrote their bias partials past the end of da1, into whatever tensor came next.
-    const size_t wg2 = (size_t)((T + TILE_ALIGN + W2_CHUNK - 1) / W2_CHUNK) * batch;
-    const size_t wgf = (size_t)2 * fb_device_cus() + batch;
-    const size_t need = std::max(wg2, wgf) * ((C + Kc + 127) / 128 * 128);
-    if (need <= slab_floats / 2) {
-      slab_floats -= need;
-      bias_scratch2 = bwd->da1 + slab_floats;
-      bias2_floats = need;
-    }
-  }
-  // head weight gradients (wgrad2): slabs + bias partials in dfg
-  float *head_slab = bwd->dfg, *head_bias = nullptr;
-  size_t head_slab_floats = (size_t)batch * 2 * C * g.Tp;
-  bool head_scratch_ok = false;
-  {
-    const size_t chunks = (size_t)(g.S + TILE_ALIGN + W2_CHUNK - 1) / W2_CHUNK;
-    const size_t mpad = (size_t)(Q + 127) / 128 * 128;
-    const size_t need_bias = chunks * batch * mpad, need_slab = chunks * batch * mpad * mpad;
-    if (need_bias + need_slab <= head_slab_floats) {
-      head_slab_floats -= need_bias;
-      head_bias = bwd->dfg + head_slab_floats;
-      head_scratch_ok = true;
-    }
-  }
-  Act dskip = act_view(bwd->dskip, batch, Kc, g.Sp);
-  Act a1v = act_view(fwd->a1, batch, Q, g.Sp);
-  Act skipv = act_view(fwd->skip, batch, Kc, g.Sp);
-  // the head's data gradients as bf16 x 3 strip kernels (fused_fwd_bf3.h): their LDS images go behind the forward's
-  // in the forward's z scratch, which nothing else touches between the two passes
-  float *bwd_head_img = nullptr;
-  {
-    const size_t off = (size_t)g.L * std::max(FS3_PACK_F, FSC_PACK_F) + DS3_IMG_F;
-    if (head_q_strip(Q) && Kc == 64 && fwd->z && forward_bf3_enabled() && (size_t)g.act >= off + DS3_BWD_IMG_F &&
-        rows_fit_rsrc(Q, g.Sp))
-      bwd_head_img = fwd->z + off;
-  }
-  // layers, last to first
-  int A_lo[4096];
-  {
-    int A = 0;
-    for (int l = 0; l <= g.L && l < 4096; ++l) {
-      A_lo[l] = A;
-      if (l < g.L) A += dilation_of(dims, l);
-    }
-  }
   const bool has_ctx = fwd->ctx != nullptr;
-  if (glob && !bf16 && (!gpair || has_ctx || !global_backward_fast(dims, g, batch) ||
-               gpair_floats < 2 * (size_t)g.act + (size_t)batch * GC_PER_WG)) {
+  if (glob && !bf16 && (!m.scratch || has_ctx || !global_backward_fast(dims, g, batch) ||
+               m.scratch_floats < 2 * (size_t)g.act + (size_t)batch * GC_PER_WG)) {
     set_error("mvn_backward_global: needs the one-kernel layer backward at residual = skip channels = 64 without context "
               "(mvn_global_fast_path)");
     return MVN_ERR_UNSUPPORTED;
@@ -1493,107 +1667,24 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
     set_error("mvn_backward: context given without dctx buffer / context-conv gradients");
     return MVN_ERR_BAD_ARG;
   }
-  // (tensors too small for the reservation above -- the parity tests' smallest -- get a bias region sized for
-  // the workgroups that fit: the plan takes fewer, longer chunks then)
-  float *sc_bias = bias_scratch2, *sc_slab = slab;
-  size_t sc_bias_floats = bias2_floats, sc_slab_floats = slab_floats;
-  const bool ext = gpair && (glob || has_ctx) && (!bf16 || ctx16) && gpair_floats >= 2 * (size_t)g.act + (size_t)batch * GC_PER_WG;
-  // (the context pass's share of the caller's scratch: all of it, whatever the layer pass is held to below)
-  float *cx_bias = nullptr, *cx_slab = nullptr;
-  size_t cx_bias_floats = 0, cx_slab_floats = 0;
-  if (ext) {  // the caller's scratch: the second scatter pair, then the slabs, then the bias partials
-    const size_t n_fit = (gpair_floats - 2 * (size_t)g.act) / GC_PER_WG;
-    sc_slab = gpair + 2 * (size_t)g.act;
-    sc_slab_floats = n_fit * (GC_PER_WG - 128);
-    sc_bias = sc_slab + sc_slab_floats;
-    sc_bias_floats = n_fit * 128;
-    if (ctx16) {
-      cx_bias = sc_bias; cx_slab = sc_slab; cx_bias_floats = sc_bias_floats; cx_slab_floats = sc_slab_floats;
-      // never more workgroups in the layer pass than mvn_backward_bf16 would place at this shape (its slabs live in da1,
-      // else in the forward's z scratch): both passes then cut a sequence into the same chunks, and zero context weights
-      // give the audio-only pass's gradients to the bit.  Where that pass places nothing, the scratch alone decides.
-      const size_t per_wg = GC_PER_WG - 128;
-      size_t n_audio = std::min(slab ? slab_floats / per_wg : 0, bias_scratch2 ? bias2_floats / 128 : 0);
-      if (n_audio < (size_t)batch && slab) {  // (its second try in da1: one region cut into slabs and partials)
-        const size_t total = (size_t)batch * Q * g.Sp, nd = total / GC_PER_WG;
-        if (nd >= (size_t)batch && !bias_scratch2) n_audio = std::min((total - nd * 128) / per_wg, nd);
-      }
-      if (n_audio < (size_t)batch && fwd->z) {
-        const size_t total = (size_t)g.act, nz = total / GC_PER_WG;
-        n_audio = std::min((total - nz * 128) / per_wg, nz);
-      }
-      if (n_audio >= (size_t)batch && n_audio < n_fit) {
-        sc_slab_floats = n_audio * per_wg;
-        sc_bias_floats = n_audio * 128;
-      }
-    }
-  } else if (!sc_bias && !has_ctx && slab) {
-    const size_t total = (size_t)batch * Q * g.Sp, n_fit = total / (128 * 64 + 128 * 128 + 128);
-    if (n_fit >= (size_t)batch) {
-      sc_bias_floats = n_fit * 128;
-      sc_slab_floats = total - sc_bias_floats;
-      sc_bias = bwd->da1 + sc_slab_floats;
-    }
-  }
-  float *g_part = nullptr;  // bf16 + labels: the layer kernel's partial row sums of df | dg, one 128-vector per workgroup
-  if (bf16) {  // (decided before any launch: there is no fp32 fall-back)
-    rc = mode_supported(m, g, batch, fwd);
-    if (rc) return rc;
-    if (ctx16 && !ext) {
-      set_error("mvn_backward_bf16_ctx: scratch missing or smaller than mvn_bf16_ctx_scratch_floats()");
-      return MVN_ERR_BAD_ARG;
-    }
-    if (glob) {
-      // the caller's scratch (mvn_global_bf16_scratch_floats): slabs, bias partials, row-sum partials of n_fit
-      // workgroups -- independent of what da1 or the forward's z scratch hold (short outputs, small Q)
-      if (!gpair || !global_bf16_path(g, batch) || gpair_floats < global_bf16_scratch_floats(dims, g, batch)) {
-        set_error("mvn_backward_bf16_global: scratch missing or smaller than mvn_global_bf16_scratch_floats()");
-        return MVN_ERR_BAD_ARG;
-      }
-      const size_t n_fit = gpair_floats / GC16_PER_WG, per_wg = GC_PER_WG - 128;
-      // never more workgroups than mvn_backward_bf16 would place at this shape (its slabs live in da1, else in the
-      // forward's z scratch -- below): both passes then cut a sequence into the same chunks, and a zero label term gives
-      // the audio-only pass's gradients to the bit.  Where that pass places nothing, the scratch alone decides.
-      size_t n_audio = std::min(sc_slab ? sc_slab_floats / per_wg : 0, sc_bias ? sc_bias_floats / 128 : 0);
-      if (n_audio < (size_t)batch && fwd->z) {
-        const size_t total = (size_t)g.act, nz = total / GC_PER_WG;
-        n_audio = std::min((total - nz * 128) / per_wg, nz);
-      }
-      const size_t n_use = n_audio >= (size_t)batch ? std::min(n_fit, n_audio) : n_fit;
-      sc_slab = gpair;
-      sc_slab_floats = n_use * per_wg;
-      sc_bias = gpair + n_fit * per_wg;
-      sc_bias_floats = n_use * 128;
-      g_part = sc_bias + n_fit * 128;  // n_fit * 128 floats: the plan never places more workgroups than n_use <= n_fit
-    }
-    FusedBwdLPlan pl0;
-    auto fits = [&]() {
-      return sc_bias && g.L < 4095 && bwd_layer64_plan(A_lo[1], T, batch, sc_bias, sc_bias_floats, sc_slab, sc_slab_floats, &pl0);
-    };
-    if (!fits() && fwd->z && !glob && !ctx16) {
-      // short outputs (da1 is (B, Q, Sp)): the slabs go to the forward's z scratch instead, which holds nothing the layer
-      // loop reads -- the bf16 forward keeps z in registers and its weight images there, and the head's backward, which
-      // may stage its own images in it, runs before the loop on the same stream
-      const size_t total = (size_t)g.act, n_fit = total / (128 * 64 + 128 * 128 + 128);
-      sc_bias_floats = n_fit * 128;
-      sc_slab = fwd->z;
-      sc_slab_floats = total - sc_bias_floats;
-      sc_bias = fwd->z + sc_slab_floats;
-    }
-    if (!fits()) {
-      set_error("mvn_backward_bf16: the layer kernel's weight-gradient slabs do not fit the scratch at batch %d, t_len %d",
-                batch, t_len);
-      return MVN_ERR_UNSUPPORTED;
-    }
-    int cc0 = 0, cct0 = 0;
-    if (ctx16 && !bwd_dctx_wgctx64_fits(A_lo[1], T, batch, cx_bias, cx_bias_floats, cx_slab, cx_slab_floats, &cc0, &cct0)) {
-      set_error("mvn_backward_bf16_ctx: the context pass's slabs do not fit the scratch at batch %d, t_len %d", batch, t_len);
-      return MVN_ERR_UNSUPPORTED;
-    }
-  }
-  if (!ctx16) {  // (every other form gives the context pass the layer pass's scratch)
-    cx_bias = sc_bias; cx_slab = sc_slab; cx_bias_floats = sc_bias_floats; cx_slab_floats = sc_slab_floats;
-  }
+  rc = mode_supported(m, g, batch, fwd);  // (there is no fp32 fall-back)
+  if (rc) return rc;
+  // every region of scratch, every kernel form and every remaining refusal, in front of the first launch: a refused
+  // call has written nothing and leaves mvn_last_backward_form() as it was
+  BwdPlan pl;
+  rc = plan_backward(m, g, dims, switches(), cus, batch, fwd, bwd, pl);
+  if (rc) return rc;
+  g_last_bwd_form = pl.form;
+  const int *const A_lo = pl.A_lo;
+  hipStream_t s = (hipStream_t)stream_;
+  const int C = g.C, Kc = g.Kc, Q = g.Q, T = g.T;
+  const int t_skip0 = g.rf - 1;
+
+  Act dlog = act_view(bwd->dlogit, batch, Q, g.Sp);
+  Act da1 = act_view(bwd->da1, batch, Q, g.Sp);
+  Act dskip = act_view(bwd->dskip, batch, Kc, g.Sp);
+  Act a1v = act_view(fwd->a1, batch, Q, g.Sp);
+  Act skipv = act_view(fwd->skip, batch, Kc, g.Sp);
   if (!dout) {
     // the caller has filled bwd->dlogit itself (mvn_softmax_ce_backward: the trainer's loss and
     // the model's softmax differentiated in one pass)
@@ -1603,30 +1694,29 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
   else
     hipLaunchKernelGGL(softmax_bwd_kernel, dim3((g.S + 255) / 256, batch), dim3(256), 0, s, out, dout,
                      dlog, Q, S_out, g.S, normalize, g.pad);
-  {  // head conv2: weight grad, then data grad (x lrelu'(a1))
+  {  // head conv2: weight grad (wgrad2's slabs + bias partials in dfg, free until the layer loop: da1 is what the data
+     // gradient writes), then data grad (x lrelu'(a1))
     WgDenseOp<IN_ID> w2;
     w2.t_begin = g.pad; w2.t_end = g.pad + g.S; w2.M = Q; w2.N = Q; w2.aact = dlog; w2.xact = a1v;
     w2.dwm = gr->head2_w; w2.dbv = gr->head2_b;
-    // (slab + bias scratch of wgrad2 live in da1, which conv2's data gradient below writes:
-    // the head uses the dfg tensor instead, free until the layer loop)
-    if (head_scratch_ok)
-      launch_wgrad2<2>(w2, Q, Q, batch, head_bias, head_slab, head_slab_floats, s);
+    if (pl.head_bias.p)
+      launch_wgrad2<2>(w2, Q, Q, batch, pl.head_bias.p, pl.head_slab.p, pl.head_slab.floats, s);
     else
-      launch_wgrad(w2, Q, Q, batch, bias_scratch, s);
-    DenseOp<IN_ID, OUT_MUL_DLRELU, true> d2;
-    d2.K = Q; d2.t_begin = g.pad; d2.t_end = g.pad + g.S; d2.M = Q; d2.wmat = p->head2_w; d2.ldw = Q;
-    d2.bias = nullptr; d2.xin = dlog; d2.yout = da1; d2.ref = a1v; d2.t_out_end = g.pad + g.S;
-    d2.aligned_out = 1;
-    // (the fp32 strip form measured 454 us here against 342: its 64 leaky-ReLU reference loads per strip
-    // come after the MFMAs, and there is no register left to fetch them ahead.  r3: the bf16 x 3 strip -- four row
-    // blocks of 64, reference values requested before the products, images packed behind the forward's in the z scratch)
-    if (bwd_head_img) {
+      launch_wgrad(w2, Q, Q, batch, pl.wg_bias.p, s);
+    // (the fp32 strip form measured 454 us here against 342: its 64 leaky-ReLU reference loads per strip come after the
+    // MFMAs, and there is no register left to fetch them ahead.  r3: the bf16 x 3 strip -- four row blocks of 64,
+    // reference values requested before the products, images packed behind the forward's in the z scratch)
+    if (pl.head_img) {
       DenseStripArgs da;
-      da.t_begin = d2.t_begin; da.t_end = d2.t_end; da.t_out_end = d2.t_out_end;
+      da.t_begin = g.pad; da.t_end = g.pad + g.S; da.t_out_end = g.pad + g.S;
       da.wmat = p->head2_w; da.ldw = Q; da.bias = nullptr; da.xin = dlog; da.yout = da1; da.ref = a1v;
-      rc = MVN_HEAD_Q(head_bwd2_bf3)(da, p, bwd_head_img, batch, s);
+      rc = MVN_HEAD_Q(head_bwd2_bf3)(da, p, pl.head_img, batch, s);
       if (rc) return rc;
     } else {
+      DenseOp<IN_ID, OUT_MUL_DLRELU, true> d2;
+      d2.K = Q; d2.t_begin = g.pad; d2.t_end = g.pad + g.S; d2.M = Q; d2.wmat = p->head2_w; d2.ldw = Q;
+      d2.bias = nullptr; d2.xin = dlog; d2.yout = da1; d2.ref = a1v; d2.t_out_end = g.pad + g.S;
+      d2.aligned_out = 1;
       launch_gemm_staged(d2, Q, batch, s);
     }
   }
@@ -1634,23 +1724,23 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
     WgDenseOp<IN_LRELU> w1;
     w1.t_begin = g.pad; w1.t_end = g.pad + g.S; w1.M = Q; w1.N = Kc; w1.aact = da1; w1.xact = skipv;
     w1.dwm = gr->head1_w; w1.dbv = gr->head1_b;
-    if (head_scratch_ok)
-      launch_wgrad2<1>(w1, Q, Kc, batch, head_bias, head_slab, head_slab_floats, s);
+    if (pl.head_bias.p)
+      launch_wgrad2<1>(w1, Q, Kc, batch, pl.head_bias.p, pl.head_slab.p, pl.head_slab.floats, s);
     else
-      launch_wgrad(w1, Q, Kc, batch, bias_scratch, s);
-    DenseOp<IN_ID, OUT_MUL_DLRELU, true> d1;
-    d1.K = Q; d1.t_begin = g.pad; d1.t_end = g.pad + g.S; d1.M = Kc; d1.wmat = p->head1_w; d1.ldw = Kc;
-    d1.bias = nullptr; d1.xin = da1; d1.yout = dskip; d1.ref = skipv; d1.t_out_end = g.pad + g.S;
-    d1.aligned_out = 1;
-    // (conv1's data gradient has ONE 64-row output block: the generic kernel already reads da1 once,
-    // and the fp32 strip form measured 143 us against its 113; r3: the bf16 x 3 strip)
-    if (bwd_head_img && Kc == 64) {
+      launch_wgrad(w1, Q, Kc, batch, pl.wg_bias.p, s);
+    // (conv1's data gradient has ONE 64-row output block: the generic kernel already reads da1 once, and the fp32
+    // strip form measured 143 us against its 113; r3: the bf16 x 3 strip, which the plan takes at Kc = 64 only)
+    if (pl.head_img) {
       DenseStripArgs da;
-      da.t_begin = d1.t_begin; da.t_end = d1.t_end; da.t_out_end = d1.t_out_end;
+      da.t_begin = g.pad; da.t_end = g.pad + g.S; da.t_out_end = g.pad + g.S;
       da.wmat = p->head1_w; da.ldw = Kc; da.bias = nullptr; da.xin = da1; da.yout = dskip; da.ref = skipv;
-      rc = MVN_HEAD_Q(head_bwd1_bf3)(da, p, Kc, bwd_head_img, batch, s);
+      rc = MVN_HEAD_Q(head_bwd1_bf3)(da, p, Kc, pl.head_img, batch, s);
       if (rc) return rc;
     } else {
+      DenseOp<IN_ID, OUT_MUL_DLRELU, true> d1;
+      d1.K = Q; d1.t_begin = g.pad; d1.t_end = g.pad + g.S; d1.M = Kc; d1.wmat = p->head1_w; d1.ldw = Kc;
+      d1.bias = nullptr; d1.xin = da1; d1.yout = dskip; d1.ref = skipv; d1.t_out_end = g.pad + g.S;
+      d1.aligned_out = 1;
       launch_gemm_staged(d1, Kc, batch, s);
     }
   }
@@ -1660,227 +1750,148 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
     rc = check_hip(hipMemsetAsync(bwd->dctx, 0, sizeof(float) * (size_t)g.act, s), "memset dctx");
     if (rc) return rc;
   }
-  // bias partials of the context convs: dfg is busy while WgFgOp runs, use dlogit
-  float *ctx_bias_scratch = bwd->dlogit;
-  {
-    const size_t need = (size_t)((T + WG_CHUNK - 1) / WG_CHUNK) * batch * ((2 * C + 63) / 64 * 64);
-    if (need > (size_t)g.hid) ctx_bias_scratch = nullptr;
-  }
   float *dxo_p = nullptr;  // gradient w.r.t. the layer's residual output
-  float *cur = bwd->dx_a, *nxt = bwd->dx_b;
   Act dfg = act_view(bwd->dfg, batch, 2 * C, g.Tp);
-  // Two streams: per layer  WgRs || Dz  then  WgFg || (Dctx,) Dx.
+  // what every form of a layer shares
+  auto layer_ops = [&](int l, Act dxo, WgRsOp &wr, WgFgOpT<false> &wf, FusedBwdCArgs &fc, WgCtxOp &co) {
+    const int t_lo = A_lo[l + 1];
+    wr.t_begin = t_lo; wr.t_end = T; wr.C = C; wr.Kc = Kc; wr.t_skip0 = t_skip0; wr.t_base = g.t_base;
+    wr.dxo = dxo; wr.dskip = dskip;
+    wr.th = act_view(fwd->th + (size_t)l * g.act, batch, C, g.Tp);
+    wr.sg = act_view(fwd->sg + (size_t)l * g.act, batch, C, g.Tp);
+    wr.dwr = gr->residual_w[l]; wr.dbr = gr->residual_b[l]; wr.dws = gr->skip_w[l]; wr.dbs = gr->skip_b[l];
+    wf.t_begin = t_lo; wf.t_end = T; wf.C = C; wf.d = dilation_of(dims, l); wf.dfg = dfg; wf.ctx = ctxv;
+    wf.xin = act_view(fwd->acts + (size_t)l * g.act, batch, C, g.Tp);
+    wf.dwf = gr->filter_w[l]; wf.dwg = gr->gate_w[l];
+    wf.dwcf = nullptr; wf.dwcg = nullptr; wf.dbcf = nullptr; wf.dbcg = nullptr;
+    if (!has_ctx) return;
+    fc.t_begin = t_lo; fc.t_end = T; fc.wcf = p->ctx_filter_w[l]; fc.wcg = p->ctx_gate_w[l];
+    fc.dfg = dfg; fc.ctx = ctxv; fc.dctx = dctxv;
+    co.dwcf = gr->ctx_filter_w[l]; co.dwcg = gr->ctx_gate_w[l]; co.dbcf = gr->ctx_filter_b[l]; co.dbcg = gr->ctx_gate_b[l];
+  };
+  if (pl.scatter) {
+    // r4: the layer's backward as ONE kernel, input gradients in scatter form (fused_bwd_l.h): df | dg stays on chip;
+    // conditioned and fp32-labelled layers still write dfg, for the context pass / the row sums
+    int po = 1 ^ ((g.L - 1) & 1);  // (so that layer 0 writes pair 1 and the dense dx0 can go to dx_a)
+    for (int l = g.L - 1; l >= 0; --l) {
+      const int t_lo = A_lo[l + 1];
+      WgRsOp wr; WgFgOpT<false> wf; FusedBwdCArgs fc; WgCtxOp co;
+      FusedBwdLArgs fa;
+      fa.ga = pl.spair[po ^ 1][0]; fa.gp = pl.spair[po ^ 1][1];
+      if (l == g.L - 1) fa.ga.p = nullptr;  // the last layer's residual output is unused: no dxo
+      layer_ops(l, fa.ga, wr, wf, fc, co);
+      fa.t_lo = t_lo; fa.t_end = T; fa.d = wf.d; fa.t_skip0 = t_skip0; fa.t_base = g.t_base;
+      fa.up_lo = l + 1 < g.L ? A_lo[l + 2] : 0;
+      fa.up_d = l + 1 < g.L ? dilation_of(dims, l + 1) : 0;
+      fa.wr = p->residual_w[l]; fa.ws = p->skip_w[l]; fa.wf = p->filter_w[l]; fa.wg = p->gate_w[l];
+      fa.dskip = dskip; fa.th = wr.th; fa.sg = wr.sg; fa.xin = wf.xin;
+      fa.oa = pl.spair[po][0]; fa.op = pl.spair[po][1];
+      fa.dfg = (has_ctx || (glob && !bf16)) ? dfg : Act{nullptr, 0, 0};
+      FusedBwdLPlan lp;  // (it fits: plan_backward asked for the first layer, and the answer is the same for every layer)
+      (void)bwd_layer64_plan(pl.cus, t_lo, T, batch, pl.sc_bias.p, pl.sc_bias.floats, pl.sc_slab.p, pl.sc_slab.floats, &lp);
+      // (bf16 + labels: the row sums come out of the layer kernel itself, no dfg tensor -- fused_bf16.h)
+      rc = bf16 ? launch_bwd_layer64_bf16(fa, wr, wf, batch, lp, s, pl.g_part, pl.g_part ? grow + (size_t)l * batch * 128 : nullptr)
+                : launch_bwd_layer64(fa, wr, wf, batch, lp, s);
+      if (rc) return rc;
+      if (glob && !bf16)  // the label's term: row sums of df | dg over the layer's valid columns (global_cond.h)
+        hipLaunchKernelGGL(global_rowsum_kernel, dim3(32, batch), dim3(256), 0, s, bwd->dfg, (long long)2 * C * g.Tp, g.Tp,
+                           t_lo, T, grow + (size_t)l * batch * 128);
+      if (has_ctx) {  // (behind the layer's reduce: the slab scratch is free again; plan_backward asked for every layer)
+        int c_chunks = 0, c_chunk_t = 0;
+        (void)bwd_dz_wgrs64_fits(pl.cus, t_lo, T, batch, pl.cx_bias.p, pl.cx_bias.floats, pl.cx_slab.p, pl.cx_slab.floats,
+                                    &c_chunks, &c_chunk_t);
+        launch_bwd_dctx_wgctx64(fc, co, batch, pl.cx_bias.p, pl.cx_slab.p, c_chunks, c_chunk_t, s);
+      }
+      po ^= 1;
+    }
+    // the first layer's input gradient in dense form for the embedding / causal-conv gradient below
+    hipLaunchKernelGGL(bwd_scatter_combine_kernel, dim3((T + 255) / 256, C, batch), dim3(256), 0, s, pl.spair[po ^ 1][0],
+                       pl.spair[po ^ 1][1], pl.spair[0][0], C, A_lo[1], dilation_of(dims, 0), T);
+    dxo_p = bwd->dx_a;
+  }
+  // The loop.  Two streams: per layer  WgRs || Dz  then  WgFg || (Dctx,) Dx.
   //   ev[0]: dx of the previous layer / the head's dskip ready (s -> s2)
   //   ev[1]: dfg of this layer ready (s -> s2)
   //   ev[2], ev[3]: WgRs / WgFg done (s2 -> s: the buffers they read may be overwritten)
   SideStream *side = nullptr;
-  // MOVENET_HIP_NO_FUSED_BACKWARD=1: the two-kernel forms (cross-checks, profiling); so do rows longer than the fused
-  // kernels' buffer resources span in the (2C, Tp) dfg tensor (common.h rows_fit_rsrc: Tp > ~4.2 M at C = 64)
-  const bool fused_bwd = !switches().no_fused_backward && rows_fit_rsrc(2 * C, g.Tp);
-  // (with both fused halves every kernel of the layer loop runs on the caller's stream: no fork,
-  // and none of the two event records + waits per layer that go with it -- ~60 gaps of ~8 us per step)
-  const bool all_fused = bf16 || (fused_bwd && C == 64 && Kc == 64);  // (conditioned layers too: bwd_dctx_wgctx64_kernel)
-  const bool fork = bias_scratch2 && !all_fused;
   hipStream_t s2 = s;
-  if (fork) {
+  if (pl.fork) {
     rc = side_stream(&side);
     if (rc) return rc;
     s2 = side->s;
     if (check_hip(hipEventRecord(side->ev[0], s), "hipEventRecord")) return MVN_ERR_LAUNCH;
   }
   auto signal = [&](int e, hipStream_t from) {
-    if (fork) (void)hipEventRecord(side->ev[e], from);
+    if (pl.fork) (void)hipEventRecord(side->ev[e], from);
   };
   auto await = [&](int e, hipStream_t on) {
-    if (fork) (void)hipStreamWaitEvent(on, side->ev[e], 0);
+    if (pl.fork) (void)hipStreamWaitEvent(on, side->ev[e], 0);
   };
-  // r4: the layer's backward as ONE kernel, input gradients in scatter form (fused_bwd_l.h): df | dg stays on chip.
-  // Two pairs (A', P0) of (B, C, Tp) tensors alternate between the layers: dx_a | dx_b and -- audio only -- the two
-  // row halves of the dfg tensor, which nothing else uses then; conditioned layers still write dfg for the context
-  // pass, their second pair lives in dlogit (dead behind the head's backward) when it is large enough.
-  // MOVENET_HIP_BWD_FORM=split keeps the two-half form of r2 / r3 (cross-checks, A/B; common.h: Switches).
-  Act spair[2][2];
-  bool scatter = false;
-  if (all_fused && sc_bias && g.L < 4095 && g.Tp <= (1 << 21) && (bf16 || !switches().bwd_split)) {
-    spair[0][0] = act_view(bwd->dx_a, batch, C, g.Tp);
-    spair[0][1] = act_view(bwd->dx_b, batch, C, g.Tp);
-    bool have = true;
-    if (ext) {
-      spair[1][0] = act_view(gpair, batch, C, g.Tp);
-      spair[1][1] = act_view(gpair + (size_t)g.act, batch, C, g.Tp);
-    } else if (!has_ctx) {
-      spair[1][0] = Act{bwd->dfg, (long long)2 * C * g.Tp, g.Tp};
-      spair[1][1] = Act{bwd->dfg + (size_t)C * g.Tp, (long long)2 * C * g.Tp, g.Tp};
-    } else if (2 * g.act <= g.hid) {
-      spair[1][0] = act_view(bwd->dlogit, batch, C, g.Tp);
-      spair[1][1] = act_view(bwd->dlogit + (size_t)g.act, batch, C, g.Tp);
-    } else {
-      have = false;
-    }
-    FusedBwdLPlan pl0;
-    int cc = 0, cct = 0;
-    scatter = have && bwd_layer64_plan(A_lo[1], T, batch, sc_bias, sc_bias_floats, sc_slab, sc_slab_floats, &pl0) &&
-              (!has_ctx || bwd_dctx_wgctx64_fits(A_lo[1], T, batch, cx_bias, cx_bias_floats, cx_slab, cx_slab_floats, &cc, &cct));
-  }
-  if (bf16 && !scatter) {
-    set_error("mvn_backward_bf16: the bf16 layer kernels cannot run these buffers");
-    return MVN_ERR_UNSUPPORTED;
-  }
-  if (glob && !scatter) {
-    set_error("mvn_backward_global: the one-kernel layer backward cannot run these buffers");
-    return MVN_ERR_UNSUPPORTED;
-  }
-  g_last_bwd_form = bf16 ? (glob ? MVN_BWD_FORM_BF16_GLOBAL : ctx16 ? MVN_BWD_FORM_BF16_CTX : MVN_BWD_FORM_BF16) : glob ? MVN_BWD_FORM_ONE_GLOBAL : scatter ? MVN_BWD_FORM_ONE : MVN_BWD_FORM_GENERIC;
-  if (scatter) {
-    int po = 1 ^ ((g.L - 1) & 1);  // (so that layer 0 writes pair 1 and the dense dx0 can go to dx_a)
-    for (int l = g.L - 1; l >= 0; --l) {
-      const int t_lo = A_lo[l + 1];
-      FusedBwdLArgs fa;
-      fa.t_lo = t_lo; fa.t_end = T; fa.d = dilation_of(dims, l); fa.t_skip0 = t_skip0; fa.t_base = g.t_base;
-      fa.up_lo = l + 1 < g.L ? A_lo[l + 2] : 0;
-      fa.up_d = l + 1 < g.L ? dilation_of(dims, l + 1) : 0;
-      fa.wr = p->residual_w[l]; fa.ws = p->skip_w[l]; fa.wf = p->filter_w[l]; fa.wg = p->gate_w[l];
-      fa.ga = spair[po ^ 1][0]; fa.gp = spair[po ^ 1][1];
-      if (l == g.L - 1) fa.ga.p = nullptr;  // the last layer's residual output is unused: no dxo
-      fa.dskip = dskip;
-      fa.th = act_view(fwd->th + (size_t)l * g.act, batch, C, g.Tp);
-      fa.sg = act_view(fwd->sg + (size_t)l * g.act, batch, C, g.Tp);
-      fa.xin = act_view(fwd->acts + (size_t)l * g.act, batch, C, g.Tp);
-      fa.oa = spair[po][0]; fa.op = spair[po][1];
-      fa.dfg = (has_ctx || (glob && !bf16)) ? dfg : Act{nullptr, 0, 0};
-      WgRsOp wr;
-      wr.t_begin = t_lo; wr.t_end = T; wr.C = C; wr.Kc = Kc; wr.t_skip0 = t_skip0; wr.t_base = g.t_base;
-      wr.dxo = fa.ga; wr.dskip = dskip; wr.th = fa.th; wr.sg = fa.sg;
-      wr.dwr = gr->residual_w[l]; wr.dbr = gr->residual_b[l]; wr.dws = gr->skip_w[l]; wr.dbs = gr->skip_b[l];
-      WgFgOpT<false> wf;
-      wf.t_begin = t_lo; wf.t_end = T; wf.C = C; wf.d = fa.d; wf.dfg = dfg; wf.xin = fa.xin; wf.ctx = ctxv;
-      wf.dwf = gr->filter_w[l]; wf.dwg = gr->gate_w[l];
-      wf.dwcf = nullptr; wf.dwcg = nullptr; wf.dbcf = nullptr; wf.dbcg = nullptr;
-      FusedBwdLPlan pl;
-      if (!bwd_layer64_plan(t_lo, T, batch, sc_bias, sc_bias_floats, sc_slab, sc_slab_floats, &pl)) {
-        set_error("mvn_backward: the fused layer backward lost its scratch at layer %d", l);
-        return MVN_ERR_BAD_ARG;
-      }
-      // (bf16 + labels: the row sums come out of the layer kernel itself, no dfg tensor -- fused_bf16.h)
-      rc = bf16 ? launch_bwd_layer64_bf16(fa, wr, wf, batch, pl, s, g_part, g_part ? grow + (size_t)l * batch * 128 : nullptr)
-                : launch_bwd_layer64(fa, wr, wf, batch, pl, s);
-      if (rc) return rc;
-      if (glob && !bf16)  // the label's term: row sums of df | dg over the layer's valid columns (global_cond.h)
-        hipLaunchKernelGGL(global_rowsum_kernel, dim3(32, batch), dim3(256), 0, s, bwd->dfg, (long long)2 * C * g.Tp, g.Tp,
-                           t_lo, T, grow + (size_t)l * batch * 128);
-      if (has_ctx) {  // (behind the layer's reduce: the slab scratch is free again)
-        int c_chunks = 0, c_chunk_t = 0;
-        if (!bwd_dctx_wgctx64_fits(t_lo, T, batch, cx_bias, cx_bias_floats, cx_slab, cx_slab_floats, &c_chunks, &c_chunk_t)) {
-          set_error("mvn_backward: the context pass lost its scratch at layer %d", l);
-          return MVN_ERR_BAD_ARG;
-        }
-        FusedBwdCArgs fc;
-        fc.t_begin = t_lo; fc.t_end = T; fc.wcf = p->ctx_filter_w[l]; fc.wcg = p->ctx_gate_w[l];
-        fc.dfg = dfg; fc.ctx = ctxv; fc.dctx = dctxv;
-        WgCtxOp co;
-        co.dwcf = gr->ctx_filter_w[l]; co.dwcg = gr->ctx_gate_w[l]; co.dbcf = gr->ctx_filter_b[l]; co.dbcg = gr->ctx_gate_b[l];
-        launch_bwd_dctx_wgctx64(fc, co, batch, cx_bias, cx_slab, c_chunks, c_chunk_t, s);
-      }
-      po ^= 1;
-    }
-    // the first layer's input gradient in dense form for the embedding / causal-conv gradient below
-    hipLaunchKernelGGL(bwd_scatter_combine_kernel, dim3((T + 255) / 256, C, batch), dim3(256), 0, s, spair[po ^ 1][0],
-                       spair[po ^ 1][1], spair[0][0], C, A_lo[1], dilation_of(dims, 0), T);
-    dxo_p = bwd->dx_a;
-  }
-  for (int l = scatter ? -1 : g.L - 1; l >= 0; --l) {
+  float *cur = bwd->dx_a, *nxt = bwd->dx_b;
+  for (int l = pl.scatter ? -1 : g.L - 1; l >= 0; --l) {
     const int d = dilation_of(dims, l);
     const int t_lo = A_lo[l + 1];
-    Act th = act_view(fwd->th + (size_t)l * g.act, batch, C, g.Tp);
-    Act sg = act_view(fwd->sg + (size_t)l * g.act, batch, C, g.Tp);
-    Act xin = act_view(fwd->acts + (size_t)l * g.act, batch, C, g.Tp);
+    const HalvesGeom h = halves_geometry(pl, g, has_ctx, batch, l);
     Act dxo = act_view(dxo_p, batch, C, g.Tp);
+    WgRsOp wr; WgFgOpT<false> wf; FusedBwdCArgs fc; WgCtxOp co;
+    layer_ops(l, dxo, wr, wf, fc, co);
     if (l < g.L - 1) {  // the side stream's work on the previous layer read dxo's twin and dfg
       await(2, s);
       await(3, s);
     }
     await(0, s2);
-    WgRsOp wr;
-    wr.t_begin = t_lo; wr.t_end = T; wr.C = C; wr.Kc = Kc; wr.t_skip0 = t_skip0; wr.t_base = g.t_base;
-    wr.dxo = dxo; wr.dskip = dskip; wr.th = th; wr.sg = sg;
-    wr.dwr = gr->residual_w[l]; wr.dbr = gr->residual_b[l]; wr.dws = gr->skip_w[l];
-    wr.dbs = gr->skip_b[l];
-    bool fused_a = false;
     PendingRsReduce<WgRsOp> pend;
-    if (fused_bwd && C == 64 && Kc == 64 && bias_scratch2) {
-      // dz and the residual/skip weight gradients from ONE pass over dxo, dskip, tanh, sigmoid
-      // (fused_bwd.h; conditioned layers too: nothing here touches the context); on the main
-      // stream: the side stream only keeps the filter/gate gradient
+    if (h.a) {
+      // dz and the residual/skip weight gradients from ONE pass over dxo, dskip, tanh, sigmoid (fused_bwd.h; conditioned
+      // layers too: nothing here touches the context); its reduction runs in the second half's reduce launch
       FusedBwdAArgs fa;
       fa.t_begin = t_lo; fa.t_end = T; fa.t_skip0 = t_skip0; fa.t_base = g.t_base;
       fa.wr = p->residual_w[l]; fa.ws = p->skip_w[l];
-      fa.dxo = dxo; fa.dskip = dskip; fa.th = th; fa.sg = sg; fa.dfg = dfg;
-      // (all_fused: its reduction runs in the second half's reduce launch)
-      fused_a = launch_bwd_dz_wgrs64(fa, wr, batch, bias_scratch2, bias2_floats, slab, slab_floats, s,
-                                     all_fused ? &pend : nullptr);
-    }
-    if (!fused_a) {
-      if (bias_scratch2)
-        launch_wgrad2<1>(wr, C + Kc, C, batch, bias_scratch2, slab, slab_floats, s2);
-      else
-        launch_wgrad(wr, C + Kc, C, batch, bias_scratch, s2);
+      fa.dxo = dxo; fa.dskip = dskip; fa.th = wr.th; fa.sg = wr.sg; fa.dfg = dfg;
+      launch_bwd_dz_wgrs64(fa, wr, batch, pl.bias2.p, pl.slab.p, h.a_chunks, h.a_chunk_t, s, &pend);
+    } else if (pl.bias2.p) {
+      launch_wgrad2<1>(wr, C + Kc, C, batch, pl.bias2.p, pl.slab.p, pl.slab.floats, s2);
+    } else {
+      launch_wgrad(wr, C + Kc, C, batch, pl.wg_bias.p, s2);
     }
     signal(2, s2);
-    if (!fused_a) {
+    if (!h.a) {
       DzOp dz;
       dz.K = C + Kc; dz.t_begin = t_lo; dz.t_end = T; dz.C = C; dz.Kc = Kc; dz.t_skip0 = t_skip0;
       dz.t_base = g.t_base;
       dz.wr = p->residual_w[l]; dz.ws = p->skip_w[l];
-      dz.dxo = dxo; dz.dskip = dskip; dz.th = th; dz.sg = sg; dz.dfg = dfg;
+      dz.dxo = dxo; dz.dskip = dskip; dz.th = wr.th; dz.sg = wr.sg; dz.dfg = dfg;
       launch_gemm_staged(dz, C, batch, s);
     }
     signal(1, s);
-    // conditioned layer: dctx and the context-conv gradients as a third fused pass over dfg
-    // (fused_bwd.h), which leaves the audio taps to the fused second half; decided up front from
-    // the scratch sizes -- the generic conditioned path computes taps and context rows TOGETHER
-    int c_chunks = 0, c_chunk_t = 0;
-    const bool fused_c = has_ctx && fused_a && all_fused &&
-                         bwd_dctx_wgctx64_fits(t_lo, T, batch, bias_scratch2, bias2_floats, slab, slab_floats, &c_chunks,
-                                               &c_chunk_t);
-    bool fused_b = false;
-    if (fused_bwd && C == 64 && (!has_ctx || fused_c)) {
-      // dx and the filter/gate weight gradients from ONE pass over dfg (fused_bwd.h)
+    if (h.b) {  // dx and the filter/gate weight gradients from ONE pass over dfg (fused_bwd.h), behind the first half's slabs
       FusedBwdBArgs fb;
       fb.t_out0 = A_lo[l]; fb.t_lo = t_lo; fb.t_end = T; fb.d = d;
       fb.wf = p->filter_w[l]; fb.wg = p->gate_w[l];
-      fb.dxo = dxo; fb.dfg = dfg; fb.xin = xin; fb.dxi = act_view(cur, batch, C, g.Tp);
-      WgFgOpT<false> wf;
-      wf.t_begin = t_lo; wf.t_end = T; wf.C = C; wf.d = d; wf.dfg = dfg; wf.xin = xin; wf.ctx = ctxv;
-      wf.dwf = gr->filter_w[l]; wf.dwg = gr->gate_w[l];
-      wf.dwcf = nullptr; wf.dwcg = nullptr; wf.dbcf = nullptr; wf.dbcg = nullptr;
-      rc = launch_bwd_dx_wgfg64(fb, wf, batch, slab, slab_floats, s, &fused_b, &pend);
+      fb.dxo = dxo; fb.dfg = dfg; fb.xin = wf.xin; fb.dxi = act_view(cur, batch, C, g.Tp);
+      rc = launch_bwd_dx_wgfg64(fb, wf, batch, pl.slab.p + h.a_used, h.b_chunks, h.b_chunk_t, s, &pend);
       if (rc) return rc;
     }
     flush_pending_rs(pend, s);  // (only if the second half did not take it along)
-    if (fused_a && fused_b) g_last_bwd_form = MVN_BWD_FORM_HALVES;
-    const bool ctx_done = fused_c && fused_b;
-    if (ctx_done) {  // (behind the layer's reduce: the slab scratch is free again)
-      FusedBwdCArgs fc;
-      fc.t_begin = t_lo; fc.t_end = T; fc.wcf = p->ctx_filter_w[l]; fc.wcg = p->ctx_gate_w[l];
-      fc.dfg = dfg; fc.ctx = ctxv; fc.dctx = dctxv;
-      WgCtxOp co;
-      co.dwcf = gr->ctx_filter_w[l]; co.dwcg = gr->ctx_gate_w[l]; co.dbcf = gr->ctx_filter_b[l]; co.dbcg = gr->ctx_gate_b[l];
-      launch_bwd_dctx_wgctx64(fc, co, batch, bias_scratch2, slab, c_chunks, c_chunk_t, s);
-    }
+    // conditioned layer: dctx and the context-conv gradients as a third fused pass over dfg (fused_bwd.h), which leaves
+    // the audio taps to the fused second half (behind the layer's reduce: the slab scratch is free again); the generic
+    // conditioned path computes taps and context rows TOGETHER
+    const bool ctx_done = has_ctx && h.a && h.b;
+    if (ctx_done) launch_bwd_dctx_wgctx64(fc, co, batch, pl.bias2.p, pl.slab.p, h.a_chunks, h.a_chunk_t, s);
     await(1, s2);
-    auto run_wf = [&](auto wf) {
-      wf.t_begin = t_lo; wf.t_end = T; wf.C = C; wf.d = d; wf.dfg = dfg; wf.xin = xin; wf.ctx = ctxv;
-      wf.dwf = gr->filter_w[l]; wf.dwg = gr->gate_w[l];
-      wf.dwcf = has_ctx ? gr->ctx_filter_w[l] : nullptr; wf.dwcg = has_ctx ? gr->ctx_gate_w[l] : nullptr;
-      wf.dbcf = has_ctx ? gr->ctx_filter_b[l] : nullptr; wf.dbcg = has_ctx ? gr->ctx_gate_b[l] : nullptr;
+    auto run_wf = [&](auto w) {
+      w.t_begin = t_lo; w.t_end = T; w.C = C; w.d = d; w.dfg = dfg; w.xin = wf.xin; w.ctx = ctxv;
+      w.dwf = gr->filter_w[l]; w.dwg = gr->gate_w[l];
+      w.dwcf = has_ctx ? gr->ctx_filter_w[l] : nullptr; w.dwcg = has_ctx ? gr->ctx_gate_w[l] : nullptr;
+      w.dbcf = has_ctx ? gr->ctx_filter_b[l] : nullptr; w.dbcg = has_ctx ? gr->ctx_gate_b[l] : nullptr;
       if (!has_ctx)
-        launch_wgrad2<2>(wf, 2 * C, 2 * C, batch, nullptr, slab, slab_floats, s2);
-      else if (bias_scratch2)  // (shares the bias scratch with WgRs: same stream, one after the other)
-        launch_wgrad2<2>(wf, 2 * C, 3 * C, batch, bias_scratch2, slab, slab_floats, s2);
+        launch_wgrad2<2>(w, 2 * C, 2 * C, batch, nullptr, pl.slab.p, pl.slab.floats, s2);
+      else if (pl.bias2.p)  // (shares the bias scratch with WgRs: same stream, one after the other)
+        launch_wgrad2<2>(w, 2 * C, 3 * C, batch, pl.bias2.p, pl.slab.p, pl.slab.floats, s2);
       else
-        launch_wgrad(wf, 2 * C, 3 * C, batch, ctx_bias_scratch, s2);
+        launch_wgrad(w, 2 * C, 3 * C, batch, pl.ctx_wg_bias, s2);
     };
-    if (fused_b) {
+    if (h.b) {
     } else if (has_ctx) run_wf(WgFgOpT<true>()); else run_wf(WgFgOpT<false>());
     signal(3, s2);
     if (has_ctx && !ctx_done) {
@@ -1889,7 +1900,7 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
       dc.wcf = p->ctx_filter_w[l]; dc.wcg = p->ctx_gate_w[l]; dc.dfg = dfg; dc.dctx = dctxv;
       launch_gemm_staged(dc, C, batch, s);
     }
-    if (!fused_b) {
+    if (!h.b) {
       DxOp dx;
       dx.K = 4 * C; dx.t_begin = A_lo[l]; dx.t_end = T; dx.C = C; dx.d = d; dx.t_lo = t_lo;
       dx.wf = p->filter_w[l]; dx.wg = p->gate_w[l];
@@ -1902,55 +1913,37 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
   }
   await(2, s);  // join: everything the side stream did is ordered before what follows on s
   await(3, s);
-  if (fwd->dense_audio) {
+  const Act dx0 = act_view(dxo_p, batch, C, g.Tp);
+  float *const tab = pl.embed_tab.p;
+  if (pl.embed == EMBED_DENSE_AUDIO) {
     WgCausalOp wc;
-    wc.t_begin = 0; wc.t_end = T; wc.C = C; wc.Q = Q; wc.dx0 = act_view(dxo_p, batch, C, g.Tp);
+    wc.t_begin = 0; wc.t_end = T; wc.C = C; wc.Q = Q; wc.dx0 = dx0;
     wc.audio = act_view(const_cast<float *>(fwd->dense_audio), batch, Q, fwd->dense_ld);
     wc.dcw = gr->causal_w;
     launch_wgrad(wc, C, 2 * Q, batch, nullptr, s);
-  } else {
-    // channels per workgroup: the table slice [cg][Q][2] fits 64 KB of LDS
-    if (Q > 8192) {
-      set_error("mvn_backward: input_channels %d > 8192 not supported by the embedding gradient", Q);
-      return MVN_ERR_UNSUPPORTED;
-    }
+  } else if (pl.embed == EMBED_MFMA || pl.embed == EMBED_LDS) {
     const int chunks64 = (T + EG64_CHUNK - 1) / EG64_CHUNK;
-    // bf16 at short outputs (da1 too small for the per-chunk tables): the layer loop's slab scratch, idle by now, so
-    // that the table is summed in chunk order there too, not with atomics -- the audio-only and the conditioned pass
-    // then agree to the bit (same partials, same order, whichever buffer holds them)
-    if (bf16 && !(slab && (size_t)chunks64 * batch * 2 * Q * 64 <= slab_floats) && cx_slab &&
-        (size_t)chunks64 * batch * 2 * Q * 64 <= cx_slab_floats) {
-      slab = cx_slab;
-      slab_floats = cx_slab_floats;
+    if (pl.embed == EMBED_MFMA) {
+      hipLaunchKernelGGL(embed_grad64_mfma_kernel, dim3(chunks64, batch), dim3(256), 0, s, index, index_stride, dx0, T, tab);
+    } else {
+      const size_t lds = (size_t)Q / EG64_PARTS * 64 * sizeof(float) + EG64_CHUNK * sizeof(int);
+      rc = ensure_max_dynamic_lds((const void *)embed_grad64_kernel, "hipFuncSetAttribute(embed_grad64)");
+      if (rc) return rc;
+      hipLaunchKernelGGL(embed_grad64_kernel, dim3(chunks64, batch, 2 * EG64_PARTS), dim3(64), lds, s, index, index_stride,
+                         dx0, Q, T, tab);
     }
-    if (C == 64 && Q % EG64_PARTS == 0 && (size_t)Q / EG64_PARTS * 64 * sizeof(float) <= 64 * 1024 && slab &&
-        (size_t)chunks64 * batch * 2 * Q * 64 <= slab_floats) {
-      // Q = 256: the product form; any other Q: the LDS read-modify-write kernel
-      if (Q == 256) {
-        hipLaunchKernelGGL(embed_grad64_mfma_kernel, dim3(chunks64, batch), dim3(256), 0, s, index, index_stride,
-                           act_view(dxo_p, batch, C, g.Tp), T, slab);
-      } else {
-        const size_t lds = (size_t)Q / EG64_PARTS * 64 * sizeof(float) + EG64_CHUNK * sizeof(int);
-        rc = ensure_max_dynamic_lds((const void *)embed_grad64_kernel, "hipFuncSetAttribute(embed_grad64)");
-        if (rc) return rc;
-        hipLaunchKernelGGL(embed_grad64_kernel, dim3(chunks64, batch, 2 * EG64_PARTS), dim3(64), lds, s, index, index_stride,
-                           act_view(dxo_p, batch, C, g.Tp), Q, T, slab);
-      }
-      EmbedSlabOp64 eo;
-      eo.dcw = gr->causal_w; eo.Q = Q;
-      hipLaunchKernelGGL(slab_reduce_kernel<EmbedSlabOp64>, dim3((unsigned)(2 * Q * 64 / 32)), dim3(32 * RED_SEG), 0, s,
-                         eo, slab, chunks64 * batch, 2 * Q, 64);
-      return check_hip(hipGetLastError(), "mvn_backward");
-    }
+    EmbedSlabOp64 eo;
+    eo.dcw = gr->causal_w; eo.Q = Q;
+    hipLaunchKernelGGL(slab_reduce_kernel<EmbedSlabOp64>, dim3((unsigned)(2 * Q * 64 / 32)), dim3(32 * RED_SEG), 0, s,
+                       eo, tab, chunks64 * batch, 2 * Q, 64);
+  } else {
     const int cg = std::max(1, std::min(C, 8192 / Q));
     const int chunks = (T + EG_CHUNK - 1) / EG_CHUNK;
-    // one table copy per (chunk, sequence) in the layer loop's slab scratch (idle by now), summed by
-    // slab_reduce_kernel; without room for them the workgroups add to the table with atomics
     const size_t table = (size_t)C * Q * 2;
-    float *part = (table % 64 == 0 && slab && (size_t)chunks * batch * table <= slab_floats) ? slab : nullptr;
+    float *part = pl.embed == EMBED_TABLES ? tab : nullptr;
     hipLaunchKernelGGL(embed_grad_kernel, dim3(chunks, (C + cg - 1) / cg, batch),
                        dim3(1024), (size_t)cg * Q * 2 * sizeof(float), s, gr->causal_w, index,
-                       index_stride, act_view(dxo_p, batch, C, g.Tp), C, Q, T, cg, part);
+                       index_stride, dx0, C, Q, T, cg, part);
     if (part) {
       EmbedSlabOp eo;
       eo.dcw = gr->causal_w;
@@ -1966,7 +1959,7 @@ int mvn_backward(const mvn_dims *dims, const mvn_params *p, const mvn_param_grad
                  const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
                  const float *dout, int normalize, int remove_last, void *stream_) {
   const SeqMode m = {SeqMode::F32, SeqMode::PLAIN, "mvn_backward"};
-  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m);
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m, fb_device_cus());
 }
 
 int mvn_backward_bf16(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
@@ -1974,7 +1967,7 @@ int mvn_backward_bf16(const mvn_dims *dims, const mvn_params *p, const mvn_param
                       const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
                       const float *dout, int normalize, int remove_last, void *stream_) {
   const SeqMode m = {SeqMode::BF16, SeqMode::PLAIN, "mvn_backward_bf16"};
-  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m);
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m, fb_device_cus());
 }
 
 // The queries answer 0 for anything make_geometry refuses and for an empty batch
@@ -2062,7 +2055,7 @@ int mvn_backward_global(const mvn_dims *dims, const mvn_params *p, const mvn_par
     return MVN_ERR_BAD_ARG;
   }
   const SeqMode m = {SeqMode::F32, SeqMode::GLOBAL, "mvn_backward_global", scratch, scratch_floats, rowsum};
-  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m);
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m, fb_device_cus());
 }
 
 int mvn_global_bf16_path(const mvn_dims *dims, int batch, int t_len) {
@@ -2072,7 +2065,7 @@ int mvn_global_bf16_path(const mvn_dims *dims, int batch, int t_len) {
 
 size_t mvn_global_bf16_scratch_floats(const mvn_dims *dims, int batch, int t_len) {
   Geometry g;
-  return query_geometry(dims, batch, t_len, g) ? global_bf16_scratch_floats(dims, g, batch) : 0;
+  return query_geometry(dims, batch, t_len, g) ? global_bf16_scratch_floats(dims, g, batch, fb_device_cus()) : 0;
 }
 
 int mvn_forward_bf16_global(const mvn_dims *dims, const mvn_params *p, const int32_t *index, int index_stride,
@@ -2103,12 +2096,13 @@ int mvn_backward_bf16_global(const mvn_dims *dims, const mvn_params *p, const mv
     set_error("mvn_backward_bf16_global: scratch / rowsum is NULL");
     return MVN_ERR_BAD_ARG;
   }
-  if (batch >= 1 && scratch_floats < global_bf16_scratch_floats(dims, g, batch)) {
+  const int cus = fb_device_cus();
+  if (batch >= 1 && scratch_floats < global_bf16_scratch_floats(dims, g, batch, cus)) {
     set_error("mvn_backward_bf16_global: scratch holds %zu floats, mvn_global_bf16_scratch_floats() asks for %zu", scratch_floats,
-              global_bf16_scratch_floats(dims, g, batch));
+              global_bf16_scratch_floats(dims, g, batch, cus));
     return MVN_ERR_BAD_ARG;
   }
-  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m);
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m, cus);
 }
 
 // Video context on bf16 operands (fused_bf16.h: the CTX and WRITE_DFG instantiations, with the fp32
@@ -2155,11 +2149,12 @@ int mvn_backward_bf16_ctx(const mvn_dims *dims, const mvn_params *p, const mvn_p
     set_error("mvn_backward_bf16_ctx: no context-conv parameters or gradients / ctx_ld < t_len");
     return MVN_ERR_BAD_ARG;
   }
-  if (!scratch || (batch >= 1 && scratch_floats < global_scratch_floats(dims, g, batch))) {
+  const int cus = fb_device_cus();
+  if (!scratch || (batch >= 1 && scratch_floats < global_scratch_floats(dims, g, batch, cus))) {
     set_error("mvn_backward_bf16_ctx: scratch is NULL or holds fewer floats than mvn_bf16_ctx_scratch_floats()");
     return MVN_ERR_BAD_ARG;
   }
-  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m);
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m, cus);
 }
 
 int mvn_backward_scratch(const mvn_dims *dims, const mvn_params *p, const mvn_param_grads *gr,
@@ -2172,12 +2167,12 @@ int mvn_backward_scratch(const mvn_dims *dims, const mvn_params *p, const mvn_pa
     return MVN_ERR_BAD_ARG;
   }
   const SeqMode m = {SeqMode::F32, SeqMode::PLAIN, "mvn_backward_scratch", scratch, scratch_floats};
-  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m);
+  return backward_impl(dims, p, gr, index, index_stride, batch, t_len, fwd, bwd, out, dout, normalize, remove_last, stream_, m, fb_device_cus());
 }
 
 size_t mvn_global_scratch_floats(const mvn_dims *dims, int batch, int t_len) {
   Geometry g;
-  return query_geometry(dims, batch, t_len, g) ? global_scratch_floats(dims, g, batch) : 0;
+  return query_geometry(dims, batch, t_len, g) ? global_scratch_floats(dims, g, batch, fb_device_cus()) : 0;
 }
 
 int mvn_context_add_global(float *context_tm, const float *global, int batch, int channels, int t_len, int fill,

@@ -34,11 +34,11 @@ Branches (C = K = 64, Q = 256; constants from the sources, asserted per row by _
   123200 (fused_fwd_bf3.h:837-839); g.act = B 64 Tp.
   z "layers":   g.act >= L FS3_PACK_F                                   (sequence.hip forward_impl, `bf3 && ...`)
   z "fwd head": g.act >= L FSC_PACK_F + DS3_IMG_F                       (forward_impl, `head_img`)
-  z "bwd head": g.act >= L FSC_PACK_F + DS3_IMG_F + DS3_BWD_IMG_F       (backward_impl, `bwd_head_img`)
-  bias "reserved": max(ceil((T + 31) / 512) B, 2 CUs + B) 128 <= B Q Sp / 2   (backward_impl, `bias_scratch2`)
-  bias "small":    not reserved and  B Q Sp / 24704 >= B                       (backward_impl, `sc_bias`)
+  z "bwd head": g.act >= L FSC_PACK_F + DS3_IMG_F + DS3_BWD_IMG_F       (plan_backward, `BwdPlan::head_img`)
+  bias "reserved": max(ceil((T + 31) / 512) B, 2 CUs + B) 128 <= B Q Sp / 2   (plan_backward, `BwdPlan::bias2`)
+  bias "small":    not reserved and  B Q Sp / 24704 >= B                       (plan_backward, `BwdPlan::sc_bias`)
   bias "none":     neither: no one-kernel form, mvn_last_backward_form() == 1
-  head_scratch_ok: ceil((S + 31) / 512) B 256 257 <= B 128 Tp                  (backward_impl, `head_scratch_ok`)
+  head_scratch_ok: ceil((S + 31) / 512) B 256 257 <= B 128 Tp                  (plan_backward, `BwdPlan::head_bias`)
 
 Largest errors seen on an MI355X (256 CUs; the file runs in 17 s), printed per case with pytest -s:
   forward, fp32 entry point (bound 2e-5) ... out 4.7e-7, acts 4.2e-7, th 7.8e-7, sg 2.3e-7, skip 2.8e-7, a1 2.3e-7
@@ -404,7 +404,7 @@ def _full(c, what, entry="f32", form=None):
 
 # ---- 1. C = K = 64, Q = 256: the default forms on both sides of every scratch threshold ---------------------------
 def _branches(c, cus):
-    """What the host code of forward_impl / backward_impl decides for a C = K = 64, Q = 256 audio-only call
+    """What plan_forward / plan_backward (sequence.hip) decide for a C = K = 64, Q = 256 audio-only call
     (inequalities and constants: module docstring)"""
     pl = N.lib().mvn_padded_len
     Tp, Sp = pl(c.T), pl(c.S + 31)
@@ -474,9 +474,10 @@ class _Switch:
 
 
 def _halves_fit(c, cus):
-    """Whether the two fused halves (form 2) find their slabs at layer 0, the longest: fused_bwd.h launch_bwd_dz_wgrs64
-    (chunks from fb_chunks, two workgroups per CU; 128 x 64 floats and 128 bias sums each) and launch_bwd_dx_wgfg64
-    (one per CU; 128 x 128 floats each, behind the first half's), in da1 less the bias_scratch2 reservation"""
+    """Whether the two fused halves (form 2) find their slabs at layer 0, the longest (sequence.hip halves_geometry):
+    fused_bwd.h bwd_dz_wgrs64_fits (chunks from fb_chunks, two workgroups per CU; 128 x 64 floats and 128 bias sums
+    each) and bwd_dx_wgfg64_fits (one per CU; 128 x 128 floats each, behind the first half's), in BwdPlan::slab, which
+    is da1 less the BwdPlan::bias2 reservation"""
     Sp = N.lib().mvn_padded_len(c.S + 31)
     bias2 = max((c.T + 31 + 511) // 512 * c.B, 2 * cus + c.B) * 128
 
@@ -619,7 +620,7 @@ def test_bf16_entry_points(name):
     from test_bf16_train_gpu import _check_grads
     ls, ss, Q, B, T = BF16[name]
     c = Case(ls, ss, Q, 64, 64, B, T, wide=True, rl=True)
-    if name == "t_rf_plus_1":   # sequence.hip backward_impl, `if (!fits() && fwd->z)`: n_fit = B Q Sp / 24704 < B
+    if name == "t_rf_plus_1":   # sequence.hip plan_backward, `!layer_fits() && fwd->z`: B Q Sp / 24704 < B
         assert c.B * c.Q * N.lib().mvn_padded_len(c.S + 31) // 24704 < c.B
     r = Run(c, "bf16")
     ref, emu = r.d["ref"], _emulation(c.key())
