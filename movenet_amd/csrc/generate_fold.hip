@@ -20,8 +20,9 @@
 // reads zl and sk but no xp', so its helpers send sk' first and no xp'.
 // Waves 0-3 (the chain) compute
 //     z_0 = gate(Wc_0 xp + (Wc_0 Wr_prev) zl + pf_0)
-//     z_1 = gate((Wc_1 Wr_0) z_0 + base_1 + pf_1)          and (Wc_2 Wr_0) z_0 for the helpers' base_2
-//     z_2 = gate((Wc_2 Wr_1) z_1 + base_2 + pf_2)          -> sent on as the next stage's zl
+//     z_1 = gate((Wc_1 Wr_0) z_0 + base_1 + pf_1)
+//     z_2 = gate((Wc_2 Wr_1) z_1 + (Wc_2 Wr_0) z_0 + base_2 + pf_2)   -> sent on as the next stage's zl
+//           (the z_0 term from registers, while the LDS reads of z_1 are in flight)
 // with their five matrices in registers; waves 4-7 (the helpers) compute one phase ahead
 //     base_1 = Wc_1 xp + (Wc_1 Wr_prev) zl,    x_0 = xp + Wr_prev zl
 //     base_2 = Wc_2 x_0  [+ the chain's term]
@@ -139,6 +140,37 @@ __device__ __forceinline__ void pair_acc(v2f (&acc)[4], const v2f (&w)[16], cons
   }
 }
 __device__ __forceinline__ v2f pair_sum(const v2f (&acc)[4]) { return (acc[0] + acc[2]) + (acc[1] + acc[3]); }
+// acc (+)= w * {x.x, x.x}: pk_fma_hi's twin for the low element of a register pair
+__device__ __forceinline__ v2f pk_fma_lo(v2f w, v2f xpair, v2f acc) {
+  asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(w), "v"(xpair));
+  return acc;
+}
+__device__ __forceinline__ v2f pk_mul_lo(v2f w, v2f xpair) {
+  v2f r;
+  asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(r) : "v"(w), "v"(xpair));
+  return r;
+}
+// pair_acc<true> with EVERY broadcast spelled as an op_sel form, against inputs held as four 128-bit registers: the
+// same 16 products into the same four accumulators in the same order.  For a block whose other instructions do not
+// lead the compiler to fold the broadcasts (it copies each input to a fresh register pair there: 16 moves more).
+typedef float vf4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void pair_acc_sel(v2f (&acc)[4], const v2f (&w)[16], const vf4 (&x)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const v2f lo = v2f{x[i].x, x[i].y}, hi = v2f{x[i].z, x[i].w};
+    if (i == 0) {
+      acc[0] = pk_mul_lo(w[0], lo);
+      acc[1] = pk_mul_hi(w[1], lo);
+      acc[2] = pk_mul_lo(w[2], hi);
+      acc[3] = pk_mul_hi(w[3], hi);
+    } else {
+      acc[0] = pk_fma_lo(w[4 * i], lo, acc[0]);
+      acc[1] = pk_fma_hi(w[4 * i + 1], lo, acc[1]);
+      acc[2] = pk_fma_lo(w[4 * i + 2], hi, acc[2]);
+      acc[3] = pk_fma_hi(w[4 * i + 3], hi, acc[3]);
+    }
+  }
+}
 // SPLIT format, half H: one row against the 16 inputs
 template <int H>
 __device__ __forceinline__ float split_dot(const v2f (&w)[16], const f4 (&x)[4]) {
@@ -155,14 +187,13 @@ __device__ __forceinline__ float split_dot(const v2f (&w)[16], const f4 (&x)[4])
 // LDS accesses by byte address: base register + immediate (an address formed from the dynamic
 // LDS symbol is a register per address; 20 of them spilled the chain's weights)
 typedef __attribute__((address_space(3))) float lds_f;
-typedef float vf4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) vf4 lds_f4;
-__device__ __forceinline__ f4 lds_load4(unsigned addr) {
-  const vf4 v = *(const lds_f4 *)(uintptr_t)addr;
+__device__ __forceinline__ f4 as_f4(vf4 v) {
   f4 r;
   r.x = v.x; r.y = v.y; r.z = v.z; r.w = v.w;
   return r;
 }
+__device__ __forceinline__ f4 lds_load4(unsigned addr) { return as_f4(*(const lds_f4 *)(uintptr_t)addr); }
 __device__ __forceinline__ unsigned lds_addr(const float *p) { return (unsigned)(uintptr_t)(lds_f *)p; }
 #define LDSF(addr, off) (*(lds_f *)(uintptr_t)((addr) + 4u * (unsigned)(off)))
 template <int N4>
@@ -481,15 +512,17 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
       MVN_FINE(b, s, ts - a.t_begin, 2, 0);
       // ---- phase 1
       v2f b2 = {0.f, 0.f};  // chain: (Wc_2 Wr_0) z_0, this thread's 16 inputs; helpers: .x = their 16 terms of Wr_0 z_0
+      // z_0, this lane's 16 inputs: both groups read it here; the chain keeps it across the phase-1 barrier for its
+      // second product on it, (Wc_2 Wr_0) z_0, which is first needed at the end of phase 2 (one set of registers for both
+      // groups: held in the chain's branch alone, the 16 registers would be live through the helpers' phase 1 as well)
+      vf4 z0v[NF4];
+#pragma unroll
+      for (int i = 0; i < NF4; ++i) z0v[i] = *(const lds_f4 *)(uintptr_t)(vq + 4u * O_Z0 + 16u * i);
       if (chain) {
-        f4 xz[NF4];
-        ldsv<NF4>(xz, vq, O_Z0);
-        v2f acc[4], acc2[4];
+        const f4 xz[NF4] = {as_f4(z0v[0]), as_f4(z0v[1]), as_f4(z0v[2]), as_f4(z0v[3])};
+        v2f acc[4];
         pair_acc<true>(acc, m2.w, xz);
-        pair_acc<true>(acc2, m4.w, xz);  // (same block as the first: the broadcasts fold into op_sel)
         const v2f fg = pair_sum(acc);
-        b2 = pair_sum(acc2);
-        asm volatile("" : "+v"(b2));  // not to be sunk past the gate (into a block where the broadcasts become moves)
         const float f = chan_sum<KQ>(fg.x) + (LDSF(vc, O_B1) + pf[1]);
         const float g = chan_sum<KQ>(fg.y) + (LDSF(vc, O_B1 + C) + pg[1]);
         const float z = gate_fast(f, g);
@@ -501,9 +534,9 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
         // split over the two phases: this thread's 16 terms of Wr_0 z_0 are summed here and held in b2.x (the
         // register pair the chain keeps its own b2 in); the cross-lane adds and the stream update wait for phase 2.
         // (Measured, DESIGN 4.1c: this phase closes on the helpers again, ~100 cycles later; the hop gives back more.)
-        f4 xa[NF4], xz0[NF4];
+        f4 xa[NF4];
         ldsv<NF4>(xa, vq, O_X0);
-        ldsv<NF4>(xz0, vq, O_Z0);
+        const f4 xz0[NF4] = {as_f4(z0v[0]), as_f4(z0v[1]), as_f4(z0v[2]), as_f4(z0v[3])};
         v2f acc[4];
         pair_acc<true>(acc, m2.w, xa);                             // Wc_2 x_0
         b2.x = split_dot<1>(m3.w, xz0);                            // Wr_0 z_0, before the sum over the channel's lanes
@@ -521,9 +554,20 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
       MVN_FINE(b, s, ts - a.t_begin, 4, 0);
       // ---- phase 2: the chain's z_2 and the helpers' xp' leave as granules; the skip sum follows
       if (chain) {
-        f4 xz[NF4];
-        ldsv<NF4>(xz, vq, O_Z1);
-        v2f acc[4];
+        // the four reads of z_1 go out first; while the LDS serves them (about 128 cycles in which nothing else on the
+        // chain is ready) the SIMD issues (Wc_2 Wr_0) z_0 from the registers kept since phase 1.  Two fences hold the
+        // product in that window: the first (behind the reads, which may not sink past it) keeps it behind the barrier,
+        // the second makes b2 a value BEFORE z_1's first quartet is one (every accumulator chain of the next product starts
+        // on that quartet), so the waits for the reads stand behind the product.
+        vf4 z1v[NF4];
+#pragma unroll
+        for (int i = 0; i < NF4; ++i) z1v[i] = *(const lds_f4 *)(uintptr_t)(vq + 4u * O_Z1 + 16u * i);
+        asm volatile("" : "+v"(z0v[0]), "+v"(z0v[1]), "+v"(z0v[2]), "+v"(z0v[3]) : : "memory");
+        v2f acc[4], acc2[4];
+        pair_acc_sel(acc2, m4.w, z0v);
+        b2 = pair_sum(acc2);
+        asm volatile("" : "+v"(b2), "+v"(z1v[0]));
+        const f4 xz[NF4] = {as_f4(z1v[0]), as_f4(z1v[1]), as_f4(z1v[2]), as_f4(z1v[3])};
         pair_acc<true>(acc, m3.w, xz);
         const v2f fg = pair_sum(acc) + b2;
         const float f = chan_sum<KQ>(fg.x) + (LDSF(vc, O_B2) + pf[2]);
