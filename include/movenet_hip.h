@@ -950,6 +950,51 @@ int mvn_block_dense_backward(const float *w1, const float *w2, int in_channels, 
                              const mvn_block_tensor *dx, float *dw1, float *db1, float *dw2, float *db2, int batch,
                              float *scratch, size_t scratch_floats, void *stream);
 
+/* ---- Local conditioning on log-mel frames (csrc/features.hip; additive, ABI version unchanged) ----
+ * The feature front end: (batch, n_samples) int32 class indices -> (batch, n_mels, F) fp32 log-mel frames,
+ * F = n_samples / hop + 1 (integer division).  With N = n_fft:
+ *   x[b, t]  the mu-law decode of index[b, t] by the formula of the decode call above; 0 for t outside [0, n_samples)
+ *            and for an index outside [0, classes) (nothing is raised)
+ *   frame j  covers samples [j hop - N/2, j hop + N/2), times the window w[n]
+ *   P[k]     |sum_n w[n] x[n] e^{-2 pi i k n / N}|^2, k = 0 .. N/2
+ *   mel      log(max(sum_k fbank[m, k] P[k], floor)), natural log; `energies` != 0: the sum itself, no floor, no log
+ * The kernel knows no mel scale; it reads three DEVICE tables: window (N), twiddle (2 N: cos(2 pi m / N) for m < N, then
+ * sin(2 pi m / N), indexed by (k n) mod N) and fbank (n_mels, N/2 + 1).  The DFT is a product on the fp32 matrix cores
+ * (v_mfma_f32_32x32x2_f32), fp32 throughout, every sum in a fixed order, no atomics: two calls give the same bits.
+ *   mel      DEVICE (batch, n_mels, mel_ld) with mel_ld >= F; only the first F columns of a row are written
+ *   scratch  DEVICE, at least the sizing call's answer in floats (the decoded signal and the power spectra)
+ * MVN_ERR_BAD_ARG before any launch: a null pointer, n_fft not a power of two in [32, 2048], hop outside [1, n_fft],
+ * n_mels < 1, floor <= 0 (NaN included), batch < 0, n_samples < 1, classes < 2, mel_ld < F, a scratch that is too
+ * small, batch or n_mels above 65535, n_samples above 2^30, batch * n_samples above 2^31 - 1.  batch == 0 is MVN_OK
+ * and launches nothing. */
+size_t mvn_logmel_scratch_floats(int batch, int n_samples, int n_fft, int hop);
+int mvn_logmel_frontend(const int32_t *index, int batch, int n_samples, int classes, int n_fft, int hop, int n_mels,
+                        const float *window, const float *twiddle, const float *fbank, float floor, int energies,
+                        float *mel, int mel_ld, float *scratch, size_t scratch_floats, void *stream);
+
+/* The frame up-sampler: mel (batch, n_mels, frames), w (channels, n_mels), bias (channels) -> ctx (batch, channels,
+ * n_samples).  With j = t / hop, a = (t mod hop) / hop, j1 = min(j + 1, frames - 1):
+ *   ctx[b, c, t] = bias[c] + sum_m w[c, m] ((1 - a) mel[b, m, j] + a mel[b, m, j1])
+ * formed as the 1x1 product at frame rate (into scratch) and the interpolation of its rows, stored 16 bytes at a time:
+ * ctx must be 16-byte aligned and ctx_ld a multiple of 4 (>= n_samples).  Needs frames >= (n_samples - 1) / hop + 1.
+ * Any channels >= 1 and n_mels >= 1 (each at most 65535).  scratch: the sizing call's floats.
+ *
+ * The backward: dctx (batch, channels, n_samples) -> dw (channels, n_mels) and dbias (channels), both ACCUMULATED INTO
+ * (NULL: not wanted), and dmel (batch, n_mels, frames), written in full (NULL: not wanted).  dP[b, c, j], the weighted
+ * sum of the up to 2 hop columns of dctx that touch frame j, is formed first (one workgroup per row segment); then
+ * dw = sum dP mel^T, dbias = sum dP, dmel = w^T dP at frame rate.  A frame no column touches has dP = 0 and dmel = 0
+ * exactly.  Fixed order, no atomics.  Every refusal (MVN_ERR_BAD_ARG: null pointers, sizes below 1, a row stride
+ * below its length, a misaligned ctx / ctx_ld, too few frames, a small scratch, batch < 0, frames or n_samples above
+ * 2^30, hop above 2^24) comes before the first launch and writes nothing; batch == 0 is MVN_OK. */
+size_t mvn_upsample_features_scratch_floats(int batch, int channels, int frames);
+int mvn_upsample_features(const float *mel, int mel_ld, const float *w, const float *bias, int batch, int n_mels,
+                          int frames, int channels, int hop, int n_samples, float *ctx, int ctx_ld, float *scratch,
+                          size_t scratch_floats, void *stream);
+int mvn_upsample_features_backward(const float *dctx, int dctx_ld, const float *mel, int mel_ld, const float *w,
+                                   int batch, int n_mels, int frames, int channels, int hop, int n_samples, float *dw,
+                                   float *dbias, float *dmel, int dmel_ld, float *scratch, size_t scratch_floats,
+                                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

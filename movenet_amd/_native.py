@@ -289,6 +289,18 @@ SIGNATURES = {
     "mvn_block_dense_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _BT, _BT, _BT, _BT, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                            C.c_void_p]),
+    # local conditioning on log-mel frames (csrc/features.hip)
+    "mvn_logmel_scratch_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mvn_logmel_frontend": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                      C.c_size_t, C.c_void_p]),
+    "mvn_upsample_features_scratch_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mvn_upsample_features": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]),
+    "mvn_upsample_features_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

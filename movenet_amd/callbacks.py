@@ -136,6 +136,10 @@ class LogSamplesCallback:
         if gen is not None and self.guidance != 1.0:  # (as a sweep's rows carry their temperature)
             for r in rows:
                 r["guidance"] = self.guidance
+        if gen is not None and getattr(pl_module, "use_mel", False):
+            # (each clip was generated under its SOURCE clip's log-mel frames: copy-synthesis)
+            for r in rows:
+                r["conditioning"] = "mel"
         if prompt_ok is not None:
             for r in rows:
                 r["skipped_short"] = skipped_short

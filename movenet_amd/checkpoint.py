@@ -32,10 +32,17 @@ def strip_prefixes(sd: Dict[str, torch.Tensor]) -> "OrderedDict[str, torch.Tenso
     return out
 
 
+def _read(path):
+    return torch.load(path, map_location="cpu", weights_only=True)
+
+
 def load_state_dict_file(path, ema: bool = False) -> "OrderedDict[str, torch.Tensor]":
     """The weights in ``path``; with ``ema`` the averaged weights a run with ``--ema_decay`` saves beside them
     (``"ema_state_dict"``, same prefixes) -- ValueError for a file that holds none."""
-    obj = torch.load(path, map_location="cpu", weights_only=True)
+    return _state_dict_of(_read(path), path, ema)
+
+
+def _state_dict_of(obj, path, ema: bool) -> "OrderedDict[str, torch.Tensor]":
     if ema:
         if not (isinstance(obj, dict) and isinstance(obj.get("ema_state_dict"), dict)):
             raise ValueError(f"{path}: no 'ema_state_dict' (not a checkpoint of a run with --ema_decay > 0)")
@@ -47,6 +54,26 @@ def load_state_dict_file(path, ema: bool = False) -> "OrderedDict[str, torch.Ten
     return strip_prefixes(obj)
 
 
+def _local_record(obj):
+    rec = obj.get("local_conditioning") if isinstance(obj, dict) else None
+    return dict(rec) if isinstance(rec, dict) else None
+
+
+def local_conditioning_of(path):
+    """The ``"local_conditioning"`` record of a checkpoint trained with ``--use_mel 1`` -- ``local_channels``,
+    ``local_hop`` and the mel settings its features were computed with (``mel_fft``, ``mel_fmin``, ``mel_fmax``,
+    ``audio_rate``) -- or None for a file without one."""
+    return _local_record(_read(path))
+
+
 def load_into(model: torch.nn.Module, path, strict: bool = True, ema: bool = False):
-    """model.load_state_dict from any of the reference's checkpoint flavours (``ema``: the averaged weights)."""
-    return model.load_state_dict(load_state_dict_file(path, ema=ema), strict=strict)
+    """model.load_state_dict from any of the reference's checkpoint flavours (``ema``: the averaged weights).  A
+    checkpoint of a run with ``--use_mel 1`` carries its local-conditioning record: a model without a matching
+    ``local_conv`` is given one first (``WaveNet.set_local_conditioning``, on the device of its other parameters), and
+    the record is left in ``model.local_conditioning`` for whoever computes the features."""
+    obj = _read(path)  # (read once: the record and the weights come from the same object)
+    rec = _local_record(obj)
+    if rec is not None and hasattr(model, "set_local_conditioning"):
+        model.set_local_conditioning(int(rec["local_channels"]), int(rec["local_hop"]))
+        model.local_conditioning = rec
+    return model.load_state_dict(_state_dict_of(obj, path, ema), strict=strict)

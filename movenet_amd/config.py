@@ -105,6 +105,18 @@ class TrainingConfig:
     clip_length: str = "resample"
     audio_rate: int = 16000
 
+    # local conditioning on the clip's own log-mel frames (WaveNet(local_channels=mel_bins, local_hop=mel_hop), DESIGN
+    # 4.5d): every batch's features are computed on the GPU from its class indices (ops.logmel: frames of mel_fft samples
+    # mel_hop apart, an HTK filterbank of mel_bins triangles from mel_fmin to mel_fmax Hz at audio_rate; mel_fmax None:
+    # audio_rate / 2) and go to forward() as local_features.  Not with use_video.  Not reference fields: a JSON written
+    # without them loads with the defaults (off).
+    use_mel: bool = False
+    mel_bins: int = 80
+    mel_fft: int = 1024
+    mel_hop: int = 256
+    mel_fmin: float = 0.0
+    mel_fmax: Optional[float] = None
+
     scheduler: Optional[str] = "OneCycleLR"
     lr_pct_start: float = 0.45
     base_learning_rate: float = 0.0003
@@ -193,6 +205,12 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--score_samples", type=_flag, default=False)
     a("--clip_length", type=str, default="resample", choices=["resample", "native"])
     a("--audio_rate", type=int, default=16000)
+    a("--use_mel", type=_flag, default=False)
+    a("--mel_bins", type=int, default=80)
+    a("--mel_fft", type=int, default=1024)
+    a("--mel_hop", type=int, default=256)
+    a("--mel_fmin", type=float, default=0.0)
+    a("--mel_fmax", type=float, default=None)
     a("--n_epochs", type=int, default=10)
     a("--n_steps_per_epoch", type=int, default=None)
     a("--use_video", type=_flag, default=True)
@@ -240,7 +258,7 @@ def config_from_args(args) -> TrainingConfig:
         "lr_pct_start base_learning_rate scheduler_step_size_up scheduler_step_size_down "
         "scheduler_cyclic_mode scheduler_cyclic_gamma scheduler_cycle_momentum max_learning_rate "
         "scheduler_step_size scheduler_step_gamma scheduler_milestones weight_decay "
-        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule ema_decay ema_warmup score_samples clip_length audio_rate accumulation_steps num_workers val_num_workers "
+        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule ema_decay ema_warmup score_samples clip_length audio_rate use_mel mel_bins mel_fft mel_hop mel_fmin mel_fmax accumulation_steps num_workers val_num_workers "
         "pin_memory n_epochs n_steps_per_epoch use_video use_global bf16_video generate_guidance global_dropout video_antialias batch_subsample_frac "
         "val_batch_subsample_frac dist_backend dist_port model_output_path log_samples_every"
     ).split()

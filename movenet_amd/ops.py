@@ -544,6 +544,157 @@ def upsample_video(model, video: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ---- local conditioning on log-mel frames (csrc/features.hip) -------------------------------------------
+def mel_filterbank(n_mels: int, n_fft: int, rate: float, f_min: float = 0.0, f_max: Optional[float] = None):
+    """The (n_mels, n_fft // 2 + 1) float64 numpy filterbank mvn_logmel_frontend takes: HTK mel scale
+    ``2595 log10(1 + f / 700)``, triangles between ``n_mels + 2`` equally spaced mel points from ``f_min`` to ``f_max``
+    (default ``rate / 2``), evaluated at the bin frequencies ``k rate / n_fft``, peak 1, no area normalisation."""
+    import numpy as np
+    f_max = rate / 2.0 if f_max is None else float(f_max)
+    if n_mels < 1 or n_fft < 2 or not 0.0 <= f_min < f_max <= rate / 2.0 + 1e-9:
+        raise ValueError(f"mel_filterbank: need n_mels >= 1 and 0 <= f_min < f_max <= rate / 2, got n_mels={n_mels}, "
+                         f"f_min={f_min}, f_max={f_max}, rate={rate}")
+
+    def mel(f):
+        return 2595.0 * np.log10(1.0 + np.asarray(f, dtype=np.float64) / 700.0)
+    points = 700.0 * (10.0 ** (np.linspace(mel(f_min), mel(f_max), n_mels + 2) / 2595.0) - 1.0)
+    freqs = np.arange(n_fft // 2 + 1, dtype=np.float64) * (float(rate) / n_fft)
+    lo, mid, hi = points[:-2, None], points[1:-1, None], points[2:, None]
+    return np.maximum(0.0, np.minimum((freqs[None, :] - lo) / (mid - lo), (hi - freqs[None, :]) / (hi - mid)))
+
+
+def logmel_frames(n_samples: int, hop: int) -> int:
+    """The frame count of ``logmel`` for a row of ``n_samples``: frames sit at 0, hop, 2 hop, ... <= n_samples."""
+    return int(n_samples) // int(hop) + 1
+
+
+_LOGMEL_TABLES: dict = {}
+
+
+def _logmel_tables(device, n_fft: int):
+    """(window, twiddle) of mvn_logmel_frontend on ``device``, made in float64 on the host once per (device, n_fft)."""
+    key = (str(device), int(n_fft))
+    if key not in _LOGMEL_TABLES:
+        import numpy as np
+        ang = 2.0 * np.pi * np.arange(n_fft, dtype=np.float64) / n_fft
+        window = 0.5 - 0.5 * np.cos(ang)
+        twiddle = np.concatenate([np.cos(ang), np.sin(ang)])
+        _LOGMEL_TABLES[key] = tuple(torch.from_numpy(t.astype(np.float32)).to(device) for t in (window, twiddle))
+    return _LOGMEL_TABLES[key]
+
+
+def logmel(indices: torch.Tensor, classes: int, n_fft: int, hop: int, fbank, floor: float = 1e-5,
+           energies: bool = False) -> torch.Tensor:
+    """(B, T) class indices on the GPU -> (B, n_mels, T // hop + 1) float32 log-mel frames of the waveform
+    ``mu_law_decode`` gives (mvn_logmel_frontend: centred frames of ``n_fft`` samples, zeros outside the clip, periodic
+    Hann window, power spectrum, ``fbank`` -- a (n_mels, n_fft // 2 + 1) array or tensor, e.g. ``mel_filterbank`` --
+    floor, natural log).  ``energies``: the mel energies before floor and log.  Nothing here is differentiable."""
+    _require_gpu(indices, "indices")
+    if indices.dim() != 2 or indices.is_floating_point():
+        raise ValueError(f"indices must be (batch, samples) integer classes, got {tuple(indices.shape)} {indices.dtype}")
+    dev = indices.device
+    idx = indices.detach().to(torch.int32).contiguous()
+    fb = torch.as_tensor(fbank).detach().to(device=dev, dtype=torch.float32).contiguous()
+    if fb.dim() != 2 or fb.shape[1] != int(n_fft) // 2 + 1:
+        raise ValueError(f"fbank must be (n_mels, {int(n_fft) // 2 + 1}), got {tuple(fb.shape)}")
+    B, T = idx.shape
+    M, F = int(fb.shape[0]), logmel_frames(T, hop) if int(hop) >= 1 else 0
+    lib = N.lib()
+    with torch.cuda.device(dev):
+        window, twiddle = _logmel_tables(dev, int(n_fft))
+        out = torch.empty((B, M, max(F, 0)), dtype=torch.float32, device=dev)
+        n = int(lib.mvn_logmel_scratch_floats(B, T, int(n_fft), int(hop)))
+        scratch = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+        N.check(lib.mvn_logmel_frontend(idx.data_ptr(), B, T, int(classes), int(n_fft), int(hop), M, window.data_ptr(),
+                                        twiddle.data_ptr(), fb.data_ptr(), float(floor), int(bool(energies)),
+                                        out.data_ptr(), max(F, 1), scratch.data_ptr(), n, _stream_ptr(dev)),
+                "mvn_logmel_frontend")
+    return out
+
+
+class _UpsampleFeaturesFunction(torch.autograd.Function):
+    """feats (B, M, F), W (C, M), bias (C) -> context (B, C, T) through mvn_upsample_features."""
+
+    @staticmethod
+    def forward(ctx_, hop, T, feats, w, bias):
+        lib = N.lib()
+        dev = feats.device
+        mel = feats.detach().to(torch.float32).contiguous()
+        wf = w.detach().to(torch.float32).contiguous()
+        bf = bias.detach().to(torch.float32).contiguous()
+        B, M, F = mel.shape
+        C = wf.shape[0]
+        with torch.cuda.device(dev):
+            ld = (T + 3) // 4 * 4  # rows start on 16 bytes
+            buf = torch.empty((B, C, ld), dtype=torch.float32, device=dev)
+            n = int(lib.mvn_upsample_features_scratch_floats(B, C, F))
+            scratch = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+            N.check(lib.mvn_upsample_features(mel.data_ptr(), mel.stride(1), wf.data_ptr(), bf.data_ptr(), B, M, F, C,
+                                              hop, T, buf.data_ptr(), ld, scratch.data_ptr(), n, _stream_ptr(dev)),
+                    "mvn_upsample_features")
+        ctx_.geom = (hop, T)
+        ctx_.save_for_backward(mel, wf)
+        return buf[:, :, :T]
+
+    @staticmethod
+    def backward(ctx_, dout):
+        lib = N.lib()
+        mel, wf = ctx_.saved_tensors
+        hop, T = ctx_.geom
+        B, M, F = mel.shape
+        C = wf.shape[0]
+        dev = mel.device
+        dout = dout.to(torch.float32).contiguous()
+        need_mel = ctx_.needs_input_grad[2]
+        with torch.cuda.device(dev):
+            dw = torch.zeros_like(wf)
+            db = torch.zeros(C, dtype=torch.float32, device=dev)
+            dmel = torch.empty_like(mel) if need_mel else None
+            n = int(lib.mvn_upsample_features_scratch_floats(B, C, F))
+            scratch = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+            N.check(lib.mvn_upsample_features_backward(
+                dout.data_ptr(), dout.stride(1), mel.data_ptr(), mel.stride(1), wf.data_ptr(), B, M, F, C, hop, T,
+                dw.data_ptr(), db.data_ptr(), dmel.data_ptr() if need_mel else None, F, scratch.data_ptr(), n,
+                _stream_ptr(dev)), "mvn_upsample_features_backward")
+        need = ctx_.needs_input_grad
+        return None, None, dmel, dw if need[3] else None, db if need[4] else None
+
+
+def local_frames_needed(T: int, hop: int) -> int:
+    return (int(T) - 1) // int(hop) + 1
+
+
+def check_local_features(model, local_features, batch: int, T: int) -> None:
+    """The ValueErrors of ``local_features`` for a (batch, T) pass, before anything is launched: given to a model
+    without ``local_channels``, missing on one with, a wrong shape, or too few frames for T."""
+    M, hop = int(getattr(model, "local_channels", 0)), int(getattr(model, "local_hop", 0))
+    if M <= 0:
+        if local_features is not None:
+            raise ValueError("local_features given to a model built without local_channels")
+        return
+    if local_features is None:
+        raise ValueError(f"this model was built with local_channels={M}: local_features is required")
+    if not torch.is_tensor(local_features) or local_features.dim() != 3 or not local_features.is_floating_point():
+        raise ValueError(f"local_features must be a ({batch}, {M}, frames) float tensor")
+    if local_features.shape[0] != batch or local_features.shape[1] != M:
+        raise ValueError(f"local_features must be ({batch}, {M}, frames), got {tuple(local_features.shape)}")
+    need = local_frames_needed(T, hop)
+    if local_features.shape[2] < need:
+        raise ValueError(f"local_features holds {local_features.shape[2]} frames; {T} samples at hop {hop} need {need}")
+
+
+def upsample_features(model, feats: torch.Tensor, T: int) -> torch.Tensor:
+    """``feats`` (B, local_channels, F) -> the (B, C, T) context of ``model.local_conv`` applied at frame rate and
+    interpolated linearly between frames ``model.local_hop`` samples apart (mvn_upsample_features); differentiable in
+    ``feats`` and in the conv's weight and bias."""
+    check_local_features(model, feats, int(feats.shape[0]) if torch.is_tensor(feats) and feats.dim() == 3 else -1, T)
+    _require_gpu(feats, "local_features")
+    if int(T) < 1:
+        raise ValueError(f"upsample_features: T must be at least 1, got {T}")
+    conv = model.local_conv
+    return _UpsampleFeaturesFunction.apply(int(model.local_hop), int(T), feats, conv.weight[:, :, 0], conv.bias)
+
+
 _BIAS_WITH_VIDEO = "global_path 'bias' runs models without a video context"
 
 

@@ -45,7 +45,23 @@ class Dance2Music(nn.Module):
         self.config = config
         # --use_global 1: the sorted context folders of the TRAINING set are the classes of the model's global embedding
         self.global_classes = self._class_map() if getattr(config, "use_global", False) else []
-        self.model = WaveNet(**asdict(config.model_config), global_classes=len(self.global_classes))
+        # --use_mel 1: local conditioning on the batch's own log-mel frames
+        self.use_mel = bool(getattr(config, "use_mel", False))  # (a config pickled before the field existed)
+        if self.use_mel and config.use_video:
+            raise ValueError("--use_mel 1 cannot be combined with --use_video 1: one local context at a time")
+        local = {}
+        if self.use_mel:
+            from .ops import mel_filterbank
+            rate = int(getattr(config, "audio_rate", 16000))
+            fmax = rate / 2.0 if config.mel_fmax is None else float(config.mel_fmax)
+            # (the filterbank's own ValueErrors come first: nothing is built on bad settings)
+            self.mel_fbank = torch.from_numpy(mel_filterbank(int(config.mel_bins), int(config.mel_fft), rate,
+                                                             float(config.mel_fmin), fmax)).to(torch.float32)
+            self.local_conditioning = {"local_channels": int(config.mel_bins), "local_hop": int(config.mel_hop),
+                                       "mel_fft": int(config.mel_fft), "mel_fmin": float(config.mel_fmin),
+                                       "mel_fmax": fmax, "audio_rate": rate}
+            local = {"local_channels": int(config.mel_bins), "local_hop": int(config.mel_hop)}
+        self.model = WaveNet(**asdict(config.model_config), global_classes=len(self.global_classes), **local)
         self.model.generate_sampling = config.generate_sampling  # (ValueError for an unknown rule)
         self.model.generate_top_k = config.generate_top_k        # (... a negative k, a p outside (0, 1])
         self.model.generate_top_p = config.generate_top_p
@@ -77,6 +93,19 @@ class Dance2Music(nn.Module):
     def forward(self, audio, video, **kwargs):
         return self.model(audio, video, **kwargs)
 
+    def mel_features(self, audio):
+        """The (B, mel_bins, T // mel_hop + 1) log-mel frames of a one-hot batch on the device (``ops.logmel`` of its
+        class indices, no gradient), or None without ``--use_mel``."""
+        if not self.use_mel:
+            return None
+        from .ops import logmel
+        c = self.config
+        with torch.no_grad():
+            if self.mel_fbank.device != audio.device:
+                self.mel_fbank = self.mel_fbank.to(audio.device)
+            return logmel(audio.argmax(1).to(torch.int32), c.model_config.input_channels, int(c.mel_fft), int(c.mel_hop),
+                          self.mel_fbank)
+
     def _class_map(self):
         names = training_contexts(self.dataset_fp)
         if not names:
@@ -106,24 +135,26 @@ class Dance2Music(nn.Module):
         return (self.config.log_samples_every is not None
                 and (self.current_epoch + 1) % self.config.log_samples_every == 0)
 
-    def _sample_outputs(self, audio, video, labels, lengths=None) -> dict:
+    def _sample_outputs(self, audio, video, labels, lengths=None, feats=None) -> dict:
         """A step's ``generated_output`` for the sample logger -- ``generate`` on the averaged weights when there are
         any -- and, with ``--score_samples 1`` on a step that generates, the clips' scores under ``"sample_scores"`` (a
         key that is absent otherwise).  (The views are swapped only on a step that generates; the step's autograd graph
         holds the parameters themselves, which point into the raw buffer again before ``backward`` runs.)"""
         with (self.averaged_weights() if self._generates_now() else contextlib.nullcontext()):
-            gen = self.generate(audio, video, labels)  # (which keeps the epoch gate: None on the other epochs)
+            # (which keeps the epoch gate: None on the other epochs; the features only where the model takes them)
+            gen = self.generate(audio, video, labels, **({} if feats is None else {"local_features": feats}))
             out = {"generated_output": gen}
             if gen is not None and getattr(self.config, "score_samples", False):
                 # (the call without lengths is the call it was: the argument goes only where the batch has lengths)
                 out["sample_scores"] = self.score_samples(gen, audio, video, labels,
-                                                          **({} if lengths is None else {"lengths": lengths}))
+                                                          **({} if lengths is None else {"lengths": lengths}),
+                                                          **({} if feats is None else {"local_features": feats}))
             if gen is not None and lengths is not None:
                 # the logger prompts from a clip's first RF samples: clips shorter than that are left out of its rows
                 out["prompt_ok"] = [int(n) >= self.model.receptive_fields for n in lengths]
         return out
 
-    def score_samples(self, generated, audio, video, labels=None, lengths=None) -> dict:
+    def score_samples(self, generated, audio, video, labels=None, lengths=None, local_features=None) -> dict:
         """bits per sample of the generated clips and of the clips they were prompted from, each under the clip's own
         conditioning (video, label; temperature 1, no guidance: the model's own distribution), from ONE
         ``WaveNet.score`` call: the generated rows (len(sweep) per clip, clip-major, under a temperature sweep), then
@@ -137,27 +168,30 @@ class Dance2Music(nn.Module):
 
         def both(per_clip):
             return None if per_clip is None else torch.cat([per_clip.repeat_interleave(n, dim=0), per_clip])
+        # (--use_mel: a generated clip is scored under the features it was generated under -- its source clip's)
+        mel = {} if local_features is None else {"local_features": both(local_features)}
         res = self.model.score(torch.cat([generated[:, :, :frames], audio[:, :, :frames].to(generated.dtype)]),
-                               both(video), both(labels),
+                               both(video), both(labels), **mel,
                                lengths=None if lengths is None else
                                [frames] * int(generated.shape[0]) + [min(int(v), frames) for v in lengths])
         bits = res.bits_per_sample.detach()
         return {"bits_per_sample": bits[:generated.shape[0]], "source_bits_per_sample": bits[generated.shape[0]:]}
 
-    def generate(self, audio, video, labels=None):
-        if self._generates_now():
-            sweep = list(getattr(self.config, "generate_temperature_sweep", None) or ())
-            if sweep:
-                # every clip once per temperature, clip-major, in ONE generate() call (LogSamplesCallback's layout)
-                n = len(sweep)
-                return self.model.generate(
-                    audio.repeat_interleave(n, dim=0), None if video is None else video.repeat_interleave(n, dim=0),
-                    None if labels is None else labels.repeat_interleave(n, dim=0),
-                    n_samples=self.config.generate_n_samples, temperature=sweep * audio.shape[0]).detach()
-            return self.model.generate(
-                audio, video, labels, n_samples=self.config.generate_n_samples,
-                temperature=self.config.generate_temperature).detach()
-        return None
+    def generate(self, audio, video, labels=None, local_features=None):
+        if not self._generates_now():
+            return None
+        sweep = list(getattr(self.config, "generate_temperature_sweep", None) or ())
+        n = len(sweep)
+
+        def rows(t):  # every clip once per temperature, clip-major, in ONE generate() call (LogSamplesCallback's layout)
+            return t if t is None or not sweep else t.repeat_interleave(n, dim=0)
+        # (--use_mel: generate() keeps the reference's signature, so the frames go in through the model's setting, which
+        # the call uses up)
+        if local_features is not None:
+            self.model.generate_local_features = rows(local_features)
+        return self.model.generate(
+            rows(audio), rows(video), rows(labels), n_samples=self.config.generate_n_samples,
+            temperature=sweep * audio.shape[0] if sweep else self.config.generate_temperature).detach()
 
     def _shared_step(self, batch, prefix: str):
         audio, video, contexts, fps, info = batch
@@ -183,24 +217,27 @@ class Dance2Music(nn.Module):
             # host arithmetic on the loader's host list: no synchronisation
             self.log(f"{prefix}_valid_frac", sum(valid_columns(lengths, T, rf)) / max(len(lengths) * (T - rf), 1),
                      batch_size=self.config.batch_size)
+        feats = self.mel_features(audio)  # (None without --use_mel)
+        if feats is not None:
+            extra["local_features"] = feats
         loss, acc, output = self(audio, video if self.config.use_video else None, return_loss=True, **extra)
         self.log(f"{prefix}_loss", loss, batch_size=self.config.batch_size)
         self.log(f"{prefix}_acc", acc, batch_size=self.config.batch_size)
         if self.model.loss_rule == "model":  # the loss is a likelihood in nats: also in bits (a device scalar, no sync)
             self.log(f"{prefix}_bits_per_sample", loss.detach() / math.log(2.0), batch_size=self.config.batch_size)
-        return loss, output, audio, video, labels, lengths
+        return loss, output, audio, video, labels, lengths, feats
 
     def training_step(self, batch, batch_idx):
         if self.model.global_dropout > 0:
             # (generate() leaves the model in eval mode, as the reference's does: with samples logged on train steps the
             # rest of the epoch would run without label dropout, which forward applies in train mode only)
             self.model.train()
-        loss, output, audio, video, labels, lengths = self._shared_step(batch, "train")
-        return {"loss": loss, "output": output.detach(), **self._sample_outputs(audio, video, labels, lengths)}
+        loss, output, audio, video, labels, lengths, feats = self._shared_step(batch, "train")
+        return {"loss": loss, "output": output.detach(), **self._sample_outputs(audio, video, labels, lengths, feats)}
 
     def validation_step(self, batch, batch_idx):
-        _, output, audio, video, labels, lengths = self._shared_step(batch, "val")
-        return {"output": output.detach(), **self._sample_outputs(audio, video, labels, lengths)}
+        _, output, audio, video, labels, lengths, feats = self._shared_step(batch, "val")
+        return {"output": output.detach(), **self._sample_outputs(audio, video, labels, lengths, feats)}
 
     def _loader(self, train: bool):
         c = self.config
@@ -243,7 +280,7 @@ class Dance2Music(nn.Module):
         if flat:
             # same update rule as torch.optim.Adam / AdamW, one HIP kernel over one flat buffer
             # (labels train the layers' context convs too: their gradients sit where a video-conditioned run's do)
-            optimizer = FlatAdamW(order_like_backward(self.model, bool(c.use_video) or bool(self.global_classes)), decoupled=c.optimizer == "AdamW",
+            optimizer = FlatAdamW(order_like_backward(self.model, bool(c.use_video) or bool(self.global_classes) or self.use_mel), decoupled=c.optimizer == "AdamW",
                                   ema_decay=ema_decay, ema_warmup=bool(getattr(c, "ema_warmup", True)),
                                   **opt_kw[c.optimizer])
             self.ema_optimizer = optimizer if ema_decay > 0 else None
@@ -498,6 +535,9 @@ class Trainer:
                            if averaging else {})  # (absent without --ema_decay)
                     torch.save({"epoch": epoch, "global_step": self.global_step,
                                 **({"global_classes": names} if names else {}), **ema,
+                                # (--use_mel: what checkpoint.load_into rebuilds local_conv from; absent otherwise)
+                                **({"local_conditioning": dict(model.local_conditioning)}
+                                   if getattr(model, "use_mel", False) else {}),
                                 "state_dict": {f"model.{k}": v.detach().cpu()
                                                for k, v in model.model.state_dict().items()}},
                                ck / f"epoch={epoch}-step={self.global_step}.ckpt")

@@ -68,13 +68,27 @@ class ScoreResult(_ScoreFields):
 class WaveNet(nn.Module):
     def __init__(self, layer_size: int, stack_size: int, input_channels: int,
                  residual_channels: int = 16, skip_channels: int = 16,
-                 context_in_channels: int = 1, global_classes: int = 0):
+                 context_in_channels: int = 1, global_classes: int = 0, local_channels: int = 0,
+                 local_hop: int = 0):
         """``global_classes`` (an extension behind the reference's arguments; 0, the default, is the reference's
         module to the bit): G > 0 registers ``global_embedding.weight`` (G, residual_channels) behind every other
-        parameter and makes ``global_features`` a required input of ``forward`` / ``generate``."""
+        parameter and makes ``global_features`` a required input of ``forward`` / ``generate``.
+
+        ``local_channels`` / ``local_hop`` (likewise an extension; 0: off, the module unchanged): M > 0 registers
+        ``local_conv = nn.Conv1d(M, residual_channels, 1)`` behind every other parameter, ``global_embedding``
+        included, and makes ``local_features`` -- (B, M, F) feature frames ``local_hop`` samples apart, e.g.
+        ``ops.logmel`` -- a required input of ``forward`` / ``score`` / ``classify``, and ``generate_local_features`` one
+        of ``generate``."""
         super().__init__()
         if isinstance(global_classes, bool) or not isinstance(global_classes, int) or global_classes < 0:
             raise ValueError(f"global_classes must be an integer >= 0, got {global_classes!r}")
+        for name, v in (("local_channels", local_channels), ("local_hop", local_hop)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"{name} must be an integer >= 0, got {v!r}")
+        if (local_channels > 0) != (local_hop > 0):
+            raise ValueError("local_channels and local_hop go together: both above 0, or both 0 (off), got "
+                             f"{local_channels} and {local_hop}")
+        self.local_channels, self.local_hop = local_channels, local_hop
         self.global_classes = global_classes
         self.layer_size = layer_size
         self.stack_size = stack_size
@@ -97,6 +111,8 @@ class WaveNet(nn.Module):
         self.dense_conv = DenseConv(K, Q)
         if global_classes > 0:  # (registered last: the draws of every other parameter under a seed do not move)
             self.global_embedding = nn.Embedding(global_classes, C)
+        if local_channels > 0:  # (behind everything else, for the same reason)
+            self.local_conv = nn.Conv1d(local_channels, C, 1)
         # "auto" (default): global conditioning takes the fast path where it exists (C = K = 64, fp32, no video: one
         # bias vector per layer and sequence); "context": always the general path, the label as a constant context
         self._global_path = "auto"
@@ -115,6 +131,19 @@ class WaveNet(nn.Module):
         self._gen_sampling = "reference"
         self._gen_top_k, self._gen_top_p = 0, 1.0
         self._loss_rule = "reference"
+
+    def set_local_conditioning(self, local_channels: int, local_hop: int) -> None:
+        """Give the model the ``local_conv`` of ``WaveNet(local_channels=..., local_hop=...)`` (what
+        ``checkpoint.load_into`` does for a checkpoint that records one): a new ``nn.Conv1d`` behind every other
+        parameter, on their device, unless the model already has one of that width; ``local_hop`` is set either way."""
+        if local_channels < 1 or local_hop < 1:
+            raise ValueError(f"local_channels and local_hop must be above 0, got {local_channels} and {local_hop}")
+        if int(getattr(self, "local_channels", 0)) != local_channels:
+            if hasattr(self, "local_conv"):
+                del self.local_conv
+            ref = self.causal_conv.conv.weight
+            self.local_conv = nn.Conv1d(local_channels, self.residual_channels, 1).to(device=ref.device, dtype=ref.dtype)
+        self.local_channels, self.local_hop = int(local_channels), int(local_hop)
 
     # ---- precision of generate() ----------------------------------------
     @property
@@ -199,6 +228,27 @@ class WaveNet(nn.Module):
         if int(getattr(self, "global_classes", 0)) <= 0 and any(s != 1.0 for s in scales):
             raise ValueError("generate_guidance needs a model built with global_classes (there is no label to guide by)")
         self._gen_guidance = list(scales) if N.any_per_sequence(value) else scales[0]
+
+    # ---- the feature frames generate() runs under -------------------
+    @property
+    def generate_local_features(self):
+        """None (default) or the (B, local_channels, F) feature frames ``generate()`` conditions on -- what ``forward``
+        takes as ``local_features``, with frames for every sample asked for.  Required (ValueError at ``generate()``) on
+        a model built with ``local_channels``; setting it on a model without is a ValueError.  ONE call uses it: the
+        next ``generate()`` takes the frames and leaves the setting at None again (also when it raises), so frames
+        of one prompt are never reused silently for another, no device tensor stays alive behind the module and none
+        is pickled with it between calls.  Set it before every ``generate()``."""
+        return getattr(self, "_gen_local_features", None)
+
+    @generate_local_features.setter
+    def generate_local_features(self, value) -> None:
+        if value is not None:
+            if int(getattr(self, "local_channels", 0)) <= 0:
+                raise ValueError("generate_local_features set on a model built without local_channels")
+            if not torch.is_tensor(value) or value.dim() != 3 or value.shape[1] != self.local_channels \
+                    or not value.is_floating_point():
+                raise ValueError(f"generate_local_features must be a (batch, {self.local_channels}, frames) float tensor")
+        self._gen_local_features = value
 
     # ---- label dropout of train-mode forward() ---------------------------------
     @property
@@ -327,7 +377,7 @@ class WaveNet(nn.Module):
 
     def _decoder_state(self):
         return {k: v for k, v in self.state_dict().items()
-                if not k.startswith("video_") and not k.startswith("global_embedding.")}
+                if not k.startswith(("video_", "global_embedding.", "local_conv."))}
 
     # ---- model API ------------------------------------------------------
     def upsample_video(self, video):
@@ -338,7 +388,8 @@ class WaveNet(nn.Module):
         return out
 
     def forward(self, audio, video=None, global_features=None, output_unnormalized: bool = True,
-                remove_last: bool = True, return_loss: bool = False, target=None, lengths=None):
+                remove_last: bool = True, return_loss: bool = False, target=None, lengths=None, *,
+                local_features=None):
         """BUILD DEFINITION for video != None: the reference raises a shape error at
         modules.py:75-77; here the upsampled video is added to the filter
         and gate pre-activations at the same absolute time (right-aligned, like the
@@ -363,16 +414,24 @@ class WaveNet(nn.Module):
         holds ``lengths[b]`` real samples and padding behind them; loss and accuracy then run over the columns that
         predict a real sample (``ops.valid_columns``), divided by their number, and the padding's columns receive a
         gradient of exactly 0.  Refused together with ``video``: video batches are fixed at
-        MAX_AUDIO_FRAMES frames."""
+        MAX_AUDIO_FRAMES frames.
+
+        ``local_features`` (a model built with ``local_channels = M > 0``, which requires it; ValueError on a model
+        without): (B, M, F) feature frames ``local_hop`` samples apart, F >= (T - 1) // local_hop + 1.  ``local_conv``
+        and a linear interpolation between frames make them the (B, C, T) context (``ops.upsample_features``) -- an
+        ordinary context: a label joins it as it joins a video's, bf16 needs ``bf16_context``, ``global_path = "bias"``
+        refuses it.  Not together with ``video`` (ValueError); ``lengths`` is accepted with it."""
         from .ops import global_vector, plan_sequence, wavenet_forward, wavenet_forward_loss  # HIP full-sequence kernels
         self._lengths_checks(lengths, video, return_loss)
+        self._local_checks(audio, video, local_features)
         gvec = global_vector(self, global_features, int(audio.shape[0]))  # (ValueError before anything is launched)
         if gvec is not None and self.training:  # label dropout: both paths below see an ordinary e
             keep = self.global_dropout_mask(int(audio.shape[0]))
             if keep is not None:
                 gvec = gvec * keep.to(device=gvec.device, dtype=gvec.dtype)[:, None]
-        plan_sequence(self, video is not None, gvec is not None)  # (refused before the video encoder runs)
-        context = None if video is None else self.upsample_video(video)
+        # (refused before the video encoder / the feature up-sampler runs)
+        plan_sequence(self, video is not None or local_features is not None, gvec is not None)
+        context = self._context_of(audio, video, local_features)
         if return_loss:
             return wavenet_forward_loss(self, audio, context, target, gvec=gvec, lengths=lengths)
         return wavenet_forward(self, audio, context, output_unnormalized=output_unnormalized,
@@ -388,12 +447,29 @@ class WaveNet(nn.Module):
             raise ValueError(f"lengths cannot be combined with video: video batches are fixed at {MAX_AUDIO_FRAMES} "
                              "frames")
 
+    def _local_checks(self, audio, video, local_features, n_total=None):
+        """The ValueErrors of ``local_features`` (ops.check_local_features, for the audio's length or ``n_total``),
+        before anything is launched; never together with ``video``."""
+        from .ops import check_local_features
+        if local_features is not None and video is not None:
+            raise ValueError("local_features cannot be combined with video: one local context at a time")
+        check_local_features(self, local_features, int(audio.shape[0]),
+                             int(audio.shape[2]) if n_total is None else int(n_total))
+
+    def _context_of(self, audio, video, local_features, n_total=None):
+        """The (B, C, T) local context of a pass: the up-sampled video, the up-sampled feature frames, or None."""
+        if local_features is not None:
+            from .ops import upsample_features
+            return upsample_features(self, local_features, int(audio.shape[2]) if n_total is None else int(n_total))
+        return None if video is None else self.upsample_video(video)
+
     # ---- likelihood of GIVEN audio (DESIGN 4.5b) ---------------------------
-    def _score_checks(self, audio, video, global_features):
+    def _score_checks(self, audio, video, global_features, local_features=None):
         """The forward's own refusals, before anything is launched; returns (gvec, the pass's planned mode)."""
         from .ops import global_vector, plan_sequence
+        self._local_checks(audio, video, local_features)
         gvec = global_vector(self, global_features, int(audio.shape[0]))
-        mode = plan_sequence(self, video is not None, gvec is not None)
+        mode = plan_sequence(self, video is not None or local_features is not None, gvec is not None)
         self.compute_output_size(audio)
         return gvec, mode
 
@@ -421,7 +497,7 @@ class WaveNet(nn.Module):
 
     @torch.no_grad()
     def score(self, audio, video=None, global_features=None, temperature: float = 1.0, entropy: bool = False,
-              rank: bool = False, lengths=None) -> "ScoreResult":
+              rank: bool = False, lengths=None, *, local_features=None) -> "ScoreResult":
         """How likely ``audio`` is under the model: log p(x_t | x_<t, conditioning) of every sample past the
         receptive field, per position and per sequence, from the logits of one forward pass (same checks, same
         kernels, ``forward_precision`` and ``global_path`` as ``forward``; nothing saved, no probability tensor).
@@ -436,18 +512,19 @@ class WaveNet(nn.Module):
         ``lengths`` (as in ``forward``; default None): sequence b is scored over the positions that predict one of
         its ``lengths[b]`` real samples -- ``positions`` (B,) int32 holds their number, ``bits_per_sample`` and
         ``accuracy`` divide by ``max(positions, 1)``, and the other positions come back as logp = entropy = 0 and
-        rank = -1.  Refused together with ``video``."""
+        rank = -1.  Refused together with ``video``.  ``local_features``: as in ``forward``."""
         from .ops import score_temperature, wavenet_score
         temperature = score_temperature(temperature)  # (ValueError before the video encoder runs)
         self._lengths_checks(lengths, video)
-        gvec, _ = self._score_checks(audio, video, global_features)
+        gvec, _ = self._score_checks(audio, video, global_features, local_features)
         valid = self._valid_on_device(lengths, audio)
-        context = None if video is None else self.upsample_video(video)
+        context = self._context_of(audio, video, local_features)
         raw = wavenet_score(self, audio, context, gvec, temperature, entropy=entropy, rank=rank, valid=valid)
         return self._score_result(raw, int(audio.shape[2]) - self.receptive_fields, valid)
 
     @torch.no_grad()
-    def classify(self, audio, video=None, log_prior=None, logits_budget_bytes: int = 1 << 30, lengths=None):
+    def classify(self, audio, video=None, log_prior=None, logits_budget_bytes: int = 1 << 30, lengths=None, *,
+                 local_features=None):
         """Which class label explains ``audio`` best (a model built with ``global_classes = G > 0``; ValueError
         otherwise): returns ``(loglik, posterior)``, both (B, G) -- ``loglik[b, c]`` = log p(x_b | class c), the
         ``-nll`` of ``score`` with ``global_features = c``, and ``posterior`` = softmax(loglik + ``log_prior``)
@@ -469,9 +546,9 @@ class WaveNet(nn.Module):
             if tuple(log_prior.shape) not in ((G,), (B, G)):
                 raise ValueError(f"log_prior must be ({G},) or ({B}, {G}), got {tuple(log_prior.shape)}")
         self._lengths_checks(lengths, video)
-        _, mode = self._score_checks(audio, video, torch.zeros(B, dtype=torch.int64))
+        _, mode = self._score_checks(audio, video, torch.zeros(B, dtype=torch.int64), local_features)
         valid = self._valid_on_device(lengths, audio)
-        context = None if video is None else self.upsample_video(video)
+        context = self._context_of(audio, video, local_features)
         idx = self._indices_of(audio)  # ValueError unless one-hot
         positions = int(audio.shape[2]) - self.receptive_fields
         per_pair = 4 * self.input_channels * max(positions, 1)
@@ -499,8 +576,14 @@ class WaveNet(nn.Module):
         on one prompt is ONE launch: repeat the prompt), and ``generate_seed`` likewise; with either a sequence,
         sequence b draws on its own seed and row b whatever the launch plan.  A wrong length or a bad value is a
         ValueError before anything runs.  ``global_features``: as in ``forward`` -- the label's vector conditions
-        every step (required for a model built with ``global_classes``)."""
+        every step (required for a model built with ``global_classes``).  A model built with ``local_channels`` reads
+        its feature frames from ``generate_local_features`` (the signature stays the reference's, as for the other
+        generation settings; this one is used up by the call): frames for all ``n_samples`` -- the up-sampled (B, C, n_samples) tensor is the
+        generators' ``context``."""
         from .ops import global_vector
+        local_features, self._gen_local_features = self.generate_local_features, None  # (taken: one call uses it)
+        self._local_checks(audio, video, local_features,
+                           n_total=max(int(audio.shape[2]) if n_samples is None else int(n_samples), 1))
         gvec = global_vector(self, global_features, int(audio.shape[0]))
         top_k, top_p, seed = self.generate_top_k, self.generate_top_p, self.generate_seed
         guidance = self.generate_guidance
@@ -519,9 +602,9 @@ class WaveNet(nn.Module):
         self.eval()  # the reference leaves the module in eval mode
         # BUILD DEFINITION for video != None (the reference fails its size assert there,
         # SURVEY.md Q7): the context column of time t conditions the step that consumes x_t
-        context = None if video is None else self.upsample_video(video)
         rf = self.receptive_fields
         n_total = int(audio.shape[2]) if n_samples is None else int(n_samples)
+        context = self._context_of(audio, video, local_features, n_total=max(n_total, 1))
         idx = self._indices_of(audio)
         if idx.shape[1] < rf or n_total <= rf:
             # nothing to generate: the reference returns zeros with the prompt copied in
