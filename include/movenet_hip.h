@@ -834,6 +834,49 @@ int mvn_audio_frontend_var(const int16_t *pcm, long long pcm_len, const mvn_audi
                            int classes, int width, int normalize, float *y, float *scratch, int32_t *index,
                            void *stream);
 
+/* The front end by rate on a WINDOW of a file: row b is the columns [out_first, out_first + n_out) of the resample of
+ * its whole file from rate_in to rate_out, formed from the span of source frames those columns' taps reach -- the only
+ * part of the file that is uploaded.  With g = gcd(rate_in, rate_out), orig = rate_in / g, new = rate_out / g, and s, W
+ * as for the calls above from (orig, new): the file's resample has n_file = ceil(file_frames new / orig) outputs, and
+ * for the global output index j (64-bit) p = j orig, i0 = p / new, frac = (p mod new) / new,
+ *   y = sum_{d = -W}^{W + 1} m[i0 + d] h(d - frac),   m = 0 outside [0, file_frames),
+ * taps and channel mean those of the calls above.  The 2 W + 2 products are summed in blocks of 128 -- each block from
+ * 0 by fmaf in ascending d, the block sums added in ascending order -- so that a long filter (1216 taps at 100 : 1)
+ * keeps the accuracy of a short one.  Nothing in a sample depends on where its row starts: a window is a crop of the
+ * whole file's resample by this call, to the bit; and up to 128 taps (rate_in <= 10 rate_out) the sum is one block,
+ * the bits of mvn_audio_frontend_var where its frames : n_out reduces to the same orig : new.  Columns [n_out, width) get y = 0 and the
+ * silence class, as there.  When `normalize`: by (lo, hi) where hi > lo (and hi - lo finite) -- the host's per-file
+ * gain -- else by the window's own (min, max), max == min left alone.
+ *   clips     DEVICE, one 64-byte descriptor per row
+ *   y, index  DEVICE (batch, width);  scratch  mvn_audio_frontend_window_scratch_floats(batch, width) floats, 8-byte
+ *   aligned.  Host refusals as above.
+ * Checked on the device; a refused row has index = -1 and y = 0 and nothing of the upload is read for it:
+ *   - the span [offset, offset + span_frames channels) does not lie inside [0, pcm_len), or span_frames < 1;
+ *   - n_out outside [1, width];
+ *   - rate_in, rate_out or channels < 1;
+ *   - a ratio whose window of 64 outputs does not fit the LDS tile (rate_in <= 100 rate_out always fits);
+ *   - out_first < 0 or out_first + n_out > n_file (file_frames < 1, or file_frames new >= 2^62, has no n_file);
+ *   - the span does not cover [i0(out_first) - W, i0(out_first + n_out - 1) + W + 1] intersected with
+ *     [0, file_frames): span_first above its first frame, or span_first + span_frames - 1 below its last.
+ * Two launches, no atomics: bit-reproducible, and a row does not depend on its place in the batch. */
+typedef struct {
+  int64_t offset;      /* element offset of the uploaded span in pcm */
+  int64_t span_first;  /* source frame index of the span's first frame */
+  int64_t out_first;   /* global output index of the row's first column */
+  int64_t file_frames; /* frames in the whole file */
+  int32_t span_frames; /* frames in the uploaded span */
+  int32_t channels;
+  int32_t n_out;
+  int32_t rate_in;
+  int32_t rate_out;
+  float lo, hi;        /* given normalisation range; hi <= lo: the window's own */
+  int32_t reserved;
+} mvn_audio_clip_window;
+size_t mvn_audio_frontend_window_scratch_floats(int batch, int width);
+int mvn_audio_frontend_window(const int16_t *pcm, long long pcm_len, const mvn_audio_clip_window *clips, int batch,
+                              int classes, int width, int normalize, float *y, float *scratch, int32_t *index,
+                              void *stream);
+
 /* The loader's video front end (movenet/dataset.py:292-310 behind the decoder): a batch of clips of different
  * resolutions, as interleaved uint8 frames in one upload, -> (batch, n_frames, 64, 64) uint8 gray levels.  Per frame:
  * L = uint8(0.2989 r + 0.587 g + 0.114 b), fp32 products and sums each rounded, the cast truncating (skipped for

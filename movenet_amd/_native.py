@@ -266,6 +266,9 @@ SIGNATURES = {
     "mvn_audio_frontend_var_scratch_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "mvn_audio_frontend_var": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mvn_audio_frontend_window_scratch_floats": (C.c_size_t, [C.c_int, C.c_int]),
+    "mvn_audio_frontend_window": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mvn_video_frontend": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "mvn_publish_words": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -102,8 +102,12 @@ class TrainingConfig:
     # clips of a WAV folder at their own length (WavFolderLoader): "resample" stretches every clip onto
     # the batch width (the reference's rule); "native" resamples every clip to audio_rate, pads the batch to that width
     # and leaves the padding out of the loss.  Not reference fields: a JSON written without them loads with the defaults.
+    # "window" trains on random windows of long recordings: rows are `frames` consecutive samples of a
+    # file's resample to audio_rate, normalised by the whole file's range (window_gain "file") or the window's own
+    # ("window").
     clip_length: str = "resample"
     audio_rate: int = 16000
+    window_gain: str = "file"
 
     # local conditioning on the clip's own log-mel frames (WaveNet(local_channels=mel_bins, local_hop=mel_hop), DESIGN
     # 4.5d): every batch's features are computed on the GPU from its class indices (ops.logmel: frames of mel_fft samples
@@ -203,7 +207,8 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--ema_decay", type=float, default=0.0)
     a("--ema_warmup", type=_flag, default=True)
     a("--score_samples", type=_flag, default=False)
-    a("--clip_length", type=str, default="resample", choices=["resample", "native"])
+    a("--clip_length", type=str, default="resample", choices=["resample", "native", "window"])
+    a("--window_gain", type=str, default="file", choices=["file", "window"])
     a("--audio_rate", type=int, default=16000)
     a("--use_mel", type=_flag, default=False)
     a("--mel_bins", type=int, default=80)
@@ -258,7 +263,7 @@ def config_from_args(args) -> TrainingConfig:
         "lr_pct_start base_learning_rate scheduler_step_size_up scheduler_step_size_down "
         "scheduler_cyclic_mode scheduler_cyclic_gamma scheduler_cycle_momentum max_learning_rate "
         "scheduler_step_size scheduler_step_gamma scheduler_milestones weight_decay "
-        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule ema_decay ema_warmup score_samples clip_length audio_rate use_mel mel_bins mel_fft mel_hop mel_fmin mel_fmax accumulation_steps num_workers val_num_workers "
+        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule ema_decay ema_warmup score_samples clip_length audio_rate window_gain use_mel mel_bins mel_fft mel_hop mel_fmin mel_fmax accumulation_steps num_workers val_num_workers "
         "pin_memory n_epochs n_steps_per_epoch use_video use_global bf16_video generate_guidance global_dropout video_antialias batch_subsample_frac "
         "val_batch_subsample_frac dist_backend dist_port model_output_path log_samples_every"
     ).split()

@@ -231,7 +231,27 @@ def read_wav_pcm16(path: str) -> tuple:
     h = read_wav_header(path)
     with wave.open(str(path), "rb") as w:
         raw = w.readframes(h["frames"])
-    width, ch = h["width"], h["channels"]
+    pcm, n = _pcm16_of(raw, h["width"], h["channels"])
+    return pcm, n, h["channels"], h["rate"]
+
+
+def read_wav_span(path: str, first: int, frames: int, header: Optional[dict] = None) -> tuple:
+    """``read_wav_pcm16`` of the frames [first, first + frames) alone (``wave.setpos`` / ``readframes``: nothing else of
+    the file is read): (interleaved int16 samples, frames read, channels, rate), the same 8/16/24/32-bit handling.
+    The span is clipped to the file."""
+    import wave
+    h = read_wav_header(path) if header is None else header
+    first = min(max(int(first), 0), h["frames"])
+    frames = min(max(int(frames), 0), h["frames"] - first)
+    with wave.open(str(path), "rb") as w:
+        w.setpos(first)
+        raw = w.readframes(frames)
+    pcm, n = _pcm16_of(raw, h["width"], h["channels"])
+    return pcm, n, h["channels"], h["rate"]
+
+
+def _pcm16_of(raw: bytes, width: int, ch: int) -> tuple:
+    """(interleaved int16 samples, whole frames) of a WAV's data bytes at ``width`` bytes per sample."""
     n = len(raw) // (width * ch)
     raw = raw[: n * width * ch]
     if width == 2:
@@ -244,7 +264,43 @@ def read_wav_pcm16(path: str) -> tuple:
         v = np.where(v >= 1 << (8 * width - 1), v - (1 << (8 * width)), v)  # two's complement
         shift = 8 * width - 16
         pcm = np.clip((v + (1 << (shift - 1))) >> shift, -32768, 32767)
-    return np.ascontiguousarray(pcm, dtype=np.int16), n, ch, h["rate"]
+    return np.ascontiguousarray(pcm, dtype=np.int16), n
+
+
+FILE_RANGE_CHUNK = 1 << 20  # frames per read of wav_file_range
+
+
+def wav_file_range(path: str, header: Optional[dict] = None) -> tuple:
+    """(lo, hi) of a file's channel-mean PCM / 32768, as float32 numbers formed the way the front end forms them (the
+    integer channel sum over fp32(32768 channels)); the file is read FILE_RANGE_CHUNK frames at a time."""
+    h = read_wav_header(path) if header is None else header
+    lo = hi = None
+    for first in range(0, h["frames"], FILE_RANGE_CHUNK):
+        pcm, n, ch, _ = read_wav_span(path, first, FILE_RANGE_CHUNK, header=h)
+        if n < 1:
+            break
+        sums = pcm.reshape(n, ch).sum(axis=1, dtype=np.int64)
+        lo = int(sums.min()) if lo is None else min(lo, int(sums.min()))
+        hi = int(sums.max()) if hi is None else max(hi, int(sums.max()))
+    if lo is None:
+        return 0.0, 0.0
+    den = np.float32(32768.0) * np.float32(h["channels"])
+    return float(np.float32(lo) / den), float(np.float32(hi) / den)
+
+
+def window_geometry(rate: int, audio_rate: int) -> tuple:
+    """(orig, new, W) of the resample from ``rate`` to ``audio_rate``: the reduced ratio and how far the taps of one
+    output reach, i0 - W .. i0 + W + 1 -- the front end's own numbers (csrc/audio.hip: af_geom_taps)."""
+    g = math.gcd(int(rate), int(audio_rate))
+    orig, new = int(rate) // g, int(audio_rate) // g
+    s = 0.99 * min(orig, new) / orig
+    return orig, new, int(6.0 / s) + 1
+
+
+def resampled_frames(file_frames: int, rate: int, audio_rate: int) -> int:
+    """n_file = ceil(file_frames new / orig): the outputs a whole file resamples to."""
+    orig, new, _ = window_geometry(rate, audio_rate)
+    return -(-int(file_frames) * new // orig)
 
 
 class _IndexCache:
@@ -255,6 +311,7 @@ class _IndexCache:
         self.max_bytes, self.bytes = int(max_bytes), 0
         self.rows: dict = {}
         self.lengths: dict = {}  # clip -> real samples of its row (by-rate rows end in silence), beside the indices
+        self.ranges: dict = {}  # file -> (lo, hi) of its channel mean (clip_length="window", window_gain="file")
         self.hits = self.misses = 0
 
     def put(self, key, row: torch.Tensor, length: Optional[int] = None) -> None:
@@ -357,7 +414,20 @@ class WavFolderLoader:
     ``frames`` -- into rows of the unchanged width ``frames`` with silence behind it (ops.audio_frontend_var), and
     ``Batch.lengths`` says how many samples of each row are real; the index cache keeps the lengths beside the
     indices.  With ``batch_subsample_frac`` the window is drawn as above and a clip's length inside it is
-    ``clamp(len_b - start, 0, n)``.  Refused with ``use_video`` (video batches are fixed at ``frames``)."""
+    ``clamp(len_b - start, 0, n)``.  Refused with ``use_video`` (video batches are fixed at ``frames``).
+
+    Random windows of long files (``clip_length="window"``): a row is ``frames`` consecutive samples of
+    a file's resample to ``audio_rate``, starting at ``out_first``; only the source frames those samples' taps reach are
+    read from disk (``read_wav_span``) and uploaded (``window_plan``), and ops.audio_frontend_window forms the row --
+    the bits the whole file's resample has at those columns.  File i, ``n_file_i`` samples long at ``audio_rate``,
+    has ``max(1, ceil(n_file_i / frames))`` windows per epoch, so an epoch covers the corpus once in expectation;
+    sharding and shuffling are the rules above applied to (file, window) pairs.  Training windows start at a draw
+    from U{0 .. max(0, n_file - frames)} keyed on (seed, epoch, file, window) alone -- not on rank, batch size or
+    order -- and pass the index cache by; validation windows tile the file (window w starts at ``w * frames``, the
+    last one is short) and are cached by (file, window).  ``Batch.lengths`` carries every row's real samples and
+    ``info`` rows the window's ``out_first``.  ``window_gain="file"`` (the default) normalises every window by the
+    (min, max) of its whole file's channel mean, found on the host in bounded chunks when the file is first touched;
+    ``"window"`` by the window's own.  Refused with ``use_video``; a file's length is not limited."""
 
     @staticmethod
     def native_plan(clip_frames: int, clip_rate: int, frames: int, audio_rate: int):
@@ -366,6 +436,33 @@ class WavFolderLoader:
         if n > frames:
             return min(int(clip_frames), int(math.ceil(frames * clip_rate / audio_rate))), int(frames)
         return int(clip_frames), max(n, 1)
+
+    @staticmethod
+    def window_plan(file_frames: int, rate: int, frames: int, audio_rate: int, out_first: int):
+        """(span_first, span_frames, n_out) of the window of ``frames`` samples at ``out_first`` of a file's resample to
+        ``audio_rate``: n_out = min(frames, n_file - out_first) samples, formed from the source frames
+        [i0(out_first) - W, i0(out_first + n_out - 1) + W + 1] clipped to the file, i0(j) = j orig // new."""
+        orig, new, W = window_geometry(rate, audio_rate)
+        n_file = -(-int(file_frames) * new // orig)
+        if not 0 <= out_first < n_file:
+            raise ValueError(f"out_first {out_first} lies outside the file's {n_file} samples")
+        n_out = min(int(frames), n_file - int(out_first))
+        first = max(0, int(out_first) * orig // new - W)
+        last = min(int(file_frames) - 1, (int(out_first) + n_out - 1) * orig // new + W + 1)
+        return first, last - first + 1, n_out
+
+    @staticmethod
+    def window_count(file_frames: int, rate: int, frames: int, audio_rate: int) -> int:
+        """Windows of one file per epoch: max(1, ceil(n_file / frames))."""
+        return max(1, -(-resampled_frames(file_frames, rate, audio_rate) // int(frames)))
+
+    def window_start(self, file: int, window: int) -> int:
+        """``out_first`` of (file, window) in this epoch: validation windows tile the file; a training window is drawn
+        from U{0 .. max(0, n_file - frames)} by a generator keyed on (seed, epoch, file, window)."""
+        if not self.train:
+            return window * self.frames
+        key = ((self.seed * 1000003 + self.epoch) * 1000003 + file) * 1000003 + window
+        return random.Random(key).randint(0, max(0, self.n_file[file] - self.frames))
 
     @staticmethod
     def cropped_lengths(lengths, start: int, n: int):
@@ -377,7 +474,7 @@ class WavFolderLoader:
                  batch_subsample_frac: Optional[float] = None, use_video: bool = False,
                  normalize_audio: bool = True, device=None, cache_bytes: int = 4 << 30,
                  video_antialias: bool = False, video_cache_bytes: int = 4 << 30,
-                 clip_length: str = "resample", audio_rate: int = 16000, **_ignored):
+                 clip_length: str = "resample", audio_rate: int = 16000, window_gain: str = "file", **_ignored):
         import os
         from pathlib import Path
         from . import wavenet as W
@@ -393,13 +490,16 @@ class WavFolderLoader:
             raise ValueError("video batches need frames % 1000 == 0 and no batch_subsample_frac "
                              "(the reference crops audio and video independently, dataset.py:232-242, "
                              "which its own size assert then rejects)")
-        if clip_length not in ("resample", "native"):
-            raise ValueError(f"clip_length must be 'resample' or 'native', got {clip_length!r}")
+        if clip_length not in ("resample", "native", "window"):
+            raise ValueError(f"clip_length must be 'resample', 'native' or 'window', got {clip_length!r}")
+        if window_gain not in ("file", "window"):
+            raise ValueError(f"window_gain must be 'file' or 'window', got {window_gain!r}")
         if isinstance(audio_rate, bool) or not isinstance(audio_rate, int) or audio_rate < 1:
             raise ValueError(f"audio_rate must be a positive integer, got {audio_rate!r}")
         self.native, self.audio_rate = clip_length == "native", int(audio_rate)
-        if self.native and use_video:
-            raise ValueError(f"clip_length='native' cannot be combined with use_video: video batches are fixed at "
+        self.window, self.window_gain, self.train = clip_length == "window", window_gain, bool(train)
+        if (self.native or self.window) and use_video:
+            raise ValueError(f"clip_length={clip_length!r} cannot be combined with use_video: video batches are fixed at "
                              f"{self.frames} frames")
         if input_channels > 32768:
             raise ValueError("input_channels above 32768 do not fit the int16 index cache")
@@ -417,9 +517,9 @@ class WavFolderLoader:
                 h = read_wav_header(str(fp))
                 if h["frames"] < 1:
                     raise ValueError(f"{fp}: no audio frames")
-                if self.native and h["rate"] > 100 * self.audio_rate:
+                if (self.native or self.window) and h["rate"] > 100 * self.audio_rate:
                     raise ValueError(f"{fp}: a rate of {h['rate']} Hz is more than 100 x audio_rate {self.audio_rate}")
-                if not self.native and h["frames"] > 100 * self.frames:
+                if not (self.native or self.window) and h["frames"] > 100 * self.frames:
                     raise ValueError(f"{fp}: {h['frames']} frames is more than 100 x the {self.frames} frames "
                                      "the front end resamples to")
                 if use_video and not fp.with_suffix(".npy").is_file():
@@ -439,6 +539,13 @@ class WavFolderLoader:
         key = (os.path.abspath(str(self.root_path)), self.Q, self.frames, self.normalize, str(self.device))
         if self.native:  # (by-rate rows are other rows: a cache of their own per rate)
             key += ("native", self.audio_rate)
+        if self.window:
+            key += ("window", self.audio_rate, self.window_gain)
+            # an epoch's rows are (file, window) pairs; _order shuffles and shards their numbers
+            self.n_file = [resampled_frames(h["frames"], h["rate"], self.audio_rate) for _, _, h in self.index]
+            self.pairs = [(i, w) for i, (_, _, h) in enumerate(self.index)
+                          for w in range(self.window_count(h["frames"], h["rate"], self.frames, self.audio_rate))]
+            self.n_clips = len(self.pairs)
         self.plans = [self.native_plan(h["frames"], h["rate"], self.frames, self.audio_rate) if self.native
                       else (int(h["frames"]), self.frames) for _, _, h in self.index]
         cache = _INDEX_CACHES.get(key)
@@ -585,6 +692,63 @@ class WavFolderLoader:
             return idx
         return torch.stack([fresh[i] if i in fresh else cache.rows[i].to(torch.int32) for i in ids])
 
+    def file_range(self, file: int) -> tuple:
+        """(lo, hi) the windows of ``file`` are normalised by: its channel mean's (min, max) under window_gain="file"
+        (found once per loader cache), (0, 0) -- the window's own -- otherwise."""
+        if self.window_gain != "file":
+            return 0.0, 0.0
+        ranges = self.cache.ranges
+        if file not in ranges:
+            ranges[file] = wav_file_range(self.index[file][1], header=self.index[file][2])
+        return ranges[file]
+
+    def _window_indices(self, rows: list) -> tuple:
+        """``rows``: (file, window, out_first) per row -> ((B, frames) int32 class indices on the device, lengths).
+        Validation windows come from and go to the index cache, keyed (file, window); of the others only the spans
+        their taps reach are read and uploaded, and ONE launch pair forms them."""
+        from .ops import audio_clip_window_descriptors, audio_frontend_window
+        cache, dev = self.cache, self.device
+        keys = [(i, w) for i, w, _ in rows]
+        cached = [not self.train and k in cache.rows for k in keys]
+        if not self.train:
+            cache.hits += sum(cached)
+            cache.misses += len(rows) - sum(cached)
+        todo, plans = [], []
+        for (i, w, out_first), hit in zip(rows, cached):
+            if not hit and (self.train or (i, w) not in [(a, b) for a, b, _ in todo]):
+                h = self.index[i][2]
+                todo.append((i, w, out_first))
+                plans.append(self.window_plan(h["frames"], h["rate"], self.frames, self.audio_rate, out_first))
+        fresh, idx = [], None
+        if todo:
+            spans = [read_wav_span(self.index[i][1], p[0], p[1], header=self.index[i][2])
+                     for (i, _, _), p in zip(todo, plans)]
+            for (i, _, _), p, sp in zip(todo, plans, spans):
+                if sp[1] != p[1]:
+                    raise ValueError(f"{self.index[i][1]}: {sp[1]} of the {p[1]} frames at {p[0]} could be read")
+            total = sum(sp[0].size for sp in spans)
+            # (padded to a 256 Ki-sample step: batches of like-sized spans reuse the ring's pinned buffers)
+            pcm = np.zeros(-(-max(total, 1) // (1 << 18)) * (1 << 18), dtype=np.int16)
+            np.concatenate([sp[0] for sp in spans], out=pcm[:total])
+            ranges = [self.file_range(i) for i, _, _ in todo]
+            desc = audio_clip_window_descriptors(
+                [p[0] for p in plans], [p[1] for p in plans], [self.index[i][2]["frames"] for i, _, _ in todo],
+                [sp[2] for sp in spans], [o for _, _, o in todo], [p[2] for p in plans],
+                [self.index[i][2]["rate"] for i, _, _ in todo], self.audio_rate,
+                lo=[r[0] for r in ranges], hi=[r[1] for r in ranges])
+            d_pcm = _PinnedRing.to_device(_ring("pcm", dev).stage(pcm), dev)
+            d_desc = _PinnedRing.to_device(_ring("clips_window", dev).stage(desc), dev)
+            idx = audio_frontend_window(d_pcm, d_desc, self.Q, self.frames, normalize=self.normalize)
+            for row, ((i, w, _), p) in enumerate(zip(todo, plans)):
+                fresh.append(((i, w), idx[row], p[2]))
+                if not self.train:
+                    cache.put((i, w), idx[row], p[2])
+        if len(todo) == len(rows):
+            return idx, [p[2] for p in plans]
+        made = {k: (row, n) for k, row, n in fresh}
+        out = [made[k] if k in made else (cache.rows[k].to(torch.int32), cache.lengths[k]) for k in keys]
+        return torch.stack([r for r, _ in out]), [n for _, n in out]
+
     def __iter__(self) -> Iterator[Batch]:
         if self.device is None or self.device.type != "cuda":
             raise RuntimeError("WavFolderLoader: the waveform front end is a HIP kernel; pass device= an MI355X "
@@ -595,10 +759,17 @@ class WavFolderLoader:
         dev = self.device
         for s in range(0, len(order), self.batch_size):
             ids = order[s:s + self.batch_size]
+            info = None
             with torch.cuda.device(dev):
-                idx = self._indices(ids)
+                if self.window:  # the order's numbers are (file, window) pairs; from here on `ids` are their files
+                    rows = [self.pairs[k] + (self.window_start(*self.pairs[k]),) for k in ids]
+                    idx, lengths = self._window_indices(rows)
+                    ids = [i for i, _, _ in rows]
+                    info = [dict(self.info[i], out_first=o) for i, _, o in rows]
+                else:
+                    idx = self._indices(ids)
+                    lengths = [self.cache.lengths.get(i, self.plans[i][1]) for i in ids] if self.native else None
                 B, T = idx.shape
-                lengths = [self.cache.lengths.get(i, self.plans[i][1]) for i in ids] if self.native else None
                 if self.frac is not None:  # dataset.py:232-237, on the indices: only the crop is expanded
                     n = math.ceil(T * self.frac)
                     start = crop_rng.randint(0, T - n)
@@ -613,7 +784,7 @@ class WavFolderLoader:
             if self.use_video:
                 video = self._video_batch(ids)
             yield Batch(audio, video, [self.index[i][0] for i in ids], [self.filepaths[i] for i in ids],
-                        [self.info[i] for i in ids], lengths=lengths)
+                        [self.info[i] for i in ids] if info is None else info, lengths=lengths)
         self.check_video_status()
 
 
@@ -648,7 +819,7 @@ def get_dataloader(filepath, input_channels: int, batch_size: int = 64, train: b
     with a ``train`` or ``valid`` sub-folder gives a WavFolderLoader; anything else raises ValueError."""
     if not str(filepath).startswith("synthetic://") and _is_wav_folder(filepath):
         extra = {k: kwargs[k] for k in ("cache_bytes", "video_antialias", "video_cache_bytes", "clip_length",
-                                        "audio_rate") if k in kwargs}
+                                        "audio_rate", "window_gain") if k in kwargs}
         return WavFolderLoader(filepath, input_channels, batch_size, train=train, rank=rank,
                                world_size=world_size, shuffle=kwargs.get("shuffle", False),
                                batch_subsample_frac=batch_subsample_frac, use_video=use_video,

@@ -1088,6 +1088,63 @@ def audio_frontend_var(pcm: torch.Tensor, descriptors: torch.Tensor, quantizatio
     return (idx, y) if return_waveform else idx
 
 
+_AUDIO_CLIP_WINDOW = [("offset", "<i8"), ("span_first", "<i8"), ("out_first", "<i8"), ("file_frames", "<i8"),
+                      ("span_frames", "<i4"), ("channels", "<i4"), ("n_out", "<i4"), ("rate_in", "<i4"),
+                      ("rate_out", "<i4"), ("lo", "<f4"), ("hi", "<f4"), ("reserved", "<i4")]
+
+
+def audio_clip_window_descriptors(span_first, span_frames, file_frames, channels, out_first, n_out, rate_in, rate_out,
+                                  lo=None, hi=None, offsets=None):
+    """Host array of mvn_audio_clip_window records (64 bytes each: int64 offset, span_first, out_first, file_frames;
+    int32 span_frames, channels, n_out, rate_in, rate_out; float32 lo, hi; int32 reserved) as (B, 16) int32.  One
+    sequence per field (``rate_out`` may be one number); ``lo`` / ``hi`` default to 0, 0 -- the window's own range --
+    and ``offsets`` to the spans lying back to back in the upload."""
+    import numpy as np
+    rec = np.zeros(len(span_frames), dtype=_AUDIO_CLIP_WINDOW)
+    rec["span_first"], rec["span_frames"], rec["file_frames"] = span_first, span_frames, file_frames
+    rec["channels"], rec["out_first"], rec["n_out"] = channels, out_first, n_out
+    rec["rate_in"], rec["rate_out"] = rate_in, rate_out
+    if lo is not None:
+        rec["lo"] = lo
+    if hi is not None:
+        rec["hi"] = hi
+    if offsets is None:
+        spans = rec["span_frames"].astype(np.int64) * rec["channels"]
+        offsets = np.concatenate([[0], np.cumsum(spans)[:-1]]) if len(spans) else []
+    rec["offset"] = offsets
+    return rec.view(np.int32).reshape(len(span_frames), 16)
+
+
+def audio_frontend_window(pcm: torch.Tensor, descriptors: torch.Tensor, quantization_channels: int, width: int,
+                          normalize: bool = True, return_waveform: bool = False):
+    """Windows of files -> class indices by RATE (mvn_audio_frontend_window): row b is the columns ``[out_first,
+    out_first + n_out)`` of its whole file's resample from ``rate_in`` to ``rate_out`` -- the bits this call gives for
+    the whole file, cropped, which up to ``rate_in = 10 rate_out`` are ``audio_frontend_var``'s -- formed from the
+    uploaded span alone, silence behind them.  With ``normalize``
+    a descriptor's ``hi > lo`` is the range to normalise by (the loader's per-file gain), else the window's own
+    (min, max).  ``descriptors``: (B, 16) int32 on the GPU (``audio_clip_window_descriptors``), checked on the device:
+    a refused row (span outside the upload or not covering the window's taps, ``n_out`` outside [1, width], a window
+    outside the file, rates or channels < 1) is -1.  Nothing here waits for the GPU."""
+    _require_gpu(pcm, "pcm")
+    if pcm.dtype != torch.int16 or pcm.dim() != 1 or not pcm.is_contiguous():
+        raise ValueError("pcm must be a contiguous 1-D int16 tensor")
+    _require_gpu(descriptors, "descriptors")
+    if descriptors.dim() != 2 or descriptors.shape[1] != 16 or descriptors.dtype != torch.int32 \
+            or not descriptors.is_contiguous() or descriptors.shape[0] < 1:
+        raise ValueError("descriptors must be a contiguous (B, 16) int32 tensor")
+    B, dev, lib = int(descriptors.shape[0]), pcm.device, N.lib()
+    with torch.cuda.device(dev):
+        y = torch.empty(B, width, dtype=torch.float32, device=dev)
+        idx = torch.empty(B, width, dtype=torch.int32, device=dev)
+        scratch = torch.empty(max(int(lib.mvn_audio_frontend_window_scratch_floats(B, width)), 2),
+                              dtype=torch.float32, device=dev)
+        N.check(lib.mvn_audio_frontend_window(pcm.data_ptr(), pcm.numel(), descriptors.data_ptr(), B,
+                                              int(quantization_channels), int(width), int(bool(normalize)),
+                                              y.data_ptr(), scratch.data_ptr(), idx.data_ptr(), _stream_ptr(dev)),
+                "mvn_audio_frontend_window")
+    return (idx, y) if return_waveform else idx
+
+
 VIDEO_FRONTEND_SIZE = 64       # the front end's output is (64, 64) per frame (movenet/dataset.py:292-310)
 VIDEO_FRONTEND_MAX_DIM = 4096  # H, W <= 4096: a gray source row fits the kernel's LDS row
 

@@ -251,6 +251,7 @@ class Dance2Music(nn.Module):
             # field existed)
             video_antialias=bool(getattr(c, "video_antialias", False)),
             clip_length=getattr(c, "clip_length", "resample"), audio_rate=int(getattr(c, "audio_rate", 16000)),
+            window_gain=getattr(c, "window_gain", "file"),
             # row F2: class indices cross PCIe (4 bytes per sample), the (B,Q,T) one-hot the Batch
             # contract asks for is formed on the device
             device=self.device if self.device.type == "cuda" else None)
