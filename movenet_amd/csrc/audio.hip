@@ -1,22 +1,31 @@
 // The loader's waveform front end (movenet/dataset.py:253-289 without the decoder): interleaved int16 PCM of a batch of
-// clips of different lengths -> (B, N) class indices, in two kernels.
+// clips of different lengths -> (B, width) class indices, in two kernels.
 //
-//   af_resample_kernel   channel mean + sinc_interp_hann resample of the WHOLE clip to N frames (lowpass_filter_width 6,
+//   af_resample_kernel   channel mean + sinc_interp_hann resample to the row's N frames (lowpass_filter_width 6,
 //                        roll-off 0.99), fp32 y, and the (min, max) of every tile of outputs
-//   af_quantise_kernel   the clip's (min, max) from the tile partials, min-max normalise, mu-law, clamp -> int32 index
+//   af_quantise_kernel   the row's (min, max) from the tile partials, min-max normalise, mu-law, clamp -> int32 index
 //
-// Per output sample k of a clip of n frames (g = gcd(n, N), orig = n/g, new = N/g, s = 0.99 min(orig, new)/orig):
-//   c = k orig/new,  y[k] = sum_i m[i] h(i - c),  u = (i - c) s,  h = s sinc(pi u) cos^2(pi u/12) for |u| < 6, else 0
-// k orig is a 64-bit integer product; i0 = floor(c) and the phase (k orig) mod new are taken from it exactly, so the
-// float part of a tap's argument is (i - i0) - phase/new: a small integer minus a fraction, whatever the clip's length.
+// ONE form serves the three entry points.  A row (AfRow) is N <= width outputs, silence behind them, that are the
+// columns [j0, j0 + N) of the resample orig : new of a FILE of file_frames frames, formed from an uploaded span whose
+// frame 0 is the file's frame `first`.  The three descriptors only say how a row is found:
+//   mvn_audio_clip          the whole clip to N = width = n_out frames: j0 = first = 0, the span is the file
+//   mvn_audio_clip_var      the whole clip to its own N = n_out <= width frames: placed as above
+//   mvn_audio_clip_window   N columns at out_first of a file's resample rate_in : rate_out, and a range to normalise by
 //
-// Clips come through a DEVICE descriptor array (one launch per batch, not per clip).  Every read of the upload is
+// Per output j of a file of n frames (orig : new the reduced ratio, s = 0.99 min(orig, new)/orig):
+//   c = j orig/new,  y[j] = sum_i m[i] h(i - c),  u = (i - c) s,  h = s sinc(pi u) cos^2(pi u/12) for |u| < 6, else 0
+// j orig is a 64-bit integer product; i0 = floor(c) and the phase (j orig) mod new are taken from it exactly, so the
+// float part of a tap's argument is (i - i0) - phase/new: a small integer minus a fraction, whatever the file's length.
+//
+// Rows come through a DEVICE descriptor array (one launch per batch, not per clip).  Every read of the upload is
 // bounded by the descriptor's own span [offset, offset + frames channels), and a descriptor whose span does not lie
-// inside [0, pcm_len) -- or whose ratio n/N needs a longer window than the LDS tile holds (n <= 100 N always fits) --
+// inside [0, pcm_len) -- or whose ratio needs a longer window than the LDS tile holds (n <= 100 N always fits) --
 // is never read through: its row of indices is filled with -1.
 #include "common.h"
 
 #include <cmath>
+#include <cstdint>
+#include <string>
 
 namespace mvn {
 
@@ -33,6 +42,31 @@ struct AfGeom {
   int sub;   // outputs per staged window
   bool ok;
 };
+
+// A row's place in its file: column k of the row is the file's output j0 + k, frame i of the file is frame i - first
+// of the span, and m[i] = 0 outside [0, file_frames).
+struct AfAt {
+  long long j0, first, file_frames;
+};
+
+struct AfRow {
+  mvn_audio_clip c;  // the uploaded span: offset, frames, channels
+  AfGeom g;
+  AfAt at;
+  int N;          // outputs to form; `width` where g.ok is false, so that the whole row is marked
+  float lo, hi;   // the given normalisation range, hi > lo; else lo = hi = 0: the row's own
+};
+
+// [offset, offset + frames channels) lies inside [0, pcm_len); frames, channels in [1, 2^31), so no sum or product
+// here leaves 64 bits whatever the offset
+constexpr bool af_span_ok(long long offset, long long frames, long long channels, long long pcm_len) {
+  return offset >= 0 && frames * channels <= pcm_len && offset <= pcm_len - frames * channels;
+}
+static_assert(af_span_ok(10, 45, 2, 100), "a span ending exactly at pcm_len lies inside");
+static_assert(!af_span_ok(11, 45, 2, 100), "one sample past pcm_len");
+static_assert(!af_span_ok(-1, 45, 2, 100), "offset = -1");
+static_assert(!af_span_ok(INT64_MAX, 50, 2, 1000) && !af_span_ok(INT64_MAX - 10, 50, 2, 1000), "offset near 2^63");
+static_assert(!af_span_ok(0, INT32_MAX, INT32_MAX, 1LL << 40), "the largest span, without overflow");
 
 __device__ __forceinline__ long long af_gcd(long long a, long long b) {
   while (b) {
@@ -58,80 +92,54 @@ __device__ __forceinline__ void af_geom_taps(AfGeom &g) {
   if (g.sub < kAfMinSub) g.ok = false;
 }
 
-__device__ __forceinline__ AfGeom af_geom(const mvn_audio_clip &c, long long pcm_len, int N) {
-  AfGeom g;
-  g.ok = c.frames >= 1 && c.channels >= 1 && c.offset >= 0 &&
-         c.offset + (long long)c.frames * c.channels <= pcm_len;
-  g.orig = g.neu = 1;
-  g.s = 0.f;
-  g.W = g.sub = 0;
-  if (!g.ok) return g;
-  const long long a = af_gcd(c.frames, N);
-  g.orig = c.frames / a;
-  g.neu = N / a;
-  af_geom_taps(g);
-  return g;
+// the refused row of `width` columns over the span (offset, frames, channels); the builders below fill in the rest
+__device__ __forceinline__ AfRow af_row_refused(long long offset, int frames, int channels, int width) {
+  AfRow r;
+  r.c.offset = offset;
+  r.c.frames = frames;
+  r.c.channels = channels;
+  r.g.orig = r.g.neu = 1;
+  r.g.s = 0.f;
+  r.g.W = r.g.sub = 0;
+  r.g.ok = false;
+  r.at = AfAt{0, 0, frames};
+  r.N = width;
+  r.lo = r.hi = 0.f;
+  return r;
 }
 
-__device__ __forceinline__ float wave_min(float v) { return -wave_max(-v); }
-
-// The by-rate form (mvn_audio_frontend_var): clip b is resampled to ITS OWN n_out frames into a row of `width`; the rest
-// of the row is silence.  The descriptor, and what it makes of a row: N outputs to form (the whole width for a
-// descriptor that is refused, so that the whole row is marked), by the geometry of the plain form for N.
-struct AfRow {
-  mvn_audio_clip c;
-  AfGeom g;
-  int N;
-};
-__device__ __forceinline__ AfRow af_row_var(const mvn_audio_clip_var &v, long long pcm_len, int width) {
-  AfRow r;
-  r.c.offset = v.offset;
-  r.c.frames = v.frames;
-  r.c.channels = v.channels;
-  const bool fits = v.n_out >= 1 && v.n_out <= width;
-  r.N = fits ? v.n_out : width;
-  r.g = af_geom(r.c, pcm_len, r.N);
-  if (!fits) r.g.ok = false;
-  if (!r.g.ok) r.N = width;
+// The by-rate form (mvn_audio_frontend_var): the whole clip, resampled to ITS OWN n_out frames
+__device__ __forceinline__ AfRow af_row(const mvn_audio_clip_var &v, long long pcm_len, int width) {
+  AfRow r = af_row_refused(v.offset, v.frames, v.channels, width);
+  if (v.n_out < 1 || v.n_out > width) return r;
+  if (v.frames < 1 || v.channels < 1 || !af_span_ok(v.offset, v.frames, v.channels, pcm_len)) return r;
+  const long long a = af_gcd(v.frames, v.n_out);
+  r.g.orig = v.frames / a;
+  r.g.neu = v.n_out / a;
+  r.g.ok = true;
+  af_geom_taps(r.g);
+  if (r.g.ok) r.N = v.n_out;
   return r;
+}
+
+// The plain form (mvn_audio_frontend): the by-rate form with n_out = width for every clip
+__device__ __forceinline__ AfRow af_row(const mvn_audio_clip &c, long long pcm_len, int width) {
+  return af_row(mvn_audio_clip_var{c.offset, c.frames, c.channels, width, 0}, pcm_len, width);
 }
 
 // The windowed by-rate form (mvn_audio_frontend_window): row b is the columns [out_first, out_first + n_out) of the
 // resample of a whole FILE from rate_in to rate_out, of which only the span the taps of those columns reach was
-// uploaded.  AfAt places a row in its file: column k of the row is the file's output j0 + k, frame i of the file is
-// frame i - first of the span, and m[i] = 0 outside [0, file_frames).  (The other two forms are j0 = first = 0 with
-// the span the whole clip.)
-struct AfAt {
-  long long j0, first, file_frames;
-};
-struct AfWinRow {
-  mvn_audio_clip c;  // the uploaded span: offset, span_frames, channels
-  AfGeom g;
-  AfAt at;
-  int N;
-  float lo, hi;  // the given normalisation range, hi > lo; else lo = hi = 0: the window's own
-};
-__device__ __forceinline__ AfWinRow af_row_window(const mvn_audio_clip_window &v, long long pcm_len, int width) {
-  AfWinRow r;
-  r.c.offset = v.offset;
-  r.c.frames = v.span_frames;
-  r.c.channels = v.channels;
-  r.at.j0 = v.out_first;
-  r.at.first = v.span_first;
-  r.at.file_frames = v.file_frames;
-  r.N = width;
+// uploaded.
+__device__ __forceinline__ AfRow af_row(const mvn_audio_clip_window &v, long long pcm_len, int width) {
+  AfRow r = af_row_refused(v.offset, v.span_frames, v.channels, width);
+  r.at = AfAt{v.out_first, v.span_first, v.file_frames};
   const bool given = v.hi > v.lo && v.hi - v.lo < INFINITY;  // (NaN or an infinite range: not given)
   r.lo = given ? v.lo : 0.f;
   r.hi = given ? v.hi : 0.f;
   AfGeom &g = r.g;
-  g.orig = g.neu = 1;
-  g.s = 0.f;
-  g.W = g.sub = 0;
-  g.ok = false;
   if (v.n_out < 1 || v.n_out > width) return r;
   if (v.rate_in < 1 || v.rate_out < 1 || v.channels < 1 || v.span_frames < 1) return r;
-  const long long span = (long long)v.span_frames * v.channels;
-  if (v.offset < 0 || span > pcm_len || v.offset > pcm_len - span) return r;
+  if (!af_span_ok(v.offset, v.span_frames, v.channels, pcm_len)) return r;
   const long long a = af_gcd(v.rate_in, v.rate_out);
   g.orig = v.rate_in / a;
   g.neu = v.rate_out / a;
@@ -152,30 +160,34 @@ __device__ __forceinline__ AfWinRow af_row_window(const mvn_audio_clip_window &v
   return r;
 }
 
-// VAR = false: N outputs per row, rows N apart (the plain form, as it was).  VAR = true: N of `width` outputs.
-// WIN (with VAR): the row's place in its file is `at`; without it `at` is not looked at.  WIN also sums an output's
-// taps in blocks of kAfTapBlock: each block from 0 by fmaf in ascending d, the block sums added in ascending order.
-// One chain of fmaf over 2 W + 2 taps loses accuracy as sqrt(taps) -- 1.4e-6 against float64 at 100 : 1, 1216 taps,
-// where float32 numpy's pairwise sum stays near 2e-7 -- and blocks of 128 hold it near 4e-7.  An output of at most
-// kAfTapBlock taps (rate_in <= 10 rate_out) is ONE block, to which nothing is added: the other forms' bits.
-template <bool VAR, bool WIN = false>
-__device__ __forceinline__ void af_resample(const int16_t *__restrict__ pcm, const mvn_audio_clip &c, const AfGeom &g,
-                                            int N, int width, float *__restrict__ y, float2 *__restrict__ part,
-                                            const AfAt at = AfAt{0, 0, 0}) {
+__device__ __forceinline__ float wave_min(float v) { return -wave_max(-v); }
+
+// Row blockIdx.y, tile blockIdx.x: r.N of `width` outputs by r.g, placed in their file by r.at; y = 0 behind them,
+// and in the whole row where r.g.ok is false.
+// BLOCKS (the windowed form) sums an output's taps in blocks of kAfTapBlock: each block from 0 by fmaf in ascending d,
+// the block sums added in ascending order.  One chain of fmaf over 2 W + 2 taps loses accuracy as sqrt(taps) --
+// 1.4e-6 against float64 at 100 : 1, 1216 taps, where float32 numpy's pairwise sum stays near 2e-7 -- and blocks of
+// 128 hold it near 4e-7.  An output of at most kAfTapBlock taps (rate_in <= 10 rate_out) is ONE block, to which
+// nothing is added: the bits of the one chain the other two forms keep at every ratio.
+template <bool BLOCKS>
+__device__ __forceinline__ void af_resample(const int16_t *__restrict__ pcm, const AfRow &r, int width,
+                                            float *__restrict__ y, float2 *__restrict__ part) {
   __shared__ float win[kAfWin];
   __shared__ float red[2 * (kAfThreads / kWave)];
-  const int b = blockIdx.y, tid = threadIdx.x;
+  const mvn_audio_clip &c = r.c;
+  const AfGeom &g = r.g;
+  const AfAt &at = r.at;
+  const int b = blockIdx.y, tid = threadIdx.x, N = r.N;
   const int t0 = blockIdx.x * kAfTile, t1 = min(N, t0 + kAfTile);
-  float *yb = y + (size_t)b * (VAR ? width : N);
+  float *yb = y + (size_t)b * width;
   if (!g.ok) {  // (workgroup-uniform) nothing of the upload is read
     for (int k = t0 + tid; k < t1; k += kAfThreads) yb[k] = 0.f;
     if (tid == 0) part[(size_t)b * gridDim.x + blockIdx.x] = make_float2(0.f, 0.f);
     return;
   }
-  if (VAR) {  // the silence behind the clip; a tile that holds nothing else ends here (workgroup-uniform)
-    for (int k = max(N, t0) + tid; k < min(width, t0 + kAfTile); k += kAfThreads) yb[k] = 0.f;
-    if (t0 >= N) return;
-  }
+  // the silence behind the clip; a tile that holds nothing else ends here (workgroup-uniform)
+  for (int k = max(N, t0) + tid; k < min(width, t0 + kAfTile); k += kAfThreads) yb[k] = 0.f;
+  if (t0 >= N) return;
   const int16_t *src = pcm + c.offset;
   const int ch = c.channels, W = g.W;
   const float den = 32768.0f * (float)ch, s = g.s, fneu = (float)g.neu;
@@ -183,16 +195,15 @@ __device__ __forceinline__ void af_resample(const int16_t *__restrict__ pcm, con
   float mn = INFINITY, mx = -INFINITY;
   for (int k0 = t0; k0 < t1; k0 += g.sub) {
     const int k1 = min(t1, k0 + g.sub);
-    const long long j0 = WIN ? at.j0 : 0LL;
-    const long long lo = ((j0 + k0) * g.orig) / g.neu - W;
-    const long long hi = ((j0 + (k1 - 1)) * g.orig) / g.neu + W + 1;
-    const int len = (int)min(hi - lo + 1, (long long)kAfWin);  // (af_geom sized sub so that the window fits)
+    const long long lo = ((at.j0 + k0) * g.orig) / g.neu - W;
+    const long long hi = ((at.j0 + (k1 - 1)) * g.orig) / g.neu + W + 1;
+    const int len = (int)min(hi - lo + 1, (long long)kAfWin);  // (af_geom_taps sized sub so that the window fits)
     __syncthreads();  // the previous window has been consumed
     for (int j = tid; j < len; j += kAfThreads) {
       const long long i = lo + j;
-      float v = 0.f;  // m[i] = 0 outside the clip
-      const long long is = WIN ? i - at.first : i;  // its place in the upload: every read stays inside the span
-      if (i >= 0 && is >= 0 && is < c.frames && (!WIN || i < at.file_frames)) {
+      float v = 0.f;  // m[i] = 0 outside the file
+      const long long is = i - at.first;  // its place in the upload: every read stays inside the span
+      if (i >= 0 && is >= 0 && is < c.frames && i < at.file_frames) {
         int sum = 0;
         for (int q = 0; q < ch; ++q) sum += src[is * ch + q];
         v = (float)sum / den;
@@ -201,13 +212,13 @@ __device__ __forceinline__ void af_resample(const int16_t *__restrict__ pcm, con
     }
     __syncthreads();
     for (int k = k0 + tid; k < k1; k += kAfThreads) {
-      const long long p = (j0 + k) * g.orig;
+      const long long p = (at.j0 + k) * g.orig;
       const long long i0 = p / g.neu;
       const float frac = (float)(p - i0 * g.neu) / fneu;
       const float *w = win + (int)(i0 - lo);
       float acc = 0.f, blocks = 0.f;
       for (int d = -W; d <= W + 1; ++d) {
-        if (WIN && d != -W && (d + W) % kAfTapBlock == 0) {  // a block is full
+        if (BLOCKS && d != -W && (d + W) % kAfTapBlock == 0) {  // a block is full
           blocks += acc;
           acc = 0.f;
         }
@@ -220,7 +231,7 @@ __device__ __forceinline__ void af_resample(const int16_t *__restrict__ pcm, con
         }
         acc = fmaf(w[d], h, acc);
       }
-      if (WIN && 2 * W + 2 > kAfTapBlock) acc = blocks + acc;
+      if (BLOCKS && 2 * W + 2 > kAfTapBlock) acc = blocks + acc;
       yb[k] = acc;
       mn = fminf(mn, acc);
       mx = fmaxf(mx, acc);
@@ -243,60 +254,38 @@ __device__ __forceinline__ void af_resample(const int16_t *__restrict__ pcm, con
   }
 }
 
+template <class Clip, bool BLOCKS>
 __global__ __launch_bounds__(kAfThreads) void af_resample_kernel(const int16_t *__restrict__ pcm, long long pcm_len,
-                                                                 const mvn_audio_clip *__restrict__ clips, int N,
+                                                                 const Clip *__restrict__ clips, int width,
                                                                  float *__restrict__ y, float2 *__restrict__ part) {
-  const mvn_audio_clip c = clips[blockIdx.y];
-  const AfGeom g = af_geom(c, pcm_len, N);
-  af_resample<false>(pcm, c, g, N, N, y, part);
-}
-
-__global__ __launch_bounds__(kAfThreads) void af_resample_var_kernel(const int16_t *__restrict__ pcm,
-                                                                     long long pcm_len,
-                                                                     const mvn_audio_clip_var *__restrict__ clips,
-                                                                     int width, float *__restrict__ y,
-                                                                     float2 *__restrict__ part) {
-  const AfRow r = af_row_var(clips[blockIdx.y], pcm_len, width);
-  af_resample<true>(pcm, r.c, r.g, r.N, width, y, part);
-}
-
-__global__ __launch_bounds__(kAfThreads) void af_resample_window_kernel(const int16_t *__restrict__ pcm,
-                                                                        long long pcm_len,
-                                                                        const mvn_audio_clip_window *__restrict__ clips,
-                                                                        int width, float *__restrict__ y,
-                                                                        float2 *__restrict__ part) {
-  const AfWinRow r = af_row_window(clips[blockIdx.y], pcm_len, width);
-  af_resample<true, true>(pcm, r.c, r.g, r.N, width, y, part, r.at);
+  const AfRow r = af_row(clips[blockIdx.y], pcm_len, width);
+  af_resample<BLOCKS>(pcm, r, width, y, part);
 }
 
 // audio <- (audio - min) / (max - min); audio * 2 - 1 (dataset.py:271-275), a clip with max == min left as it is (the
 // silent clip of the reference's `sum() == 0` test); then the mu-law of mu_law_encode_kernel, clamped to 0 .. Q-1
 // (an un-normalised resample may overshoot [-1, 1]).
-// VAR: the (min, max) runs over the tiles that hold the clip's N outputs, of the `tiles` slots a row has; the columns
-// behind them get the class mu-law gives 0.0.  WIN: a range ghi > glo is the (min, max) to normalise by, given with
-// the row (workgroup-uniform); without one the row's own.
-template <bool VAR, bool WIN = false>
-__device__ __forceinline__ void af_quantise(const AfGeom &g, int N, int width, int Q, int normalize, int tiles,
+// The (min, max) is r.hi > r.lo where the row gives one (workgroup-uniform), else it runs over the tiles that hold the
+// row's N outputs, of the `tiles` slots a row has; the columns behind them get the class mu-law gives 0.0.
+__device__ __forceinline__ void af_quantise(const AfRow &r, int width, int Q, int normalize, int tiles,
                                             const float *__restrict__ y, const float2 *__restrict__ part,
-                                            int32_t *__restrict__ idx, float glo = 0.f, float ghi = 0.f) {
+                                            int32_t *__restrict__ idx) {
   __shared__ float red[2 * (kAfThreads / kWave)];
-  const int b = blockIdx.y, tid = threadIdx.x;
+  const int b = blockIdx.y, tid = threadIdx.x, N = r.N;
   const int t0 = blockIdx.x * kAfTile, t1 = min(N, t0 + kAfTile);
-  int32_t *ib = idx + (size_t)b * (VAR ? width : N);
-  if (!g.ok) {
+  int32_t *ib = idx + (size_t)b * width;
+  if (!r.g.ok) {
     for (int k = t0 + tid; k < t1; k += kAfThreads) ib[k] = -1;
     return;
   }
-  if (VAR) {  // (workgroup-uniform)
-    const int silence = (int)((float)(Q - 1) / 2.0f + 0.5f);
-    for (int k = max(N, t0) + tid; k < min(width, t0 + kAfTile); k += kAfThreads) ib[k] = silence;
-    if (t0 >= N) return;
-  }
-  const int own = VAR ? (N + kAfTile - 1) / kAfTile : tiles;
+  const int silence = (int)((float)(Q - 1) / 2.0f + 0.5f);
+  for (int k = max(N, t0) + tid; k < min(width, t0 + kAfTile); k += kAfThreads) ib[k] = silence;
+  if (t0 >= N) return;  // (workgroup-uniform)
+  const int own = (N + kAfTile - 1) / kAfTile;
   float mn = INFINITY, mx = -INFINITY;
-  if (WIN && normalize && ghi > glo) {
-    mn = glo;
-    mx = ghi;
+  if (normalize && r.hi > r.lo) {
+    mn = r.lo;
+    mx = r.hi;
   } else if (normalize) {  // every workgroup folds the clip's partials in the same order: one (min, max) per clip, reproducibly
     for (int t = tid; t < own; t += kAfThreads) {
       const float2 p = part[(size_t)b * tiles + t];
@@ -319,7 +308,7 @@ __device__ __forceinline__ void af_quantise(const AfGeom &g, int N, int width, i
   }
   const bool scale = normalize && mx != mn;
   const float mu = (float)(Q - 1), range = mx - mn, lmu = log1pf(mu);
-  const float *yb = y + (size_t)b * (VAR ? width : N);
+  const float *yb = y + (size_t)b * width;
   for (int k = t0 + tid; k < t1; k += kAfThreads) {
     float v = yb[k];
     if (scale) {
@@ -332,33 +321,39 @@ __device__ __forceinline__ void af_quantise(const AfGeom &g, int N, int width, i
   }
 }
 
-__global__ __launch_bounds__(kAfThreads) void af_quantise_kernel(const mvn_audio_clip *__restrict__ clips,
-                                                                 long long pcm_len, int N, int Q, int normalize,
-                                                                 int tiles, const float *__restrict__ y,
+template <class Clip>
+__global__ __launch_bounds__(kAfThreads) void af_quantise_kernel(const Clip *__restrict__ clips, long long pcm_len,
+                                                                 int width, int Q, int normalize, int tiles,
+                                                                 const float *__restrict__ y,
                                                                  const float2 *__restrict__ part,
                                                                  int32_t *__restrict__ idx) {
-  const AfGeom g = af_geom(clips[blockIdx.y], pcm_len, N);
-  af_quantise<false>(g, N, N, Q, normalize, tiles, y, part, idx);
+  const AfRow r = af_row(clips[blockIdx.y], pcm_len, width);
+  af_quantise(r, width, Q, normalize, tiles, y, part, idx);
 }
 
-__global__ __launch_bounds__(kAfThreads) void af_quantise_var_kernel(const mvn_audio_clip_var *__restrict__ clips,
-                                                                     long long pcm_len, int width, int Q,
-                                                                     int normalize, int tiles,
-                                                                     const float *__restrict__ y,
-                                                                     const float2 *__restrict__ part,
-                                                                     int32_t *__restrict__ idx) {
-  const AfRow r = af_row_var(clips[blockIdx.y], pcm_len, width);
-  af_quantise<true>(r.g, r.N, width, Q, normalize, tiles, y, part, idx);
-}
-
-__global__ __launch_bounds__(kAfThreads) void af_quantise_window_kernel(const mvn_audio_clip_window *__restrict__ clips,
-                                                                        long long pcm_len, int width, int Q,
-                                                                        int normalize, int tiles,
-                                                                        const float *__restrict__ y,
-                                                                        const float2 *__restrict__ part,
-                                                                        int32_t *__restrict__ idx) {
-  const AfWinRow r = af_row_window(clips[blockIdx.y], pcm_len, width);
-  af_quantise<true, true>(r.g, r.N, width, Q, normalize, tiles, y, part, idx, r.lo, r.hi);
+// The three entry points: `what` is the entry point's name without its mvn_ prefix
+template <class Clip, bool BLOCKS>
+static int audio_frontend_launch(const char *what, const int16_t *pcm, long long pcm_len, const Clip *clips, int batch,
+                                 int classes, int width, int normalize, float *y, float *scratch, int32_t *index,
+                                 void *stream) {
+  if (!pcm || !clips || !y || !scratch || !index || pcm_len < 1 || batch < 1 || batch > 65535 || width < 1 ||
+      classes < 2 || classes > 65536) {
+    set_error("mvn_%s: bad argument", what);
+    return MVN_ERR_BAD_ARG;
+  }
+  if (((uintptr_t)scratch & 7u) != 0) {
+    set_error("mvn_%s: scratch must be 8-byte aligned", what);
+    return MVN_ERR_BAD_ARG;
+  }
+  const int tiles = (width + kAfTile - 1) / kAfTile;
+  const dim3 grid(tiles, batch);
+  hipLaunchKernelGGL((af_resample_kernel<Clip, BLOCKS>), grid, dim3(kAfThreads), 0, (hipStream_t)stream, pcm, pcm_len,
+                     clips, width, y, (float2 *)scratch);
+  int rc = check_hip(hipGetLastError(), (std::string(what) + " (resample)").c_str());
+  if (rc) return rc;
+  hipLaunchKernelGGL((af_quantise_kernel<Clip>), grid, dim3(kAfThreads), 0, (hipStream_t)stream, clips, pcm_len, width,
+                     classes, normalize, tiles, (const float *)y, (const float2 *)scratch, index);
+  return check_hip(hipGetLastError(), (std::string(what) + " (quantise)").c_str());
 }
 
 }  // namespace mvn
@@ -372,24 +367,8 @@ size_t mvn_audio_frontend_scratch_floats(int batch, int n_out) {
 
 int mvn_audio_frontend(const int16_t *pcm, long long pcm_len, const mvn_audio_clip *clips, int batch, int classes,
                        int n_out, int normalize, float *y, float *scratch, int32_t *index, void *stream) {
-  if (!pcm || !clips || !y || !scratch || !index || pcm_len < 1 || batch < 1 || batch > 65535 || n_out < 1 ||
-      classes < 2 || classes > 65536) {
-    mvn::set_error("mvn_audio_frontend: bad argument");
-    return MVN_ERR_BAD_ARG;
-  }
-  if (((uintptr_t)scratch & 7u) != 0) {
-    mvn::set_error("mvn_audio_frontend: scratch must be 8-byte aligned");
-    return MVN_ERR_BAD_ARG;
-  }
-  const int tiles = (n_out + mvn::kAfTile - 1) / mvn::kAfTile;
-  const dim3 grid(tiles, batch);
-  hipLaunchKernelGGL(mvn::af_resample_kernel, grid, dim3(mvn::kAfThreads), 0, (hipStream_t)stream, pcm, pcm_len,
-                     clips, n_out, y, (float2 *)scratch);
-  int rc = mvn::check_hip(hipGetLastError(), "audio_frontend (resample)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(mvn::af_quantise_kernel, grid, dim3(mvn::kAfThreads), 0, (hipStream_t)stream, clips, pcm_len,
-                     n_out, classes, normalize, tiles, (const float *)y, (const float2 *)scratch, index);
-  return mvn::check_hip(hipGetLastError(), "audio_frontend (quantise)");
+  return mvn::audio_frontend_launch<mvn_audio_clip, false>("audio_frontend", pcm, pcm_len, clips, batch, classes,
+                                                           n_out, normalize, y, scratch, index, stream);
 }
 
 size_t mvn_audio_frontend_var_scratch_floats(int batch, int width) {
@@ -399,24 +378,8 @@ size_t mvn_audio_frontend_var_scratch_floats(int batch, int width) {
 int mvn_audio_frontend_var(const int16_t *pcm, long long pcm_len, const mvn_audio_clip_var *clips, int batch,
                            int classes, int width, int normalize, float *y, float *scratch, int32_t *index,
                            void *stream) {
-  if (!pcm || !clips || !y || !scratch || !index || pcm_len < 1 || batch < 1 || batch > 65535 || width < 1 ||
-      classes < 2 || classes > 65536) {
-    mvn::set_error("mvn_audio_frontend_var: bad argument");
-    return MVN_ERR_BAD_ARG;
-  }
-  if (((uintptr_t)scratch & 7u) != 0) {
-    mvn::set_error("mvn_audio_frontend_var: scratch must be 8-byte aligned");
-    return MVN_ERR_BAD_ARG;
-  }
-  const int tiles = (width + mvn::kAfTile - 1) / mvn::kAfTile;
-  const dim3 grid(tiles, batch);
-  hipLaunchKernelGGL(mvn::af_resample_var_kernel, grid, dim3(mvn::kAfThreads), 0, (hipStream_t)stream, pcm, pcm_len,
-                     clips, width, y, (float2 *)scratch);
-  int rc = mvn::check_hip(hipGetLastError(), "audio_frontend_var (resample)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(mvn::af_quantise_var_kernel, grid, dim3(mvn::kAfThreads), 0, (hipStream_t)stream, clips, pcm_len,
-                     width, classes, normalize, tiles, (const float *)y, (const float2 *)scratch, index);
-  return mvn::check_hip(hipGetLastError(), "audio_frontend_var (quantise)");
+  return mvn::audio_frontend_launch<mvn_audio_clip_var, false>("audio_frontend_var", pcm, pcm_len, clips, batch,
+                                                               classes, width, normalize, y, scratch, index, stream);
 }
 
 size_t mvn_audio_frontend_window_scratch_floats(int batch, int width) {
@@ -426,24 +389,8 @@ size_t mvn_audio_frontend_window_scratch_floats(int batch, int width) {
 int mvn_audio_frontend_window(const int16_t *pcm, long long pcm_len, const mvn_audio_clip_window *clips, int batch,
                               int classes, int width, int normalize, float *y, float *scratch, int32_t *index,
                               void *stream) {
-  if (!pcm || !clips || !y || !scratch || !index || pcm_len < 1 || batch < 1 || batch > 65535 || width < 1 ||
-      classes < 2 || classes > 65536) {
-    mvn::set_error("mvn_audio_frontend_window: bad argument");
-    return MVN_ERR_BAD_ARG;
-  }
-  if (((uintptr_t)scratch & 7u) != 0) {
-    mvn::set_error("mvn_audio_frontend_window: scratch must be 8-byte aligned");
-    return MVN_ERR_BAD_ARG;
-  }
-  const int tiles = (width + mvn::kAfTile - 1) / mvn::kAfTile;
-  const dim3 grid(tiles, batch);
-  hipLaunchKernelGGL(mvn::af_resample_window_kernel, grid, dim3(mvn::kAfThreads), 0, (hipStream_t)stream, pcm,
-                     pcm_len, clips, width, y, (float2 *)scratch);
-  int rc = mvn::check_hip(hipGetLastError(), "audio_frontend_window (resample)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(mvn::af_quantise_window_kernel, grid, dim3(mvn::kAfThreads), 0, (hipStream_t)stream, clips,
-                     pcm_len, width, classes, normalize, tiles, (const float *)y, (const float2 *)scratch, index);
-  return mvn::check_hip(hipGetLastError(), "audio_frontend_window (quantise)");
+  return mvn::audio_frontend_launch<mvn_audio_clip_window, true>("audio_frontend_window", pcm, pcm_len, clips, batch,
+                                                                 classes, width, normalize, y, scratch, index, stream);
 }
 
 }  // extern "C"

@@ -207,6 +207,17 @@ def _to_device_async(x: np.ndarray, device: torch.device) -> torch.Tensor:
         return _PinnedRing.to_device(_ring("video", device).stage(np.ascontiguousarray(x)), device)
 
 
+def _upload_pcm(device: torch.device, parts: list, kind: str, desc: np.ndarray, least: int = 0) -> tuple:
+    """A batch's int16 ``parts`` back to back in ONE upload (at least ``least`` samples of it) and its descriptor array
+    ``desc``, through the pinned rings "pcm" and ``kind`` -> (PCM, descriptors) on the device."""
+    total = sum(p.size for p in parts)
+    # (padded to a 256 Ki-sample step: batches of like-sized clips reuse the ring's pinned buffers)
+    pcm = np.zeros(-(-max(total, least) // (1 << 18)) * (1 << 18), dtype=np.int16)
+    np.concatenate(parts, out=pcm[:total])
+    d_pcm = _PinnedRing.to_device(_ring("pcm", device).stage(pcm), device)
+    return d_pcm, _PinnedRing.to_device(_ring(kind, device).stage(desc), device)
+
+
 def read_wav_header(path: str) -> dict:
     """rate / frames / channels / sample width of an integer-PCM WAV (standard library ``wave``); ValueError naming
     the file for anything else (float WAVs, compressed formats, broken headers)."""
@@ -670,19 +681,13 @@ class WavFolderLoader:
             if self.native:  # a clip that would come out longer than the row contributes its head
                 clips = [(c[0].reshape(-1)[:self.plans[i][0] * c[2]], self.plans[i][0], c[2])
                          for i, c in zip(todo, clips)]
-            total = sum(c[0].size for c in clips)
-            # (padded to a 256 Ki-sample step: batches of like-sized clips reuse the ring's pinned buffers)
-            pcm = np.zeros(-(-total // (1 << 18)) * (1 << 18), dtype=np.int16)
-            np.concatenate([c[0] for c in clips], out=pcm[:total])
-            frames, channels = [c[1] for c in clips], [c[2] for c in clips]
-            d_pcm = _PinnedRing.to_device(_ring("pcm", dev).stage(pcm), dev)
+            pcm, frames, channels = [c[0] for c in clips], [c[1] for c in clips], [c[2] for c in clips]
             if self.native:
-                d_desc = _PinnedRing.to_device(_ring("clips_var", dev).stage(
-                    audio_clip_var_descriptors(frames, channels, [self.plans[i][1] for i in todo])), dev)
+                d_pcm, d_desc = _upload_pcm(dev, pcm, "clips_var", audio_clip_var_descriptors(
+                    frames, channels, [self.plans[i][1] for i in todo]))
                 idx = audio_frontend_var(d_pcm, d_desc, self.Q, self.frames, normalize=self.normalize)
             else:
-                d_desc = _PinnedRing.to_device(
-                    _ring("clips", dev).stage(audio_clip_descriptors(frames, channels)), dev)
+                d_pcm, d_desc = _upload_pcm(dev, pcm, "clips", audio_clip_descriptors(frames, channels))
                 idx = audio_frontend(d_pcm, frames, channels, self.Q, n_out=self.frames, normalize=self.normalize,
                                      descriptors=d_desc)
             for row, i in enumerate(todo):
@@ -726,18 +731,13 @@ class WavFolderLoader:
             for (i, _, _), p, sp in zip(todo, plans, spans):
                 if sp[1] != p[1]:
                     raise ValueError(f"{self.index[i][1]}: {sp[1]} of the {p[1]} frames at {p[0]} could be read")
-            total = sum(sp[0].size for sp in spans)
-            # (padded to a 256 Ki-sample step: batches of like-sized spans reuse the ring's pinned buffers)
-            pcm = np.zeros(-(-max(total, 1) // (1 << 18)) * (1 << 18), dtype=np.int16)
-            np.concatenate([sp[0] for sp in spans], out=pcm[:total])
             ranges = [self.file_range(i) for i, _, _ in todo]
             desc = audio_clip_window_descriptors(
                 [p[0] for p in plans], [p[1] for p in plans], [self.index[i][2]["frames"] for i, _, _ in todo],
                 [sp[2] for sp in spans], [o for _, _, o in todo], [p[2] for p in plans],
                 [self.index[i][2]["rate"] for i, _, _ in todo], self.audio_rate,
                 lo=[r[0] for r in ranges], hi=[r[1] for r in ranges])
-            d_pcm = _PinnedRing.to_device(_ring("pcm", dev).stage(pcm), dev)
-            d_desc = _PinnedRing.to_device(_ring("clips_window", dev).stage(desc), dev)
+            d_pcm, d_desc = _upload_pcm(dev, [sp[0] for sp in spans], "clips_window", desc, least=1)
             idx = audio_frontend_window(d_pcm, d_desc, self.Q, self.frames, normalize=self.normalize)
             for row, ((i, w, _), p) in enumerate(zip(todo, plans)):
                 fresh.append(((i, w), idx[row], p[2]))

@@ -980,17 +980,62 @@ def mu_law_decode(index: torch.Tensor, quantization_channels: int) -> torch.Tens
 AUDIO_FRONTEND_MAX_RATIO = 100  # frames <= 100 n_out: the longest clip whose output tile's window fits the LDS
 
 
+_AUDIO_CLIP = [("offset", "<i8"), ("frames", "<i4"), ("channels", "<i4")]
+_AUDIO_CLIP_VAR = _AUDIO_CLIP + [("n_out", "<i4"), ("reserved", "<i4")]
+_AUDIO_CLIP_WINDOW = [("offset", "<i8"), ("span_first", "<i8"), ("out_first", "<i8"), ("file_frames", "<i8"),
+                      ("span_frames", "<i4"), ("channels", "<i4"), ("n_out", "<i4"), ("rate_in", "<i4"),
+                      ("rate_out", "<i4"), ("lo", "<f4"), ("hi", "<f4"), ("reserved", "<i4")]
+
+
+def _back_to_back(spans, offsets=None):
+    """A descriptor array's ``offsets`` as given, else those of ``spans`` (int64 elements each) lying back to back in
+    the upload"""
+    import numpy as np
+    if offsets is not None:
+        return offsets
+    return np.concatenate([[0], np.cumsum(spans)[:-1]]) if len(spans) else []
+
+
 def audio_clip_descriptors(frames, channels, offsets=None):
     """Host array of mvn_audio_clip records (int64 offset, int32 frames, int32 channels) as (B, 4) int32;
     ``offsets`` default to the clips lying back to back in the upload."""
     import numpy as np
-    rec = np.zeros(len(frames), dtype=[("offset", "<i8"), ("frames", "<i4"), ("channels", "<i4")])
+    rec = np.zeros(len(frames), dtype=_AUDIO_CLIP)
     rec["frames"], rec["channels"] = frames, channels
-    if offsets is None:
-        spans = rec["frames"].astype(np.int64) * rec["channels"]
-        offsets = np.concatenate([[0], np.cumsum(spans)[:-1]]) if len(spans) else []
-    rec["offset"] = offsets
+    rec["offset"] = _back_to_back(rec["frames"].astype(np.int64) * rec["channels"], offsets)
     return rec.view(np.int32).reshape(len(frames), 4)
+
+
+def _check_pcm(pcm: torch.Tensor) -> None:
+    _require_gpu(pcm, "pcm")
+    if pcm.dtype != torch.int16 or pcm.dim() != 1 or not pcm.is_contiguous():
+        raise ValueError("pcm must be a contiguous 1-D int16 tensor")
+
+
+def _audio_frontend_call(entry: str, scratch_entry: str, pcm, descriptors, words: int, B, Q, width, normalize,
+                         y=None, idx=None):
+    """One launch pair of the front end through ``entry`` (all three share one kernel pair, see csrc/audio.hip):
+    ``descriptors`` a (B, words) int32 tensor on the GPU, B its own row count where None; ``y`` / ``idx`` the
+    (B, width) outputs where the caller brings them.  Returns (idx, y)."""
+    _check_pcm(pcm)
+    _require_gpu(descriptors, "descriptors")
+    if B is None and descriptors.dim() == 2:
+        B = int(descriptors.shape[0])
+    if B is None or B < 1 or tuple(descriptors.shape) != (B, words) or descriptors.dtype != torch.int32 \
+            or not descriptors.is_contiguous():
+        raise ValueError(f"descriptors must be a contiguous (B, {words}) int32 tensor")
+    dev, lib = pcm.device, N.lib()
+    with torch.cuda.device(dev):
+        y = torch.empty(B, width, dtype=torch.float32, device=dev) if y is None else y
+        idx = torch.empty(B, width, dtype=torch.int32, device=dev) if idx is None else idx
+        for t, dt, what in ((y, torch.float32, "waveform_out"), (idx, torch.int32, "out")):
+            if tuple(t.shape) != (B, width) or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{what} must be a contiguous ({B}, {width}) {dt} tensor on {dev}")
+        scratch = torch.empty(max(int(getattr(lib, scratch_entry)(B, width)), 2), dtype=torch.float32, device=dev)
+        N.check(getattr(lib, entry)(pcm.data_ptr(), pcm.numel(), descriptors.data_ptr(), B, int(Q), int(width),
+                                    int(bool(normalize)), y.data_ptr(), scratch.data_ptr(), idx.data_ptr(),
+                                    _stream_ptr(dev)), entry)
+    return idx, y
 
 
 def audio_frontend(pcm: torch.Tensor, frames, channels, quantization_channels: int, n_out: int = None,
@@ -1006,9 +1051,7 @@ def audio_frontend(pcm: torch.Tensor, frames, channels, quantization_channels: i
     already on the device ((B, 4) int32 of audio_clip_descriptors -- the loader ships it through its pinned ring).
     Returns (B, n_out) int32 indices, with ``return_waveform`` also the (B, n_out) fp32 waveform before
     normalisation.  Nothing here waits for the GPU."""
-    _require_gpu(pcm, "pcm")
-    if pcm.dtype != torch.int16 or pcm.dim() != 1 or not pcm.is_contiguous():
-        raise ValueError("pcm must be a contiguous 1-D int16 tensor")
+    _check_pcm(pcm)  # (before the host lists are held against it)
     if n_out is None:
         from . import wavenet as W
         n_out = W.MAX_AUDIO_FRAMES
@@ -1016,7 +1059,7 @@ def audio_frontend(pcm: torch.Tensor, frames, channels, quantization_channels: i
     if B < 1 or len(channels) != B:
         raise ValueError("frames and channels must name the same, non-zero number of clips")
     desc = audio_clip_descriptors(frames, channels, offsets)
-    rec = desc.view([("offset", "<i8"), ("frames", "<i4"), ("channels", "<i4")]).reshape(B)
+    rec = desc.view(_AUDIO_CLIP).reshape(B)
     for b in range(B):
         o, n, c = int(rec["offset"][b]), int(rec["frames"][b]), int(rec["channels"][b])
         if n < 1 or c < 1 or o < 0 or o + n * c > pcm.numel():
@@ -1025,27 +1068,11 @@ def audio_frontend(pcm: torch.Tensor, frames, channels, quantization_channels: i
         if n > AUDIO_FRONTEND_MAX_RATIO * n_out:
             raise ValueError(f"clip {b}: {n} frames is more than {AUDIO_FRONTEND_MAX_RATIO} x the {n_out} "
                              "output frames the front end resamples to")
-    dev = pcm.device
-    lib = N.lib()
-    with torch.cuda.device(dev):
-        if descriptors is None:
-            descriptors = torch.from_numpy(desc).to(dev)
-        if tuple(descriptors.shape) != (B, 4) or descriptors.dtype != torch.int32 or not descriptors.is_contiguous():
-            raise ValueError("descriptors must be a contiguous (B, 4) int32 tensor")
-        y = waveform_out if waveform_out is not None else torch.empty(B, n_out, dtype=torch.float32, device=dev)
-        idx = out if out is not None else torch.empty(B, n_out, dtype=torch.int32, device=dev)
-        for t, dt, what in ((y, torch.float32, "waveform_out"), (idx, torch.int32, "out")):
-            if tuple(t.shape) != (B, n_out) or t.dtype != dt or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"{what} must be a contiguous ({B}, {n_out}) {dt} tensor on {dev}")
-        scratch = torch.empty(max(int(lib.mvn_audio_frontend_scratch_floats(B, n_out)), 2), dtype=torch.float32,
-                              device=dev)
-        N.check(lib.mvn_audio_frontend(pcm.data_ptr(), pcm.numel(), descriptors.data_ptr(), B,
-                                       int(quantization_channels), int(n_out), int(bool(normalize)), y.data_ptr(),
-                                       scratch.data_ptr(), idx.data_ptr(), _stream_ptr(dev)), "mvn_audio_frontend")
+    if descriptors is None:
+        descriptors = torch.from_numpy(desc).to(pcm.device)
+    idx, y = _audio_frontend_call("mvn_audio_frontend", "mvn_audio_frontend_scratch_floats", pcm, descriptors, 4, B,
+                                  quantization_channels, n_out, normalize, waveform_out, out)
     return (idx, y) if return_waveform else idx
-
-
-_AUDIO_CLIP_VAR = [("offset", "<i8"), ("frames", "<i4"), ("channels", "<i4"), ("n_out", "<i4"), ("reserved", "<i4")]
 
 
 def audio_clip_var_descriptors(frames, channels, n_out, offsets=None):
@@ -1054,10 +1081,7 @@ def audio_clip_var_descriptors(frames, channels, n_out, offsets=None):
     import numpy as np
     rec = np.zeros(len(frames), dtype=_AUDIO_CLIP_VAR)
     rec["frames"], rec["channels"], rec["n_out"] = frames, channels, n_out
-    if offsets is None:
-        spans = rec["frames"].astype(np.int64) * rec["channels"]
-        offsets = np.concatenate([[0], np.cumsum(spans)[:-1]]) if len(spans) else []
-    rec["offset"] = offsets
+    rec["offset"] = _back_to_back(rec["frames"].astype(np.int64) * rec["channels"], offsets)
     return rec.view(np.int32).reshape(len(frames), 6)
 
 
@@ -1068,29 +1092,9 @@ def audio_frontend_var(pcm: torch.Tensor, descriptors: torch.Tensor, quantizatio
     indices, silence (the class of 0.0) behind it.  ``descriptors``: (B, 6) int32 on the GPU
     (``audio_clip_var_descriptors``), checked on the device: a clip outside the upload or with ``n_out`` outside
     [1, width] gives a row of -1.  Nothing here waits for the GPU."""
-    _require_gpu(pcm, "pcm")
-    if pcm.dtype != torch.int16 or pcm.dim() != 1 or not pcm.is_contiguous():
-        raise ValueError("pcm must be a contiguous 1-D int16 tensor")
-    _require_gpu(descriptors, "descriptors")
-    if descriptors.dim() != 2 or descriptors.shape[1] != 6 or descriptors.dtype != torch.int32 \
-            or not descriptors.is_contiguous() or descriptors.shape[0] < 1:
-        raise ValueError("descriptors must be a contiguous (B, 6) int32 tensor")
-    B, dev, lib = int(descriptors.shape[0]), pcm.device, N.lib()
-    with torch.cuda.device(dev):
-        y = torch.empty(B, width, dtype=torch.float32, device=dev)
-        idx = torch.empty(B, width, dtype=torch.int32, device=dev)
-        scratch = torch.empty(max(int(lib.mvn_audio_frontend_var_scratch_floats(B, width)), 2), dtype=torch.float32,
-                              device=dev)
-        N.check(lib.mvn_audio_frontend_var(pcm.data_ptr(), pcm.numel(), descriptors.data_ptr(), B,
-                                           int(quantization_channels), int(width), int(bool(normalize)),
-                                           y.data_ptr(), scratch.data_ptr(), idx.data_ptr(), _stream_ptr(dev)),
-                "mvn_audio_frontend_var")
+    idx, y = _audio_frontend_call("mvn_audio_frontend_var", "mvn_audio_frontend_var_scratch_floats", pcm, descriptors,
+                                  6, None, quantization_channels, width, normalize)
     return (idx, y) if return_waveform else idx
-
-
-_AUDIO_CLIP_WINDOW = [("offset", "<i8"), ("span_first", "<i8"), ("out_first", "<i8"), ("file_frames", "<i8"),
-                      ("span_frames", "<i4"), ("channels", "<i4"), ("n_out", "<i4"), ("rate_in", "<i4"),
-                      ("rate_out", "<i4"), ("lo", "<f4"), ("hi", "<f4"), ("reserved", "<i4")]
 
 
 def audio_clip_window_descriptors(span_first, span_frames, file_frames, channels, out_first, n_out, rate_in, rate_out,
@@ -1108,10 +1112,7 @@ def audio_clip_window_descriptors(span_first, span_frames, file_frames, channels
         rec["lo"] = lo
     if hi is not None:
         rec["hi"] = hi
-    if offsets is None:
-        spans = rec["span_frames"].astype(np.int64) * rec["channels"]
-        offsets = np.concatenate([[0], np.cumsum(spans)[:-1]]) if len(spans) else []
-    rec["offset"] = offsets
+    rec["offset"] = _back_to_back(rec["span_frames"].astype(np.int64) * rec["channels"], offsets)
     return rec.view(np.int32).reshape(len(span_frames), 16)
 
 
@@ -1125,23 +1126,8 @@ def audio_frontend_window(pcm: torch.Tensor, descriptors: torch.Tensor, quantiza
     (min, max).  ``descriptors``: (B, 16) int32 on the GPU (``audio_clip_window_descriptors``), checked on the device:
     a refused row (span outside the upload or not covering the window's taps, ``n_out`` outside [1, width], a window
     outside the file, rates or channels < 1) is -1.  Nothing here waits for the GPU."""
-    _require_gpu(pcm, "pcm")
-    if pcm.dtype != torch.int16 or pcm.dim() != 1 or not pcm.is_contiguous():
-        raise ValueError("pcm must be a contiguous 1-D int16 tensor")
-    _require_gpu(descriptors, "descriptors")
-    if descriptors.dim() != 2 or descriptors.shape[1] != 16 or descriptors.dtype != torch.int32 \
-            or not descriptors.is_contiguous() or descriptors.shape[0] < 1:
-        raise ValueError("descriptors must be a contiguous (B, 16) int32 tensor")
-    B, dev, lib = int(descriptors.shape[0]), pcm.device, N.lib()
-    with torch.cuda.device(dev):
-        y = torch.empty(B, width, dtype=torch.float32, device=dev)
-        idx = torch.empty(B, width, dtype=torch.int32, device=dev)
-        scratch = torch.empty(max(int(lib.mvn_audio_frontend_window_scratch_floats(B, width)), 2),
-                              dtype=torch.float32, device=dev)
-        N.check(lib.mvn_audio_frontend_window(pcm.data_ptr(), pcm.numel(), descriptors.data_ptr(), B,
-                                              int(quantization_channels), int(width), int(bool(normalize)),
-                                              y.data_ptr(), scratch.data_ptr(), idx.data_ptr(), _stream_ptr(dev)),
-                "mvn_audio_frontend_window")
+    idx, y = _audio_frontend_call("mvn_audio_frontend_window", "mvn_audio_frontend_window_scratch_floats", pcm,
+                                  descriptors, 16, None, quantization_channels, width, normalize)
     return (idx, y) if return_waveform else idx
 
 
@@ -1160,10 +1146,7 @@ def video_clip_descriptors(shapes, n_frames: int, offsets=None):
     if len(shapes):
         arr = np.asarray(shapes, dtype=np.int64).reshape(len(shapes), 3)
         rec["height"], rec["width"], rec["channels"] = arr[:, 0], arr[:, 1], arr[:, 2]
-        if offsets is None:
-            spans = int(n_frames) * arr[:, 0] * arr[:, 1] * arr[:, 2]
-            offsets = np.concatenate([[0], np.cumsum(spans)[:-1]])
-        rec["offset"] = offsets
+        rec["offset"] = _back_to_back(int(n_frames) * arr[:, 0] * arr[:, 1] * arr[:, 2], offsets)
     return rec.view(np.int32).reshape(len(shapes), 6)
 
 
