@@ -28,19 +28,7 @@
 
 namespace mvn {
 
-typedef float f32x2_b16 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_b16 __attribute__((ext_vector_type(2)));
-
-// {bf16(a), bf16(b)} in one register, a in the low half (round to nearest even)
-__device__ __forceinline__ unsigned b16_pack2(float a, float b) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_b16{a, b}, bf16x2_b16));
-}
-__device__ __forceinline__ u32x4 b16_pack8(const float *x) {
-  return u32x4{b16_pack2(x[0], x[1]), b16_pack2(x[2], x[3]), b16_pack2(x[4], x[5]), b16_pack2(x[6], x[7])};
-}
-__device__ __forceinline__ unsigned short b16_one(float w) { return __builtin_bit_cast(unsigned short, (__bf16)w); }
-#define B16_MFMA(acc_, a_, b_) \
-  acc_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a_), __builtin_bit_cast(bf16x8, b_), acc_, 0, 0, 0)
+// (b16_pack2 / b16_pack8 / b16_one / B16_MFMA, the conversions of both directions, stand in fused_bwd_l.h)
 
 // ----------------------------------------------------------------------------------------
 // Forward: fused_layer64s_bf3_kernel with one plane.  LDS image [block][k-step][lane][8 bf16] (1 KB per block and
@@ -415,457 +403,62 @@ static void launch_layer_form(const LayerForm &f, const FusedFwdPArgs &a, int ba
 }
 
 // ----------------------------------------------------------------------------------------
-// Backward: bwd_layer64_kernel<false> with one plane -- same roles, tiles, barriers, scatter outputs (A', P0) and slab /
-// bias-partial formats (reduce_layer64_kernel and bwd_scatter_combine_kernel are shared).  Per slot: the LDS reads of the
-// next operand, four conversions, ONE MFMA.  [Wr | Ws]^T is a 16 KB image (48 KB as planes), the tap weights of a wave
-// 16 registers (48): 118 KB of LDS in all.
+// Backward: the scaffold of bwd_layer64_kernel (bwd_layer64_body.inc, described in fused_bwd_l.h) under the one-plane
+// operand policy -- same roles, tiles, barriers, scatter outputs (A', P0) and slab / bias-partial formats
+// (reduce_layer64_kernel and bwd_scatter_combine_kernel are shared).
 // ----------------------------------------------------------------------------------------
-constexpr int FBL16_WIMG_BYTES = 2 * 8 * 1024;  // [c block][k-step][lane][8 bf16]
-constexpr int FBL16_LDS_BYTES = 3 * FBL_TILE_F * 4 + FBL16_WIMG_BYTES;
-
-// WRITE_DFG (mvn_backward_bf16_ctx; never together with GLOBAL): the same arithmetic, the fp32 df | dg tile also written
-// to a.dfg for the context pass, as bwd_layer64_kernel<true> does.
+// GLOBAL (mvn_backward_bf16_global): the row sums of df | dg leave in g_part.  WRITE_DFG (mvn_backward_bf16_ctx; never
+// together with GLOBAL): the fp32 df | dg tile also written to a.dfg for the context pass, as bwd_layer64_kernel<true> does.
+#define FBL_BF3 0
 template <bool GLOBAL, bool WRITE_DFG = false>
 __global__ __launch_bounds__(512, 1) void bwd_layer64_bf16_kernel(FusedBwdLArgs a, int chunks_per_b, int chunk_t,
                                                                  float *__restrict__ rs_bias_part, float *__restrict__ rs_part,
-                                                                 float *__restrict__ fg_part, float *__restrict__ g_part) {
-  static_assert(!(GLOBAL && WRITE_DFG), "the label's row sums and the dfg output are separate kernels");
-  constexpr int C = FB_C, LD = W2_LD, TT = W2_T;
-  extern __shared__ __attribute__((aligned(16))) float fbl16_lds[];
-  float (*U)[LD] = (float (*)[LD])fbl16_lds;                      // [dxo; dskip], then [x(t - d); x(t)]
-  float (*Gt)[LD] = (float (*)[LD])(fbl16_lds + FBL_TILE_F);      // tanh | sigmoid, then df | dg
-  float (*O)[LD] = (float (*)[LD])(fbl16_lds + 2 * FBL_TILE_F);   // dxo -> A' | P0
-  unsigned short *wimg = (unsigned short *)(fbl16_lds + 3 * FBL_TILE_F);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x / chunks_per_b, ch = blockIdx.x - b * chunks_per_b;
-  const int li = lane & 31, lh = lane >> 5, h4 = 4 * lh;
-  const int tb = (a.t_lo & ~TILE_ALIGN) + ch * chunk_t, te = min(a.t_end, tb + chunk_t);
-  const int skip_lo = max(a.t_lo, a.t_skip0);
-  const bool has_dxo = a.ga.p != nullptr;
+                                                                 float *__restrict__ fg_part, float *__restrict__ g_part)
+#include "bwd_layer64_body.inc"
+#undef FBL_BF3
 
-  // ---- [Wr | Ws]^T as the dz product's A operand: lane -> row c = 32 cb + (lane & 31), element j of k-step ks ->
-  // o = 16 ks + 8 (lane >> 5) + j (o < 64: residual rows, else skip rows)
-  for (int i = tid; i < 2 * C * C; i += 512) {
-    const int o = i >> 6, c = i & 63;
-    const float w = o < C ? a.wr[(size_t)o * C + c] : a.ws[(size_t)(o - C) * C + c];
-    wimg[((((c >> 5) * 8 + (o >> 4)) * 64 + (c & 31) + 32 * ((o >> 3) & 1)) * 8) + (o & 7)] = b16_one(w);
-  }
-  const unsigned wa0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned short *)wimg + 16u * lane;
+// The layer backward's kernels, [bf16][plain | dfg output | label row sums]: what a launch needs besides its arguments
+// (the fp32 label's row sums come from the dfg output and a kernel of their own: global_cond.h)
+struct BwdLayerForm {
+  const void *kernel[3];
+  size_t lds_bytes;
+  const char *name, *attr_what;
+};
+static const BwdLayerForm BWD_LAYER_FORMS[2] = {
+    {{(const void *)bwd_layer64_kernel<false>, (const void *)bwd_layer64_kernel<true>, nullptr}, FBL_LDS_BYTES, "bwd_layer64",
+     "hipFuncSetAttribute(bwd_layer64)"},
+    {{(const void *)bwd_layer64_bf16_kernel<false>, (const void *)bwd_layer64_bf16_kernel<false, true>,
+      (const void *)bwd_layer64_bf16_kernel<true>}, FBL16_LDS_BYTES, "bwd_layer64_bf16", "hipFuncSetAttribute(bwd_layer64_bf16)"},
+};
 
-  // ---- phase-2 roles: tap half, K half, channel block; B operand W_tap[o][32 wc + li] for o = 64 kh + 16 j + 8 lh + e
-  const int half = wave >> 2, kh = (wave >> 1) & 1, wc = wave & 1;
-  u32x4 wp[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    float wv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int o = 64 * kh + 16 * j + 8 * lh + e;
-      const float *src = o < C ? a.wf : a.wg;
-      wv[e] = src[((size_t)(o & (C - 1)) * C + 32 * wc + li) * 2 + (half ? 0 : 1)];
-    }
-    wp[j] = b16_pack8(wv);
-  }
-  const int wm = wave >> 1, wn = wave & 1;  // filter / gate weight gradient: rows [32 wm, +32), columns [64 wn, +64)
-  f32x16 accw[2], accr;                     // accr: residual / skip weight gradient, block (rows [32 wm, +32), channels [32 wn, +32))
-#pragma unroll
-  for (int r = 0; r < 16; ++r) accw[0][r] = accw[1][r] = accr[r] = 0.f;
-  // phase-1 roles: dz block (channels [32 cb1, +32), steps [32 tq1, +32)) over the K half kh1 of the tile's 128 rows
-  const int kh1 = wave >> 2, tq1 = (wave >> 1) & 1, cb1 = wave & 1;
-  float *Zx = &O[C][0];  // the first K halves' partial dz in the P0 staging rows, idle in phase 1
-
-  // ---- staging (bwd_layer64_kernel's): thread -> rows (tid >> 4) + 32 p, columns 4 (tid & 15) .. +3
-  const int srow = tid >> 4, st = 4 * (tid & 15);
-  f4 r_ga[2], r_gp[2], r_ds[2], r_th[2], r_sg[2], r_x[4];
-  float bsum[4] = {0.f, 0.f, 0.f, 0.f};
-  // (GLOBAL only: row sums of df | dg, rows 32 p + srow; <false> never touches it and the compiler drops it)
-  [[maybe_unused]] float gsum[GLOBAL ? 4 : 1] = {};
-  bool z_ga = false, z_ds = false;
-  const __amdgpu_buffer_rsrc_t gab = fb_rsrc(a.ga.p + (size_t)b * a.ga.sb);
-  const __amdgpu_buffer_rsrc_t gpb = fb_rsrc(a.gp.p + (size_t)b * a.gp.sb);
-  const __amdgpu_buffer_rsrc_t dskb = fb_rsrc(a.dskip.p + (size_t)b * a.dskip.sb);
-  const __amdgpu_buffer_rsrc_t thb = fb_rsrc(a.th.p + (size_t)b * a.th.sb);
-  const __amdgpu_buffer_rsrc_t sgb = fb_rsrc(a.sg.p + (size_t)b * a.sg.sb);
-  const __amdgpu_buffer_rsrc_t xinb = fb_rsrc(a.xin.p + (size_t)b * a.xin.sb);
-  const __amdgpu_buffer_rsrc_t oab = fb_rsrc(a.oa.p + (size_t)b * a.oa.sb);
-  const __amdgpu_buffer_rsrc_t opb = fb_rsrc(a.op.p + (size_t)b * a.op.sb);
-  [[maybe_unused]] __amdgpu_buffer_rsrc_t dfgb;  // WRITE_DFG: df | dg (B, 2C, Tp) for the context pass
-  if constexpr (WRITE_DFG) dfgb = fb_rsrc(a.dfg.p + (size_t)b * a.dfg.sb);
-  const int vo_t = 4 * (srow * a.th.ld + st), vo_ds = 4 * (srow * a.dskip.ld + st);
-  auto interior = [&](int t0) {
-    const bool x_full = t0 >= a.t_lo && t0 + TT <= te;
-    const bool ga_ok = !has_dxo || t0 >= a.up_lo || t0 + TT <= a.up_lo;
-    const bool gp_ok = !has_dxo || t0 + TT + a.up_d <= a.t_end || t0 + a.up_d >= a.t_end;
-    const bool s_ok = t0 >= skip_lo || t0 + TT <= skip_lo;
-    return x_full && ga_ok && gp_ok && s_ok;
-  };
-  auto gload_r_part = [&](int t0, int part) {  // part 0..4: A', P0 (shifted), dskip, tanh, sigmoid of tile t0
-    int ld_t = 4 * a.th.ld, ld_ds = 4 * a.dskip.ld;
-    asm volatile("" : "+s"(ld_t), "+s"(ld_ds));
-    const int c4 = 4 * t0;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      if (part == 0) {
-        r_ga[p] = (has_dxo && t0 >= a.up_lo) ? fb_load16(gab, vo_t, 32 * p * ld_t + c4) : fb_load16(thb, vo_t, c4);
-      } else if (part == 1) {
-        r_gp[p] = (has_dxo && t0 + a.up_d < a.t_end) ? fb_load16(gpb, vo_t, 32 * p * ld_t + c4 + 4 * a.up_d) : kZero4;
-      } else if (part == 2) {
-        r_ds[p] = t0 >= skip_lo ? fb_load16(dskb, vo_ds, 32 * p * ld_ds + c4 - 4 * a.t_base) : fb_load16(sgb, vo_t, c4);
-      } else if (part == 3) {
-        r_th[p] = fb_load16(thb, vo_t, 32 * p * ld_t + c4);
-      } else {
-        r_sg[p] = fb_load16(sgb, vo_t, 32 * p * ld_t + c4);
-      }
-    }
-  };
-  auto gload_r_edge = [&](int t0) {
-    int srow_q = srow;
-    asm volatile("" : "+v"(srow_q));
-    const int t = t0 + st;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int row = 32 * p + srow_q;
-      r_ga[p] = has_dxo ? ld4_edge(a.ga.at(b, row, 0), t, a.up_lo, te) : kZero4;
-      r_gp[p] = has_dxo ? ld4_edge(a.gp.at(b, row, 0) + a.up_d, t, a.t_lo, min(a.t_end - a.up_d, te)) : kZero4;
-    }
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int row = 32 * p + srow_q;
-      r_ds[p] = ld4_edge(a.dskip.at(b, row, 0) - a.t_base, t, skip_lo, te);
-      r_th[p] = ld4_edge(a.th.at(b, row, 0), t, a.t_lo, te);
-      r_sg[p] = ld4_edge(a.sg.at(b, row, 0), t, a.t_lo, te);
-    }
-  };
-  auto set_zero_flags = [&](int t0, bool inter) {
-    z_ga = inter && (!has_dxo || t0 < a.up_lo);
-    z_ds = inter && t0 < skip_lo;
-  };
-  auto gload_x = [&](int t0) {  // rows [0, 64): x(t - d); [64, 128): x(t)
-    if (t0 >= a.t_lo && t0 + TT <= te) {
-      int ld_x = 4 * a.th.ld;
-      asm volatile("" : "+s"(ld_x));
-#pragma unroll
-      for (int p = 0; p < 4; ++p) r_x[p] = fb_load16(xinb, vo_t, 32 * (p & 1) * ld_x + 4 * t0 - (p < 2 ? 4 * a.d : 0));
-    } else {
-      int srow_q = srow;
-      asm volatile("" : "+v"(srow_q));
-      const int t = t0 + st;
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-        r_x[p] = ld4_edge(a.xin.at(b, 32 * (p & 1) + srow_q, 0) - (p < 2 ? a.d : 0), t, a.t_lo, te);
-    }
-  };
-  auto lstore_r = [&]() {
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const f4 dxo = z_ga ? r_gp[p] : f4_add(r_ga[p], r_gp[p]);
-      const f4 dsk = z_ds ? kZero4 : r_ds[p];
-      *(f4 *)&U[32 * p + srow][st] = dxo;
-      *(f4 *)&O[32 * p + srow][st] = dxo;
-      *(f4 *)&U[C + 32 * p + srow][st] = dsk;
-      bsum[p] += (dxo.x + dxo.y) + (dxo.z + dxo.w);  // bias gradients = row sums (fp32)
-      bsum[2 + p] += (dsk.x + dsk.y) + (dsk.z + dsk.w);
-      *(f4 *)&Gt[32 * p + srow][st] = r_th[p];
-      *(f4 *)&Gt[C + 32 * p + srow][st] = r_sg[p];
-    }
-  };
-  auto row8 = [&](const float *row, float (&o)[8]) {  // 8 consecutive values of a row
-    const f4 a0 = *(const f4 *)row, a1 = *(const f4 *)(row + 4);
-    o[0] = a0.x; o[1] = a0.y; o[2] = a0.z; o[3] = a0.w; o[4] = a1.x; o[5] = a1.y; o[6] = a1.z; o[7] = a1.w;
-  };
-
-  {
-    const bool inter = interior(tb);
-    if (inter) {
-#pragma unroll
-      for (int part = 0; part < 5; ++part) gload_r_part(tb, part);
-    } else {
-      gload_r_edge(tb);
-    }
-    set_zero_flags(tb, inter);
-  }
-  lstore_r();
-  __syncthreads();  // (covers the weight image too)
-  typedef __attribute__((address_space(3))) u32x4 lds_u4;
-  for (int t0 = tb; t0 < te; t0 += TT) {
-    const bool more = t0 + TT < te;
-    gload_x(t0);  // this tile's x rows fly under phase 1
-    f32x16 accd;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accd[r] = 0.f;
-    {
-      // ---- phase 1: 12 slots
-      //   slots 0-3:  dz (32 c x 32 t), this wave's K half = [Wr | Ws]^T (A: image in LDS) x [dxo; dskip] (B: read across
-      //               the tile's rows), one k-step each;
-      //   slots 4-11: residual / skip weight gradient, rows [32 wm, +32) of [dxo; dskip] x z^T (channels [32 wn, +32)),
-      //               K = time: per 16 steps the row operand (even slot), then z = tanh x sigmoid and the product
-      float ob[2][8], sgv[2][8];
-      auto fetch1 = [&](int sI, float (&o)[8], float (&s)[8]) {
-        if (sI < 4) {
-          const int ks = 4 * kh1 + sI;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = U[16 * ks + 8 * lh + e][32 * tq1 + li];
-        } else {
-          const int G = (sI - 4) >> 1;
-          if (((sI - 4) & 1) == 0) {
-            row8(&U[32 * wm + li][16 * G + 2 * h4], o);
-          } else {
-            row8(&Gt[32 * wn + li][16 * G + 2 * h4], o);
-            row8(&Gt[C + 32 * wn + li][16 * G + 2 * h4], s);
-          }
-        }
-      };
-      u32x4 wA[2], aq;
-      auto fetchA = [&](int sI, u32x4 &w) { w = *(const lds_u4 *)(uintptr_t)(wa0 + 1024u * (unsigned)(cb1 * 8 + 4 * kh1 + sI)); };
-      fetch1(0, ob[0], sgv[0]);
-      fetchA(0, wA[0]);
-#pragma clang loop unroll(full)
-      for (int sI = 0; sI < 12; ++sI) {
-        if (sI + 1 < 12) fetch1(sI + 1, ob[(sI + 1) & 1], sgv[(sI + 1) & 1]);
-        if (sI + 1 < 4) fetchA(sI + 1, wA[(sI + 1) & 1]);
-        float (&xc)[8] = ob[sI & 1];
-        if (sI < 4) {
-          B16_MFMA(accd, wA[sI & 1], b16_pack8(xc));
-        } else if (((sI - 4) & 1) == 0) {
-          aq = b16_pack8(xc);
-        } else {
-          float zv[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) zv[e] = xc[e] * sgv[sI & 1][e];
-          B16_MFMA(accr, aq, b16_pack8(zv));
-        }
-      }
-      // the two K halves of a block meet through the P0 staging rows, each wave handing over the HALF of its partial
-      // sums the other one finishes (registers 8 (1 - kh1) .. +8)
-#pragma unroll
-      for (int r = 0; r < 8; ++r) Zx[(((2 * tq1 + cb1) * 2 + kh1) * 8 + r) * 64 + lane] = kh1 ? accd[r] : accd[8 + r];
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the x rows (and the previous tile's stores)
-    __syncthreads();  // B1: U and tanh | sigmoid have been read; the partial sums of dz are staged
-    {
-      // ---- gate derivative in place (fp32): this lane holds dz of channels 32 cb1 + acc_row(r) at t = 32 tq1 + li
-      float tv[8], sv[8], dzv[8];
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int rr = 8 * kh1 + r, c = 32 * cb1 + (rr & 3) + 8 * (rr >> 2) + h4, tc = 32 * tq1 + li;
-        tv[r] = Gt[c][tc];
-        sv[r] = Gt[C + c][tc];
-        dzv[r] = Zx[(((2 * tq1 + cb1) * 2 + (1 - kh1)) * 8 + r) * 64 + lane];
-      }
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int rr = 8 * kh1 + r, c = 32 * cb1 + (rr & 3) + 8 * (rr >> 2) + h4, tc = 32 * tq1 + li;
-        const float dz = dzv[r] + (kh1 ? accd[8 + r] : accd[r]);
-        Gt[c][tc] = dz * sv[r] * (1.0f - tv[r] * tv[r]);
-        Gt[C + c][tc] = dz * tv[r] * sv[r] * (1.0f - sv[r]);
-      }
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) *(f4 *)&U[32 * p + srow][st] = r_x[p];
-    __syncthreads();  // B2: df | dg and the x rows are staged
-    if constexpr (WRITE_DFG) {
-      // the fp32, unrounded df | dg tile for the context pass (bwd_dctx_wgctx64_kernel), columns [t_lo, te) only: the
-      // store of bwd_layer64_kernel<true>
-      const int t = t0 + st;
-      if (t >= a.t_lo && t + 3 < te) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) fb_store16(*(const f4 *)&Gt[32 * p + srow][st], dfgb, vo_t, 4 * (32 * p * a.th.ld + t0));
-      } else {
-        float *base = a.dfg.p + (size_t)b * a.dfg.sb + t;
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (t + e >= a.t_lo && t + e < te) base[(size_t)(32 * p + srow) * a.dfg.ld + e] = Gt[32 * p + srow][st + e];
-      }
-    }
-    if constexpr (GLOBAL) {
-      // the label's term: this thread's share of the rows of df | dg (fp32, unrounded), columns [t_lo, te) only.  A
-      // column outside is zero already -- its tanh, sigmoid, dxo and dskip were staged as zeros (ld4_edge), so
-      // dz = 0 and df = dg = 0 x 0 -- but the mask costs an edge tile four compares and leaves nothing to a stale value.
-      const int tg = t0 + st;
-      const bool full = t0 >= a.t_lo && t0 + TT <= te;
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        f4 v = *(const f4 *)&Gt[32 * p + srow][st];
-        if (!full) {
-          v.x = (tg >= a.t_lo && tg < te) ? v.x : 0.f;
-          v.y = (tg + 1 >= a.t_lo && tg + 1 < te) ? v.y : 0.f;
-          v.z = (tg + 2 >= a.t_lo && tg + 2 < te) ? v.z : 0.f;
-          v.w = (tg + 3 >= a.t_lo && tg + 3 < te) ? v.w : 0.f;
-        }
-        gsum[p] += (v.x + v.y) + (v.z + v.w);
-      }
-    }
-    const bool spread = more && interior(t0 + TT);
-    if (more && !spread) gload_r_edge(t0 + TT);
-    // ---- phase 2: this wave's K half of its tap's product for both 32-step blocks, and its two blocks of the
-    // filter / gate weight gradient; the next tile's loads in parts between the steps
-    f32x16 accd2[2];
-#pragma unroll
-    for (int ub = 0; ub < 2; ++ub)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) accd2[ub][r] = 0.f;
-    {
-      // 20 slots, five per 16 time steps: the weight gradient's row operand of dfg, its two x operands, then this wave's
-      // k-step of the tap product for both 32-step blocks (operand read ACROSS the tile's rows)
-      float xb[2][8];
-      auto fetch2 = [&](int sI, float (&o)[8]) {
-        const int G = sI / 5, k = sI - 5 * G;
-        if (k < 3) {
-          const float *row = k == 0 ? &Gt[32 * wm + li][0] : &U[64 * wn + 32 * (k - 1) + li][0];
-          row8(row + 16 * G + 2 * h4, o);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = Gt[64 * kh + 16 * G + 8 * lh + e][32 * (k - 3) + li];
-        }
-      };
-      u32x4 aq;
-      fetch2(0, xb[0]);
-#pragma clang loop unroll(full)
-      for (int sI = 0; sI < 20; ++sI) {
-        const int G = sI / 5, k = sI - 5 * G;
-        if (sI + 1 < 20) fetch2(sI + 1, xb[(sI + 1) & 1]);
-        if (spread && k == 0) {
-          gload_r_part(t0 + TT, G);
-          if (G == 3) gload_r_part(t0 + TT, 4);
-        }
-        const u32x4 xq = b16_pack8(xb[sI & 1]);
-        if (k == 0) {
-          aq = xq;
-        } else if (k < 3) {
-          B16_MFMA(accw[k - 1], aq, xq);
-        } else {
-          B16_MFMA(accd2[k - 3], xq, wp[G]);
-        }
-      }
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the next tile's loads, ahead of this tile's stores
-    // ---- the K halves meet in O: rows [0, 64) hold dxo (tap 1: A' = dxo + W1^T dfg), rows [64, 128) take P0
-    if (kh == 0) {
-#pragma unroll
-      for (int ub = 0; ub < 2; ++ub)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          f4 *p4 = (f4 *)&O[64 * half + 32 * wc + li][32 * ub + 8 * q + h4];
-          const f4 v = f4{accd2[ub][4 * q], accd2[ub][4 * q + 1], accd2[ub][4 * q + 2], accd2[ub][4 * q + 3]};
-          *p4 = half ? v : f4_add(*p4, v);
-        }
-    }
-    __syncthreads();  // B3: U and G have been read; the first K halves are in O
-    if (kh == 1) {
-#pragma unroll
-      for (int ub = 0; ub < 2; ++ub)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          f4 *p4 = (f4 *)&O[64 * half + 32 * wc + li][32 * ub + 8 * q + h4];
-          *p4 = f4_add(*p4, f4{accd2[ub][4 * q], accd2[ub][4 * q + 1], accd2[ub][4 * q + 2], accd2[ub][4 * q + 3]});
-        }
-    }
-    __syncthreads();  // B4
-    {
-      // whole-row float4 stores: rows srow + 32 p (A' rows, then P0 rows), columns t0 + st .. +3 inside [t_lo, te)
-      const int t = t0 + st;
-      if (t >= a.t_lo && t + 3 < te) {
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-          fb_store16(*(const f4 *)&O[32 * p + srow][st], oab, vo_t, 4 * (32 * p * a.th.ld + t0));
-          fb_store16(*(const f4 *)&O[C + 32 * p + srow][st], opb, vo_t, 4 * (32 * p * a.th.ld + t0));
-        }
-      } else {
-        float *ba = a.oa.p + (size_t)b * a.oa.sb + t, *bp = a.op.p + (size_t)b * a.op.sb + t;
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (t + e >= a.t_lo && t + e < te) {
-              ba[(size_t)(32 * p + srow) * a.oa.ld + e] = O[32 * p + srow][st + e];
-              bp[(size_t)(32 * p + srow) * a.op.ld + e] = O[C + 32 * p + srow][st + e];
-            }
-      }
-    }
-    // (a thread's lstore_r() overwrites exactly the O elements the same thread has just read; U and G were
-    // last read before B3)
-    if (more) {
-      set_zero_flags(t0 + TT, spread);
-      lstore_r();
-    }
-    __syncthreads();  // B5
-  }
-  // ---- this workgroup's slabs and bias partial sums (wgrad2_kernel's formats: 128 x 128, 128 x 64, 128)
-  {
-    int tid_e = threadIdx.x;
-    asm volatile("" : "+v"(tid_e));
-    const int lane_e = tid_e & 63, wave_e = tid_e >> 6, wm_e = wave_e >> 1, wn_e = wave_e & 1;
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = 32 * wm_e + acc_row(r, lane_e), n = 64 * wn_e + 32 * ni + (lane_e & 31);
-        fg_part[((size_t)blockIdx.x * 128 + m) * 128 + n] = accw[ni][r];
-      }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = 32 * wm_e + acc_row(r, lane_e), n = 32 * wn_e + (lane_e & 31);
-      rs_part[((size_t)blockIdx.x * 128 + m) * 64 + n] = accr[r];
-    }
-  }
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    float v = bsum[p];  // 16 lanes share a row
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    v += __shfl_xor(v, 8, 64);
-    if ((tid & 15) == 0) rs_bias_part[(size_t)blockIdx.x * 128 + (p < 2 ? 32 * p : C + 32 * (p - 2)) + srow] = v;
-  }
-  if constexpr (GLOBAL) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      float v = gsum[p];  // 16 lanes share a row
-      v += __shfl_xor(v, 1, 64);
-      v += __shfl_xor(v, 2, 64);
-      v += __shfl_xor(v, 4, 64);
-      v += __shfl_xor(v, 8, 64);
-      if ((tid & 15) == 0) g_part[(size_t)blockIdx.x * 128 + 32 * p + srow] = v;  // rows [0, 64): df, [64, 128): dg
-    }
-  }
-}
-
-// launch_bwd_layer64 for the bf16 kernel (a.dfg given: the conditioned form, which writes df | dg); same plan, same reduce.  g_part / rowsum (both or neither):
-// the GLOBAL instantiation leaves a 128-float partial of the df | dg row sums per workgroup in g_part (as many as the
-// plan's bias partials), and rowsum (batch, 128) of this layer receives their sums.
+// One layer's backward (a.dfg given: the form that writes df | dg) and the reduction of its slabs.  g_part / rowsum (both
+// or neither; bf16 only): the GLOBAL instantiation leaves a 128-float partial of the df | dg row sums per workgroup in
+// g_part (as many as the plan's bias partials), and rowsum (batch, 128) of this layer receives their sums.
 template <class RsOp, class FgOp>
-static int launch_bwd_layer64_bf16(const FusedBwdLArgs &a, const RsOp &rs, const FgOp &fg, int batch, const FusedBwdLPlan &pl,
-                                   hipStream_t s, float *g_part = nullptr, float *rowsum = nullptr) {
+static int launch_bwd_layer64(bool bf16, const FusedBwdLArgs &a, const RsOp &rs, const FgOp &fg, int batch,
+                              const FusedBwdLPlan &pl, hipStream_t s, float *g_part = nullptr, float *rowsum = nullptr) {
   if (pl.chunks <= 0) return MVN_OK;
+  const BwdLayerForm &f = BWD_LAYER_FORMS[bf16];
+  auto refuse = [&](const char *why) {
+    set_error("%s: %s", f.name, why);
+    return MVN_ERR_BAD_ARG;
+  };
   const int ldt = a.th.ld;
-  const bool wd = a.dfg.p != nullptr;
+  const bool wd = a.dfg.p != nullptr, glob = g_part != nullptr;
   if ((wd && a.dfg.ld != ldt) || a.sg.ld != ldt || a.xin.ld != ldt || a.oa.ld != ldt || a.op.ld != ldt || a.gp.ld != ldt ||
-      (a.ga.p && a.ga.ld != ldt)) {
-    set_error("bwd_layer64_bf16: the (B, ch, Tp) views must share one row pitch");
-    return MVN_ERR_BAD_ARG;
-  }
+      (a.ga.p && a.ga.ld != ldt))
+    return refuse("the (B, ch, Tp) views must share one row pitch");
+  if (glob && wd) return refuse("the label's row sums and a dfg output do not go together");
+  if (glob != (rowsum != nullptr)) return refuse("g_part and rowsum go together");
+  const void *fn = f.kernel[wd ? 1 : glob ? 2 : 0];
+  // (not reached from backward_impl: plan_backward hands out a g_part under bf16 only; it keeps a null kernel unlaunched)
+  if (!fn) return refuse("no form with the label's row sums");
   const int n = pl.chunks * batch;
-  const bool glob = g_part != nullptr;
-  if (glob && wd) {
-    set_error("bwd_layer64_bf16: the label's row sums and a dfg output do not go together");
-    return MVN_ERR_BAD_ARG;
-  }
-  if (glob != (rowsum != nullptr)) {
-    set_error("bwd_layer64_bf16: g_part and rowsum go together");
-    return MVN_ERR_BAD_ARG;
-  }
-  const void *fn = wd     ? (const void *)bwd_layer64_bf16_kernel<false, true>
-                   : glob ? (const void *)bwd_layer64_bf16_kernel<true>
-                          : (const void *)bwd_layer64_bf16_kernel<false>;
-  const int rc = ensure_max_dynamic_lds(fn, "hipFuncSetAttribute(bwd_layer64_bf16)");
+  const int rc = ensure_max_dynamic_lds(fn, f.attr_what);
   if (rc) return rc;
   void *args[] = {(void *)&a, (void *)&pl.chunks, (void *)&pl.chunk_t, (void *)&pl.bias, (void *)&pl.rs, (void *)&pl.fg,
-                  (void *)&g_part};
-  if (check_hip(hipLaunchKernel(fn, dim3(n), dim3(512), args, (size_t)FBL16_LDS_BYTES, s), "bwd_layer64_bf16"))
-    return MVN_ERR_LAUNCH;
+                  (void *)&g_part};  // (the fp32 kernels take the first six)
+  if (check_hip(hipLaunchKernel(fn, dim3(n), dim3(512), args, f.lds_bytes, s), f.name)) return MVN_ERR_LAUNCH;
   hipLaunchKernelGGL((reduce_layer64_kernel<RsOp, FgOp>), dim3(260 + 128 * 128 / 32), dim3(32 * RED_SEG), 0, s, rs, pl.rs,
                      pl.bias, n, fg, pl.fg, n);
   if (glob) {  // (a failed launch would leave the caller's zero-filled rowsum: silently zero context gradients)

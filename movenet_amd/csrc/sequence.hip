@@ -1790,8 +1790,7 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
       FusedBwdLPlan lp;  // (it fits: plan_backward asked for the first layer, and the answer is the same for every layer)
       (void)bwd_layer64_plan(pl.cus, t_lo, T, batch, pl.sc_bias.p, pl.sc_bias.floats, pl.sc_slab.p, pl.sc_slab.floats, &lp);
       // (bf16 + labels: the row sums come out of the layer kernel itself, no dfg tensor -- fused_bf16.h)
-      rc = bf16 ? launch_bwd_layer64_bf16(fa, wr, wf, batch, lp, s, pl.g_part, pl.g_part ? grow + (size_t)l * batch * 128 : nullptr)
-                : launch_bwd_layer64(fa, wr, wf, batch, lp, s);
+      rc = launch_bwd_layer64(bf16, fa, wr, wf, batch, lp, s, pl.g_part, pl.g_part ? grow + (size_t)l * batch * 128 : nullptr);
       if (rc) return rc;
       if (glob && !bf16)  // the label's term: row sums of df | dg over the layer's valid columns (global_cond.h)
         hipLaunchKernelGGL(global_rowsum_kernel, dim3(32, batch), dim3(256), 0, s, bwd->dfg, (long long)2 * C * g.Tp, g.Tp,
