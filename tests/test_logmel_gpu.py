@@ -3,7 +3,8 @@
 The error is taken on the mel ENERGIES, per frame, as max_m |E - E64| / max_m E64.  The yardstick is the same
 expression evaluated in fp32 on the CPU by torch matmul (a direct DFT with the same fp32 tables: the same algorithm
 class); the kernel may be at most 4 x as far from float64 as the yardstick is -- the 4 allows for another order of an
-N-term fp32 sum and says nothing about the kernel.  Measured (yardstick / kernel, worst frame): see DESIGN 4.5d."""
+N-term fp32 sum and says nothing about the kernel.  Measured (yardstick / kernel, worst frame): see DESIGN 4.5d.
+Where a frame lands (which frame tile, which workgroup) is also held to the bit, by translating the clip."""
 import functools
 
 import numpy as np
@@ -17,7 +18,15 @@ from movenet_amd import ops
 
 pytestmark = pytest.mark.gpu
 Q = 256
+kTile = 32   # frames per workgroup of lm_dft_kernel
 SHAPES = [(3, 100, 64, 16, 8), (2, 1000, 256, 64, 20), (1, 17, 64, 64, 3), (2, 2048, 1024, 256, 80)]
+# More than one frame tile of lm_dft_kernel (32 frames) and more than one workgroup of lm_mel_kernel (64 frames):
+SHAPES += [
+    (2, 1100, 64, 16, 8),       # F = 69: three frame tiles, the last with 5 live frames; two lm_mel workgroups
+    (1, 1008, 64, 16, 5),       # F = 64 = p_ld: every tile full
+    (1, 1024, 64, 16, 5),       # F = 65: one frame into a third tile and into a second lm_mel workgroup
+    (1, 8448, 1024, 256, 80),   # F = 34 at the production n_fft, hop and M: two frame tiles, 17 bin tiles
+]
 
 
 def _indices(B, T, seed):
@@ -101,6 +110,30 @@ def test_energies_and_log_against_float64(shape):
     # ... and through the Python entry point, cached tables and all
     via = ops.logmel(torch.from_numpy(idx).to(DEV), Q, n_fft, hop, fbank)
     assert tuple(via.shape) == (B, M, F) and torch.equal(via.cpu(), lg[:, :, :F])
+
+
+def test_a_frame_tile_is_a_translation_of_tile_0_to_the_bit():
+    """n_fft 64, hop 16, T = 1600 (F = 101, four frame tiles): clip b is clip a moved right by 512 samples = 32 hops =
+    one frame tile.  Frame j + 32 of b then has the operands of frame j of a on the same lane (j & 31) of the same waves,
+    and lm_mel_kernel's sum per frame knows no position: the same bits, no tolerance."""
+    B, T, n_fft, hop, M, shift = 2, 1600, 64, 16, 8, 512
+    assert shift == kTile * hop
+    idx_a = _indices(B, T, 1600)
+    idx_b = np.concatenate([_indices(B, shift, 512), idx_a[:, :T - shift]], axis=1)
+    assert idx_b.shape == idx_a.shape and not np.array_equal(idx_b[:, :shift], idx_a[:, :shift])
+    fbank = R.mel_filterbank(M, n_fft, 16000.0, 0.0, 8000.0)
+    F = T // hop + 1
+    # frames of a whose window [16 j - 32, 16 j + 32) lies inside [0, T - 512)
+    js = np.array([j for j in range(F) if j * hop - n_fft // 2 >= 0 and j * hop + n_fft // 2 <= T - shift])
+    assert js[0] == 2 and js[-1] == 66 and len(js) >= 60
+    to = js + kTile
+    assert to[-1] < F and {int(t) // kTile for t in to} == {1, 2, 3}
+    for energies in (True, False):
+        a = _call(idx_a, n_fft, hop, fbank, energies=energies)[:, :, :F]
+        b = _call(idx_b, n_fft, hop, fbank, energies=energies)[:, :, :F]
+        assert bool(torch.isfinite(a).all()) and bool(torch.isfinite(b).all())
+        assert torch.equal(b[:, :, to], a[:, :, js]), "a frame tile is not a translation of tile 0"
+        assert not torch.equal(b[:, :, js], a[:, :, js])   # (b is another clip, not the same one)
 
 
 def test_sine_on_a_bin_lands_in_its_band():
