@@ -113,207 +113,44 @@ __device__ __forceinline__ void fb16_product(f32x16 (&acc)[4], unsigned wa, BV b
   }
 }
 
-// CTX (mvn_forward_bf16_ctx; never together with GLOBAL): the conditioned layer -- K = 192, the context as k-steps 8..11 of
+// ----------------------------------------------------------------------------------------
+// The forward STRIP layer kernels: one scaffold (csrc/fwd_layer64s_body.inc), included behind each kernel's parameter
+// list under the kernel's product policy FS_FORM.  They stand together here because this header sees every policy's
+// helpers.  As with the backward (fused_bwd_l.h), the body is TEXT, not a function the kernels call.
+// ----------------------------------------------------------------------------------------
+// fp32 MFMAs (fused_fwd.h; MOVENET_HIP_FORWARD_MFMA=f32, or a context with no room for the ctxw2 images).  HAS_CTX: the
+// context is a third K block of the first product, in the registers that otherwise fetch x(t) a strip ahead.
+#define FS_FORM FS_FORM_F32
+template <bool HAS_CTX>
+__global__ __launch_bounds__(512, 1) void fused_layer64s_kernel(FusedFwdPArgs a, int chunks_per_b, int chunk_t)
+#include "fwd_layer64s_body.inc"
+#undef FS_FORM
+
+// bf16 x 3 (fused_fwd_bf3.h).  GLOBAL (global conditioning): a label is constant in time, so its context
+// term is ONE 2C-vector per (layer, sequence), gbias = [Wcf e_b + bcf | Wcg e_b + bcg] (global_cond.h:
+// global_bias_kernel); the instantiation keeps it in 128 floats of LDS behind br | bs and adds it to the f | g
+// pre-activations in front of tanh / sigmoid.
+#define FS_FORM FS_FORM_BF3
+template <bool GLOBAL>
+__global__ __launch_bounds__(512, 1) void fused_layer64s_bf3_kernel(FusedFwdPArgs a, int chunks_per_b, int chunk_t)
+#include "fwd_layer64s_body.inc"
+#undef FS_FORM
+
+// the conditioned layer with x(t - d) and the second product as planes (fused_fwd_bf3.h: fsc_pack_kernel's image)
+#define FS_FORM FS_FORM_CTXW2
+__global__ __launch_bounds__(512, 1) void fused_layer64s_ctxw2_kernel(FusedFwdPArgs a, int chunks_per_b, int chunk_t)
+#include "fwd_layer64s_body.inc"
+#undef FS_FORM
+
+// one bf16 plane.  GLOBAL: the f | g accumulators start from the label's vector (the head of this file).  CTX
+// (mvn_forward_bf16_ctx; never together with GLOBAL): the conditioned layer -- K = 192, the context as k-steps 8..11 of
 // a 12-k-step image, the accumulators started from bcf | bcg (one vector for all sequences).
+#define FS_FORM FS_FORM_BF16
 template <bool GLOBAL, bool CTX = false>
-__global__ __launch_bounds__(512, 1) void fused_layer64s_bf16_kernel(FusedFwdPArgs a, int chunks_per_b, int chunk_t) {
-  static_assert(!(GLOBAL && CTX), "the label's bias form and the context form are separate kernels");
-  extern __shared__ __attribute__((aligned(16))) unsigned char fb16_lds[];
-  constexpr int W1_BYTES = CTX ? FB16C_W1_BYTES : FB16_W1_BYTES, LDS_BYTES = CTX ? FB16C_LDS_BYTES : FB16_LDS_BYTES;
-  constexpr int NKS1 = CTX ? 12 : 8;
-  // br | bs (GLOBAL: | gb f rows | gb g rows; CTX: | bcf | bcg)
-  const float *BI = (const float *)(fb16_lds + W1_BYTES + FB16_W2_BYTES);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x / chunks_per_b, ch = blockIdx.x - b * chunks_per_b;
-  const int li = lane & 31, lh = lane >> 5;
-  const int tb = (a.t_begin & ~TILE_ALIGN) + ch * chunk_t, te = min(a.t_end, tb + chunk_t);
-  const int skip_lo = max(a.t_begin, a.t_skip0);
-  // ---- weights into LDS: the image fb16_pack_kernel wrote once per forward call (a linear copy), or converted here
-  if (a.wpack) {
-    typedef float f4_ __attribute__((ext_vector_type(4)));
-    constexpr int N16 = LDS_BYTES / 16, PER = (N16 + 511) / 512;
-    const f4_ *src = (const f4_ *)a.wpack;
-    f4_ v[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int at = tid + 512 * i;
-      if (at < N16) v[i] = src[at];
-    }
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int at = tid + 512 * i;
-      if (at < N16) ((f4_ *)fb16_lds)[at] = v[i];
-    }
-  } else if constexpr (CTX) {
-    fb16c_stage_weights(fb16_lds, a.wf, a.wg, a.wr, a.ws, a.br, a.bs, a.wcf, a.wcg, a.bcf, a.bcg, tid, 512);
-  } else {
-    fb16_stage_weights(fb16_lds, a.wf, a.wg, a.wr, a.ws, a.br, a.bs, tid, 512);
-  }
-  if constexpr (GLOBAL) {
-    if (tid < 128) ((float *)fb16_lds)[FB16_PACK_F + tid] = a.gbias[(size_t)b * 128 + tid];  // (this sequence's f | g rows)
-  }
-  __syncthreads();
-  const unsigned w1a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)fb16_lds + 16u * lane;
-  const unsigned w2a = w1a + (unsigned)W1_BYTES;
-  const int cbase = 4 * lh;
+__global__ __launch_bounds__(512, 1) void fused_layer64s_bf16_kernel(FusedFwdPArgs a, int chunks_per_b, int chunk_t)
+#include "fwd_layer64s_body.inc"
+#undef FS_FORM
 
-  constexpr int RSRC = 0x00020000;  // raw buffer, 32-bit data format (gfx9)
-  const __amdgpu_buffer_rsrc_t xb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.xin.p + (size_t)b * a.xin.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t thb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.th.p + (size_t)b * a.th.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t sgb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.sg.p + (size_t)b * a.sg.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t xob = __builtin_amdgcn_make_buffer_rsrc((void *)(a.xout.p + (size_t)b * a.xout.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t skb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.skip.p + (size_t)b * a.skip.sb - a.t_base), 0, 0x7FFFFFFF, RSRC);
-  const bool save = a.th.p != nullptr, has_out = a.xout.p != nullptr;
-  int xld4 = 4 * a.xin.ld, thld4 = 4 * a.th.ld, xold4 = 4 * a.xout.ld, skld4 = 4 * a.skip.ld;
-  // CTX: the context (B, C, ctx_ld), column t = time t, read like the x(t) block (its own row pitch)
-  [[maybe_unused]] __amdgpu_buffer_rsrc_t cxb;
-  [[maybe_unused]] int cxld4 = 0;
-  if constexpr (CTX) {
-    cxb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.ctx.p + (size_t)b * a.ctx.sb), 0, 0x7FFFFFFF, RSRC);
-    cxld4 = 4 * a.ctx.ld;
-  }
-
-  // (the strip schedule of fused_layer64s_bf3_kernel: x(t) one strip ahead, x(t - d) at the top of the strip, the skip
-  // accumulator's old values under the second product; lanes that must not store carry an offset past the resource)
-  auto column = [&](int t0_, bool &live_, int &tc_) {
-    const int t_ = t0_ + li;
-    live_ = t_ >= a.t_begin && t_ < te;
-    tc_ = live_ ? t_ : a.t_begin;  // (clamped: dead lanes read a valid column, zeroed afterwards)
-  };
-  float xb1[32];  // x(t) of the current strip: B operand of k-steps 0..3, residual input
-  {
-    bool lv;
-    int tcc;
-    column(tb + 32 * wave, lv, tcc);
-    const int o1 = 4 * (cbase * a.xin.ld + tcc);
-    FS_FENCE(xld4);
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      const float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, o1, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
-      xb1[j] = lv ? v : 0.f;
-    }
-  }
-
-  constexpr int FS_OOB = (int)0x80000000;
-  for (int t0 = tb + 32 * wave; t0 < te; t0 += 32 * 8) {
-    const int t = t0 + li;
-    bool live;
-    int tc;
-    column(t0, live, tc);
-    const bool skip_live = t >= skip_lo && t < te;
-    const int ox0 = 4 * (cbase * a.xin.ld + tc - a.d);
-    const int oth = (save && live) ? 4 * (cbase * a.th.ld + tc) : FS_OOB, oxo = 4 * (cbase * a.xout.ld + tc);
-    const int osk = 4 * (cbase * a.skip.ld + (skip_live ? t : skip_lo));
-    float xn1[32];  // x(t) of the NEXT strip
-    float xa0[32];  // x(t - d): B operand of k-steps 4..7; later the skip accumulator's old values
-    FS_FENCE(xld4);
-#pragma unroll
-    for (int j = 0; j < 32; ++j)
-      xa0[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, ox0, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
-    if (!(t0 >= a.t_begin && t0 + 32 <= te)) {
-#pragma unroll
-      for (int j = 0; j < 32; ++j) xa0[j] = live ? xa0[j] : 0.f;
-    }
-    // CTX: ctx(t) of this strip, B operand of k-steps 8..11 (requested with x(t - d), consumed in a phase of its own
-    // behind the audio product: the three operand blocks are never all live in bf16 form at once)
-    [[maybe_unused]] float xc[CTX ? 32 : 1];
-    if constexpr (CTX) {
-      const int oc = 4 * (cbase * a.ctx.ld + tc);
-      FS_FENCE(cxld4);
-#pragma unroll
-      for (int j = 0; j < 32; ++j)
-        xc[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(cxb, oc, ((j & 3) + 8 * (j >> 2)) * cxld4, 0));
-      if (!(t0 >= a.t_begin && t0 + 32 <= te)) {
-#pragma unroll
-        for (int j = 0; j < 32; ++j) xc[j] = live ? xc[j] : 0.f;
-      }
-    }
-    // ---- f | g: four 32 x 32 blocks (f c<32, f c>=32, g c<32, g c>=32), K = 128 = 8 k-steps, the x(t) half first
-    f32x16 acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if constexpr (GLOBAL || CTX)  // accumulator row = channel (r & 3) + 8 (r >> 2) + 4 lh of block i, the same in every lane
-          acc[i][r] = BI[128 + 32 * i + (r & 3) + 8 * (r >> 2) + cbase];
-        else
-          acc[i][r] = 0.f;
-      }
-    fb16_product<8, NKS1>(acc, w1a, [&](int ks, int e) { return ks < 4 ? xb1[8 * ks + e] : xa0[8 * (ks - 4) + e]; });
-    if constexpr (CTX) fb16_product<4, NKS1, 8>(acc, w1a, [&](int ks, int e) { return xc[8 * ks + e]; });
-    // ---- gate in registers (fp32); tanh / sigmoid leave; z in accumulator order = the next B operand
-    float z[32];
-    FS_FENCE(thld4);
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float tv = tanh_fast(acc[h][r]);
-        const float sv = sigmoid_fast(acc[2 + h][r]);
-        z[16 * h + r] = tv * sv;
-        const int c0 = 32 * h + (r & 3) + 8 * (r >> 2);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(tv), thb, oth, c0 * thld4, FS_AUX_SAVE);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sv), sgb, oth, c0 * thld4, FS_AUX_SAVE);
-      }
-    FS_FENCE(skld4);
-    if (!a.first_layer) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          xa0[16 * h + r] = __uint_as_float(
-              __builtin_amdgcn_raw_buffer_load_b32(skb, osk, (32 * h + (r & 3) + 8 * (r >> 2)) * skld4, 0));
-    }
-    if (t0 + 32 * 8 < te) {
-      bool lv;
-      int tcc;
-      column(t0 + 32 * 8, lv, tcc);
-      const int o1 = 4 * (cbase * a.xin.ld + tcc);
-      FS_FENCE(xld4);
-#pragma unroll
-      for (int j = 0; j < 32; ++j)
-        xn1[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, o1, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
-      if (!(t0 + 32 * 8 >= a.t_begin && t0 + 32 * 8 + 32 <= te)) {
-#pragma unroll
-        for (int j = 0; j < 32; ++j) xn1[j] = lv ? xn1[j] : 0.f;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 32; ++j) xn1[j] = 0.f;
-    }
-    // ---- residual | skip: four blocks (res c<32, res c>=32, skip k<32, skip k>=32), K = 64 = 4 k-steps
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    fb16_product<4>(acc, w2a, [&](int ks, int e) { return z[8 * ks + e]; });
-    // ---- x' = (y + br) + x(t); skip (+)= y + bs, columns t - t_base, live from skip_lo
-    FS_FENCE(xold4);
-    FS_FENCE(skld4);
-    {
-      const int oxo_m = (has_out && live) ? oxo : FS_OOB, osk_m = skip_live ? osk : FS_OOB;
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int c0 = 32 * h + (r & 3) + 8 * (r >> 2);
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((acc[h][r] + BI[c0 + cbase]) + xb1[16 * h + r]), xob, oxo_m,
-                                                c0 * xold4, 0);
-        }
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int k0 = 32 * h + (r & 3) + 8 * (r >> 2);
-          const float v = acc[2 + h][r] + BI[64 + k0 + cbase];
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a.first_layer ? v : xa0[16 * h + r] + v), skb, osk_m, k0 * skld4, 0);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 32; ++j) xb1[j] = xn1[j];
-  }
-}
 
 // ----------------------------------------------------------------------------------------
 // The forward's layer forms, one row each: what a launch needs besides the layer's arguments.  (The table stands here

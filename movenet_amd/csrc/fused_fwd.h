@@ -309,253 +309,39 @@ __global__ __launch_bounds__(256, 2) void fused_layer64p_kernel(FusedFwdPArgs a,
 // 128-byte row segment a store instruction writes is ONE cache line, not two halves: 148.6 -> 142.4 us
 // per layer), and tanh / sigmoid -- written once, read by the backward pass much later -- leave with
 // the non-temporal hint (-> 135.8 us; on x' and the skip sums, which the next layer reads, it costs 5 us).
+//
+// Where the text lives: the strip scaffold is written once, csrc/fwd_layer64s_body.inc, and is the body of
+// fused_layer64s_kernel<HAS_CTX> (the fp32-MFMA form described here) and of its siblings -- bf16 x 3
+// (fused_fwd_bf3.h), one bf16 plane (fused_bf16.h).  The kernels' signatures stand together in fused_bf16.h,
+// in front of the LAYER_FORMS table, where every policy's helpers are in sight.  This header holds what
+// the body shares with the dense strip kernels.
 constexpr int FS_AUX_SAVE = 2;  // nt
-template <bool HAS_CTX>
-__global__ __launch_bounds__(512, 1) void fused_layer64s_kernel(FusedFwdPArgs a, int chunks_per_b, int chunk_t) {
-  constexpr int C = 64, NK1 = HAS_CTX ? 24 : 16, W1_F = 4 * NK1 * 256;
-  extern __shared__ __attribute__((aligned(16))) float fs_lds[];
-  float *W1 = fs_lds, *W2 = fs_lds + W1_F, *BI = fs_lds + W1_F + 8192;  // BI: br | bs | bcf | bcg
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x / chunks_per_b, ch = blockIdx.x - b * chunks_per_b;
-  const int li = lane & 31, lh = lane >> 5;
-  const int tb = (a.t_begin & ~TILE_ALIGN) + ch * chunk_t, te = min(a.t_end, tb + chunk_t);
-  const int skip_lo = max(a.t_begin, a.t_skip0);
-  // ---- weights into LDS: [block][k-step / 4][lane][k-step % 4].  The loop runs over the SOURCE
-  // elements (coalesced reads of the (out, in, tap) / (out, in) tensors) and scatters into LDS.
-  for (int sI = tid; sI < 2 * 8192; sI += 512) {
-    const int g = sI >> 13, r = sI & 8191;        // g: 0 filter, 1 gate
-    const int tap = r & 1, kc = (r >> 1) & 63, cm = r >> 7;
-    const int lhs = (kc >> 2) & 1, j = (kc & 3) + 4 * (kc >> 3), kk = j + 32 * tap;
-    const int blk = 2 * g + (cm >> 5), ln = (cm & 31) + 32 * lhs;
-    W1[((blk * NK1 + (kk >> 2)) * 64 + ln) * 4 + (kk & 3)] = (g ? a.wg : a.wf)[r];
-  }
-  if (HAS_CTX) {
-    for (int sI = tid; sI < 2 * 4096; sI += 512) {
-      const int g = sI >> 12, r = sI & 4095;      // g: 0 filter, 1 gate context conv
-      const int kc = r & 63, cm = r >> 6;
-      const int lhs = (kc >> 2) & 1, kk = 64 + (kc & 3) + 4 * (kc >> 3);
-      const int blk = 2 * g + (cm >> 5), ln = (cm & 31) + 32 * lhs;
-      W1[((blk * NK1 + (kk >> 2)) * 64 + ln) * 4 + (kk & 3)] = (g ? a.wcg : a.wcf)[r];
-    }
-    if (tid < 128) BI[128 + tid] = tid < 64 ? a.bcf[tid] : a.bcg[tid - 64];
-  }
-  for (int sI = tid; sI < 2 * 4096; sI += 512) {
-    const int g = sI >> 12, r = sI & 4095;        // g: 0 residual, 1 skip
-    const int kc = r & 63, m2 = r >> 6;
-    const int lhs = (kc >> 2) & 1, kk = (kc & 3) + 4 * (kc >> 3);
-    const int blk = 2 * g + (m2 >> 5), ln = (m2 & 31) + 32 * lhs;
-    W2[((blk * 8 + (kk >> 2)) * 64 + ln) * 4 + (kk & 3)] = (g ? a.ws : a.wr)[r];
-  }
-  if (tid < 128) BI[tid] = tid < 64 ? a.br[tid] : a.bs[tid - 64];
-  __syncthreads();
-  const unsigned w1a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float *)W1 + 16u * lane;
-  const unsigned w2a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float *)W2 + 16u * lane;
-  typedef float fsv4 __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(3))) fsv4 lds_v4;
-  // channel of accumulator register r of block h in this lane: 32 h + (r & 3) + 8 (r >> 2) + 4 lh
-  const int cbase = 4 * lh;
+#define FS_FENCE(x) asm volatile("" : "+s"(x))  // (a row pitch `ld`: its row * ld products are re-formed behind it)
+// the product policies of fwd_layer64s_body.inc (FS_FORM)
+#define FS_FORM_F32 0
+#define FS_FORM_BF3 1
+#define FS_FORM_BF16 2
+#define FS_FORM_CTXW2 3
 
-  // Every global access below is a raw BUFFER access: (a resource per tensor and sequence:
-  // four scalar registers) + (row * ld: one scalar offset) + (one of five per-lane byte offsets).
-  // Formed as 64-bit vector addresses the ~290 accesses of a strip spilled 443 registers; as
-  // scalar row pointers + vector offsets they still cost a 64-bit vector add each and spilled the
-  // scalar file (130 v_writelane / v_readlane per strip).
-  constexpr int RSRC = 0x00020000;  // raw buffer, 32-bit data format (gfx9)
-  const __amdgpu_buffer_rsrc_t xb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.xin.p + (size_t)b * a.xin.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t thb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.th.p + (size_t)b * a.th.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t sgb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.sg.p + (size_t)b * a.sg.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t xob = __builtin_amdgcn_make_buffer_rsrc((void *)(a.xout.p + (size_t)b * a.xout.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t skb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.skip.p + (size_t)b * a.skip.sb - a.t_base), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t cb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.ctx.p + (size_t)b * a.ctx.sb), 0, 0x7FFFFFFF, RSRC);
-  constexpr bool st_ok = true;
-  const bool save = st_ok && a.th.p != nullptr, has_out = st_ok && a.xout.p != nullptr;
-  int xld4 = 4 * a.xin.ld, thld4 = 4 * a.th.ld, xold4 = 4 * a.xout.ld, skld4 = 4 * a.skip.ld, cld4 = 4 * a.ctx.ld;
-  // (row offsets = row * ld are re-formed where they are used, behind a fence on ld: hoisted out of
-  // the strip loop the ~120 products filled the scalar file and were spilled to vector lanes)
-#define FS_FENCE(x) asm volatile("" : "+s"(x))
-
-  // x(t) of a strip (the tap-1 half of the input, 32 registers) is fetched one strip AHEAD, under
-  // the second product of the strip before; the first product consumes it first, which gives the
-  // x(t - d) half, requested at the top of the strip, 128 MFMAs to arrive.  (Without it the wave
-  // counters showed 51 % of the wave cycles waiting for memory: a wave that issues MFMAs back to
-  // back starves the other wave of its SIMD, so the two fall into step and wait together.)
-  auto column = [&](int t0_, bool &live_, int &tc_) {
-    const int t_ = t0_ + li;
-    live_ = t_ >= a.t_begin && t_ < te;
-    tc_ = live_ ? t_ : a.t_begin;  // (clamped: dead lanes read a valid column, zeroed afterwards)
-  };
-  float xb1[32];  // x(t) of the current strip: B operand of k-steps 32..63, residual input
-  if (!HAS_CTX) {
-    bool lv;
-    int tcc;
-    column(tb + 32 * wave, lv, tcc);
-    const int o1 = 4 * (cbase * a.xin.ld + tcc);
-    FS_FENCE(xld4);
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      const float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, o1, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
-      xb1[j] = lv ? v : 0.f;
-    }
+// A packed weight image (BYTES of it, from `src_`) into the LDS array `lds_` by the workgroup's 512 threads (reads
+// `tid`), linearly: every load is in flight before the first store.  Text, not a function: as a __forceinline__
+// function the partly filled last vector came out zero-filled in front of its masked load (four v_mov per copy) and
+// the loads took other registers -- other instructions in every kernel that copies an image.
+#define LDS_IMAGE_COPY(lds_, src_, BYTES)                                   \
+  {                                                                         \
+    typedef float f4_ __attribute__((ext_vector_type(4)));                  \
+    constexpr int N16 = (BYTES) / 16, PER = (N16 + 511) / 512;              \
+    const f4_ *src = (const f4_ *)(src_);                                   \
+    f4_ v[PER];                                                             \
+    _Pragma("unroll") for (int i = 0; i < PER; ++i) {                       \
+      const int at = tid + 512 * i;                                         \
+      if (at < N16) v[i] = src[at];                                         \
+    }                                                                       \
+    _Pragma("unroll") for (int i = 0; i < PER; ++i) {                       \
+      const int at = tid + 512 * i;                                         \
+      if (at < N16) ((f4_ *)(lds_))[at] = v[i];                             \
+    }                                                                       \
   }
-
-  // Lanes that must not store (columns outside [t_begin, te), no output tensor) carry an offset
-  // beyond the buffer's num_records: the hardware drops the access -- no exec-mask branch per store.
-  // (Tried: holding a strip's x' and skip sums in registers until after the next strip's first
-  // product, so that no wait on a prefetched load sits right behind 64 fresh stores -- on gfx9 loads
-  // and stores retire through one in-order counter and the compiler's wait at the loop edge was
-  // vmcnt(0).  Measured 131.4 against 131.9 us per layer: the second wave of the SIMD covers it.)
-  constexpr int FS_OOB = (int)0x80000000;
-  for (int t0 = tb + 32 * wave; t0 < te; t0 += 32 * 8) {
-    const int t = t0 + li;
-    bool live;
-    int tc;
-    column(t0, live, tc);
-    const bool skip_live = st_ok && t >= skip_lo && t < te;
-    // per-lane byte offsets (channel part 4 lh of the row + the column)
-    const int ox0 = 4 * (cbase * a.xin.ld + tc - a.d);
-    const int oth = (save && live) ? 4 * (cbase * a.th.ld + tc) : FS_OOB, oxo = 4 * (cbase * a.xout.ld + tc);
-    const int osk = 4 * (cbase * a.skip.ld + (skip_live ? t : skip_lo));
-    float xn1[32];  // without context: x(t) of the NEXT strip; with: ctx(t) of this one (k-steps 64..95)
-    if (HAS_CTX) {
-      const int o1 = 4 * (cbase * a.xin.ld + tc), oc = 4 * (cbase * a.ctx.ld + tc);
-      FS_FENCE(xld4);
-      FS_FENCE(cld4);
-#pragma unroll
-      for (int j = 0; j < 32; ++j) {
-        const float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, o1, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
-        xb1[j] = live ? v : 0.f;
-      }
-#pragma unroll
-      for (int j = 0; j < 32; ++j) {
-        const float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(cb, oc, ((j & 3) + 8 * (j >> 2)) * cld4, 0));
-        xn1[j] = live ? v : 0.f;
-      }
-    }
-    // ---- x(t - d) of channel kc(j) + 4 lh: B operand of k-steps 0..31; later the skip accumulator's old values
-    float xa0[32];
-    FS_FENCE(xld4);
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      const float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, ox0, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
-      xa0[j] = v;
-    }
-    // (interior strips -- wave-uniform test -- need no masking: 32 selects less per strip)
-    if (!(t0 >= a.t_begin && t0 + 32 <= te)) {
-#pragma unroll
-      for (int j = 0; j < 32; ++j) xa0[j] = live ? xa0[j] : 0.f;
-    }
-    // ---- f | g: four 32 x 32 blocks (f c<32, f c>=32, g c<32, g c>=32), K = 128, the x(t) half first
-    f32x16 acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-#pragma unroll
-    for (int kq = 0; kq < NK1; ++kq) {
-      const int k4 = kq < 8 ? 8 + kq : kq < 16 ? kq - 8 : kq;  // x(t), x(t - d), context
-      fsv4 aw[4];
-#pragma unroll
-      for (int blk = 0; blk < 4; ++blk) aw[blk] = *(const lds_v4 *)(uintptr_t)(w1a + 4u * (unsigned)((blk * NK1 + k4) * 256));
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int blk = 0; blk < 4; ++blk)
-          acc[blk] = __builtin_amdgcn_mfma_f32_32x32x2f32(
-              aw[blk][e], k4 >= 16 ? xn1[4 * (k4 - 16) + e] : k4 >= 8 ? xb1[4 * (k4 - 8) + e] : xa0[4 * k4 + e], acc[blk], 0, 0, 0);
-    }
-    // ---- gate in registers; tanh / sigmoid leave; z in accumulator order = the next B operand
-    float z[32];
-    FS_FENCE(thld4);
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int cg_ = 32 * h + (r & 3) + 8 * (r >> 2) + cbase;
-        const float tv = tanh_fast(HAS_CTX ? acc[h][r] + BI[128 + cg_] : acc[h][r]);
-        const float sv = sigmoid_fast(HAS_CTX ? acc[2 + h][r] + BI[192 + cg_] : acc[2 + h][r]);
-        z[16 * h + r] = tv * sv;
-        const int c0 = 32 * h + (r & 3) + 8 * (r >> 2);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(tv), thb, oth, c0 * thld4, FS_AUX_SAVE);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sv), sgb, oth, c0 * thld4, FS_AUX_SAVE);
-      }
-    // the skip accumulator's old values, into the x(t - d) registers (dead now), and the NEXT strip's
-    // x(t), both under the MFMAs below
-    FS_FENCE(skld4);
-    if (!a.first_layer) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          xa0[16 * h + r] = __uint_as_float(
-              __builtin_amdgcn_raw_buffer_load_b32(skb, osk, (32 * h + (r & 3) + 8 * (r >> 2)) * skld4, 0));
-    }
-    const bool more = !HAS_CTX && t0 + 32 * 8 < te;
-    if (HAS_CTX) {
-    } else if (more) {
-      bool lv;
-      int tcc;
-      column(t0 + 32 * 8, lv, tcc);
-      const int o1 = 4 * (cbase * a.xin.ld + tcc);
-      FS_FENCE(xld4);
-#pragma unroll
-      for (int j = 0; j < 32; ++j) {
-        const float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, o1, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
-        xn1[j] = v;
-      }
-      if (!(t0 + 32 * 8 >= a.t_begin && t0 + 32 * 8 + 32 <= te)) {
-#pragma unroll
-        for (int j = 0; j < 32; ++j) xn1[j] = lv ? xn1[j] : 0.f;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 32; ++j) xn1[j] = 0.f;
-    }
-    // ---- residual | skip: four blocks (res c<32, res c>=32, skip k<32, skip k>=32), K = 64
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-#pragma unroll
-    for (int k4 = 0; k4 < 8; ++k4) {
-      fsv4 aw[4];
-#pragma unroll
-      for (int blk = 0; blk < 4; ++blk) aw[blk] = *(const lds_v4 *)(uintptr_t)(w2a + 4u * (unsigned)((blk * 8 + k4) * 256));
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int blk = 0; blk < 4; ++blk)
-          acc[blk] = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[blk][e], z[4 * k4 + e], acc[blk], 0, 0, 0);
-    }
-    // ---- x' = (y + br) + x(t): x(t) of this lane's channel is input register 32 + 16 h + r;
-    // skip (+)= y + bs, columns t - t_base, live from skip_lo
-    FS_FENCE(xold4);
-    FS_FENCE(skld4);
-    {
-      const int oxo_m = (has_out && live) ? oxo : FS_OOB, osk_m = skip_live ? osk : FS_OOB;
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int c0 = 32 * h + (r & 3) + 8 * (r >> 2);
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((acc[h][r] + BI[c0 + cbase]) + xb1[16 * h + r]), xob, oxo_m,
-                                                c0 * xold4, 0);
-        }
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int k0 = 32 * h + (r & 3) + 8 * (r >> 2);
-          const float v = acc[2 + h][r] + BI[64 + k0 + cbase];
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a.first_layer ? v : xa0[16 * h + r] + v), skb, osk_m, k0 * skld4, 0);
-        }
-    }
-    if (!HAS_CTX) {
-#pragma unroll
-      for (int j = 0; j < 32; ++j) xb1[j] = xn1[j];
-    }
-  }
-}
 
 // ----------------------------------------------------------------------------------------
 // The strip form for the head's 1x1 convs with 64 x 256 weights (conv1 forward: 64 -> 256 rows,

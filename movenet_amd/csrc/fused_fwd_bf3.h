@@ -159,212 +159,8 @@ __global__ __launch_bounds__(256) void fs3_pack_kernel(Fs3PackArgs p, float *dst
   fs3_stage_weights((unsigned char *)(dst + (size_t)l * FS3_PACK_F), p.wf[l], p.wg[l], p.wr[l], p.ws[l], p.br[l], p.bs[l],
                     blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
 }
-
-// GLOBAL (global conditioning): a label is constant in time, so its context term is ONE 2C-vector per
-// (layer, sequence), gbias = [Wcf e_b + bcf | Wcg e_b + bcg] (global_cond.h: global_bias_kernel); the instantiation
-// keeps it in 128 floats of LDS behind br | bs and adds it to the f | g pre-activations in front of tanh / sigmoid.
-// GLOBAL = false is the audio-only kernel as it was: every added line sits under `if constexpr (GLOBAL)`.
-template <bool GLOBAL>
-__global__ __launch_bounds__(512, 1) void fused_layer64s_bf3_kernel(FusedFwdPArgs a, int chunks_per_b, int chunk_t) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char fs3_lds[];
-  unsigned short *W1 = (unsigned short *)fs3_lds;                     // [4 blocks][8 k-steps][3 planes][64 lanes][8]
-  unsigned short *W2 = (unsigned short *)(fs3_lds + FS3_W1_BYTES);    // [4 blocks][4 k-steps][3 planes][64 lanes][8]
-  float *BI = (float *)(fs3_lds + FS3_W1_BYTES + FS3_W2_BYTES);      // br | bs
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x / chunks_per_b, ch = blockIdx.x - b * chunks_per_b;
-  const int li = lane & 31, lh = lane >> 5;
-  const int tb = (a.t_begin & ~TILE_ALIGN) + ch * chunk_t, te = min(a.t_end, tb + chunk_t);
-  const int skip_lo = max(a.t_begin, a.t_skip0);
-  // ---- weights into LDS: the image fs3_pack_kernel wrote once per forward call (a linear 144 KB copy, every load
-  // in flight before the first store), or, without one, converted here (17 us per launch: 48 dependent
-  // global load -> split -> three 2-byte LDS stores per thread; timing build 26)
-  if (a.wpack) {
-    typedef float f4_ __attribute__((ext_vector_type(4)));
-    constexpr int N16 = FS3_LDS_BYTES / 16, PER = (N16 + 511) / 512;
-    const f4_ *src = (const f4_ *)a.wpack;
-    f4_ v[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int at = tid + 512 * i;
-      if (at < N16) v[i] = src[at];
-    }
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int at = tid + 512 * i;
-      if (at < N16) ((f4_ *)fs3_lds)[at] = v[i];
-    }
-  } else {
-    fs3_stage_weights(fs3_lds, a.wf, a.wg, a.wr, a.ws, a.br, a.bs, tid, 512);
-  }
-  if constexpr (GLOBAL) {
-    if (tid < 128) BI[128 + tid] = a.gbias[(size_t)b * 128 + tid];  // (f rows | g rows of this sequence)
-  }
-  __syncthreads();
-  const unsigned w1a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)fs3_lds + 16u * lane;
-  // (two base registers per matrix: every plane is then within a ds_read's 16-bit offset of one of them)
-  unsigned w1b = w1a + 2u * 8u * 3072u, w2a = w1a + (unsigned)FS3_W1_BYTES, w2b = w2a + 2u * 4u * 3072u;
-  asm volatile("" : "+v"(w1b), "+v"(w2a), "+v"(w2b));
-  const int cbase = 4 * lh;
-
-  constexpr int RSRC = 0x00020000;  // raw buffer, 32-bit data format (gfx9)
-  const __amdgpu_buffer_rsrc_t xb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.xin.p + (size_t)b * a.xin.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t thb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.th.p + (size_t)b * a.th.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t sgb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.sg.p + (size_t)b * a.sg.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t xob = __builtin_amdgcn_make_buffer_rsrc((void *)(a.xout.p + (size_t)b * a.xout.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t skb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.skip.p + (size_t)b * a.skip.sb - a.t_base), 0, 0x7FFFFFFF, RSRC);
-  // timing builds (wrong results; python -m movenet_amd.csrc.build --stamps --exp=N, scripts/exp_fwd.sh): 21 no tanh /
-  // sigmoid stores, 22 no stores, 23 no loads after a wave's first strip, 24 = 22 + 23, 25 no MFMAs (nor splits)
-  constexpr bool aux_ok = true;
-  constexpr bool st_ok = true;
-  constexpr bool ld_ok = true;
-  const bool save = aux_ok && a.th.p != nullptr, has_out = st_ok && a.xout.p != nullptr;
-  int xld4 = 4 * a.xin.ld, thld4 = 4 * a.th.ld, xold4 = 4 * a.xout.ld, skld4 = 4 * a.skip.ld;
-
-  // x(t) of a strip is fetched one strip ahead, under the second product of the strip before, and consumed first,
-  // which gives the x(t - d) half, requested at the top of the strip, the first half of the first product to
-  // arrive; the skip accumulator's old values arrive under the second product in the x(t - d) registers
-  // (as in fused_layer64s_kernel).  (Tried: 8-byte stores -- a lane pair exchanges two registers by DPP so that one
-  // store instruction writes 4 row segments of 128 bytes instead of 2, half the store instructions: 91.9 against
-  // 91.2 us, the stores cost their bytes, not their count.  Tried: x(t - d) a strip ahead too and the old skip sums at the top of the
-  // strip, both as initial values of the second product's accumulators: 17 us per layer SLOWER -- a wave has 64
-  // vector-memory instructions in flight at most (6-bit vmcnt), a strip issues 224, and 96 loads queued in front
-  // of the 64 stores of the strip before stall the stores.)  Timing builds, us per layer: all 92, no tanh / sigmoid
-  // stores 79, no stores 65, no loads 78, neither 62, no MFMAs / splits 70.
-  auto column = [&](int t0_, bool &live_, int &tc_) {
-    const int t_ = t0_ + li;
-    live_ = t_ >= a.t_begin && t_ < te;
-    tc_ = live_ ? t_ : a.t_begin;  // (clamped: dead lanes read a valid column, zeroed afterwards)
-  };
-  float xb1[32];  // x(t) of the current strip: B operand of k-steps 0..3, residual input
-  {
-    bool lv;
-    int tcc;
-    column(tb + 32 * wave, lv, tcc);
-    const int o1 = 4 * (cbase * a.xin.ld + tcc);
-    FS_FENCE(xld4);
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      const float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, o1, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
-      xb1[j] = lv ? v : 0.f;
-    }
-  }
-
-  constexpr int FS_OOB = (int)0x80000000;
-  for (int t0 = tb + 32 * wave; t0 < te; t0 += 32 * 8) {
-    const int t = t0 + li;
-    bool live;
-    int tc;
-    column(t0, live, tc);
-    const bool skip_live = st_ok && t >= skip_lo && t < te;
-    const int ox0 = 4 * (cbase * a.xin.ld + tc - a.d);
-    const int oth = (save && live) ? 4 * (cbase * a.th.ld + tc) : FS_OOB, oxo = 4 * (cbase * a.xout.ld + tc);
-    const int osk = 4 * (cbase * a.skip.ld + (skip_live ? t : skip_lo));
-    float xn1[32];  // x(t) of the NEXT strip
-    // ---- x(t - d): B operand of k-steps 4..7; later the skip accumulator's old values
-    float xa0[32];
-    FS_FENCE(xld4);
-    if (ld_ok || t0 == tb + 32 * wave) {
-#pragma unroll
-      for (int j = 0; j < 32; ++j)
-        xa0[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, ox0, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
-    } else {
-#pragma unroll
-      for (int j = 0; j < 32; ++j) xa0[j] = xb1[j] * 0.5f;
-    }
-    // (interior strips -- wave-uniform test -- need no masking)
-    if (!(t0 >= a.t_begin && t0 + 32 <= te)) {
-#pragma unroll
-      for (int j = 0; j < 32; ++j) xa0[j] = live ? xa0[j] : 0.f;
-    }
-    // ---- f | g: four 32 x 32 blocks (f c<32, f c>=32, g c<32, g c>=32), K = 128 = 8 k-steps, the x(t) half first
-    f32x16 acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    BF3_PRODUCT(8, w1a, w1b, (ks_ < 4 ? xb1[8 * ks_ + e_] : xa0[8 * (ks_ - 4) + e_]));
-    // ---- gate in registers; tanh / sigmoid leave; z in accumulator order = the next B operand
-    float z[32];
-    FS_FENCE(thld4);
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int c0 = 32 * h + (r & 3) + 8 * (r >> 2);
-        float fv = acc[h][r], gv = acc[2 + h][r];
-        if constexpr (GLOBAL) {
-          fv += BI[128 + c0 + cbase];
-          gv += BI[192 + c0 + cbase];
-        }
-        const float tv = tanh_fast(fv);
-        const float sv = sigmoid_fast(gv);
-        z[16 * h + r] = tv * sv;
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(tv), thb, oth, c0 * thld4, FS_AUX_SAVE);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sv), sgb, oth, c0 * thld4, FS_AUX_SAVE);
-      }
-    // the skip accumulator's old values, into the x(t - d) registers (dead now), and the NEXT strip's x(t), both
-    // under the MFMAs below
-    FS_FENCE(skld4);
-    if (!a.first_layer && ld_ok) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          xa0[16 * h + r] = __uint_as_float(
-              __builtin_amdgcn_raw_buffer_load_b32(skb, osk, (32 * h + (r & 3) + 8 * (r >> 2)) * skld4, 0));
-    }
-    if (ld_ok && t0 + 32 * 8 < te) {
-      bool lv;
-      int tcc;
-      column(t0 + 32 * 8, lv, tcc);
-      const int o1 = 4 * (cbase * a.xin.ld + tcc);
-      FS_FENCE(xld4);
-#pragma unroll
-      for (int j = 0; j < 32; ++j)
-        xn1[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, o1, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
-      if (!(t0 + 32 * 8 >= a.t_begin && t0 + 32 * 8 + 32 <= te)) {
-#pragma unroll
-        for (int j = 0; j < 32; ++j) xn1[j] = lv ? xn1[j] : 0.f;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 32; ++j) xn1[j] = ld_ok ? 0.f : xb1[j];
-    }
-    // ---- residual | skip: four blocks (res c<32, res c>=32, skip k<32, skip k>=32), K = 64 = 4 k-steps
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    BF3_PRODUCT(4, w2a, w2b, z[8 * ks_ + e_]);
-    // ---- x' = (y + br) + x(t): x(t) of this lane's channel is input register 16 h + r;
-    // skip (+)= y + bs, columns t - t_base, live from skip_lo
-    FS_FENCE(xold4);
-    FS_FENCE(skld4);
-    {
-      const int oxo_m = (has_out && live) ? oxo : FS_OOB, osk_m = skip_live ? osk : FS_OOB;
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int c0 = 32 * h + (r & 3) + 8 * (r >> 2);
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((acc[h][r] + BI[c0 + cbase]) + xb1[16 * h + r]), xob, oxo_m,
-                                                c0 * xold4, 0);
-        }
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int k0 = 32 * h + (r & 3) + 8 * (r >> 2);
-          const float v = acc[2 + h][r] + BI[64 + k0 + cbase];
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((a.first_layer || !ld_ok) ? v : xa0[16 * h + r] + v), skb, osk_m,
-                                                k0 * skld4, 0);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 32; ++j) xb1[j] = xn1[j];
-  }
-}
+// (fused_layer64s_bf3_kernel itself: the strip scaffold, csrc/fwd_layer64s_body.inc, under FS_FORM_BF3 -- its signature
+// stands in fused_bf16.h with the other strip kernels')
 
 // ----------------------------------------------------------------------------------------
 // The CONDITIONED layer (fused_layer64s_kernel<true>, fused_fwd.h) with what fits of this on it: its f | g product has
@@ -426,247 +222,9 @@ __global__ __launch_bounds__(256) void fsc_pack_kernel(Fs3PackArgs p, Fb16cPackA
   }
 }
 
-__global__ __launch_bounds__(512, 1) void fused_layer64s_ctxw2_kernel(FusedFwdPArgs a, int chunks_per_b, int chunk_t) {
-  constexpr bool HAS_CTX = true;
-  constexpr int C = 64, NK1 = 16;
-  extern __shared__ __attribute__((aligned(16))) float fs_lds[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x / chunks_per_b, ch = blockIdx.x - b * chunks_per_b;
-  const int li = lane & 31, lh = lane >> 5;
-  const int tb = (a.t_begin & ~TILE_ALIGN) + ch * chunk_t, te = min(a.t_end, tb + chunk_t);
-  const int skip_lo = max(a.t_begin, a.t_skip0);
-  // ---- weights into LDS: the image fsc_pack_kernel wrote once per forward call (W1 as fp32 MFMA operands,
-  // [block][k-step / 4][lane][k-step % 4]; W2 as three bf16 planes; the four bias vectors)
-  {
-    typedef float f4_ __attribute__((ext_vector_type(4)));
-    constexpr int N16 = FSC_LDS_BYTES / 16, PER = (N16 + 511) / 512;
-    const f4_ *src = (const f4_ *)a.wpack;
-    f4_ v[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int at = tid + 512 * i;
-      if (at < N16) v[i] = src[at];
-    }
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int at = tid + 512 * i;
-      if (at < N16) ((f4_ *)fs_lds)[at] = v[i];
-    }
-  }
-  __syncthreads();
-  const unsigned xda = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float *)fs_lds + 16u * lane;
-  const unsigned w1a = xda + (unsigned)FSC_XD_BYTES;
-  unsigned w2a = w1a + (unsigned)FSC_W1_BYTES, w2b = w2a + 2u * 4u * 3072u;
-  asm volatile("" : "+v"(w2a), "+v"(w2b));
-  // the bias vectors, one register each (lane i: element i), read with ds_bpermute
-  const int bv_r = __float_as_int(a.br[lane]), bv_s = __float_as_int(a.bs[lane]);
-  const int bv_cf = __float_as_int(a.bcf[lane]), bv_cg = __float_as_int(a.bcg[lane]);
-#define FSC_BIAS(vec_, ch_) __int_as_float(__builtin_amdgcn_ds_bpermute(4 * (ch_), (vec_)))
-  typedef float fsv4 __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(3))) fsv4 lds_v4;
-  // channel of accumulator register r of block h in this lane: 32 h + (r & 3) + 8 (r >> 2) + 4 lh
-  const int cbase = 4 * lh;
+// (fused_layer64s_ctxw2_kernel itself: the strip scaffold, csrc/fwd_layer64s_body.inc, under FS_FORM_CTXW2 -- its
+// signature stands in fused_bf16.h with the other strip kernels')
 
-  // Every global access below is a raw BUFFER access: (a resource per tensor and sequence:
-  // four scalar registers) + (row * ld: one scalar offset) + (one of five per-lane byte offsets).
-  // Formed as 64-bit vector addresses the ~290 accesses of a strip spilled 443 registers; as
-  // scalar row pointers + vector offsets they still cost a 64-bit vector add each and spilled the
-  // scalar file (130 v_writelane / v_readlane per strip).
-  constexpr int RSRC = 0x00020000;  // raw buffer, 32-bit data format (gfx9)
-  const __amdgpu_buffer_rsrc_t xb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.xin.p + (size_t)b * a.xin.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t thb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.th.p + (size_t)b * a.th.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t sgb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.sg.p + (size_t)b * a.sg.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t xob = __builtin_amdgcn_make_buffer_rsrc((void *)(a.xout.p + (size_t)b * a.xout.sb), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t skb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.skip.p + (size_t)b * a.skip.sb - a.t_base), 0, 0x7FFFFFFF, RSRC);
-  const __amdgpu_buffer_rsrc_t cb = __builtin_amdgcn_make_buffer_rsrc((void *)(a.ctx.p + (size_t)b * a.ctx.sb), 0, 0x7FFFFFFF, RSRC);
-  constexpr bool st_ok = true;
-  const bool save = st_ok && a.th.p != nullptr, has_out = st_ok && a.xout.p != nullptr;
-  int xld4 = 4 * a.xin.ld, thld4 = 4 * a.th.ld, xold4 = 4 * a.xout.ld, skld4 = 4 * a.skip.ld, cld4 = 4 * a.ctx.ld;
-  // (row offsets = row * ld are re-formed where they are used, behind a fence on ld: hoisted out of
-  // the strip loop the ~120 products filled the scalar file and were spilled to vector lanes)
-#define FS_FENCE(x) asm volatile("" : "+s"(x))
-
-  // x(t) of a strip (the tap-1 half of the input, 32 registers) is fetched one strip AHEAD, under
-  // the second product of the strip before; the first product consumes it first, which gives the
-  // x(t - d) half, requested at the top of the strip, 128 MFMAs to arrive.  (Without it the wave
-  // counters showed 51 % of the wave cycles waiting for memory: a wave that issues MFMAs back to
-  // back starves the other wave of its SIMD, so the two fall into step and wait together.)
-  auto column = [&](int t0_, bool &live_, int &tc_) {
-    const int t_ = t0_ + li;
-    live_ = t_ >= a.t_begin && t_ < te;
-    tc_ = live_ ? t_ : a.t_begin;  // (clamped: dead lanes read a valid column, zeroed afterwards)
-  };
-  float xb1[32];  // x(t) of the current strip: B operand of k-steps 32..63, residual input
-  if (!HAS_CTX) {
-    bool lv;
-    int tcc;
-    column(tb + 32 * wave, lv, tcc);
-    const int o1 = 4 * (cbase * a.xin.ld + tcc);
-    FS_FENCE(xld4);
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      const float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, o1, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
-      xb1[j] = lv ? v : 0.f;
-    }
-  }
-
-  // Lanes that must not store (columns outside [t_begin, te), no output tensor) carry an offset
-  // beyond the buffer's num_records: the hardware drops the access -- no exec-mask branch per store.
-  // (Tried: holding a strip's x' and skip sums in registers until after the next strip's first
-  // product, so that no wait on a prefetched load sits right behind 64 fresh stores -- on gfx9 loads
-  // and stores retire through one in-order counter and the compiler's wait at the loop edge was
-  // vmcnt(0).  Measured 131.4 against 131.9 us per layer: the second wave of the SIMD covers it.)
-  constexpr int FS_OOB = (int)0x80000000;
-  for (int t0 = tb + 32 * wave; t0 < te; t0 += 32 * 8) {
-    const int t = t0 + li;
-    bool live;
-    int tc;
-    column(t0, live, tc);
-    const bool skip_live = st_ok && t >= skip_lo && t < te;
-    // per-lane byte offsets (channel part 4 lh of the row + the column)
-    const int ox0 = 4 * (cbase * a.xin.ld + tc - a.d);
-    const int oth = (save && live) ? 4 * (cbase * a.th.ld + tc) : FS_OOB, oxo = 4 * (cbase * a.xout.ld + tc);
-    const int osk = 4 * (cbase * a.skip.ld + (skip_live ? t : skip_lo));
-    float xn1[32];  // without context: x(t) of the NEXT strip; with: ctx(t) of this one (k-steps 64..95)
-    if (HAS_CTX) {
-      const int o1 = 4 * (cbase * a.xin.ld + tc), oc = 4 * (cbase * a.ctx.ld + tc);
-      FS_FENCE(xld4);
-      FS_FENCE(cld4);
-#pragma unroll
-      for (int j = 0; j < 32; ++j) {
-        const float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, o1, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
-        xb1[j] = live ? v : 0.f;
-      }
-#pragma unroll
-      for (int j = 0; j < 32; ++j) {
-        const float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(cb, oc, ((j & 3) + 8 * (j >> 2)) * cld4, 0));
-        xn1[j] = live ? v : 0.f;
-      }
-    }
-    // ---- x(t - d) of channel kc(j) + 4 lh: B operand of k-steps 0..31; later the skip accumulator's old values
-    float xa0[32];
-    FS_FENCE(xld4);
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      const float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, ox0, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
-      xa0[j] = v;
-    }
-    // (interior strips -- wave-uniform test -- need no masking: 32 selects less per strip)
-    if (!(t0 >= a.t_begin && t0 + 32 <= te)) {
-#pragma unroll
-      for (int j = 0; j < 32; ++j) xa0[j] = live ? xa0[j] : 0.f;
-    }
-    // ---- f | g: four 32 x 32 blocks (f c<32, f c>=32, g c<32, g c>=32), K = 128, the x(t) half first
-    f32x16 acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    // x(t) (prefetched: consumed first, fp32 MFMAs), x(t - d) (bf16 planes), context (fp32 MFMAs)
-#pragma unroll
-    for (int kq = 0; kq < NK1; ++kq) {
-      if (kq == 8) {
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          u32x4 bh, bm, bl;
-          bf3_split8(&xa0[8 * ks], bh, bm, bl);
-#pragma unroll
-          for (int blk = 0; blk < 4; ++blk) bf3_mfma6(acc[blk], xda + 3072u * (unsigned)(blk * 4 + ks), bh, bm, bl);
-        }
-      }
-      fsv4 aw[4];
-#pragma unroll
-      for (int blk = 0; blk < 4; ++blk) aw[blk] = *(const lds_v4 *)(uintptr_t)(w1a + 4u * (unsigned)((blk * NK1 + kq) * 256));
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int blk = 0; blk < 4; ++blk)
-          acc[blk] = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[blk][e], kq >= 8 ? xn1[4 * (kq - 8) + e] : xb1[4 * kq + e], acc[blk], 0, 0,
-                                                          0);
-    }
-    // ---- gate in registers; tanh / sigmoid leave; z in accumulator order = the next B operand
-    float z[32];
-    FS_FENCE(thld4);
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int cg_ = 32 * h + (r & 3) + 8 * (r >> 2) + cbase;
-        const float tv = tanh_fast(acc[h][r] + FSC_BIAS(bv_cf, cg_));
-        const float sv = sigmoid_fast(acc[2 + h][r] + FSC_BIAS(bv_cg, cg_));
-        z[16 * h + r] = tv * sv;
-        const int c0 = 32 * h + (r & 3) + 8 * (r >> 2);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(tv), thb, oth, c0 * thld4, FS_AUX_SAVE);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sv), sgb, oth, c0 * thld4, FS_AUX_SAVE);
-      }
-    // the skip accumulator's old values, into the x(t - d) registers (dead now), and the NEXT strip's
-    // x(t), both under the MFMAs below
-    FS_FENCE(skld4);
-    if (!a.first_layer) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          xa0[16 * h + r] = __uint_as_float(
-              __builtin_amdgcn_raw_buffer_load_b32(skb, osk, (32 * h + (r & 3) + 8 * (r >> 2)) * skld4, 0));
-    }
-    const bool more = !HAS_CTX && t0 + 32 * 8 < te;
-    if (HAS_CTX) {
-    } else if (more) {
-      bool lv;
-      int tcc;
-      column(t0 + 32 * 8, lv, tcc);
-      const int o1 = 4 * (cbase * a.xin.ld + tcc);
-      FS_FENCE(xld4);
-#pragma unroll
-      for (int j = 0; j < 32; ++j) {
-        const float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xb, o1, ((j & 3) + 8 * (j >> 2)) * xld4, 0));
-        xn1[j] = v;
-      }
-      if (!(t0 + 32 * 8 >= a.t_begin && t0 + 32 * 8 + 32 <= te)) {
-#pragma unroll
-        for (int j = 0; j < 32; ++j) xn1[j] = lv ? xn1[j] : 0.f;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 32; ++j) xn1[j] = 0.f;
-    }
-    // ---- residual | skip: four blocks (res c<32, res c>=32, skip k<32, skip k>=32), K = 64
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    BF3_PRODUCT(4, w2a, w2b, z[8 * ks_ + e_]);  // (the residual | skip product on the bf16 matrix cores)
-    // ---- x' = (y + br) + x(t): x(t) of this lane's channel is input register 32 + 16 h + r;
-    // skip (+)= y + bs, columns t - t_base, live from skip_lo
-    FS_FENCE(xold4);
-    FS_FENCE(skld4);
-    {
-      const int oxo_m = (has_out && live) ? oxo : FS_OOB, osk_m = skip_live ? osk : FS_OOB;
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int c0 = 32 * h + (r & 3) + 8 * (r >> 2);
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((acc[h][r] + FSC_BIAS(bv_r, c0 + cbase)) + xb1[16 * h + r]), xob, oxo_m,
-                                                c0 * xold4, 0);
-        }
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int k0 = 32 * h + (r & 3) + 8 * (r >> 2);
-          const float v = acc[2 + h][r] + FSC_BIAS(bv_s, k0 + cbase);
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a.first_layer ? v : xa0[16 * h + r] + v), skb, osk_m, k0 * skld4, 0);
-        }
-    }
-    if (!HAS_CTX) {
-#pragma unroll
-      for (int j = 0; j < 32; ++j) xb1[j] = xn1[j];
-    }
-  }
-}
 
 // ----------------------------------------------------------------------------------------
 // The head's two forward convolutions (dense_strip_kernel, fused_fwd.h) in the same form: weights as three bf16
@@ -719,20 +277,7 @@ __global__ __launch_bounds__(512, 1) void dense_strip_bf3_kernel(DenseStripArgs 
   const int li = lane & 31, lh = lane >> 5;
   const int tb = (a.t_begin & ~TILE_ALIGN) + ch * chunk_t, te = min(a.t_end, tb + chunk_t);
   if (wimg) {
-    typedef float f4_ __attribute__((ext_vector_type(4)));
-    constexpr int N16 = IMG_BYTES / 16, PER = (N16 + 511) / 512;
-    const f4_ *src = (const f4_ *)(wimg + (size_t)blockIdx.y * (IMG_BYTES / 4));
-    f4_ v[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int at = tid + 512 * i;
-      if (at < N16) v[i] = src[at];
-    }
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int at = tid + 512 * i;
-      if (at < N16) ((f4_ *)ds3_lds)[at] = v[i];
-    }
+    LDS_IMAGE_COPY(ds3_lds, wimg + (size_t)blockIdx.y * (IMG_BYTES / 4), IMG_BYTES);
   } else {
     ds3_stage<K, M, TRANSPOSED>(ds3_lds, a.wmat, a.ldw, a.bias, m_base, tid, 512);
   }

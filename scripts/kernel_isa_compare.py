@@ -7,10 +7,12 @@
 to DIR/<kernel>.parent.s and DIR/<kernel>.branch.s, to be diffed.
 
 Each LIB is a movenet_amd/lib directory left by `python -m movenet_amd.csrc.build --force --keep-temps` (or the
-sequence-hip-amdgcn-amd-amdhsa-gfx950.s file itself).  For each of the ten layer kernels: the resource figures the
-compiler prints behind the kernel (the ones -Rpass-analysis=kernel-resource-usage reports), the code bytes, and the
+sequence-hip-amdgcn-amd-amdhsa-gfx950.s file itself).  For each layer kernel (KERNELS) and each instantiation of the
+PREFIXES' templates that the file holds: the resource figures the compiler prints behind the kernel (the ones -Rpass-analysis=kernel-resource-usage reports), the code bytes, and the
 SHA-256 of the instruction text from the kernel's label to its s_endpgm with comments stripped and local labels
-renumbered.  Text only: no instruction is looked for.
+renumbered.  Text only: no instruction is looked for.  The kernels of REPORTED (and REPORTED_PREFIXES) -- the weight
+pack kernels, which run once per forward call -- are listed with the same figures under "reported"; they do not decide
+the exit status.
 """
 import hashlib
 import json
@@ -25,17 +27,29 @@ KERNELS = [
     "fused_layer64s_bf3_kernel<false>", "fused_layer64s_bf3_kernel<true>",
     "fused_layer64s_bf16_kernel<false, false>", "fused_layer64s_bf16_kernel<true, false>",
     "fused_layer64s_bf16_kernel<false, true>",
+    "fused_layer64s_kernel<false>", "fused_layer64s_kernel<true>", "fused_layer64s_ctxw2_kernel",
 ]
+PREFIXES = ["dense_strip_bf3_kernel<"]  # every instantiation sequence.hip emits
+REPORTED = ["fs3_pack_kernel", "fb16_pack_kernel", "fb16c_pack_kernel", "fsc_pack_kernel"]
+REPORTED_PREFIXES = ["ds3_pack_kernel<"]
 FIGURES = {"vgpr": "NumVgprs", "agpr": "NumAgprs", "sgpr": "TotalNumSgprs", "scratch_bytes": "ScratchSize",
            "lds_bytes": "LDSByteSize", "occupancy": "Occupancy", "code_bytes": "codeLenInByte"}
 
 
 def short_name(sym):
-    """_ZN3mvn18bwd_layer64_kernelILb1EEEv... -> bwd_layer64_kernel<true>"""
-    m = re.match(r"_ZN3mvn\d+([a-z0-9_]+)I((?:Lb[01]E)+)E", sym)
+    """_ZN3mvn18bwd_layer64_kernelILb1EEEv... -> bwd_layer64_kernel<true>; ...kernelILi64ELb0EEEv -> kernel<64, false>;
+    _ZN3mvn27fused_layer64s_ctxw2_kernelENS_... (no template) -> fused_layer64s_ctxw2_kernel"""
+    m = re.match(r"_ZN3mvn\d+([a-z0-9_]+?)(?:I((?:L[bi]\d+E)+)E|E)", sym)
     if not m:
         return sym
-    return "%s<%s>" % (m.group(1), ", ".join("true" if f == "1" else "false" for f in re.findall(r"Lb([01])E", m.group(2))))
+    if not m.group(2):
+        return m.group(1)
+    args = [("true" if v == "1" else "false") if t == "b" else v for t, v in re.findall(r"L([bi])(\d+)E", m.group(2))]
+    return "%s<%s>" % (m.group(1), ", ".join(args))
+
+
+def wanted(name, names, prefixes):
+    return name in names or any(name.startswith(p) for p in prefixes)
 
 
 def kernels_of(path):
@@ -46,7 +60,7 @@ def kernels_of(path):
     short = {s: short_name(s) for _, s in starts}
     res = {}
     for n, (i, sym) in enumerate(starts):
-        if short[sym] not in KERNELS:
+        if not wanted(short[sym], KERNELS + REPORTED, PREFIXES + REPORTED_PREFIXES):
             continue
         end = starts[n + 1][0] if n + 1 < len(starts) else len(lines)
         body, tail = [], lines[i:end]
@@ -78,7 +92,16 @@ LAUNCH_LDS_BYTES = {
     "fused_layer64s_bf3_kernel<false>": 147968, "fused_layer64s_bf3_kernel<true>": 148480,        # FS3_LDS_BYTES (+ 512)
     "fused_layer64s_bf16_kernel<false, false>": 49664, "fused_layer64s_bf16_kernel<true, false>": 50176,  # FB16_LDS_BYTES
     "fused_layer64s_bf16_kernel<false, true>": 66560,                                             # FB16C_LDS_BYTES
+    "fused_layer64s_kernel<false>": 99328, "fused_layer64s_kernel<true>": 132096,                 # F32_STRIP(_CTX)_LDS_BYTES
+    "fused_layer64s_ctxw2_kernel": 163840,                                                        # FSC_LDS_BYTES
 }
+
+
+def launch_lds_bytes(k):
+    if k.startswith("dense_strip_bf3_kernel<"):  # <K, M, ...>: K x M x 6 bytes of planes + M floats of bias
+        K, M = [int(v) for v in k[k.index("<") + 1:].split(", ")[:2]]
+        return K * M * 6 + M * 4
+    return LAUNCH_LDS_BYTES[k]
 
 
 def option(name):
@@ -90,11 +113,18 @@ def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     out, dump = option("out"), option("dump")
     parent, branch = kernels_of(args[0]), kernels_of(args[1])
-    doc = {"kernels": {}}
-    for k in KERNELS:
+    doc = {"kernels": {}, "reported": {}}
+    both = sorted(set(parent) | set(branch))
+    for k in [k for k in both if wanted(k, REPORTED, REPORTED_PREFIXES)]:
+        p, b = parent[k], branch[k]
+        doc["reported"][k] = {"parent": p[0], "branch": b[0], "identical": p[1] == b[1]}
+        print("%-45s %s  vgpr %s/%s sgpr %s/%s scratch %s/%s code %s/%s (reported only)" % (
+            k, "same" if p[1] == b[1] else "differs", p[0]["vgpr"], b[0]["vgpr"], p[0]["sgpr"], b[0]["sgpr"],
+            p[0]["scratch_bytes"], b[0]["scratch_bytes"], p[0]["code_bytes"], b[0]["code_bytes"]))
+    for k in KERNELS + [k for k in both if wanted(k, [], PREFIXES)]:
         p, b = parent[k], branch[k]
         doc["kernels"][k] = {"parent": p[0], "branch": b[0], "identical": p[1] == b[1],
-                             "launch_lds_bytes": LAUNCH_LDS_BYTES[k]}
+                             "launch_lds_bytes": launch_lds_bytes(k)}
         print("%-45s %s  vgpr %s/%s scratch %s/%s occ %s/%s" % (k, "same" if p[1] == b[1] else "DIFFERS", p[0]["vgpr"], b[0]["vgpr"],
               p[0]["scratch_bytes"], b[0]["scratch_bytes"], p[0]["occupancy"], b[0]["occupancy"]))
         if p[1] != b[1] and dump:

@@ -13,17 +13,21 @@ One case per mode, each asserting its ``mvn_last_backward_form()``:
     bf16          MVN_BWD_FORM_BF16         bwd_layer64_bf16_kernel<false, false>
     bf16-label    MVN_BWD_FORM_BF16_GLOBAL  bwd_layer64_bf16_kernel<true, false> (row sums inside the kernel)
     bf16-ctx      MVN_BWD_FORM_BF16_CTX     bwd_layer64_bf16_kernel<false, true>
+    fp32-mfma     MVN_BWD_FORM_ONE          as fp32, behind fused_layer64s_kernel<false>
+    fp32-mfma-ctx MVN_BWD_FORM_ONE          as fp32-ctx, behind fused_layer64s_kernel<true>
 
-and the forward of each mode runs the matching strip kernel (fused_layer64s_bf3_kernel<false | true>, the context
-forms, fused_layer64s_bf16_kernel<...>).  What is hashed: the logits; the forward's saved tensors, read from the
-pass's buffers before the backward runs -- tanh and sigmoid of every layer over its valid columns [t_lo, T) and the
+and the forward of each mode runs the matching strip kernel (fused_layer64s_bf3_kernel<false | true>,
+fused_layer64s_ctxw2_kernel, fused_layer64s_bf16_kernel<...>), all of them one body (csrc/fwd_layer64s_body.inc).  The
+two fp32-mfma cases run under MOVENET_HIP_FORWARD_MFMA=f32, which keeps the layers on the fp32-MFMA strip kernels
+(fused_layer64s_kernel<false | true>) that no other case reaches.  What is hashed: the logits; the forward's saved
+tensors, read from the pass's buffers before the backward runs -- tanh and sigmoid of every layer over its valid columns [t_lo, T) and the
 skip sum over [RF - 1, T) --; the gradient of every parameter -- the layers' weights and biases, the head, the context
 convs (the label's come from ``rowsum``), ``global_embedding.weight`` (from ``de``) -- and, in the context modes,
 ``dctx`` as the gradient of the context leaf.  The saved tensors tell a forward that changed from a backward that did.
 
 Shape: C = K = 64, layer_size 3, stack_size 2 (dilations 1, 2, 4, 1, 2, 4; receptive field 16), Q = 64, batch 32,
-T = 2600 = 40 x 64 + 40.  fp32-ctx alone runs at Q = 128: the fp32 plan keeps the conditioned layers' second A' | P0
-pair in the dlogit tensor, which holds it from Q = 128 on; at Q = 64 it takes the two-half form and
+T = 2600 = 40 x 64 + 40.  fp32-ctx and fp32-mfma-ctx run at Q = 128: the fp32 plan keeps the conditioned layers' second
+A' | P0 pair in the dlogit tensor, which holds it from Q = 128 on; at Q = 64 it takes the two-half form and
 bwd_layer64_kernel<true> does not run there (the layer kernels never see Q).
 
 * Tiles.  A layer's t_lo is 1, 3, 7, 8, 10 or 14, never a multiple of 64: tile 0 is an edge tile, so is tile 40 (columns
@@ -47,7 +51,9 @@ Inputs are integer arithmetic in numpy (an index hash): no RNG stream, no transc
 make_state_dict.
 
 Before the recording the parent's library ran every case twice, in separate processes: every tensor of every case
-came out with the same bytes both times, so none is left out of the fixture.
+came out with the same bytes both times, so none is left out of the fixture.  (The fixture was recorded again, all
+eight cases from one library, when the two fp32-mfma cases joined: the two new cases reproduced in two processes, and
+the six older cases' hashes came out as in the first recording.)
 
 Recording: with MOVENET_LAYER_KERNELS_RECORD=<commit> the test writes the fixture instead of comparing.  That is only
 worth something from the parent's library, so it refuses to run unless MOVENET_HIP_LIB names the library to record
@@ -76,14 +82,16 @@ B, T, C, G, RF, CUS = 32, 2600, 64, 4, 16, 256
 T_LO = (1, 3, 7, 8, 10, 14)  # first valid column of each layer's outputs: the dilations summed
 CTX = "context"  # the key the gradient of the context is filed under
 
-# case -> (forward_precision, conditioning, Q, expected backward form)
+# case -> (forward_precision, conditioning, Q, expected backward form, MOVENET_HIP_FORWARD_MFMA or None)
 CASES = {
-    "fp32": ("fp32", None, 64, N.BWD_FORM_ONE),
-    "fp32-ctx": ("fp32", "ctx", 128, N.BWD_FORM_ONE),
-    "fp32-label": ("fp32", "label", 64, N.BWD_FORM_ONE_GLOBAL),
-    "bf16": ("bf16", None, 64, N.BWD_FORM_BF16),
-    "bf16-label": ("bf16", "label", 64, N.BWD_FORM_BF16_GLOBAL),
-    "bf16-ctx": ("bf16", "ctx", 64, N.BWD_FORM_BF16_CTX),
+    "fp32": ("fp32", None, 64, N.BWD_FORM_ONE, None),
+    "fp32-ctx": ("fp32", "ctx", 128, N.BWD_FORM_ONE, None),
+    "fp32-label": ("fp32", "label", 64, N.BWD_FORM_ONE_GLOBAL, None),
+    "bf16": ("bf16", None, 64, N.BWD_FORM_BF16, None),
+    "bf16-label": ("bf16", "label", 64, N.BWD_FORM_BF16_GLOBAL, None),
+    "bf16-ctx": ("bf16", "ctx", 64, N.BWD_FORM_BF16_CTX, None),
+    "fp32-mfma": ("fp32", None, 64, N.BWD_FORM_ONE, "f32"),
+    "fp32-mfma-ctx": ("fp32", "ctx", 128, N.BWD_FORM_ONE, "f32"),
 }
 
 
@@ -155,8 +163,9 @@ def test_chunk_arithmetic():
 
 
 def run_case(case: str) -> dict:
+    """One training step of ``case`` (the caller has set the case's MOVENET_HIP_FORWARD_MFMA)."""
     from movenet_amd.wavenet import WaveNet
-    precision, cond, Q, form = CASES[case]
+    precision, cond, Q, form, _ = CASES[case]
     inp, full = _inputs(Q), _weights(Q)
     if cond == "label":
         m = WaveNet(**_cfg(Q), global_classes=G)
@@ -214,7 +223,9 @@ def _record(case: str, got: dict) -> None:
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", list(CASES))
-def test_outputs_equal_the_recording(case):
+def test_outputs_equal_the_recording(monkeypatch, case):
+    if CASES[case][4]:
+        monkeypatch.setenv("MOVENET_HIP_FORWARD_MFMA", CASES[case][4])  # (read again by the passes: MOVENET_DEBUG_GUARD)
     if not RECORD:
         with open(FIXTURE) as f:
             fixture = json.load(f)
