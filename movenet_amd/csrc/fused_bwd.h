@@ -32,6 +32,11 @@ struct FusedBwdAArgs {
   const float *wr, *ws;                 // (64 out, 64 in) each
   Act dxo, dskip, th, sg, dfg;          // dxo.p == NULL: last layer (its residual output is unused)
 };
+struct FusedBwdCArgs {      // the context pass of a conditioned layer (described in front of bwd_dctx_wgctx64_kernel)
+  int t_begin, t_end;       // the layer's outputs cover [t_begin = A_{l+1}, t_end)
+  const float *wcf, *wcg;   // (64 out, 64 in) each
+  Act dfg, ctx, dctx;       // dfg (B, 128, Tp) read; ctx (B, 64, ld) read; dctx (B, 64, Tp) accumulated in place
+};
 
 constexpr int FB_C = 64;
 
@@ -80,214 +85,44 @@ __device__ __forceinline__ void fb_store16(f4 x, __amdgpu_buffer_rsrc_t r, int v
                                          r, voff, soff, 0);
 }
 
+// The output rows RB_ p + srow (p < NP_) of a tile, columns t0 + st .. +3, inside [lo_, te): whole-row float4 stores
+// (fb_store16 through rsrc_ / vo_, the resource and per-lane offset of act_) where the thread's four columns all lie
+// inside, else element-wise.  V4_ / VE_: a row block's float4 / its element e, expressions in p and e that are
+// evaluated on the path that stores them.  Reads the kernel's b, t0, st, srow and te.  (A macro: the kernels of this
+// file sit at their register budgets, see fused_bwd_l.h on functions and lambdas there.  The second half's store, whose
+// value is a sum formed per row block inside the branch, keeps its own wording: through this macro its instructions
+// changed.)
+#define FB_TILE_STORE(NP_, RB_, act_, rsrc_, vo_, lo_, V4_, VE_)                                                        \
+  {                                                                                                                     \
+    const int t = t0 + st;                                                                                              \
+    float *base = (act_).p + (size_t)b * (act_).sb + t;                                                                 \
+    if (t >= (lo_) && t + 3 < te) {                                                                                     \
+      _Pragma("unroll") for (int p = 0; p < (NP_); ++p) fb_store16(V4_, rsrc_, vo_, 4 * ((RB_) * p * (act_).ld + t0)); \
+    } else {                                                                                                            \
+      _Pragma("unroll") for (int p = 0; p < (NP_); ++p) _Pragma("unroll") for (int e = 0; e < 4; ++e)                   \
+        if (t + e >= (lo_) && t + e < te) base[(size_t)((RB_) * p + srow) * (act_).ld + e] = VE_;                       \
+    }                                                                                                                   \
+  }
+// A wave's two 32 x 32 accumulator blocks into the workgroup's slab (wgrad2_kernel's format, 128 rows of COLS_): block i
+// at rows M0_ + i MS_, columns N0_ + i NS_.  (A macro for the same reason.)
+#define FB_SLAB_STORE(acc_, M0_, MS_, N0_, NS_, COLS_, lane_)                                     \
+  _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int r = 0; r < 16; ++r) { \
+    const int m = (M0_) + (MS_) * i + acc_row(r, lane_), n = (N0_) + (NS_) * i + ((lane_) & 31); \
+    part[((size_t)blockIdx.x * 128 + m) * (COLS_) + n] = acc_[i][r];                             \
+  }
+
+// The two 256-thread passes -- this first half and the conditioned layers' context pass, bwd_dctx_wgctx64_kernel below --
+// are one SCAFFOLD (bwd_half64_body.inc): index setup and chunk bounds, the 64 weights per lane, staging geometry, buffer
+// resources, the gload / lstore skeleton, the prefetch loop, the transposed product, the wait ahead of the stores, the
+// tile store and the slab / bias-partial epilogue.  A policy (FBH_CTX) supplies, in place under `if constexpr` and marked
+// [policy]: where the weights come from; which tensors are staged under which masks; the weight-gradient product; what
+// becomes of the transposed product.  The body is TEXT behind each kernel's parameter list (see fused_bwd_l.h).
+#define FBH_CTX 0
 __global__ __launch_bounds__(256, 2) void bwd_dz_wgrs64_kernel(FusedBwdAArgs a, int chunks_per_b, int chunk_t,
                                                               float *__restrict__ bias_part,
-                                                              float *__restrict__ part) {
-  constexpr int C = FB_C, LD = W2_LD, TT = W2_T;
-  __shared__ __attribute__((aligned(16))) float As[2 * C][LD];  // dxo rows | dskip rows; later df | dg
-  __shared__ __attribute__((aligned(16))) float Th[C][LD];
-  __shared__ __attribute__((aligned(16))) float Sg[C][LD];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x / chunks_per_b, ch = blockIdx.x - b * chunks_per_b;
-  const int li = lane & 31, lh = lane >> 5, h4 = 4 * lh;
-  const int tb = (a.t_begin & ~TILE_ALIGN) + ch * chunk_t, te = min(a.t_end, tb + chunk_t);
-  const int skip_lo = max(a.t_begin, a.t_skip0);
-  const bool has_dxo = a.dxo.p != nullptr;
-
-  // ---- B operand of the dz product: W[o][32 wc + li] for o = 2 kk + lh, in registers
-  const int wt = wave >> 1, wc = wave & 1;  // dz block: t in [32 wt, +32), c in [32 wc, +32)
-  float wreg[C];
-#pragma unroll
-  for (int kk = 0; kk < C; ++kk) {
-    const int o = 2 * kk + lh;
-    wreg[kk] = o < C ? (has_dxo ? a.wr[(size_t)o * C + 32 * wc + li] : 0.f)
-                     : a.ws[(size_t)(o - C) * C + 32 * wc + li];
-  }
-  // weight-gradient block of this wave (as wgrad2_kernel<.., 1>): rows [64 wm, +64), cols [32 wn, +32)
-  const int wm = wave >> 1, wn = wave & 1;
-  f32x16 accw[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accw[i][r] = 0.f;
-
-  // ---- staging: thread -> rows (tid >> 4) + 16 p, columns 4 (tid & 15) .. +3
-  const int srow = tid >> 4, st = 4 * (tid & 15);
-  f4 areg[8], treg[4], sreg[4];
-  float bsum[8];
-#pragma unroll
-  for (int p = 0; p < 8; ++p) bsum[p] = 0.f;
-  unsigned azero = 0;
-  const __amdgpu_buffer_rsrc_t dxob = fb_rsrc(a.dxo.p + (size_t)b * a.dxo.sb);
-  const __amdgpu_buffer_rsrc_t dskb = fb_rsrc(a.dskip.p + (size_t)b * a.dskip.sb);
-  const __amdgpu_buffer_rsrc_t thb = fb_rsrc(a.th.p + (size_t)b * a.th.sb);
-  const __amdgpu_buffer_rsrc_t sgb = fb_rsrc(a.sg.p + (size_t)b * a.sg.sb);
-  const __amdgpu_buffer_rsrc_t dfgb = fb_rsrc(a.dfg.p + (size_t)b * a.dfg.sb);
-  const int vo_dxo = 4 * (srow * a.dxo.ld + st), vo_dsk = 4 * (srow * a.dskip.ld + st);
-  const int vo_th = 4 * (srow * a.th.ld + st), vo_sg = 4 * (srow * a.sg.ld + st), vo_dfg = 4 * (srow * a.dfg.ld + st);
-  auto gload = [&](int t0) {
-    int srow_q = srow;
-    asm volatile("" : "+v"(srow_q));
-    const int t = t0 + st;
-    // the tile lies inside every live row's range (one test per tile, workgroup-uniform):
-    // sixteen back-to-back 16-byte loads; rows whose range misses the tile altogether (dskip
-    // before t_skip0, the absent dxo of the last layer) load a row that IS valid and are zeroed
-    // at the LDS store
-    const bool x_full = t0 >= a.t_begin && t0 + TT <= te;
-    const bool s_full = t0 >= skip_lo && t0 + TT <= te, s_none = t0 + TT <= skip_lo;
-    azero = (has_dxo ? 0u : 0x0Fu) | (s_none ? 0xF0u : 0u);
-    if (x_full && (s_full || s_none)) {
-      // raw buffer loads (fb_load16): per-lane offset of (row srow, column st) + scalar offset of the
-      // row block and the tile
-      int ld_dxo = 4 * a.dxo.ld, ld_dsk = 4 * a.dskip.ld, ld_th = 4 * a.th.ld, ld_sg = 4 * a.sg.ld;
-      asm volatile("" : "+s"(ld_dxo), "+s"(ld_dsk), "+s"(ld_th), "+s"(ld_sg));
-      const int c4 = 4 * t0;
-#pragma unroll
-      for (int p = 0; p < 8; ++p) {
-        if ((azero >> p) & 1u)
-          areg[p] = fb_load16(thb, vo_th, c4);
-        else if (p < 4)
-          areg[p] = fb_load16(dxob, vo_dxo, 16 * p * ld_dxo + c4);
-        else
-          areg[p] = fb_load16(dskb, vo_dsk, 16 * (p - 4) * ld_dsk + c4 - 4 * a.t_base);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        treg[p] = fb_load16(thb, vo_th, 16 * p * ld_th + c4);
-        sreg[p] = fb_load16(sgb, vo_sg, 16 * p * ld_sg + c4);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    } else {
-#pragma unroll
-      for (int p = 0; p < 8; ++p) {
-        if (p < 4)
-          areg[p] = has_dxo ? ld4_edge(a.dxo.at(b, 16 * p + srow_q, 0), t, a.t_begin, te) : kZero4;
-        else
-          areg[p] = ld4_edge(a.dskip.at(b, 16 * (p - 4) + srow_q, 0) - a.t_base, t, skip_lo, te);
-      }
-      azero = 0;
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        treg[p] = ld4_edge(a.th.at(b, 16 * p + srow_q, 0), t, a.t_begin, te);
-        sreg[p] = ld4_edge(a.sg.at(b, 16 * p + srow_q, 0), t, a.t_begin, te);
-      }
-    }
-  };
-  auto lstore = [&]() {
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-      if ((azero >> p) & 1u) areg[p] = kZero4;
-      *(f4 *)&As[16 * p + srow][st] = areg[p];
-      bsum[p] += (areg[p].x + areg[p].y) + (areg[p].z + areg[p].w);  // bias gradient = row sums
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      *(f4 *)&Th[16 * p + srow][st] = treg[p];
-      *(f4 *)&Sg[16 * p + srow][st] = sreg[p];
-    }
-  };
-
-  gload(tb);
-  lstore();
-  __syncthreads();
-  for (int t0 = tb; t0 < te; t0 += TT) {
-    const bool more = t0 + TT < te;
-    if (more) gload(t0 + TT);  // the next tile's loads fly under this tile's MFMAs
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- dz' (32 t x 32 c) = sum over the 128 rows of the tile
-    f32x16 accd;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accd[r] = 0.f;
-#pragma unroll
-    for (int kk = 0; kk < C; ++kk)
-      accd = __builtin_amdgcn_mfma_f32_32x32x2f32(As[2 * kk + lh][32 * wt + li], wreg[kk], accd, 0, 0, 0);
-    // ---- weight gradient: (64 x 32) += A (64 x 64 t) z^T
-    // (r3, measured: this product on the bf16 matrix cores as in the second half -- 115.9 against 100.4 us: the
-    // planes do not fit beside this kernel's 248 registers, 13 spill in the tile loop.  It stays on fp32 MFMAs.)
-    // (... and the dz product above with its K split between wave pairs as in the second half's dx: 111.3 against
-    // 104.9 us -- this kernel is bound by its barriers and its bytes, a third barrier per tile costs more than the
-    // matrix time it saves.)
-#pragma unroll
-    for (int g = 0; g < TT / 8; ++g) {
-      f4 av[2];
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) av[mi] = *(const f4 *)&As[64 * wm + 32 * mi + li][8 * g + h4];
-      const f4 tv = *(const f4 *)&Th[32 * wn + li][8 * g + h4], sv = *(const f4 *)&Sg[32 * wn + li][8 * g + h4];
-      const f4 zv = f4{tv.x * sv.x, tv.y * sv.y, tv.z * sv.z, tv.w * sv.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-          accw[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(f4_get(av[mi], j), f4_get(zv, j), accw[mi], 0, 0, 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    // The next tile's loads have had the whole MFMA section to land: wait for them HERE.  On
-    // gfx9 stores count in vmcnt too, and the number of stores below depends on the path (edge
-    // tiles), so the compiler's own wait in front of lstore() was vmcnt(0) -- behind this tile's
-    // global stores, i.e. one full store round trip per tile with the matrix cores idle.
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
-    __syncthreads();  // every wave has read the tile: As becomes the df | dg staging tile
-    // ---- gate derivative: this lane holds dz of channel 32 wc + li at t = 32 wt + 8 q + 4 lh + e
-    // (after the barrier, straight into the staging tile: held in registers across it, the 32
-    // values spilled next to the next tile's 64 staging registers.  Stored to global memory straight
-    // from this layout -- 16 bytes per lane and row, no staging tile, two barriers per tile instead of
-    // three -- the kernel took 104.6 against 98.8 us: the write path wants whole cache lines.)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int tc = 32 * wt + 8 * q + h4;
-      const f4 tv = *(const f4 *)&Th[32 * wc + li][tc], sv = *(const f4 *)&Sg[32 * wc + li][tc];
-      const f4 dz = f4{accd[4 * q], accd[4 * q + 1], accd[4 * q + 2], accd[4 * q + 3]};
-      *(f4 *)&As[32 * wc + li][tc] =
-          f4{dz.x * sv.x * (1.0f - tv.x * tv.x), dz.y * sv.y * (1.0f - tv.y * tv.y),
-             dz.z * sv.z * (1.0f - tv.z * tv.z), dz.w * sv.w * (1.0f - tv.w * tv.w)};
-      *(f4 *)&As[C + 32 * wc + li][tc] =
-          f4{dz.x * tv.x * sv.x * (1.0f - sv.x), dz.y * tv.y * sv.y * (1.0f - sv.y),
-             dz.z * tv.z * sv.z * (1.0f - sv.z), dz.w * tv.w * sv.w * (1.0f - sv.w)};
-    }
-    __syncthreads();
-    {
-      // whole-row float4 stores: rows 16 p + srow, columns t0 + st .. +3, inside [t_begin, te)
-      const int t = t0 + st;
-      float *base = a.dfg.p + (size_t)b * a.dfg.sb + t;
-      if (t >= a.t_begin && t + 3 < te) {
-#pragma unroll
-        for (int p = 0; p < 8; ++p)
-          fb_store16(*(const f4 *)&As[16 * p + srow][st], dfgb, vo_dfg, 4 * (16 * p * a.dfg.ld + t0));
-      } else {
-#pragma unroll
-        for (int p = 0; p < 8; ++p)
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (t + e >= a.t_begin && t + e < te) base[(size_t)(16 * p + srow) * a.dfg.ld + e] = As[16 * p + srow][st + e];
-      }
-    }
-    // (no barrier here: a thread's lstore() overwrites exactly the staging elements the same thread
-    // has just read for its global stores, and Th / Sg were last read before the barrier above)
-    if (more) {
-      lstore();
-      __syncthreads();
-    }
-  }
-  // ---- this workgroup's slab and bias partial sums (wgrad2_kernel's format, m_rows_pad 128, n_cols_pad 64)
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = 64 * wm + 32 * mi + acc_row(r, lane), n = 32 * wn + li;
-      part[((size_t)blockIdx.x * 128 + m) * 64 + n] = accw[mi][r];
-    }
-#pragma unroll
-  for (int p = 0; p < 8; ++p) {
-    float v = bsum[p];  // 16 lanes share a row
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    v += __shfl_xor(v, 8, 64);
-    if ((tid & 15) == 0) bias_part[(size_t)blockIdx.x * 128 + 16 * p + srow] = v;
-  }
-}
+                                                              float *__restrict__ part)
+#include "bwd_half64_body.inc"
+#undef FBH_CTX
 
 // The first half's two reductions in ONE launch (slab_reduce_kernel's scheme: 32 elements x RED_SEG
 // slab segments per workgroup, fixed order): workgroups [0, 256) take the 128 x 64 weight-gradient
@@ -311,11 +146,12 @@ __global__ __launch_bounds__(32 * RED_SEG) void reduce_rs64_kernel(Op op, const 
   }
 }
 
-// Launch geometry of the first half on `cus` CUs (one round of two workgroups per CU): slab chunks * batch * 128 * 64
+// Launch geometry of either 256-thread pass, the first half or the context pass, on `cus` CUs (one round of two
+// workgroups per CU; the context pass of a layer takes the first half's geometry from the same scratch): slab chunks * batch * 128 * 64
 // floats, bias_scratch chunks * batch * 128 floats (the bias partials are checked too: the scratch was sized for
 // wgrad2's 512-column chunks, and short sequences in small batches launch more workgroups than that has room for).
 // False when the scratch cannot hold it: the caller's plan then takes the two-kernel form.  chunks == 0: nothing to run.
-static bool bwd_dz_wgrs64_fits(int cus, int t_begin, int t_end, int batch, const float *bias_scratch, size_t bias_floats,
+static bool bwd_pass256_fits(int cus, int t_begin, int t_end, int batch, const float *bias_scratch, size_t bias_floats,
                                const float *slab, size_t slab_floats, int *chunks, int *chunk_t) {
   *chunks = 0;
   *chunk_t = 0;
@@ -358,7 +194,8 @@ static void flush_pending_rs(PendingRsReduce<WgOp> &p, hipStream_t s) {
 // :75-77): f | g += Wc ctx + bc.  Its backward, from the SAME dfg tile the first half wrote:
 //   dctx[t]  += Wcf^T df[t] + Wcg^T dg[t]                       (accumulated over the layers)
 //   dWcf|dWcg += dfg ctx^T,   dbcf|dbcg += sum_t dfg
-// This is the first half's shape with other operands -- A = dfg (128 rows), "z" = ctx (64 rows),
+// This is the first half's shape with other operands (and its text: bwd_half64_body.inc under FBH_CTX = 1) --
+// A = dfg (128 rows), "z" = ctx (64 rows),
 // W = [Wcf; Wcg] (128 x 64) in registers for the transposed product, weight gradient as wgrad2 --
 // so it is the same structure: one staging pass per 64-step tile, the next tile's loads in
 // registers under the MFMAs, slabs in wgrad2's format (reduce_rs64_kernel<WgCtxOp>).  The
@@ -368,12 +205,6 @@ static void flush_pending_rs(PendingRsReduce<WgOp> &p, hipStream_t s) {
 // gemm_wx_staged<DctxOp> (68 us) and lets the audio taps run in bwd_dx_wgfg64_kernel (the generic
 // Dx took 138 us): r2 434 us per layer of second-half work.
 // ----------------------------------------------------------------------------------------
-struct FusedBwdCArgs {
-  int t_begin, t_end;       // the layer's outputs cover [t_begin = A_{l+1}, t_end)
-  const float *wcf, *wcg;   // (64 out, 64 in) each
-  Act dfg, ctx, dctx;       // dfg (B, 128, Tp) read; ctx (B, 64, ld) read; dctx (B, 64, Tp) accumulated in place
-};
-
 struct WgCtxOp {  // where the context-conv gradients go (rows: filter | gate)
   float *dwcf, *dwcg, *dbcf, *dbcg;
   __device__ __forceinline__ float *dw(int m, int n) const {
@@ -386,174 +217,14 @@ struct WgCtxOp {  // where the context-conv gradients go (rows: filter | gate)
   }
 };
 
+#define FBH_CTX 1
 __global__ __launch_bounds__(256, 2) void bwd_dctx_wgctx64_kernel(FusedBwdCArgs a, int chunks_per_b, int chunk_t,
                                                                  float *__restrict__ bias_part,
-                                                                 float *__restrict__ part) {
-  constexpr int C = FB_C, LD = W2_LD, TT = W2_T;
-  __shared__ __attribute__((aligned(16))) float As[2 * C][LD];  // df rows | dg rows
-  __shared__ __attribute__((aligned(16))) float Cx[C][LD];      // the context
-  __shared__ __attribute__((aligned(16))) float Dc[C][LD];      // dctx so far; updated in place
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x / chunks_per_b, ch = blockIdx.x - b * chunks_per_b;
-  const int li = lane & 31, lh = lane >> 5, h4 = 4 * lh;
-  const int tb = (a.t_begin & ~TILE_ALIGN) + ch * chunk_t, te = min(a.t_end, tb + chunk_t);
+                                                                 float *__restrict__ part)
+#include "bwd_half64_body.inc"
+#undef FBH_CTX
 
-  // ---- B operand of the dctx product: W[o][32 wc + li] for o = 2 kk + lh, in registers
-  const int wt = wave >> 1, wc = wave & 1;  // block: t in [32 wt, +32), c in [32 wc, +32)
-  float wreg[C];
-#pragma unroll
-  for (int kk = 0; kk < C; ++kk) {
-    const int o = 2 * kk + lh;
-    wreg[kk] = o < C ? a.wcf[(size_t)o * C + 32 * wc + li] : a.wcg[(size_t)(o - C) * C + 32 * wc + li];
-  }
-  // weight-gradient block of this wave: rows [64 wm, +64), cols [32 wn, +32)
-  const int wm = wave >> 1, wn = wave & 1;
-  f32x16 accw[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accw[i][r] = 0.f;
-
-  // ---- staging: thread -> rows (tid >> 4) + 16 p, columns 4 (tid & 15) .. +3
-  const int srow = tid >> 4, st = 4 * (tid & 15);
-  f4 areg[8], creg[4], dreg[4];
-  float bsum[8];
-#pragma unroll
-  for (int p = 0; p < 8; ++p) bsum[p] = 0.f;
-  const __amdgpu_buffer_rsrc_t dfgb = fb_rsrc(a.dfg.p + (size_t)b * a.dfg.sb);
-  const __amdgpu_buffer_rsrc_t ctxb = fb_rsrc(a.ctx.p + (size_t)b * a.ctx.sb);
-  const __amdgpu_buffer_rsrc_t dcb = fb_rsrc(a.dctx.p + (size_t)b * a.dctx.sb);
-  const int vo_dfg = 4 * (srow * a.dfg.ld + st), vo_ctx = 4 * (srow * a.ctx.ld + st), vo_dc = 4 * (srow * a.dctx.ld + st);
-  auto gload = [&](int t0) {
-    int srow_q = srow;
-    asm volatile("" : "+v"(srow_q));
-    const int t = t0 + st;
-    if (t0 >= a.t_begin && t0 + TT <= te) {  // interior tile: raw buffer loads (see fb_load16)
-      int ld_dfg = 4 * a.dfg.ld, ld_ctx = 4 * a.ctx.ld, ld_dc = 4 * a.dctx.ld;
-      asm volatile("" : "+s"(ld_dfg), "+s"(ld_ctx), "+s"(ld_dc));
-      const int c4 = 4 * t0;
-#pragma unroll
-      for (int p = 0; p < 8; ++p) {
-        areg[p] = fb_load16(dfgb, vo_dfg, 16 * p * ld_dfg + c4);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        creg[p] = fb_load16(ctxb, vo_ctx, 16 * p * ld_ctx + c4);
-        dreg[p] = fb_load16(dcb, vo_dc, 16 * p * ld_dc + c4);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    } else {
-#pragma unroll
-      for (int p = 0; p < 8; ++p) areg[p] = ld4_edge(a.dfg.at(b, 16 * p + srow_q, 0), t, a.t_begin, te);
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        creg[p] = ld4_edge(a.ctx.at(b, 16 * p + srow_q, 0), t, a.t_begin, te);
-        dreg[p] = ld4_edge(a.dctx.at(b, 16 * p + srow_q, 0), t, a.t_begin, te);
-      }
-    }
-  };
-  auto lstore = [&]() {
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-      *(f4 *)&As[16 * p + srow][st] = areg[p];
-      bsum[p] += (areg[p].x + areg[p].y) + (areg[p].z + areg[p].w);  // bias gradient = row sums
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      *(f4 *)&Cx[16 * p + srow][st] = creg[p];
-      *(f4 *)&Dc[16 * p + srow][st] = dreg[p];
-    }
-  };
-
-  gload(tb);
-  lstore();
-  __syncthreads();
-  for (int t0 = tb; t0 < te; t0 += TT) {
-    const bool more = t0 + TT < te;
-    if (more) gload(t0 + TT);  // the next tile's loads fly under this tile's MFMAs
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- dctx' (32 t x 32 c) = sum over the 128 rows of the tile
-    f32x16 accd;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accd[r] = 0.f;
-#pragma unroll
-    for (int kk = 0; kk < C; ++kk)
-      accd = __builtin_amdgcn_mfma_f32_32x32x2f32(As[2 * kk + lh][32 * wt + li], wreg[kk], accd, 0, 0, 0);
-    // ---- weight gradient: (64 x 32) += dfg (64 x 64 t) ctx^T
-#pragma unroll
-    for (int G = 0; G < TT / 16; ++G) {
-      u32x4 ah[2], am[2], al[2], ch, cm, cl;
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) {
-        const f4 v0 = *(const f4 *)&As[64 * wm + 32 * mi + li][16 * G + 2 * h4];
-        const f4 v1 = *(const f4 *)&As[64 * wm + 32 * mi + li][16 * G + 2 * h4 + 4];
-        const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        bf3_split8(v, ah[mi], am[mi], al[mi]);
-      }
-      {
-        const f4 v0 = *(const f4 *)&Cx[32 * wn + li][16 * G + 2 * h4], v1 = *(const f4 *)&Cx[32 * wn + li][16 * G + 2 * h4 + 4];
-        const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        bf3_split8(v, ch, cm, cl);
-      }
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) bf3_mfma6r(accw[mi], ah[mi], am[mi], al[mi], ch, cm, cl);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- this lane owns dctx of channel 32 wc + li at t = 32 wt + 8 q + 4 lh + e: add in LDS
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int tc = 32 * wt + 8 * q + h4;
-      const f4 o = *(const f4 *)&Dc[32 * wc + li][tc];
-      *(f4 *)&Dc[32 * wc + li][tc] =
-          f4{o.x + accd[4 * q], o.y + accd[4 * q + 1], o.z + accd[4 * q + 2], o.w + accd[4 * q + 3]};
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the next tile's loads, ahead of this tile's stores
-    __syncthreads();  // the dctx tile is complete AND every wave has read As / Cx
-    {
-      // whole-row float4 stores: rows 16 p + srow, columns t0 + st .. +3, inside [t_begin, te)
-      const int t = t0 + st;
-      float *base = a.dctx.p + (size_t)b * a.dctx.sb + t;
-      if (t >= a.t_begin && t + 3 < te) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-          fb_store16(*(const f4 *)&Dc[16 * p + srow][st], dcb, vo_dc, 4 * (16 * p * a.dctx.ld + t0));
-      } else {
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (t + e >= a.t_begin && t + e < te) base[(size_t)(16 * p + srow) * a.dctx.ld + e] = Dc[16 * p + srow][st + e];
-      }
-    }
-    // (a thread's lstore() overwrites exactly the Dc elements the same thread has just read for its
-    // global stores; As / Cx were last read before the barrier above)
-    if (more) {
-      lstore();
-      __syncthreads();
-    }
-  }
-  // ---- this workgroup's slab and bias partial sums (wgrad2_kernel's format, m_rows_pad 128, n_cols_pad 64)
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = 64 * wm + 32 * mi + acc_row(r, lane), n = 32 * wn + li;
-      part[((size_t)blockIdx.x * 128 + m) * 64 + n] = accw[mi][r];
-    }
-#pragma unroll
-  for (int p = 0; p < 8; ++p) {
-    float v = bsum[p];  // 16 lanes share a row
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    v += __shfl_xor(v, 8, 64);
-    if ((tid & 15) == 0) bias_part[(size_t)blockIdx.x * 128 + 16 * p + srow] = v;
-  }
-}
-
-// (launch geometry of the conditioned pass: the first half's, bwd_dz_wgrs64_fits, from the same scratch)
+// (launch geometry of the conditioned pass: the first half's, bwd_pass256_fits, from the same scratch)
 static void launch_bwd_dctx_wgctx64(const FusedBwdCArgs &a, const WgCtxOp &op, int batch, float *bias_scratch,
                                     float *slab, int chunks, int chunk_t, hipStream_t s) {
   if (chunks <= 0) return;
@@ -817,13 +488,7 @@ __global__ __launch_bounds__(512, 1) void bwd_dx_wgfg64_kernel(FusedBwdBArgs a, 
     int tid_e = threadIdx.x;
     asm volatile("" : "+v"(tid_e));
     const int lane_e = tid_e & 63, wave_e = tid_e >> 6, wm_e = wave_e >> 1, wn_e = wave_e & 1;
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = 32 * wm_e + acc_row(r, lane_e), n = 64 * wn_e + 32 * ni + (lane_e & 31);
-        part[((size_t)blockIdx.x * 128 + m) * 128 + n] = accw[ni][r];
-      }
+    FB_SLAB_STORE(accw, 32 * wm_e, 0, 64 * wn_e, 32, 128, lane_e);
   }
 }
 

@@ -1264,7 +1264,7 @@ struct HalvesGeom { bool a, b; int a_chunks, a_chunk_t, b_chunks, b_chunk_t; siz
 static HalvesGeom halves_geometry(const BwdPlan &pl, const Geometry &g, bool has_ctx, int batch, int l) {
   HalvesGeom h = {};
   const bool c64 = pl.fused_bwd && g.C == 64;
-  h.a = c64 && g.Kc == 64 && bwd_dz_wgrs64_fits(pl.cus, pl.A_lo[l + 1], g.T, batch, pl.bias2.p, pl.bias2.floats, pl.slab.p,
+  h.a = c64 && g.Kc == 64 && bwd_pass256_fits(pl.cus, pl.A_lo[l + 1], g.T, batch, pl.bias2.p, pl.bias2.floats, pl.slab.p,
                                                 pl.slab.floats, &h.a_chunks, &h.a_chunk_t);
   if (!h.a) h.a_chunks = 0;
   h.a_used = (size_t)h.a_chunks * batch * 128 * 64;
@@ -1362,7 +1362,7 @@ static int plan_backward(const SeqMode &m, const Geometry &g, const mvn_dims *di
   };
   int cc = 0, cct = 0;
   auto ctx_fits = [&](int t_lo) {
-    return bwd_dz_wgrs64_fits(cus, t_lo, T, batch, pl.cx_bias.p, pl.cx_bias.floats, pl.cx_slab.p, pl.cx_slab.floats, &cc, &cct);
+    return bwd_pass256_fits(cus, t_lo, T, batch, pl.cx_bias.p, pl.cx_bias.floats, pl.cx_slab.p, pl.cx_slab.floats, &cc, &cct);
   };
   if (bf16) {
     // short outputs (da1 is (B, Q, Sp)): the slabs go to the forward's z scratch instead, which holds nothing the layer
@@ -1797,7 +1797,7 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
                            t_lo, T, grow + (size_t)l * batch * 128);
       if (has_ctx) {  // (behind the layer's reduce: the slab scratch is free again; plan_backward asked for every layer)
         int c_chunks = 0, c_chunk_t = 0;
-        (void)bwd_dz_wgrs64_fits(pl.cus, t_lo, T, batch, pl.cx_bias.p, pl.cx_bias.floats, pl.cx_slab.p, pl.cx_slab.floats,
+        (void)bwd_pass256_fits(pl.cus, t_lo, T, batch, pl.cx_bias.p, pl.cx_bias.floats, pl.cx_slab.p, pl.cx_slab.floats,
                                     &c_chunks, &c_chunk_t);
         launch_bwd_dctx_wgctx64(fc, co, batch, pl.cx_bias.p, pl.cx_slab.p, c_chunks, c_chunk_t, s);
       }

@@ -28,6 +28,7 @@ KERNELS = [
     "fused_layer64s_bf16_kernel<false, false>", "fused_layer64s_bf16_kernel<true, false>",
     "fused_layer64s_bf16_kernel<false, true>",
     "fused_layer64s_kernel<false>", "fused_layer64s_kernel<true>", "fused_layer64s_ctxw2_kernel",
+    "bwd_dz_wgrs64_kernel", "bwd_dctx_wgctx64_kernel", "bwd_dx_wgfg64_kernel",
 ]
 PREFIXES = ["dense_strip_bf3_kernel<"]  # every instantiation sequence.hip emits
 REPORTED = ["fs3_pack_kernel", "fb16_pack_kernel", "fb16c_pack_kernel", "fsc_pack_kernel"]
@@ -83,7 +84,8 @@ def kernels_of(path):
 
 
 # The kernels' LDS is dynamic, so the compiler reports 0 bytes: what their launchers pass instead (the constants of
-# fused_bwd_l.h, fused_fwd_bf3.h and fused_bf16.h; the bias forms add GBIAS_LDS_BYTES = 512).  Unchanged by a refactor
+# fused_bwd_l.h, fused_fwd_bf3.h and fused_bf16.h; the bias forms add GBIAS_LDS_BYTES = 512).  The two 256-thread passes
+# of fused_bwd.h declare theirs statically: the compiler reports the same figure.  Unchanged by a refactor
 # that leaves those constants alone; kept here so that the file this script writes says what a workgroup occupies.
 LAUNCH_LDS_BYTES = {
     "bwd_layer64_kernel<false>": 153600, "bwd_layer64_kernel<true>": 153600,                      # FBL_LDS_BYTES
@@ -94,6 +96,8 @@ LAUNCH_LDS_BYTES = {
     "fused_layer64s_bf16_kernel<false, true>": 66560,                                             # FB16C_LDS_BYTES
     "fused_layer64s_kernel<false>": 99328, "fused_layer64s_kernel<true>": 132096,                 # F32_STRIP(_CTX)_LDS_BYTES
     "fused_layer64s_ctxw2_kernel": 163840,                                                        # FSC_LDS_BYTES
+    "bwd_dz_wgrs64_kernel": 69632, "bwd_dctx_wgctx64_kernel": 69632,            # static: (128 + 64 + 64) x W2_LD x 4
+    "bwd_dx_wgfg64_kernel": 139264,                                                               # FBB_LDS_FLOATS x 4
 }
 
 

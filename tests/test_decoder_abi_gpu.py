@@ -475,7 +475,7 @@ class _Switch:
 
 def _halves_fit(c, cus):
     """Whether the two fused halves (form 2) find their slabs at layer 0, the longest (sequence.hip halves_geometry):
-    fused_bwd.h bwd_dz_wgrs64_fits (chunks from fb_chunks, two workgroups per CU; 128 x 64 floats and 128 bias sums
+    fused_bwd.h bwd_pass256_fits (chunks from fb_chunks, two workgroups per CU; 128 x 64 floats and 128 bias sums
     each) and bwd_dx_wgfg64_fits (one per CU; 128 x 128 floats each, behind the first half's), in BwdPlan::slab, which
     is da1 less the BwdPlan::bias2 reservation"""
     Sp = N.lib().mvn_padded_len(c.S + 31)

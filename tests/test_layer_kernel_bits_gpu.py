@@ -1,9 +1,10 @@
-"""GPU: the layer kernels compute what they computed BEFORE the two layer backward kernels (fp32 as bf16 x 3, and
-bf16) shared one body (csrc/bwd_layer64_body.inc): SHA-256 of the logits, of every parameter gradient and of the
-context's gradient, for one training step per mode, against a recording made on an MI355X from a library built at the
-commit before that change (tests/golden/layer_kernels_sha256.json; its header names the commit, the device and its CU
-count).  The fixture also holds the hashes of every case's input bytes, so that an input that drifted is told apart
-from a kernel that changed.
+"""GPU: the layer kernels compute what they computed BEFORE their bodies were shared -- the two one-kernel layer
+backward kernels (csrc/bwd_layer64_body.inc), the forward strip kernels (csrc/fwd_layer64s_body.inc) and the two
+256-thread passes of the two-half backward (csrc/bwd_half64_body.inc): SHA-256 of the logits, of every parameter
+gradient and of the context's gradient, for one training step per mode, against a recording made on an MI355X from a
+library built at the commit before such a change (tests/golden/layer_kernels_sha256.json; its header names the commit,
+the device and its CU count).  The fixture also holds the hashes of every case's input bytes, so that an input that
+drifted is told apart from a kernel that changed.
 
 One case per mode, each asserting its ``mvn_last_backward_form()``:
 
@@ -15,6 +16,8 @@ One case per mode, each asserting its ``mvn_last_backward_form()``:
     bf16-ctx      MVN_BWD_FORM_BF16_CTX     bwd_layer64_bf16_kernel<false, true>
     fp32-mfma     MVN_BWD_FORM_ONE          as fp32, behind fused_layer64s_kernel<false>
     fp32-mfma-ctx MVN_BWD_FORM_ONE          as fp32-ctx, behind fused_layer64s_kernel<true>
+    fp32-halves   MVN_BWD_FORM_HALVES       bwd_dz_wgrs64_kernel and bwd_dx_wgfg64_kernel (MOVENET_HIP_BWD_FORM=split)
+    fp32-ctx-halves MVN_BWD_FORM_HALVES     both halves and bwd_dctx_wgctx64_kernel in the first half's chunks (split)
 
 and the forward of each mode runs the matching strip kernel (fused_layer64s_bf3_kernel<false | true>,
 fused_layer64s_ctxw2_kernel, fused_layer64s_bf16_kernel<...>), all of them one body (csrc/fwd_layer64s_body.inc).  The
@@ -28,7 +31,9 @@ convs (the label's come from ``rowsum``), ``global_embedding.weight`` (from ``de
 Shape: C = K = 64, layer_size 3, stack_size 2 (dilations 1, 2, 4, 1, 2, 4; receptive field 16), Q = 64, batch 32,
 T = 2600 = 40 x 64 + 40.  fp32-ctx and fp32-mfma-ctx run at Q = 128: the fp32 plan keeps the conditioned layers' second
 A' | P0 pair in the dlogit tensor, which holds it from Q = 128 on; at Q = 64 it takes the two-half form and
-bwd_layer64_kernel<true> does not run there (the layer kernels never see Q).
+bwd_layer64_kernel<true> does not run there (the layer kernels never see Q).  The two halves cases run at Q = 128 as
+well: both halves' slabs of a layer lie in da1 at once, 14 x 32 x 8192 + 7 x 32 x 16384 = 7.34 M floats (and 57 344 bias
+partials), which da1 holds at Q = 128 and not at Q = 64; with less the plan takes the two-kernel forms.
 
 * Tiles.  A layer's t_lo is 1, 3, 7, 8, 10 or 14, never a multiple of 64: tile 0 is an edge tile, so is tile 40 (columns
   2560 .. 2599), and tiles 1 .. 39 are interior (tile 39 ends at 2560, and 2560 + up_d <= 2600).
@@ -40,6 +45,12 @@ bwd_layer64_kernel<true> does not run there (the layer kernels never see Q).
   the loop (edge in chunk 0, interior elsewhere), interior tiles prefetched in parts between the slots (spread), and in
   the last chunk the edge tile 40 prefetched inside the loop (gload_r_edge, set_zero_flags(.., false)).
   test_chunk_arithmetic checks this paragraph with the planner's formula.
+* The halves' chunks (bwd_pass256_fits, bwd_dx_wgfg64_fits).  The first half and the context pass run two workgroups per
+  CU: 16 chunks wanted, 41 tiles in chunks of 3, that is 14 chunks, the last one tiles 39 .. 40.  Every workgroup
+  prefetches at least one tile inside its loop; chunk 0 loads the edge tile 0 in front of the loop, the last chunk
+  prefetches the edge tile 40 inside it.  In fp32-ctx-halves the context pass runs in exactly these chunks from the
+  same scratch (fp32-ctx has it in the layer kernel's chunks of 6).  The second half runs one workgroup per CU: the
+  7 chunks of 6 above, interior tiles prefetched in parts, tile 40 prefetched by gload_edge inside the loop.
 * Forward chunks (fb_chunks with a granule of 8 waves x 32 columns = 256): ceil(2600 / 256) = 11 rounds over at most 8
   chunks, so a chunk is 2 rounds = 512 columns: every wave of chunks 0 .. 4 takes two strips (next-strip prefetch with a
   live next strip, the old-skip loads across strips), the last chunk holds columns 2560 .. 2599 only.
@@ -53,7 +64,9 @@ make_state_dict.
 Before the recording the parent's library ran every case twice, in separate processes: every tensor of every case
 came out with the same bytes both times, so none is left out of the fixture.  (The fixture was recorded again, all
 eight cases from one library, when the two fp32-mfma cases joined: the two new cases reproduced in two processes, and
-the six older cases' hashes came out as in the first recording.)
+the six older cases' hashes came out as in the first recording.  Likewise when the two halves cases joined: each ran
+twice in separate processes from the parent's library, every tensor came out with the same bytes both times, so none is
+left out; the eight older cases' hashes are the ones recorded before.)
 
 Recording: with MOVENET_LAYER_KERNELS_RECORD=<commit> the test writes the fixture instead of comparing.  That is only
 worth something from the parent's library, so it refuses to run unless MOVENET_HIP_LIB names the library to record
@@ -82,16 +95,19 @@ B, T, C, G, RF, CUS = 32, 2600, 64, 4, 16, 256
 T_LO = (1, 3, 7, 8, 10, 14)  # first valid column of each layer's outputs: the dilations summed
 CTX = "context"  # the key the gradient of the context is filed under
 
-# case -> (forward_precision, conditioning, Q, expected backward form, MOVENET_HIP_FORWARD_MFMA or None)
+# case -> (forward_precision, conditioning, Q, expected backward form, the case's environment)
+MFMA_F32, SPLIT = {"MOVENET_HIP_FORWARD_MFMA": "f32"}, {"MOVENET_HIP_BWD_FORM": "split"}
 CASES = {
-    "fp32": ("fp32", None, 64, N.BWD_FORM_ONE, None),
-    "fp32-ctx": ("fp32", "ctx", 128, N.BWD_FORM_ONE, None),
-    "fp32-label": ("fp32", "label", 64, N.BWD_FORM_ONE_GLOBAL, None),
-    "bf16": ("bf16", None, 64, N.BWD_FORM_BF16, None),
-    "bf16-label": ("bf16", "label", 64, N.BWD_FORM_BF16_GLOBAL, None),
-    "bf16-ctx": ("bf16", "ctx", 64, N.BWD_FORM_BF16_CTX, None),
-    "fp32-mfma": ("fp32", None, 64, N.BWD_FORM_ONE, "f32"),
-    "fp32-mfma-ctx": ("fp32", "ctx", 128, N.BWD_FORM_ONE, "f32"),
+    "fp32": ("fp32", None, 64, N.BWD_FORM_ONE, {}),
+    "fp32-ctx": ("fp32", "ctx", 128, N.BWD_FORM_ONE, {}),
+    "fp32-label": ("fp32", "label", 64, N.BWD_FORM_ONE_GLOBAL, {}),
+    "bf16": ("bf16", None, 64, N.BWD_FORM_BF16, {}),
+    "bf16-label": ("bf16", "label", 64, N.BWD_FORM_BF16_GLOBAL, {}),
+    "bf16-ctx": ("bf16", "ctx", 64, N.BWD_FORM_BF16_CTX, {}),
+    "fp32-mfma": ("fp32", None, 64, N.BWD_FORM_ONE, MFMA_F32),
+    "fp32-mfma-ctx": ("fp32", "ctx", 128, N.BWD_FORM_ONE, MFMA_F32),
+    "fp32-halves": ("fp32", None, 128, N.BWD_FORM_HALVES, SPLIT),
+    "fp32-ctx-halves": ("fp32", "ctx", 128, N.BWD_FORM_HALVES, SPLIT),
 }
 
 
@@ -160,10 +176,21 @@ def test_chunk_arithmetic():
         chunks, per_chunk, last = _chunks(T, n, 64)
         assert chunks <= n and last >= 5 and per_chunk >= 5, (n, chunks, per_chunk, last)
     assert _chunks(T, CUS // B, 256) == (6, 2, 1)  # forward: two strips per wave in chunks 0 .. 4
+    # the halves (MOVENET_HIP_BWD_FORM=split).  A layer's tiles start at (t_lo & ~31) = 0: its span is T for every layer
+    assert all(t < 32 for t in T_LO)
+    # first half and context pass, two workgroups per CU: every workgroup prefetches inside its loop (>= 2 tiles), chunk 0
+    # starts on the edge tile 0, the last chunk is tiles 39 .. 40 and prefetches the edge tile 40
+    assert _chunks(T, 2 * CUS // B, 64) == (14, 3, 2) and 13 * 3 == 39 and 40 * 64 < T < 41 * 64
+    # second half, one per CU: interior tiles prefetched in parts, the last chunk tiles 36 .. 40 with the edge tile
+    # prefetched in the loop
+    assert _chunks(T, CUS // B, 64) == (7, 6, 5)
+    # both halves' slabs of a layer and the first half's bias partials: in da1 (B, Q, Sp >= T - RF) at Q = 128, not at 64
+    need = 14 * B * 128 * 64 + 7 * B * 128 * 128 + 14 * B * 128
+    assert B * 64 * T < need <= B * 128 * (T - RF)
 
 
 def run_case(case: str) -> dict:
-    """One training step of ``case`` (the caller has set the case's MOVENET_HIP_FORWARD_MFMA)."""
+    """One training step of ``case`` (the caller has set the case's environment)."""
     from movenet_amd.wavenet import WaveNet
     precision, cond, Q, form, _ = CASES[case]
     inp, full = _inputs(Q), _weights(Q)
@@ -224,8 +251,8 @@ def _record(case: str, got: dict) -> None:
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", list(CASES))
 def test_outputs_equal_the_recording(monkeypatch, case):
-    if CASES[case][4]:
-        monkeypatch.setenv("MOVENET_HIP_FORWARD_MFMA", CASES[case][4])  # (read again by the passes: MOVENET_DEBUG_GUARD)
+    for name, value in CASES[case][4].items():
+        monkeypatch.setenv(name, value)  # (read again by the passes: MOVENET_DEBUG_GUARD)
     if not RECORD:
         with open(FIXTURE) as f:
             fixture = json.load(f)
