@@ -792,6 +792,20 @@ int mvn_adamw_ema_step(float *param, const float *grad, float *exp_avg, float *e
 int mvn_mu_law_encode(const float *x, int32_t *index, size_t n, int classes, void *stream);
 int mvn_mu_law_decode(const int32_t *index, float *x, size_t n, int classes, void *stream);
 
+/* Finished samples to 16-bit PCM, for handing audio out while it is being generated: for row b < batch and column
+ * j < n, pcm[b * pcm_stride + j] is the PCM value of class samples[b * sample_stride + t0 + j].  To the bit, that is
+ * what the sample logger's WAV writer stores for mvn_mu_law_decode of the class: the float mvn_mu_law_decode gives,
+ * then (in double) clipped to [-1, 1], multiplied by 32767 and rounded half to even.  The value depends on the class
+ * alone; a class outside [0, classes) is clamped to the nearest end, as the generators clamp a pick.
+ *   samples  DEVICE (batch, sample_stride) int32, e.g. the generators' sample buffer
+ *   pcm      DEVICE int16, rows pcm_stride elements apart (2-byte aligned is enough; nothing outside [0, n) of a
+ *            row is written)
+ * One launch, a pure stream.  MVN_ERR_BAD_ARG with a mvn_last_error() text, before any launch: a NULL pointer,
+ * batch < 1, n < 0, t0 < 0, t0 + n > sample_stride, pcm_stride < n, classes outside 2 .. 32768.  n == 0 is MVN_OK
+ * without a launch. */
+int mvn_pcm16_chunk(const int32_t *samples, int batch, int sample_stride, int t0, int n, int classes, int16_t *pcm,
+                    int pcm_stride, void *stream);
+
 /* The loader's waveform front end (movenet/dataset.py:253-289 behind the decoder): a batch of clips of different
  * lengths, as interleaved int16 PCM in one upload, -> (batch, n_out) int32 class indices.  Per clip: channel mean of
  * pcm / 32768; resample of the whole clip to n_out frames by torchaudio's sinc_interp_hann rule (lowpass_filter_width

@@ -356,9 +356,86 @@ static int audio_frontend_launch(const char *what, const int16_t *pcm, long long
   return check_hip(hipGetLastError(), (std::string(what) + " (quantise)").c_str());
 }
 
+// ---- finished samples to 16-bit PCM (mvn_pcm16_chunk) ----------------------------------------------------------------
+// Class q of column t0 + j of row b -> pcm[b pcm_stride + j]: the mu-law expansion of mu_law_decode_kernel (its float
+// expression, so its bits), then what the sample logger's WAV writer does to that float in float64 numpy: clip to
+// [-1, 1], times 32767, round half to even.  The value depends on the class alone; a class outside [0, Q) is clamped,
+// as the generators clamp a pick.
+//
+// A pure stream.  Thread i of a row owns the four columns h + 4 i .. h + 4 i + 3, h = 1 where the row's first PCM
+// element sits on an odd int16 (so that every quad starts on 4 bytes): one 16-byte load of the int32 columns (they are
+// only 4-byte aligned: the load is typed so), two int16 pairs packed into one 8-byte store (typed as 4-byte aligned).
+// The thread behind the last full quad writes what is left -- the head column where h = 1 and up to three tail
+// columns: a packed pair where two are left, single int16 stores otherwise.  Nothing outside [0, n) of a row is read
+// or written.
+constexpr int kPcmThreads = 256;
+
+typedef int32_t pcm_i32x4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t pcm_u32x2 __attribute__((ext_vector_type(2), aligned(4)));
+
+__device__ __forceinline__ uint32_t pcm16_of(int q, int Q, float mu, float lmu) {
+  q = min(max(q, 0), Q - 1);
+  const float y = ((float)q / mu) * 2.0f - 1.0f;  // (the expression of mu_law_decode_kernel)
+  const float x = copysignf((expf(fabsf(y) * lmu) - 1.0f) / mu, y);
+  const double v = fmin(fmax((double)x, -1.0), 1.0) * 32767.0;
+  return (uint32_t)(uint16_t)(int16_t)(int)rint(v);  // rint: half to even, as numpy's round
+}
+
+__global__ __launch_bounds__(kPcmThreads) void pcm16_chunk_kernel(const int32_t *__restrict__ samples, int batch,
+                                                                  int sample_stride, int t0, int n, int Q,
+                                                                  int16_t *__restrict__ pcm, int pcm_stride) {
+  const float mu = (float)(Q - 1), lmu = log1pf(mu);
+  const int i = blockIdx.x * kPcmThreads + threadIdx.x;
+  for (int b = blockIdx.y; b < batch; b += gridDim.y) {
+    const int32_t *src = samples + (size_t)b * sample_stride + t0;
+    int16_t *dst = pcm + (size_t)b * pcm_stride;
+    const int h = (int)(((uintptr_t)dst >> 1) & 1u);  // n >= 1 here: the head column exists
+    const int quads = (n - h) / 4;
+    if (i < quads) {
+      const int c = h + 4 * i;
+      const pcm_i32x4 q = *(const pcm_i32x4 *)(src + c);
+      pcm_u32x2 w;
+      w.x = pcm16_of(q.x, Q, mu, lmu) | (pcm16_of(q.y, Q, mu, lmu) << 16);
+      w.y = pcm16_of(q.z, Q, mu, lmu) | (pcm16_of(q.w, Q, mu, lmu) << 16);
+      *(pcm_u32x2 *)(dst + c) = w;
+    } else if (i == quads) {
+      if (h) dst[0] = (int16_t)pcm16_of(src[0], Q, mu, lmu);
+      int c = h + 4 * quads;  // 0 .. 3 columns left, the first of them on 4 bytes
+      if (n - c >= 2) {
+        *(uint32_t *)(dst + c) = pcm16_of(src[c], Q, mu, lmu) | (pcm16_of(src[c + 1], Q, mu, lmu) << 16);
+        c += 2;
+      }
+      if (c < n) dst[c] = (int16_t)pcm16_of(src[c], Q, mu, lmu);
+    }
+  }
+}
+
 }  // namespace mvn
 
 extern "C" {
+
+int mvn_pcm16_chunk(const int32_t *samples, int batch, int sample_stride, int t0, int n, int classes, int16_t *pcm,
+                    int pcm_stride, void *stream) {
+  if (!samples || !pcm) {
+    mvn::set_error("mvn_pcm16_chunk: bad argument (NULL samples or pcm)");
+    return MVN_ERR_BAD_ARG;
+  }
+  if (batch < 1 || n < 0 || t0 < 0 || (long long)t0 + (long long)n > (long long)sample_stride || pcm_stride < n) {
+    mvn::set_error("mvn_pcm16_chunk: bad argument (batch %d, t0 %d, n %d, sample_stride %d, pcm_stride %d)", batch, t0,
+                   n, sample_stride, pcm_stride);
+    return MVN_ERR_BAD_ARG;
+  }
+  if (classes < 2 || classes > 32768) {
+    mvn::set_error("mvn_pcm16_chunk: bad argument (classes %d outside 2 .. 32768)", classes);
+    return MVN_ERR_BAD_ARG;
+  }
+  if (n == 0) return MVN_OK;
+  const int threads = n / 4 + 1;  // one per quad and the one behind them
+  const dim3 grid((threads + mvn::kPcmThreads - 1) / mvn::kPcmThreads, batch < 65535 ? batch : 65535);
+  hipLaunchKernelGGL(mvn::pcm16_chunk_kernel, grid, dim3(mvn::kPcmThreads), 0, (hipStream_t)stream, samples, batch,
+                     sample_stride, t0, n, classes, pcm, pcm_stride);
+  return mvn::check_hip(hipGetLastError(), "pcm16_chunk");
+}
 
 size_t mvn_audio_frontend_scratch_floats(int batch, int n_out) {
   if (batch < 1 || n_out < 1) return 0;

@@ -438,6 +438,17 @@ class RingGenerator:
         self._run(self.t, t_end, self.n_given)
         self.t = t_end
 
+    def stream(self, n_new: int, chunk: int = 4000):
+        """Generate ``n_new`` further samples per sequence (after ``prime()``) and hand them out while they are being
+        made: yields ``(t0, pcm)`` per launch of ``chunk`` steps (the last may be shorter) -- ``pcm`` the (batch, n)
+        int16 numpy view of a pinned host buffer holding the 16-bit PCM (``mvn_pcm16_chunk``) of the columns
+        [t0, t0 + n) just finished, valid until the next ``next()``.  Launch k + 1 is enqueued before the host waits
+        for chunk k, so the GPU does not idle while the consumer handles a chunk.  A hand-off timeout of a pipelined
+        variant raises ``PipeHandoffTimeout`` at the chunk where its status word is seen; ``check_errors()`` runs
+        before the last chunk is handed out.  ``chunk < 1`` is a ValueError, raised here."""
+        chunks = plan_chunks(self.t + 1, min(int(n_new), self.n_total - 1 - self.t), chunk)
+        return _stream_parts([(self, 0, self.batch)], self.batch, self.Q, chunks, self.device, self.check_errors)
+
     def teacher_forced(self, indices: torch.Tensor, logits_t0: int):
         """Feed a fully given (B, n_total) history; return (choices, logits) for
         times >= logits_t0 -- used by the parity tests.  Guided: both rows of a pair are fed the history; the
@@ -697,3 +708,76 @@ class GroupedGenerator:
     def check_errors(self) -> None:
         for g in self.groups:
             g.check_errors()
+
+    def stream(self, n_new: int, chunk: int = 4000):
+        """``RingGenerator.stream`` for the groups: per chunk one launch per group, each group's PCM into its row block
+        of the chunk's buffer, every group's status word beside it, one event behind them all."""
+        t = self.groups[0].t
+        chunks = plan_chunks(t + 1, min(int(n_new), self.n_total - 1 - t), chunk)
+
+        def finish():
+            self._collect()
+            self.check_errors()
+        parts = [(g, b0, b1) for g, (b0, b1) in zip(self.groups, self.bounds)]
+        return _stream_parts(parts, self.batch, self.groups[0].Q, chunks, self.device, finish)
+
+
+def plan_chunks(first: int, n_new: int, chunk: int):
+    """The launches of a streamed generation: ``[(t0, n), ...]`` -- ``n_new`` columns from column ``first`` on in runs
+    of ``chunk``, the last one shorter where ``chunk`` does not divide ``n_new``; none for ``n_new <= 0``.
+    ``chunk < 1`` (or not an integer) is a ValueError."""
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f"chunk must be an integer >= 1, got {chunk!r}")
+    first, n_new = int(first), max(int(n_new), 0)
+    return [(first + k, min(chunk, n_new - k)) for k in range(0, n_new, chunk)]
+
+
+def _stream_parts(parts, batch: int, classes: int, chunks, device, finish):
+    """What ``RingGenerator.stream`` and ``GroupedGenerator.stream`` share.  ``parts``: ``(generator, b0, b1)`` -- the
+    generators that advance together and the rows of the chunk they own; ``finish``: run once everything has been
+    enqueued and has completed, before the last chunk is handed out.
+
+    Per chunk, on the current stream: every part's launch, its ``mvn_pcm16_chunk`` into the device PCM buffer, one
+    non-blocking copy of that buffer and one of every pipelined part's status word into the chunk's pinned host
+    buffer (two of them, taking turns), and an event.  The host enqueues chunk k + 1, then waits for chunk k's event."""
+    if not chunks:
+        finish()
+        return
+    import numpy as np
+    from .ops import pcm16_chunk
+    width = max(n for _, n in chunks)
+    pcm_bytes = (2 * batch * width + 3) // 4 * 4  # the status words start on 4 bytes behind the PCM
+    with torch.cuda.device(device):
+        dev = torch.empty(batch * width, dtype=torch.int16, device=device)
+        words = [g.status_word() for g, _, _ in parts]  # (None for a variant without hand-offs)
+    host = [torch.zeros(pcm_bytes + 4 * len(parts), dtype=torch.uint8).pin_memory() for _ in range(2)]
+    status = [h[pcm_bytes:].view(torch.int32) for h in host]
+    status_np = [s.numpy() for s in status]
+
+    def enqueue(k: int):
+        t0, n = chunks[k]
+        out = dev[:batch * n].view(batch, n)
+        with torch.cuda.device(device):
+            for g, b0, b1 in parts:
+                g.advance(n)
+                pcm16_chunk(g.samples, t0, n, classes, out=out[b0:b1])
+            host[k % 2][:2 * batch * n].view(torch.int16).view(batch, n).copy_(out, non_blocking=True)
+            for i, w in enumerate(words):
+                if w is not None:
+                    status[k % 2][i:i + 1].copy_(w, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record(torch.cuda.current_stream(device))
+        return event
+
+    event = enqueue(0)
+    for k, (t0, n) in enumerate(chunks):
+        ahead = enqueue(k + 1) if k + 1 < len(chunks) else None
+        wait_event(event)
+        if np.any(status_np[k % 2] != 0):
+            raise PipeHandoffTimeout(
+                "movenet_amd: PIPE generator hand-off timed out (pipeline stages not co-resident); the samples from "
+                f"column {t0} on are not valid")
+        if ahead is None:
+            finish()
+        yield t0, host[k % 2][:2 * batch * n].view(torch.int16).view(batch, n).numpy()
+        event = ahead

@@ -977,6 +977,39 @@ def mu_law_decode(index: torch.Tensor, quantization_channels: int) -> torch.Tens
     return out
 
 
+def pcm16_chunk(samples: torch.Tensor, t0: int, n: int, classes: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Columns [t0, t0 + n) of (batch, T) int32 class indices on the GPU -> (batch, n) int16 PCM on the GPU
+    (mvn_pcm16_chunk): to the bit what ``callbacks.write_wav`` stores for ``mu_law_decode`` of those classes, a class
+    outside [0, classes) clamped.  ``samples`` may be a row block or column view of a larger tensor (its last
+    dimension contiguous); ``out``: an int16 tensor of at least (batch, n) whose first n columns are written."""
+    _require_gpu(samples, "samples")
+    if samples.dim() != 2 or samples.dtype != torch.int32 or (samples.shape[1] > 1 and samples.stride(1) != 1):
+        raise ValueError(f"samples must be (batch, T) int32 with contiguous rows, got {tuple(samples.shape)} "
+                         f"{samples.dtype}")
+    B, T = samples.shape
+    t0, n = int(t0), int(n)
+    if t0 < 0 or n < 0 or t0 + n > T:
+        raise ValueError(f"columns [{t0}, {t0 + n}) do not lie inside the {T} of samples")
+    if out is None:
+        out = torch.empty((B, n), dtype=torch.int16, device=samples.device)
+    else:
+        _require_gpu(out, "out")
+        if out.dim() != 2 or out.dtype != torch.int16 or out.shape[0] != B or out.shape[1] < n or \
+                (out.shape[1] > 1 and out.stride(1) != 1) or out.device != samples.device:
+            raise ValueError(f"out must be ({B}, >= {n}) int16 with contiguous rows on {samples.device}")
+    if B == 0 or n == 0:
+        return out[:, :n]
+    # (the row stride bounds what a launch may read of a row: a view's last row ends at its own T columns)
+    stride = samples.stride(0) if B > 1 else T
+    if stride < T or (B > 1 and out.stride(0) < n):
+        raise ValueError("samples / out: rows overlap")
+    with torch.cuda.device(samples.device):
+        N.check(N.lib().mvn_pcm16_chunk(samples.data_ptr(), B, stride, t0, n, int(classes), out.data_ptr(),
+                                        out.stride(0) if B > 1 else max(out.shape[1], n), _stream_ptr(samples.device)),
+                "mvn_pcm16_chunk")
+    return out[:, :n]
+
+
 AUDIO_FRONTEND_MAX_RATIO = 100  # frames <= 100 n_out: the longest clip whose output tile's window fits the LDS
 
 

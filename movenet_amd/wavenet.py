@@ -566,20 +566,14 @@ class WaveNet(nn.Module):
         post = loglik.double() if log_prior is None else loglik.double() + log_prior.to(loglik.device).double()
         return loglik, torch.softmax(post, dim=1).to(torch.float32)
 
-    @torch.no_grad()
-    def generate(self, audio, video=None, global_features=None, n_samples: Optional[int] = None,
-                 temperature=1.0):
-        """wavenet.py:193-239: copy the first RF prompt samples, then generate
-        autoregressively up to n_samples (default: the prompt's own length).
-
-        ``temperature`` takes one value or a sequence of B values, one per sequence of the batch (a temperature sweep
-        on one prompt is ONE launch: repeat the prompt), and ``generate_seed`` likewise; with either a sequence,
-        sequence b draws on its own seed and row b whatever the launch plan.  A wrong length or a bad value is a
-        ValueError before anything runs.  ``global_features``: as in ``forward`` -- the label's vector conditions
-        every step (required for a model built with ``global_classes``).  A model built with ``local_channels`` reads
-        its feature frames from ``generate_local_features`` (the signature stays the reference's, as for the other
-        generation settings; this one is used up by the call): frames for all ``n_samples`` -- the up-sampled (B, C, n_samples) tensor is the
-        generators' ``context``."""
+    def _generate_setup(self, audio, video, global_features, n_samples, temperature, what: str = "generate"):
+        """What ``generate()`` and ``generate_stream()`` share, up to the launch plan: the checks in their order, the
+        settings taken from the attributes, the context, the prompt's class indices, the seed and the plan of
+        ``auto_plan``.  Returns a namespace -- ``idx``, ``rf``, ``n_total``, and ``make`` = None where there is nothing to
+        generate, else ``make(variant, group)`` (a new generator, not yet primed), ``variant`` / ``group`` (0: one
+        launch) of the plan and ``fallback()``: the kernel a timed-out pipelined call is rerun on -- recorded in
+        ``last_generate_fallback`` and announced on stderr."""
+        from types import SimpleNamespace
         from .ops import global_vector
         local_features, self._gen_local_features = self.generate_local_features, None  # (taken: one call uses it)
         self._local_checks(audio, video, local_features,
@@ -606,13 +600,9 @@ class WaveNet(nn.Module):
         n_total = int(audio.shape[2]) if n_samples is None else int(n_samples)
         context = self._context_of(audio, video, local_features, n_total=max(n_total, 1))
         idx = self._indices_of(audio)
+        plan = SimpleNamespace(idx=idx, rf=rf, n_total=n_total, make=None)
         if idx.shape[1] < rf or n_total <= rf:
-            # nothing to generate: the reference returns zeros with the prompt copied in
-            out = torch.zeros(audio.shape[0], audio.shape[1], n_total, dtype=audio.dtype,
-                              device=audio.device)
-            n = min(rf, n_total, audio.shape[2])
-            out[:, :, :n] = audio[:, :, :n]
-            return out
+            return plan
         if seed is None:
             seed = int(torch.empty((), dtype=torch.int64).random_().item())
         state = self._decoder_state()
@@ -627,19 +617,15 @@ class WaveNet(nn.Module):
                   sampling=self.generate_sampling, top_k=top_k, top_p=top_p)
         if guidance is not None:
             kw["guidance"] = guidance
-        def run(variant, group):
+
+        def make(variant, group):
             if group:
-                gen = GroupedGenerator(self.layer_size, self.stack_size, self.input_channels,
-                                       self.residual_channels, self.skip_channels, state,
-                                       group=group, variant=variant, **kw)
-            else:
-                gen = RingGenerator(self.layer_size, self.stack_size, self.input_channels,
-                                    self.residual_channels, self.skip_channels, state,
-                                    variant=variant, **kw)
-            gen.prime(idx[:, :rf])
-            gen.advance(n_total - rf)
-            gen.check_errors()  # synchronises; never hand unchecked samples on
-            return gen
+                return GroupedGenerator(self.layer_size, self.stack_size, self.input_channels,
+                                        self.residual_channels, self.skip_channels, state,
+                                        group=group, variant=variant, **kw)
+            return RingGenerator(self.layer_size, self.stack_size, self.input_channels,
+                                 self.residual_channels, self.skip_channels, state,
+                                 variant=variant, **kw)
 
         with torch.cuda.device(audio.device):
             if self._gen_variant == N.GEN_AUTO:
@@ -650,21 +636,102 @@ class WaveNet(nn.Module):
                 if variant == N.GEN_PIPE_F16 and idx.shape[0] > max_pipe_batch(self._dims, variant,
                                                                                guided=guidance is not None):
                     kind, group = "grouped", max_pipe_batch(self._dims, variant, guided=guidance is not None)  # groups take turns
-        try:
-            gen = run(variant, group if kind == "grouped" else 0)
-        except PipeHandoffTimeout:
+
+        def fallback():
             # the pipelined kernel needs all its stages co-resident and something else held
             # CUs: rerun THIS call (same prompt, same seed) on a kernel without hand-offs
             with torch.cuda.device(audio.device):
                 lib = N.lib()
                 # (STREAM: C = K = 64, any batch in one launch, conditioned or not -- r4; GENERIC otherwise)
-                fallback = N.GEN_STREAM if guidance is None and lib.mvn_gen_variant(
+                fb = N.GEN_STREAM if guidance is None and lib.mvn_gen_variant(
                     self._dims, N.GEN_STREAM, idx.shape[0]) == N.GEN_STREAM else N.GEN_GENERIC  # (guided: GENERIC)
-            self.last_generate_fallback = fallback
-            name = {N.GEN_STREAM: "STREAM", N.GEN_GENERIC: "GENERIC"}[fallback]
-            print(f"[movenet_amd] generate: pipelined kernel (variant {variant}) timed out waiting for a "
+            self.last_generate_fallback = fb
+            name = {N.GEN_STREAM: "STREAM", N.GEN_GENERIC: "GENERIC"}[fb]
+            print(f"[movenet_amd] {what}: pipelined kernel (variant {variant}) timed out waiting for a "
                   f"co-resident stage; rerunning this call on {name}"
                   + (" -- fp32 arithmetic instead of the fp16 operands asked for" if variant == N.GEN_PIPE_F16
                      else ""), file=sys.stderr, flush=True)
-            gen = run(fallback, 0)
+            return fb
+
+        plan.make, plan.variant, plan.group, plan.fallback = make, variant, group if kind == "grouped" else 0, fallback
+        return plan
+
+    @torch.no_grad()
+    def generate(self, audio, video=None, global_features=None, n_samples: Optional[int] = None,
+                 temperature=1.0):
+        """wavenet.py:193-239: copy the first RF prompt samples, then generate
+        autoregressively up to n_samples (default: the prompt's own length).
+
+        ``temperature`` takes one value or a sequence of B values, one per sequence of the batch (a temperature sweep
+        on one prompt is ONE launch: repeat the prompt), and ``generate_seed`` likewise; with either a sequence,
+        sequence b draws on its own seed and row b whatever the launch plan.  A wrong length or a bad value is a
+        ValueError before anything runs.  ``global_features``: as in ``forward`` -- the label's vector conditions
+        every step (required for a model built with ``global_classes``).  A model built with ``local_channels`` reads
+        its feature frames from ``generate_local_features`` (the signature stays the reference's, as for the other
+        generation settings; this one is used up by the call): frames for all ``n_samples`` -- the up-sampled (B, C, n_samples) tensor is the
+        generators' ``context``."""
+        plan = self._generate_setup(audio, video, global_features, n_samples, temperature)
+        idx, rf, n_total = plan.idx, plan.rf, plan.n_total
+        if plan.make is None:
+            # nothing to generate: the reference returns zeros with the prompt copied in
+            out = torch.zeros(audio.shape[0], audio.shape[1], n_total, dtype=audio.dtype,
+                              device=audio.device)
+            n = min(rf, n_total, audio.shape[2])
+            out[:, :, :n] = audio[:, :, :n]
+            return out
+
+        def run(variant, group):
+            gen = plan.make(variant, group)
+            gen.prime(idx[:, :rf])
+            gen.advance(n_total - rf)
+            gen.check_errors()  # synchronises; never hand unchecked samples on
+            return gen
+
+        try:
+            gen = run(plan.variant, plan.group)
+        except PipeHandoffTimeout:
+            gen = run(plan.fallback(), 0)
         return self._one_hot_of(gen.samples, audio.dtype)
+
+    @torch.no_grad()
+    def generate_stream(self, audio, video=None, global_features=None, n_samples: Optional[int] = None,
+                        temperature=1.0, chunk: int = 4000):
+        """``generate()`` handing the audio out while it is being made: a generator of ``(t0, pcm)`` --
+        ``pcm`` a (B, n) int16 numpy array on the host, the 16-bit PCM of columns [t0, t0 + n) of every sequence, to the
+        bit what ``callbacks.write_wav`` stores for ``ops.mu_law_decode`` of ``generate()``'s classes under the same
+        settings and ``generate_seed``.  First ``(0, pcm)`` of the copied prompt columns [0, RF), then one pair per
+        launch of ``chunk`` steps (the last may be shorter); an array is valid until the next ``next()``.  Where
+        ``generate()`` has nothing to generate, the one pair is its zeros-plus-prompt result: all ``n_samples`` columns,
+        class 0 behind the prompt.
+
+        Same arguments, attributes, checks (in the same order, at the first ``next()``) and launch plan as
+        ``generate()``; ``chunk < 1`` is a ValueError before any of them.  A hand-off timeout of a pipelined kernel
+        before the first generated chunk has been handed out reruns the call on the fallback kernel, as ``generate()``
+        does; later it reaches the caller as ``PipeHandoffTimeout`` -- audio already delivered cannot be taken back."""
+        from .generation import plan_chunks
+        from .ops import pcm16_chunk
+        plan_chunks(0, 0, chunk)  # ValueError before anything is used up
+        plan = self._generate_setup(audio, video, global_features, n_samples, temperature, what="generate_stream")
+        idx, rf, n_total = plan.idx, plan.rf, plan.n_total
+        if plan.make is None:
+            n = min(rf, n_total, int(audio.shape[2]))
+            given = torch.zeros(idx.shape[0], max(n_total, 0), dtype=torch.int32, device=idx.device)
+            given[:, :n] = idx[:, :n]
+            yield 0, pcm16_chunk(given, 0, given.shape[1], self.input_channels).cpu().numpy()
+            return
+        yield 0, pcm16_chunk(idx, 0, rf, self.input_channels).cpu().numpy()
+
+        def chunks_of(variant, group):
+            gen = plan.make(variant, group)
+            gen.prime(idx[:, :rf])
+            return gen.stream(n_total - rf, chunk)
+
+        chunks = chunks_of(plan.variant, plan.group)
+        try:
+            first = next(chunks, None)
+        except PipeHandoffTimeout:
+            chunks = chunks_of(plan.fallback(), 0)
+            first = next(chunks, None)
+        if first is not None:
+            yield first
+            yield from chunks
