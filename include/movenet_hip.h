@@ -368,7 +368,11 @@ typedef struct mvn_fwd_buffers {
  * No buffer has to be initialised: the library reads only what it (or the caller, for the
  * inputs' columns < t_len) has written.  Every argument is checked before the first launch:
  * a call that returns MVN_ERR_BAD_ARG / _BAD_DIMS / _TOO_SHORT / _UNSUPPORTED has written
- * nothing. */
+ * nothing.
+ * index: class of step t of sequence b at index[b * index_stride + t], t < t_len.  A class outside
+ * [0, input_channels) is not an error: it is taken as the nearest end (negative -> 0, too large ->
+ * input_channels - 1), by this call and its siblings and IDENTICALLY by mvn_backward and its siblings,
+ * so the embedding gradient of such a step goes to the table row the forward read. */
 int mvn_forward(const mvn_dims *dims, const mvn_params *params, const int32_t *index,
                 int index_stride, int batch, int t_len, const mvn_fwd_buffers *buf, float *out,
                 int normalize, int remove_last, int save, void *stream);
@@ -442,7 +446,9 @@ typedef struct mvn_bwd_buffers {
  * Every refusal of mvn_backward and its siblings below is decided in front of the first launch -- also the
  * ones that depend on the scratch sizes (buffers the bf16 / one-kernel layer backward cannot run, a context
  * pass whose slabs do not fit at some layer, input_channels > 8192 without dense audio): a refused call has
- * written nothing and leaves mvn_last_backward_form() as it was. */
+ * written nothing and leaves mvn_last_backward_form() and mvn_last_embed_form() as they were.
+ * index: as in mvn_forward -- a class outside [0, input_channels) is taken as the nearest end, identically in
+ * both passes (every form of the embedding gradient clamps as the forward's gather does). */
 int mvn_backward(const mvn_dims *dims, const mvn_params *params, const mvn_param_grads *grads,
                  const int32_t *index, int index_stride, int batch, int t_len,
                  const mvn_fwd_buffers *fwd, const mvn_bwd_buffers *bwd, const float *out,
@@ -472,6 +478,21 @@ int mvn_backward_bf16(const mvn_dims *dims, const mvn_params *params, const mvn_
 #define MVN_BWD_FORM_ONE_GLOBAL 5 /* form 3 with the label's row sums: mvn_backward_global */
 #define MVN_BWD_FORM_BF16_GLOBAL 6 /* form 4 with the label's row sums: mvn_backward_bf16_global */
 int mvn_last_backward_form(void);
+
+/* Diagnostic: which form the embedding gradient (the causal conv's weight gradient) of the process's last
+ * mvn_backward or sibling took -- 0 none yet, 1 the dense product (fwd->dense_audio given), 2 the product on the
+ * matrix cores (C = 64, Q = 256), 3 the LDS read-modify-write kernel (C = 64, Q < 256), 4 one table copy per
+ * (chunk, sequence) summed in chunk order, 5 global atomics.  Forms 2 to 4 need room for their per-chunk tables in
+ * the backward's scratch; a call without that room (or, for form 4, with a table that is no multiple of 64 floats)
+ * takes form 5.  Forms 2 to 4 add every table word's steps and copies in a fixed order and give the same bits
+ * whenever they run; form 5 adds to the table with global atomics, so its last bits vary from run to run.
+ * Tests assert on it for the reason given at mvn_last_backward_form; a refused call leaves it as it was. */
+#define MVN_EMBED_FORM_DENSE 1
+#define MVN_EMBED_FORM_MFMA 2
+#define MVN_EMBED_FORM_LDS 3
+#define MVN_EMBED_FORM_TABLES 4
+#define MVN_EMBED_FORM_ATOMICS 5
+int mvn_last_embed_form(void);
 
 /* ------------------------------------------------------------------------
  * Global conditioning on a class label (BUILD DEFINITION): sequence b carries a

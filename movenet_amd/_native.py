@@ -29,6 +29,8 @@ BLOCK_FORM_GENERIC, BLOCK_FORM_FUSED64 = 1, 2  # mvn_block_last_form: the kernel
 BWD_FORM_ONE_GLOBAL = 5  # mvn_backward_global: BWD_FORM_ONE with the label's row sums of df | dg
 BWD_FORM_BF16_GLOBAL = 6  # mvn_backward_bf16_global: BWD_FORM_BF16 with the row sums formed inside the layer kernel
 BWD_FORM_BF16_CTX = 7  # mvn_backward_bf16_ctx: BWD_FORM_BF16 writing df | dg for the fp32 context pass
+# mvn_last_embed_form: the embedding gradient's kernel form in the last backward (include/movenet_hip.h)
+EMBED_FORM_DENSE, EMBED_FORM_MFMA, EMBED_FORM_LDS, EMBED_FORM_TABLES, EMBED_FORM_ATOMICS = 1, 2, 3, 4, 5
 SAMPLE_REFERENCE, SAMPLE_MODEL = 0, 1  # mvn_generate_ex's rule of a sampled step (include/movenet_hip.h)
 SAMPLING_RULES = {"reference": SAMPLE_REFERENCE, "model": SAMPLE_MODEL}
 LOSS_REFERENCE, LOSS_MODEL = 0, 1  # mvn_softmax_ce_*_ex's loss rule (include/movenet_hip.h)
@@ -174,6 +176,7 @@ SIGNATURES = {
                                     C.POINTER(BwdBuffers), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_void_p]),
     "mvn_last_backward_form": (C.c_int, []),
+    "mvn_last_embed_form": (C.c_int, []),
     "mvn_context_add_global": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mvn_global_fast_path": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_int]),
     "mvn_global_bias": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

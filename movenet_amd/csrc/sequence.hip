@@ -585,39 +585,57 @@ __global__ __launch_bounds__(256) void embed4_kernel(const float *__restrict__ c
 // Gradient of the causal conv on a one-hot input = a scatter-add of dx0 columns into the two
 // embedding tables (tap 1 at class idx[t], tap 0 at idx[t-1]).  A workgroup owns `cg` channels
 // and EG_CHUNK time steps of one sequence and accumulates them in an LDS copy of its table
-// slice [cg][Q][2] (ds_add_f32: lanes walk t, so a collision needs two lanes of one wave
-// on the same class); the slice is then added to HBM once -- T/EG_CHUNK times fewer
-// global atomics than one per (channel, time step).
-constexpr int EG_CHUNK = 1024;
+// slice [cg][Q][2]; the slice is then added to HBM once -- T/EG_CHUNK times fewer global
+// atomics than one per (channel, time step).
+// EVERY TABLE WORD HAS ONE OWNER, which adds its steps in ascending time: thread (c, r) = (tid / J, tid % J), J a
+// power of two with cg J <= 1024, owns the classes q = r (mod J) of channel c, both taps.  The chunk's classes are
+// staged in LDS once and dx0 in tiles of EG_TILE steps (coalesced); every thread then walks the tile's steps and
+// adds where the step's class is one of its own -- plain LDS read-modify-write, no atomics, so a table copy has
+// the same bits whenever it is formed.  Tile rows are EG_TILE + 1 floats apart: the channels of one wave read
+// different LDS banks.
+// cg = embed_grad_channels(C, Q): the table slice within 64 KB and at most EG_MAX_CG channels, so that the LDS
+// request (slice + 8 KB of classes + tile <= 105 KB) fits the 160 KB of a CU at every C, and J >= 16.
+constexpr int EG_CHUNK = 1024, EG_TILE = 128, EG_MAX_CG = 64;
+static int embed_grad_channels(int C, int Q) { return std::max(1, std::min(std::min(C, EG_MAX_CG), 8192 / Q)); }
+static size_t embed_grad_lds_bytes(int cg, int Q) {
+  return ((size_t)cg * Q * 2 + 2 * EG_CHUNK + (size_t)cg * (EG_TILE + 1)) * sizeof(float);
+}
+static_assert(((size_t)8192 * 2 + 2 * EG_CHUNK + (size_t)EG_MAX_CG * (EG_TILE + 1)) * sizeof(float) <= 160 * 1024,
+              "embed_grad_kernel: table slice + classes + dx0 tile exceed a CU's LDS");
 __global__ __launch_bounds__(1024) void embed_grad_kernel(float *__restrict__ dcw,
                                                          const int32_t *__restrict__ idx, int idx_stride,
-                                                         Act dx0, int C, int Q, int T, int cg,
+                                                         Act dx0, int C, int Q, int T, int cg, int J,
                                                          float *__restrict__ part) {
-  extern __shared__ float tab[];  // [cg][Q][2]
+  extern __shared__ float tab[];  // [cg][Q][2] | classes of tap 1, of tap 0: [EG_CHUNK] each | dx0 tile [cg][EG_TILE + 1]
+  int *const s1 = (int *)(tab + (size_t)cg * Q * 2), *const s0 = s1 + EG_CHUNK;
+  float *const xs = (float *)(s0 + EG_CHUNK);
+  const int tid = threadIdx.x;
   const int b = blockIdx.z, c0 = blockIdx.y * cg, t0 = blockIdx.x * EG_CHUNK;
   const int nc = min(cg, C - c0), t1 = min(T, t0 + EG_CHUNK);
-  for (int i = threadIdx.x; i < cg * Q * 2; i += blockDim.x) tab[i] = 0.f;
-  __syncthreads();
+  for (int i = tid; i < cg * Q * 2; i += blockDim.x) tab[i] = 0.f;
   const int32_t *ib = idx + (size_t)b * idx_stride;
-  for (int t = t0 + threadIdx.x; t < t1; t += blockDim.x) {
-    const int q1 = min(max(ib[t], 0), Q - 1), q0 = t > 0 ? min(max(ib[t - 1], 0), Q - 1) : -1;
-    // eight channels' loads in flight per thread (one at a time, each in front of its two LDS
-    // atomics, the kernel was a chain of load latencies: 183 us for 65 MB)
-    int c = 0;
-    for (; c + 8 <= nc; c += 8) {
-      float g[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) g[j] = *dx0.at(b, c0 + c + j, t);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        atomicAdd(&tab[((c + j) * Q + q1) * 2 + 1], g[j]);
-        if (q0 >= 0) atomicAdd(&tab[((c + j) * Q + q0) * 2 + 0], g[j]);
-      }
+  for (int i = tid; i < EG_CHUNK; i += blockDim.x) {  // (-1: no contribution)
+    const int t = t0 + i;
+    s1[i] = t < t1 ? min(max(ib[t], 0), Q - 1) : -1;
+    s0[i] = t < t1 && t > 0 ? min(max(ib[t - 1], 0), Q - 1) : -1;
+  }
+  const int c = tid / J, r = tid & (J - 1);
+  float *const mine = tab + (size_t)min(c, cg - 1) * Q * 2;
+  for (int tile = 0; t0 + tile < t1; tile += EG_TILE) {
+    __syncthreads();  // the tile before has been read (first pass: the table is zero, the classes are staged)
+    for (int i = tid; i < nc * EG_TILE; i += blockDim.x) {
+      const int cc = i / EG_TILE, t = t0 + tile + i % EG_TILE;
+      xs[cc * (EG_TILE + 1) + i % EG_TILE] = t < t1 ? *dx0.at(b, c0 + cc, t) : 0.f;
     }
-    for (; c < nc; ++c) {
-      const float g = *dx0.at(b, c0 + c, t);
-      atomicAdd(&tab[(c * Q + q1) * 2 + 1], g);
-      if (q0 >= 0) atomicAdd(&tab[(c * Q + q0) * 2 + 0], g);
+    __syncthreads();
+    if (c < nc) {
+      const float *x = xs + c * (EG_TILE + 1);
+      const int n = min(EG_TILE, t1 - t0 - tile);
+      for (int i = 0; i < n; ++i) {
+        const int q1 = s1[tile + i], q0 = s0[tile + i];
+        if ((q1 & (J - 1)) == r) mine[q1 * 2 + 1] += x[i];  // (q1 >= 0 for every step below t1)
+        if (q0 >= 0 && (q0 & (J - 1)) == r) mine[q0 * 2 + 0] += x[i];
+      }
     }
   }
   __syncthreads();
@@ -626,10 +644,10 @@ __global__ __launch_bounds__(1024) void embed_grad_kernel(float *__restrict__ dc
     // (Flushed with atomics, the 128 workgroups per table word queued up at the memory side:
     // 4.2 M device-scope float atomics took ~150 of the kernel's 181 us.)
     float *dst = part + ((size_t)blockIdx.x * gridDim.z + b) * ((size_t)C * Q * 2) + (size_t)c0 * Q * 2;
-    for (int i = threadIdx.x; i < nc * Q * 2; i += blockDim.x) dst[i] = tab[i];
+    for (int i = tid; i < nc * Q * 2; i += blockDim.x) dst[i] = tab[i];
     return;
   }
-  for (int i = threadIdx.x; i < nc * Q * 2; i += blockDim.x) {
+  for (int i = tid; i < nc * Q * 2; i += blockDim.x) {
     const float v = tab[i];
     if (v != 0.f) atomicAdd(dcw + (size_t)c0 * Q * 2 + i, v);
   }
@@ -1430,7 +1448,7 @@ static int plan_backward(const SeqMode &m, const Geometry &g, const mvn_dims *di
   pl.embed = EMBED_DENSE_AUDIO;
   pl.embed_tab = Region{};
   if (!fwd->dense_audio) {
-    if (Q > 8192) {  // channels per workgroup: the table slice [cg][Q][2] fits 64 KB of LDS
+    if (Q > 8192) {  // embed_grad_kernel: one channel's table slice [Q][2] within 64 KB of LDS (embed_grad_channels)
       set_error("mvn_backward: input_channels %d > 8192 not supported by the embedding gradient", Q);
       return MVN_ERR_UNSUPPORTED;
     }
@@ -1627,6 +1645,8 @@ int mvn_forward_f16(const mvn_dims *dims, const mvn_params *p, const int32_t *in
 
 static int g_last_bwd_form = 0;  // (process-wide: autograd runs the backward on a thread of its own)
 int mvn_last_backward_form(void) { return g_last_bwd_form; }
+static int g_last_embed_form = 0;  // BwdPlan::embed of the last backward, as MVN_EMBED_FORM_*
+int mvn_last_embed_form(void) { return g_last_embed_form; }
 
 // m.scratch: the caller's scratch for the one-kernel layer backward (GLOBAL, CTX16, and conditioned fp32 layers, which
 // without it look for that room in dlogit / da1 and take another form where those are too small: short outputs, small
@@ -1670,11 +1690,16 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
   rc = mode_supported(m, g, batch, fwd);  // (there is no fp32 fall-back)
   if (rc) return rc;
   // every region of scratch, every kernel form and every remaining refusal, in front of the first launch: a refused
-  // call has written nothing and leaves mvn_last_backward_form() as it was
+  // call has written nothing and leaves mvn_last_backward_form() and mvn_last_embed_form() as they were
   BwdPlan pl;
   rc = plan_backward(m, g, dims, switches(), cus, batch, fwd, bwd, pl);
   if (rc) return rc;
   g_last_bwd_form = pl.form;
+  g_last_embed_form = pl.embed == EMBED_DENSE_AUDIO ? MVN_EMBED_FORM_DENSE
+                      : pl.embed == EMBED_MFMA      ? MVN_EMBED_FORM_MFMA
+                      : pl.embed == EMBED_LDS       ? MVN_EMBED_FORM_LDS
+                      : pl.embed == EMBED_TABLES    ? MVN_EMBED_FORM_TABLES
+                                                    : MVN_EMBED_FORM_ATOMICS;
   const int *const A_lo = pl.A_lo;
   hipStream_t s = (hipStream_t)stream_;
   const int C = g.C, Kc = g.Kc, Q = g.Q, T = g.T;
@@ -1936,13 +1961,17 @@ static int backward_impl(const mvn_dims *dims, const mvn_params *p, const mvn_pa
     hipLaunchKernelGGL(slab_reduce_kernel<EmbedSlabOp64>, dim3((unsigned)(2 * Q * 64 / 32)), dim3(32 * RED_SEG), 0, s,
                        eo, tab, chunks64 * batch, 2 * Q, 64);
   } else {
-    const int cg = std::max(1, std::min(C, 8192 / Q));
+    const int cg = embed_grad_channels(C, Q);
     const int chunks = (T + EG_CHUNK - 1) / EG_CHUNK;
     const size_t table = (size_t)C * Q * 2;
     float *part = pl.embed == EMBED_TABLES ? tab : nullptr;
+    int J = 1024;  // threads per channel: the largest power of two with cg J <= 1024 (cg <= 64: J >= 16)
+    while (cg * J > 1024) J >>= 1;
+    rc = ensure_max_dynamic_lds((const void *)embed_grad_kernel, "hipFuncSetAttribute(embed_grad)");
+    if (rc) return rc;
     hipLaunchKernelGGL(embed_grad_kernel, dim3(chunks, (C + cg - 1) / cg, batch),
-                       dim3(1024), (size_t)cg * Q * 2 * sizeof(float), s, gr->causal_w, index,
-                       index_stride, dx0, C, Q, T, cg, part);
+                       dim3(1024), embed_grad_lds_bytes(cg, Q), s, gr->causal_w, index,
+                       index_stride, dx0, C, Q, T, cg, J, part);
     if (part) {
       EmbedSlabOp eo;
       eo.dcw = gr->causal_w;

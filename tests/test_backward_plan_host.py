@@ -1,7 +1,7 @@
 """No GPU: the refusals of the full-sequence backward are all decided in front of its first launch (sequence.hip
 plan_backward).  Every call here must refuse, so nothing is ever launched: the buffers are host structs whose device
 pointers are dummy non-null values, and without a device the library plans for 256 CUs.  A refused call leaves
-mvn_last_backward_form() as it was."""
+mvn_last_backward_form() and mvn_last_embed_form() as they were."""
 import ctypes as C
 
 import pytest
@@ -31,11 +31,23 @@ def _rf(layer_size, stack_size):
 
 def _refused(call, rc, text):
     lib = N.lib()
-    form = lib.mvn_last_backward_form()
+    form, embed = lib.mvn_last_backward_form(), lib.mvn_last_embed_form()
     got = call(lib)
     assert got == rc, (got, lib.mvn_last_error().decode())
     assert text in lib.mvn_last_error().decode(), lib.mvn_last_error().decode()
     assert lib.mvn_last_backward_form() == form
+    assert lib.mvn_last_embed_form() == embed
+
+
+def test_embed_form_constants_match_the_header():
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "movenet_hip.h")).read()
+    for name, value in (("DENSE", 1), ("MFMA", 2), ("LDS", 3), ("TABLES", 4), ("ATOMICS", 5)):
+        assert re.search(rf"#define MVN_EMBED_FORM_{name} {value}\b", header), name
+        assert getattr(N, "EMBED_FORM_" + name) == value
+    assert 0 <= N.lib().mvn_last_embed_form() <= 5   # (0: no backward in this process yet)
 
 
 def test_embedding_gradient_refusal_comes_before_every_launch():

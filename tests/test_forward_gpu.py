@@ -292,11 +292,14 @@ def test_fused_backward_kernels_match_two_kernel_forms_and_oracle(monkeypatch, l
 
 @pytest.mark.parametrize("pattern", ["constant", "runs", "pairs"])
 def test_embedding_gradient_with_repeated_classes(pattern):
-    """The C = 64 embedding gradient (embed_grad64_kernel) keeps four time steps in flight per wave and
-    merges equal classes among them before its read-modify-write of the LDS table: inputs whose
-    neighbouring samples repeat a class are the case random indices hardly ever produce.  The
-    length crosses a 1024-step chunk and is no multiple of 4; checked against autograd on the
-    oracle (movenet/modules.py CausalConv1d, the first op of WaveNet.forward)."""
+    """The C = 64, Q = 256 embedding gradient with room for its per-chunk tables: the product form on the matrix
+    cores (embed_grad64_mfma_kernel, asserted below), which builds its one-hot operand from the tile's classes --
+    NOT embed_grad64_kernel, the LDS read-modify-write kernel of Q < 256 that this test was written for and whose
+    merge of equal classes tests/test_embedding_gradient_gpu.py now covers.  Inputs whose neighbouring samples
+    repeat a class are the case random indices hardly ever produce.  The length crosses a 1024-step chunk and is
+    no multiple of 4; checked against autograd on the oracle (movenet/modules.py CausalConv1d, the first op of
+    WaveNet.forward)."""
+    from movenet_amd import _native as N
     from oracle import wavenet_oracle as O
     from movenet_amd.utils.weights import make_state_dict
     cfg = dict(layer_size=3, stack_size=1, input_channels=256, residual_channels=64, skip_channels=64)
@@ -316,6 +319,8 @@ def test_embedding_gradient_with_repeated_classes(pattern):
     m = _model(cfg, sd).train()
     out = m(x.to(DEV), output_unnormalized=False)
     (out * w.to(DEV)).square().mean().backward()
+    torch.cuda.synchronize()
+    assert N.lib().mvn_last_embed_form() == N.EMBED_FORM_MFMA, N.lib().mvn_last_embed_form()
     params = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
     out_o = O.forward(params, dims, x, output_unnormalized=False)
     (out_o * w).square().mean().backward()
