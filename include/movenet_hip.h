@@ -827,6 +827,22 @@ int mvn_mu_law_decode(const int32_t *index, float *x, size_t n, int classes, voi
 int mvn_pcm16_chunk(const int32_t *samples, int batch, int sample_stride, int t0, int n, int classes, int16_t *pcm,
                     int pcm_stride, void *stream);
 
+/* mvn_pcm16_chunk through the DE-EMPHASIS filter, the inverse of mvn_audio_frontend_emph's pre-emphasis, with the
+ * filter's state carried from call to call.  Per row b, columns in order, with x the float mvn_mu_law_decode gives for
+ * the (clamped) class and a = coef, both widened to double:
+ *     y   = ((1 + a) * x) + (a * y_prev)     two products and one sum, each rounded once in double, no fma
+ *     pcm = y clipped to [-1, 1], times 32767, rounded half to even (as above)
+ *     y_prev = y
+ * y_prev is state[b] at entry and is written back to state[b] at exit; the caller zeroes it before a row's column 0.
+ * The recurrence is defined -- and run -- sequentially in time (one wave per row, rows in parallel), so a clip cut into
+ * chunks of any lengths gives the bits of the whole clip in one call.
+ *   state  DEVICE, batch doubles, 8-byte aligned
+ *   coef   in [0, 1)
+ * Refusals as mvn_pcm16_chunk, and: state NULL or not 8-byte aligned, coef outside [0, 1) (NaN included) --
+ * MVN_ERR_BAD_ARG before any launch.  n == 0 is MVN_OK without a launch: the state is left as it is. */
+int mvn_pcm16_deemph_chunk(const int32_t *samples, int batch, int sample_stride, int t0, int n, int classes, float coef,
+                           double *state, int16_t *pcm, int pcm_stride, void *stream);
+
 /* The loader's waveform front end (movenet/dataset.py:253-289 behind the decoder): a batch of clips of different
  * lengths, as interleaved int16 PCM in one upload, -> (batch, n_out) int32 class indices.  Per clip: channel mean of
  * pcm / 32768; resample of the whole clip to n_out frames by torchaudio's sinc_interp_hann rule (lowpass_filter_width
@@ -911,6 +927,27 @@ size_t mvn_audio_frontend_window_scratch_floats(int batch, int width);
 int mvn_audio_frontend_window(const int16_t *pcm, long long pcm_len, const mvn_audio_clip_window *clips, int batch,
                               int classes, int width, int normalize, float *y, float *scratch, int32_t *index,
                               void *stream);
+
+/* Any of the three front ends above with PRE-EMPHASIS in front of mu-law.  `form` says which call this one stands for
+ * and with it what `clips` points at (mvn_audio_clip, _var or _window records); every other argument, the device-side
+ * refusals and the first launch (the resample, y and the (min, max) partials) are that call's.  With vn[k] the value that
+ * call hands to mu-law for column k of a row -- normalised when `normalize`, the raw resample otherwise -- the second
+ * launch quantises
+ *     e[k] = (vn[k] - coef * vn[k-1]) / (1 + coef),   vn[-1] := 0,
+ * in float, each operation rounded once (no fma), so |e| <= 1 wherever |vn| <= 1.  k - 1 is column k - 1 of the SAME
+ * ROW: the row's first column has no predecessor, also where a window starts in the middle of its file.  The
+ * normalisation range is the un-emphasised row's, as before.
+ *   coef   in [0, 1); 0 gives the indices of the call it stands for
+ *   emph   DEVICE (batch, width) fp32: e, written in full -- 0 in the columns behind a row's n_out, which get the
+ *          silence class as before, and in a refused row, whose indices are -1 as before
+ * emph == NULL, a coef outside [0, 1) (NaN included) or an unknown form is MVN_ERR_BAD_ARG before any launch, like the
+ * host refusals of the call it stands for.  Two launches, no atomics: bit-reproducible. */
+#define MVN_AUDIO_FORM_CLIP 0
+#define MVN_AUDIO_FORM_VAR 1
+#define MVN_AUDIO_FORM_WINDOW 2
+int mvn_audio_frontend_emph(int form, const int16_t *pcm, long long pcm_len, const void *clips, int batch, int classes,
+                            int width, int normalize, float coef, float *y, float *scratch, int32_t *index,
+                            float *emph, void *stream);
 
 /* The loader's video front end (movenet/dataset.py:292-310 behind the decoder): a batch of clips of different
  * resolutions, as interleaved uint8 frames in one upload, -> (batch, n_frames, 64, 64) uint8 gray levels.  Per frame:

@@ -261,6 +261,8 @@ SIGNATURES = {
     "mvn_mu_law_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "mvn_pcm16_chunk": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                   C.c_void_p]),
+    "mvn_pcm16_deemph_chunk": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "mvn_onehot_to_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p]),
     "mvn_index_to_onehot": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
@@ -274,6 +276,10 @@ SIGNATURES = {
     "mvn_audio_frontend_window_scratch_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "mvn_audio_frontend_window": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (form -- AUDIO_FORM_* below -- in front, the coefficient behind `normalize`, the emphasised waveform behind `index`)
+    "mvn_audio_frontend_emph": (C.c_int, [C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "mvn_video_frontend": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "mvn_publish_words": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -379,6 +385,18 @@ def truncation(top_k, top_p):
     if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0.0 < top_p <= 1.0:
         raise ValueError(f"top_p must lie in (0, 1] (1: off), got {top_p!r}")
     return int(top_k), float(top_p)
+
+
+AUDIO_FORM_CLIP, AUDIO_FORM_VAR, AUDIO_FORM_WINDOW = 0, 1, 2  # MVN_AUDIO_FORM_* of mvn_audio_frontend_emph
+
+
+def emphasis(value, name: str = "preemphasis") -> float:
+    """The pre- / de-emphasis coefficient as the float32 value the kernels take; ValueError unless it is a number in
+    [0, 1) (0: off; NaN refused)."""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.0 <= value < 1.0 \
+            or not C.c_float(value).value < 1.0:  # (a double just below 1 that rounds to 1.0f)
+        raise ValueError(f"{name} must lie in [0, 1) (0: off), got {value!r}")
+    return float(C.c_float(value).value)
 
 
 def _per_sequence(value) -> bool:

@@ -25,6 +25,10 @@ With ``--ema_decay`` the module generates ``outputs["generated_output"]`` on the
 (``Dance2Music.averaged_weights``), on the train hook and on the validation hook, and the validation hook's
 ``outputs["output"]`` comes from them too (the whole validation loop runs on them); the train hook's
 ``outputs["output"]`` is the raw iterate's, like the train metrics.
+
+With ``--preemphasis A`` (A > 0) the classes describe the pre-emphasised signal, so every file -- origin, prediction
+and each generated one -- is written from ``ops.deemphasis_pcm16``: the bytes ``synthesize`` streams for the same
+classes.  Every row then carries ``preemphasis``; at 0 nothing changes and no row carries the key.
 """
 from __future__ import annotations
 
@@ -36,7 +40,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .ops import mu_law_decode
+from .ops import deemphasis_pcm16, mu_law_decode
 from .wavenet import MAX_AUDIO_FRAMES
 
 COLUMNS = ["split", "epoch", "batch_idx", "fp", "origin_audio", "pred_audio", "gen_audio"]
@@ -46,6 +50,15 @@ SAMPLE_RATE = MAX_AUDIO_FRAMES // 10  # 16,000 (callbacks.py:88)
 def write_wav(path: Path, waveform: np.ndarray, sample_rate: int = SAMPLE_RATE) -> None:
     """waveform in [-1, 1] -> mono 16-bit PCM."""
     pcm = (np.clip(np.asarray(waveform, dtype=np.float64), -1.0, 1.0) * 32767.0).round().astype("<i2")
+    write_pcm16(path, pcm, sample_rate)
+
+
+def write_pcm16(path: Path, pcm: np.ndarray, sample_rate: int = SAMPLE_RATE) -> None:
+    """int16 PCM -> mono 16-bit WAV, the samples as they are."""
+    pcm = np.asarray(pcm)
+    if pcm.dtype != np.int16:
+        raise ValueError(f"pcm must be int16, got {pcm.dtype}")
+    pcm = pcm.astype("<i2", copy=False)
     path.parent.mkdir(parents=True, exist_ok=True)
     with wave.open(str(path), "wb") as w:
         w.setnchannels(1)
@@ -56,13 +69,16 @@ def write_wav(path: Path, waveform: np.ndarray, sample_rate: int = SAMPLE_RATE) 
 
 class LogSamplesCallback:
     def __init__(self, log_every_n_epochs: int = 10, log_video: bool = True, temperature: float = 1.0,
-                 out_dir: Optional[str] = None, temperature_sweep=(), guidance: float = 1.0):
+                 out_dir: Optional[str] = None, temperature_sweep=(), guidance: float = 1.0,
+                 preemphasis: float = 0.0):
         self.log_every_n_epochs = log_every_n_epochs
         self.log_video = log_video  # kept for signature parity: there is no video to re-attach
         self.temperature = temperature
         self.out_dir = Path(out_dir) if out_dir is not None else None
         self.temperature_sweep = [float(t) for t in (temperature_sweep or ())]
         self.guidance = float(guidance)  # the module's classifier-free guidance scale (1.0: off, no field in the rows)
+        # the run's pre-emphasis coefficient (0.0: off -- the files and rows as they were)
+        self.preemphasis = float(preemphasis)
         self.columns = list(COLUMNS)
 
     def on_train_batch_end(self, trainer, pl_module, outputs, batch, batch_idx):
@@ -80,6 +96,11 @@ class LogSamplesCallback:
         """(B, Q, S) probabilities / one-hot -> (B, S) waveforms in [-1, 1]."""
         return mu_law_decode(one_hot_like.argmax(1).to(torch.int32), classes).cpu().numpy()
 
+    def _decode_deemphasised(self, one_hot_like: torch.Tensor, classes: int) -> np.ndarray:
+        """(B, Q, S) probabilities / one-hot -> (B, S) int16 PCM through the de-emphasis filter, whole clips."""
+        return deemphasis_pcm16(one_hot_like.argmax(1).to(torch.int32).contiguous(), self.preemphasis,
+                                classes).cpu().numpy()
+
     def log_samples(self, split, trainer, pl_module, outputs, batch, batch_idx):
         if getattr(trainer, "rank", 0) != 0:
             return
@@ -90,11 +111,13 @@ class LogSamplesCallback:
         # (a model with global classes was given each clip's own label; the row says which)
         labelled = bool(getattr(pl_module, "global_classes", None))
         Q = pl_module.config.model_config.input_channels
-        origin = self._decode(audio.to(outputs["output"].device), Q)
-        pred = self._decode(outputs["output"], Q)
+        decode, write = ((self._decode_deemphasised, write_pcm16) if self.preemphasis > 0.0
+                         else (self._decode, write_wav))
+        origin = decode(audio.to(outputs["output"].device), Q)
+        pred = decode(outputs["output"], Q)
         gen = None
         if outputs.get("generated_output", None) is not None:
-            gen = self._decode(outputs["generated_output"], Q)
+            gen = decode(outputs["generated_output"], Q)
         sweep = self.temperature_sweep if gen is not None else []
         if sweep and len(gen) != len(fps) * len(sweep):
             raise ValueError(f"generated_output holds {len(gen)} clips for {len(fps)} clips x {len(sweep)} temperatures")
@@ -109,18 +132,18 @@ class LogSamplesCallback:
             stem = f"epoch={trainer.current_epoch}-batch={batch_idx}-clip={i}"
             files = {"origin_audio": root / split / f"{stem}-origin.wav",
                      "pred_audio": root / split / f"{stem}-pred.wav"}
-            write_wav(files["origin_audio"], origin[i])
-            write_wav(files["pred_audio"], pred[i])
+            write(files["origin_audio"], origin[i])
+            write(files["pred_audio"], pred[i])
             for j, t in enumerate(sweep):
                 swept = dict(files, gen_audio=root / split / f"{stem}-gen-T{t:g}.wav")
-                write_wav(swept["gen_audio"], gen[i * len(sweep) + j])
+                write(swept["gen_audio"], gen[i * len(sweep) + j])
                 rows.append({"split": split, "epoch": trainer.current_epoch, "batch_idx": batch_idx, "fp": fp,
                              **{k: str(v.relative_to(root)) for k, v in swept.items()}, "temperature": t})
             if sweep:
                 continue
             if gen is not None:
                 files["gen_audio"] = root / split / f"{stem}-gen.wav"
-                write_wav(files["gen_audio"], gen[i])
+                write(files["gen_audio"], gen[i])
             rows.append({"split": split, "epoch": trainer.current_epoch, "batch_idx": batch_idx, "fp": fp,
                          **{k: str(v.relative_to(root)) for k, v in files.items()}})
         scores = outputs.get("sample_scores", None) if gen is not None else None
@@ -136,6 +159,9 @@ class LogSamplesCallback:
         if gen is not None and self.guidance != 1.0:  # (as a sweep's rows carry their temperature)
             for r in rows:
                 r["guidance"] = self.guidance
+        if self.preemphasis > 0.0:
+            for r in rows:
+                r["preemphasis"] = self.preemphasis
         if gen is not None and getattr(pl_module, "use_mel", False):
             # (each clip was generated under its SOURCE clip's log-mel frames: copy-synthesis)
             for r in rows:

@@ -66,12 +66,34 @@ def local_conditioning_of(path):
     return _local_record(_read(path))
 
 
+def _preemphasis_record(obj) -> float:
+    v = obj.get("preemphasis", 0.0) if isinstance(obj, dict) else 0.0
+    return float(v) if isinstance(v, (int, float)) and not isinstance(v, bool) else 0.0
+
+
+def preemphasis_record(model) -> dict:
+    """What a checkpoint of ``model`` carries beside its weights for ``--preemphasis``: ``{"preemphasis": a}`` for a
+    model whose ``preemphasis`` is above 0, nothing otherwise (a run without the flag writes the file it wrote before)."""
+    a = float(getattr(model, "preemphasis", 0.0))
+    return {"preemphasis": a} if a > 0.0 else {}
+
+
+def preemphasis_of(path) -> float:
+    """The ``"preemphasis"`` record of a checkpoint trained with ``--preemphasis A`` -- the coefficient its training
+    audio was pre-emphasised with -- or 0.0 for a file without one (the record is written only when A > 0)."""
+    return _preemphasis_record(_read(path))
+
+
 def load_into(model: torch.nn.Module, path, strict: bool = True, ema: bool = False):
     """model.load_state_dict from any of the reference's checkpoint flavours (``ema``: the averaged weights).  A
     checkpoint of a run with ``--use_mel 1`` carries its local-conditioning record: a model without a matching
     ``local_conv`` is given one first (``WaveNet.set_local_conditioning``, on the device of its other parameters), and
-    the record is left in ``model.local_conditioning`` for whoever computes the features."""
+    the record is left in ``model.local_conditioning`` for whoever computes the features.  A checkpoint of a run with
+    ``--preemphasis A`` sets ``model.preemphasis`` (a model that has the attribute; a file without the record leaves
+    it as it is)."""
     obj = _read(path)  # (read once: the record and the weights come from the same object)
+    if _preemphasis_record(obj) > 0.0 and hasattr(type(model), "preemphasis"):
+        model.preemphasis = _preemphasis_record(obj)
     rec = _local_record(obj)
     if rec is not None and hasattr(model, "set_local_conditioning"):
         model.set_local_conditioning(int(rec["local_channels"]), int(rec["local_hop"]))

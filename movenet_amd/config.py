@@ -121,6 +121,12 @@ class TrainingConfig:
     mel_fmin: float = 0.0
     mel_fmax: Optional[float] = None
 
+    # pre-emphasis of the training audio (WavFolderLoader(preemphasis=a)): the front end quantises
+    # (vn[k] - a vn[k-1]) / (1 + a) of the normalised waveform, the checkpoint records a, and everything that turns the
+    # model's classes back into audio (the sample logger, synthesize) runs the inverse filter.  0: off.  Not a reference
+    # field: a JSON written without it loads with the default.
+    preemphasis: float = 0.0
+
     scheduler: Optional[str] = "OneCycleLR"
     lr_pct_start: float = 0.45
     base_learning_rate: float = 0.0003
@@ -216,6 +222,7 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--mel_hop", type=int, default=256)
     a("--mel_fmin", type=float, default=0.0)
     a("--mel_fmax", type=float, default=None)
+    a("--preemphasis", type=float, default=0.0)
     a("--n_epochs", type=int, default=10)
     a("--n_steps_per_epoch", type=int, default=None)
     a("--use_video", type=_flag, default=True)
@@ -263,7 +270,7 @@ def config_from_args(args) -> TrainingConfig:
         "lr_pct_start base_learning_rate scheduler_step_size_up scheduler_step_size_down "
         "scheduler_cyclic_mode scheduler_cyclic_gamma scheduler_cycle_momentum max_learning_rate "
         "scheduler_step_size scheduler_step_gamma scheduler_milestones weight_decay "
-        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule ema_decay ema_warmup score_samples clip_length audio_rate window_gain use_mel mel_bins mel_fft mel_hop mel_fmin mel_fmax accumulation_steps num_workers val_num_workers "
+        "generate_n_samples generate_temperature generate_sampling generate_top_k generate_top_p generate_temperature_sweep loss_rule ema_decay ema_warmup score_samples clip_length audio_rate window_gain use_mel mel_bins mel_fft mel_hop mel_fmin mel_fmax preemphasis accumulation_steps num_workers val_num_workers "
         "pin_memory n_epochs n_steps_per_epoch use_video use_global bf16_video generate_guidance global_dropout video_antialias batch_subsample_frac "
         "val_batch_subsample_frac dist_backend dist_port model_output_path log_samples_every"
     ).split()

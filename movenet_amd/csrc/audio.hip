@@ -267,19 +267,39 @@ __global__ __launch_bounds__(kAfThreads) void af_resample_kernel(const int16_t *
 // (an un-normalised resample may overshoot [-1, 1]).
 // The (min, max) is r.hi > r.lo where the row gives one (workgroup-uniform), else it runs over the tiles that hold the
 // row's N outputs, of the `tiles` slots a row has; the columns behind them get the class mu-law gives 0.0.
+//
+// EMPH (mvn_audio_frontend_emph): what is quantised is the pre-emphasised row e[k] = (vn[k] - a vn[k-1]) / (1 + a) of
+// af_emphasise, vn the value formed above for column k and vn[-1] = 0 -- the ROW's column 0 has no predecessor, a
+// window's first column included.  Column k - 1 may lie in the previous tile: y is complete, it is read from there
+// and normalised by the same expressions.  e goes to `emph` as well, 0 behind the row's N columns and in a refused
+// row.  EMPH = false is the kernel as it was, instruction for instruction.
+__device__ __forceinline__ float af_emphasise(float v, float prev, float a) {
+#pragma clang fp contract(off)
+  const float t = a * prev;
+  return (v - t) / (1.0f + a);
+}
+
+template <bool EMPH>
 __device__ __forceinline__ void af_quantise(const AfRow &r, int width, int Q, int normalize, int tiles,
                                             const float *__restrict__ y, const float2 *__restrict__ part,
-                                            int32_t *__restrict__ idx) {
+                                            int32_t *__restrict__ idx, float a, float *__restrict__ emph) {
   __shared__ float red[2 * (kAfThreads / kWave)];
   const int b = blockIdx.y, tid = threadIdx.x, N = r.N;
   const int t0 = blockIdx.x * kAfTile, t1 = min(N, t0 + kAfTile);
   int32_t *ib = idx + (size_t)b * width;
+  float *eb = EMPH ? emph + (size_t)b * width : nullptr;
   if (!r.g.ok) {
-    for (int k = t0 + tid; k < t1; k += kAfThreads) ib[k] = -1;
+    for (int k = t0 + tid; k < t1; k += kAfThreads) {
+      ib[k] = -1;
+      if (EMPH) eb[k] = 0.f;
+    }
     return;
   }
   const int silence = (int)((float)(Q - 1) / 2.0f + 0.5f);
-  for (int k = max(N, t0) + tid; k < min(width, t0 + kAfTile); k += kAfThreads) ib[k] = silence;
+  for (int k = max(N, t0) + tid; k < min(width, t0 + kAfTile); k += kAfThreads) {
+    ib[k] = silence;
+    if (EMPH) eb[k] = 0.f;
+  }
   if (t0 >= N) return;  // (workgroup-uniform)
   const int own = (N + kAfTile - 1) / kAfTile;
   float mn = INFINITY, mx = -INFINITY;
@@ -315,6 +335,15 @@ __device__ __forceinline__ void af_quantise(const AfRow &r, int width, int Q, in
       v = (v - mn) / range;
       v = v * 2.0f - 1.0f;
     }
+    if (EMPH) {
+      float prev = k > 0 ? yb[k - 1] : 0.f;
+      if (scale && k > 0) {
+        prev = (prev - mn) / range;
+        prev = prev * 2.0f - 1.0f;
+      }
+      v = af_emphasise(v, prev, a);
+      eb[k] = v;
+    }
     const float z = copysignf(log1pf(mu * fabsf(v)) / lmu, v);
     const int q = (int)((z + 1.0f) / 2.0f * mu + 0.5f);
     ib[k] = min(max(q, 0), Q - 1);
@@ -328,14 +357,26 @@ __global__ __launch_bounds__(kAfThreads) void af_quantise_kernel(const Clip *__r
                                                                  const float2 *__restrict__ part,
                                                                  int32_t *__restrict__ idx) {
   const AfRow r = af_row(clips[blockIdx.y], pcm_len, width);
-  af_quantise(r, width, Q, normalize, tiles, y, part, idx);
+  af_quantise<false>(r, width, Q, normalize, tiles, y, part, idx, 0.f, nullptr);
 }
 
-// The three entry points: `what` is the entry point's name without its mvn_ prefix
+template <class Clip>
+__global__ __launch_bounds__(kAfThreads) void af_quantise_emph_kernel(const Clip *__restrict__ clips, long long pcm_len,
+                                                                      int width, int Q, int normalize, int tiles,
+                                                                      const float *__restrict__ y,
+                                                                      const float2 *__restrict__ part,
+                                                                      int32_t *__restrict__ idx, float a,
+                                                                      float *__restrict__ emph) {
+  const AfRow r = af_row(clips[blockIdx.y], pcm_len, width);
+  af_quantise<true>(r, width, Q, normalize, tiles, y, part, idx, a, emph);
+}
+
+// The entry points: `what` is the entry point's name without its mvn_ prefix.  `emph` non-null (mvn_audio_frontend_emph):
+// the second launch is the pre-emphasising quantise kernel with coefficient `a`; null: the two launches as they were.
 template <class Clip, bool BLOCKS>
 static int audio_frontend_launch(const char *what, const int16_t *pcm, long long pcm_len, const Clip *clips, int batch,
                                  int classes, int width, int normalize, float *y, float *scratch, int32_t *index,
-                                 void *stream) {
+                                 void *stream, float a = 0.f, float *emph = nullptr) {
   if (!pcm || !clips || !y || !scratch || !index || pcm_len < 1 || batch < 1 || batch > 65535 || width < 1 ||
       classes < 2 || classes > 65536) {
     set_error("mvn_%s: bad argument", what);
@@ -351,8 +392,12 @@ static int audio_frontend_launch(const char *what, const int16_t *pcm, long long
                      clips, width, y, (float2 *)scratch);
   int rc = check_hip(hipGetLastError(), (std::string(what) + " (resample)").c_str());
   if (rc) return rc;
-  hipLaunchKernelGGL((af_quantise_kernel<Clip>), grid, dim3(kAfThreads), 0, (hipStream_t)stream, clips, pcm_len, width,
-                     classes, normalize, tiles, (const float *)y, (const float2 *)scratch, index);
+  if (emph)
+    hipLaunchKernelGGL((af_quantise_emph_kernel<Clip>), grid, dim3(kAfThreads), 0, (hipStream_t)stream, clips, pcm_len,
+                       width, classes, normalize, tiles, (const float *)y, (const float2 *)scratch, index, a, emph);
+  else
+    hipLaunchKernelGGL((af_quantise_kernel<Clip>), grid, dim3(kAfThreads), 0, (hipStream_t)stream, clips, pcm_len,
+                       width, classes, normalize, tiles, (const float *)y, (const float2 *)scratch, index);
   return check_hip(hipGetLastError(), (std::string(what) + " (quantise)").c_str());
 }
 
@@ -373,12 +418,20 @@ constexpr int kPcmThreads = 256;
 typedef int32_t pcm_i32x4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef uint32_t pcm_u32x2 __attribute__((ext_vector_type(2), aligned(4)));
 
-__device__ __forceinline__ uint32_t pcm16_of(int q, int Q, float mu, float lmu) {
+// the float mu_law_decode_kernel gives for class q, clamped to [0, Q)
+__device__ __forceinline__ float pcm_decode(int q, int Q, float mu, float lmu) {
   q = min(max(q, 0), Q - 1);
   const float y = ((float)q / mu) * 2.0f - 1.0f;  // (the expression of mu_law_decode_kernel)
-  const float x = copysignf((expf(fabsf(y) * lmu) - 1.0f) / mu, y);
-  const double v = fmin(fmax((double)x, -1.0), 1.0) * 32767.0;
+  return copysignf((expf(fabsf(y) * lmu) - 1.0f) / mu, y);
+}
+
+__device__ __forceinline__ uint32_t pcm16_round(double x) {
+  const double v = fmin(fmax(x, -1.0), 1.0) * 32767.0;
   return (uint32_t)(uint16_t)(int16_t)(int)rint(v);  // rint: half to even, as numpy's round
+}
+
+__device__ __forceinline__ uint32_t pcm16_of(int q, int Q, float mu, float lmu) {
+  return pcm16_round((double)pcm_decode(q, Q, mu, lmu));
 }
 
 __global__ __launch_bounds__(kPcmThreads) void pcm16_chunk_kernel(const int32_t *__restrict__ samples, int batch,
@@ -410,31 +463,107 @@ __global__ __launch_bounds__(kPcmThreads) void pcm16_chunk_kernel(const int32_t 
   }
 }
 
+// ---- ... through the de-emphasis filter (mvn_pcm16_deemph_chunk) ----------------------------------------------------
+// The inverse of the front end's pre-emphasis, fused into the conversion: with x the float of pcm_decode, per row and
+// in column order, in double,
+//   y = ((1 + a) x) + (a y_prev),   pcm = pcm16_round(y),   y_prev = y
+// two products and a sum, each rounded once (no fma), y_prev from state[b] at entry and back there at exit.  The
+// recurrence is DEFINED sequentially, so that the bits do not depend on how a clip is cut into chunks; it is therefore
+// run sequentially -- no scan, which would round differently.  One wave per row.  Per 64 columns every lane decodes its
+// own column (expf and the product by 1 + a: the expensive part, in parallel), then the wave walks the 64 columns
+// together: it reads lane j's product with a cross-lane read and every lane forms the same y (a product and a sum in
+// the dependent chain), lane j keeping it for its column.  The next 64 classes are loaded before the walk.  A column
+// is stored as one int16, whatever the row's alignment.  Nothing outside [0, n) of a row is read or written.
+__device__ __forceinline__ double wave_read(double v, int lane) {  // (lane: wave-uniform)
+  const long long u = __double_as_longlong(v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)u, lane);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(u >> 32), lane);
+  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+__global__ __launch_bounds__(kWave) void pcm16_deemph_chunk_kernel(const int32_t *__restrict__ samples, int batch,
+                                                                   int sample_stride, int t0, int n, int Q, double a,
+                                                                   double *__restrict__ state,
+                                                                   int16_t *__restrict__ pcm, int pcm_stride) {
+#pragma clang fp contract(off)
+  const float mu = (float)(Q - 1), lmu = log1pf(mu);
+  const double gain = 1.0 + a;
+  const int lane = threadIdx.x;
+  for (int b = blockIdx.x; b < batch; b += gridDim.x) {
+    const int32_t *src = samples + (size_t)b * sample_stride + t0;
+    int16_t *dst = pcm + (size_t)b * pcm_stride;
+    double prev = state[b];
+    int q = lane < n ? src[lane] : 0;
+    for (int c0 = 0; c0 < n; c0 += kWave) {
+      const int m = min(n - c0, kWave), c = c0 + lane;
+      const int q_next = c + kWave < n ? src[c + kWave] : 0;
+      const double xs = gain * (double)pcm_decode(q, Q, mu, lmu);
+      double mine = 0.0;
+#pragma unroll
+      for (int j = 0; j < kWave; ++j) {
+        if (j >= m) break;  // (wave-uniform)
+        const double fed = a * prev;
+        prev = wave_read(xs, j) + fed;
+        if (lane == j) mine = prev;
+      }
+      if (lane < m) dst[c] = (int16_t)pcm16_round(mine);
+      q = q_next;
+    }
+    if (lane == 0) state[b] = prev;
+  }
+}
+
 }  // namespace mvn
+
+// what mvn_pcm16_chunk and mvn_pcm16_deemph_chunk refuse alike; `what` is the entry point's name
+static int pcm16_check(const char *what, const int32_t *samples, int batch, int sample_stride, int t0, int n,
+                       int classes, const int16_t *pcm, int pcm_stride) {
+  if (!samples || !pcm) {
+    mvn::set_error("%s: bad argument (NULL samples or pcm)", what);
+    return MVN_ERR_BAD_ARG;
+  }
+  if (batch < 1 || n < 0 || t0 < 0 || (long long)t0 + (long long)n > (long long)sample_stride || pcm_stride < n) {
+    mvn::set_error("%s: bad argument (batch %d, t0 %d, n %d, sample_stride %d, pcm_stride %d)", what, batch, t0, n,
+                   sample_stride, pcm_stride);
+    return MVN_ERR_BAD_ARG;
+  }
+  if (classes < 2 || classes > 32768) {
+    mvn::set_error("%s: bad argument (classes %d outside 2 .. 32768)", what, classes);
+    return MVN_ERR_BAD_ARG;
+  }
+  return MVN_OK;
+}
 
 extern "C" {
 
 int mvn_pcm16_chunk(const int32_t *samples, int batch, int sample_stride, int t0, int n, int classes, int16_t *pcm,
                     int pcm_stride, void *stream) {
-  if (!samples || !pcm) {
-    mvn::set_error("mvn_pcm16_chunk: bad argument (NULL samples or pcm)");
-    return MVN_ERR_BAD_ARG;
-  }
-  if (batch < 1 || n < 0 || t0 < 0 || (long long)t0 + (long long)n > (long long)sample_stride || pcm_stride < n) {
-    mvn::set_error("mvn_pcm16_chunk: bad argument (batch %d, t0 %d, n %d, sample_stride %d, pcm_stride %d)", batch, t0,
-                   n, sample_stride, pcm_stride);
-    return MVN_ERR_BAD_ARG;
-  }
-  if (classes < 2 || classes > 32768) {
-    mvn::set_error("mvn_pcm16_chunk: bad argument (classes %d outside 2 .. 32768)", classes);
-    return MVN_ERR_BAD_ARG;
-  }
+  const int rc = pcm16_check("mvn_pcm16_chunk", samples, batch, sample_stride, t0, n, classes, pcm, pcm_stride);
+  if (rc) return rc;
   if (n == 0) return MVN_OK;
   const int threads = n / 4 + 1;  // one per quad and the one behind them
   const dim3 grid((threads + mvn::kPcmThreads - 1) / mvn::kPcmThreads, batch < 65535 ? batch : 65535);
   hipLaunchKernelGGL(mvn::pcm16_chunk_kernel, grid, dim3(mvn::kPcmThreads), 0, (hipStream_t)stream, samples, batch,
                      sample_stride, t0, n, classes, pcm, pcm_stride);
   return mvn::check_hip(hipGetLastError(), "pcm16_chunk");
+}
+
+int mvn_pcm16_deemph_chunk(const int32_t *samples, int batch, int sample_stride, int t0, int n, int classes, float coef,
+                           double *state, int16_t *pcm, int pcm_stride, void *stream) {
+  const int rc = pcm16_check("mvn_pcm16_deemph_chunk", samples, batch, sample_stride, t0, n, classes, pcm, pcm_stride);
+  if (rc) return rc;
+  if (!state || ((uintptr_t)state & 7u) != 0) {
+    mvn::set_error("mvn_pcm16_deemph_chunk: bad argument (state NULL or not 8-byte aligned)");
+    return MVN_ERR_BAD_ARG;
+  }
+  if (!(coef >= 0.0f && coef < 1.0f)) {  // (a NaN fails both)
+    mvn::set_error("mvn_pcm16_deemph_chunk: bad argument (coef %g outside [0, 1))", (double)coef);
+    return MVN_ERR_BAD_ARG;
+  }
+  if (n == 0) return MVN_OK;
+  hipLaunchKernelGGL(mvn::pcm16_deemph_chunk_kernel, dim3(batch), dim3(mvn::kWave), 0, (hipStream_t)stream, samples,
+                     batch, sample_stride, t0, n, classes, (double)coef, state, pcm, pcm_stride);
+  return mvn::check_hip(hipGetLastError(), "pcm16_deemph_chunk");
 }
 
 size_t mvn_audio_frontend_scratch_floats(int batch, int n_out) {
@@ -468,6 +597,33 @@ int mvn_audio_frontend_window(const int16_t *pcm, long long pcm_len, const mvn_a
                               void *stream) {
   return mvn::audio_frontend_launch<mvn_audio_clip_window, true>("audio_frontend_window", pcm, pcm_len, clips, batch,
                                                                  classes, width, normalize, y, scratch, index, stream);
+}
+
+int mvn_audio_frontend_emph(int form, const int16_t *pcm, long long pcm_len, const void *clips, int batch, int classes,
+                            int width, int normalize, float coef, float *y, float *scratch, int32_t *index,
+                            float *emph, void *stream) {
+  if (!emph || !(coef >= 0.0f && coef < 1.0f)) {  // (a NaN fails both)
+    mvn::set_error("mvn_audio_frontend_emph: bad argument (emph NULL, or coef %g outside [0, 1))", (double)coef);
+    return MVN_ERR_BAD_ARG;
+  }
+  switch (form) {
+    case MVN_AUDIO_FORM_CLIP:
+      return mvn::audio_frontend_launch<mvn_audio_clip, false>("audio_frontend_emph", pcm, pcm_len,
+                                                               (const mvn_audio_clip *)clips, batch, classes, width,
+                                                               normalize, y, scratch, index, stream, coef, emph);
+    case MVN_AUDIO_FORM_VAR:
+      return mvn::audio_frontend_launch<mvn_audio_clip_var, false>("audio_frontend_emph", pcm, pcm_len,
+                                                                   (const mvn_audio_clip_var *)clips, batch, classes,
+                                                                   width, normalize, y, scratch, index, stream, coef,
+                                                                   emph);
+    case MVN_AUDIO_FORM_WINDOW:
+      return mvn::audio_frontend_launch<mvn_audio_clip_window, true>("audio_frontend_emph", pcm, pcm_len,
+                                                                     (const mvn_audio_clip_window *)clips, batch,
+                                                                     classes, width, normalize, y, scratch, index,
+                                                                     stream, coef, emph);
+  }
+  mvn::set_error("mvn_audio_frontend_emph: bad argument (form %d)", form);
+  return MVN_ERR_BAD_ARG;
 }
 
 }  // extern "C"

@@ -438,7 +438,12 @@ class WavFolderLoader:
     last one is short) and are cached by (file, window).  ``Batch.lengths`` carries every row's real samples and
     ``info`` rows the window's ``out_first``.  ``window_gain="file"`` (the default) normalises every window by the
     (min, max) of its whole file's channel mean, found on the host in bounded chunks when the file is first touched;
-    ``"window"`` by the window's own.  Refused with ``use_video``; a file's length is not limited."""
+    ``"window"`` by the window's own.  Refused with ``use_video``; a file's length is not limited.
+
+    ``preemphasis=a`` (0 < a < 1; 0, the default, leaves every call above as it is), fixed per loader: whichever
+    front-end form the loader uses quantises the pre-emphasised row (vn[k] - a vn[k-1]) / (1 + a) of the normalised
+    waveform, a row's first column without a predecessor (``ops.audio_frontend``), in all three ``clip_length`` modes.
+    The index cache then holds emphasised classes, in a cache of its own per coefficient."""
 
     @staticmethod
     def native_plan(clip_frames: int, clip_rate: int, frames: int, audio_rate: int):
@@ -485,7 +490,8 @@ class WavFolderLoader:
                  batch_subsample_frac: Optional[float] = None, use_video: bool = False,
                  normalize_audio: bool = True, device=None, cache_bytes: int = 4 << 30,
                  video_antialias: bool = False, video_cache_bytes: int = 4 << 30,
-                 clip_length: str = "resample", audio_rate: int = 16000, window_gain: str = "file", **_ignored):
+                 clip_length: str = "resample", audio_rate: int = 16000, window_gain: str = "file",
+                 preemphasis: float = 0.0, **_ignored):
         import os
         from pathlib import Path
         from . import wavenet as W
@@ -517,6 +523,11 @@ class WavFolderLoader:
         if video_antialias not in (False, True, 0, 1):
             raise ValueError(f"video_antialias must be 0 or 1, got {video_antialias!r}")
         self.video_antialias = bool(video_antialias)
+        from ._native import emphasis
+        emphasis(preemphasis)  # ValueError outside [0, 1)
+        self.preemphasis = float(preemphasis)
+        # (what the front-end calls get: nothing at 0, so that they are the calls they were)
+        self._emph = {"preemphasis": self.preemphasis} if self.preemphasis > 0.0 else {}
         self._video_status: list = []  # (clips, status tensor) of the front-end launches not yet looked at
         self.raw_video: dict = {}  # clip -> (F, H, W, channels) of a raw-frame file (pre-made files are absent)
         self.contexts = _context_folders(self.root_path)
@@ -557,6 +568,8 @@ class WavFolderLoader:
             self.pairs = [(i, w) for i, (_, _, h) in enumerate(self.index)
                           for w in range(self.window_count(h["frames"], h["rate"], self.frames, self.audio_rate))]
             self.n_clips = len(self.pairs)
+        if self._emph:  # (emphasised classes are other rows: a cache of their own per coefficient)
+            key += ("preemphasis", self.preemphasis)
         self.plans = [self.native_plan(h["frames"], h["rate"], self.frames, self.audio_rate) if self.native
                       else (int(h["frames"]), self.frames) for _, _, h in self.index]
         cache = _INDEX_CACHES.get(key)
@@ -685,11 +698,11 @@ class WavFolderLoader:
             if self.native:
                 d_pcm, d_desc = _upload_pcm(dev, pcm, "clips_var", audio_clip_var_descriptors(
                     frames, channels, [self.plans[i][1] for i in todo]))
-                idx = audio_frontend_var(d_pcm, d_desc, self.Q, self.frames, normalize=self.normalize)
+                idx = audio_frontend_var(d_pcm, d_desc, self.Q, self.frames, normalize=self.normalize, **self._emph)
             else:
                 d_pcm, d_desc = _upload_pcm(dev, pcm, "clips", audio_clip_descriptors(frames, channels))
                 idx = audio_frontend(d_pcm, frames, channels, self.Q, n_out=self.frames, normalize=self.normalize,
-                                     descriptors=d_desc)
+                                     descriptors=d_desc, **self._emph)
             for row, i in enumerate(todo):
                 fresh[i] = idx[row]
                 cache.put(i, idx[row], self.plans[i][1])
@@ -738,7 +751,8 @@ class WavFolderLoader:
                 [self.index[i][2]["rate"] for i, _, _ in todo], self.audio_rate,
                 lo=[r[0] for r in ranges], hi=[r[1] for r in ranges])
             d_pcm, d_desc = _upload_pcm(dev, [sp[0] for sp in spans], "clips_window", desc, least=1)
-            idx = audio_frontend_window(d_pcm, d_desc, self.Q, self.frames, normalize=self.normalize)
+            idx = audio_frontend_window(d_pcm, d_desc, self.Q, self.frames, normalize=self.normalize,
+                                        **self._emph)
             for row, ((i, w, _), p) in enumerate(zip(todo, plans)):
                 fresh.append(((i, w), idx[row], p[2]))
                 if not self.train:
@@ -819,7 +833,7 @@ def get_dataloader(filepath, input_channels: int, batch_size: int = 64, train: b
     with a ``train`` or ``valid`` sub-folder gives a WavFolderLoader; anything else raises ValueError."""
     if not str(filepath).startswith("synthetic://") and _is_wav_folder(filepath):
         extra = {k: kwargs[k] for k in ("cache_bytes", "video_antialias", "video_cache_bytes", "clip_length",
-                                        "audio_rate", "window_gain") if k in kwargs}
+                                        "audio_rate", "window_gain", "preemphasis") if k in kwargs}
         return WavFolderLoader(filepath, input_channels, batch_size, train=train, rank=rank,
                                world_size=world_size, shuffle=kwargs.get("shuffle", False),
                                batch_subsample_frac=batch_subsample_frac, use_video=use_video,

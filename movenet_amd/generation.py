@@ -438,16 +438,21 @@ class RingGenerator:
         self._run(self.t, t_end, self.n_given)
         self.t = t_end
 
-    def stream(self, n_new: int, chunk: int = 4000):
+    def stream(self, n_new: int, chunk: int = 4000, deemphasis: float = 0.0, state=None):
         """Generate ``n_new`` further samples per sequence (after ``prime()``) and hand them out while they are being
         made: yields ``(t0, pcm)`` per launch of ``chunk`` steps (the last may be shorter) -- ``pcm`` the (batch, n)
         int16 numpy view of a pinned host buffer holding the 16-bit PCM (``mvn_pcm16_chunk``) of the columns
         [t0, t0 + n) just finished, valid until the next ``next()``.  Launch k + 1 is enqueued before the host waits
         for chunk k, so the GPU does not idle while the consumer handles a chunk.  A hand-off timeout of a pipelined
         variant raises ``PipeHandoffTimeout`` at the chunk where its status word is seen; ``check_errors()`` runs
-        before the last chunk is handed out.  ``chunk < 1`` is a ValueError, raised here."""
+        before the last chunk is handed out.  ``chunk < 1`` is a ValueError, raised here.
+
+        ``deemphasis`` = a > 0 with ``state`` (``ops.pcm16_chunk``): the PCM of every chunk goes through the de-emphasis
+        filter, whose (batch,) float64 state on the device -- zero, or as the prompt's columns left it -- is carried
+        from chunk to chunk in ``state``."""
         chunks = plan_chunks(self.t + 1, min(int(n_new), self.n_total - 1 - self.t), chunk)
-        return _stream_parts([(self, 0, self.batch)], self.batch, self.Q, chunks, self.device, self.check_errors)
+        return _stream_parts([(self, 0, self.batch)], self.batch, self.Q, chunks, self.device, self.check_errors,
+                             deemphasis, state)
 
     def teacher_forced(self, indices: torch.Tensor, logits_t0: int):
         """Feed a fully given (B, n_total) history; return (choices, logits) for
@@ -709,9 +714,10 @@ class GroupedGenerator:
         for g in self.groups:
             g.check_errors()
 
-    def stream(self, n_new: int, chunk: int = 4000):
+    def stream(self, n_new: int, chunk: int = 4000, deemphasis: float = 0.0, state=None):
         """``RingGenerator.stream`` for the groups: per chunk one launch per group, each group's PCM into its row block
-        of the chunk's buffer, every group's status word beside it, one event behind them all."""
+        of the chunk's buffer (through its row block of the de-emphasis ``state``), every group's status word beside it,
+        one event behind them all."""
         t = self.groups[0].t
         chunks = plan_chunks(t + 1, min(int(n_new), self.n_total - 1 - t), chunk)
 
@@ -719,7 +725,7 @@ class GroupedGenerator:
             self._collect()
             self.check_errors()
         parts = [(g, b0, b1) for g, (b0, b1) in zip(self.groups, self.bounds)]
-        return _stream_parts(parts, self.batch, self.groups[0].Q, chunks, self.device, finish)
+        return _stream_parts(parts, self.batch, self.groups[0].Q, chunks, self.device, finish, deemphasis, state)
 
 
 def plan_chunks(first: int, n_new: int, chunk: int):
@@ -732,14 +738,18 @@ def plan_chunks(first: int, n_new: int, chunk: int):
     return [(first + k, min(chunk, n_new - k)) for k in range(0, n_new, chunk)]
 
 
-def _stream_parts(parts, batch: int, classes: int, chunks, device, finish):
+def _stream_parts(parts, batch: int, classes: int, chunks, device, finish, deemphasis: float = 0.0, state=None):
     """What ``RingGenerator.stream`` and ``GroupedGenerator.stream`` share.  ``parts``: ``(generator, b0, b1)`` -- the
     generators that advance together and the rows of the chunk they own; ``finish``: run once everything has been
-    enqueued and has completed, before the last chunk is handed out.
+    enqueued and has completed, before the last chunk is handed out.  ``deemphasis`` > 0: the conversion is
+    ``mvn_pcm16_deemph_chunk`` with the caller's (batch,) float64 ``state``, a part filtering through its own rows of it;
+    a launch updates the state in stream order, so enqueueing ahead changes nothing.
 
     Per chunk, on the current stream: every part's launch, its ``mvn_pcm16_chunk`` into the device PCM buffer, one
     non-blocking copy of that buffer and one of every pipelined part's status word into the chunk's pinned host
     buffer (two of them, taking turns), and an event.  The host enqueues chunk k + 1, then waits for chunk k's event."""
+    if deemphasis > 0.0 and (state is None or tuple(state.shape) != (batch,)):
+        raise ValueError(f"deemphasis > 0 needs state: a ({batch},) float64 tensor on the device")
     if not chunks:
         finish()
         return
@@ -760,7 +770,10 @@ def _stream_parts(parts, batch: int, classes: int, chunks, device, finish):
         with torch.cuda.device(device):
             for g, b0, b1 in parts:
                 g.advance(n)
-                pcm16_chunk(g.samples, t0, n, classes, out=out[b0:b1])
+                if deemphasis > 0.0:
+                    pcm16_chunk(g.samples, t0, n, classes, out=out[b0:b1], deemphasis=deemphasis, state=state[b0:b1])
+                else:
+                    pcm16_chunk(g.samples, t0, n, classes, out=out[b0:b1])
             host[k % 2][:2 * batch * n].view(torch.int16).view(batch, n).copy_(out, non_blocking=True)
             for i, w in enumerate(words):
                 if w is not None:

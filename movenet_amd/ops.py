@@ -977,11 +977,23 @@ def mu_law_decode(index: torch.Tensor, quantization_channels: int) -> torch.Tens
     return out
 
 
-def pcm16_chunk(samples: torch.Tensor, t0: int, n: int, classes: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def pcm16_chunk(samples: torch.Tensor, t0: int, n: int, classes: int, out: Optional[torch.Tensor] = None,
+                deemphasis: float = 0.0, state: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Columns [t0, t0 + n) of (batch, T) int32 class indices on the GPU -> (batch, n) int16 PCM on the GPU
     (mvn_pcm16_chunk): to the bit what ``callbacks.write_wav`` stores for ``mu_law_decode`` of those classes, a class
     outside [0, classes) clamped.  ``samples`` may be a row block or column view of a larger tensor (its last
-    dimension contiguous); ``out``: an int16 tensor of at least (batch, n) whose first n columns are written."""
+    dimension contiguous); ``out``: an int16 tensor of at least (batch, n) whose first n columns are written.
+
+    ``deemphasis`` = a in (0, 1) (mvn_pcm16_deemph_chunk; 0, the default, is the call above, untouched): the decoded
+    samples go through y[t] = (1 + a) x[t] + a y[t-1] in float64 before the rounding -- the inverse of the front
+    end's ``preemphasis`` -- with y[t-1] of each row carried in ``state``, a (batch,) float64 tensor on the GPU that the
+    caller zeroes before a clip's column 0 and hands to every later chunk of that clip.  The PCM does not depend on how
+    the clip is cut into chunks."""
+    a = N.emphasis(deemphasis, "deemphasis")
+    if a > 0.0:
+        if state is None:
+            raise ValueError("deemphasis > 0 needs state: a (batch,) float64 tensor on the GPU, zero before column 0")
+        _require_gpu(state, "state")
     _require_gpu(samples, "samples")
     if samples.dim() != 2 or samples.dtype != torch.int32 or (samples.shape[1] > 1 and samples.stride(1) != 1):
         raise ValueError(f"samples must be (batch, T) int32 with contiguous rows, got {tuple(samples.shape)} "
@@ -990,6 +1002,9 @@ def pcm16_chunk(samples: torch.Tensor, t0: int, n: int, classes: int, out: Optio
     t0, n = int(t0), int(n)
     if t0 < 0 or n < 0 or t0 + n > T:
         raise ValueError(f"columns [{t0}, {t0 + n}) do not lie inside the {T} of samples")
+    if a > 0.0 and (tuple(state.shape) != (B,) or state.dtype != torch.float64 or not state.is_contiguous()
+                    or state.device != samples.device):
+        raise ValueError(f"state must be a contiguous ({B},) float64 tensor on {samples.device}")
     if out is None:
         out = torch.empty((B, n), dtype=torch.int16, device=samples.device)
     else:
@@ -1003,11 +1018,25 @@ def pcm16_chunk(samples: torch.Tensor, t0: int, n: int, classes: int, out: Optio
     stride = samples.stride(0) if B > 1 else T
     if stride < T or (B > 1 and out.stride(0) < n):
         raise ValueError("samples / out: rows overlap")
+    pcm_stride = out.stride(0) if B > 1 else max(out.shape[1], n)
     with torch.cuda.device(samples.device):
-        N.check(N.lib().mvn_pcm16_chunk(samples.data_ptr(), B, stride, t0, n, int(classes), out.data_ptr(),
-                                        out.stride(0) if B > 1 else max(out.shape[1], n), _stream_ptr(samples.device)),
-                "mvn_pcm16_chunk")
+        if a > 0.0:
+            N.check(N.lib().mvn_pcm16_deemph_chunk(samples.data_ptr(), B, stride, t0, n, int(classes), a,
+                                                   state.data_ptr(), out.data_ptr(), pcm_stride,
+                                                   _stream_ptr(samples.device)), "mvn_pcm16_deemph_chunk")
+        else:
+            N.check(N.lib().mvn_pcm16_chunk(samples.data_ptr(), B, stride, t0, n, int(classes), out.data_ptr(),
+                                            pcm_stride, _stream_ptr(samples.device)), "mvn_pcm16_chunk")
     return out[:, :n]
+
+
+def deemphasis_pcm16(classes: torch.Tensor, a: float, quantization_channels: int) -> torch.Tensor:
+    """Whole clips: (batch, T) int32 class indices on the GPU -> (batch, T) int16 PCM through the de-emphasis filter
+    from a zero state (``pcm16_chunk`` with ``deemphasis=a`` over all columns) -- the bits a stream of the same classes
+    delivers chunk by chunk.  ``a == 0`` is plain ``pcm16_chunk``."""
+    _require_gpu(classes, "classes")
+    state = torch.zeros(classes.shape[0], dtype=torch.float64, device=classes.device) if a > 0 else None
+    return pcm16_chunk(classes, 0, classes.shape[1], quantization_channels, deemphasis=a, state=state)
 
 
 AUDIO_FRONTEND_MAX_RATIO = 100  # frames <= 100 n_out: the longest clip whose output tile's window fits the LDS
@@ -1045,11 +1074,17 @@ def _check_pcm(pcm: torch.Tensor) -> None:
         raise ValueError("pcm must be a contiguous 1-D int16 tensor")
 
 
+_AUDIO_FORMS = {"mvn_audio_frontend": N.AUDIO_FORM_CLIP, "mvn_audio_frontend_var": N.AUDIO_FORM_VAR,
+                "mvn_audio_frontend_window": N.AUDIO_FORM_WINDOW}
+
+
 def _audio_frontend_call(entry: str, scratch_entry: str, pcm, descriptors, words: int, B, Q, width, normalize,
-                         y=None, idx=None):
+                         y=None, idx=None, preemphasis: float = 0.0):
     """One launch pair of the front end through ``entry`` (all three share one kernel pair, see csrc/audio.hip):
     ``descriptors`` a (B, words) int32 tensor on the GPU, B its own row count where None; ``y`` / ``idx`` the
-    (B, width) outputs where the caller brings them.  Returns (idx, y)."""
+    (B, width) outputs where the caller brings them.  Returns (idx, y, None) -- with ``preemphasis`` > 0, through
+    mvn_audio_frontend_emph in ``entry``'s form, (idx, y, e): the indices of the pre-emphasised rows and those rows."""
+    a = N.emphasis(preemphasis)
     _check_pcm(pcm)
     _require_gpu(descriptors, "descriptors")
     if B is None and descriptors.dim() == 2:
@@ -1065,15 +1100,29 @@ def _audio_frontend_call(entry: str, scratch_entry: str, pcm, descriptors, words
             if tuple(t.shape) != (B, width) or t.dtype != dt or not t.is_contiguous() or t.device != dev:
                 raise ValueError(f"{what} must be a contiguous ({B}, {width}) {dt} tensor on {dev}")
         scratch = torch.empty(max(int(getattr(lib, scratch_entry)(B, width)), 2), dtype=torch.float32, device=dev)
+        if a > 0.0:
+            e = torch.empty(B, width, dtype=torch.float32, device=dev)
+            N.check(lib.mvn_audio_frontend_emph(_AUDIO_FORMS[entry], pcm.data_ptr(), pcm.numel(),
+                                                descriptors.data_ptr(), B, int(Q), int(width), int(bool(normalize)), a,
+                                                y.data_ptr(), scratch.data_ptr(), idx.data_ptr(), e.data_ptr(),
+                                                _stream_ptr(dev)), "mvn_audio_frontend_emph")
+            return idx, y, e
         N.check(getattr(lib, entry)(pcm.data_ptr(), pcm.numel(), descriptors.data_ptr(), B, int(Q), int(width),
                                     int(bool(normalize)), y.data_ptr(), scratch.data_ptr(), idx.data_ptr(),
                                     _stream_ptr(dev)), entry)
-    return idx, y
+    return idx, y, None
+
+
+def _frontend_result(return_waveform: bool, idx, y, e):
+    if not return_waveform:
+        return idx
+    return (idx, y) if e is None else (idx, y, e)
 
 
 def audio_frontend(pcm: torch.Tensor, frames, channels, quantization_channels: int, n_out: int = None,
                    normalize: bool = True, offsets=None, descriptors: torch.Tensor = None,
-                   return_waveform: bool = False, out: torch.Tensor = None, waveform_out: torch.Tensor = None):
+                   return_waveform: bool = False, out: torch.Tensor = None, waveform_out: torch.Tensor = None,
+                   preemphasis: float = 0.0):
     """Waveforms -> class indices on the GPU (mvn_audio_frontend): channel mean, resample of each whole clip to
     ``n_out`` frames (default MAX_AUDIO_FRAMES; sinc_interp_hann, width 6, roll-off 0.99), min-max normalisation,
     mu-law.
@@ -1083,7 +1132,12 @@ def audio_frontend(pcm: torch.Tensor, frames, channels, quantization_channels: i
     sequences (offsets default to back-to-back), checked here against the upload; ``descriptors`` is the same
     already on the device ((B, 4) int32 of audio_clip_descriptors -- the loader ships it through its pinned ring).
     Returns (B, n_out) int32 indices, with ``return_waveform`` also the (B, n_out) fp32 waveform before
-    normalisation.  Nothing here waits for the GPU."""
+    normalisation.  Nothing here waits for the GPU.
+
+    ``preemphasis`` = a in (0, 1) (mvn_audio_frontend_emph; 0, the default, is the call above, untouched): what goes
+    to mu-law is e[k] = (vn[k] - a vn[k-1]) / (1 + a) of the normalised row vn, vn[-1] = 0 -- the signal a model
+    whose output is de-emphasised (``pcm16_chunk(deemphasis=a)``) trains on.  ``return_waveform`` then returns
+    (indices, waveform, e)."""
     _check_pcm(pcm)  # (before the host lists are held against it)
     if n_out is None:
         from . import wavenet as W
@@ -1103,9 +1157,9 @@ def audio_frontend(pcm: torch.Tensor, frames, channels, quantization_channels: i
                              "output frames the front end resamples to")
     if descriptors is None:
         descriptors = torch.from_numpy(desc).to(pcm.device)
-    idx, y = _audio_frontend_call("mvn_audio_frontend", "mvn_audio_frontend_scratch_floats", pcm, descriptors, 4, B,
-                                  quantization_channels, n_out, normalize, waveform_out, out)
-    return (idx, y) if return_waveform else idx
+    return _frontend_result(return_waveform, *_audio_frontend_call(
+        "mvn_audio_frontend", "mvn_audio_frontend_scratch_floats", pcm, descriptors, 4, B, quantization_channels, n_out,
+        normalize, waveform_out, out, preemphasis))
 
 
 def audio_clip_var_descriptors(frames, channels, n_out, offsets=None):
@@ -1119,15 +1173,16 @@ def audio_clip_var_descriptors(frames, channels, n_out, offsets=None):
 
 
 def audio_frontend_var(pcm: torch.Tensor, descriptors: torch.Tensor, quantization_channels: int, width: int,
-                       normalize: bool = True, return_waveform: bool = False):
+                       normalize: bool = True, return_waveform: bool = False, preemphasis: float = 0.0):
     """Waveforms -> class indices by RATE (mvn_audio_frontend_var): clip b resampled as a whole to its own ``n_out``
     frames -- ``audio_frontend`` of that clip alone with that ``n_out``, bit for bit -- into row b of (B, ``width``)
     indices, silence (the class of 0.0) behind it.  ``descriptors``: (B, 6) int32 on the GPU
     (``audio_clip_var_descriptors``), checked on the device: a clip outside the upload or with ``n_out`` outside
-    [1, width] gives a row of -1.  Nothing here waits for the GPU."""
-    idx, y = _audio_frontend_call("mvn_audio_frontend_var", "mvn_audio_frontend_var_scratch_floats", pcm, descriptors,
-                                  6, None, quantization_channels, width, normalize)
-    return (idx, y) if return_waveform else idx
+    [1, width] gives a row of -1.  Nothing here waits for the GPU.  ``preemphasis``: as in ``audio_frontend``, over
+    the row's own ``n_out`` columns; e is 0 behind them."""
+    return _frontend_result(return_waveform, *_audio_frontend_call(
+        "mvn_audio_frontend_var", "mvn_audio_frontend_var_scratch_floats", pcm, descriptors, 6, None,
+        quantization_channels, width, normalize, preemphasis=preemphasis))
 
 
 def audio_clip_window_descriptors(span_first, span_frames, file_frames, channels, out_first, n_out, rate_in, rate_out,
@@ -1150,7 +1205,7 @@ def audio_clip_window_descriptors(span_first, span_frames, file_frames, channels
 
 
 def audio_frontend_window(pcm: torch.Tensor, descriptors: torch.Tensor, quantization_channels: int, width: int,
-                          normalize: bool = True, return_waveform: bool = False):
+                          normalize: bool = True, return_waveform: bool = False, preemphasis: float = 0.0):
     """Windows of files -> class indices by RATE (mvn_audio_frontend_window): row b is the columns ``[out_first,
     out_first + n_out)`` of its whole file's resample from ``rate_in`` to ``rate_out`` -- the bits this call gives for
     the whole file, cropped, which up to ``rate_in = 10 rate_out`` are ``audio_frontend_var``'s -- formed from the
@@ -1158,10 +1213,12 @@ def audio_frontend_window(pcm: torch.Tensor, descriptors: torch.Tensor, quantiza
     a descriptor's ``hi > lo`` is the range to normalise by (the loader's per-file gain), else the window's own
     (min, max).  ``descriptors``: (B, 16) int32 on the GPU (``audio_clip_window_descriptors``), checked on the device:
     a refused row (span outside the upload or not covering the window's taps, ``n_out`` outside [1, width], a window
-    outside the file, rates or channels < 1) is -1.  Nothing here waits for the GPU."""
-    idx, y = _audio_frontend_call("mvn_audio_frontend_window", "mvn_audio_frontend_window_scratch_floats", pcm,
-                                  descriptors, 16, None, quantization_channels, width, normalize)
-    return (idx, y) if return_waveform else idx
+    outside the file, rates or channels < 1) is -1.  Nothing here waits for the GPU.  ``preemphasis``: as in
+    ``audio_frontend``; the WINDOW's first column has no predecessor (vn[-1] = 0), not the file's previous sample --
+    a convention, so a window is no longer a crop of the whole file's emphasised row in its first column."""
+    return _frontend_result(return_waveform, *_audio_frontend_call(
+        "mvn_audio_frontend_window", "mvn_audio_frontend_window_scratch_floats", pcm, descriptors, 16, None,
+        quantization_channels, width, normalize, preemphasis=preemphasis))
 
 
 VIDEO_FRONTEND_SIZE = 64       # the front end's output is (64, 64) per frame (movenet/dataset.py:292-310)

@@ -28,6 +28,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
+from .checkpoint import preemphasis_record
 from .config import TrainingConfig, arg_parser, config_from_args
 from .dataset import get_dataloader, training_contexts
 from .optim import FlatAdamW, order_like_backward
@@ -71,6 +72,8 @@ class Dance2Music(nn.Module):
         if float(getattr(config, "generate_guidance", 1.0)) != 1.0:
             self.model.generate_guidance = float(config.generate_guidance)  # (ValueError without global classes)
         self.model.global_dropout = float(getattr(config, "global_dropout", 0.0))
+        # --preemphasis A: the loader's front end emphasises, the model remembers A for whoever turns its classes into audio
+        self.model.preemphasis = float(getattr(config, "preemphasis", 0.0))  # (ValueError outside [0, 1))
         self.model.global_dropout_generator = torch.Generator().manual_seed(torch.initial_seed() & (2 ** 63 - 1))
         self.current_epoch = 0
         self.precision = 32
@@ -252,6 +255,8 @@ class Dance2Music(nn.Module):
             video_antialias=bool(getattr(c, "video_antialias", False)),
             clip_length=getattr(c, "clip_length", "resample"), audio_rate=int(getattr(c, "audio_rate", 16000)),
             window_gain=getattr(c, "window_gain", "file"),
+            # (--preemphasis: the keyword goes only where it is on, the call without it is the call it was)
+            **({"preemphasis": self.model.preemphasis} if self.model.preemphasis > 0 else {}),
             # row F2: class indices cross PCIe (4 bytes per sample), the (B,Q,T) one-hot the Batch
             # contract asks for is formed on the device
             device=self.device if self.device.type == "cuda" else None)
@@ -539,6 +544,8 @@ class Trainer:
                                 # (--use_mel: what checkpoint.load_into rebuilds local_conv from; absent otherwise)
                                 **({"local_conditioning": dict(model.local_conditioning)}
                                    if getattr(model, "use_mel", False) else {}),
+                                # (--preemphasis A > 0: what checkpoint.load_into sets model.preemphasis from)
+                                **preemphasis_record(model.model),
                                 "state_dict": {f"model.{k}": v.detach().cpu()
                                                for k, v in model.model.state_dict().items()}},
                                ck / f"epoch={epoch}-step={self.global_step}.ckpt")
@@ -562,7 +569,8 @@ def train_model(dataset: str, config: TrainingConfig, logger_name: Optional[str]
         from .callbacks import LogSamplesCallback
         callbacks.append(LogSamplesCallback(log_every_n_epochs=config.log_samples_every, log_video=log_video,
                                             temperature_sweep=getattr(config, "generate_temperature_sweep", None) or (),
-                                            guidance=float(getattr(config, "generate_guidance", 1.0))))
+                                            guidance=float(getattr(config, "generate_guidance", 1.0)),
+                                            preemphasis=float(getattr(config, "preemphasis", 0.0))))
     trainer = Trainer(
         max_epochs=config.n_epochs, default_root_dir=config.model_output_path,
         gradient_clip_val=config.gradient_clipping,

@@ -17,6 +17,11 @@ Two sources, exactly one per call:
 ``writeframesraw`` per chunk and fixes the header on close, so a closed file is byte for byte what
 ``callbacks.write_wav`` writes for the whole clip.  Batch k of a run draws on ``--seed`` + k.  One line per file goes to
 stdout: path, samples, seconds of audio, wall seconds, seconds to the first generated chunk.
+
+A checkpoint of a run with ``--preemphasis A`` records A: the model's PCM then comes out through the de-emphasis filter
+and ``--from_wavs`` files go through the front end with that pre-emphasis, with no flag given.  ``--preemphasis``
+overrides it for a checkpoint that records none; a value other than the recorded one is an error unless
+``--force_preemphasis 1``.
 """
 from __future__ import annotations
 
@@ -109,18 +114,30 @@ def build_parser() -> argparse.ArgumentParser:
     a("--seed", type=int, default=None)
     a("--precision", type=str, default="fp32", choices=["fp32", "fp16"])
     a("--device", type=str, default="cuda")
+    a("--preemphasis", type=float, default=None, help="default: the checkpoint's record (0 without one)")
+    a("--force_preemphasis", type=int, default=0, help="1: take --preemphasis against the checkpoint's record")
     return p
 
 
 def load_model(args, fail):
     """The WaveNet of the model flags with the checkpoint's weights, on the CPU; ``local_conditioning`` and
     ``global_classes`` come from the checkpoint's records.  ``fail(message)`` is called (and must not return) where the
-    flags and the state dict's shapes disagree.  Returns (model, local record or None, class names)."""
-    from .checkpoint import _local_record, _read, _state_dict_of
+    flags and the state dict's shapes disagree, or ``--preemphasis`` and the checkpoint's record do.  The model's
+    ``preemphasis`` is the record's, or the flag's where it may stand.  Returns (model, local record or None, class names)."""
+    from .checkpoint import _local_record, _preemphasis_record, _read, _state_dict_of
     from .wavenet import WaveNet
     obj = _read(args.checkpoint)
     rec = _local_record(obj)
     names = list(obj.get("global_classes") or []) if isinstance(obj, dict) else []
+    emph = _preemphasis_record(obj)
+    if args.preemphasis is not None:
+        if not 0.0 <= args.preemphasis < 1.0:
+            fail(f"--preemphasis must lie in [0, 1), got {args.preemphasis}")
+        # (a file without the record -- a run without the flag, or an older file -- says nothing: the flag stands)
+        if emph > 0.0 and args.preemphasis != emph and not args.force_preemphasis:
+            fail(f"--preemphasis {args.preemphasis} given, but {args.checkpoint} records preemphasis {emph}: the model "
+                 "was trained on audio emphasised with that value (--force_preemphasis 1 to use the flag anyway)")
+        emph = float(args.preemphasis)
     try:
         sd = _state_dict_of(obj, args.checkpoint, bool(args.ema))
     except ValueError as e:
@@ -143,6 +160,7 @@ def load_model(args, fail):
              f"--stack_size {args.stack_size} ({len(wrong)} shapes differ, {len(missing)} keys missing, {len(extra)} "
              "unexpected): " + "; ".join(parts))
     model.load_state_dict(sd, strict=True)
+    model.preemphasis = emph
     if rec is not None:
         model.local_conditioning = rec
     return model, rec, names
@@ -162,7 +180,9 @@ def wav_batch(model, rec: dict, paths: List[str], device):
     with torch.cuda.device(device):
         d_pcm, d_desc = _upload_pcm(device, [c[0] for c in clips], "clips_var", audio_clip_var_descriptors(
             [c[1] for c in clips], [c[2] for c in clips], lengths))
-        idx = audio_frontend_var(d_pcm, d_desc, Q, width, normalize=True)
+        # (the checkpoint's pre-emphasis: the indices, and with them the mel frames, are those training saw)
+        emph = {"preemphasis": model.preemphasis} if model.preemphasis > 0.0 else {}
+        idx = audio_frontend_var(d_pcm, d_desc, Q, width, normalize=True, **emph)
         if bool((idx < 0).any().item()):
             bad = [paths[b] for b in range(len(paths)) if bool((idx[b] < 0).any().item())]
             raise ValueError(f"the audio front end refused {bad[0]} (resampling ratio beyond what it takes)")

@@ -229,6 +229,20 @@ class WaveNet(nn.Module):
             raise ValueError("generate_guidance needs a model built with global_classes (there is no label to guide by)")
         self._gen_guidance = list(scales) if N.any_per_sequence(value) else scales[0]
 
+    # ---- the pre-emphasis the model's classes were made under -------------
+    @property
+    def preemphasis(self) -> float:
+        """0.0 (default: off) or the coefficient a in (0, 1) of the pre-emphasis the training audio went through
+        (``WavFolderLoader(preemphasis=a)``): ``generate_stream`` then hands its PCM out through the inverse filter
+        (``ops.pcm16_chunk(deemphasis=a)``).  Not part of ``state_dict``: a checkpoint carries it as a record of its
+        own, which ``checkpoint.load_into`` sets here.  ``generate()`` returns classes and does not consult it."""
+        return getattr(self, "_preemphasis", 0.0)  # (a module pickled before the attribute existed)
+
+    @preemphasis.setter
+    def preemphasis(self, value: float) -> None:
+        N.emphasis(value)  # ValueError for anything outside [0, 1)
+        self._preemphasis = float(value)  # (as given: the kernels take its float32 value)
+
     # ---- the feature frames generate() runs under (DESIGN 4.5d) -------------------
     @property
     def generate_local_features(self):
@@ -713,18 +727,23 @@ class WaveNet(nn.Module):
         plan_chunks(0, 0, chunk)  # ValueError before anything is used up
         plan = self._generate_setup(audio, video, global_features, n_samples, temperature, what="generate_stream")
         idx, rf, n_total = plan.idx, plan.rf, plan.n_total
+        # (preemphasis > 0: one filter state per call, zero before column 0; the prompt's columns go through it first)
+        a = self.preemphasis
+        filt = {} if a <= 0.0 else {"deemphasis": a, "state": torch.zeros(idx.shape[0], dtype=torch.float64,
+                                                                          device=idx.device)}
         if plan.make is None:
             n = min(rf, n_total, int(audio.shape[2]))
             given = torch.zeros(idx.shape[0], max(n_total, 0), dtype=torch.int32, device=idx.device)
             given[:, :n] = idx[:, :n]
-            yield 0, pcm16_chunk(given, 0, given.shape[1], self.input_channels).cpu().numpy()
+            yield 0, pcm16_chunk(given, 0, given.shape[1], self.input_channels, **filt).cpu().numpy()
             return
-        yield 0, pcm16_chunk(idx, 0, rf, self.input_channels).cpu().numpy()
+        yield 0, pcm16_chunk(idx, 0, rf, self.input_channels, **filt).cpu().numpy()
 
         def chunks_of(variant, group):
             gen = plan.make(variant, group)
             gen.prime(idx[:, :rf])
-            return gen.stream(n_total - rf, chunk)
+            # (a rerun on the fallback kernel starts again behind the prompt: each run filters from a copy of that state)
+            return gen.stream(n_total - rf, chunk, **(filt and {"deemphasis": a, "state": filt["state"].clone()}))
 
         chunks = chunks_of(plan.variant, plan.group)
         try:
