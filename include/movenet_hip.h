@@ -1110,6 +1110,27 @@ int mvn_upsample_features_backward(const float *dctx, int dctx_ld, const float *
                                    float *dbias, float *dmel, int dmel_ld, float *scratch, size_t scratch_floats,
                                    void *stream);
 
+/* ---- Distance between two feature tensors (csrc/metrics.hip; additive, ABI version unchanged) ----
+ * a, b (batch, n_mels, frames) fp32, contiguous, DEVICE, read only; first, count (batch) int32, DEVICE: sequence s
+ * counts its frames [first[s], first[s] + count[s]).  With d = (double)a[s,m,f] - (double)b[s,m,f] over that span:
+ *     rms_f          = sqrt((1 / n_mels) sum_m d^2)
+ *     lsd[s]         = (10 / ln 10) (1 / count[s]) sum_f rms_f     dB where the features are natural logs of power
+ *     l1[s]          = (1 / (n_mels count[s])) sum_f sum_m |d|
+ *     per_frame[s,f] = (float)(rms_f 10 / ln 10) inside the span, 0.0f outside it
+ *   lsd, l1    DEVICE (batch) double each; count[s] == 0 stores 0.0 in both (nothing is divided)
+ *   per_frame  DEVICE (batch, frames) fp32, written in full; NULL: not formed, not written
+ *   scratch    DEVICE, 8-byte aligned, mvn_feature_distance_scratch_floats(batch, frames) floats, NOT initialised by
+ *              the caller: one pair of doubles per workgroup of 256 frames, all of them written by the first kernel
+ * No frame outside a sequence's span is read, whatever it holds; the kernels clamp the span to [0, frames) and the
+ * caller checks the range proper.  Every sum is formed in double in a fixed order, no atomics: the same inputs give
+ * the same bits on every call, and a sequence's results do not depend on the other sequences of the launch.
+ * MVN_ERR_BAD_ARG before any launch: a null pointer (per_frame excepted), batch, n_mels or frames below 1, batch above
+ * 65535, a scratch that is too small or misaligned. */
+size_t mvn_feature_distance_scratch_floats(int batch, int frames);
+int mvn_feature_distance(const float *a, const float *b, int batch, int n_mels, int frames, const int32_t *first,
+                         const int32_t *count, double *lsd, double *l1, float *per_frame, float *scratch,
+                         size_t scratch_floats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -315,6 +315,10 @@ SIGNATURES = {
     "mvn_upsample_features_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # distance between two feature tensors (csrc/metrics.hip)
+    "mvn_feature_distance_scratch_floats": (C.c_size_t, [C.c_int, C.c_int]),
+    "mvn_feature_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -19,7 +19,9 @@ written as ``...-gen-T<value>.wav``, one index row per (clip, temperature) with 
 With ``--score_samples 1`` the module also scores each logged batch (``Dance2Music.score_samples``: one
 ``WaveNet.score`` call) and every row of a clip carries ``bits_per_sample`` -- of the generated clip under the
 conditioning it was generated with -- and ``source_bits_per_sample`` -- of the clip it was prompted from.  Off (the
-default), no row carries either key.
+default), no row carries either key.  Under ``--use_mel 1`` the scores also hold ``mel_distance_db`` and ``mel_l1``, the
+log-mel distance of each generated row from the clip it was prompted from (``WaveNet.spectral_distance``), and every
+row carries them too; without ``--use_mel 1`` the rows are what they were.
 
 With ``--ema_decay`` the module generates ``outputs["generated_output"]`` on the averaged weights
 (``Dance2Music.averaged_weights``), on the train hook and on the validation hook, and the validation hook's
@@ -150,12 +152,16 @@ class LogSamplesCallback:
         if scores is not None:  # (--score_samples 1; rows are clip-major, len(sweep) or one per clip, as gen is)
             bits = scores["bits_per_sample"].cpu().tolist()
             source = scores["source_bits_per_sample"].cpu().tolist()
+            # (--use_mel 1: the log-mel distance of each generated row from its source clip; absent otherwise)
+            mel = {k: scores[k].cpu().tolist() for k in ("mel_distance_db", "mel_l1") if k in scores}
             per_clip = max(len(sweep), 1)
             kept = [i for i in range(len(fps)) if prompt_ok is None or prompt_ok[i]]
             for k, r in enumerate(rows):  # (the scores cover every clip of the batch; the rows only the kept ones)
                 clip = kept[k // per_clip]
                 r["bits_per_sample"] = bits[clip * per_clip + k % per_clip]
                 r["source_bits_per_sample"] = source[clip]
+                for name, values in mel.items():
+                    r[name] = values[clip * per_clip + k % per_clip]
         if gen is not None and self.guidance != 1.0:  # (as a sweep's rows carry their temperature)
             for r in rows:
                 r["guidance"] = self.guidance

@@ -347,12 +347,8 @@ def _grads_for_autograd(ctx_, grads, dctx, dgvec, n_fixed, need):
     return (*([None] * (n_fixed - 2)), dcontext, dgvec if need[n_fixed - 1] else None, *result)
 
 
-def valid_columns(lengths, T: int, RF: int):
-    """Per-sequence count of loss columns from per-sequence lengths: ``valid_b = clamp(len_b - RF, 0, S)`` with
-    ``S = T - RF`` (column s predicts sample RF + s, so it counts when that sample is real).  ``lengths``: (B,) host
-    sequence, numpy array or integer tensor of ``0 <= len_b <= T``.  Returns a list of ints; ValueError -- before
-    anything is launched -- for a wrong shape, a non-integer, a negative length or one above ``T``.  A tensor on the
-    GPU is read once through the pinned word channel of the one-hot check (generation.HostWords)."""
+def _checked_lengths(lengths, T: int):
+    """``lengths`` of ``valid_columns`` as a host list of ints in [0, T], its ValueErrors included."""
     if isinstance(lengths, torch.Tensor):
         if lengths.dim() != 1 or lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool:
             raise ValueError(f"lengths must be a (batch,) integer tensor, got {tuple(lengths.shape)} {lengths.dtype}")
@@ -369,15 +365,22 @@ def valid_columns(lengths, T: int, RF: int):
         if getattr(lengths, "ndim", 1) != 1:
             raise ValueError(f"lengths must be one-dimensional, got shape {getattr(lengths, 'shape', None)}")
         values = lengths.tolist() if hasattr(lengths, "tolist") else list(lengths)
-    S = max(int(T) - int(RF), 0)
-    out = []
     for b, v in enumerate(values):
         if isinstance(v, bool) or not isinstance(v, int):
             raise ValueError(f"lengths[{b}] = {v!r} is not an integer")
         if v < 0 or v > T:
             raise ValueError(f"lengths[{b}] = {v} lies outside [0, {T}]")
-        out.append(min(max(v - int(RF), 0), S))
-    return out
+    return values
+
+
+def valid_columns(lengths, T: int, RF: int):
+    """Per-sequence count of loss columns from per-sequence lengths: ``valid_b = clamp(len_b - RF, 0, S)`` with
+    ``S = T - RF`` (column s predicts sample RF + s, so it counts when that sample is real).  ``lengths``: (B,) host
+    sequence, numpy array or integer tensor of ``0 <= len_b <= T``.  Returns a list of ints; ValueError -- before
+    anything is launched -- for a wrong shape, a non-integer, a negative length or one above ``T``.  A tensor on the
+    GPU is read once through the pinned word channel of the one-hot check (generation.HostWords)."""
+    S = max(int(T) - int(RF), 0)
+    return [min(max(v - int(RF), 0), S) for v in _checked_lengths(lengths, T)]
 
 
 def _valid_for_batch(lengths, B: int, T: int, RF: int):
@@ -609,6 +612,96 @@ def logmel(indices: torch.Tensor, classes: int, n_fft: int, hop: int, fbank, flo
                                         twiddle.data_ptr(), fb.data_ptr(), float(floor), int(bool(energies)),
                                         out.data_ptr(), max(F, 1), scratch.data_ptr(), n, _stream_ptr(dev)),
                 "mvn_logmel_frontend")
+    return out
+
+
+# ---- distance between two feature tensors (csrc/metrics.hip) --------------------------------------------
+def distance_frame_span(lengths, T: int, n_fft: int, hop: int, skip: int = 0, batch: int = 1):
+    """The frames of ``logmel`` that count in a spectral distance, as ``(first, count)``, two host lists of one int per
+    sequence.  Frame f covers samples ``[f hop - h, f hop - h + n_fft)`` with ``h = n_fft // 2``; it counts when that
+    window lies wholly inside ``[skip, len_b)``:
+
+        first_b = ceil((skip + h) / hop),  last_b = floor((len_b - n_fft + h) / hop),
+        count_b = max(0, min(last_b, F - 1) - first_b + 1),  F = logmel_frames(T, hop)
+
+    ``skip`` keeps a copy-synthesis clip's prompt -- the source's own first samples -- from counting as a perfect
+    match.  ``lengths``: as in ``valid_columns`` (its ValueErrors too), or None: each of ``batch`` rows is ``T``
+    long.  Host integers only; nothing is launched."""
+    T, n_fft, hop = int(T), int(n_fft), int(hop)
+    if isinstance(skip, bool) or not isinstance(skip, int) or skip < 0:
+        raise ValueError(f"skip must be an integer >= 0, got {skip!r}")
+    if T < 1 or n_fft < 1 or hop < 1:
+        raise ValueError(f"distance_frame_span: need T, n_fft and hop of at least 1, got {T}, {n_fft}, {hop}")
+    values = [T] * int(batch) if lengths is None else _checked_lengths(lengths, T)
+    h, F = n_fft // 2, logmel_frames(T, hop)
+    first_f = -((-(skip + h)) // hop)  # ceil
+
+    def count(n):
+        last = (n - n_fft + h) // hop  # floor, also of a negative numerator
+        return max(0, min(last, F - 1) - first_f + 1)
+    return [first_f] * len(values), [count(v) for v in values]
+
+
+def _span_values(values, name: str, B: int):
+    """``first`` / ``count`` of ``feature_distance`` as a host list of B ints."""
+    if isinstance(values, torch.Tensor):
+        if values.dim() != 1 or values.is_floating_point() or values.is_complex() or values.dtype == torch.bool:
+            raise ValueError(f"{name} must be a (batch,) integer tensor, got {tuple(values.shape)} {values.dtype}")
+        values = values.detach().cpu().tolist()
+    else:
+        if isinstance(values, (str, bytes)) or not hasattr(values, "__len__") or getattr(values, "ndim", 1) != 1:
+            raise ValueError(f"{name} must be a one-dimensional sequence of one integer per sequence, got {values!r}")
+        values = values.tolist() if hasattr(values, "tolist") else list(values)
+    if len(values) != B:
+        raise ValueError(f"{name} names {len(values)} sequences, the batch holds {B}")
+    for b, v in enumerate(values):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{name}[{b}] = {v!r} is not an integer")
+    return values
+
+
+def feature_distance(a: torch.Tensor, b: torch.Tensor, first=None, count=None, per_frame: bool = False) -> dict:
+    """Log-spectral distance and mean absolute difference of two (B, M, F) float32 feature tensors on the GPU, e.g.
+    two ``logmel`` outputs, over ONE span of frames per sequence (mvn_feature_distance; read only).  With
+    ``d = a - b`` in double over frames ``[first_b, first_b + count_b)``:
+
+        rms_f = sqrt(mean_m d^2),  lsd_db[b] = (10 / ln 10) mean_f rms_f,  l1[b] = mean_{f,m} |d|
+
+    ``first`` / ``count``: host sequences, numpy arrays or integer tensors of B values (default: every frame).  Returns
+    ``{"lsd_db": (B,) float64, "l1": (B,) float64, "frames": (B,) int32}`` and, on request, ``"per_frame"``: (B, F)
+    float32, ``rms_f 10 / ln 10`` inside the span and exactly 0 outside it.  An empty span gives 0.0, never NaN.  No
+    frame outside a span is read.  Every sum is formed in double in a fixed order: the same bits on every call, and
+    a row's result does not depend on the other rows.  ValueError before any launch for a shape or dtype mismatch or
+    a span that leaves [0, F]; RuntimeError for a CPU tensor."""
+    _require_gpu(a, "a")
+    _require_gpu(b, "b")
+    if a.dim() != 3 or a.dtype != torch.float32 or min(a.shape) < 1:
+        raise ValueError(f"a must be a (batch, bins, frames) float32 tensor with no empty axis, got {tuple(a.shape)} "
+                         f"{a.dtype}")
+    if tuple(b.shape) != tuple(a.shape) or b.dtype != torch.float32 or b.device != a.device:
+        raise ValueError(f"b must be a {tuple(a.shape)} float32 tensor on {a.device}, got {tuple(b.shape)} {b.dtype} "
+                         f"on {b.device}")
+    B, M, F = (int(v) for v in a.shape)
+    first = [0] * B if first is None else _span_values(first, "first", B)
+    count = [F - f for f in first] if count is None else _span_values(count, "count", B)
+    for s, (f0, n) in enumerate(zip(first, count)):
+        if f0 < 0 or n < 0 or f0 + n > F:
+            raise ValueError(f"the span of sequence {s}, first = {f0} and count = {n}, leaves the {F} frames")
+    dev = a.device
+    x, y = a.detach().contiguous(), b.detach().contiguous()
+    lib = N.lib()
+    with torch.cuda.device(dev):
+        span = counts_to_device(first + count, dev)  # (one copy: first in front, count behind)
+        out = {"lsd_db": torch.empty(B, dtype=torch.float64, device=dev),
+               "l1": torch.empty(B, dtype=torch.float64, device=dev), "frames": span[B:]}
+        if per_frame:
+            out["per_frame"] = torch.empty(B, F, dtype=torch.float32, device=dev)
+        n = int(lib.mvn_feature_distance_scratch_floats(B, F))
+        scratch = torch.empty(max(n, 1) // 2 + 1, dtype=torch.float64, device=dev)  # (doubles: 8-byte aligned)
+        N.check(lib.mvn_feature_distance(x.data_ptr(), y.data_ptr(), B, M, F, span.data_ptr(), span[B:].data_ptr(),
+                                         out["lsd_db"].data_ptr(), out["l1"].data_ptr(),
+                                         out["per_frame"].data_ptr() if per_frame else None, scratch.data_ptr(), n,
+                                         _stream_ptr(dev)), "mvn_feature_distance")
     return out
 
 

@@ -63,6 +63,8 @@ class Dance2Music(nn.Module):
                                        "mel_fmax": fmax, "audio_rate": rate}
             local = {"local_channels": int(config.mel_bins), "local_hop": int(config.mel_hop)}
         self.model = WaveNet(**asdict(config.model_config), global_classes=len(self.global_classes), **local)
+        if self.use_mel:  # (what checkpoint.load_into leaves there: WaveNet.spectral_distance reads the mel settings)
+            self.model.local_conditioning = dict(self.local_conditioning)
         self.model.generate_sampling = config.generate_sampling  # (ValueError for an unknown rule)
         self.model.generate_top_k = config.generate_top_k        # (... a negative k, a p outside (0, 1])
         self.model.generate_top_p = config.generate_top_p
@@ -163,7 +165,8 @@ class Dance2Music(nn.Module):
         ``WaveNet.score`` call: the generated rows (len(sweep) per clip, clip-major, under a temperature sweep), then
         the sources.  A generated length other than the source's is scored over the common leading part.  With
         ``lengths`` (the batch's, clip_length="native") a source is scored over its own real samples only; the
-        generated rows are scored in full."""
+        generated rows are scored in full.  With ``local_features`` (``--use_mel 1``) also ``mel_distance_db`` and
+        ``mel_l1``, one value per generated row: its log-mel distance from its source clip."""
         n = generated.shape[0] // audio.shape[0]
         frames = min(int(generated.shape[2]), int(audio.shape[2]))
         if video is not None and frames != int(audio.shape[2]):
@@ -178,7 +181,17 @@ class Dance2Music(nn.Module):
                                lengths=None if lengths is None else
                                [frames] * int(generated.shape[0]) + [min(int(v), frames) for v in lengths])
         bits = res.bits_per_sample.detach()
-        return {"bits_per_sample": bits[:generated.shape[0]], "source_bits_per_sample": bits[generated.shape[0]:]}
+        out = {"bits_per_sample": bits[:generated.shape[0]], "source_bits_per_sample": bits[generated.shape[0]:]}
+        if local_features is not None:
+            # --use_mel: the clip is a copy-synthesis of its source, so the two can be compared -- the log-mel distance
+            # of each generated row from the clip it was prompted from, over the frames past the prompt and inside the
+            # clip's own length (WaveNet.spectral_distance)
+            clip_len = [frames] * int(audio.shape[0]) if lengths is None else [min(int(v), frames) for v in lengths]
+            dist = self.model.spectral_distance(
+                generated[:, :, :frames].argmax(1), audio[:, :, :frames].argmax(1).repeat_interleave(n, dim=0),
+                lengths=[v for v in clip_len for _ in range(n)])
+            out["mel_distance_db"], out["mel_l1"] = dist.lsd_db, dist.l1
+        return out
 
     def generate(self, audio, video, labels=None, local_features=None):
         if not self._generates_now():

@@ -166,15 +166,19 @@ def load_model(args, fail):
     return model, rec, names
 
 
-def wav_batch(model, rec: dict, paths: List[str], device):
-    """The front end of copy-synthesis for one batch of files: (idx, lengths, feats) -- ``idx`` (B, width) int32 class
-    indices on the device, each file resampled as a whole to ``rec["audio_rate"]`` (``lengths[b]`` samples, silence
-    behind them up to the batch's longest), ``feats`` their log-mel frames by the checkpoint's mel settings."""
+def wav_indices(model, rate: int, paths: List[str], device, max_samples: Optional[int] = None):
+    """One batch of files through the loader's GPU front end: (idx, lengths) -- ``idx`` (B, width) int32 class indices
+    on the device, each file resampled as a whole to ``rate`` (``lengths[b]`` samples, silence behind them up to the
+    batch's longest), under the model's pre-emphasis.  ``max_samples``: a file that resamples to more is a ValueError
+    that names it and the limit, before anything is uploaded."""
     from .dataset import WavFolderLoader, _upload_pcm, read_wav_pcm16
-    from .ops import audio_clip_var_descriptors, audio_frontend_var, logmel, mel_filterbank
-    rate, device = int(rec["audio_rate"]), torch.device(device)
+    from .ops import audio_clip_var_descriptors, audio_frontend_var
+    rate, device = int(rate), torch.device(device)
     clips = [read_wav_pcm16(p) for p in paths]
     lengths = [WavFolderLoader.native_plan(c[1], c[3], 1 << 30, rate)[1] for c in clips]
+    for p, n in zip(paths, lengths):
+        if max_samples is not None and n > max_samples:
+            raise ValueError(f"{p} is {n} samples long at {rate} Hz: more than the {max_samples} samples of one row")
     width = max(lengths)
     Q = model.input_channels
     with torch.cuda.device(device):
@@ -186,6 +190,17 @@ def wav_batch(model, rec: dict, paths: List[str], device):
         if bool((idx < 0).any().item()):
             bad = [paths[b] for b in range(len(paths)) if bool((idx[b] < 0).any().item())]
             raise ValueError(f"the audio front end refused {bad[0]} (resampling ratio beyond what it takes)")
+    return idx, lengths
+
+
+def wav_batch(model, rec: dict, paths: List[str], device, max_samples: Optional[int] = None):
+    """The front end of copy-synthesis for one batch of files: (idx, lengths, feats) -- ``wav_indices`` at
+    ``rec["audio_rate"]``, and ``feats``, the indices' log-mel frames by the checkpoint's mel settings."""
+    from .ops import logmel, mel_filterbank
+    rate, device = int(rec["audio_rate"]), torch.device(device)
+    idx, lengths = wav_indices(model, rate, paths, device, max_samples)
+    Q = model.input_channels
+    with torch.cuda.device(device):
         fbank = mel_filterbank(int(rec["local_channels"]), int(rec["mel_fft"]), rate, float(rec["mel_fmin"]),
                                float(rec["mel_fmax"]))
         feats = logmel(idx, Q, int(rec["mel_fft"]), int(rec["local_hop"]), torch.from_numpy(fbank).to(torch.float32))

@@ -65,6 +65,14 @@ class ScoreResult(_ScoreFields):
         return self
 
 
+class SpectralDistance(NamedTuple):
+    """What ``WaveNet.spectral_distance`` returns, one value per sequence."""
+    lsd_db: torch.Tensor   # (B,) float64 log-spectral distance of the log-mel frames, dB
+    l1: torch.Tensor       # (B,) float64 mean absolute difference of the log-mel frames, nats
+    frames: torch.Tensor   # (B,) int32 frames that were compared
+    per_frame: Optional[torch.Tensor] = None  # (B, F) float32 distance of each frame, dB; 0 outside the span (on request)
+
+
 class WaveNet(nn.Module):
     def __init__(self, layer_size: int, stack_size: int, input_channels: int,
                  residual_channels: int = 16, skip_channels: int = 16,
@@ -535,6 +543,65 @@ class WaveNet(nn.Module):
         context = self._context_of(audio, video, local_features)
         raw = wavenet_score(self, audio, context, gvec, temperature, entropy=entropy, rank=rank, valid=valid)
         return self._score_result(raw, int(audio.shape[2]) - self.receptive_fields, valid)
+
+    def _class_indices(self, x: torch.Tensor, what: str) -> torch.Tensor:
+        """(B, T) integer classes, or (B, Q, T) one-hot through ``_indices_of``, as (B, T) int32 on the device."""
+        _require_gpu(x, what)
+        if x.dim() == 3:
+            return self._indices_of(x)
+        if x.dim() != 2 or x.is_floating_point() or x.dtype == torch.bool:
+            raise ValueError(f"{what} must be (batch, samples) integer classes or (batch, {self.input_channels}, "
+                             f"samples) one-hot, got {tuple(x.shape)} {x.dtype}")
+        return x.detach().to(torch.int32).contiguous()
+
+    @torch.no_grad()
+    def spectral_distance(self, generated, source, lengths=None, skip: Optional[int] = None, per_frame: bool = False, *,
+                          n_fft: Optional[int] = None, hop: Optional[int] = None, n_mels: Optional[int] = None,
+                          rate: Optional[float] = None, f_min: Optional[float] = None,
+                          f_max: Optional[float] = None) -> "SpectralDistance":
+        """How far ``generated`` is from ``source`` in the log-mel domain: the log-spectral distance (dB) and the
+        mean absolute difference (nats) of their ``ops.logmel`` frames, per sequence (``ops.feature_distance``).
+        Both are (B, T) integer class indices on the GPU, or (B, Q, T) one-hot.
+
+        The frames are made with the settings of the model's ``local_conditioning`` record (a model trained with
+        ``--use_mel 1``, or loaded from its checkpoint); any of ``n_fft``, ``hop``, ``n_mels``, ``rate``, ``f_min``,
+        ``f_max`` given here takes the record's place, and a model without the record needs the first four.  A frame
+        counts when its window lies wholly past the first ``skip`` samples (default: ``receptive_fields``, the prompt
+        of a copy-synthesis, which is the source's own) and inside the row's ``lengths[b]`` real samples (default:
+        the whole row) -- ``ops.distance_frame_span``.
+
+        Under ``preemphasis`` both sides are the EMPHASISED signal, because that is what the class indices encode:
+        the distance weighs high frequencies more than one taken on the de-emphasised audio would.
+
+        Returns a ``SpectralDistance``: ``lsd_db``, ``l1`` (B,) float64, ``frames`` (B,) int32 and, on request,
+        ``per_frame`` (B, F) float32 (else None).  A row with no counted frame has 0.0 in both."""
+        from . import ops
+        rec = getattr(self, "local_conditioning", None) or {}
+        given = {"n_fft": n_fft, "hop": hop, "n_mels": n_mels, "rate": rate, "f_min": f_min, "f_max": f_max}
+        keys = {"n_fft": "mel_fft", "hop": "local_hop", "n_mels": "local_channels", "rate": "audio_rate",
+                "f_min": "mel_fmin", "f_max": "mel_fmax"}
+        s = {k: (v if v is not None else rec.get(keys[k])) for k, v in given.items()}
+        missing = [k for k in ("n_fft", "hop", "n_mels", "rate") if s[k] is None]
+        if missing:
+            raise ValueError("spectral_distance: the model has no local_conditioning record (it was not trained with "
+                             "--use_mel 1); pass the keyword arguments n_fft, hop, n_mels, rate (and f_min, f_max) "
+                             f"instead -- missing: {', '.join(missing)}")
+        g, x = self._class_indices(generated, "generated"), self._class_indices(source, "source")
+        if g.shape != x.shape or g.device != x.device:
+            raise ValueError(f"generated {tuple(g.shape)} on {g.device} and source {tuple(x.shape)} on {x.device} "
+                             "must agree")
+        B, T = (int(v) for v in x.shape)
+        skip = self.receptive_fields if skip is None else skip
+        first, count = ops.distance_frame_span(lengths, T, int(s["n_fft"]), int(s["hop"]), skip, batch=B)
+        if len(first) != B:
+            raise ValueError(f"lengths names {len(first)} sequences, the batch holds {B}")
+        F = ops.logmel_frames(T, int(s["hop"]))
+        first = [min(f, F - n) for f, n in zip(first, count)]  # (an empty span past the last frame starts at F)
+        fbank = ops.mel_filterbank(int(s["n_mels"]), int(s["n_fft"]), float(s["rate"]),
+                                   0.0 if s["f_min"] is None else float(s["f_min"]), s["f_max"])
+        mels = [ops.logmel(i, self.input_channels, int(s["n_fft"]), int(s["hop"]), fbank) for i in (g, x)]
+        out = ops.feature_distance(mels[0], mels[1], first, count, per_frame=per_frame)
+        return SpectralDistance(out["lsd_db"], out["l1"], out["frames"], out.get("per_frame"))
 
     @torch.no_grad()
     def classify(self, audio, video=None, log_prior=None, logits_budget_bytes: int = 1 << 30, lengths=None, *,
