@@ -1,4 +1,7 @@
-"""ctypes binding of libmovenet_hip.so (the C ABI in include/movenet_hip.h).
+"""ctypes binding of libmovenet_hip.so, READ from the C ABI's header include/movenet_hip.h at import: every
+``mvn_*`` prototype becomes a row of ``SIGNATURES`` and every ``#define MVN_* <integer>`` a module attribute.  Only
+the struct layouts below are written out by hand (tests/test_abi_layout_host.py pins them to the header with a
+compiler).  Importing this module needs the header, not the library and not a GPU.
 
 There is deliberately NO fallback: if the library is missing or fails to load,
 every entry point raises ``NativeLibraryError`` -- the product never routes
@@ -8,34 +11,15 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from typing import Optional, Sequence
 
 # MOVENET_HIP_LIB selects another build of the SAME library (the diagnostic twin with
 # in-kernel stamps); it is not a fallback mechanism.
 LIB_PATH = os.environ.get("MOVENET_HIP_LIB") or os.path.join(
     os.path.dirname(os.path.abspath(__file__)), "lib", "libmovenet_hip.so")
-
-MVN_OK = 0
-MVN_ERR_BAD_DIMS = -1
-MVN_ERR_BAD_ARG = -2
-MVN_ERR_TOO_SHORT = -3
-MVN_ERR_LAUNCH = -4
-MVN_ERR_UNSUPPORTED = -5
-
-GEN_AUTO, GEN_GENERIC, GEN_STREAM, GEN_PIPE, GEN_PIPE_F16, GEN_FOLD = 0, 1, 2, 3, 4, 5
-BWD_FORM_GENERIC, BWD_FORM_HALVES, BWD_FORM_ONE = 1, 2, 3  # mvn_last_backward_form (include/movenet_hip.h)
-BWD_FORM_BF16 = 4  # mvn_backward_bf16's layer kernel
-BLOCK_FORM_GENERIC, BLOCK_FORM_FUSED64 = 1, 2  # mvn_block_last_form: the kernel form of the last block call
-BWD_FORM_ONE_GLOBAL = 5  # mvn_backward_global: BWD_FORM_ONE with the label's row sums of df | dg
-BWD_FORM_BF16_GLOBAL = 6  # mvn_backward_bf16_global: BWD_FORM_BF16 with the row sums formed inside the layer kernel
-BWD_FORM_BF16_CTX = 7  # mvn_backward_bf16_ctx: BWD_FORM_BF16 writing df | dg for the fp32 context pass
-# mvn_last_embed_form: the embedding gradient's kernel form in the last backward (include/movenet_hip.h)
-EMBED_FORM_DENSE, EMBED_FORM_MFMA, EMBED_FORM_LDS, EMBED_FORM_TABLES, EMBED_FORM_ATOMICS = 1, 2, 3, 4, 5
-SAMPLE_REFERENCE, SAMPLE_MODEL = 0, 1  # mvn_generate_ex's rule of a sampled step (include/movenet_hip.h)
-SAMPLING_RULES = {"reference": SAMPLE_REFERENCE, "model": SAMPLE_MODEL}
-LOSS_REFERENCE, LOSS_MODEL = 0, 1  # mvn_softmax_ce_*_ex's loss rule (include/movenet_hip.h)
-LOSS_RULES = {"reference": LOSS_REFERENCE, "model": LOSS_MODEL}
-PIPE_VARIANTS = (GEN_PIPE, GEN_PIPE_F16, GEN_FOLD)  # variants with a hand-off status word
+# The contract; csrc/build.py compiles against this same file.
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "movenet_hip.h")
 
 
 class NativeLibraryError(RuntimeError):
@@ -66,9 +50,6 @@ class Params(C.Structure):
         ("head1_w", C.c_void_p), ("head1_b", C.c_void_p),
         ("head2_w", C.c_void_p), ("head2_b", C.c_void_p),
     ]
-
-
-_FP = C.POINTER(C.c_void_p)
 
 
 class FwdBuffers(C.Structure):
@@ -113,213 +94,95 @@ class BlockGatedParams(C.Structure):  # also used for mvn_block_gated_grads (sam
         "residual_w", "residual_b", "skip_w", "skip_b")]
 
 
-_BT = C.POINTER(BlockTensor)
-_BG = C.POINTER(BlockGatedParams)
-
-
 class VideoParams(C.Structure):  # also used for mvn_video_grads (same layout)
     _fields_ = [("conv_w", C.c_void_p), ("conv_b", C.c_void_p),
                 ("up_w", C.c_void_p * 3), ("up_b", C.c_void_p * 3)]
 
 
-# name -> (restype, argtypes); tests/test_capi.py checks the header against this
-SIGNATURES = {
-    "mvn_abi_version": (C.c_int, []),
-    "mvn_reload_switches": (C.c_int, []),
-    "mvn_last_error": (C.c_char_p, []),
-    "mvn_receptive_fields": (C.c_int, [C.POINTER(Dims)]),
-    "mvn_output_size": (C.c_int, [C.POINTER(Dims), C.c_int]),
-    "mvn_gen_variant": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_int]),
-    "mvn_gen_launch_pipelines": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_int]),
-    "mvn_gen_launch_is_cooperative": (C.c_int, []),
-    "mvn_gen_weights_floats": (C.c_size_t, [C.POINTER(Dims), C.c_int]),
-    "mvn_gen_state_floats": (C.c_size_t, [C.POINTER(Dims), C.c_int]),
-    "mvn_gen_status_offset": (C.c_size_t, [C.POINTER(Dims), C.c_int]),
-    "mvn_gen_pack_weights": (C.c_int, [C.POINTER(Dims), C.c_int, C.POINTER(Params), C.c_void_p,
-                                       C.c_void_p]),
-    "mvn_generate": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                               C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "mvn_generate_ex": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                  C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
-    "mvn_generate_trunc": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                     C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                     C.c_float, C.c_void_p]),
-    "mvn_seq_sampling_check": (C.c_int, [C.POINTER(SeqSampling), C.c_int, C.c_int]),
-    "mvn_generate_seq": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
-    "mvn_gen_guided_max_pairs": (C.c_int, [C.POINTER(Dims), C.c_int]),
-    "mvn_generate_guided": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
-    "mvn_transpose_context": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                        C.c_void_p]),
-    "mvn_padded_len": (C.c_int, [C.c_int]),
-    "mvn_forward": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.c_void_p, C.c_int, C.c_int,
-                              C.c_int, C.POINTER(FwdBuffers), C.c_void_p, C.c_int, C.c_int,
-                              C.c_int, C.c_void_p]),
-    "mvn_forward_f16": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.c_void_p, C.c_int, C.c_int,
-                                  C.c_int, C.POINTER(FwdBuffers), C.c_void_p, C.c_int, C.c_int,
-                                  C.c_int, C.c_void_p]),
-    "mvn_backward": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(ParamGrads),
-                               C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FwdBuffers),
-                               C.POINTER(BwdBuffers), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                               C.c_void_p]),
-    "mvn_forward_bf16": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.c_void_p, C.c_int, C.c_int,
-                                   C.c_int, C.POINTER(FwdBuffers), C.c_void_p, C.c_int, C.c_int,
-                                   C.c_int, C.c_void_p]),
-    "mvn_backward_bf16": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(ParamGrads),
-                                    C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FwdBuffers),
-                                    C.POINTER(BwdBuffers), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                    C.c_void_p]),
-    "mvn_last_backward_form": (C.c_int, []),
-    "mvn_last_embed_form": (C.c_int, []),
-    "mvn_context_add_global": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "mvn_global_fast_path": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_int]),
-    "mvn_global_bias": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "mvn_forward_global": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.c_void_p, C.c_int, C.c_int,
-                                     C.c_int, C.POINTER(FwdBuffers), C.c_void_p, C.c_int, C.c_int,
-                                     C.c_int, C.c_void_p, C.c_void_p]),
-    "mvn_backward_global": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(ParamGrads),
-                                      C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FwdBuffers),
-                                      C.POINTER(BwdBuffers), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
-    "mvn_backward_scratch": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(ParamGrads),
-                                       C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FwdBuffers),
-                                       C.POINTER(BwdBuffers), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                       C.c_void_p, C.c_size_t, C.c_void_p]),
-    "mvn_global_scratch_floats": (C.c_size_t, [C.POINTER(Dims), C.c_int, C.c_int]),
-    "mvn_global_bias_backward": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(ParamGrads), C.c_void_p,
-                                           C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "mvn_global_bf16_path": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_int]),
-    "mvn_global_bf16_scratch_floats": (C.c_size_t, [C.POINTER(Dims), C.c_int, C.c_int]),
-    "mvn_forward_bf16_global": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.c_void_p, C.c_int, C.c_int,
-                                          C.c_int, C.POINTER(FwdBuffers), C.c_void_p, C.c_int, C.c_int,
-                                          C.c_int, C.c_void_p, C.c_void_p]),
-    "mvn_backward_bf16_global": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(ParamGrads),
-                                           C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FwdBuffers),
-                                           C.POINTER(BwdBuffers), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
-    "mvn_bf16_ctx_path": (C.c_int, [C.POINTER(Dims), C.c_int, C.c_int]),
-    "mvn_bf16_ctx_scratch_floats": (C.c_size_t, [C.POINTER(Dims), C.c_int, C.c_int]),
-    "mvn_forward_bf16_ctx": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.c_void_p, C.c_int, C.c_int,
-                                       C.c_int, C.POINTER(FwdBuffers), C.c_void_p, C.c_int, C.c_int,
-                                       C.c_int, C.c_void_p]),
-    "mvn_backward_bf16_ctx": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(ParamGrads),
-                                        C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FwdBuffers),
-                                        C.POINTER(BwdBuffers), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                        C.c_void_p, C.c_size_t, C.c_void_p]),
-    "mvn_upsample_video": (C.c_int, [C.POINTER(Dims), C.POINTER(VideoParams), C.c_void_p, C.c_int,
-                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_int, C.c_void_p]),
-    "mvn_upsample_video_scratch_floats": (C.c_size_t, [C.POINTER(Dims), C.c_int, C.c_int]),
-    "mvn_upsample_video_backward": (C.c_int, [C.POINTER(Dims), C.POINTER(VideoParams),
-                                              C.POINTER(VideoParams), C.c_void_p, C.c_int, C.c_int,
-                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "mvn_gen_prime_from_forward": (C.c_int, [C.POINTER(Dims), C.POINTER(FwdBuffers), C.c_int,
-                                             C.c_int, C.c_void_p, C.c_void_p]),
-    "mvn_ce_parts": (C.c_int, [C.c_int, C.c_int]),
-    "mvn_ce_on_probs_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                          C.c_void_p, C.c_void_p]),
-    "mvn_ce_on_probs_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mvn_softmax_ce_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                         C.c_void_p, C.c_void_p]),
-    "mvn_softmax_ce_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                          C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
-                                          C.c_void_p]),
-    "mvn_softmax_ce_forward_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                            C.c_void_p, C.c_int, C.c_void_p]),
-    "mvn_softmax_ce_backward_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                             C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
-                                             C.c_int, C.c_void_p]),
-    # (the _ex pair and mvn_score_columns with a DEVICE array of per-sequence column counts before the stream)
-    "mvn_softmax_ce_forward_len": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "mvn_softmax_ce_backward_len": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                              C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
-                                              C.c_int, C.c_void_p, C.c_void_p]),
-    "mvn_score_columns_len": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                        C.c_void_p, C.c_void_p]),
-    "mvn_score_scratch_floats": (C.c_size_t, [C.c_int, C.c_int]),
-    "mvn_score_columns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                    C.c_void_p]),
-    "mvn_adamw_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float,
-                                 C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
-                                 C.POINTER(C.c_size_t), C.c_int, C.c_void_p]),
-    "mvn_adamw_ema_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                     C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
-                                     C.c_float, C.POINTER(C.c_size_t), C.c_int, C.c_void_p]),
-    "mvn_mu_law_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
-    "mvn_mu_law_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
-    "mvn_pcm16_chunk": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                  C.c_void_p]),
-    "mvn_pcm16_deemph_chunk": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "mvn_onehot_to_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                      C.c_void_p]),
-    "mvn_index_to_onehot": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                      C.c_void_p]),
-    "mvn_audio_frontend_scratch_floats": (C.c_size_t, [C.c_int, C.c_int]),
-    "mvn_audio_frontend": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mvn_audio_frontend_var_scratch_floats": (C.c_size_t, [C.c_int, C.c_int]),
-    "mvn_audio_frontend_var": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mvn_audio_frontend_window_scratch_floats": (C.c_size_t, [C.c_int, C.c_int]),
-    "mvn_audio_frontend_window": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    # (form -- AUDIO_FORM_* below -- in front, the coefficient behind `normalize`, the emphasised waveform behind `index`)
-    "mvn_audio_frontend_emph": (C.c_int, [C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                          C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p]),
-    "mvn_video_frontend": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                     C.c_void_p, C.c_void_p]),
-    "mvn_publish_words": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_void_p]),
-    # the five building blocks (csrc/blocks.hip)
-    "mvn_block_last_form": (C.c_int, []),
-    "mvn_block_conv_scratch_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "mvn_block_causal_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _BT, _BT, C.c_int, C.c_void_p]),
-    "mvn_block_causal_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _BT, _BT, _BT, C.c_void_p, C.c_void_p,
-                                            C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "mvn_block_dilated_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _BT, _BT, C.c_int, C.c_void_p]),
-    "mvn_block_dilated_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _BT, _BT, _BT, C.c_void_p, C.c_void_p,
-                                             C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "mvn_block_gated_scratch_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "mvn_block_gated_forward": (C.c_int, [_BG, C.c_int, C.c_int, C.c_int, _BT, _BT, _BT, _BT, _BT, _BT, C.c_int,
-                                          C.c_void_p, C.c_size_t, C.c_void_p]),
-    "mvn_block_gated_backward": (C.c_int, [_BG, _BG, C.c_int, C.c_int, C.c_int, _BT, _BT, _BT, _BT, _BT, _BT, _BT, _BT,
-                                           C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "mvn_block_dense_scratch_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "mvn_block_dense_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _BT, _BT,
-                                          _BT, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "mvn_block_dense_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _BT, _BT, _BT, _BT, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
-                                           C.c_void_p]),
-    # local conditioning on log-mel frames (csrc/features.hip)
-    "mvn_logmel_scratch_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "mvn_logmel_frontend": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                      C.c_size_t, C.c_void_p]),
-    "mvn_upsample_features_scratch_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "mvn_upsample_features": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
-                                        C.c_void_p]),
-    "mvn_upsample_features_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
-                                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
-    # distance between two feature tensors (csrc/metrics.hip)
-    "mvn_feature_distance_scratch_floats": (C.c_size_t, [C.c_int, C.c_int]),
-    "mvn_feature_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-}
+# ---- the header reader: C declarations -> ctypes.  What it does not know it refuses; it never guesses. ----
+_SCALARS = {"int": C.c_int, "float": C.c_float, "size_t": C.c_size_t, "long long": C.c_longlong,
+            "int32_t": C.c_int32, "uint64_t": C.c_uint64, "unsigned long long": C.c_uint64}
+# `T *` for a T that Python fills in HOST memory is POINTER(its class); every other pointer -- device memory, the
+# stream, the device-side descriptor arrays -- is a c_void_p.
+_HOST_POINTEES = {"mvn_dims": Dims, "mvn_params": Params, "mvn_param_grads": ParamGrads, "mvn_fwd_buffers": FwdBuffers,
+                  "mvn_bwd_buffers": BwdBuffers, "mvn_video_params": VideoParams, "mvn_video_grads": VideoParams,
+                  "mvn_block_tensor": BlockTensor, "mvn_block_gated_params": BlockGatedParams,
+                  "mvn_block_gated_grads": BlockGatedParams, "mvn_seq_sampling": SeqSampling,
+                  "size_t": C.c_size_t}  # (mvn_adamw_step's skip_ranges)
+# The exceptions to that rule, by (function, parameter name): these two take a DEVICE array of mvn_seq_sampling
+# (only mvn_seq_sampling_check takes the host array).
+_OVERRIDES = {("mvn_generate_seq", "per_seq"): C.c_void_p, ("mvn_generate_guided", "per_seq"): C.c_void_p}
+
+
+def _ctype(function: str, decl: str, position: Optional[int] = None):
+    """The ctypes type of one declaration of ``function``: its parameter number ``position``, else its return type."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    stars, name = words.count("*"), ""
+    if position is not None and len(words) > 1 and words[-1].isidentifier() and (
+            stars or " ".join(words) not in _SCALARS):  # (the name is optional: `long long` has none)
+        name = words.pop()
+    base, kind = " ".join(words[:len(words) - stars]), None
+    if base and words[len(words) - stars:] == ["*"] * stars:
+        if position is None:
+            kind = C.c_char_p if (base, stars) == ("char", 1) else None if stars else _SCALARS.get(base)
+        elif (function, name) in _OVERRIDES:
+            kind = _OVERRIDES[function, name]
+        elif not stars:
+            kind = _SCALARS.get(base)
+        else:
+            kind = C.POINTER(_HOST_POINTEES[base]) if stars == 1 and base in _HOST_POINTEES else C.c_void_p
+    if kind is None:
+        what = "the return type" if position is None else f"parameter {name!r}" if name else f"parameter {position}"
+        raise NativeLibraryError(f"{function}: {what} is declared `{' '.join(decl.split())}`, which the header reader "
+                                 "does not know (movenet_amd/_native.py)")
+    return kind
+
+
+def read_header(text: str):
+    """A header's text as (constants, signatures): every ``#define MVN_NAME <integer>`` (the integer may stand in
+    parentheses; a ``MVN_*`` macro of any other shape is refused) as {"MVN_NAME": value}, and every prototype
+    ``<ret> mvn_name(<params>);`` as name -> (restype, [argtypes])."""
+    lines = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S).replace("\\\n", " ").split("\n")  # (no comments)
+    constants, signatures, code = {}, {}, []
+    for line in lines:
+        if not line.lstrip().startswith("#"):
+            code.append(line)
+            continue
+        words = line.strip()[1:].split(None, 2)
+        if words[:1] == ["define"] and len(words) > 1 and words[1].startswith("MVN_"):
+            value = words[2].strip() if len(words) > 2 and words[1].isidentifier() else ""  # (no macro with arguments)
+            if value.startswith("(") and value.endswith(")"):
+                value = value[1:-1]
+            try:
+                constants[words[1]] = int(value)
+            except ValueError:
+                raise NativeLibraryError(f"`{line.strip()}` is not an integer constant") from None
+    # (a statement runs from the last `;`, `{` or `}`: whatever stands in front of the name is the return type)
+    for ret, name, params in re.findall(r"(?<![^;{}])([^;{}()]*)\b(mvn_\w+)\s*\(([^()]*)\)\s*;", "\n".join(code)):
+        if name in signatures:
+            raise NativeLibraryError(f"{name} is declared twice")
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        signatures[name] = (_ctype(name, ret), [_ctype(name, p, i) for i, p in enumerate(params)])
+    return constants, signatures
+
+
+def _read_header_file():
+    try:
+        with open(HEADER_PATH, encoding="utf-8") as f:
+            return read_header(f.read())
+    except OSError as e:
+        raise NativeLibraryError(f"cannot read the C ABI's header {HEADER_PATH}: {e}") from e
+
+
+# SIGNATURES: name -> (restype, argtypes), one row per prototype of the header -- a new entry point needs no line here
+_CONSTANTS, SIGNATURES = _read_header_file()
+# MVN_OK and MVN_ERR_* under their own names, every other constant without the prefix: GEN_FOLD, BWD_FORM_BF16_CTX,
+# EMBED_FORM_TABLES, SAMPLE_MODEL, LOSS_MODEL, BLOCK_FORM_FUSED64, AUDIO_FORM_WINDOW, ABI_VERSION, ...
+globals().update((k if k == "MVN_OK" or k.startswith("MVN_ERR_") else k[len("MVN_"):], v)
+                 for k, v in _CONSTANTS.items())
+SAMPLING_RULES = {"reference": SAMPLE_REFERENCE, "model": SAMPLE_MODEL}  # noqa: F821
+LOSS_RULES = {"reference": LOSS_REFERENCE, "model": LOSS_MODEL}  # noqa: F821
+PIPE_VARIANTS = (GEN_PIPE, GEN_PIPE_F16, GEN_FOLD)  # noqa: F821  variants with a hand-off status word
 
 _lib: Optional[C.CDLL] = None
 
@@ -345,7 +208,7 @@ def lib() -> C.CDLL:
             raise NativeLibraryError(f"{LIB_PATH} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if handle.mvn_abi_version() != 2:
+    if handle.mvn_abi_version() != ABI_VERSION:  # noqa: F821
         raise NativeLibraryError("libmovenet_hip.so ABI version mismatch")
     _lib = handle
     return handle
@@ -360,9 +223,9 @@ def check(rc: int, what: str) -> int:
     if rc >= 0:
         return rc
     msg = f"{what}: {last_error()} (status {rc})"
-    if rc == MVN_ERR_TOO_SHORT:
+    if rc == MVN_ERR_TOO_SHORT:  # noqa: F821
         raise ValueError(last_error())  # movenet/wavenet.py:141-146
-    if rc in (MVN_ERR_BAD_DIMS, MVN_ERR_BAD_ARG, MVN_ERR_UNSUPPORTED):
+    if rc in (MVN_ERR_BAD_DIMS, MVN_ERR_BAD_ARG, MVN_ERR_UNSUPPORTED):  # noqa: F821
         raise ValueError(msg)
     raise RuntimeError(msg)
 
@@ -389,9 +252,6 @@ def truncation(top_k, top_p):
     if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0.0 < top_p <= 1.0:
         raise ValueError(f"top_p must lie in (0, 1] (1: off), got {top_p!r}")
     return int(top_k), float(top_p)
-
-
-AUDIO_FORM_CLIP, AUDIO_FORM_VAR, AUDIO_FORM_WINDOW = 0, 1, 2  # MVN_AUDIO_FORM_* of mvn_audio_frontend_emph
 
 
 def emphasis(value, name: str = "preemphasis") -> float:
@@ -458,7 +318,7 @@ def seq_sampling_array(batch: int, classes: int, temperature, top_k, top_p, seed
     for b, (t, k, p, s, r) in enumerate(zip(*cols)):
         arr[b] = SeqSampling(t, k, p, r, s & (2 ** 64 - 1))
     rc = lib().mvn_seq_sampling_check(arr, batch, int(classes))
-    if rc != MVN_OK:
+    if rc != MVN_OK:  # noqa: F821
         raise ValueError(last_error())
     return arr
 

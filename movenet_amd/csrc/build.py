@@ -12,15 +12,16 @@ import subprocess
 import sys
 from typing import List
 
+from .._native import HEADER_PATH  # include/movenet_hip.h: the binding reads the file this build compiles against
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
-ROOT = os.path.dirname(PKG)
 LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libmovenet_hip.so")
 STAMP = os.path.join(LIB_DIR, "libmovenet_hip.stamp")
 
 SOURCES = ["common.hip", "generate.hip", "generate_pipe.hip", "generate_pipe_h16.hip", "generate_fold.hip", "sequence.hip", "video.hip", "trainer.hip", "audio.hip", "video_frontend.hip", "blocks.hip", "score.hip", "features.hip", "metrics.hip"]
-HEADERS = ["common.h", "gen_common.h", "pipe_common.h", "gemm_family.h", "fused_bwd.h", "bwd_half64_body.inc", "fused_bwd_l.h", "bwd_layer64_body.inc", "fused_fwd.h", "fwd_layer64s_body.inc", "fused_fwd_bf3.h", "bf3.h", "fused_bf16.h", "global_cond.h", os.path.join(ROOT, "include", "movenet_hip.h")]
+HEADERS = ["common.h", "gen_common.h", "pipe_common.h", "gemm_family.h", "fused_bwd.h", "bwd_half64_body.inc", "fused_bwd_l.h", "bwd_layer64_body.inc", "fused_fwd.h", "fwd_layer64s_body.inc", "fused_fwd_bf3.h", "bf3.h", "fused_bf16.h", "global_cond.h", HEADER_PATH]
 FLAGS = [
     "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC",
     "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-Wno-unused-variable",
@@ -55,7 +56,7 @@ def _compile_and_link(out: str, defs: List[str], keep_temps: bool, verbose: bool
     from concurrent.futures import ThreadPoolExecutor
     objdir = os.path.join(LIB_DIR, "obj_" + os.path.basename(out).replace(".so", ""))
     os.makedirs(objdir, exist_ok=True)
-    base = [_hipcc()] + FLAGS + defs + ["-I", os.path.join(ROOT, "include"), "-I", HERE]
+    base = [_hipcc()] + FLAGS + defs + ["-I", os.path.dirname(HEADER_PATH), "-I", HERE]
     if keep_temps:
         base += ["-save-temps=obj", "-Rpass-analysis=kernel-resource-usage"]
 
