@@ -144,6 +144,12 @@ class TrainingConfig:
     dist_port: str = "8888"
 
     pretrained_model_path: Optional[Path] = None
+    # resuming.  resume_from: a checkpoint of this run to go on from -- weights, optimizer, scheduler,
+    # generators, epoch and batch position -- or "auto": <model_output_path>/checkpoints/last.ckpt if there is one, a
+    # fresh run if not.  checkpoint_every_n_steps N > 0: also rewrite last.ckpt after every N-th optimizer step (0: only
+    # at the end of an epoch).  Not reference fields: a JSON written without them loads with the defaults (off).
+    resume_from: Optional[str] = None
+    checkpoint_every_n_steps: int = 0
     model_output_path: Path = Path("models")
     tensorboard_dir: Path = Path("tensorboard_logs")
     log_samples_every: Optional[int] = None
@@ -244,6 +250,8 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--dist_port", type=str, default="8888")
     a("--pretrained_model_path", type=_opt_path, default=None)
     a("--pretrained_run_exp_name", type=lambda x: None if x is None or x == "" else x, default=None)
+    a("--resume_from", type=lambda x: None if x is None or x == "" else x, default=None)
+    a("--checkpoint_every_n_steps", type=int, default=0)
     a("--model_output_path", type=Path,
       default=Path("models") / datetime.now().strftime("%Y%m%d%H%M%S"))
     a("--training_logs_path", type=Path, default=Path("training_logs"))
@@ -284,5 +292,8 @@ def config_from_args(args) -> TrainingConfig:
                                if args.pretrained_model_path and args.pretrained_run_exp_name
                                else None),
         tensorboard_dir=args.training_logs_path,
+        # (getattr: an argument namespace built before the flags existed)
+        resume_from=getattr(args, "resume_from", None),
+        checkpoint_every_n_steps=int(getattr(args, "checkpoint_every_n_steps", 0) or 0),
         **kw,
     )

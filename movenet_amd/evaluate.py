@@ -40,11 +40,12 @@ def build_parser() -> argparse.ArgumentParser:
     a("--checkpoint", type=str, required=True)
     a("--wavs", type=str, required=True, help="every *.wav of this folder is evaluated")
     a("--ema", type=int, default=0, help="1: the averaged weights of a run with --ema_decay")
-    a("--input_channels", type=int, default=256)
-    a("--residual_channels", type=int, default=64)
-    a("--skip_channels", type=int, default=64)
-    a("--layer_size", type=int, default=10)
-    a("--stack_size", type=int, default=3)
+    # the five model flags: default, the checkpoint's hyper_parameters record; without one 256 / 64 / 64 / 10 / 3
+    a("--input_channels", type=int, default=None)
+    a("--residual_channels", type=int, default=None)
+    a("--skip_channels", type=int, default=None)
+    a("--layer_size", type=int, default=None)
+    a("--stack_size", type=int, default=None)
     a("--synthesize", type=int, default=0, help="1: also copy-synthesise each file and compare (mel checkpoint)")
     a("--label", type=str, default=None, help="one of the checkpoint's class names")
     a("--out", type=str, default=None, help="also write the lines to this file")

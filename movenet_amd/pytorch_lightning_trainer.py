@@ -28,7 +28,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from .checkpoint import preemphasis_record
+from . import checkpoint
 from .config import TrainingConfig, arg_parser, config_from_args
 from .dataset import get_dataloader, training_contexts
 from .optim import FlatAdamW, order_like_backward
@@ -368,7 +368,7 @@ class Trainer:
                  num_sanity_val_steps: int = 0, callbacks=None, track_grad_norm: int = 2,
                  limit_train_batches: Optional[int] = None, device: Optional[str] = None,
                  enable_checkpointing: bool = True, limit_val_batches: Optional[int] = None,
-                 precision=32, bf16_video: bool = False):
+                 precision=32, bf16_video: bool = False, checkpoint_every_n_steps: int = 0):
         # bf16_video: with precision="bf16", train a use_video model too -- the conditioned layers on bf16 operands
         # (WaveNet.bf16_context, which fit() sets and leaves set); ValueError with precision=32.
         # Lightning's precision switch: 32 (default) trains in exact fp32; "bf16" runs the layer stack's
@@ -376,6 +376,8 @@ class Trainer:
         # everywhere else -- master weights, optimizer, head and loss included.  fit() then SETS, and leaves set,
         # model.model.forward_precision = "bf16" and, on a model with class labels (--use_global), model.model.global_path
         # = "bias": the model keeps both after training (reset them for an fp32 use with video, which "bias" refuses)
+        # checkpoint_every_n_steps N > 0: after every N-th optimizer step checkpoints/last.ckpt is rewritten with the
+        # run's position inside the epoch (no epoch=... file); 0: checkpoints at the end of an epoch only.
         if precision in (16, "16", "16-mixed"):
             raise NotImplementedError("precision=16 (fp16 training) needs loss scaling, which movenet_amd "
                                       "does not implement; use precision='bf16' or 32")
@@ -397,6 +399,7 @@ class Trainer:
         self.epoch_seconds = []  # wall time of each epoch's training loop
         self.device = device
         self.checkpointing = enable_checkpointing
+        self.checkpoint_every_n_steps = max(0, int(checkpoint_every_n_steps or 0))
         self.callbacks = list(callbacks or [])
         self.current_epoch = 0
         self.rank = 0
@@ -404,7 +407,42 @@ class Trainer:
         self.global_step = 0
         self.optimizer = None  # what fit() steps (its averaged_parameters() / ema_state_dict() when --ema_decay is on)
 
-    def fit(self, model: Dance2Music) -> None:
+    def _hyper(self, model: "Dance2Music", world: int) -> dict:
+        return checkpoint.hyper_parameters(model.config, model.dataset_fp, self.precision, self.bf16_video, self.accum,
+                                           world)
+
+    def _checked_checkpoint(self, model: "Dance2Music", ckpt_path, world: int) -> dict:
+        """The checkpoint to resume from, read and checked against this run (``checkpoint.check_resumable``) with
+        nothing but the host: every refusal is a ValueError raised before the device is touched."""
+        obj = checkpoint.read_checkpoint(ckpt_path)
+        c = model.config
+        averaging = (float(getattr(c, "ema_decay", 0.0)) > 0) and c.optimizer in ("Adam", "AdamW")
+        checkpoint.check_resumable(obj, ckpt_path, self._hyper(model, world), self.max_epochs, averaging)
+        names = checkpoint.global_classes_of(obj)
+        if names != list(model.global_classes):
+            raise ValueError(f"{ckpt_path}: global_classes is {names}, but this run's training set has "
+                             f"{list(model.global_classes)}")
+        return obj
+
+    def _save_checkpoint(self, model: "Dance2Music", scheduler, world: int, epoch: int, next_epoch: int,
+                         batches_done: int, epoch_file: bool) -> None:
+        """Rank 0's checkpoint of this moment (``checkpoint.training_checkpoint``): ``checkpoints/last.ckpt``, and at the
+        end of an epoch (``epoch_file``) ``checkpoints/epoch=E-step=S.ckpt`` with the same content before it.  Both
+        through a temporary file and ``os.replace``."""
+        ck = self.root / "checkpoints"
+        ck.mkdir(parents=True, exist_ok=True)
+        obj = checkpoint.training_checkpoint(
+            model, self.optimizer, scheduler, epoch=epoch, global_step=self.global_step, next_epoch=next_epoch,
+            batches_done=batches_done, hyper=self._hyper(model, world), history_len=self.global_step)
+        if epoch_file:
+            checkpoint.write_checkpoint(obj, ck / f"epoch={epoch}-step={self.global_step}.ckpt")
+        checkpoint.write_checkpoint(obj, ck / "last.ckpt")
+
+    def fit(self, model: Dance2Music, ckpt_path=None) -> None:
+        """``ckpt_path``: a checkpoint this trainer wrote (``last.ckpt``, or an ``epoch=...`` file) -- the run goes on
+        from it: weights, optimizer moments and step counts, the weights' average, scheduler, the label-dropout and
+        torch CPU generators, ``global_step``, and the batch of the epoch it stopped before.  Every rank
+        reads the file itself.  ``history`` starts empty; its records' step numbers continue from ``global_step``."""
         if self.precision == "bf16":
             if model.config.use_video and not self.bf16_video:
                 raise ValueError("Trainer(precision='bf16') trains audio-only models: set use_video to False")
@@ -422,6 +460,7 @@ class Trainer:
                                                    model.config.dist_port)
         model.rank, model.world_size = rank, world
         self.rank = rank
+        resumed = None if ckpt_path is None else self._checked_checkpoint(model, ckpt_path, world)
         cap_torch_threads()  # the container's CPU share, not the visible cores (utils/host.py)
         dev = torch.device(self.device) if self.device else torch.device("cuda", local_rank)
         if dev.type != "cuda":
@@ -433,7 +472,22 @@ class Trainer:
         scheduler = opt_cfg.get("lr_scheduler", {}).get("scheduler")
         sync = FlatGradSync(model.model.parameters(), world)
         sync.broadcast_parameters(0)
-        if averaging and world > 1:
+        start_epoch = skip_batches = 0
+        if resumed is not None:
+            # the weights go INTO the storage the parameters already have (load_state_dict copies in place: with
+            # FlatAdamW that storage is optimizer.flat), then the moments, step counts and the average into theirs
+            model.model.load_state_dict(checkpoint._state_dict_of(resumed, ckpt_path, False), strict=True)
+            optimizer.load_state_dict(resumed["optimizer_states"][0])
+            if scheduler is not None:
+                scheduler.load_state_dict(resumed["lr_schedulers"][0])
+            where = resumed["resume"]
+            gen = getattr(model.model, "global_dropout_generator", None)
+            if gen is not None:
+                gen.set_state(where["global_dropout_generator"])
+            torch.set_rng_state(where["torch_rng"])
+            self.global_step = int(resumed["global_step"])
+            start_epoch, skip_batches = int(where["epoch"]), int(where["batches_done"])
+        elif averaging and world > 1:
             # the average starts at the parameters every rank now holds; from here each rank forms the same average from
             # the same reduced gradients, and nothing of it is ever exchanged
             with torch.no_grad():
@@ -457,7 +511,8 @@ class Trainer:
                         log_f.write(json.dumps(rec) + "\n")
                         log_f.flush()
 
-        for epoch in range(self.max_epochs):
+        saving = rank == 0 and self.root is not None and self.checkpointing
+        for epoch in range(start_epoch, self.max_epochs):
             model.current_epoch = self.current_epoch = epoch
             model.train()
             loader = model.train_dataloader()
@@ -465,7 +520,14 @@ class Trainer:
             n_batches = len(loader) if self.limit is None else min(len(loader), self.limit)
             optimizer.zero_grad(set_to_none=True)
             t0 = time.perf_counter()
-            for batch_idx, batch in enumerate(loader):
+            batches = enumerate(loader)
+            if skip_batches:
+                # a resumed epoch: the batches the saved run had consumed are drawn and dropped (the loaders key their
+                # draws on (seed, epoch, ...) and SyntheticLoader's crops are sequential within the epoch)
+                for _ in range(skip_batches):
+                    next(batches, None)
+                skip_batches = 0
+            for batch_idx, batch in batches:
                 if batch_idx >= n_batches:
                     break
                 out = model.training_step(batch, batch_idx)
@@ -506,6 +568,10 @@ class Trainer:
                     self.global_step += 1
                     flush_records()          # the PREVIOUS step's values: ready by now
                     pending.append(_DeferredRecord(rec))
+                    if self.checkpoint_every_n_steps and self.global_step % self.checkpoint_every_n_steps == 0:
+                        flush_records()  # history and metrics.jsonl hold every step the file's global_step counts
+                        if saving:
+                            self._save_checkpoint(model, scheduler, world, epoch, epoch, batch_idx + 1, False)
             flush_records()
             torch.cuda.synchronize(dev)
             epoch_s = time.perf_counter() - t0
@@ -543,25 +609,10 @@ class Trainer:
                 print(json.dumps({"epoch": epoch, "epoch_seconds": epoch_s,
                                   **{k: v for k, v in model.logged.items() if k.startswith("val")}}),
                       flush=True)
-                if self.root is not None and self.checkpointing:
-                    ck = self.root / "checkpoints"
-                    ck.mkdir(parents=True, exist_ok=True)
-                    # Lightning's layout: "state_dict" with the LightningModule's "model." prefix
-                    names = list(getattr(model, "global_classes", []) or [])  # class i of global_embedding <-> names[i]
-                    ema = ({"ema_state_dict": {f"model.{k}": v.detach().cpu()
-                                               for k, v in optimizer.ema_state_dict(model.model).items()},
-                            "ema_decay": optimizer.ema_decay, "ema_updates": optimizer.ema_updates}
-                           if averaging else {})  # (absent without --ema_decay)
-                    torch.save({"epoch": epoch, "global_step": self.global_step,
-                                **({"global_classes": names} if names else {}), **ema,
-                                # (--use_mel: what checkpoint.load_into rebuilds local_conv from; absent otherwise)
-                                **({"local_conditioning": dict(model.local_conditioning)}
-                                   if getattr(model, "use_mel", False) else {}),
-                                # (--preemphasis A > 0: what checkpoint.load_into sets model.preemphasis from)
-                                **preemphasis_record(model.model),
-                                "state_dict": {f"model.{k}": v.detach().cpu()
-                                               for k, v in model.model.state_dict().items()}},
-                               ck / f"epoch={epoch}-step={self.global_step}.ckpt")
+                if saving:
+                    # Lightning's layout: "state_dict" with the LightningModule's "model." prefix; the resumed run's
+                    # next epoch is epoch + 1, none of its batches consumed
+                    self._save_checkpoint(model, scheduler, world, epoch, epoch + 1, 0, True)
         if log_f:
             log_f.close()
 
@@ -571,6 +622,19 @@ def train_model(dataset: str, config: TrainingConfig, logger_name: Optional[str]
                 limit_train_batches: Optional[int] = None, precision=32) -> Trainer:
     # (bf16_video travels in the config: --bf16_video 1)
     model = Dance2Music(dataset, config)
+    pretrained = getattr(config, "pretrained_model_path", None)
+    if pretrained and getattr(config, "resume_from", None):
+        raise ValueError("--pretrained_model_path starts a new run from a file's weights, --resume_from continues a "
+                         "run: give one of them")
+    resume = checkpoint.resolve_resume(getattr(config, "resume_from", None), config.model_output_path)
+    if pretrained:
+        # fine-tuning, the reference's semantics (its trainer.py:240-262): the file's weights, then a fresh optimizer,
+        # a fresh scheduler and epoch 0
+        names = checkpoint.global_classes_of(checkpoint.read_checkpoint(pretrained))
+        if names != list(model.global_classes):
+            raise ValueError(f"{pretrained}: global_classes is {names}, but this run's training set has "
+                             f"{list(model.global_classes)}")
+        checkpoint.load_into(model.model, pretrained, strict=True)
     if logger_name == "wandb":
         raise NotImplementedError("wandb logging is a SaaS integration and out of scope "
                                   "(SURVEY.md section 2); metrics go to <model_output_path>/metrics.jsonl")
@@ -591,8 +655,10 @@ def train_model(dataset: str, config: TrainingConfig, logger_name: Optional[str]
         num_sanity_val_steps=0, callbacks=callbacks, track_grad_norm=2,
         limit_train_batches=(limit_train_batches if limit_train_batches is not None
                              else config.n_steps_per_epoch),
-        precision=precision, bf16_video=bool(getattr(config, "bf16_video", False)))
-    trainer.fit(model=model)
+        precision=precision, bf16_video=bool(getattr(config, "bf16_video", False)),
+        checkpoint_every_n_steps=int(getattr(config, "checkpoint_every_n_steps", 0) or 0))
+    # (a fresh run makes the call it always made)
+    trainer.fit(model=model, **({} if resume is None else {"ckpt_path": resume}))
     return trainer
 
 

@@ -1,8 +1,10 @@
 """Checkpoint -> WAV files, written while they are being generated.
 
-    python -m movenet_amd.synthesize --checkpoint run/checkpoints/last.ckpt --input_channels 256 \\
-        --residual_channels 64 --skip_channels 64 --layer_size 10 --stack_size 3 \\
+    python -m movenet_amd.synthesize --checkpoint run/checkpoints/last.ckpt \\
         --from_wavs clips/ --out synth/ --batch 16 --chunk 4000
+
+The model's shape comes from the checkpoint's ``hyper_parameters`` record; ``--input_channels``, ``--residual_channels``,
+``--skip_channels``, ``--layer_size`` and ``--stack_size`` are for files without one (defaults 256 / 64 / 64 / 10 / 3).
 
 Two sources, exactly one per call:
 
@@ -94,11 +96,12 @@ def build_parser() -> argparse.ArgumentParser:
     a = p.add_argument
     a("--checkpoint", type=str, required=True)
     a("--ema", type=int, default=0, help="1: the averaged weights of a run with --ema_decay")
-    a("--input_channels", type=int, default=256)
-    a("--residual_channels", type=int, default=64)
-    a("--skip_channels", type=int, default=64)
-    a("--layer_size", type=int, default=10)
-    a("--stack_size", type=int, default=3)
+    # the five model flags: default, the checkpoint's hyper_parameters record; without one 256 / 64 / 64 / 10 / 3
+    a("--input_channels", type=int, default=None)
+    a("--residual_channels", type=int, default=None)
+    a("--skip_channels", type=int, default=None)
+    a("--layer_size", type=int, default=None)
+    a("--stack_size", type=int, default=None)
     a("--from_wavs", type=str, default=None, help="copy-synthesis of every *.wav of this folder (mel checkpoint)")
     a("--seconds", type=float, default=None)
     a("--count", type=int, default=1)
@@ -120,13 +123,20 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def load_model(args, fail):
-    """The WaveNet of the model flags with the checkpoint's weights, on the CPU; ``local_conditioning`` and
-    ``global_classes`` come from the checkpoint's records.  ``fail(message)`` is called (and must not return) where the
+    """The WaveNet of the model flags -- one not given (None) is filled in, in ``args``, from the checkpoint's
+    ``hyper_parameters``, or without that record from the defaults 256 / 64 / 64 / 10 / 3 -- with the checkpoint's
+    weights, on the CPU; ``local_conditioning`` and ``global_classes`` come from the checkpoint's records.  ``fail(message)`` is called (and must not return) where the
     flags and the state dict's shapes disagree, or ``--preemphasis`` and the checkpoint's record do.  The model's
     ``preemphasis`` is the record's, or the flag's where it may stand.  Returns (model, local record or None, class names)."""
-    from .checkpoint import _local_record, _preemphasis_record, _read, _state_dict_of
+    from .checkpoint import (CLI_MODEL_DEFAULTS, _local_record, _preemphasis_record, _read, _state_dict_of,
+                             hyper_parameters_of)
     from .wavenet import WaveNet
     obj = _read(args.checkpoint)
+    # a model flag that was not given: the shape the checkpoint records (the trainer's hyper_parameters), else the default
+    recorded = hyper_parameters_of(obj)
+    for flag, default in CLI_MODEL_DEFAULTS.items():
+        if getattr(args, flag, None) is None:
+            setattr(args, flag, int(recorded.get(flag, default)))
     rec = _local_record(obj)
     names = list(obj.get("global_classes") or []) if isinstance(obj, dict) else []
     emph = _preemphasis_record(obj)
