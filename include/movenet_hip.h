@@ -1110,6 +1110,35 @@ int mvn_upsample_features_backward(const float *dctx, int dctx_ld, const float *
                                    float *dbias, float *dmel, int dmel_ld, float *scratch, size_t scratch_floats,
                                    void *stream);
 
+/* The frame up-sampler with a window of neighbouring frames (additive, ABI version unchanged): w is
+ * (channels, n_mels, taps) in nn.Conv1d's own layout, taps = 2 k + 1 for k frames of context on each side.  With
+ * F = frames, the number of frames GIVEN, and cl(i) = min(max(i, 0), F - 1):
+ *   proj[b, c, j] = bias[c] + sum_{d = -k..k} sum_m w[c, m, d + k] mel[b, m, cl(j + d)]               j = 0 .. F - 1
+ *   ctx[b, c, t]  = (1 - a) proj[b, c, j] + a proj[b, c, min(j + 1, F - 1)]       j = t / hop, a = (t mod hop) / hop
+ * Edge frames are replicated, not zero-filled (a log-mel of 0.0 is a loud frame, not silence), and the clamp is to the
+ * last frame of the tensor handed in, surplus frames included, as j1 above.  No element of a mel row at or beyond
+ * column F is read.  proj goes into scratch (the sizing call above); the rows are interpolated and stored as above, so
+ * ctx has the alignment rules of mvn_upsample_features.  taps == 1 gives that call's bits.
+ *
+ * The backward: dP[b, c, j] exactly as above, then
+ *   dbias[c]          += sum_{b, j} dP[b, c, j]
+ *   dw[c, m, d + k]   += sum_b sum_j dP[b, c, j] mel[b, m, cl(j + d)]
+ *   dmel[b, m, i]      = sum_d sum_{j : cl(j + d) = i} sum_c w[c, m, d + k] dP[b, c, j]
+ * An interior frame i collects j = i - d; frame 0 collects every j <= -d and frame F - 1 every j >= F - 1 - d, so the
+ * two edge frames sum several (j, d) pairs each, and with F <= k every tap of every frame clamps.  dmel is formed in
+ * gather form, one thread per word: fixed order, no atomics, the same bits on every call.  dw and dbias are
+ * ACCUMULATED INTO, dmel is written in full (its first F columns of each row), and each of the three may be NULL.
+ * MVN_ERR_BAD_ARG before any launch, with nothing written: everything the two calls above refuse (null pointers,
+ * sizes below 1, a row stride below its length, a misaligned ctx / ctx_ld, too few frames, a small scratch, the size
+ * limits), and taps even, below 1 or above 33.  batch == 0 is MVN_OK. */
+int mvn_upsample_features_win(const float *mel, int mel_ld, const float *w, const float *bias, int batch, int n_mels,
+                              int frames, int channels, int taps, int hop, int n_samples, float *ctx, int ctx_ld,
+                              float *scratch, size_t scratch_floats, void *stream);
+int mvn_upsample_features_win_backward(const float *dctx, int dctx_ld, const float *mel, int mel_ld, const float *w,
+                                       int batch, int n_mels, int frames, int channels, int taps, int hop,
+                                       int n_samples, float *dw, float *dbias, float *dmel, int dmel_ld,
+                                       float *scratch, size_t scratch_floats, void *stream);
+
 /* ---- Distance between two feature tensors (csrc/metrics.hip; additive, ABI version unchanged) ----
  * a, b (batch, n_mels, frames) fp32, contiguous, DEVICE, read only; first, count (batch) int32, DEVICE: sequence s
  * counts its frames [first[s], first[s] + count[s]).  With d = (double)a[s,m,f] - (double)b[s,m,f] over that span:

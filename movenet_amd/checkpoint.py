@@ -81,8 +81,14 @@ def _local_record(obj):
 def local_conditioning_of(path):
     """The ``"local_conditioning"`` record of a checkpoint trained with ``--use_mel 1`` -- ``local_channels``,
     ``local_hop`` and the mel settings its features were computed with (``mel_fft``, ``mel_fmin``, ``mel_fmax``,
-    ``audio_rate``) -- or None for a file without one."""
+    ``audio_rate``), and ``local_window`` where the run had ``--mel_window K > 0`` -- or None for a file without one."""
     return _local_record(_read(path))
+
+
+def local_window_of(rec) -> int:
+    """The ``local_window`` of a ``"local_conditioning"`` record: the key is written only by a run with ``--mel_window
+    K > 0``, so a record without it (every file written before the flag existed, and every K = 0 run) reads as 0."""
+    return int(rec.get("local_window", 0)) if isinstance(rec, dict) else 0
 
 
 def _preemphasis_record(obj) -> float:
@@ -115,7 +121,7 @@ def load_into(model: torch.nn.Module, path, strict: bool = True, ema: bool = Fal
         model.preemphasis = _preemphasis_record(obj)
     rec = _local_record(obj)
     if rec is not None and hasattr(model, "set_local_conditioning"):
-        model.set_local_conditioning(int(rec["local_channels"]), int(rec["local_hop"]))
+        model.set_local_conditioning(int(rec["local_channels"]), int(rec["local_hop"]), local_window_of(rec))
         model.local_conditioning = rec
     return model.load_state_dict(_state_dict_of(obj, path, ema), strict=strict)
 
@@ -254,10 +260,11 @@ def resolve_resume(value, output_path) -> Optional[Path]:
     return Path(value)
 
 
-def check_resumable(obj, path, run: dict, max_epochs: int, averaging: bool) -> None:
+def check_resumable(obj, path, run: dict, max_epochs: int, averaging: bool, local_window: int = 0) -> None:
     """ValueError -- naming the file and the field -- for a checkpoint that ``Trainer.fit(ckpt_path=path)`` must not
     continue: one without ``optimizer_states`` (a file of weights: ``--pretrained_model_path`` takes those), one whose
     ``hyper_parameters`` disagree with the run's (``run``, from ``hyper_parameters()``) in any of ``RESUME_FIELDS``, one
+    whose ``local_conditioning`` record holds another ``local_window`` than the run's ``--mel_window`` (absent: 0), one
     whose ``resume["epoch"]`` is not below ``max_epochs``, and -- with the weights' average on in the run -- one whose
     optimizer state holds no ``ema`` (``FlatAdamW.load_state_dict`` would start the average over without a word)."""
     if not isinstance(obj, dict) or not obj.get("optimizer_states"):
@@ -271,6 +278,10 @@ def check_resumable(obj, path, run: dict, max_epochs: int, averaging: bool) -> N
         if saved.get(field) != run[field]:
             raise ValueError(f"{path}: hyper_parameters[{field!r}] is {saved.get(field)!r}, but this run has "
                              f"{run[field]!r}: a resumed run continues the run that wrote the file")
+    saved_window = local_window_of(_local_record(obj))
+    if saved_window != int(local_window):
+        raise ValueError(f"{path}: local_conditioning['local_window'] is {saved_window}, but this run has "
+                         f"{int(local_window)} (--mel_window): a resumed run continues the run that wrote the file")
     if int(resume["epoch"]) >= int(max_epochs):
         raise ValueError(f"{path}: resume['epoch'] is {int(resume['epoch'])}, but this run ends after max_epochs = "
                          f"{int(max_epochs)}: nothing is left to train")

@@ -113,13 +113,15 @@ class TrainingConfig:
     # 4.5d): every batch's features are computed on the GPU from its class indices (ops.logmel: frames of mel_fft samples
     # mel_hop apart, an HTK filterbank of mel_bins triangles from mel_fmin to mel_fmax Hz at audio_rate; mel_fmax None:
     # audio_rate / 2) and go to forward() as local_features.  Not with use_video.  Not reference fields: a JSON written
-    # without them loads with the defaults (off).
+    # without them loads with the defaults (off).  mel_window K > 0: local_conv is a conv over 2 K + 1
+    # frames, K on each side, the edge frames repeated past the clip's ends; 0: the 1 x 1 conv.  Needs use_mel.
     use_mel: bool = False
     mel_bins: int = 80
     mel_fft: int = 1024
     mel_hop: int = 256
     mel_fmin: float = 0.0
     mel_fmax: Optional[float] = None
+    mel_window: int = 0
 
     # pre-emphasis of the training audio (WavFolderLoader(preemphasis=a)): the front end quantises
     # (vn[k] - a vn[k-1]) / (1 + a) of the normalised waveform, the checkpoint records a, and everything that turns the
@@ -228,6 +230,7 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--mel_hop", type=int, default=256)
     a("--mel_fmin", type=float, default=0.0)
     a("--mel_fmax", type=float, default=None)
+    a("--mel_window", type=int, default=0)
     a("--preemphasis", type=float, default=0.0)
     a("--n_epochs", type=int, default=10)
     a("--n_steps_per_epoch", type=int, default=None)
@@ -283,6 +286,11 @@ def config_from_args(args) -> TrainingConfig:
         "val_batch_subsample_frac dist_backend dist_port model_output_path log_samples_every"
     ).split()
     kw = {k: getattr(args, k) for k in copied}  # NB: gradient_clipping is not among them (Q11)
+    mel_window = int(getattr(args, "mel_window", 0) or 0)  # (getattr: a namespace built before the flag existed)
+    if mel_window < 0 or mel_window > 16:
+        raise ValueError(f"--mel_window must lie in [0, 16], got {mel_window}")
+    if mel_window and not kw["use_mel"]:
+        raise ValueError(f"--mel_window {mel_window} needs --use_mel 1: there are no frames to take a window of")
     return TrainingConfig(
         model_config=ModelConfig(
             input_channels=args.input_channels, residual_channels=args.residual_channels,
@@ -295,5 +303,6 @@ def config_from_args(args) -> TrainingConfig:
         # (getattr: an argument namespace built before the flags existed)
         resume_from=getattr(args, "resume_from", None),
         checkpoint_every_n_steps=int(getattr(args, "checkpoint_every_n_steps", 0) or 0),
+        mel_window=mel_window,
         **kw,
     )

@@ -8,6 +8,8 @@
 //   uf_project_kernel  bias + W mel at frame rate;  uf_interp_kernel  the interpolated rows, 16 bytes per store
 //   uf_dp_kernel       dP[b, c, j]: the weighted sum of the dctx columns that touch frame j (a wave per frame)
 //   uf_dw_kernel       dW += dP mel^T, dbias += sum dP (a wave per word);  uf_dmel_kernel  dmel = W^T dP
+//   uf_project_win_kernel, uf_dw_win_kernel, uf_dmel_win_kernel  the same three over a window of 2 k + 1 frames whose
+//                      ends repeat the edge frames; uf_interp_kernel and uf_dp_kernel serve both
 //
 // No atomics anywhere; every sum has one order, so two calls give the same bits.
 #include "common.h"
@@ -212,6 +214,78 @@ __global__ __launch_bounds__(kWave) void uf_dmel_kernel(const float *__restrict_
   dmel[((size_t)b * M + m) * dmel_ld + j] = acc;
 }
 
+// ---- the frame up-sampler with a window of neighbouring frames ---------------------------------------------
+// w is (C, M, taps), taps = 2 k + 1; frame j + d stands for frame cl(j + d) = min(max(j + d, 0), F - 1) of the F given.
+constexpr int kUfMaxTaps = 33;
+
+__device__ __forceinline__ int uf_cl(int i, int F) { return min(max(i, 0), F - 1); }
+
+// grid (ceil(F / 64), C, batch): proj[b, c, j] = bias[c] + sum_m sum_d W[c, m, d + k] mel[b, m, cl(j + d)].  A lane per
+// frame: the taps reads of a row are 64 consecutive words each (the clamped ends repeat one), the weights are
+// wave-uniform; taps = 1 is uf_project_kernel's sum, term by term.
+__global__ __launch_bounds__(kWave) void uf_project_win_kernel(const float *__restrict__ mel, int mel_ld,
+                                                               const float *__restrict__ w,
+                                                               const float *__restrict__ bias, int M, int F, int C,
+                                                               int taps, float *__restrict__ proj) {
+  const int j = blockIdx.x * kWave + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
+  if (j >= F) return;
+  const int k = taps >> 1;
+  const float *wr = w + (size_t)c * M * taps;
+  const float *mb = mel + (size_t)b * M * mel_ld;
+  float acc = bias[c];
+  for (int m = 0; m < M; ++m) {
+    const float *row = mb + (size_t)m * mel_ld;
+    const float *wm = wr + (size_t)m * taps;
+    for (int d = -k; d <= k; ++d) acc = fmaf(wm[d + k], row[uf_cl(j + d, F)], acc);
+  }
+  proj[((size_t)b * C + c) * F + j] = acc;
+}
+
+// grid (M taps + 1, C): a wave per word -- dW[c, m, d + k] for x = m taps + d + k < M taps, dbias[c] for x == M taps --
+// over the (b, j) pairs in order (uf_dw_kernel's order: taps = 1 gives its bits)
+__global__ __launch_bounds__(kWave) void uf_dw_win_kernel(const float *__restrict__ dP, const float *__restrict__ mel,
+                                                          int mel_ld, int B, int M, int F, int C, int taps,
+                                                          float *__restrict__ dw, float *__restrict__ dbias) {
+  const int x = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
+  const bool is_bias = x == M * taps;
+  if (is_bias ? dbias == nullptr : dw == nullptr) return;  // (workgroup-uniform)
+  const int m = is_bias ? 0 : x / taps, d = is_bias ? 0 : x - m * taps - (taps >> 1);
+  float acc = 0.f;
+  for (int b = 0; b < B; ++b) {
+    const float *dp = dP + ((size_t)b * C + c) * F;
+    const float *mr = mel + ((size_t)b * M + m) * mel_ld;
+    for (int j = lane; j < F; j += kWave) acc = is_bias ? acc + dp[j] : fmaf(dp[j], mr[uf_cl(j + d, F)], acc);
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) {
+    if (is_bias) dbias[c] += acc;
+    else dw[(size_t)c * M * taps + x] += acc;
+  }
+}
+
+// grid (ceil(F / 64), M, batch): dmel[b, m, i] = sum_c sum_d sum_{j : cl(j + d) = i} W[c, m, d + k] dP[b, c, j], a lane
+// per word (gather form).  The frames j with cl(j + d) = i are [lo, hi]: i - d alone for an interior i, every j <= -d
+// for i = 0 and every j >= F - 1 - d for i = F - 1 (both, i.e. every j, where F = 1), cut to [0, F - 1] -- at most
+// k + 1 of them, and none where i - d falls outside.  taps = 1 is uf_dmel_kernel's sum, term by term.
+__global__ __launch_bounds__(kWave) void uf_dmel_win_kernel(const float *__restrict__ dP, const float *__restrict__ w,
+                                                            int M, int F, int C, int taps, float *__restrict__ dmel,
+                                                            int dmel_ld) {
+  const int i = blockIdx.x * kWave + threadIdx.x, m = blockIdx.y, b = blockIdx.z;
+  if (i >= F) return;
+  const int k = taps >> 1;
+  float acc = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float *dp = dP + ((size_t)b * C + c) * F;
+    const float *wm = w + ((size_t)c * M + m) * taps;
+    for (int d = -k; d <= k; ++d) {
+      const int lo = i == 0 ? 0 : max(i - d, 0), hi = i == F - 1 ? F - 1 : min(i - d, F - 1);
+      const float wv = wm[d + k];
+      for (int j = lo; j <= hi; ++j) acc = fmaf(wv, dp[j], acc);
+    }
+  }
+  dmel[((size_t)b * M + m) * dmel_ld + i] = acc;
+}
+
 static bool lm_shape_ok(int batch, int T, int N, int hop) {
   return batch >= 0 && batch <= 65535 && T >= 1 && T <= kFeatMaxRow && (long long)batch * T <= kLmMaxSamples &&
          N >= kLmMinFft && N <= kLmMaxFft && (N & (N - 1)) == 0 && hop >= 1 && hop <= N;
@@ -328,6 +402,63 @@ int mvn_upsample_features_backward(const float *dctx, int dctx_ld, const float *
     hipLaunchKernelGGL(mvn::uf_dmel_kernel, dim3((frames + mvn::kWave - 1) / mvn::kWave, n_mels, batch),
                        dim3(mvn::kWave), 0, st, (const float *)scratch, w, n_mels, frames, channels, dmel, dmel_ld);
     rc = mvn::check_hip(hipGetLastError(), "upsample_features_backward (dmel)");
+  }
+  return rc;
+}
+
+int mvn_upsample_features_win(const float *mel, int mel_ld, const float *w, const float *bias, int batch, int n_mels,
+                              int frames, int channels, int taps, int hop, int n_samples, float *ctx, int ctx_ld,
+                              float *scratch, size_t scratch_floats, void *stream) {
+  const char *what = "mvn_upsample_features_win";
+  if (!mel || !w || !bias || !ctx) return mvn::uf_refuse(what, "bad argument (null pointer)");
+  if (taps < 1 || taps > mvn::kUfMaxTaps || (taps & 1) == 0)
+    return mvn::uf_refuse(what, "bad argument (taps must be odd, in [1, 33])");
+  int rc = mvn::uf_check(what, batch, n_mels, frames, channels, hop, n_samples, scratch, scratch_floats);
+  if (rc) return rc;
+  if (mel_ld < frames || ctx_ld < n_samples) return mvn::uf_refuse(what, "a row stride is below its row's length");
+  if ((ctx_ld & 3) != 0 || ((uintptr_t)ctx & 15u) != 0)
+    return mvn::uf_refuse(what, "ctx must be 16-byte aligned and ctx_ld a multiple of 4");
+  if (batch == 0) return MVN_OK;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mvn::uf_project_win_kernel, dim3((frames + mvn::kWave - 1) / mvn::kWave, channels, batch),
+                     dim3(mvn::kWave), 0, st, mel, mel_ld, w, bias, n_mels, frames, channels, taps, scratch);
+  rc = mvn::check_hip(hipGetLastError(), "upsample_features_win (project)");
+  if (rc) return rc;
+  const int per = 4 * mvn::kUfThreads;
+  hipLaunchKernelGGL(mvn::uf_interp_kernel, dim3((n_samples + per - 1) / per, channels, batch), dim3(mvn::kUfThreads), 0,
+                     st, (const float *)scratch, frames, channels, hop, n_samples, ctx, ctx_ld);
+  return mvn::check_hip(hipGetLastError(), "upsample_features_win (interpolate)");
+}
+
+int mvn_upsample_features_win_backward(const float *dctx, int dctx_ld, const float *mel, int mel_ld, const float *w,
+                                       int batch, int n_mels, int frames, int channels, int taps, int hop,
+                                       int n_samples, float *dw, float *dbias, float *dmel, int dmel_ld,
+                                       float *scratch, size_t scratch_floats, void *stream) {
+  const char *what = "mvn_upsample_features_win_backward";
+  if (!dctx || !mel || !w) return mvn::uf_refuse(what, "bad argument (null pointer)");
+  if (taps < 1 || taps > mvn::kUfMaxTaps || (taps & 1) == 0)
+    return mvn::uf_refuse(what, "bad argument (taps must be odd, in [1, 33])");
+  int rc = mvn::uf_check(what, batch, n_mels, frames, channels, hop, n_samples, scratch, scratch_floats);
+  if (rc) return rc;
+  if (mel_ld < frames || dctx_ld < n_samples || (dmel && dmel_ld < frames))
+    return mvn::uf_refuse(what, "a row stride is below its row's length");
+  if (batch == 0) return MVN_OK;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mvn::uf_dp_kernel, dim3((frames + mvn::kUfSegment - 1) / mvn::kUfSegment, channels, batch),
+                     dim3(mvn::kUfThreads), 0, st, dctx, dctx_ld, frames, channels, hop, n_samples, scratch);
+  rc = mvn::check_hip(hipGetLastError(), "upsample_features_win_backward (dP)");
+  if (rc) return rc;
+  if (dw || dbias) {
+    hipLaunchKernelGGL(mvn::uf_dw_win_kernel, dim3(n_mels * taps + 1, channels), dim3(mvn::kWave), 0, st,
+                       (const float *)scratch, mel, mel_ld, batch, n_mels, frames, channels, taps, dw, dbias);
+    rc = mvn::check_hip(hipGetLastError(), "upsample_features_win_backward (dW)");
+    if (rc) return rc;
+  }
+  if (dmel) {
+    hipLaunchKernelGGL(mvn::uf_dmel_win_kernel, dim3((frames + mvn::kWave - 1) / mvn::kWave, n_mels, batch),
+                       dim3(mvn::kWave), 0, st, (const float *)scratch, w, n_mels, frames, channels, taps, dmel,
+                       dmel_ld);
+    rc = mvn::check_hip(hipGetLastError(), "upsample_features_win_backward (dmel)");
   }
   return rc;
 }

@@ -706,14 +706,16 @@ def feature_distance(a: torch.Tensor, b: torch.Tensor, first=None, count=None, p
 
 
 class _UpsampleFeaturesFunction(torch.autograd.Function):
-    """feats (B, M, F), W (C, M), bias (C) -> context (B, C, T) through mvn_upsample_features."""
+    """feats (B, M, F), W (C, M, taps) -- the conv's own weight -- and bias (C) -> context (B, C, T): taps = 1 through
+    mvn_upsample_features, as ever; taps = 2 k + 1 > 1 through mvn_upsample_features_win."""
 
     @staticmethod
     def forward(ctx_, hop, T, feats, w, bias):
         lib = N.lib()
         dev = feats.device
+        taps = int(w.shape[2])
         mel = feats.detach().to(torch.float32).contiguous()
-        wf = w.detach().to(torch.float32).contiguous()
+        wf = (w[:, :, 0] if taps == 1 else w).detach().to(torch.float32).contiguous()
         bf = bias.detach().to(torch.float32).contiguous()
         B, M, F = mel.shape
         C = wf.shape[0]
@@ -722,10 +724,15 @@ class _UpsampleFeaturesFunction(torch.autograd.Function):
             buf = torch.empty((B, C, ld), dtype=torch.float32, device=dev)
             n = int(lib.mvn_upsample_features_scratch_floats(B, C, F))
             scratch = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
-            N.check(lib.mvn_upsample_features(mel.data_ptr(), mel.stride(1), wf.data_ptr(), bf.data_ptr(), B, M, F, C,
-                                              hop, T, buf.data_ptr(), ld, scratch.data_ptr(), n, _stream_ptr(dev)),
-                    "mvn_upsample_features")
-        ctx_.geom = (hop, T)
+            if taps == 1:
+                N.check(lib.mvn_upsample_features(mel.data_ptr(), mel.stride(1), wf.data_ptr(), bf.data_ptr(), B, M, F,
+                                                  C, hop, T, buf.data_ptr(), ld, scratch.data_ptr(), n,
+                                                  _stream_ptr(dev)), "mvn_upsample_features")
+            else:
+                N.check(lib.mvn_upsample_features_win(mel.data_ptr(), mel.stride(1), wf.data_ptr(), bf.data_ptr(), B, M,
+                                                      F, C, taps, hop, T, buf.data_ptr(), ld, scratch.data_ptr(), n,
+                                                      _stream_ptr(dev)), "mvn_upsample_features_win")
+        ctx_.geom = (hop, T, taps)
         ctx_.save_for_backward(mel, wf)
         return buf[:, :, :T]
 
@@ -733,7 +740,7 @@ class _UpsampleFeaturesFunction(torch.autograd.Function):
     def backward(ctx_, dout):
         lib = N.lib()
         mel, wf = ctx_.saved_tensors
-        hop, T = ctx_.geom
+        hop, T, taps = ctx_.geom
         B, M, F = mel.shape
         C = wf.shape[0]
         dev = mel.device
@@ -745,10 +752,17 @@ class _UpsampleFeaturesFunction(torch.autograd.Function):
             dmel = torch.empty_like(mel) if need_mel else None
             n = int(lib.mvn_upsample_features_scratch_floats(B, C, F))
             scratch = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
-            N.check(lib.mvn_upsample_features_backward(
-                dout.data_ptr(), dout.stride(1), mel.data_ptr(), mel.stride(1), wf.data_ptr(), B, M, F, C, hop, T,
-                dw.data_ptr(), db.data_ptr(), dmel.data_ptr() if need_mel else None, F, scratch.data_ptr(), n,
-                _stream_ptr(dev)), "mvn_upsample_features_backward")
+            if taps == 1:
+                N.check(lib.mvn_upsample_features_backward(
+                    dout.data_ptr(), dout.stride(1), mel.data_ptr(), mel.stride(1), wf.data_ptr(), B, M, F, C, hop, T,
+                    dw.data_ptr(), db.data_ptr(), dmel.data_ptr() if need_mel else None, F, scratch.data_ptr(), n,
+                    _stream_ptr(dev)), "mvn_upsample_features_backward")
+                dw = dw[:, :, None]  # (the conv's (C, M, 1))
+            else:
+                N.check(lib.mvn_upsample_features_win_backward(
+                    dout.data_ptr(), dout.stride(1), mel.data_ptr(), mel.stride(1), wf.data_ptr(), B, M, F, C, taps, hop,
+                    T, dw.data_ptr(), db.data_ptr(), dmel.data_ptr() if need_mel else None, F, scratch.data_ptr(), n,
+                    _stream_ptr(dev)), "mvn_upsample_features_win_backward")
         need = ctx_.needs_input_grad
         return None, None, dmel, dw if need[3] else None, db if need[4] else None
 
@@ -779,13 +793,14 @@ def check_local_features(model, local_features, batch: int, T: int) -> None:
 def upsample_features(model, feats: torch.Tensor, T: int) -> torch.Tensor:
     """``feats`` (B, local_channels, F) -> the (B, C, T) context of ``model.local_conv`` applied at frame rate and
     interpolated linearly between frames ``model.local_hop`` samples apart (mvn_upsample_features); differentiable in
-    ``feats`` and in the conv's weight and bias."""
+    ``feats`` and in the conv's weight and bias.  A conv of kernel size 2 k + 1 > 1 (``local_window = k``) sees k frames
+    on each side of a frame, the edge frames repeated past the ends of ``feats`` (mvn_upsample_features_win)."""
     check_local_features(model, feats, int(feats.shape[0]) if torch.is_tensor(feats) and feats.dim() == 3 else -1, T)
     _require_gpu(feats, "local_features")
     if int(T) < 1:
         raise ValueError(f"upsample_features: T must be at least 1, got {T}")
     conv = model.local_conv
-    return _UpsampleFeaturesFunction.apply(int(model.local_hop), int(T), feats, conv.weight[:, :, 0], conv.bias)
+    return _UpsampleFeaturesFunction.apply(int(model.local_hop), int(T), feats, conv.weight, conv.bias)
 
 
 _BIAS_WITH_VIDEO = "global_path 'bias' runs models without a video context"

@@ -51,6 +51,10 @@ class Dance2Music(nn.Module):
         if self.use_mel and config.use_video:
             raise ValueError("--use_mel 1 cannot be combined with --use_video 1: one local context at a time")
         local = {}
+        # --mel_window K: local_conv sees K frames on each side of a frame; 0: the 1 x 1 conv
+        self.mel_window = int(getattr(config, "mel_window", 0))  # (a config pickled before the field existed)
+        if self.mel_window and not self.use_mel:
+            raise ValueError(f"--mel_window {self.mel_window} needs --use_mel 1: there are no frames to take a window of")
         if self.use_mel:
             from .ops import mel_filterbank
             rate = int(getattr(config, "audio_rate", 16000))
@@ -62,6 +66,9 @@ class Dance2Music(nn.Module):
                                        "mel_fft": int(config.mel_fft), "mel_fmin": float(config.mel_fmin),
                                        "mel_fmax": fmax, "audio_rate": rate}
             local = {"local_channels": int(config.mel_bins), "local_hop": int(config.mel_hop)}
+            if self.mel_window:  # (the record carries the key only then: a K = 0 run writes the file it wrote before)
+                self.local_conditioning["local_window"] = self.mel_window
+                local["local_window"] = self.mel_window
         self.model = WaveNet(**asdict(config.model_config), global_classes=len(self.global_classes), **local)
         if self.use_mel:  # (what checkpoint.load_into leaves there: WaveNet.spectral_distance reads the mel settings)
             self.model.local_conditioning = dict(self.local_conditioning)
@@ -417,7 +424,8 @@ class Trainer:
         obj = checkpoint.read_checkpoint(ckpt_path)
         c = model.config
         averaging = (float(getattr(c, "ema_decay", 0.0)) > 0) and c.optimizer in ("Adam", "AdamW")
-        checkpoint.check_resumable(obj, ckpt_path, self._hyper(model, world), self.max_epochs, averaging)
+        checkpoint.check_resumable(obj, ckpt_path, self._hyper(model, world), self.max_epochs, averaging,
+                                   local_window=int(getattr(model, "mel_window", 0)))
         names = checkpoint.global_classes_of(obj)
         if names != list(model.global_classes):
             raise ValueError(f"{ckpt_path}: global_classes is {names}, but this run's training set has "

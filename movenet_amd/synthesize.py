@@ -129,7 +129,7 @@ def load_model(args, fail):
     flags and the state dict's shapes disagree, or ``--preemphasis`` and the checkpoint's record do.  The model's
     ``preemphasis`` is the record's, or the flag's where it may stand.  Returns (model, local record or None, class names)."""
     from .checkpoint import (CLI_MODEL_DEFAULTS, _local_record, _preemphasis_record, _read, _state_dict_of,
-                             hyper_parameters_of)
+                             hyper_parameters_of, local_window_of)
     from .wavenet import WaveNet
     obj = _read(args.checkpoint)
     # a model flag that was not given: the shape the checkpoint records (the trainer's hyper_parameters), else the default
@@ -152,7 +152,8 @@ def load_model(args, fail):
         sd = _state_dict_of(obj, args.checkpoint, bool(args.ema))
     except ValueError as e:
         fail(str(e))
-    local = {} if rec is None else {"local_channels": int(rec["local_channels"]), "local_hop": int(rec["local_hop"])}
+    local = {} if rec is None else {"local_channels": int(rec["local_channels"]), "local_hop": int(rec["local_hop"]),
+                                    "local_window": local_window_of(rec)}  # (a record without the key: 0)
     model = WaveNet(args.layer_size, args.stack_size, args.input_channels, args.residual_channels, args.skip_channels,
                     global_classes=len(names), **local)
     want = {k: tuple(v.shape) for k, v in model.state_dict().items()}

@@ -35,6 +35,7 @@ MAX_AUDIO_FRAMES = 160000
 MAX_VIDEO_FRAMES = 160
 VIDEO_KERNEL_SIZE = (1, 64, 64)
 UPSAMPLE_STRIDE = 10
+MAX_LOCAL_WINDOW = 16  # frames of context on each side of local_conv (33 taps: mvn_upsample_features_win's limit)
 
 
 def upsample_kernel_size_solver(in_size, out_size, stride=1, padding=0, output_padding=0, dilation=1):
@@ -77,7 +78,7 @@ class WaveNet(nn.Module):
     def __init__(self, layer_size: int, stack_size: int, input_channels: int,
                  residual_channels: int = 16, skip_channels: int = 16,
                  context_in_channels: int = 1, global_classes: int = 0, local_channels: int = 0,
-                 local_hop: int = 0):
+                 local_hop: int = 0, local_window: int = 0):
         """``global_classes`` (an extension behind the reference's arguments; 0, the default, is the reference's
         module to the bit): G > 0 registers ``global_embedding.weight`` (G, residual_channels) behind every other
         parameter and makes ``global_features`` a required input of ``forward`` / ``generate``.
@@ -86,7 +87,11 @@ class WaveNet(nn.Module):
         ``local_conv = nn.Conv1d(M, residual_channels, 1)`` behind every other parameter, ``global_embedding``
         included, and makes ``local_features`` -- (B, M, F) feature frames ``local_hop`` samples apart, e.g.
         ``ops.logmel`` -- a required input of ``forward`` / ``score`` / ``classify``, and ``generate_local_features`` one
-        of ``generate``."""
+        of ``generate``.
+
+        ``local_window`` (0, the default: the module above, same shapes, keys and RNG draws): k > 0 makes it
+        ``local_conv = nn.Conv1d(M, residual_channels, 2 k + 1)`` -- a frame's projection sees k frames on each side, the
+        edge frames repeated past the ends of ``local_features``.  At most ``MAX_LOCAL_WINDOW`` = 16."""
         super().__init__()
         if isinstance(global_classes, bool) or not isinstance(global_classes, int) or global_classes < 0:
             raise ValueError(f"global_classes must be an integer >= 0, got {global_classes!r}")
@@ -97,6 +102,7 @@ class WaveNet(nn.Module):
             raise ValueError("local_channels and local_hop go together: both above 0, or both 0 (off), got "
                              f"{local_channels} and {local_hop}")
         self.local_channels, self.local_hop = local_channels, local_hop
+        self.local_window = self._checked_local_window(local_window, local_channels)
         self.global_classes = global_classes
         self.layer_size = layer_size
         self.stack_size = stack_size
@@ -120,7 +126,7 @@ class WaveNet(nn.Module):
         if global_classes > 0:  # (registered last: the draws of every other parameter under a seed do not move)
             self.global_embedding = nn.Embedding(global_classes, C)
         if local_channels > 0:  # (behind everything else, for the same reason)
-            self.local_conv = nn.Conv1d(local_channels, C, 1)
+            self.local_conv = nn.Conv1d(local_channels, C, 2 * self.local_window + 1)
         # "auto" (default): global conditioning takes the fast path where it exists (C = K = 64, fp32, no video: one
         # bias vector per layer and sequence); "context": always the general path, the label as a constant context
         self._global_path = "auto"
@@ -140,18 +146,32 @@ class WaveNet(nn.Module):
         self._gen_top_k, self._gen_top_p = 0, 1.0
         self._loss_rule = "reference"
 
-    def set_local_conditioning(self, local_channels: int, local_hop: int) -> None:
-        """Give the model the ``local_conv`` of ``WaveNet(local_channels=..., local_hop=...)`` (what
+    @staticmethod
+    def _checked_local_window(local_window, local_channels) -> int:
+        if isinstance(local_window, bool) or not isinstance(local_window, int) or local_window < 0:
+            raise ValueError(f"local_window must be an integer >= 0, got {local_window!r}")
+        if local_window > MAX_LOCAL_WINDOW:
+            raise ValueError(f"local_window must be at most {MAX_LOCAL_WINDOW}, got {local_window}")
+        if local_window > 0 and local_channels <= 0:
+            raise ValueError(f"local_window = {local_window} needs local_channels: there is no local_conv to widen")
+        return local_window
+
+    def set_local_conditioning(self, local_channels: int, local_hop: int, local_window: int = 0) -> None:
+        """Give the model the ``local_conv`` of ``WaveNet(local_channels=..., local_hop=..., local_window=...)`` (what
         ``checkpoint.load_into`` does for a checkpoint that records one): a new ``nn.Conv1d`` behind every other
-        parameter, on their device, unless the model already has one of that width; ``local_hop`` is set either way."""
+        parameter, on their device, unless the model already has one of that width and window; ``local_hop`` is set
+        either way."""
         if local_channels < 1 or local_hop < 1:
             raise ValueError(f"local_channels and local_hop must be above 0, got {local_channels} and {local_hop}")
-        if int(getattr(self, "local_channels", 0)) != local_channels:
+        local_window = self._checked_local_window(local_window, local_channels)
+        if int(getattr(self, "local_channels", 0)) != local_channels or \
+                int(getattr(self, "local_window", 0)) != local_window:
             if hasattr(self, "local_conv"):
                 del self.local_conv
             ref = self.causal_conv.conv.weight
-            self.local_conv = nn.Conv1d(local_channels, self.residual_channels, 1).to(device=ref.device, dtype=ref.dtype)
-        self.local_channels, self.local_hop = int(local_channels), int(local_hop)
+            self.local_conv = nn.Conv1d(local_channels, self.residual_channels,
+                                        2 * local_window + 1).to(device=ref.device, dtype=ref.dtype)
+        self.local_channels, self.local_hop, self.local_window = int(local_channels), int(local_hop), local_window
 
     # ---- precision of generate() ----------------------------------------
     @property
