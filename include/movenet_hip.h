@@ -317,6 +317,32 @@ int mvn_generate_guided(const mvn_dims *dims, int variant, const float *packed, 
 int mvn_transpose_context(const float *ctx, int ctx_ld, int batch, int channels, int t_len,
                           float *context_tm, void *stream);
 
+/* A launch whose local conditioning arrives as a WINDOW of the time-major context (additive, ABI version unchanged;
+ * DESIGN.md section 4.1g).  The one general call: the parameters of mvn_generate_trunc, mvn_generate_seq and
+ * mvn_generate_guided together, and in place of context_tm
+ *   context_win  DEVICE (rows, ctx_len, C) fp32, time-major: columns [ctx_t0, ctx_t0 + ctx_len) of every row's context,
+ *                rows = batch (guided: 2 * batch, unconditional rows first), a row ctx_len * C floats from the next
+ *   ctx_t0, ctx_len  the first column the buffer holds and how many
+ *   per_seq      NULL: temperature, seed, top_k and top_p hold for every sequence (mvn_generate_trunc); a DEVICE array:
+ *                mvn_generate_seq's, and the four scalars are not read
+ *   guidance     NULL, or mvn_generate_guided's DEVICE scales; `batch` then counts PAIRS and per_seq is required
+ * Which context columns a launch over [t_begin, t_end) reads, by variant, as the kernels have it:
+ *   MVN_GEN_GENERIC, MVN_GEN_STREAM          column t in the step t it runs: exactly [t_begin, t_end)
+ *   MVN_GEN_PIPE, MVN_GEN_PIPE_F16, MVN_GEN_FOLD  column t_begin in the prologue, column t + 1 during step t while
+ *                                            t + 1 < t_end (the look-ahead stops at the launch's end): exactly
+ *                                            [t_begin, t_end)
+ * and no element of context_win outside those columns is read, whatever it holds.  With ctx_t0 = 0, ctx_len = n_total
+ * and the whole context_tm the call is the matching one of the three to the bit.
+ * MVN_ERR_BAD_ARG with a mvn_last_error() text that names both column ranges: context_win NULL, ctx_len < 1,
+ * ctx_t0 < 0, or [t_begin, t_end) not inside [ctx_t0, ctx_t0 + ctx_len) (an empty launch lies inside any window).
+ * Otherwise everything mvn_generate_guided (where guidance is given) and then mvn_generate_seq / mvn_generate_trunc
+ * refuse, in their order.  Every refusal comes before any launch and before any buffer is touched. */
+int mvn_generate_windowed(const mvn_dims *dims, int variant, const float *packed, float *state, int32_t *samples,
+                          int batch, int sample_stride, int n_total, int n_given, int t_begin, int t_end,
+                          float temperature, uint64_t seed, int top_k, float top_p, const mvn_seq_sampling *per_seq,
+                          const float *guidance, float *logits_out, int32_t *choices_out, int logits_t0,
+                          const float *context_win, int ctx_t0, int ctx_len, int sampling, void *stream);
+
 /* ------------------------------------------------------------------------
  * Full-sequence forward (replaces movenet/wavenet.py:166-191: causal conv ->
  * L gated residual layers -> sum of skips -> dense head -> [drop last] ->
@@ -1138,6 +1164,36 @@ int mvn_upsample_features_win_backward(const float *dctx, int dctx_ld, const flo
                                        int batch, int n_mels, int frames, int channels, int taps, int hop,
                                        int n_samples, float *dw, float *dbias, float *dmel, int dmel_ld,
                                        float *scratch, size_t scratch_floats, void *stream);
+
+/* The frame-rate half of mvn_upsample_features_win with its result kept, and one window of the generators' time-major
+ * context formed from it (additive, ABI version unchanged).
+ *
+ * mvn_project_features: mel (batch, n_mels, frames), w (channels, n_mels, taps), bias (channels) -> proj (batch,
+ * channels, proj_ld), the first `frames` columns of a row written: the bits mvn_upsample_features_win leaves in its
+ * scratch for the same inputs (the same kernel through the same launcher, edge frames clamped to the `frames` given).
+ * MVN_ERR_BAD_ARG before any launch: what that call refuses of these arguments (null pointers, taps, sizes below 1,
+ * batch / n_mels / channels above 65535, frames above 2^30, mel_ld or proj_ld below frames).  batch == 0 is MVN_OK.
+ *
+ * mvn_context_window: win (rows, n, channels) time-major, columns [t0, t0 + n) of every row.  With F = frames,
+ * j = t / hop, a = (t mod hop) / hop, p = proj[r mod proj_rows] (proj is (proj_rows, channels, proj_ld)):
+ *   win[r, t - t0, c] = ((1 - a) p[c, j] + a p[c, min(j + 1, F - 1)])  [+ glob[r, c]]         t = t0 .. t0 + n - 1
+ *   proj == NULL   win[r, t - t0, c] = glob[r, c]: the label-only window, the same for every t0
+ *   glob == NULL   no label; glob is (rows, channels), zeros in the unconditional rows of a guided pair
+ *   proj_rows      the two rows of a guided pair share one projection: rows = 2 * proj_rows
+ * The contract is bit equality with columns [t0, t0 + n) of mvn_upsample_features_win over any n_samples >= t0 + n
+ * followed by mvn_transpose_context and mvn_context_add_global: a = (float)(t mod hop) * (1.0f / (float)hop), the word
+ * is fmaf(a, p[c, j1], (1.0f - a) * p[c, j]) as in that call's interpolation, and the label's vector is added last.
+ * t0 need not be a multiple of hop or of 4.  A thread stores four channels at once (16 bytes) where channels is a
+ * multiple of 4 and win 16-byte aligned, one otherwise; fixed order, no atomics; nothing outside win's rows * n *
+ * channels floats is written.
+ * MVN_ERR_BAD_ARG before any launch, with nothing written: win NULL; proj and glob both NULL; rows < 0, channels or
+ * n below 1; t0 < 0; rows or channels above 65535; t0 + n above 2^30; with proj: proj_rows, frames or hop below 1,
+ * proj_ld below frames, frames above 2^30, hop above 2^24, frames below (t0 + n - 1) / hop + 1 (the text names the
+ * columns).  rows == 0 is MVN_OK. */
+int mvn_project_features(const float *mel, int mel_ld, const float *w, const float *bias, int batch, int n_mels,
+                         int frames, int channels, int taps, float *proj, int proj_ld, void *stream);
+int mvn_context_window(const float *proj, int proj_ld, int proj_rows, int frames, const float *glob, int rows,
+                       int channels, int hop, int t0, int n, float *win, void *stream);
 
 /* ---- Distance between two feature tensors (csrc/metrics.hip; additive, ABI version unchanged) ----
  * a, b (batch, n_mels, frames) fp32, contiguous, DEVICE, read only; first, count (batch) int32, DEVICE: sequence s

@@ -109,9 +109,10 @@ _HOST_POINTEES = {"mvn_dims": Dims, "mvn_params": Params, "mvn_param_grads": Par
                   "mvn_block_tensor": BlockTensor, "mvn_block_gated_params": BlockGatedParams,
                   "mvn_block_gated_grads": BlockGatedParams, "mvn_seq_sampling": SeqSampling,
                   "size_t": C.c_size_t}  # (mvn_adamw_step's skip_ranges)
-# The exceptions to that rule, by (function, parameter name): these two take a DEVICE array of mvn_seq_sampling
+# The exceptions to that rule, by (function, parameter name): these three take a DEVICE array of mvn_seq_sampling
 # (only mvn_seq_sampling_check takes the host array).
-_OVERRIDES = {("mvn_generate_seq", "per_seq"): C.c_void_p, ("mvn_generate_guided", "per_seq"): C.c_void_p}
+_OVERRIDES = {("mvn_generate_seq", "per_seq"): C.c_void_p, ("mvn_generate_guided", "per_seq"): C.c_void_p,
+              ("mvn_generate_windowed", "per_seq"): C.c_void_p}
 
 
 def _ctype(function: str, decl: str, position: Optional[int] = None):

@@ -10,6 +10,9 @@
 //   uf_dw_kernel       dW += dP mel^T, dbias += sum dP (a wave per word);  uf_dmel_kernel  dmel = W^T dP
 //   uf_project_win_kernel, uf_dw_win_kernel, uf_dmel_win_kernel  the same three over a window of 2 k + 1 frames whose
 //                      ends repeat the edge frames; uf_interp_kernel and uf_dp_kernel serve both
+//   uf_window_kernel   columns [t0, t0 + n) of the generators' TIME-major context, straight from frame-rate rows and /
+//                      or the label's vector: uf_interp_kernel's expression, then the vector, 16 bytes
+//                      per store along the channels
 //
 // No atomics anywhere; every sum has one order, so two calls give the same bits.
 #include "common.h"
@@ -220,13 +223,14 @@ constexpr int kUfMaxTaps = 33;
 
 __device__ __forceinline__ int uf_cl(int i, int F) { return min(max(i, 0), F - 1); }
 
-// grid (ceil(F / 64), C, batch): proj[b, c, j] = bias[c] + sum_m sum_d W[c, m, d + k] mel[b, m, cl(j + d)].  A lane per
+// grid (ceil(F / 64), C, batch): proj[b, c, j] = bias[c] + sum_m sum_d W[c, m, d + k] mel[b, m, cl(j + d)], rows
+// proj_ld words apart (F in the up-sampler's scratch).  A lane per
 // frame: the taps reads of a row are 64 consecutive words each (the clamped ends repeat one), the weights are
 // wave-uniform; taps = 1 is uf_project_kernel's sum, term by term.
 __global__ __launch_bounds__(kWave) void uf_project_win_kernel(const float *__restrict__ mel, int mel_ld,
                                                                const float *__restrict__ w,
                                                                const float *__restrict__ bias, int M, int F, int C,
-                                                               int taps, float *__restrict__ proj) {
+                                                               int taps, float *__restrict__ proj, int proj_ld) {
   const int j = blockIdx.x * kWave + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
   if (j >= F) return;
   const int k = taps >> 1;
@@ -238,7 +242,7 @@ __global__ __launch_bounds__(kWave) void uf_project_win_kernel(const float *__re
     const float *wm = wr + (size_t)m * taps;
     for (int d = -k; d <= k; ++d) acc = fmaf(wm[d + k], row[uf_cl(j + d, F)], acc);
   }
-  proj[((size_t)b * C + c) * F + j] = acc;
+  proj[((size_t)b * C + c) * proj_ld + j] = acc;
 }
 
 // grid (M taps + 1, C): a wave per word -- dW[c, m, d + k] for x = m taps + d + k < M taps, dbias[c] for x == M taps --
@@ -284,6 +288,55 @@ __global__ __launch_bounds__(kWave) void uf_dmel_win_kernel(const float *__restr
     }
   }
   dmel[((size_t)b * M + m) * dmel_ld + i] = acc;
+}
+
+// ---- one window of the generators' time-major context -------------------------------------------------
+// win (rows, n, C): win[r, t - t0, c] = uf_at(proj[r mod proj_rows, c, :], t) [+ glob[r, c]] for t in [t0, t0 + n) --
+// the word uf_interp_kernel stores at (c, t), moved by transpose_ctx_kernel and then summed with the label's vector by
+// context_add_global_kernel (row[i] + v); proj == nullptr: glob[r, c] itself (that kernel's fill).
+// grid (ceil(n / tt), rows), tt columns per workgroup; a thread forms V consecutive channels of one column and stores
+// them at once (V = 4: 16 bytes, a wave's stores back to back along c and then t).
+constexpr int kUwPerGroup = 1024;  // stores per workgroup (four per thread)
+
+template <int V>
+__global__ __launch_bounds__(kUfThreads) void uf_window_kernel(const float *__restrict__ proj, int proj_ld,
+                                                               int proj_rows, int F, const float *__restrict__ glob,
+                                                               int C, int hop, int t0, int n, int tt,
+                                                               float *__restrict__ win) {
+  const int r = blockIdx.y, cv = C / V;
+  const int tl0 = blockIdx.x * tt, cols = min(tt, n - tl0);
+  const float *rows = proj ? proj + (size_t)(r % proj_rows) * C * proj_ld : nullptr;
+  const float *gv = glob ? glob + (size_t)r * C : nullptr;
+  float *out = win + ((size_t)r * n + tl0) * C;
+  const float rhop = 1.0f / (float)hop;
+  for (int e = threadIdx.x; e < cols * cv; e += kUfThreads) {
+    const int tl = e / cv, c = (e - tl * cv) * V;
+    const long long t = (long long)t0 + tl0 + tl;
+    float v[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      if (rows) {
+        v[i] = uf_at(rows + (size_t)(c + i) * proj_ld, F, hop, rhop, t);
+        if (gv) v[i] = v[i] + gv[c + i];
+      } else {
+        v[i] = gv[c + i];
+      }
+    }
+    float *o = out + (size_t)tl * C + c;
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4 *>(o) = float4{v[0], v[1], v[2], v[3]};
+    } else {
+      o[0] = v[0];
+    }
+  }
+}
+
+// the frame-rate product of the windowed up-sampler, for its scratch or for a caller's tensor
+static int uf_launch_project(const char *stage, const float *mel, int mel_ld, const float *w, const float *bias,
+                             int batch, int M, int F, int C, int taps, float *proj, int proj_ld, hipStream_t st) {
+  hipLaunchKernelGGL(uf_project_win_kernel, dim3((F + kWave - 1) / kWave, C, batch), dim3(kWave), 0, st, mel, mel_ld, w,
+                     bias, M, F, C, taps, proj, proj_ld);
+  return check_hip(hipGetLastError(), stage);
 }
 
 static bool lm_shape_ok(int batch, int T, int N, int hop) {
@@ -420,9 +473,8 @@ int mvn_upsample_features_win(const float *mel, int mel_ld, const float *w, cons
     return mvn::uf_refuse(what, "ctx must be 16-byte aligned and ctx_ld a multiple of 4");
   if (batch == 0) return MVN_OK;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(mvn::uf_project_win_kernel, dim3((frames + mvn::kWave - 1) / mvn::kWave, channels, batch),
-                     dim3(mvn::kWave), 0, st, mel, mel_ld, w, bias, n_mels, frames, channels, taps, scratch);
-  rc = mvn::check_hip(hipGetLastError(), "upsample_features_win (project)");
+  rc = mvn::uf_launch_project("upsample_features_win (project)", mel, mel_ld, w, bias, batch, n_mels, frames, channels,
+                              taps, scratch, frames, st);
   if (rc) return rc;
   const int per = 4 * mvn::kUfThreads;
   hipLaunchKernelGGL(mvn::uf_interp_kernel, dim3((n_samples + per - 1) / per, channels, batch), dim3(mvn::kUfThreads), 0,
@@ -461,6 +513,59 @@ int mvn_upsample_features_win_backward(const float *dctx, int dctx_ld, const flo
     rc = mvn::check_hip(hipGetLastError(), "upsample_features_win_backward (dmel)");
   }
   return rc;
+}
+
+int mvn_project_features(const float *mel, int mel_ld, const float *w, const float *bias, int batch, int n_mels,
+                         int frames, int channels, int taps, float *proj, int proj_ld, void *stream) {
+  const char *what = "mvn_project_features";
+  if (!mel || !w || !bias || !proj) return mvn::uf_refuse(what, "bad argument (null pointer)");
+  if (taps < 1 || taps > mvn::kUfMaxTaps || (taps & 1) == 0)
+    return mvn::uf_refuse(what, "bad argument (taps must be odd, in [1, 33])");
+  // (the up-sampler's size checks: no hop and no samples here, and proj stands where its scratch does)
+  int rc = mvn::uf_check(what, batch, n_mels, frames, channels, 1, 1, proj,
+                         (size_t)(batch > 0 ? batch : 0) * (channels > 0 ? channels : 0) * (frames > 0 ? frames : 0));
+  if (rc) return rc;
+  if (mel_ld < frames || proj_ld < frames) return mvn::uf_refuse(what, "a row stride is below its row's length");
+  if (batch == 0) return MVN_OK;
+  return mvn::uf_launch_project("project_features", mel, mel_ld, w, bias, batch, n_mels, frames, channels, taps, proj,
+                                proj_ld, (hipStream_t)stream);
+}
+
+int mvn_context_window(const float *proj, int proj_ld, int proj_rows, int frames, const float *glob, int rows,
+                       int channels, int hop, int t0, int n, float *win, void *stream) {
+  const char *what = "mvn_context_window";
+  if (!win) return mvn::uf_refuse(what, "bad argument (win is NULL)");
+  if (!proj && !glob) return mvn::uf_refuse(what, "bad argument (proj and glob are both NULL: nothing to write)");
+  if (rows < 0 || rows > 65535 || channels < 1 || channels > 65535 || n < 1)
+    return mvn::uf_refuse(what, "bad argument (a size below 1, or rows / channels above 65535)");
+  if (t0 < 0) return mvn::uf_refuse(what, "bad argument (t0 is negative)");
+  if (n > mvn::kFeatMaxRow || (long long)t0 + n > mvn::kFeatMaxRow)
+    return mvn::uf_refuse(what, "bad argument (n, or t0 + n, above 2^30)");
+  if (proj) {
+    if (proj_rows < 1 || frames < 1 || hop < 1 || proj_ld < frames)
+      return mvn::uf_refuse(what, "bad argument (proj_rows, frames or hop below 1, or proj_ld below frames)");
+    if (frames > mvn::kFeatMaxRow || hop > mvn::kFeatMaxHop)
+      return mvn::uf_refuse(what, "bad argument (frames above 2^30, or hop above 2^24)");
+    if ((long long)frames < ((long long)t0 + n - 1) / hop + 1) {
+      mvn::set_error("%s: too few frames for columns [%d, %lld): %d given at hop %d", what, t0, (long long)t0 + n, frames,
+                     hop);
+      return MVN_ERR_BAD_ARG;
+    }
+  }
+  if (rows == 0) return MVN_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = (channels & 3) == 0 && ((uintptr_t)win & 15u) == 0;
+  const int cv = vec ? channels / 4 : channels;
+  const int tt = cv >= mvn::kUwPerGroup ? 1 : mvn::kUwPerGroup / cv;
+  const dim3 grid((unsigned)((n + tt - 1) / tt), (unsigned)rows);
+  if (!proj) proj_ld = proj_rows = frames = hop = 1;  // (not read)
+  if (vec)
+    hipLaunchKernelGGL(mvn::uf_window_kernel<4>, grid, dim3(mvn::kUfThreads), 0, st, proj, proj_ld, proj_rows, frames, glob,
+                       channels, hop, t0, n, tt, win);
+  else
+    hipLaunchKernelGGL(mvn::uf_window_kernel<1>, grid, dim3(mvn::kUfThreads), 0, st, proj, proj_ld, proj_rows, frames, glob,
+                       channels, hop, t0, n, tt, win);
+  return mvn::check_hip(hipGetLastError(), "mvn_context_window");
 }
 
 }  // extern "C"

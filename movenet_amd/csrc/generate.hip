@@ -1136,13 +1136,15 @@ int mvn_seq_sampling_check(mvn_seq_sampling *host, int batch, int classes) {
 }
 
 // The one host driver of every mvn_generate* entry point: `per_seq` NULL (the four scalars hold for every sequence,
-// row = its index) or the checked device array of mvn_generate_seq (the scalars are then not read).
+// row = its index) or the checked device array of mvn_generate_seq (the scalars are then not read).  `context_tm` holds
+// the columns [ctx_t0, ctx_t0 + ctx_len) of every row, ctx_len C floats apart (the whole context: 0 and n_total); only
+// mvn_generate_windowed passes anything else, and it has checked that the launch's columns lie inside.
 static int generate_driver(const mvn_dims *dims, int variant, const float *packed, float *state,
                            int32_t *samples, int batch, int sample_stride, int n_total, int n_given,
                            int t_begin, int t_end, float temperature, uint64_t seed, float *logits_out,
                            int32_t *choices_out, int logits_t0, const float *context_tm, int sampling,
                            int top_k, float top_p, const mvn_seq_sampling *per_seq, const float *guidance,
-                           void *stream);
+                           int ctx_t0, int ctx_len, void *stream);
 
 int mvn_generate_trunc(const mvn_dims *dims, int variant, const float *packed, float *state,
                        int32_t *samples, int batch, int sample_stride, int n_total, int n_given,
@@ -1151,7 +1153,7 @@ int mvn_generate_trunc(const mvn_dims *dims, int variant, const float *packed, f
                        int top_k, float top_p, void *stream) {
   return generate_driver(dims, variant, packed, state, samples, batch, sample_stride, n_total, n_given, t_begin,
                          t_end, temperature, seed, logits_out, choices_out, logits_t0, context_tm, sampling, top_k,
-                         top_p, nullptr, nullptr, stream);
+                         top_p, nullptr, nullptr, 0, n_total, stream);
 }
 
 int mvn_generate_seq(const mvn_dims *dims, int variant, const float *packed, float *state,
@@ -1164,7 +1166,7 @@ int mvn_generate_seq(const mvn_dims *dims, int variant, const float *packed, flo
   }
   return generate_driver(dims, variant, packed, state, samples, batch, sample_stride, n_total, n_given, t_begin,
                          t_end, 0.f, 0, logits_out, choices_out, logits_t0, context_tm, sampling, 0, 1.0f, per_seq,
-                         nullptr, stream);
+                         nullptr, 0, n_total, stream);
 }
 
 int mvn_gen_guided_max_pairs(const mvn_dims *dims, int variant) {
@@ -1177,11 +1179,9 @@ int mvn_gen_guided_max_pairs(const mvn_dims *dims, int variant) {
   return v->stages ? v->launch_pipelines(dims, 1 << 20) : 0x3FFFFFFF;
 }
 
-int mvn_generate_guided(const mvn_dims *dims, int variant, const float *packed, float *state,
-                        int32_t *samples, int pairs, int sample_stride, int n_total, int n_given,
-                        int t_begin, int t_end, const mvn_seq_sampling *per_seq, const float *guidance,
-                        float *logits_out, int32_t *choices_out, int logits_t0, const float *context_tm,
-                        int sampling, void *stream) {
+// what a guided launch refuses before the driver's own checks; 0: fine
+static int guided_check(const mvn_dims *dims, int variant, int pairs, const mvn_seq_sampling *per_seq,
+                        const float *guidance) {
   if (!per_seq || !guidance || pairs < 1) {
     mvn::set_error("mvn_generate_guided: bad argument (per_seq %s, guidance %s, pairs %d)", per_seq ? "given" : "is NULL",
                    guidance ? "given" : "is NULL", pairs);
@@ -1200,9 +1200,48 @@ int mvn_generate_guided(const mvn_dims *dims, int variant, const float *packed, 
                    "(%d asked for)", v ? v->name : "unknown", limit, pairs);
     return MVN_ERR_UNSUPPORTED;
   }
+  return MVN_OK;
+}
+
+int mvn_generate_guided(const mvn_dims *dims, int variant, const float *packed, float *state,
+                        int32_t *samples, int pairs, int sample_stride, int n_total, int n_given,
+                        int t_begin, int t_end, const mvn_seq_sampling *per_seq, const float *guidance,
+                        float *logits_out, int32_t *choices_out, int logits_t0, const float *context_tm,
+                        int sampling, void *stream) {
+  const int rc = guided_check(dims, variant, pairs, per_seq, guidance);
+  if (rc) return rc;
   return generate_driver(dims, variant, packed, state, samples, 2 * pairs, sample_stride, n_total, n_given, t_begin,
                          t_end, 0.f, 0, logits_out, choices_out, logits_t0, context_tm, sampling, 0, 1.0f, per_seq,
-                         guidance, stream);
+                         guidance, 0, n_total, stream);
+}
+
+int mvn_generate_windowed(const mvn_dims *dims, int variant, const float *packed, float *state, int32_t *samples,
+                          int batch, int sample_stride, int n_total, int n_given, int t_begin, int t_end,
+                          float temperature, uint64_t seed, int top_k, float top_p, const mvn_seq_sampling *per_seq,
+                          const float *guidance, float *logits_out, int32_t *choices_out, int logits_t0,
+                          const float *context_win, int ctx_t0, int ctx_len, int sampling, void *stream) {
+  // (an empty launch reads no column; long long: ctx_t0 + ctx_len may pass 2^31)
+  if (!context_win || ctx_len < 1 || ctx_t0 < 0 ||
+      (t_begin < t_end && (t_begin < ctx_t0 || (long long)t_end > (long long)ctx_t0 + ctx_len))) {
+    mvn::set_error("mvn_generate_windowed: bad argument (context_win %s holds columns [%d, %lld), the launch reads "
+                   "columns [%d, %d))", context_win ? "given," : "is NULL,", ctx_t0, (long long)ctx_t0 + ctx_len, t_begin,
+                   t_end);
+    return MVN_ERR_BAD_ARG;
+  }
+  if (guidance) {
+    const int rc = guided_check(dims, variant, batch, per_seq, guidance);
+    if (rc) return rc;
+    return generate_driver(dims, variant, packed, state, samples, 2 * batch, sample_stride, n_total, n_given, t_begin,
+                           t_end, 0.f, 0, logits_out, choices_out, logits_t0, context_win, sampling, 0, 1.0f, per_seq,
+                           guidance, ctx_t0, ctx_len, stream);
+  }
+  if (per_seq)
+    return generate_driver(dims, variant, packed, state, samples, batch, sample_stride, n_total, n_given, t_begin, t_end,
+                           0.f, 0, logits_out, choices_out, logits_t0, context_win, sampling, 0, 1.0f, per_seq, nullptr,
+                           ctx_t0, ctx_len, stream);
+  return generate_driver(dims, variant, packed, state, samples, batch, sample_stride, n_total, n_given, t_begin, t_end,
+                         temperature, seed, logits_out, choices_out, logits_t0, context_win, sampling, top_k, top_p,
+                         nullptr, nullptr, ctx_t0, ctx_len, stream);
 }
 
 static int generate_driver(const mvn_dims *dims, int variant, const float *packed, float *state,
@@ -1210,7 +1249,7 @@ static int generate_driver(const mvn_dims *dims, int variant, const float *packe
                            int t_begin, int t_end, float temperature, uint64_t seed, float *logits_out,
                            int32_t *choices_out, int logits_t0, const float *context_tm, int sampling,
                            int top_k, float top_p, const mvn_seq_sampling *per_seq, const float *guidance,
-                           void *stream) {
+                           int ctx_t0, int ctx_len, void *stream) {
   if (variant == MVN_GEN_AUTO) {
     mvn::set_error("mvn_generate: resolve the variant with mvn_gen_variant first (the packed "
                    "weight layout depends on it)");
@@ -1262,8 +1301,12 @@ static int generate_driver(const mvn_dims *dims, int variant, const float *packe
   a.top_p = top_p;
   a.per_seq = per_seq;
   a.guidance = guidance;
-  a.ctx_tm = context_tm;
-  a.ctx_stride_b = (long long)n_total * dims->residual_channels;
+  // the kernels read column t of row b at ctx_tm[b ctx_stride_b + t C + c]: the base of a window stands ctx_t0 columns in
+  // front of it (formed as an integer: no pointer leaves its object; the whole context: the pointer itself)
+  a.ctx_tm = context_tm ? (const float *)((uintptr_t)context_tm -
+                                          (uintptr_t)ctx_t0 * (uintptr_t)dims->residual_channels * sizeof(float))
+                        : nullptr;
+  a.ctx_stride_b = (long long)ctx_len * dims->residual_channels;
   const mvn::GenVariant &v = *mvn::find_variant(variant);
   a.wctx = packed + v.weights_floats(dims);
   float *hand = state + (size_t)batch * a.state_per_seq;  // (behind the queues; the pipelined variants' only)

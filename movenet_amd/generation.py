@@ -165,6 +165,57 @@ def pack_params(dims: N.Dims, sd: Dict[str, torch.Tensor], n_layers: int):
     return p, keep
 
 
+class ContextSource:
+    """What a generator with a WINDOWED context reads its conditioning from: the frame-rate rows and / or
+    the label's vectors, a few hundred kilobytes where the two whole-context tensors take 8 C bytes per generated column
+    and row.  ``RingGenerator(context_source=...)`` forms the columns of each launch from it (``ops.context_window``).
+
+    ``proj``: (batch, C, F) fp32 on the device from ``ops.project_features``, frames ``hop`` samples apart, or None;
+    ``glob``: (batch, C) fp32, one vector per sequence, or None (not both None);
+    ``prompt``: with ``proj``, a callable P -> the (batch, C, P) channel-major local context of columns [0, P), as
+    ``ops.upsample_features(model, feats, P)`` forms it from ALL the frames -- ``prime()`` runs the prompt's forward
+    pass on it."""
+
+    def __init__(self, proj: Optional[torch.Tensor] = None, hop: int = 0, glob: Optional[torch.Tensor] = None,
+                 prompt=None):
+        if proj is None and glob is None:
+            raise ValueError("ContextSource: proj and glob are both None (an unconditioned generator takes no source)")
+        if proj is not None:
+            _require_gpu(proj, "ContextSource.proj")
+            if proj.dim() != 3 or proj.dtype != torch.float32:
+                raise ValueError(f"proj must be (batch, C, frames) float32, got {tuple(proj.shape)} {proj.dtype}")
+            if isinstance(hop, bool) or not isinstance(hop, int) or hop < 1:
+                raise ValueError(f"hop must be an integer >= 1, got {hop!r}")
+            if prompt is None:
+                raise ValueError("ContextSource: proj needs prompt, the callable that forms the prompt's columns")
+            proj = proj.detach().contiguous()
+        if glob is not None:
+            _require_gpu(glob, "ContextSource.glob")
+            if glob.dim() != 2 or (proj is not None and (glob.shape[0] != proj.shape[0] or glob.shape[1] != proj.shape[1])):
+                raise ValueError(f"glob must be (batch, C), got {tuple(glob.shape)}")
+            glob = glob.detach().to(torch.float32).contiguous()
+        self.proj, self.hop, self.glob, self.prompt = proj, int(hop), glob, prompt
+
+    @property
+    def batch(self) -> int:
+        return int((self.proj if self.proj is not None else self.glob).shape[0])
+
+    @property
+    def channels(self) -> int:
+        return int((self.proj if self.proj is not None else self.glob).shape[1])
+
+    def columns(self) -> Optional[int]:
+        """How many columns the frames cover (None: any number, a label alone)."""
+        return None if self.proj is None else int(self.proj.shape[2]) * self.hop
+
+    def rows(self, b0: int, b1: int) -> "ContextSource":
+        """The source of sequences [b0, b1) (``GroupedGenerator``'s groups)."""
+        prompt = self.prompt
+        return ContextSource(None if self.proj is None else self.proj[b0:b1], self.hop,
+                             None if self.glob is None else self.glob[b0:b1],
+                             None if prompt is None else (lambda P: prompt(P)[b0:b1]))
+
+
 class RingGenerator:
     """One batch of sequences being generated on one GPU.
 
@@ -179,8 +230,16 @@ class RingGenerator:
                  batch: int, n_total: int, device, variant: int = N.GEN_AUTO,
                  temperature: float = 0.0, seed: int = 0,
                  context: Optional[torch.Tensor] = None, sampling: str = "reference", top_k: int = 0,
-                 top_p: float = 1.0, rows=None, global_context: Optional[torch.Tensor] = None, guidance=None):
-        """``guidance`` (classifier-free guidance): None (off), one scale or a sequence of ``batch``
+                 top_p: float = 1.0, rows=None, global_context: Optional[torch.Tensor] = None, guidance=None,
+                 context_source: Optional[ContextSource] = None):
+        """``context_source``: a ``ContextSource`` in place of ``context`` and ``global_context`` (giving
+        it with either is a ValueError).  Nothing of n_total columns is built: ``context`` and ``context_tm`` stay None,
+        every launch forms its own columns [t_begin, t_end) in one buffer on the generator's stream
+        (``ops.context_window``; a label alone: filled once, re-based per launch) and goes through
+        ``mvn_generate_windowed``.  The stream's order protects the buffer: the next window is written behind the launch
+        that read the last.  Samples, logits and choices are those of the whole-context generator to the bit;
+        ``teacher_forced`` is the whole-context generator's.
+        ``guidance`` (classifier-free guidance): None (off), one scale or a sequence of ``batch``
         scales.  The generator then owns 2 * batch rows -- ``samples_all``: rows [0, batch) the unconditional ones,
         WITHOUT ``global_context`` (the zero vector in its place), rows [batch, 2 batch) the conditional ones with it;
         both with the same prompt, the same ``context`` and the caller's per-sequence settings (``rows`` included) --
@@ -202,6 +261,16 @@ class RingGenerator:
         (default b), so its draws do not depend on where in which batch it sits.  The attributes are then lists."""
         self._sampling = N.sampling_rule(sampling)
         self.sampling = sampling
+        if context_source is not None:
+            if context is not None or global_context is not None:
+                raise ValueError("context_source replaces context and global_context: give one or the other")
+            if context_source.batch != int(batch) or context_source.channels != int(residual_channels):
+                raise ValueError(f"context_source must hold ({int(batch)}, {int(residual_channels)}, ...) rows, got "
+                                 f"({context_source.batch}, {context_source.channels}, ...)")
+            cover = context_source.columns()
+            if cover is not None and (int(n_total) - 1) // context_source.hop + 1 > cover // context_source.hop:
+                raise ValueError(f"context_source holds {cover // context_source.hop} frames; {int(n_total)} samples at "
+                                 f"hop {context_source.hop} need {(int(n_total) - 1) // context_source.hop + 1}")
         self.guidance = None if guidance is None else N.guidance_scales(batch, guidance)  # ValueError before anything is allocated
         guided = self.guidance is not None
         seq_host = None
@@ -280,6 +349,15 @@ class RingGenerator:
                 N.check(self.lib.mvn_context_add_global(
                     self.context_tm.data_ptr(), self.global_context.data_ptr(), self.nrows, residual_channels,
                     self.n_total, int(fill), _stream_ptr(self.device)), "mvn_context_add_global")
+        # windowed context: the source, the label's vectors of ALL rows (guided: zeros in the unconditional ones, as
+        # above) and the one window buffer; _win_cols: the columns a label-only buffer was filled for
+        self._source, self._win, self._win_cols = context_source, None, 0
+        if context_source is not None:
+            _require_gpu(context_source.proj if context_source.proj is not None else context_source.glob, "context_source")
+            g = context_source.glob
+            if g is not None and guided:
+                g = torch.cat([torch.zeros_like(g), g], 0)
+            self.global_context = g
         self.temperature, self.seed = temperature, seed
         self._per_seq = None  # device copy of the mvn_seq_sampling array (per-sequence settings only)
         self._guidance = None  # device copy of the scales, one per pair (guided only)
@@ -366,6 +444,8 @@ class RingGenerator:
 
     def _run(self, t_begin: int, t_end: int, n_given: int, logits_out=None, choices_out=None,
              logits_t0: int = 0) -> None:
+        if self._source is not None:
+            return self._run_windowed(t_begin, t_end, n_given, logits_out, choices_out, logits_t0)
         if self._guidance is not None:
             with torch.cuda.device(self.device):
                 N.check(self.lib.mvn_generate_guided(
@@ -398,6 +478,38 @@ class RingGenerator:
                 logits_t0, None if self.context_tm is None else self.context_tm.data_ptr(),
                 self._sampling, self.top_k, self.top_p, _stream_ptr(self.device)), "mvn_generate_trunc")
 
+    def _window(self, t_begin: int, n: int):
+        """(buffer, ctx_t0, ctx_len) holding the context columns [t_begin, t_begin + n) of every row, written on the
+        current stream.  A label alone: every column is the same, so the buffer is filled once (again only for a wider
+        launch) and merely re-based."""
+        from .ops import context_window
+        src, C = self._source, self.dims.residual_channels
+        if src.proj is None:
+            if self._win is None or self._win_cols < n:
+                self._win = context_window(None, 1, 0, n, glob=self.global_context)
+                self._win_cols = n
+            return self._win, t_begin, self._win_cols
+        if self._win is None or self._win.numel() < self.nrows * n * C:
+            self._win = torch.empty(self.nrows * n * C, dtype=torch.float32, device=self.device)
+        context_window(src.proj, src.hop, t_begin, n, glob=self.global_context, proj_rows=self.batch, out=self._win)
+        return self._win, t_begin, n
+
+    def _run_windowed(self, t_begin: int, t_end: int, n_given: int, logits_out, choices_out, logits_t0: int) -> None:
+        if t_end <= t_begin:
+            return
+        guided, scalar = self._guidance is not None, self._per_seq is None
+        with torch.cuda.device(self.device):
+            win, ctx_t0, ctx_len = self._window(t_begin, t_end - t_begin)
+            N.check(self.lib.mvn_generate_windowed(
+                self.dims, self.variant, self.packed.data_ptr(), self.state.data_ptr(),
+                (self.samples_all if guided else self.samples).data_ptr(), self.batch, self.samples_all.stride(0),
+                self.n_total, n_given, t_begin, t_end, self.temperature if scalar else 0.0, self.seed if scalar else 0,
+                self.top_k if scalar else 0, self.top_p if scalar else 1.0,
+                None if scalar else self._per_seq.data_ptr(), self._guidance.data_ptr() if guided else None,
+                None if logits_out is None else logits_out.data_ptr(),
+                None if choices_out is None else choices_out.data_ptr(), logits_t0, win.data_ptr(), ctx_t0, ctx_len,
+                self._sampling, _stream_ptr(self.device)), "mvn_generate_windowed")
+
     def prime(self, prompt_idx: torch.Tensor) -> None:
         """Load a (B, P) prompt (P >= 1 class indices per sequence) and run the
         network over all but its last sample so that the queues are primed."""
@@ -418,6 +530,10 @@ class RingGenerator:
             from .ops import SequenceMode, run_forward
             idx = self.samples_all[:, :P].contiguous()
             ctx = None if self.context is None else self.context[:, :, :P]
+            if self._source is not None and self._source.proj is not None:  # (all the frames: the clip's own edge clamp)
+                ctx = self._source.prompt(P).detach().to(torch.float32)
+                if self._guidance is not None:
+                    ctx = torch.cat([ctx, ctx], 0)
             if self.global_context is not None:  # (the prompt's columns only: the steps read the time-major copy)
                 g = self.global_context[:, :, None]
                 ctx = g.expand(-1, -1, P) if ctx is None else ctx + g
@@ -458,6 +574,9 @@ class RingGenerator:
         """Feed a fully given (B, n_total) history; return (choices, logits) for
         times >= logits_t0 -- used by the parity tests.  Guided: both rows of a pair are fed the history; the
         conditional rows' (choices, logits) are returned and ``teacher_forced_all`` keeps those of all 2 * batch rows."""
+        if self._source is not None:
+            raise RuntimeError("movenet_amd: teacher_forced runs on a whole-context generator (context= / "
+                               "global_context=), not on one built with context_source")
         _require_gpu(indices, "indices")
         assert indices.shape == (self.batch, self.n_total)
         self.reset()
@@ -655,12 +774,16 @@ class GroupedGenerator:
                  state_dict, batch: int, n_total: int, device, group: int, temperature: float = 0.0,
                  seed: int = 0, context: Optional[torch.Tensor] = None, variant: int = N.GEN_PIPE,
                  sampling: str = "reference", top_k: int = 0, top_p: float = 1.0, rows=None,
-                 global_context: Optional[torch.Tensor] = None, guidance=None):
-        """``guidance``: as ``RingGenerator``'s; the groups are then groups of ``group`` PAIRS, each sequence keeps
+                 global_context: Optional[torch.Tensor] = None, guidance=None,
+                 context_source: Optional[ContextSource] = None):
+        """``context_source``: as ``RingGenerator``'s; each group takes its own sequences' rows of it.
+        ``guidance``: as ``RingGenerator``'s; the groups are then groups of ``group`` PAIRS, each sequence keeps
         its own settings and global row (as with per-sequence settings), and ``samples`` collects the groups'
         conditional rows after every ``prime`` / ``advance``."""
         N.sampling_rule(sampling)  # ValueError before anything is allocated
         self.sampling = sampling
+        if context_source is not None and (context is not None or global_context is not None):
+            raise ValueError("context_source replaces context and global_context: give one or the other")
         self.guidance = None if guidance is None else N.guidance_scales(batch, guidance)
         per_seq = None
         if self.guidance is not None or rows is not None or N.any_per_sequence(temperature, seed, top_k, top_p):
@@ -688,6 +811,7 @@ class GroupedGenerator:
                               variant=variant, context=None if context is None else context[b0:b1],
                               global_context=None if global_context is None else global_context[b0:b1],
                               sampling=sampling, guidance=None if self.guidance is None else self.guidance[b0:b1],
+                              context_source=None if context_source is None else context_source.rows(b0, b1),
                               **settings)
             if self.guidance is None:
                 g.samples = self.samples[b0:b1]  # a contiguous row block of the shared tensor

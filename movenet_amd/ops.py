@@ -803,6 +803,71 @@ def upsample_features(model, feats: torch.Tensor, T: int) -> torch.Tensor:
     return _UpsampleFeaturesFunction.apply(int(model.local_hop), int(T), feats, conv.weight, conv.bias)
 
 
+@torch.no_grad()
+def project_features(model, feats: torch.Tensor) -> torch.Tensor:
+    """``feats`` (B, local_channels, F) -> (B, C, F) fp32: ``model.local_conv`` applied at frame rate, the edge frames
+    repeated past the ends of ``feats`` (mvn_project_features) -- what ``upsample_features`` interpolates between,
+    kept, to the bit.  Not differentiable: the source of a windowed generator context."""
+    check_local_features(model, feats, int(feats.shape[0]) if torch.is_tensor(feats) and feats.dim() == 3 else -1, 1)
+    _require_gpu(feats, "local_features")
+    conv = model.local_conv
+    mel = feats.detach().to(torch.float32).contiguous()
+    w = conv.weight.detach().to(torch.float32).contiguous()  # (C, M, taps)
+    b = conv.bias.detach().to(torch.float32).contiguous()
+    B, M, F = mel.shape
+    C, taps = int(w.shape[0]), int(w.shape[2])
+    with torch.cuda.device(mel.device):
+        proj = torch.empty((B, C, F), dtype=torch.float32, device=mel.device)
+        N.check(N.lib().mvn_project_features(mel.data_ptr(), mel.stride(1), w.data_ptr(), b.data_ptr(), B, M, F, C,
+                                             taps, proj.data_ptr(), F, _stream_ptr(mel.device)), "mvn_project_features")
+    return proj
+
+
+@torch.no_grad()
+def context_window(proj, hop: int, t0: int, n: int, glob=None, proj_rows=None, out=None) -> torch.Tensor:
+    """Columns [t0, t0 + n) of the generators' time-major context, (rows, n, C) fp32 (mvn_context_window): ``proj``
+    (proj_rows, C, F) from ``project_features`` interpolated between frames ``hop`` samples apart, plus ``glob``
+    (rows, C), the label's vectors; either may be None (not both) -- ``proj`` None is the label-only window.  Row r
+    reads ``proj[r % proj_rows]`` (default: ``proj``'s rows), so the two rows of a guided pair share a projection;
+    rows = ``glob``'s, else ``out``'s, else ``proj``'s.  ``out``: a contiguous fp32 tensor of at least rows * n * C
+    elements to write into (its first rows * n * C are the result).  The bits are those of ``upsample_features`` ->
+    ``mvn_transpose_context`` -> ``mvn_context_add_global``.  Not differentiable."""
+    if proj is None and glob is None:
+        raise ValueError("context_window: proj and glob are both None")
+    src = proj if proj is not None else glob
+    _require_gpu(src, "context_window's source")
+    dev = src.device
+    if proj is not None:
+        if proj.dim() != 3 or proj.dtype != torch.float32:
+            raise ValueError(f"proj must be (rows, C, frames) float32, got {tuple(proj.shape)} {proj.dtype}")
+        if proj.stride(2) != 1 or proj.stride(0) != proj.shape[1] * proj.stride(1):
+            proj = proj.contiguous()
+    C = int(proj.shape[1]) if proj is not None else int(glob.shape[1])
+    if glob is not None:
+        if glob.dim() != 2 or int(glob.shape[1]) != C or glob.dtype != torch.float32 or glob.device != dev:
+            raise ValueError(f"glob must be (rows, {C}) float32 on {dev}, got {tuple(glob.shape)} {glob.dtype}")
+        glob = glob.contiguous()
+    if proj_rows is None:
+        proj_rows = int(proj.shape[0]) if proj is not None else 1
+    if proj is not None and not 1 <= int(proj_rows) <= int(proj.shape[0]):
+        raise ValueError(f"proj_rows must lie in [1, {int(proj.shape[0])}], got {proj_rows}")
+    rows = int(glob.shape[0]) if glob is not None else int(out.shape[0]) if out is not None and out.dim() == 3 \
+        else int(proj.shape[0])
+    t0, n = int(t0), int(n)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((rows, max(n, 0), C), dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or out.device != dev or not out.is_contiguous() or \
+                out.numel() < rows * max(n, 0) * C:
+            raise ValueError(f"out must be a contiguous float32 tensor of at least {rows * max(n, 0) * C} elements "
+                             f"on {dev}")
+        N.check(N.lib().mvn_context_window(
+            None if proj is None else proj.data_ptr(), 1 if proj is None else proj.stride(1), int(proj_rows),
+            1 if proj is None else int(proj.shape[2]), None if glob is None else glob.data_ptr(), rows, C, int(hop),
+            t0, n, out.data_ptr(), _stream_ptr(dev)), "mvn_context_window")
+    return out.view(-1)[:rows * n * C].view(rows, n, C)
+
+
 _BIAS_WITH_VIDEO = "global_path 'bias' runs models without a video context"
 
 

@@ -17,7 +17,9 @@ Two sources, exactly one per call:
 
 ``WaveNet.generate_stream`` hands the PCM out chunk by chunk; each sequence has one ``wave`` writer that takes
 ``writeframesraw`` per chunk and fixes the header on close, so a closed file is byte for byte what
-``callbacks.write_wav`` writes for the whole clip.  Batch k of a run draws on ``--seed`` + k.  One line per file goes to
+``callbacks.write_wav`` writes for the whole clip.  ``--context auto|whole|windowed`` (default auto) chooses how the
+conditioning reaches the generators: ``windowed`` forms each chunk's columns in front of its launch, in memory that does
+not grow with the clip; ``auto`` takes it where the whole context would exceed 1 GiB.  The audio is the same either way.  Batch k of a run draws on ``--seed`` + k.  One line per file goes to
 stdout: path, samples, seconds of audio, wall seconds, seconds to the first generated chunk.
 
 A checkpoint of a run with ``--preemphasis A`` records A: the model's PCM then comes out through the de-emphasis filter
@@ -119,7 +121,27 @@ def build_parser() -> argparse.ArgumentParser:
     a("--device", type=str, default="cuda")
     a("--preemphasis", type=float, default=None, help="default: the checkpoint's record (0 without one)")
     a("--force_preemphasis", type=int, default=0, help="1: take --preemphasis against the checkpoint's record")
+    a("--context", type=str, default="auto", choices=["auto", "whole", "windowed"],
+      help="the generators' conditioning: built whole before the first step, or one window per chunk; auto: windowed "
+           "where the whole context would take more than 1 GiB")
     return p
+
+
+WHOLE_CONTEXT_LIMIT = 1 << 30  # bytes: beyond it --context auto takes the windowed path
+
+
+def whole_context_bytes(rows: int, channels: int, n_total: int) -> int:
+    """What the two whole-context tensors of a conditioned generator take: (rows, C, n_total) channel-major and its
+    (rows, n_total, C) time-major copy, fp32."""
+    return 2 * int(rows) * int(channels) * int(n_total) * 4
+
+
+def context_mode(flag: str, conditioned: bool, rows: int, channels: int, n_total: int) -> str:
+    """``--context``: "whole" / "windowed" as given; "auto": windowed where a conditioned model's two whole-context
+    tensors would exceed 1 GiB, today's path otherwise (an unconditioned model builds no context: whole)."""
+    if flag != "auto":
+        return flag
+    return "windowed" if conditioned and whole_context_bytes(rows, channels, n_total) > WHOLE_CONTEXT_LIMIT else "whole"
 
 
 def load_model(args, fail):
@@ -239,8 +261,11 @@ def stream_to_files(model, prompt_idx, n_total: int, lengths: List[int], paths: 
         if feats is not None:
             model.generate_local_features = feats
         audio = model._one_hot_of(prompt_idx.contiguous(), torch.float32)
+        rows = int(prompt_idx.shape[0]) * (2 if getattr(args, "guidance", 1.0) != 1.0 else 1)
+        mode = context_mode(getattr(args, "context", "auto"), feats is not None or labels is not None, rows,
+                            model.residual_channels, n_total)
         for t0, pcm in model.generate_stream(audio, None, labels, n_samples=n_total, temperature=args.temperature,
-                                             chunk=args.chunk):
+                                             chunk=args.chunk, context=mode):
             if t0 > 0 and first_chunk is None:
                 first_chunk = time.perf_counter() - began
             for b, w in enumerate(writers):

@@ -667,13 +667,16 @@ class WaveNet(nn.Module):
         post = loglik.double() if log_prior is None else loglik.double() + log_prior.to(loglik.device).double()
         return loglik, torch.softmax(post, dim=1).to(torch.float32)
 
-    def _generate_setup(self, audio, video, global_features, n_samples, temperature, what: str = "generate"):
+    def _generate_setup(self, audio, video, global_features, n_samples, temperature, what: str = "generate",
+                        windowed: bool = False):
         """What ``generate()`` and ``generate_stream()`` share, up to the launch plan: the checks in their order, the
         settings taken from the attributes, the context, the prompt's class indices, the seed and the plan of
         ``auto_plan``.  Returns a namespace -- ``idx``, ``rf``, ``n_total``, and ``make`` = None where there is nothing to
         generate, else ``make(variant, group)`` (a new generator, not yet primed), ``variant`` / ``group`` (0: one
         launch) of the plan and ``fallback()``: the kernel a timed-out pipelined call is rerun on -- recorded in
-        ``last_generate_fallback`` and announced on stderr."""
+        ``last_generate_fallback`` and announced on stderr.  ``windowed`` (``generate_stream(context="windowed")``): the
+        generators take a ``ContextSource`` -- the frame-rate projection and / or the label's vectors -- in place of the
+        (B, C, n_total) context; the fallback's generator is built from the same source."""
         from types import SimpleNamespace
         from .ops import global_vector
         local_features, self._gen_local_features = self.generate_local_features, None  # (taken: one call uses it)
@@ -699,7 +702,17 @@ class WaveNet(nn.Module):
         # SURVEY.md Q7): the context column of time t conditions the step that consumes x_t
         rf = self.receptive_fields
         n_total = int(audio.shape[2]) if n_samples is None else int(n_samples)
-        context = self._context_of(audio, video, local_features, n_total=max(n_total, 1))
+        source = None
+        if windowed and (local_features is not None or gvec is not None):
+            from .generation import ContextSource
+            from .ops import project_features, upsample_features
+            glob = None if gvec is None else gvec.detach().to(torch.float32).contiguous()
+            if local_features is None:
+                source = ContextSource(glob=glob)
+            else:
+                source = ContextSource(project_features(self, local_features), int(self.local_hop), glob,
+                                       prompt=lambda P: upsample_features(self, local_features, P))
+        context = None if windowed else self._context_of(audio, video, local_features, n_total=max(n_total, 1))
         idx = self._indices_of(audio)
         plan = SimpleNamespace(idx=idx, rf=rf, n_total=n_total, make=None)
         if idx.shape[1] < rf or n_total <= rf:
@@ -707,7 +720,7 @@ class WaveNet(nn.Module):
         if seed is None:
             seed = int(torch.empty((), dtype=torch.int64).random_().item())
         state = self._decoder_state()
-        if context is None and gvec is None:
+        if context is None and gvec is None and source is None:
             state = {k: v for k, v in state.items() if ".context_conv_" not in k}
         elif context is not None and context.shape[2] < n_total:
             raise ValueError(f"the upsampled video covers {context.shape[2]} samples, "
@@ -718,6 +731,8 @@ class WaveNet(nn.Module):
                   sampling=self.generate_sampling, top_k=top_k, top_p=top_p)
         if guidance is not None:
             kw["guidance"] = guidance
+        if source is not None:
+            kw.update(context=None, global_context=None, context_source=source)
 
         def make(variant, group):
             if group:
@@ -730,7 +745,8 @@ class WaveNet(nn.Module):
 
         with torch.cuda.device(audio.device):
             if self._gen_variant == N.GEN_AUTO:
-                kind, group, variant = auto_plan(self._dims, idx.shape[0], context is not None or gvec is not None,
+                kind, group, variant = auto_plan(self._dims, idx.shape[0],
+                                                 context is not None or gvec is not None or source is not None,
                                                  guided=guidance is not None)
             else:
                 kind, group, variant = "single", 0, self._gen_variant
@@ -796,7 +812,7 @@ class WaveNet(nn.Module):
 
     @torch.no_grad()
     def generate_stream(self, audio, video=None, global_features=None, n_samples: Optional[int] = None,
-                        temperature=1.0, chunk: int = 4000):
+                        temperature=1.0, chunk: int = 4000, context: str = "whole"):
         """``generate()`` handing the audio out while it is being made: a generator of ``(t0, pcm)`` --
         ``pcm`` a (B, n) int16 numpy array on the host, the 16-bit PCM of columns [t0, t0 + n) of every sequence, to the
         bit what ``callbacks.write_wav`` stores for ``ops.mu_law_decode`` of ``generate()``'s classes under the same
@@ -808,11 +824,23 @@ class WaveNet(nn.Module):
         Same arguments, attributes, checks (in the same order, at the first ``next()``) and launch plan as
         ``generate()``; ``chunk < 1`` is a ValueError before any of them.  A hand-off timeout of a pipelined kernel
         before the first generated chunk has been handed out reruns the call on the fallback kernel, as ``generate()``
-        does; later it reaches the caller as ``PipeHandoffTimeout`` -- audio already delivered cannot be taken back."""
+        does; later it reaches the caller as ``PipeHandoffTimeout`` -- audio already delivered cannot be taken back.
+
+        ``context``: "whole" builds the (B, C, n_samples) conditioning and its time-major copy before the
+        first step, as ``generate()`` does; "windowed" keeps the frame-rate projection of the feature frames and / or
+        the label's vectors and forms each launch's columns in front of it, in one buffer of B x chunk x C floats -- the
+        same PCM byte for byte, in memory that does not grow with ``n_samples``.  Not with ``video`` (ValueError: clips
+        are capped at MAX_AUDIO_FRAMES, and the transposed-conv up-sampler has no windowed form); on a model with neither
+        labels nor local features it is the unconditioned path."""
         from .generation import plan_chunks
         from .ops import pcm16_chunk
         plan_chunks(0, 0, chunk)  # ValueError before anything is used up
-        plan = self._generate_setup(audio, video, global_features, n_samples, temperature, what="generate_stream")
+        if context not in ("whole", "windowed"):
+            raise ValueError(f"context must be 'whole' or 'windowed', got {context!r}")
+        if context == "windowed" and video is not None:
+            raise ValueError("context='windowed' cannot be combined with video: the video up-sampler has no windowed form")
+        plan = self._generate_setup(audio, video, global_features, n_samples, temperature, what="generate_stream",
+                                    windowed=context == "windowed")
         idx, rf, n_total = plan.idx, plan.rf, plan.n_total
         # (preemphasis > 0: one filter state per call, zero before column 0; the prompt's columns go through it first)
         a = self.preemphasis
