@@ -1216,6 +1216,53 @@ int mvn_feature_distance(const float *a, const float *b, int batch, int n_mels, 
                          const int32_t *count, double *lsd, double *l1, float *per_frame, float *scratch,
                          size_t scratch_floats, void *stream);
 
+/* ---- A frame-wise pitch tracker and the distance of two pitch tracks (csrc/pitch.hip; additive, ABI version
+ * unchanged) ----
+ * mvn_pitch_frames: the YIN estimator, one result per frame.  Exactly one of `index` and `wave` is non-NULL, both
+ * (batch, n_samples), DEVICE, read only:
+ *   index    int32 class indices; x is their mu-law decode by the formula of mvn_mu_law_decode (the float
+ *            mvn_logmel_frontend forms), 0 for an index outside [0, classes) (nothing is raised)
+ *   wave     fp32 samples, taken as they are; `classes` is ignored
+ *   x[t] = 0 for t outside [0, n_samples)
+ * F = n_samples / hop + 1 frames (integer division; mvn_logmel_frontend's frames).  With L = win + tau_max, frame j
+ * covers samples [s_j, s_j + L), s_j = j hop - L / 2 (integer division).  For tau = 1 .. tau_max:
+ *   d(tau) = sum_{n = 0}^{win - 1} (x[s_j + n] - x[s_j + n + tau])^2      the squared differences themselves, in fp32
+ *   c(0) = 1,  c(tau) = d(tau) tau / sum_{k = 1}^{tau} d(k),  1 where that sum is 0 (a constant frame)
+ *   tau_0   the smallest tau in [tau_min, tau_max] with c(tau) < threshold.  Found: the frame is VOICED and tau* is
+ *           where the walk `while tau + 1 <= tau_max and c(tau + 1) < c(tau)` from tau_0 stops.  None: the frame is
+ *           UNVOICED and tau* is the smallest tau of the range that attains the minimum of c.
+ *   refinement, only where 1 <= tau* - 1, tau* + 1 <= tau_max and c(tau*) <= both neighbours:
+ *           tau* + (c(tau* - 1) - c(tau* + 1)) / (2 (c(tau* - 1) - 2 c(tau*) + c(tau* + 1))), offset 0 where the
+ *           denominator is 0; tau* otherwise.  |refined - tau*| <= 1/2.
+ *   period  DEVICE (batch, F) fp32: the refined period in samples of a voiced frame, exactly 0.0f for an unvoiced one
+ *   aper    DEVICE (batch, F) fp32: c(tau*)
+ *   cmnd    DEVICE (batch, F, tau_max + 1) fp32: c(0 .. tau_max) of every frame; NULL: not formed in memory, not written
+ *   scratch DEVICE, mvn_pitch_scratch_floats(...) floats (the decoded signal), required with either entry
+ * Fixed order, no atomics: the same inputs give the same bits on every call; a row's results do not depend on the other
+ * rows of the launch; a non-finite sample affects only the frames whose span contains it.
+ * MVN_ERR_BAD_ARG before any launch, with nothing written: both or neither of index / wave; period, aper or scratch
+ * NULL; win outside [16, 4096]; tau_max outside [2, 1024]; tau_min outside [1, tau_max]; hop outside [1, 2^24];
+ * threshold not in (0, 1] (NaN included); classes < 2 with index; batch < 0 or above 65535; n_samples < 1 or above
+ * 2^30; batch * n_samples above 2^31 - 1; a scratch that is too small.  batch == 0 is MVN_OK and launches nothing. */
+size_t mvn_pitch_scratch_floats(int batch, int n_samples, int win, int tau_max);
+int mvn_pitch_frames(const int32_t *index, const float *wave, int batch, int n_samples, int classes, int win, int hop,
+                     int tau_min, int tau_max, float threshold, float *period, float *aper, float *cmnd,
+                     float *scratch, size_t scratch_floats, void *stream);
+
+/* mvn_pitch_distance: two period tracks (batch, frames) fp32, DEVICE, read only, as mvn_pitch_frames writes them (a
+ * frame is voiced where its period is above 0); first, count (batch) int32, DEVICE.  Over the frames
+ * [first[s], first[s] + count[s]) of sequence s, clamped to [0, frames):
+ *   both    frames voiced in a and in b;    vuv   frames voiced in exactly one of them
+ *   e_f     1200 log2(period_b / period_a) in double on the `both` frames
+ *   gross   the `both` frames with |period_a / period_b - 1| > gross_ratio
+ *   rmse_cents[s] = sqrt(sum e_f^2 / both), 0.0 where both == 0      DEVICE (batch) double
+ *   counts  DEVICE (batch, 4) int32: both, vuv, gross, the clamped count
+ * Sums in double in a fixed order, no atomics; no frame outside a span is read.
+ * MVN_ERR_BAD_ARG before any launch: a null pointer, batch or frames below 1, batch above 65535, gross_ratio not finite
+ * or <= 0. */
+int mvn_pitch_distance(const float *period_a, const float *period_b, int batch, int frames, const int32_t *first,
+                       const int32_t *count, double gross_ratio, double *rmse_cents, int32_t *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

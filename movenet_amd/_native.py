@@ -110,9 +110,10 @@ _HOST_POINTEES = {"mvn_dims": Dims, "mvn_params": Params, "mvn_param_grads": Par
                   "mvn_block_gated_grads": BlockGatedParams, "mvn_seq_sampling": SeqSampling,
                   "size_t": C.c_size_t}  # (mvn_adamw_step's skip_ranges)
 # The exceptions to that rule, by (function, parameter name): these three take a DEVICE array of mvn_seq_sampling
-# (only mvn_seq_sampling_check takes the host array).
+# (only mvn_seq_sampling_check takes the host array), and one call takes a double by value (no rule for the type: a
+# `double` anywhere else is still refused).
 _OVERRIDES = {("mvn_generate_seq", "per_seq"): C.c_void_p, ("mvn_generate_guided", "per_seq"): C.c_void_p,
-              ("mvn_generate_windowed", "per_seq"): C.c_void_p}
+              ("mvn_generate_windowed", "per_seq"): C.c_void_p, ("mvn_pitch_distance", "gross_ratio"): C.c_double}
 
 
 def _ctype(function: str, decl: str, position: Optional[int] = None):

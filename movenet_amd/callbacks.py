@@ -21,7 +21,9 @@ With ``--score_samples 1`` the module also scores each logged batch (``Dance2Mus
 conditioning it was generated with -- and ``source_bits_per_sample`` -- of the clip it was prompted from.  Off (the
 default), no row carries either key.  Under ``--use_mel 1`` the scores also hold ``mel_distance_db`` and ``mel_l1``, the
 log-mel distance of each generated row from the clip it was prompted from (``WaveNet.spectral_distance``), and every
-row carries them too; without ``--use_mel 1`` the rows are what they were.
+row carries them too; without ``--use_mel 1`` the rows are what they were.  ``--score_pitch 1`` (with both flags above)
+adds ``f0_rmse_cents``, ``vuv_error_rate`` and ``gross_pitch_error_rate`` of the same pairs (``WaveNet.pitch_distance``,
+one call per logged batch; null where a figure's denominator is 0); off, no row carries them.
 
 With ``--ema_decay`` the module generates ``outputs["generated_output"]`` on the averaged weights
 (``Dance2Music.averaged_weights``), on the train hook and on the validation hook, and the validation hook's
@@ -154,6 +156,9 @@ class LogSamplesCallback:
             source = scores["source_bits_per_sample"].cpu().tolist()
             # (--use_mel 1: the log-mel distance of each generated row from its source clip; absent otherwise)
             mel = {k: scores[k].cpu().tolist() for k in ("mel_distance_db", "mel_l1") if k in scores}
+            # (--score_pitch 1: the pitch figures of the same pairs; a figure whose denominator is 0 is written as null)
+            mel.update({k: [v if v == v else None for v in scores[k].cpu().tolist()]
+                        for k in ("f0_rmse_cents", "vuv_error_rate", "gross_pitch_error_rate") if k in scores})
             per_clip = max(len(sweep), 1)
             kept = [i for i in range(len(fps)) if prompt_ok is None or prompt_ok[i]]
             for k, r in enumerate(rows):  # (the scores cover every clip of the batch; the rows only the kept ones)

@@ -98,6 +98,10 @@ class TrainingConfig:
     # was prompted from -- into the clip's index.jsonl rows.  Not a reference field: a JSON written without it loads
     # with the default (off: no row changes).
     score_samples: bool = False
+    # ... and, with use_mel, track the pitch of each generated clip and of its source (WaveNet.pitch_distance, one call
+    # per logged batch): f0_rmse_cents, vuv_error_rate and gross_pitch_error_rate in the rows.  Needs
+    # score_samples and use_mel.  Not a reference field: a JSON written without it loads with the default (off).
+    score_pitch: bool = False
 
     # clips of a WAV folder at their own length (WavFolderLoader): "resample" stretches every clip onto
     # the batch width (the reference's rule); "native" resamples every clip to audio_rate, pads the batch to that width
@@ -181,6 +185,13 @@ def _flag(x) -> bool:
     return bool(int(x))
 
 
+def check_score_pitch(score_pitch, score_samples, use_mel) -> None:
+    """ValueError where --score_pitch stands without what it adds its figures to."""
+    if score_pitch and not (score_samples and use_mel):
+        raise ValueError("--score_pitch 1 needs --score_samples 1 --use_mel 1: the pitch figures go beside the log-mel "
+                         "distance of a copy-synthesis")
+
+
 def _opt_path(x):
     return None if x is None or x == "" else Path(x)
 
@@ -221,6 +232,7 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--ema_decay", type=float, default=0.0)
     a("--ema_warmup", type=_flag, default=True)
     a("--score_samples", type=_flag, default=False)
+    a("--score_pitch", type=_flag, default=False)
     a("--clip_length", type=str, default="resample", choices=["resample", "native", "window"])
     a("--window_gain", type=str, default="file", choices=["file", "window"])
     a("--audio_rate", type=int, default=16000)
@@ -291,6 +303,8 @@ def config_from_args(args) -> TrainingConfig:
         raise ValueError(f"--mel_window must lie in [0, 16], got {mel_window}")
     if mel_window and not kw["use_mel"]:
         raise ValueError(f"--mel_window {mel_window} needs --use_mel 1: there are no frames to take a window of")
+    score_pitch = bool(getattr(args, "score_pitch", False))  # (getattr: a namespace built before the flag existed)
+    check_score_pitch(score_pitch, kw["score_samples"], kw["use_mel"])
     return TrainingConfig(
         model_config=ModelConfig(
             input_channels=args.input_channels, residual_channels=args.residual_channels,
@@ -304,5 +318,6 @@ def config_from_args(args) -> TrainingConfig:
         resume_from=getattr(args, "resume_from", None),
         checkpoint_every_n_steps=int(getattr(args, "checkpoint_every_n_steps", 0) or 0),
         mel_window=mel_window,
+        score_pitch=score_pitch,
         **kw,
     )

@@ -14,8 +14,15 @@ its own frames -- ``generate()`` with the sampling flags of ``synthesize``; batc
 what compares the copy with the source: ``mel_distance_db``, ``mel_l1`` and ``frames`` (``WaveNet.spectral_distance``:
 the frames past the prompt and inside the file), and ``generated_bits_per_sample``, the copy's own likelihood.
 
+``--pitch 1`` (with ``--synthesize 1``; ``--pitch_fmin 60 --pitch_fmax 500 --pitch_threshold 0.15``) also tracks the
+pitch of the copy and of the source (``WaveNet.pitch_distance``) and adds ``f0_rmse_cents``,
+``voiced_frames``, ``vuv_error_rate`` (frames voiced in exactly one of the two, over the frames compared) and
+``gross_pitch_error_rate`` (voiced frames whose periods lie more than 20 % apart, over ``voiced_frames``), each null
+where its denominator is 0.
+
 The last line is the summary: ``{"files": n, "bits_per_sample": mean weighted by scored positions,
-"mel_distance_db": mean weighted by frames (null without --synthesize)}``.
+"mel_distance_db": mean weighted by frames (null without --synthesize)}`` and, with ``--pitch 1``, ``f0_rmse_cents``
+(the root of the mean squared error weighted by ``voiced_frames``) and the two rates pooled over their denominators.
 """
 from __future__ import annotations
 
@@ -47,6 +54,10 @@ def build_parser() -> argparse.ArgumentParser:
     a("--layer_size", type=int, default=None)
     a("--stack_size", type=int, default=None)
     a("--synthesize", type=int, default=0, help="1: also copy-synthesise each file and compare (mel checkpoint)")
+    a("--pitch", type=int, default=0, help="1: with --synthesize 1, also compare the pitch tracks of copy and source")
+    a("--pitch_fmin", type=float, default=60.0)
+    a("--pitch_fmax", type=float, default=500.0)
+    a("--pitch_threshold", type=float, default=0.15)
     a("--label", type=str, default=None, help="one of the checkpoint's class names")
     a("--out", type=str, default=None, help="also write the lines to this file")
     a("--batch", type=int, default=16)
@@ -70,8 +81,9 @@ def weighted_mean(values, weights):
     return sum(v * w for v, w in pairs) / total if total else None
 
 
-def evaluate_batch(model, rec, paths, device, args, labels, seed) -> list:
-    """The records of one batch of files (dicts, in the order of ``paths``)."""
+def evaluate_batch(model, rec, paths, device, args, labels, seed, pitch_counts=None) -> list:
+    """The records of one batch of files (dicts, in the order of ``paths``).  ``pitch_counts`` (a list, with
+    ``--pitch 1``) gains each record's (vuv errors, gross errors, frames compared) for the summary's pooled rates."""
     rate = SAMPLE_RATE if rec is None else int(rec["audio_rate"])
     if rec is None:
         idx, lengths = wav_indices(model, rate, paths, device, MAX_ROW_SAMPLES)
@@ -99,7 +111,28 @@ def evaluate_batch(model, rec, paths, device, args, labels, seed) -> list:
                                   dist.frames.cpu().tolist(), own):
             r.update(mel_distance_db=d, mel_l1=l1, frames=int(f),
                      generated_bits_per_sample=g if r["positions"] > 0 else None)
+        if getattr(args, "pitch", 0):
+            pd = model.pitch_distance(gen, idx, lengths=lengths, f_min=args.pitch_fmin, f_max=args.pitch_fmax,
+                                      threshold=args.pitch_threshold)
+            for r, e, both, vuv, gross, f in zip(records, *(t.cpu().tolist() for t in pd)):
+                r.update(f0_rmse_cents=e if both > 0 else None, voiced_frames=int(both),
+                         vuv_error_rate=vuv / f if f > 0 else None,
+                         gross_pitch_error_rate=gross / both if both > 0 else None)
+                if pitch_counts is not None:
+                    pitch_counts.append((int(vuv), int(gross), int(f)))
     return records
+
+
+def pitch_summary(records, pitch_counts) -> dict:
+    """The pooled pitch figures of the summary line: the root of the mean squared error in cents weighted by
+    ``voiced_frames``, and the two rates as summed numerators over summed denominators (None where those are 0).
+    ``pitch_counts``: each record's (vuv errors, gross errors, frames compared), as ``evaluate_batch`` collects them."""
+    both = sum(r["voiced_frames"] for r in records)
+    vuv, gross, frames = (sum(c[i] for c in pitch_counts) for i in range(3))
+    square = sum((r["f0_rmse_cents"] or 0.0) ** 2 * r["voiced_frames"] for r in records)
+    return {"f0_rmse_cents": (square / both) ** 0.5 if both else None,
+            "vuv_error_rate": vuv / frames if frames else None,
+            "gross_pitch_error_rate": gross / both if both else None}
 
 
 def main(argv=None) -> int:
@@ -107,6 +140,8 @@ def main(argv=None) -> int:
     args = parser.parse_args(argv)
     if args.batch < 1:
         parser.error("--batch must be at least 1")
+    if args.pitch and not args.synthesize:
+        parser.error("--pitch 1 needs --synthesize 1: the pitch of a copy is compared with its source's")
     model, rec, names = load_model(args, parser.error)
     if args.synthesize and rec is None:
         parser.error(f"--synthesize 1 needs a checkpoint trained with --use_mel 1: {args.checkpoint} has no "
@@ -124,7 +159,7 @@ def main(argv=None) -> int:
     device = torch.device(args.device)
     model = model.to(device).eval()
     sink = open(args.out, "w") if args.out else None
-    records = []
+    records, pitch_counts = [], []
 
     def emit(record):
         line = json.dumps(record)
@@ -137,7 +172,7 @@ def main(argv=None) -> int:
             labels = None if label is None else torch.full((len(paths),), label, dtype=torch.int64)
             try:
                 batch = evaluate_batch(model, rec, paths, device, args, labels,
-                                       None if args.seed is None else args.seed + k)
+                                       None if args.seed is None else args.seed + k, pitch_counts)
             except ValueError as e:
                 parser.error(str(e))
             for r in batch:
@@ -147,7 +182,8 @@ def main(argv=None) -> int:
               "bits_per_sample": weighted_mean([r["bits_per_sample"] or 0.0 for r in records],
                                                [r["positions"] for r in records]),
               "mel_distance_db": weighted_mean([r["mel_distance_db"] for r in records],
-                                               [r["frames"] for r in records]) if args.synthesize else None})
+                                               [r["frames"] for r in records]) if args.synthesize else None,
+              **(pitch_summary(records, pitch_counts) if args.pitch else {})})
     finally:
         if sink is not None:
             sink.close()

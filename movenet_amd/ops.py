@@ -705,6 +705,137 @@ def feature_distance(a: torch.Tensor, b: torch.Tensor, first=None, count=None, p
     return out
 
 
+# ---- pitch tracks and their distance (csrc/pitch.hip) ---------------------------------------------------
+PITCH_MIN_WIN, PITCH_MAX_WIN, PITCH_MIN_LAG, PITCH_MAX_LAG, PITCH_MAX_HOP = 16, 4096, 2, 1024, 1 << 24
+
+
+def pitch_lags(rate: float, f_min: float, f_max: float):
+    """``(tau_min, tau_max) = (floor(rate / f_max), ceil(rate / f_min))``: the lags, in samples at ``rate``, of the
+    periods of ``f_max`` .. ``f_min`` Hz.  A host function; ValueError unless 0 < f_min < f_max and rate > 0."""
+    import math
+    rate, f_min, f_max = float(rate), float(f_min), float(f_max)
+    if not (rate > 0.0 and 0.0 < f_min < f_max) or math.isinf(rate) or math.isinf(f_max):
+        raise ValueError(f"pitch_lags: need rate > 0 and 0 < f_min < f_max, got rate={rate}, f_min={f_min}, f_max={f_max}")
+    return int(math.floor(rate / f_max)), int(math.ceil(rate / f_min))
+
+
+def _whole(value, name: str) -> int:
+    if isinstance(value, bool) or not isinstance(value, int):
+        raise ValueError(f"{name} must be an integer, got {value!r}")
+    return value
+
+
+def check_pitch_settings(win, hop, tau_min, tau_max, threshold):
+    """The settings of ``pitch`` as ``(win, hop, tau_min, tau_max, threshold)``; ValueError for what mvn_pitch_frames
+    refuses of them."""
+    win, hop, tau_min, tau_max = (_whole(v, n) for v, n in ((win, "win"), (hop, "hop"), (tau_min, "tau_min"),
+                                                            (tau_max, "tau_max")))
+    if not PITCH_MIN_WIN <= win <= PITCH_MAX_WIN:
+        raise ValueError(f"win must lie in [{PITCH_MIN_WIN}, {PITCH_MAX_WIN}], got {win}")
+    if not PITCH_MIN_LAG <= tau_max <= PITCH_MAX_LAG:
+        raise ValueError(f"tau_max must lie in [{PITCH_MIN_LAG}, {PITCH_MAX_LAG}], got {tau_max}")
+    if not 1 <= tau_min <= tau_max:
+        raise ValueError(f"tau_min must lie in [1, tau_max = {tau_max}], got {tau_min}")
+    if not 1 <= hop <= PITCH_MAX_HOP:
+        raise ValueError(f"hop must lie in [1, 2^24], got {hop}")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not 0.0 < threshold <= 1.0:
+        raise ValueError(f"threshold must lie in (0, 1], got {threshold!r}")
+    return win, hop, tau_min, tau_max, float(threshold)
+
+
+def pitch(indices_or_wave: torch.Tensor, classes: Optional[int] = None, *, win: int, hop: int, tau_min: int,
+          tau_max: int, threshold: float = 0.15, cmnd: bool = False) -> dict:
+    """The YIN pitch track of (B, T) audio on the GPU, one estimate per ``logmel`` frame (mvn_pitch_frames): an integer
+    tensor is class indices, tracked on the waveform ``mu_law_decode(indices, classes)`` gives (an index outside
+    [0, classes) is a 0.0 sample); a float32 tensor is the waveform itself and ``classes`` is not used.
+
+    With L = win + tau_max, frame j covers samples [j hop - L // 2, j hop - L // 2 + L), zeros outside the row:
+    ``distance_frame_span(lengths, T, L, hop, skip)`` names the frames that lie inside a clip.  Over that frame
+    d(tau) = sum_{n < win} (x[n] - x[n + tau])^2, c(tau) = d(tau) tau / sum_{k <= tau} d(k) (1 where the sum is 0); the
+    frame is voiced where some c(tau) < ``threshold`` for tau in [tau_min, tau_max] -- the pick is the first such dip's
+    local minimum, refined by a parabola through its neighbours -- and unvoiced otherwise.
+
+    Returns ``{"period": (B, F) float32 -- samples, exactly 0 where unvoiced --, "aper": (B, F) float32 -- c at the
+    pick --}`` and with ``cmnd`` also ``"cmnd"``: (B, F, tau_max + 1) float32, c(0 .. tau_max) of every frame.  The same
+    bits on every call and in every batch.  ValueError before any launch for a shape, dtype or range mvn_pitch_frames
+    refuses; RuntimeError for a CPU tensor."""
+    x = indices_or_wave
+    _require_gpu(x, "indices_or_wave")
+    if x.dim() != 2 or x.is_complex() or x.dtype == torch.bool or (x.is_floating_point() and x.dtype != torch.float32):
+        raise ValueError(f"indices_or_wave must be (batch, samples) integer classes or a float32 waveform, got "
+                         f"{tuple(x.shape)} {x.dtype}")
+    win, hop, tau_min, tau_max, threshold = check_pitch_settings(win, hop, tau_min, tau_max, threshold)
+    is_wave = x.is_floating_point()
+    if not is_wave and (classes is None or _whole(classes, "classes") < 2):
+        raise ValueError(f"class indices need classes >= 2, got {classes!r}")
+    B, T = (int(v) for v in x.shape)
+    if B > 65535 or T < 1 or T > 1 << 30 or B * T > 2 ** 31 - 1:
+        raise ValueError(f"indices_or_wave {tuple(x.shape)}: need batch <= 65535, 1 <= samples <= 2^30 and at most "
+                         "2^31 - 1 samples in all")
+    dev = x.device
+    x = x.detach().contiguous() if is_wave else x.detach().to(torch.int32).contiguous()
+    F = logmel_frames(T, hop)
+    lib = N.lib()
+    with torch.cuda.device(dev):
+        out = {"period": torch.empty((B, F), dtype=torch.float32, device=dev),
+               "aper": torch.empty((B, F), dtype=torch.float32, device=dev)}
+        if cmnd:
+            out["cmnd"] = torch.empty((B, F, tau_max + 1), dtype=torch.float32, device=dev)
+        n = int(lib.mvn_pitch_scratch_floats(B, T, win, tau_max))
+        scratch = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+        N.check(lib.mvn_pitch_frames(None if is_wave else x.data_ptr(), x.data_ptr() if is_wave else None, B, T,
+                                     0 if is_wave else int(classes), win, hop, tau_min, tau_max, threshold,
+                                     out["period"].data_ptr(), out["aper"].data_ptr(),
+                                     out["cmnd"].data_ptr() if cmnd else None, scratch.data_ptr(),
+                                     n, _stream_ptr(dev)), "mvn_pitch_frames")
+    return out
+
+
+def pitch_distance(period_a: torch.Tensor, period_b: torch.Tensor, first=None, count=None,
+                   gross_ratio: float = 0.2) -> dict:
+    """F0 error of two (B, F) float32 period tracks on the GPU, e.g. two ``pitch`` outputs, over ONE span of frames per
+    sequence (mvn_pitch_distance; read only).  A frame is voiced where its period is above 0.  Over the frames
+    ``[first_b, first_b + count_b)``: ``voiced_frames`` are voiced in both tracks, ``vuv_errors`` in exactly one,
+    ``f0_rmse_cents`` is the root mean square of ``1200 log2(period_b / period_a)`` over the former (0.0 where there
+    are none), and ``gross_errors`` counts those with ``|period_a / period_b - 1| > gross_ratio``.
+
+    ``first`` / ``count``: as in ``feature_distance`` (its span checks too; default: every frame).  Returns
+    ``{"f0_rmse_cents": (B,) float64, "voiced_frames", "vuv_errors", "gross_errors", "frames": (B,) int32}``.  Sums in
+    double in a fixed order; no frame outside a span is read.  ValueError before any launch for a shape or dtype
+    mismatch, a span that leaves [0, F] or a ``gross_ratio`` that is not a finite number above 0; RuntimeError for a
+    CPU tensor."""
+    _require_gpu(period_a, "period_a")
+    _require_gpu(period_b, "period_b")
+    a, b = period_a, period_b
+    if a.dim() != 2 or a.dtype != torch.float32 or min(a.shape) < 1:
+        raise ValueError(f"period_a must be a (batch, frames) float32 tensor with no empty axis, got {tuple(a.shape)} "
+                         f"{a.dtype}")
+    if tuple(b.shape) != tuple(a.shape) or b.dtype != torch.float32 or b.device != a.device:
+        raise ValueError(f"period_b must be a {tuple(a.shape)} float32 tensor on {a.device}, got {tuple(b.shape)} "
+                         f"{b.dtype} on {b.device}")
+    if isinstance(gross_ratio, bool) or not isinstance(gross_ratio, (int, float)) or not 0.0 < gross_ratio < float("inf"):
+        raise ValueError(f"gross_ratio must be a finite number above 0, got {gross_ratio!r}")
+    B, F = (int(v) for v in a.shape)
+    if B > 65535:
+        raise ValueError(f"at most 65535 sequences, got {B}")
+    first = [0] * B if first is None else _span_values(first, "first", B)
+    count = [F - f for f in first] if count is None else _span_values(count, "count", B)
+    for s, (f0, n) in enumerate(zip(first, count)):
+        if f0 < 0 or n < 0 or f0 + n > F:
+            raise ValueError(f"the span of sequence {s}, first = {f0} and count = {n}, leaves the {F} frames")
+    dev = a.device
+    x, y = a.detach().contiguous(), b.detach().contiguous()
+    with torch.cuda.device(dev):
+        span = counts_to_device(first + count, dev)  # (one copy: first in front, count behind)
+        rmse = torch.empty(B, dtype=torch.float64, device=dev)
+        counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        N.check(N.lib().mvn_pitch_distance(x.data_ptr(), y.data_ptr(), B, F, span.data_ptr(), span[B:].data_ptr(),
+                                           float(gross_ratio), rmse.data_ptr(), counts.data_ptr(), _stream_ptr(dev)),
+                "mvn_pitch_distance")
+    return {"f0_rmse_cents": rmse, "voiced_frames": counts[:, 0], "vuv_errors": counts[:, 1],
+            "gross_errors": counts[:, 2], "frames": counts[:, 3]}
+
+
 class _UpsampleFeaturesFunction(torch.autograd.Function):
     """feats (B, M, F), W (C, M, taps) -- the conv's own weight -- and bias (C) -> context (B, C, T): taps = 1 through
     mvn_upsample_features, as ever; taps = 2 k + 1 > 1 through mvn_upsample_features_win."""

@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import checkpoint
-from .config import TrainingConfig, arg_parser, config_from_args
+from .config import TrainingConfig, arg_parser, check_score_pitch, config_from_args
 from .dataset import get_dataloader, training_contexts
 from .optim import FlatAdamW, order_like_backward
 from .generation import HostWords
@@ -55,6 +55,9 @@ class Dance2Music(nn.Module):
         self.mel_window = int(getattr(config, "mel_window", 0))  # (a config pickled before the field existed)
         if self.mel_window and not self.use_mel:
             raise ValueError(f"--mel_window {self.mel_window} needs --use_mel 1: there are no frames to take a window of")
+        # --score_pitch 1: the pitch figures of each logged batch beside its log-mel distance
+        self.score_pitch = bool(getattr(config, "score_pitch", False))  # (a config pickled before the field existed)
+        check_score_pitch(self.score_pitch, getattr(config, "score_samples", False), self.use_mel)
         if self.use_mel:
             from .ops import mel_filterbank
             rate = int(getattr(config, "audio_rate", 16000))
@@ -194,10 +197,19 @@ class Dance2Music(nn.Module):
             # of each generated row from the clip it was prompted from, over the frames past the prompt and inside the
             # clip's own length (WaveNet.spectral_distance)
             clip_len = [frames] * int(audio.shape[0]) if lengths is None else [min(int(v), frames) for v in lengths]
-            dist = self.model.spectral_distance(
-                generated[:, :, :frames].argmax(1), audio[:, :, :frames].argmax(1).repeat_interleave(n, dim=0),
-                lengths=[v for v in clip_len for _ in range(n)])
+            gen_idx = generated[:, :, :frames].argmax(1)
+            src_idx = audio[:, :, :frames].argmax(1).repeat_interleave(n, dim=0)
+            row_len = [v for v in clip_len for _ in range(n)]
+            dist = self.model.spectral_distance(gen_idx, src_idx, lengths=row_len)
             out["mel_distance_db"], out["mel_l1"] = dist.lsd_db, dist.l1
+            if self.score_pitch:
+                # --score_pitch 1: the pitch track of each generated row against its source's, over the same kind of
+                # span (WaveNet.pitch_distance); a rate is NaN where its denominator is 0
+                pd = self.model.pitch_distance(gen_idx, src_idx, lengths=row_len)
+                out["f0_rmse_cents"] = torch.where(pd.voiced_frames > 0, pd.f0_rmse_cents,
+                                                   torch.full_like(pd.f0_rmse_cents, float("nan")))
+                out["vuv_error_rate"] = pd.vuv_errors.double() / pd.frames.double()
+                out["gross_pitch_error_rate"] = pd.gross_errors.double() / pd.voiced_frames.double()
         return out
 
     def generate(self, audio, video, labels=None, local_features=None):

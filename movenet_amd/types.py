@@ -9,11 +9,22 @@ type checker, nothing at run time.  Layouts:
   time contiguous;
 * ``VideoTensor``: ``(batch, frames, height, width, channels)`` -- 64 x 64 grayscale frames.
 """
-from typing import Annotated
+from typing import Annotated, NamedTuple
 
 import torch
 
 AudioTensor = Annotated[torch.Tensor, ("batch", "channels", "frames")]
 VideoTensor = Annotated[torch.Tensor, ("batch", "frames", "height", "width", "channels")]
 
-__all__ = ["AudioTensor", "VideoTensor"]
+
+class PitchDistance(NamedTuple):
+    """What ``WaveNet.pitch_distance`` returns, one value per sequence (``movenet_amd.wavenet`` exports it beside
+    ``SpectralDistance``)."""
+    f0_rmse_cents: torch.Tensor  # (B,) float64 RMS of 1200 log2(F0_generated / F0_source) over voiced_frames; 0.0 with none
+    voiced_frames: torch.Tensor  # (B,) int32 frames voiced in both tracks
+    vuv_errors: torch.Tensor     # (B,) int32 frames voiced in exactly one of them
+    gross_errors: torch.Tensor   # (B,) int32 voiced_frames whose periods differ by more than gross_ratio
+    frames: torch.Tensor         # (B,) int32 frames that were compared
+
+
+__all__ = ["AudioTensor", "VideoTensor", "PitchDistance"]

@@ -26,7 +26,7 @@ import torch.nn as nn
 
 from . import _native as N
 from .modules import CausalConv1d, DenseConv, ResidualConvStack
-from .types import AudioTensor, VideoTensor  # noqa: F401  (re-exported like movenet/wavenet.py:15)
+from .types import AudioTensor, PitchDistance, VideoTensor  # noqa: F401  (re-exported like movenet/wavenet.py:15)
 from .generation import (GroupedGenerator, HostWords, PipeHandoffTimeout, RingGenerator, _require_gpu,
                          _stream_ptr, auto_plan, max_pipe_batch)
 
@@ -622,6 +622,67 @@ class WaveNet(nn.Module):
         mels = [ops.logmel(i, self.input_channels, int(s["n_fft"]), int(s["hop"]), fbank) for i in (g, x)]
         out = ops.feature_distance(mels[0], mels[1], first, count, per_frame=per_frame)
         return SpectralDistance(out["lsd_db"], out["l1"], out["frames"], out.get("per_frame"))
+
+    @torch.no_grad()
+    def pitch_distance(self, generated, source, lengths=None, skip: Optional[int] = None, *,
+                       win: Optional[int] = None, hop: Optional[int] = None, rate: Optional[float] = None,
+                       f_min: float = 60.0, f_max: float = 500.0, threshold: float = 0.15,
+                       gross_ratio: float = 0.2) -> "PitchDistance":
+        """How far the pitch of ``generated`` is from that of ``source``: both are tracked frame by frame with
+        ``ops.pitch`` (YIN) and the two tracks compared with ``ops.pitch_distance``, per sequence.  Both are (B, T)
+        integer class indices on the GPU, or (B, Q, T) one-hot -- the arguments of ``spectral_distance``, which this
+        call mirrors.
+
+        ``win`` (the samples a lag's difference is summed over), ``hop`` and ``rate`` come from the model's
+        ``local_conditioning`` record -- ``mel_fft``, ``local_hop`` and ``audio_rate`` -- so the pitch frames are the
+        log-mel frames; a keyword given here takes the record's place, and a model without the record needs all
+        three.  The lags searched are ``ops.pitch_lags(rate, f_min, f_max)``.  A frame covers ``win + tau_max``
+        samples and counts when they lie wholly past the first ``skip`` samples (default: ``receptive_fields``, the
+        prompt of a copy-synthesis) and inside the row's ``lengths[b]`` real samples:
+        ``ops.distance_frame_span`` with ``n_fft = win + tau_max``.
+
+        Under ``preemphasis`` A > 0 both sides are tracked on the DE-EMPHASISED audio (``ops.deemphasis_pcm16`` of the
+        classes, over 32768, as a float32 waveform), not on what the class indices encode as ``spectral_distance``
+        does: pre-emphasis attenuates the fundamental, which is what a pitch tracker needs.  At A = 0 the class
+        indices go to the tracker as they are.
+
+        Returns a ``PitchDistance``: ``f0_rmse_cents`` (B,) float64 -- the RMS of 1200 log2(F0 generated / F0 source)
+        over the frames voiced in both, 0.0 where there are none --, ``voiced_frames``, ``vuv_errors`` (voiced in
+        exactly one), ``gross_errors`` (periods more than ``gross_ratio`` apart) and ``frames``, (B,) int32 each."""
+        from . import ops
+        rec = getattr(self, "local_conditioning", None) or {}
+        given = {"win": win, "hop": hop, "rate": rate}
+        keys = {"win": "mel_fft", "hop": "local_hop", "rate": "audio_rate"}
+        s = {k: (v if v is not None else rec.get(keys[k])) for k, v in given.items()}
+        missing = [k for k in ("win", "hop", "rate") if s[k] is None]
+        if missing:
+            raise ValueError("pitch_distance: the model has no local_conditioning record (it was not trained with "
+                             "--use_mel 1); pass the keyword arguments win, hop and rate instead -- missing: "
+                             f"{', '.join(missing)}")
+        tau_min, tau_max = ops.pitch_lags(float(s["rate"]), f_min, f_max)
+        win, hop, tau_min, tau_max, threshold = ops.check_pitch_settings(int(s["win"]), int(s["hop"]), tau_min,
+                                                                         tau_max, threshold)
+        g, x = self._class_indices(generated, "generated"), self._class_indices(source, "source")
+        if g.shape != x.shape or g.device != x.device:
+            raise ValueError(f"generated {tuple(g.shape)} on {g.device} and source {tuple(x.shape)} on {x.device} "
+                             "must agree")
+        B, T = (int(v) for v in x.shape)
+        skip = self.receptive_fields if skip is None else skip
+        first, count = ops.distance_frame_span(lengths, T, win + tau_max, hop, skip, batch=B)
+        if len(first) != B:
+            raise ValueError(f"lengths names {len(first)} sequences, the batch holds {B}")
+        F = ops.logmel_frames(T, hop)
+        first = [min(f, F - n) for f, n in zip(first, count)]  # (an empty span past the last frame starts at F)
+        a = self.preemphasis
+        settings = dict(win=win, hop=hop, tau_min=tau_min, tau_max=tau_max, threshold=threshold)
+        if a > 0.0:
+            tracks = [ops.pitch(ops.deemphasis_pcm16(i, a, self.input_channels).float() / 32768, **settings)
+                      for i in (g, x)]
+        else:
+            tracks = [ops.pitch(i, self.input_channels, **settings) for i in (g, x)]
+        out = ops.pitch_distance(tracks[0]["period"], tracks[1]["period"], first, count, gross_ratio=gross_ratio)
+        return PitchDistance(out["f0_rmse_cents"], out["voiced_frames"], out["vuv_errors"], out["gross_errors"],
+                             out["frames"])
 
     @torch.no_grad()
     def classify(self, audio, video=None, log_prior=None, logits_budget_bytes: int = 1 << 30, lengths=None, *,
