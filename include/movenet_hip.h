@@ -1263,6 +1263,25 @@ int mvn_pitch_frames(const int32_t *index, const float *wave, int batch, int n_s
 int mvn_pitch_distance(const float *period_a, const float *period_b, int batch, int frames, const int32_t *first,
                        const int32_t *count, double gross_ratio, double *rmse_cents, int32_t *counts, void *stream);
 
+/* ---- A pitch track as two local-conditioning channels (csrc/pitch_features.hip; additive, ABI version unchanged;
+ * DESIGN 4.5j) ----
+ * mvn_pitch_features: period (batch, frames) fp32, DEVICE, read only, as mvn_pitch_frames writes it.  Frame j of a row
+ * is voiced, v[j], where period[j] > 0 (0, a negative value and NaN are unvoiced).  With
+ *   lf[j] = (float) log2((double)rate / ((double)period[j] * (double)f_ref))                         for a voiced j,
+ *   lf[j] = fmaf(a, lf[n], (1.0f - a) * lf[p]),  a = (float)(j - p) / (float)(n - p)                 for an unvoiced j
+ * between p, the nearest voiced frame below it, and n, the nearest above it; lf of the first voiced frame in front of
+ * it and of the last voiced frame behind it; 0 in a row without a voiced frame:
+ *   out[b * row_stride + j]               = lf[j] + shift[b]       (shift: DEVICE (batch) fp32, octaves; NULL: zeros)
+ *   out[b * row_stride + chan_stride + j] = v[j] ? 1.0f : 0.0f
+ * Strides in floats: row_stride = (M + 2) * ld, chan_stride = ld and out = base + M * ld write channels M and M + 1 of
+ * a (batch, M + 2, ld) tensor; nothing but those 2 * frames words of a sequence is written.  `out` must not overlap
+ * `period`.  One workgroup per row, fixed order, no atomics: the same bits on every call and at every batch position.
+ * MVN_ERR_BAD_ARG before any launch, with nothing written: period or out NULL; frames < 1 or above 2^30; batch < 0 or
+ * above 65535; rate or f_ref not finite and above 0 (NaN included); chan_stride < frames; with batch > 1, row_stride <
+ * chan_stride + frames.  batch == 0 is MVN_OK and launches nothing. */
+int mvn_pitch_features(const float *period, int batch, int frames, float rate, float f_ref, const float *shift,
+                       float *out, long long row_stride, long long chan_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,7 +81,8 @@ def _local_record(obj):
 def local_conditioning_of(path):
     """The ``"local_conditioning"`` record of a checkpoint trained with ``--use_mel 1`` -- ``local_channels``,
     ``local_hop`` and the mel settings its features were computed with (``mel_fft``, ``mel_fmin``, ``mel_fmax``,
-    ``audio_rate``), and ``local_window`` where the run had ``--mel_window K > 0`` -- or None for a file without one."""
+    ``audio_rate``), ``local_window`` where the run had ``--mel_window K > 0`` and ``f0`` where it had ``--mel_f0 1`` --
+    or None for a file without one."""
     return _local_record(_read(path))
 
 
@@ -89,6 +90,20 @@ def local_window_of(rec) -> int:
     """The ``local_window`` of a ``"local_conditioning"`` record: the key is written only by a run with ``--mel_window
     K > 0``, so a record without it (every file written before the flag existed, and every K = 0 run) reads as 0."""
     return int(rec.get("local_window", 0)) if isinstance(rec, dict) else 0
+
+
+def f0_record_of(rec):
+    """The ``"f0"`` entry of a ``"local_conditioning"`` record -- ``{"f_min", "f_max", "f_ref"}``, the pitch search range
+    in Hz and the frequency the log-F0 channel is 0 at -- or None: the key is written only by a run with ``--mel_f0 1``,
+    so a record without it (every file written before the flag existed, and every ``--mel_f0 0`` run) reads as off."""
+    f0 = rec.get("f0") if isinstance(rec, dict) else None
+    return {k: float(f0[k]) for k in ("f_min", "f_max", "f_ref")} if isinstance(f0, dict) else None
+
+
+def local_channels_of(rec) -> int:
+    """The input channels of the ``local_conv`` a ``"local_conditioning"`` record describes: its ``local_channels`` mel
+    bins, and the two F0 channels behind them where it has an ``"f0"`` entry."""
+    return int(rec["local_channels"]) + (2 if f0_record_of(rec) else 0)
 
 
 def _preemphasis_record(obj) -> float:
@@ -121,7 +136,7 @@ def load_into(model: torch.nn.Module, path, strict: bool = True, ema: bool = Fal
         model.preemphasis = _preemphasis_record(obj)
     rec = _local_record(obj)
     if rec is not None and hasattr(model, "set_local_conditioning"):
-        model.set_local_conditioning(int(rec["local_channels"]), int(rec["local_hop"]), local_window_of(rec))
+        model.set_local_conditioning(local_channels_of(rec), int(rec["local_hop"]), local_window_of(rec))
         model.local_conditioning = rec
     return model.load_state_dict(_state_dict_of(obj, path, ema), strict=strict)
 
@@ -260,11 +275,12 @@ def resolve_resume(value, output_path) -> Optional[Path]:
     return Path(value)
 
 
-def check_resumable(obj, path, run: dict, max_epochs: int, averaging: bool, local_window: int = 0) -> None:
+def check_resumable(obj, path, run: dict, max_epochs: int, averaging: bool, local_window: int = 0, f0=None) -> None:
     """ValueError -- naming the file and the field -- for a checkpoint that ``Trainer.fit(ckpt_path=path)`` must not
     continue: one without ``optimizer_states`` (a file of weights: ``--pretrained_model_path`` takes those), one whose
     ``hyper_parameters`` disagree with the run's (``run``, from ``hyper_parameters()``) in any of ``RESUME_FIELDS``, one
-    whose ``local_conditioning`` record holds another ``local_window`` than the run's ``--mel_window`` (absent: 0), one
+    whose ``local_conditioning`` record holds another ``local_window`` than the run's ``--mel_window`` (absent: 0) or
+    another ``f0`` entry than the run's (``f0``: ``{"f_min", "f_max", ...}`` under ``--mel_f0 1``, else None), one
     whose ``resume["epoch"]`` is not below ``max_epochs``, and -- with the weights' average on in the run -- one whose
     optimizer state holds no ``ema`` (``FlatAdamW.load_state_dict`` would start the average over without a word)."""
     if not isinstance(obj, dict) or not obj.get("optimizer_states"):
@@ -282,6 +298,14 @@ def check_resumable(obj, path, run: dict, max_epochs: int, averaging: bool, loca
     if saved_window != int(local_window):
         raise ValueError(f"{path}: local_conditioning['local_window'] is {saved_window}, but this run has "
                          f"{int(local_window)} (--mel_window): a resumed run continues the run that wrote the file")
+    saved_f0 = f0_record_of(_local_record(obj))
+    if (saved_f0 is None) != (f0 is None):
+        raise ValueError(f"{path}: local_conditioning['f0'] is {'absent' if saved_f0 is None else 'present'}, but this "
+                         f"run has --mel_f0 {int(f0 is not None)}: a resumed run continues the run that wrote the file")
+    for key, flag in (("f_min", "--f0_min"), ("f_max", "--f0_max")):
+        if saved_f0 is not None and saved_f0[key] != float(f0[key]):
+            raise ValueError(f"{path}: local_conditioning['f0'][{key!r}] is {saved_f0[key]}, but this run has "
+                             f"{float(f0[key])} ({flag}): a resumed run continues the run that wrote the file")
     if int(resume["epoch"]) >= int(max_epochs):
         raise ValueError(f"{path}: resume['epoch'] is {int(resume['epoch'])}, but this run ends after max_epochs = "
                          f"{int(max_epochs)}: nothing is left to train")

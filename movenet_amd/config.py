@@ -126,6 +126,12 @@ class TrainingConfig:
     mel_fmin: float = 0.0
     mel_fmax: Optional[float] = None
     mel_window: int = 0
+    # mel_f0: two more local channels behind the mel bins -- a continuous log2(F0 / sqrt(f0_min f0_max))
+    # of the YIN track searched between f0_min and f0_max Hz at the mel frames, and its voiced flag
+    # (ops.local_features).  Needs use_mel.
+    mel_f0: bool = False
+    f0_min: float = 60.0
+    f0_max: float = 500.0
 
     # pre-emphasis of the training audio (WavFolderLoader(preemphasis=a)): the front end quantises
     # (vn[k] - a vn[k-1]) / (1 + a) of the normalised waveform, the checkpoint records a, and everything that turns the
@@ -243,6 +249,9 @@ def arg_parser() -> argparse.ArgumentParser:
     a("--mel_fmin", type=float, default=0.0)
     a("--mel_fmax", type=float, default=None)
     a("--mel_window", type=int, default=0)
+    a("--mel_f0", type=_flag, default=False)
+    a("--f0_min", type=float, default=60.0)
+    a("--f0_max", type=float, default=500.0)
     a("--preemphasis", type=float, default=0.0)
     a("--n_epochs", type=int, default=10)
     a("--n_steps_per_epoch", type=int, default=None)
@@ -287,6 +296,16 @@ def _precision(x):
     return 32 if x == "32" else x
 
 
+def check_mel_f0(mel_f0, use_mel, f0_min, f0_max) -> None:
+    """ValueError where --mel_f0 stands without the frames it rides on, or with a search range that is none."""
+    if not mel_f0:
+        return
+    if not use_mel:
+        raise ValueError("--mel_f0 1 needs --use_mel 1: the F0 channels go behind the log-mel frames")
+    if not 0.0 < float(f0_min) < float(f0_max) < float("inf"):
+        raise ValueError(f"--f0_min and --f0_max must be finite with 0 < f0_min < f0_max, got {f0_min} and {f0_max}")
+
+
 def config_from_args(args) -> TrainingConfig:
     copied = (
         "batch_size val_batch_size checkpoint_every optimizer learning_rate momentum scheduler "
@@ -305,6 +324,9 @@ def config_from_args(args) -> TrainingConfig:
         raise ValueError(f"--mel_window {mel_window} needs --use_mel 1: there are no frames to take a window of")
     score_pitch = bool(getattr(args, "score_pitch", False))  # (getattr: a namespace built before the flag existed)
     check_score_pitch(score_pitch, kw["score_samples"], kw["use_mel"])
+    mel_f0 = bool(getattr(args, "mel_f0", False))  # (getattr: a namespace built before the flags existed)
+    f0_min, f0_max = float(getattr(args, "f0_min", 60.0)), float(getattr(args, "f0_max", 500.0))
+    check_mel_f0(mel_f0, kw["use_mel"], f0_min, f0_max)
     return TrainingConfig(
         model_config=ModelConfig(
             input_channels=args.input_channels, residual_channels=args.residual_channels,
@@ -319,5 +341,6 @@ def config_from_args(args) -> TrainingConfig:
         checkpoint_every_n_steps=int(getattr(args, "checkpoint_every_n_steps", 0) or 0),
         mel_window=mel_window,
         score_pitch=score_pitch,
+        mel_f0=mel_f0, f0_min=f0_min, f0_max=f0_max,
         **kw,
     )

@@ -20,7 +20,7 @@ LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libmovenet_hip.so")
 STAMP = os.path.join(LIB_DIR, "libmovenet_hip.stamp")
 
-SOURCES = ["common.hip", "generate.hip", "generate_pipe.hip", "generate_pipe_h16.hip", "generate_fold.hip", "sequence.hip", "video.hip", "trainer.hip", "audio.hip", "video_frontend.hip", "blocks.hip", "score.hip", "features.hip", "metrics.hip", "pitch.hip"]
+SOURCES = ["common.hip", "generate.hip", "generate_pipe.hip", "generate_pipe_h16.hip", "generate_fold.hip", "sequence.hip", "video.hip", "trainer.hip", "audio.hip", "video_frontend.hip", "blocks.hip", "score.hip", "features.hip", "metrics.hip", "pitch.hip", "pitch_features.hip"]
 HEADERS = ["common.h", "gen_common.h", "pipe_common.h", "gemm_family.h", "fused_bwd.h", "bwd_half64_body.inc", "fused_bwd_l.h", "bwd_layer64_body.inc", "fused_fwd.h", "fwd_layer64s_body.inc", "fused_fwd_bf3.h", "bf3.h", "fused_bf16.h", "global_cond.h", HEADER_PATH]
 FLAGS = [
     "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC",

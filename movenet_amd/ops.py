@@ -836,6 +836,148 @@ def pitch_distance(period_a: torch.Tensor, period_b: torch.Tensor, first=None, c
             "gross_errors": counts[:, 2], "frames": counts[:, 3]}
 
 
+def pitch_of_classes(indices: torch.Tensor, classes: int, preemphasis: float = 0.0, **settings) -> dict:
+    """``pitch`` of (B, T) class indices as the model's users hear them: at ``preemphasis`` A > 0 the tracker runs on
+    the DE-EMPHASISED audio (``deemphasis_pcm16`` of the classes, over 32768, as a float32 waveform) -- pre-emphasis
+    attenuates the fundamental, which is what a pitch tracker needs --, at A = 0 on the class indices as they are."""
+    if preemphasis > 0.0:
+        return pitch(deemphasis_pcm16(indices, preemphasis, classes).float() / 32768, **settings)
+    return pitch(indices, classes, **settings)
+
+
+# ---- a pitch track as local-conditioning channels (csrc/pitch_features.hip, DESIGN 4.5j) ------------------------------
+PITCH_FEATURES_CHUNK = 256  # the frames a workgroup of mvn_pitch_features scans at a time (kPfThreads)
+
+
+def f0_reference(f_min: float, f_max: float) -> float:
+    """``sqrt(f_min f_max)``: the frequency the log-F0 channel is 0 at, the middle of the search range in octaves.
+    ValueError unless 0 < f_min < f_max, both finite."""
+    import math
+    f_min, f_max = float(f_min), float(f_max)
+    if not 0.0 < f_min < f_max < math.inf:
+        raise ValueError(f"f0_min and f0_max must be finite with 0 < f0_min < f0_max, got {f_min} and {f_max}")
+    return math.sqrt(f_min * f_max)
+
+
+def _shift_values(shift, B: int):
+    """``shift`` of ``pitch_features`` as None (no shift) or a host list of B floats (octaves)."""
+    if shift is None:
+        return None
+    if N.any_per_sequence(shift):
+        values = shift.detach().cpu().tolist() if isinstance(shift, torch.Tensor) else \
+            shift.tolist() if hasattr(shift, "tolist") else list(shift)
+        if not isinstance(values, list) or any(isinstance(v, (list, tuple)) for v in values) or len(values) != B:
+            raise ValueError(f"shift must be a number or one number per sequence ({B}), got {shift!r}")
+    else:
+        values = [shift.item() if isinstance(shift, torch.Tensor) else shift] * B
+    for b, v in enumerate(values):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), float("-inf")):
+            raise ValueError(f"shift of sequence {b} is {v!r}, not a finite number")
+    return None if all(v == 0 for v in values) else [float(v) for v in values]
+
+
+def pitch_features(period: torch.Tensor, rate: float, f_ref: float, shift=None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A (B, F) float32 period track on the GPU, e.g. ``pitch(...)["period"]`` -- voiced where above 0 -- as two
+    frame-rate conditioning channels (mvn_pitch_features):
+
+        [:, -2]  the continuous log-F0 ``log2(rate / (period f_ref))`` (formed in double, rounded once), interpolated
+                 linearly between the nearest voiced frames across an unvoiced gap, held at the first / last voiced
+                 value in front of / behind them, 0 in a row without a voiced frame; plus ``shift`` octaves
+        [:, -1]  1.0 where the frame is voiced, else 0.0
+
+    ``shift``: None, a number, or one number per sequence (list, array or tensor).  ``out``: a float32 tensor
+    (B, >= 2, >= F) with contiguous frames whose LAST TWO channels' first F frames are written -- nothing else of it is
+    --, e.g. the (B, M + 2, F) features with the log-mel frames in front; default: a new (B, 2, F).  Returns ``out``.
+    The same bits on every call and at every batch position.  ValueError before any launch for a shape, dtype or value
+    mvn_pitch_features refuses; RuntimeError for a CPU tensor."""
+    import math
+    _require_gpu(period, "period")
+    if period.dim() != 2 or period.dtype != torch.float32:
+        raise ValueError(f"period must be a (batch, frames) float32 tensor, got {tuple(period.shape)} {period.dtype}")
+    B, F = (int(v) for v in period.shape)
+    if B > 65535 or F < 1 or F > 1 << 30:
+        raise ValueError(f"period {tuple(period.shape)}: need batch <= 65535 and 1 <= frames <= 2^30")
+    for name, v in (("rate", rate), ("f_ref", f_ref)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 < v < math.inf or \
+                not 0.0 < ctypes.c_float(v).value < math.inf:
+            raise ValueError(f"{name} must be a finite number above 0, got {v!r}")
+    values = _shift_values(shift, B)
+    dev = period.device
+    if out is not None:
+        _require_gpu(out, "out")
+        if out.dim() != 3 or out.dtype != torch.float32 or out.device != dev or out.shape[0] != B or \
+                out.shape[1] < 2 or out.shape[2] < F or (out.shape[2] > 1 and out.stride(2) != 1) or \
+                out.stride(1) < F or (B > 1 and out.stride(0) < out.stride(1) + F):
+            raise ValueError(f"out must be a ({B}, >= 2, >= {F}) float32 tensor on {dev} with contiguous frames and "
+                             f"rows that do not overlap, got {tuple(out.shape)} {out.dtype} strides {out.stride()}")
+    per = period.detach().contiguous()
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((B, 2, F), dtype=torch.float32, device=dev)
+        sh = None if values is None else torch.tensor(values, dtype=torch.float32).to(dev)
+        rows = out[:, out.shape[1] - 2:]
+        N.check(N.lib().mvn_pitch_features(per.data_ptr(), B, F, float(rate), float(f_ref),
+                                           None if sh is None else sh.data_ptr(), rows.data_ptr(),
+                                           out.stride(0) if B > 1 else out.stride(1) + F, out.stride(1),
+                                           _stream_ptr(dev)), "mvn_pitch_features")
+    return out
+
+
+_MEL_FBANKS: dict = {}
+
+
+def _record_fbank(device, record: dict) -> torch.Tensor:
+    """The float32 ``mel_filterbank`` of a ``"local_conditioning"`` record on ``device``, made once per settings."""
+    key = (str(device), int(record["local_channels"]), int(record["mel_fft"]), int(record["audio_rate"]),
+           float(record["mel_fmin"]), float(record["mel_fmax"]))
+    if key not in _MEL_FBANKS:
+        fbank = mel_filterbank(key[1], key[2], key[3], key[4], key[5])
+        _MEL_FBANKS[key] = torch.from_numpy(fbank).to(torch.float32).to(device)
+    return _MEL_FBANKS[key]
+
+
+@torch.no_grad()
+def local_features(indices: torch.Tensor, classes: int, record: dict, shift=None, lengths=None,
+                   preemphasis: float = 0.0) -> torch.Tensor:
+    """(B, T) class indices on the GPU -> the local features of a model trained under ``record``, a checkpoint's
+    ``"local_conditioning"`` record: the one place that turns audio into what ``forward`` / ``generate`` take as
+    ``local_features``, for the trainer, its sample logger, ``synthesize`` and ``evaluate`` alike.
+
+    Without an ``"f0"`` entry: ``logmel`` by the record's mel settings, (B, M, F) -- the same call, the same bits.
+    With one (``--mel_f0 1``): (B, M + 2, F) -- channels 0 .. M - 1 are those log-mel frames, bit for bit (one device
+    copy: mvn_logmel_frontend writes a tensor of its own width), and the last two are ``pitch_features`` of the YIN
+    track taken at ``win = mel_fft``, ``hop = local_hop`` and ``pitch_lags(audio_rate, f_min, f_max)``, so a pitch
+    frame is a log-mel frame.  ``preemphasis``: the model's (``pitch_of_classes``: the tracker hears the de-emphasised
+    audio).  ``shift``: octaves added to the log-F0 channel, a number or one per sequence; a non-zero shift on a record
+    without ``"f0"`` is a ValueError.  ``lengths`` (real samples per row, as in ``valid_columns``): a frame centred at
+    or past its row's end counts as unvoiced whatever the tracker finds in the padding; the log-mel channels do not
+    depend on it."""
+    from .checkpoint import f0_record_of
+    f0 = f0_record_of(record)
+    mel = logmel(indices, classes, int(record["mel_fft"]), int(record["local_hop"]),
+                 _record_fbank(indices.device, record))
+    B, M, F = (int(v) for v in mel.shape)
+    if f0 is None:
+        if _shift_values(shift, B) is not None:
+            raise ValueError("a pitch shift needs a checkpoint trained with --mel_f0 1: this local_conditioning record "
+                             "has no 'f0' entry, the model has no F0 channel to shift")
+        return mel
+    rate, hop = int(record["audio_rate"]), int(record["local_hop"])
+    tau_min, tau_max = pitch_lags(rate, float(f0["f_min"]), float(f0["f_max"]))
+    period = pitch_of_classes(indices.detach().to(torch.int32).contiguous(), int(classes), float(preemphasis),
+                              win=int(record["mel_fft"]), hop=hop, tau_min=tau_min, tau_max=tau_max)["period"]
+    if lengths is not None:
+        ends = counts_to_device([-(-v // hop) for v in _checked_lengths(lengths, int(indices.shape[1]))], mel.device)
+        if int(ends.shape[0]) != B:
+            raise ValueError(f"lengths names {int(ends.shape[0])} sequences, the batch holds {B}")
+        period = period.masked_fill(torch.arange(F, device=mel.device)[None, :] >= ends[:, None], 0.0)
+    with torch.cuda.device(mel.device):
+        feats = torch.empty((B, M + 2, F), dtype=torch.float32, device=mel.device)
+        feats[:, :M].copy_(mel)
+    return pitch_features(period, float(rate), float(f0["f_ref"]), shift, out=feats)
+
+
 class _UpsampleFeaturesFunction(torch.autograd.Function):
     """feats (B, M, F), W (C, M, taps) -- the conv's own weight -- and bias (C) -> context (B, C, T): taps = 1 through
     mvn_upsample_features, as ever; taps = 2 k + 1 > 1 through mvn_upsample_features_win."""

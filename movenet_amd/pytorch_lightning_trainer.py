@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import checkpoint
-from .config import TrainingConfig, arg_parser, check_score_pitch, config_from_args
+from .config import TrainingConfig, arg_parser, check_mel_f0, check_score_pitch, config_from_args
 from .dataset import get_dataloader, training_contexts
 from .optim import FlatAdamW, order_like_backward
 from .generation import HostWords
@@ -58,8 +58,11 @@ class Dance2Music(nn.Module):
         # --score_pitch 1: the pitch figures of each logged batch beside its log-mel distance
         self.score_pitch = bool(getattr(config, "score_pitch", False))  # (a config pickled before the field existed)
         check_score_pitch(self.score_pitch, getattr(config, "score_samples", False), self.use_mel)
+        # --mel_f0 1: a continuous log-F0 and its voiced flag behind the mel bins
+        self.mel_f0 = bool(getattr(config, "mel_f0", False))  # (a config pickled before the field existed)
+        check_mel_f0(self.mel_f0, self.use_mel, getattr(config, "f0_min", 60.0), getattr(config, "f0_max", 500.0))
         if self.use_mel:
-            from .ops import mel_filterbank
+            from .ops import f0_reference, mel_filterbank
             rate = int(getattr(config, "audio_rate", 16000))
             fmax = rate / 2.0 if config.mel_fmax is None else float(config.mel_fmax)
             # (the filterbank's own ValueErrors come first: nothing is built on bad settings)
@@ -72,6 +75,10 @@ class Dance2Music(nn.Module):
             if self.mel_window:  # (the record carries the key only then: a K = 0 run writes the file it wrote before)
                 self.local_conditioning["local_window"] = self.mel_window
                 local["local_window"] = self.mel_window
+            if self.mel_f0:  # (likewise: a --mel_f0 0 run writes the file it wrote before)
+                f_min, f_max = float(config.f0_min), float(config.f0_max)
+                self.local_conditioning["f0"] = {"f_min": f_min, "f_max": f_max, "f_ref": f0_reference(f_min, f_max)}
+                local["local_channels"] = checkpoint.local_channels_of(self.local_conditioning)  # (the mel bins + 2)
         self.model = WaveNet(**asdict(config.model_config), global_classes=len(self.global_classes), **local)
         if self.use_mel:  # (what checkpoint.load_into leaves there: WaveNet.spectral_distance reads the mel settings)
             self.model.local_conditioning = dict(self.local_conditioning)
@@ -108,18 +115,16 @@ class Dance2Music(nn.Module):
     def forward(self, audio, video, **kwargs):
         return self.model(audio, video, **kwargs)
 
-    def mel_features(self, audio):
-        """The (B, mel_bins, T // mel_hop + 1) log-mel frames of a one-hot batch on the device (``ops.logmel`` of its
-        class indices, no gradient), or None without ``--use_mel``."""
+    def mel_features(self, audio, lengths=None):
+        """The local features of a one-hot batch on the device, no gradient (``ops.local_features`` of its class
+        indices under the run's ``local_conditioning`` record): the (B, mel_bins, T // mel_hop + 1) log-mel frames,
+        with ``--mel_f0 1`` the two F0 channels behind them; None without ``--use_mel``.  ``lengths``: the batch's."""
         if not self.use_mel:
             return None
-        from .ops import logmel
-        c = self.config
-        with torch.no_grad():
-            if self.mel_fbank.device != audio.device:
-                self.mel_fbank = self.mel_fbank.to(audio.device)
-            return logmel(audio.argmax(1).to(torch.int32), c.model_config.input_channels, int(c.mel_fft), int(c.mel_hop),
-                          self.mel_fbank)
+        from .ops import local_features
+        extra = {} if lengths is None else {"lengths": lengths}
+        return local_features(audio.argmax(1).to(torch.int32), self.config.model_config.input_channels,
+                              self.local_conditioning, preemphasis=self.model.preemphasis, **extra)
 
     def _class_map(self):
         names = training_contexts(self.dataset_fp)
@@ -252,7 +257,7 @@ class Dance2Music(nn.Module):
             # host arithmetic on the loader's host list: no synchronisation
             self.log(f"{prefix}_valid_frac", sum(valid_columns(lengths, T, rf)) / max(len(lengths) * (T - rf), 1),
                      batch_size=self.config.batch_size)
-        feats = self.mel_features(audio)  # (None without --use_mel)
+        feats = self.mel_features(audio, lengths)  # (None without --use_mel)
         if feats is not None:
             extra["local_features"] = feats
         loss, acc, output = self(audio, video if self.config.use_video else None, return_loss=True, **extra)
@@ -437,7 +442,8 @@ class Trainer:
         c = model.config
         averaging = (float(getattr(c, "ema_decay", 0.0)) > 0) and c.optimizer in ("Adam", "AdamW")
         checkpoint.check_resumable(obj, ckpt_path, self._hyper(model, world), self.max_epochs, averaging,
-                                   local_window=int(getattr(model, "mel_window", 0)))
+                                   local_window=int(getattr(model, "mel_window", 0)),
+                                   f0=(getattr(model, "local_conditioning", None) or {}).get("f0"))
         names = checkpoint.global_classes_of(obj)
         if names != list(model.global_classes):
             raise ValueError(f"{ckpt_path}: global_classes is {names}, but this run's training set has "

@@ -26,10 +26,16 @@ A checkpoint of a run with ``--preemphasis A`` records A: the model's PCM then c
 and ``--from_wavs`` files go through the front end with that pre-emphasis, with no flag given.  ``--preemphasis``
 overrides it for a checkpoint that records none; a value other than the recorded one is an error unless
 ``--force_preemphasis 1``.
+
+``--pitch_shift SEMITONES`` (a checkpoint trained with ``--mel_f0 1``): the log-F0 channel of the ``--from_wavs``
+features is moved by SEMITONES / 12 octaves; the log-mel and voicing channels stay the source's.  How far the output's
+pitch follows depends on how much of the pitch the model learnt to read from that channel: the mel channels still carry
+the source's harmonics.  On a checkpoint without the F0 record a non-zero value is an error.
 """
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import sys
 import time
@@ -121,6 +127,8 @@ def build_parser() -> argparse.ArgumentParser:
     a("--device", type=str, default="cuda")
     a("--preemphasis", type=float, default=None, help="default: the checkpoint's record (0 without one)")
     a("--force_preemphasis", type=int, default=0, help="1: take --preemphasis against the checkpoint's record")
+    a("--pitch_shift", type=float, default=0.0,
+      help="semitones added to the F0 channel of a --mel_f0 1 checkpoint's features (--from_wavs)")
     a("--context", type=str, default="auto", choices=["auto", "whole", "windowed"],
       help="the generators' conditioning: built whole before the first step, or one window per chunk; auto: windowed "
            "where the whole context would take more than 1 GiB")
@@ -151,7 +159,7 @@ def load_model(args, fail):
     flags and the state dict's shapes disagree, or ``--preemphasis`` and the checkpoint's record do.  The model's
     ``preemphasis`` is the record's, or the flag's where it may stand.  Returns (model, local record or None, class names)."""
     from .checkpoint import (CLI_MODEL_DEFAULTS, _local_record, _preemphasis_record, _read, _state_dict_of,
-                             hyper_parameters_of, local_window_of)
+                             hyper_parameters_of, local_channels_of, local_window_of)
     from .wavenet import WaveNet
     obj = _read(args.checkpoint)
     # a model flag that was not given: the shape the checkpoint records (the trainer's hyper_parameters), else the default
@@ -174,7 +182,8 @@ def load_model(args, fail):
         sd = _state_dict_of(obj, args.checkpoint, bool(args.ema))
     except ValueError as e:
         fail(str(e))
-    local = {} if rec is None else {"local_channels": int(rec["local_channels"]), "local_hop": int(rec["local_hop"]),
+    # (the mel bins, and the two F0 channels of a --mel_f0 1 run behind them)
+    local = {} if rec is None else {"local_channels": local_channels_of(rec), "local_hop": int(rec["local_hop"]),
                                     "local_window": local_window_of(rec)}  # (a record without the key: 0)
     model = WaveNet(args.layer_size, args.stack_size, args.input_channels, args.residual_channels, args.skip_channels,
                     global_classes=len(names), **local)
@@ -226,17 +235,15 @@ def wav_indices(model, rate: int, paths: List[str], device, max_samples: Optiona
     return idx, lengths
 
 
-def wav_batch(model, rec: dict, paths: List[str], device, max_samples: Optional[int] = None):
+def wav_batch(model, rec: dict, paths: List[str], device, max_samples: Optional[int] = None, shift=None):
     """The front end of copy-synthesis for one batch of files: (idx, lengths, feats) -- ``wav_indices`` at
-    ``rec["audio_rate"]``, and ``feats``, the indices' log-mel frames by the checkpoint's mel settings."""
-    from .ops import logmel, mel_filterbank
-    rate, device = int(rec["audio_rate"]), torch.device(device)
-    idx, lengths = wav_indices(model, rate, paths, device, max_samples)
-    Q = model.input_channels
-    with torch.cuda.device(device):
-        fbank = mel_filterbank(int(rec["local_channels"]), int(rec["mel_fft"]), rate, float(rec["mel_fmin"]),
-                               float(rec["mel_fmax"]))
-        feats = logmel(idx, Q, int(rec["mel_fft"]), int(rec["local_hop"]), torch.from_numpy(fbank).to(torch.float32))
+    ``rec["audio_rate"]``, and ``feats``, the indices' local features by the checkpoint's record
+    (``ops.local_features``: log-mel frames, with an ``"f0"`` entry the two F0 channels behind them, the log-F0 one
+    moved by ``shift`` octaves)."""
+    from .ops import local_features
+    idx, lengths = wav_indices(model, int(rec["audio_rate"]), paths, torch.device(device), max_samples)
+    feats = local_features(idx, model.input_channels, rec, shift=shift, lengths=lengths,
+                           preemphasis=model.preemphasis)
     return idx, lengths, feats
 
 
@@ -303,6 +310,13 @@ def main(argv=None) -> int:
     if args.seconds is not None and rec is not None:
         parser.error(f"{args.checkpoint} was trained with --use_mel 1: it generates under log-mel frames, give "
                      "--from_wavs")
+    if args.pitch_shift != 0.0:
+        from .checkpoint import f0_record_of
+        if not math.isfinite(args.pitch_shift):
+            parser.error(f"--pitch_shift must be a finite number of semitones, got {args.pitch_shift}")
+        if f0_record_of(rec) is None:
+            parser.error(f"--pitch_shift {args.pitch_shift} needs a checkpoint trained with --mel_f0 1: "
+                         f"{args.checkpoint} has no 'f0' entry in its local_conditioning record")
     label = None
     if names:
         if args.label is None or args.label not in names:
@@ -328,7 +342,7 @@ def main(argv=None) -> int:
         rate = int(rec["audio_rate"])
         for k, b0 in enumerate(range(0, len(files), args.batch)):
             paths = files[b0:b0 + args.batch]
-            idx, lengths, feats = wav_batch(model, rec, paths, device)
+            idx, lengths, feats = wav_batch(model, rec, paths, device, shift=args.pitch_shift / 12.0)
             apply_settings(model, args, seed_of(k))
             stream_to_files(model, idx[:, :rf], int(idx.shape[1]), lengths,
                             [out_dir / os.path.basename(p) for p in paths], rate, args, labels_for(len(paths)), feats)

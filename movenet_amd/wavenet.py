@@ -675,11 +675,7 @@ class WaveNet(nn.Module):
         first = [min(f, F - n) for f, n in zip(first, count)]  # (an empty span past the last frame starts at F)
         a = self.preemphasis
         settings = dict(win=win, hop=hop, tau_min=tau_min, tau_max=tau_max, threshold=threshold)
-        if a > 0.0:
-            tracks = [ops.pitch(ops.deemphasis_pcm16(i, a, self.input_channels).float() / 32768, **settings)
-                      for i in (g, x)]
-        else:
-            tracks = [ops.pitch(i, self.input_channels, **settings) for i in (g, x)]
+        tracks = [ops.pitch_of_classes(i, self.input_channels, a, **settings) for i in (g, x)]
         out = ops.pitch_distance(tracks[0]["period"], tracks[1]["period"], first, count, gross_ratio=gross_ratio)
         return PitchDistance(out["f0_rmse_cents"], out["voiced_frames"], out["vuv_errors"], out["gross_errors"],
                              out["frames"])
