@@ -778,7 +778,9 @@ __global__ __launch_bounds__(512, 2) void gen_fold_kernel(KArgs<SEQ, GUIDED> a, 
       r.w = (((p[0].w + p[1].w) + (p[2].w + p[3].w)) + ((p[4].w + p[5].w) + (p[6].w + p[7].w))) + b2v.w;
       return r;
     };
-    head_loop<C, GRAN, MULTI, SEQ, 2, 0, GUIDED, true>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, part, await, logits,
+    // (SEND_AHEAD for one sequence per pipeline only: several sequences in turn pay the row's read, which stands behind
+    // the read of the turn's indices, in front of every wait -- DESIGN 4.1c)
+    head_loop<C, GRAN, MULTI, SEQ, 2, 0, GUIDED, true, !MULTI>(a, hand, NS, nb, b, G, fast_edge, E0, E1, iflag, hidx, part, await, logits,
                                                  take);
   }
 }

@@ -736,6 +736,12 @@ __device__ __forceinline__ void head_conv2_f32(const v2f (&w2)[4][16], const flo
 // WAVE_INBOX (FOLD): await is called by EVERY wave and stores the input where that wave alone reads it; no barrier
 // follows it -- logits() meets at its own first barrier, also when do_head is false -- and iflag[0], set to 1 by the
 // caller in front of a barrier, is cleared by a wave whose wait times out.
+// SEND_AHEAD (FOLD; C = 64, one channel per lane of wave 0): the E0 row of a send is the row of idx_prev, which was
+// idx_cur for the whole step before -- wave 0 reads its channel of E0[idx_cur] at the top of the step, in front of the
+// wait for the step's input, and the value moves to idx_prev's place where the index does (a launch's first send, in
+// front of the step loop, reads both rows; MULTI re-reads the indices from hidx at the top of a turn, and the row
+// behind them -- FOLD leaves its MULTI forms on send_h0).  One LDS read less between the pick and the put; the sum is
+// E1 + E0 as before.
 // iflag / hidx: LDS words ([0]: the hand-off's ok flag; MULTI: [GMAX][2] = {idx_cur, idx_prev} of each sequence
 // between its turns).
 // SEQ (mvn_generate_seq): the settings of a step are those of the sequence whose turn it is, a.per_seq[bq], loaded
@@ -749,11 +755,12 @@ struct HeadLgbRead {
   __device__ __forceinline__ f4 operator()(const float *lgb, int lane) const { return ((const f4 *)lgb)[lane]; }
 };
 template <int C, int GRAN, bool MULTI, bool SEQ, int NZ, int NZ_SENT = NZ, bool GUIDED = false, bool WAVE_INBOX = false,
-          class Await, class Logits, class Take = HeadLgbRead>
+          bool SEND_AHEAD = false, class Await, class Logits, class Take = HeadLgbRead>
 __device__ __forceinline__ void head_loop(const KArgs<SEQ, GUIDED> &a, u64 *hand, int NS, int nb, int b, int G, bool fast_edge,
                                           const float *E0, const float *E1, int *iflag, int *hidx, const float *lgb,
                                           Await await, Logits logits, Take take = Take()) {
   static_assert(GRAN == (1 + NZ) * C && NZ_SENT <= NZ, "residual stream + NZ zero lanes");
+  static_assert(!SEND_AHEAD || C == 64, "SEND_AHEAD: one channel per lane of wave 0");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, s = NS - 1;
   int bq;  // the sequence whose turn it is: b + g nb
   const u64 *inbox;
@@ -777,6 +784,15 @@ __device__ __forceinline__ void head_loop(const KArgs<SEQ, GUIDED> &a, u64 *hand
 #pragma unroll
       for (int z = 1; z <= NZ_SENT; ++z) put_granule(outbox + z * C + ch, ep, 0.f, fast_edge);
     }
+  };
+  // SEND_AHEAD, wave 0: this lane's channel of E0's row of idx_cur / of idx_prev (unused where the index is < 0)
+  [[maybe_unused]] float e0_cur = 0.f, e0_prev = 0.f;
+  auto send_ahead = [&](unsigned ep) {  // wave 0: send_h0 with idx_prev's row already in e0_prev
+    float v = E1[min(max(idx_cur, 0), a.Q - 1) * C + lane];
+    if (idx_prev >= 0) v += e0_prev;
+    put_granule(outbox + lane, ep, v, fast_edge);
+#pragma unroll
+    for (int z = 1; z <= NZ_SENT; ++z) put_granule(outbox + z * C + lane, ep, 0.f, fast_edge);
   };
   for (int g = 0; g < G; ++g) {
     bind(g);
@@ -824,6 +840,12 @@ __device__ __forceinline__ void head_loop(const KArgs<SEQ, GUIDED> &a, u64 *hand
       uni = philox_uniform(ss.seed, (uint32_t)u, ss.row);
       asm volatile("" : "+v"(uni));
     }
+    if constexpr (SEND_AHEAD) {
+      if (wave == 0) {  // (MULTI: idx_cur is this turn's, just re-read from hidx)
+        e0_cur = idx_cur >= 0 ? E0[min(idx_cur, a.Q - 1) * C + lane] : 0.f;
+        asm volatile("" : "+v"(e0_cur));  // in a register before the wait, not sunk to the send
+      }
+    }
     if constexpr (WAVE_INBOX) {
       if (wave == 0 && u < a.n_given) next_idx = samples[u];  // prompt / teacher forcing
       if (!await(inbox, epoch) && lane == 0) iflag[0] = 0;
@@ -857,11 +879,12 @@ __device__ __forceinline__ void head_loop(const KArgs<SEQ, GUIDED> &a, u64 *hand
           }
           idx_prev = idx_cur;  // (one pair of indices: both rows consume the same samples)
           idx_cur = next_idx;
-          if (ts + 1 < a.t_end) {
+          e0_prev = e0_cur;
+          if (ts + 1 < a.t_end) {  // (SEND_AHEAD: one row read ahead, two puts)
             bind(0);
-            send_h0(epoch + 1);
+            SEND_AHEAD ? send_ahead(epoch + 1) : send_h0(epoch + 1);
             bind(1);
-            send_h0(epoch + 1);
+            SEND_AHEAD ? send_ahead(epoch + 1) : send_h0(epoch + 1);
           }
           if (lane == 0) {
             if (do_head) {
@@ -892,7 +915,8 @@ __device__ __forceinline__ void head_loop(const KArgs<SEQ, GUIDED> &a, u64 *hand
       }
       idx_prev = idx_cur;
       idx_cur = next_idx;
-      if (ts + 1 < a.t_end) send_h0(epoch + 1);
+      e0_prev = e0_cur;
+      if (ts + 1 < a.t_end) SEND_AHEAD ? send_ahead(epoch + 1) : send_h0(epoch + 1);
       MVN_STAMP(b, s, ts + 1 - a.t_begin, 1);
       MVN_FINE(b, s, ts - a.t_begin, 5, 0);
       if (do_head && lane == 0) {
